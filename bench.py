@@ -29,7 +29,13 @@ CPU oracle in the reference's loop structure on the host cores).
 ``--gpus N`` without torchrun's environment starts the N ranks itself (one child process per GPU,
 before this process has touched the GPU); under ``python -m torch.distributed.run`` it is one of them.
 
-usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mc 30] [--batch 256] [--workload cfg2|cfg3]
+``--dump-outputs DIR`` writes what the timed path computed, as rank 0 holds it after its last timed step, to ``DIR/<name>.npy``
+(float32 / float64, a few kB): config 2 -- ``tile_mean`` / ``tile_std`` [batch, 2] of the last timed batch and ``slide_pred`` /
+``slide_unc`` / ``slide_count`` of the slide reduce over all timed batches, for the slides they reached; config 3 -- the slide
+table ``evaluate`` returned.  Every dumped value is finite.
+Inputs depend only on the arguments (seeded tiles and Philox counters), so two builds can be compared output for output.
+
+usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mc 30] [--batch 256] [--workload cfg2|cfg3] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -91,7 +97,23 @@ def parse_args(argv=None):
     ap.add_argument('--fixed-streams', action='store_true', help='exactly --streams batches in flight, no calibration')
     ap.add_argument('--streams', type=int, default=4,
                     help='batches in flight: independent contexts on HIP streams that own disjoint groups of XCDs (2 or 4)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write the timed path's outputs (rank 0, last timed step) as DIR/<name>.npy for output comparisons")
     return ap.parse_args(argv)
+
+
+def dump_outputs(d, arrays):
+    """Write ``{name: array}`` as ``d/<name>.npy``: floating arrays keep float32 / float64, integer counts become float64.
+    Every value must be finite: a NaN or Inf in what the path returned is an error, not an output."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if not np.isfinite(a).all():
+            raise SystemExit(f'[bench] --dump-outputs: {name} holds {int((~np.isfinite(a)).sum())} non-finite values')
+        np.save(os.path.join(d, f'{name}.npy'), np.ascontiguousarray(a))
 
 
 # ----------------------------------------------------------------------------- rank launcher
@@ -313,6 +335,8 @@ def run(args):
         tot = tuple(sum(a[j] for a in acc[1:]) + acc[0][j] if len(acc) > 1 else acc[0][j] for j in range(3))
         return pe.engines[0].slide_finish(tot)
 
+    last = {}                                     # outputs of the most recent timed region (tensors; read after it)
+
     def timed(mode, steps, pe=None, stain=False):
         pe = pe or pool_e
         acc = zero_acc()
@@ -331,6 +355,11 @@ def run(args):
         barrier()
         dt = max_over_ranks(time.perf_counter() - t0)
         assert int(cnt.sum()) == steps * B and bool(torch.isfinite(mp[cnt > 0]).all())
+        kl = (steps - 1) % len(pe)                 # the context that ran the last timed step (see step())
+        # the slide table holds the slides the timed steps reached: tiles 0 .. steps * B - 1 (the buffers have room for more
+        # slides, which stay empty and whose mean is NaN)
+        ns = -(-steps * B // TILES_PER_SLIDE)
+        last.update(tile_mean=mean[kl], tile_std=std[kl], slide_pred=mp[:ns], slide_unc=mu[:ns], slide_count=cnt[:ns])
         return dt
 
     # Untimed calibration of the number of batches in flight.  Each batch in flight owns 1/n of the chip's
@@ -352,6 +381,8 @@ def run(args):
     streams_used = len(pool_e)
     dt = timed(args.mode, K)
     value = world * K * B / dt
+    if args.dump_outputs and rank == 0:           # before any later leg reuses the result buffers
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in last.items()})
 
     out = {
         'metric': 'tiles/sec at MC-dropout=30, 299x299x3 (Xception, slide-level pred/sigma reduce)',
@@ -564,6 +595,8 @@ def run_cfg3(args, rank, world, dev, pool_e, pool, barrier, max_over_ranks):
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
     assert int(res.slide_count.sum()) == NT and np.isfinite(res.slide_pred).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'slide_pred': res.slide_pred, 'slide_unc': res.slide_unc, 'slide_count': res.slide_count})
     # what the f16 range monitor costs (evaluate's default: the eight taps on eight tiles every 200 batches, no host sync): the same run
     # without it
     barrier()

@@ -151,20 +151,27 @@ def _json_line(p):
     return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
 
 
-def test_eight_rank_rehearsal_on_one_gpu(tmp_path):
-    """What the driver runs at N = 8, end to end with real engines on the ONE GPU of this box (eight HIP contexts on device 0, a
-    gloo group: RCCL refuses several ranks on one device): ``bench.py --gpus 8`` on config 2 and on a ragged config 3 with the tile
-    table, and the CLI at world 8 with the shards spliced and the consumer run by rank 0 -- rank 0's results equal to the
-    single-rank run bit for bit (digests of the slide table and of tile_predictions_eval.csv, the printed metrics)."""
+# Ranks of the multi-rank rehearsal.  The suite keeps at most six processes on the GPU at a time, and this test's own process
+# holds it too: five ranks.  (Eight ranks -- BASELINE config 3's world -- run in tests/test_distributed.py
+# with stand-in engines, on the CPU.)
+REHEARSAL_WORLD = 5
+
+
+def test_multi_rank_rehearsal_on_one_gpu(tmp_path):
+    """What the driver runs at N > 1, end to end with real engines on the ONE GPU of this box (REHEARSAL_WORLD HIP contexts on
+    device 0, a gloo group: RCCL refuses several ranks on one device): ``bench.py --gpus N`` on config 2 and on a ragged config 3
+    with the tile table, and the CLI at world N with the shards spliced and the consumer run by rank 0 -- rank 0's results equal
+    to the single-rank run bit for bit (digests of the slide table and of tile_predictions_eval.csv, the printed metrics)."""
+    n = REHEARSAL_WORLD
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'LOCAL_WORLD_SIZE')}
     common = ['--local-device', '0', '--dist-backend', 'gloo', '--batch', '16', '--mc', '5', '--streams', '1', '--no-extras',
               '--no-cpu-baseline', '--no-profile']
     run = lambda *a: subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *a, *common], env=env, cwd=ROOT,     # noqa: E731
                                     capture_output=True, text=True, timeout=1500)
-    w8 = _json_line(run('--gpus', '8', '--steps', '2', '--warmup', '1'))
-    assert w8['n_gpus'] == 8 and w8['scaling'] == 'weak' and w8['value'] > 0
-    assert w8['collective'] == {'backend': 'gloo', 'ranks_seen': 8, 'rccl_ranks': 0}
-    assert w8['host_cores_of_rank0'] >= 1                       # pin_rank against this box's sysfs: a share, never empty
+    wn = _json_line(run('--gpus', str(n), '--steps', '2', '--warmup', '1'))
+    assert wn['n_gpus'] == n and wn['scaling'] == 'weak' and wn['value'] > 0
+    assert wn['collective'] == {'backend': 'gloo', 'ranks_seen': n, 'rccl_ranks': 0}
+    assert wn['host_cores_of_rank0'] >= 1                       # pin_rank against this box's sysfs: a share, never empty
     # the DRIVER's form of the same: torchrun starts the ranks (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from its environment)
     tr = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4', '--master-addr', '127.0.0.1',
                          '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--steps', '2', '--warmup', '1',
@@ -172,31 +179,32 @@ def test_eight_rank_rehearsal_on_one_gpu(tmp_path):
     w4 = _json_line(tr)
     assert w4['n_gpus'] == 4 and w4['steps'] == 2 and w4['collective']['ranks_seen'] == 4 and w4['value'] > 0
     cfg3 = ['--workload', 'cfg3', '--slides', '19', '--tiles-per-slide', '24', '--ragged']
-    s8, s1 = _json_line(run('--gpus', '8', *cfg3)), _json_line(run('--gpus', '1', *cfg3))
-    assert s8['n_gpus'] == 8 and s8['config']['ragged'] and sum(s8['config']['slides_per_rank']) == 19
-    assert s8['slide_table_sha256'] == s1['slide_table_sha256']
-    assert s8['tile_table']['sha256'] == s1['tile_table']['sha256'] and s8['tile_table']['rows'] == s1['tile_table']['rows'] > 0
-    # the CLI: eight ranks, shards spliced by rank 0, threshold.detect / apply on THE table
+    sn, s1 = _json_line(run('--gpus', str(n), *cfg3)), _json_line(run('--gpus', '1', *cfg3))
+    assert sn['n_gpus'] == n and sn['config']['ragged'] and sum(sn['config']['slides_per_rank']) == 19
+    assert sn['slide_table_sha256'] == s1['slide_table_sha256']
+    assert sn['tile_table']['sha256'] == s1['tile_table']['sha256'] and sn['tile_table']['rows'] == s1['tile_table']['rows'] > 0
+    # the CLI: n ranks, shards spliced by rank 0, threshold.detect / apply on THE table
     counts = '9,3,7,4,5,0,11,6,2,8,1,10'
     cli = [sys.executable, '-m', 'biscuit_amd', '--synthetic', counts, '--batch', '8', '--mc', '5', '--detect', '--local-device', '0',
            '--dist-backend', 'gloo']
     port = _free_port()
     procs = []
-    for r in range(8):
-        e = dict(env, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE='8', LOCAL_WORLD_SIZE='8', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
-        procs.append(subprocess.Popen(cli + ['--out', str(tmp_path / 'w8')], env=e, cwd=ROOT, text=True,
+    for r in range(n):
+        e = dict(env, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n), MASTER_ADDR='127.0.0.1',
+                 MASTER_PORT=str(port))
+        procs.append(subprocess.Popen(cli + ['--out', str(tmp_path / 'wn')], env=e, cwd=ROOT, text=True,
                                       stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, stderr=subprocess.PIPE if r == 0 else None))
     out0, err0 = procs[0].communicate(timeout=900)
-    assert [p.wait(timeout=300) for p in procs] == [0] * 8, err0[-3000:]
+    assert [p.wait(timeout=300) for p in procs] == [0] * n, err0[-3000:]
     one = subprocess.run(cli + ['--out', str(tmp_path / 'w1')], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     a = json.loads([ln for ln in out0.splitlines() if ln.startswith('{')][-1])
     b = _json_line(one)
-    assert a.pop('world') == 8 and b.pop('world') == 1
+    assert a.pop('world') == n and b.pop('world') == 1
     ta, tb = a.pop('tile_table'), b.pop('tile_table')
     assert a == b and a['tiles'] == 66 and 'auc' in a and 'detected' in a, (a, b)
     assert open(ta, 'rb').read() == open(tb, 'rb').read()
     name = 'slide_predictions_cohort_eval.csv'
-    assert open(tmp_path / 'w8' / name, 'rb').read() == open(tmp_path / 'w1' / name, 'rb').read()
+    assert open(tmp_path / 'wn' / name, 'rb').read() == open(tmp_path / 'w1' / name, 'rb').read()
 
 
 def test_config3_one_ranks_share_at_real_size():
