@@ -12,6 +12,7 @@ import argparse
 import glob
 import json
 import os
+import sys
 
 import numpy as np
 import pandas as pd
@@ -20,8 +21,9 @@ import pandas as pd
 def model_hp(params):
     """(ModelParams, norm_fit) from what ``keras_import.read_params`` found in a model's params.json: the dropout
     rate (and ``uq_n`` when stored) drive the MC statistics, so they come from the model, never from the defaults;
-    a stain normaliser other than the one this path implements (`reinhard_fast`, hp.py:19) is an error, and its fit
-    is used only when that normaliser is the model's."""
+    a stain normaliser other than the ones this path implements (`reinhard_fast`, hp.py:19, and `macenko`) is an error, and
+    its fit is used only when that normaliser is the model's and the fit is one of that method."""
+    from .stain import macenko_fit
     from .hp import ModelParams
     hp = ModelParams()
     if not params:
@@ -37,9 +39,16 @@ def model_hp(params):
                          f"normaliser the model was trained with")
     hp.normalizer = normalizer
     hp.validate()
-    if normalizer not in (None, 'reinhard_fast'):
+    if normalizer not in (None, 'reinhard_fast', 'macenko'):
         raise SystemExit(f"{params.get('path', 'params.json')}: the model was trained with normalizer={normalizer!r}; this "
-                         f"path implements 'reinhard_fast' (biscuit/hp.py:19) or none")
+                         f"path implements 'reinhard_fast' (biscuit/hp.py:19), 'macenko' or none")
+    if normalizer == 'macenko':
+        fit = params.get('norm_fit')
+        try:
+            macenko_fit(fit)
+        except ValueError as e:
+            raise SystemExit(f"{params.get('path', 'params.json')}: normalizer='macenko' but {e}") from None
+        return hp, fit
     fit = params.get('norm_fit') if normalizer == 'reinhard_fast' else None
     if normalizer == 'reinhard_fast' and not fit:
         raise SystemExit(f"{params.get('path', 'params.json')}: normalizer='reinhard_fast' but no norm_fit block")
@@ -89,7 +98,8 @@ def main(argv=None):
     ap.add_argument('--dtype', default='f16', choices=['f16', 'bf16', 'f32'])
     ap.add_argument('--streams', type=int, default=1,
                     help='batches in flight, each on its share of the chip (1 measured fastest through evaluate(): 25.8 k vs 25.4 k tiles/s)')
-    ap.add_argument('--params', help="Slideflow params.json: its norm_fit switches on the reinhard_fast stain normaliser (hp.py:19)")
+    ap.add_argument('--params', help="Slideflow params.json: its hp.normalizer ('reinhard_fast', the default, or 'macenko') and "
+                                     "norm_fit switch on that stain normaliser (hp.py:19)")
     ap.add_argument('--tile-uq', type=float, default=0.0, help='tile-level uncertainty threshold (0 = off)')
     ap.add_argument('--slide-uq', type=float, default=0.0, help='slide-level uncertainty threshold (0 = off)')
     ap.add_argument('--gpu-decode', type=int, default=0, metavar='CUS',
@@ -171,7 +181,7 @@ def main(argv=None):
         probe = _first_tiles(next((s for s in slides if s.n_tiles), None), 16)
         if probe is not None and not args.no_calibrate:
             from .engine import Engine
-            act_exp, peaks = Engine.calibrate(w, probe, hp=hp, device=local, norm_fit=norm_fit)
+            act_exp, peaks = Engine.calibrate(w, probe, hp=hp, device=local, norm_fit=norm_fit, normalizer=hp.normalizer)
             if rank == 0 and any(act_exp.values()):
                 big = {t: k for t, k in act_exp.items() if k}
                 print(f'f16: activation exponents from the first {len(probe)} tiles (peak {max(peaks.values()):.3g}): {big}', flush=True)
@@ -179,9 +189,9 @@ def main(argv=None):
                       act_exp=act_exp, reserve_cus=max(0, args.gpu_decode))
     if probe is not None:
         import torch
+        from .stain import normalise
         t = torch.from_numpy(probe[:8]).to(pool.engines[0].device)
-        if norm_fit is not None:
-            t = pool.engines[0].reinhard_fast(t, norm_fit['target_means'], norm_fit['target_stds'])
+        t = normalise(pool.engines[0], t, hp.normalizer, norm_fit)
         hr = pool.engines[0].f16_headroom(t)                      # the check behind the construction
         if any(hr['saturated'].values()):
             raise SystemExit(f'f16 storage saturates with these weights ({hr["saturated"]}): run with --dtype bf16 or f32')
@@ -191,7 +201,10 @@ def main(argv=None):
     # the tile table streams to disk while the GPU works (every rank its shard; rank 0 splices them after the gather): the frame
     # is not kept in memory, the consumer reads the file -- as biscuit does (experiment.py:688-699)
     res = evaluate(pool, slides, outcome=args.outcome, mc_n=args.mc, seed=args.seed, batch=args.batch,
-                   save_dir=args.out, rank=rank, world=world, norm_fit=norm_fit, keep_tiles=False)
+                   save_dir=args.out, rank=rank, world=world, norm_fit=norm_fit, keep_tiles=False, normalizer=hp.normalizer)
+    if res.stain_passthrough:
+        print(f'rank {rank}: the {hp.normalizer} normaliser passed {res.stain_passthrough} degenerate tile(s) through unchanged '
+              f'(too little tissue or one colour)', file=sys.stderr, flush=True)
     if rank == 0:
         from .predictions import load_tile_predictions
         sf, _ = res.slide_frame(0.5)

@@ -46,6 +46,8 @@ ABI = {
     'bq_set_option': (_i, [_vp, C.c_char_p, _i]),
     'bq_stain_reinhard_fast': (_i, [_vp, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp]),
     'bq_stain_lab_stats': (_i, [_vp, _vp, _i, _vp, _vp]),
+    'bq_stain_macenko': (_i, [_vp, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),
+    'bq_stain_macenko_stats': (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     'bq_backbone': (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
     'bq_backbone_u8': (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
     'bq_mc_head': (_i, [_vp, _vp, _i, _i64, _i, _i, _u64, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -908,6 +908,31 @@ int bq_stain_lab_stats(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_stats6
     return BQ_OK;
 }
 
+int bq_stain_macenko(bq_ctx* c, const uint8_t* d_tiles, int n, const float* he_ref6, const float* maxc_ref2,
+                     uint8_t* d_out, int* d_status, bq_stream_t stream) {
+    if (!c || !d_tiles || !d_out || !he_ref6 || !maxc_ref2 || n < 0)
+        return fail(c, BQ_ERR_ARG, "bq_stain_macenko: bad argument");
+    for (int i = 0; i < 6; ++i)
+        if (!std::isfinite(he_ref6[i])) return fail(c, BQ_ERR_ARG, "bq_stain_macenko: non-finite stain matrix");
+    for (int i = 0; i < 2; ++i)
+        if (!std::isfinite(maxc_ref2[i]) || !(maxc_ref2[i] > 0.f))
+            return fail(c, BQ_ERR_ARG, "bq_stain_macenko: target concentrations must be finite and > 0");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "stain_macenko", 400.0 * n * 299 * 299, 3.0 * n * kStaged);
+    if (launch_macenko(d_tiles, n, 299, he_ref6, maxc_ref2, d_out, nullptr, d_status, 1, s))
+        return fail(c, BQ_ERR_HIP, "macenko launch failed");
+    return BQ_OK;
+}
+
+int bq_stain_macenko_stats(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_stats8, int* d_status2, bq_stream_t stream) {
+    if (!c || !d_tiles || !d_stats8 || n < 0) return fail(c, BQ_ERR_ARG, "bq_stain_macenko_stats: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "stain_macenko_stats", 350.0 * n * 299 * 299, 1.0 * n * kStaged);
+    if (launch_macenko(d_tiles, n, 299, nullptr, nullptr, nullptr, d_stats8, d_status2, 2, s))
+        return fail(c, BQ_ERR_HIP, "macenko stats launch failed");
+    return BQ_OK;
+}
+
 int bq_png_unfilter(bq_ctx* c, const uint8_t* d_rows, int n, int px, uint8_t* d_out, bq_stream_t stream) {
     if (!c || !d_rows || !d_out || n < 0 || px <= 0) return fail(c, BQ_ERR_ARG, "bq_png_unfilter: bad argument");
     if (launch_png_unfilter(d_rows, n, px, d_out, (hipStream_t)stream)) return fail(c, BQ_ERR_HIP, "png unfilter launch failed");

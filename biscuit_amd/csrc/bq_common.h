@@ -119,6 +119,9 @@ int launch_stage_u8(const uint8_t* tiles, int n, int px, void* out, int dtype, d
 int launch_reinhard(const uint8_t* tiles, int n, int px, const float* d_lut, const float* consts27,
                     const float* tgt_mean, const float* tgt_std, uint8_t* dst, float* d_stats, hipStream_t s);
 int launch_stage_stats(const uint8_t* tiles, int n, int px, double* stats_scratch, hipStream_t s);
+// kernels_stain.hip: Macenko stain normalisation, one workgroup per tile (dst may be null: statistics only, or == tiles)
+int launch_macenko(const uint8_t* tiles, int n, int px, const float* he_ref6, const float* maxc_ref2, uint8_t* dst,
+                   float* d_stats8, int* d_status, int status_stride, hipStream_t s);
 int launch_front(int dtype, const uint8_t* tiles, const unsigned long long* stats, const void* ws16, const float* s_scale,
                  const float* s_bias, const void* wc16, const float* c_scale, const float* c_bias, void* out, int n, int num_cus,
                  hipStream_t s);

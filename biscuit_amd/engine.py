@@ -92,18 +92,19 @@ class Engine:
                        ('block13_out', (10, 10, 1024)), ('block14_sepconv1', (10, 10, 1536)), ('block14_sepconv2', (10, 10, 2048))])
 
     @staticmethod
-    def calibrate(weights, tiles_u8, hp=None, device=None, target_log2=12, norm_fit=None):
+    def calibrate(weights, tiles_u8, hp=None, device=None, target_log2=12, norm_fit=None, normalizer='reinhard_fast'):
         """Activation exponents for the f16 storage type, measured: up to 16 of ``tiles_u8`` (uint8 [n,299,299,3], host or
         device; the tiles the model will see -- stain-normalised here when ``norm_fit`` is given) go through the fp32 kernels
         of this library, which have no range limit, every stored tensor is tapped, and ``weights.choose_act_exponents`` turns
-        the peaks into powers of two.  Returns ``(act_exp, peaks)``; pass ``act_exp`` to ``Engine`` / ``EnginePool``.  A
+        the peaks into powers of two (``normalizer``: the method of ``norm_fit``, stain.METHODS).  Returns ``(act_exp, peaks)``; pass ``act_exp`` to ``Engine`` / ``EnginePool``.  A
         network whose activations fit IEEE half as they are gets all-zero exponents and the blob it always had."""
+        from . import stain
+        stain.check(normalizer, norm_fit)
         t = torch.as_tensor(np.asarray(tiles_u8[:16]) if not torch.is_tensor(tiles_u8) else tiles_u8[:16])
         eng = Engine(weights, hp=hp, dtype='f32', max_batch=max(1, int(t.shape[0])), max_mc=1, device=device)
         try:
             t = t.to(eng.device).contiguous()
-            if norm_fit is not None:
-                t = eng.reinhard_fast(t, norm_fit['target_means'], norm_fit['target_stds'])
+            t = stain.normalise(eng, t, normalizer, norm_fit)
             staged = eng.stage(t)
             peaks = {}
             for tensor, taps in tensor_taps().items():
@@ -236,6 +237,33 @@ class Engine:
         self._check(self._lib.bq_stain_lab_stats(self._ctx, _ptr(tiles_u8), tiles_u8.shape[0], _ptr(out),
                                                  self._stream()))
         return out
+
+    def macenko(self, tiles_u8, he_ref, maxc_ref, out=None, status=None):
+        """`macenko` stain normalisation (``bq_stain_macenko``; DESIGN.md "Macenko"): uint8 NHWC [n,299,299,3] -> uint8 NHWC.
+        he_ref: the fit's stain matrix (3x2, columns H and E), maxc_ref: its two concentrations (> 0).  `out` may be the input
+        tensor (in place).  `status` (int32 [n] on the device, optional) receives each tile's status: 0 normalised, 1 / 2 / 3
+        degenerate (too little tissue / singular stain matrix / non-finite or non-positive concentration) and passed through."""
+        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous()
+        he = np.asarray(he_ref, dtype=np.float32).reshape(6)
+        mc = np.asarray(maxc_ref, dtype=np.float32).reshape(2)
+        if out is None:
+            out = torch.empty_like(tiles_u8)
+        if status is not None:
+            assert status.dtype == torch.int32 and status.is_cuda and status.is_contiguous() and status.numel() >= tiles_u8.shape[0]
+        self._check(self._lib.bq_stain_macenko(self._ctx, _ptr(tiles_u8), tiles_u8.shape[0], (C.c_float * 6)(*he.tolist()),
+                                               (C.c_float * 2)(*mc.tolist()), _ptr(out), _ptr(status), self._stream()))
+        return out
+
+    def macenko_stats(self, tiles_u8):
+        """Each tile's own Macenko fit (what ``stain.Macenko.fit`` stores): ``(stats, status)`` device tensors, stats float32
+        [n,8] = HE row-major (3x2, H first), maxC (2) -- NaN where a degenerate tile stopped before them --, status int32 [n,2] =
+        status (as ``macenko``), number of tissue pixels."""
+        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous()
+        n = tiles_u8.shape[0]
+        stats = torch.empty((n, 8), dtype=torch.float32, device=self.device)
+        st = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+        self._check(self._lib.bq_stain_macenko_stats(self._ctx, _ptr(tiles_u8), n, _ptr(stats), _ptr(st), self._stream()))
+        return stats, st
 
     def stage_f32(self, tiles_f32):
         assert tiles_f32.dtype == torch.float32 and tiles_f32.is_cuda and tiles_f32.is_contiguous()
@@ -597,14 +625,12 @@ class UncertaintyInterface:
     tiles, returns ``(mean, uncertainty)`` each ``[B, 2]``; ``uncertainty[0][0]`` is what
     ``results.py:258`` compares with the tile-UQ threshold."""
 
-    def __init__(self, engine: Engine, uq_n=30, seed=0, norm_fit=None):
+    def __init__(self, engine: Engine, uq_n=30, seed=0, norm_fit=None, normalizer='reinhard_fast'):
+        from .stain import make_normalizer
         self.engine, self.uq_n, self.seed = engine, int(uq_n), int(seed)
         self._calls = 0
         # results.py:251-252: `if interface.wsi_normalizer: norm_image = ...rgb_to_rgb(image)`
-        self.wsi_normalizer = None
-        if norm_fit is not None:
-            from .stain import ReinhardFast
-            self.wsi_normalizer = ReinhardFast(engine, norm_fit['target_means'], norm_fit['target_stds'])
+        self.wsi_normalizer = make_normalizer(engine, normalizer, norm_fit)
 
     def enable_graph(self):
         """Capture the one-tile call (stage -> ~60 backbone launches -> MC head) in a HIP graph: the heatmap loop of

@@ -41,8 +41,11 @@ def tile_grid(region, tile_px=299, stride_div=1):
 
 
 class Heatmap:
-    def __init__(self, engine, tiles, grid, grid_shape=None, mc_n=30, seed=0, batch=256, norm_fit=None):
-        """tiles: uint8 [T,299,299,3] (host or device); grid: int [T,2] (gx, gy) cell of each tile."""
+    def __init__(self, engine, tiles, grid, grid_shape=None, mc_n=30, seed=0, batch=256, norm_fit=None, normalizer='reinhard_fast'):
+        """tiles: uint8 [T,299,299,3] (host or device); grid: int [T,2] (gx, gy) cell of each tile.  ``norm_fit`` / ``normalizer``:
+        the model's stain normaliser (stain.METHODS; ``norm_fit=None``: none)."""
+        from . import stain
+        stain.check(normalizer, norm_fit)
         grid = np.asarray(grid, dtype=np.int64).reshape(-1, 2)
         n = int(tiles.shape[0])
         if grid.shape[0] != n:
@@ -61,8 +64,7 @@ class Heatmap:
         t = tiles if torch.is_tensor(tiles) else torch.from_numpy(np.ascontiguousarray(tiles))
         for s in range(0, n, batch):
             cur = t[s:s + batch].to(dev).contiguous()
-            if norm_fit is not None:
-                cur = engine.reinhard_fast(cur, norm_fit['target_means'], norm_fit['target_stds'])
+            cur = stain.normalise(engine, cur, normalizer, norm_fit)
             mean, std = engine.mc_infer(cur, mc_n, seed, tile_idx0=s)
             g = grid[s:s + batch]
             self.logits[g[:, 1], g[:, 0]] = mean.cpu().numpy()

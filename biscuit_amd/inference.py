@@ -202,6 +202,7 @@ class EvalResult:
     table_rows: int = 0                      # rows this rank wrote
     f16_headroom: float = float('inf')       # minimum over the run's range checks of 65504 / max |stored activation| (f16 engines)
     f16_checks: int = 0
+    stain_passthrough: int = 0               # tiles of this rank the Macenko normaliser passed through unchanged (degenerate)
 
     def slide_frame(self, pred_thresh=0.5, level='slide'):
         """Group table in ``process_group_predictions`` form from the device-reduced means."""
@@ -560,7 +561,7 @@ class _TableStream:
 
 def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=None, batch=256,
              mc_mode='head', tile_uq=None, save_dir=None, keep_tiles=True, rank=0, world=1, norm_fit=None,
-             table_name=EVAL_NAME, table_writer='native', headroom_every=200, headroom_min=2.0):
+             table_name=EVAL_NAME, table_writer='native', headroom_every=200, headroom_min=2.0, normalizer='reinhard_fast'):
     """Run MC-dropout inference over ``slides`` and return tile- and slide-level results.
 
     Every rank passes the SAME slide list; rank r processes ``partition_slides(...)[r]``.
@@ -581,7 +582,12 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
 
     ``norm_fit`` (``{'target_means': [3], 'target_stds': [3]}``, the block of that name in the model's
     params.json) switches on the `reinhard_fast` stain normaliser of hp.py:19 in front of the staging
-    kernel, where results.py:251-252 applies it."""
+    kernel, where results.py:251-252 applies it.  ``normalizer='macenko'`` takes a Macenko fit instead
+    (``{'stain_matrix_target': 3x2, 'target_concentrations': 2}``); the tiles it passes through unchanged (degenerate: no
+    tissue, one colour) are counted on the device and read once at the end: ``EvalResult.stain_passthrough`` (this rank's)."""
+    from . import stain
+    stain.check(normalizer, norm_fit)
+    macenko = norm_fit is not None and normalizer == 'macenko'
     hp = engine.hp
     mc_n = int(mc_n or hp.uq_n)
     seed = int(hp.seed if seed is None else seed)
@@ -595,6 +601,7 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
     pool = engine if hasattr(engine, 'engines') else None
     engines = pool.engines[:len(pool)] if pool else [engine]      # len(pool) = batches in flight
     acc = [None] * len(engines)
+    passthrough = [None] * len(engines)          # per stream: int64 device count of the tiles the Macenko kernel passed through
     n_batches = 0
     rows_mean, rows_std, rows_slide, rows_true, rows_loc = [], [], [], [], []
     with_loc = any(s.n_tiles for s in slides) and all(s.loc is not None for s in slides if s.n_tiles)    # (every rank decides the same: one header)
@@ -672,8 +679,13 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
                 headroom_look(block=True)            # the previous check: one interval old, long finished -- a run fails one interval late at most
 
             def work(eng, cur=cur, gdev=gdev):
-                if norm_fit is not None:
-                    cur = eng.reinhard_fast(cur, norm_fit['target_means'], norm_fit['target_stds'])
+                if macenko:
+                    st = torch.empty(cur.shape[0], dtype=torch.int32, device=dev)
+                    cur = stain.normalise(eng, cur, normalizer, norm_fit, status=st)
+                    cnt = st.ne(0).sum()
+                    passthrough[k] = cnt if passthrough[k] is None else passthrough[k].add_(cnt)
+                elif norm_fit is not None:
+                    cur = stain.normalise(eng, cur, normalizer, norm_fit)
                 if gdev is None:
                     eng.mc_infer(cur, mc_n, seed, tile_idx0=int(cg[0]), mc_mode=mc_mode, out=(mean, std))
                 else:
@@ -892,5 +904,7 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
                     if slides[si].n_tiles:
                         order.append([si, slides[si].name, slides[si].n_tiles, 0, 0])
                 write_shard_index(table_path, rank, world, outcome, 'loc_x' in tile_df.columns, order)
+    n_pass = sum(int(c) for c in passthrough if c is not None)
     return EvalResult(tile_df, [s.name for s in slides], g_pred, g_unc, g_cnt,
-                      np.array([s.y_true for s in slides]), list(mine), table_path, table_rows, hr_state['min'], hr_state['checks'])
+                      np.array([s.y_true for s in slides]), list(mine), table_path, table_rows, hr_state['min'], hr_state['checks'],
+                      n_pass)

@@ -6,6 +6,7 @@
  * table.  Each entry point below names the reference call site it replaces:
  *
  *   bq_stain_reinhard_fast  interface.wsi_normalizer.rgb_to_rgb(image)   results.py:251-252, hp.py:19
+ *   bq_stain_macenko        the same, for a model trained with normalizer='macenko'
  *   bq_stage        tf.image.per_image_standardization(norm_image)      results.py:256
  *   bq_backbone     keras Xception(include_top=False, pooling='avg')     biscuit/hp.py:4,20,22
  *   bq_mc_head      the UQ loop behind UncertaintyInterface(model)(batch) -> (mean, std)
@@ -106,6 +107,20 @@ int bq_stain_reinhard_fast(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, cons
 /* Per-tile CIE-LAB channel statistics [n][6] = mean L, a, b, population std L, a, b: what the
  * normaliser's fit() stores as norm_fit for a target image. */
 int bq_stain_lab_stats(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, float* d_stats6, bq_stream_t stream);
+
+/* K0, optional front half: the `macenko` stain normaliser (Slideflow's normalizer='macenko'; DESIGN.md "Macenko" states the
+ * spec, the precision contract and the degenerate-tile rule).  uint8 NHWC [n,px,px,3] -> uint8 NHWC; d_out may equal d_tiles.
+ * he_ref6 (row-major 3x2, columns H and E) and maxc_ref2 are HOST pointers to the model's fit (norm_fit
+ * stain_matrix_target / target_concentrations; finite, concentrations > 0).  d_status (nullable): int [n], 0 = normalised,
+ * 1 = fewer than 2 tissue pixels, 2 = |det(HE^T HE)| < 1e-12, 3 = a maxC <= 0 or a non-finite intermediate; a tile whose
+ * status is not 0 passes through unchanged.  Unpinned, like reinhard_fast. */
+int bq_stain_macenko(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, const float* he_ref6, const float* maxc_ref2,
+                     uint8_t* d_out_nhwc, int* d_status, bq_stream_t stream);
+
+/* The Macenko fit of each tile: d_stats8 float [n][8] = HE row-major 3x2, maxC 2 (NaN where a degenerate tile stopped before
+ * computing them); d_status2 (nullable) int [n][2] = status (as above), number of tissue pixels. */
+int bq_stain_macenko_stats(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, float* d_stats8, int* d_status2,
+                           bq_stream_t stream);
 
 /* Input side, PNG tiles: the reversal of the PNG scanline filters on the device.  d_rows:
  * [n][px][1 + 3*px] bytes -- per row the filter-type byte and the filtered RGB bytes, i.e. the inflated IDAT stream of an
