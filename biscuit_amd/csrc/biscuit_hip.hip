@@ -176,10 +176,9 @@ struct ProfScope {
 int pick_shape(const bq_ctx* c, int prod, int nfp) {
     if (prod == PROD_IM2COL) return SHAPE_A;
     if (is16(c->cfg.dtype)) {
-        static const bool s2_small = !bq_exp_env("BQ_S2_BIG");
         // 64-row tiles halve the staging tile: four workgroups per CU instead of two for N = 256
         // (128->256 @37x37: 0.161 -> 0.111 ms); for N = 128 they measured slower (0.194 -> 0.234 ms)
-        if (prod == PROD_S2 && s2_small && nfp == 8) return SHAPE_K;
+        if (prod == PROD_S2 && nfp == 8) return SHAPE_K;
         switch (nfp) {
             case 4: return SHAPE_B;
             case 8: return SHAPE_C;
@@ -244,15 +243,11 @@ int run_conv(bq_ctx* c, const ConvArgs& a, hipStream_t s) {
              L.cout, a.H, a.W);
     // Two-kernel form (depthwise kernel + 128x128-tile GEMM): always for the wide exit-flow layers
     // (K >= 1024: the fused kernel can only hold 32-64 rows of A in LDS there and re-streams the
-    // 3-6 MB weight matrix per 32-64 rows); BQ_SPLIT=1 forces it for every separable conv.
-    static const bool split_env = bq_exp_env("BQ_SPLIT") != nullptr;
-    static const bool no_split = bq_exp_env("BQ_NO_SPLIT") != nullptr;
-    const bool will_split = !no_split && (split_env || L.kpad >= 1024) && is16(dtype) && dwp &&
-                            L.nfp % 4 == 0 && a.dwtmp && nsplit == 1;
+    // 3-6 MB weight matrix per 32-64 rows).
+    const bool will_split = L.kpad >= 1024 && is16(dtype) && dwp && L.nfp % 4 == 0 && a.dwtmp && nsplit == 1;
     ProfScope ps(c, s, will_split ? std::string("split_") + cls : std::string(cls), will_split ? 0.0 : flops, will_split ? 0.0 : bytes);
     // round 4: the 147x147 separable convolutions of block 2 on the streaming kernel (kernels_stream.hip)
-    static const bool no_stream = bq_exp_env("BQ_NO_STREAM") != nullptr;
-    if (!no_stream && dwp && L.wp16 && !a.residual && nsplit == 1 && a.H == a.Hi && a.W == a.Wi && a.ldi == L.kpad &&
+    if (dwp && L.wp16 && !a.residual && nsplit == 1 && a.H == a.Hi && a.W == a.Wi && a.ldi == L.kpad &&
         a.ldo == L.cout && stream_supported(dtype, L.kpad, L.cout, a.prod == PROD_DW_RELU, a.n, a.H, a.W)) {
         const int e = launch_sepconv_stream(dtype, L.kpad, L.cout, a.prod == PROD_DW_RELU, a.in, L.wp16, L.dw, L.scale, L.bias,
                                             a.out, a.n, a.H, a.W, a.relu, c->num_cus, s);
@@ -260,9 +255,7 @@ int run_conv(bq_ctx* c, const ConvArgs& a, hipStream_t s) {
                                                    hipGetErrorString((hipError_t)e));
         return BQ_OK;
     }
-    static const bool no_tile = bq_exp_env("BQ_NO_TILE") != nullptr;
-    static const int tile_mask = bq_exp_env("BQ_TILE_MASK") ? atoi(bq_exp_env("BQ_TILE_MASK")) : 15;  // kinds enabled (bit k)
-    if (!no_tile && is16(dtype) && !a.residual) {
+    if (is16(dtype) && !a.residual) {
         int kind = -1;
         if (a.prod == PROD_IM2COL && L.cin == 32 && L.cout == 64) kind = 0;
         else if (a.prod == PROD_DW && L.cin == 64 && L.cout == 128) kind = 1;
@@ -271,7 +264,7 @@ int run_conv(bq_ctx* c, const ConvArgs& a, hipStream_t s) {
                  !(L.wp16 && a.H == a.Hi && a.W == a.Wi && nsplit == 1 &&
                    wide_supported(dtype, a.prod, L.nfp, a.H, a.W, L.kpad, a.ldo, a.ldi, a.ldo, p.M, false)))
             kind = 3;               // (block3_sepconv1: the wide kernel's 74x74 instance when its weights are there)
-        if (kind >= 0 && ((tile_mask >> kind) & 1)) {
+        if (kind >= 0) {
             const int e = launch_tile_conv(dtype, kind, a.in, L.wp, L.dw, L.scale, L.bias, a.out, a.n, a.H, a.W, a.Hi, a.Wi,
                                            a.relu, c->num_cus, s);
             if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch(tile) ") + a.layer + ": " +
@@ -294,8 +287,7 @@ int run_conv(bq_ctx* c, const ConvArgs& a, hipStream_t s) {
         if (gap) *a.gap_done = true;
         // round 4: one image's pixels x 256 channels per workgroup on 16x16x32 fragments (kernels_exit.hip) when the layer's
         // weights are there in that order -- block 14
-        static const bool no_exit = bq_exp_env("BQ_NO_EXIT") != nullptr;
-        if (!no_exit && L.wp16 && !a.residual && a.ldi == L.kpad && a.ldo == L.cout &&
+        if (L.wp16 && !a.residual && a.ldi == L.kpad && a.ldo == L.cout &&
             exit_supported(dtype, L.kpad, L.cout, a.H * a.W, a.n)) {
             const int e = launch_exit_gemm(dtype, a.dwtmp, L.wp16, L.scale, L.bias, a.out, gap ? a.gap_out : nullptr, a.n,
                                            a.H * a.W, L.kpad, L.cout, a.relu, c->feat_mul, s);
@@ -310,8 +302,7 @@ int run_conv(bq_ctx* c, const ConvArgs& a, hipStream_t s) {
     }
     // strided shortcut convolutions with many channels (blocks 4 and 13: K = 256 / 736): a plain GEMM whose A rows are the
     // even pixels of the input map -- the 128 x 128-tile kernel (block 13: 0.13 -> 0.085 ms against the fused-producer form; block 4: the same 0.09 ms)
-    static const bool no_s2tile = bq_exp_env("BQ_NO_S2TILE") != nullptr;
-    if (!no_s2tile && a.prod == PROD_S2 && is16(dtype) && L.kpad >= 256 && L.nfp % 4 == 0 && nsplit == 1 && !a.residual) {
+    if (a.prod == PROD_S2 && is16(dtype) && L.kpad >= 256 && L.nfp % 4 == 0 && nsplit == 1 && !a.residual) {
         p.K = L.kpad; p.k_off = 0; p.kb0 = 0;
         p.scale = L.scale; p.bias = L.bias; p.relu = a.relu; p.residual = nullptr; p.out = a.out;
         const int e = launch_gemm_tile(dtype, p, true, s);
@@ -319,8 +310,7 @@ int run_conv(bq_ctx* c, const ConvArgs& a, hipStream_t s) {
                                                    hipGetErrorString((hipError_t)e));
         return BQ_OK;
     }
-    static const bool no_wide = bq_exp_env("BQ_NO_WIDE") != nullptr;
-    if (!no_wide && nsplit == 1 && L.wp16 && a.H == a.Hi && a.W == a.Wi &&
+    if (nsplit == 1 && L.wp16 && a.H == a.Hi && a.W == a.Wi &&
         wide_supported(dtype, a.prod, L.nfp, a.H, a.W, L.kpad, a.ldo, a.ldi, a.ldo, p.M, a.residual != nullptr)) {
         p.K = L.kpad; p.k_off = 0; p.kb0 = 0;
         p.scale = L.scale; p.bias = L.bias; p.relu = a.relu; p.residual = a.residual; p.out = a.out;
@@ -329,8 +319,7 @@ int run_conv(bq_ctx* c, const ConvArgs& a, hipStream_t s) {
                                                    hipGetErrorString((hipError_t)e));
         return BQ_OK;
     }
-    static const bool no_pipe = bq_exp_env("BQ_NO_PIPE") != nullptr;
-    if (!no_pipe && nsplit == 1 && pipe_supported(dtype, a.prod, L.nfp, a.W, L.kpad)) {
+    if (nsplit == 1 && pipe_supported(dtype, a.prod, L.nfp, a.W, L.kpad)) {
         p.K = L.kpad; p.k_off = 0; p.kb0 = 0;
         p.scale = L.scale; p.bias = L.bias; p.relu = a.relu; p.residual = a.residual; p.out = a.out;
         const int e = launch_sepconv_pipe(dtype, a.prod, p, s);
@@ -389,18 +378,11 @@ int block_end(bq_ctx* c, const char* res_name, const char* pool_name, const void
     if (it == c->layers.end()) return fail(c, BQ_ERR_WEIGHTS, std::string("layer not loaded: ") + res_name);
     const GemmLayer& L = it->second;
     const bool want_res = tap && tap->want && strcmp(tap->want, res_name) == 0;
-    static const bool no_fuse = bq_exp_env("BQ_NO_RESPOOL") != nullptr;
     *tapped = 0;
-    // measured per batch of 256 (one stream): block 2 0.62 -> 0.46 ms, block 3 0.34 -> 0.27 ms; block 4 (K = 256, six
-    // 128-channel workgroups per pixel tile) 0.26 -> 0.34 ms and block 13 0.19 -> 0.20 ms stay on the two-kernel path
-    static const bool fuse_all = bq_exp_env("BQ_RESPOOL_ALL") != nullptr;
     // round 4: the shortcuts of blocks 3, 4 and 13 (K = 128 / 256 / 736) as the tiled GEMM with the pooling pass as its store pass
     // (kernels_split.hip, EPI_POOL): the shortcut tensor never goes to HBM, one launch instead of two
-    static const bool no_poolgemm = bq_exp_env("BQ_NO_POOLGEMM") != nullptr;
-#ifndef POOLGEMM_MINK
-#define POOLGEMM_MINK 128     // block 3 (K = 128) too: 0.273 -> 0.242 ms against kernels_respool.hip; block 2 (K = 64) lives in the fused tail
-#endif
-    if (is16(c->cfg.dtype) && !want_res && !no_poolgemm && L.kpad >= POOLGEMM_MINK && L.nfp % 4 == 0) {
+    constexpr int kPoolGemmMinK = 128;   // block 3 (K = 128) too: 0.273 -> 0.242 ms against kernels_respool.hip; block 2 (K = 64) lives in the fused tail
+    if (is16(c->cfg.dtype) && !want_res && L.kpad >= kPoolGemmMinK && L.nfp % 4 == 0) {
         const double px = (double)n * Ho * Ho;
         GemmParams p{};
         p.in = x; p.wp = L.wp; p.scale = L.scale; p.bias = L.bias; p.residual = y; p.out = out;
@@ -414,7 +396,9 @@ int block_end(bq_ctx* c, const char* res_name, const char* pool_name, const void
         if (e) return fail(c, BQ_ERR_HIP, std::string("launch(gemm_tile pool) ") + res_name + ": " + hipGetErrorString((hipError_t)e));
         return BQ_OK;
     }
-    if (is16(c->cfg.dtype) && L.wp32 && !want_res && !no_fuse && (L.kpad <= 128 || fuse_all)) {
+    // kernels_respool.hip, measured per batch of 256 (one stream): block 2 0.62 -> 0.46 ms, block 3 0.34 -> 0.27 ms; block 4
+    // (K = 256, six 128-channel workgroups per pixel tile) 0.26 -> 0.34 ms and block 13 0.19 -> 0.20 ms stay off it
+    if (is16(c->cfg.dtype) && L.wp32 && !want_res && L.kpad <= 128) {
         const double px = (double)n * Ho * Ho;
         ProfScope ps(c, s, std::string("respool_") + std::to_string(Hi) + "_c" + std::to_string(cout),
                      2.0 * px * L.cin * L.cout + 9.0 * px * co,
@@ -497,10 +481,9 @@ int entry_flow(bq_ctx* c, const void* in_nchw, int n, void* out4, void* A, void*
         void* dst = e.block == 4 ? out4 : nxt;
         {   // round 4: the block's tail in one kernel (kernels_stream.hip) -- sepconv2 + BN, max-pool, shortcut conv + BN, add --
             // unless the tensors it no longer writes were asked for
-            static const bool no_tail = bq_exp_env("BQ_NO_TAIL") != nullptr;
             auto l2 = c->layers.find(nm), lr = c->layers.find(rn);
             const bool want_mid = tap && tap->want && (strcmp(tap->want, nm) == 0 || strcmp(tap->want, rn) == 0);
-            if (!no_tail && !want_mid && l2 != c->layers.end() && lr != c->layers.end() && l2->second.wp16 && lr->second.wp16 &&
+            if (!want_mid && l2 != c->layers.end() && lr != c->layers.end() && l2->second.wp16 && lr->second.wp16 &&
                 e.cout == co && e.cin == ci && tail_supported(dt, co, co, ci, n, e.Hi, e.Hi)) {
                 const double M = (double)n * e.Hi * e.Hi, Mo = (double)n * Ho * Ho;
                 char cls[64];
@@ -532,38 +515,18 @@ int entry_flow(bq_ctx* c, const void* in_nchw, int n, void* out4, void* A, void*
     return BQ_OK;
 }
 
-// part: bit 0 = stem + entry flow (blocks 1-4; its output stays in the workspace), bit 1 = middle + exit flow (reads it there):
-// (experiments build: bq_mc_infer_part lets a scheduler run the two halves of two batches against each other)
 int backbone_impl(bq_ctx* c, const void* in_nchw, int n, float* feat, unsigned char* ws, hipStream_t s,
-                  Tap* tap, const uint8_t* u8 = nullptr, int part = 3) {
+                  Tap* tap, const uint8_t* u8 = nullptr) {
     const WsLayout L = ws_layout(c, n, 1);
     void* A = ws + L.a; void* B = ws + L.b; void* C = ws + L.c; void* R = ws + L.r;
     const int dt = c->cfg.dtype;
     const double es = (double)esize(c);
-    // Entry flow in sub-batches: its activations are the big ones (up to 5.5 MB per tile and layer);
-    // with a small sub-batch every intermediate buffer is re-used at the same addresses and stays in
-    // the 256 MiB Infinity Cache instead of round-tripping through HBM.  The block-4 outputs of all
-    // sub-batches are gathered in the upper half of buffer B (the sub-batches only touch the front).
-    static const int env_sub = bq_exp_env("BQ_SUB") ? atoi(bq_exp_env("BQ_SUB")) : 0;
-    int sub = (tap && tap->want) ? n : env_sub;
-    if (sub <= 0 || sub > n / 2 || part != 3) sub = n;
-    const size_t tile4 = (size_t)361 * 736 * esize(c);
-    // Block 4 reads its input from B (blocks 2-4 alternate between B and R) and must not write over it: in one piece
-    // its output goes to R, and B is the scratch buffer S of the middle and exit flow; in sub-batches it goes to the
-    // upper half of B, which no sub-batch touches.
-    unsigned char* X4 = sub == n ? (unsigned char*)R : (unsigned char*)B + (size_t)(n / 2) * kMaxAct * esize(c);
-    void* S = sub == n ? B : R;
-    if (sub == n) {
-        if (part & 1) RUN(entry_flow(c, in_nchw, n, X4, A, B, C, R, s, tap, u8));
-        if (tap && tap->written >= 0) return BQ_OK;
-        if (!(part & 2)) return BQ_OK;
-    } else {
-        for (int i0 = 0; i0 < n; i0 += sub) {
-            const int ns = n - i0 < sub ? n - i0 : sub;
-            const unsigned char* in_i = (const unsigned char*)in_nchw + (size_t)i0 * kStaged * esize(c);
-            RUN(entry_flow(c, in_i, ns, X4 + (size_t)i0 * tile4, A, B, C, R, s, nullptr, u8 ? u8 + (size_t)i0 * kStaged : nullptr));
-        }
-    }
+    // Block 4 reads its input from B (blocks 2-4 alternate between B and R) and must not write over it: its output goes
+    // to R, and B is the scratch buffer S of the middle and exit flow.
+    void* X4 = R;
+    void* S = B;
+    RUN(entry_flow(c, in_nchw, n, X4, A, B, C, R, s, tap, u8));
+    if (tap && tap->written >= 0) return BQ_OK;
     // middle flow: blocks 5-12 at 19x19x728 (stride 736)
     void* X = X4; void* Y = A;
     for (int block = 5; block <= 12; ++block) {
@@ -596,10 +559,9 @@ int backbone_impl(bq_ctx* c, const void* in_nchw, int n, float* feat, unsigned c
     {   // round 4: the global average pool is the epilogue of block14_sepconv2's GEMM (one workgroup owns an image's 100
         // pixels) unless the convolution's own output was asked for
         const bool want14 = tap && tap->want && strcmp(tap->want, "block14_sepconv2") == 0;
-        static const bool no_gapfuse = bq_exp_env("BQ_NO_GAPFUSE") != nullptr;
         bool gap_done = false;
         ConvArgs a14{"block14_sepconv2", PROD_DW, Y, C, nullptr, S, n, 10, 10, 10, 10, 1536, 2048, 1, X};
-        if (!want14 && !no_gapfuse) { a14.gap_out = feat; a14.gap_done = &gap_done; }
+        if (!want14) { a14.gap_out = feat; a14.gap_done = &gap_done; }
         RUN(run_conv(c, a14, s));
         if (!gap_done) {
             TAP("block14_sepconv2", C, 10, 10, 2048, 2048);
@@ -718,7 +680,6 @@ bq_ctx* bq_create(int device_id, const bq_config* cfg) {
     c->cfg = *cfg;
     c->device = device_id;
     c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (const char* e = bq_exp_env("BQ_NUM_CUS")) { const int v = atoi(e); if (v > 0) c->num_cus = v; }   // persistent-grid sizing (experiments)
     {   // tables of the Reinhard normaliser (oracle/stain.py states the same arithmetic):
         // [0,256)   sRGB -> linear, float64 evaluation rounded to float32
         // [256,511) linear -> 8-bit sRGB as 255 switching points: entry v-1 is the smallest float32 c for which
@@ -869,8 +830,7 @@ int bq_stage(bq_ctx* c, const uint8_t* d_tiles, int n, void* d_out, bq_stream_t 
     if (!c || !d_tiles || !d_out || n < 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_stage: bad argument");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(c, s, "stage_u8_standardize", 4.0 * n * kStaged, (double)n * kStaged * (1.0 + esize(c)));
-    static const bool one_kernel = bq_exp_env("BQ_STAGE_1K") != nullptr;
-    if (launch_stage_u8(d_tiles, n, 299, d_out, c->cfg.dtype, one_kernel ? nullptr : c->d_stage_stats, s))
+    if (launch_stage_u8(d_tiles, n, 299, d_out, c->cfg.dtype, c->d_stage_stats, s))
         return fail(c, BQ_ERR_HIP, "stage launch failed");
     return BQ_OK;
 }
@@ -1039,14 +999,13 @@ int bq_set_tile_index_array(bq_ctx* c, const int64_t* d_tile_idx) {
 // the planar tensor.  bq_mc_infer and bq_backbone_u8 share it, so a tile's features do not depend on which of the two a
 // caller used for its batch.
 static int features_from_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* feat, unsigned char* ws, const WsLayout& L,
-                            bq_stream_t stream, int part = 3) {
+                            bq_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    static const bool no_front = bq_exp_env("BQ_NO_FRONT") != nullptr;
-    const bool front = !no_front && is16(c->cfg.dtype) && c->front_ws16 && c->front_wc16;
-    if (front) return backbone_impl(c, nullptr, n, feat, ws, s, nullptr, d_tiles, part);
+    const bool front = is16(c->cfg.dtype) && c->front_ws16 && c->front_wc16;
+    if (front) return backbone_impl(c, nullptr, n, feat, ws, s, nullptr, d_tiles);
     void* staged = ws + L.staged;
-    if (part & 1) RUN(bq_stage(c, d_tiles, n, staged, stream));
-    return backbone_impl(c, staged, n, feat, ws, s, nullptr, nullptr, part);
+    RUN(bq_stage(c, d_tiles, n, staged, stream));
+    return backbone_impl(c, staged, n, feat, ws, s, nullptr, nullptr);
 }
 
 int bq_mc_infer(bq_ctx* c, const uint8_t* d_tiles, int n, int64_t tile_idx0, int mc_n, uint64_t seed,
@@ -1072,28 +1031,6 @@ int bq_mc_infer(bq_ctx* c, const uint8_t* d_tiles, int n, int64_t tile_idx0, int
     }
     return BQ_OK;
 }
-
-#ifdef BQ_EXPERIMENTS
-// bq_mc_infer (BQ_MC_HEAD) in two parts, for a scheduler that runs the entry parts and the rests of two batches against each other
-// (tools/phased_pool.py): ENTRY = staging, stem and entry flow, whose output stays in the workspace; REST = middle and exit flow + the
-// MC head.  Round 5 measured every such schedule equal to or slower than free-running streams (profiles/r05_schedules_steps.log), so
-// the entry point is not part of the product library: `make EXPERIMENTS=1` builds it.
-enum { BQ_PART_ENTRY = 1, BQ_PART_REST = 2, BQ_PART_ALL = 3 };
-extern "C" int bq_mc_infer_part(bq_ctx* c, const uint8_t* d_tiles, int n, int64_t tile_idx0, int mc_n, uint64_t seed, int part,
-                                float* d_mean2, float* d_std2, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
-    if (!c || !d_tiles || !d_mean2 || !d_std2 || !d_ws || n <= 0 || mc_n <= 0 || n > c->cfg.max_batch ||
-        mc_n > c->cfg.max_mc || (part != BQ_PART_ENTRY && part != BQ_PART_REST && part != BQ_PART_ALL))
-        return fail(c, BQ_ERR_ARG, "bq_mc_infer_part: bad argument");
-    if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
-    const WsLayout L = ws_layout(c, n, mc_n);
-    if (ws_bytes < L.total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
-    unsigned char* ws = (unsigned char*)d_ws;
-    float* feat = (float*)(ws + L.feat);
-    RUN(features_from_u8(c, d_tiles, n, feat, ws, L, stream, part));
-    if (!(part & BQ_PART_REST)) return BQ_OK;
-    return head_impl(c, feat, n, tile_idx0, mc_n, 0, seed, 1, 1, (float*)(ws + L.state), d_mean2, d_std2, ws, (hipStream_t)stream);
-}
-#endif
 
 int bq_backbone_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_feat, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
     if (!c || !d_tiles || !d_feat || !d_ws || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_backbone_u8: bad argument");

@@ -4,15 +4,6 @@
 #include <stdint.h>
 #include <stddef.h>
 
-#include <stdlib.h>
-
-// Experiment switches (ablations, alternative tilings, in-kernel stamps) exist only in -DBQ_EXPERIMENTS builds
-// (`make EXPERIMENTS=1`); the product library reads no environment variable and carries no debug branch.
-#ifdef BQ_EXPERIMENTS
-inline const char* bq_exp_env(const char* name) { return getenv(name); }
-#else
-inline const char* bq_exp_env(const char*) { return nullptr; }
-#endif
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the current device only: remember, per device, the
 // largest size already set for one kernel (one `BqLdsAttr` object per kernel instantiation).

@@ -17,9 +17,8 @@ generated assembly and fails the build unless, in every sepconv_wide*_kernel ins
 import re
 import sys
 
-warn_only = '--warn' in sys.argv          # experiments builds (in-kernel stamps cost registers): report, do not fail
 kernels = []
-for path in [a for a in sys.argv[1:] if a != '--warn']:
+for path in sys.argv[1:]:
     found = re.findall(r'^(_ZN\S*sepconv_wide\d*_kernel\S*):[^\n]*\n(.*?)s_endpgm', open(path).read(), re.S | re.M)
     if not found:
         sys.exit('check_wide: no sepconv_wide*_kernel instance found in ' + path)
@@ -117,8 +116,8 @@ for name, body in kernels:
         m = re.match(r's_nop\s+(\d+)', ln)
         states += int(m.group(1)) + 1 if m else 1
 if bad:
-    print('check_wide: FAILED' + (' (warning only)' if warn_only else ''), file=sys.stderr)
+    print('check_wide: FAILED', file=sys.stderr)
     for b in bad[:20]:
         print('  ' + b, file=sys.stderr)
-    sys.exit(0 if warn_only else 1)
+    sys.exit(1)
 print(f'check_wide: ok ({len(kernels)} instances: accumulators in place, no scratch in the K loop, no VALU->MFMA operand hazard)')

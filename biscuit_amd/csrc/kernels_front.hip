@@ -23,12 +23,6 @@
 // 11 independent waves per CU, no workgroup barrier after the weights are in LDS.
 #include "gemm_common.h"
 
-// ablation switches of tools/ubench/stream_bench.hip (timing only, wrong results): 1 no stores, 4 no conv2 MFMAs, 8 no uint8
-// loads, 32 no stem (operand build + MFMAs + epilogue).  The product build has none of them.
-#ifndef FRONT_ABL
-#define FRONT_ABL 0
-#endif
-
 namespace {
 using namespace bqk;
 
@@ -37,10 +31,7 @@ typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 
 constexpr int PX = 299, SO = 149, CO = 147;     // tile, stem output, conv2 output edge
 constexpr int ROWB = PX * 3;                    // bytes per uint8 row
-#ifndef FRONT_NW
-#define FRONT_NW 11
-#endif
-constexpr int NWF = FRONT_NW;                   // waves per workgroup (11 = strips per image row: at batch 256 every wave gets 6 items)
+constexpr int NWF = 11;                         // waves per workgroup (11 = strips per image row: at batch 256 every wave gets 6 items)
 constexpr int SW = 14;                          // conv2 columns per strip: 16 stem columns = ONE MFMA pixel tile for the stem
 constexpr float LO_SCALE = 1.0f / 2048.0f;      // weights.py: HEAD_SPLIT_SCALE
 
@@ -170,7 +161,6 @@ __global__ void __launch_bounds__(NWF * 64) front_stream_kernel(const FrontParam
             a4 = a4 < 0 ? 0 : (a4 > last4 ? last4 : a4);
             shr_out = (int)over * 8;
             shl_out = shl;
-            if constexpr (FRONT_ABL & 8) return (unsigned)a4;
             return *reinterpret_cast<const unsigned*>(p.tiles + a4);
         };
         const int lrow = lane >> 5, ldw = lane & 31;
@@ -194,11 +184,7 @@ __global__ void __launch_bounds__(NWF * 64) front_stream_kernel(const FrontParam
                       sh2 = (int)(reinterpret_cast<uintptr_t>(r0 + 2 * ROWB) & 3);
             {   // every lane stores (lanes past the 26 dwords into the row's padding, both halves the same third row): under
                 // `if (ldw < 26)` the compiler loses count of what is in flight and waits for the previous step's stores too
-                if constexpr (FRONT_ABL & 32) {
-                if (ua == 0x12345u) *reinterpret_cast<unsigned*>(ring + slot * RING_PITCH + lane * 4) = ua ^ ub;
-                return;
-            }
-            const int dwc = ldw < U8_DW ? ldw : U8_PITCH / 4 - 1;
+                const int dwc = ldw < U8_DW ? ldw : U8_PITCH / 4 - 1;
                 *reinterpret_cast<unsigned*>(u8l + lrow * U8_PITCH + 4 * dwc) = (ua >> ua_r) << ua_l;
                 *reinterpret_cast<unsigned*>(u8l + 2 * U8_PITCH + 4 * dwc) = (ub >> ub_r) << ub_l;
             }
@@ -301,10 +287,7 @@ __global__ void __launch_bounds__(NWF * 64) front_stream_kernel(const FrontParam
 #pragma unroll
                     for (int r = 0; r < 2; ++r)
 #pragma unroll
-                        for (int f = 0; f < 4; ++f) {
-                            if constexpr (FRONT_ABL & 4) { acc[r][f][0] += __uint_as_float(w[t & 1][f].x ^ b[dy + r][dx].x); acc[r][f][1] += __uint_as_float(w[t & 1][f].y ^ b[dy + r][dx].w); }
-                            else acc[r][f] = mmaT<T>(w[t & 1][f], b[dy + r][dx], acc[r][f]);
-                        }
+                        for (int f = 0; f < 4; ++f) acc[r][f] = mmaT<T>(w[t & 1][f], b[dy + r][dx], acc[r][f]);
                 }
             }
 #pragma unroll
@@ -320,7 +303,7 @@ __global__ void __launch_bounds__(NWF * 64) front_stream_kernel(const FrontParam
                     o[1] = H16<T>::pack2(fmaxf(fmaf(u[2], a0.z, b0.z), 0.f), fmaxf(fmaf(u[3], a0.w, b0.w), 0.f));
                     o[2] = H16<T>::pack2(fmaxf(fmaf(v[0], a1.x, b1.x), 0.f), fmaxf(fmaf(v[1], a1.y, b1.y), 0.f));
                     o[3] = H16<T>::pack2(fmaxf(fmaf(v[2], a1.z, b1.z), 0.f), fmaxf(fmaf(v[3], a1.w, b1.w), 0.f));
-                    if (!(FRONT_ABL & 1) || o[0] == 0x12345678u) __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, (int)off + 64 * q, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, (int)off + 64 * q, 0, 0);
                 }
             }
             { const int t0 = s0, t1 = s1; s0 = s2; s1 = s3; s2 = t0; s3 = t1; }

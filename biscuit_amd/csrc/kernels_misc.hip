@@ -25,69 +25,10 @@ template <typename T> __device__ __forceinline__ void f16_mode() {
 }
 
 // ---------------------------------------------------------------- K0 staging
-// One workgroup per tile.  Pass 1: exact integer sum / sum of squares of the uint8
-// bytes (order-independent, so the statistics are bit-reproducible), pass 2 re-reads the
-// (now L2-resident) 268 KB tile, standardises and writes three contiguous planes.
-template <typename T>
-__global__ void __launch_bounds__(512) stage_u8_kernel(const uint8_t* __restrict__ tiles, int px,
-                                                       T* __restrict__ out) {
-    f16_mode<T>();
-    const int npix = px * px;
-    const int nbytes = npix * 3;
-    const uint8_t* src = tiles + (size_t)blockIdx.x * nbytes;
-    const int tid = threadIdx.x, nt = blockDim.x;
-
-    unsigned long long s1 = 0, s2 = 0;
-    // aligned 4-byte body, scalar head/tail
-    const int head = (int)((4 - ((uintptr_t)src & 3)) & 3);
-    const int body = (nbytes - head) >> 2;
-    if (tid < head) { const unsigned v = src[tid]; s1 += v; s2 += v * v; }
-    const unsigned* w = reinterpret_cast<const unsigned*>(src + head);
-    for (int i = tid; i < body; i += nt) {
-        const unsigned u = w[i];
-        const unsigned a = u & 255u, b = (u >> 8) & 255u, c = (u >> 16) & 255u, d = u >> 24;
-        s1 += a + b + c + d;
-        s2 += a * a + b * b + c * c + d * d;
-    }
-    const int tail0 = head + body * 4;
-    if (tid < nbytes - tail0) { const unsigned v = src[tail0 + tid]; s1 += v; s2 += v * v; }
-
-    __shared__ unsigned long long red[2][8];
-    __shared__ float stat[2];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o);
-        s2 += __shfl_xor(s2, o);
-    }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long a = 0, b = 0;
-        for (int i = 0; i < nt / 64; ++i) { a += red[0][i]; b += red[1][i]; }
-        const double n = (double)nbytes;
-        const double mean = (double)a / n;
-        double var = (double)b / n - mean * mean;
-        if (var < 0) var = 0;
-        const double sd = sqrt(var);
-        const double floor_sd = 1.0 / sqrt(n);  // tf.image.per_image_standardization
-        stat[0] = (float)mean;
-        stat[1] = (float)(1.0 / (sd > floor_sd ? sd : floor_sd));
-    }
-    __syncthreads();
-    const float mean = stat[0], inv = stat[1];
-    T* o0 = out + (size_t)blockIdx.x * nbytes;
-    for (int p = tid; p < npix; p += nt) {
-        const uint8_t* q = src + p * 3;
-        o0[p] = from_f32<T>(((float)q[0] - mean) * inv);
-        o0[npix + p] = from_f32<T>(((float)q[1] - mean) * inv);
-        o0[2 * npix + p] = from_f32<T>(((float)q[2] - mean) * inv);
-    }
-}
-
-// Two-kernel form of K0 with SLICES workgroups per tile (one workgroup per tile leaves the chip at one
-// workgroup per CU for an HBM-bound pass: 0.157 ms per 256 tiles against a 0.04 ms roofline): integer sums
-// into two 64-bit atomics per tile (exact and order-independent, like the one-kernel form), then the
-// standardisation pass.
+// Two kernels with SLICES workgroups per tile (one workgroup per tile leaves the chip at one workgroup per
+// CU for an HBM-bound pass: 0.157 ms per 256 tiles against a 0.04 ms roofline): exact integer sum / sum of
+// squares of the uint8 bytes into two 64-bit atomics per tile (order-independent, so the statistics are
+// bit-reproducible), then the standardisation pass, which writes three contiguous planes.
 constexpr int kStageSlices = 8;
 
 __global__ void __launch_bounds__(256) stage_stats_kernel(const uint8_t* __restrict__ tiles, int px,
@@ -139,7 +80,7 @@ __global__ void __launch_bounds__(256) stage_apply_kernel(const uint8_t* __restr
     const int npix = px * px, nbytes = npix * 3;
     const int tile = blockIdx.x / kStageSlices, sl = blockIdx.x - tile * kStageSlices;
     const uint8_t* src = tiles + (size_t)tile * nbytes;
-    // same arithmetic as the one-kernel form: float64 statistics from the exact integer sums
+    // float64 statistics from the exact integer sums
     const double n = (double)nbytes;
     const double mean_d = (double)stats[2 * tile] / n;
     double var = (double)stats[2 * tile + 1] / n - mean_d * mean_d;
@@ -460,20 +401,16 @@ inline int grid_for(long long total, int block) { return (int)((total + block - 
         else { using T_ = float; __VA_ARGS__; }                                \
     } while (0)
 
+// stats_scratch: 2 x 64-bit per tile, zeroed here
 int launch_stage_u8(const uint8_t* tiles, int n, int px, void* out, int dtype, double* stats_scratch, hipStream_t s) {
     if (n <= 0) return 0;
-    if (stats_scratch) {          // 2 x 64-bit per tile, zeroed here
-        unsigned long long* st = reinterpret_cast<unsigned long long*>(stats_scratch);
-        hipError_t e = hipMemsetAsync(st, 0, (size_t)n * 16, s);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(stage_stats_kernel, dim3(n * kStageSlices), dim3(256), 0, s, tiles, px, st);
-        BQ_DISPATCH_T(dtype,
-                      hipLaunchKernelGGL(stage_apply_kernel<T_>, dim3(n * kStageSlices), dim3(256), 0, s, tiles, px,
-                                         st, (T_*)out));
-        return (int)hipGetLastError();
-    }
+    unsigned long long* st = reinterpret_cast<unsigned long long*>(stats_scratch);
+    hipError_t e = hipMemsetAsync(st, 0, (size_t)n * 16, s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(stage_stats_kernel, dim3(n * kStageSlices), dim3(256), 0, s, tiles, px, st);
     BQ_DISPATCH_T(dtype,
-                  hipLaunchKernelGGL(stage_u8_kernel<T_>, dim3(n), dim3(512), 0, s, tiles, px, (T_*)out));
+                  hipLaunchKernelGGL(stage_apply_kernel<T_>, dim3(n * kStageSlices), dim3(256), 0, s, tiles, px,
+                                     st, (T_*)out));
     return (int)hipGetLastError();
 }
 

@@ -623,9 +623,8 @@ int launch_sepconv_pipe_t(int prod, const GemmParams& p, hipStream_t s) {
     const bool relu = prod == PROD_DW_RELU;
     if (pipe_variant(p.NFp, p.W) == 0) return relu ? launch_pipe<T, true, 3, 3, 1>(p, s) : launch_pipe<T, false, 3, 3, 1>(p, s);
     // 256-wide: 192-row tiles on 16 waves where the halo of a 96-row tile is larger than the tile itself
-    static const bool no_wide = bq_exp_env("BQ_PIPE_NO_WM2") != nullptr;
     const size_t lds2 = (size_t)2 * (192 + 2 * (p.W + 1)) * RAW_ROW + 2 * 192 * A_STR + (size_t)9 * p.K * 4;
-    if (!no_wide && p.W >= 48 && lds2 + (size_t)p.NFp * 32 * 8 + 16 <= 160 * 1024 && (192 + 2 * (p.W + 1)) * CPR <= 3 * 1024)
+    if (p.W >= 48 && lds2 + (size_t)p.NFp * 32 * 8 + 16 <= 160 * 1024 && (192 + 2 * (p.W + 1)) * CPR <= 3 * 1024)
         return relu ? launch_pipe<T, true, 1, 3, 2>(p, s) : launch_pipe<T, false, 1, 3, 2>(p, s);
     return relu ? launch_pipe<T, true, 1, 4, 1>(p, s) : launch_pipe<T, false, 1, 4, 1>(p, s);
 }

@@ -26,27 +26,11 @@
 //    the others' depthwise and matrix work.
 #include "mfma16_common.h"
 
-// ablation switches of tools/ubench/stream_bench.hip (timing only, wrong results): 1 no stores, 2 no depthwise arithmetic,
-// 4 no MFMAs, 8 no input loads, 16 no pooling / shortcut.  The product build has none of them.
-#ifndef STREAM_ABL
-#define STREAM_ABL 0
-#endif
-#ifndef STREAM_NW
-#define STREAM_NW 12
-#endif
-// The depthwise stage of f16 instances in PACKED HALF arithmetic (v_pk_fma_f16 on the dwords as they arrive: taps rounded to f16,
-// nine roundings per output instead of one; no conversions, half the registers of the running sums): bit 0 = the fused block
-// tails (block2_sepconv2, block3_sepconv2), bit 1 = the plain streaming layers (block2_sepconv1, block3_sepconv1).  Measured in
-// round 6 (experiments/r06.md).
-#ifndef STREAM_DW_F16
-#define STREAM_DW_F16 0
-#endif
-#ifndef TAIL_NW
-#define TAIL_NW 8
-#endif
-
 namespace {
 using namespace bqk;
+
+constexpr int STREAM_NW = 12;   // waves per workgroup of the plain streaming kernel (<= 128 output channels)
+constexpr int TAIL_NW = 8;      // waves per workgroup of the fused block-2 tail
 
 // first element and length of part s when n elements are cut into ns parts of nearly equal length
 __device__ __forceinline__ void strip_span(int s, int n, int ns, int& x0, int& nc) {
@@ -61,6 +45,7 @@ __device__ __forceinline__ void strip_span(int s, int n, int ns, int& x0, int& n
 //   OUT:  out(y)[x] = sa[x] + taps(2, .) . row[x ..]  -> rounded, written to the A tile (one ds_write_b32 per column)
 //   then  sa[x] = sb[x] + taps(1, .) . row[x ..],  sb[x] = 0 + taps(0, .) . row[x ..]
 // Tap order per output: (0,0) (0,1) (0,2) (1,0) ... (2,2), each `a = fma(tap, v, a)` from 0.0f: the tile kernels' order.
+// (The same sums in packed half arithmetic for the f16 instances were measured in round 6 and not adopted: experiments/r06.md.)
 template <typename T, int NCOL>
 struct DwSums {
     f32x2s sa[NCOL], sb[NCOL];
@@ -77,69 +62,21 @@ struct DwSums {
         for (int x = 0; x < NCOL; ++x) {
             if constexpr (OUT) {
                 f32x2s o = sa[x];
-                if constexpr (STREAM_ABL & 2) o = v[x + 1];
-                else
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) o = __builtin_elementwise_fma(tap[6 + dx], v[x + dx], o);
                 *reinterpret_cast<unsigned*>(a_lane + x * ast) = H16<T>::pack2(o.x, o.y);
             }
-            if constexpr (!(STREAM_ABL & 2)) {
-                f32x2s a = sb[x];
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) a = __builtin_elementwise_fma(tap[3 + dx], v[x + dx], a);
-                sa[x] = a;
-                f32x2s b = {0.f, 0.f};
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) b = __builtin_elementwise_fma(tap[dx], v[x + dx], b);
-                sb[x] = b;
-            }
-        }
-    }
-};
-
-// The same running sums in packed half arithmetic (STREAM_DW_F16, f16 instances only): the window is the packed dwords themselves.
-typedef _Float16 h16x2p __attribute__((ext_vector_type(2)));
-template <int NCOL>
-struct DwSumsH {
-    h16x2p sa[NCOL], sb[NCOL];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int x = 0; x < NCOL; ++x) { sa[x] = (h16x2p){0, 0}; sb[x] = (h16x2p){0, 0}; }
-    }
-    template <bool OUT>
-    __device__ __forceinline__ void push(const h16x2p (&tap)[9], const unsigned (&row)[NCOL + 2], unsigned char* a_lane, int ast) {
-        h16x2p v[NCOL + 2];
-#pragma unroll
-        for (int j = 0; j < NCOL + 2; ++j) v[j] = __builtin_bit_cast(h16x2p, row[j]);
-#pragma unroll
-        for (int x = 0; x < NCOL; ++x) {
-            if constexpr (OUT) {
-                h16x2p o = sa[x];
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) o = __builtin_elementwise_fma(tap[6 + dx], v[x + dx], o);
-                *reinterpret_cast<unsigned*>(a_lane + x * ast) = __builtin_bit_cast(unsigned, o);
-            }
-            h16x2p a = sb[x];
+            f32x2s a = sb[x];
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) a = __builtin_elementwise_fma(tap[3 + dx], v[x + dx], a);
             sa[x] = a;
-            h16x2p b = {0, 0};
+            f32x2s b = {0.f, 0.f};
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) b = __builtin_elementwise_fma(tap[dx], v[x + dx], b);
             sb[x] = b;
         }
     }
 };
-// the depthwise state of an instance: packed half for f16 when STREAM_DW_F16, fp32 pairs otherwise
-template <typename T, int NCOL, bool WANT> struct DwSel { typedef DwSums<T, NCOL> sums; typedef f32x2s tap_t; };
-template <int NCOL> struct DwSel<f16_t, NCOL, true> { typedef DwSumsH<NCOL> sums; typedef h16x2p tap_t; };
-constexpr bool DW_HALF_TAIL = (STREAM_DW_F16 & 1) != 0, DW_HALF_PLAIN = (STREAM_DW_F16 & 2) != 0;
-template <typename TAP>
-__device__ __forceinline__ TAP load_tap(const float* p) {
-    const f32x2s t = *reinterpret_cast<const f32x2s*>(p);
-    if constexpr (sizeof(TAP) == 4) return (TAP){(_Float16)t.x, (_Float16)t.y};
-    else return t;
-}
 
 // ---- pointwise: D[cout][pixel] = W[cout][k] * A[pixel][k] from the wave's A tile (LDS operations of a wave complete in order)
 template <typename T, int KS, int NF>
@@ -167,8 +104,7 @@ __device__ __forceinline__ void pointwise(const unsigned char* smem_w, const uns
 #pragma unroll
         for (int i = 0; i < G; ++i) {
             const int ks = (grp * G + i) / NF, f = (grp * G + i) % NF;
-            if constexpr (STREAM_ABL & 4) { acc[f][0] += __uint_as_float(w[grp & 1][i].x ^ b[ks].x); acc[f][1] += __uint_as_float(w[grp & 1][i].y ^ b[ks].y); }
-            else acc[f] = mma16<T>(w[grp & 1][i], b[ks], acc[f]);
+            acc[f] = mma16<T>(w[grp & 1][i], b[ks], acc[f]);
         }
     }
 }
@@ -215,10 +151,9 @@ __global__ void __launch_bounds__(NW * 64) sepconv_stream_kernel(const StreamPar
     }
     const int cpair = HALVES == 1 ? lane : (lane & 31);
     const int chalf = HALVES == 1 ? 0 : (lane >> 5);
-    typedef DwSel<T, NCOL, DW_HALF_PLAIN> DW;
-    typename DW::tap_t tap[9];
+    f32x2s tap[9];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) tap[t] = load_tap<typename DW::tap_t>(p.dw + t * CIN + 2 * cpair);
+    for (int t = 0; t < 9; ++t) tap[t] = *reinterpret_cast<const f32x2s*>(p.dw + t * CIN + 2 * cpair);
     __syncthreads();                            // the only workgroup barrier of the kernel
 
     unsigned char* const At = smem + A_OFF + wave * A_BYTES;
@@ -258,10 +193,7 @@ __global__ void __launch_bounds__(NW * 64) sepconv_stream_kernel(const StreamPar
             const int yc = y < 0 ? 0 : (y >= p.H ? p.H - 1 : y);
             const T* rp = img_in + (size_t)yc * p.W * CIN;
 #pragma unroll
-            for (int j = 0; j < NWIN; ++j) {
-                if constexpr (STREAM_ABL & 8) nx[j] = (unsigned)(size_t)rp + j;
-                else nx[j] = *reinterpret_cast<const unsigned*>(rp + j * CIN);
-            }
+            for (int j = 0; j < NWIN; ++j) nx[j] = *reinterpret_cast<const unsigned*>(rp + j * CIN);
         };
         auto take_row = [&](int y) {                       // nx (row y) -> row, zero outside the image, ReLU of the layer in front
             const unsigned m = (unsigned)y < (unsigned)p.H ? cmask : 0u;
@@ -272,7 +204,7 @@ __global__ void __launch_bounds__(NW * 64) sepconv_stream_kernel(const StreamPar
 #pragma unroll
             for (int j = 0; j < NWIN; ++j) row[j] = ((m >> j) & 1u) ? row[j] : 0u;
         };
-        typename DW::sums dws;
+        DwSums<T, NCOL> dws;
         dws.clear();
         load_row(y0 - 1); take_row(y0 - 1);
         load_row(y0);
@@ -311,8 +243,7 @@ __global__ void __launch_bounds__(NW * 64) sepconv_stream_kernel(const StreamPar
 #pragma unroll
                 for (int i = 0; i < 4; ++i) asm("v_pk_max_i16 %0, %1, %2" : "=v"(o[i]) : "v"(o[i]), "v"(lo2));
                 const u32x4s ov = {o[0], o[1], o[2], o[3]};
-                if constexpr (STREAM_ABL & 1) { if (o[0] == 0x12345678u && o[1] == 0x9abcdef0u) __builtin_amdgcn_raw_buffer_store_b128(ov, orsrc, (int)ooff + 64 * q, 0, 0); }
-                else __builtin_amdgcn_raw_buffer_store_b128(ov, orsrc, (int)ooff + 64 * q, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(ov, orsrc, (int)ooff + 64 * q, 0, 0);
             }
         }
     }
@@ -384,10 +315,9 @@ __global__ void __launch_bounds__(NW * 64) block_tail_stream_kernel(const TailPa
         float* sbw = reinterpret_cast<float*>(smem + SB_OFF);
         sbw[i] = p.scale[i]; sbw[COUT + i] = p.bias[i]; sbw[2 * COUT + i] = p.rscale[i]; sbw[3 * COUT + i] = p.rbias[i];
     }
-    typedef DwSel<T, NCOL, DW_HALF_TAIL> DW;
-    typename DW::tap_t tap[9];
+    f32x2s tap[9];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) tap[t] = load_tap<typename DW::tap_t>(p.dw + t * CIN + 2 * lane);
+    for (int t = 0; t < 9; ++t) tap[t] = *reinterpret_cast<const f32x2s*>(p.dw + t * CIN + 2 * lane);
     __syncthreads();
 
     unsigned char* const At = smem + A_OFF + wave * A_BYTES;
@@ -436,10 +366,7 @@ __global__ void __launch_bounds__(NW * 64) block_tail_stream_kernel(const TailPa
             const int yc = y < 0 ? 0 : (y >= p.H ? p.H - 1 : y);
             const T* rp = img_in + (size_t)yc * p.W * CIN;
 #pragma unroll
-            for (int j = 0; j < NWIN; ++j) {
-                if constexpr (STREAM_ABL & 8) nx[j] = (unsigned)(size_t)rp + j;
-                else nx[j] = *reinterpret_cast<const unsigned*>(rp + j * CIN);
-            }
+            for (int j = 0; j < NWIN; ++j) nx[j] = *reinterpret_cast<const unsigned*>(rp + j * CIN);
         };
         auto take_row = [&](int y) {
             const unsigned m = (unsigned)y < (unsigned)p.H ? cmask : 0u;
@@ -450,7 +377,7 @@ __global__ void __launch_bounds__(NW * 64) block_tail_stream_kernel(const TailPa
 #pragma unroll
             for (int j = 0; j < NWIN; ++j) row[j] = ((m >> j) & 1u) ? row[j] : 0u;
         };
-        typename DW::sums dws;
+        DwSums<T, NCOL> dws;
         dws.clear();
         load_row(ys - 1); take_row(ys - 1);
         load_row(ys);
@@ -507,7 +434,7 @@ __global__ void __launch_bounds__(NW * 64) block_tail_stream_kernel(const TailPa
             u32x4s po[NQ];
 #pragma unroll
             for (int q = 0; q < NQ; ++q) po[q] = (u32x4s){0u, 0u, 0u, 0u};
-            if (do_emit && !(STREAM_ABL & 16)) {          // wave-uniform; no memory operation of the vmcnt stream inside
+            if (do_emit) {                                // wave-uniform; no memory operation of the vmcnt stream inside
                 asm volatile("" ::: "memory");            // a real branch: left alone hipcc runs all of this on every row and selects
                 // shortcut: D[cout][slot] = Wr[cout][k] x[k][slot]
                 f32x4 ar[NF];
@@ -540,13 +467,7 @@ __global__ void __launch_bounds__(NW * 64) block_tail_stream_kernel(const TailPa
                 const unsigned off = (do_emit && lane_out) ? obase + (unsigned)yo * (unsigned)(p.Wo * COUT * sizeof(T)) : 0xfffff000u;
 #pragma unroll
                 for (int q = 0; q < NQ; ++q)
-                    if (!(STREAM_ABL & 1) || po[q][0] == 0x12345678u) __builtin_amdgcn_raw_buffer_store_b128(po[q], orsrc, (int)off + 64 * q, 0, 0);
-                if constexpr (STREAM_ABL & 16) {
-                    unsigned h = xb[0].x ^ xb[KR - 1].w;
-#pragma unroll
-                    for (int i = 0; i < 4 * NQ; ++i) h ^= VM[i];
-                    if (h == 0x12345678u) __builtin_amdgcn_raw_buffer_store_b128(po[0], orsrc, (int)h, 0, 0);
-                }
+                    __builtin_amdgcn_raw_buffer_store_b128(po[q], orsrc, (int)off + 64 * q, 0, 0);
             }
             if (t_even) {
 #pragma unroll
@@ -575,7 +496,7 @@ inline int pick_bands(long long base_items, int rows, int rows_per_band, int min
 // 74x74x256 tensor between the convolution and the pool is never written.
 template <typename T>
 struct CoopParams {
-    const T* in;           // sepconv2's input [n][H][W][C]           (C = 256: block 3; 128: block 2)
+    const T* in;           // sepconv2's input [n][H][W][C]           (C = 256: block 3)
     const uint4* wp16;     // [C / 32][C / 16][64] x 16 B
     const float* dw;       // [9][C]
     const float* scale;    // [C]
@@ -617,10 +538,9 @@ __global__ void __launch_bounds__(C * 2, WGS) block_tail_coop_kernel(const CoopP
 #pragma unroll
         for (int i = 0; i < 2; ++i) wrq[ks][i] = p.wr16[((size_t)ks * NFR + 2 * wave + i) * 64 + lane];
     const int pair = lane & 15, cg = lane >> 4;                      // depthwise role: channels 32 w + 2 pair (+1), columns 4 cg .. 4 cg + 3
-    typedef DwSel<T, NCOL, DW_HALF_TAIL> DW;
-    typename DW::tap_t tap[9];
+    f32x2s tap[9];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) tap[t] = load_tap<typename DW::tap_t>(p.dw + t * CIN + 32 * wave + 2 * pair);
+    for (int t = 0; t < 9; ++t) tap[t] = *reinterpret_cast<const f32x2s*>(p.dw + t * CIN + 32 * wave + 2 * pair);
     __syncthreads();
 
     const int px = lane & 15, g = lane >> 4;                         // matrix role: pixel slot, channel group
@@ -663,10 +583,7 @@ __global__ void __launch_bounds__(C * 2, WGS) block_tail_coop_kernel(const CoopP
             const int yc = y < 0 ? 0 : (y >= p.H ? p.H - 1 : y);
             const T* rp = img_in + (size_t)yc * p.W * CIN;
 #pragma unroll
-            for (int j = 0; j < NWIN; ++j) {
-                if constexpr (STREAM_ABL & 8) nx[j] = (unsigned)(size_t)rp + j;
-                else nx[j] = *reinterpret_cast<const unsigned*>(rp + j * CIN);
-            }
+            for (int j = 0; j < NWIN; ++j) nx[j] = *reinterpret_cast<const unsigned*>(rp + j * CIN);
         };
         auto take_row = [&](int y, const unsigned (&nx)[NWIN]) {
             const unsigned m = (unsigned)y < (unsigned)p.H ? cmask : 0u;
@@ -677,7 +594,7 @@ __global__ void __launch_bounds__(C * 2, WGS) block_tail_coop_kernel(const CoopP
 #pragma unroll
             for (int j = 0; j < NWIN; ++j) row[j] = ((m >> j) & 1u) ? row[j] : 0u;
         };
-        typename DW::sums dws;
+        DwSums<T, NCOL> dws;
         dws.clear();
         unsigned char* a_lane0 = smem + (NCOL * cg) * AST + (32 * wave + 2 * pair) * 2;      // buffer 0; buffer 1 at + A_BYTES
         // Software pipeline: a step pushes row y + 2 -- the depthwise output of row y + 1 goes to the OTHER A buffer -- and
@@ -688,10 +605,7 @@ __global__ void __launch_bounds__(C * 2, WGS) block_tail_coop_kernel(const CoopP
         auto load_x = [&](int yo) {
             const T* xr = xcol + (size_t)(2 * yo) * p.W * CX;
 #pragma unroll
-            for (int ks = 0; ks < KR; ++ks) {
-                if constexpr (STREAM_ABL & 8) xb[ks] = make_uint4((unsigned)(size_t)xr, ks, 3, 4);
-                else xb[ks] = *reinterpret_cast<const uint4*>(xr + 32 * ks);
-            }
+            for (int ks = 0; ks < KR; ++ks) xb[ks] = *reinterpret_cast<const uint4*>(xr + 32 * ks);
         };
         load_x(p0);       // the first window this band completes; OLDEST in the queue: the first emit must not wait for the rows
         load_row(ys - 1, nxA); load_row(ys, nxB);
@@ -731,10 +645,7 @@ __global__ void __launch_bounds__(C * 2, WGS) block_tail_coop_kernel(const CoopP
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        if constexpr (STREAM_ABL & 4) { acc[i][0] += __uint_as_float(wq[ks][i].x ^ b[ks].x); acc[i][1] += __uint_as_float(wq[ks][i].y ^ b[ks].y); }
-                        else acc[i] = mma16<T>(wq[ks][i], b[ks], acc[i]);
-                    }
+                    for (int i = 0; i < 2; ++i) acc[i] = mma16<T>(wq[ks][i], b[ks], acc[i]);
             }
             // ... next to the depthwise stage of row y + 1 (-> the other buffer)
             dws.template push<true>(tap, row, a_lane0 + (buf ^ 1) * A_BYTES, AST);
@@ -767,7 +678,7 @@ __global__ void __launch_bounds__(C * 2, WGS) block_tail_coop_kernel(const CoopP
             }
             {
                 const unsigned off = (do_emit && lane_out) ? obase + (unsigned)yo * (unsigned)(p.Wo * COUT * sizeof(T)) : 0xfffff000u;
-                if (!(STREAM_ABL & 1) || po[0] == 0x12345678u) __builtin_amdgcn_raw_buffer_store_b128(po, orsrc, (int)off, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(po, orsrc, (int)off, 0, 0);
             }
             // The shortcut operand of the NEXT regular emit (two steps on: windows complete on every other row), behind this
             // step's use of the registers.  vmcnt retires in order: fetched at the top of the emitting step itself, the wait
@@ -780,8 +691,7 @@ __global__ void __launch_bounds__(C * 2, WGS) block_tail_coop_kernel(const CoopP
                 for (int i = 0; i < 4; ++i) VM[i] = cur[i];
             }
             // row y + 1's A tile is complete, and row y's is read, when every wave is here: ONE LDS-only barrier per row
-            if constexpr (STREAM_ABL & 32) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         };
         // (input row y + 2 of the first step sits in set B, of the second in set A: see the prologue)
         // Steps come in pairs with STATIC roles -- A buffer, register set, and the parity of t = y + pt: a band starts on an even
@@ -914,21 +824,6 @@ int launch_block_tail(int dtype, int cin, int cout, int cx, const void* y1, cons
         };
         return dtype == 2 ? go3(f16_t{}) : go3(bf16_t{});
     }
-#ifdef TAIL2_COOP
-    {
-        auto go2 = [&](auto tag) {
-            typedef decltype(tag) T;
-            CoopParams<T> p;
-            p.in = reinterpret_cast<const T*>(y1); p.wp16 = reinterpret_cast<const uint4*>(wp16); p.dw = dw;
-            p.scale = scale; p.bias = bias;
-            p.x = reinterpret_cast<const T*>(x); p.wr16 = reinterpret_cast<const uint4*>(wr16); p.rscale = rscale; p.rbias = rbias;
-            p.out = reinterpret_cast<T*>(out);
-            p.n = n; p.H = H; p.W = W; p.Ho = p.Wo = p.nstrips = p.nbands = p.items = 0;
-            return launch_coop<T, 128, TAIL2_COOP>(p, num_cus, s);
-        };
-        return dtype == 2 ? go2(f16_t{}) : go2(bf16_t{});
-    }
-#endif
     auto go = [&](auto tag) {
         typedef decltype(tag) T;
         TailParams<T> p;

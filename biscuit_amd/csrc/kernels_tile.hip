@@ -19,22 +19,18 @@
 //  * Per tile the (8+2)x(16+2) input halo is loaded with all of a thread's 16-byte loads in
 //    flight at once, zero-filled outside the image ('same' padding for free), and the loads of
 //    tile t+1 are issued before tile t is computed (register prefetch across the tile loop).
-//  * No A tile: the MFMA operand layout D[cout][pixel] = W[cout][k] * Act[k][pixel] wants, per
-//    lane, 8 consecutive k of ONE pixel -- exactly one depthwise result (8 channels of a
-//    pixel) or, for the 3x3 stem conv, 16 bytes of a shifted halo pixel.  Each wave owns two
-//    tile rows (32 pixels = one 32x32 fragment) and feeds its depthwise results straight into
-//    its MFMAs: no LDS round trip, no barrier between the vector-ALU and matrix stages.
+//  * No A tile in the 3x3 conv: the MFMA operand layout D[cout][pixel] = W[cout][k] * Act[k][pixel]
+//    wants, per lane, 8 consecutive k of ONE pixel -- 16 bytes of a shifted halo pixel.  Each wave
+//    owns two tile rows (32 pixels = one 32x32 fragment) and reads its operands straight from the
+//    halo in LDS.  (The separable form below builds a wave-private A tile.)
 //  * Epilogue: folded BN + ReLU in registers, tile parked in LDS (aliasing the dead halo),
 //    streamed out as 16 x Cout x 2 B contiguous row segments.
 #include "gemm_common.h"
-
-#include <stdlib.h>
 
 namespace {
 using namespace bqk;
 
 constexpr int TH = 8, TW = 16, RH = TH + 2, RW = TW + 2, RPIX = RH * RW;   // 180 halo pixels
-enum { MODE_CONV3 = 0, MODE_SEP = 1 };
 
 typedef float f32x2t __attribute__((ext_vector_type(2)));
 
@@ -44,7 +40,7 @@ template <typename T>
 struct TileParams {
     const T* in;           // NHWC [n][Hi][Wi][CIN]
     const uint4* wp;       // fragment-packed weights [NF][KB][64] x 16 B
-    const float* dw;       // [9][CIN] fp32 (MODE_SEP)
+    const float* dw;       // [9][CIN] fp32 (tile_sep2*_kernel)
     const float* scale;    // [NF*32]
     const float* bias;
     T* out;                // NHWC [n][H][W][NF*32]; tile_sep2p_kernel: [n][H][W][ldo]
@@ -56,9 +52,8 @@ struct TileParams {
                            // schedule hipcc found when this field sat in the middle of its kernel arguments.
 };
 
-// WPE = waves per SIMD the register budget is set for (= persistent workgroups per CU): measured 0.68 -> 0.57 ms
-// for the 64 -> 128 layer at 3 (its LDS footprint allows 3 workgroups); the 128 -> 128 layer's LDS allows 2.
-template <typename T, int MODE, int CIN, int NF, bool RELU_IN, int WPE>
+// 3x3 valid convolution (block1_conv2).  WPE = waves per SIMD the register budget is set for (= persistent workgroups per CU).
+template <typename T, int CIN, int NF, bool RELU_IN, int WPE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 tile_conv_kernel(const TileParams<T> p) {
     if constexpr (H16<T>::F16) bq_f16_saturate();
@@ -71,34 +66,26 @@ tile_conv_kernel(const TileParams<T> p) {
     // 0-3/12-15 of one tile row with 4-11 of the next; with pitch = 0 (mod 16 slots) the second
     // row lands exactly on the slots the first leaves free (measured 24 % conflict cycles before)
     constexpr int RP = (RW * PS + 255) / 256 * 256;
-    constexpr int KB = (MODE == MODE_CONV3 ? 9 * CIN : CIN) / 16;
+    constexpr int KB = 9 * CIN / 16;
     constexpr int KBP = KB / NPASS;                    // k-blocks per pass
     constexpr int NLOAD = (RPIX * PPP + NT - 1) / NT;  // raw 16-byte loads per thread and pass
     constexpr int N = NF * 32;
     constexpr int SST = N * 2 + 16;                    // staging row stride
     constexpr int W_BYTES = NF * KB * 1024;
-    constexpr int TAP_BYTES = MODE == MODE_SEP ? 9 * CIN * 4 : 0;
-    // folded-BN scale | bias as fp32 [2][N] in LDS -- except for the 64->128 instance, whose three workgroups
-    // per CU leave no room for it (LDS is handed out in 1280-byte granules: +1 KB costs the third workgroup)
+    // folded-BN scale | bias as fp32 [2][N] in LDS -- unless three workgroups per CU leave no room for it (LDS is
+    // handed out in 1280-byte granules: +1 KB can cost the third workgroup)
     constexpr bool SB_LDS = WPE < 3;
-    constexpr int SB_OFF = W_BYTES + TAP_BYTES;
+    constexpr int SB_OFF = W_BYTES;
     constexpr int BUF_OFF = SB_OFF + (SB_LDS ? 2 * N * 4 : 0);   // raw halo / output staging share this region
-    static_assert(MODE == MODE_SEP || NPASS == 1, "the 3x3 conv stages all its channels at once");
+    static_assert(NPASS == 1, "the 3x3 conv stages all its channels at once");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r32 = lane & 31, h = lane >> 5;
 
-    // ---- one-time: weights (fragment order) and depthwise taps -> LDS
+    // ---- one-time: weights (fragment order) -> LDS
     for (int i = tid; i < W_BYTES / 16; i += NT)
         *reinterpret_cast<uint4*>(smem + i * 16) = p.wp[i];
-    if (MODE == MODE_SEP) {
-        for (int i = tid * 4; i < 9 * CIN; i += NT * 4) {
-            const float4 wv = *reinterpret_cast<const float4*>(p.dw + i);
-            // (w0,w2,w1,w3): the order the packed-FMA depthwise consumes them in
-            *reinterpret_cast<float4*>(smem + W_BYTES + i * 4) = make_float4(wv.x, wv.z, wv.y, wv.w);
-        }
-    }
 
     if (SB_LDS) {
         for (int i = tid; i < N; i += NT) {
@@ -109,7 +96,6 @@ tile_conv_kernel(const TileParams<T> p) {
 
     const int tiles_per_img = p.tyn * p.txn;
     const int ntiles = p.n * tiles_per_img;
-    const int org = MODE == MODE_SEP ? -1 : 0;         // halo origin relative to the tile origin
 
     // tile-independent part of this thread's halo pieces: (ry, rx) and the element offset
     int rel[NLOAD], ryx[NLOAD];
@@ -127,7 +113,7 @@ tile_conv_kernel(const TileParams<T> p) {
         const int img = tile / tiles_per_img;
         const int trem = tile - img * tiles_per_img;
         const int ty = trem / p.txn, tx = trem - ty * p.txn;
-        const int gy0 = ty * TH + org, gx0 = tx * TW + org;
+        const int gy0 = ty * TH, gx0 = tx * TW;         // valid convolution: the halo starts at the tile origin
         const long long base = ((long long)(img * p.Hi + gy0) * p.Wi + gx0) * CIN + pass * CC;
 #pragma unroll
         for (int q = 0; q < NLOAD; ++q) {
@@ -166,7 +152,7 @@ tile_conv_kernel(const TileParams<T> p) {
         for (int pass = 0; pass < NPASS; ++pass) {
             __syncthreads();             // previous readers of the halo / staging region are done
             store_pass();
-            __syncthreads();             // halo (and, first time, weights/taps) visible
+            __syncthreads();             // halo (and, first time, weights) visible
             // next halo in flight while this one is computed
             if (pass + 1 < NPASS) load_pass(tile, pass + 1);
             else if (tile + (int)gridDim.x < ntiles) load_pass(tile + gridDim.x, 0);
@@ -174,35 +160,10 @@ tile_conv_kernel(const TileParams<T> p) {
 #pragma unroll 2
             for (int kl = 0; kl < KBP; ++kl) {
                 const int kb = pass * KBP + kl;
-                uint4 opnd;
-                if constexpr (MODE == MODE_CONV3) {
-                    // k = tap*CIN + channel: this k-block is 16 channels of one tap
-                    const int tap = (kb * 16) / CIN, c0 = (kb * 16) % CIN;
-                    const int dy = tap / 3, dx = tap - dy * 3;
-                    opnd = *reinterpret_cast<const uint4*>(smem + raw_lane + dy * RP + dx * PS + (c0 + h * 8) * 2);
-                } else {
-                    // depthwise 3x3 of 8 channels (piece 2*kl + h of this pass) of this lane's pixel
-                    const int wbase = W_BYTES + (2 * kb + h) * 32;
-                    const int rbase = raw_lane + (2 * kl + h) * 16;
-                    f32x2t aA = {0.f, 0.f}, aB = {0.f, 0.f}, aC = {0.f, 0.f}, aD = {0.f, 0.f};
-#pragma unroll
-                    for (int t = 0; t < 9; ++t) {
-                        const uint4 v = *reinterpret_cast<const uint4*>(smem + rbase + (t / 3) * RP + (t % 3) * PS);
-                        const float4 w0 = *reinterpret_cast<const float4*>(smem + wbase + t * CIN * 4);
-                        const float4 w1 = *reinterpret_cast<const float4*>(smem + wbase + t * CIN * 4 + 16);
-                        typedef H16<T> F;
-                        const f32x2t lo01 = {F::lo(v.x), F::lo(v.y)};
-                        const f32x2t hi01 = {F::hi(v.x), F::hi(v.y)};
-                        const f32x2t lo23 = {F::lo(v.z), F::lo(v.w)};
-                        const f32x2t hi23 = {F::hi(v.z), F::hi(v.w)};
-                        aA = __builtin_elementwise_fma((f32x2t){w0.x, w0.y}, lo01, aA);
-                        aB = __builtin_elementwise_fma((f32x2t){w0.z, w0.w}, hi01, aB);
-                        aC = __builtin_elementwise_fma((f32x2t){w1.x, w1.y}, lo23, aC);
-                        aD = __builtin_elementwise_fma((f32x2t){w1.z, w1.w}, hi23, aD);
-                    }
-                    const float a8[8] = {aA.x, aB.x, aA.y, aB.y, aC.x, aD.x, aC.y, aD.y};
-                    opnd = pack<T>(a8);
-                }
+                // k = tap*CIN + channel: this k-block is 16 channels of one tap
+                const int tap = (kb * 16) / CIN, c0 = (kb * 16) % CIN;
+                const int dy = tap / 3, dx = tap - dy * 3;
+                const uint4 opnd = *reinterpret_cast<const uint4*>(smem + raw_lane + dy * RP + dx * PS + (c0 + h * 8) * 2);
 #pragma unroll
                 for (int j = 0; j < NF; ++j) {
                     const uint4 wf = *reinterpret_cast<const uint4*>(smem + ((j * KB + kb) * 64 + lane) * 16);
@@ -255,22 +216,19 @@ tile_conv_kernel(const TileParams<T> p) {
     }
 }
 
-template <typename T, int MODE, int CIN, int NF, bool RELU_IN, int WPE>
+template <typename T, int CIN, int NF, bool RELU_IN, int WPE>
 int launch_tile(const TileParams<T>& p, int num_cus, hipStream_t s) {
-    constexpr int KB = (MODE == MODE_CONV3 ? 9 * CIN : CIN) / 16;
+    constexpr int KB = 9 * CIN / 16;
     constexpr size_t W_BYTES = (size_t)NF * KB * 1024;
-    constexpr size_t TAP_BYTES = MODE == MODE_SEP ? 9 * CIN * 4 : 0;
     constexpr size_t RAW_BYTES = (size_t)RH * ((RW * ((CIN < 64 ? CIN : 64) * 2 + 16) + 255) / 256 * 256);
     constexpr size_t STAGE_BYTES = (size_t)TH * TW * (NF * 64 + 16);
-    constexpr size_t lds = W_BYTES + TAP_BYTES + (WPE < 3 ? (size_t)NF * 32 * 8 : 0) + (RAW_BYTES > STAGE_BYTES ? RAW_BYTES : STAGE_BYTES);
+    constexpr size_t lds = W_BYTES + (WPE < 3 ? (size_t)NF * 32 * 8 : 0) + (RAW_BYTES > STAGE_BYTES ? RAW_BYTES : STAGE_BYTES);
     static_assert(lds <= 160 * 1024, "tile kernel LDS budget");
-    auto kern = tile_conv_kernel<T, MODE, CIN, NF, RELU_IN, WPE>;
+    auto kern = tile_conv_kernel<T, CIN, NF, RELU_IN, WPE>;
     static BqLdsAttr attr;
     if (const int e = attr.ensure(reinterpret_cast<const void*>(kern), lds)) return e;
     const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
-    static const int env_wgs = bq_exp_env("BQ_TILE_WGS") ? atoi(bq_exp_env("BQ_TILE_WGS")) : 0;
-    int wgs = per_cu > WPE ? WPE : per_cu;     // persistent workgroups per CU = waves per SIMD
-    if (env_wgs > 0 && env_wgs < wgs) wgs = env_wgs;
+    const int wgs = per_cu > WPE ? WPE : per_cu;     // persistent workgroups per CU = waves per SIMD
     const int ntiles = p.n * p.tyn * p.txn;
     int grid = num_cus * wgs;
     if (grid > ntiles) grid = ntiles;
@@ -279,11 +237,11 @@ int launch_tile(const TileParams<T>& p, int num_cus, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Second form of the separable tile kernel: depthwise with lane = CHANNEL PAIR and a sliding 3x3 window.
+// The separable tile kernel: depthwise with lane = CHANNEL PAIR and a sliding 3x3 window.
 //
-// In the kernel above a lane owns one pixel and eight channels, so for every tap it reads 16 B of halo and 32 B
-// of fp32 taps from LDS: 432 B per pixel and 8 channels, 6.9 KB per pixel at 128 channels -- the kernel is bound
-// by LDS bandwidth, two thirds of it tap vectors that are the same for every pixel.  Here a half-wave owns one
+// Its first form, the kernel above with a depthwise producer, had a lane own one pixel and eight channels, so for every tap
+// it read 16 B of halo and 32 B of fp32 taps from LDS: 432 B per pixel and 8 channels, 6.9 KB per pixel at 128 channels --
+// bound by LDS bandwidth, two thirds of it tap vectors that are the same for every pixel.  Here a half-wave owns one
 // row of the tile and its 32 lanes the 64 channels of a pass, two each: the nine tap pairs of a lane live in
 // registers for the whole pass, and walking along the row only the three halo values of the new column are read
 // (4 B each) -- 0.77 KB of LDS per pixel at 128 channels, and 15 instead of 27 vector instructions per pixel and
@@ -715,10 +673,10 @@ int launch_tile_conv_t(int kind, const void* in, const void* wp, const float* dw
     p.n = n; p.H = H; p.W = W; p.Hi = Hi; p.Wi = Wi;
     p.tyn = (H + TH - 1) / TH; p.txn = (W + TW - 1) / TW;
     p.relu = relu;
-    static const bool sep2 = bq_exp_env("BQ_TILE_SEP1") == nullptr;   // the lane = channel-pair form (default)
-    if (sep2 && kind == 1) return launch_tile_sep2<T, 64, 4, false>(p, num_cus, s);
-    if (sep2 && kind == 2) { p.ldo = 128; return launch_tile_sep2<T, 128, 4, false>(p, num_cus, s); }
-    if (sep2 && kind == 3) {
+    if (kind == 0) return launch_tile<T, 32, 2, false, 2>(p, num_cus, s);
+    if (kind == 1) return launch_tile_sep2<T, 64, 4, false>(p, num_cus, s);
+    if (kind == 2) { p.ldo = 128; return launch_tile_sep2<T, 128, 4, false>(p, num_cus, s); }
+    if (kind == 3) {
         // 128 -> 256 (block3_sepconv1, 74x74): the 128 -> 128 kernel twice, each launch its half of the output channels
         // (weights, scale and bias of a half are contiguous; the pixel rows of the output are 256 channels apart).
         // The depthwise stage and the input read are done twice -- 0.58 ms on the pipelined kernel against 2 x 0.2 ms.
@@ -731,12 +689,6 @@ int launch_tile_conv_t(int kind, const void* in, const void* wp, const float* dw
             if (const int e = launch_tile_sep2<T, 128, 4, true>(q, num_cus, s)) return e;
         }
         return 0;
-    }
-    switch (kind) {
-        case 0: return launch_tile<T, MODE_CONV3, 32, 2, false, 2>(p, num_cus, s);
-        case 1: return launch_tile<T, MODE_SEP, 64, 4, false, 3>(p, num_cus, s);
-        case 2: return launch_tile<T, MODE_SEP, 128, 4, false, 2>(p, num_cus, s);
-        case 3: return launch_tile<T, MODE_SEP, 128, 8, true, 1>(p, num_cus, s);
     }
     return -1;
 }

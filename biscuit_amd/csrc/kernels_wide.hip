@@ -28,23 +28,13 @@
 // 32..79 loaded at the start of the epilogue, EVERY load before the first store (vmcnt retires in order and a store
 // retires ~1.8 k cycles after issue: a load behind a store cannot be consumed earlier; the first form of this epilogue,
 // loads and stores alternating, took 27 k cycles per tile instead of 11 k).
-// Measured (in-kernel stamps, tools/stamps_wide.py): chunks 3.0-3.3 k cycles each (the MFMAs alone: 1.92 k), the two
+// Measured (in-kernel stamps, round 3; experiments/r01-r04.md): chunks 3.0-3.3 k cycles each (the MFMAs alone: 1.92 k), the two
 // chunks after an epilogue 4-5 k (their weight loads queue behind its stores), epilogue 4 k without / 11 k with a
 // residual input; 51-55 k per tile against 58-66 k in round 2 -- 0.160 -> 0.148 ms per layer, bit-identical results.
 // Tap order and fp32 accumulation of the depthwise stage are those of every other producer in this library.
 #include "gemm_common.h"
 
-#include <stdio.h>
-
 #include <type_traits>
-#include <vector>
-
-#ifndef WIDE_ABLATE
-#define WIDE_ABLATE 0
-#endif
-#ifndef WIDE_ZERO_PAD
-#define WIDE_ZERO_PAD 1
-#endif
 
 namespace {
 using namespace bqk;
@@ -126,21 +116,7 @@ struct WideParams {
     int n;                  // images
     int relu;               // ReLU in the epilogue
     int nwg;                // persistent workgroups launched (a multiple of 8)
-#ifdef BQ_EXPERIMENTS
-    unsigned long long* stamps;   // s_memtime stamps [64 blocks from stamp_b0][wave][32] (diagnostic builds only)
-    unsigned stamp_b0;
-#endif
 };
-
-#ifdef BQ_EXPERIMENTS
-constexpr int STAMP_TILES = 8;        // tiles of a workgroup that get a row of 32 stamps each
-#define WSTAMP(ev) do { if (stp && stamp_it < STAMP_TILES) stp[stamp_it * 32 + (ev)] = __builtin_amdgcn_s_memtime(); } while (0)
-// the 100 MHz real-time counter next to the cycle counter: events 30 (tile start) and 31 (tile end) -> the in-kernel clock
-#define WSTAMP_RT(ev) do { if (stp && stamp_it < STAMP_TILES) stp[stamp_it * 32 + (ev)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define WSTAMP(ev) do { } while (0)
-#define WSTAMP_RT(ev) do { } while (0)
-#endif
 
 // One LDS-DMA instruction: lanes in `mask` copy 16 bytes each from sbase + voff to LDS at lds_dst + 16*lane.
 // Inline asm on purpose: a DMA the compiler can see makes it wait vmcnt(0) in front of every later LDS read.
@@ -386,13 +362,6 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
     const int nwg = gridDim.x;
     int vb = blockIdx.x;
 
-#ifdef BQ_EXPERIMENTS
-    // (a wave-uniform pointer: every lane stores the same stamp to the same address -- no per-lane registers)
-    unsigned long long* stp = (p.stamps && blockIdx.x >= p.stamp_b0 && blockIdx.x < p.stamp_b0 + 64)
-                                  ? p.stamps + ((blockIdx.x - p.stamp_b0) * WN + wave) * (32 * STAMP_TILES) : nullptr;
-    int stamp_it = 0;
-#endif
-    WSTAMP(0);
     // ---- per-lane constants (none depends on the tile) ---------------------------------------------------------
     // halo image: piece P = (wave + 8 t) * 64 + lane of the padded image (piece = slot * 8 + 16-byte part), i.e. LDS-DMA
     // instruction wave + 8 t covers pieces [64 (wave + 8t), + 64); the same P is the piece this thread zeroes when its slot
@@ -537,7 +506,6 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
             *reinterpret_cast<uint4*>(smem + OFF_RAW + RAW_BYTES + (wave + WN * t) * 1024 + voff) = make_uint4(0u, 0u, 0u, 0u);
         }
     }
-#if WIDE_ZERO_PAD
     // A rows past the tile's last pixel (76..79 of 80) are never written: whatever LDS held goes through the MFMAs of every k-step
     // and is thrown away.  Zeros cost the matrix pipe less energy than noise (the kernel runs against the power management).
     if constexpr (TR * IW < MT) {
@@ -547,14 +515,10 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
             *reinterpret_cast<uint4*>(smem + OFF_A + b * A_BYTES + TR * IW * A_STR + k * 16) = make_uint4(0u, 0u, 0u, 0u);
         }
     }
-#endif
     f32x4v acc[MF][RN];                                          // first written by the first k-step's MFMAs (C = 0)
 
-    WSTAMP(1);
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(HPW) : "memory");  // all but the DMAs of halo chunk 1 have landed
-    WSTAMP(2);
     __syncthreads();
-    WSTAMP(3);
     {   // D(0) of the first tile: nothing to overlap it with
         DwState<T> st;
         AwAddr<NSTEP - OOB0, NSTEP> aw0;
@@ -563,10 +527,8 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
         aw0.last = last_run;
         dw_ops<T, RELU, PW, KP, NSTEP, 0, NDW>(st, smem, opaque(opaque(raw_lane) + OFF_RAW), opaque(tap_lane), aw0);
     }
-    WSTAMP(4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // halo chunk 1
     __syncthreads();
-    WSTAMP(5);
 
     // ---- K loop ------------------------------------------------------------------------------------------------
     // iteration c: G(c) on A[c & 1]; D(c+1) from raw[(c+1) & 1] into A[(c+1) & 1]; DMA of halo chunk c+2 into raw[c & 1].
@@ -594,12 +556,10 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
         const int cd = c + 1 < NCH ? c + 1 : 0;                 // chunk the depthwise stage builds
         {
             const int cc = c + 2 < NCH ? c + 2 : c + 2 - NCH;   // chunk the DMA fetches (c >= NCH-2: of the next tile)
-#if !(defined(BQ_EXPERIMENTS) && (WIDE_ABLATE & 8))          // timing ablation (wrong results): 8 = no halo DMA in the loop
             if (c + 2 < NCH || has_next) {
                 if (c + 2 >= NCH) halo_zero(CUR);
                 halo_dma(cc, CUR);
             }
-#endif
         }
         if constexpr (has_res) { if (c < NRES) res_dma(c); }
         if constexpr (BPRE) {                                   // the next chunk's fragments (past the end: the next tile's first chunk)
@@ -625,42 +585,23 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
         static_for<0, KSC * MF * RN>([&](auto qc) {
             constexpr int Q = decltype(qc)::value;
             constexpr int D = Q / (MF * RN), J = (Q % (MF * RN)) / MF, I = Q % MF;
-#if !(defined(BQ_EXPERIMENTS) && (WIDE_ABLATE & 16))         // timing ablation (wrong results): 16 = no A-fragment reads
             if constexpr (Q == 0) {                             // A fragments of the chunk's first k-step
 #pragma unroll
                 for (int i = 0; i < MF; ++i) a[i] = *reinterpret_cast<const uint4*>(smem + a_cur + i * 16 * A_STR);
             }
-#else
-            if constexpr (Q == 0) {
-#pragma unroll
-                for (int i = 0; i < MF; ++i) asm volatile("" : "=v"(a[i].x), "=v"(a[i].y), "=v"(a[i].z), "=v"(a[i].w));
-            }
-#endif
-#if !(defined(BQ_EXPERIMENTS) && (WIDE_ABLATE & 2))          // timing ablations (wrong results): 2 = no depthwise
             if constexpr (DMODE == 1) dw_ops<T, RELU, PW, KP, NSTEP, dw_before<NSLOTQ, NDW>(Q), dw_before<NSLOTQ, NDW>(Q + 1)>(st, smem, raw_addr, tap_addr, awn);
             if constexpr (DMODE == 2) dw_ops<T, RELU, PW, KP, NSTEP, dw_before<NSLOTQ, NDW>(2 * Q), dw_before<NSLOTQ, NDW>(2 * Q + 2)>(st, smem, raw_addr, tap_addr, awn);
-#endif
-#if defined(BQ_EXPERIMENTS) && (WIDE_ABLATE & 96)           // 32 = no MFMA on the last m-fragment, 64 = none on n-fragments 4, 5 of six:
-            if constexpr (!(((WIDE_ABLATE & 32) && I == MF - 1 && MF == 5) || ((WIDE_ABLATE & 64) && RN == 6 && J >= 4)))   // what the padding costs
-#endif
-#if !(defined(BQ_EXPERIMENTS) && (WIDE_ABLATE & 4))          // 4 = no MFMA
             if constexpr (BPRE) mfma16_ab<T, FIRST && D == 0>(acc[I][J], bb[CUR][D][J], a[I]);
             else if constexpr (FIRST && D == 0) mfma16_first<T>(acc[I][J], bq[J], a[I]);
             else mfma16<T>(acc[I][J], bq[J], a[I]);
-#endif
-#if !(defined(BQ_EXPERIMENTS) && (WIDE_ABLATE & 1))          // 1 = weights stay in registers
             if constexpr (I == MF - 1 && !BPRE) {               // the fragment is dead: fetch it for the next k-step
                 const int nx = ks0 + D + 1;
                 bq[J] = load_b(nx < KST ? nx : 0, J);           // past the end: k-step 0, the next tile's first
             }
-#endif
-#if !(defined(BQ_EXPERIMENTS) && (WIDE_ABLATE & 16))
             if constexpr (J == RN - 1 && D + 1 < KSC)           // last use of this A fragment: fetch the next k-step's
                 a[I] = *reinterpret_cast<const uint4*>(smem + a_cur + I * 16 * A_STR + (D + 1) * 64);
-#endif
             __builtin_amdgcn_sched_barrier(0);                  // the source order of this loop IS the schedule
         });
-        WSTAMP(6 + c);
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(BPRE ? 0 : RN) : "memory");
         __syncthreads();
     };
@@ -675,8 +616,6 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
 
     for (;;) {
         has_next = vb + nwg < ntiles;
-        WSTAMP(18);
-        WSTAMP_RT(30);
         if constexpr (NCH > 2) {
             chunk(I0{}, K2{}, I1{}, std::true_type{}, 0);
             chunk(I1{}, K2{}, I1{}, std::false_type{}, 1);
@@ -715,7 +654,6 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
             asm volatile("" : BQ_ACC_ROW(7), BQ_ACC_ROW(8), BQ_ACC_ROW(MF - 1));
 #undef BQ_ACC_ROW
         }
-        WSTAMP(20);
         // ---- epilogue: folded BN (+ residual) (+ ReLU), 16-bit, straight from the accumulators to HBM -----------------
         {
             const unsigned lo2 = p.relu ? 0u : 0x80008000u;     // packed int16 max with 0 = ReLU, with -32768 = no-op
@@ -790,11 +728,6 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
                 }
             }
         }
-        WSTAMP(22);
-        WSTAMP_RT(31);
-#ifdef BQ_EXPERIMENTS
-        ++stamp_it;
-#endif
         if (!has_next) break;
         vb += nwg;
     }
@@ -870,35 +803,11 @@ int launch_sepconv_wide(int dtype, int prod, const GemmParams& g, const void* wp
     if (nwg < 8) nwg = 8;
     if (nwg > ntiles) nwg = ntiles;         // fewer tiles than CUs: one tile each (any count: nobody takes a second tile)
     p.nwg = nwg;
-#ifdef BQ_EXPERIMENTS
-    // BQ_STAMPS_WIDE=<file>: in-kernel s_memtime stamps of the first launch with (BQ_STAMPS_NORES: without) a residual
-    static const char* stamp_file = bq_exp_env("BQ_STAMPS_WIDE");
-    static const bool want_res = bq_exp_env("BQ_STAMPS_NORES") == nullptr;
-    static int state = 0;
-    static unsigned long long* d_stamps = nullptr;
-    p.stamps = nullptr;
-    p.stamp_b0 = bq_exp_env("BQ_STAMPS_B0") ? (unsigned)atoi(bq_exp_env("BQ_STAMPS_B0")) : 0u;
-    if (stamp_file && state == 0 && (p.residual != nullptr) == want_res && p.n >= 64 &&
-        hipMalloc(&d_stamps, 64 * WN * 32 * STAMP_TILES * 8) == hipSuccess) {
-        (void)hipMemsetAsync(d_stamps, 0, 64 * WN * 32 * STAMP_TILES * 8, s);
-        p.stamps = d_stamps;
-        state = 1;
-    }
-#endif
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * WN), lds, s, p);
     if (b13) {                              // the second 512 columns: weights 32 n-fragments on, tables and output 512 channels on
         p.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(wp16) + (size_t)NPlan<512>::NFT * 1024);
         p.scale += 512; p.bias += 512; p.out += 512;
         hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * WN), lds, s, p);
     }
-#ifdef BQ_EXPERIMENTS
-    if (state == 1) {
-        std::vector<unsigned long long> h(64 * WN * 32 * STAMP_TILES);
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h.data(), d_stamps, h.size() * 8, hipMemcpyDeviceToHost);
-        if (FILE* f = fopen(stamp_file, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-        state = 2;
-    }
-#endif
     return (int)hipGetLastError();
 }
