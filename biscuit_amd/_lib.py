@@ -31,6 +31,7 @@ _vp, _i, _i64, _u64, _sz, _f = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_s
 ABI = {
     'bq_create': (_vp, [_i, C.POINTER(BqConfig)]),
     'bq_destroy': (None, [_vp]),
+    'bq_set_dropout': (_i, [_vp, C.c_double]),
     'bq_last_error': (C.c_char_p, [_vp]),
     'bq_workspace_bytes': (_sz, [_vp, _i, _i]),
     'bq_load_weights': (_i, [_vp, _vp, _sz]),

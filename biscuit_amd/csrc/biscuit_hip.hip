@@ -31,7 +31,10 @@ struct GemmLayer {
     int nfp = 0;             // padded n-frags in wp
 };
 
-struct HeadLayer { const void* wh = nullptr; const void* wl = nullptr; const float* bias = nullptr; int k = 0; };
+struct HeadLayer {
+    const void* wh = nullptr; const void* wl = nullptr; const float* bias = nullptr; int k = 0;
+    int wexp = 0;                  // "hidden_N/wexp" of the blob: wh / wl hold W * 2^-wexp (weights.py: head_weight_exponent)
+};
 
 struct ProfRec { int cls; hipEvent_t a, b; };
 
@@ -50,6 +53,8 @@ struct bq_ctx {
     const void* front_wc16 = nullptr;
     const float* logits_w = nullptr; const float* logits_b = nullptr;
     HeadLayer head[2];             // hidden_0, hidden_1: weights split into two halves (kernels_head.hip)
+    unsigned drop_thresh = 0;      // the dropout contract of oracle/philox.py from the rate as a double (bq_set_dropout):
+    float drop_scale = 1.f;        // keep = r >= floor(rate * 2^32), y = x * fp32(1 / (1 - rate))
     bool loaded = false;
     int num_cus = 256;
     float* d_srgb_lut = nullptr;   // tables of the Reinhard normaliser
@@ -100,7 +105,7 @@ constexpr long long kMaxAct = 147LL * 147 * 128;
 constexpr long long kMaxRes = 74LL * 74 * 128;
 
 struct WsLayout {
-    size_t a, b, c, r, staged, feat, h0, h1, state, total;
+    size_t a, b, c, r, staged, feat, h0, h1, state, rmax, total;
 };
 
 WsLayout ws_layout(const bq_ctx* c, int n, int mc) {
@@ -124,6 +129,7 @@ WsLayout ws_layout(const bq_ctx* c, int n, int mc) {
     L.h0 = take(rows * 1024 * 4);
     L.h1 = take(rows * 1024 * 4);
     L.state = take((size_t)n * 5 * 4);
+    L.rmax = take(rows * 2 * 4);            // max |hidden_0| per row and column half (kernels_head.hip)
     L.total = off;
     return L;
 }
@@ -579,11 +585,9 @@ int head_impl(bq_ctx* c, const float* feat, int n, int64_t tile0, int mc_n, int 
     const WsLayout L = ws_layout(c, n, mc_n);
     float* h0 = (float*)(ws + L.h0);
     float* h1 = (float*)(ws + L.h1);
-    const double rate = (double)c->cfg.dropout;
-    double t = floor(rate * 4294967296.0);
-    if (t < 0) t = 0; if (t > 4294967295.0) t = 4294967295.0;
-    const unsigned thresh = (unsigned)t;
-    const float dscale = (float)(1.0 / (1.0 - rate));
+    float* rmax = (float*)(ws + L.rmax);
+    const unsigned thresh = c->drop_thresh;
+    const float dscale = c->drop_scale;
     const int rows = n * mc_n;
     for (int layer = 0; layer < 2; ++layer) {
         const HeadLayer& G = c->head[layer];
@@ -592,9 +596,9 @@ int head_impl(bq_ctx* c, const float* feat, int n, int64_t tile0, int mc_n, int 
         // three f16 MFMAs per fp32 product (kernels_head.hip): 6 x the nominal FLOPs of the layer
         ProfScope ps(c, s, layer == 0 ? "mc_head_dense0" : "mc_head_dense1", 2.0 * rows * (double)K * 1024,
                      4.0 * ((layer == 0 ? (double)n : (double)rows) * K + (double)rows * 1024 + (double)K * 1024));
-        const int e = launch_head_dense(layer == 0 ? feat : h0, G.wh, G.wl, G.bias, layer == 0 ? h0 : h1, rows, K, mc_n, pass0,
-                                        layer == 0 ? 1 : 0, layer, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), thresh,
-                                        dscale, tile0, c->d_tile0, c->d_tile_idx, s);
+        const int e = launch_head_dense(layer == 0 ? feat : h0, G.wh, G.wl, G.bias, G.wexp, layer == 0 ? h0 : h1, rmax, rows, K,
+                                        mc_n, pass0, layer == 0 ? 1 : 0, layer, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32),
+                                        thresh, dscale, tile0, c->d_tile0, c->d_tile_idx, s);
         if (e) return fail(c, BQ_ERR_HIP, std::string("head dense launch: ") + hipGetErrorString((hipError_t)e));
     }
     {
@@ -604,6 +608,13 @@ int head_impl(bq_ctx* c, const float* feat, int n, int64_t tile0, int mc_n, int 
             return fail(c, BQ_ERR_HIP, "head_final launch failed");
     }
     return BQ_OK;
+}
+
+// The dropout contract of oracle/philox.py for `rate` (checked by the callers: 0 <= rate < 1).
+void set_dropout(bq_ctx* c, double rate) {
+    const double t = floor(rate * 4294967296.0);
+    c->drop_thresh = t > 4294967295.0 ? 4294967295u : (unsigned)t;
+    c->drop_scale = (float)(1.0 / (1.0 - rate));
 }
 
 const float* entry_f32(bq_ctx* c, const std::string& name) {
@@ -678,6 +689,7 @@ bq_ctx* bq_create(int device_id, const bq_config* cfg) {
     DeviceGuard guard(device_id);            // allocations below go to the context's device; the caller's stays current
     if (!guard.ok) { g_create_error = "hipSetDevice failed"; delete c; return nullptr; }
     c->cfg = *cfg;
+    set_dropout(c, (double)cfg->dropout);
     c->device = device_id;
     c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     {   // tables of the Reinhard normaliser (oracle/stain.py states the same arithmetic):
@@ -724,6 +736,13 @@ bq_ctx* bq_create(int device_id, const bq_config* cfg) {
         return nullptr;
     }
     return c;
+}
+
+int bq_set_dropout(bq_ctx* c, double rate) {
+    if (!c) return fail(c, BQ_ERR_ARG, "bq_set_dropout: null context");
+    if (!(rate >= 0.0) || !(rate < 1.0)) return fail(c, BQ_ERR_ARG, "bq_set_dropout: the rate must lie in [0, 1)");
+    set_dropout(c, rate);
+    return BQ_OK;
 }
 
 void bq_destroy(bq_ctx* c) {
@@ -820,7 +839,14 @@ int bq_load_weights(bq_ctx* c, const void* host_blob, size_t nbytes) {
         if (wh == c->entries.end() || wl == c->entries.end() || bi == c->entries.end() || wh->second.n != want ||
             wl->second.n != want || bi->second.n < 1024 * 4)
             return fail(c, BQ_ERR_WEIGHTS, "missing or malformed head tensors of " + name);
-        c->head[layer] = HeadLayer{wh->second.p, wl->second.p, reinterpret_cast<const float*>(bi->second.p), K};
+        int wexp = 0;
+        auto we = c->entries.find(name + "/wexp");
+        if (we != c->entries.end()) {
+            if (we->second.n < 4) return fail(c, BQ_ERR_WEIGHTS, "bad size for " + name + "/wexp");
+            memcpy(&wexp, hb + (we->second.p - c->d_blob), 4);
+            if (wexp < -64 || wexp > 64) return fail(c, BQ_ERR_WEIGHTS, name + "/wexp must lie in [-64, 64]");
+        }
+        c->head[layer] = HeadLayer{wh->second.p, wl->second.p, reinterpret_cast<const float*>(bi->second.p), K, wexp};
     }
     c->loaded = true;
     return BQ_OK;

@@ -131,9 +131,10 @@ int launch_pool_add(const void* y, const void* res, void* out, int n, int Hi, in
 int launch_respool(int dtype, const void* x, const void* wp32, const float* scale, const float* bias, const void* y, void* out,
                    int n, int Hi, int Wi, int K, int ldx, int ld, int nf32, hipStream_t s);
 int launch_gap(const void* x, int n, int HW, int C, int ld, float* feat, float mul, int dtype, hipStream_t s);
-int launch_head_dense(const float* in, const void* wh, const void* wl, const float* bias, float* out, int rows, int K,
-                      int mc_n, int pass0, int in_row_is_tile, int layer, unsigned seed_lo, unsigned seed_hi, unsigned thresh,
-                      float dscale, long long tile0, const long long* tile0_dev, const long long* tile_idx, hipStream_t s);
+int launch_head_dense(const float* in, const void* wh, const void* wl, const float* bias, int wexp, float* out, float* rmax,
+                      int rows, int K, int mc_n, int pass0, int in_row_is_tile, int layer, unsigned seed_lo, unsigned seed_hi,
+                      unsigned thresh, float dscale, long long tile0, const long long* tile0_dev, const long long* tile_idx,
+                      hipStream_t s);
 int launch_head_final(const float* h1, int n, int mc_n, int pass0, long long tile0, const long long* tile0_dev, const long long* tile_idx,
                       unsigned seed_lo, unsigned seed_hi, unsigned thresh, float dscale,
                       const float* w2, const float* b2, int init, int finalize, float* state,

@@ -17,6 +17,20 @@
 // key = seed: the contract of oracle/philox.py), applies the inverted dropout, splits and writes the two A planes to
 // LDS; the matrix stage reads A fragments from LDS and streams the pre-split weight fragments (host-packed hi / lo in
 // fragment order) from L2 through a register ring.
+//
+// Range.  The split is fp32-grade only for about 2^-14 <= |v| < 2^16: below, hi and lo turn subnormal and lose bits; above,
+// both saturate (MODE.FP16_OVFL) and 1e5 would be read as 65536.  So both operands carry power-of-two exponents:
+//   * per row, e: the producer multiplies by dscale * 2^-e instead of dscale.  Layer 0 takes e from max |x| * dscale of the
+//     row's feature row (a prologue over the 1-64 tiles of the workgroup); layer 1 from max |h0| * dscale, which the layer-0
+//     epilogue leaves in rmax[row][column half];
+//   * per layer, s: the weights are stored as W * 2^-s (weights.py: head_weight_exponent, "hidden_N/wexp" of the blob).
+// The epilogue multiplies the accumulator by 2^(e + s) before the bias.  Both scalings are exact.  An exponent is 0 whenever
+// its peak lies in [2^-8, 2^14] (today's networks: the same bits as without exponents); otherwise it brings the peak to
+// [2^13, 2^14).
+//
+// Non-finite operands.  The f16 MFMAs do not carry a NaN operand into the sum (a NaN feature acted as 0; an inf one gave inf,
+// its NaN lo part dropped), so the producer notes a kept operand that is not finite (fma(f, 0, nf) turns NaN once one is met)
+// and the epilogue writes NaN for the whole row; the ReLU passes NaN through.  A non-finite input never gives a plausible result.
 #include "gemm_common.h"
 
 namespace {
@@ -27,6 +41,8 @@ constexpr float HSCALE = 2048.f, HINV = 1.f / 2048.f;
 
 struct HeadParams {
     const float* in;        // [tiles][K] (in_row_is_tile) or [rows][K]
+    const float* rmax_in;   // layer 1: [rows][2] max |h0| per row and column half (written by layer 0), else null
+    float* rmax_out;        // layer 0: where to write it, else null
     const uint4* wh;        // f16(W) in fragment order [1024 / 32][K / 16][64] x 16 B
     const uint4* wl;        // f16((W - hi) * 2^11), same order
     const float* bias;      // [1024]
@@ -35,10 +51,25 @@ struct HeadParams {
     int mc_n, pass0, in_row_is_tile, layer;
     unsigned seed_lo, seed_hi, thresh;
     float dscale;
+    int wexp;               // the weights are stored as W * 2^-wexp
     long long tile0;
     const long long* tile0_dev;
     const long long* tile_idx;  // per-tile Philox indices [tiles] (bq_set_tile_index_array) or null: tile i counts as tile0 + i
 };
+
+// Power-of-two exponent of a row whose largest split operand is `peak`: 0 in [2^-8, 2^14] (and for 0, NaN, inf), else the e that
+// brings the peak to [2^13, 2^14), within [-64, 64] so that dscale * 2^-e stays a normal float.
+__device__ __forceinline__ int head_row_exp(float peak) {
+    if (!(peak > 0.f) || !__builtin_isfinite(peak) || (peak >= 0x1p-8f && peak <= 0x1p14f)) return 0;
+    const int e = ilogbf(peak) - 13;
+    return e < -64 ? -64 : (e > 64 ? 64 : e);
+}
+
+// ReLU that keeps NaN (fmaxf(NaN, 0) is 0); the same bits as fmaxf(v, 0) otherwise.
+__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
+__device__ __forceinline__ float max4(float4 v) { return fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)); }
+__device__ __forceinline__ float4 fabs4(float4 v) { return make_float4(fabsf(v.x), fabsf(v.y), fabsf(v.z), fabsf(v.w)); }
 
 __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
     hi = H16<f16_t>::pack2(a, b);
@@ -72,6 +103,35 @@ __global__ void __launch_bounds__(512) head_dense_pipe_kernel(const HeadParams p
     const unsigned pctr = (unsigned)(tile0 + (p.tile_idx ? p.tile_idx[ptile] : (long long)ptile));   // the Philox tile counter of this row
     const float* prow_ptr = p.in + (size_t)(p.in_row_is_tile ? ptile : (plive ? pm : 0)) * p.K;
 
+    // Row exponents (see the header).  Layer 0: max |x| of each of the tiles the 64 rows belong to, one tile per pass of the
+    // whole workgroup over its K / 4 float4 (K / 4 is a multiple of 64, so every wave stays on one tile and loops as a whole).
+    __shared__ int rexp[HM];
+    __shared__ int rbad[HM];                        // the row met a kept operand that is not finite
+    if (tid < HM) rbad[tid] = 0;
+    if (p.in_row_is_tile) {
+        __shared__ unsigned tmax[HM];               // float bits of non-negative maxima order as unsigned integers
+        const int t0 = m0 / p.mc_n;
+        const int nt = ((m0 + HM < p.rows ? m0 + HM : p.rows) - 1) / p.mc_n - t0 + 1;
+        const int kq = p.K >> 2;
+        if (tid < HM) tmax[tid] = 0u;
+        __syncthreads();
+        for (int j = tid; j < nt * kq; j += 512) {
+            const int lt = j / kq;
+            float a = max4(fabs4(*reinterpret_cast<const float4*>(p.in + (size_t)(t0 + lt) * p.K + (size_t)(j - lt * kq) * 4)));
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o));
+            if (lane == 0) atomicMax(&tmax[lt], __float_as_uint(a));
+        }
+        __syncthreads();
+        if (tid < HM) rexp[tid] = m0 + tid < p.rows ? head_row_exp(__uint_as_float(tmax[(m0 + tid) / p.mc_n - t0]) * p.dscale) : 0;
+    } else if (tid < HM) {
+        const int m = m0 + tid;
+        rexp[tid] = m < p.rows ? head_row_exp(fmaxf(p.rmax_in[2 * (size_t)m], p.rmax_in[2 * (size_t)m + 1]) * p.dscale) : 0;
+    }
+    __syncthreads();
+    const float pscale = ldexpf(p.dscale, -rexp[prow]);     // dscale * 2^-e of the producer's row (exact)
+    float nf = 0.f;                                          // NaN once a kept operand of this thread was not finite
+
     f32x16 acc1[2][2], acc2[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -102,10 +162,11 @@ __global__ void __launch_bounds__(512) head_dense_pipe_kernel(const HeadParams p
             const int g = (k0 >> 2) + gi;
             unsigned rnd[4];
             philox4x32_10((unsigned)g, (unsigned)p.layer, (unsigned)ppass, pctr, p.seed_lo, p.seed_hi, rnd);
-            const float f0 = (plive && rnd[0] >= p.thresh) ? v[i].x * p.dscale : 0.f;
-            const float f1 = (plive && rnd[1] >= p.thresh) ? v[i].y * p.dscale : 0.f;
-            const float f2 = (plive && rnd[2] >= p.thresh) ? v[i].z * p.dscale : 0.f;
-            const float f3 = (plive && rnd[3] >= p.thresh) ? v[i].w * p.dscale : 0.f;
+            const float f0 = (plive && rnd[0] >= p.thresh) ? v[i].x * pscale : 0.f;
+            const float f1 = (plive && rnd[1] >= p.thresh) ? v[i].y * pscale : 0.f;
+            const float f2 = (plive && rnd[2] >= p.thresh) ? v[i].z * pscale : 0.f;
+            const float f3 = (plive && rnd[3] >= p.thresh) ? v[i].w * pscale : 0.f;
+            nf = fmaf(f0, 0.f, fmaf(f1, 0.f, fmaf(f2, 0.f, fmaf(f3, 0.f, nf))));
             uint2 hi, lo;
             split2(f0, f1, hi.x, lo.x);
             split2(f2, f3, hi.y, lo.y);
@@ -113,6 +174,7 @@ __global__ void __launch_bounds__(512) head_dense_pipe_kernel(const HeadParams p
             *reinterpret_cast<uint2*>(base + off) = hi;
             *reinterpret_cast<uint2*>(base + PPLANE + off) = lo;
         }
+        if (nf != nf) rbad[prow] = 1;                        // (read after the loop's last barrier)
     };
     auto multiply = [&](int k0, int buf) {
         const unsigned char* a_hi = smem + buf * 2 * PPLANE + r32 * PSTR + h * 16;
@@ -160,6 +222,14 @@ __global__ void __launch_bounds__(512) head_dense_pipe_kernel(const HeadParams p
         }
         __syncthreads();
     }
+    int oexp[2];                                    // 2^(e + s) of the two rows this lane writes
+    bool bad[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        oexp[i] = rexp[i * 32 + r32] + p.wexp;
+        bad[i] = rbad[i * 32 + r32] != 0;
+    }
+    float rmax[2] = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -171,26 +241,48 @@ __global__ void __launch_bounds__(512) head_dense_pipe_kernel(const HeadParams p
                 const int m = m0 + i * 32 + r32;
                 if (m < p.rows) {
                     float4 o;
-                    o.x = fmaxf(fmaf(acc2[i][j][g * 4 + 0], HINV, acc1[i][j][g * 4 + 0]) + b.x, 0.f);
-                    o.y = fmaxf(fmaf(acc2[i][j][g * 4 + 1], HINV, acc1[i][j][g * 4 + 1]) + b.y, 0.f);
-                    o.z = fmaxf(fmaf(acc2[i][j][g * 4 + 2], HINV, acc1[i][j][g * 4 + 2]) + b.z, 0.f);
-                    o.w = fmaxf(fmaf(acc2[i][j][g * 4 + 3], HINV, acc1[i][j][g * 4 + 3]) + b.w, 0.f);
+                    o.x = relu_nan(ldexpf(fmaf(acc2[i][j][g * 4 + 0], HINV, acc1[i][j][g * 4 + 0]), oexp[i]) + b.x);
+                    o.y = relu_nan(ldexpf(fmaf(acc2[i][j][g * 4 + 1], HINV, acc1[i][j][g * 4 + 1]), oexp[i]) + b.y);
+                    o.z = relu_nan(ldexpf(fmaf(acc2[i][j][g * 4 + 2], HINV, acc1[i][j][g * 4 + 2]), oexp[i]) + b.z);
+                    o.w = relu_nan(ldexpf(fmaf(acc2[i][j][g * 4 + 3], HINV, acc1[i][j][g * 4 + 3]), oexp[i]) + b.w);
+                    if (bad[i]) o = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
                     *reinterpret_cast<float4*>(p.out + (size_t)m * 1024 + n0) = o;
+                    rmax[i] = fmaxf(rmax[i], max4(o));
                 }
             }
         }
+    if (p.rmax_out) {
+        // max over this workgroup's 512 columns of each row: the two lane halves, then the eight waves through LDS (the A planes
+        // are free since the loop's last barrier)
+        float* red = reinterpret_cast<float*>(smem);          // [8 waves][64 rows]
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            rmax[i] = fmaxf(rmax[i], __shfl_xor(rmax[i], 32));
+            if (h == 0) red[wave * HM + i * 32 + r32] = rmax[i];
+        }
+        __syncthreads();
+        if (tid < HM && m0 + tid < p.rows) {
+            float r = red[tid];
+#pragma unroll
+            for (int w = 1; w < 8; ++w) r = fmaxf(r, red[w * HM + tid]);
+            p.rmax_out[2 * (size_t)(m0 + tid) + blockIdx.y] = r;
+        }
+    }
 }
 
 }  // namespace
 
 // One Dense(1024, relu) layer of the MC head over `rows` = tiles x passes rows.  K = 2048 (layer 0) or 1024 (layer 1).
-int launch_head_dense(const float* in, const void* wh, const void* wl, const float* bias, float* out, int rows, int K,
-                      int mc_n, int pass0, int in_row_is_tile, int layer, unsigned seed_lo, unsigned seed_hi, unsigned thresh,
-                      float dscale, long long tile0, const long long* tile0_dev, const long long* tile_idx, hipStream_t s) {
+// Layer 0 (in_row_is_tile) writes rmax [rows][2], layer 1 reads it (see the header).
+int launch_head_dense(const float* in, const void* wh, const void* wl, const float* bias, int wexp, float* out, float* rmax,
+                      int rows, int K, int mc_n, int pass0, int in_row_is_tile, int layer, unsigned seed_lo, unsigned seed_hi,
+                      unsigned thresh, float dscale, long long tile0, const long long* tile0_dev, const long long* tile_idx,
+                      hipStream_t s) {
     if (rows <= 0) return 0;
-    if (K % PKC != 0 || !wh || !wl || !bias) return (int)hipErrorInvalidValue;
+    if (K % PKC != 0 || !wh || !wl || !bias || !rmax) return (int)hipErrorInvalidValue;
     HeadParams p;
-    p.in = in; p.wh = reinterpret_cast<const uint4*>(wh); p.wl = reinterpret_cast<const uint4*>(wl);
+    p.in = in; p.rmax_in = in_row_is_tile ? nullptr : rmax; p.rmax_out = in_row_is_tile ? rmax : nullptr; p.wexp = wexp;
+    p.wh = reinterpret_cast<const uint4*>(wh); p.wl = reinterpret_cast<const uint4*>(wl);
     p.bias = bias; p.out = out; p.rows = rows; p.K = K;
     p.mc_n = mc_n; p.pass0 = pass0; p.in_row_is_tile = in_row_is_tile; p.layer = layer;
     p.seed_lo = seed_lo; p.seed_hi = seed_hi; p.thresh = thresh; p.dscale = dscale;

@@ -324,8 +324,9 @@ __global__ void __launch_bounds__(64 * kHeadFinalWaves) head_final_kernel(const 
         if (finalize) {
             mean2[tile * 2] = mu0;
             mean2[tile * 2 + 1] = mu1;
-            std2[tile * 2] = sqrtf(fmaxf(q0, 0.f) / cnt);      // population std (ddof = 0)
-            std2[tile * 2 + 1] = sqrtf(fmaxf(q1, 0.f) / cnt);
+            // population std (ddof = 0); a NaN tile keeps its NaN (fmaxf(NaN, 0) would report 0)
+            std2[tile * 2] = sqrtf((q0 != q0 ? q0 : fmaxf(q0, 0.f)) / cnt);
+            std2[tile * 2 + 1] = sqrtf((q1 != q1 ? q1 : fmaxf(q1, 0.f)) / cnt);
         }
     }
 }

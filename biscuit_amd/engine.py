@@ -70,6 +70,7 @@ class Engine:
         self._ctx = self._lib.bq_create(self.device.index, C.byref(cfg))
         if not self._ctx:
             raise BiscuitHipError('bq_create: ' + self._lib.bq_last_error(None).decode())
+        self._check(self._lib.bq_set_dropout(self._ctx, float(self.hp.dropout)))     # the contract's rate is a double
         # activation exponents (weights.py: choose_act_exponents / Engine.calibrate): the f16 mode's range by construction
         self.act_exp = {t: int(k) for t, k in (act_exp or {}).items() if int(k)} if dtype == 'f16' else {}
         self._tap_exp = {tap: self.act_exp.get(t, 0) for t, taps in tensor_taps().items() for tap in taps}

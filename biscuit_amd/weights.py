@@ -212,11 +212,26 @@ HEAD_SPLIT_SCALE = 2048.0          # 2^11: kernels_head.hip HSCALE
 
 
 def split_f16(a):
-    """float32 -> (hi, lo) IEEE-half bit patterns with a ~= hi + lo / 2^11: hi = f16(a), lo = f16((a - hi) * 2^11)."""
+    """float32 -> (hi, lo) IEEE-half bit patterns with a ~= hi + lo / 2^11: hi = f16(a), lo = f16((a - hi) * 2^11).
+
+    The pair carries 22 significand bits -- fp32 grade -- only for about 2^-14 <= |a| < 2^16.  Below, hi and lo turn subnormal and
+    lose bits (relative error 1.5e-5 at 2^-20); from 65504 up both saturate, as the device's conversions do (MODE.FP16_OVFL), so
+    1e5 reads as 65536.  The head therefore stores its weights divided by 2^head_weight_exponent, which puts their peak in that
+    range."""
     a = np.ascontiguousarray(a, dtype=np.float32)
     hi = np.clip(a, -65504.0, 65504.0).astype(np.float16)
-    lo = ((a - hi.astype(np.float32)) * np.float32(HEAD_SPLIT_SCALE)).astype(np.float16)
+    lo = np.clip((a - hi.astype(np.float64)) * HEAD_SPLIT_SCALE, -65504.0, 65504.0).astype(np.float16)   # (exact in range)
     return hi.view(np.uint16), lo.view(np.uint16)
+
+
+def head_weight_exponent(k):
+    """Power-of-two exponent s of a head kernel (kernels_head.hip, "Range"): the device holds k * 2^-s as split_f16 halves and
+    multiplies the accumulator by 2^s.  0 when max |k| lies in [2^-8, 2^14] (or k is all zero); otherwise the s that brings the
+    peak to [2^13, 2^14), within [-64, 64]."""
+    peak = float(np.abs(np.asarray(k, np.float32)).max(initial=0.0))
+    if not np.isfinite(peak) or peak == 0.0 or 2.0 ** -8 <= peak <= 2.0 ** 14:
+        return 0
+    return int(np.clip(np.frexp(peak)[1] - 1 - 13, -64, 64))
 
 
 DTYPE_CODE = {'f32': 0, 'bf16': 1, 'f16': 2}      # BQ_DTYPE_* of include/biscuit_hip.h
@@ -470,12 +485,17 @@ def pack_blob(w, dtype='bf16', act_exp=None):
     # The head keeps fp32 ACCURACY regardless of the backbone dtype (MC std ~1e-2 must not be quantisation noise), at the
     # 16-bit matrix rate: every weight is split into two IEEE halves, w = hi + lo / 2^11 (22 significand bits; the scale
     # keeps lo out of the subnormals), both in 32x32x16 fragment order (kernels_head.hip multiplies three of the four
-    # hi / lo cross terms of x * w with fp32 accumulation).
+    # hi / lo cross terms of x * w with fp32 accumulation).  Weights whose peak leaves the range of that split are stored
+    # divided by 2^s, s = "<layer>/wexp" (head_weight_exponent; absent: 0, the blob of a network that fits as it is).
     for name, kin in (('hidden_0', 2048), ('hidden_1', 1024)):
-        p = pack_fragments(w[name + '/kernel'], kin, 8)
+        s_exp = head_weight_exponent(w[name + '/kernel'])
+        k = w[name + '/kernel'] if s_exp == 0 else np.ldexp(np.asarray(w[name + '/kernel'], np.float32), -s_exp).astype(np.float32)
+        p = pack_fragments(k, kin, 8)
         hi, lo = split_f16(p)
         add(name + '/wph', hi)
         add(name + '/wpl', lo)
+        if s_exp:
+            add(name + '/wexp', np.array([s_exp], np.int32))
         add(name + '/bias', _padvec(w[name + '/bias'].astype(np.float32), p.shape[0] * 32))
     add('logits/w', w['logits/kernel'].astype(np.float32))
     add('logits/bias', w['logits/bias'].astype(np.float32))

@@ -56,7 +56,8 @@ typedef struct bq_config {
     int32_t dtype;        /* BQ_DTYPE_*: storage/matrix-core type of the backbone activations */
     int32_t tile_px;      /* 299 (biscuit/hp.py:5) */
     int32_t n_classes;    /* 2 (LUAD vs LUSC) */
-    float dropout;        /* 0.1 (biscuit/hp.py:11) */
+    float dropout;        /* 0.1 (biscuit/hp.py:11); the default rate, taken as the double of this float: a caller
+                             with a double rate (0.3 is 0.30000001 as a float) passes it to bq_set_dropout */
     int32_t max_batch;    /* largest n any call will pass (sizes the workspace) */
     int32_t max_mc;       /* largest mc_n any call will pass */
 } bq_config;
@@ -64,6 +65,11 @@ typedef struct bq_config {
 /* Lifetime. */
 bq_ctx* bq_create(int device_id, const bq_config* cfg);
 void bq_destroy(bq_ctx* ctx);
+
+/* The dropout rate of the head, as a double (0 <= rate < 1, else BQ_ERR_ARG and the rate stays): the keep threshold
+ * floor(rate * 2^32) and the scale fp32(1 / (1 - rate)) of the mask contract (oracle/philox.py) are computed from it.  Applies
+ * to the launches enqueued after the call; bq_create sets it from cfg->dropout. */
+int bq_set_dropout(bq_ctx* ctx, double rate);
 const char* bq_last_error(bq_ctx* ctx); /* ctx may be NULL: last creation error */
 
 /* Bytes of device workspace bq_backbone/bq_mc_head/bq_mc_infer need for `batch` tiles
