@@ -19,7 +19,14 @@ all-gather of the slide (pred, sigma, n) table; ``value`` = S x T / max-over-ran
 
 mc_mode 'head' (default, reported as ``value``): backbone once per tile, the 30 stochastic
 passes run in the head -- bit-identical to 30 full passes because every dropout layer sits
-behind the global pool and BN is in inference mode.  Extra keys (N = 1 only, never the headline):
+behind the global pool and BN is in inference mode.
+
+A plain run sets up, calibrates the batches in flight, warms up, times the K steps, writes ``--dump-outputs``
+and prints the result line; nothing else.  ``--full`` adds the legs that take runs of their own: the per-kernel
+table and ``roofline`` (HIP events around every launch, rank 0) and, at N = 1, the extra keys below; config 3
+adds the run without the f16 range monitor (``range_monitor.cost_frac``) and the run that writes the tile table.
+``--no-profile`` / ``--no-extras`` / ``--no-cpu-baseline`` / ``--no-table`` drop single legs of a ``--full`` run.
+Extra keys (``--full``, N = 1 only, never the headline):
 ``full_mode_value`` (the reference's loop structure, 30 complete forward passes, same kernels),
 ``with_reinhard_value`` (hp.py:19's stain normaliser in the timed region), ``bf16_value`` / ``f32_value`` (the other
 storage types on the same loop), ``b1_latency`` (``UncertaintyInterface`` on one tile, results.py:257), ``tfrecords``
@@ -35,7 +42,7 @@ before this process has touched the GPU); under ``python -m torch.distributed.ru
 table ``evaluate`` returned.  Every dumped value is finite.
 Inputs depend only on the arguments (seeded tiles and Philox counters), so two builds can be compared output for output.
 
-usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mc 30] [--batch 256] [--workload cfg2|cfg3] [--dump-outputs DIR]
+usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mc 30] [--batch 256] [--workload cfg2|cfg3] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -99,6 +106,10 @@ def parse_args(argv=None):
                     help='batches in flight: independent contexts on HIP streams that own disjoint groups of XCDs (2 or 4)')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help="write the timed path's outputs (rank 0, last timed step) as DIR/<name>.npy for output comparisons")
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the legs that take runs of their own: other modes and storage types, '
+                         'stain normaliser, B=1 latency, TFRecord and host-memory inputs, per-kernel roofline, CPU baseline; '
+                         'config 3: the run without the range monitor and the run that writes the tile table')
     return ap.parse_args(argv)
 
 
@@ -293,16 +304,18 @@ def run(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    if args.workload == 'cfg3':
-        out = run_cfg3(args, rank, world, dev, pool_e, pool, barrier, max_over_ranks)
-        out['collective'] = coll
-        out['rccl_ranks'] = coll['rccl_ranks']
+    def report(out):
         if rank == 0:
             print(json.dumps(out))
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
-        return
+
+    if args.workload == 'cfg3':
+        out = run_cfg3(args, rank, world, dev, pool_e, pool, barrier, max_over_ranks)
+        out['collective'] = coll
+        out['rccl_ranks'] = coll['rccl_ranks']
+        return report(out)
 
     NSTEP = max(K, Wm, 8)                         # the per-kernel pass and the full-mode leg run up to 8 steps
     n_slides_local = (NSTEP * B + TILES_PER_SLIDE - 1) // TILES_PER_SLIDE + 1
@@ -411,9 +424,11 @@ def run(args):
             'hbm_frac_vs_measured_peak': per_gpu * BYTES_PER_TILE_BF16 / PEAK_HBM_MEASURED if args.dtype in HALF else None,
             'mfma_frac': per_gpu * flop_tile / (PEAK_BF16 if args.dtype in HALF else PEAK_F32),
             'bytes_per_tile': BYTES_PER_TILE_BF16, 'flop_per_tile': flop_tile}
+    if not args.full:                                   # a plain run ends at its headline
+        return report(out)
 
     solo = world == 1 and rank == 0
-    leg_s = {}                                          # wall seconds of the extra legs (what a default run spends where)
+    leg_s = {}                                          # wall seconds of the extra legs (what a --full run spends where)
     t_leg = time.perf_counter()
 
     def leg_done(name):
@@ -544,12 +559,7 @@ def run(args):
         leg_done('cpu_baseline')
     if leg_s:
         out['leg_seconds'] = leg_s
-
-    if rank == 0:
-        print(json.dumps(out))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    report(out)
 
 
 def run_cfg3(args, rank, world, dev, pool_e, pool, barrier, max_over_ranks):
@@ -597,18 +607,21 @@ def run_cfg3(args, rank, world, dev, pool_e, pool, barrier, max_over_ranks):
     assert int(res.slide_count.sum()) == NT and np.isfinite(res.slide_pred).all()
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, {'slide_pred': res.slide_pred, 'slide_unc': res.slide_unc, 'slide_count': res.slide_count})
+    monitor = {'checks': int(res.f16_checks), 'min_headroom': (None if not np.isfinite(res.f16_headroom) else float(res.f16_headroom))}
     # what the f16 range monitor costs (evaluate's default: the eight taps on eight tiles every 200 batches, no host sync): the same run
     # without it
-    barrier()
-    t0 = time.perf_counter()
-    evaluate(pool_e, slides, mc_n=args.mc, seed=1234, batch=B, mc_mode=args.mode, keep_tiles=False, rank=rank, world=world,
-             headroom_every=0)
-    barrier()
-    dt_nomon = max_over_ranks(time.perf_counter() - t0)
+    if args.full:
+        barrier()
+        t0 = time.perf_counter()
+        evaluate(pool_e, slides, mc_n=args.mc, seed=1234, batch=B, mc_mode=args.mode, keep_tiles=False, rank=rank, world=world,
+                 headroom_every=0)
+        barrier()
+        dt_nomon = max_over_ranks(time.perf_counter() - t0)
+        monitor.update(value_without=NT / dt_nomon, cost_frac=dt / dt_nomon - 1.0)
     # the same run WITH the path's product: the tile table streamed to disk while the GPU works (every rank its shard, closed before
     # the all-gather; rank 0 splices them into tile_predictions_eval.csv) -- rows written and the file closed inside the timed region
     table = None
-    if not args.no_table:
+    if args.full and not args.no_table:
         import shutil
         import tempfile
         # one directory all ranks of this run derive by themselves (no object collective): the rendezvous port names the run
@@ -647,8 +660,7 @@ def run_cfg3(args, rank, world, dev, pool_e, pool, barrier, max_over_ranks):
             'ms_per_step': dt / steps * 1e3, 'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None,
             'dtype': args.dtype, 'data': 'synthetic', 'seconds': dt,
             'with_table_value': table['with_table_value'] if table else None, 'tile_table': table,
-            'range_monitor': {'checks': int(res.f16_checks), 'min_headroom': (None if not np.isfinite(res.f16_headroom) else float(res.f16_headroom)),
-                              'value_without': NT / dt_nomon, 'cost_frac': dt / dt_nomon - 1.0},
+            'range_monitor': monitor,
             # the slide table every rank holds after the gather, as a digest: equal at every world size (Philox counters are global
             # tile indices, the slide sums order-free fixed point)
             'slide_table_sha256': __import__('hashlib').sha256(np.ascontiguousarray(res.slide_pred).tobytes()

@@ -151,6 +151,24 @@ def _json_line(p):
     return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
 
 
+def test_plain_bench_run_times_only_the_headline(tmp_path):
+    """`python bench.py --gpus 1` without --full: the headline, its dumped outputs and nothing that takes runs of its own;
+    --full (here without the TFRecord / storage-type / CPU legs) still adds the other MC mode and the per-kernel roofline."""
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'LOCAL_WORLD_SIZE')}
+    common = ['--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '16', '--mc', '5']
+    run = lambda *a: subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *common, *a], env=env, cwd=ROOT,     # noqa: E731
+                                    capture_output=True, text=True, timeout=600)
+    legs = {'full_mode_value', 'with_reinhard_value', 'bf16_value', 'f32_value', 'b1_latency', 'tfrecords', 'host_tiles',
+            'cpu_baseline', 'roofline', 'kernels', 'entry_side_ms', 'leg_seconds'}
+    plain = _json_line(run('--dump-outputs', str(tmp_path)))
+    assert plain['value'] > 0 and plain['steps'] == 2 and plain['warmup'] == 1 and plain['dtype'] == 'f16'
+    assert abs(plain['ms_per_step'] - 16 / plain['value'] * 1e3) < 1e-9 * plain['ms_per_step']     # one batch of 16 per step
+    assert not legs & set(plain), legs & set(plain)
+    assert sorted(os.listdir(tmp_path)) == sorted(f'{n}.npy' for n in ('tile_mean', 'tile_std', 'slide_pred', 'slide_unc', 'slide_count'))
+    full = _json_line(run('--full', '--no-extras', '--no-cpu-baseline'))
+    assert full['full_mode_value'] > 0 and full['kernels'] and full['roofline']['kernel'] and 'leg_seconds' in full
+
+
 # Ranks of the multi-rank rehearsal.  The suite keeps at most six processes on the GPU at a time, and this test's own process
 # holds it too: five ranks.  (Eight ranks -- BASELINE config 3's world -- run in tests/test_distributed.py
 # with stand-in engines, on the CPU.)
@@ -178,7 +196,7 @@ def test_multi_rank_rehearsal_on_one_gpu(tmp_path):
                          *common], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     w4 = _json_line(tr)
     assert w4['n_gpus'] == 4 and w4['steps'] == 2 and w4['collective']['ranks_seen'] == 4 and w4['value'] > 0
-    cfg3 = ['--workload', 'cfg3', '--slides', '19', '--tiles-per-slide', '24', '--ragged']
+    cfg3 = ['--workload', 'cfg3', '--slides', '19', '--tiles-per-slide', '24', '--ragged', '--full']     # --full: the tile-table run
     sn, s1 = _json_line(run('--gpus', str(n), *cfg3)), _json_line(run('--gpus', '1', *cfg3))
     assert sn['n_gpus'] == n and sn['config']['ragged'] and sum(sn['config']['slides_per_rank']) == 19
     assert sn['slide_table_sha256'] == s1['slide_table_sha256']

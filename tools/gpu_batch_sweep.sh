@@ -3,7 +3,7 @@
 # 256 persistent workgroups (153 -> 765 tiles = 3 each, 205 -> 1 025 = 4 each, 256 -> 1 280 = 5 each), per-tile time of the dominant kernel.
 cd ${GRAFT_REPO_ROOT:-.}
 for b in 256 205 153 102 256; do
-  timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 60 --batch $b --streams 1 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 60 --batch $b --streams 1 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 ks={k['name']:k for k in d['kernels']}

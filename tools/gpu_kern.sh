@@ -5,7 +5,7 @@ T=${1:-x}; N=${2:-2}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R; mkdir -p gpurun_out
 for i in $(seq 1 $N); do
-python bench.py --no-extras --no-cpu-baseline --steps 100 2>/dev/null | python -c "
+python bench.py --full --no-extras --no-cpu-baseline --steps 100 2>/dev/null | python -c "
 import json,sys
 j=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('value %.0f tiles/s  ms_per_step %.4f  entry_side_ms %.4f  streams %s' % (j['value'], j['ms_per_step'], j.get('entry_side_ms',0), j['config']['hip_streams']))

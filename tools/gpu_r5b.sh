@@ -21,7 +21,7 @@ cp biscuit_amd/libbiscuit_hip.so biscuit_amd/libKEEP.so
 for rep in 1 2 3; do
   for v in A B C; do
     cp biscuit_amd/lib$v.so biscuit_amd/libbiscuit_hip.so
-    timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 100 2>$O/err_$v.log | show "lds_$v rep$rep" >> $O/ab.log
+    timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 100 2>$O/err_$v.log | show "lds_$v rep$rep" >> $O/ab.log
   done
 done
 cp biscuit_amd/libKEEP.so biscuit_amd/libbiscuit_hip.so

@@ -4,7 +4,7 @@
 # WRITE_SIZE do not fit one pass: MI355X_MICROARCH.md, rocprofv3 PMC slots).
 TAG=${1:-r01}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-OUT=$R/gpurun_out/prof_$TAG
+OUT=${OUT:-$R/evidence}/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 BENCH="python3 $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-profile --no-extras --dtype ${2:-f16}"
