@@ -121,6 +121,10 @@ def main(argv=None):
                          "tiles/s on 16 cores)")
     ap.add_argument('--no-calibrate', action='store_true',
                     help='f16 with external weights: skip the activation-exponent calibration on the first tiles (the headroom check stays)')
+    ap.add_argument('--range-screen', action=argparse.BooleanOptionalAction, default=False,
+                    help='f16: screen every tile for the f16 range limit -- each tile is ranked on the GPU by how far its standardised '
+                         'input reaches and the riskiest of each interval go through the range taps; a run that would clamp stops with '
+                         'an error.  Off by default: it costs 0.9 %% of throughput against a bar of 0.5 %% (DESIGN.md section 4)')
     args = ap.parse_args(argv)
 
     if args.skip_existing and os.path.exists(os.path.join(args.out, 'tile_predictions_eval.csv')):
@@ -201,7 +205,8 @@ def main(argv=None):
     # the tile table streams to disk while the GPU works (every rank its shard; rank 0 splices them after the gather): the frame
     # is not kept in memory, the consumer reads the file -- as biscuit does (experiment.py:688-699)
     res = evaluate(pool, slides, outcome=args.outcome, mc_n=args.mc, seed=args.seed, batch=args.batch,
-                   save_dir=args.out, rank=rank, world=world, norm_fit=norm_fit, keep_tiles=False, normalizer=hp.normalizer)
+                   save_dir=args.out, rank=rank, world=world, norm_fit=norm_fit, keep_tiles=False, normalizer=hp.normalizer,
+                   range_screen=args.range_screen)
     if res.stain_passthrough:
         print(f'rank {rank}: the {hp.normalizer} normaliser passed {res.stain_passthrough} degenerate tile(s) through unchanged '
               f'(too little tissue or one colour)', file=sys.stderr, flush=True)

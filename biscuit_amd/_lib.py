@@ -49,6 +49,9 @@ ABI = {
     'bq_stain_lab_stats': (_i, [_vp, _vp, _i, _vp, _vp]),
     'bq_stain_macenko': (_i, [_vp, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),
     'bq_stain_macenko_stats': (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    'bq_range_ws_bytes': (_sz, [_i]),
+    'bq_range_key': (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    'bq_range_screen': (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     'bq_backbone': (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
     'bq_backbone_u8': (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
     'bq_mc_head': (_i, [_vp, _vp, _i, _i64, _i, _i, _u64, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -919,6 +919,32 @@ int bq_stain_macenko_stats(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_st
     return BQ_OK;
 }
 
+size_t bq_range_ws_bytes(int n) { return n < 0 ? 0 : range_ws_bytes(n); }
+
+int bq_range_key(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_key, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || (n > 0 && (!d_tiles || !d_key || !d_ws))) return fail(c, BQ_ERR_ARG, "bq_range_key: bad argument");
+    if (ws_bytes < range_ws_bytes(n)) return fail(c, BQ_ERR_ARG, "bq_range_key: scratch smaller than bq_range_ws_bytes(n)");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "range_key", 2.0 * n * kStaged, (double)n * kStaged);
+    if (launch_range_key(d_tiles, n, 299, d_ws, d_key, s)) return fail(c, BQ_ERR_HIP, "range key launch failed");
+    return BQ_OK;
+}
+
+int bq_range_screen(bq_ctx* c, const uint8_t* d_tiles, int n, int64_t tile_idx0, const int64_t* d_tile_idx, float* d_cand_key,
+                    int64_t* d_cand_idx, uint8_t* d_cand_tiles, int k, int filled, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || n > 2048 || (n > 0 && (!d_tiles || !d_cand_key || !d_cand_idx || !d_cand_tiles || !d_ws)))
+        return fail(c, BQ_ERR_ARG, "bq_range_screen: bad argument");
+    if (k < 1 || k > range_max_slots() || filled < 0 || filled > k)
+        return fail(c, BQ_ERR_ARG, "bq_range_screen: need 1 <= k <= " + std::to_string(range_max_slots()) + " and 0 <= filled <= k");
+    if (ws_bytes < range_ws_bytes(n)) return fail(c, BQ_ERR_ARG, "bq_range_screen: scratch smaller than bq_range_ws_bytes(n)");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "range_screen", 2.0 * n * kStaged, (double)n * kStaged);
+    if (launch_range_screen(d_tiles, n, 299, (long long)tile_idx0, reinterpret_cast<const long long*>(d_tile_idx), d_cand_key,
+                            reinterpret_cast<long long*>(d_cand_idx), d_cand_tiles, k, filled, d_ws, s))
+        return fail(c, BQ_ERR_HIP, "range screen launch failed");
+    return BQ_OK;
+}
+
 int bq_png_unfilter(bq_ctx* c, const uint8_t* d_rows, int n, int px, uint8_t* d_out, bq_stream_t stream) {
     if (!c || !d_rows || !d_out || n < 0 || px <= 0) return fail(c, BQ_ERR_ARG, "bq_png_unfilter: bad argument");
     if (launch_png_unfilter(d_rows, n, px, d_out, (hipStream_t)stream)) return fail(c, BQ_ERR_HIP, "png unfilter launch failed");

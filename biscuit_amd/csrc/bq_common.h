@@ -113,6 +113,13 @@ int launch_stage_stats(const uint8_t* tiles, int n, int px, double* stats_scratc
 // kernels_stain.hip: Macenko stain normalisation, one workgroup per tile (dst may be null: statistics only, or == tiles)
 int launch_macenko(const uint8_t* tiles, int n, int px, const float* he_ref6, const float* maxc_ref2, uint8_t* dst,
                    float* d_stats8, int* d_status, int status_stride, hipStream_t s);
+// kernels_screen.hip: the f16 range screen's key (bq_range_key) and its top-k candidate slots (bq_range_screen)
+size_t range_ws_bytes(int n);
+int range_max_slots();
+size_t range_select_lds(int filled, int n);
+int launch_range_key(const uint8_t* tiles, int n, int px, void* ws, float* key, hipStream_t s);
+int launch_range_screen(const uint8_t* tiles, int n, int px, long long tile_idx0, const long long* tile_idx, float* cand_key,
+                        long long* cand_idx, uint8_t* cand_tiles, int k, int filled, void* ws, hipStream_t s);
 int launch_front(int dtype, const uint8_t* tiles, const unsigned long long* stats, const void* ws16, const float* s_scale,
                  const float* s_bias, const void* wc16, const float* c_scale, const float* c_bias, void* out, int n, int num_cus,
                  hipStream_t s);

@@ -474,6 +474,17 @@ class Engine:
             rows.append(torch.stack([a.max(), (a >= limit).sum().to(torch.float32)]))
         return torch.stack(rows)
 
+    def range_key(self, tiles_u8):
+        """The range screen's key of every tile (``bq_range_key``): uint8 NHWC [n,299,299,3] (device, any byte offset) -> float32
+        [n] on the device, the largest |value| per-image standardisation gives the tile, max(hi - mu, mu - lo) / max(sd, 1/sqrt(N))
+        from its exact byte sums in float64."""
+        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous()
+        n = tiles_u8.shape[0]
+        key = torch.empty(n, dtype=torch.float32, device=self.device)
+        ws = torch.empty(self._lib.bq_range_ws_bytes(n), dtype=torch.uint8, device=self.device)
+        self._check(self._lib.bq_range_key(self._ctx, _ptr(tiles_u8), n, _ptr(key), _ptr(ws), ws.numel(), self._stream()))
+        return key
+
     # ------------------------------------------------------------------ profiling
     def profile_enable(self, on=True):
         self._check(self._lib.bq_profile_enable(self._ctx, 1 if on else 0))
@@ -483,6 +494,62 @@ class Engine:
         k = self._check(self._lib.bq_profile_read(self._ctx, arr, _lib.BQ_PROF_MAX))
         return [ProfileEntry(arr[i].name.decode(), arr[i].launches, arr[i].ms, arr[i].flops,
                              arr[i].bytes) for i in range(k)]
+
+
+class RangeScreen:
+    """The f16 range screen of one engine (``bq_range_screen``): ``k`` candidate slots on the engine's device
+    that keep the tiles with the largest ``Engine.range_key`` seen since the last ``reset()`` -- key, global tile index and the
+    tile's bytes -- ranked by (key desc, global index asc).  ``update`` enqueues on the current stream and never synchronises; the
+    number of filled slots is known on the host (min(k, tiles since the reset)), so ``tiles`` is a view without a device read.
+    ``screened`` counts the tiles that went through the key."""
+
+    MAX_BATCH = 2048
+
+    def __init__(self, engine, k=8, max_batch=None):
+        k = int(k)
+        if not 1 <= k <= 64:
+            raise ValueError(f'k must lie in [1, 64], not {k}')
+        max_batch = int(engine.max_batch if max_batch is None else max_batch)
+        if not 1 <= max_batch <= self.MAX_BATCH:
+            raise ValueError(f'max_batch must lie in [1, {self.MAX_BATCH}], not {max_batch}')
+        self.engine, self.k, self.max_batch = engine, k, max_batch
+        dev = engine.device
+        self.key = torch.empty(k, dtype=torch.float32, device=dev)
+        self.idx = torch.empty(k, dtype=torch.int64, device=dev)
+        self.slots = torch.empty((k, TILE_PX, TILE_PX, 3), dtype=torch.uint8, device=dev)
+        self._ws = torch.empty(engine._lib.bq_range_ws_bytes(max_batch), dtype=torch.uint8, device=dev)
+        self.filled = 0
+        self.screened = 0
+
+    def update(self, tiles, tile_idx0=0, tile_idx=None):
+        """Merge a batch (uint8 [n,299,299,3], device) into the slots; its global tile indices are ``tile_idx0 + row``, or
+        ``tile_idx`` (int64 [n], device) when given -- ``Engine.mc_infer``'s convention."""
+        assert tiles.dtype == torch.uint8 and tiles.is_cuda and tiles.is_contiguous() and tuple(tiles.shape[1:]) == (TILE_PX, TILE_PX, 3)
+        n = int(tiles.shape[0])
+        if n > self.max_batch:
+            raise ValueError(f'batch of {n} tiles exceeds the screen\'s max_batch {self.max_batch}')
+        if tile_idx is not None:
+            assert tile_idx.dtype == torch.int64 and tile_idx.is_cuda and tile_idx.is_contiguous() and tile_idx.numel() == n
+        if n == 0:
+            return
+        eng = self.engine
+        eng._check(eng._lib.bq_range_screen(eng._ctx, _ptr(tiles), n, int(tile_idx0), _ptr(tile_idx), _ptr(self.key), _ptr(self.idx),
+                                            _ptr(self.slots), self.k, self.filled, _ptr(self._ws), self._ws.numel(), eng._stream()))
+        self.filled = min(self.k, self.filled + n)
+        self.screened += n
+
+    def reset(self):
+        """Start a new interval: the slots count as empty (nothing is launched; the next update overwrites them in stream order)."""
+        self.filled = 0
+
+    @property
+    def tiles(self):
+        """The filled slots, uint8 [m,299,299,3] (a view)."""
+        return self.slots[:self.filled]
+
+    def candidates(self):
+        """(key float32 [m], global tile index int64 [m]) of the filled slots: device views, in slot order."""
+        return self.key[:self.filled], self.idx[:self.filled]
 
 
 class EnginePool:

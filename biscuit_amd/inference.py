@@ -203,6 +203,10 @@ class EvalResult:
     f16_headroom: float = float('inf')       # minimum over the run's range checks of 65504 / max |stored activation| (f16 engines)
     f16_checks: int = 0
     stain_passthrough: int = 0               # tiles of this rank the Macenko normaliser passed through unchanged (degenerate)
+    f16_screen_checks: int = 0               # range screen (evaluate(range_screen=True)): tap runs on the screened candidates
+    f16_screen_headroom: float = float('inf')    # ... the minimum of 65504 / max |stored activation| over them
+    f16_screened: int = 0                    # ... tiles of this rank that went through the key (0: the screen did not run)
+    f16_screen_max_key: float = 0.0          # ... the largest key among the candidates looked at
 
     def slide_frame(self, pred_thresh=0.5, level='slide'):
         """Group table in ``process_group_predictions`` form from the device-reduced means."""
@@ -561,7 +565,8 @@ class _TableStream:
 
 def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=None, batch=256,
              mc_mode='head', tile_uq=None, save_dir=None, keep_tiles=True, rank=0, world=1, norm_fit=None,
-             table_name=EVAL_NAME, table_writer='native', headroom_every=200, headroom_min=2.0, normalizer='reinhard_fast'):
+             table_name=EVAL_NAME, table_writer='native', headroom_every=200, headroom_min=2.0, normalizer='reinhard_fast',
+             range_screen=False):
     """Run MC-dropout inference over ``slides`` and return tile- and slide-level results.
 
     Every rank passes the SAME slide list; rank r processes ``partition_slides(...)[r]``.
@@ -579,6 +584,14 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
     maxima are copied out asynchronously and looked at when the next check is due (and at the end).  A value at the clamp, or
     less than ``headroom_min`` x of range left, raises ``F16RangeError``: the calibration batch at the start of a run says
     nothing about the 10^5 tiles behind it, and f16's clamp is silent.  ``EvalResult.f16_headroom`` = the minimum seen.
+
+    ``range_screen`` (f16 engines only): every tile of the run -- as the network sees it, after the stain
+    normaliser -- is ranked on the device by ``Engine.range_key`` (how far its standardised input reaches), each engine keeps the
+    eight riskiest of its interval in a ``RangeScreen``, and the same eight range taps run on THOSE tiles every ``headroom_every``
+    batches of that engine (0 / None: once, at the end) and on what is left at the end; the results are looked at one interval
+    late, like the sampling monitor's, and raise ``F16RangeError`` the same way, naming the candidates' slides, global tile indices
+    and keys.  No host synchronisation per batch, no result changes.  ``EvalResult.f16_screen_*`` / ``f16_screened`` report it.
+    With another dtype, or False, nothing is launched or allocated.
 
     ``norm_fit`` (``{'target_means': [3], 'target_stds': [3]}``, the block of that name in the model's
     params.json) switches on the `reinhard_fast` stain normaliser of hp.py:19 in front of the staging
@@ -623,6 +636,57 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
     # the f16 range monitor (see the docstring): checks in flight = (batch number, first global tile index, pinned [8, 2], event)
     monitor = bool(headroom_every) and all(getattr(e, 'dtype', None) == 'f16' and hasattr(e, 'f16_headroom_async') for e in engines)
     hr_pending, hr_state = [], {'min': float('inf'), 'checks': 0}
+    # the range screen (see the docstring): per engine its slots, its own batch count and its tap in flight
+    # (engine number, batch number, pinned [8, 2] tap result, pinned keys, pinned global indices, event)
+    screens = []
+    if range_screen and all(getattr(e, 'dtype', None) == 'f16' and hasattr(e, 'f16_headroom_async') for e in engines):
+        from .engine import RangeScreen
+        screens = [RangeScreen(e, k=min(8, e.max_batch), max_batch=batch) for e in engines]
+    sc_count, sc_pending = [0] * len(engines), [[] for _ in engines]
+    sc_state = {'min': float('inf'), 'checks': 0, 'max_key': 0.0}
+
+    def screen_tap(k, eng, nb):
+        scr = screens[k]
+        if not scr.filled:
+            return
+        hr = eng.f16_headroom_async(scr.tiles)
+        key, idx = scr.candidates()
+        host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (hr, key, idx)]
+        for h, t in zip(host, (hr, key, idx)):
+            h.copy_(t, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        sc_pending[k].append((k, nb, *host, ev))
+        scr.reset()
+
+    def where(g):
+        for si in range(len(slides) - 1, -1, -1):
+            if counts[si] and offsets[si] <= g:
+                return f'{slides[si].name} tile {g - offsets[si]}'
+        return '?'
+
+    def screen_look(ks):
+        from .engine import Engine, F16RangeError
+        for k in ks:
+            while sc_pending[k]:
+                _, nb, host, hkey, hidx, ev = sc_pending[k].pop(0)
+                ev.synchronize()
+                a, keys, gidx = host.numpy(), hkey.numpy(), hidx.numpy()
+                sc_state['checks'] += 1
+                sc_state['max_key'] = max(sc_state['max_key'], float(keys.max()))
+                worst = int(np.argmax(a[:, 0]))
+                hr = 65504.0 / max(float(a[worst, 0]), 1e-30)
+                sc_state['min'] = min(sc_state['min'], hr)
+                if a[:, 1].sum() > 0 or hr < float(headroom_min):
+                    sat = {Engine.HEADROOM_TAPS[i][0]: int(a[i, 1]) for i in range(a.shape[0]) if a[i, 1] > 0}
+                    order = sorted(range(len(keys)), key=lambda i: (-keys[i], gidx[i]))
+                    cands = '; '.join(f'{where(int(gidx[i]))} (global tile {int(gidx[i])}, key {float(keys[i]):.4g})' for i in order)
+                    raise F16RangeError(
+                        f'f16 storage at its range limit on the riskiest tiles of stream {k}\'s interval ending at batch {nb}: ' +
+                        (f'{sat} values clamped at +-65504' if sat else f'only {hr:.2f}x of range left at {Engine.HEADROOM_TAPS[worst][0]} '
+                         f'(peak {float(a[worst, 0]):.4g}; headroom_min {headroom_min})') +
+                        f'; candidates looked at, largest standardised input first: {cands}.  The results of these tiles would be '
+                        'plausible and wrong.  Re-run with Engine.calibrate() on tiles like these, or with dtype bf16 / f32')
 
     def headroom_look(block):
         from .engine import Engine, F16RangeError
@@ -677,6 +741,8 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
 
             if monitor and hr_pending and n_batches % int(headroom_every) == 0:
                 headroom_look(block=True)            # the previous check: one interval old, long finished -- a run fails one interval late at most
+            if screens and headroom_every and (sc_count[k] + 1) % int(headroom_every) == 0:
+                screen_look([k])                     # this engine's previous screen tap, one of its intervals old
 
             def work(eng, cur=cur, gdev=gdev):
                 if macenko:
@@ -686,6 +752,8 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
                     passthrough[k] = cnt if passthrough[k] is None else passthrough[k].add_(cnt)
                 elif norm_fit is not None:
                     cur = stain.normalise(eng, cur, normalizer, norm_fit)
+                if screens:                          # the tiles exactly as the network sees them
+                    screens[k].update(cur, tile_idx0=int(cg[0]) if gdev is None else 0, tile_idx=gdev)
                 if gdev is None:
                     eng.mc_infer(cur, mc_n, seed, tile_idx0=int(cg[0]), mc_mode=mc_mode, out=(mean, std))
                 else:
@@ -698,6 +766,10 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream(dev))
                     hr_pending.append((n_batches, int(cg[0]), host, ev))
+                if screens:
+                    sc_count[k] += 1
+                    if headroom_every and sc_count[k] % int(headroom_every) == 0:
+                        screen_tap(k, eng, n_batches)
             if pool:
                 # these tensors were allocated on the caller's stream and are read on the pool's: tell the
                 # caching allocator, or the next batch's temporaries may reuse their memory while this
@@ -865,6 +937,19 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
             if table is not None:
                 table.abort()
             raise
+    if screens:
+        # the last, partial interval of every engine: tapped here, on the engine's stream, and looked at at once
+        try:
+            for k, eng in enumerate(engines):
+                if pool:
+                    pool.run(k, lambda e, k=k: screen_tap(k, e, n_batches - 1))
+                else:
+                    screen_tap(k, eng, n_batches - 1)
+            screen_look(range(len(engines)))
+        except BaseException:
+            if table is not None:
+                table.abort()
+            raise
     try:
         check_z(block=True)                         # what is left: the last chunks
     except BaseException:
@@ -907,4 +992,5 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
     n_pass = sum(int(c) for c in passthrough if c is not None)
     return EvalResult(tile_df, [s.name for s in slides], g_pred, g_unc, g_cnt,
                       np.array([s.y_true for s in slides]), list(mine), table_path, table_rows, hr_state['min'], hr_state['checks'],
-                      n_pass)
+                      n_pass, f16_screen_checks=sc_state['checks'], f16_screen_headroom=sc_state['min'],
+                      f16_screened=sum(s.screened for s in screens), f16_screen_max_key=sc_state['max_key'])

@@ -8,6 +8,7 @@
  *   bq_stain_reinhard_fast  interface.wsi_normalizer.rgb_to_rgb(image)   results.py:251-252, hp.py:19
  *   bq_stain_macenko        the same, for a model trained with normalizer='macenko'
  *   bq_stage        tf.image.per_image_standardization(norm_image)      results.py:256
+ *   bq_range_screen no reference counterpart: picks the tiles for the f16 range taps
  *   bq_backbone     keras Xception(include_top=False, pooling='avg')     biscuit/hp.py:4,20,22
  *   bq_mc_head      the UQ loop behind UncertaintyInterface(model)(batch) -> (mean, std)
  *                                                                        results.py:234,257-258
@@ -127,6 +128,35 @@ int bq_stain_macenko(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, const floa
  * computing them); d_status2 (nullable) int [n][2] = status (as above), number of tissue pixels. */
 int bq_stain_macenko_stats(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, float* d_stats8, int* d_status2,
                            bq_stream_t stream);
+
+/* The f16 range screen: f16 storage clamps at +-65504 without a signal, and an input-driven extreme is what
+ * the stem amplifies, so the tiles whose standardised input reaches furthest are the ones to run through the range taps.
+ *
+ * A tile's key is the largest |value| tf.image.per_image_standardization gives it (what bq_stage feeds the network):
+ *     key = max(hi - mu, mu - lo) / max(sd, 1/sqrt(N))     N = 299 * 299 * 3
+ * hi, lo: its largest and smallest byte; mu = S1/N, var = max(S2/N - mu^2, 0), sd = sqrt(var) from the exact integer sums S1, S2
+ * of its bytes, in float64 without FP contraction, rounded once to float32 (a float64 numpy restatement gives the same bits).
+ *
+ * Both calls take caller-owned device scratch d_ws of bq_range_ws_bytes(n) bytes, used only by the launches of that call (it may be
+ * reused by the next call on the same stream), enqueue everything on `stream` without a host synchronisation, and return 0 for n = 0
+ * without a launch (the device pointers may then be NULL).  Errors as everywhere: BQ_ERR_ARG for a bad argument (nothing enqueued), BQ_ERR_HIP for a failed launch. */
+size_t bq_range_ws_bytes(int n);
+
+/* Keys only (tests, diagnostics): uint8 NHWC tiles [n,299,299,3] (any byte alignment) -> d_key float [n]. */
+int bq_range_key(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, float* d_key, void* d_ws, size_t ws_bytes, bq_stream_t stream);
+
+/* Keys of a batch merged into k candidate slots (1 <= k <= 64), all caller-owned device memory: d_cand_key float [k], d_cand_idx
+ * int64 [k] (global tile index), d_cand_tiles uint8 [k][299][299][3].  The first `filled` slots (0 <= filled <= k) hold candidates
+ * from earlier calls; the rest are empty and are not read.  The batch's global tile indices follow bq_mc_infer: d_tile_idx[i]
+ * (int64 [n], device) when it is not NULL, else tile_idx0 + i.  Afterwards the first min(k, filled + n) slots hold the top of
+ * (candidates + batch) by key descending, global index ascending (equal key and index: the older entry first), a total order:
+ * candidates that stay keep their slot, newly admitted tiles take the freed slots in rank order, lowest slot first, and their bytes
+ * are copied there.  So the caller knows the number of filled slots without reading the device: min(k, tiles since it started
+ * from filled = 0).  Stream order is the only synchronisation: work on `stream` enqueued before the call may read the slots, work
+ * after it sees the update.  n <= 2048. */
+int bq_range_screen(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, int64_t tile_idx0, const int64_t* d_tile_idx,
+                    float* d_cand_key, int64_t* d_cand_idx, uint8_t* d_cand_tiles, int k, int filled, void* d_ws,
+                    size_t ws_bytes, bq_stream_t stream);
 
 /* Input side, PNG tiles: the reversal of the PNG scanline filters on the device.  d_rows:
  * [n][px][1 + 3*px] bytes -- per row the filter-type byte and the filtered RGB bytes, i.e. the inflated IDAT stream of an
