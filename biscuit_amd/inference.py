@@ -9,6 +9,10 @@ Slides are sharded over ranks (one process per GPU); tiles stream in batches of
 segmented reduce); each tile's Philox counter is its GLOBAL index in dataset order, so
 results do not depend on batch size, sharding or rank count.
 """
+import contextlib
+import os
+import queue
+import threading
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence
 
@@ -157,7 +161,6 @@ def slides_from_tfrecords(paths, labels, patients=None, tile_px=299, pinned=None
     the inflated PNG scanlines and the GPU reverses their filters (``Engine.png_unfilter``) -- 12-30 % more tiles per host
     core for 0.4-0.6 ms of GPU time per launch of up to 512 tiles (host side): for hosts whose cores,
     not the GPU, bound the run."""
-    import os
     from . import tfrecord
     if pinned is None:
         pinned = torch.cuda.is_available()
@@ -236,7 +239,7 @@ class _PinnedRing:
     of the two chunk layouts of its tile size -- decoded tiles (px * px * 3 bytes) and filtered PNG scanlines (px * (1 + 3 px))
     -- so alternating the two modes does not re-allocate it (round 4 did: one size in the cache at a time)."""
     _idle = []                       # rings not leased at the moment
-    _lock = None
+    _lock = threading.Lock()
     MAX_IDLE = 2
 
     def __init__(self, nbytes):
@@ -251,9 +254,6 @@ class _PinnedRing:
 
     @classmethod
     def lease(cls, nbytes):
-        import threading
-        if cls._lock is None:
-            cls._lock = threading.Lock()
         with cls._lock:
             for i, r in enumerate(cls._idle):
                 if r.nbytes >= nbytes:
@@ -279,182 +279,229 @@ class _PinnedRing:
         return i
 
 
-def _feed_chunks(slides, mine, dev, copy_stream):
-    """Generator over this rank's slides in order: yields (li, si, first, count, tensor, event, is_rows).  Slides with a
-    ``source`` are decoded chunk by chunk on a feeder thread into the pinned ring and copied to the device on
-    ``copy_stream`` (event = the copy's completion; the tensor was allocated on that stream); PREFETCH_CHUNKS chunks may
-    wait decoded and copied while the GPU works -- with 512-tile chunks that is two 1 000-tile slides of lead.  Other
-    slides are loaded whole on the same thread and handed over as they are (event None)."""
-    import queue
-    import threading
-    q = queue.Queue(maxsize=PREFETCH_CHUNKS)
-    stop = threading.Event()
+@dataclass
+class _Chunk:
+    """What the feeder hands over: tiles in dataset order, ``segs`` = [(li, si, first, count)] (local and global slide index, tile
+    range; several only in a compressed chunk).  ``kind``: 'tiles' ([count,px,px,3]), 'rows' (PNG scanlines [count,px,1+3*px], filters to be
+    reversed) or 'z' (``_ZChunk``'s layout, ``cap`` slots).  ``event``: behind the copy of ``data`` to the device; None: as the loader left it."""
+    kind: str
+    segs: list
+    data: object
+    event: object
+    cap: int = 0
 
-    def put(item):
-        while not stop.is_set():
+
+class _ZChunk:
+    """The compressed chunk being filled (gpu_decode): [off u32[cap] | len u32[cap] | packed zlib streams] in one pinned slot, one H2D copy.
+    It runs ACROSS slides (the device inflates one stream per lane: a 1 000-tile slide alone would leave the decode CUs' waves mostly empty)."""
+
+    def __init__(self, ring, slot, cap, px):
+        self.slot, self.cap, self.px = slot, cap, px
+        self.buf = ring.bufs[slot].numpy()
+        self.hdr = (8 * cap + 15) & ~15
+        self.n = self.pos = 0                            # tiles in the chunk, bytes of their streams
+        self.segs = []
+
+    def add(self, src, li, si, first, left):
+        """Pack tiles [first, ...) of ``src``, ``left`` at most, behind what is there; returns how many went in (0: the slot is full)."""
+        cap = self.cap
+        cnt = min(cap - self.n, left)
+        off = self.buf[:4 * cap].view(np.uint32)[self.n:]
+        ln = self.buf[4 * cap:8 * cap].view(np.uint32)[self.n:]
+        room = self.buf[self.hdr + self.pos:]
+        while cnt:
             try:
-                q.put(item, timeout=0.1)
-                return True
-            except queue.Full:
-                continue
-        return False
+                used = src.read_z(first, cnt, room, off, ln)
+                break
+            except MemoryError:
+                if cnt == 1 and not self.segs:
+                    raise
+                cnt //= 2                                # (tiles that compress worse than the slot was sized for)
+        if cnt:
+            off[:cnt] += np.uint32(self.pos)
+            self.segs.append((li, si, first, cnt))
+            self.n += cnt
+            self.pos += used
+        return cnt
 
-    zc = None                                            # the compressed chunk being filled (gpu_decode), if any
 
-    def emit_z():
-        nonlocal zc
-        c, zc = zc, None
-        if c is None or not c['segs']:
-            return True
-        total = c['hdr'] + c['pos']
-        with torch.cuda.stream(copy_stream):
-            d = torch.empty(total, dtype=torch.uint8, device=dev)
-            d.copy_(c['ring'].bufs[c['slot']][:total], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(copy_stream)
-        c['ring'].events[c['slot']] = ev
-        return put((c['segs'], c['cap'], 0, c['n'], d, ev, 'z'))
+class _FeederStopped(Exception):
+    """The consumer has gone (its ``finally`` set the stop flag): the feeder thread unwinds."""
 
-    def work():
-        nonlocal zc
-        ring = None
-        n_chunks = 0                                     # chunks decoded so far in this run (over all slides)
+
+class _Feeder:
+    """Iterable over this rank's slides in order: yields ``_Chunk``s.  Slides with a ``source`` are decoded chunk by chunk on a
+    feeder thread into the pinned ring and copied to the device on ``copy_stream``; PREFETCH_CHUNKS chunks may wait decoded and copied
+    while the GPU works -- with 512-tile chunks that is two 1 000-tile slides of lead; the native decoder releases the GIL, so decode,
+    H2D copy and kernels overlap.  Other slides are loaded whole on the same thread and handed over as they are (event None)."""
+
+    def __init__(self, slides, mine, dev, copy_stream):
+        self.slides, self.mine, self.dev, self.copy_stream = slides, mine, dev, copy_stream
+        self.q = queue.Queue(maxsize=PREFETCH_CHUNKS)
+        self.stop = threading.Event()
+        self.ring = None
+        self.n_chunks = 0                                # chunks decoded so far in this run (over all slides)
+        self.zc = None                                   # the compressed chunk being filled (gpu_decode), if any
+
+    def __iter__(self):
+        th = threading.Thread(target=self._work, name='bq-tile-feeder', daemon=True)
+        th.start()
         try:
-            for li, si in enumerate(mine):
-                s = slides[si]
-                src = getattr(s, 'source', None)
-                if src is None or s.n_tiles == 0 or copy_stream is None:
-                    if not emit_z():
-                        return
-                    if copy_stream is None:
-                        item = (li, si, 0, s.n_tiles, s.load(), None, False)
-                    else:
-                        # a loader may launch GPU work of its own (tiles resident on the device): on this thread that must
-                        # not be the legacy default stream -- a barrier across the pool's streams, and unordered against the
-                        # consumer's -- but the copy stream, with an event for the consumer to wait on
-                        with torch.cuda.stream(copy_stream):
-                            loaded = s.load()
-                            ev = None
-                            if torch.is_tensor(loaded) and loaded.is_cuda:
-                                ev = torch.cuda.Event()
-                                ev.record(copy_stream)
-                        item = (li, si, 0, s.n_tiles, loaded, ev, False)
-                    if not put(item):
-                        return
-                    continue
-                if getattr(src, 'z', False) and src.z_ok():
-                    # compressed chunks: [off u32[cap] | len u32[cap] | packed zlib streams] in one pinned slot, one H2D copy.  A
-                    # chunk runs ACROSS slides (the device inflates one stream per lane: a 1 000-tile slide alone would leave the
-                    # decode CUs' waves mostly empty); item = (segments [(li, si, first, count)], cap, 0, tiles, buffer, event, 'z')
-                    px = src.tile_px
-                    need = min(CHUNK_TILES_Z * (8 + int(Z_FRACTION * px * (1 + 3 * px))) + 64, Z_SLOT_MAX)   # (larger tiles: chunks of fewer)
-                    if ring is None or ring.nbytes < need:
-                        if not emit_z():
-                            return
-                        if ring is not None:
-                            ring.release()
-                        ring = _PinnedRing.lease(need)
-                    try:
-                        first = 0
-                        while first < s.n_tiles:
-                            if zc is None:
-                                cap = RAMP_CHUNKS_Z[n_chunks] if n_chunks < len(RAMP_CHUNKS_Z) else CHUNK_TILES_Z
-                                n_chunks += 1
-                                slot = ring.acquire()
-                                zc = {'slot': slot, 'buf': ring.bufs[slot].numpy(), 'cap': cap, 'hdr': (8 * cap + 15) & ~15, 'n': 0,
-                                      'pos': 0, 'segs': [], 'px': px, 'ring': ring}
-                            elif zc['px'] != px:
-                                if not emit_z():
-                                    return
-                                continue
-                            k, cap, buf = zc['n'], zc['cap'], zc['buf']
-                            cnt = min(cap - k, s.n_tiles - first)
-                            off = buf[:4 * cap].view(np.uint32)[k:]
-                            ln = buf[4 * cap:8 * cap].view(np.uint32)[k:]
-                            room = buf[zc['hdr'] + zc['pos']:ring.nbytes]
-                            while cnt:
-                                try:
-                                    used = src.read_z(first, cnt, room, off, ln)
-                                    break
-                                except MemoryError:
-                                    if cnt == 1 and not zc['segs']:
-                                        raise
-                                    cnt //= 2                      # (tiles that compress worse than the slot was sized for)
-                            if cnt:
-                                off[:cnt] += np.uint32(zc['pos'])
-                                zc['segs'].append((li, si, first, cnt))
-                                zc['n'] += cnt
-                                zc['pos'] += used
-                                first += cnt
-                            if not cnt or zc['n'] == cap:
-                                if not emit_z():
-                                    return
-                    finally:
-                        src.close()
-                    continue
-                if not emit_z():                                   # (a slide that goes the decoded way: what is open goes first)
+            while True:
+                item = self.q.get()
+                if item is None:
                     return
-                per = int(np.prod(src.chunk_shape(1)))
-                px = getattr(src, 'tile_px', None)
-                need = max(CHUNK_TILES * per, _PinnedRing.chunk_bytes(px) if px else 0)
-                if ring is None or ring.nbytes < need:
-                    if ring is not None:
-                        ring.release()
-                    ring = _PinnedRing.lease(need)
-                try:
-                    first = 0
-                    while first < s.n_tiles:
-                        size = RAMP_CHUNKS[n_chunks] if n_chunks < len(RAMP_CHUNKS) else CHUNK_TILES
-                        n_chunks += 1
-                        cnt = min(size, s.n_tiles - first)
-                        slot = ring.acquire()
-                        host = ring.bufs[slot][:cnt * per].view(src.chunk_shape(cnt))
-                        src.read(first, cnt, host.numpy())
-                        with torch.cuda.stream(copy_stream):
-                            d = torch.empty(src.chunk_shape(cnt), dtype=torch.uint8, device=dev)
-                            d.copy_(host, non_blocking=True)
+                if isinstance(item, BaseException):
+                    raise item
+                yield item
+        finally:
+            self.stop.set()
+            th.join(timeout=30)
+
+    def _put(self, item):
+        while not self.stop.is_set():
+            with contextlib.suppress(queue.Full):
+                self.q.put(item, timeout=0.1)
+                return
+        raise _FeederStopped
+
+    def _work(self):
+        try:
+            for li, si in enumerate(self.mine):
+                s = self.slides[si]
+                src = getattr(s, 'source', None)
+                if src is None or s.n_tiles == 0 or self.copy_stream is None:
+                    self._emit_z()
+                    # a loader may launch GPU work of its own (tiles resident on the device): on this thread that must
+                    # not be the legacy default stream -- a barrier across the pool's streams, and unordered against the
+                    # consumer's -- but the copy stream, with an event for the consumer to wait on
+                    ev = None
+                    with (torch.cuda.stream(self.copy_stream) if self.copy_stream is not None else contextlib.nullcontext()):
+                        loaded = s.load()
+                        if self.copy_stream is not None and torch.is_tensor(loaded) and loaded.is_cuda:
                             ev = torch.cuda.Event()
-                            ev.record(copy_stream)
-                        ring.events[slot] = ev
-                        if not put((li, si, first, cnt, d, ev, src.rows)):
-                            return
-                        first += cnt
+                            ev.record(self.copy_stream)
+                    rows = isinstance(loaded, PngRows)
+                    self._put(_Chunk('rows' if rows else 'tiles', [(li, si, 0, s.n_tiles)], loaded.rows if rows else loaded, ev))
+                    continue
+                try:
+                    if getattr(src, 'z', False) and src.z_ok():
+                        self._compressed(li, si, s, src)
+                    else:
+                        self._emit_z()                   # (a slide that goes the decoded way: what is open goes first)
+                        self._decoded(li, si, s, src)
                 finally:
                     src.close()
-            if emit_z():
-                put(None)
-        except BaseException as e:                   # noqa: BLE001 -- re-raised in the consumer
-            put(e)
+            self._emit_z()
+            self._put(None)
+        except _FeederStopped:
+            pass
+        except BaseException as e:                       # noqa: BLE001 -- re-raised in the consumer
+            with contextlib.suppress(_FeederStopped):
+                self._put(e)
         finally:
-            if ring is not None:
-                ring.release()
+            if self.ring is not None:
+                self.ring.release()
 
-    th = threading.Thread(target=work, name='bq-tile-feeder', daemon=True)
-    th.start()
-    try:
-        while True:
-            item = q.get()
-            if item is None:
-                return
-            if isinstance(item, BaseException):
-                raise item
-            yield item
-    finally:
-        stop.set()
-        th.join(timeout=30)
+    def _need_ring(self, need):
+        """The leased ring's slots hold ``need`` bytes after this (an open compressed chunk sits in the ring that goes: it goes first)."""
+        if self.ring is None or self.ring.nbytes < need:
+            self._emit_z()
+            if self.ring is not None:
+                self.ring.release()
+            self.ring = _PinnedRing.lease(need)
+
+    def _upload(self, slot, host):
+        """``host`` (a view of ring slot ``slot``) -> a new device tensor, on the copy stream; (tensor, the copy's event)."""
+        with torch.cuda.stream(self.copy_stream):
+            d = torch.empty(host.shape, dtype=torch.uint8, device=self.dev)
+            d.copy_(host, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        self.ring.events[slot] = ev
+        return d, ev
+
+    def _emit_z(self):
+        c, self.zc = self.zc, None
+        if c is not None and c.segs:
+            d, ev = self._upload(c.slot, self.ring.bufs[c.slot][:c.hdr + c.pos])
+            self._put(_Chunk('z', c.segs, d, ev, c.cap))
+
+    def _compressed(self, li, si, s, src):
+        px = src.tile_px
+        self._need_ring(min(CHUNK_TILES_Z * (8 + int(Z_FRACTION * px * (1 + 3 * px))) + 64, Z_SLOT_MAX))   # (larger tiles: chunks of fewer)
+        first = 0
+        while first < s.n_tiles:
+            if self.zc is not None and self.zc.px != px:
+                self._emit_z()
+            if self.zc is None:
+                cap = RAMP_CHUNKS_Z[self.n_chunks] if self.n_chunks < len(RAMP_CHUNKS_Z) else CHUNK_TILES_Z
+                self.n_chunks += 1
+                self.zc = _ZChunk(self.ring, self.ring.acquire(), cap, px)
+            cnt = self.zc.add(src, li, si, first, s.n_tiles - first)
+            first += cnt
+            if not cnt or self.zc.n == self.zc.cap:
+                self._emit_z()
+
+    def _decoded(self, li, si, s, src):
+        per = int(np.prod(src.chunk_shape(1)))
+        px = getattr(src, 'tile_px', None)
+        self._need_ring(max(CHUNK_TILES * per, _PinnedRing.chunk_bytes(px) if px else 0))
+        first = 0
+        while first < s.n_tiles:
+            size = RAMP_CHUNKS[self.n_chunks] if self.n_chunks < len(RAMP_CHUNKS) else CHUNK_TILES
+            self.n_chunks += 1
+            cnt = min(size, s.n_tiles - first)
+            slot = self.ring.acquire()
+            host = self.ring.bufs[slot][:cnt * per].view(src.chunk_shape(cnt))
+            src.read(first, cnt, host.numpy())
+            d, ev = self._upload(slot, host)
+            self._put(_Chunk('rows' if src.rows else 'tiles', [(li, si, first, cnt)], d, ev))
+            first += cnt
 
 
-def _take_front(parts, k, cat):
-    """(the first k rows of the arrays in ``parts``, what is left of the list): views where possible, ``cat`` only over the pieces of a
-    front that spans several arrays."""
+def _take_front(parts, k, size=len, cut=lambda t, a, b: t[a:b]):
+    """(the pieces that make up the first k rows of the arrays in ``parts``, what is left of the list): whole arrays and views, no copy."""
     out, i = [], 0
     while k > 0:
         t = parts[i]
-        if t.shape[0] <= k:
-            out.append(t); k -= t.shape[0]; i += 1
+        if size(t) <= k:
+            out.append(t); k -= size(t); i += 1
         else:
-            out.append(t[:k]); parts = parts[:i] + [t[k:]] + parts[i + 1:]; k = 0
-    return (out[0] if len(out) == 1 else cat(out)), parts[i:]
+            out.append(cut(t, 0, k)); parts = parts[:i] + [cut(t, k, size(t))] + parts[i + 1:]; k = 0
+    return out, parts[i:]
+
+
+class _Pending:
+    """The tiles that wait for a batch, in dataset order: the device tensors they lie in and, per run of tiles of one slide, every
+    tile's local slide index (int32, device) and global index (int64, host) and the table's segment (si, name, y_true, loc, count)."""
+
+    def __init__(self):
+        self.tiles, self.sidx, self.gidx, self.segs = [], [], [], []
+        self.n = 0
+
+    def push(self, tiles, sidx, gidx, segs):                # one tensor; per slide in it one entry of each list (``segs``: empty without a table)
+        self.tiles.append(tiles)
+        self.sidx += sidx
+        self.gidx += gidx
+        self.segs += segs
+        self.n += tiles.shape[0]
+
+    def take(self, k):
+        """The first ``k`` tiles: (tiles, slide indices, global indices, table segments)."""
+        # the first `k` rows of what is pending: a VIEW when they lie in one tensor, one batch-sized copy when the batch spans
+        # two (round 4 concatenated everything pending -- a 1 000-tile slide behind a 200-tile remainder: 330 MB copied to cut 256
+        # tiles off the front, 0.11 ms per batch in config 3's trace)
+        cur, self.tiles = _take_front(self.tiles, k)
+        cs, self.sidx = _take_front(self.sidx, k)
+        cg, self.gidx = _take_front(self.gidx, k)
+        segs = []
+        if self.segs:
+            segs, self.segs = _take_front(self.segs, k, size=lambda seg: seg[4],
+                                          cut=lambda seg, a, b: (*seg[:3], None if seg[3] is None else seg[3][a:b], b - a))
+        self.n -= k
+        return (cur[0] if len(cur) == 1 else torch.cat(cur), cs[0] if len(cs) == 1 else torch.cat(cs),
+                cg[0] if len(cg) == 1 else np.concatenate(cg), segs)
 
 
 def _to_device(t, device):
@@ -473,8 +520,6 @@ class _TableStream:
     of a multi-rank run it also notes every slide's byte range (``write_shard_index``)."""
 
     def __init__(self, path, outcome, with_loc, dev, max_batch, shard=None):
-        import queue
-        import threading
         self.writer = TableWriter(path, outcome, with_loc)
         self.path, self.outcome, self.with_loc, self.shard = path, outcome, with_loc, shard
         self.dev = torch.device(dev)
@@ -563,6 +608,235 @@ class _TableStream:
         return rows
 
 
+def _f16_verdict(a, headroom_min):
+    """One [8, 2] result of ``Engine.f16_headroom_async`` (per tap: peak |activation| as stored, values at the clamp) ->
+    (headroom = 65504 / peak, None or what is wrong: a value at the clamp, or less than ``headroom_min`` x of range left)."""
+    worst = int(np.argmax(a[:, 0]))
+    hr = 65504.0 / max(float(a[worst, 0]), 1e-30)
+    if not (a[:, 1].sum() > 0 or hr < float(headroom_min)):
+        return hr, None
+    from .engine import Engine
+    sat = {Engine.HEADROOM_TAPS[i][0]: int(a[i, 1]) for i in range(a.shape[0]) if a[i, 1] > 0}
+    return hr, (f'{sat} values clamped at +-65504' if sat else f'only {hr:.2f}x of range left at {Engine.HEADROOM_TAPS[worst][0]} '
+                f'(peak {float(a[worst, 0]):.4g}; headroom_min {headroom_min})')
+
+
+class _RangeWatch:
+    """``evaluate``'s sampling monitor (the first tiles of a batch) and range screen (the riskiest tiles of an engine's interval): the
+    eight f16 range taps run behind the batches and are looked at later, with no host synchronisation in between.  Taps in flight, per
+    engine: (batch number, first global tile index or None, pinned [8, 2] result [+ the candidates' keys, global indices], event)."""
+
+    def __init__(self, n_engines, headroom_min, dev, slides, offsets):
+        self.pending = [[] for _ in range(n_engines)]
+        self.headroom_min, self.dev, self.slides, self.offsets = headroom_min, dev, slides, offsets
+        self.min, self.checks, self.max_key = float('inf'), 0, 0.0
+
+    def tap(self, k, eng, tiles, batch_no, g0=None, candidates=()):
+        """Enqueue the taps on ``tiles`` and the copies out on the current stream (engine ``k``'s); reported on failure: ``g0`` / ``candidates``."""
+        parts = (eng.f16_headroom_async(tiles), *candidates)
+        host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in parts]
+        for h, t in zip(host, parts):
+            h.copy_(t, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        self.pending[k].append((batch_no, g0, host, ev))
+
+    def look(self, ks=None):
+        """Wait for the taps in flight (of engines ``ks``; default: all) and judge them: ``F16RangeError`` at the first that fails.  (Engine
+        by engine, not in batch order: every tap is preceded by a look, so an engine has one in flight at most and the order cannot matter.)"""
+        for k in range(len(self.pending)) if ks is None else ks:
+            while self.pending[k]:
+                nb, g0, host, ev = self.pending[k].pop(0)
+                ev.synchronize()
+                self.checks += 1
+                if len(host) > 1:
+                    self.max_key = max(self.max_key, float(host[1].numpy().max()))
+                hr, wrong = _f16_verdict(host[0].numpy(), self.headroom_min)
+                self.min = min(self.min, hr)
+                if wrong is not None:
+                    raise self._error(k, nb, g0, host[1:], wrong)
+
+    def _tile_name(self, g):
+        for si in range(len(self.slides) - 1, -1, -1):
+            if self.slides[si].n_tiles and self.offsets[si] <= g:
+                return f'{self.slides[si].name} tile {g - self.offsets[si]}'
+        return '?'
+
+    def _error(self, k, nb, g0, candidates, wrong):
+        from .engine import F16RangeError
+        if not candidates:
+            where = f'in batch {nb} (global tile {g0} on): '
+            then = '; the results from there on would be plausible and wrong.'
+        else:
+            keys, gidx = (h.numpy() for h in candidates)
+            order = sorted(range(len(keys)), key=lambda i: (-keys[i], gidx[i]))
+            cands = '; '.join(f'{self._tile_name(int(gidx[i]))} (global tile {int(gidx[i])}, key {float(keys[i]):.4g})' for i in order)
+            where = f'on the riskiest tiles of stream {k}\'s interval ending at batch {nb}: '
+            then = (f'; candidates looked at, largest standardised input first: {cands}.  The results of these tiles would be '
+                    'plausible and wrong.')
+        return F16RangeError(f'f16 storage at its range limit {where}{wrong}{then}  Re-run with Engine.calibrate() on tiles like '
+                             'these, or with dtype bf16 / f32')
+
+
+class _DeviceInflate:
+    """gpu_decode: compressed chunks are inflated on the pool's decode streams (CU-masked: the compute units it keeps out of the
+    inference streams; without a pool, the current stream), round-robin, each with its own table scratch; the status words are
+    looked at one chunk late (``check``)."""
+
+    def __init__(self, eng0, pool, dev, slides):
+        self.eng0, self.dev, self.slides = eng0, dev, slides
+        self.streams = getattr(pool, 'decode_streams', None) if pool else None
+        self.k = 0                                       # chunks so far: the round-robin counter
+        self.scratch = {}                                # decode stream -> its table scratch
+        self.status = []                                 # in flight: (the chunk's segments, pinned status words, event)
+
+    def check(self, block):
+        while self.status and (block or self.status[0][2].query()):
+            segs, status, ev = self.status.pop(0)
+            ev.synchronize()
+            bad = np.flatnonzero(status.numpy()).tolist()
+            if bad:
+                at, where = 0, None
+                for (_, si, first, c) in segs:
+                    if at <= bad[0] < at + c:
+                        where = f'{self.slides[si].name}, tile {first + bad[0] - at}'
+                    at += c
+                raise IOError(f'the device inflate refused {len(bad)} tile(s) (first: {where}, status {int(status[bad[0]])}): damaged PNG '
+                              f'data; decode on the host (gpu_decode=False) to see the decoder\'s own error')
+
+    def decode(self, chunk, px):
+        """A compressed chunk -> its tiles' filtered scanlines, ordered before the current stream's work that follows."""
+        eng0, buf, cap, count = self.eng0, chunk.data, chunk.cap, sum(c for *_, c in chunk.segs)
+        main = torch.cuda.current_stream(self.dev)
+        dec = self.streams[self.k % len(self.streams)] if self.streams else main
+        self.k += 1
+        off = buf[:4 * count].view(torch.int32)
+        ln = buf[4 * cap:4 * cap + 4 * count].view(torch.int32)
+        z = buf[(8 * cap + 15) & ~15:]
+        dec.wait_event(chunk.event)
+        buf.record_stream(dec)
+        key = dec.cuda_stream
+        with torch.cuda.stream(dec):
+            if key not in self.scratch or self.scratch[key].numel() < eng0._lib.bq_png_inflate_scratch_bytes(count):
+                self.scratch[key] = eng0.inflate_scratch(max(count, CHUNK_TILES_Z))
+            rows, status = eng0.png_inflate(z, off, ln, px=px, scratch=self.scratch[key])
+            done = torch.cuda.Event()
+            done.record(dec)
+        main.wait_event(done)
+        rows.record_stream(main)
+        # the status words leave the device behind the inflate (a few KB, pinned, on the decode stream) and are looked at when the NEXT
+        # chunk arrives -- one chunk late, without stalling anything: a damaged stream stops the run there instead of after it
+        host = torch.empty(status.shape, dtype=status.dtype, pin_memory=True)
+        with torch.cuda.stream(dec):
+            host.copy_(status, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(dec)
+        self.check(block=False)
+        self.status.append((chunk.segs, host, ev))
+        return rows
+
+
+class _Batches:
+    """``evaluate``'s batches, round-robin over the engines (a pool's: each on its own stream): accumulators, range watches, table hand-over."""
+
+    def __init__(self, pool, engines, table, dev, n_local, slides, offsets, stain, *, batch, mc_n, seed, mc_mode, tile_uq, normalizer, norm_fit,
+                 keep_tiles, headroom_every, headroom_min, range_screen):
+        self.pool, self.engines, self.table, self.dev, self.n_local, self.stain = pool, engines, table, dev, n_local, stain
+        self.streams = getattr(pool, 'streams', None) if pool else None
+        self.mc_n, self.seed, self.mc_mode, self.tile_uq = mc_n, seed, mc_mode, tile_uq
+        self.normalizer, self.norm_fit, self.keep_tiles = normalizer, norm_fit, keep_tiles
+        self.n = 0                                       # batches enqueued
+        self.acc = [None] * len(engines)
+        self.passthrough = [None] * len(engines)         # per stream: int64 device count of the tiles the Macenko kernel passed through
+        self.rows = []                                   # keep_tiles: the batches' (mean | std), on the device; copied to the host at the end
+        f16 = all(getattr(e, 'dtype', None) == 'f16' and hasattr(e, 'f16_headroom_async') for e in engines)
+        self.every = int(headroom_every or 0) if f16 else 0      # batches between range checks (0: neither monitor nor mid-run screen taps)
+        self.monitor = _RangeWatch(len(engines), headroom_min, dev, slides, offsets)
+        self.screen = _RangeWatch(len(engines), headroom_min, dev, slides, offsets)
+        self.screens = []
+        if range_screen and f16:
+            from .engine import RangeScreen
+            self.screens = [RangeScreen(e, k=min(8, e.max_batch), max_batch=batch) for e in engines]
+        self.sc_count = [0] * len(engines)
+
+    def _screen_tap(self, k, eng, batch_no):
+        scr = self.screens[k]
+        if scr.filled:
+            self.screen.tap(k, eng, scr.tiles, batch_no, candidates=scr.candidates())
+            scr.reset()
+
+    def _work(self, eng, k, cur, cs, g0, gdev, mean, std):
+        if self.norm_fit is not None:
+            if self.normalizer == 'macenko':
+                st = torch.empty(cur.shape[0], dtype=torch.int32, device=self.dev)
+                cur = self.stain.normalise(eng, cur, self.normalizer, self.norm_fit, status=st)
+                cnt = st.ne(0).sum()
+                self.passthrough[k] = cnt if self.passthrough[k] is None else self.passthrough[k].add_(cnt)
+            else:
+                cur = self.stain.normalise(eng, cur, self.normalizer, self.norm_fit)
+        if self.screens:                                 # the tiles exactly as the network sees them
+            self.screens[k].update(cur, tile_idx0=g0 if gdev is None else 0, tile_idx=gdev)
+        if gdev is None:
+            eng.mc_infer(cur, self.mc_n, self.seed, tile_idx0=g0, mc_mode=self.mc_mode, out=(mean, std))
+        else:
+            eng.mc_infer(cur, self.mc_n, self.seed, tile_idx0=0, mc_mode=self.mc_mode, out=(mean, std), tile_idx=gdev)
+        self.acc[k] = eng.slide_reduce(mean, std, cs, max(self.n_local, 1), tile_uq=self.tile_uq, acc=self.acc[k])
+        if self.every and self.n % self.every == 0:
+            self.monitor.tap(k, eng, cur, self.n, g0=g0)
+        if self.screens:
+            self.sc_count[k] += 1
+            if self.every and self.sc_count[k] % self.every == 0:
+                self._screen_tap(k, eng, self.n)
+
+    def run(self, cur, cs, cg, segs):
+        """Enqueue one batch: the tiles, every tile's local slide index and global index (host), the table segments of its slides."""
+        n, k = cur.shape[0], self.n % len(self.engines)
+        cur, cs = cur.contiguous(), cs.contiguous()
+        out2 = torch.empty((2, n, 2), dtype=torch.float32, device=self.dev)       # mean | std: ONE device-to-host copy per batch
+        # a batch that spans slides holds tiles whose global indices are not one consecutive run: the backbone does not care,
+        # the head's Philox counter does -- it takes the indices as an array then (bq_set_tile_index_array): ONE launch sequence
+        # per batch whatever its composition (round 4: one head call per run, 4 x the head time with 64-tile slides), and a
+        # tile's result does not depend on batch size, sharding or rank count
+        gdev = None
+        if (np.diff(cg) != 1).any():
+            gdev = torch.from_numpy(np.ascontiguousarray(cg)).to(self.dev, non_blocking=True)
+        if self.every and self.n % self.every == 0:
+            self.monitor.look()                      # the previous check: one interval old, long finished -- a run fails one interval late at most
+        if self.screens and self.every and (self.sc_count[k] + 1) % self.every == 0:
+            self.screen.look([k])                    # this engine's previous screen tap, one of its intervals old
+        if self.pool:
+            # these tensors were allocated on the caller's stream and are read on the pool's: tell the
+            # caching allocator, or the next batch's temporaries may reuse their memory while this
+            # batch's kernels are still in flight
+            if self.streams and cur.is_cuda:
+                for t in (cur, cs, out2) + ((gdev,) if gdev is not None else ()):
+                    t.record_stream(self.streams[k])
+            self.pool.run(self.n, lambda eng: self._work(eng, k, cur, cs, int(cg[0]), gdev, out2[0], out2[1]), wait_for_current=True)
+        else:
+            self._work(self.engines[0], k, cur, cs, int(cg[0]), gdev, out2[0], out2[1])
+        if self.table is not None:
+            ev = None
+            if out2.is_cuda:
+                ev = torch.cuda.Event()
+                ev.record(self.streams[k] if self.streams else torch.cuda.current_stream(self.dev))
+            self.table.submit(out2, ev, segs)
+        self.n += 1
+        if self.keep_tiles:
+            self.rows.append(out2)
+
+    def final_looks(self):
+        if self.every:
+            self.monitor.look()
+        if self.screens:
+            # the last, partial interval of every engine: tapped here, on the engine's stream, and looked at at once
+            for k, eng in enumerate(self.engines):
+                if self.pool:
+                    self.pool.run(k, lambda e, k=k: self._screen_tap(k, e, self.n - 1))
+                else:
+                    self._screen_tap(k, eng, self.n - 1)
+            self.screen.look()
+
+
 def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=None, batch=256,
              mc_mode='head', tile_uq=None, save_dir=None, keep_tiles=True, rank=0, world=1, norm_fit=None,
              table_name=EVAL_NAME, table_writer='native', headroom_every=200, headroom_min=2.0, normalizer='reinhard_fast',
@@ -600,370 +874,99 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
     tissue, one colour) are counted on the device and read once at the end: ``EvalResult.stain_passthrough`` (this rank's)."""
     from . import stain
     stain.check(normalizer, norm_fit)
-    macenko = norm_fit is not None and normalizer == 'macenko'
-    hp = engine.hp
-    mc_n = int(mc_n or hp.uq_n)
-    seed = int(hp.seed if seed is None else seed)
+    mc_n = int(mc_n or engine.hp.uq_n)
+    seed = int(engine.hp.seed if seed is None else seed)
     counts = [s.n_tiles for s in slides]
     parts = D.partition_slides(counts, world)
     mine = parts[rank]
     offsets = D.global_tile_offsets(counts)
     dev = engine.device
+    cuda = torch.device(dev).type == 'cuda'
     n_local = len(mine)
     # an EnginePool alternates batches over independent contexts / HIP streams
     pool = engine if hasattr(engine, 'engines') else None
     engines = pool.engines[:len(pool)] if pool else [engine]      # len(pool) = batches in flight
-    acc = [None] * len(engines)
-    passthrough = [None] * len(engines)          # per stream: int64 device count of the tiles the Macenko kernel passed through
-    n_batches = 0
-    rows_mean, rows_std, rows_slide, rows_true, rows_loc = [], [], [], [], []
+    rows_slide, rows_true, rows_loc = [], [], []
     with_loc = any(s.n_tiles for s in slides) and all(s.loc is not None for s in slides if s.n_tiles)    # (every rank decides the same: one header)
     native = save_dir is not None and table_writer == 'native' and table_name.endswith('.csv')
     if table_writer not in ('native', 'pandas'):
         raise ValueError(f"table_writer must be 'native' or 'pandas', not {table_writer!r}")
     if save_dir is not None and not native and not keep_tiles:
         raise ValueError('the pandas writer needs keep_tiles=True (it writes the frame after the run)')
+    if save_dir is not None and rank == 0 and os.path.isdir(save_dir):
+        remove_stale_shards(save_dir, world if world > 1 else 0, table_name)      # (a one-rank run leaves THE table only)
     table = None
-    if save_dir is not None and rank == 0:
-        import os
-        if os.path.isdir(save_dir):
-            remove_stale_shards(save_dir, world if world > 1 else 0, table_name)      # (a one-rank run leaves THE table only)
     if native:
-        import os
         tpath = os.path.join(save_dir, table_name if world == 1 else shard_name(table_name, rank))
         table = _TableStream(tpath, outcome, with_loc, dev, batch, shard=None if world == 1 else (rank, world))
-    pend_segs = []                           # (slide index, name, y_true, loc rows or None, count) of the pending tiles, in order
-    # the f16 range monitor (see the docstring): checks in flight = (batch number, first global tile index, pinned [8, 2], event)
-    monitor = bool(headroom_every) and all(getattr(e, 'dtype', None) == 'f16' and hasattr(e, 'f16_headroom_async') for e in engines)
-    hr_pending, hr_state = [], {'min': float('inf'), 'checks': 0}
-    # the range screen (see the docstring): per engine its slots, its own batch count and its tap in flight
-    # (engine number, batch number, pinned [8, 2] tap result, pinned keys, pinned global indices, event)
-    screens = []
-    if range_screen and all(getattr(e, 'dtype', None) == 'f16' and hasattr(e, 'f16_headroom_async') for e in engines):
-        from .engine import RangeScreen
-        screens = [RangeScreen(e, k=min(8, e.max_batch), max_batch=batch) for e in engines]
-    sc_count, sc_pending = [0] * len(engines), [[] for _ in engines]
-    sc_state = {'min': float('inf'), 'checks': 0, 'max_key': 0.0}
-
-    def screen_tap(k, eng, nb):
-        scr = screens[k]
-        if not scr.filled:
-            return
-        hr = eng.f16_headroom_async(scr.tiles)
-        key, idx = scr.candidates()
-        host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (hr, key, idx)]
-        for h, t in zip(host, (hr, key, idx)):
-            h.copy_(t, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-        sc_pending[k].append((k, nb, *host, ev))
-        scr.reset()
-
-    def where(g):
-        for si in range(len(slides) - 1, -1, -1):
-            if counts[si] and offsets[si] <= g:
-                return f'{slides[si].name} tile {g - offsets[si]}'
-        return '?'
-
-    def screen_look(ks):
-        from .engine import Engine, F16RangeError
-        for k in ks:
-            while sc_pending[k]:
-                _, nb, host, hkey, hidx, ev = sc_pending[k].pop(0)
-                ev.synchronize()
-                a, keys, gidx = host.numpy(), hkey.numpy(), hidx.numpy()
-                sc_state['checks'] += 1
-                sc_state['max_key'] = max(sc_state['max_key'], float(keys.max()))
-                worst = int(np.argmax(a[:, 0]))
-                hr = 65504.0 / max(float(a[worst, 0]), 1e-30)
-                sc_state['min'] = min(sc_state['min'], hr)
-                if a[:, 1].sum() > 0 or hr < float(headroom_min):
-                    sat = {Engine.HEADROOM_TAPS[i][0]: int(a[i, 1]) for i in range(a.shape[0]) if a[i, 1] > 0}
-                    order = sorted(range(len(keys)), key=lambda i: (-keys[i], gidx[i]))
-                    cands = '; '.join(f'{where(int(gidx[i]))} (global tile {int(gidx[i])}, key {float(keys[i]):.4g})' for i in order)
-                    raise F16RangeError(
-                        f'f16 storage at its range limit on the riskiest tiles of stream {k}\'s interval ending at batch {nb}: ' +
-                        (f'{sat} values clamped at +-65504' if sat else f'only {hr:.2f}x of range left at {Engine.HEADROOM_TAPS[worst][0]} '
-                         f'(peak {float(a[worst, 0]):.4g}; headroom_min {headroom_min})') +
-                        f'; candidates looked at, largest standardised input first: {cands}.  The results of these tiles would be '
-                        'plausible and wrong.  Re-run with Engine.calibrate() on tiles like these, or with dtype bf16 / f32')
-
-    def headroom_look(block):
-        from .engine import Engine, F16RangeError
-        while hr_pending and (block or hr_pending[0][3].query()):
-            nb, g0, host, ev = hr_pending.pop(0)
-            ev.synchronize()
-            a = host.numpy()
-            hr_state['checks'] += 1
-            worst = int(np.argmax(a[:, 0]))
-            hr = 65504.0 / max(float(a[worst, 0]), 1e-30)
-            hr_state['min'] = min(hr_state['min'], hr)
-            if a[:, 1].sum() > 0 or hr < float(headroom_min):
-                sat = {Engine.HEADROOM_TAPS[i][0]: int(a[i, 1]) for i in range(a.shape[0]) if a[i, 1] > 0}
-                raise F16RangeError(
-                    f'f16 storage at its range limit in batch {nb} (global tile {g0} on): ' +
-                    (f'{sat} values clamped at +-65504' if sat else f'only {hr:.2f}x of range left at {Engine.HEADROOM_TAPS[worst][0]} '
-                     f'(peak {float(a[worst, 0]):.4g}; headroom_min {headroom_min})') +
-                    '; the results from there on would be plausible and wrong.  Re-run with Engine.calibrate() on tiles like these, '
-                    'or with dtype bf16 / f32')
-
-    # stream tiles of this rank's slides in batches that may span slides
-    pend_tiles, pend_sidx, pend_gidx = [], [], []
-    pend_n = 0
-
-    def flush(final=False):
-        nonlocal pend_tiles, pend_sidx, pend_gidx, pend_n, n_batches
-        while pend_n >= batch or (final and pend_n > 0):
-            take = min(batch, pend_n)
-            # the first `take` rows of what is pending: a VIEW when they lie in one tensor, one batch-sized copy when the batch spans
-            # two (round 4 concatenated everything pending -- a 1 000-tile slide behind a 200-tile remainder: 330 MB copied to cut 256
-            # tiles off the front, 0.11 ms per batch in config 3's trace)
-            cur, pend_tiles = _take_front(pend_tiles, take, torch.cat)
-            cs, pend_sidx = _take_front(pend_sidx, take, torch.cat)
-            cg, pend_gidx = _take_front(pend_gidx, take, np.concatenate)
-            cur, cs = cur.contiguous(), cs.contiguous()
-            # global tile indices inside a batch are contiguous per slide but not across
-            # slides: run one bq_mc_infer per contiguous run so the Philox counter is exact
-            out2 = torch.empty((2, take, 2), dtype=torch.float32, device=dev)       # mean | std: ONE device-to-host copy per batch
-            mean, std = out2[0], out2[1]
-            brk = np.flatnonzero(np.diff(cg) != 1) + 1
-            starts = np.concatenate([[0], brk]); ends = np.concatenate([brk, [take]])
-            k = n_batches % len(engines)
-
-            # a batch that spans slides holds tiles whose global indices are not one consecutive run: the backbone does not care,
-            # the head's Philox counter does -- it takes the indices as an array then (bq_set_tile_index_array): ONE launch sequence
-            # per batch whatever its composition (round 4: one head call per run, 4 x the head time with 64-tile slides), and a
-            # tile's result does not depend on batch size, sharding or rank count
-            gdev = None
-            if len(starts) > 1:
-                gdev = torch.from_numpy(np.ascontiguousarray(cg)).to(dev, non_blocking=True) if torch.device(dev).type == 'cuda' \
-                    else torch.from_numpy(np.ascontiguousarray(cg))
-
-            if monitor and hr_pending and n_batches % int(headroom_every) == 0:
-                headroom_look(block=True)            # the previous check: one interval old, long finished -- a run fails one interval late at most
-            if screens and headroom_every and (sc_count[k] + 1) % int(headroom_every) == 0:
-                screen_look([k])                     # this engine's previous screen tap, one of its intervals old
-
-            def work(eng, cur=cur, gdev=gdev):
-                if macenko:
-                    st = torch.empty(cur.shape[0], dtype=torch.int32, device=dev)
-                    cur = stain.normalise(eng, cur, normalizer, norm_fit, status=st)
-                    cnt = st.ne(0).sum()
-                    passthrough[k] = cnt if passthrough[k] is None else passthrough[k].add_(cnt)
-                elif norm_fit is not None:
-                    cur = stain.normalise(eng, cur, normalizer, norm_fit)
-                if screens:                          # the tiles exactly as the network sees them
-                    screens[k].update(cur, tile_idx0=int(cg[0]) if gdev is None else 0, tile_idx=gdev)
-                if gdev is None:
-                    eng.mc_infer(cur, mc_n, seed, tile_idx0=int(cg[0]), mc_mode=mc_mode, out=(mean, std))
-                else:
-                    eng.mc_infer(cur, mc_n, seed, tile_idx0=0, mc_mode=mc_mode, out=(mean, std), tile_idx=gdev)
-                acc[k] = eng.slide_reduce(mean, std, cs, max(n_local, 1), tile_uq=tile_uq, acc=acc[k])
-                if monitor and n_batches % int(headroom_every) == 0:
-                    hr = eng.f16_headroom_async(cur)
-                    host = torch.empty(hr.shape, dtype=torch.float32, pin_memory=True)
-                    host.copy_(hr, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(dev))
-                    hr_pending.append((n_batches, int(cg[0]), host, ev))
-                if screens:
-                    sc_count[k] += 1
-                    if headroom_every and sc_count[k] % int(headroom_every) == 0:
-                        screen_tap(k, eng, n_batches)
-            if pool:
-                # these tensors were allocated on the caller's stream and are read on the pool's: tell the
-                # caching allocator, or the next batch's temporaries may reuse their memory while this
-                # batch's kernels are still in flight
-                st = getattr(pool, 'streams', None)
-                if st and cur.is_cuda:
-                    for t in (cur, cs, out2) + ((gdev,) if gdev is not None else ()):
-                        t.record_stream(st[k])
-                pool.run(n_batches, work, wait_for_current=True)
-            else:
-                work(engine)
-            if table is not None:
-                ev = None
-                if out2.is_cuda:
-                    ev = torch.cuda.Event()
-                    st = getattr(pool, 'streams', None) if pool else None
-                    ev.record(st[k] if st else torch.cuda.current_stream(dev))
-                segs, left = [], take
-                while left:
-                    si, name, yt, loc, c = pend_segs[0]
-                    if c <= left:
-                        segs.append(pend_segs.pop(0)); left -= c
-                    else:
-                        segs.append((si, name, yt, None if loc is None else loc[:left], left))
-                        pend_segs[0] = (si, name, yt, None if loc is None else loc[left:], c - left)
-                        left = 0
-                table.submit(out2, ev, segs)
-            n_batches += 1
-            if keep_tiles:          # device tensors; copied to the host once everything has been enqueued
-                rows_mean.append(mean); rows_std.append(std)
-            pend_n -= take
-
-    # With a pool, everything this function itself enqueues (H2D copies, concatenations, a device-side loader) goes to
-    # a side stream, not to the default stream: the pool's CU-masked streams are ordinary (blocking) HIP streams, and
-    # an operation on the legacy default stream is a barrier across all of those -- one such operation per batch and
-    # the batches in flight never overlap (measured: 14.9 k tiles/s instead of 24 k through this function).
-    prep = torch.cuda.Stream(device=dev) if (pool and torch.device(dev).type == 'cuda') else None
-    if prep is not None:
-        prep.wait_stream(torch.cuda.current_stream(dev))        # the caller's tensors were made there
-
-    def on_prep(fn):
-        def call():
-            if prep is None:
-                return fn()
-            with torch.cuda.stream(prep):
-                return fn()
-        return call
-    # Tiles arrive through a feeder thread: slides with a chunk source (TFRecords) are decoded 512 tiles at a time into a
-    # ring of three reusable pinned buffers and copied to the device on a stream of their own, two chunks ahead of the
-    # GPU; the native decoder releases the GIL, so decode, H2D copy and kernels overlap.  (Round 3 allocated a fresh
-    # page-locked tensor per slide and prefetched one slide.)
-    import contextlib
-    copy_stream = torch.cuda.Stream(device=dev) if torch.device(dev).type == 'cuda' else None
-
-    # gpu_decode: compressed chunks are inflated on the pool's decode streams (CU-masked: the compute units it keeps out of the
-    # inference streams; without a pool, the current stream), round-robin, each with its own table scratch; the status words are
-    # looked at one chunk late (check_z)
-    z_state = {'k': 0, 'scratch': {}, 'status': []}
-
-    def check_z(block):
-        while z_state['status'] and (block or z_state['status'][0][2].query()):
-            segs, status, ev2 = z_state['status'].pop(0)
-            ev2.synchronize()
-            bad = np.flatnonzero(status.numpy()).tolist()
-            if bad:
-                at, where = 0, None
-                for (_, si, first, c) in segs:
-                    if at <= bad[0] < at + c:
-                        where = f'{slides[si].name}, tile {first + bad[0] - at}'
-                    at += c
-                raise IOError(f'the device inflate refused {len(bad)} tile(s) (first: {where}, status {int(status[bad[0]])}): damaged PNG '
-                              f'data; decode on the host (gpu_decode=False) to see the decoder\'s own error')
-
-    def decode_z(buf, cap, count, ev, px, segs):
-        eng0 = engines[0]
-        dstreams = getattr(pool, 'decode_streams', None) if pool else None
-        main = torch.cuda.current_stream(dev)
-        dec = dstreams[z_state['k'] % len(dstreams)] if dstreams else main
-        z_state['k'] += 1
-        off = buf[:4 * count].view(torch.int32)
-        ln = buf[4 * cap:4 * cap + 4 * count].view(torch.int32)
-        z = buf[(8 * cap + 15) & ~15:]
-        dec.wait_event(ev)
-        buf.record_stream(dec)
-        key = dec.cuda_stream
-        with torch.cuda.stream(dec):
-            if key not in z_state['scratch'] or z_state['scratch'][key].numel() < eng0._lib.bq_png_inflate_scratch_bytes(count):
-                z_state['scratch'][key] = eng0.inflate_scratch(max(count, CHUNK_TILES_Z))
-            rows, status = eng0.png_inflate(z, off, ln, px=px, scratch=z_state['scratch'][key])
-            done = torch.cuda.Event()
-            done.record(dec)
-        main.wait_event(done)
-        rows.record_stream(main)
-        # the status words leave the device behind the inflate (a few KB, pinned, on the decode stream) and are looked at when the NEXT
-        # chunk arrives -- one chunk late, without stalling anything: a damaged stream stops the run there instead of after it
-        host = torch.empty(status.shape, dtype=status.dtype, pin_memory=True)
-        with torch.cuda.stream(dec):
-            host.copy_(status, non_blocking=True)
-            ev2 = torch.cuda.Event()
-            ev2.record(dec)
-        check_z(block=False)
-        z_state['status'].append((segs, host, ev2))
-        return eng0.png_unfilter_strided(rows, px=px)
-
-    def stream_slides():
-        nonlocal pend_n, rows_slide, rows_true
-        cur_stream = (lambda: torch.cuda.current_stream(dev)) if copy_stream is not None else None
-        def push(li, si, first, count, t):
-            nonlocal pend_n, rows_slide, rows_true
-            s = slides[si]
-            if count == 0:
-                return
-            if t is not None:                        # (None: the tiles are part of a tensor that is already in the list)
-                assert t.shape[0] == count, (s.name, t.shape, count)
-                pend_tiles.append(t)
-            pend_sidx.append(torch.full((count,), li, dtype=torch.int32, device=dev))
-            pend_gidx.append(offsets[si] + first + np.arange(count, dtype=np.int64))
-            pend_n += count
-            if table is not None:
-                pend_segs.append((si, s.name, int(s.y_true), np.asarray(s.loc)[first:first + count] if with_loc else None, count))
-            if keep_tiles:
-                rows_slide += [s.name] * count
-                rows_true += [s.y_true] * count
-                if s.loc is not None:
-                    rows_loc.append(np.asarray(s.loc)[first:first + count])
-
-        for li, si, first, count, loaded, ev, is_rows in _feed_chunks(slides, mine, dev, copy_stream):
-            if is_rows == 'z':                       # a compressed chunk: inflate on the decode CUs, un-filter here
-                segs, cap = li, si
-                t = decode_z(loaded, cap, count, ev, slides[segs[0][1]].source.tile_px, segs)
-                assert t.shape[0] == count == sum(c for *_, c in segs)
-                pend_tiles.append(t)
-                for (li, si, first, c) in segs:
-                    push(li, si, first, c, None)
-                flush()
-                continue
-            if ev is not None:                       # made on the copy stream: order it before this stream's work
-                cur_stream().wait_event(ev)
-                loaded.record_stream(cur_stream())
-                t = engines[0].png_unfilter(loaded) if is_rows else loaded.contiguous()
-            elif isinstance(loaded, PngRows):        # filtered PNG scanlines: H2D, then the filters are reversed on the device
-                t = engines[0].png_unfilter(_to_device(loaded.rows, dev))
-            else:
-                t = _to_device(loaded, dev)
-            push(li, si, first, count, t)
-            flush()
-        flush(final=True)
-
+    # from here to table.finish() a failure, wherever it surfaces, stops the writer thread and closes the file before it goes on up
     try:
-        with (torch.cuda.stream(prep) if prep is not None else contextlib.nullcontext()):
-            stream_slides()
+        run = _Batches(pool, engines, table, dev, n_local, slides, offsets, stain, batch=batch, mc_n=mc_n, seed=seed, mc_mode=mc_mode,
+                       tile_uq=tile_uq, normalizer=normalizer, norm_fit=norm_fit, keep_tiles=keep_tiles,
+                       headroom_every=headroom_every, headroom_min=headroom_min, range_screen=range_screen)
+        pending = _Pending()
+        inflate = _DeviceInflate(engines[0], pool, dev, slides)
+        # With a pool, everything this function itself enqueues (H2D copies, concatenations, a device-side loader) goes to
+        # a side stream, not to the default stream: the pool's CU-masked streams are ordinary (blocking) HIP streams, and
+        # an operation on the legacy default stream is a barrier across all of those -- one such operation per batch and
+        # the batches in flight never overlap (measured: 14.9 k tiles/s instead of 24 k through this function).
+        prep = torch.cuda.Stream(device=dev) if (pool and cuda) else None
+        if prep is not None:
+            prep.wait_stream(torch.cuda.current_stream(dev))        # the caller's tensors were made there
+        copy_stream = torch.cuda.Stream(device=dev) if cuda else None
+        with (torch.cuda.stream(prep) if prep is not None else contextlib.nullcontext()), \
+                contextlib.closing(iter(_Feeder(slides, mine, dev, copy_stream))) as chunks:
+            for chunk in chunks:
+                if chunk.kind == 'z':                    # a compressed chunk: inflate on the decode CUs, un-filter here
+                    px = slides[chunk.segs[0][1]].source.tile_px
+                    tiles = engines[0].png_unfilter_strided(inflate.decode(chunk, px), px=px)
+                elif chunk.event is None:                # as the slide's loader left them
+                    tiles = _to_device(chunk.data, dev)
+                else:                                    # made on the copy stream: order it before this stream's work
+                    torch.cuda.current_stream(dev).wait_event(chunk.event)
+                    chunk.data.record_stream(torch.cuda.current_stream(dev))
+                    tiles = chunk.data.contiguous()
+                if chunk.kind == 'rows':                 # filtered PNG scanlines: the filters are reversed on the device
+                    tiles = engines[0].png_unfilter(tiles)
+                sidx, gidx, segs = [], [], []
+                for li, si, first, count in chunk.segs:
+                    s = slides[si]
+                    if count == 0:
+                        continue
+                    sidx.append(torch.full((count,), li, dtype=torch.int32, device=dev))
+                    gidx.append(offsets[si] + first + np.arange(count, dtype=np.int64))
+                    if table is not None:
+                        segs.append((si, s.name, int(s.y_true), np.asarray(s.loc)[first:first + count] if with_loc else None, count))
+                    if keep_tiles:
+                        rows_slide += [s.name] * count
+                        rows_true += [s.y_true] * count
+                        if s.loc is not None:
+                            rows_loc.append(np.asarray(s.loc)[first:first + count])
+                if sidx:
+                    assert tiles.shape[0] == sum(len(g) for g in gidx), (chunk.segs, tiles.shape)
+                    pending.push(tiles, sidx, gidx, segs)
+                while pending.n >= batch:
+                    run.run(*pending.take(batch))
+            if pending.n:
+                run.run(*pending.take(pending.n))
+        if prep is not None:
+            torch.cuda.current_stream(dev).wait_stream(prep)
+        if pool:
+            pool.synchronize()
+        run.final_looks()
+        inflate.check(block=True)                        # what is left: the last chunks
+        live = [a for a in run.acc if a is not None]
+        if live:
+            # per-stream fixed-point accumulators are integers: their sum is exact and order-free
+            tot = live[0] if len(live) == 1 else tuple(sum(a[j] for a in live[1:]) + live[0][j] for j in range(3))
+            mp, mu, cnt = engines[0].slide_finish(tot)
+            mp, mu, cnt = mp.cpu().numpy(), mu.cpu().numpy(), cnt.cpu().numpy()
+        else:
+            mp = mu = np.zeros(0); cnt = np.zeros(0, dtype=np.int64)
     except BaseException:
         if table is not None:
             table.abort()
         raise
-    if prep is not None:
-        torch.cuda.current_stream(dev).wait_stream(prep)
-
-    if pool:
-        pool.synchronize()
-    if monitor:
-        try:
-            headroom_look(block=True)
-        except BaseException:
-            if table is not None:
-                table.abort()
-            raise
-    if screens:
-        # the last, partial interval of every engine: tapped here, on the engine's stream, and looked at at once
-        try:
-            for k, eng in enumerate(engines):
-                if pool:
-                    pool.run(k, lambda e, k=k: screen_tap(k, e, n_batches - 1))
-                else:
-                    screen_tap(k, eng, n_batches - 1)
-            screen_look(range(len(engines)))
-        except BaseException:
-            if table is not None:
-                table.abort()
-            raise
-    try:
-        check_z(block=True)                         # what is left: the last chunks
-    except BaseException:
-        if table is not None:
-            table.abort()
-        raise
-    live = [a for a in acc if a is not None]
-    if live:
-        # per-stream fixed-point accumulators are integers: their sum is exact and order-free
-        tot = live[0] if len(live) == 1 else tuple(sum(a[j] for a in live[1:]) + live[0][j] for j in range(3))
-        mp, mu, cnt = engines[0].slide_finish(tot)
-        mp, mu, cnt = mp.cpu().numpy(), mu.cpu().numpy(), cnt.cpu().numpy()
-    else:
-        mp = mu = np.zeros(0); cnt = np.zeros(0, dtype=np.int64)
     # this rank's rows are on disk and its file closed BEFORE the collective: whoever leaves the gather knows every shard is complete
     table_path, table_rows = None, 0
     if table is not None:
@@ -976,21 +979,17 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
         table_path = assemble_shards(save_dir, table_name)
     tile_df = None
     if keep_tiles:
-        mean = torch.cat(rows_mean).cpu().numpy() if rows_mean else np.zeros((0, 2), np.float32)
-        std = torch.cat(rows_std).cpu().numpy() if rows_std else np.zeros((0, 2), np.float32)
+        mean, std = torch.cat(run.rows, 1).cpu().numpy() if run.rows else np.zeros((2, 0, 2), np.float32)
         loc = np.concatenate(rows_loc) if rows_loc and sum(len(x) for x in rows_loc) == len(rows_slide) else None
         tile_df = tile_frame(outcome, rows_slide, rows_true, mean, std, loc if (with_loc or table is None) else None)
         if save_dir is not None and table is None:
             table_path = save_tile_predictions(tile_df, save_dir, table_name if world == 1 else shard_name(table_name, rank))
             table_rows = len(tile_df)
             if world > 1:                        # (pandas shards carry the same index, without byte ranges: row counts order them)
-                order, at = [], 0
-                for si in mine:
-                    if slides[si].n_tiles:
-                        order.append([si, slides[si].name, slides[si].n_tiles, 0, 0])
+                order = [[si, slides[si].name, slides[si].n_tiles, 0, 0] for si in mine if slides[si].n_tiles]
                 write_shard_index(table_path, rank, world, outcome, 'loc_x' in tile_df.columns, order)
-    n_pass = sum(int(c) for c in passthrough if c is not None)
+    n_pass = sum(int(c) for c in run.passthrough if c is not None)
     return EvalResult(tile_df, [s.name for s in slides], g_pred, g_unc, g_cnt,
-                      np.array([s.y_true for s in slides]), list(mine), table_path, table_rows, hr_state['min'], hr_state['checks'],
-                      n_pass, f16_screen_checks=sc_state['checks'], f16_screen_headroom=sc_state['min'],
-                      f16_screened=sum(s.screened for s in screens), f16_screen_max_key=sc_state['max_key'])
+                      np.array([s.y_true for s in slides]), list(mine), table_path, table_rows, run.monitor.min, run.monitor.checks,
+                      n_pass, f16_screen_checks=run.screen.checks, f16_screen_headroom=run.screen.min,
+                      f16_screened=sum(s.screened for s in run.screens), f16_screen_max_key=run.screen.max_key)

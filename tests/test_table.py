@@ -135,6 +135,22 @@ def test_a_nan_from_the_engine_fails_the_run(tmp_path):
         evaluate(NanEngine(), _slides(COUNTS), mc_n=30, seed=1, batch=8, save_dir=str(tmp_path), keep_tiles=False)
 
 
+def test_a_failure_behind_the_last_batch_leaves_no_thread_behind(tmp_path):
+    """An error that surfaces when the streams are synchronised (a HIP error of an earlier launch) stops the table writer and the
+    feeder like one inside the loop: the caller sees the pool's exception, and neither thread outlives the call."""
+    import threading
+
+    class StreamError(RuntimeError):
+        pass
+
+    class FailingPool(StandInPool):
+        def synchronize(self):
+            raise StreamError('a launch of an earlier batch failed')
+    with pytest.raises(StreamError):
+        evaluate(FailingPool(2), _slides(COUNTS), mc_n=30, seed=1, batch=8, save_dir=str(tmp_path), keep_tiles=False)
+    assert not [t.name for t in threading.enumerate() if t.is_alive() and t.name in ('bq-table-writer', 'bq-tile-feeder')]
+
+
 PARQUET = 'tile_predictions_eval.parquet.gzip'          # the other on-disk form the reference reads (utils.py:190-228)
 
 
