@@ -18,18 +18,70 @@ std::string g_create_error;
 
 struct Blob { const unsigned char* p = nullptr; size_t n = 0; };
 
-struct GemmLayer {
-    std::string name;
+constexpr int pad16(int c) { return (c + 15) / 16 * 16; }
+
+// ---- the matrix layers of Xception, in network order ---------------------------------------------------------------
+// What is fixed about each: bq_load_weights registers from this table, the backbone walks it, choose_route decides from it.
+enum LayerFlags : int {
+    F_RES = 1,         // adds the block's input (the third separable convolution of a middle-flow block)
+    F_DWTMP = 2,       // the walker has scratch for the depthwise kernel's output (two-kernel form)
+    F_SPLIT_TMP = 4,   // ... and for the partial sums of split-K
+    F_POOLED = 8       // feeds the global average pool
+};
+
+struct Layer {
+    const char* name;       // blob prefix; the debug-tap name of its output, except:
+    const char* out_name;   // the block output this layer completes ("blockN_out": shortcut rows, F_RES rows), or null
+    int cin, cout;          // true channels
+    int ldi, ldo;           // padded channels: the row strides of its input and output (elements)
+    int kpad;               // padded contraction length
+    int prod;               // BqProducer; PROD_DW*: has depthwise taps
+    int Hi, H;              // input / output map (square)
+    int relu;               // ReLU behind it
+    int flags;
+};
+
+#define SEP(name, out, cin, cout, prod, hw, relu, flags) {name, out, cin, cout, pad16(cin), pad16(cout), pad16(cin), prod, hw, hw, relu, flags}
+#define SHORTCUT(b, cin, cout, hi) {"block" #b "_res", "block" #b "_out", cin, cout, pad16(cin), pad16(cout), pad16(cin), PROD_S2, hi, (hi + 1) / 2, 0, 0}
+#define ENTRY(b, cin, cout, prod1, hw)                                                 \
+    SEP("block" #b "_sepconv1", nullptr, cin, cout, prod1, hw, 1, 0),                   \
+    SEP("block" #b "_sepconv2", nullptr, cout, cout, PROD_DW, hw, 0, 0),                \
+    SHORTCUT(b, cin, cout, hw)
+#define MIDDLE(b)                                                                      \
+    SEP("block" #b "_sepconv1", nullptr, 728, 728, PROD_DW_RELU, 19, 1, F_DWTMP),       \
+    SEP("block" #b "_sepconv2", nullptr, 728, 728, PROD_DW, 19, 1, F_DWTMP),            \
+    SEP("block" #b "_sepconv3", "block" #b "_out", 728, 728, PROD_DW, 19, 0, F_DWTMP | F_RES)
+const Layer kLayers[] = {
+    {"block1_conv2", nullptr, 32, 64, 32, 64, 288, PROD_IM2COL, 149, 147, 1, 0},
+    ENTRY(2, 64, 128, PROD_DW, 147),
+    ENTRY(3, 128, 256, PROD_DW_RELU, 74),
+    ENTRY(4, 256, 728, PROD_DW_RELU, 37),
+    MIDDLE(5), MIDDLE(6), MIDDLE(7), MIDDLE(8), MIDDLE(9), MIDDLE(10), MIDDLE(11), MIDDLE(12),
+    SEP("block13_sepconv1", nullptr, 728, 728, PROD_DW_RELU, 19, 1, 0),
+    SEP("block13_sepconv2", nullptr, 728, 1024, PROD_DW, 19, 0, 0),
+    SHORTCUT(13, 728, 1024, 19),
+    SEP("block14_sepconv1", nullptr, 1024, 1536, PROD_DW, 10, 1, F_DWTMP | F_SPLIT_TMP),
+    SEP("block14_sepconv2", nullptr, 1536, 2048, PROD_DW, 10, 1, F_DWTMP | F_SPLIT_TMP | F_POOLED),
+};
+#undef SEP
+#undef SHORTCUT
+#undef ENTRY
+#undef MIDDLE
+constexpr int kNumLayers = sizeof kLayers / sizeof kLayers[0];
+// first rows of the blocks the walker names: three rows per block up to block 13 (a strided block's third is its shortcut)
+constexpr int kConv2 = 0, kBlock2 = 1, kBlock5 = 10, kBlock13 = 34, kBlock14 = 37;
+static_assert(kNumLayers == 39, "block1_conv2, 34 separable convolutions, 4 shortcuts");
+
+struct GemmLayer {   // what the blob holds for row i of kLayers
     const void* wp = nullptr;
-    const void* wp16 = nullptr;   // the same weights in 16x16x32 fragment order (728 -> 728 layers, kernels_wide.hip)
+    const void* wp16 = nullptr;   // the same weights in 16x16x32 fragment order (kernels_wide / stream / exit.hip)
     const void* wp32 = nullptr;   // ... in 32x32x16 fragment order (strided shortcuts, kernels_respool.hip)
     const float* scale = nullptr;
     const float* bias = nullptr;
     const float* dw = nullptr;
-    int cin = 0, cout = 0;   // true channel counts
-    int kpad = 0;            // padded contraction length
     int nfp = 0;             // padded n-frags in wp
 };
+
 
 struct HeadLayer {
     const void* wh = nullptr; const void* wl = nullptr; const float* bias = nullptr; int k = 0;
@@ -47,7 +99,7 @@ struct bq_ctx {
     unsigned char* d_blob = nullptr;
     size_t blob_bytes = 0;
     std::map<std::string, Blob> entries;
-    std::map<std::string, GemmLayer> layers;
+    GemmLayer layers[kNumLayers];   // by row of kLayers
     const float* stem_w = nullptr; const float* stem_s = nullptr; const float* stem_b = nullptr;
     const void* front_ws16 = nullptr;   // "block1_conv1/w16" + "block1_conv2/wp16": the fused front kernel (kernels_front.hip)
     const void* front_wc16 = nullptr;
@@ -96,7 +148,6 @@ struct DeviceGuard {
 };
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline int pad16(int c) { return (c + 15) / 16 * 16; }
 inline bool is16(int dtype) { return dtype == BQ_DTYPE_BF16 || dtype == BQ_DTYPE_F16; }
 inline size_t esize(const bq_ctx* c) { return is16(c->cfg.dtype) ? 2 : 4; }
 
@@ -178,7 +229,7 @@ struct ProfScope {
     }
 };
 
-// ---- GEMM layer launch -----------------------------------------------------------
+// ---- routes: which kernel family runs a layer ------------------------------------------
 int pick_shape(const bq_ctx* c, int prod, int nfp) {
     if (prod == PROD_IM2COL) return SHAPE_A;
     if (is16(c->cfg.dtype)) {
@@ -200,156 +251,127 @@ int pick_shape(const bq_ctx* c, int prod, int nfp) {
     return SHAPE_H;
 }
 
-struct ConvArgs {
-    const char* layer;
-    int prod;
-    const void* in; void* out; const void* residual; void* split_tmp;
-    int n, H, W, Hi, Wi;   // output / input spatial dims
-    int ldi, ldo;          // row strides (elements)
-    int relu;
-    void* dwtmp = nullptr; // scratch for the two-kernel (depthwise + GEMM) form, >= n*H*W*ldi elements
-    float* gap_out = nullptr;   // round 4: global average pool as the GEMM's epilogue -> fp32 [n][ldo]; `out` is not written.
-    bool* gap_done = nullptr;   // set when that form ran (it needs the two-kernel path and H * W <= 128)
+enum RouteKind : int {
+    R_ERROR,
+    R_FRONT,               // uint8 tiles: staging + block1_conv1 + block1_conv2 in one kernel (kernels_front.hip)
+    R_STREAM,              // kernels_stream.hip
+    R_TILE,                // kernels_tile.hip, instance `tile_kind`
+    R_DW_THEN_EXIT,        // depthwise kernel (kernels_split.hip), then kernels_exit.hip
+    R_DW_THEN_TILED_GEMM,  // depthwise kernel, then the 128 x 128-tile GEMM (kernels_split.hip)
+    R_S2_TILED_GEMM,       // the tiled GEMM over the even pixels of the input map
+    R_WIDE,                // kernels_wide.hip
+    R_PIPE,                // kernels_pipe.hip
+    R_FUSED_GEMM,          // kernels_gemm.hip, `nsplit` launches over slices of K
+    // the end of a block with a strided shortcut (asked of its shortcut row):
+    R_BLOCK_TAIL,          // sepconv2 + max-pool + shortcut + add in one kernel (kernels_stream.hip); sepconv2 is not launched
+    R_POOL_GEMM,           // the shortcut as the tiled GEMM with the pooling pass as its store pass
+    R_RESPOOL,             // kernels_respool.hip
+    R_CONV_THEN_POOL       // the shortcut by its own route `conv`, then the pool + add kernel (kernels_misc.hip)
+};
+const char* const kRouteNames[] = {"ERROR", "FRONT", "STREAM", "TILE", "DW_THEN_EXIT", "DW_THEN_TILED_GEMM", "S2_TILED_GEMM", "WIDE",
+                                   "PIPE", "FUSED_GEMM", "BLOCK_TAIL", "POOL_GEMM", "RESPOOL", "CONV_THEN_POOL"};
+
+struct Route {
+    RouteKind kind = R_ERROR;
+    RouteKind conv = R_ERROR;   // the convolution's own route: `kind` itself unless kind == R_CONV_THEN_POOL
+    int tile_kind = -1;         // R_TILE
+    int nsplit = 1, shape = -1; // R_FUSED_GEMM
+    bool gap = false;           // R_DW_THEN_*: the global average pool is the GEMM's epilogue (GAP_EPILOGUE), the tensor is not written
+    int err = BQ_OK;            // R_ERROR: the code, its text in *why
 };
 
-int run_conv(bq_ctx* c, const ConvArgs& a, hipStream_t s) {
-    auto it = c->layers.find(a.layer);
-    if (it == c->layers.end()) return fail(c, BQ_ERR_WEIGHTS, std::string("layer not loaded: ") + a.layer);
-    const GemmLayer& L = it->second;
-    const int dtype = c->cfg.dtype;
-    const int shape = pick_shape(c, a.prod, L.nfp);
-    if (shape < 0) return fail(c, BQ_ERR_ARG, std::string("no kernel shape for ") + a.layer);
-    const int vec = is16(dtype) ? 8 : 4;
-    int nsplit = 1;
-    while (gemm_lds_bytes(dtype, shape, L.kpad / nsplit) > 160 * 1024) {
-        nsplit *= 2;
-        if ((L.kpad / nsplit) % (2 * vec) != 0 || nsplit > 8)
-            return fail(c, BQ_ERR_ARG, std::string("cannot split K for ") + a.layer);
-    }
-    if (nsplit > 1 && (a.residual || !a.split_tmp))
-        return fail(c, BQ_ERR_ARG, std::string("split-K needs a temp and no residual: ") + a.layer);
-
-    GemmParams p{};
-    p.in = a.in; p.wp = L.wp; p.dw = L.dw;
-    p.M = a.n * a.H * a.W;
-    p.KBtot = L.kpad / (2 * vec);
-    p.NFp = L.nfp; p.Nstore = a.ldo; p.ldo = a.ldo; p.ldi = a.ldi;
-    p.H = a.H; p.W = a.W; p.Hi = a.Hi; p.Wi = a.Wi;
-    const double es = (double)esize(c);
-    const double M = (double)p.M;
-    const bool dwp = a.prod == PROD_DW || a.prod == PROD_DW_RELU;
-    const double flops = 2.0 * M * L.cin * L.cout + (dwp ? 18.0 * M * L.cin : 0.0);
-    const double in_rows = (double)a.n * a.Hi * a.Wi;
-    const double kin = a.prod == PROD_IM2COL ? (double)a.ldi : (double)L.cin;
-    const double bytes = es * (in_rows * kin * (a.prod == PROD_S2 ? 0.25 : 1.0) + M * L.cout * (a.residual ? 2.0 : 1.0)) +
-                         es * (double)L.cin * L.cout;
-    char cls[96];
-    snprintf(cls, sizeof cls, "%s_k%d_n%d_%dx%d",
-             a.prod == PROD_S2 ? "res1x1s2" : (a.prod == PROD_IM2COL ? "conv3x3" : "sepconv"), L.cin,
-             L.cout, a.H, a.W);
-    // Two-kernel form (depthwise kernel + 128x128-tile GEMM): always for the wide exit-flow layers
-    // (K >= 1024: the fused kernel can only hold 32-64 rows of A in LDS there and re-streams the
-    // 3-6 MB weight matrix per 32-64 rows).
-    const bool will_split = L.kpad >= 1024 && is16(dtype) && dwp && L.nfp % 4 == 0 && a.dwtmp && nsplit == 1;
-    ProfScope ps(c, s, will_split ? std::string("split_") + cls : std::string(cls), will_split ? 0.0 : flops, will_split ? 0.0 : bytes);
-    // round 4: the 147x147 separable convolutions of block 2 on the streaming kernel (kernels_stream.hip)
-    if (dwp && L.wp16 && !a.residual && nsplit == 1 && a.H == a.Hi && a.W == a.Wi && a.ldi == L.kpad &&
-        a.ldo == L.cout && stream_supported(dtype, L.kpad, L.cout, a.prod == PROD_DW_RELU, a.n, a.H, a.W)) {
-        const int e = launch_sepconv_stream(dtype, L.kpad, L.cout, a.prod == PROD_DW_RELU, a.in, L.wp16, L.dw, L.scale, L.bias,
-                                            a.out, a.n, a.H, a.W, a.relu, c->num_cus, s);
-        if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch(stream) ") + a.layer + ": " +
-                                                   hipGetErrorString((hipError_t)e));
-        return BQ_OK;
-    }
-    if (is16(dtype) && !a.residual) {
-        int kind = -1;
-        if (a.prod == PROD_IM2COL && L.cin == 32 && L.cout == 64) kind = 0;
-        else if (a.prod == PROD_DW && L.cin == 64 && L.cout == 128) kind = 1;
-        else if (a.prod == PROD_DW && L.cin == 128 && L.cout == 128) kind = 2;
-        else if (a.prod == PROD_DW_RELU && L.cin == 128 && L.cout == 256 &&
-                 !(L.wp16 && a.H == a.Hi && a.W == a.Wi && nsplit == 1 &&
-                   wide_supported(dtype, a.prod, L.nfp, a.H, a.W, L.kpad, a.ldo, a.ldi, a.ldo, p.M, false)))
-            kind = 3;               // (block3_sepconv1: the wide kernel's 74x74 instance when its weights are there)
-        if (kind >= 0) {
-            const int e = launch_tile_conv(dtype, kind, a.in, L.wp, L.dw, L.scale, L.bias, a.out, a.n, a.H, a.W, a.Hi, a.Wi,
-                                           a.relu, c->num_cus, s);
-            if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch(tile) ") + a.layer + ": " +
-                                                       hipGetErrorString((hipError_t)e));
-            return BQ_OK;
-        }
-    }
-    if (will_split) {
-        {
-            ProfScope pd(c, s, std::string("dw3x3_") + cls, 18.0 * M * L.cin, 2.0 * es * M * L.cin);
-            const int e = launch_dw3x3(dtype, a.in, L.dw, a.dwtmp, a.n, a.H, a.W, a.ldi, a.prod == PROD_DW_RELU, s);
-            if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch(dw3x3) ") + a.layer);
-        }
-        const bool gap = a.gap_out && a.gap_done && !a.residual && a.H * a.W <= 128 && a.ldo == L.cout;
-        ProfScope pg(c, s, std::string(gap ? "gemm_gap_" : "gemm_") + cls, 2.0 * M * L.cin * L.cout + (gap ? M * L.cout : 0.0),
-                     gap ? es * M * L.cin + 4.0 * a.n * L.cout
-                         : es * (M * L.cin + M * L.cout * (a.residual ? 2.0 : 1.0)));
-        p.in = a.dwtmp; p.K = L.kpad; p.k_off = 0; p.kb0 = 0; p.gap_mul = c->feat_mul;
-        p.scale = L.scale; p.bias = L.bias; p.relu = a.relu; p.residual = a.residual; p.out = gap ? (void*)a.gap_out : a.out;
-        if (gap) *a.gap_done = true;
-        // round 4: one image's pixels x 256 channels per workgroup on 16x16x32 fragments (kernels_exit.hip) when the layer's
-        // weights are there in that order -- block 14
-        if (L.wp16 && !a.residual && a.ldi == L.kpad && a.ldo == L.cout &&
-            exit_supported(dtype, L.kpad, L.cout, a.H * a.W, a.n)) {
-            const int e = launch_exit_gemm(dtype, a.dwtmp, L.wp16, L.scale, L.bias, a.out, gap ? a.gap_out : nullptr, a.n,
-                                           a.H * a.W, L.kpad, L.cout, a.relu, c->feat_mul, s);
-            if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch(exit_gemm) ") + a.layer + ": " +
-                                                       hipGetErrorString((hipError_t)e));
-            return BQ_OK;
-        }
-        const int e = launch_gemm_tile(dtype, p, false, s, gap ? 1 : 0);
-        if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch(gemm_tile) ") + a.layer + ": " +
-                                                   hipGetErrorString((hipError_t)e));
-        return BQ_OK;
-    }
-    // strided shortcut convolutions with many channels (blocks 4 and 13: K = 256 / 736): a plain GEMM whose A rows are the
-    // even pixels of the input map -- the 128 x 128-tile kernel (block 13: 0.13 -> 0.085 ms against the fused-producer form; block 4: the same 0.09 ms)
-    if (a.prod == PROD_S2 && is16(dtype) && L.kpad >= 256 && L.nfp % 4 == 0 && nsplit == 1 && !a.residual) {
-        p.K = L.kpad; p.k_off = 0; p.kb0 = 0;
-        p.scale = L.scale; p.bias = L.bias; p.relu = a.relu; p.residual = nullptr; p.out = a.out;
-        const int e = launch_gemm_tile(dtype, p, true, s);
-        if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch(gemm_tile s2) ") + a.layer + ": " +
-                                                   hipGetErrorString((hipError_t)e));
-        return BQ_OK;
-    }
-    if (nsplit == 1 && L.wp16 && a.H == a.Hi && a.W == a.Wi &&
-        wide_supported(dtype, a.prod, L.nfp, a.H, a.W, L.kpad, a.ldo, a.ldi, a.ldo, p.M, a.residual != nullptr)) {
-        p.K = L.kpad; p.k_off = 0; p.kb0 = 0;
-        p.scale = L.scale; p.bias = L.bias; p.relu = a.relu; p.residual = a.residual; p.out = a.out;
-        const int e = launch_sepconv_wide(dtype, a.prod, p, L.wp16, c->num_cus, s);
-        if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch(wide) ") + a.layer + ": " +
-                                                   hipGetErrorString((hipError_t)e));
-        return BQ_OK;
-    }
-    if (nsplit == 1 && pipe_supported(dtype, a.prod, L.nfp, a.W, L.kpad)) {
-        p.K = L.kpad; p.k_off = 0; p.kb0 = 0;
-        p.scale = L.scale; p.bias = L.bias; p.relu = a.relu; p.residual = a.residual; p.out = a.out;
-        const int e = launch_sepconv_pipe(dtype, a.prod, p, s);
-        if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch(pipe) ") + a.layer + ": " +
-                                                   hipGetErrorString((hipError_t)e));
-        return BQ_OK;
-    }
-    for (int sp = 0; sp < nsplit; ++sp) {
-        const bool last = sp == nsplit - 1;
-        p.K = L.kpad / nsplit;
-        p.k_off = sp * p.K;
-        p.kb0 = sp * (p.K / (2 * vec));
-        p.scale = L.scale;
-        p.bias = last ? L.bias : nullptr;
-        p.relu = last ? a.relu : 0;
-        p.residual = last ? (nsplit > 1 ? a.split_tmp : a.residual) : (sp > 0 ? a.split_tmp : nullptr);
-        p.out = last ? a.out : a.split_tmp;
-        const int e = launch_gemm(dtype, a.prod, shape, p, s);
-        if (e != 0) return fail(c, BQ_ERR_HIP, std::string("launch ") + a.layer + ": " +
-                                                   hipGetErrorString((hipError_t)e));
-    }
-    return BQ_OK;
+// was one of these tensors, which a fusion does not write, asked for by a debug tap?
+bool wants(const char* tap, const char* a, const char* b = nullptr) {
+    return tap && (strcmp(tap, a) == 0 || (b && strcmp(tap, b) == 0));
 }
 
+bool has_front(const bq_ctx* c) { return is16(c->cfg.dtype) && c->front_ws16 && c->front_wc16 && c->layers[kConv2].wp; }
+
+// THE schedule: the route of layer `li` for a batch of n tiles.  `from_u8`: the walk starts from the uint8 tiles (block1_conv2
+// only); `tap`: the debug tap of this walk, or null.  Decides only: nothing is launched or allocated.  The order of the tests is
+// the specification -- the first route whose conditions hold wins.
+Route choose_route(const bq_ctx* c, int li, int n, bool from_u8, const char* tap, std::string* why) {
+    const Layer& L = kLayers[li];
+    const GemmLayer& G = c->layers[li];
+    const int dtype = c->cfg.dtype;
+    Route r;
+    auto error = [&](int code, const std::string& msg) { r.kind = r.conv = R_ERROR; r.err = code; *why = msg; return r; };
+    auto conv = [&](RouteKind k) { r.conv = k; if (r.kind != R_CONV_THEN_POOL) r.kind = k; return r; };
+    if (!G.wp) return error(BQ_ERR_WEIGHTS, std::string("layer not loaded: ") + L.name);
+    if (li == kConv2 && from_u8) {
+        if (!has_front(c)) return error(BQ_ERR_ARG, "the fused front kernel needs a 16-bit context with its weights loaded");
+        if (wants(tap, "staged", "block1_conv1"))
+            return error(BQ_ERR_ARG, "the fused front kernel does not materialise the staged tile or block1_conv1");
+        return conv(R_FRONT);
+    }
+    if (L.prod == PROD_S2) {   // a block's end
+        const Layer& L2 = kLayers[li - 1];   // the block's last separable convolution is the row in front of its shortcut
+        const GemmLayer& G2 = c->layers[li - 1];
+        if (!wants(tap, L2.name, L.name) && G2.wp16 && G.wp16 && L2.cout == L.ldo && L.cin == L.ldi &&
+            tail_supported(dtype, L.ldo, L.ldo, L.ldi, n, L.Hi, L.Hi))
+            return conv(R_BLOCK_TAIL);
+        const bool want_res = wants(tap, L.name);
+        // blocks 3, 4 and 13 (K = 128 / 256 / 736): the shortcut tensor never goes to HBM, one launch instead of two
+        // (block 3: 0.273 -> 0.242 ms against kernels_respool.hip; block 2, K = 64, lives in the fused tail)
+        if (is16(dtype) && !want_res && L.kpad >= 128 && G.nfp % 4 == 0) return conv(R_POOL_GEMM);
+        // kernels_respool.hip, measured per batch of 256 (one stream): block 2 0.62 -> 0.46 ms, block 3 0.34 -> 0.27 ms; block 4
+        // (K = 256, six 128-channel workgroups per pixel tile) 0.26 -> 0.34 ms and block 13 0.19 -> 0.20 ms stay off it
+        if (is16(dtype) && G.wp32 && !want_res && L.kpad <= 128) return conv(R_RESPOOL);
+        r.kind = R_CONV_THEN_POOL;
+    }
+    const bool residual = L.flags & F_RES, dwp = L.prod == PROD_DW || L.prod == PROD_DW_RELU, same = L.H == L.Hi;
+    const int vec = is16(dtype) ? 8 : 4, M = n * L.H * L.H;
+    r.shape = pick_shape(c, L.prod, G.nfp);
+    if (r.shape < 0) return error(BQ_ERR_ARG, std::string("no kernel shape for ") + L.name);
+    while (gemm_lds_bytes(dtype, r.shape, L.kpad / r.nsplit) > 160 * 1024) {
+        r.nsplit *= 2;
+        if ((L.kpad / r.nsplit) % (2 * vec) != 0 || r.nsplit > 8) return error(BQ_ERR_ARG, std::string("cannot split K for ") + L.name);
+    }
+    const int nsplit = r.nsplit;
+    if (nsplit > 1 && (residual || !(L.flags & F_SPLIT_TMP)))
+        return error(BQ_ERR_ARG, std::string("split-K needs a temp and no residual: ") + L.name);
+    // the 147x147 separable convolutions of block 2 and block3_sepconv1 on the streaming kernel
+    if (dwp && G.wp16 && !residual && nsplit == 1 && same && L.ldi == L.kpad && L.ldo == L.cout &&
+        stream_supported(dtype, L.kpad, L.cout, L.prod == PROD_DW_RELU, n, L.H, L.H))
+        return conv(R_STREAM);
+    if (is16(dtype) && !residual) {
+        if (L.prod == PROD_IM2COL && L.cin == 32 && L.cout == 64) r.tile_kind = 0;
+        else if (L.prod == PROD_DW && L.cin == 64 && L.cout == 128) r.tile_kind = 1;
+        else if (L.prod == PROD_DW && L.cin == 128 && L.cout == 128) r.tile_kind = 2;
+        else if (L.prod == PROD_DW_RELU && L.cin == 128 && L.cout == 256 &&
+                 !(G.wp16 && same && nsplit == 1 && wide_supported(dtype, L.prod, G.nfp, L.H, L.H, L.kpad, L.ldo, L.ldi, L.ldo, M, false)))
+            r.tile_kind = 3;        // (block3_sepconv1 when neither the streaming nor the wide kernel takes it)
+        if (r.tile_kind >= 0) return conv(R_TILE);
+    }
+    // Two-kernel form (depthwise kernel + GEMM): always for the wide exit-flow layers (K >= 1024: the fused kernel can only hold
+    // 32-64 rows of A in LDS there and re-streams the 3-6 MB weight matrix per 32-64 rows).  No STREAM or TILE layer is that wide.
+    if (L.kpad >= 1024 && is16(dtype) && dwp && G.nfp % 4 == 0 && (L.flags & F_DWTMP) && nsplit == 1) {
+        // the pool as the epilogue (one workgroup owns an image's pixels) unless the convolution's own output was asked for
+        r.gap = (L.flags & F_POOLED) && !wants(tap, L.name) && !residual && L.H * L.H <= 128 && L.ldo == L.cout;
+        // one image's pixels x 256 channels per workgroup on 16x16x32 fragments when the weights are there in that order: block 14
+        if (G.wp16 && !residual && L.ldi == L.kpad && L.ldo == L.cout && exit_supported(dtype, L.kpad, L.cout, L.H * L.H, n))
+            return conv(R_DW_THEN_EXIT);
+        return conv(R_DW_THEN_TILED_GEMM);
+    }
+    // strided shortcut convolutions with many channels (blocks 4 and 13: K = 256 / 736): a plain GEMM whose A rows are the even
+    // pixels of the input map (block 13: 0.13 -> 0.085 ms against the fused-producer form; block 4: the same 0.09 ms)
+    if (L.prod == PROD_S2 && is16(dtype) && L.kpad >= 256 && G.nfp % 4 == 0 && nsplit == 1 && !residual) return conv(R_S2_TILED_GEMM);
+    if (nsplit == 1 && G.wp16 && same && wide_supported(dtype, L.prod, G.nfp, L.H, L.H, L.kpad, L.ldo, L.ldi, L.ldo, M, residual))
+        return conv(R_WIDE);
+    if (nsplit == 1 && pipe_supported(dtype, L.prod, G.nfp, L.H, L.kpad)) return conv(R_PIPE);
+    return conv(R_FUSED_GEMM);
+}
+
+std::string route_text(const Route& r) {
+    std::string t = kRouteNames[r.kind];
+    if (r.kind == R_CONV_THEN_POOL) t += std::string(" ") + kRouteNames[r.conv];
+    if (r.conv == R_TILE) t += " kind=" + std::to_string(r.tile_kind);
+    if (r.conv == R_FUSED_GEMM) t += " nsplit=" + std::to_string(r.nsplit);
+    if (r.conv == R_DW_THEN_EXIT || r.conv == R_DW_THEN_TILED_GEMM) t += r.gap ? " GAP_EPILOGUE=yes" : " GAP_EPILOGUE=no";
+    return t;
+}
+
+// ---- one walk of the backbone ----------------------------------------------------------
 struct Tap {
     const char* want = nullptr;   // requested activation name (null: none)
     float* out = nullptr;
@@ -357,225 +379,304 @@ struct Tap {
     int64_t written = -1;
 };
 
-// returns 1 if the tap matched (caller stops), 0 otherwise, <0 on error
-int tap_nhwc(bq_ctx* c, Tap* t, const char* name, const void* buf, int n, int H, int W, int C, int ld,
-             hipStream_t s) {
-    if (!t || !t->want || strcmp(t->want, name) != 0) return 0;
-    const long long rows = (long long)n * H * W;
-    if ((size_t)(rows * C) > t->out_elems) return fail(c, BQ_ERR_ARG, "debug output too small");
-    const int e = launch_to_f32_nhwc(buf, rows, C, ld, t->out, c->cfg.dtype, s);
-    if (e) return fail(c, BQ_ERR_HIP, "debug copy failed");
+struct Walk {
+    bq_ctx* c; int n; hipStream_t s; Tap* tap;
+    std::string* plan;   // bq_describe_schedule: "<layer or tensor> <route>\n" per step instead of its launches
+    const char* want() const { return tap ? tap->want : nullptr; }
+    bool tapped() const { return tap && tap->written >= 0; }
+    void note(const char* what, const std::string& route) const { *plan += std::string(what) + " " + route + "\n"; }
+};
+
+// the route of layer li, or the failure; RUN-able
+int route_for(const Walk& w, int li, bool from_u8, Route* r) {
+    std::string why;
+    *r = choose_route(w.c, li, w.n, from_u8, w.want(), &why);
+    return r->kind == R_ERROR ? fail(w.c, r->err, why) : BQ_OK;
+}
+
+int launch_failed(bq_ctx* c, const char* what, const char* layer, int e) {
+    return fail(c, BQ_ERR_HIP, std::string(what) + layer + ": " + hipGetErrorString((hipError_t)e));
+}
+
+// returns 1 if the tap asks for this tensor (the walk stops), 0 otherwise, <0 on error
+int tap_nhwc(const Walk& w, const char* name, const void* buf, int H, int C, int ld) {
+    Tap* t = w.tap;
+    if (!wants(w.want(), name)) return 0;
+    const long long rows = (long long)w.n * H * H;
+    if (w.plan) { t->written = 0; return 1; }
+    if ((size_t)(rows * C) > t->out_elems) return fail(w.c, BQ_ERR_ARG, "debug output too small");
+    const int e = launch_to_f32_nhwc(buf, rows, C, ld, t->out, w.c->cfg.dtype, w.s);
+    if (e) return fail(w.c, BQ_ERR_HIP, "debug copy failed");
     t->written = rows * C;
     return 1;
 }
 
 #define RUN(expr) do { int _r = (expr); if (_r != BQ_OK) return _r; } while (0)
-#define TAP(name, buf, H, W, C, ld) \
-    do { int _t = tap_nhwc(c, tap, name, buf, n, H, W, C, ld, s); if (_t) return _t < 0 ? _t : BQ_OK; } while (0)
+#define TAP_AT(name, buf, H, C, ld) \
+    do { int _t = tap_nhwc(w, name, buf, H, C, ld); if (_t) return _t < 0 ? _t : BQ_OK; } while (0)
+// row li's output under `name`: the row's own, or that of the block output it completes
+#define TAP(name, li, buf) TAP_AT(name, buf, kLayers[li].H, kLayers[li].cout, kLayers[li].ldo)
 
-// End of a block with a strided shortcut: out = maxpool3x3/s2(y) + BN(conv1x1/s2(x)).  bf16: one kernel
-// (kernels_respool.hip) unless the shortcut tensor itself was asked for; otherwise the shortcut goes to `out` first and
-// the pooling pass adds to it in place.  x and out must not overlap.
-int block_end(bq_ctx* c, const char* res_name, const char* pool_name, const void* x, const void* y, void* out, int n,
-              int Hi, int ci, int co, int cout, hipStream_t s, Tap* tap, int* tapped) {
-    const int Ho = (Hi + 1) / 2;
+GemmParams gemm_params(const bq_ctx* c, int li, int n, const void* in, const void* residual, void* out) {
+    const Layer& L = kLayers[li];
+    const GemmLayer& G = c->layers[li];
+    GemmParams p{};
+    p.in = in; p.wp = G.wp; p.dw = G.dw; p.scale = G.scale; p.bias = G.bias; p.residual = residual; p.out = out;
+    p.M = n * L.H * L.H;
+    p.K = L.kpad; p.KBtot = L.kpad / (is16(c->cfg.dtype) ? 16 : 8); p.kb0 = 0; p.k_off = 0;
+    p.NFp = G.nfp; p.Nstore = L.ldo; p.ldo = L.ldo; p.ldi = L.ldi;
+    p.H = L.H; p.W = L.H; p.Hi = L.Hi; p.Wi = L.Hi; p.relu = L.relu;
+    return p;
+}
+
+// What the walker has for a convolution; the row's flags say which of the optional ones it takes.
+struct ConvBufs {
+    const void* in; void* out;
+    const void* residual = nullptr;   // F_RES
+    void* split_tmp = nullptr;        // F_SPLIT_TMP: partial sums of split-K
+    void* dwtmp = nullptr;            // F_DWTMP: the depthwise kernel's output, >= n*H*W*ldi elements
+    float* gap_out = nullptr;         // F_POOLED: fp32 [n][ldo] of the pooling epilogue; `out` is not written then
+};
+
+int launch_conv(const Walk& w, int li, const Route& rt, const ConvBufs& b) {
+    bq_ctx* c = w.c;
+    const Layer& L = kLayers[li];
+    const GemmLayer& G = c->layers[li];
+    if (w.plan) { w.note(L.prod == PROD_S2 ? L.out_name : L.name, route_text(rt)); return BQ_OK; }
+    const int dtype = c->cfg.dtype, n = w.n, vec = is16(dtype) ? 8 : 4;
+    hipStream_t s = w.s;
+    const void* residual = (L.flags & F_RES) ? b.residual : nullptr;
+    void* dwtmp = (L.flags & F_DWTMP) ? b.dwtmp : nullptr;
+    void* split_tmp = (L.flags & F_SPLIT_TMP) ? b.split_tmp : nullptr;
+    GemmParams p = gemm_params(c, li, n, b.in, residual, b.out);
     const double es = (double)esize(c);
-    auto it = c->layers.find(res_name);
-    if (it == c->layers.end()) return fail(c, BQ_ERR_WEIGHTS, std::string("layer not loaded: ") + res_name);
-    const GemmLayer& L = it->second;
-    const bool want_res = tap && tap->want && strcmp(tap->want, res_name) == 0;
-    *tapped = 0;
-    // round 4: the shortcuts of blocks 3, 4 and 13 (K = 128 / 256 / 736) as the tiled GEMM with the pooling pass as its store pass
-    // (kernels_split.hip, EPI_POOL): the shortcut tensor never goes to HBM, one launch instead of two
-    constexpr int kPoolGemmMinK = 128;   // block 3 (K = 128) too: 0.273 -> 0.242 ms against kernels_respool.hip; block 2 (K = 64) lives in the fused tail
-    if (is16(c->cfg.dtype) && !want_res && L.kpad >= kPoolGemmMinK && L.nfp % 4 == 0) {
-        const double px = (double)n * Ho * Ho;
-        GemmParams p{};
-        p.in = x; p.wp = L.wp; p.scale = L.scale; p.bias = L.bias; p.residual = y; p.out = out;
-        p.M = n * Ho * Ho; p.K = L.kpad; p.KBtot = L.kpad / 16; p.kb0 = 0; p.k_off = 0;
-        p.NFp = L.nfp; p.Nstore = co; p.ldo = co; p.ldi = ci;
-        p.H = Ho; p.W = Ho; p.Hi = Hi; p.Wi = Hi; p.relu = 0;
-        ProfScope ps(c, s, std::string("respool_") + std::to_string(Hi) + "_c" + std::to_string(cout),
-                     2.0 * px * L.cin * L.cout + 9.0 * px * co,
-                     es * ((double)n * Hi * Hi * co + px * co + px * ci) + es * (double)L.cin * L.cout);
-        const int e = launch_gemm_tile(c->cfg.dtype, p, true, s, 2);
-        if (e) return fail(c, BQ_ERR_HIP, std::string("launch(gemm_tile pool) ") + res_name + ": " + hipGetErrorString((hipError_t)e));
-        return BQ_OK;
+    const double M = (double)p.M;
+    const bool dwp = L.prod == PROD_DW || L.prod == PROD_DW_RELU;
+    const double flops = 2.0 * M * L.cin * L.cout + (dwp ? 18.0 * M * L.cin : 0.0);
+    const double in_rows = (double)n * L.Hi * L.Hi;
+    const double kin = L.prod == PROD_IM2COL ? (double)L.ldi : (double)L.cin;
+    const double bytes = es * (in_rows * kin * (L.prod == PROD_S2 ? 0.25 : 1.0) + M * L.cout * (residual ? 2.0 : 1.0)) +
+                         es * (double)L.cin * L.cout;
+    char cls[96];
+    snprintf(cls, sizeof cls, "%s_k%d_n%d_%dx%d",
+             L.prod == PROD_S2 ? "res1x1s2" : (L.prod == PROD_IM2COL ? "conv3x3" : "sepconv"), L.cin, L.cout, L.H, L.H);
+    const bool two = rt.conv == R_DW_THEN_EXIT || rt.conv == R_DW_THEN_TILED_GEMM;   // its two kernels have scopes of their own
+    ProfScope ps(c, s, two ? std::string("split_") + cls : std::string(cls), two ? 0.0 : flops, two ? 0.0 : bytes);
+    const char* what = "launch ";
+    int e = 0;
+    switch (rt.conv) {
+    case R_STREAM:
+        what = "launch(stream) ";
+        e = launch_sepconv_stream(dtype, L.kpad, L.cout, L.prod == PROD_DW_RELU, b.in, G.wp16, G.dw, G.scale, G.bias, b.out, n, L.H, L.H,
+                                  L.relu, c->num_cus, s);
+        break;
+    case R_TILE:
+        what = "launch(tile) ";
+        e = launch_tile_conv(dtype, rt.tile_kind, b.in, G.wp, G.dw, G.scale, G.bias, b.out, n, L.H, L.H, L.Hi, L.Hi, L.relu, c->num_cus, s);
+        break;
+    case R_DW_THEN_EXIT:
+    case R_DW_THEN_TILED_GEMM: {
+        const bool gap = rt.gap;
+        {
+            ProfScope pd(c, s, std::string("dw3x3_") + cls, 18.0 * M * L.cin, 2.0 * es * M * L.cin);
+            what = "launch(dw3x3) ";
+            e = launch_dw3x3(dtype, b.in, G.dw, dwtmp, n, L.H, L.H, L.ldi, L.prod == PROD_DW_RELU, s);
+        }
+        if (e) break;
+        ProfScope pg(c, s, std::string(gap ? "gemm_gap_" : "gemm_") + cls, 2.0 * M * L.cin * L.cout + (gap ? M * L.cout : 0.0),
+                     gap ? es * M * L.cin + 4.0 * n * L.cout : es * (M * L.cin + M * L.cout * (residual ? 2.0 : 1.0)));
+        if (rt.conv == R_DW_THEN_EXIT) {
+            what = "launch(exit_gemm) ";
+            e = launch_exit_gemm(dtype, dwtmp, G.wp16, G.scale, G.bias, b.out, gap ? b.gap_out : nullptr, n, L.H * L.H, L.kpad, L.cout,
+                                 L.relu, c->feat_mul, s);
+        } else {
+            p.in = dwtmp; p.gap_mul = c->feat_mul;
+            if (gap) p.out = b.gap_out;
+            what = "launch(gemm_tile) ";
+            e = launch_gemm_tile(dtype, p, false, s, gap ? 1 : 0);
+        }
+        break;
     }
-    // kernels_respool.hip, measured per batch of 256 (one stream): block 2 0.62 -> 0.46 ms, block 3 0.34 -> 0.27 ms; block 4
-    // (K = 256, six 128-channel workgroups per pixel tile) 0.26 -> 0.34 ms and block 13 0.19 -> 0.20 ms stay off it
-    if (is16(c->cfg.dtype) && L.wp32 && !want_res && L.kpad <= 128) {
-        const double px = (double)n * Ho * Ho;
-        ProfScope ps(c, s, std::string("respool_") + std::to_string(Hi) + "_c" + std::to_string(cout),
-                     2.0 * px * L.cin * L.cout + 9.0 * px * co,
-                     es * ((double)n * Hi * Hi * co + px * co + px * ci) + es * (double)L.cin * L.cout);
-        const int e = launch_respool(c->cfg.dtype, x, L.wp32, L.scale, L.bias, y, out, n, Hi, Hi, L.kpad, ci, co, L.nfp, s);
-        if (e) return fail(c, BQ_ERR_HIP, std::string("launch(respool) ") + res_name + ": " + hipGetErrorString((hipError_t)e));
-        return BQ_OK;
+    case R_S2_TILED_GEMM:
+        what = "launch(gemm_tile s2) ";
+        e = launch_gemm_tile(dtype, p, true, s);
+        break;
+    case R_WIDE:
+        what = "launch(wide) ";
+        e = launch_sepconv_wide(dtype, L.prod, p, G.wp16, c->num_cus, s);
+        break;
+    case R_PIPE:
+        what = "launch(pipe) ";
+        e = launch_sepconv_pipe(dtype, L.prod, p, s);
+        break;
+    case R_FUSED_GEMM:
+        for (int sp = 0; sp < rt.nsplit && e == 0; ++sp) {
+            const bool last = sp == rt.nsplit - 1;
+            p.K = L.kpad / rt.nsplit;
+            p.k_off = sp * p.K;
+            p.kb0 = sp * (p.K / (2 * vec));
+            p.bias = last ? G.bias : nullptr;
+            p.relu = last ? L.relu : 0;
+            p.residual = last ? (rt.nsplit > 1 ? split_tmp : residual) : (sp > 0 ? split_tmp : nullptr);
+            p.out = last ? b.out : split_tmp;
+            e = launch_gemm(dtype, L.prod, rt.shape, p, s);
+        }
+        break;
+    default:
+        return fail(c, BQ_ERR_ARG, std::string("not a convolution's route: ") + L.name);
     }
+    return e != 0 ? launch_failed(c, what, L.name, e) : BQ_OK;
+}
+
+// *gap: the layer's route pooled its output into b.gap_out
+int run_conv(const Walk& w, int li, const ConvBufs& b, bool* gap = nullptr) {
+    Route rt;
+    RUN(route_for(w, li, false, &rt));
+    if (gap) *gap = rt.gap;
+    return launch_conv(w, li, rt, b);
+}
+
+// uint8 tiles -> block1_conv2 (R_FRONT): the tiles' statistics, then staging + block1_conv1 + block1_conv2 as one kernel
+int launch_front_route(const Walk& w, const uint8_t* u8, void* out) {
+    bq_ctx* c = w.c;
+    const int n = w.n;
+    const GemmLayer& G = c->layers[kConv2];
+    if (w.plan) { w.note(kLayers[kConv2].name, kRouteNames[R_FRONT]); return BQ_OK; }
     {
-        const int r = run_conv(c, {res_name, PROD_S2, x, out, nullptr, nullptr, n, Ho, Ho, Hi, Hi, ci, co, 0}, s);
-        if (r != BQ_OK) return r;
-        const int t = tap_nhwc(c, tap, res_name, out, n, Ho, Ho, cout, co, s);
-        if (t) { *tapped = 1; return t < 0 ? t : BQ_OK; }
+        ProfScope ps(c, w.s, "stage_stats", 2.0 * n * kStaged, (double)n * kStaged);
+        if (launch_stage_stats(u8, n, 299, c->d_stage_stats, w.s)) return fail(c, BQ_ERR_HIP, "stage stats launch failed");
     }
-    const double px = (double)n * Ho * Ho * co;
-    ProfScope ps(c, s, pool_name, 9.0 * px, es * ((double)n * Hi * Hi * co + 2.0 * px));
-    if (launch_pool_add(y, out, out, n, Hi, Hi, co, c->cfg.dtype, s)) return fail(c, BQ_ERR_HIP, "pool_add launch failed");
-    return BQ_OK;
+    const double p1 = (double)n * 149 * 149, p2 = (double)n * 147 * 147;
+    ProfScope ps(c, w.s, "front_stage_stem_conv2", 2.0 * p1 * 27 * 32 + 2.0 * p2 * 288 * 64 + 4.0 * n * kStaged,
+                 (double)n * kStaged + (double)esize(c) * p2 * 64);
+    const int e = launch_front(c->cfg.dtype, u8, reinterpret_cast<const unsigned long long*>(c->d_stage_stats), c->front_ws16, c->stem_s,
+                               c->stem_b, c->front_wc16, G.scale, G.bias, out, n, c->num_cus, w.s);
+    return e ? launch_failed(c, "launch(front)", "", e) : BQ_OK;
 }
 
-// Stem + entry flow (blocks 1-4) of n tiles.  A/B/C/R are scratch for n tiles; the block-4 output
-// (19x19x736 per tile) goes to out4.  Returns 1 if a debug tap matched (caller stops).
-// u8 != nullptr: the uint8 tiles themselves -- staging, block1_conv1 and block1_conv2 run as ONE kernel (kernels_front.hip;
-// `in_nchw` is not read) when its weights are loaded
-int entry_flow(bq_ctx* c, const void* in_nchw, int n, void* out4, void* A, void* B, void* C, void* R,
-               hipStream_t s, Tap* tap, const uint8_t* u8 = nullptr) {
-    const int dt = c->cfg.dtype;
-    const double es = (double)esize(c);
-    if (u8) {
-        auto l2 = c->layers.find("block1_conv2");
-        if (!c->front_ws16 || !c->front_wc16 || l2 == c->layers.end() || !is16(dt))
-            return fail(c, BQ_ERR_ARG, "the fused front kernel needs a 16-bit context with its weights loaded");
-        if (tap && tap->want && (strcmp(tap->want, "staged") == 0 || strcmp(tap->want, "block1_conv1") == 0))
-            return fail(c, BQ_ERR_ARG, "the fused front kernel does not materialise the staged tile or block1_conv1");
-        {
-            ProfScope ps(c, s, "stage_stats", 2.0 * n * kStaged, (double)n * kStaged);
-            if (launch_stage_stats(u8, n, 299, c->d_stage_stats, s)) return fail(c, BQ_ERR_HIP, "stage stats launch failed");
-        }
-        {
-            const double p1 = (double)n * 149 * 149, p2 = (double)n * 147 * 147;
-            ProfScope ps(c, s, "front_stage_stem_conv2", 2.0 * p1 * 27 * 32 + 2.0 * p2 * 288 * 64 + 4.0 * n * kStaged,
-                         (double)n * kStaged + es * p2 * 64);
-            const int e = launch_front(dt, u8, reinterpret_cast<const unsigned long long*>(c->d_stage_stats), c->front_ws16, c->stem_s,
-                                       c->stem_b, c->front_wc16, l2->second.scale, l2->second.bias, B, n, c->num_cus, s);
-            if (e) return fail(c, BQ_ERR_HIP, std::string("launch(front): ") + hipGetErrorString((hipError_t)e));
-        }
-    } else {
-    if (tap && tap->want && strcmp(tap->want, "staged") == 0) {
-        if ((size_t)n * kStaged > tap->out_elems) return fail(c, BQ_ERR_ARG, "debug output too small");
-        if (launch_nchw_to_f32_nhwc(in_nchw, n, 3, 299 * 299, tap->out, dt, s))
-            return fail(c, BQ_ERR_HIP, "debug copy failed");
-        tap->written = (int64_t)n * kStaged;
+// End of a block with a strided shortcut (row li), by route rt: out = maxpool3x3/s2(sepconv2) + BN(conv1x1/s2(x)).  y: sepconv2's
+// output -- R_BLOCK_TAIL: sepconv1's, the tail runs sepconv2 itself.  R_CONV_THEN_POOL puts the shortcut into `out` first (where
+// a tap finds it) and the pooling pass adds to it in place.  x and out must not overlap.
+int launch_block_end(const Walk& w, int li, const Route& rt, const void* x, const void* y, void* out) {
+    bq_ctx* c = w.c;
+    const Layer& L = kLayers[li];
+    const GemmLayer& G = c->layers[li];
+    const GemmLayer& G2 = c->layers[li - 1];
+    const int dtype = c->cfg.dtype, n = w.n, ci = L.ldi, co = L.ldo;
+    hipStream_t s = w.s;
+    const double es = (double)esize(c), M = (double)n * L.Hi * L.Hi, Mo = (double)n * L.H * L.H;
+    if (rt.kind == R_CONV_THEN_POOL) {
+        RUN(launch_conv(w, li, rt, {x, out}));
+        TAP(L.name, li, out);
+        if (w.plan) return BQ_OK;
+        char cls[64];
+        snprintf(cls, sizeof cls, "maxpool_add_%d_c%d", L.Hi, L.cout);
+        ProfScope ps(c, s, cls, 9.0 * Mo * co, es * ((double)n * L.Hi * L.Hi * co + 2.0 * Mo * co));
+        if (launch_pool_add(y, out, out, n, L.Hi, L.Hi, co, dtype, s)) return fail(c, BQ_ERR_HIP, "pool_add launch failed");
         return BQ_OK;
     }
-    {   // block1_conv1 + bn + relu  (vector ALU)
-        const double px = (double)n * 149 * 149;
-        ProfScope ps(c, s, "stem_conv1_3x3s2", 2.0 * px * 27 * 32, es * ((double)n * kStaged + px * 32));
-        if (launch_stem1(in_nchw, n, c->stem_w, c->stem_s, c->stem_b, A, dt, s))
-            return fail(c, BQ_ERR_HIP, "stem1 launch failed");
+    if (w.plan) { w.note(L.out_name, route_text(rt)); return BQ_OK; }
+    if (rt.kind == R_BLOCK_TAIL) {
+        char cls[64];
+        snprintf(cls, sizeof cls, "blocktail_%d_c%d", L.Hi, L.cout);
+        ProfScope ps(c, s, cls, 2.0 * M * co * co + 18.0 * M * co + 2.0 * Mo * ci * co + 9.0 * Mo * co,
+                     es * (M * co + Mo * ci + Mo * co) + es * ((double)co * co + (double)ci * co));
+        const int e = launch_block_tail(dtype, co, co, ci, y, G2.wp16, G2.dw, G2.scale, G2.bias, x, G.wp16, G.scale, G.bias, out, n,
+                                        L.Hi, L.Hi, c->num_cus, s);
+        return e ? launch_failed(c, "launch(block tail) ", kLayers[li - 1].name, e) : BQ_OK;
     }
-    TAP("block1_conv1", A, 149, 149, 32, 32);
-    RUN(run_conv(c, {"block1_conv2", PROD_IM2COL, A, B, nullptr, nullptr, n, 147, 147, 149, 149, 32, 64, 1}, s));
+    ProfScope ps(c, s, std::string("respool_") + std::to_string(L.Hi) + "_c" + std::to_string(L.cout),
+                 2.0 * Mo * L.cin * L.cout + 9.0 * Mo * co, es * ((double)n * L.Hi * L.Hi * co + Mo * co + Mo * ci) + es * (double)L.cin * L.cout);
+    if (rt.kind == R_POOL_GEMM) {
+        const int e = launch_gemm_tile(dtype, gemm_params(c, li, n, x, y, out), true, s, 2);
+        return e ? launch_failed(c, "launch(gemm_tile pool) ", L.name, e) : BQ_OK;
     }
-    TAP("block1_conv2", B, 147, 147, 64, 64);
+    const int e = launch_respool(dtype, x, G.wp32, G.scale, G.bias, y, out, n, L.Hi, L.Hi, L.kpad, ci, co, G.nfp, s);
+    return e ? launch_failed(c, "launch(respool) ", L.name, e) : BQ_OK;
+}
 
-    // entry flow: blocks 2-4.  The block's input lives in `cur`, its output goes to `nxt` (block 4: out4)
-    struct Entry { int block, cin, cout, Hi; };
-    const Entry entry[3] = {{2, 64, 128, 147}, {3, 128, 256, 74}, {4, 256, 728, 37}};
-    void* cur = B; void* nxt = R;
-    for (const Entry& e : entry) {
-        const int Ho = (e.Hi + 1) / 2;
-        const int ci = pad16(e.cin), co = pad16(e.cout);
-        char nm[64], rn[64], tn[64];
-        snprintf(nm, sizeof nm, "block%d_sepconv1", e.block);
-        RUN(run_conv(c, {nm, e.block == 2 ? PROD_DW : PROD_DW_RELU, cur, A, nullptr, nullptr, n, e.Hi, e.Hi,
-                         e.Hi, e.Hi, ci, co, 1}, s));
-        TAP(nm, A, e.Hi, e.Hi, e.cout, co);
-        snprintf(nm, sizeof nm, "block%d_sepconv2", e.block);
-        snprintf(rn, sizeof rn, "block%d_res", e.block);
-        void* dst = e.block == 4 ? out4 : nxt;
-        {   // round 4: the block's tail in one kernel (kernels_stream.hip) -- sepconv2 + BN, max-pool, shortcut conv + BN, add --
-            // unless the tensors it no longer writes were asked for
-            auto l2 = c->layers.find(nm), lr = c->layers.find(rn);
-            const bool want_mid = tap && tap->want && (strcmp(tap->want, nm) == 0 || strcmp(tap->want, rn) == 0);
-            if (!want_mid && l2 != c->layers.end() && lr != c->layers.end() && l2->second.wp16 && lr->second.wp16 &&
-                e.cout == co && e.cin == ci && tail_supported(dt, co, co, ci, n, e.Hi, e.Hi)) {
-                const double M = (double)n * e.Hi * e.Hi, Mo = (double)n * Ho * Ho;
-                char cls[64];
-                snprintf(cls, sizeof cls, "blocktail_%d_c%d", e.Hi, e.cout);
-                {
-                    ProfScope ps(c, s, cls, 2.0 * M * co * co + 18.0 * M * co + 2.0 * Mo * ci * co + 9.0 * Mo * co,
-                                 es * (M * co + Mo * ci + Mo * co) + es * ((double)co * co + (double)ci * co));
-                    const int er = launch_block_tail(dt, co, co, ci, A, l2->second.wp16, l2->second.dw, l2->second.scale,
-                                                     l2->second.bias, cur, lr->second.wp16, lr->second.scale, lr->second.bias, dst,
-                                                     n, e.Hi, e.Hi, c->num_cus, s);
-                    if (er) return fail(c, BQ_ERR_HIP, std::string("launch(block tail) ") + nm + ": " + hipGetErrorString((hipError_t)er));
-                }
-                snprintf(nm, sizeof nm, "block%d_out", e.block);
-                TAP(nm, dst, Ho, Ho, e.cout, co);
-                void* t = cur; cur = nxt; nxt = t;
-                continue;
-            }
-        }
-        RUN(run_conv(c, {nm, PROD_DW, A, C, nullptr, nullptr, n, e.Hi, e.Hi, e.Hi, e.Hi, co, co, 0}, s));
-        TAP(nm, C, e.Hi, e.Hi, e.cout, co);
-        snprintf(tn, sizeof tn, "maxpool_add_%d_c%d", e.Hi, e.cout);
-        int tapped = 0;
-        RUN(block_end(c, rn, tn, cur, C, dst, n, e.Hi, ci, co, e.cout, s, tap, &tapped));
-        if (tapped) return BQ_OK;
-        snprintf(nm, sizeof nm, "block%d_out", e.block);
-        TAP(nm, dst, Ho, Ho, e.cout, co);
-        void* t = cur; cur = nxt; nxt = t;
+// One block with a strided shortcut: rows s1 (first separable convolution), s1 + 1, s1 + 2 (shortcut).  x -> out; t1, t2: scratch.
+int strided_block(const Walk& w, int s1, const void* x, void* t1, void* t2, void* out) {
+    RUN(run_conv(w, s1, {x, t1}));
+    TAP(kLayers[s1].name, s1, t1);
+    Route end;
+    RUN(route_for(w, s1 + 2, false, &end));
+    if (end.kind != R_BLOCK_TAIL) {
+        RUN(run_conv(w, s1 + 1, {t1, t2}));
+        TAP(kLayers[s1 + 1].name, s1 + 1, t2);
     }
+    RUN(launch_block_end(w, s1 + 2, end, x, end.kind == R_BLOCK_TAIL ? t1 : t2, out));
+    if (w.tapped()) return BQ_OK;
+    TAP(kLayers[s1 + 2].out_name, s1 + 2, out);
     return BQ_OK;
 }
 
-int backbone_impl(bq_ctx* c, const void* in_nchw, int n, float* feat, unsigned char* ws, hipStream_t s,
-                  Tap* tap, const uint8_t* u8 = nullptr) {
+// The backbone of w.n tiles, walking kLayers in order: in_nchw (the staged planar tensor) or, u8 != nullptr, the uint8 tiles
+// themselves -> feat.  Stops behind the tensor w.tap asks for.
+int backbone_impl(const Walk& w, const void* in_nchw, float* feat, unsigned char* ws, const uint8_t* u8 = nullptr) {
+    bq_ctx* c = w.c;
+    const int n = w.n, dt = c->cfg.dtype;
+    hipStream_t s = w.s;
     const WsLayout L = ws_layout(c, n, 1);
-    void* A = ws + L.a; void* B = ws + L.b; void* C = ws + L.c; void* R = ws + L.r;
-    const int dt = c->cfg.dtype;
+    auto at = [&](size_t off) { return reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(ws) + off); };   // (ws is null under w.plan)
+    void* A = at(L.a); void* B = at(L.b); void* C = at(L.c); void* R = at(L.r);
     const double es = (double)esize(c);
-    // Block 4 reads its input from B (blocks 2-4 alternate between B and R) and must not write over it: its output goes
-    // to R, and B is the scratch buffer S of the middle and exit flow.
-    void* X4 = R;
-    void* S = B;
-    RUN(entry_flow(c, in_nchw, n, X4, A, B, C, R, s, tap, u8));
-    if (tap && tap->written >= 0) return BQ_OK;
-    // middle flow: blocks 5-12 at 19x19x728 (stride 736)
-    void* X = X4; void* Y = A;
-    for (int block = 5; block <= 12; ++block) {
-        char nm[64];
-        snprintf(nm, sizeof nm, "block%d_sepconv1", block);
-        RUN(run_conv(c, {nm, PROD_DW_RELU, X, Y, nullptr, nullptr, n, 19, 19, 19, 19, 736, 736, 1, S}, s));
-        TAP(nm, Y, 19, 19, 728, 736);
-        snprintf(nm, sizeof nm, "block%d_sepconv2", block);
-        RUN(run_conv(c, {nm, PROD_DW, Y, C, nullptr, nullptr, n, 19, 19, 19, 19, 736, 736, 1, S}, s));
-        TAP(nm, C, 19, 19, 728, 736);
-        snprintf(nm, sizeof nm, "block%d_sepconv3", block);
-        RUN(run_conv(c, {nm, PROD_DW, C, Y, X, nullptr, n, 19, 19, 19, 19, 736, 736, 0, S}, s));
+    Route front;
+    RUN(route_for(w, kConv2, u8 != nullptr, &front));
+    if (front.kind == R_FRONT) {
+        RUN(launch_front_route(w, u8, B));
+    } else {
+        if (wants(w.want(), "staged")) {
+            if (w.plan) { w.tap->written = 0; return BQ_OK; }
+            if ((size_t)n * kStaged > w.tap->out_elems) return fail(c, BQ_ERR_ARG, "debug output too small");
+            if (launch_nchw_to_f32_nhwc(in_nchw, n, 3, 299 * 299, w.tap->out, dt, s)) return fail(c, BQ_ERR_HIP, "debug copy failed");
+            w.tap->written = (int64_t)n * kStaged;
+            return BQ_OK;
+        }
+        if (!w.plan) {   // block1_conv1 + bn + relu  (vector ALU)
+            const double px = (double)n * 149 * 149;
+            ProfScope ps(c, s, "stem_conv1_3x3s2", 2.0 * px * 27 * 32, es * ((double)n * kStaged + px * 32));
+            if (launch_stem1(in_nchw, n, c->stem_w, c->stem_s, c->stem_b, A, dt, s)) return fail(c, BQ_ERR_HIP, "stem1 launch failed");
+        }
+        TAP_AT("block1_conv1", A, 149, 32, 32);   // (not a matrix layer: no row)
+        RUN(launch_conv(w, kConv2, front, {A, B}));
+    }
+    TAP(kLayers[kConv2].name, kConv2, B);
+    // entry flow, blocks 2-4: input and output alternate between B and R, A and C are scratch.  Block 4 reads B and writes R.
+    void* X = B; void* Y = R;
+    for (int s1 = kBlock2; s1 < kBlock5; s1 += 3) {
+        RUN(strided_block(w, s1, X, A, C, Y));
+        if (w.tapped()) return BQ_OK;
         void* t = X; X = Y; Y = t;
-        snprintf(nm, sizeof nm, "block%d_out", block);
-        TAP(nm, X, 19, 19, 728, 736);
     }
-    // exit flow
-    RUN(run_conv(c, {"block13_sepconv1", PROD_DW_RELU, X, Y, nullptr, nullptr, n, 19, 19, 19, 19, 736, 736, 1}, s));
-    TAP("block13_sepconv1", Y, 19, 19, 728, 736);
-    RUN(run_conv(c, {"block13_sepconv2", PROD_DW, Y, C, nullptr, nullptr, n, 19, 19, 19, 19, 736, 1024, 0}, s));
-    TAP("block13_sepconv2", C, 19, 19, 1024, 1024);
-    {   // the block's output goes to S (X is its input); X is scratch from here on
-        int tapped = 0;
-        RUN(block_end(c, "block13_res", "maxpool_add_19_c1024", X, C, S, n, 19, 736, 1024, 1024, s, tap, &tapped));
-        if (tapped) return BQ_OK;
+    // middle flow, blocks 5-12 at 19x19x728 (stride 736): B is the scratch buffer S of the middle and exit flow
+    void* S = B; Y = A;
+    for (int s1 = kBlock5; s1 < kBlock13; s1 += 3) {
+        RUN(run_conv(w, s1, {X, Y, nullptr, nullptr, S}));
+        TAP(kLayers[s1].name, s1, Y);
+        RUN(run_conv(w, s1 + 1, {Y, C, nullptr, nullptr, S}));
+        TAP(kLayers[s1 + 1].name, s1 + 1, C);
+        RUN(run_conv(w, s1 + 2, {C, Y, X, nullptr, S}));
+        void* t = X; X = Y; Y = t;
+        TAP(kLayers[s1 + 2].out_name, s1 + 2, X);
     }
-    TAP("block13_out", S, 10, 10, 1024, 1024);
-    RUN(run_conv(c, {"block14_sepconv1", PROD_DW, S, Y, nullptr, C, n, 10, 10, 10, 10, 1024, 1536, 1, X}, s));
-    TAP("block14_sepconv1", Y, 10, 10, 1536, 1536);
-    {   // round 4: the global average pool is the epilogue of block14_sepconv2's GEMM (one workgroup owns an image's 100
-        // pixels) unless the convolution's own output was asked for
-        const bool want14 = tap && tap->want && strcmp(tap->want, "block14_sepconv2") == 0;
-        bool gap_done = false;
-        ConvArgs a14{"block14_sepconv2", PROD_DW, Y, C, nullptr, S, n, 10, 10, 10, 10, 1536, 2048, 1, X};
-        if (!want14) { a14.gap_out = feat; a14.gap_done = &gap_done; }
-        RUN(run_conv(c, a14, s));
-        if (!gap_done) {
-            TAP("block14_sepconv2", C, 10, 10, 2048, 2048);
+    // exit flow: block 13's output goes to S (X is its input); X is scratch from there on
+    RUN(strided_block(w, kBlock13, X, Y, C, S));
+    if (w.tapped()) return BQ_OK;
+    RUN(run_conv(w, kBlock14, {S, Y, nullptr, C, X}));
+    TAP(kLayers[kBlock14].name, kBlock14, Y);
+    bool pooled = false;
+    RUN(run_conv(w, kBlock14 + 1, {Y, C, nullptr, S, X, feat}, &pooled));
+    if (!pooled) {
+        TAP(kLayers[kBlock14 + 1].name, kBlock14 + 1, C);
+        if (w.plan) {
+            w.note("global_avg_pool", "GAP_KERNEL");
+        } else {
             ProfScope ps(c, s, "global_avg_pool", (double)n * 100 * 2048, es * (double)n * 100 * 2048 + 4.0 * n * 2048);
             if (launch_gap(C, n, 100, 2048, 2048, feat, c->feat_mul, dt, s)) return fail(c, BQ_ERR_HIP, "gap launch failed");
         }
     }
-    if (tap && tap->want) return fail(c, BQ_ERR_ARG, std::string("unknown activation: ") + tap->want);
+    if (w.want()) return fail(c, BQ_ERR_ARG, std::string("unknown activation: ") + w.want());
     return BQ_OK;
 }
 
@@ -622,10 +723,12 @@ const float* entry_f32(bq_ctx* c, const std::string& name) {
     return it == c->entries.end() ? nullptr : reinterpret_cast<const float*>(it->second.p);
 }
 
-int register_gemm_layer(bq_ctx* c, const std::string& name, int cin, int cout, int kpad, bool has_dw,
-                        int vec, int elt) {
+// row li of kLayers from the blob's entries
+int register_gemm_layer(bq_ctx* c, int li, int vec, int elt) {
+    const std::string name = kLayers[li].name;
+    const int cout = kLayers[li].cout, kpad = kLayers[li].kpad;
+    const bool has_dw = kLayers[li].prod == PROD_DW || kLayers[li].prod == PROD_DW_RELU;
     GemmLayer L;
-    L.name = name; L.cin = cin; L.cout = cout; L.kpad = kpad;
     auto w = c->entries.find(name + "/wp");
     if (w == c->entries.end()) return fail(c, BQ_ERR_WEIGHTS, "missing " + name + "/wp");
     const size_t per_nf = (size_t)(kpad / (2 * vec)) * 64 * vec * elt;
@@ -656,7 +759,7 @@ int register_gemm_layer(bq_ctx* c, const std::string& name, int cin, int cout, i
         if (c->entries[name + "/dw"].n < (size_t)9 * kpad * 4)
             return fail(c, BQ_ERR_WEIGHTS, "depthwise taps of " + name + " shorter than 9 x its padded input channels");
     }
-    c->layers[name] = L;
+    c->layers[li] = L;
     return BQ_OK;
 }
 
@@ -779,7 +882,8 @@ int bq_load_weights(bq_ctx* c, const void* host_blob, size_t nbytes) {
     DeviceGuard guard(c->device);            // restores the caller's current device on every exit path
     if (!guard.ok) return fail(c, BQ_ERR_HIP, "hipSetDevice failed");
     if (c->d_blob) { (void)hipFree(c->d_blob); c->d_blob = nullptr; }
-    c->entries.clear(); c->layers.clear(); c->loaded = false;
+    c->entries.clear(); c->loaded = false;
+    for (GemmLayer& g : c->layers) g = GemmLayer{};
     c->head[0] = c->head[1] = HeadLayer{};
     HIPCHK(c, hipMalloc((void**)&c->d_blob, nbytes));
     HIPCHK(c, hipMemcpy(c->d_blob, hb, nbytes, hipMemcpyHostToDevice));
@@ -818,19 +922,7 @@ int bq_load_weights(bq_ctx* c, const void* host_blob, size_t nbytes) {
             c->front_wc16 = b->second.p;
         }
     }
-    RUN(register_gemm_layer(c, "block1_conv2", 32, 64, 288, false, vec, elt));
-    const int res[4][3] = {{2, 64, 128}, {3, 128, 256}, {4, 256, 728}, {13, 728, 1024}};
-    for (auto& r : res)
-        RUN(register_gemm_layer(c, "block" + std::to_string(r[0]) + "_res", r[1], r[2], pad16(r[1]), false, vec, elt));
-    struct S { int block, idx, cin, cout; };
-    std::vector<S> seps = {{2, 1, 64, 128}, {2, 2, 128, 128}, {3, 1, 128, 256}, {3, 2, 256, 256},
-                           {4, 1, 256, 728}, {4, 2, 728, 728}};
-    for (int b = 5; b <= 12; ++b) for (int i = 1; i <= 3; ++i) seps.push_back({b, i, 728, 728});
-    seps.push_back({13, 1, 728, 728}); seps.push_back({13, 2, 728, 1024});
-    seps.push_back({14, 1, 1024, 1536}); seps.push_back({14, 2, 1536, 2048});
-    for (auto& sp : seps)
-        RUN(register_gemm_layer(c, "block" + std::to_string(sp.block) + "_sepconv" + std::to_string(sp.idx),
-                                sp.cin, sp.cout, pad16(sp.cin), true, vec, elt));
+    for (int li = 0; li < kNumLayers; ++li) RUN(register_gemm_layer(c, li, vec, elt));
     for (int layer = 0; layer < 2; ++layer) {
         const std::string name = layer == 0 ? "hidden_0" : "hidden_1";
         const int K = layer == 0 ? 2048 : 1024;
@@ -1019,7 +1111,7 @@ int bq_backbone(bq_ctx* c, const void* d_in, int n, float* d_feat, void* d_ws, s
     if (!c || !d_in || !d_feat || !d_ws || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_backbone: bad argument");
     if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
     if (ws_bytes < ws_layout(c, n, 1).total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
-    return backbone_impl(c, d_in, n, d_feat, (unsigned char*)d_ws, (hipStream_t)stream, nullptr);
+    return backbone_impl({c, n, (hipStream_t)stream, nullptr, nullptr}, d_in, d_feat, (unsigned char*)d_ws);
 }
 
 int bq_mc_head(bq_ctx* c, const float* d_feat, int n, int64_t tile_idx0, int mc_n, int pass0, uint64_t seed,
@@ -1052,12 +1144,11 @@ int bq_set_tile_index_array(bq_ctx* c, const int64_t* d_tile_idx) {
 // caller used for its batch.
 static int features_from_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* feat, unsigned char* ws, const WsLayout& L,
                             bq_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const bool front = is16(c->cfg.dtype) && c->front_ws16 && c->front_wc16;
-    if (front) return backbone_impl(c, nullptr, n, feat, ws, s, nullptr, d_tiles);
+    const Walk w{c, n, (hipStream_t)stream, nullptr, nullptr};
+    if (has_front(c)) return backbone_impl(w, nullptr, feat, ws, d_tiles);
     void* staged = ws + L.staged;
     RUN(bq_stage(c, d_tiles, n, staged, stream));
-    return backbone_impl(c, staged, n, feat, ws, s, nullptr, nullptr);
+    return backbone_impl(w, staged, feat, ws);
 }
 
 int bq_mc_infer(bq_ctx* c, const uint8_t* d_tiles, int n, int64_t tile_idx0, int mc_n, uint64_t seed,
@@ -1172,7 +1263,7 @@ int64_t bq_debug_activation(bq_ctx* c, const char* name, const void* d_in, int n
     if (ws_bytes < L.total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
     Tap t; t.want = name; t.out = d_out; t.out_elems = out_elems;
     unsigned char* ws = (unsigned char*)d_ws;
-    const int r = backbone_impl(c, d_in, n, (float*)(ws + L.feat), ws, (hipStream_t)stream, &t);
+    const int r = backbone_impl({c, n, (hipStream_t)stream, &t, nullptr}, d_in, (float*)(ws + L.feat), ws);
     if (r != BQ_OK) return r;
     return t.written;
 }
@@ -1185,9 +1276,25 @@ int64_t bq_debug_activation_u8(bq_ctx* c, const char* name, const uint8_t* d_til
     if (ws_bytes < L.total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
     Tap t; t.want = name; t.out = d_out; t.out_elems = out_elems;
     unsigned char* ws = (unsigned char*)d_ws;
-    const int r = backbone_impl(c, nullptr, n, (float*)(ws + L.feat), ws, (hipStream_t)stream, &t, d_tiles);
+    const int r = backbone_impl({c, n, (hipStream_t)stream, &t, nullptr}, nullptr, (float*)(ws + L.feat), ws, d_tiles);
     if (r != BQ_OK) return r;
     return t.written;
+}
+
+// The routes of one walk as text, one "<layer or block output> <route>" line per step, through the walker and choose_route of
+// the calls above; nothing is launched.  from_u8: the walk of bq_mc_infer / bq_backbone_u8 (tap: of bq_debug_activation_u8),
+// otherwise of bq_backbone / bq_debug_activation.  Ends behind the tapped tensor.  Returns the text's length.
+int bq_describe_schedule(bq_ctx* c, int n, int from_u8, const char* tap, char* out, size_t cap) {
+    if (!c || !out || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_describe_schedule: bad argument");
+    if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
+    std::string plan;
+    Tap t; t.want = tap;
+    // (the tiles' pointer only says which entry the walk takes: nothing is read)
+    const uint8_t* tiles = from_u8 && (tap || has_front(c)) ? reinterpret_cast<const uint8_t*>(out) : nullptr;
+    RUN(backbone_impl({c, n, nullptr, &t, &plan}, nullptr, nullptr, nullptr, tiles));
+    if (plan.size() + 1 > cap) return fail(c, BQ_ERR_ARG, "bq_describe_schedule: output too small");
+    memcpy(out, plan.c_str(), plan.size() + 1);
+    return (int)plan.size();
 }
 
 }  // extern "C"

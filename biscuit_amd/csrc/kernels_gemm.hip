@@ -1,6 +1,8 @@
 // Fused "producer -> LDS A tile -> MFMA" kernel: the workhorse of the Xception backbone
 // (SeparableConv2D = depthwise 3x3 + pointwise 1x1 + folded BN [+ residual] [+ ReLU],
 // residual 1x1/s2 convs, block1_conv2 as im2col).  (The MC-dropout Dense layers have their own kernel, kernels_head.hip.)
+// WHO STILL RUNS THIS FILE: choose_route's last resort (biscuit_hip.hip: FUSED_GEMM) -- every layer of the fp32 context; in a 16-bit
+// context block2_res / block3_res under a debug tap of theirs, and any layer no other route takes.
 //
 // Design (gfx950 / CDNA4, wave64):
 //  * One workgroup owns MT = 32*MF output pixels and ALL output channels.  Phase 1

@@ -1,5 +1,5 @@
 // WHO STILL RUNS THIS FILE (round 5).  The headline path (bq_mc_infer / bq_backbone_u8 in a 16-bit context) does not: its front is
-// kernels_front.hip, block 2 and block3_sepconv1 are kernels_stream.hip.  run_conv (biscuit_hip.hip) comes here for
+// kernels_front.hip, block 2 and block3_sepconv1 are kernels_stream.hip.  choose_route (biscuit_hip.hip: TILE) comes here for
 //   * block1_conv2 (kind 0) on the float / planar entry: bq_backbone (UncertaintyInterface: standardised float tiles),
 //     bq_debug_activation, and a blob without "block1_conv1/w16" / "block1_conv2/wp16";
 //   * block2_sepconv1 / block2_sepconv2 (kinds 1, 2) and block3_sepconv1 (kind 3) only when the streaming kernel refuses the launch:

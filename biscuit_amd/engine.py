@@ -433,6 +433,14 @@ class Engine:
         k = self._tap_exp.get(name, 0)
         return out * float(2.0 ** k) if (k and true_scale) else out
 
+    def schedule(self, n, u8=True, tap=None):
+        """The launch schedule of a batch of ``n`` tiles as ``[(layer or block output, route)]`` (``bq_describe_schedule``): which
+        kernel family runs each matrix layer from uint8 tiles (``mc_infer`` / ``backbone_u8``; ``u8=False``: from staged tiles,
+        ``backbone``), up to the debug tap ``tap`` if one is named.  Decided by the code that launches; launches nothing."""
+        buf = C.create_string_buffer(8192)
+        self._check(self._lib.bq_describe_schedule(self._ctx, int(n), 1 if u8 else 0, tap.encode() if tap else None, buf, len(buf)))
+        return [tuple(line.split(' ', 1)) for line in buf.value.decode().splitlines()]
+
     # layers whose outputs the 16-bit storage can clip: the largest activations of Xception sit behind the un-normalised sums
     # of the residual stream and in front of the pooled features
     HEADROOM_TAPS = (('block1_conv2', (147, 147, 64)), ('block2_out', (74, 74, 128)), ('block4_out', (19, 19, 728)),

@@ -296,13 +296,14 @@ def wide_layers():
     """The separable convolutions of kernels_wide.hip (8 waves, 16x16x32 fragment order with interleaved n-fragment pairs):
     the 26 layers 728 -> 728 -- block4_sepconv2 (37x37 maps), blocks 5-12 and block13_sepconv1 (19x19 maps) --,
     block4_sepconv1 (256 -> 728, 37x37), block3_sepconv1 / 2 (128 / 256 -> 256, 74x74) and block13_sepconv2 (728 -> 1024,
-    19x19, as two launches of 512 columns)."""
+    19x19, as two launches of 512 columns).  (block3_sepconv1 is listed for its ``wp16`` entry: the streaming kernel, which reads
+    the same order, is tried first and runs it -- DESIGN.md section 3; block3_sepconv2 runs there only when block 3's tail is off.)"""
     return (['block3_sepconv1', 'block3_sepconv2', 'block4_sepconv1', 'block4_sepconv2'] +
             [f'block{b}_sepconv{i}' for b in range(5, 13) for i in (1, 2, 3)] + ['block13_sepconv1', 'block13_sepconv2'])
 
 
 # kernels_stream.hip (round 4): the 147x147 separable convolutions of block 2 take the same 16x16x32 fragment order
-STREAM_LAYERS = ('block2_sepconv1', 'block2_sepconv2')      # (block3_sepconv1 has its wp16 as a wide layer)
+STREAM_LAYERS = ('block2_sepconv1', 'block2_sepconv2')      # (+ block3_sepconv1, whose wp16 comes with wide_layers())
 TAIL_RES_LAYERS = ('block2_res', 'block3_res')
 # kernels_exit.hip (round 4): block 14's pointwise GEMMs, the same fragment order
 EXIT_LAYERS = ('block14_sepconv1', 'block14_sepconv2')

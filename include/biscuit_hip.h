@@ -283,6 +283,15 @@ int64_t bq_debug_activation_u8(bq_ctx* ctx, const char* name, const uint8_t* d_t
                                void* d_ws, size_t ws_bytes, float* d_out, size_t out_elems,
                                bq_stream_t stream);
 
+/* Which kernel family would run each matrix layer: the launch schedule of a batch of n tiles as text, one line
+ * "<layer or block output> <route>" per step in launch order (the routes are the RouteKind names of csrc/biscuit_hip.hip, e.g.
+ * "block5_sepconv1 WIDE", "block3_out BLOCK_TAIL", "block14_sepconv2 DW_THEN_EXIT GAP_EPILOGUE=yes"), NUL-terminated, into
+ * out[cap].  from_u8 != 0: the walk of bq_mc_infer / bq_backbone_u8 (with `name`: of bq_debug_activation_u8), otherwise of
+ * bq_backbone (bq_debug_activation).  name: a debug tap as above, or NULL; the text ends behind the tapped tensor, and a call
+ * those hooks refuse is refused here with the same error.  Decided by the code that launches; launches nothing.  Returns the
+ * text's length, or <0. */
+int bq_describe_schedule(bq_ctx* ctx, int n, int from_u8, const char* name, char* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
