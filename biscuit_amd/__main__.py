@@ -103,10 +103,15 @@ def main(argv=None):
     ap.add_argument('--tile-uq', type=float, default=0.0, help='tile-level uncertainty threshold (0 = off)')
     ap.add_argument('--slide-uq', type=float, default=0.0, help='slide-level uncertainty threshold (0 = off)')
     ap.add_argument('--gpu-decode', type=int, default=0, metavar='CUS',
-                    help='decode PNG tiles on the GPU: the host only copies their zlib streams, CUS compute units (16-32) kept out of '
-                         'the inference streams inflate them.  For hosts with few free cores per GPU and runs of >= 30 k tiles; '
-                         'slower than 16 host threads otherwise (profiles/r05_inflate.txt).  Pins 3 x up to 1 GiB of host memory per rank for the '
-                         'compressed ring (4 096-tile chunks) and allocates ~3 GB on the device per chunk in flight')
+                    help='decode PNG and baseline-JPEG tiles on the GPU: the host only copies their zlib streams / entropy-coded scans, CUS '
+                         'compute units (16-32) kept out of the inference streams decode them; slides outside both device subsets '
+                         '(progressive, grey or restart-interval JPEG, ...) stay on the host.  PNG: for hosts with few free cores per GPU '
+                         'and runs of >= 30 k tiles; slower than 16 host threads otherwise (profiles/r05_inflate.txt).  JPEG at quality '
+                         '<= 95: faster than the host decoder on hosts with 16 free cores per GPU or fewer (20 k tiles/s on 16 CUs, 29 k '
+                         'on 32, against 17 k); not at quality 100, and not needed with ~28 or more free cores per GPU '
+                         '(profiles/jpeg_decode.txt).  Pins 3 x up to 1 GiB of host memory per rank for the compressed ring (4 096-tile '
+                         'chunks) and allocates ~3 GB on the device per chunk in flight; JPEG adds 1.14 GB of coefficient scratch per '
+                         'decode stream (554 KB per 299-px tile, rounds of 2 048 tiles)')
     ap.add_argument('--skip-existing', action='store_true',
                     help='do nothing when OUT already holds tile_predictions_eval.csv (the idempotence of the reference\'s Step 6: '
                          'utils.eval_exists, biscuit/experiment.py:913-914)')

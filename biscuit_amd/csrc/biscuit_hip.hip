@@ -1059,6 +1059,22 @@ int bq_png_inflate(bq_ctx* c, const uint8_t* d_z, const uint32_t* d_off, const u
     return BQ_OK;
 }
 
+size_t bq_jpeg_scratch_bytes(int n, int px) { return jpeg_scratch_bytes(n, px); }
+
+int bq_jpeg_decode(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px,
+                   uint8_t* d_out, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || px <= 0 || px > 4096 || n_tables < 0) return fail(c, BQ_ERR_ARG, "bq_jpeg_decode: bad argument");
+    if (n == 0) return BQ_OK;
+    if (!d_scan || !d_desc || !d_tables || n_tables == 0 || !d_out || !d_status || !d_scratch || ((uintptr_t)d_tables & 3) ||
+        ((uintptr_t)d_scan & 15) || ((uintptr_t)d_desc & 3))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_decode: bad argument");
+    if (scratch_bytes < jpeg_scratch_bytes(n, px)) return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_decode: scratch too small");
+    ProfScope ps(c, (hipStream_t)stream, "jpeg_decode", 0.0, (double)n * px * px * 3.0);
+    const int e = launch_jpeg_decode(d_scan, d_desc, d_tables, n_tables, n, px, d_out, d_status, d_scratch, scratch_bytes, (hipStream_t)stream);
+    if (e) return fail(c, BQ_ERR_HIP, std::string("jpeg decode launch: ") + hipGetErrorString((hipError_t)e));
+    return BQ_OK;
+}
+
 int bq_png_unfilter_strided(bq_ctx* c, const uint8_t* d_rows, size_t rows_stride, int n, int px, uint8_t* d_out, bq_stream_t stream) {
     if (!c || !d_rows || !d_out || n < 0 || px <= 0) return fail(c, BQ_ERR_ARG, "bq_png_unfilter_strided: bad argument");
     if (launch_png_unfilter(d_rows, n, px, d_out, (hipStream_t)stream, rows_stride)) return fail(c, BQ_ERR_HIP, "png unfilter launch failed");

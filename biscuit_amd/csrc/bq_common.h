@@ -131,6 +131,10 @@ size_t inflate_scratch_bytes(int n);
 int launch_inflate(const unsigned char* d_z, const unsigned* d_off, const unsigned* d_len, int n, unsigned char* d_out, unsigned out_len,
                    unsigned out_stride, void* d_scratch, int* d_status, hipStream_t s, int variant = 0, unsigned row_len = 0);
 // (row_len != 0: the outputs are PNG scanlines of that length; a filter-type byte above 4 is flagged too)
+// kernels_jpeg.hip: n baseline-JPEG tiles as bqio_extract_jpeg packs them -> uint8 NHWC, status 0 = decoded (jpeg_device.h)
+size_t jpeg_scratch_bytes(int n, int px);
+int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px, uint8_t* d_out,
+                       int* d_status, void* d_scratch, size_t scratch_bytes, hipStream_t s);
 int launch_stem1(const void* in_nchw, int n, const float* w27x32, const float* scale,
                  const float* bias, void* out_nhwc, int dtype, hipStream_t s);
 int launch_pool_add(const void* y, const void* res, void* out, int n, int Hi, int Wi, int C,

@@ -471,12 +471,18 @@ inline bool decode_block(Bits& B, const Huff& dc, const Huff& ac, const uint16_t
     return idct_islow(coef, out, stride);
 }
 
-// data[0..n): a whole JPEG file.  out: px*px*3 RGB bytes.  probe_only: stop in front of the entropy decoder -- everything the
-// markers and the scan's structure can refuse (progressive / arithmetic / lossless frames, sampling factors, colour spaces, restart
-// structure, size) has been checked by then, at the cost of one pass over the bytes; `out` is not written.
-inline int decode(const uint8_t* data, size_t n, int px, uint8_t* out, Scratch& S, bool probe_only = false) {
+// What the markers in front of the scan say (parse_header), for the entropy decoder here and for the extractor that packs
+// the scan for the device decoder (bqio_extract_jpeg): ONE header walk, so the two refuse the same files.
+struct Header {
+    int W = 0, H = 0, ncomp = 0, restart = 0;
+    int hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
+    size_t scan = 0;                     // first byte of the entropy-coded segment
+};
+
+// data[0..n): a whole JPEG file.  Everything the markers can refuse (progressive / arithmetic / lossless frames, sampling factors,
+// colour spaces, size) is refused here; the tables and the components' geometry are left in S.
+inline int parse_header(const uint8_t* data, size_t n, int px, Scratch& S, Header& Hd) {
     if (n < 4 || data[0] != 0xFF || data[1] != 0xD8) return UNSUPPORTED;
-    color_tables(S);
     for (int i = 0; i < 4; ++i) { S.dc[i].defined = S.ac[i].defined = false; S.qdef[i] = false; }
     size_t p = 2;
     int W = 0, H = 0, ncomp = 0, restart = 0;
@@ -578,12 +584,20 @@ inline int decode(const uint8_t* data, size_t n, int px, uint8_t* out, Scratch& 
         if (!S.qdef[K.tq] || !S.dc[K.td].defined || !S.ac[K.ta].defined) return UNSUPPORTED;
         K.stride = mcux * K.h * 8; K.rows = mcuy * K.v * 8;
         K.dw = (W * K.h + hmax - 1) / hmax; K.dh = (H * K.v + vmax - 1) / vmax;
-        K.plane.resize((size_t)K.stride * K.rows + 16);             // the row loops read whole vectors
         K.pred = 0;
     }
     if (ncomp == 3 && hmax == 2 && S.comp[1].dw <= 2) return UNSUPPORTED;       // libjpeg replicates instead of filtering
+    Hd.W = W; Hd.H = H; Hd.ncomp = ncomp; Hd.restart = restart;
+    Hd.hmax = hmax; Hd.vmax = vmax; Hd.mcux = mcux; Hd.mcuy = mcuy; Hd.scan = scan;
+    return OK;
+}
 
-    // ---- entropy-coded segment: drop the stuffed zeros, split at the restart markers ---------------------------------
+// The entropy-coded segment behind a header parse_header accepted: the stuffed zeros dropped, split at the restart markers
+// (S.ecs, S.seg; ECS_PAD zero bytes behind the last interval).  Refuses what the scan's structure can refuse: no end marker,
+// fill bytes, restart markers out of order or in the wrong number, another marker.
+inline int unstuff_scan(const uint8_t* data, size_t n, const Header& Hd, Scratch& S) {
+    const size_t scan = Hd.scan;
+    const int restart = Hd.restart;
     S.ecs.clear(); S.seg.clear();
     S.ecs.reserve(n - scan + ECS_PAD);
     S.seg.push_back(0);
@@ -611,10 +625,30 @@ inline int decode(const uint8_t* data, size_t n, int px, uint8_t* out, Scratch& 
     }
     S.seg.push_back(S.ecs.size());
     S.ecs.insert(S.ecs.end(), ECS_PAD, (uint8_t)0);
-    const int64_t total_mcu = (int64_t)mcux * mcuy;
+    const int64_t total_mcu = (int64_t)Hd.mcux * Hd.mcuy;
     const int64_t per_seg = restart ? restart : total_mcu;
     if ((int64_t)(S.seg.size() - 1) != (total_mcu + per_seg - 1) / per_seg) return UNSUPPORTED;
+    return OK;
+}
+
+// data[0..n): a whole JPEG file.  out: px*px*3 RGB bytes.  probe_only: stop in front of the entropy decoder -- everything the
+// markers and the scan's structure can refuse (progressive / arithmetic / lossless frames, sampling factors, colour spaces, restart
+// structure, size) has been checked by then, at the cost of one pass over the bytes; `out` is not written.
+inline int decode(const uint8_t* data, size_t n, int px, uint8_t* out, Scratch& S, bool probe_only = false) {
+    Header Hd;
+    int e = parse_header(data, n, px, S, Hd);
+    if (e != OK) return e;
+    e = unstuff_scan(data, n, Hd, S);
+    if (e != OK) return e;
     if (probe_only) return OK;
+    color_tables(S);
+    const int W = Hd.W, H = Hd.H, ncomp = Hd.ncomp, restart = Hd.restart, hmax = Hd.hmax, vmax = Hd.vmax, mcux = Hd.mcux;
+    const int64_t total_mcu = (int64_t)Hd.mcux * Hd.mcuy;
+    const int64_t per_seg = restart ? restart : total_mcu;
+    for (int c = 0; c < ncomp; ++c) {
+        Comp& K = S.comp[c];
+        K.plane.resize((size_t)K.stride * K.rows + 16);             // the row loops read whole vectors
+    }
 
     Bits B;
     int64_t mcu = 0;

@@ -1,0 +1,150 @@
+// kernels_jpeg.hip -- baseline-JPEG tiles decoded on the device (bq_jpeg_decode): the routines of jpeg_device.h, which
+// libbiscuit_io runs unchanged on the CPU (bqio_jpeg_decode_extracted), behind three kernels.
+//
+//   entropy  one LANE per tile, the arrangement of the device inflate (kernels_inflate.hip): Huffman-decode and dequantise the
+//            tile's blocks into int16 coefficients, natural order, per component plane, in the caller's scratch (zeroed by a
+//            memset in front of the kernel).  The tile's table set -- 21 KB of lookups -- sits in LDS: the workgroup (one wave)
+//            loads the set of its first tile; a lane whose tile names another set reads that one from global memory through
+//            the same pointer type, so tiles with different tables may stand side by side.
+//   idct     one thread per 8 x 8 block: the islow IDCT in registers, the 64 samples written over the block's own
+//            coefficients (no second plane buffer); a block outside the range rule sets the tile's status.
+//   colour   four output pixels per thread over the flattened NHWC output: h2v1 / h2v2 triangle upsampling of the chroma
+//            samples, BT.601 in fixed point, three aligned dword stores.
+//
+// Integer arithmetic throughout; the result is held to Pillow's bytes (tests/test_gpu_jpeg.py), not to a tolerance.
+// A tile costs tile_coef_bytes(px) of scratch (554 KB at 299 px, sized for 4:4:4), so a call works in rounds of as many
+// tiles as the caller's scratch holds (jpeg_round_tiles).
+#include "bq_common.h"
+#include "jpeg_device.h"
+
+namespace {
+
+constexpr int JE_NT = 64;                // entropy kernel: one wave per workgroup, one table set in LDS
+constexpr int JP_NT = 256;
+constexpr int JPEG_ROUND = 2048;         // tiles per round that bq_jpeg_scratch_bytes asks scratch for
+
+struct JpegParams {
+    const uint8_t* scan;
+    const bqjd::Desc* desc;              // of the round's first tile
+    const bqjd::TableSet* tables;
+    int n_tables;
+    int n;                               // tiles of this round
+    int px;
+    int16_t* coef;                       // [n][tile_i16]
+    size_t tile_i16;
+    int* status;                         // of the round's first tile
+    uint8_t* out;                        // of the CALL's first tile
+    long long p0, p1;                    // the round's pixels within the call's flattened output
+    long long t0;                        // the round's first tile within the call
+};
+
+__global__ void __launch_bounds__(JE_NT) jpeg_entropy_kernel(const JpegParams p) {
+    __shared__ bqjd::TableSet sT;
+    const int first = blockIdx.x * JE_NT;
+    const uint32_t primary = p.desc[first].tset;
+    if (primary < (uint32_t)p.n_tables) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(p.tables + primary);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&sT);
+        for (unsigned w = threadIdx.x; w < sizeof(bqjd::TableSet) / 4; w += JE_NT) dst[w] = src[w];
+    }
+    __syncthreads();
+    const int i = first + (int)threadIdx.x;
+    if (i >= p.n) return;
+    const bqjd::Desc d = p.desc[i];
+    bqjd::Geom G;
+    if (!bqjd::geom_of(d.geom, p.px, G) || d.tset >= (uint32_t)p.n_tables) { p.status[i] = bqjd::ST_DESC; return; }
+    const bqjd::TableSet* T = d.tset == primary ? &sT : p.tables + d.tset;
+    p.status[i] = bqjd::entropy_tile(p.scan + d.off, d.len, G, T, p.coef + (size_t)i * p.tile_i16);
+}
+
+__global__ void __launch_bounds__(JP_NT) jpeg_idct_kernel(const JpegParams p) {
+    const int i = blockIdx.y;
+    bqjd::Geom G;
+    if (!bqjd::geom_of(p.desc[i].geom, p.px, G)) return;
+    const uint32_t nblk = G.base[2] + (uint32_t)(G.mcux * G.mcuy);
+    const uint32_t b = blockIdx.x * JP_NT + threadIdx.x;
+    if (b >= nblk) return;
+    if (!bqjd::idct_in_place(p.coef + (size_t)i * p.tile_i16 + (size_t)b * 64)) atomicOr(&p.status[i], (int)bqjd::ST_RANGE);
+}
+
+__global__ void __launch_bounds__(JP_NT) jpeg_colour_kernel(const JpegParams p) {
+    const long long q = p.p0 / 4 + (long long)blockIdx.x * JP_NT + threadIdx.x;     // group of four pixels of the call's output
+    const long long a = q * 4;
+    if (a >= p.p1) return;
+    const int px = p.px;
+    const long long ppt = (long long)px * px;
+    long long tile = a / ppt;
+    const int rem = (int)(a - tile * ppt);
+    int y = rem / px, x = rem - y * px;
+    uint8_t b[12];
+    bool all = true;
+    long long cur = -1;
+    bqjd::Geom G;
+    bool gok = false;
+    const uint8_t* planes = nullptr;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long P = a + j;
+        const bool valid = P >= p.p0 && P < p.p1;
+        all &= valid;
+        b[3 * j] = b[3 * j + 1] = b[3 * j + 2] = 0;
+        if (valid) {
+            if (tile != cur) {
+                cur = tile;
+                gok = bqjd::geom_of(p.desc[tile - p.t0].geom, px, G);
+                planes = reinterpret_cast<const uint8_t*>(p.coef + (size_t)(tile - p.t0) * p.tile_i16);
+            }
+            if (gok) bqjd::pixel_rgb(planes, G, y, x, b + 3 * j);
+        }
+        if (++x == px) { x = 0; if (++y == px) { y = 0; ++tile; } }
+    }
+    uint8_t* o = p.out + 12 * q;
+    if (all && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+        uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            o4[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) | ((uint32_t)b[4 * k + 3] << 24);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long P = a + j;
+            if (P >= p.p0 && P < p.p1) { o[3 * j] = b[3 * j]; o[3 * j + 1] = b[3 * j + 1]; o[3 * j + 2] = b[3 * j + 2]; }
+        }
+    }
+}
+
+}  // namespace
+
+size_t jpeg_scratch_bytes(int n, int px) {
+    if (n <= 0 || px <= 0) return 0;
+    return (size_t)(n < JPEG_ROUND ? n : JPEG_ROUND) * bqjd::tile_coef_bytes(px);
+}
+
+// n tiles as bqio_extract_jpeg packed them -> uint8 NHWC + status, in rounds of as many tiles as d_scratch holds.
+int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px, uint8_t* d_out,
+                       int* d_status, void* d_scratch, size_t scratch_bytes, hipStream_t s) {
+    if (n <= 0) return 0;
+    const size_t per = bqjd::tile_coef_bytes(px);
+    size_t m = scratch_bytes / per;
+    if (m < 1) return (int)hipErrorInvalidValue;
+    if (m > 32768) m = 32768;            // (the idct kernel's grid counts tiles in y)
+    if (m >= JE_NT) m &= ~(size_t)(JE_NT - 1);
+    const long long ppt = (long long)px * px;
+    for (long long t0 = 0; t0 < n; t0 += (long long)m) {
+        const int cnt = (int)(n - t0 < (long long)m ? n - t0 : (long long)m);
+        JpegParams p;
+        p.scan = d_scan;
+        p.desc = reinterpret_cast<const bqjd::Desc*>(d_desc) + t0;
+        p.tables = reinterpret_cast<const bqjd::TableSet*>(d_tables);
+        p.n_tables = n_tables; p.n = cnt; p.px = px;
+        p.coef = reinterpret_cast<int16_t*>(d_scratch); p.tile_i16 = per / 2;
+        p.status = d_status + t0; p.out = d_out;
+        p.p0 = t0 * ppt; p.p1 = (t0 + cnt) * ppt; p.t0 = t0;
+        if (const hipError_t e = hipMemsetAsync(d_scratch, 0, (size_t)cnt * per, s)) return (int)e;
+        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((cnt + JE_NT - 1) / JE_NT), dim3(JE_NT), 0, s, p);
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((bqjd::tile_blocks(px) + JP_NT - 1) / JP_NT, cnt), dim3(JP_NT), 0, s, p);
+        const long long groups = (p.p1 + 3) / 4 - p.p0 / 4;
+        hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((groups + JP_NT - 1) / JP_NT)), dim3(JP_NT), 0, s, p);
+    }
+    return (int)hipGetLastError();
+}

@@ -4,6 +4,7 @@
 #include "../../include/biscuit_io.h"
 #include "inflate_fast.h"
 #include "jpeg_baseline.h"
+#include "jpeg_device.h"
 
 #include <fcntl.h>
 #include <string.h>
@@ -676,6 +677,203 @@ int bqio_decode_jpeg(const uint8_t* data, size_t len, int tile_px, uint8_t* out)
     std::unique_ptr<bqjpg::Scratch> S(new bqjpg::Scratch());
     const int j = bqjpg::decode(data, len, tile_px, out, *S);
     return j == bqjpg::OK ? BQIO_OK : j == bqjpg::WRONG_SIZE ? BQIO_ERR_FORMAT : BQIO_ERR_UNSUPPORTED;
+}
+
+}  // extern "C"
+
+// ---- baseline JPEG for the device decoder ----------------------------------------------------------------------------------
+namespace {
+
+// The tables the frame and scan headers select for components 0..2, in the device decoder's layout.  Built from what
+// bqjpg::parse_header left in S; equal tables give equal bytes (no stale tails), so that sets can be compared with memcmp.
+void table_set_of(const bqjpg::Scratch& S, bqjd::TableSet& T) {
+    static_assert(sizeof(T.fast[0]) == sizeof(S.ac[0].fast) && sizeof(T.dc[0].look) == sizeof(S.dc[0].look), "same lookup sizes");
+    static_assert(bqjd::LOOK == bqjpg::LOOK && bqjd::FAST == bqjpg::FAST, "same lookup sizes");
+    memset(&T, 0, sizeof(T));
+    auto core = [](const bqjpg::Huff& H, bqjd::HuffD& D) {
+        memcpy(D.look, H.look, sizeof(D.look));
+        int nvals = 0;
+        for (int l = 1; l <= 16; ++l) {
+            D.maxcode[l] = H.maxcode[l];
+            D.valoff[l] = H.valoff[l];
+            if (H.maxcode[l] >= 0 && H.maxcode[l] + H.valoff[l] + 1 > nvals) nvals = H.maxcode[l] + H.valoff[l] + 1;
+        }
+        D.maxcode[17] = H.maxcode[17];
+        memcpy(D.vals, H.vals, (size_t)(nvals < 256 ? nvals : 256));
+    };
+    for (int c = 0; c < 3; ++c) {
+        const bqjpg::Comp& K = S.comp[c];
+        core(S.dc[K.td], T.dc[c]);
+        core(S.ac[K.ta], T.ac[c]);
+        memcpy(T.fast[c], S.ac[K.ta].fast, sizeof(T.fast[c]));
+        memcpy(T.q[c], S.q[K.tq], sizeof(T.q[c]));
+    }
+    memcpy(T.zigzag, bqjpg::ZIGZAG, 64);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t bqio_jpeg_table_bytes(void) { return sizeof(bqjd::TableSet); }
+size_t bqio_jpeg_ecs_pad(void) { return bqjd::ECS_PAD; }
+size_t bqio_jpeg_coef_bytes(int tile_px) { return tile_px > 0 ? bqjd::tile_coef_bytes(tile_px) : 0; }
+
+int bqio_extract_jpeg(bqio_reader* r, int64_t first, int64_t count, int tile_px, uint8_t* out_scan, size_t cap, uint32_t* desc,
+                      void* tables, int table_cap, int* n_tables, int64_t* loc, size_t* used, int n_threads, int64_t* bad_index) {
+    if (!r || first < 0 || count < 0 || first + count > (int64_t)r->records.size() || tile_px <= 0 || !used || !n_tables ||
+        table_cap < 0 || (out_scan && (!desc || (table_cap && !tables)))) return BQIO_ERR_ARG;
+    if (bad_index) *bad_index = -1;
+    *used = 0; *n_tables = 0;
+    if (count == 0) return BQIO_OK;
+    const bool keep = out_scan != nullptr;                // NULL: sizes only (the once-per-slide probe)
+    struct TileJ { std::vector<uint8_t> ecs; uint32_t len = 0, geom = 0; int worker = 0, set = 0; };
+    std::vector<TileJ> tiles((size_t)count);
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > count) n_threads = (int)count;
+    std::vector<std::vector<std::unique_ptr<bqjd::TableSet>>> sets((size_t)n_threads);
+    std::atomic<int64_t> next(0), bad(INT64_MAX);
+    std::vector<int> bad_err((size_t)n_threads, BQIO_OK);
+    std::vector<int64_t> bad_at((size_t)n_threads, INT64_MAX);
+    auto work = [&](int w) {
+        std::unique_ptr<bqjpg::Scratch> S(new bqjpg::Scratch());
+        std::unique_ptr<bqjd::TableSet> T(new bqjd::TableSet());
+        for (;;) {
+            const int64_t i0 = next.fetch_add(8);
+            if (i0 >= count || i0 > bad.load()) return;
+            for (int64_t i = i0; i < i0 + 8 && i < count; ++i) {
+                Example ex;
+                int e = BQIO_OK;
+                bqjpg::Header Hd;
+                if (!parse_example(r->records[(size_t)(first + i)], ex) || !ex.image.p) e = BQIO_ERR_CORRUPT;
+                else if (image_format(ex.image) != BQIO_IMG_JPEG) e = BQIO_ERR_UNSUPPORTED;
+                else {
+                    int j = bqjpg::parse_header(ex.image.p, ex.image.n, tile_px, *S, Hd);
+                    // beyond the host decoder's refusals: grey tiles and restart intervals stay on the host decoder
+                    if (j == bqjpg::OK && (Hd.ncomp != 3 || Hd.restart != 0)) j = bqjpg::UNSUPPORTED;
+                    if (j == bqjpg::OK) j = bqjpg::unstuff_scan(ex.image.p, ex.image.n, Hd, *S);
+                    e = j == bqjpg::OK ? BQIO_OK : j == bqjpg::WRONG_SIZE ? BQIO_ERR_FORMAT : BQIO_ERR_UNSUPPORTED;
+                    if (e == BQIO_OK && S->seg[1] > 0x7fffffffull) e = BQIO_ERR_UNSUPPORTED;
+                }
+                if (e != BQIO_OK) {
+                    if (i < bad_at[(size_t)w]) { bad_at[(size_t)w] = i; bad_err[(size_t)w] = e; }
+                    int64_t cur = bad.load();
+                    while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
+                    return;
+                }
+                TileJ& t = tiles[(size_t)i];
+                t.len = (uint32_t)S->seg[1];
+                t.geom = (uint32_t)Hd.hmax | ((uint32_t)Hd.vmax << 8) | (3u << 16);
+                t.worker = w;
+                table_set_of(*S, *T);
+                auto& mine = sets[(size_t)w];
+                int k = (int)mine.size() - 1;
+                while (k >= 0 && memcmp(mine[(size_t)k].get(), T.get(), sizeof(bqjd::TableSet)) != 0) --k;
+                if (k < 0) {
+                    k = (int)mine.size();
+                    mine.emplace_back(new bqjd::TableSet(*T));
+                }
+                t.set = k;
+                if (keep) { S->ecs.resize(t.len); t.ecs.swap(S->ecs); }
+                if (loc) { loc[2 * i] = ex.loc_x; loc[2 * i + 1] = ex.loc_y; }
+            }
+        }
+    };
+    {
+        std::vector<std::thread> pool;
+        for (int t = 1; t < n_threads; ++t) pool.emplace_back(work, t);
+        work(0);
+        for (auto& th : pool) th.join();
+    }
+    if (bad.load() != INT64_MAX) {
+        int e = BQIO_ERR_UNSUPPORTED;
+        for (int w = 0; w < n_threads; ++w)
+            if (bad_at[(size_t)w] == bad.load()) e = bad_err[(size_t)w];
+        if (bad_index) *bad_index = first + bad.load();
+        r->err = e == BQIO_ERR_UNSUPPORTED ? "image_raw is not a baseline JPEG the device decoder handles"
+                 : e == BQIO_ERR_FORMAT    ? "tile size differs from tile_px" : "corrupt record";
+        return e;
+    }
+    // the table sets of the call: the workers' lists merged
+    std::vector<const bqjd::TableSet*> all;
+    std::vector<std::vector<int>> global((size_t)n_threads);
+    for (int w = 0; w < n_threads; ++w)
+        for (auto& sp : sets[(size_t)w]) {
+            int k = (int)all.size() - 1;
+            while (k >= 0 && memcmp(all[(size_t)k], sp.get(), sizeof(bqjd::TableSet)) != 0) --k;
+            if (k < 0) { k = (int)all.size(); all.push_back(sp.get()); }
+            global[(size_t)w].push_back(k);
+        }
+    size_t at = 0;
+    std::vector<size_t> offs((size_t)count + 1);
+    for (int64_t i = 0; i < count; ++i) {
+        offs[(size_t)i] = at;
+        at = (at + tiles[(size_t)i].len + bqjd::ECS_PAD + bqjd::ECS_ALIGN - 1) & ~(size_t)(bqjd::ECS_ALIGN - 1);
+    }
+    offs[(size_t)count] = at;
+    *used = at;
+    *n_tables = (int)all.size();
+    if (at > 0xfffffff0ull) return BQIO_ERR_ARG;
+    if (!keep) return BQIO_OK;
+    if (at > cap || (int)all.size() > table_cap) return BQIO_ERR_ARG;
+    for (size_t k = 0; k < all.size(); ++k) memcpy((uint8_t*)tables + k * sizeof(bqjd::TableSet), all[k], sizeof(bqjd::TableSet));
+    next.store(0);
+    auto copy = [&]() {
+        for (;;) {
+            const int64_t i0 = next.fetch_add(8);
+            if (i0 >= count) return;
+            for (int64_t i = i0; i < i0 + 8 && i < count; ++i) {
+                const TileJ& t = tiles[(size_t)i];
+                uint8_t* d = out_scan + offs[(size_t)i];
+                if (t.len) memcpy(d, t.ecs.data(), t.len);
+                memset(d + t.len, 0, offs[(size_t)i + 1] - offs[(size_t)i] - t.len);
+                uint32_t* ds = desc + 4 * i;
+                ds[0] = (uint32_t)offs[(size_t)i]; ds[1] = t.len; ds[2] = t.geom;
+                ds[3] = (uint32_t)global[(size_t)t.worker][(size_t)t.set];
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < n_threads; ++t) pool.emplace_back(copy);
+    copy();
+    for (auto& th : pool) th.join();
+    return BQIO_OK;
+}
+
+int bqio_jpeg_decode_extracted(const uint8_t* scan, const uint32_t* desc, const void* tables, int n_tables, int n, int tile_px,
+                               uint8_t* out, int32_t* status, int n_threads) {
+    if (n < 0 || tile_px <= 0 || tile_px > 4096 || n_tables < 0 || (n && (!scan || !desc || !out || !status)) || (n_tables && !tables))
+        return BQIO_ERR_ARG;
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > n) n_threads = n ? n : 1;
+    const bqjd::TableSet* T = (const bqjd::TableSet*)tables;
+    std::atomic<int> next(0);
+    auto work = [&]() {
+        std::vector<int16_t> coef;
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n) return;
+            bqjd::Desc d;
+            memcpy(&d, desc + 4 * (size_t)i, sizeof(d));
+            bqjd::Geom G;
+            if (!bqjd::geom_of(d.geom, tile_px, G) || d.tset >= (uint32_t)n_tables) { status[i] = bqjd::ST_DESC; continue; }
+            coef.assign((size_t)bqjd::tile_blocks(tile_px) * 64, (int16_t)0);      // exactly the tile's coefficient space
+            int st = bqjd::entropy_tile(scan + d.off, d.len, G, T + d.tset, coef.data());
+            const uint32_t nblk = G.base[2] + (uint32_t)(G.mcux * G.mcuy);
+            for (uint32_t b = 0; b < nblk; ++b)
+                if (!bqjd::idct_in_place(coef.data() + (size_t)b * 64)) st |= bqjd::ST_RANGE;
+            const uint8_t* planes = (const uint8_t*)coef.data();
+            uint8_t* o = out + (size_t)i * tile_px * tile_px * 3;
+            for (int y = 0; y < tile_px; ++y)
+                for (int x = 0; x < tile_px; ++x) bqjd::pixel_rgb(planes, G, y, x, o + 3 * ((size_t)y * tile_px + x));
+            status[i] = st;
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < n_threads; ++t) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    return BQIO_OK;
 }
 
 }  // extern "C"

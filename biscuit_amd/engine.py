@@ -218,6 +218,35 @@ class Engine:
         self._check(self._lib.bq_png_unfilter_strided(self._ctx, _ptr(rows), rows.shape[1], n, px, _ptr(out), self._stream()))
         return out, status
 
+    def jpeg_decode(self, scan, desc, tables, px=TILE_PX, scratch=None):
+        """n baseline-JPEG tiles decoded on the device (``bq_jpeg_decode``, kernels_jpeg.hip: entropy decode one tile per lane,
+        then IDCT, upsampling and colour conversion): ``scan`` uint8 [bytes], ``desc`` int32 / uint32 [n, 4] and ``tables`` uint8
+        [k, table bytes] as ``NativeReader.extract_jpeg`` wrote them, all on this device.  Returns ``(tiles, status)``: tiles uint8
+        NHWC [n,px,px,3] -- the bytes the host decoder and Pillow give -- and status int32 [n], 0 where the tile decoded (a tile
+        whose status is not 0 was refused: its bytes are no image).  ``scratch``: ``jpeg_scratch(n, px)`` or larger; launches that
+        may overlap on different streams bring their own."""
+        assert scan.dtype == torch.uint8 and scan.is_cuda and scan.is_contiguous()
+        n = int(desc.shape[0])
+        assert desc.is_cuda and desc.is_contiguous() and desc.element_size() == 4 and tuple(desc.shape) == (n, 4)
+        assert tables.dtype == torch.uint8 and tables.is_cuda and tables.is_contiguous() and tables.dim() == 2
+        out = torch.empty((n, px, px, 3), dtype=torch.uint8, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        need = int(self._lib.bq_jpeg_scratch_bytes(n, px))
+        if scratch is None:
+            if getattr(self, '_jpeg_ws', None) is None or self._jpeg_ws.numel() < need:
+                self._jpeg_ws = None
+                self._jpeg_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            scratch = self._jpeg_ws
+        assert scratch.numel() >= need
+        self._check(self._lib.bq_jpeg_decode(self._ctx, _ptr(scan), _ptr(desc), _ptr(tables), int(tables.shape[0]), n, px, _ptr(out),
+                                             _ptr(status), _ptr(scratch), scratch.numel(), self._stream()))
+        return out, status
+
+    def jpeg_scratch(self, n, px=TILE_PX):
+        """Coefficient space for ``jpeg_decode`` over ``n`` tiles (``bq_jpeg_scratch_bytes``: 554 KB per 299-px tile, for 2 048
+        tiles at most -- 1.14 GB; a longer call works in rounds)."""
+        return torch.empty(int(self._lib.bq_jpeg_scratch_bytes(int(n), int(px))), dtype=torch.uint8, device=self.device)
+
     def reinhard_fast(self, tiles_u8, target_means, target_stds, out=None):
         """`reinhard_fast` stain normalisation (hp.py:19; results.py:251-252 `wsi_normalizer.rgb_to_rgb`):
         uint8 NHWC [n,299,299,3] -> uint8 NHWC.  target_means/target_stds: the CIE-LAB `norm_fit` of the

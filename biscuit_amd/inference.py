@@ -59,8 +59,9 @@ class TFRecordSource:
     a record outside the native decoders' subset is decoded whole with Pillow once and served from memory."""
     def __init__(self, path, n_tiles, tile_px=299, rows=False, z=False):
         self.path, self.n_tiles, self.tile_px, self.rows = path, int(n_tiles), int(tile_px), bool(rows)
-        # z: hand the tiles over COMPRESSED (``read_z``: the records' zlib streams, packed; the device inflates them -- bq_png_inflate);
-        # decided per slide before its first chunk: a slide with a record that is not an 8-bit RGB PNG tile stays on ``read``
+        # z: hand the tiles over COMPRESSED (``read_z``: the records' zlib streams, packed; the device inflates them -- bq_png_inflate;
+        # ``read_jpeg``: the entropy-coded segments of baseline-JPEG tiles; the device decodes them -- bq_jpeg_decode);
+        # decided per slide before its first chunk: a slide with a record outside both device subsets stays on ``read``
         self.z = bool(z)
         self._reader = None
         self._fallback = None
@@ -89,6 +90,29 @@ class TFRecordSource:
         """The zlib streams of tiles [first, first + count) packed into ``z`` (uint8), offsets / lengths into ``off`` / ``length``
         (uint32 [count]).  Returns the bytes used; MemoryError (bytes needed in ``.args[1]``) when ``z`` is too small."""
         return self._reader.extract_z(first, count, self.tile_px, z, off, length)[0]
+
+    def jpeg_ok(self):
+        """True when the whole slide can go to the device JPEG decoder: every record a baseline JPEG of the tile size inside
+        ``NativeReader.extract_jpeg``'s subset -- the host decoder's (8-bit, Huffman, one interleaved scan, 4:4:4 / 4:2:2 / 4:2:0)
+        WITHOUT grey tiles and WITHOUT restart intervals; a slide with one such record, or one progressive record, stays on
+        ``read`` whole (host decoder or Pillow, as its probe decides).  One pass over the slide's bytes, nothing decoded."""
+        from . import tfrecord_native as tn
+        if not (self.z and tn.available() and self.n_tiles):
+            return False
+        if self._reader is None:
+            self._reader = tn.NativeReader(self.path)
+        for first in range(0, self.n_tiles, CHUNK_TILES_Z):      # (chunk-wise: the offsets of one call are 32-bit)
+            try:
+                self._reader.extract_jpeg(first, min(CHUNK_TILES_Z, self.n_tiles - first), self.tile_px, None, None, None)
+            except (tn.UnsupportedImage, ValueError, IOError):
+                return False
+        return True
+
+    def read_jpeg(self, first, count, scan, desc, tables):
+        """The entropy-coded segments of tiles [first, first + count) packed into ``scan`` (uint8), descriptors into ``desc`` (uint32
+        [count, 4]), the distinct table sets into ``tables``.  Returns (bytes used, table sets used); MemoryError (bytes and sets
+        needed in ``.args[1:]``) when ``scan`` or ``tables`` is too small."""
+        return self._reader.extract_jpeg(first, count, self.tile_px, scan, desc, tables)[:2]
 
     def chunk_shape(self, count):
         px = self.tile_px
@@ -170,6 +194,8 @@ def slides_from_tfrecords(paths, labels, patients=None, tile_px=299, pinned=None
     # gpu_decode (round 5): the host only walks the record framing and copies the PNG tiles' zlib streams; the GPU inflates them
     # (one stream per lane, on compute units an ``EnginePool(reserve_cus=...)`` keeps out of the inference streams' masks) and
     # reverses the scanline filters.  For hosts with few cores per GPU: 16 CUs inflate 27-39 k tiles/s (profiles/r05_inflate.txt).
+    # Baseline-JPEG slides go the same way: the host parses the markers and copies the scan bytes, the GPU does the entropy decode,
+    # the IDCT, the upsampling and the colour conversion (``Engine.jpeg_decode``; profiles/jpeg_decode.txt) -- the same bytes.
     gpu_decode = bool(gpu_decode) and bool(pinned)
     out = []
     for path in paths:
@@ -227,6 +253,7 @@ RAMP_CHUNKS_Z = (512, 1024, 2048)
 Z_SLOT_MAX = 1 << 30      # bytes of one pinned slot of the compressed ring at most (three slots are leased)
 Z_FRACTION = 0.9         # pinned bytes per tile of a compressed chunk, as a fraction of the raw scanlines (a nearly incompressible 299-px
                          # PNG: 227 KB of 268 KB = 0.85; a photograph-like one 0.58); a chunk that does not fit is cut in two
+JPEG_SETS = 16           # table sets (Huffman lookups + quantisers, 21 KB each) a compressed JPEG chunk carries at most; a slide's tiles share one
 RING_SLOTS = 3
 PREFETCH_CHUNKS = 2      # decoded chunks waiting for the GPU (plus the one being decoded)
 
@@ -283,17 +310,20 @@ class _PinnedRing:
 class _Chunk:
     """What the feeder hands over: tiles in dataset order, ``segs`` = [(li, si, first, count)] (local and global slide index, tile
     range; several only in a compressed chunk).  ``kind``: 'tiles' ([count,px,px,3]), 'rows' (PNG scanlines [count,px,1+3*px], filters to be
-    reversed) or 'z' (``_ZChunk``'s layout, ``cap`` slots).  ``event``: behind the copy of ``data`` to the device; None: as the loader left it."""
+    reversed), 'z' (``_ZChunk``'s layout, ``cap`` slots) or 'j' (``_JChunk``'s layout, ``cap`` slots, ``sets`` table sets).  ``event``: behind
+    the copy of ``data`` to the device; None: as the loader left it."""
     kind: str
     segs: list
     data: object
     event: object
     cap: int = 0
+    sets: int = 0
 
 
 class _ZChunk:
     """The compressed chunk being filled (gpu_decode): [off u32[cap] | len u32[cap] | packed zlib streams] in one pinned slot, one H2D copy.
     It runs ACROSS slides (the device inflates one stream per lane: a 1 000-tile slide alone would leave the decode CUs' waves mostly empty)."""
+    kind = 'z'
 
     def __init__(self, ring, slot, cap, px):
         self.slot, self.cap, self.px = slot, cap, px
@@ -319,6 +349,58 @@ class _ZChunk:
                 cnt //= 2                                # (tiles that compress worse than the slot was sized for)
         if cnt:
             off[:cnt] += np.uint32(self.pos)
+            self.segs.append((li, si, first, cnt))
+            self.n += cnt
+            self.pos += used
+        return cnt
+
+
+class _JChunk:
+    """The compressed JPEG chunk being filled (gpu_decode): [desc u32[cap][4] | JPEG_SETS table sets | packed entropy-coded segments] in
+    one pinned slot, one H2D copy.  Like ``_ZChunk`` it runs across slides; the table sets of the slides in it are kept once each."""
+    kind = 'j'
+
+    def __init__(self, ring, slot, cap, px):
+        from . import tfrecord_native as tn
+        self.slot, self.cap, self.px = slot, cap, px
+        self.buf = ring.bufs[slot].numpy()
+        self.tb = tn.jpeg_table_bytes()
+        self.tab0, self.hdr = self.layout(cap, self.tb)
+        self.n = self.pos = 0                            # tiles in the chunk, bytes of their segments
+        self.segs, self.sets = [], []                    # ..., the chunk's table sets (bytes)
+        self.tmp = np.zeros((JPEG_SETS, self.tb), np.uint8)
+
+    @staticmethod
+    def layout(cap, tb):
+        """(offset of the table sets, offset of the segments) in a chunk of ``cap`` slots."""
+        tab0 = (16 * cap + 15) & ~15
+        return tab0, (tab0 + JPEG_SETS * tb + 15) & ~15
+
+    def add(self, src, li, si, first, left):
+        """Pack tiles [first, ...) of ``src``, ``left`` at most, behind what is there; returns how many went in (0: the slot is full)."""
+        cap = self.cap
+        cnt = min(cap - self.n, left)
+        desc = self.buf[:16 * cap].view(np.uint32).reshape(cap, 4)[self.n:]
+        room = self.buf[self.hdr + self.pos:]
+        while cnt:
+            try:
+                used, nt = src.read_jpeg(first, cnt, room, desc, self.tmp)
+                break
+            except MemoryError:
+                if cnt == 1 and not self.segs:
+                    raise
+                cnt //= 2                                # (tiles larger than the slot was sized for, or more table sets than a chunk carries)
+        if cnt:
+            new = [b for b in dict.fromkeys(self.tmp[k].tobytes() for k in range(nt)) if b not in self.sets]
+            if len(self.sets) + len(new) > JPEG_SETS:    # (no room for this slide's tables: it starts the next chunk)
+                return 0
+            for b in new:
+                k = len(self.sets)
+                self.buf[self.tab0 + k * self.tb:self.tab0 + (k + 1) * self.tb] = np.frombuffer(b, np.uint8)
+                self.sets.append(b)
+            remap = np.array([self.sets.index(self.tmp[k].tobytes()) for k in range(nt)], np.uint32)
+            desc[:cnt, 0] += np.uint32(self.pos)
+            desc[:cnt, 3] = remap[desc[:cnt, 3]]
             self.segs.append((li, si, first, cnt))
             self.n += cnt
             self.pos += used
@@ -386,7 +468,9 @@ class _Feeder:
                     continue
                 try:
                     if getattr(src, 'z', False) and src.z_ok():
-                        self._compressed(li, si, s, src)
+                        self._compressed(li, si, s, src, _ZChunk)
+                    elif getattr(src, 'z', False) and src.jpeg_ok():
+                        self._compressed(li, si, s, src, _JChunk)
                     else:
                         self._emit_z()                   # (a slide that goes the decoded way: what is open goes first)
                         self._decoded(li, si, s, src)
@@ -425,19 +509,22 @@ class _Feeder:
         c, self.zc = self.zc, None
         if c is not None and c.segs:
             d, ev = self._upload(c.slot, self.ring.bufs[c.slot][:c.hdr + c.pos])
-            self._put(_Chunk('z', c.segs, d, ev, c.cap))
+            self._put(_Chunk(c.kind, c.segs, d, ev, c.cap, len(getattr(c, 'sets', ()))))
 
-    def _compressed(self, li, si, s, src):
+    def _compressed(self, li, si, s, src, chunk_type):
+        """A slide that goes to the device compressed: PNG (``_ZChunk``) or baseline JPEG (``_JChunk``).  A chunk holds one format."""
         px = src.tile_px
-        self._need_ring(min(CHUNK_TILES_Z * (8 + int(Z_FRACTION * px * (1 + 3 * px))) + 64, Z_SLOT_MAX))   # (larger tiles: chunks of fewer)
+        from . import tfrecord_native as tn
+        # (larger tiles: chunks of fewer; both layouts fit: 16 bytes of descriptor per tile and the table sets are the JPEG chunk's)
+        self._need_ring(min(CHUNK_TILES_Z * (16 + int(Z_FRACTION * px * (1 + 3 * px))) + JPEG_SETS * tn.jpeg_table_bytes() + 64, Z_SLOT_MAX))
         first = 0
         while first < s.n_tiles:
-            if self.zc is not None and self.zc.px != px:
+            if self.zc is not None and (self.zc.px != px or type(self.zc) is not chunk_type):
                 self._emit_z()
             if self.zc is None:
                 cap = RAMP_CHUNKS_Z[self.n_chunks] if self.n_chunks < len(RAMP_CHUNKS_Z) else CHUNK_TILES_Z
                 self.n_chunks += 1
-                self.zc = _ZChunk(self.ring, self.ring.acquire(), cap, px)
+                self.zc = chunk_type(self.ring, self.ring.acquire(), cap, px)
             cnt = self.zc.add(src, li, si, first, s.n_tiles - first)
             first += cnt
             if not cnt or self.zc.n == self.zc.cap:
@@ -678,21 +765,21 @@ class _RangeWatch:
                              'these, or with dtype bf16 / f32')
 
 
-class _DeviceInflate:
-    """gpu_decode: compressed chunks are inflated on the pool's decode streams (CU-masked: the compute units it keeps out of the
-    inference streams; without a pool, the current stream), round-robin, each with its own table scratch; the status words are
-    looked at one chunk late (``check``)."""
+class _DeviceDecode:
+    """gpu_decode: compressed chunks are decoded on the pool's decode streams (CU-masked: the compute units it keeps out of the
+    inference streams; without a pool, the current stream), round-robin, each with its own scratch -- PNG chunks inflated
+    (``decode``), baseline-JPEG chunks decoded to tiles (``decode_jpeg``); the status words are looked at one chunk late (``check``)."""
 
     def __init__(self, eng0, pool, dev, slides):
         self.eng0, self.dev, self.slides = eng0, dev, slides
         self.streams = getattr(pool, 'decode_streams', None) if pool else None
         self.k = 0                                       # chunks so far: the round-robin counter
         self.scratch = {}                                # decode stream -> its table scratch
-        self.status = []                                 # in flight: (the chunk's segments, pinned status words, event)
+        self.status = []                                 # in flight: (the chunk's segments, pinned status words, event, format)
 
     def check(self, block):
         while self.status and (block or self.status[0][2].query()):
-            segs, status, ev = self.status.pop(0)
+            segs, status, ev, fmt = self.status.pop(0)
             ev.synchronize()
             bad = np.flatnonzero(status.numpy()).tolist()
             if bad:
@@ -701,30 +788,54 @@ class _DeviceInflate:
                     if at <= bad[0] < at + c:
                         where = f'{self.slides[si].name}, tile {first + bad[0] - at}'
                     at += c
-                raise IOError(f'the device inflate refused {len(bad)} tile(s) (first: {where}, status {int(status[bad[0]])}): damaged PNG '
+                what = 'inflate' if fmt == 'PNG' else 'JPEG decoder'
+                raise IOError(f'the device {what} refused {len(bad)} tile(s) (first: {where}, status {int(status[bad[0]])}): damaged {fmt} '
                               f'data; decode on the host (gpu_decode=False) to see the decoder\'s own error')
 
     def decode(self, chunk, px):
-        """A compressed chunk -> its tiles' filtered scanlines, ordered before the current stream's work that follows."""
+        """A compressed PNG chunk -> its tiles' filtered scanlines, ordered before the current stream's work that follows."""
         eng0, buf, cap, count = self.eng0, chunk.data, chunk.cap, sum(c for *_, c in chunk.segs)
-        main = torch.cuda.current_stream(self.dev)
-        dec = self.streams[self.k % len(self.streams)] if self.streams else main
-        self.k += 1
         off = buf[:4 * count].view(torch.int32)
         ln = buf[4 * cap:4 * cap + 4 * count].view(torch.int32)
         z = buf[(8 * cap + 15) & ~15:]
-        dec.wait_event(chunk.event)
-        buf.record_stream(dec)
-        key = dec.cuda_stream
-        with torch.cuda.stream(dec):
+
+        def work(key):
             if key not in self.scratch or self.scratch[key].numel() < eng0._lib.bq_png_inflate_scratch_bytes(count):
                 self.scratch[key] = eng0.inflate_scratch(max(count, CHUNK_TILES_Z))
-            rows, status = eng0.png_inflate(z, off, ln, px=px, scratch=self.scratch[key])
+            return eng0.png_inflate(z, off, ln, px=px, scratch=self.scratch[key])
+        return self._on_decode_stream(chunk, work, 'PNG')
+
+    def decode_jpeg(self, chunk, px):
+        """A compressed JPEG chunk -> its tiles (uint8 NHWC), ordered before the current stream's work that follows."""
+        from . import tfrecord_native as tn
+        eng0, buf, cap, count = self.eng0, chunk.data, chunk.cap, sum(c for *_, c in chunk.segs)
+        tb = tn.jpeg_table_bytes()
+        tab0, hdr = _JChunk.layout(cap, tb)
+        desc = buf[:16 * count].view(torch.int32).view(count, 4)
+        tables = buf[tab0:tab0 + chunk.sets * tb].view(chunk.sets, tb)
+        scan = buf[hdr:]
+
+        def work(key):
+            key = (key, 'jpeg')
+            if key not in self.scratch or self.scratch[key].numel() < eng0._lib.bq_jpeg_scratch_bytes(count, px):
+                self.scratch[key] = eng0.jpeg_scratch(max(count, CHUNK_TILES_Z), px)
+            return eng0.jpeg_decode(scan, desc, tables, px=px, scratch=self.scratch[key])
+        return self._on_decode_stream(chunk, work, 'JPEG')
+
+    def _on_decode_stream(self, chunk, work, fmt):
+        buf = chunk.data
+        main = torch.cuda.current_stream(self.dev)
+        dec = self.streams[self.k % len(self.streams)] if self.streams else main
+        self.k += 1
+        dec.wait_event(chunk.event)
+        buf.record_stream(dec)
+        with torch.cuda.stream(dec):
+            rows, status = work(dec.cuda_stream)
             done = torch.cuda.Event()
             done.record(dec)
         main.wait_event(done)
         rows.record_stream(main)
-        # the status words leave the device behind the inflate (a few KB, pinned, on the decode stream) and are looked at when the NEXT
+        # the status words leave the device behind the decode (a few KB, pinned, on the decode stream) and are looked at when the NEXT
         # chunk arrives -- one chunk late, without stalling anything: a damaged stream stops the run there instead of after it
         host = torch.empty(status.shape, dtype=status.dtype, pin_memory=True)
         with torch.cuda.stream(dec):
@@ -732,7 +843,7 @@ class _DeviceInflate:
             ev = torch.cuda.Event()
             ev.record(dec)
         self.check(block=False)
-        self.status.append((chunk.segs, host, ev))
+        self.status.append((chunk.segs, host, ev, fmt))
         return rows
 
 
@@ -905,7 +1016,7 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
                        tile_uq=tile_uq, normalizer=normalizer, norm_fit=norm_fit, keep_tiles=keep_tiles,
                        headroom_every=headroom_every, headroom_min=headroom_min, range_screen=range_screen)
         pending = _Pending()
-        inflate = _DeviceInflate(engines[0], pool, dev, slides)
+        decoder = _DeviceDecode(engines[0], pool, dev, slides)
         # With a pool, everything this function itself enqueues (H2D copies, concatenations, a device-side loader) goes to
         # a side stream, not to the default stream: the pool's CU-masked streams are ordinary (blocking) HIP streams, and
         # an operation on the legacy default stream is a barrier across all of those -- one such operation per batch and
@@ -919,7 +1030,9 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
             for chunk in chunks:
                 if chunk.kind == 'z':                    # a compressed chunk: inflate on the decode CUs, un-filter here
                     px = slides[chunk.segs[0][1]].source.tile_px
-                    tiles = engines[0].png_unfilter_strided(inflate.decode(chunk, px), px=px)
+                    tiles = engines[0].png_unfilter_strided(decoder.decode(chunk, px), px=px)
+                elif chunk.kind == 'j':                  # a compressed JPEG chunk: decoded to tiles on the decode CUs
+                    tiles = decoder.decode_jpeg(chunk, slides[chunk.segs[0][1]].source.tile_px)
                 elif chunk.event is None:                # as the slide's loader left them
                     tiles = _to_device(chunk.data, dev)
                 else:                                    # made on the copy stream: order it before this stream's work
@@ -954,7 +1067,7 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
         if pool:
             pool.synchronize()
         run.final_looks()
-        inflate.check(block=True)                        # what is left: the last chunks
+        decoder.check(block=True)                        # what is left: the last chunks
         live = [a for a in run.acc if a is not None]
         if live:
             # per-stream fixed-point accumulators are integers: their sum is exact and order-free

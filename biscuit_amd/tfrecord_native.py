@@ -31,6 +31,12 @@ ABI = {
     'bqio_decode_rows': (_i, [_vp, _i64, _i64, _i, _vp, _vp, _i, C.POINTER(_i64)]),
     'bqio_probe': (_i, [_vp, _i64, _i64, _i, C.POINTER(_i64)]),
     'bqio_extract_z': (_i, [_vp, _i64, _i64, _i, _vp, C.c_size_t, _vp, _vp, _vp, C.POINTER(C.c_size_t), _i, C.POINTER(_i64)]),
+    'bqio_extract_jpeg': (_i, [_vp, _i64, _i64, _i, _vp, C.c_size_t, _vp, _vp, _i, C.POINTER(_i), _vp, C.POINTER(C.c_size_t), _i,
+                               C.POINTER(_i64)]),
+    'bqio_jpeg_table_bytes': (C.c_size_t, []),
+    'bqio_jpeg_ecs_pad': (C.c_size_t, []),
+    'bqio_jpeg_coef_bytes': (C.c_size_t, [_i]),
+    'bqio_jpeg_decode_extracted': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i]),
     'bqio_masked_crc32c': (C.c_uint32, [C.c_char_p, C.c_size_t]),
     'bqio_inflate': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t]),
     'bqio_inflate2': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t, C.c_char_p, C.c_size_t, _vp, C.c_size_t,
@@ -107,6 +113,27 @@ def decode_jpeg(raw, tile_px=299):
     if e != 0:
         raise ValueError(f'bqio_decode_jpeg: error {e}')
     return out
+
+
+def jpeg_table_bytes():
+    """Bytes of one table set of ``NativeReader.extract_jpeg`` (the Huffman lookups and quantisers of a tile's three components)."""
+    return int(lib().bqio_jpeg_table_bytes())
+
+
+def jpeg_decode_extracted(scan, desc, tables, px=299, threads=None):
+    """The device JPEG decoder's routines (csrc/jpeg_device.h) on the CPU, over what ``NativeReader.extract_jpeg`` wrote:
+    -> (tiles uint8 [n,px,px,3], status int32 [n]); a tile whose status is not 0 was refused and its bytes are no image.
+    What ``Engine.jpeg_decode`` computes, byte for byte and status for status.  For tests."""
+    scan, desc, tables = np.ascontiguousarray(scan, np.uint8), np.ascontiguousarray(desc, np.uint32), np.ascontiguousarray(tables, np.uint8)
+    n = desc.shape[0]
+    assert desc.shape == (n, 4) and tables.size % jpeg_table_bytes() == 0
+    out = np.zeros((n, px, px, 3), np.uint8)
+    status = np.zeros(n, np.int32)
+    e = lib().bqio_jpeg_decode_extracted(scan.ctypes.data, desc.ctypes.data, tables.ctypes.data, tables.size // jpeg_table_bytes(), n, px,
+                                         out.ctypes.data, status.ctypes.data, threads or default_threads())
+    if e != 0:
+        raise ValueError(f'bqio_jpeg_decode_extracted: error {e}')
+    return out, status
 
 
 def inflate_fallbacks():
@@ -211,6 +238,36 @@ class NativeReader:
         if e != 0:
             raise IOError(f'{self.path}: {self._lib.bqio_last_error(self._h).decode()} (record {bad.value})')
         return int(used.value), loc
+
+    def extract_jpeg(self, first, count, tile_px, out_scan, desc, tables, threads=None):
+        """The JPEG counterpart of ``extract_z``, for the device decoder (``Engine.jpeg_decode``): the entropy-coded segments of
+        records [first, first + count), stuffed zeros removed and padded, packed into ``out_scan`` (uint8, usually pinned);
+        ``desc`` (uint32 [count, 4]: offset, length, sampling, table set) and ``tables`` (uint8 [k, jpeg_table_bytes()]: the call's
+        distinct table sets) are filled.  Returns (bytes used, table sets used, loc int64 [count, 2]).  ``out_scan=None``: only the
+        two sizes, nothing copied (the once-per-slide check).  The subset is the host decoder's (``probe``) without grey tiles and
+        without restart intervals: ``UnsupportedImage`` for a record outside it -- progressive, arithmetic-coded, CMYK, truncated,
+        grey, with restart markers, not a JPEG --, ``ValueError`` for a tile of another size; ``MemoryError`` (bytes needed in
+        ``.args[1]``, table sets needed in ``.args[2]``) when ``out_scan`` or ``tables`` is too small."""
+        loc = np.zeros((count, 2), np.int64)
+        used, nt, bad = C.c_size_t(0), C.c_int(0), _i64(-1)
+        if out_scan is None:
+            args = (None, 0, None, None, 0)
+        else:
+            assert out_scan.dtype == np.uint8 and out_scan.flags['C_CONTIGUOUS'] and desc.dtype == np.uint32 and desc.flags['C_CONTIGUOUS']
+            assert desc.size >= 4 * count and tables.dtype == np.uint8 and tables.flags['C_CONTIGUOUS']
+            args = (out_scan.ctypes.data, out_scan.size, desc.ctypes.data, tables.ctypes.data, tables.size // jpeg_table_bytes())
+        e = self._lib.bqio_extract_jpeg(self._h, first, count, tile_px, *args, C.byref(nt), loc.ctypes.data, C.byref(used),
+                                        threads or default_threads(), C.byref(bad))
+        if e == ERR_UNSUPPORTED:
+            raise UnsupportedImage(bad.value)
+        if e == ERR_FORMAT:
+            raise ValueError(f'{self.path}: record {bad.value}: tile size differs from {(tile_px, tile_px, 3)}')
+        if e != 0 and bad.value < 0 and out_scan is not None and (used.value > args[1] or nt.value > args[4]):
+            raise MemoryError(f'extract_jpeg: {used.value} bytes and {nt.value} table sets needed, {args[1]} and {args[4]} given',
+                              used.value, nt.value)
+        if e != 0:
+            raise IOError(f'{self.path}: {self._lib.bqio_last_error(self._h).decode()} (record {bad.value})')
+        return int(used.value), int(nt.value), loc
 
     def decode(self, first=0, count=None, tile_px=299, out=None, threads=None, rows=False):
         """-> (tiles uint8 [count,px,px,3], loc int64 [count,2]).  `out`: optional C-contiguous uint8

@@ -178,6 +178,24 @@ int bq_png_inflate(bq_ctx* ctx, const uint8_t* d_z, const uint32_t* d_off, const
 int bq_png_unfilter_strided(bq_ctx* ctx, const uint8_t* d_rows, size_t rows_stride, int n, int px, uint8_t* d_out_nhwc,
                             bq_stream_t stream);
 
+/* Input side, JPEG tiles, decoded on the device: n baseline-JPEG tiles (8-bit, Huffman, one interleaved scan of three components
+ * at 4:4:4 / 4:2:2 / 4:2:0, no restart intervals) as libbiscuit_io's bqio_extract_jpeg packs them -- d_scan: the entropy-coded
+ * segments, stuffed zeros removed, each at a multiple of 16 with bqio_jpeg_ecs_pad() zero bytes behind it; d_desc: n x 4 uint32
+ * (offset, length, sampling, table set); d_tables: n_tables table sets of bqio_jpeg_table_bytes() each, 4-byte aligned -- become
+ * uint8 NHWC tiles d_out_nhwc[n][px][px][3]: THE BYTES libjpeg's defaults give (islow IDCT, fancy upsampling, 16-bit BT.601), i.e.
+ * those of the host decoder and of Pillow.  An entropy kernel (one tile per lane, tables in LDS) leaves dequantised int16
+ * coefficients in d_scratch, a pixel stage (IDCT per block, then upsampling and colour per pixel) writes the tiles; tiles whose
+ * table sets, samplings and lengths differ may stand side by side.  d_status[i] = 0 iff tile i decoded; otherwise bits -- 1 a code
+ * that does not exist, 2 a zero run past coefficient 63, 4 data used from beyond the segment's end, 8 outside the range in which
+ * libjpeg's builds agree (a product or intermediate beyond 15 bits, a sample beyond -512..511), 16 a descriptor outside the subset
+ * -- and the tile's bytes are no image: the caller decodes that record on the host.  Scratch: 128 bytes per 8 x 8 block of a 4:4:4
+ * tile rounded up to whole 16 x 16 units -- 554 496 bytes per 299-px tile --; bq_jpeg_scratch_bytes(n, px) asks for min(n, 2048)
+ * tiles' worth (1.14 GB at 299 px) and the call works in rounds of as many tiles as d_scratch holds (more scratch: fewer, fuller
+ * rounds).  The scratch is zeroed as part of the call.  No reference counterpart (tf.io.decode_jpeg under tf.data). */
+size_t bq_jpeg_scratch_bytes(int n, int px);
+int bq_jpeg_decode(bq_ctx* ctx, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px,
+                   uint8_t* d_out_nhwc, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
+
 /* Variant for callers that already hold standardised float32 NHWC tiles (the
  * UncertaintyInterface contract, results.py:256-257): converts to planar NCHW. */
 int bq_stage_f32(bq_ctx* ctx, const float* d_tiles_nhwc_f32, int n, void* d_out_nchw,

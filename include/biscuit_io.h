@@ -81,6 +81,32 @@ int bqio_probe(bqio_reader* r, int64_t first, int64_t count, int tile_px, int64_
 int bqio_extract_z(bqio_reader* r, int64_t first, int64_t count, int tile_px, uint8_t* out_z, size_t cap, uint32_t* off,
                    uint32_t* len, int64_t* loc, size_t* used, int n_threads, int64_t* bad_index);
 
+/* The compressed side of baseline-JPEG tiles for the DEVICE decoder (libbiscuit_hip: bq_jpeg_decode), the JPEG counterpart of
+ * bqio_extract_z.  For records [first, first + count) the host parses the markers -- the header walk of the host decoder
+ * (csrc/jpeg_baseline.h: the same subset, the same refusals as bqio_probe) -- and copies every entropy-coded segment into
+ * out_scan with the stuffed zero bytes removed: segment i at its offset (a multiple of 16), bqio_jpeg_ecs_pad() zero bytes behind
+ * it.  desc[i] = four uint32: offset, length, hmax | vmax << 8 | components << 16 (4:4:4 / 4:2:2 / 4:2:0), index of the tile's
+ * TABLE SET.  tables receives the call's distinct table sets (Huffman lookups and quantisers per component,
+ * bqio_jpeg_table_bytes() each); the tiles of a slide normally share one, tiles with different sets may stand side by side.
+ * Narrower than the host decoder in two places: grey (one-component) tiles and files with restart intervals are
+ * BQIO_ERR_UNSUPPORTED here -- such a slide stays on bqio_decode.  Errors as bqio_extract_z (*bad_index = the record).
+ * *used = bytes of out_scan, *n_tables = table sets needed; too small a `cap` or `table_cap`: BQIO_ERR_ARG with both set.
+ * out_scan == NULL: nothing is copied, BQIO_OK with the two sizes (the once-per-slide check). */
+int bqio_extract_jpeg(bqio_reader* r, int64_t first, int64_t count, int tile_px, uint8_t* out_scan, size_t cap, uint32_t* desc,
+                      void* tables, int table_cap, int* n_tables, int64_t* loc, size_t* used, int n_threads, int64_t* bad_index);
+size_t bqio_jpeg_table_bytes(void);
+size_t bqio_jpeg_ecs_pad(void);
+/* int16 coefficient space the decoder uses per tile of this size (the device decoder's scratch per tile). */
+size_t bqio_jpeg_coef_bytes(int tile_px);
+
+/* The device decoder's own routines (csrc/jpeg_device.h) run on the CPU over what bqio_extract_jpeg wrote: n tiles ->
+ * out[n][tile_px][tile_px][3] and status[n] (0 = decoded; otherwise bits: 1 a code that does not exist, 2 a zero run past
+ * coefficient 63, 4 data used from beyond the segment's end, 8 outside the range in which libjpeg's builds agree, 16 a
+ * descriptor outside the subset; the tile's bytes are then not an image).  What bq_jpeg_decode computes, byte for byte and
+ * status for status: for tests and the fuzzer. */
+int bqio_jpeg_decode_extracted(const uint8_t* scan, const uint32_t* desc, const void* tables, int n_tables, int n, int tile_px,
+                               uint8_t* out, int32_t* status, int n_threads);
+
 /* One JPEG file (as bqio_image_bytes returns it) -> out[tile_px][tile_px][3], the decoder
  * bqio_decode uses, exported for tests.  BQIO_OK / BQIO_ERR_UNSUPPORTED / BQIO_ERR_FORMAT. */
 int bqio_decode_jpeg(const uint8_t* data, size_t len, int tile_px, uint8_t* out);
