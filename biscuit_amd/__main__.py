@@ -55,6 +55,34 @@ def model_hp(params):
     return hp, fit
 
 
+def load_model_weights(model=None, weights=None):
+    """(weights, params or None) of ``--model DIR`` (a Slideflow model directory: SavedModel weights plus params.json),
+    ``--weights FILE``, or neither (seeded random init): what both command lines load."""
+    if model:
+        from .keras_import import load_model_dir
+        return load_model_dir(model)
+    if weights:
+        from .keras_import import load_weights
+        return load_weights(weights), None
+    from .weights import synthetic_weights
+    return synthetic_weights(1), None
+
+
+def model_hp_from(model_params, params_path=None):
+    """``model_hp`` of the model directory's params, or -- when ``--params FILE`` is given -- of that params.json, which must
+    carry a norm_fit block."""
+    hp, norm_fit = model_hp(model_params)
+    if not params_path:
+        return hp, norm_fit
+    with open(params_path) as f:
+        raw = json.load(f)
+    hp, norm_fit = model_hp({'hp': raw.get('hp') or {}, 'normalizer': (raw.get('hp') or {}).get('normalizer', raw.get('normalizer', 'reinhard_fast')),
+                             'norm_fit': raw.get('norm_fit'), 'path': params_path})
+    if not norm_fit:
+        raise SystemExit(f'{params_path}: no norm_fit block')
+    return hp, norm_fit
+
+
 def _first_tiles(slide, n):
     """The first ``n`` decoded tiles of a slide as a uint8 array, reading no more than those: through the slide's chunk source
     when it has one (TFRecords: ``n`` records, not the slide -- a 10^4-tile slide is 2.7 GB decoded), with the PNG filters
@@ -137,22 +165,14 @@ def main(argv=None):
         if int(os.environ.get('RANK', '0')) == 0:
             print(json.dumps({'skipped': True, 'tile_table': os.path.join(args.out, 'tile_predictions_eval.csv')}))
         return
-    from . import distributed as D, threshold, weights as W
+    from . import distributed as D, threshold
     from .engine import EnginePool
     from .inference import Slide, evaluate, slides_from_tfrecords
     from .synthetic import make_slides
 
     rank, world, local = D.init_from_env('cuda', backend=args.dist_backend, local_device=args.local_device)
     D.pin_rank(int(os.environ.get('LOCAL_RANK', rank)), int(os.environ.get('LOCAL_WORLD_SIZE', world)), device_index=local)     # before any thread pool exists
-    model_params = None
-    if args.model:
-        from .keras_import import load_model_dir
-        w, model_params = load_model_dir(args.model)
-    elif args.weights:
-        from .keras_import import load_weights
-        w = load_weights(args.weights)
-    else:
-        w = W.synthetic_weights(1)
+    w, model_params = load_model_weights(args.model, args.weights)
     patients = None
     if args.tfrecords:
         lab = pd.read_csv(args.labels, dtype={'slide': str}) if args.labels else pd.DataFrame(columns=['slide', 'label'])
@@ -171,14 +191,7 @@ def main(argv=None):
             counts = [int(x) for x in args.synthetic.split(',')]
             slides = [Slide(f'slide{i:03d}', make_tiles(c, seed=500 + i, slide_bias=[(i % 2) * 60.0 - 30.0, 0.0, (i % 3) * 10.0]), c,
                             y_true=i % 2) for i, c in enumerate(counts)]
-    hp, norm_fit = model_hp(model_params)
-    if args.params:
-        with open(args.params) as f:
-            raw = json.load(f)
-        hp, norm_fit = model_hp({'hp': raw.get('hp') or {}, 'normalizer': (raw.get('hp') or {}).get('normalizer', raw.get('normalizer', 'reinhard_fast')),
-                                 'norm_fit': raw.get('norm_fit'), 'path': args.params})
-        if not norm_fit:
-            raise SystemExit(f'{args.params}: no norm_fit block')
+    hp, norm_fit = model_hp_from(model_params, args.params)
     if args.mc is None:
         args.mc = hp.uq_n
     act_exp, probe = None, None

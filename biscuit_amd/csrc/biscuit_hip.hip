@@ -1075,6 +1075,41 @@ int bq_jpeg_decode(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, const v
     return BQ_OK;
 }
 
+int bq_tile_resample(bq_ctx* c, const uint8_t* d_canvas, int H, int W, const int32_t* d_origin, int n, int src_px, int px,
+                     const int32_t* d_bounds, const int32_t* d_coef, int ksize, uint8_t* d_out, bq_stream_t stream) {
+    if (!c || n < 0 || n > (1 << 20) || px <= 0 || px > 4096 || src_px <= 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28) ||
+        (int64_t)src_px > 8ll * px || (int64_t)px > 8ll * src_px)
+        return fail(c, BQ_ERR_ARG, "bq_tile_resample: bad argument (need 0 < px <= 4096, px / 8 <= src_px <= 8 px, 0 <= n <= 2^20, H, W <= 2^28)");
+    if (n == 0) return BQ_OK;
+    if (!d_canvas || !d_origin || !d_out || ((uintptr_t)d_origin & 3)) return fail(c, BQ_ERR_ARG, "bq_tile_resample: bad argument");
+    if (src_px != px) {
+        if (!d_bounds || !d_coef || ((uintptr_t)d_bounds & 3) || ((uintptr_t)d_coef & 3) || ksize != resample_ksize(src_px, px))
+            return fail(c, BQ_ERR_ARG, "bq_tile_resample: the tap tables are not bqio_resample_taps(src_px, px)'s");
+        int rows = 0;
+        if (!resample_strip_rows(src_px, px, ksize, &rows))
+            return fail(c, BQ_ERR_ARG, "bq_tile_resample: the taps of one output row do not fit the kernel's LDS at this px and ratio");
+    }
+    if (resample_grid(n, src_px, px, ksize) > 0x7fffffffll)
+        return fail(c, BQ_ERR_ARG, "bq_tile_resample: n x strips of output rows exceeds 2^31 - 1 workgroups; split the call");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tile_resample", 2.0 * 2 * 3 * (double)n * px * px * (src_px == px ? 0 : ksize),
+                 (double)n * 3 * ((double)src_px * src_px + (double)px * px));
+    if (launch_tile_resample(d_canvas, H, W, d_origin, n, src_px, px, d_bounds, d_coef, ksize, d_out, s))
+        return fail(c, BQ_ERR_HIP, "tile resample launch failed");
+    return BQ_OK;
+}
+
+int bq_tile_grayspace(bq_ctx* c, const uint8_t* d_tiles, int n, int px, const int32_t* d_limit256, int32_t* d_count, bq_stream_t stream) {
+    if (!c || n < 0 || px <= 0 || px > 4096) return fail(c, BQ_ERR_ARG, "bq_tile_grayspace: bad argument");
+    if (n == 0) return BQ_OK;
+    if (!d_tiles || !d_limit256 || !d_count || ((uintptr_t)d_limit256 & 3) || ((uintptr_t)d_count & 3))
+        return fail(c, BQ_ERR_ARG, "bq_tile_grayspace: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tile_grayspace", 6.0 * n * px * px, 3.0 * n * px * px);
+    if (launch_tile_grayspace(d_tiles, n, px, d_limit256, d_count, s)) return fail(c, BQ_ERR_HIP, "grayspace launch failed");
+    return BQ_OK;
+}
+
 int bq_png_unfilter_strided(bq_ctx* c, const uint8_t* d_rows, size_t rows_stride, int n, int px, uint8_t* d_out, bq_stream_t stream) {
     if (!c || !d_rows || !d_out || n < 0 || px <= 0) return fail(c, BQ_ERR_ARG, "bq_png_unfilter_strided: bad argument");
     if (launch_png_unfilter(d_rows, n, px, d_out, (hipStream_t)stream, rows_stride)) return fail(c, BQ_ERR_HIP, "png unfilter launch failed");

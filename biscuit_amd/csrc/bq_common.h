@@ -135,6 +135,14 @@ int launch_inflate(const unsigned char* d_z, const unsigned* d_off, const unsign
 size_t jpeg_scratch_bytes(int n, int px);
 int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px, uint8_t* d_out,
                        int* d_status, void* d_scratch, size_t scratch_bytes, hipStream_t s);
+// kernels_resample.hip: the heatmap's tile grid cut from a canvas and resampled as Pillow's LANCZOS does (resample_device.h),
+// and the background filter's grey-pixel count
+int resample_ksize(int src_px, int px);
+int resample_strip_rows(int src_px, int px, int ksize, int* max_rows);      // 0: the ratio's taps do not fit the kernel's LDS
+long long resample_grid(int n, int src_px, int px, int ksize);
+int launch_tile_resample(const uint8_t* canvas, int H, int W, const int* origin, int n, int src_px, int px, const int* bounds,
+                         const int* coef, int ksize, uint8_t* out, hipStream_t s);
+int launch_tile_grayspace(const uint8_t* tiles, int n, int px, const int* limit256, int* count, hipStream_t s);
 int launch_stem1(const void* in_nchw, int n, const float* w27x32, const float* scale,
                  const float* bias, void* out_nhwc, int dtype, hipStream_t s);
 int launch_pool_add(const void* y, const void* res, void* out, int n, int Hi, int Wi, int C,

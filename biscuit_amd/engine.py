@@ -78,6 +78,8 @@ class Engine:
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
         self._check(self._lib.bq_load_weights(self._ctx, C.cast(buf, C.c_void_p), len(blob)))
         self._ws = None
+        self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
+        self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
         self._elt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[dtype]
 
     # shapes of the stored tensors by debug-tap name
@@ -122,6 +124,7 @@ class Engine:
         if getattr(self, '_ctx', None):
             self._lib.bq_destroy(self._ctx)
             self._ctx = None
+            self._resample_taps, self._grayspace_limit = {}, {}
 
     def __del__(self):
         try:
@@ -246,6 +249,50 @@ class Engine:
         """Coefficient space for ``jpeg_decode`` over ``n`` tiles (``bq_jpeg_scratch_bytes``: 554 KB per 299-px tile, for 2 048
         tiles at most -- 1.14 GB; a longer call works in rounds)."""
         return torch.empty(int(self._lib.bq_jpeg_scratch_bytes(int(n), int(px))), dtype=torch.uint8, device=self.device)
+
+    def tile_resample(self, canvas, origin, src_px, px=TILE_PX, out=None):
+        """The heatmap's tile grid cut from a slide canvas and resampled on the device (``bq_tile_resample``,
+        kernels_resample.hip): ``canvas`` uint8 [H, W, 3] and ``origin`` int32 [n, 2] -- the (x, y) of every tile's ``src_px``
+        window in the canvas; windows may overlap and may leave the canvas (white there) -- on this device -> uint8 NHWC
+        [n, px, px, 3], the bytes Pillow's ``resize((px, px), LANCZOS)`` gives for each window (``src_px == px``: the window
+        itself).  ``out``: a contiguous [n, px, px, 3] uint8 tensor (or view) to write into.  The tap tables of a ``(src_px,
+        px)`` pair are built on the host once (``resample.taps``) and stay on the device."""
+        assert canvas.dtype == torch.uint8 and canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == 3 and canvas.shape[2] == 3
+        assert origin.dtype == torch.int32 and origin.is_cuda and origin.is_contiguous() and origin.dim() == 2 and origin.shape[1] == 2
+        n, src_px, px = int(origin.shape[0]), int(src_px), int(px)
+        if out is None:
+            out = torch.empty((n, px, px, 3), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, px, px, 3)
+        bounds = coef = None
+        k = 0
+        if src_px != px:
+            cache = self._resample_taps
+            if (src_px, px) not in cache:
+                from . import resample
+                b, c = resample.taps(src_px, px)
+                cache[(src_px, px)] = (torch.from_numpy(b).to(self.device), torch.from_numpy(c).to(self.device))
+            bounds, coef = cache[(src_px, px)]
+            k = int(coef.shape[1])
+        self._check(self._lib.bq_tile_resample(self._ctx, _ptr(canvas), int(canvas.shape[0]), int(canvas.shape[1]), _ptr(origin), n,
+                                               src_px, px, _ptr(bounds), _ptr(coef), k, _ptr(out), self._stream()))
+        return out
+
+    def tile_grayspace(self, tiles_u8, threshold=0.05):
+        """Grey pixels per tile (``bq_tile_grayspace``): uint8 NHWC [n, px, px, 3] on this device -> int32 [n] on the device,
+        the number of pixels whose HSV saturation is below ``threshold`` by the float64 definition (``resample.grayspace_limit``
+        turns it into the integer table the kernel compares against)."""
+        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous() and tiles_u8.dim() == 4
+        assert tiles_u8.shape[1] == tiles_u8.shape[2] and tiles_u8.shape[3] == 3
+        cache = self._grayspace_limit
+        key = float(threshold)
+        if key not in cache:
+            from . import resample
+            cache[key] = torch.from_numpy(resample.grayspace_limit(key)).to(self.device)
+        n = int(tiles_u8.shape[0])
+        count = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._check(self._lib.bq_tile_grayspace(self._ctx, _ptr(tiles_u8), n, int(tiles_u8.shape[1]), _ptr(cache[key]), _ptr(count),
+                                                self._stream()))
+        return count
 
     def reinhard_fast(self, tiles_u8, target_means, target_stds, out=None):
         """`reinhard_fast` stain normalisation (hp.py:19; results.py:251-252 `wsi_normalizer.rgb_to_rgb`):

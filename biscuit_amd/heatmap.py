@@ -58,6 +58,7 @@ class Heatmap:
         if n and (grid[:, 0].max() >= gx or grid[:, 1].max() >= gy):
             raise ValueError('grid position outside grid_shape')
         self.grid = grid
+        self.dropped = 0                 # tiles a background filter left out (from_slide(grayspace_fraction=...))
         self.logits = np.full((gy, gx, 2), MASKED, dtype=np.float32)
         self.uncertainty = np.full((gy, gx, 2), MASKED, dtype=np.float32)
         dev = engine.device
@@ -80,19 +81,98 @@ class Heatmap:
         return cls(engine, tiles, grid, grid_shape=shape, **kw)
 
     @classmethod
-    def from_slide(cls, engine, path, tile_px=299, tile_um=302, stride_div=1, mpp=None, **kw):
+    def from_slide(cls, engine, path, tile_px=299, tile_um=302, stride_div=1, mpp=None, resample='gpu', canvas_bytes=256 << 20,
+                   grayspace_fraction=None, grayspace_threshold=0.05, **kw):
         """``sf.Heatmap(slide, model, stride_div=1)`` (results.py:217) for a pyramidal TIFF / SVS slide file: the tile grid of
         ``wsi.WSI(path, tile_px, tile_um, stride_div)`` through the MC-dropout kernels.  (The reader is this build's own --
-        ``biscuit_amd/wsi.py`` says what it reads and what about it is unpinned.)"""
+        ``biscuit_amd/wsi.py`` says what it reads and what about it is unpinned.)
+
+        ``resample='gpu'`` (default) streams the slide: the grid is read as bands of one canvas each (``WSI.bands``, at most
+        ``canvas_bytes`` a canvas), a band's canvas is uploaded once and its tiles are cut and resampled on the device
+        (``Engine.tile_resample``: Pillow's LANCZOS bytes), batch by batch, straight into the stain normaliser and ``mc_infer``;
+        no tile is held on the host and the device holds one canvas and one batch.  ``resample='host'`` reads and resamples
+        every tile on the host first (``WSI.tiles``); both give the same arrays.  A tile's Philox index is its row-major grid
+        index ``gy * grid_w + gx`` either way.
+
+        ``grayspace_fraction`` (``resample='gpu'`` only; default None = off): drop a tile as background when more than this
+        fraction of its pixels has an HSV saturation below ``grayspace_threshold`` (Slideflow's extraction filter, restated:
+        fraction 0.6 and threshold 0.05 there), before stain normalisation.  Dropped cells hold ``MASKED`` in both grids,
+        ``self.grid`` lists the kept tiles only and ``self.dropped`` counts the rest; a kept tile's values do not depend on the
+        filter."""
         from .wsi import WSI
+        if resample not in ('gpu', 'host'):
+            raise ValueError(f"resample must be 'gpu' or 'host', not {resample!r}")
+        if resample == 'host' and grayspace_fraction is not None:
+            raise ValueError("the background filter runs on the device: grayspace_fraction needs resample='gpu'")
         w = WSI(path, tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
         try:
-            tiles, grid = w.tiles()
-            if len(grid) == 0:
+            if w.grid_w * w.grid_h == 0:
                 raise ValueError(f'{path}: the slide holds no {tile_um} um tile')
-            return cls(engine, tiles, grid, grid_shape=(w.grid_h, w.grid_w), **kw)
+            if resample == 'host':
+                tiles, grid = w.tiles()
+                return cls(engine, tiles, grid, grid_shape=(w.grid_h, w.grid_w), **kw)
+            return cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, **kw)
         finally:
             w.close()
+
+    @classmethod
+    def _streamed(cls, engine, w, canvas_bytes, gray_fraction, gray_threshold, mc_n=30, seed=0, batch=256, norm_fit=None,
+                  normalizer='reinhard_fast'):
+        """``from_slide(resample='gpu')``: bands -> batches of exactly the tiles ``Heatmap(engine, *w.tiles())`` would put in
+        each batch (a batch is filled across band boundaries), so an unfiltered slide runs the same launches on the same bytes."""
+        from . import stain
+        stain.check(normalizer, norm_fit)
+        if gray_fraction is not None and not 0.0 <= float(gray_fraction) <= 1.0:
+            raise ValueError('grayspace_fraction must lie in [0, 1]')
+        hm = cls.__new__(cls)
+        gh, gw, px, dev, batch = w.grid_h, w.grid_w, w.tile_px, engine.device, int(batch)
+        hm.logits = np.full((gh, gw, 2), MASKED, dtype=np.float32)
+        hm.uncertainty = np.full((gh, gw, 2), MASKED, dtype=np.float32)
+        hm.dropped = 0
+        buf = torch.empty((batch, px, px, 3), dtype=torch.uint8, device=dev)      # the one batch the device holds
+        idx = np.empty(batch, np.int64)                                          # its tiles' row-major grid indices
+        kept, fill = [], 0
+
+        def flush(n):
+            cur = stain.normalise(engine, buf[:n], normalizer, norm_fit)
+            mean, std = engine.mc_infer(cur, mc_n, seed, tile_idx=torch.from_numpy(idx[:n]).to(dev))
+            gy, gx = np.divmod(idx[:n], gw)
+            hm.logits[gy, gx] = mean.cpu().numpy()
+            hm.uncertainty[gy, gx] = std.cpu().numpy()
+            kept.append(idx[:n].copy())
+
+        for gy0, gy1, gx0, gx1, canvas, origin, src_px in w.bands(canvas_bytes):
+            d_canvas = torch.from_numpy(canvas).to(dev)
+            d_origin = torch.from_numpy(origin).to(dev)
+            del canvas, origin                                                   # uploaded: the host holds one canvas at a time
+            cell = (np.arange(gy0, gy1, dtype=np.int64)[:, None] * gw + np.arange(gx0, gx1, dtype=np.int64)[None, :]).reshape(-1)
+            a = 0
+            while a < len(cell):
+                m = min(len(cell) - a, batch - fill)
+                dst = buf[fill:fill + m]
+                engine.tile_resample(d_canvas, d_origin[a:a + m], src_px, px, out=dst)
+                ids = cell[a:a + m]
+                if gray_fraction is not None:
+                    grey = engine.tile_grayspace(dst, gray_threshold).cpu().numpy()
+                    keep = ~(grey / float(px * px) > float(gray_fraction))
+                    if not keep.all():
+                        sel = torch.from_numpy(np.flatnonzero(keep)).to(dev)
+                        if len(sel):
+                            dst[:len(sel)] = dst[sel]                             # (the right side is a copy: no overlap)
+                        hm.dropped += m - len(sel)
+                        ids = ids[keep]
+                idx[fill:fill + len(ids)] = ids
+                fill += len(ids)
+                a += m
+                if fill == batch:
+                    flush(fill)
+                    fill = 0
+            del d_canvas
+        if fill:
+            flush(fill)
+        cells = np.concatenate(kept) if kept else np.zeros(0, np.int64)
+        hm.grid = np.stack([cells % gw, cells // gw], 1)
+        return hm
 
     def mask_uncertain(self, tile_uq_thresh):
         """results.py:224-225: ``uq_mask = hm.uncertainty[:, :, 0] > thresh; hm.logits[uq_mask, :] = [-1, -1]``.
@@ -109,3 +189,79 @@ class Heatmap:
             u = float(self.uncertainty[y, x, 0])
             (excl if u > tile_uq_thresh else incl).append((i, f'{u:.4f}-{x}-{y}.png'))
         return incl, excl
+
+
+def main(argv=None):
+    """``python -m biscuit_amd.heatmap SLIDE --out DIR``: the UQ heatmap of one slide file (results.py:216-265) on disk --
+    ``DIR/heatmap.npz`` (``logits``, ``uncertainty``, ``grid``; with ``--tile-uq`` also ``uq_mask`` and ``masked_logits``, the
+    logits with the uncertain cells set to -1 as results.py:222-225 does), ``DIR/summary.json`` and, with ``--save-tiles``, the
+    tiles as ``uq_incl/`` / ``uq_excl/`` PNGs named as results.py:259 names them."""
+    import argparse
+    import json
+    import os
+    import time
+    ap = argparse.ArgumentParser(prog='python -m biscuit_amd.heatmap', description=main.__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('slide', metavar='SLIDE', help='pyramidal TIFF / SVS slide file')
+    ap.add_argument('--weights', help='as python -m biscuit_amd --weights')
+    ap.add_argument('--model', help='as python -m biscuit_amd --model')
+    ap.add_argument('--params', help="Slideflow params.json: its normalizer and norm_fit switch the stain normaliser on")
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--stride-div', type=int, default=1)
+    ap.add_argument('--mc', type=int, default=None, help='MC-dropout passes (default: uq_n of the model, 30)')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--batch', type=int, default=256)
+    ap.add_argument('--dtype', default='f16', choices=['f16', 'bf16', 'f32'])
+    ap.add_argument('--tile-uq', type=float, default=None, help='tile-level uncertainty threshold: adds uq_mask and masked_logits')
+    ap.add_argument('--grayspace-fraction', type=float, default=None,
+                    help='drop tiles with more than this fraction of grey pixels (Slideflow extracts with 0.6); default: off')
+    ap.add_argument('--grayspace-threshold', type=float, default=0.05)
+    ap.add_argument('--mpp', type=float, default=None, help='microns per pixel, for a file that does not say')
+    ap.add_argument('--save-tiles', action='store_true', help='write the tiles to uq_incl/ and uq_excl/ (needs --tile-uq)')
+    args = ap.parse_args(argv)
+    if args.save_tiles and args.tile_uq is None:
+        ap.error('--save-tiles sorts by --tile-uq')
+    from .__main__ import load_model_weights, model_hp_from
+    from .engine import Engine
+    weights, model_params = load_model_weights(args.model, args.weights)
+    hp, norm_fit = model_hp_from(model_params, args.params)
+    mc = hp.uq_n if args.mc is None else args.mc
+    eng = Engine(weights, hp=hp, dtype=args.dtype, max_batch=args.batch, max_mc=mc)
+    try:
+        t0 = time.perf_counter()
+        hm = Heatmap.from_slide(eng, args.slide, stride_div=args.stride_div, mpp=args.mpp, mc_n=mc, seed=args.seed, batch=args.batch,
+                                norm_fit=norm_fit, normalizer=hp.normalizer or 'reinhard_fast',
+                                grayspace_fraction=args.grayspace_fraction, grayspace_threshold=args.grayspace_threshold)
+        torch.cuda.synchronize(eng.device)
+        seconds = time.perf_counter() - t0
+    finally:
+        eng.close()
+    os.makedirs(args.out, exist_ok=True)
+    arrays = {'logits': hm.logits.copy(), 'uncertainty': hm.uncertainty, 'grid': hm.grid}
+    if args.tile_uq is not None:
+        incl, excl = hm.split_by_uncertainty(args.tile_uq)
+        arrays['uq_mask'] = hm.mask_uncertain(args.tile_uq)              # (writes -1 into hm.logits: results.py:225)
+        arrays['masked_logits'] = hm.logits
+        if args.save_tiles:
+            from PIL import Image
+            from .wsi import WSI
+            w = WSI(args.slide, stride_div=args.stride_div, mpp=args.mpp)
+            try:
+                for name, items in (('uq_incl', incl), ('uq_excl', excl)):
+                    os.makedirs(os.path.join(args.out, name), exist_ok=True)
+                    for i, fname in items:
+                        gx, gy = hm.grid[i]
+                        Image.fromarray(w._tile(int(gx), int(gy))).save(os.path.join(args.out, name, fname))
+            finally:
+                w.close()
+    np.savez(os.path.join(args.out, 'heatmap.npz'), **arrays)
+    run = int(len(hm.grid))
+    summary = {'slide': args.slide, 'grid_shape': list(hm.logits.shape[:2]), 'tiles_run': run, 'tiles_dropped': int(hm.dropped),
+               'seconds': seconds, 'tiles_per_s': run / seconds if seconds > 0 else None}
+    with open(os.path.join(args.out, 'summary.json'), 'w') as f:
+        json.dump(summary, f)
+    print(json.dumps(summary))
+
+
+if __name__ == '__main__':
+    main()

@@ -301,11 +301,20 @@ class WSI:
     from the pyramid level with the largest downsample that still has at least ``tile_px`` pixels per tile and resampled to
     ``tile_px`` (Pillow LANCZOS).  ``roi_method``: only 'ignore' (what the reference passes) is implemented."""
 
+    READ_LIMIT = 1 << 16                 # pixels ``read_region`` reads at once, per side: ``bands`` splits wider grid rows
+
     @_guard
     def __init__(self, path, tile_px=TILE_PX, tile_um=TILE_UM, stride_div=1, roi_method='ignore', mpp=None):
         if roi_method != 'ignore':
             raise NotImplementedError("only roi_method='ignore' (results.py:235)")
         self.slide = TiffSlide(path)
+        try:
+            self._layout(path, tile_px, tile_um, stride_div, mpp)
+        except BaseException:
+            self.slide.close()                                           # a refusal below must not leave the file open
+            raise
+
+    def _layout(self, path, tile_px, tile_um, stride_div, mpp):
         self.path, self.tile_px, self.tile_um, self.stride_div = path, int(tile_px), float(tile_um), int(stride_div)
         self.mpp = float(mpp) if mpp else self.slide.mpp
         if not self.mpp:
@@ -356,6 +365,61 @@ class WSI:
             out[i] = t['image']
             grid[i] = t['loc']
         return out, grid
+
+    # ---- the grid as bands of one canvas each (heatmap.Heatmap.from_slide, resample='gpu') ------------------------------------
+    @property
+    def src_px(self):
+        """A tile's width in pixels of ``self.level`` (``_tile``'s ``lw``)."""
+        return max(1, int(round(self.extract_px / self.level_ds)))
+
+    def _level_xy(self, g):
+        return int(round(g * self.stride / self.level_ds))               # ``_tile``'s lx / ly of grid column / row g
+
+    @_guard
+    def band(self, gy0, gy1, gx0=0, gx1=None):
+        """Grid rows [gy0, gy1) (and columns [gx0, gx1), default all) as ONE read: ``(canvas, origin, src_px)`` -- canvas uint8
+        [H, W, 3], the rectangle of ``self.level`` that covers every tile's ``src_px`` x ``src_px`` window (white where a window
+        pokes past the level's edge, as ``read_region`` pads); origin int32 [T, 2], ``(lx - X0, ly - Y0)`` of every tile in
+        row-major grid order with ``lx, ly`` as ``_tile`` computes them; ``src_px`` = ``_tile``'s ``lw``.  Cutting the windows
+        out of the canvas and resampling them (``resample.tile_resample`` / ``Engine.tile_resample``) gives ``_tile``'s bytes."""
+        gx1 = self.grid_w if gx1 is None else gx1
+        if not (0 <= gy0 < gy1 <= self.grid_h and 0 <= gx0 < gx1 <= self.grid_w):
+            raise SlideError(f'band rows [{gy0}, {gy1}) x columns [{gx0}, {gx1}) outside the {self.grid_h} x {self.grid_w} grid')
+        lw = self.src_px
+        xs = np.array([self._level_xy(g) for g in range(gx0, gx1)], np.int64)
+        ys = np.array([self._level_xy(g) for g in range(gy0, gy1)], np.int64)
+        x0, y0 = int(xs[0]), int(ys[0])
+        canvas = self.slide.read_region(self.level, x0, y0, int(xs[-1]) + lw - x0, int(ys[-1]) + lw - y0)
+        origin = np.empty((len(ys), len(xs), 2), np.int32)
+        origin[:, :, 0] = (xs - x0)[None, :]
+        origin[:, :, 1] = (ys - y0)[:, None]
+        return canvas, origin.reshape(-1, 2), lw
+
+    def bands(self, canvas_bytes=256 << 20):
+        """Iterate the grid as bands whose canvas stays under ``canvas_bytes`` (at least one grid row each): yields ``(gy0, gy1,
+        gx0, gx1, canvas, origin, src_px)`` with ``band``'s values.  A band is split into column ranges only where one grid row
+        is wider than ``read_region`` reads at once (``READ_LIMIT``, 65 536 pixels); the tiles of such a slide then arrive band by
+        band, not in row-major order of the whole grid."""
+        lw, limit = self.src_px, self.READ_LIMIT
+        cols, gx0 = [], 0
+        while gx0 < self.grid_w:                                          # column ranges of at most `limit` pixels
+            gx1 = gx0 + 1
+            while gx1 < self.grid_w and self._level_xy(gx1) + lw - self._level_xy(gx0) <= limit:
+                gx1 += 1
+            cols.append((gx0, gx1))
+            gx0 = gx1
+        widest = max((self._level_xy(b - 1) + lw - self._level_xy(a) for a, b in cols), default=0)
+        gy0 = 0
+        while gy0 < self.grid_h:
+            gy1 = gy0 + 1
+            while gy1 < self.grid_h:
+                h = self._level_xy(gy1) + lw - self._level_xy(gy0)
+                if h > limit or h * widest * 3 > canvas_bytes:
+                    break
+                gy1 += 1
+            for a, b in cols:
+                yield (gy0, gy1, a, b) + self.band(gy0, gy1, a, b)
+            gy0 = gy1
 
     def close(self):
         self.slide.close()

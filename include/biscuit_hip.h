@@ -196,6 +196,30 @@ size_t bq_jpeg_scratch_bytes(int n, int px);
 int bq_jpeg_decode(bq_ctx* ctx, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px,
                    uint8_t* d_out_nhwc, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
 
+/* The whole-slide heatmap's input stage (kernels_resample.hip; DESIGN.md "Heatmap input"): n tiles cut out of a slide canvas in
+ * device memory and resampled to px x px -- what sf.Heatmap's slide reader does per tile on the host (results.py:217).  d_canvas
+ * uint8 [H][W][3]; tile t is the src_px x src_px window at (d_origin[2 t], d_origin[2 t + 1]) = (x, y) (int32; windows may
+ * overlap, and may leave the canvas: pixels outside read as 255); d_bounds int32 [px][2] and d_coef int32 [px][ksize] are
+ * bqio_resample_taps(src_px, px)'s tables (include/biscuit_io.h), uploaded by the caller; d_out uint8 NHWC [n][px][px][3], the
+ * batch bq_mc_infer takes.  The bytes are those of Pillow's Image.resize((px, px), Image.LANCZOS) of the window: horizontal pass
+ * rounded to bytes (kept in LDS), then the vertical pass, integer arithmetic throughout.  src_px == px copies the window (the
+ * tables may then be NULL).  Supported: 0 < px <= 4096, px / 8 <= src_px <= 8 px, and (ksize + 1) * 3 px <= 64 000 bytes of
+ * LDS (px = 299: the whole ratio range); H, W <= 2^28; n <= 2^20 and n x (strips of output rows per tile: ceil(px / R), R <= 32 the
+ * rows whose taps fit the LDS, 10 strips at px = 299) <= 2^31 - 1.  Origins are device memory and are not checked: a coordinate
+ * beyond +-2^28 is used as +-2^28, where the window lies outside the canvas (white), as bqio_tile_resample refuses it on the host.
+ * Everything is enqueued on `stream` without a host synchronisation; n = 0 returns 0
+ * without a launch; a bad argument -- a ksize that is not the ratio's included -- is BQ_ERR_ARG with nothing enqueued. */
+int bq_tile_resample(bq_ctx* ctx, const uint8_t* d_canvas, int H, int W, const int32_t* d_origin, int n, int src_px, int px,
+                     const int32_t* d_bounds, const int32_t* d_coef, int ksize, uint8_t* d_out_nhwc, bq_stream_t stream);
+
+/* The background filter's measure (Slideflow's grayspace filter at extraction, restated: DESIGN.md "Heatmap input"): d_count[t] =
+ * the number of pixels of tile t whose HSV saturation is below the threshold.  With mx = max(r, g, b), mn = min(r, g, b) a pixel
+ * counts iff mx - mn < d_limit256[mx]; the host builds the 256 int32 entries from the float64 definition (s = 0 if mx == 0 else
+ * (mx - mn) / mx; grey iff s < threshold), so the device compares integers.  d_tiles uint8 NHWC [n][px][px][3], d_count int32 [n].
+ * Enqueued on `stream`, no host synchronisation; n = 0 returns 0 without a launch. */
+int bq_tile_grayspace(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, int px, const int32_t* d_limit256, int32_t* d_count,
+                      bq_stream_t stream);
+
 /* Variant for callers that already hold standardised float32 NHWC tiles (the
  * UncertaintyInterface contract, results.py:256-257): converts to planar NCHW. */
 int bq_stage_f32(bq_ctx* ctx, const float* d_tiles_nhwc_f32, int n, void* d_out_nchw,

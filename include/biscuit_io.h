@@ -107,6 +107,25 @@ size_t bqio_jpeg_coef_bytes(int tile_px);
 int bqio_jpeg_decode_extracted(const uint8_t* scan, const uint32_t* desc, const void* tables, int n_tables, int n, int tile_px,
                                uint8_t* out, int32_t* status, int n_threads);
 
+/* ---- tile resampling for the whole-slide heatmap (csrc/resample_host.cpp, csrc/resample_device.h) ----
+ * The tap tables of Pillow's 8-bit resampler for Image.resize((px, px), Image.LANCZOS) of a src_px x src_px image: per output
+ * coordinate i, bounds[2 i] = first source coordinate, bounds[2 i + 1] = number of taps, coef[i * ksize + j] = tap j with 22
+ * fractional bits (zero behind the count).  Built as Pillow builds them: support 3, filterscale = max(src_px / px, 1), ksize =
+ * 2 ceil(3 filterscale) + 1, the window clamped to the source, taps normalised by their sum in float64 and rounded away from
+ * zero.  Supported: 0 < px <= 4096 and px / 8 <= src_px <= 8 px (ksize <= 49); anything else is BQIO_ERR_ARG and nothing is
+ * written.  The tables serve both passes (a tile is square).  bqio_resample_ksize returns ksize; bqio_resample_taps fills
+ * bounds [px][2] and coef [px][ksize] and returns ksize too (BQIO_ERR_ARG when ksize_cap < ksize; BQIO_ERR_UNSUPPORTED if
+ * 2^21 + 255 * sum |tap| of a row did not fit 31 bits -- the 32-bit accumulators of both passes rest on it). */
+int bqio_resample_ksize(int src_px, int px);
+int bqio_resample_taps(int src_px, int px, int32_t* bounds, int32_t* coef, int ksize_cap);
+
+/* The CPU restatement of bq_tile_resample, over the same per-pixel routines: n tiles cut from canvas uint8 [H][W][3] -- tile t
+ * is the src_px x src_px window at (origin[2 t], origin[2 t + 1]) = (x, y), parts of it outside the canvas read as 255 -- each
+ * resampled to out[t][px][px][3]: the horizontal pass rounded to bytes, then the vertical pass, the bytes Pillow gives.
+ * src_px == px copies the window.  BQIO_ERR_ARG for a ratio outside the range above, px <= 0, n < 0, an empty canvas or an
+ * origin beyond +-2^28; n = 0 returns BQIO_OK and touches nothing.  For tests and the sanitizer build. */
+int bqio_tile_resample(const uint8_t* canvas, int H, int W, const int32_t* origin, int n, int src_px, int px, uint8_t* out);
+
 /* One JPEG file (as bqio_image_bytes returns it) -> out[tile_px][tile_px][3], the decoder
  * bqio_decode uses, exported for tests.  BQIO_OK / BQIO_ERR_UNSUPPORTED / BQIO_ERR_FORMAT. */
 int bqio_decode_jpeg(const uint8_t* data, size_t len, int tile_px, uint8_t* out);
