@@ -77,7 +77,7 @@ class Engine:
         blob = pack_blob(weights, dtype, self.act_exp)
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
         self._check(self._lib.bq_load_weights(self._ctx, C.cast(buf, C.c_void_p), len(blob)))
-        self._ws = None
+        self._ws = self._inflate_ws = self._jpeg_ws = None        # device buffers grown on demand (``_grown``)
         self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
         self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
         self._elt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[dtype]
@@ -125,6 +125,7 @@ class Engine:
             self._lib.bq_destroy(self._ctx)
             self._ctx = None
             self._resample_taps, self._grayspace_limit = {}, {}
+            self._ws = self._inflate_ws = self._jpeg_ws = None
 
     def __del__(self):
         try:
@@ -141,13 +142,16 @@ class Engine:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _grown(self, name, need):
+        """The cached device buffer ``self.<name>`` (a torch uint8 tensor), ``need`` bytes at least: the old one goes before the larger comes."""
+        if getattr(self, name) is None or getattr(self, name).numel() < need:
+            setattr(self, name, None)
+            setattr(self, name, torch.empty(need, dtype=torch.uint8, device=self.device))
+        return getattr(self, name)
+
     def _ws_for(self, n, mc_n):
         """Caller-owned device workspace (a torch uint8 tensor), grown on demand."""
-        need = self._lib.bq_workspace_bytes(self._ctx, int(n), int(mc_n))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grown('_ws', self._lib.bq_workspace_bytes(self._ctx, int(n), int(mc_n)))
 
     def set_num_cus(self, n):
         """Size the persistent kernels' grids for ``n`` compute units (``bq_set_num_cus``; 0: the whole device): what a context
@@ -193,9 +197,7 @@ class Engine:
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         need = int(self._lib.bq_png_inflate_scratch_bytes(n))
         if scratch is None:                 # (launches that may overlap on different streams bring their own: ``inflate_scratch``)
-            if getattr(self, '_inflate_ws', None) is None or self._inflate_ws.numel() < need:
-                self._inflate_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            scratch = self._inflate_ws
+            scratch = self._grown('_inflate_ws', need)
         assert scratch.numel() >= need
         self._check(self._lib.bq_png_inflate(self._ctx, _ptr(z), _ptr(off), _ptr(length), n, px, _ptr(rows), stride,
                                              _ptr(scratch), scratch.numel(), _ptr(status), self._stream()))
@@ -216,10 +218,7 @@ class Engine:
         """Compressed PNG tiles -> uint8 NHWC [n,px,px,3] entirely on the device: ``png_inflate``, then the scanline filters
         reversed (``bq_png_unfilter_strided``).  Returns ``(tiles, status)``; a tile whose status is not 0 is undefined."""
         rows, status = self.png_inflate(z, off, length, px)
-        n = rows.shape[0]
-        out = torch.empty((n, px, px, 3), dtype=torch.uint8, device=self.device)
-        self._check(self._lib.bq_png_unfilter_strided(self._ctx, _ptr(rows), rows.shape[1], n, px, _ptr(out), self._stream()))
-        return out, status
+        return self.png_unfilter_strided(rows, px), status
 
     def jpeg_decode(self, scan, desc, tables, px=TILE_PX, scratch=None):
         """n baseline-JPEG tiles decoded on the device (``bq_jpeg_decode``, kernels_jpeg.hip: entropy decode one tile per lane,
@@ -236,10 +235,7 @@ class Engine:
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         need = int(self._lib.bq_jpeg_scratch_bytes(n, px))
         if scratch is None:
-            if getattr(self, '_jpeg_ws', None) is None or self._jpeg_ws.numel() < need:
-                self._jpeg_ws = None
-                self._jpeg_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            scratch = self._jpeg_ws
+            scratch = self._grown('_jpeg_ws', need)
         assert scratch.numel() >= need
         self._check(self._lib.bq_jpeg_decode(self._ctx, _ptr(scan), _ptr(desc), _ptr(tables), int(tables.shape[0]), n, px, _ptr(out),
                                              _ptr(status), _ptr(scratch), scratch.numel(), self._stream()))

@@ -421,8 +421,15 @@ def test_host_tiles_through_the_pinned_ring_equal_resident_tiles(monkeypatch):
     and batches span chunks: the tile table and the slide table equal those of the same tiles handed over whole."""
     import biscuit_amd.inference as inf
     from bench import _HostTiles
+    from biscuit_amd import feed
     from biscuit_amd.engine import Engine
-    monkeypatch.setattr(inf, 'CHUNK_TILES', 7)
+    monkeypatch.setattr(feed, 'CHUNK_TILES', 7)
+    calls, read = [], _HostTiles.read
+
+    def counted(self, *a):
+        calls.append(id(self))
+        return read(self, *a)
+    monkeypatch.setattr(_HostTiles, 'read', counted)
     n_slides, per = 3, 19
     tiles, sidx, y = make_slides(n_slides, per, seed=9)
     whole = [inf.Slide(f'h{i}', tiles[sidx == i], per, y_true=int(y[i])) for i in range(n_slides)]
@@ -431,6 +438,8 @@ def test_host_tiles_through_the_pinned_ring_equal_resident_tiles(monkeypatch):
     eng = Engine(synthetic_weights(1), dtype='f16', max_batch=16, max_mc=5)
     a = inf.evaluate(eng, whole, outcome='cohort', mc_n=5, seed=7, batch=16)
     b = inf.evaluate(eng, ring, outcome='cohort', mc_n=5, seed=7, batch=16)
+    # the run really was cut up: the first chunks of a run are the ramp's and hold a slide each, the last slide's 19 tiles meet CHUNK_TILES
+    assert calls.count(id(ring[-1].source)) > 1
     for col in ('cohort-y_pred1', 'cohort-uncertainty1'):
         assert np.array_equal(a.tile_df[col].to_numpy(), b.tile_df[col].to_numpy()), col
     assert np.array_equal(a.slide_pred, b.slide_pred) and np.array_equal(a.slide_count, b.slide_count)

@@ -169,10 +169,16 @@ def test_evaluate_from_compressed_chunks_equals_host_decoded_tiles(tmp_path, poo
     that several are in flight and a slide spans chunks."""
     import io
     from PIL import Image
-    from biscuit_amd import inference as inf
+    from biscuit_amd import feed, inference as inf
     from biscuit_amd.engine import Engine, EnginePool
-    monkeypatch.setattr(inf, 'CHUNK_TILES_Z', 8)
-    monkeypatch.setattr(inf, 'RAMP_CHUNKS_Z', (3, 5))
+    monkeypatch.setattr(feed, 'CHUNK_TILES_Z', 8)
+    monkeypatch.setattr(feed, 'RAMP_CHUNKS_Z', (3, 5))
+    calls, read_z = [], feed.TFRecordSource.read_z
+
+    def counted(self, *a):
+        calls.append(os.path.basename(self.path))
+        return read_z(self, *a)
+    monkeypatch.setattr(feed.TFRecordSource, 'read_z', counted)
     paths, labels = _slides_on_disk(tmp_path, 3, 19, seed=31)
     # a fourth slide with one JPEG among its PNG records
     t = make_tiles(4, seed=8)
@@ -188,6 +194,7 @@ def test_evaluate_from_compressed_chunks_equals_host_decoded_tiles(tmp_path, poo
         e = Engine(w, dtype='f16', max_batch=16, max_mc=5)
     a = inf.evaluate(e, inf.slides_from_tfrecords(paths, labels, gpu_decode=True), outcome='cohort', mc_n=5, seed=3, batch=16)
     ref = inf.evaluate(e, inf.slides_from_tfrecords(paths, labels), outcome='cohort', mc_n=5, seed=3, batch=16)
+    assert all(calls.count(f'z{i}.tfrecords') > 1 for i in range(3))          # the run really was cut up: 19 tiles, several reads
     assert list(a.slide_count) == [19, 19, 19, 4]
     for col in ('cohort-y_pred1', 'cohort-uncertainty1'):
         assert np.array_equal(a.tile_df[col].to_numpy(), ref.tile_df[col].to_numpy()), col

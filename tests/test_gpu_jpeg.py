@@ -111,10 +111,16 @@ def test_evaluate_from_jpeg_chunks_equals_the_host_decoded_run(tmp_path, pooled,
     progressive record (which stays on the host): the slide table, the per-tile mean / std and the bytes of
     tile_predictions_eval.csv are those of the host-decoded run.  Small chunks: several in flight, slides span chunks, PNG and
     JPEG chunks alternate."""
-    from biscuit_amd import inference as inf
+    from biscuit_amd import feed, inference as inf
     from biscuit_amd.engine import Engine, EnginePool
-    monkeypatch.setattr(inf, 'CHUNK_TILES_Z', 8)
-    monkeypatch.setattr(inf, 'RAMP_CHUNKS_Z', (3, 5))
+    monkeypatch.setattr(feed, 'CHUNK_TILES_Z', 8)
+    monkeypatch.setattr(feed, 'RAMP_CHUNKS_Z', (3, 5))
+    calls, read_jpeg = [], feed.TFRecordSource.read_jpeg
+
+    def counted(self, *a):
+        calls.append(os.path.basename(self.path))
+        return read_jpeg(self, *a)
+    monkeypatch.setattr(feed.TFRecordSource, 'read_jpeg', counted)
     paths, labels = _cohort(tmp_path)
     srcs = [s.source for s in inf.slides_from_tfrecords(paths, labels, gpu_decode=True)]
     assert [s.z_ok() for s in srcs] == [True, False, False, False, False, True]
@@ -131,6 +137,7 @@ def test_evaluate_from_jpeg_chunks_equals_the_host_decoded_run(tmp_path, pooled,
     os.makedirs(da); os.makedirs(dr)
     a = inf.evaluate(e, inf.slides_from_tfrecords(paths, labels, gpu_decode=True), outcome='cohort', mc_n=5, seed=3, batch=16, save_dir=da)
     ref = inf.evaluate(e, inf.slides_from_tfrecords(paths, labels), outcome='cohort', mc_n=5, seed=3, batch=16, save_dir=dr)
+    assert calls.count('jpg444.tfrecords') > 1 and calls.count('jpg420.tfrecords') > 1      # the run really was cut up: 19 tiles, several reads
     assert list(a.slide_count) == [19, 19, 0, 19, 5, 7]
     for col in ('cohort-y_pred0', 'cohort-y_pred1', 'cohort-uncertainty0', 'cohort-uncertainty1'):
         assert np.array_equal(a.tile_df[col].to_numpy(), ref.tile_df[col].to_numpy()), col
