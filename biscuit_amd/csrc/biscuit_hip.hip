@@ -75,7 +75,6 @@ static_assert(kNumLayers == 39, "block1_conv2, 34 separable convolutions, 4 shor
 struct GemmLayer {   // what the blob holds for row i of kLayers
     const void* wp = nullptr;
     const void* wp16 = nullptr;   // the same weights in 16x16x32 fragment order (kernels_wide / stream / exit.hip)
-    const void* wp32 = nullptr;   // ... in 32x32x16 fragment order (strided shortcuts, kernels_respool.hip)
     const float* scale = nullptr;
     const float* bias = nullptr;
     const float* dw = nullptr;
@@ -255,28 +254,24 @@ enum RouteKind : int {
     R_ERROR,
     R_FRONT,               // uint8 tiles: staging + block1_conv1 + block1_conv2 in one kernel (kernels_front.hip)
     R_STREAM,              // kernels_stream.hip
-    R_TILE,                // kernels_tile.hip, instance `tile_kind`
+    R_TILE,                // kernels_tile.hip: block1_conv2 of the float entry ("TILE kind=0")
     R_DW_THEN_EXIT,        // depthwise kernel (kernels_split.hip), then kernels_exit.hip
-    R_DW_THEN_TILED_GEMM,  // depthwise kernel, then the 128 x 128-tile GEMM (kernels_split.hip)
-    R_S2_TILED_GEMM,       // the tiled GEMM over the even pixels of the input map
+    R_S2_TILED_GEMM,       // the 128 x 128-tile GEMM (kernels_split.hip) over the even pixels of the input map
     R_WIDE,                // kernels_wide.hip
-    R_PIPE,                // kernels_pipe.hip
-    R_FUSED_GEMM,          // kernels_gemm.hip, `nsplit` launches over slices of K
+    R_FUSED_GEMM,          // kernels_gemm.hip, `nsplit` launches over slices of K: the one fallback below the routes above
     // the end of a block with a strided shortcut (asked of its shortcut row):
     R_BLOCK_TAIL,          // sepconv2 + max-pool + shortcut + add in one kernel (kernels_stream.hip); sepconv2 is not launched
     R_POOL_GEMM,           // the shortcut as the tiled GEMM with the pooling pass as its store pass
-    R_RESPOOL,             // kernels_respool.hip
     R_CONV_THEN_POOL       // the shortcut by its own route `conv`, then the pool + add kernel (kernels_misc.hip)
 };
-const char* const kRouteNames[] = {"ERROR", "FRONT", "STREAM", "TILE", "DW_THEN_EXIT", "DW_THEN_TILED_GEMM", "S2_TILED_GEMM", "WIDE",
-                                   "PIPE", "FUSED_GEMM", "BLOCK_TAIL", "POOL_GEMM", "RESPOOL", "CONV_THEN_POOL"};
+const char* const kRouteNames[] = {"ERROR", "FRONT", "STREAM", "TILE", "DW_THEN_EXIT", "S2_TILED_GEMM", "WIDE",
+                                   "FUSED_GEMM", "BLOCK_TAIL", "POOL_GEMM", "CONV_THEN_POOL"};
 
 struct Route {
     RouteKind kind = R_ERROR;
     RouteKind conv = R_ERROR;   // the convolution's own route: `kind` itself unless kind == R_CONV_THEN_POOL
-    int tile_kind = -1;         // R_TILE
     int nsplit = 1, shape = -1; // R_FUSED_GEMM
-    bool gap = false;           // R_DW_THEN_*: the global average pool is the GEMM's epilogue (GAP_EPILOGUE), the tensor is not written
+    bool gap = false;           // R_DW_THEN_EXIT: the global average pool is the GEMM's epilogue (GAP_EPILOGUE), the tensor is not written
     int err = BQ_OK;            // R_ERROR: the code, its text in *why
 };
 
@@ -312,11 +307,8 @@ Route choose_route(const bq_ctx* c, int li, int n, bool from_u8, const char* tap
             return conv(R_BLOCK_TAIL);
         const bool want_res = wants(tap, L.name);
         // blocks 3, 4 and 13 (K = 128 / 256 / 736): the shortcut tensor never goes to HBM, one launch instead of two
-        // (block 3: 0.273 -> 0.242 ms against kernels_respool.hip; block 2, K = 64, lives in the fused tail)
+        // (block 2, K = 64, lives in the fused tail)
         if (is16(dtype) && !want_res && L.kpad >= 128 && G.nfp % 4 == 0) return conv(R_POOL_GEMM);
-        // kernels_respool.hip, measured per batch of 256 (one stream): block 2 0.62 -> 0.46 ms, block 3 0.34 -> 0.27 ms; block 4
-        // (K = 256, six 128-channel workgroups per pixel tile) 0.26 -> 0.34 ms and block 13 0.19 -> 0.20 ms stay off it
-        if (is16(dtype) && G.wp32 && !want_res && L.kpad <= 128) return conv(R_RESPOOL);
         r.kind = R_CONV_THEN_POOL;
     }
     const bool residual = L.flags & F_RES, dwp = L.prod == PROD_DW || L.prod == PROD_DW_RELU, same = L.H == L.Hi;
@@ -334,40 +326,30 @@ Route choose_route(const bq_ctx* c, int li, int n, bool from_u8, const char* tap
     if (dwp && G.wp16 && !residual && nsplit == 1 && same && L.ldi == L.kpad && L.ldo == L.cout &&
         stream_supported(dtype, L.kpad, L.cout, L.prod == PROD_DW_RELU, n, L.H, L.H))
         return conv(R_STREAM);
-    if (is16(dtype) && !residual) {
-        if (L.prod == PROD_IM2COL && L.cin == 32 && L.cout == 64) r.tile_kind = 0;
-        else if (L.prod == PROD_DW && L.cin == 64 && L.cout == 128) r.tile_kind = 1;
-        else if (L.prod == PROD_DW && L.cin == 128 && L.cout == 128) r.tile_kind = 2;
-        else if (L.prod == PROD_DW_RELU && L.cin == 128 && L.cout == 256 &&
-                 !(G.wp16 && same && nsplit == 1 && wide_supported(dtype, L.prod, G.nfp, L.H, L.H, L.kpad, L.ldo, L.ldi, L.ldo, M, false)))
-            r.tile_kind = 3;        // (block3_sepconv1 when neither the streaming nor the wide kernel takes it)
-        if (r.tile_kind >= 0) return conv(R_TILE);
-    }
-    // Two-kernel form (depthwise kernel + GEMM): always for the wide exit-flow layers (K >= 1024: the fused kernel can only hold
-    // 32-64 rows of A in LDS there and re-streams the 3-6 MB weight matrix per 32-64 rows).  No STREAM or TILE layer is that wide.
-    if (L.kpad >= 1024 && is16(dtype) && dwp && G.nfp % 4 == 0 && (L.flags & F_DWTMP) && nsplit == 1) {
+    if (is16(dtype) && L.prod == PROD_IM2COL && L.cin == 32 && L.cout == 64) return conv(R_TILE);
+    // Two-kernel form (depthwise kernel + GEMM) for the wide exit-flow layers (K >= 1024: the fused kernel can only hold 32-64 rows
+    // of A in LDS there and re-streams the 3-6 MB weight matrix per 32-64 rows): one image's pixels x 256 channels per workgroup on
+    // 16x16x32 fragments, block 14.  No STREAM or TILE layer is that wide.
+    if (L.kpad >= 1024 && is16(dtype) && dwp && G.nfp % 4 == 0 && (L.flags & F_DWTMP) && nsplit == 1 && G.wp16 && !residual &&
+        L.ldi == L.kpad && L.ldo == L.cout && exit_supported(dtype, L.kpad, L.cout, L.H * L.H, n)) {
         // the pool as the epilogue (one workgroup owns an image's pixels) unless the convolution's own output was asked for
-        r.gap = (L.flags & F_POOLED) && !wants(tap, L.name) && !residual && L.H * L.H <= 128 && L.ldo == L.cout;
-        // one image's pixels x 256 channels per workgroup on 16x16x32 fragments when the weights are there in that order: block 14
-        if (G.wp16 && !residual && L.ldi == L.kpad && L.ldo == L.cout && exit_supported(dtype, L.kpad, L.cout, L.H * L.H, n))
-            return conv(R_DW_THEN_EXIT);
-        return conv(R_DW_THEN_TILED_GEMM);
+        r.gap = (L.flags & F_POOLED) && !wants(tap, L.name) && L.H * L.H <= 128;
+        return conv(R_DW_THEN_EXIT);
     }
     // strided shortcut convolutions with many channels (blocks 4 and 13: K = 256 / 736): a plain GEMM whose A rows are the even
     // pixels of the input map (block 13: 0.13 -> 0.085 ms against the fused-producer form; block 4: the same 0.09 ms)
     if (L.prod == PROD_S2 && is16(dtype) && L.kpad >= 256 && G.nfp % 4 == 0 && nsplit == 1 && !residual) return conv(R_S2_TILED_GEMM);
     if (nsplit == 1 && G.wp16 && same && wide_supported(dtype, L.prod, G.nfp, L.H, L.H, L.kpad, L.ldo, L.ldi, L.ldo, M, residual))
         return conv(R_WIDE);
-    if (nsplit == 1 && pipe_supported(dtype, L.prod, G.nfp, L.H, L.kpad)) return conv(R_PIPE);
     return conv(R_FUSED_GEMM);
 }
 
 std::string route_text(const Route& r) {
     std::string t = kRouteNames[r.kind];
     if (r.kind == R_CONV_THEN_POOL) t += std::string(" ") + kRouteNames[r.conv];
-    if (r.conv == R_TILE) t += " kind=" + std::to_string(r.tile_kind);
+    if (r.conv == R_TILE) t += " kind=0";
     if (r.conv == R_FUSED_GEMM) t += " nsplit=" + std::to_string(r.nsplit);
-    if (r.conv == R_DW_THEN_EXIT || r.conv == R_DW_THEN_TILED_GEMM) t += r.gap ? " GAP_EPILOGUE=yes" : " GAP_EPILOGUE=no";
+    if (r.conv == R_DW_THEN_EXIT) t += r.gap ? " GAP_EPILOGUE=yes" : " GAP_EPILOGUE=no";
     return t;
 }
 
@@ -460,7 +442,7 @@ int launch_conv(const Walk& w, int li, const Route& rt, const ConvBufs& b) {
     char cls[96];
     snprintf(cls, sizeof cls, "%s_k%d_n%d_%dx%d",
              L.prod == PROD_S2 ? "res1x1s2" : (L.prod == PROD_IM2COL ? "conv3x3" : "sepconv"), L.cin, L.cout, L.H, L.H);
-    const bool two = rt.conv == R_DW_THEN_EXIT || rt.conv == R_DW_THEN_TILED_GEMM;   // its two kernels have scopes of their own
+    const bool two = rt.conv == R_DW_THEN_EXIT;   // its two kernels have scopes of their own
     ProfScope ps(c, s, two ? std::string("split_") + cls : std::string(cls), two ? 0.0 : flops, two ? 0.0 : bytes);
     const char* what = "launch ";
     int e = 0;
@@ -472,10 +454,9 @@ int launch_conv(const Walk& w, int li, const Route& rt, const ConvBufs& b) {
         break;
     case R_TILE:
         what = "launch(tile) ";
-        e = launch_tile_conv(dtype, rt.tile_kind, b.in, G.wp, G.dw, G.scale, G.bias, b.out, n, L.H, L.H, L.Hi, L.Hi, L.relu, c->num_cus, s);
+        e = launch_tile_conv(dtype, b.in, G.wp, G.scale, G.bias, b.out, n, L.H, L.H, L.Hi, L.Hi, L.relu, c->num_cus, s);
         break;
-    case R_DW_THEN_EXIT:
-    case R_DW_THEN_TILED_GEMM: {
+    case R_DW_THEN_EXIT: {
         const bool gap = rt.gap;
         {
             ProfScope pd(c, s, std::string("dw3x3_") + cls, 18.0 * M * L.cin, 2.0 * es * M * L.cin);
@@ -485,29 +466,18 @@ int launch_conv(const Walk& w, int li, const Route& rt, const ConvBufs& b) {
         if (e) break;
         ProfScope pg(c, s, std::string(gap ? "gemm_gap_" : "gemm_") + cls, 2.0 * M * L.cin * L.cout + (gap ? M * L.cout : 0.0),
                      gap ? es * M * L.cin + 4.0 * n * L.cout : es * (M * L.cin + M * L.cout * (residual ? 2.0 : 1.0)));
-        if (rt.conv == R_DW_THEN_EXIT) {
-            what = "launch(exit_gemm) ";
-            e = launch_exit_gemm(dtype, dwtmp, G.wp16, G.scale, G.bias, b.out, gap ? b.gap_out : nullptr, n, L.H * L.H, L.kpad, L.cout,
-                                 L.relu, c->feat_mul, s);
-        } else {
-            p.in = dwtmp; p.gap_mul = c->feat_mul;
-            if (gap) p.out = b.gap_out;
-            what = "launch(gemm_tile) ";
-            e = launch_gemm_tile(dtype, p, false, s, gap ? 1 : 0);
-        }
+        what = "launch(exit_gemm) ";
+        e = launch_exit_gemm(dtype, dwtmp, G.wp16, G.scale, G.bias, b.out, gap ? b.gap_out : nullptr, n, L.H * L.H, L.kpad, L.cout, L.relu,
+                             c->feat_mul, s);
         break;
     }
     case R_S2_TILED_GEMM:
         what = "launch(gemm_tile s2) ";
-        e = launch_gemm_tile(dtype, p, true, s);
+        e = launch_gemm_tile(dtype, p, s, false);
         break;
     case R_WIDE:
         what = "launch(wide) ";
         e = launch_sepconv_wide(dtype, L.prod, p, G.wp16, c->num_cus, s);
-        break;
-    case R_PIPE:
-        what = "launch(pipe) ";
-        e = launch_sepconv_pipe(dtype, L.prod, p, s);
         break;
     case R_FUSED_GEMM:
         for (int sp = 0; sp < rt.nsplit && e == 0; ++sp) {
@@ -587,12 +557,8 @@ int launch_block_end(const Walk& w, int li, const Route& rt, const void* x, cons
     }
     ProfScope ps(c, s, std::string("respool_") + std::to_string(L.Hi) + "_c" + std::to_string(L.cout),
                  2.0 * Mo * L.cin * L.cout + 9.0 * Mo * co, es * ((double)n * L.Hi * L.Hi * co + Mo * co + Mo * ci) + es * (double)L.cin * L.cout);
-    if (rt.kind == R_POOL_GEMM) {
-        const int e = launch_gemm_tile(dtype, gemm_params(c, li, n, x, y, out), true, s, 2);
-        return e ? launch_failed(c, "launch(gemm_tile pool) ", L.name, e) : BQ_OK;
-    }
-    const int e = launch_respool(dtype, x, G.wp32, G.scale, G.bias, y, out, n, L.Hi, L.Hi, L.kpad, ci, co, G.nfp, s);
-    return e ? launch_failed(c, "launch(respool) ", L.name, e) : BQ_OK;
+    const int e = launch_gemm_tile(dtype, gemm_params(c, li, n, x, y, out), s, true);   // R_POOL_GEMM
+    return e ? launch_failed(c, "launch(gemm_tile pool) ", L.name, e) : BQ_OK;
 }
 
 // One block with a strided shortcut: rows s1 (first separable convolution), s1 + 1, s1 + 2 (shortcut).  x -> out; t1, t2: scratch.
@@ -741,12 +707,6 @@ int register_gemm_layer(bq_ctx* c, int li, int vec, int elt) {
         if (kpad % 32 || w16->second.n != (size_t)(kpad / 32) * ((size_t)L.nfp * 2) * 1024)
             return fail(c, BQ_ERR_WEIGHTS, "bad size for " + name + "/wp16");
         L.wp16 = w16->second.p;
-    }
-    auto w32 = c->entries.find(name + "/wp32");
-    if (w32 != c->entries.end()) {
-        if (w32->second.n != (size_t)(kpad / 16) * (size_t)L.nfp * 1024)
-            return fail(c, BQ_ERR_WEIGHTS, "bad size for " + name + "/wp32");
-        L.wp32 = w32->second.p;
     }
     L.scale = entry_f32(c, name + "/scale");
     L.bias = entry_f32(c, name + "/bias");

@@ -48,9 +48,7 @@ enum BqShape : int {       // MF, WM, WN, RN   (tile rows = 32*MF, waves = WM*WN
     SHAPE_F = 5,           // 2, 1, 8, 3
     SHAPE_G = 6,           // 1, 1, 8, 4
     SHAPE_H = 7,           // 1, 1, 4, 2   fp32 fallback
-    SHAPE_I = 8,           // 1, 1, 8, 2   (unused since the MC head got its own kernel)
-    SHAPE_J = 9,           // 2, 1, 4, 1   N = 128, 64-row tiles (1x1/s2 residual convs: more workgroups per CU)
-    SHAPE_K = 10           // 2, 1, 4, 2   N = 256, 64-row tiles
+    SHAPE_K = 8            // 2, 1, 4, 2   N = 256, 64-row tiles (1x1/s2 residual convs: more workgroups per CU)
 };
 
 struct GemmParams {
@@ -73,16 +71,13 @@ struct GemmParams {
     int H, W;              // output spatial size
     int Hi, Wi;            // input spatial size
     int relu;              // ReLU in the epilogue
-    int lds_total;         // dynamic LDS bytes of the launch (set by the pipe launcher)
-    float gap_mul;         // EPI_GAP of kernels_split.hip: factor on the means (0 = 1: undoes an activation exponent)
+    int unused[2];         // of the retired kernels; kept: without them the kernel-argument layout and the surviving kernels' code change
 };
 
 size_t gemm_lds_bytes(int dtype, int shape, int K);
 // Returns hipError_t as int.
 int launch_gemm(int dtype, int prod, int shape, const GemmParams& p, hipStream_t s);
 int gemm_tile_rows(int shape);
-bool pipe_supported(int dtype, int prod, int nfp, int W, int K);
-int launch_sepconv_pipe(int dtype, int prod, const GemmParams& p, hipStream_t s);
 bool wide_supported(int dtype, int prod, int nfp, int H, int W, int K, int Nstore, int ldi, int ldo, long long M, bool residual);
 int launch_sepconv_wide(int dtype, int prod, const GemmParams& p, const void* wp16, int num_cus, hipStream_t s);
 bool stream_supported(int dtype, int cin, int cout, bool relu_in, long long n, int H, int W);
@@ -94,15 +89,14 @@ int launch_block_tail(int dtype, int cin, int cout, int cx, const void* y1, cons
                       const float* scale, const float* bias, const void* x, const void* wr16, const float* rscale,
                       const float* rbias, void* out, int n, int H, int W, int num_cus, hipStream_t s);
 int launch_dw3x3(int dtype, const void* in, const float* dw, void* out, int n, int H, int W, int C, int relu, hipStream_t s);
-int launch_gemm_tile(int dtype, const GemmParams& p, bool s2, hipStream_t s, int epi = 0);   // epi: 1 = + global average pool, 2 = + max-pool + add
+int launch_gemm_tile(int dtype, const GemmParams& p, hipStream_t s, bool pool);   // the 1x1/s2 shortcuts; pool: + max-pool + add
 // kernels_exit.hip (round 4): block 14's pointwise GEMMs, one image's pixels x 256 channels per workgroup; gap != nullptr: the
 // per-image means instead of the tensor
 bool exit_supported(int dtype, int K, int N, int HW, long long n);
 int launch_exit_gemm(int dtype, const void* in, const void* wp16, const float* scale, const float* bias, void* out, float* gap,
                      int n, int HW, int K, int N, int relu, float gap_mul, hipStream_t s);
-int launch_tile_conv(int dtype, int kind, const void* in, const void* wp, const float* dw, const float* scale,
-                     const float* bias, void* out, int n, int H, int W, int Hi, int Wi, int relu, int num_cus,
-                     hipStream_t s);
+int launch_tile_conv(int dtype, const void* in, const void* wp, const float* scale, const float* bias, void* out, int n, int H,
+                     int W, int Hi, int Wi, int relu, int num_cus, hipStream_t s);
 
 // ---- small kernels (kernels_misc.hip) ----------------------------------------------
 int launch_stage_u8(const uint8_t* tiles, int n, int px, void* out, int dtype, double* stats_scratch,
@@ -147,8 +141,6 @@ int launch_stem1(const void* in_nchw, int n, const float* w27x32, const float* s
                  const float* bias, void* out_nhwc, int dtype, hipStream_t s);
 int launch_pool_add(const void* y, const void* res, void* out, int n, int Hi, int Wi, int C,
                     int dtype, hipStream_t s);
-int launch_respool(int dtype, const void* x, const void* wp32, const float* scale, const float* bias, const void* y, void* out,
-                   int n, int Hi, int Wi, int K, int ldx, int ld, int nf32, hipStream_t s);
 int launch_gap(const void* x, int n, int HW, int C, int ld, float* feat, float mul, int dtype, hipStream_t s);
 int launch_head_dense(const float* in, const void* wh, const void* wl, const float* bias, int wexp, float* out, float* rmax,
                       int rows, int K, int mc_n, int pass0, int in_row_is_tile, int layer, unsigned seed_lo, unsigned seed_hi,

@@ -1,4 +1,4 @@
-// Device helpers shared by the fused MFMA kernels (kernels_gemm.hip, kernels_pipe.hip).
+// Device helpers shared by the fused MFMA kernels (kernels_gemm.hip and the tile, split and wide kernels).
 #pragma once
 #include "bq_common.h"
 

@@ -1,8 +1,9 @@
 // Fused "producer -> LDS A tile -> MFMA" kernel: the workhorse of the Xception backbone
 // (SeparableConv2D = depthwise 3x3 + pointwise 1x1 + folded BN [+ residual] [+ ReLU],
 // residual 1x1/s2 convs, block1_conv2 as im2col).  (The MC-dropout Dense layers have their own kernel, kernels_head.hip.)
-// WHO STILL RUNS THIS FILE: choose_route's last resort (biscuit_hip.hip: FUSED_GEMM) -- every layer of the fp32 context; in a 16-bit
-// context block2_res / block3_res under a debug tap of theirs, and any layer no other route takes.
+// WHO RUNS THIS FILE: choose_route's one fallback (biscuit_hip.hip: FUSED_GEMM) -- every layer of the fp32 context; in a 16-bit
+// context block2_res / block3_res under a debug tap of theirs, and any layer whose fast route refuses: a blob without the layer's
+// "wp16" copy, or a batch beyond the route's 32-bit offsets.  It indexes with size_t.
 //
 // Design (gfx950 / CDNA4, wave64):
 //  * One workgroup owns MT = 32*MF output pixels and ALL output channels.  Phase 1
@@ -240,8 +241,8 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_fused_kernel(const GemmPara
 }
 
 struct ShapeDesc { int MF, WM, WN, RN; };
-constexpr ShapeDesc kShapes[11] = {{4, 2, 2, 1}, {4, 1, 4, 1}, {4, 1, 4, 2}, {3, 1, 8, 3}, {3, 1, 8, 2}, {2, 1, 8, 3},
-                                   {1, 1, 8, 4}, {1, 1, 4, 2}, {1, 1, 8, 2}, {2, 1, 4, 1}, {2, 1, 4, 2}};
+constexpr ShapeDesc kShapes[9] = {{4, 2, 2, 1}, {4, 1, 4, 1}, {4, 1, 4, 2}, {3, 1, 8, 3}, {3, 1, 8, 2}, {2, 1, 8, 3},
+                                  {1, 1, 8, 4}, {1, 1, 4, 2}, {2, 1, 4, 2}};
 
 template <typename T, int PROD, int SH>
 int launch_inst(const GemmParams& p, hipStream_t s) {

@@ -1,13 +1,8 @@
-// Two-kernel form of the 728-wide SeparableConv2D layers (bf16):
-//   dw3x3_kernel      depthwise 3x3 'same' (+ optional ReLU on the input), NHWC -> NHWC, HBM-bound
-//   gemm_tile_kernel  pointwise 1x1 as a tiled MFMA GEMM with folded BN / residual / ReLU epilogue
-//
-// Why not fused: keeping the whole 96 x 768 output tile of a workgroup in registers (the fused
-// kernels) leaves one fat workgroup per CU whose prologue, depthwise stage, weight stream and
-// epilogue all serialise against its MFMAs (measured 0.236 ms per layer at n = 256, 17 % of
-// the bf16 peak).  Splitting costs one extra round trip of the depthwise result through
-// HBM / Infinity Cache (272 MB per layer) but lets the GEMM run 128 x 128 tiles at 3
-// workgroups per CU, so one workgroup's loads and stores hide under another's MFMAs.
+// The two kernels that stand beside the fused ones (16-bit types):
+//   dw3x3_kernel      depthwise 3x3 'same' (+ optional ReLU on the input), NHWC -> NHWC, HBM-bound: the first half of block 14's
+//                     layers, whose GEMM is kernels_exit.hip (DW_THEN_EXIT)
+//   gemm_tile_kernel  the 1x1 / stride-2 shortcut convolutions as a tiled MFMA GEMM with folded BN, plain (S2_TILED_GEMM) or with
+//                     the block's max-pool + add as its store pass (POOL_GEMM)
 //
 // GEMM: out[M][N] = D[M][K] * W, D row-major with K innermost, W in the host-packed MFMA fragment
 // order.  Workgroup = 128 rows x 128 columns, 4 waves as 2 x 2 (64 x 64 each = 2 x 2
@@ -102,16 +97,12 @@ constexpr int ST_ROW = BN * 2 + 16;       // staging row of the output tile
 
 // S2: the rows of A are the even pixels of a larger map (1x1 / stride 2 / 'same' shortcut convolutions): row m = output
 // pixel (img, y, x) of an H x W map reads input pixel (img, 2y, 2x) of the Hi x Wi map.
-// EPI (round 4: the fusions BASELINE.json's north_star names, so that neither tensor goes through HBM on its own):
-//   EPI_GAP   the tile's rows are ONE image's H x W pixels (<= 128; the rest of the 128 MFMA rows is computed and dropped):
-//             folded BN + ReLU, rounded to the storage type -- the rounding point of the tensor GlobalAveragePooling2D
-//             used to read --, then the column means in the pixel order of the old pooling kernel (bit-identical to it),
-//             fp32 [n][ldo] to p.out.  No atomics: one workgroup owns an image's pixels.
+// EPI (round 4: a fusion BASELINE.json's north_star names, so that the shortcut tensor does not go through HBM on its own):
 //   EPI_POOL  (with S2) out = MaxPool3x3/s2 'same' (y) + BN(conv1x1/s2(x)): the shortcut tile, rounded, waits in LDS and
 //             the store pass becomes the pooling pass of kernels_misc.hip (thread = 8 channels of a pooled pixel, nine
 //             coalesced 16-byte loads of y = p.residual [n][Hi][Wi][ldo], fp32 max, + shortcut, rounded).  Three workgroups
 //             per CU: one's pooling pass runs under the others' MFMAs.
-enum { EPI_PLAIN = 0, EPI_GAP = 1, EPI_POOL = 2 };
+enum { EPI_PLAIN = 0, EPI_POOL = 2 };
 
 template <typename T, int PF, bool S2, int EPI = EPI_PLAIN>
 __global__ void __launch_bounds__(256) gemm_tile_kernel(const GemmParams p) {
@@ -123,8 +114,7 @@ __global__ void __launch_bounds__(256) gemm_tile_kernel(const GemmParams p) {
     const int ntn = p.NFp / 4;                       // 128-column tiles
     const int tile = xcd_tile(blockIdx.x, gridDim.x);
     const int mt = tile / ntn, nt = tile - mt * ntn;
-    const int rows_per_tile = EPI == EPI_GAP ? p.H * p.W : BM;
-    const int m0 = mt * rows_per_tile;
+    const int m0 = mt * BM;
     const int K = p.K, KB = K / 16, NC = (K + BK - 1) / BK;
     const T* __restrict__ A = reinterpret_cast<const T*>(p.in);
 
@@ -247,18 +237,7 @@ __global__ void __launch_bounds__(256) gemm_tile_kernel(const GemmParams p) {
             }
         }
     __syncthreads();
-    if constexpr (EPI == EPI_GAP) {
-        // column means over the image's pixels, in pixel order (the summation order of gap_kernel)
-        if (tid < BN) {
-            const int ncol = nt * BN + tid;
-            if (ncol < p.Nstore) {
-                float sum = 0.f;
-                for (int r = 0; r < rows_per_tile; ++r)
-                    sum += (float)*reinterpret_cast<const T*>(smem + (size_t)r * ST_ROW + tid * 2);
-                reinterpret_cast<float*>(p.out)[(size_t)mt * p.ldo + ncol] = sum / (float)rows_per_tile * (p.gap_mul != 0.f ? p.gap_mul : 1.f);
-            }
-        }
-    } else if constexpr (EPI == EPI_POOL) {
+    if constexpr (EPI == EPI_POOL) {
         const T* __restrict__ y = reinterpret_cast<const T*>(p.residual);
         T* __restrict__ out = reinterpret_cast<T*>(p.out);
         const int pc = tid & 15;
@@ -352,34 +331,18 @@ int launch_dw3x3(int dtype, const void* in, const float* dw, void* out, int n, i
                       : launch_dw3x3_t<bf16_t>(in, dw, out, n, H, W, C, relu, s);
 }
 
-// p.in = depthwise result [M][ldi] -- or, with s2, the map [n][Hi][Wi][ldi] whose even pixels are the rows;
-// p.NFp multiple of 4; 16-bit types only.  epi: 0 plain; 1 = global average pool (p.out = fp32 [M / (H W)][ldo], H W <= 128,
-// M a multiple of H W, no s2); 2 = max-pool + add (s2 only: p.residual = the map to pool, [n][Hi][Wi][ldo])
-int launch_gemm_tile(int dtype, const GemmParams& p, bool s2, hipStream_t s, int epi) {
-    if (p.NFp % 4 != 0 || p.K % 16 != 0) return (int)hipErrorInvalidValue;
+// The 1x1 / stride-2 shortcut convolutions: p.in = the map [n][Hi][Wi][ldi] whose even pixels are the rows; p.NFp multiple of 4; 16-bit
+// types only.  pool: + max-pool + add (p.residual = the map to pool, [n][Hi][Wi][ldo])
+int launch_gemm_tile(int dtype, const GemmParams& p, hipStream_t s, bool pool) {
+    if (p.NFp % 4 != 0 || p.K % 16 != 0 || (pool && !p.residual)) return (int)hipErrorInvalidValue;
     const size_t lds = 2 * A_BUF > BM * ST_ROW ? 2 * A_BUF : BM * ST_ROW;
-    if (epi == EPI_GAP) {
-        const int hw = p.H * p.W;
-        if (s2 || hw <= 0 || hw > BM || p.M % hw) return (int)hipErrorInvalidValue;
-        const int grid = (p.M / hw) * (p.NFp / 4);
-        if (dtype == 2) hipLaunchKernelGGL((gemm_tile_kernel<f16_t, 4, false, EPI_GAP>), dim3(grid), dim3(256), lds, s, p);
-        else hipLaunchKernelGGL((gemm_tile_kernel<bf16_t, 4, false, EPI_GAP>), dim3(grid), dim3(256), lds, s, p);
-        return (int)hipGetLastError();
-    }
-    if (epi == EPI_POOL) {
-        if (!s2 || !p.residual) return (int)hipErrorInvalidValue;
-        const int grid = ((p.M + BM - 1) / BM) * (p.NFp / 4);
+    const int grid = ((p.M + BM - 1) / BM) * (p.NFp / 4);
+    if (pool) {
         if (dtype == 2) hipLaunchKernelGGL((gemm_tile_kernel<f16_t, 4, true, EPI_POOL>), dim3(grid), dim3(256), lds, s, p);
         else hipLaunchKernelGGL((gemm_tile_kernel<bf16_t, 4, true, EPI_POOL>), dim3(grid), dim3(256), lds, s, p);
-        return (int)hipGetLastError();
-    }
-    const int grid = ((p.M + BM - 1) / BM) * (p.NFp / 4);
-    if (dtype == 2) {
-        if (s2) hipLaunchKernelGGL((gemm_tile_kernel<f16_t, 4, true>), dim3(grid), dim3(256), lds, s, p);
-        else hipLaunchKernelGGL((gemm_tile_kernel<f16_t, 4, false>), dim3(grid), dim3(256), lds, s, p);
     } else {
-        if (s2) hipLaunchKernelGGL((gemm_tile_kernel<bf16_t, 4, true>), dim3(grid), dim3(256), lds, s, p);
-        else hipLaunchKernelGGL((gemm_tile_kernel<bf16_t, 4, false>), dim3(grid), dim3(256), lds, s, p);
+        if (dtype == 2) hipLaunchKernelGGL((gemm_tile_kernel<f16_t, 4, true>), dim3(grid), dim3(256), lds, s, p);
+        else hipLaunchKernelGGL((gemm_tile_kernel<bf16_t, 4, true>), dim3(grid), dim3(256), lds, s, p);
     }
     return (int)hipGetLastError();
 }

@@ -1,5 +1,5 @@
 // SeparableConv2D from block 3 to block 13: the 25 layers 728 -> 728 on 19x19 maps (~75 % of the network's FLOPs),
-// block4_sepconv2 (728 -> 728, 37x37), block4_sepconv1 (256 -> 728, 37x37) and block 3's two layers (128 / 256 -> 256,
+// block4_sepconv2 (728 -> 728, 37x37), block4_sepconv1 (256 -> 728, 37x37) and block3_sepconv2 under its debug tap (256 -> 256,
 // 74x74: the narrow instance, see NPlan / BPRE); 16-bit storage (bf16 or f16).  The description is the 19x19 instance's; the
 // others differ in the constants Geo, KPlan and NPlan derive (rows per tile, chunks, fragments per wave).
 //
@@ -737,18 +737,17 @@ __global__ void __launch_bounds__(64 * WN) sepconv_wide_kernel(const WideParams 
 
 using G19 = Geo<19, 4>;     // blocks 5-12 and block13_sepconv1: 5 tiles of 4 (the last: 3) rows per image
 using G37 = Geo<37, 2>;     // block4_sepconv2: 19 tiles of 2 (the last: 1) rows per image
-using G74 = Geo<74, 2, 256, 256>;   // block3_sepconv1 / 2 (128 / 256 -> 256): 37 tiles of 2 rows = 148 pixels, 160 MFMA rows
+using G74 = Geo<74, 2, 256, 256>;   // block3_sepconv2 (256 -> 256): 37 tiles of 2 rows = 148 pixels, 160 MFMA rows
 
 // The kernel forms byte offsets into the activation tensors in 32 bits: n * H * W * 736 * 2 must stay below 2^32
-// (n < 8 085 images at 19x19, n < 2 132 at 37x37 -- a larger batch falls back to the pipelined kernel).
+// (n < 8 085 images at 19x19, n < 2 132 at 37x37 -- a larger batch runs on kernels_gemm.hip).
 // Instances: K = 736 (728 -> 728) on 19x19 and 37x37 maps, K = 256 (block4_sepconv1: 256 -> 728) on 37x37 maps, and
 // 256 -> 256 on 74x74 maps (block3_sepconv2: no ReLU in front, no residual input).
 bool wide_supported(int dtype, int prod, int nfp, int H, int W, int K, int Nstore, int ldi, int ldo, long long M, bool residual) {
     const bool wide = Nstore == 736 && nfp * 2 == NPlan<736>::NFT &&
                       ((K == 736 && (W == G19::IW || (W == G37::IW && !residual))) || (K == 256 && W == G37::IW && !residual));
-    // block 3: 256 -> 256 behind the ReLU of the layer before, 128 -> 256 with its own ReLU in front
-    const bool b3 = Nstore == 256 && nfp * 2 == NPlan<256>::NFT && W == G74::IW && !residual &&
-                    ((K == 256 && prod == PROD_DW) || (K == 128 && prod == PROD_DW_RELU));
+    // block3_sepconv2: 256 -> 256 behind the ReLU of the layer before
+    const bool b3 = Nstore == 256 && nfp * 2 == NPlan<256>::NFT && W == G74::IW && !residual && K == 256 && prod == PROD_DW;
     // block13_sepconv2 (728 -> 1 024): two launches of 512 columns each (160 accumulator registers per wave do not exist)
     const bool b13 = Nstore == 1024 && nfp * 2 == 2 * NPlan<512>::NFT && K == 736 && W == G19::IW && !residual && prod == PROD_DW;
     return dtype != 0 && (prod == PROD_DW || prod == PROD_DW_RELU) && H == W && (wide || b3 || b13) &&
@@ -773,7 +772,7 @@ int launch_sepconv_wide(int dtype, int prod, const GemmParams& g, const void* wp
     const bool relu_in = prod == PROD_DW_RELU;
 #define BQ_WIDE_SET(T, RES) sepconv_wide_kernel<T, false, RES, G19, 736>, sepconv_wide_kernel<T, true, RES, G19, 736>, \
                             sepconv_wide_kernel<T, false, RES, G37, 736>, sepconv_wide_kernel<T, true, RES, G37, 736>
-    void (*const kerns[26])(const WideParams) = {BQ_WIDE_SET(bf16_t, false), BQ_WIDE_SET(f16_t, false),
+    void (*const kerns[24])(const WideParams) = {BQ_WIDE_SET(bf16_t, false), BQ_WIDE_SET(f16_t, false),
                                                  BQ_WIDE_SET(bf16_t, true), BQ_WIDE_SET(f16_t, true),
                                                  sepconv_wide_kernel<bf16_t, false, false, G37, 256>,
                                                  sepconv_wide_kernel<bf16_t, true, false, G37, 256>,
@@ -781,21 +780,19 @@ int launch_sepconv_wide(int dtype, int prod, const GemmParams& g, const void* wp
                                                  sepconv_wide_kernel<f16_t, true, false, G37, 256>,
                                                  sepconv_wide_kernel<bf16_t, false, false, G74, 256, 256>,
                                                  sepconv_wide_kernel<f16_t, false, false, G74, 256, 256>,
-                                                 sepconv_wide_kernel<bf16_t, true, false, G74, 128, 256>,
-                                                 sepconv_wide_kernel<f16_t, true, false, G74, 128, 256>,
                                                  sepconv_wide_kernel<bf16_t, false, false, G19, 736, 512, 1024, 64>,
                                                  sepconv_wide_kernel<f16_t, false, false, G19, 736, 512, 1024, 64>};
 #undef BQ_WIDE_SET
     const bool b3 = g.W == G74::IW, b13 = g.Nstore == 1024;
-    const int ki = b13 ? 24 + (dtype == 2 ? 1 : 0)
-                 : b3 ? 20 + (g.K == 128 ? 2 : 0) + (dtype == 2 ? 1 : 0)
+    const int ki = b13 ? 22 + (dtype == 2 ? 1 : 0)
+                 : b3 ? 20 + (dtype == 2 ? 1 : 0)
                  : g.K == 256 ? 16 + (dtype == 2 ? 2 : 0) + (relu_in ? 1 : 0)
                               : (p.residual ? 8 : 0) + (dtype == 2 ? 4 : 0) + (big ? 2 : 0) + (relu_in ? 1 : 0);
     auto kern = kerns[ki];
     const int tpi = b3 ? G74::TPI : big ? G37::TPI : G19::TPI;
     const bool res = p.residual != nullptr;
     const int lds = b3 ? G74::lds_bytes(false) : big ? G37::lds_bytes(res) : G19::lds_bytes(res);   // (b13: G19 without a residual)
-    static BqLdsAttr attr[26];
+    static BqLdsAttr attr[24];
     if (const int e = attr[ki].ensure(reinterpret_cast<const void*>(kern), lds)) return e;
     // one persistent workgroup per CU (a multiple of 8: every workgroup stays inside its XCD's run of tiles)
     const int ntiles = p.n * tpi;

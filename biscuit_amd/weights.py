@@ -279,25 +279,12 @@ def pack_fragments16(wkn, kpad, npad):
     return np.ascontiguousarray(t).reshape(kpad // 32, npad // 16, 64, 8)
 
 
-def pack_fragments32(wkn, kpad, npad):
-    """W[K][N] -> v_mfma_f32_32x32x16 fragment order [KS][NF32][64][8] float32 (zero padded): k-step ks (16 deep), 32-wide
-    n-fragment nf, lane = h*32 + r holds W[k = ks*16 + h*8 + v][n = nf*32 + r] in element v.  All fragments of one
-    k-step are contiguous."""
-    k, n = wkn.shape
-    assert kpad % 16 == 0 and kpad >= k and npad % 32 == 0 and npad >= n
-    full = np.zeros((kpad, npad), np.float32)
-    full[:k, :n] = wkn
-    t = full.reshape(kpad // 16, 2, 8, npad // 32, 32)      # [ks][h][v][nf][r]
-    t = t.transpose(0, 3, 1, 4, 2)                          # [ks][nf][h][r][v]
-    return np.ascontiguousarray(t).reshape(kpad // 16, npad // 32, 64, 8)
-
-
 def wide_layers():
     """The separable convolutions of kernels_wide.hip (8 waves, 16x16x32 fragment order with interleaved n-fragment pairs):
     the 26 layers 728 -> 728 -- block4_sepconv2 (37x37 maps), blocks 5-12 and block13_sepconv1 (19x19 maps) --,
-    block4_sepconv1 (256 -> 728, 37x37), block3_sepconv1 / 2 (128 / 256 -> 256, 74x74) and block13_sepconv2 (728 -> 1024,
-    19x19, as two launches of 512 columns).  (block3_sepconv1 is listed for its ``wp16`` entry: the streaming kernel, which reads
-    the same order, is tried first and runs it -- DESIGN.md section 3; block3_sepconv2 runs there only when block 3's tail is off.)"""
+    block4_sepconv1 (256 -> 728, 37x37), block3_sepconv2 (256 -> 256, 74x74: only when block 3's tail is off) and
+    block13_sepconv2 (728 -> 1024, 19x19, as two launches of 512 columns).  (block3_sepconv1 is listed for its ``wp16`` entry
+    alone: the streaming kernel reads it -- DESIGN.md section 3.)"""
     return (['block3_sepconv1', 'block3_sepconv2', 'block4_sepconv1', 'block4_sepconv2'] +
             [f'block{b}_sepconv{i}' for b in range(5, 13) for i in (1, 2, 3)] + ['block13_sepconv1', 'block13_sepconv2'])
 
@@ -461,10 +448,6 @@ def pack_blob(w, dtype='bf16', act_exp=None):
     add_affine('block1_conv2', s, b, npad)
     for name, cin, cout in residual_plan():
         npad = add_mat(name, w[name + '_conv/kernel'].reshape(cin, cout), pad_channels(cin))
-        if half and npad % 128 == 0 and cin <= 128:   # kernels_respool.hip: shortcut conv + max-pool + add
-            # in one kernel (blocks 2 and 3; the wider shortcuts measured faster as two kernels)
-            add(name + '/wp32', to_bits(pack_fragments32(w[name + '_conv/kernel'].reshape(cin, cout),
-                                                                  pad_channels(cin), npad)))
         if half and name in TAIL_RES_LAYERS:          # kernels_stream.hip: the shortcut inside the fused block tail
             add(name + '/wp16', to_bits(pack_fragments16(w[name + '_conv/kernel'].reshape(cin, cout), pad_channels(cin), npad)))
         s, b = fold(name)

@@ -11,6 +11,7 @@ Tolerances (BASELINE.json north_star: tile- and slide-level mean/std within 1e-3
   * integer / index work (masks, counts, slide order) ........ bit-exact
 """
 import os
+import struct
 
 import numpy as np
 import pytest
@@ -58,6 +59,20 @@ def tiles():
     return t
 
 
+@pytest.fixture(scope='module')
+def layer_refs(oracles, tiles):
+    """``layer_refs(dtype)`` -> (taps, pooled features) of the first two tiles from the oracle of that type, computed once."""
+    from oracle.xception_ref import standardize
+    cache = {}
+
+    def get(dtype):
+        if dtype not in cache:
+            taps = {}
+            cache[dtype] = (taps, oracles[dtype].backbone(standardize(tiles[:2]), taps))
+        return cache[dtype]
+    return get
+
+
 def dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
@@ -85,7 +100,7 @@ ULP = {'bf16': 2.0 ** -8, 'f16': 2.0 ** -11}
 
 
 @pytest.mark.parametrize('dtype', ['f32', 'bf16', 'f16'])
-def test_every_layer_against_oracle(engines, oracles, tiles, dtype):
+def test_every_layer_against_oracle(engines, layer_refs, tiles, dtype):
     """Every tapped layer against the oracle that rounds at the same points.  16-bit types: identical rounding points,
     only the fp32 accumulation order differs, which flips an occasional last place, and the flips travel on and
     multiply with depth (measured, tools/layer_ulps.py: 0.01 % of the values differ after the stem, 40 % after block 4,
@@ -93,10 +108,8 @@ def test_every_layer_against_oracle(engines, oracles, tiles, dtype):
     magnitude plus a relative rms in ulps, both about twice what was measured on the default and the stress weights:
     a wrong tap, a swapped channel or a missed ReLU in ANY one layer is off by whole values -- tens to hundreds of ulps --
     where a rounding flip is one."""
-    from oracle.xception_ref import standardize
-    taps = {}
     t2 = tiles[:2]
-    feat_ref = oracles[dtype].backbone(standardize(t2), taps)
+    taps, feat_ref = layer_refs(dtype)
     eng = engines[dtype]
     staged = eng.stage(dev(t2))
     report = []
@@ -134,6 +147,74 @@ def layer_rms_ulps(k):
 
 
 FEAT_MAXABS_ULPS = 1.0      # pooled features average 100 pixels: measured 0.3-0.4
+
+
+def _without_16x16_copies(blob):
+    """The BQW1 blob re-serialised without its "<layer>/wp16" and "block1_conv1/w16" entries, as bq_load_weights reads it: a
+    16-byte header, 64-byte directory entries ``name[48], off, len``, payloads at 256-aligned offsets."""
+    magic, ver, n, dt = struct.unpack_from('<4sIII', blob, 0)
+    entries = [struct.unpack_from('<48sQQ', blob, 16 + 64 * i) for i in range(n)]
+    keep = [(nm, blob[off:off + ln]) for nm, off, ln in entries if not nm.rstrip(b'\0').endswith((b'/wp16', b'/w16'))]
+    assert 0 < len(keep) < n
+    off = (16 + 64 * len(keep) + 255) // 256 * 256
+    directory, payload = [], []
+    for nm, raw in keep:
+        directory.append(struct.pack('<48sQQ', nm, off, len(raw)))
+        pad = (-len(raw)) % 256
+        payload.append(raw + b'\0' * pad)
+        off += len(raw) + pad
+    head = struct.pack('<4sIII', magic, ver, len(keep), dt) + b''.join(directory)
+    return head + b'\0' * ((-len(head)) % 256) + b''.join(payload)
+
+
+_FUSED = 'FUSED_GEMM nsplit=1'
+# what a 16-bit context schedules from staged tiles when no fast route finds its weights
+FALLBACK_SCHEDULE = ([('block1_conv2', 'TILE kind=0'),
+                      ('block2_sepconv1', _FUSED), ('block2_sepconv2', _FUSED), ('block2_out', 'CONV_THEN_POOL ' + _FUSED),
+                      ('block3_sepconv1', _FUSED), ('block3_sepconv2', _FUSED), ('block3_out', 'POOL_GEMM'),
+                      ('block4_sepconv1', _FUSED), ('block4_sepconv2', _FUSED), ('block4_out', 'POOL_GEMM')] +
+                     [(f'block{b}_sepconv{i}', _FUSED) for b in range(5, 13) for i in (1, 2, 3)] +
+                     [('block13_sepconv1', _FUSED), ('block13_sepconv2', _FUSED), ('block13_out', 'POOL_GEMM'),
+                      ('block14_sepconv1', _FUSED), ('block14_sepconv2', _FUSED), ('global_avg_pool', 'GAP_KERNEL')])
+
+
+@pytest.mark.parametrize('dtype', ['f16', 'bf16'])
+def test_last_resort_runs_in_16_bits(weights, layer_refs, tiles, dtype, monkeypatch):
+    """A blob without any "wp16" / "w16" copy leaves a 16-bit context nothing but the kernels that read "<layer>/wp": every
+    separable convolution and block 2's shortcut on kernels_gemm.hip (FUSED_GEMM), the shortcuts of blocks 3, 4 and 13 on the
+    tiled GEMM with the pooling store pass (POOL_GEMM reads "wp" and depends on no copy, so it stays), the pool as its own
+    kernel.  Two images: the smallest batch at which the gather producers' image boundaries matter.  The bounds are those of
+    ``test_every_layer_against_oracle``: same rounding points, another accumulation order."""
+    import biscuit_amd.engine as engine_mod
+    real = engine_mod.pack_blob
+    monkeypatch.setattr(engine_mod, 'pack_blob', lambda *a, **k: _without_16x16_copies(real(*a, **k)))
+    eng = engine_mod.Engine(weights, dtype=dtype, max_batch=2, max_mc=1)
+    try:
+        sched = eng.schedule(2, u8=False)
+        assert sched == FALLBACK_SCHEDULE
+        other = [(name, route) for name, route in sched
+                 if route not in ('TILE kind=0', 'GAP_KERNEL') and not route.startswith(('FUSED_GEMM nsplit=', 'CONV_THEN_POOL FUSED_GEMM '))]
+        assert other == [(f'block{b}_out', 'POOL_GEMM') for b in (3, 4, 13)]
+        taps, feat_ref = layer_refs(dtype)
+        staged = eng.stage(dev(tiles[:2]))
+        shapes = dict(TAPS)
+        for name in ('block2_sepconv1', 'block2_out', 'block3_out', 'block4_out', 'block5_out', 'block13_out', 'block14_sepconv2'):
+            k = [t for t, _ in TAPS].index(name)
+            got = eng.debug_activation(name, staged, shapes[name]).cpu().numpy()
+            ref = taps[name].permute(0, 2, 3, 1).numpy()
+            d = np.abs(got - ref)
+            ulp = ULP[dtype] * np.abs(ref).max()
+            rms = np.sqrt((d ** 2).mean()) / np.sqrt((ref ** 2).mean())
+            print(f'{dtype} fallback {name}: max|d| {d.max() / ulp:.2f} ulps, rel. rms {rms / ULP[dtype]:.3f} ulps')
+            assert not np.isnan(got).any(), name
+            assert d.max() < layer_maxabs_ulps(k) * ulp, (name, d.max() / ulp, layer_maxabs_ulps(k))
+            assert rms < layer_rms_ulps(k) * ULP[dtype], (name, rms / ULP[dtype], layer_rms_ulps(k))
+        fr = feat_ref.numpy()
+        feat = eng.backbone(staged).cpu().numpy()
+        print(f'{dtype} fallback features: max|d| {np.abs(feat - fr).max() / (ULP[dtype] * np.abs(fr).max()):.2f} ulps')
+        assert np.abs(feat - fr).max() < FEAT_MAXABS_ULPS * ULP[dtype] * np.abs(fr).max()
+    finally:
+        eng.close()
 
 
 def test_mc_head_against_oracle(engines, oracles):

@@ -16,8 +16,11 @@ and launch (batch 256, ``synthetic_weights(1, hard=True)``), kernel names and ca
 * f32: 40 gemm_fused_kernel launches for the 39 layers (block14_sepconv2, K = 1536, is split in two), four pool_add_kernel, one
   gap_kernel.
 
-A route that needs a batch beyond the 32-bit offset limits (n > 776 at 147 x 147 x 128 in 16 bits) was not observed and is not
-asserted.
+A route that needs a batch beyond the 32-bit offset limits (n > 776 at 147 x 147 x 128 in 16 bits) was not observed on a device.
+Its DECISION is asserted (``test_16_bit_schedule_beyond_the_32_bit_limits``): the lists are those of the commit that still had the
+TILE kinds 1-3, RESPOOL and PIPE routes for n = 777 and n = 1532, read off its ``choose_route`` and the limits of
+``stream_supported`` / ``tail_supported`` / ``wide_supported`` (profiles/fallback_removal.txt), with each row that named one of
+those routes replaced by FUSED_GEMM -- and block 2's RESPOOL end by CONV_THEN_POOL FUSED_GEMM; every other row as it was.
 """
 import pytest
 import torch
@@ -28,6 +31,7 @@ from biscuit_amd.weights import synthetic_weights
 pytestmark = pytest.mark.gpu
 
 N = 256
+FUSED = 'FUSED_GEMM nsplit=1'
 MIDDLE = [(f'block{b}_sepconv{i}', 'WIDE') for b in range(5, 13) for i in (1, 2, 3)]
 SCHEDULE_16 = ([('block1_conv2', 'FRONT'),
                 ('block2_sepconv1', 'STREAM'), ('block2_out', 'BLOCK_TAIL'),
@@ -35,7 +39,6 @@ SCHEDULE_16 = ([('block1_conv2', 'FRONT'),
                 ('block4_sepconv1', 'WIDE'), ('block4_sepconv2', 'WIDE'), ('block4_out', 'POOL_GEMM')] + MIDDLE +
                [('block13_sepconv1', 'WIDE'), ('block13_sepconv2', 'WIDE'), ('block13_out', 'POOL_GEMM'),
                 ('block14_sepconv1', 'DW_THEN_EXIT GAP_EPILOGUE=no'), ('block14_sepconv2', 'DW_THEN_EXIT GAP_EPILOGUE=yes')])
-FUSED = 'FUSED_GEMM nsplit=1'
 SCHEDULE_32 = ([('block1_conv2', FUSED)] +
                [e for b in (2, 3, 4) for e in ((f'block{b}_sepconv1', FUSED), (f'block{b}_sepconv2', FUSED),
                                                (f'block{b}_out', 'CONV_THEN_POOL ' + FUSED))] +
@@ -58,6 +61,24 @@ def eng16(request, weights):
 
 def test_16_bit_schedule_from_uint8_tiles(eng16):
     assert eng16.schedule(N) == SCHEDULE_16
+
+
+# n = 777: block 2's tensors (147 x 147 x 128) pass the 32-bit offsets of the streaming kernel and of the fused tail
+SCHEDULE_16_N777 = ([('block1_conv2', 'FRONT'),
+                     ('block2_sepconv1', FUSED), ('block2_sepconv2', FUSED), ('block2_out', 'CONV_THEN_POOL ' + FUSED),
+                     ('block3_sepconv1', 'STREAM'), ('block3_out', 'BLOCK_TAIL')] + SCHEDULE_16[5:])
+# n = 1532: block 3's (74 x 74 x 256) too; its end falls to the shortcut GEMM with the pooling store pass
+SCHEDULE_16_N1532 = (SCHEDULE_16_N777[:4] +
+                     [('block3_sepconv1', FUSED), ('block3_sepconv2', FUSED), ('block3_out', 'POOL_GEMM')] + SCHEDULE_16[5:])
+
+
+def test_16_bit_schedule_beyond_the_32_bit_limits(weights):
+    eng = Engine(weights, dtype='f16', max_batch=1532)      # (the workspace grows on demand; a schedule allocates nothing)
+    try:
+        assert eng.schedule(777) == SCHEDULE_16_N777
+        assert eng.schedule(1532) == SCHEDULE_16_N1532
+    finally:
+        eng.close()
 
 
 def test_16_bit_float_entry_differs_in_block1_conv2_only(eng16):
