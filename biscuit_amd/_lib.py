@@ -43,6 +43,8 @@ ABI = {
     'bq_png_unfilter_strided': (_i, [_vp, _vp, _sz, _i, _i, _vp, _vp]),
     'bq_jpeg_scratch_bytes': (_sz, [_i, _i]),
     'bq_jpeg_decode': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'bq_jpeg_canvas_scratch_bytes': (_sz, [_i, _i, _i]),
+    'bq_jpeg_decode_canvas': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'bq_tile_resample': (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     'bq_tile_grayspace': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'bq_stream_create_masked': (_i, [_vp, C.POINTER(C.c_uint32), _i, C.POINTER(_vp)]),

@@ -1035,6 +1035,28 @@ int bq_jpeg_decode(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, const v
     return BQ_OK;
 }
 
+size_t bq_jpeg_canvas_scratch_bytes(int n, int seg_w, int seg_h) { return jpeg_canvas_scratch_bytes(n, seg_w, seg_h); }
+
+int bq_jpeg_decode_canvas(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int seg_w,
+                          int seg_h, const int32_t* d_place, uint8_t* d_canvas, int H, int W, int clip_x0, int clip_y0, int clip_x1,
+                          int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || seg_w <= 0 || seg_w > 4096 || seg_h <= 0 || seg_h > 4096 || n_tables < 0 || H <= 0 || W <= 0 || H > (1 << 28) ||
+        W > (1 << 28))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_decode_canvas: bad argument (need 0 < seg_w, seg_h <= 4096 and 0 < H, W <= 2^28)");
+    if (n == 0) return BQ_OK;
+    if (!d_scan || !d_desc || !d_tables || n_tables == 0 || !d_place || !d_canvas || !d_status || !d_scratch || ((uintptr_t)d_tables & 3) ||
+        ((uintptr_t)d_scan & 15) || ((uintptr_t)d_desc & 3) || ((uintptr_t)d_place & 3))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_decode_canvas: bad argument");
+    if (scratch_bytes < jpeg_canvas_scratch_bytes(1, seg_w, seg_h))
+        return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_decode_canvas: scratch smaller than one segment's (bq_jpeg_canvas_scratch_bytes(1, seg_w, seg_h))");
+    const int32_t clip[4] = {clip_x0, clip_y0, clip_x1, clip_y1};
+    ProfScope ps(c, (hipStream_t)stream, "jpeg_decode_canvas", 0.0, (double)n * seg_w * seg_h * 3.0);
+    const int e = launch_jpeg_decode_canvas(d_scan, d_desc, d_tables, n_tables, n, seg_w, seg_h, d_place, d_canvas, H, W, clip, d_status,
+                                            d_scratch, scratch_bytes, (hipStream_t)stream);
+    if (e) return fail(c, BQ_ERR_HIP, std::string("jpeg canvas decode launch: ") + hipGetErrorString((hipError_t)e));
+    return BQ_OK;
+}
+
 int bq_tile_resample(bq_ctx* c, const uint8_t* d_canvas, int H, int W, const int32_t* d_origin, int n, int src_px, int px,
                      const int32_t* d_bounds, const int32_t* d_coef, int ksize, uint8_t* d_out, bq_stream_t stream) {
     if (!c || n < 0 || n > (1 << 20) || px <= 0 || px > 4096 || src_px <= 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28) ||

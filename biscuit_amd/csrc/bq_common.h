@@ -129,6 +129,11 @@ int launch_inflate(const unsigned char* d_z, const unsigned* d_off, const unsign
 size_t jpeg_scratch_bytes(int n, int px);
 int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px, uint8_t* d_out,
                        int* d_status, void* d_scratch, size_t scratch_bytes, hipStream_t s);
+// the same for a TIFF page's own w x h segments, written into their places in a canvas uint8 [H][W][3] (clip: host memory)
+size_t jpeg_canvas_scratch_bytes(int n, int w, int h);
+int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int w, int h,
+                              const int32_t* d_place, uint8_t* d_canvas, int H, int W, const int32_t* clip, int* d_status, void* d_scratch,
+                              size_t scratch_bytes, hipStream_t s);
 // kernels_resample.hip: the heatmap's tile grid cut from a canvas and resampled as Pillow's LANCZOS does (resample_device.h),
 // and the background filter's grey-pixel count
 int resample_ksize(int src_px, int px);

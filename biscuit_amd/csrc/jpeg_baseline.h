@@ -479,9 +479,10 @@ struct Header {
     size_t scan = 0;                     // first byte of the entropy-coded segment
 };
 
-// data[0..n): a whole JPEG file.  Everything the markers can refuse (progressive / arithmetic / lossless frames, sampling factors,
-// colour spaces, size) is refused here; the tables and the components' geometry are left in S.
-inline int parse_header(const uint8_t* data, size_t n, int px, Scratch& S, Header& Hd) {
+// data[0..n): a whole JPEG file whose frame must be w x h (a tile record: w = h = tile_px; a TIFF segment: the page's tile size).
+// Everything the markers can refuse (progressive / arithmetic / lossless frames, sampling factors, colour spaces, size) is
+// refused here; the tables and the components' geometry are left in S.
+inline int parse_header(const uint8_t* data, size_t n, int w, int h, Scratch& S, Header& Hd) {
     if (n < 4 || data[0] != 0xFF || data[1] != 0xD8) return UNSUPPORTED;
     for (int i = 0; i < 4; ++i) { S.dc[i].defined = S.ac[i].defined = false; S.qdef[i] = false; }
     size_t p = 2;
@@ -564,7 +565,7 @@ inline int parse_header(const uint8_t* data, size_t n, int px, Scratch& S, Heade
         }
         p += len;
     }
-    if (W != px || H != px) return WRONG_SIZE;
+    if (W != w || H != h) return WRONG_SIZE;
     // colour space: what libjpeg would assume for these markers
     if (ncomp == 3) {
         if (!jfif && adobe && adobe_transform != 1) return UNSUPPORTED;
@@ -591,6 +592,8 @@ inline int parse_header(const uint8_t* data, size_t n, int px, Scratch& S, Heade
     Hd.hmax = hmax; Hd.vmax = vmax; Hd.mcux = mcux; Hd.mcuy = mcuy; Hd.scan = scan;
     return OK;
 }
+
+inline int parse_header(const uint8_t* data, size_t n, int px, Scratch& S, Header& Hd) { return parse_header(data, n, px, px, S, Hd); }
 
 // The entropy-coded segment behind a header parse_header accepted: the stuffed zeros dropped, split at the restart markers
 // (S.ecs, S.seg; ECS_PAD zero bytes behind the last interval).  Refuses what the scan's structure can refuse: no end marker,

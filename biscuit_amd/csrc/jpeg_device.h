@@ -12,6 +12,16 @@
 // The entropy decoder is total: on any byte string it terminates after a number of steps the tile size fixes (every MCU of
 // the tile, at most 64 symbols a block, at most 7 steps for a long code), reads only [scan, scan + len + ECS_PAD), writes
 // only inside the tile's coefficient blocks, and answers with a status instead of guessing.
+//
+// A tile need not be square: a TIFF page's JPEG segments are w x h (bqio_extract_jpeg_segments, bq_jpeg_decode_canvas), and the
+// argument holds for them as stated, with the numbers geom_of(g, w, h) fixes.  Steps: mcux * mcuy MCUs with mcux = ceil(w / 8 hmax)
+// and mcuy = ceil(h / 8 vmax), hmax * vmax + 2 blocks each.  Writes: a luma block's index is below bw[0] * bh[0] = (mcux hmax)
+// (mcuy vmax) and a chroma block's below base[c] + mcux * mcuy; with hmax, vmax <= 2 every plane has at most 2 ceil(w / 16) x
+// 2 ceil(h / 16) blocks (ceil(w / 8) <= 2 ceil(w / 16)), so the three planes end inside tile_blocks(w, h) whatever the
+// sampling.  Reads do not depend on the geometry.  The pixel stage reads samples (y, x) with y < h <= 8 bh[c] and x < w <=
+// 8 bw[c] only (chroma: y < ch, x < cw), which lie in the same planes.
+//
+// place_window below states, once for the host and the device, which pixels of a segment a canvas shows.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -72,30 +82,32 @@ struct Geom {
     int hmax, vmax, mcux, mcuy;
     int bw[3], bh[3];                    // blocks per plane row / column (whole MCUs)
     uint32_t base[3];                    // first block of the plane inside the tile's coefficient space
-    int cw, ch;                          // chroma samples that exist: ceil(px / hmax), ceil(px / vmax)
+    int cw, ch;                          // chroma samples that exist: ceil(w / hmax), ceil(h / vmax)
 };
 
-// Blocks of coefficient space per tile, whatever its sampling (4:2:0 rounds the luma plane up to whole 16 x 16 MCUs).
-BQJ_HD uint32_t tile_blocks(int px) {
-    const uint32_t w2 = 2u * (uint32_t)((px + 15) / 16);
-    return 3u * w2 * w2;
+// Blocks of coefficient space per w x h tile, whatever its sampling (4:2:0 rounds the luma plane up to whole 16 x 16 MCUs).
+BQJ_HD uint32_t tile_blocks(int w, int h) {
+    return 3u * (2u * (uint32_t)((w + 15) / 16)) * (2u * (uint32_t)((h + 15) / 16));
 }
-BQJ_HD size_t tile_coef_bytes(int px) { return (size_t)tile_blocks(px) * 128; }
+BQJ_HD uint32_t tile_blocks(int px) { return tile_blocks(px, px); }
+BQJ_HD size_t tile_coef_bytes(int w, int h) { return (size_t)tile_blocks(w, h) * 128; }
+BQJ_HD size_t tile_coef_bytes(int px) { return tile_coef_bytes(px, px); }
 
 // false: not 3 components at 4:4:4 / 4:2:2 / 4:2:0
-BQJ_HD bool geom_of(uint32_t g, int px, Geom& G) {
+BQJ_HD bool geom_of(uint32_t g, int w, int h, Geom& G) {
     const int hmax = (int)(g & 255), vmax = (int)((g >> 8) & 255), ncomp = (int)((g >> 16) & 255);
-    if (ncomp != 3 || hmax < 1 || hmax > 2 || vmax < 1 || vmax > 2 || (hmax == 1 && vmax == 2) || px <= 0) return false;
+    if (ncomp != 3 || hmax < 1 || hmax > 2 || vmax < 1 || vmax > 2 || (hmax == 1 && vmax == 2) || w <= 0 || h <= 0) return false;
     G.hmax = hmax; G.vmax = vmax;
-    G.mcux = (px + 8 * hmax - 1) / (8 * hmax); G.mcuy = (px + 8 * vmax - 1) / (8 * vmax);
+    G.mcux = (w + 8 * hmax - 1) / (8 * hmax); G.mcuy = (h + 8 * vmax - 1) / (8 * vmax);
     G.bw[0] = G.mcux * hmax; G.bh[0] = G.mcuy * vmax;
     G.bw[1] = G.bw[2] = G.mcux; G.bh[1] = G.bh[2] = G.mcuy;
     G.base[0] = 0;
     G.base[1] = (uint32_t)(G.bw[0] * G.bh[0]);
     G.base[2] = G.base[1] + (uint32_t)(G.mcux * G.mcuy);
-    G.cw = (px + hmax - 1) / hmax; G.ch = (px + vmax - 1) / vmax;
+    G.cw = (w + hmax - 1) / hmax; G.ch = (h + vmax - 1) / vmax;
     return true;
 }
+BQJ_HD bool geom_of(uint32_t g, int px, Geom& G) { return geom_of(g, px, px, G); }
 
 // ---- entropy decoder ----------------------------------------------------------------------------------------------------
 struct BitsD {
@@ -323,6 +335,32 @@ BQJ_HD void pixel_rgb(const uint8_t* tile, const Geom& G, int y, int x, uint8_t*
     rgb[0] = clamp8(Y + ((91881 * cr + 32768) >> 16));
     rgb[1] = clamp8(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
     rgb[2] = clamp8(Y + ((116130 * cb + 32768) >> 16));
+}
+
+// ---- a segment's place in a canvas --------------------------------------------------------------------------------------
+// A canvas is uint8 [H][W][3]; a seg_w x seg_h segment lies with its top-left pixel at canvas position (px, py), which may be
+// negative or beyond the canvas; clip = {x0, y0, x1, y1} is a rectangle in canvas coordinates (the level's image extent: what a
+// border segment holds beyond it is padding and is never shown).  The window [x0, x1) x [y0, y1) of the SEGMENT's own pixels
+// that lie inside both the canvas and the rectangle: exactly those are written, pixel (y, x) to canvas pixel (py + y, px + x).
+// false: none.  64-bit sums, so that no place or rectangle overflows.
+struct Window { int x0, y0, x1, y1; };
+BQJ_HD bool place_window(int px, int py, int seg_w, int seg_h, int H, int W, const int32_t* clip, Window& w) {
+    auto lo = [](int64_t a, int64_t b) { return a > b ? a : b; };
+    auto hi = [](int64_t a, int64_t b) { return a < b ? a : b; };
+    const int64_t cx0 = lo(clip[0], 0), cy0 = lo(clip[1], 0), cx1 = hi(clip[2], W), cy1 = hi(clip[3], H);
+    const int64_t x0 = lo(cx0 - px, 0), y0 = lo(cy0 - py, 0), x1 = hi(cx1 - px, seg_w), y1 = hi(cy1 - py, seg_h);
+    if (x1 <= x0 || y1 <= y0) return false;
+    w.x0 = (int)x0; w.y0 = (int)y0; w.x1 = (int)x1; w.y1 = (int)y1;
+    return true;
+}
+
+// The window of one decoded segment (planes: its blocks after idct_in_place) written into the canvas, pixel by pixel: the host's
+// form of the colour-and-place stage (the kernel of kernels_jpeg.hip writes the same pixels four at a time).
+BQJ_HD void place_segment(const uint8_t* planes, const Geom& G, const Window& w, int px, int py, uint8_t* canvas, int W) {
+    for (int y = w.y0; y < w.y1; ++y) {
+        uint8_t* row = canvas + ((size_t)(py + y) * (size_t)W + (size_t)(px + w.x0)) * 3;
+        for (int x = w.x0; x < w.x1; ++x) pixel_rgb(planes, G, y, x, row + 3 * (size_t)(x - w.x0));
+    }
 }
 
 }  // namespace bqjd

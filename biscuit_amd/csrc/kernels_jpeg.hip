@@ -14,6 +14,13 @@
 // Integer arithmetic throughout; the result is held to Pillow's bytes (tests/test_gpu_jpeg.py), not to a tolerance.
 // A tile costs tile_coef_bytes(px) of scratch (554 KB at 299 px, sized for 4:4:4), so a call works in rounds of as many
 // tiles as the caller's scratch holds (jpeg_round_tiles).
+//
+// bq_jpeg_decode_canvas: a TIFF page's own w x h segments (bqio_extract_jpeg_segments) through the same entropy and idct kernels
+// -- they need the (w, h) geometry and nothing else -- and, in place of `colour`,
+//   place    four pixels of the CANVAS per thread: the window of each segment that the canvas and the clip rectangle show
+//            (place_window of jpeg_device.h, the host's statement too), row by row, in groups of four flat canvas pixels -- 12
+//            bytes at a multiple of 12, so three aligned dword stores wherever the whole group belongs to the row, byte stores
+//            at a row's ragged ends (the pitch 3 W is no multiple of 4 in general).  Nothing outside a window is written.
 #include "bq_common.h"
 #include "jpeg_device.h"
 
@@ -29,7 +36,7 @@ struct JpegParams {
     const bqjd::TableSet* tables;
     int n_tables;
     int n;                               // tiles of this round
-    int px;
+    int w, h;                            // a tile's frame (bq_jpeg_decode: w = h = px)
     int16_t* coef;                       // [n][tile_i16]
     size_t tile_i16;
     int* status;                         // of the round's first tile
@@ -52,7 +59,7 @@ __global__ void __launch_bounds__(JE_NT) jpeg_entropy_kernel(const JpegParams p)
     if (i >= p.n) return;
     const bqjd::Desc d = p.desc[i];
     bqjd::Geom G;
-    if (!bqjd::geom_of(d.geom, p.px, G) || d.tset >= (uint32_t)p.n_tables) { p.status[i] = bqjd::ST_DESC; return; }
+    if (!bqjd::geom_of(d.geom, p.w, p.h, G) || d.tset >= (uint32_t)p.n_tables) { p.status[i] = bqjd::ST_DESC; return; }
     const bqjd::TableSet* T = d.tset == primary ? &sT : p.tables + d.tset;
     p.status[i] = bqjd::entropy_tile(p.scan + d.off, d.len, G, T, p.coef + (size_t)i * p.tile_i16);
 }
@@ -60,7 +67,7 @@ __global__ void __launch_bounds__(JE_NT) jpeg_entropy_kernel(const JpegParams p)
 __global__ void __launch_bounds__(JP_NT) jpeg_idct_kernel(const JpegParams p) {
     const int i = blockIdx.y;
     bqjd::Geom G;
-    if (!bqjd::geom_of(p.desc[i].geom, p.px, G)) return;
+    if (!bqjd::geom_of(p.desc[i].geom, p.w, p.h, G)) return;
     const uint32_t nblk = G.base[2] + (uint32_t)(G.mcux * G.mcuy);
     const uint32_t b = blockIdx.x * JP_NT + threadIdx.x;
     if (b >= nblk) return;
@@ -71,7 +78,7 @@ __global__ void __launch_bounds__(JP_NT) jpeg_colour_kernel(const JpegParams p) 
     const long long q = p.p0 / 4 + (long long)blockIdx.x * JP_NT + threadIdx.x;     // group of four pixels of the call's output
     const long long a = q * 4;
     if (a >= p.p1) return;
-    const int px = p.px;
+    const int px = p.w;
     const long long ppt = (long long)px * px;
     long long tile = a / ppt;
     const int rem = (int)(a - tile * ppt);
@@ -113,6 +120,57 @@ __global__ void __launch_bounds__(JP_NT) jpeg_colour_kernel(const JpegParams p) 
     }
 }
 
+struct PlaceParams {
+    const int32_t* place;                // [n][2] of the round's first segment
+    uint8_t* canvas;
+    int H, W;
+    int32_t clip[4];
+    int groups;                          // groups of four canvas pixels a segment row can touch: ceil(w / 4) + 1
+};
+
+// blockIdx.y = the segment, the x dimension = (row of the segment, group of four flat canvas pixels within the row's run).
+__global__ void __launch_bounds__(JP_NT) jpeg_place_kernel(const JpegParams p, const PlaceParams c) {
+    const int i = blockIdx.y;
+    const unsigned t = blockIdx.x * JP_NT + threadIdx.x;
+    const int r = (int)(t / (unsigned)c.groups), g = (int)(t % (unsigned)c.groups);
+    if (r >= p.h) return;
+    bqjd::Geom G;
+    if (!bqjd::geom_of(p.desc[i].geom, p.w, p.h, G)) return;
+    const int sx = c.place[2 * i], sy = c.place[2 * i + 1];
+    bqjd::Window w;
+    if (!bqjd::place_window(sx, sy, p.w, p.h, c.H, c.W, c.clip, w)) return;
+    const int y = w.y0 + r;
+    if (y >= w.y1) return;
+    // the row's run of flat canvas pixels [P0, P1): inside the canvas by place_window
+    const long long P0 = (long long)(sy + y) * c.W + (sx + w.x0), P1 = P0 + (w.x1 - w.x0);
+    const long long q = P0 / 4 + g, a = q * 4;
+    if (a >= P1) return;
+    const uint8_t* planes = reinterpret_cast<const uint8_t*>(p.coef + (size_t)i * p.tile_i16);
+    uint8_t b[12];
+    bool all = true;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long P = a + j;
+        const bool valid = P >= P0 && P < P1;
+        all &= valid;
+        b[3 * j] = b[3 * j + 1] = b[3 * j + 2] = 0;
+        if (valid) bqjd::pixel_rgb(planes, G, y, w.x0 + (int)(P - P0), b + 3 * j);
+    }
+    uint8_t* o = c.canvas + 12 * q;
+    if (all && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+        uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            o4[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) | ((uint32_t)b[4 * k + 3] << 24);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long P = a + j;
+            if (P >= P0 && P < P1) { o[3 * j] = b[3 * j]; o[3 * j + 1] = b[3 * j + 1]; o[3 * j + 2] = b[3 * j + 2]; }
+        }
+    }
+}
+
 }  // namespace
 
 size_t jpeg_scratch_bytes(int n, int px) {
@@ -136,7 +194,7 @@ int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_
         p.scan = d_scan;
         p.desc = reinterpret_cast<const bqjd::Desc*>(d_desc) + t0;
         p.tables = reinterpret_cast<const bqjd::TableSet*>(d_tables);
-        p.n_tables = n_tables; p.n = cnt; p.px = px;
+        p.n_tables = n_tables; p.n = cnt; p.w = p.h = px;
         p.coef = reinterpret_cast<int16_t*>(d_scratch); p.tile_i16 = per / 2;
         p.status = d_status + t0; p.out = d_out;
         p.p0 = t0 * ppt; p.p1 = (t0 + cnt) * ppt; p.t0 = t0;
@@ -145,6 +203,46 @@ int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_
         hipLaunchKernelGGL(jpeg_idct_kernel, dim3((bqjd::tile_blocks(px) + JP_NT - 1) / JP_NT, cnt), dim3(JP_NT), 0, s, p);
         const long long groups = (p.p1 + 3) / 4 - p.p0 / 4;
         hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((groups + JP_NT - 1) / JP_NT)), dim3(JP_NT), 0, s, p);
+    }
+    return (int)hipGetLastError();
+}
+
+size_t jpeg_canvas_scratch_bytes(int n, int w, int h) {
+    if (n <= 0 || w <= 0 || h <= 0) return 0;
+    return (size_t)(n < JPEG_ROUND ? n : JPEG_ROUND) * bqjd::tile_coef_bytes(w, h);
+}
+
+// n segments of w x h as bqio_extract_jpeg_segments packed them -> their windows in the canvas + status, in rounds of as many
+// segments as d_scratch holds (at least one).
+int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int w, int h,
+                              const int32_t* d_place, uint8_t* d_canvas, int H, int W, const int32_t* clip, int* d_status, void* d_scratch,
+                              size_t scratch_bytes, hipStream_t s) {
+    if (n <= 0) return 0;
+    const size_t per = bqjd::tile_coef_bytes(w, h);
+    size_t m = scratch_bytes / per;
+    if (m < 1) return (int)hipErrorInvalidValue;
+    if (m > 32768) m = 32768;            // (the idct and place kernels' grids count segments in y)
+    if (m >= JE_NT) m &= ~(size_t)(JE_NT - 1);
+    PlaceParams c;
+    c.canvas = d_canvas; c.H = H; c.W = W;
+    for (int k = 0; k < 4; ++k) c.clip[k] = clip[k];
+    c.groups = (w + 3) / 4 + 1;
+    const unsigned place_blocks = (unsigned)(((long long)h * c.groups + JP_NT - 1) / JP_NT);
+    for (long long t0 = 0; t0 < n; t0 += (long long)m) {
+        const int cnt = (int)(n - t0 < (long long)m ? n - t0 : (long long)m);
+        JpegParams p;
+        p.scan = d_scan;
+        p.desc = reinterpret_cast<const bqjd::Desc*>(d_desc) + t0;
+        p.tables = reinterpret_cast<const bqjd::TableSet*>(d_tables);
+        p.n_tables = n_tables; p.n = cnt; p.w = w; p.h = h;
+        p.coef = reinterpret_cast<int16_t*>(d_scratch); p.tile_i16 = per / 2;
+        p.status = d_status + t0; p.out = nullptr;
+        p.p0 = p.p1 = 0; p.t0 = t0;
+        c.place = d_place + 2 * t0;
+        if (const hipError_t e = hipMemsetAsync(d_scratch, 0, (size_t)cnt * per, s)) return (int)e;
+        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((cnt + JE_NT - 1) / JE_NT), dim3(JE_NT), 0, s, p);
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((bqjd::tile_blocks(w, h) + JP_NT - 1) / JP_NT, cnt), dim3(JP_NT), 0, s, p);
+        hipLaunchKernelGGL(jpeg_place_kernel, dim3(place_blocks, cnt), dim3(JP_NT), 0, s, p, c);
     }
     return (int)hipGetLastError();
 }

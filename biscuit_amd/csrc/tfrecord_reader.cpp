@@ -711,20 +711,13 @@ void table_set_of(const bqjpg::Scratch& S, bqjd::TableSet& T) {
     memcpy(T.zigzag, bqjpg::ZIGZAG, 64);
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t bqio_jpeg_table_bytes(void) { return sizeof(bqjd::TableSet); }
-size_t bqio_jpeg_ecs_pad(void) { return bqjd::ECS_PAD; }
-size_t bqio_jpeg_coef_bytes(int tile_px) { return tile_px > 0 ? bqjd::tile_coef_bytes(tile_px) : 0; }
-
-int bqio_extract_jpeg(bqio_reader* r, int64_t first, int64_t count, int tile_px, uint8_t* out_scan, size_t cap, uint32_t* desc,
-                      void* tables, int table_cap, int* n_tables, int64_t* loc, size_t* used, int n_threads, int64_t* bad_index) {
-    if (!r || first < 0 || count < 0 || first + count > (int64_t)r->records.size() || tile_px <= 0 || !used || !n_tables ||
-        table_cap < 0 || (out_scan && (!desc || (table_cap && !tables)))) return BQIO_ERR_ARG;
-    if (bad_index) *bad_index = -1;
-    *used = 0; *n_tables = 0;
+// What bqio_extract_jpeg and bqio_extract_jpeg_segments share: `count` JPEG streams of w x h pixels, stream i fetched by
+// get(i, buf, p, n) (BQIO_OK and its bytes [p, p + n) -- inside the caller's memory or inside buf, the worker's own buffer -- or
+// the error that refuses it), parsed, unstuffed and packed as include/biscuit_io.h describes.  *bad = the first refused stream.
+template <typename Get>
+int extract_jpeg_streams(int64_t count, int w, int h, Get get, uint8_t* out_scan, size_t cap, uint32_t* desc, void* tables, int table_cap,
+                         int* n_tables, size_t* used, int n_threads, int64_t* bad_out) {
+    *used = 0; *n_tables = 0; *bad_out = -1;
     if (count == 0) return BQIO_OK;
     const bool keep = out_scan != nullptr;                // NULL: sizes only (the once-per-slide probe)
     struct TileJ { std::vector<uint8_t> ecs; uint32_t len = 0, geom = 0; int worker = 0, set = 0; };
@@ -735,28 +728,28 @@ int bqio_extract_jpeg(bqio_reader* r, int64_t first, int64_t count, int tile_px,
     std::atomic<int64_t> next(0), bad(INT64_MAX);
     std::vector<int> bad_err((size_t)n_threads, BQIO_OK);
     std::vector<int64_t> bad_at((size_t)n_threads, INT64_MAX);
-    auto work = [&](int w) {
+    auto work = [&](int wk) {
         std::unique_ptr<bqjpg::Scratch> S(new bqjpg::Scratch());
         std::unique_ptr<bqjd::TableSet> T(new bqjd::TableSet());
+        std::vector<uint8_t> buf;
         for (;;) {
             const int64_t i0 = next.fetch_add(8);
             if (i0 >= count || i0 > bad.load()) return;
             for (int64_t i = i0; i < i0 + 8 && i < count; ++i) {
-                Example ex;
-                int e = BQIO_OK;
+                const uint8_t* p = nullptr;
+                size_t n = 0;
                 bqjpg::Header Hd;
-                if (!parse_example(r->records[(size_t)(first + i)], ex) || !ex.image.p) e = BQIO_ERR_CORRUPT;
-                else if (image_format(ex.image) != BQIO_IMG_JPEG) e = BQIO_ERR_UNSUPPORTED;
-                else {
-                    int j = bqjpg::parse_header(ex.image.p, ex.image.n, tile_px, *S, Hd);
+                int e = get(i, buf, p, n);
+                if (e == BQIO_OK) {
+                    int j = bqjpg::parse_header(p, n, w, h, *S, Hd);
                     // beyond the host decoder's refusals: grey tiles and restart intervals stay on the host decoder
                     if (j == bqjpg::OK && (Hd.ncomp != 3 || Hd.restart != 0)) j = bqjpg::UNSUPPORTED;
-                    if (j == bqjpg::OK) j = bqjpg::unstuff_scan(ex.image.p, ex.image.n, Hd, *S);
+                    if (j == bqjpg::OK) j = bqjpg::unstuff_scan(p, n, Hd, *S);
                     e = j == bqjpg::OK ? BQIO_OK : j == bqjpg::WRONG_SIZE ? BQIO_ERR_FORMAT : BQIO_ERR_UNSUPPORTED;
                     if (e == BQIO_OK && S->seg[1] > 0x7fffffffull) e = BQIO_ERR_UNSUPPORTED;
                 }
                 if (e != BQIO_OK) {
-                    if (i < bad_at[(size_t)w]) { bad_at[(size_t)w] = i; bad_err[(size_t)w] = e; }
+                    if (i < bad_at[(size_t)wk]) { bad_at[(size_t)wk] = i; bad_err[(size_t)wk] = e; }
                     int64_t cur = bad.load();
                     while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
                     return;
@@ -764,9 +757,9 @@ int bqio_extract_jpeg(bqio_reader* r, int64_t first, int64_t count, int tile_px,
                 TileJ& t = tiles[(size_t)i];
                 t.len = (uint32_t)S->seg[1];
                 t.geom = (uint32_t)Hd.hmax | ((uint32_t)Hd.vmax << 8) | (3u << 16);
-                t.worker = w;
+                t.worker = wk;
                 table_set_of(*S, *T);
-                auto& mine = sets[(size_t)w];
+                auto& mine = sets[(size_t)wk];
                 int k = (int)mine.size() - 1;
                 while (k >= 0 && memcmp(mine[(size_t)k].get(), T.get(), sizeof(bqjd::TableSet)) != 0) --k;
                 if (k < 0) {
@@ -775,7 +768,6 @@ int bqio_extract_jpeg(bqio_reader* r, int64_t first, int64_t count, int tile_px,
                 }
                 t.set = k;
                 if (keep) { S->ecs.resize(t.len); t.ecs.swap(S->ecs); }
-                if (loc) { loc[2 * i] = ex.loc_x; loc[2 * i + 1] = ex.loc_y; }
             }
         }
     };
@@ -787,22 +779,20 @@ int bqio_extract_jpeg(bqio_reader* r, int64_t first, int64_t count, int tile_px,
     }
     if (bad.load() != INT64_MAX) {
         int e = BQIO_ERR_UNSUPPORTED;
-        for (int w = 0; w < n_threads; ++w)
-            if (bad_at[(size_t)w] == bad.load()) e = bad_err[(size_t)w];
-        if (bad_index) *bad_index = first + bad.load();
-        r->err = e == BQIO_ERR_UNSUPPORTED ? "image_raw is not a baseline JPEG the device decoder handles"
-                 : e == BQIO_ERR_FORMAT    ? "tile size differs from tile_px" : "corrupt record";
+        for (int wk = 0; wk < n_threads; ++wk)
+            if (bad_at[(size_t)wk] == bad.load()) e = bad_err[(size_t)wk];
+        *bad_out = bad.load();
         return e;
     }
     // the table sets of the call: the workers' lists merged
     std::vector<const bqjd::TableSet*> all;
     std::vector<std::vector<int>> global((size_t)n_threads);
-    for (int w = 0; w < n_threads; ++w)
-        for (auto& sp : sets[(size_t)w]) {
+    for (int wk = 0; wk < n_threads; ++wk)
+        for (auto& sp : sets[(size_t)wk]) {
             int k = (int)all.size() - 1;
             while (k >= 0 && memcmp(all[(size_t)k], sp.get(), sizeof(bqjd::TableSet)) != 0) --k;
             if (k < 0) { k = (int)all.size(); all.push_back(sp.get()); }
-            global[(size_t)w].push_back(k);
+            global[(size_t)wk].push_back(k);
         }
     size_t at = 0;
     std::vector<size_t> offs((size_t)count + 1);
@@ -840,6 +830,69 @@ int bqio_extract_jpeg(bqio_reader* r, int64_t first, int64_t count, int tile_px,
     return BQIO_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+size_t bqio_jpeg_table_bytes(void) { return sizeof(bqjd::TableSet); }
+size_t bqio_jpeg_ecs_pad(void) { return bqjd::ECS_PAD; }
+size_t bqio_jpeg_coef_bytes(int tile_px) { return tile_px > 0 ? bqjd::tile_coef_bytes(tile_px) : 0; }
+
+int bqio_extract_jpeg(bqio_reader* r, int64_t first, int64_t count, int tile_px, uint8_t* out_scan, size_t cap, uint32_t* desc,
+                      void* tables, int table_cap, int* n_tables, int64_t* loc, size_t* used, int n_threads, int64_t* bad_index) {
+    if (!r || first < 0 || count < 0 || first + count > (int64_t)r->records.size() || tile_px <= 0 || !used || !n_tables ||
+        table_cap < 0 || (out_scan && (!desc || (table_cap && !tables)))) return BQIO_ERR_ARG;
+    if (bad_index) *bad_index = -1;
+    // record i of the call -> its image_raw bytes (inside the mapping)
+    auto get = [&](int64_t i, std::vector<uint8_t>&, const uint8_t*& p, size_t& n) {
+        Example ex;
+        if (!parse_example(r->records[(size_t)(first + i)], ex) || !ex.image.p) return (int)BQIO_ERR_CORRUPT;
+        if (image_format(ex.image) != BQIO_IMG_JPEG) return (int)BQIO_ERR_UNSUPPORTED;
+        p = ex.image.p; n = ex.image.n;
+        if (loc) { loc[2 * i] = ex.loc_x; loc[2 * i + 1] = ex.loc_y; }
+        return (int)BQIO_OK;
+    };
+    int64_t bad = -1;
+    const int e = extract_jpeg_streams(count, tile_px, tile_px, get, out_scan, cap, desc, tables, table_cap, n_tables, used, n_threads, &bad);
+    if (bad >= 0) {
+        if (bad_index) *bad_index = first + bad;
+        r->err = e == BQIO_ERR_UNSUPPORTED ? "image_raw is not a baseline JPEG the device decoder handles"
+                 : e == BQIO_ERR_FORMAT    ? "tile size differs from tile_px" : "corrupt record";
+    }
+    return e;
+}
+
+int bqio_extract_jpeg_segments(const uint8_t* data, size_t data_len, const uint64_t* off, const uint64_t* len, int64_t n,
+                               const uint8_t* jpeg_tables, size_t jpeg_tables_len, int seg_w, int seg_h, uint8_t* out_scan, size_t cap,
+                               uint32_t* desc, void* tables, int table_cap, int* n_tables, size_t* used, int n_threads,
+                               int64_t* bad_index) {
+    if (n < 0 || seg_w <= 0 || seg_h <= 0 || seg_w > 4096 || seg_h > 4096 || !used || !n_tables || table_cap < 0 ||
+        (n && (!data || !off || !len)) || (jpeg_tables_len && !jpeg_tables) || (out_scan && (!desc || (table_cap && !tables))))
+        return BQIO_ERR_ARG;
+    if (bad_index) *bad_index = -1;
+    for (int64_t i = 0; i < n; ++i)
+        if (off[i] > data_len || len[i] > data_len - off[i]) return BQIO_ERR_ARG;
+    // The stream a TIFF reader hands libjpeg for one segment: the page's tables stream without its EOI, then the segment
+    // without its SOI (so a table the segment defines comes later and wins); a page without JPEGTables: the segment as it is.
+    size_t tl = jpeg_tables ? jpeg_tables_len : 0;
+    if (tl >= 2 && jpeg_tables[tl - 2] == 0xFF && jpeg_tables[tl - 1] == 0xD9) tl -= 2;
+    auto get = [&](int64_t i, std::vector<uint8_t>& buf, const uint8_t*& p, size_t& m) {
+        const uint8_t* sg = data + off[i];
+        size_t sl = (size_t)len[i];
+        if (tl == 0) { p = sg; m = sl; return (int)BQIO_OK; }
+        if (sl >= 2 && sg[0] == 0xFF && sg[1] == 0xD8) { sg += 2; sl -= 2; }
+        buf.resize(tl + sl);
+        memcpy(buf.data(), jpeg_tables, tl);
+        if (sl) memcpy(buf.data() + tl, sg, sl);
+        p = buf.data(); m = buf.size();
+        return (int)BQIO_OK;
+    };
+    int64_t bad = -1;
+    const int e = extract_jpeg_streams(n, seg_w, seg_h, get, out_scan, cap, desc, tables, table_cap, n_tables, used, n_threads, &bad);
+    if (bad >= 0 && bad_index) *bad_index = bad;
+    return e;
+}
+
 int bqio_jpeg_decode_extracted(const uint8_t* scan, const uint32_t* desc, const void* tables, int n_tables, int n, int tile_px,
                                uint8_t* out, int32_t* status, int n_threads) {
     if (n < 0 || tile_px <= 0 || tile_px > 4096 || n_tables < 0 || (n && (!scan || !desc || !out || !status)) || (n_tables && !tables))
@@ -866,6 +919,42 @@ int bqio_jpeg_decode_extracted(const uint8_t* scan, const uint32_t* desc, const 
             uint8_t* o = out + (size_t)i * tile_px * tile_px * 3;
             for (int y = 0; y < tile_px; ++y)
                 for (int x = 0; x < tile_px; ++x) bqjd::pixel_rgb(planes, G, y, x, o + 3 * ((size_t)y * tile_px + x));
+            status[i] = st;
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < n_threads; ++t) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    return BQIO_OK;
+}
+
+int bqio_jpeg_decode_canvas(const uint8_t* scan, const uint32_t* desc, const void* tables, int n_tables, int n, int seg_w, int seg_h,
+                            const int32_t* place, uint8_t* canvas, int H, int W, const int32_t* clip, int32_t* status, int n_threads) {
+    if (n < 0 || seg_w <= 0 || seg_h <= 0 || seg_w > 4096 || seg_h > 4096 || n_tables < 0 || H <= 0 || W <= 0 || H > (1 << 28) ||
+        W > (1 << 28) || !canvas || !clip || (n && (!scan || !desc || !place || !status)) || (n_tables && !tables))
+        return BQIO_ERR_ARG;
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > n) n_threads = n ? n : 1;
+    const bqjd::TableSet* T = (const bqjd::TableSet*)tables;
+    std::atomic<int> next(0);
+    auto work = [&]() {
+        std::vector<int16_t> coef;
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n) return;
+            bqjd::Desc d;
+            memcpy(&d, desc + 4 * (size_t)i, sizeof(d));
+            bqjd::Geom G;
+            if (!bqjd::geom_of(d.geom, seg_w, seg_h, G) || d.tset >= (uint32_t)n_tables) { status[i] = bqjd::ST_DESC; continue; }
+            coef.assign((size_t)bqjd::tile_blocks(seg_w, seg_h) * 64, (int16_t)0);  // exactly the segment's coefficient space
+            int st = bqjd::entropy_tile(scan + d.off, d.len, G, T + d.tset, coef.data());
+            const uint32_t nblk = G.base[2] + (uint32_t)(G.mcux * G.mcuy);
+            for (uint32_t b = 0; b < nblk; ++b)
+                if (!bqjd::idct_in_place(coef.data() + (size_t)b * 64)) st |= bqjd::ST_RANGE;
+            bqjd::Window w;
+            if (bqjd::place_window(place[2 * i], place[2 * i + 1], seg_w, seg_h, H, W, clip, w))
+                bqjd::place_segment((const uint8_t*)coef.data(), G, w, place[2 * i], place[2 * i + 1], canvas, W);
             status[i] = st;
         }
     };

@@ -246,6 +246,38 @@ class Engine:
         tiles at most -- 1.14 GB; a longer call works in rounds)."""
         return torch.empty(int(self._lib.bq_jpeg_scratch_bytes(int(n), int(px))), dtype=torch.uint8, device=self.device)
 
+    def jpeg_decode_canvas(self, scan, desc, tables, seg_w, seg_h, place, canvas, clip, scratch=None):
+        """A slide page's own JPEG tiles decoded on the device INTO a canvas (``bq_jpeg_decode_canvas``, kernels_jpeg.hip: the
+        entropy and IDCT kernels of ``jpeg_decode``, then a colour-and-place kernel): ``scan``, ``desc``, ``tables`` as
+        ``tfrecord_native.extract_jpeg_segments`` packed the ``seg_w`` x ``seg_h`` segments, ``place`` int32 [n, 2] the canvas
+        position (x, y) of each segment's top-left pixel (negative or past the canvas allowed), ``canvas`` uint8 [H, W, 3] and
+        ``clip`` = (x0, y0, x1, y1) in canvas coordinates -- all tensors on this device.  Exactly the pixels of a segment inside
+        both the canvas and ``clip`` are written; the caller fills the canvas beforehand (255 for a slide).  Returns status int32
+        [n] on the device, 0 where the segment decoded.  ``scratch``: coefficient space of at least one segment
+        (``jpeg_canvas_scratch(n, seg_w, seg_h)`` holds a whole round); the call works in rounds of as many segments as it holds."""
+        assert scan.dtype == torch.uint8 and scan.is_cuda and scan.is_contiguous()
+        n, seg_w, seg_h = int(desc.shape[0]), int(seg_w), int(seg_h)
+        assert desc.is_cuda and desc.is_contiguous() and desc.element_size() == 4 and tuple(desc.shape) == (n, 4)
+        assert tables.dtype == torch.uint8 and tables.is_cuda and tables.is_contiguous() and tables.dim() == 2
+        assert place.dtype == torch.int32 and place.is_cuda and place.is_contiguous() and tuple(place.shape) == (n, 2)
+        assert canvas.dtype == torch.uint8 and canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == 3 and canvas.shape[2] == 3
+        x0, y0, x1, y1 = (int(v) for v in clip)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if scratch is None:
+            scratch = self._grown('_jpeg_ws', int(self._lib.bq_jpeg_canvas_scratch_bytes(n, seg_w, seg_h)))
+        assert scratch.is_cuda and scratch.is_contiguous()
+        self._check(self._lib.bq_jpeg_decode_canvas(self._ctx, _ptr(scan), _ptr(desc), _ptr(tables), int(tables.shape[0]), n, seg_w, seg_h,
+                                                    _ptr(place), _ptr(canvas), int(canvas.shape[0]), int(canvas.shape[1]), x0, y0, x1, y1,
+                                                    _ptr(status), _ptr(scratch), scratch.numel() * scratch.element_size(),
+                                                    self._stream()))
+        return status
+
+    def jpeg_canvas_scratch(self, n, seg_w, seg_h):
+        """Coefficient space for ``jpeg_decode_canvas`` over ``n`` segments (``bq_jpeg_canvas_scratch_bytes``: 393 KB per 256 x 256
+        segment, for 2 048 segments at most; a longer call works in rounds)."""
+        return torch.empty(int(self._lib.bq_jpeg_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h))), dtype=torch.uint8,
+                           device=self.device)
+
     def tile_resample(self, canvas, origin, src_px, px=TILE_PX, out=None):
         """The heatmap's tile grid cut from a slide canvas and resampled on the device (``bq_tile_resample``,
         kernels_resample.hip): ``canvas`` uint8 [H, W, 3] and ``origin`` int32 [n, 2] -- the (x, y) of every tile's ``src_px``

@@ -59,6 +59,7 @@ class Heatmap:
             raise ValueError('grid position outside grid_shape')
         self.grid = grid
         self.dropped = 0                 # tiles a background filter left out (from_slide(grayspace_fraction=...))
+        self.decode_stats = {'gpu_bands': 0, 'host_bands': 0, 'segments': 0}      # (from_slide(resample='gpu') counts its bands)
         self.logits = np.full((gy, gx, 2), MASKED, dtype=np.float32)
         self.uncertainty = np.full((gy, gx, 2), MASKED, dtype=np.float32)
         dev = engine.device
@@ -82,7 +83,7 @@ class Heatmap:
 
     @classmethod
     def from_slide(cls, engine, path, tile_px=299, tile_um=302, stride_div=1, mpp=None, resample='gpu', canvas_bytes=256 << 20,
-                   grayspace_fraction=None, grayspace_threshold=0.05, **kw):
+                   grayspace_fraction=None, grayspace_threshold=0.05, decode='host', **kw):
         """``sf.Heatmap(slide, model, stride_div=1)`` (results.py:217) for a pyramidal TIFF / SVS slide file: the tile grid of
         ``wsi.WSI(path, tile_px, tile_um, stride_div)`` through the MC-dropout kernels.  (The reader is this build's own --
         ``biscuit_amd/wsi.py`` says what it reads and what about it is unpinned.)
@@ -98,12 +99,24 @@ class Heatmap:
         fraction of its pixels has an HSV saturation below ``grayspace_threshold`` (Slideflow's extraction filter, restated:
         fraction 0.6 and threshold 0.05 there), before stain normalisation.  Dropped cells hold ``MASKED`` in both grids,
         ``self.grid`` lists the kept tiles only and ``self.dropped`` counts the rest; a kept tile's values do not depend on the
-        filter."""
+        filter.
+
+        ``decode='gpu'`` (``resample='gpu'`` only; default 'host'): a band whose level is a tiled JPEG page is not decoded by
+        ``read_region`` on the host -- its raw tiles are read, packed (``tfrecord_native.extract_jpeg_segments``), uploaded
+        and decoded on the device straight into the band's canvas (``Engine.jpeg_decode_canvas``): the same bytes, so the same
+        arrays.  A band goes through ``read_region`` as before -- the pixels and any ``SlideError`` are then the host's -- when
+        the extractor refuses one of its segments, when a segment's device status is not 0, or when the level is not a tiled
+        JPEG page.  ``self.decode_stats = {'gpu_bands', 'host_bands', 'segments'}`` counts the bands either way took and the
+        segments the device decoded."""
         from .wsi import WSI
         if resample not in ('gpu', 'host'):
             raise ValueError(f"resample must be 'gpu' or 'host', not {resample!r}")
         if resample == 'host' and grayspace_fraction is not None:
             raise ValueError("the background filter runs on the device: grayspace_fraction needs resample='gpu'")
+        if decode not in ('host', 'gpu'):
+            raise ValueError(f"decode must be 'host' or 'gpu', not {decode!r}")
+        if resample == 'host' and decode == 'gpu':
+            raise ValueError("the device decodes into the band's canvas: decode='gpu' needs resample='gpu'")
         w = WSI(path, tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
         try:
             if w.grid_w * w.grid_h == 0:
@@ -111,13 +124,33 @@ class Heatmap:
             if resample == 'host':
                 tiles, grid = w.tiles()
                 return cls(engine, tiles, grid, grid_shape=(w.grid_h, w.grid_w), **kw)
-            return cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, **kw)
+            return cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, decode=decode, **kw)
         finally:
             w.close()
 
     @classmethod
+    @staticmethod
+    def _decode_band(engine, sg):
+        """A band's canvas decoded on the device from its raw JPEG tiles (``wsi.BandSegments``): extract on the host, upload
+        scan, descriptors, tables and places, fill the canvas with 255, decode, read the status once.  -> the canvas (uint8
+        [H, W, 3] on the device), or None when the extractor refuses a segment or any status is not 0."""
+        from . import tfrecord_native as tn
+        try:
+            scan, desc, tables = tn.extract_jpeg_segments(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h, sg.jpeg_tables)
+        except ValueError:                                                       # (UnsupportedImage is one)
+            return None
+        dev = engine.device
+        canvas = torch.full(tuple(sg.shape) + (3,), 255, dtype=torch.uint8, device=dev)
+        if len(sg) == 0:
+            return canvas
+        status = engine.jpeg_decode_canvas(torch.from_numpy(scan).to(dev), torch.from_numpy(desc.view(np.int32)).to(dev),
+                                           torch.from_numpy(tables).to(dev), sg.seg_w, sg.seg_h, torch.from_numpy(sg.place).to(dev),
+                                           canvas, sg.clip)
+        return None if bool(status.any().item()) else canvas
+
+    @classmethod
     def _streamed(cls, engine, w, canvas_bytes, gray_fraction, gray_threshold, mc_n=30, seed=0, batch=256, norm_fit=None,
-                  normalizer='reinhard_fast'):
+                  normalizer='reinhard_fast', decode='host'):
         """``from_slide(resample='gpu')``: bands -> batches of exactly the tiles ``Heatmap(engine, *w.tiles())`` would put in
         each batch (a batch is filled across band boundaries), so an unfiltered slide runs the same launches on the same bytes."""
         from . import stain
@@ -129,6 +162,7 @@ class Heatmap:
         hm.logits = np.full((gh, gw, 2), MASKED, dtype=np.float32)
         hm.uncertainty = np.full((gh, gw, 2), MASKED, dtype=np.float32)
         hm.dropped = 0
+        hm.decode_stats = stats = {'gpu_bands': 0, 'host_bands': 0, 'segments': 0}
         buf = torch.empty((batch, px, px, 3), dtype=torch.uint8, device=dev)      # the one batch the device holds
         idx = np.empty(batch, np.int64)                                          # its tiles' row-major grid indices
         kept, fill = [], 0
@@ -141,8 +175,18 @@ class Heatmap:
             hm.uncertainty[gy, gx] = std.cpu().numpy()
             kept.append(idx[:n].copy())
 
-        for gy0, gy1, gx0, gx1, canvas, origin, src_px in w.bands(canvas_bytes):
-            d_canvas = torch.from_numpy(canvas).to(dev)
+        for gy0, gy1, gx0, gx1, canvas, origin, src_px in w.bands(canvas_bytes, segments=decode == 'gpu'):
+            d_canvas = None
+            if decode == 'gpu' and canvas is not None:
+                d_canvas = cls._decode_band(engine, canvas)
+                if d_canvas is not None:
+                    stats['gpu_bands'] += 1
+                    stats['segments'] += len(canvas)
+            if d_canvas is None:
+                if decode == 'gpu':
+                    canvas = w.band(gy0, gy1, gx0, gx1)[0]                       # the host's pixels, or the host's SlideError
+                d_canvas = torch.from_numpy(canvas).to(dev)
+                stats['host_bands'] += 1
             d_origin = torch.from_numpy(origin).to(dev)
             del canvas, origin                                                   # uploaded: the host holds one canvas at a time
             cell = (np.arange(gy0, gy1, dtype=np.int64)[:, None] * gw + np.arange(gx0, gx1, dtype=np.int64)[None, :]).reshape(-1)
@@ -216,6 +260,8 @@ def main(argv=None):
     ap.add_argument('--grayspace-fraction', type=float, default=None,
                     help='drop tiles with more than this fraction of grey pixels (Slideflow extracts with 0.6); default: off')
     ap.add_argument('--grayspace-threshold', type=float, default=0.05)
+    ap.add_argument('--gpu-decode', action='store_true',
+                    help="decode the slide's own JPEG tiles on the device (from_slide(decode='gpu')); the arrays do not change")
     ap.add_argument('--mpp', type=float, default=None, help='microns per pixel, for a file that does not say')
     ap.add_argument('--save-tiles', action='store_true', help='write the tiles to uq_incl/ and uq_excl/ (needs --tile-uq)')
     args = ap.parse_args(argv)
@@ -231,7 +277,8 @@ def main(argv=None):
         t0 = time.perf_counter()
         hm = Heatmap.from_slide(eng, args.slide, stride_div=args.stride_div, mpp=args.mpp, mc_n=mc, seed=args.seed, batch=args.batch,
                                 norm_fit=norm_fit, normalizer=hp.normalizer or 'reinhard_fast',
-                                grayspace_fraction=args.grayspace_fraction, grayspace_threshold=args.grayspace_threshold)
+                                grayspace_fraction=args.grayspace_fraction, grayspace_threshold=args.grayspace_threshold,
+                                decode='gpu' if args.gpu_decode else 'host')
         torch.cuda.synchronize(eng.device)
         seconds = time.perf_counter() - t0
     finally:
@@ -257,7 +304,7 @@ def main(argv=None):
     np.savez(os.path.join(args.out, 'heatmap.npz'), **arrays)
     run = int(len(hm.grid))
     summary = {'slide': args.slide, 'grid_shape': list(hm.logits.shape[:2]), 'tiles_run': run, 'tiles_dropped': int(hm.dropped),
-               'seconds': seconds, 'tiles_per_s': run / seconds if seconds > 0 else None}
+               'seconds': seconds, 'tiles_per_s': run / seconds if seconds > 0 else None, 'decode_stats': hm.decode_stats}
     with open(os.path.join(args.out, 'summary.json'), 'w') as f:
         json.dump(summary, f)
     print(json.dumps(summary))

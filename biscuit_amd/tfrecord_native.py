@@ -37,6 +37,9 @@ ABI = {
     'bqio_jpeg_ecs_pad': (C.c_size_t, []),
     'bqio_jpeg_coef_bytes': (C.c_size_t, [_i]),
     'bqio_jpeg_decode_extracted': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i]),
+    'bqio_extract_jpeg_segments': (_i, [_vp, C.c_size_t, _vp, _vp, _i64, _vp, C.c_size_t, _i, _i, _vp, C.c_size_t, _vp, _vp, _i,
+                                        C.POINTER(_i), C.POINTER(C.c_size_t), _i, C.POINTER(_i64)]),
+    'bqio_jpeg_decode_canvas': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i]),
     'bqio_resample_ksize': (_i, [_i, _i]),
     'bqio_resample_taps': (_i, [_i, _i, _vp, _vp, _i]),
     'bqio_tile_resample': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
@@ -137,6 +140,68 @@ def jpeg_decode_extracted(scan, desc, tables, px=299, threads=None):
     if e != 0:
         raise ValueError(f'bqio_jpeg_decode_extracted: error {e}')
     return out, status
+
+
+def extract_jpeg_segments(data, offsets, lengths, seg_w, seg_h, jpeg_tables=None, threads=None, probe=False):
+    """A TIFF page's raw JPEG segments packed for the device decoder (``bqio_extract_jpeg_segments``): ``data`` uint8 [bytes],
+    segment i = ``data[offsets[i]:offsets[i] + lengths[i]]``, every one a ``seg_w`` x ``seg_h`` frame, ``jpeg_tables`` the page's
+    ``JPEGTables`` bytes or None -> ``(scan uint8 [bytes], desc uint32 [n, 4], tables uint8 [k, jpeg_table_bytes()])`` as
+    ``NativeReader.extract_jpeg`` fills them (``probe=True``: only ``(bytes of scan, k)``, nothing packed).  Raises
+    ``UnsupportedImage`` (``.index`` = the first refused segment) for a stream outside the device decoder's subset -- not three
+    components at 4:4:4 / 4:2:2 / 4:2:0, restart intervals, RGB / CMYK coded, progressive, damaged -- and ``ValueError`` for a
+    frame of another size."""
+    data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+    off, ln = np.ascontiguousarray(offsets, np.uint64).reshape(-1), np.ascontiguousarray(lengths, np.uint64).reshape(-1)
+    n = len(off)
+    assert len(ln) == n
+    jt = np.frombuffer(bytes(jpeg_tables or b''), np.uint8)
+    tb = jpeg_table_bytes()
+    # a segment's entropy-coded bytes only shrink when the stuffed zeros go: the packed size is bounded beforehand
+    pad, cap_t = int(lib().bqio_jpeg_ecs_pad()), 8
+    cap = 0 if probe else int(((ln.astype(np.int64) + pad + 31) // 16 * 16).sum()) + 16
+    while True:
+        scan = None if probe else np.empty(cap, np.uint8)
+        desc = np.empty((n, 4), np.uint32)
+        tables = np.empty((cap_t, tb), np.uint8)
+        nt, used, bad = C.c_int(0), C.c_size_t(0), C.c_int64(-1)
+        e = lib().bqio_extract_jpeg_segments(data.ctypes.data, data.size, off.ctypes.data, ln.ctypes.data, n,
+                                             jt.ctypes.data if jt.size else None, jt.size, int(seg_w), int(seg_h),
+                                             None if probe else scan.ctypes.data, cap, desc.ctypes.data, tables.ctypes.data, cap_t,
+                                             C.byref(nt), C.byref(used), threads or default_threads(), C.byref(bad))
+        if e == ERR_UNSUPPORTED:
+            raise UnsupportedImage(int(bad.value))
+        if e == ERR_FORMAT:
+            err = ValueError(f'segment {bad.value}: frame size differs from {seg_w} x {seg_h}')
+            err.index = int(bad.value)
+            raise err
+        if e == -1 and not probe and nt.value > cap_t and used.value <= cap:      # more table sets than guessed: once more
+            cap_t = nt.value
+            continue
+        if e != 0:
+            raise ValueError(f'bqio_extract_jpeg_segments: error {e}')
+        if probe:
+            return int(used.value), int(nt.value)
+        return scan[:used.value], desc, tables[:nt.value].copy()
+
+
+def jpeg_decode_canvas(scan, desc, tables, seg_w, seg_h, place, canvas, clip, threads=None):
+    """The device canvas decoder's routines (csrc/jpeg_device.h) on the CPU (``bqio_jpeg_decode_canvas``): the segments
+    ``extract_jpeg_segments`` packed, written INTO ``canvas`` (uint8 [H, W, 3], C-contiguous, modified in place) at ``place`` int32
+    [n, 2] (x, y), clipped to ``clip`` = (x0, y0, x1, y1) in canvas coordinates.  -> status int32 [n].  What
+    ``Engine.jpeg_decode_canvas`` computes, byte for byte and status for status.  For tests."""
+    scan, desc, tables = np.ascontiguousarray(scan, np.uint8), np.ascontiguousarray(desc, np.uint32), np.ascontiguousarray(tables, np.uint8)
+    place = np.ascontiguousarray(place, np.int32).reshape(-1, 2)
+    clip = np.ascontiguousarray(clip, np.int32).reshape(4)
+    n = desc.shape[0]
+    assert desc.shape == (n, 4) and place.shape == (n, 2) and tables.size % jpeg_table_bytes() == 0
+    assert canvas.dtype == np.uint8 and canvas.ndim == 3 and canvas.shape[2] == 3 and canvas.flags.c_contiguous and canvas.flags.writeable
+    status = np.zeros(n, np.int32)
+    e = lib().bqio_jpeg_decode_canvas(scan.ctypes.data, desc.ctypes.data, tables.ctypes.data, tables.size // jpeg_table_bytes(), n,
+                                      int(seg_w), int(seg_h), place.ctypes.data, canvas.ctypes.data, canvas.shape[0], canvas.shape[1],
+                                      clip.ctypes.data, status.ctypes.data, threads or default_threads())
+    if e != 0:
+        raise ValueError(f'bqio_jpeg_decode_canvas: error {e}')
+    return status
 
 
 def inflate_fallbacks():

@@ -95,6 +95,24 @@ class _Page:
             raise SlideError('TIFF page: strip / tile tables do not cover the image')
 
 
+class BandSegments:
+    """A band's canvas as the page's own JPEG tiles, not yet decoded (``WSI.band_segments``): ``shape`` = (H, W) of the canvas
+    ``WSI.band`` would read; ``data`` uint8 [bytes], the raw segments one after the other, segment i =
+    ``data[offsets[i]:offsets[i] + lengths[i]]`` (uint64 each); ``place`` int32 [n, 2], the canvas position (x, y) of each
+    segment's top-left pixel (negative where the segment starts left of / above the canvas); ``clip`` = (x0, y0, x1, y1), the
+    level's image extent in canvas coordinates, cut to the canvas -- what a segment holds beyond it is padding; ``seg_w``,
+    ``seg_h`` the page's tile size; ``jpeg_tables`` the page's ``JPEGTables`` bytes or None.  Decoding every segment as
+    ``TiffSlide._jpeg`` reads it into a white canvas, inside ``clip`` only, gives ``WSI.band``'s canvas."""
+    __slots__ = ('shape', 'data', 'offsets', 'lengths', 'place', 'clip', 'seg_w', 'seg_h', 'jpeg_tables')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def __len__(self):
+        return len(self.offsets)
+
+
 class TiffSlide:
     """``TiffSlide(path)``: ``levels`` (pyramid pages, largest first), ``level_downsamples``, ``dimensions`` (width, height of level 0),
     ``mpp`` (microns per pixel of level 0, or None), ``read_region(level, x, y, w, h)`` in that level's pixels -> uint8 [h, w, 3]
@@ -284,6 +302,41 @@ class TiffSlide:
                     out[ay0 - y:ay1 - y, ax0 - x:ax1 - x] = seg[ay0 - sy0:ay1 - sy0, ax0 - sx0:ax1 - sx0]
         return out
 
+    @_guard
+    def region_segments(self, level, x, y, w, h):
+        """The raw JPEG tiles ``read_region(level, x, y, w, h)`` would decode, as a ``BandSegments`` over the same [h, w] canvas,
+        or None when the level is not a tiled JPEG page (compression 7 with TileWidth / TileLength: strips, deflate and
+        uncompressed pages stay on ``read_region``).  Read through ``_segment``'s bounds checks -- a byte count beyond the
+        file's size, a segment that does not lie inside the file, more segment bytes than the file holds: ``SlideError``."""
+        p = self.levels[level]
+        if not (p.tiled and p.compression == 7):
+            return None
+        if not (0 < w <= 1 << 16 and 0 < h <= 1 << 16):
+            raise SlideError(f'region of {w} x {h} pixels')
+        x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + w, p.width), min(y + h, p.height)
+        chunks, place, total = [], [], 0
+        if x1 > x0 and y1 > y0:
+            for ty in range(y0 // p.th, (y1 - 1) // p.th + 1):
+                for tx in range(x0 // p.tw, (x1 - 1) // p.tw + 1):
+                    index = ty * p.across + tx
+                    off, cnt = int(p.offsets[index]), int(p.counts[index])
+                    total += cnt
+                    if cnt > self._size or off + cnt > self._size or total > self._size:
+                        raise SlideError(f'{self.path}: segment {index} of level {level} claims more bytes than the file holds')
+                    self._f.seek(off)
+                    raw = self._f.read(cnt)
+                    if len(raw) != cnt:
+                        raise SlideError(f'{self.path}: segment {index} of level {level} runs past the end of the file')
+                    chunks.append(raw)
+                    place.append((tx * p.tw - x, ty * p.th - y))
+        lengths = np.array([len(c) for c in chunks], np.uint64)
+        offsets = np.zeros(len(chunks), np.uint64)
+        offsets[1:] = np.cumsum(lengths)[:-1]
+        return BandSegments(shape=(h, w), data=np.frombuffer(b''.join(chunks), np.uint8), offsets=offsets, lengths=lengths,
+                            place=np.array(place, np.int32).reshape(-1, 2),
+                            clip=(max(0, -x), max(0, -y), min(w, p.width - x), min(h, p.height - y)),
+                            seg_w=p.tw, seg_h=p.th, jpeg_tables=p.jpeg_tables)
+
     def close(self):
         self._f.close()
 
@@ -375,13 +428,8 @@ class WSI:
     def _level_xy(self, g):
         return int(round(g * self.stride / self.level_ds))               # ``_tile``'s lx / ly of grid column / row g
 
-    @_guard
-    def band(self, gy0, gy1, gx0=0, gx1=None):
-        """Grid rows [gy0, gy1) (and columns [gx0, gx1), default all) as ONE read: ``(canvas, origin, src_px)`` -- canvas uint8
-        [H, W, 3], the rectangle of ``self.level`` that covers every tile's ``src_px`` x ``src_px`` window (white where a window
-        pokes past the level's edge, as ``read_region`` pads); origin int32 [T, 2], ``(lx - X0, ly - Y0)`` of every tile in
-        row-major grid order with ``lx, ly`` as ``_tile`` computes them; ``src_px`` = ``_tile``'s ``lw``.  Cutting the windows
-        out of the canvas and resampling them (``resample.tile_resample`` / ``Engine.tile_resample``) gives ``_tile``'s bytes."""
+    def _band_rect(self, gy0, gy1, gx0, gx1):
+        """``band``'s geometry without its pixels: (x0, y0, W, H) of the canvas in ``self.level``, origin int32 [T, 2], ``src_px``."""
         gx1 = self.grid_w if gx1 is None else gx1
         if not (0 <= gy0 < gy1 <= self.grid_h and 0 <= gx0 < gx1 <= self.grid_w):
             raise SlideError(f'band rows [{gy0}, {gy1}) x columns [{gx0}, {gx1}) outside the {self.grid_h} x {self.grid_w} grid')
@@ -389,17 +437,39 @@ class WSI:
         xs = np.array([self._level_xy(g) for g in range(gx0, gx1)], np.int64)
         ys = np.array([self._level_xy(g) for g in range(gy0, gy1)], np.int64)
         x0, y0 = int(xs[0]), int(ys[0])
-        canvas = self.slide.read_region(self.level, x0, y0, int(xs[-1]) + lw - x0, int(ys[-1]) + lw - y0)
         origin = np.empty((len(ys), len(xs), 2), np.int32)
         origin[:, :, 0] = (xs - x0)[None, :]
         origin[:, :, 1] = (ys - y0)[:, None]
-        return canvas, origin.reshape(-1, 2), lw
+        return (x0, y0, int(xs[-1]) + lw - x0, int(ys[-1]) + lw - y0), origin.reshape(-1, 2), lw
 
-    def bands(self, canvas_bytes=256 << 20):
+    @_guard
+    def band(self, gy0, gy1, gx0=0, gx1=None):
+        """Grid rows [gy0, gy1) (and columns [gx0, gx1), default all) as ONE read: ``(canvas, origin, src_px)`` -- canvas uint8
+        [H, W, 3], the rectangle of ``self.level`` that covers every tile's ``src_px`` x ``src_px`` window (white where a window
+        pokes past the level's edge, as ``read_region`` pads); origin int32 [T, 2], ``(lx - X0, ly - Y0)`` of every tile in
+        row-major grid order with ``lx, ly`` as ``_tile`` computes them; ``src_px`` = ``_tile``'s ``lw``.  Cutting the windows
+        out of the canvas and resampling them (``resample.tile_resample`` / ``Engine.tile_resample``) gives ``_tile``'s bytes."""
+        (x0, y0, cw, ch), origin, lw = self._band_rect(gy0, gy1, gx0, gx1)
+        return self.slide.read_region(self.level, x0, y0, cw, ch), origin, lw
+
+    @_guard
+    def band_segments(self, gy0, gy1, gx0=0, gx1=None):
+        """``band`` with the canvas left compressed, for a caller that decodes it on the device (``Engine.jpeg_decode_canvas``):
+        ``(segments, origin, src_px)`` with ``band``'s origin and ``src_px`` and segments = a ``BandSegments`` over ``band``'s
+        canvas -- the level's raw JPEG tiles that cover it, their places in it and the clip rectangle -- or None when the level
+        is not a tiled JPEG page.  ``SlideError`` where the file's segment tables point outside the file."""
+        (x0, y0, cw, ch), origin, lw = self._band_rect(gy0, gy1, gx0, gx1)
+        return self.slide.region_segments(self.level, x0, y0, cw, ch), origin, lw
+
+    def bands(self, canvas_bytes=256 << 20, segments=False):
         """Iterate the grid as bands whose canvas stays under ``canvas_bytes`` (at least one grid row each): yields ``(gy0, gy1,
         gx0, gx1, canvas, origin, src_px)`` with ``band``'s values.  A band is split into column ranges only where one grid row
         is wider than ``read_region`` reads at once (``READ_LIMIT``, 65 536 pixels); the tiles of such a slide then arrive band by
-        band, not in row-major order of the whole grid."""
+        band, not in row-major order of the whole grid.
+
+        ``segments=True`` yields ``band_segments``' values instead: a ``BandSegments`` in place of the canvas, or None in its
+        place where the band has to be read with ``band`` -- the level is not a tiled JPEG page, or the segment tables point
+        outside the file (``band`` then says so)."""
         lw, limit = self.src_px, self.READ_LIMIT
         cols, gx0 = [], 0
         while gx0 < self.grid_w:                                          # column ranges of at most `limit` pixels
@@ -418,7 +488,13 @@ class WSI:
                     break
                 gy1 += 1
             for a, b in cols:
-                yield (gy0, gy1, a, b) + self.band(gy0, gy1, a, b)
+                if not segments:
+                    yield (gy0, gy1, a, b) + self.band(gy0, gy1, a, b)
+                    continue
+                try:
+                    yield (gy0, gy1, a, b) + self.band_segments(gy0, gy1, a, b)
+                except SlideError:
+                    yield (gy0, gy1, a, b, None) + self._band_rect(gy0, gy1, a, b)[1:]
             gy0 = gy1
 
     def close(self):

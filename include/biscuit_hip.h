@@ -196,6 +196,25 @@ size_t bq_jpeg_scratch_bytes(int n, int px);
 int bq_jpeg_decode(bq_ctx* ctx, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px,
                    uint8_t* d_out_nhwc, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
 
+/* The same decoder for a TIFF page's own JPEG tiles, written straight into a slide canvas (DESIGN.md "Heatmap input", "Decode"):
+ * n segments of seg_w x seg_h (each <= 4096) as libbiscuit_io's bqio_extract_jpeg_segments packs them -- d_scan, d_desc, d_tables as
+ * above -- are decoded by the same entropy and IDCT kernels, and a colour-and-place kernel writes them into d_canvas uint8
+ * [H][W][3] (H, W <= 2^28; row pitch 3 W, any alignment).  d_place int32 [n][2] = the canvas position (x, y) of each segment's
+ * top-left pixel; it may be negative or reach past the canvas.  (clip_x0, clip_y0, clip_x1, clip_y1) is a rectangle in canvas
+ * coordinates, the level's image extent: exactly the pixels of a segment inside both the canvas and the rectangle are written --
+ * aligned dword stores where four pixels of a row fall into one 12-byte group, byte stores at a row's ends -- and NOTHING else:
+ * the caller fills the canvas with 255 beforehand, so that what a border tile holds beyond the image stays white.  Segments do
+ * not overlap in a canvas (a page's tiles never do); none is checked.  d_status as bq_jpeg_decode; a segment whose descriptor is
+ * refused (16) writes nothing.  The result is bqio_jpeg_decode_canvas's byte for byte.  Scratch: 128 bytes per 8 x 8 block of a
+ * 4:4:4 segment rounded up to whole 16 x 16 units (393 216 bytes at 256 x 256); bq_jpeg_canvas_scratch_bytes(n, seg_w, seg_h)
+ * asks for min(n, 2048) segments' worth, and the call works in rounds of as many segments as d_scratch holds -- one at least,
+ * BQ_ERR_WORKSPACE below that.  Everything is enqueued on `stream` without a host synchronisation; n = 0 returns 0 without a
+ * launch. */
+size_t bq_jpeg_canvas_scratch_bytes(int n, int seg_w, int seg_h);
+int bq_jpeg_decode_canvas(bq_ctx* ctx, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int seg_w,
+                          int seg_h, const int32_t* d_place, uint8_t* d_canvas, int H, int W, int clip_x0, int clip_y0, int clip_x1,
+                          int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
+
 /* The whole-slide heatmap's input stage (kernels_resample.hip; DESIGN.md "Heatmap input"): n tiles cut out of a slide canvas in
  * device memory and resampled to px x px -- what sf.Heatmap's slide reader does per tile on the host (results.py:217).  d_canvas
  * uint8 [H][W][3]; tile t is the src_px x src_px window at (d_origin[2 t], d_origin[2 t + 1]) = (x, y) (int32; windows may

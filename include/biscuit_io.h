@@ -107,6 +107,35 @@ size_t bqio_jpeg_coef_bytes(int tile_px);
 int bqio_jpeg_decode_extracted(const uint8_t* scan, const uint32_t* desc, const void* tables, int n_tables, int n, int tile_px,
                                uint8_t* out, int32_t* status, int n_threads);
 
+/* A TIFF page's own JPEG tiles for the DEVICE decoder (libbiscuit_hip: bq_jpeg_decode_canvas; DESIGN.md "Heatmap input"):
+ * bqio_extract_jpeg for n raw segments of one page instead of tile records -- segment i = data[off[i] .. off[i] + len[i]) (all
+ * inside data_len bytes, or BQIO_ERR_ARG), every one a seg_w x seg_h frame (the page's TileWidth x TileLength, each <= 4096),
+ * jpeg_tables = the page's JPEGTables tag (NULL / 0: none).  A segment is read as the stream a TIFF reader hands libjpeg: the
+ * tables stream without its trailing EOI, then the segment without its leading SOI, so an abbreviated segment finds the
+ * page's tables and a table the segment defines itself replaces the page's; without JPEGTables the segment must be a complete
+ * stream.  The output -- out_scan, desc, tables, *used, *n_tables, the sizes-only probe with out_scan == NULL, BQIO_ERR_ARG for
+ * too small a cap or table_cap -- is bqio_extract_jpeg's, and so are the refusals, the same header walk: BQIO_ERR_UNSUPPORTED
+ * for anything but three components at 4:4:4 / 4:2:2 / 4:2:0 in one baseline scan, for restart intervals, for a stream
+ * libjpeg would read as RGB or CMYK (by its markers; the TIFF photometric tag is not consulted) and for a scan that is not
+ * clean; BQIO_ERR_FORMAT for a frame that is not seg_w x seg_h (a reader that crops larger frames keeps such a page on the
+ * host).  *bad_index (may be NULL) = the first refused segment. */
+int bqio_extract_jpeg_segments(const uint8_t* data, size_t data_len, const uint64_t* off, const uint64_t* len, int64_t n,
+                               const uint8_t* jpeg_tables, size_t jpeg_tables_len, int seg_w, int seg_h, uint8_t* out_scan, size_t cap,
+                               uint32_t* desc, void* tables, int table_cap, int* n_tables, size_t* used, int n_threads,
+                               int64_t* bad_index);
+
+/* The CPU restatement of bq_jpeg_decode_canvas over the same routines (csrc/jpeg_device.h: entropy_tile, idct_in_place,
+ * place_window, pixel_rgb), the counterpart of bqio_jpeg_decode_extracted: n extracted seg_w x seg_h segments decoded INTO
+ * canvas uint8 [H][W][3].  place int32 [n][2] = the canvas position (x, y) of each segment's top-left pixel, which may be
+ * negative or beyond the canvas; clip int32 [4] = {x0, y0, x1, y1}, a rectangle in canvas coordinates.  Exactly the pixels of a
+ * segment that lie inside both the canvas and the rectangle are written, every other byte of the canvas is left as it is
+ * (the caller fills it beforehand: white, for a slide).  status[n] as bqio_jpeg_decode_extracted; a segment whose descriptor
+ * is refused (16) writes nothing, any other non-zero status leaves bytes that are no image.  Segments must not overlap in the
+ * canvas when n_threads > 1.  BQIO_ERR_ARG: seg_w / seg_h outside 1..4096, H / W outside 1..2^28, a NULL pointer.  For
+ * tests, the sanitizer build and the fuzzer. */
+int bqio_jpeg_decode_canvas(const uint8_t* scan, const uint32_t* desc, const void* tables, int n_tables, int n, int seg_w, int seg_h,
+                            const int32_t* place, uint8_t* canvas, int H, int W, const int32_t* clip, int32_t* status, int n_threads);
+
 /* ---- tile resampling for the whole-slide heatmap (csrc/resample_host.cpp, csrc/resample_device.h) ----
  * The tap tables of Pillow's 8-bit resampler for Image.resize((px, px), Image.LANCZOS) of a src_px x src_px image: per output
  * coordinate i, bounds[2 i] = first source coordinate, bounds[2 i + 1] = number of taps, coef[i * ksize + j] = tap j with 22

@@ -11,7 +11,16 @@ the same bytes.  Per ``--stride-div`` value: ``--runs`` timed calls of ``from_sl
 every result on the host) after one untimed call; the logits / uncertainty arrays are written to ``DIR/arrays_<tag>.npz`` so
 that runs of two trees can be compared.  Then (unless ``--no-kernel``) the resample kernel alone at 302 -> 299 and 604 -> 299 and
 ``Engine.mc_infer`` alone, in tiles a second (device events around 20 launches of one batch).  One JSON object per line on
-stdout and in ``DIR/bench_heatmap_<tag>.jsonl``."""
+stdout and in ``DIR/bench_heatmap_<tag>.jsonl``.
+
+    python tools/bench_heatmap.py --out DIR --decode host --grid 72x56       # the decode leg: a slide of JPEG tiles,
+    python tools/bench_heatmap.py --out DIR --decode gpu --grid 72x56        # decoded by read_region / on the device
+
+``--decode`` times ``from_slide(decode=...)`` on a slide of the same picture written with JPEG tiles (``JPEGTables`` plus
+abbreviated streams, 4:2:0 at level 0, 4:4:4 at level 1; ``OUT/bench_slide_jpeg.svs``) and, walking the same bands stage by stage
+with a device synchronisation behind each, the seconds a band spends in read (+ extract, for 'gpu'; + the host's decode, for
+'host'), upload, device decode, and the rest (the band's share of ``from_slide`` minus those).  Run the two values in separate,
+alternating processes."""
 import argparse
 import json
 import os
@@ -25,13 +34,27 @@ import numpy as np
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def write_slide(path, gw, gh, seed, tile=256, px=302):
+def write_slide(path, gw, gh, seed, tile=256, px=302, jpeg=False):
     """A two-level tiled deflate TIFF with an Aperio description (MPP = 1.0): level 0 of gw x gh tiles' worth of pixels plus
-    a ragged border, level 1 at a quarter of it.  Smooth colour gradients plus seeded noise, a white margin on the right."""
+    a ragged border, level 1 at a quarter of it.  Smooth colour gradients plus seeded noise, a white margin on the right.
+    ``jpeg``: JPEG tiles instead (compression 7: abbreviated streams + JPEGTables, quality 85, 4:2:0 at level 0, 4:4:4 at level 1)."""
     w, h = gw * px + 57, gh * px + 31
     rng = np.random.default_rng(seed)
 
-    def level(lw, lh, f):
+    def encoder(li):
+        if not jpeg:
+            return (lambda t: zlib.compress(t.tobytes(), 1)), None
+        import io
+
+        from PIL import Image
+
+        def enc(t, streamtype=2):
+            b = io.BytesIO()
+            Image.fromarray(t).save(b, format='JPEG', quality=85, subsampling=2 if li == 0 else 0, streamtype=streamtype)
+            return b.getvalue()
+        return enc, enc(np.zeros((tile, tile, 3), np.uint8), 1)
+
+    def level(lw, lh, f, enc):
         segs = []
         xx = np.arange(-(-lw // tile) * tile, dtype=np.float32)[None, :] * f
         for ty in range(-(-lh // tile)):
@@ -42,14 +65,15 @@ def write_slide(path, gw, gh, seed, tile=256, px=302):
             row = np.clip(row, 0, 255).astype(np.uint8)
             row[:, int(0.8 * lw):] = 255
             for tx in range(-(-lw // tile)):
-                segs.append(zlib.compress(row[:, tx * tile:(tx + 1) * tile].tobytes(), 1))
+                segs.append(enc(np.ascontiguousarray(row[:, tx * tile:(tx + 1) * tile])))
         return segs
 
     with open(path, 'wb') as f:
         f.write(b'II' + struct.pack('<HHHQ', 43, 8, 0, 0))                  # BigTIFF
         ptr_at = 8
         for li, (lw, lh, fac) in enumerate(((w, h, 1.0), (w // 4, h // 4, 4.0))):
-            segs = level(lw, lh, fac)
+            enc, tables = encoder(li)
+            segs = level(lw, lh, fac, enc)
             offs = []
             for s in segs:
                 offs.append(f.tell())
@@ -57,15 +81,17 @@ def write_slide(path, gw, gh, seed, tile=256, px=302):
             desc = (b'Aperio synthetic |MPP = 1.0' if li == 0 else b'level') + b'\0'
             blobs = {}
             for tag, data in ((270, desc), (324, struct.pack(f'<{len(offs)}Q', *offs)), (325, struct.pack(f'<{len(segs)}Q', *map(len, segs))),
-                              (258, struct.pack('<3H', 8, 8, 8))):
+                              (258, struct.pack('<3H', 8, 8, 8))) + (((347, tables),) if jpeg else ()):
                 blobs[tag] = (f.tell(), data)
                 f.write(data + b'\0' * (-len(data) % 8))
-            ents = [(256, 4, 1, lw), (257, 4, 1, lh), (258, 3, 3, None), (259, 3, 1, 8), (262, 3, 1, 2), (270, 2, len(desc), None),
+            ents = [(256, 4, 1, lw), (257, 4, 1, lh), (258, 3, 3, None), (259, 3, 1, 7 if jpeg else 8), (262, 3, 1, 6 if jpeg else 2), (270, 2, len(desc), None),
                     (277, 3, 1, 3), (284, 3, 1, 1), (322, 4, 1, tile), (323, 4, 1, tile), (324, 16, len(offs), None), (325, 16, len(segs), None)]
+            if jpeg:
+                ents.append((347, 7, len(tables), None))
             ifd = f.tell()
             f.write(struct.pack('<Q', len(ents)))
             for tag, typ, cnt, val in ents:
-                size = {2: 1, 3: 2, 4: 4, 16: 8}[typ] * cnt
+                size = {2: 1, 3: 2, 4: 4, 7: 1, 16: 8}[typ] * cnt
                 f.write(struct.pack('<HHQ', tag, typ, cnt))
                 if val is not None:
                     f.write(struct.pack('<Q', val))
@@ -82,6 +108,66 @@ def write_slide(path, gw, gh, seed, tile=256, px=302):
     return w, h
 
 
+def decode_leg(args, eng, slide, tag, emit, kw):
+    """``--decode``: from_slide(decode=...) as a whole, then the same bands stage by stage."""
+    import torch
+    from biscuit_amd import tfrecord_native as tn
+    from biscuit_amd.heatmap import Heatmap
+    from biscuit_amd.wsi import WSI
+    dev, sd = eng.device, args.stride_div[0]
+
+    def sync():
+        torch.cuda.synchronize(dev)
+        return time.perf_counter()
+    total = []
+    for r in range(args.runs + 1):                                          # the first call is the warm-up
+        t0 = sync()
+        hm = Heatmap.from_slide(eng, slide, stride_div=sd, decode=args.decode, **kw)
+        if r:
+            total.append(sync() - t0)
+    np.savez(os.path.join(args.out, f'arrays_{tag}.npz'), logits=hm.logits, uncertainty=hm.uncertainty)
+    stages = []                                                             # per run: [read, upload, decode] summed over the bands
+    for r in range(args.runs + 1):
+        w = WSI(slide, stride_div=sd)
+        acc, bands, segments = [0.0, 0.0, 0.0], 0, 0
+        try:
+            for b in w.bands(segments=args.decode == 'gpu'):
+                gy0, gy1, gx0, gx1 = b[:4]
+                t0 = sync()
+                if args.decode == 'gpu':
+                    sg = w.band_segments(gy0, gy1, gx0, gx1)[0]             # (read again: the generator's read is not timed)
+                    scan, desc, tables = tn.extract_jpeg_segments(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h, sg.jpeg_tables)
+                    t1 = time.perf_counter()
+                    up = [torch.from_numpy(a).to(dev) for a in (scan, desc.view(np.int32), tables, sg.place)]
+                    t2 = sync()
+                    canvas = torch.full(tuple(sg.shape) + (3,), 255, dtype=torch.uint8, device=dev)
+                    status = eng.jpeg_decode_canvas(up[0], up[1], up[2], sg.seg_w, sg.seg_h, up[3], canvas, sg.clip)
+                    assert not bool(status.any().item())
+                    t3 = sync()
+                    segments += len(sg)
+                else:
+                    canvas = w.band(gy0, gy1, gx0, gx1)[0]
+                    t1 = time.perf_counter()
+                    canvas = torch.from_numpy(canvas).to(dev)
+                    t3 = t2 = sync()
+                acc = [acc[0] + t1 - t0, acc[1] + t2 - t1, acc[2] + t3 - t2]
+                bands += 1
+                del canvas
+        finally:
+            w.close()
+        if r:
+            stages.append(acc)
+    med = lambda v: float(np.median(v))                                      # noqa: E731
+    per = [med([s[k] for s in stages]) / bands for k in range(3)]
+    tot = med(total) / bands
+    emit({'what': 'decode_leg', 'decode': args.decode, 'stride_div': sd, 'cells': int(hm.logits.shape[0] * hm.logits.shape[1]), 'bands': bands,
+          'segments': segments, 'decode_stats': hm.decode_stats, 'mc': args.mc, 'from_slide_s': [round(t, 4) for t in total],
+          'per_band_s': {'read_extract' if args.decode == 'gpu' else 'read_decode_host': round(per[0], 4), 'upload': round(per[1], 4),
+                         'decode_device': round(per[2], 4), 'rest': round(tot - sum(per), 4), 'total': round(tot, 4)},
+          'per_band_runs_s': [[round(v / bands, 4) for v in s] for s in stages],
+          'spread_total': round((max(total) - min(total)) / med(total), 4)})
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--out', required=True)
@@ -96,14 +182,16 @@ def main():
     ap.add_argument('--mc', type=int, default=30)
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--no-kernel', action='store_true')
+    ap.add_argument('--decode', default=None, choices=['host', 'gpu'],
+                    help='the decode leg only: from_slide(decode=...) on a slide of JPEG tiles, and seconds per band by stage')
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
-    tag = args.tag or args.resample
-    slide = args.slide or os.path.join(args.out, 'bench_slide.svs')
+    tag = args.tag or (args.resample if args.decode is None else 'decode_' + args.decode)
+    slide = args.slide or os.path.join(args.out, 'bench_slide.svs' if args.decode is None else 'bench_slide_jpeg.svs')
     gw, gh = (int(v) for v in args.grid.lower().split('x'))
     if not os.path.exists(slide):
         t0 = time.perf_counter()
-        write_slide(slide, gw, gh, args.seed)
+        write_slide(slide, gw, gh, args.seed, jpeg=args.decode is not None)
         print(json.dumps({'slide': slide, 'bytes': os.path.getsize(slide), 'written_in_s': round(time.perf_counter() - t0, 2)}), flush=True)
     sys.path.insert(0, os.path.abspath(args.root))
     import torch
@@ -120,6 +208,10 @@ def main():
 
     eng = Engine(synthetic_weights(1), dtype='f16', max_batch=args.batch, max_mc=args.mc)
     kw = dict(mc_n=args.mc, seed=0, batch=args.batch)
+    if args.decode is not None:
+        decode_leg(args, eng, slide, tag, emit, kw)
+        eng.close()
+        return
     if args.resample != 'default':
         kw['resample'] = args.resample
     arrays = {}
