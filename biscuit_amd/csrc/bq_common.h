@@ -142,6 +142,9 @@ long long resample_grid(int n, int src_px, int px, int ksize);
 int launch_tile_resample(const uint8_t* canvas, int H, int W, const int* origin, int n, int src_px, int px, const int* bounds,
                          const int* coef, int ksize, uint8_t* out, hipStream_t s);
 int launch_tile_grayspace(const uint8_t* tiles, int n, int px, const int* limit256, int* count, hipStream_t s);
+// kernels_render.hip: one plane of the heatmap grid drawn over the slide's thumbnail through a colour table (DESIGN.md "Heatmap output")
+int launch_heatmap_render(const float* values, int gh, int gw, const int32_t* col, const int32_t* row, int bicubic, const uint8_t* lut,
+                          const uint8_t* thumb, uint8_t* out, int H, int W, float vmin, float inv, int A, hipStream_t s);
 int launch_stem1(const void* in_nchw, int n, const float* w27x32, const float* scale,
                  const float* bias, void* out_nhwc, int dtype, hipStream_t s);
 int launch_pool_add(const void* y, const void* res, void* out, int n, int Hi, int Wi, int C,

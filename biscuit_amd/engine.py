@@ -322,6 +322,36 @@ class Engine:
                                                 self._stream()))
         return count
 
+    def heatmap_render(self, values, col_table, row_table, lut, thumb, vmin=0.0, vmax=1.0, alpha=0.6, interpolation='none', out=None):
+        """One plane of the heatmap grid drawn over the slide's thumbnail (``bq_heatmap_render``, kernels_render.hip; DESIGN.md
+        "Heatmap output"): ``values`` float32 [gh, gw] (a cell that holds -1 or a non-finite value is transparent), ``col_table``
+        / ``row_table`` int32 as ``render.render_tables`` builds them for ``interpolation`` ('none': [W] / [H]; 'bicubic': [W, 9]
+        / [H, 9]), ``lut`` uint8 [256, 3] and ``thumb`` uint8 [H, W, 3] -- all on this device -> uint8 [H, W, 3], the bytes of
+        the numpy restatement.  ``out``: a contiguous [H, W, 3] uint8 tensor to write into; it may be ``thumb`` itself (in place)
+        and must not overlap it otherwise.  ValueError for ``vmin >= vmax``, a non-finite bound, ``alpha`` outside [0, 1], a
+        table of the wrong shape or an unknown interpolation (``render.check_params``)."""
+        from . import render
+        lo, inv, a256, mode = render.check_params(vmin, vmax, alpha, interpolation)
+        for t in (values, col_table, row_table, lut, thumb):
+            assert t.is_cuda and t.is_contiguous()
+        if values.dtype != torch.float32 or values.dim() != 2 or values.numel() == 0:
+            raise ValueError('values must be float32 [gh, gw]')
+        if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+            raise ValueError(f'a colour table is uint8 [256, 3], not {lut.dtype} {list(lut.shape)}')
+        if thumb.dtype != torch.uint8 or thumb.dim() != 3 or thumb.shape[2] != 3:
+            raise ValueError('thumb must be uint8 [H, W, 3]')
+        h, w = int(thumb.shape[0]), int(thumb.shape[1])
+        want = ((w,), (h,)) if mode == 0 else ((w, render.RENDER_ENTRY), (h, render.RENDER_ENTRY))
+        if col_table.dtype != torch.int32 or row_table.dtype != torch.int32 or (tuple(col_table.shape), tuple(row_table.shape)) != want:
+            raise ValueError(f'the tables of a {h} x {w} {interpolation!r} render are int32 {list(want[0])} and {list(want[1])}')
+        if out is None:
+            out = torch.empty_like(thumb)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.shape == thumb.shape
+        self._check(self._lib.bq_heatmap_render(self._ctx, _ptr(values), int(values.shape[0]), int(values.shape[1]), _ptr(col_table),
+                                                _ptr(row_table), mode, _ptr(lut), _ptr(thumb), _ptr(out), h, w, float(lo), float(inv),
+                                                a256, self._stream()))
+        return out
+
     def reinhard_fast(self, tiles_u8, target_means, target_stds, out=None):
         """`reinhard_fast` stain normalisation (hp.py:19; results.py:251-252 `wsi_normalizer.rgb_to_rgb`):
         uint8 NHWC [n,299,299,3] -> uint8 NHWC.  target_means/target_stds: the CIE-LAB `norm_fit` of the

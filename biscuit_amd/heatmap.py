@@ -11,6 +11,12 @@ round 6) -- and lays the same MC-dropout kernels' outputs out as the two grids t
     hm.uncertainty  [gy, gx, 2]   their population std
 
 Grid cells without a tile hold -1, the value results.py:225 also writes into masked cells.
+
+The picture of Figure 5a (results.py:216-227: ``hm.save(dir, cmap=truncate_colormap(PRGn, 0.1, 0.9))``, once for the full map and
+once after the uncertain cells are set to -1) is ``Heatmap.render`` / ``Heatmap.save``: one plane of a grid drawn over the slide's
+thumbnail (``wsi.WSI.thumbnail``) through a 256-entry colour table by ``Engine.heatmap_render`` (csrc/kernels_render.hip), masked
+cells transparent, written as PNGs through Pillow.  DESIGN.md "Heatmap output" states what is drawn; ``render.py`` holds the host
+side (geometry tables, colour table, checks).
 """
 import numpy as np
 import torch
@@ -41,6 +47,10 @@ def tile_grid(region, tile_px=299, stride_div=1):
 
 
 class Heatmap:
+    # what ``render`` needs to place the grid on the slide; ``from_slide`` records them, the other constructors have no slide
+    slide_path = slide_w0 = slide_h0 = stride = extract_px = None
+    _slide_kw = None
+
     def __init__(self, engine, tiles, grid, grid_shape=None, mc_n=30, seed=0, batch=256, norm_fit=None, normalizer='reinhard_fast'):
         """tiles: uint8 [T,299,299,3] (host or device); grid: int [T,2] (gx, gy) cell of each tile.  ``norm_fit`` / ``normalizer``:
         the model's stain normaliser (stain.METHODS; ``norm_fit=None``: none)."""
@@ -123,8 +133,12 @@ class Heatmap:
                 raise ValueError(f'{path}: the slide holds no {tile_um} um tile')
             if resample == 'host':
                 tiles, grid = w.tiles()
-                return cls(engine, tiles, grid, grid_shape=(w.grid_h, w.grid_w), **kw)
-            return cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, decode=decode, **kw)
+                hm = cls(engine, tiles, grid, grid_shape=(w.grid_h, w.grid_w), **kw)
+            else:
+                hm = cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, decode=decode, **kw)
+            hm.slide_path, (hm.slide_w0, hm.slide_h0), hm.stride, hm.extract_px = path, w.slide.dimensions, w.stride, w.extract_px
+            hm._slide_kw = dict(tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
+            return hm
         finally:
             w.close()
 
@@ -218,6 +232,108 @@ class Heatmap:
         hm.grid = np.stack([cells % gw, cells // gw], 1)
         return hm
 
+    # ---- the picture (results.py:216-227; DESIGN.md "Heatmap output") -----------------------------------------------------------
+    def _plane(self, plane, index):
+        if isinstance(plane, str):
+            if plane not in ('logits', 'uncertainty'):
+                raise ValueError(f"plane must be 'logits', 'uncertainty' or a float32 [gh, gw] array, not {plane!r}")
+            src = getattr(self, plane)
+            if not 0 <= int(index) < src.shape[2]:
+                raise ValueError(f'{plane} has planes 0 .. {src.shape[2] - 1}, not {index}')
+            return np.ascontiguousarray(src[:, :, int(index)], np.float32)
+        v = np.ascontiguousarray(plane, np.float32)
+        if v.shape != self.logits.shape[:2]:
+            raise ValueError(f'a plane of this heatmap is [{self.logits.shape[0]}, {self.logits.shape[1]}], not {list(v.shape)}')
+        return v
+
+    def thumbnail(self, width=2048):
+        """The slide's thumbnail (``wsi.WSI.thumbnail``), for a heatmap ``from_slide`` built."""
+        from .wsi import WSI
+        if self.slide_path is None:
+            raise ValueError('this heatmap was not built from a slide file (from_slide): pass thumb=')
+        w = WSI(self.slide_path, **self._slide_kw)
+        try:
+            return w.thumbnail(width)
+        finally:
+            w.close()
+
+    def render(self, engine, plane='logits', index=0, thumb=None, cmap=None, vmin=0.0, vmax=1.0, alpha=0.6, interpolation='none',
+               width=2048, slide_w0=None, slide_h0=None, stride=None, extract_px=None):
+        """One plane of the heatmap drawn over the slide's thumbnail -> uint8 [H, W, 3] (DESIGN.md "Heatmap output"):
+        ``plane`` / ``index`` name ``hm.logits[:, :, index]`` or ``hm.uncertainty[:, :, index]`` (``plane`` may also be a float32
+        [gh, gw] array); ``thumb`` uint8 [H, W, 3] (None: the slide's ``thumbnail(width)`` is read); ``cmap`` a uint8 [256, 3]
+        table or a matplotlib colormap (None: ``render.PRGN_TRUNC``, the reference's); values are mapped from [``vmin``,
+        ``vmax``]; ``alpha`` is the overlay's weight; ``interpolation`` 'none' or 'bicubic'.  Cells that hold -1 or a non-finite
+        value stay transparent.  A heatmap built by ``Heatmap(...)`` or ``from_region`` has no slide: it needs ``thumb`` and
+        the four geometry numbers ``slide_w0``, ``slide_h0``, ``stride``, ``extract_px`` (level-0 pixels) as keywords."""
+        from . import render as R
+        R.check_params(vmin, vmax, alpha, interpolation)
+        lut = R.lut_from(cmap)
+        values = self._plane(plane, index)
+        geom = {'slide_w0': slide_w0, 'slide_h0': slide_h0, 'stride': stride, 'extract_px': extract_px}
+        geom = {k: getattr(self, k) if v is None else v for k, v in geom.items()}
+        missing = [k for k, v in geom.items() if v is None]
+        if missing:
+            raise ValueError('this heatmap was not built from a slide file (from_slide): render needs thumb= and the geometry '
+                             f'keywords slide_w0, slide_h0, stride, extract_px; missing: {", ".join(missing)}')
+        if thumb is None:
+            thumb = self.thumbnail(width)
+        thumb = np.ascontiguousarray(thumb)
+        if thumb.dtype != np.uint8 or thumb.ndim != 3 or thumb.shape[2] != 3:
+            raise ValueError('thumb must be uint8 [H, W, 3]')
+        gh, gw = values.shape
+        col, row = R.render_tables(gw, gh, thumb.shape[1], thumb.shape[0], interpolation=interpolation, **geom)
+        dev = engine.device
+
+        def up(a):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)              # (a Pillow array is read-only)
+        d_thumb = up(thumb)
+        out = engine.heatmap_render(up(values), up(col), up(row), up(lut), d_thumb, vmin=vmin, vmax=vmax, alpha=alpha,
+                                    interpolation=interpolation, out=d_thumb)
+        return out.cpu().numpy()
+
+    def save(self, engine, outdir, name=None, tile_uq_thresh=None, uncertainty_vmax=None, **render_kw):
+        """``hm.save(dir, cmap=...)`` (results.py:219, 227) as PNGs through Pillow: ``<name>-raw.png`` (the thumbnail),
+        ``<name>-0.png`` and ``<name>-1.png`` (the two planes of ``logits``) and ``<name>-uncertainty.png`` (``uncertainty[:, :,
+        0]`` over [0, ``uncertainty_vmax``]; default: its largest live value, 1 when no live value is positive); with
+        ``tile_uq_thresh`` also ``high_confidence/<name>-0.png`` and ``-1.png`` from a COPY of the logits with the cells whose
+        ``uncertainty[:, :, 0]`` exceeds the threshold set to -1 (results.py:222-225) -- ``hm.logits`` is not touched.  ``name``
+        defaults to the slide file's name without its extension.  ``render_kw``: ``render``'s keywords.  -> the paths written."""
+        import os
+        from PIL import Image
+        if name is None:
+            name = os.path.splitext(os.path.basename(str(self.slide_path)))[0] if self.slide_path is not None else 'heatmap'
+        kw = dict(render_kw)
+        for k in ('plane', 'index'):
+            if k in kw:
+                raise ValueError(f'save draws every plane: {k}= is not one of its keywords')
+        if kw.get('thumb') is None:
+            kw['thumb'] = self.thumbnail(kw.get('width', 2048))
+        thumb = np.ascontiguousarray(kw['thumb'])
+        paths = []
+
+        def write(sub, suffix, img):
+            d = os.path.join(outdir, sub) if sub else outdir
+            os.makedirs(d, exist_ok=True)
+            paths.append(os.path.join(d, f'{name}-{suffix}.png'))
+            Image.fromarray(img).save(paths[-1])
+
+        write('', 'raw', thumb)
+        for c in (0, 1):
+            write('', str(c), self.render(engine, 'logits', c, **kw))
+        unc = self.uncertainty[:, :, 0]
+        live = unc[np.isfinite(unc) & (unc != MASKED)]
+        if uncertainty_vmax is None:
+            uncertainty_vmax = float(live.max()) if live.size and float(live.max()) > 0.0 else 1.0
+        write('', 'uncertainty', self.render(engine, 'uncertainty', 0, **dict(kw, vmin=0.0, vmax=uncertainty_vmax)))
+        if tile_uq_thresh is not None:
+            masked = self.logits.copy()
+            masked[unc > tile_uq_thresh, :] = [MASKED, MASKED]
+            for c in (0, 1):
+                write('high_confidence', str(c), self.render(engine, masked[:, :, c], **kw))
+        return paths
+
     def mask_uncertain(self, tile_uq_thresh):
         """results.py:224-225: ``uq_mask = hm.uncertainty[:, :, 0] > thresh; hm.logits[uq_mask, :] = [-1, -1]``.
         Returns the mask."""
@@ -239,7 +355,9 @@ def main(argv=None):
     """``python -m biscuit_amd.heatmap SLIDE --out DIR``: the UQ heatmap of one slide file (results.py:216-265) on disk --
     ``DIR/heatmap.npz`` (``logits``, ``uncertainty``, ``grid``; with ``--tile-uq`` also ``uq_mask`` and ``masked_logits``, the
     logits with the uncertain cells set to -1 as results.py:222-225 does), ``DIR/summary.json`` and, with ``--save-tiles``, the
-    tiles as ``uq_incl/`` / ``uq_excl/`` PNGs named as results.py:259 names them."""
+    tiles as ``uq_incl/`` / ``uq_excl/`` PNGs named as results.py:259 names them.  ``--render`` adds the pictures of
+    ``Heatmap.save`` (results.py:217-227): ``<slide>-raw.png``, ``-0.png``, ``-1.png``, ``-uncertainty.png`` and, with ``--tile-uq``,
+    the masked pair under ``high_confidence/``; ``summary.json`` then lists them as ``rendered``."""
     import argparse
     import json
     import os
@@ -264,6 +382,11 @@ def main(argv=None):
                     help="decode the slide's own JPEG tiles on the device (from_slide(decode='gpu')); the arrays do not change")
     ap.add_argument('--mpp', type=float, default=None, help='microns per pixel, for a file that does not say')
     ap.add_argument('--save-tiles', action='store_true', help='write the tiles to uq_incl/ and uq_excl/ (needs --tile-uq)')
+    ap.add_argument('--render', action='store_true',
+                    help='write the heatmap as PNGs over the slide thumbnail (Heatmap.save); with --tile-uq also high_confidence/')
+    ap.add_argument('--render-interpolation', default='none', choices=['none', 'bicubic'])
+    ap.add_argument('--render-width', type=int, default=2048, help='thumbnail width in pixels')
+    ap.add_argument('--render-alpha', type=float, default=0.6, help='weight of the overlay, 0 .. 1')
     args = ap.parse_args(argv)
     if args.save_tiles and args.tile_uq is None:
         ap.error('--save-tiles sorts by --tile-uq')
@@ -281,6 +404,11 @@ def main(argv=None):
                                 decode='gpu' if args.gpu_decode else 'host')
         torch.cuda.synchronize(eng.device)
         seconds = time.perf_counter() - t0
+        rendered = None
+        if args.render:                                                  # (after the clock: the engine stays open for it)
+            paths = hm.save(eng, args.out, tile_uq_thresh=args.tile_uq, interpolation=args.render_interpolation,
+                            width=args.render_width, alpha=args.render_alpha)
+            rendered = [os.path.relpath(p, args.out) for p in paths]
     finally:
         eng.close()
     os.makedirs(args.out, exist_ok=True)
@@ -305,6 +433,8 @@ def main(argv=None):
     run = int(len(hm.grid))
     summary = {'slide': args.slide, 'grid_shape': list(hm.logits.shape[:2]), 'tiles_run': run, 'tiles_dropped': int(hm.dropped),
                'seconds': seconds, 'tiles_per_s': run / seconds if seconds > 0 else None, 'decode_stats': hm.decode_stats}
+    if rendered is not None:
+        summary['rendered'] = rendered
     with open(os.path.join(args.out, 'summary.json'), 'w') as f:
         json.dump(summary, f)
     print(json.dumps(summary))

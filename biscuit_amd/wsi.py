@@ -497,5 +497,30 @@ class WSI:
                     yield (gy0, gy1, a, b, None) + self._band_rect(gy0, gy1, a, b)[1:]
             gy0 = gy1
 
+    # ---- the picture under a rendered heatmap (heatmap.Heatmap.render) --------------------------------------------------------
+    @_guard
+    def thumbnail(self, width=2048):
+        """The slide as one uint8 [H, W, 3] picture ``width`` pixels wide (DESIGN.md "Heatmap output"): the coarsest pyramid level
+        that is still at least ``width`` wide (level 0 if none is), read whole in pieces of at most ``READ_LIMIT`` pixels a side
+        and reduced to ``(width, round(h * width / w))`` with Pillow's LANCZOS.  A slide narrower than ``width`` is not
+        upsampled: the thumbnail is then level 0 itself.  (Unpinned like ``_tile``: not the libvips resampler Slideflow uses.)"""
+        from PIL import Image
+        width = int(width)
+        if width < 1:
+            raise SlideError(f'thumbnail of width {width}')
+        dims = self.slide.level_dimensions
+        ok = [i for i, (w, _) in enumerate(dims) if w >= width]
+        li = min(ok, key=lambda i: dims[i][0]) if ok else 0
+        w, h = dims[li]
+        img = np.empty((h, w, 3), np.uint8)
+        step = self.READ_LIMIT
+        for y in range(0, h, step):
+            for x in range(0, w, step):
+                ph, pw = min(step, h - y), min(step, w - x)
+                img[y:y + ph, x:x + pw] = self.slide.read_region(li, x, y, pw, ph)
+        if w <= width:
+            return img
+        return np.asarray(Image.fromarray(img).resize((width, max(1, int(round(h * width / w)))), Image.LANCZOS))
+
     def close(self):
         self.slide.close()

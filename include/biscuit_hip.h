@@ -239,6 +239,25 @@ int bq_tile_resample(bq_ctx* ctx, const uint8_t* d_canvas, int H, int W, const i
 int bq_tile_grayspace(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, int px, const int32_t* d_limit256, int32_t* d_count,
                       bq_stream_t stream);
 
+/* The whole-slide heatmap's output stage (kernels_render.hip; DESIGN.md "Heatmap output"): one plane of the grid drawn over the
+ * slide's thumbnail through a colour table -- the picture sf.Heatmap(...).save(dir, cmap=...) writes on the host, for the full map
+ * and again after the uncertain cells are set to -1 (results.py:217-227).  d_values float32 [gh][gw] (hm.logits[:, :, c] or
+ * hm.uncertainty[:, :, c]); a cell whose value is -1 or not finite is transparent.  d_col / d_row are render.render_tables'
+ * tables, one entry per output column / row, built on the host in float64 -- the kernel does no coordinate arithmetic:
+ * interpolation 0 ('none'): int32 [W] / [H], the pixel's cell or -1; interpolation 1 ('bicubic'): int32 [W][9] / [H][9] = the
+ * pixel's cell or -1, four tap cells clamped to the grid and four Catmull-Rom weights with 12 fractional bits that sum to 4096.
+ * d_lut uint8 [256][3]; d_thumb, d_out uint8 [H][W][3] (row pitch 3 W, any alignment); d_out may be d_thumb (in place), otherwise
+ * the two must not overlap.  Per cell q = clamp(floor(((v - vmin) * inv_span) * 65536), 0, 65535) with the float32 subtraction
+ * and multiplication un-fused; 'none' takes lut[q >> 8] of the pixel's cell; 'bicubic' the weighted mean of q over the live taps
+ * in 64-bit integers, rounded, clamped (the pixel's own q where the live weights do not sum above 0); a pixel whose own cell is
+ * transparent, or that has none, keeps the thumbnail's bytes.  Blend per channel: (A colour + (256 - A) thumb + 128) >> 8, A in
+ * [0, 256].  Cell indices are device memory and are clamped to the grid, not checked.  0 < gh, gw <= 32768, 0 < H, W <= 16384,
+ * vmin finite, inv_span = 1 / (vmax - vmin) a normal positive float32.  Allocates nothing; enqueued on `stream` without a host
+ * synchronisation; a bad argument is BQ_ERR_ARG with nothing enqueued. */
+int bq_heatmap_render(bq_ctx* ctx, const float* d_values, int gh, int gw, const int32_t* d_col_table, const int32_t* d_row_table,
+                      int interpolation, const uint8_t* d_lut, const uint8_t* d_thumb, uint8_t* d_out, int H, int W, float vmin,
+                      float inv_span, int A, bq_stream_t stream);
+
 /* Variant for callers that already hold standardised float32 NHWC tiles (the
  * UncertaintyInterface contract, results.py:256-257): converts to planar NCHW. */
 int bq_stage_f32(bq_ctx* ctx, const float* d_tiles_nhwc_f32, int n, void* d_out_nchw,

@@ -20,7 +20,13 @@ stdout and in ``DIR/bench_heatmap_<tag>.jsonl``.
 abbreviated streams, 4:2:0 at level 0, 4:4:4 at level 1; ``OUT/bench_slide_jpeg.svs``) and, walking the same bands stage by stage
 with a device synchronisation behind each, the seconds a band spends in read (+ extract, for 'gpu'; + the host's decode, for
 'host'), upload, device decode, and the rest (the band's share of ``from_slide`` minus those).  Run the two values in separate,
-alternating processes."""
+alternating processes.
+
+    python tools/bench_heatmap.py --out DIR --render                         # the render leg: no slide, no inference
+
+``--render`` times ``Engine.heatmap_render`` alone (device events around 20 launches, out of place) on a 100 x 100 grid with a
+tenth of its cells masked under a 2 048 x 1 536 thumbnail, in both interpolation modes, next to the wall time of the numpy
+restatement (``tests/_render_ref.py``) on the same inputs, and checks that the two pictures are equal."""
 import argparse
 import json
 import os
@@ -168,6 +174,41 @@ def decode_leg(args, eng, slide, tag, emit, kw):
           'spread_total': round((max(total) - min(total)) / med(total), 4)})
 
 
+def render_leg(args, eng, emit):
+    """``--render``: the kernel's milliseconds per picture and the numpy restatement's, same inputs, same bytes."""
+    import torch
+    sys.path.insert(0, HERE)
+    from biscuit_amd import render as R
+    from tests import _render_ref as ref
+    rng = np.random.default_rng(args.seed)
+    gw = gh = 100
+    W, H = 2048, 1536
+    geom = dict(slide_w0=gw * 302 + 57, slide_h0=gh * 302 + 31, stride=302, extract_px=302)
+    values = rng.uniform(0, 1, (gh, gw)).astype(np.float32)
+    values[rng.uniform(0, 1, (gh, gw)) < 0.1] = R.MASKED
+    thumb = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(eng.device)                    # noqa: E731
+    d_values, d_lut, d_thumb, out = up(values), up(R.PRGN_TRUNC), up(thumb), torch.empty((H, W, 3), dtype=torch.uint8, device=eng.device)
+    for mode in R.INTERPOLATIONS:
+        col, row = (up(t) for t in R.render_tables(gw, gh, W, H, interpolation=mode, **geom))
+        fn = lambda: eng.heatmap_render(d_values, col, row, d_lut, d_thumb, interpolation=mode, out=out)   # noqa: E731
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = 20
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        b.synchronize()
+        t0 = time.perf_counter()
+        want = ref.render(values, thumb, R.PRGN_TRUNC, interpolation=mode, **geom)
+        numpy_s = time.perf_counter() - t0
+        emit({'what': 'heatmap_render', 'interpolation': mode, 'grid': [gh, gw], 'thumb': [H, W], 'masked_cells': int((values == R.MASKED).sum()),
+              'device_ms': round(a.elapsed_time(b) / reps, 4), 'numpy_ms': round(numpy_s * 1e3, 1),
+              'equal': bool(np.array_equal(out.cpu().numpy(), want))})
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--out', required=True)
@@ -184,12 +225,13 @@ def main():
     ap.add_argument('--no-kernel', action='store_true')
     ap.add_argument('--decode', default=None, choices=['host', 'gpu'],
                     help='the decode leg only: from_slide(decode=...) on a slide of JPEG tiles, and seconds per band by stage')
+    ap.add_argument('--render', action='store_true', help='the render leg only: Engine.heatmap_render next to its numpy restatement')
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
-    tag = args.tag or (args.resample if args.decode is None else 'decode_' + args.decode)
+    tag = args.tag or ('render' if args.render else args.resample if args.decode is None else 'decode_' + args.decode)
     slide = args.slide or os.path.join(args.out, 'bench_slide.svs' if args.decode is None else 'bench_slide_jpeg.svs')
     gw, gh = (int(v) for v in args.grid.lower().split('x'))
-    if not os.path.exists(slide):
+    if not os.path.exists(slide) and not args.render:
         t0 = time.perf_counter()
         write_slide(slide, gw, gh, args.seed, jpeg=args.decode is not None)
         print(json.dumps({'slide': slide, 'bytes': os.path.getsize(slide), 'written_in_s': round(time.perf_counter() - t0, 2)}), flush=True)
@@ -208,6 +250,10 @@ def main():
 
     eng = Engine(synthetic_weights(1), dtype='f16', max_batch=args.batch, max_mc=args.mc)
     kw = dict(mc_n=args.mc, seed=0, batch=args.batch)
+    if args.render:
+        render_leg(args, eng, emit)
+        eng.close()
+        return
     if args.decode is not None:
         decode_leg(args, eng, slide, tag, emit, kw)
         eng.close()
