@@ -1113,6 +1113,39 @@ int bq_heatmap_render(bq_ctx* c, const float* d_values, int gh, int gw, const in
     return BQ_OK;
 }
 
+int bq_tissue_blur(bq_ctx* c, const uint8_t* d_thumb, int H, int W, const int32_t* d_sdiv256, uint8_t* d_plane, int32_t* d_hist,
+                   bq_stream_t stream) {
+    if (!c || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31))
+        return fail(c, BQ_ERR_ARG, "bq_tissue_blur: bad argument (need 0 < H, W and H * W < 2^31)");
+    if (!d_thumb || !d_sdiv256 || !d_plane || !d_hist || ((uintptr_t)d_sdiv256 & 3) || ((uintptr_t)d_hist & 3))
+        return fail(c, BQ_ERR_ARG, "bq_tissue_blur: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tissue_blur", 0.0, 4.0 * (double)H * W);
+    if (launch_tissue_blur(d_thumb, H, W, d_sdiv256, d_plane, d_hist, s)) return fail(c, BQ_ERR_HIP, "tissue blur launch failed");
+    return BQ_OK;
+}
+
+int bq_tissue_cells(bq_ctx* c, const uint8_t* d_plane, int H, int W, int T, const int32_t* col_ranges, int gw, const int32_t* row_ranges,
+                    int gh, int32_t* d_ranges, int32_t* d_count, bq_stream_t stream) {
+    if (!c || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31) || gw <= 0 || gh <= 0 || gw > (1 << 15) || gh > (1 << 15) || T < 0 || T > 255)
+        return fail(c, BQ_ERR_ARG, "bq_tissue_cells: bad argument (need 0 < H, W, H * W < 2^31, 0 < gw, gh <= 32768 and 0 <= T <= 255)");
+    if (!d_plane || !col_ranges || !row_ranges || !d_ranges || !d_count || ((uintptr_t)d_ranges & 3) || ((uintptr_t)d_count & 3))
+        return fail(c, BQ_ERR_ARG, "bq_tissue_cells: bad argument");
+    for (int i = 0; i < gw; ++i)
+        if (col_ranges[2 * i] < 0 || col_ranges[2 * i] >= col_ranges[2 * i + 1] || col_ranges[2 * i + 1] > W)
+            return fail(c, BQ_ERR_ARG, "bq_tissue_cells: a column range is empty or outside the plane");
+    for (int i = 0; i < gh; ++i)
+        if (row_ranges[2 * i] < 0 || row_ranges[2 * i] >= row_ranges[2 * i + 1] || row_ranges[2 * i + 1] > H)
+            return fail(c, BQ_ERR_ARG, "bq_tissue_cells: a row range is empty or outside the plane");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tissue_cells", 0.0, (double)H * W);
+    HIPCHK(c, hipMemcpyAsync(d_ranges, col_ranges, (size_t)gw * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_ranges + 2 * gw, row_ranges, (size_t)gh * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (launch_tissue_cells(d_plane, H, W, T, d_ranges, d_ranges + 2 * gw, gw, gh, d_count, s))
+        return fail(c, BQ_ERR_HIP, "tissue cells launch failed");
+    return BQ_OK;
+}
+
 int bq_png_unfilter_strided(bq_ctx* c, const uint8_t* d_rows, size_t rows_stride, int n, int px, uint8_t* d_out, bq_stream_t stream) {
     if (!c || !d_rows || !d_out || n < 0 || px <= 0) return fail(c, BQ_ERR_ARG, "bq_png_unfilter_strided: bad argument");
     if (launch_png_unfilter(d_rows, n, px, d_out, (hipStream_t)stream, rows_stride)) return fail(c, BQ_ERR_HIP, "png unfilter launch failed");

@@ -145,6 +145,11 @@ int launch_tile_grayspace(const uint8_t* tiles, int n, int px, const int* limit2
 // kernels_render.hip: one plane of the heatmap grid drawn over the slide's thumbnail through a colour table (DESIGN.md "Heatmap output")
 int launch_heatmap_render(const float* values, int gh, int gw, const int32_t* col, const int32_t* row, int bicubic, const uint8_t* lut,
                           const uint8_t* thumb, uint8_t* out, int H, int W, float vmin, float inv, int A, hipStream_t s);
+// kernels_tissue.hip: the tissue mask on the slide's thumbnail (DESIGN.md "Heatmap input", Tissue mask): the 7 x 7 median of the
+// 8-bit saturation with its histogram, and the background pixels of every grid cell
+int launch_tissue_blur(const uint8_t* thumb, int H, int W, const int* sdiv256, uint8_t* plane, int* hist, hipStream_t s);
+int launch_tissue_cells(const uint8_t* plane, int H, int W, int T, const int* col, const int* row, int gw, int gh, int* count,
+                        hipStream_t s);
 int launch_stem1(const void* in_nchw, int n, const float* w27x32, const float* scale,
                  const float* bias, void* out_nhwc, int dtype, hipStream_t s);
 int launch_pool_add(const void* y, const void* res, void* out, int n, int Hi, int Wi, int C,

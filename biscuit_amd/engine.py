@@ -80,6 +80,8 @@ class Engine:
         self._ws = self._inflate_ws = self._jpeg_ws = None        # device buffers grown on demand (``_grown``)
         self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
         self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
+        self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
+        self._tissue_host = None         # the range tables of the last tissue_cells call, alive while the stream copies them
         self._elt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[dtype]
 
     # shapes of the stored tensors by debug-tap name
@@ -351,6 +353,51 @@ class Engine:
                                                 _ptr(row_table), mode, _ptr(lut), _ptr(thumb), _ptr(out), h, w, float(lo), float(inv),
                                                 a256, self._stream()))
         return out
+
+    def tissue_blur(self, thumb_u8):
+        """The tissue mask's first stage (``bq_tissue_blur``, kernels_tissue.hip; DESIGN.md "Heatmap input", Tissue mask): the
+        slide's thumbnail uint8 [H, W, 3] on this device -> (plane uint8 [H, W], the 7 x 7 median of its 8-bit saturation with a
+        replicated border, and hist int32 [256], the plane's histogram), both on the device, the integers of the numpy
+        restatement.  ``H * W < 2^31``; H or W below 7 are legal."""
+        if not (torch.is_tensor(thumb_u8) and thumb_u8.dtype == torch.uint8 and thumb_u8.dim() == 3 and thumb_u8.shape[2] == 3):
+            raise ValueError('thumb must be uint8 [H, W, 3]')
+        assert thumb_u8.is_cuda and thumb_u8.is_contiguous()
+        h, w = int(thumb_u8.shape[0]), int(thumb_u8.shape[1])
+        if h < 1 or w < 1 or h * w >= 1 << 31:
+            raise ValueError(f'a thumbnail has 1 <= H, W and H * W < 2^31, not {h} x {w}')
+        if self._tissue_sdiv is None:
+            from . import tissue
+            self._tissue_sdiv = torch.from_numpy(tissue.sdiv_table()).to(self.device)
+        plane = torch.empty((h, w), dtype=torch.uint8, device=self.device)
+        hist = torch.empty(256, dtype=torch.int32, device=self.device)
+        self._check(self._lib.bq_tissue_blur(self._ctx, _ptr(thumb_u8), h, w, _ptr(self._tissue_sdiv), _ptr(plane), _ptr(hist),
+                                             self._stream()))
+        return plane, hist
+
+    def tissue_cells(self, plane, T, col, row):
+        """The tissue mask's second stage (``bq_tissue_cells``): ``plane`` uint8 [H, W] on this device (``tissue_blur``'s), the
+        threshold ``T`` in 0 .. 255 and the cells' ranges ``col`` int32 [gw, 2] / ``row`` int32 [gh, 2] in plane pixels
+        (``tissue.cell_ranges``; host arrays) -> int32 [gh, gw] on the device: the pixels with ``plane <= T`` in every cell.
+        ValueError for a range that is empty or leaves the plane."""
+        if not (torch.is_tensor(plane) and plane.dtype == torch.uint8 and plane.dim() == 2 and plane.numel() > 0):
+            raise ValueError('plane must be uint8 [H, W]')
+        assert plane.is_cuda and plane.is_contiguous()
+        h, w = int(plane.shape[0]), int(plane.shape[1])
+        col, row = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(row, np.int32)
+        if col.ndim != 2 or col.shape[1] != 2 or row.ndim != 2 or row.shape[1] != 2 or len(col) < 1 or len(row) < 1:
+            raise ValueError('col and row must be int32 [gw, 2] and [gh, 2]')
+        if not 0 <= int(T) <= 255:
+            raise ValueError(f'T must lie in 0 .. 255, not {T!r}')
+        for name, r, n in (('col', col, w), ('row', row, h)):
+            if (r[:, 0] < 0).any() or (r[:, 0] >= r[:, 1]).any() or (r[:, 1] > n).any():
+                raise ValueError(f'a {name} range is empty or outside the {h} x {w} plane')
+        gw, gh = len(col), len(row)
+        ranges = torch.empty(2 * (gw + gh), dtype=torch.int32, device=self.device)
+        count = torch.empty((gh, gw), dtype=torch.int32, device=self.device)
+        self._tissue_host = (col, row)                                      # the host tables live until the stream has copied them
+        self._check(self._lib.bq_tissue_cells(self._ctx, _ptr(plane), h, w, int(T), col.ctypes.data, gw, row.ctypes.data, gh,
+                                              _ptr(ranges), _ptr(count), self._stream()))
+        return count
 
     def reinhard_fast(self, tiles_u8, target_means, target_stds, out=None):
         """`reinhard_fast` stain normalisation (hp.py:19; results.py:251-252 `wsi_normalizer.rgb_to_rgb`):

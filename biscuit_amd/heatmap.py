@@ -50,6 +50,8 @@ class Heatmap:
     # what ``render`` needs to place the grid on the slide; ``from_slide`` records them, the other constructors have no slide
     slide_path = slide_w0 = slide_h0 = stride = extract_px = None
     _slide_kw = None
+    # the tissue mask ``from_slide(cell_mask=..., qc=...)`` ran under: the bool [gh, gw] mask and what it did; None without one
+    cell_mask = qc = None
 
     def __init__(self, engine, tiles, grid, grid_shape=None, mc_n=30, seed=0, batch=256, norm_fit=None, normalizer='reinhard_fast'):
         """tiles: uint8 [T,299,299,3] (host or device); grid: int [T,2] (gx, gy) cell of each tile.  ``norm_fit`` / ``normalizer``:
@@ -93,7 +95,8 @@ class Heatmap:
 
     @classmethod
     def from_slide(cls, engine, path, tile_px=299, tile_um=302, stride_div=1, mpp=None, resample='gpu', canvas_bytes=256 << 20,
-                   grayspace_fraction=None, grayspace_threshold=0.05, decode='host', **kw):
+                   grayspace_fraction=None, grayspace_threshold=0.05, decode='host', cell_mask=None, qc=None, qc_width=2048,
+                   qc_fraction=0.6, **kw):
         """``sf.Heatmap(slide, model, stride_div=1)`` (results.py:217) for a pyramidal TIFF / SVS slide file: the tile grid of
         ``wsi.WSI(path, tile_px, tile_um, stride_div)`` through the MC-dropout kernels.  (The reader is this build's own --
         ``biscuit_amd/wsi.py`` says what it reads and what about it is unpinned.)
@@ -117,7 +120,20 @@ class Heatmap:
         arrays.  A band goes through ``read_region`` as before -- the pixels and any ``SlideError`` are then the host's -- when
         the extractor refuses one of its segments, when a segment's device status is not 0, or when the level is not a tiled
         JPEG page.  ``self.decode_stats = {'gpu_bands', 'host_bands', 'segments'}`` counts the bands either way took and the
-        segments the device decoded."""
+        segments the device decoded.
+
+        ``cell_mask`` / ``qc`` (``resample='gpu'`` only; default None = off): a keep mask over the grid, applied BEFORE anything
+        is read at full resolution (DESIGN.md "Heatmap input", Tissue mask).  ``cell_mask`` is the caller's own bool [grid_h,
+        grid_w] (True = run the cell).  ``qc='otsu'`` computes one from the slide's ``thumbnail(qc_width)`` on the device
+        (``Engine.tissue_blur`` / ``tissue_cells``; ``tissue.py``): one Otsu threshold on the 7 x 7 median of the saturation
+        channel, and a cell is dropped when more than ``qc_fraction`` of its thumbnail pixels are background -- Slideflow's
+        ``qc='otsu'`` restated from memory, unpinned.  Given both, a cell must pass both.  Only bands that hold a kept cell are
+        read (``WSI.bands(keep=...)``) and only kept cells are resampled; ``grayspace_fraction``, if on, then judges what
+        remains.  Dropped cells hold ``MASKED``, ``self.dropped`` counts every cell not run, ``self.cell_mask`` is the mask used
+        and ``self.qc = {'method', 'threshold', 'cells_dropped', 'bands_read', 'bands_skipped_rows'}`` says what it did (the Otsu
+        threshold; cells the mask dropped; bands read; grid rows never read).  A kept cell's values do not depend on the mask.
+        A mask that keeps no cell gives an all-``MASKED`` heatmap with an empty ``grid``."""
+        from . import tissue
         from .wsi import WSI
         if resample not in ('gpu', 'host'):
             raise ValueError(f"resample must be 'gpu' or 'host', not {resample!r}")
@@ -127,6 +143,14 @@ class Heatmap:
             raise ValueError(f"decode must be 'host' or 'gpu', not {decode!r}")
         if resample == 'host' and decode == 'gpu':
             raise ValueError("the device decodes into the band's canvas: decode='gpu' needs resample='gpu'")
+        if qc is not None and qc not in tissue.QC_METHODS:
+            raise ValueError(f"qc must be None or one of {tissue.QC_METHODS}, not {qc!r}")
+        if resample == 'host' and (qc is not None or cell_mask is not None):
+            raise ValueError("the tissue mask steers the streamed read: qc and cell_mask need resample='gpu'")
+        if qc is not None:
+            tissue.check_fraction(qc_fraction)
+            if int(qc_width) < 1:
+                raise ValueError(f'qc_width must be at least 1, not {qc_width!r}')
         w = WSI(path, tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
         try:
             if w.grid_w * w.grid_h == 0:
@@ -135,12 +159,33 @@ class Heatmap:
                 tiles, grid = w.tiles()
                 hm = cls(engine, tiles, grid, grid_shape=(w.grid_h, w.grid_w), **kw)
             else:
-                hm = cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, decode=decode, **kw)
+                keep = threshold = None
+                if cell_mask is not None:
+                    keep = tissue.check_mask(cell_mask, w.grid_h, w.grid_w).copy()
+                if qc is not None:
+                    qc_keep, threshold = cls._otsu_mask(engine, w, int(qc_width), qc_fraction)
+                    keep = qc_keep if keep is None else keep & qc_keep
+                hm = cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, decode=decode, keep=keep, **kw)
+                if keep is not None:
+                    hm.qc = dict(hm.qc, method=qc, threshold=threshold)
             hm.slide_path, (hm.slide_w0, hm.slide_h0), hm.stride, hm.extract_px = path, w.slide.dimensions, w.stride, w.extract_px
             hm._slide_kw = dict(tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
             return hm
         finally:
             w.close()
+
+    @staticmethod
+    def _otsu_mask(engine, w, qc_width, qc_fraction):
+        """``qc='otsu'`` for the open slide ``w``: (keep bool [grid_h, grid_w], the Otsu threshold).  The thumbnail goes up once;
+        256 histogram counts and the cells' counts come back."""
+        from . import tissue
+        thumb = np.ascontiguousarray(w.thumbnail(qc_width))
+        plane, hist = engine.tissue_blur(torch.from_numpy(thumb if thumb.flags.writeable else thumb.copy()).to(engine.device))
+        threshold = tissue.otsu_threshold(hist.cpu().numpy())
+        sw, sh = w.slide.dimensions
+        col, row = tissue.cell_ranges(w.grid_w, w.grid_h, thumb.shape[1], thumb.shape[0], sw, sh, w.stride, w.extract_px)
+        counts = engine.tissue_cells(plane, threshold, col, row).cpu().numpy()
+        return tissue.keep_from_counts(counts, col, row, qc_fraction), threshold
 
     @classmethod
     @staticmethod
@@ -164,9 +209,10 @@ class Heatmap:
 
     @classmethod
     def _streamed(cls, engine, w, canvas_bytes, gray_fraction, gray_threshold, mc_n=30, seed=0, batch=256, norm_fit=None,
-                  normalizer='reinhard_fast', decode='host'):
+                  normalizer='reinhard_fast', decode='host', keep=None):
         """``from_slide(resample='gpu')``: bands -> batches of exactly the tiles ``Heatmap(engine, *w.tiles())`` would put in
-        each batch (a batch is filled across band boundaries), so an unfiltered slide runs the same launches on the same bytes."""
+        each batch (a batch is filled across band boundaries), so an unfiltered slide runs the same launches on the same bytes.
+        ``keep`` (bool [grid_h, grid_w] or None): the tissue mask -- only its bands are read and only its cells are resampled."""
         from . import stain
         stain.check(normalizer, norm_fit)
         if gray_fraction is not None and not 0.0 <= float(gray_fraction) <= 1.0:
@@ -189,7 +235,13 @@ class Heatmap:
             hm.uncertainty[gy, gx] = std.cpu().numpy()
             kept.append(idx[:n].copy())
 
-        for gy0, gy1, gx0, gx1, canvas, origin, src_px in w.bands(canvas_bytes, segments=decode == 'gpu'):
+        mask = keep                                                          # (`keep` below is the grayspace filter's, per batch)
+        if mask is not None:
+            hm.cell_mask = mask
+            hm.dropped = int(mask.size - mask.sum())
+            hm.qc = {'method': None, 'threshold': None, 'cells_dropped': hm.dropped, 'bands_read': 0,
+                     'bands_skipped_rows': int((~mask.any(1)).sum())}
+        for gy0, gy1, gx0, gx1, canvas, origin, src_px in w.bands(canvas_bytes, segments=decode == 'gpu', keep=mask):
             d_canvas = None
             if decode == 'gpu' and canvas is not None:
                 d_canvas = cls._decode_band(engine, canvas)
@@ -204,6 +256,11 @@ class Heatmap:
             d_origin = torch.from_numpy(origin).to(dev)
             del canvas, origin                                                   # uploaded: the host holds one canvas at a time
             cell = (np.arange(gy0, gy1, dtype=np.int64)[:, None] * gw + np.arange(gx0, gx1, dtype=np.int64)[None, :]).reshape(-1)
+            if mask is not None:
+                hm.qc['bands_read'] += 1
+                pos = np.flatnonzero(mask[gy0:gy1, gx0:gx1].reshape(-1))       # the rectangle's kept cells, row-major
+                if len(pos) < len(cell):
+                    d_origin, cell = d_origin[torch.from_numpy(pos).to(dev)], cell[pos]
             a = 0
             while a < len(cell):
                 m = min(len(cell) - a, batch - fill)
@@ -355,7 +412,9 @@ def main(argv=None):
     """``python -m biscuit_amd.heatmap SLIDE --out DIR``: the UQ heatmap of one slide file (results.py:216-265) on disk --
     ``DIR/heatmap.npz`` (``logits``, ``uncertainty``, ``grid``; with ``--tile-uq`` also ``uq_mask`` and ``masked_logits``, the
     logits with the uncertain cells set to -1 as results.py:222-225 does), ``DIR/summary.json`` and, with ``--save-tiles``, the
-    tiles as ``uq_incl/`` / ``uq_excl/`` PNGs named as results.py:259 names them.  ``--render`` adds the pictures of
+    tiles as ``uq_incl/`` / ``uq_excl/`` PNGs named as results.py:259 names them.  ``--qc otsu`` masks the slide's background from
+    its thumbnail first (``from_slide(qc='otsu')``): ``heatmap.npz`` then also holds ``cell_mask`` and ``summary.json`` a ``qc``
+    entry.  ``--render`` adds the pictures of
     ``Heatmap.save`` (results.py:217-227): ``<slide>-raw.png``, ``-0.png``, ``-1.png``, ``-uncertainty.png`` and, with ``--tile-uq``,
     the masked pair under ``high_confidence/``; ``summary.json`` then lists them as ``rendered``."""
     import argparse
@@ -378,6 +437,12 @@ def main(argv=None):
     ap.add_argument('--grayspace-fraction', type=float, default=None,
                     help='drop tiles with more than this fraction of grey pixels (Slideflow extracts with 0.6); default: off')
     ap.add_argument('--grayspace-threshold', type=float, default=0.05)
+    ap.add_argument('--qc', default=None, choices=['otsu'],
+                    help="tissue mask from the slide's thumbnail before anything is read at full resolution (from_slide(qc=...)): "
+                         'adds cell_mask to heatmap.npz and qc to summary.json; default: off')
+    ap.add_argument('--qc-width', type=int, default=2048, help='width of the thumbnail --qc judges')
+    ap.add_argument('--qc-fraction', type=float, default=0.6,
+                    help='--qc drops a cell with more than this fraction of background pixels')
     ap.add_argument('--gpu-decode', action='store_true',
                     help="decode the slide's own JPEG tiles on the device (from_slide(decode='gpu')); the arrays do not change")
     ap.add_argument('--mpp', type=float, default=None, help='microns per pixel, for a file that does not say')
@@ -401,7 +466,8 @@ def main(argv=None):
         hm = Heatmap.from_slide(eng, args.slide, stride_div=args.stride_div, mpp=args.mpp, mc_n=mc, seed=args.seed, batch=args.batch,
                                 norm_fit=norm_fit, normalizer=hp.normalizer or 'reinhard_fast',
                                 grayspace_fraction=args.grayspace_fraction, grayspace_threshold=args.grayspace_threshold,
-                                decode='gpu' if args.gpu_decode else 'host')
+                                decode='gpu' if args.gpu_decode else 'host', qc=args.qc, qc_width=args.qc_width,
+                                qc_fraction=args.qc_fraction)
         torch.cuda.synchronize(eng.device)
         seconds = time.perf_counter() - t0
         rendered = None
@@ -429,10 +495,14 @@ def main(argv=None):
                         Image.fromarray(w._tile(int(gx), int(gy))).save(os.path.join(args.out, name, fname))
             finally:
                 w.close()
+    if args.qc is not None:
+        arrays['cell_mask'] = hm.cell_mask
     np.savez(os.path.join(args.out, 'heatmap.npz'), **arrays)
     run = int(len(hm.grid))
     summary = {'slide': args.slide, 'grid_shape': list(hm.logits.shape[:2]), 'tiles_run': run, 'tiles_dropped': int(hm.dropped),
                'seconds': seconds, 'tiles_per_s': run / seconds if seconds > 0 else None, 'decode_stats': hm.decode_stats}
+    if args.qc is not None:
+        summary['qc'] = hm.qc
     if rendered is not None:
         summary['rendered'] = rendered
     with open(os.path.join(args.out, 'summary.json'), 'w') as f:

@@ -461,7 +461,7 @@ class WSI:
         (x0, y0, cw, ch), origin, lw = self._band_rect(gy0, gy1, gx0, gx1)
         return self.slide.region_segments(self.level, x0, y0, cw, ch), origin, lw
 
-    def bands(self, canvas_bytes=256 << 20, segments=False):
+    def bands(self, canvas_bytes=256 << 20, segments=False, keep=None):
         """Iterate the grid as bands whose canvas stays under ``canvas_bytes`` (at least one grid row each): yields ``(gy0, gy1,
         gx0, gx1, canvas, origin, src_px)`` with ``band``'s values.  A band is split into column ranges only where one grid row
         is wider than ``read_region`` reads at once (``READ_LIMIT``, 65 536 pixels); the tiles of such a slide then arrive band by
@@ -469,7 +469,18 @@ class WSI:
 
         ``segments=True`` yields ``band_segments``' values instead: a ``BandSegments`` in place of the canvas, or None in its
         place where the band has to be read with ``band`` -- the level is not a tiled JPEG page, or the segment tables point
-        outside the file (``band`` then says so)."""
+        outside the file (``band`` then says so).
+
+        ``keep`` (bool [grid_h, grid_w]; None: every cell, the bands above): only what a kept cell needs is read (DESIGN.md
+        "Heatmap input", Tissue mask).  Grid rows without a kept cell are never read and end a band; within a band every column
+        range is cut down to the rectangle its kept cells span, so no band is without a kept cell and every band's first and
+        last row and first and last column hold one.  The rectangles are disjoint and together hold every kept cell once;
+        ``origin`` still lists every cell of the rectangle in row-major order, kept or not."""
+        if keep is not None:
+            keep = np.asarray(keep)
+            if keep.dtype != np.bool_ or keep.shape != (self.grid_h, self.grid_w):
+                raise ValueError(f'keep must be bool [{self.grid_h}, {self.grid_w}], not {keep.dtype} {list(keep.shape)}')
+            live = keep.any(1)
         lw, limit = self.src_px, self.READ_LIMIT
         cols, gx0 = [], 0
         while gx0 < self.grid_w:                                          # column ranges of at most `limit` pixels
@@ -481,20 +492,30 @@ class WSI:
         widest = max((self._level_xy(b - 1) + lw - self._level_xy(a) for a, b in cols), default=0)
         gy0 = 0
         while gy0 < self.grid_h:
+            if keep is not None and not live[gy0]:
+                gy0 += 1
+                continue
             gy1 = gy0 + 1
-            while gy1 < self.grid_h:
+            while gy1 < self.grid_h and (keep is None or live[gy1]):
                 h = self._level_xy(gy1) + lw - self._level_xy(gy0)
                 if h > limit or h * widest * 3 > canvas_bytes:
                     break
                 gy1 += 1
             for a, b in cols:
+                r0, r1 = gy0, gy1
+                if keep is not None:                                      # the rectangle this column range's kept cells span
+                    sub = keep[gy0:gy1, a:b]
+                    if not sub.any():
+                        continue
+                    cs, rs = np.flatnonzero(sub.any(0)), np.flatnonzero(sub.any(1))
+                    a, b, r0, r1 = a + int(cs[0]), a + int(cs[-1]) + 1, gy0 + int(rs[0]), gy0 + int(rs[-1]) + 1
                 if not segments:
-                    yield (gy0, gy1, a, b) + self.band(gy0, gy1, a, b)
+                    yield (r0, r1, a, b) + self.band(r0, r1, a, b)
                     continue
                 try:
-                    yield (gy0, gy1, a, b) + self.band_segments(gy0, gy1, a, b)
+                    yield (r0, r1, a, b) + self.band_segments(r0, r1, a, b)
                 except SlideError:
-                    yield (gy0, gy1, a, b, None) + self._band_rect(gy0, gy1, a, b)[1:]
+                    yield (r0, r1, a, b, None) + self._band_rect(r0, r1, a, b)[1:]
             gy0 = gy1
 
     # ---- the picture under a rendered heatmap (heatmap.Heatmap.render) --------------------------------------------------------

@@ -258,6 +258,24 @@ int bq_heatmap_render(bq_ctx* ctx, const float* d_values, int gh, int gw, const 
                       int interpolation, const uint8_t* d_lut, const uint8_t* d_thumb, uint8_t* d_out, int H, int W, float vmin,
                       float inv_span, int A, bq_stream_t stream);
 
+/* The whole-slide heatmap's tissue mask (kernels_tissue.hip; DESIGN.md "Heatmap input", Tissue mask): Otsu QC on the slide's
+ * thumbnail, restated in integers (Slideflow's qc='otsu', from memory: unpinned).  bq_tissue_blur: d_thumb uint8 [H][W][3] ->
+ * d_plane uint8 [H][W], the 7 x 7 median (the 25th smallest of the 49 neighbours, coordinates clamped to the image; H or W below
+ * 7 are legal) of the 8-bit saturation S = ((mx - mn) d_sdiv256[mx] + 2048) >> 12 with mx / mn the largest / smallest of r, g,
+ * b, and d_hist int32 [256], the histogram of d_plane (zeroed by the call).  d_sdiv256 int32 [256] is the host's table
+ * (tissue.sdiv_table: 0, then rint(255 * 4096 / v)).  One launch.  0 < H, W and H * W < 2^31.
+ * bq_tissue_cells: d_count[gy][gx] (int32 [gh][gw]) = the number of pixels of d_plane with value <= T inside columns
+ * [col_ranges[2 gx], col_ranges[2 gx + 1]) x rows [row_ranges[2 gy], row_ranges[2 gy + 1]).  The two range tables (int32 [gw][2],
+ * [gh][2]: tissue.cell_ranges) are HOST memory: every range is checked here -- non-empty and inside the plane -- and the tables
+ * are then copied into d_ranges (device, int32 [2 (gw + gh)], caller-owned) on `stream`; they must stay valid until the stream
+ * has passed the call.  Ranges may overlap and may be one pixel wide.  0 <= T <= 255, 0 < gw, gh <= 32768.
+ * Both allocate nothing and are enqueued on `stream` without a host synchronisation; a bad argument -- a null pointer, H * W >=
+ * 2^31, an empty range or one outside the plane -- is BQ_ERR_ARG with nothing enqueued. */
+int bq_tissue_blur(bq_ctx* ctx, const uint8_t* d_thumb, int H, int W, const int32_t* d_sdiv256, uint8_t* d_plane, int32_t* d_hist,
+                   bq_stream_t stream);
+int bq_tissue_cells(bq_ctx* ctx, const uint8_t* d_plane, int H, int W, int T, const int32_t* col_ranges, int gw,
+                    const int32_t* row_ranges, int gh, int32_t* d_ranges, int32_t* d_count, bq_stream_t stream);
+
 /* Variant for callers that already hold standardised float32 NHWC tiles (the
  * UncertaintyInterface contract, results.py:256-257): converts to planar NCHW. */
 int bq_stage_f32(bq_ctx* ctx, const float* d_tiles_nhwc_f32, int n, void* d_out_nchw,

@@ -26,7 +26,15 @@ alternating processes.
 
 ``--render`` times ``Engine.heatmap_render`` alone (device events around 20 launches, out of place) on a 100 x 100 grid with a
 tenth of its cells masked under a 2 048 x 1 536 thumbnail, in both interpolation modes, next to the wall time of the numpy
-restatement (``tests/_render_ref.py``) on the same inputs, and checks that the two pictures are equal."""
+restatement (``tests/_render_ref.py``) on the same inputs, and checks that the two pictures are equal.
+
+    python tools/bench_heatmap.py --out DIR --qc off --stride-div 1          # the tissue-mask leg: the deflate slide (its right
+    python tools/bench_heatmap.py --out DIR --qc otsu --stride-div 1         # fifth is glass) without and with the mask
+
+``--qc`` times ``from_slide(qc=...)`` at the first ``--stride-div`` value -- 'off' passes no mask -- and prints the tiles run, the
+mask's own report (``hm.qc``) and, for 'otsu', the host seconds of ``WSI.thumbnail`` and the device milliseconds of
+``Engine.tissue_blur`` and ``Engine.tissue_cells`` alone (device events around 20 launches) on that thumbnail.  Run the two values
+in separate, alternating processes."""
 import argparse
 import json
 import os
@@ -174,6 +182,59 @@ def decode_leg(args, eng, slide, tag, emit, kw):
           'spread_total': round((max(total) - min(total)) / med(total), 4)})
 
 
+def qc_leg(args, eng, slide, tag, emit, kw):
+    """``--qc``: from_slide with or without the tissue mask, then the mask's own pieces."""
+    import torch
+    from biscuit_amd import tissue
+    from biscuit_amd.heatmap import Heatmap
+    from biscuit_amd.wsi import WSI
+    sd = args.stride_div[0]
+    if args.qc != 'off':
+        kw = dict(kw, qc=args.qc, qc_width=args.qc_width)
+    times = []
+    for r in range(args.runs + 1):                                          # the first call is the warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        hm = Heatmap.from_slide(eng, slide, stride_div=sd, **kw)
+        torch.cuda.synchronize()
+        if r:
+            times.append(time.perf_counter() - t0)
+    np.savez(os.path.join(args.out, f'arrays_{tag}.npz'), logits=hm.logits, uncertainty=hm.uncertainty)
+    cells, med = int(hm.logits.shape[0] * hm.logits.shape[1]), float(np.median(times))
+    emit({'what': 'from_slide_qc', 'qc': args.qc, 'stride_div': sd, 'mc': args.mc, 'cells': cells, 'tiles_run': int(len(hm.grid)),
+          'dropped': int(hm.dropped), 'qc_report': hm.qc, 'seconds': [round(t, 4) for t in times], 'median_s': round(med, 4),
+          'spread': round((max(times) - min(times)) / med, 4)})
+    if args.qc == 'off':
+        return
+    w = WSI(slide, stride_div=sd)
+    try:
+        host = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            thumb = np.ascontiguousarray(w.thumbnail(args.qc_width))
+            host.append(time.perf_counter() - t0)
+        col, row = tissue.cell_ranges(w.grid_w, w.grid_h, thumb.shape[1], thumb.shape[0], *w.slide.dimensions, w.stride, w.extract_px)
+    finally:
+        w.close()
+    d_thumb = torch.from_numpy(thumb if thumb.flags.writeable else thumb.copy()).to(eng.device)
+    plane, hist = eng.tissue_blur(d_thumb)
+    thr = tissue.otsu_threshold(hist.cpu().numpy())
+
+    def ms(fn, reps=20):
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        b.synchronize()
+        return round(a.elapsed_time(b) / reps, 4)
+    emit({'what': 'tissue_mask_parts', 'thumb': list(thumb.shape[:2]), 'grid': [len(row), len(col)], 'threshold': thr,
+          'thumbnail_host_s': [round(t, 4) for t in host], 'tissue_blur_ms': ms(lambda: eng.tissue_blur(d_thumb)),
+          'tissue_cells_ms': ms(lambda: eng.tissue_cells(plane, thr, col, row))})
+
+
 def render_leg(args, eng, emit):
     """``--render``: the kernel's milliseconds per picture and the numpy restatement's, same inputs, same bytes."""
     import torch
@@ -226,9 +287,13 @@ def main():
     ap.add_argument('--decode', default=None, choices=['host', 'gpu'],
                     help='the decode leg only: from_slide(decode=...) on a slide of JPEG tiles, and seconds per band by stage')
     ap.add_argument('--render', action='store_true', help='the render leg only: Engine.heatmap_render next to its numpy restatement')
+    ap.add_argument('--qc', default=None, choices=['off', 'otsu'],
+                    help="the tissue-mask leg only: from_slide without ('off') or with the mask, and the mask's own pieces")
+    ap.add_argument('--qc-width', type=int, default=2048)
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
-    tag = args.tag or ('render' if args.render else args.resample if args.decode is None else 'decode_' + args.decode)
+    tag = args.tag or ('render' if args.render else 'qc_' + args.qc if args.qc is not None else
+                       args.resample if args.decode is None else 'decode_' + args.decode)
     slide = args.slide or os.path.join(args.out, 'bench_slide.svs' if args.decode is None else 'bench_slide_jpeg.svs')
     gw, gh = (int(v) for v in args.grid.lower().split('x'))
     if not os.path.exists(slide) and not args.render:
@@ -256,6 +321,10 @@ def main():
         return
     if args.decode is not None:
         decode_leg(args, eng, slide, tag, emit, kw)
+        eng.close()
+        return
+    if args.qc is not None:
+        qc_leg(args, eng, slide, tag, emit, kw)
         eng.close()
         return
     if args.resample != 'default':
