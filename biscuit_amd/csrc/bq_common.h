@@ -150,6 +150,12 @@ int launch_heatmap_render(const float* values, int gh, int gw, const int32_t* co
 int launch_tissue_blur(const uint8_t* thumb, int H, int W, const int* sdiv256, uint8_t* plane, int* hist, hipStream_t s);
 int launch_tissue_cells(const uint8_t* plane, int H, int W, int T, const int* col, const int* row, int gw, int gh, int* count,
                         hipStream_t s);
+// kernels_focus.hip: the focus mask on a 4 um / pixel thumbnail (DESIGN.md "Heatmap input", Focus mask): gray, |Laplacian| and a
+// separable Gaussian in integers with one threshold, and every grid cell's pixels that are background or out of focus
+int launch_tissue_focus(const uint8_t* thumb, int H, int W, const int* taps, int r, int thr, int* work, int* value, uint8_t* plane,
+                        int* count, hipStream_t s);
+int launch_tissue_cells_union(const uint8_t* otsu, int Ho, int Wo, int T, const uint8_t* focus, int Hf, int Wf, const int* xmap,
+                              const int* ymap, const int* col, const int* row, int gw, int gh, int* count, hipStream_t s);
 int launch_stem1(const void* in_nchw, int n, const float* w27x32, const float* scale,
                  const float* bias, void* out_nhwc, int dtype, hipStream_t s);
 int launch_pool_add(const void* y, const void* res, void* out, int n, int Hi, int Wi, int C,

@@ -82,6 +82,7 @@ class Engine:
         self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
         self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
         self._tissue_host = None         # the range tables of the last tissue_cells call, alive while the stream copies them
+        self._tissue_taps = {}           # sigma -> (the Gaussian's taps on the device, r) (tissue_focus)
         self._elt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[dtype]
 
     # shapes of the stored tensors by debug-tap name
@@ -397,6 +398,78 @@ class Engine:
         self._tissue_host = (col, row)                                      # the host tables live until the stream has copied them
         self._check(self._lib.bq_tissue_cells(self._ctx, _ptr(plane), h, w, int(T), col.ctypes.data, gw, row.ctypes.data, gh,
                                               _ptr(ranges), _ptr(count), self._stream()))
+        return count
+
+    def tissue_focus(self, thumb_u8, threshold=0.02, sigma=3.0, value=False):
+        """The focus mask's first stage (``bq_tissue_focus``, kernels_focus.hip; DESIGN.md "Heatmap input", Focus mask): a
+        thumbnail uint8 [H, W, 3] on this device -> (plane uint8 [H, W], 1 = in focus and 0 = out of focus, and count int32 [1],
+        the number of out-of-focus pixels), with ``value=True`` also V int32 [H, W], the Gaussian-blurred |Laplacian| of the
+        gray image in units of ``tissue.FOCUS_SCALE`` -- all on the device, the integers of the numpy restatement.  A pixel is
+        out of focus iff ``V <= floor(threshold * FOCUS_SCALE)``.  ``H * W < 2^31``; H or W below the radius are legal.
+        ValueError as ``tissue.check_focus``."""
+        from . import tissue
+        if not (torch.is_tensor(thumb_u8) and thumb_u8.dtype == torch.uint8 and thumb_u8.dim() == 3 and thumb_u8.shape[2] == 3):
+            raise ValueError('thumb must be uint8 [H, W, 3]')
+        if not thumb_u8.is_cuda or thumb_u8.device != self.device:
+            raise ValueError(f'thumb must be on {self.device}, not {thumb_u8.device}')
+        assert thumb_u8.is_contiguous()
+        h, w = int(thumb_u8.shape[0]), int(thumb_u8.shape[1])
+        if h < 1 or w < 1 or h * w >= 1 << 31:
+            raise ValueError(f'a thumbnail has 1 <= H, W and H * W < 2^31, not {h} x {w}')
+        thr = tissue.focus_units(threshold)
+        key = float(sigma)
+        if key not in self._tissue_taps:
+            taps = tissue.focus_taps(key)
+            self._tissue_taps[key] = (torch.from_numpy(taps).to(self.device), (len(taps) - 1) // 2)
+        d_taps, r = self._tissue_taps[key]
+        work = torch.empty((h, w), dtype=torch.int32, device=self.device)
+        v = torch.empty((h, w), dtype=torch.int32, device=self.device) if value else None
+        plane = torch.empty((h, w), dtype=torch.uint8, device=self.device)
+        count = torch.empty(1, dtype=torch.int32, device=self.device)
+        self._check(self._lib.bq_tissue_focus(self._ctx, _ptr(thumb_u8), h, w, _ptr(d_taps), r, thr, _ptr(work),
+                                              None if v is None else _ptr(v), _ptr(plane), _ptr(count), self._stream()))
+        return (plane, count, v) if value else (plane, count)
+
+    def tissue_cells_union(self, otsu_plane, T, focus_plane, col, row, xmap=None, ymap=None):
+        """The union of the two masks per grid cell (``bq_tissue_cells_union``): ``otsu_plane`` uint8 [Ho, Wo] (``tissue_blur``'s)
+        with its threshold ``T``, ``focus_plane`` uint8 [Hf, Wf] (``tissue_focus``'s), both on this device, and the cells' ranges
+        in pixels of the Otsu plane (``tissue.cell_ranges``; host arrays) -> int32 [gh, gw] on the device: the pixels of every
+        cell with ``otsu_plane <= T`` or ``focus_plane[ymap[y], xmap[x]] == 0``.  ``xmap`` int32 [Wo] / ``ymap`` int32 [Ho] lay the
+        focus plane over the Otsu plane; None: ``tissue.plane_map``'s nearest-neighbour resize.  ValueError for a range that is
+        empty or leaves the plane, and for a map of the wrong length, outside the focus plane or decreasing."""
+        from . import tissue
+        for name, p in (('otsu_plane', otsu_plane), ('focus_plane', focus_plane)):
+            if not (torch.is_tensor(p) and p.dtype == torch.uint8 and p.dim() == 2 and p.numel() > 0):
+                raise ValueError(f'{name} must be uint8 [H, W]')
+            if not p.is_cuda or p.device != self.device:
+                raise ValueError(f'{name} must be on {self.device}, not {p.device}')
+            assert p.is_contiguous()
+        ho, wo = int(otsu_plane.shape[0]), int(otsu_plane.shape[1])
+        hf, wf = int(focus_plane.shape[0]), int(focus_plane.shape[1])
+        col, row = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(row, np.int32)
+        if col.ndim != 2 or col.shape[1] != 2 or row.ndim != 2 or row.shape[1] != 2 or len(col) < 1 or len(row) < 1:
+            raise ValueError('col and row must be int32 [gw, 2] and [gh, 2]')
+        gw, gh = len(col), len(row)
+        if gw > tissue.MAX_GRID or gh > tissue.MAX_GRID:
+            raise ValueError(f'a grid is 1 .. {tissue.MAX_GRID} cells a side, not {gh} x {gw}')
+        if not 0 <= int(T) <= 255:
+            raise ValueError(f'T must lie in 0 .. 255, not {T!r}')
+        for name, r, n in (('col', col, wo), ('row', row, ho)):
+            if (r[:, 0] < 0).any() or (r[:, 0] >= r[:, 1]).any() or (r[:, 1] > n).any():
+                raise ValueError(f'a {name} range is empty or outside the {ho} x {wo} plane')
+        xmap = tissue.plane_map(wo, wf) if xmap is None else np.ascontiguousarray(xmap, np.int32)
+        ymap = tissue.plane_map(ho, hf) if ymap is None else np.ascontiguousarray(ymap, np.int32)
+        for name, m, n_to, n_from in (('xmap', xmap, wo, wf), ('ymap', ymap, ho, hf)):
+            if m.shape != (n_to,):
+                raise ValueError(f'{name} must be int32 [{n_to}], not {list(m.shape)}')
+            if (m < 0).any() or (m >= n_from).any() or (np.diff(m) < 0).any():
+                raise ValueError(f'{name} leaves the focus plane ({n_from}) or decreases')
+        tables = torch.empty(wo + ho + 2 * (gw + gh), dtype=torch.int32, device=self.device)
+        count = torch.empty((gh, gw), dtype=torch.int32, device=self.device)
+        self._tissue_host = (col, row, xmap, ymap)                          # the host tables live until the stream has copied them
+        self._check(self._lib.bq_tissue_cells_union(self._ctx, _ptr(otsu_plane), ho, wo, int(T), _ptr(focus_plane), hf, wf,
+                                                    xmap.ctypes.data, ymap.ctypes.data, col.ctypes.data, gw, row.ctypes.data, gh,
+                                                    _ptr(tables), _ptr(count), self._stream()))
         return count
 
     def reinhard_fast(self, tiles_u8, target_means, target_stds, out=None):

@@ -96,7 +96,7 @@ class Heatmap:
     @classmethod
     def from_slide(cls, engine, path, tile_px=299, tile_um=302, stride_div=1, mpp=None, resample='gpu', canvas_bytes=256 << 20,
                    grayspace_fraction=None, grayspace_threshold=0.05, decode='host', cell_mask=None, qc=None, qc_width=2048,
-                   qc_fraction=0.6, **kw):
+                   qc_fraction=0.6, focus_threshold=None, focus_mpp=4.0, focus_sigma=3.0, **kw):
         """``sf.Heatmap(slide, model, stride_div=1)`` (results.py:217) for a pyramidal TIFF / SVS slide file: the tile grid of
         ``wsi.WSI(path, tile_px, tile_um, stride_div)`` through the MC-dropout kernels.  (The reader is this build's own --
         ``biscuit_amd/wsi.py`` says what it reads and what about it is unpinned.)
@@ -132,7 +132,18 @@ class Heatmap:
         remains.  Dropped cells hold ``MASKED``, ``self.dropped`` counts every cell not run, ``self.cell_mask`` is the mask used
         and ``self.qc = {'method', 'threshold', 'cells_dropped', 'bands_read', 'bands_skipped_rows'}`` says what it did (the Otsu
         threshold; cells the mask dropped; bands read; grid rows never read).  A kept cell's values do not depend on the mask.
-        A mask that keeps no cell gives an all-``MASKED`` heatmap with an empty ``grid``."""
+        A mask that keeps no cell gives an all-``MASKED`` heatmap with an empty ``grid``.
+
+        ``focus_threshold`` (``resample='gpu'`` only; default None = off): the focus mask, Slideflow's Gaussian blur QC restated
+        from memory in integers, unpinned (DESIGN.md "Heatmap input", Focus mask).  On the slide's thumbnail at ``focus_mpp``
+        microns per pixel (``tissue.focus_width``; separate from ``qc_width``) the device takes the gray image, the absolute
+        Laplacian and a Gaussian of ``focus_sigma`` pixels (``Engine.tissue_focus``); a pixel is out of focus when the result is
+        at most ``focus_threshold``, and a cell is dropped when more than ``qc_fraction`` of its thumbnail pixels are.  ``qc``
+        keeps its strings: Slideflow's ``qc='blur'`` is spelled ``focus_threshold=0.02`` and its ``qc='both'`` is ``qc='otsu',
+        focus_threshold=0.02`` -- a pixel of the Otsu plane is then bad when it is background or when the focus plane, resized
+        onto it by nearest neighbour, says out of focus (``Engine.tissue_cells_union``), and ``qc_fraction`` judges the union.
+        ``cell_mask`` still ANDs on top.  ``self.qc`` then also holds ``focus_threshold``, ``focus_width`` and ``focus_share``
+        (out-of-focus pixels / all pixels of the focus thumbnail)."""
         from . import tissue
         from .wsi import WSI
         if resample not in ('gpu', 'host'):
@@ -151,6 +162,11 @@ class Heatmap:
             tissue.check_fraction(qc_fraction)
             if int(qc_width) < 1:
                 raise ValueError(f'qc_width must be at least 1, not {qc_width!r}')
+        tissue.check_focus(0.0 if focus_threshold is None else focus_threshold, focus_mpp, focus_sigma)      # (its keywords, on or off)
+        if focus_threshold is not None:
+            if resample == 'host':
+                raise ValueError("the focus mask steers the streamed read: focus_threshold needs resample='gpu'")
+            tissue.check_fraction(qc_fraction)
         w = WSI(path, tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
         try:
             if w.grid_w * w.grid_h == 0:
@@ -162,12 +178,17 @@ class Heatmap:
                 keep = threshold = None
                 if cell_mask is not None:
                     keep = tissue.check_mask(cell_mask, w.grid_h, w.grid_w).copy()
-                if qc is not None:
+                focus = None
+                if focus_threshold is not None:
+                    qc_keep, threshold, focus = cls._focus_mask(engine, w, qc, int(qc_width), qc_fraction, focus_threshold, focus_mpp,
+                                                                focus_sigma)
+                    keep = qc_keep if keep is None else keep & qc_keep
+                elif qc is not None:
                     qc_keep, threshold = cls._otsu_mask(engine, w, int(qc_width), qc_fraction)
                     keep = qc_keep if keep is None else keep & qc_keep
                 hm = cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, decode=decode, keep=keep, **kw)
                 if keep is not None:
-                    hm.qc = dict(hm.qc, method=qc, threshold=threshold)
+                    hm.qc = dict(hm.qc, method=qc, threshold=threshold, **(focus or {}))
             hm.slide_path, (hm.slide_w0, hm.slide_h0), hm.stride, hm.extract_px = path, w.slide.dimensions, w.stride, w.extract_px
             hm._slide_kw = dict(tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
             return hm
@@ -186,6 +207,34 @@ class Heatmap:
         col, row = tissue.cell_ranges(w.grid_w, w.grid_h, thumb.shape[1], thumb.shape[0], sw, sh, w.stride, w.extract_px)
         counts = engine.tissue_cells(plane, threshold, col, row).cpu().numpy()
         return tissue.keep_from_counts(counts, col, row, qc_fraction), threshold
+
+    @staticmethod
+    def _focus_mask(engine, w, qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma):
+        """``focus_threshold=...`` for the open slide ``w``, alone (``qc`` None) or with ``qc='otsu'``: (keep bool [grid_h,
+        grid_w], the Otsu threshold or None, the focus entries of ``hm.qc``).  Alone, a cell's out-of-focus pixels are counted
+        over its range of the focus plane; with Otsu, the union is counted over its range of the Otsu plane."""
+        from . import tissue
+
+        def up(a):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a if a.flags.writeable else a.copy()).to(engine.device)
+        sw, sh = w.slide.dimensions
+        fthumb = up(w.thumbnail(tissue.focus_width(sw, w.mpp, focus_mpp)))
+        fh, fw = int(fthumb.shape[0]), int(fthumb.shape[1])
+        fplane, fcount = engine.tissue_focus(fthumb, focus_threshold, focus_sigma)
+        del fthumb
+        threshold = None
+        if qc is None:
+            col, row = tissue.cell_ranges(w.grid_w, w.grid_h, fw, fh, sw, sh, w.stride, w.extract_px)
+            counts = engine.tissue_cells(fplane, 0, col, row)
+        else:
+            othumb = up(w.thumbnail(qc_width))
+            oplane, hist = engine.tissue_blur(othumb)
+            threshold = tissue.otsu_threshold(hist.cpu().numpy())
+            col, row = tissue.cell_ranges(w.grid_w, w.grid_h, int(othumb.shape[1]), int(othumb.shape[0]), sw, sh, w.stride, w.extract_px)
+            counts = engine.tissue_cells_union(oplane, threshold, fplane, col, row)
+        info = {'focus_threshold': float(focus_threshold), 'focus_width': fw, 'focus_share': int(fcount.cpu().numpy()[0]) / float(fh * fw)}
+        return tissue.keep_from_counts(counts.cpu().numpy(), col, row, qc_fraction), threshold, info
 
     @classmethod
     @staticmethod
@@ -414,7 +463,8 @@ def main(argv=None):
     logits with the uncertain cells set to -1 as results.py:222-225 does), ``DIR/summary.json`` and, with ``--save-tiles``, the
     tiles as ``uq_incl/`` / ``uq_excl/`` PNGs named as results.py:259 names them.  ``--qc otsu`` masks the slide's background from
     its thumbnail first (``from_slide(qc='otsu')``): ``heatmap.npz`` then also holds ``cell_mask`` and ``summary.json`` a ``qc``
-    entry.  ``--render`` adds the pictures of
+    entry.  ``--qc-focus [THRESHOLD]`` (bare: 0.02) masks its out-of-focus regions (``from_slide(focus_threshold=...)``), alone or
+    with ``--qc otsu`` (Slideflow's ``qc='both'``), and writes the same two.  ``--render`` adds the pictures of
     ``Heatmap.save`` (results.py:217-227): ``<slide>-raw.png``, ``-0.png``, ``-1.png``, ``-uncertainty.png`` and, with ``--tile-uq``,
     the masked pair under ``high_confidence/``; ``summary.json`` then lists them as ``rendered``."""
     import argparse
@@ -443,6 +493,11 @@ def main(argv=None):
     ap.add_argument('--qc-width', type=int, default=2048, help='width of the thumbnail --qc judges')
     ap.add_argument('--qc-fraction', type=float, default=0.6,
                     help='--qc drops a cell with more than this fraction of background pixels')
+    ap.add_argument('--qc-focus', type=float, nargs='?', const=0.02, default=None, metavar='THRESHOLD',
+                    help="focus mask from the slide's 4 um / pixel thumbnail (from_slide(focus_threshold=...); bare: 0.02), alone or "
+                         "with --qc otsu (Slideflow's qc='both'): adds cell_mask to heatmap.npz and qc to summary.json; default: off")
+    ap.add_argument('--qc-focus-mpp', type=float, default=4.0, help='microns per pixel of the thumbnail --qc-focus judges')
+    ap.add_argument('--qc-focus-sigma', type=float, default=3.0, help="sigma of --qc-focus's Gaussian, in thumbnail pixels")
     ap.add_argument('--gpu-decode', action='store_true',
                     help="decode the slide's own JPEG tiles on the device (from_slide(decode='gpu')); the arrays do not change")
     ap.add_argument('--mpp', type=float, default=None, help='microns per pixel, for a file that does not say')
@@ -467,7 +522,8 @@ def main(argv=None):
                                 norm_fit=norm_fit, normalizer=hp.normalizer or 'reinhard_fast',
                                 grayspace_fraction=args.grayspace_fraction, grayspace_threshold=args.grayspace_threshold,
                                 decode='gpu' if args.gpu_decode else 'host', qc=args.qc, qc_width=args.qc_width,
-                                qc_fraction=args.qc_fraction)
+                                qc_fraction=args.qc_fraction, focus_threshold=args.qc_focus, focus_mpp=args.qc_focus_mpp,
+                                focus_sigma=args.qc_focus_sigma)
         torch.cuda.synchronize(eng.device)
         seconds = time.perf_counter() - t0
         rendered = None
@@ -495,13 +551,13 @@ def main(argv=None):
                         Image.fromarray(w._tile(int(gx), int(gy))).save(os.path.join(args.out, name, fname))
             finally:
                 w.close()
-    if args.qc is not None:
+    if args.qc is not None or args.qc_focus is not None:
         arrays['cell_mask'] = hm.cell_mask
     np.savez(os.path.join(args.out, 'heatmap.npz'), **arrays)
     run = int(len(hm.grid))
     summary = {'slide': args.slide, 'grid_shape': list(hm.logits.shape[:2]), 'tiles_run': run, 'tiles_dropped': int(hm.dropped),
                'seconds': seconds, 'tiles_per_s': run / seconds if seconds > 0 else None, 'decode_stats': hm.decode_stats}
-    if args.qc is not None:
+    if args.qc is not None or args.qc_focus is not None:
         summary['qc'] = hm.qc
     if rendered is not None:
         summary['rendered'] = rendered

@@ -5,7 +5,17 @@ here to pin it against) in integer arithmetic throughout, so the device and a nu
 saturation table the kernel receives (``sdiv_table``), the exact Otsu threshold of the 256 histogram counts (``otsu_threshold``),
 the grid cells' ranges in thumbnail pixels (``cell_ranges``), the keep decision (``keep_from_counts``) and the argument checks.
 The device side is ``Engine.tissue_blur`` / ``Engine.tissue_cells`` (csrc/kernels_tissue.hip); ``Heatmap.from_slide(qc='otsu')``
-puts the two together."""
+puts the two together.
+
+The focus mask (DESIGN.md "Heatmap input", Focus mask) is the other half of Slideflow's ``qc='both'``: its Gaussian blur filter,
+also restated from memory in integers -- gray, |Laplacian|, a separable Gaussian and one threshold on a 4 um / pixel thumbnail.
+Here: the Gaussian's integer taps (``focus_taps``), the threshold in integer units (``focus_units``), the thumbnail's width
+(``focus_width``), the nearest-neighbour map that lays the focus plane over the Otsu plane (``plane_map``) and the argument checks
+(``check_focus``).  The device side is ``Engine.tissue_focus`` / ``Engine.tissue_cells_union`` (csrc/kernels_focus.hip);
+``Heatmap.from_slide(focus_threshold=...)`` puts them together.  ``QC_METHODS`` stays ``('otsu',)``: Slideflow's ``'blur'`` is
+spelled ``focus_threshold=0.02`` and its ``'both'`` ``qc='otsu', focus_threshold=0.02``."""
+import math
+
 import numpy as np
 
 QC_METHODS = ('otsu',)
@@ -14,6 +24,12 @@ QC_FRACTION = 0.6                        # a cell is dropped when more than this
 MEDIAN_K = 7                             # the median's window, MEDIAN_K x MEDIAN_K with a replicated border
 SAT_SHIFT = 12                           # S = ((mx - mn) * sdiv[mx] + 2^11) >> 12
 MAX_GRID = 1 << 15                       # cells a side ``bq_tissue_cells`` takes
+FOCUS_SCALE = 2_550_000                  # integer units per unit of the [0, 1] gray image: G = 2125 r + 7154 g + 721 b
+FOCUS_MPP = 4.0                          # microns per pixel of the focus thumbnail
+FOCUS_SIGMA = 3.0                        # the Gaussian's sigma, in thumbnail pixels
+FOCUS_THRESHOLD = 0.02                   # a pixel is out of focus iff its blurred |Laplacian| is <= this (Slideflow's default)
+FOCUS_TAP_SHIFT = 16                     # the taps sum to 2^16
+FOCUS_MAX_RADIUS = 16                    # the largest radius ``bq_tissue_focus`` takes
 
 
 def sdiv_table():
@@ -112,3 +128,58 @@ def check_mask(mask, gh, gw, name='cell_mask'):
     if m.dtype != np.bool_ or m.shape != (gh, gw):
         raise ValueError(f'{name} must be bool [{gh}, {gw}] (the slide\'s grid), not {m.dtype} {list(m.shape)}')
     return m
+
+
+def focus_taps(sigma=FOCUS_SIGMA):
+    """int32 [2 r + 1], ``r = int(4 sigma + 0.5)`` (scipy's ``truncate=4``): ``w[k] = rint(65536 g_k)`` of the normalised Gaussian
+    ``g_k ~ exp(-(k - r)^2 / (2 sigma^2))``, the centre tap corrected so that the sum is exactly 65536.  ValueError for a sigma
+    that is not finite, or whose radius is outside 1 .. 16 (what ``bq_tissue_focus`` takes)."""
+    sigma = float(sigma)
+    if not math.isfinite(sigma) or sigma <= 0:
+        raise ValueError(f'focus_sigma must be a positive finite number, not {sigma!r}')
+    r = int(4.0 * sigma + 0.5)
+    if not 1 <= r <= FOCUS_MAX_RADIUS:
+        raise ValueError(f'focus_sigma {sigma!r} gives a radius of {r}; the kernel takes 1 .. {FOCUS_MAX_RADIUS}')
+    x = np.arange(-r, r + 1, dtype=np.float64)
+    g = np.exp(-0.5 * x * x / (sigma * sigma))
+    g /= g.sum()
+    w = np.rint(g * (1 << FOCUS_TAP_SHIFT)).astype(np.int64)
+    w[r] += (1 << FOCUS_TAP_SHIFT) - int(w.sum())
+    assert int(w.sum()) == 1 << FOCUS_TAP_SHIFT and int(w.min()) >= 0
+    return w.astype(np.int32)
+
+
+def focus_units(threshold=FOCUS_THRESHOLD):
+    """``thr = floor(threshold * FOCUS_SCALE)``: a pixel is out of focus iff ``V <= thr`` (51 000 for 0.02).  ValueError for a
+    threshold that is not finite, negative, or beyond int32 in units."""
+    t = float(threshold)
+    if not math.isfinite(t) or t < 0.0:
+        raise ValueError(f'focus_threshold must be a finite number >= 0, not {threshold!r}')
+    thr = math.floor(t * FOCUS_SCALE)
+    if thr >= 1 << 31:
+        raise ValueError(f'focus_threshold {threshold!r} is beyond every value the blurred Laplacian takes (at most 4)')
+    return int(thr)
+
+
+def focus_width(slide_w0, mpp, focus_mpp=FOCUS_MPP):
+    """The focus thumbnail's width: ``max(1, min(slide_w0, round(slide_w0 * mpp / focus_mpp)))``."""
+    return max(1, min(int(slide_w0), int(round(int(slide_w0) * float(mpp) / float(focus_mpp)))))
+
+
+def plane_map(n_to, n_from):
+    """int32 [n_to]: ``m[i] = ((2 i + 1) n_from) // (2 n_to)`` in Python integers -- the pixel of an ``n_from``-long axis that the
+    centre of pixel ``i`` of an ``n_to``-long axis falls into (a nearest-neighbour resize).  Non-decreasing, inside [0, n_from)."""
+    if int(n_to) != n_to or int(n_from) != n_from or n_to < 1 or n_from < 1 or n_from >= 1 << 31:
+        raise ValueError(f'plane_map takes two positive lengths, not {n_to!r} and {n_from!r}')
+    n_to, n_from = int(n_to), int(n_from)
+    return np.array([((2 * i + 1) * n_from) // (2 * n_to) for i in range(n_to)], np.int32)
+
+
+def check_focus(threshold, mpp=FOCUS_MPP, sigma=FOCUS_SIGMA):
+    """-> (thr in integer units, focus_mpp, the taps); ValueError as ``focus_units`` / ``focus_taps``, and for a ``focus_mpp`` that
+    is not a positive finite number."""
+    thr = focus_units(threshold)
+    m = float(mpp)
+    if not math.isfinite(m) or m <= 0.0:
+        raise ValueError(f'focus_mpp must be a positive finite number, not {mpp!r}')
+    return thr, m, focus_taps(sigma)

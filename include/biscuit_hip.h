@@ -276,6 +276,31 @@ int bq_tissue_blur(bq_ctx* ctx, const uint8_t* d_thumb, int H, int W, const int3
 int bq_tissue_cells(bq_ctx* ctx, const uint8_t* d_plane, int H, int W, int T, const int32_t* col_ranges, int gw,
                     const int32_t* row_ranges, int gh, int32_t* d_ranges, int32_t* d_count, bq_stream_t stream);
 
+/* The heatmap's focus mask (kernels_focus.hip; DESIGN.md "Heatmap input", Focus mask): Slideflow's Gaussian blur QC on a 4 um /
+ * pixel thumbnail, restated in integers (from memory: unpinned against Slideflow and scikit-image; pinned to scipy.ndimage in float64
+ * within a derived band by a CPU test).  bq_tissue_focus: d_thumb uint8 [H][W][3] ->
+ *     G = 2125 r + 7154 g + 721 b                                   (scikit-image's luma weights x 10 000; 2 550 000 per unit)
+ *     L = |4 G(y,x) - G(y-1,x) - G(y+1,x) - G(y,x-1) - G(y,x+1)|    (coordinates clamped to the image)
+ *     A(y,x) = (sum_k w[k] L(y, clamp(x + k - r)) + 32768) >> 16    (d_work, int32 [H][W], caller-owned)
+ *     V(y,x) = (sum_k w[k] A(clamp(y + k - r), x) + 32768) >> 16    (64-bit sums; d_value_or_null int32 [H][W] receives V if given)
+ * d_plane uint8 [H][W] = 1 where V > thr (in focus), 0 where V <= thr (out of focus); d_count, one int32, = the number of zeros
+ * (zeroed by the call, one add per workgroup).  d_taps int32 [2 r + 1] is the host's table in device memory (tissue.focus_taps:
+ * rint(65536 g_k) of the normalised Gaussian, the centre corrected so that the sum is 65536, every tap >= 0) and is not checked.
+ * Two launches.  0 < H, W, H * W < 2^31, 1 <= r <= 16, 0 <= thr.
+ * bq_tissue_cells_union: d_count[gy][gx] (int32 [gh][gw]) = the pixels (x, y) of the cell's range of the Otsu plane d_otsu_plane
+ * uint8 [Ho][Wo] with d_otsu_plane[y][x] <= T or d_focus_plane[ymap[y]][xmap[x]] == 0, d_focus_plane uint8 [Hf][Wf].  xmap int32
+ * [Wo], ymap int32 [Ho] (tissue.plane_map: ((2 i + 1) n_focus) / (2 n_otsu), a nearest-neighbour resize) and the two range tables
+ * (as bq_tissue_cells') are HOST memory: checked here -- ranges non-empty and inside the Otsu plane, maps inside the focus plane and
+ * non-decreasing -- then copied into d_tables (device, int32 [Wo + Ho + 2 (gw + gh)], caller-owned) on `stream`; they must stay
+ * valid until the stream has passed the call.  0 <= T <= 255, 0 < gw, gh <= 32768, both planes below 2^31 pixels.
+ * Both allocate nothing and are enqueued on `stream` without a host synchronisation; a bad argument is BQ_ERR_ARG with nothing
+ * enqueued. */
+int bq_tissue_focus(bq_ctx* ctx, const uint8_t* d_thumb, int H, int W, const int32_t* d_taps, int r, int thr, int32_t* d_work,
+                    int32_t* d_value_or_null, uint8_t* d_plane, int32_t* d_count, bq_stream_t stream);
+int bq_tissue_cells_union(bq_ctx* ctx, const uint8_t* d_otsu_plane, int Ho, int Wo, int T, const uint8_t* d_focus_plane, int Hf, int Wf,
+                          const int32_t* xmap, const int32_t* ymap, const int32_t* col_ranges, int gw, const int32_t* row_ranges,
+                          int gh, int32_t* d_tables, int32_t* d_count, bq_stream_t stream);
+
 /* Variant for callers that already hold standardised float32 NHWC tiles (the
  * UncertaintyInterface contract, results.py:256-257): converts to planar NCHW. */
 int bq_stage_f32(bq_ctx* ctx, const float* d_tiles_nhwc_f32, int n, void* d_out_nchw,

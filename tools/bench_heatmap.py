@@ -34,7 +34,15 @@ restatement (``tests/_render_ref.py``) on the same inputs, and checks that the t
 ``--qc`` times ``from_slide(qc=...)`` at the first ``--stride-div`` value -- 'off' passes no mask -- and prints the tiles run, the
 mask's own report (``hm.qc``) and, for 'otsu', the host seconds of ``WSI.thumbnail`` and the device milliseconds of
 ``Engine.tissue_blur`` and ``Engine.tissue_cells`` alone (device events around 20 launches) on that thumbnail.  Run the two values
-in separate, alternating processes."""
+in separate, alternating processes.
+
+    python tools/bench_heatmap.py --out DIR --qc otsu --qc-focus --stride-div 1      # the focus mask on top (Slideflow's 'both')
+    python tools/bench_heatmap.py --out DIR --qc off --qc-focus --stride-div 1       # the focus mask alone
+
+``--qc-focus [THRESHOLD]`` (with ``--qc``; bare: 0.02) passes ``focus_threshold`` as well and prints, as ``focus_mask_parts``, the
+host seconds of the 4 um / pixel thumbnail and the device milliseconds of ``Engine.tissue_focus`` on it and of
+``Engine.tissue_cells`` / ``Engine.tissue_cells_union`` behind it.  The tool's slide has no out-of-focus region: what the mask
+skips on a real slide (``qc_report``: ``cells_dropped``, ``bands_skipped_rows``, ``focus_share``) needs ``--slide`` with one."""
 import argparse
 import json
 import os
@@ -191,6 +199,8 @@ def qc_leg(args, eng, slide, tag, emit, kw):
     sd = args.stride_div[0]
     if args.qc != 'off':
         kw = dict(kw, qc=args.qc, qc_width=args.qc_width)
+    if args.qc_focus is not None:
+        kw = dict(kw, focus_threshold=args.qc_focus)
     times = []
     for r in range(args.runs + 1):                                          # the first call is the warm-up
         torch.cuda.synchronize()
@@ -201,24 +211,25 @@ def qc_leg(args, eng, slide, tag, emit, kw):
             times.append(time.perf_counter() - t0)
     np.savez(os.path.join(args.out, f'arrays_{tag}.npz'), logits=hm.logits, uncertainty=hm.uncertainty)
     cells, med = int(hm.logits.shape[0] * hm.logits.shape[1]), float(np.median(times))
-    emit({'what': 'from_slide_qc', 'qc': args.qc, 'stride_div': sd, 'mc': args.mc, 'cells': cells, 'tiles_run': int(len(hm.grid)),
+    emit({'what': 'from_slide_qc', 'qc': args.qc, 'qc_focus': args.qc_focus, 'stride_div': sd, 'mc': args.mc, 'cells': cells, 'tiles_run': int(len(hm.grid)),
           'dropped': int(hm.dropped), 'qc_report': hm.qc, 'seconds': [round(t, 4) for t in times], 'median_s': round(med, 4),
           'spread': round((max(times) - min(times)) / med, 4)})
-    if args.qc == 'off':
+    if args.qc == 'off' and args.qc_focus is None:
         return
-    w = WSI(slide, stride_div=sd)
-    try:
-        host = []
-        for _ in range(3):
-            t0 = time.perf_counter()
-            thumb = np.ascontiguousarray(w.thumbnail(args.qc_width))
-            host.append(time.perf_counter() - t0)
-        col, row = tissue.cell_ranges(w.grid_w, w.grid_h, thumb.shape[1], thumb.shape[0], *w.slide.dimensions, w.stride, w.extract_px)
-    finally:
-        w.close()
-    d_thumb = torch.from_numpy(thumb if thumb.flags.writeable else thumb.copy()).to(eng.device)
-    plane, hist = eng.tissue_blur(d_thumb)
-    thr = tissue.otsu_threshold(hist.cpu().numpy())
+
+    def thumb_of(width_of):
+        """-> (the thumbnail, its cells' ranges, the host seconds of three reads)."""
+        w = WSI(slide, stride_div=sd)
+        try:
+            host = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                thumb = np.ascontiguousarray(w.thumbnail(width_of(w)))
+                host.append(time.perf_counter() - t0)
+            col, row = tissue.cell_ranges(w.grid_w, w.grid_h, thumb.shape[1], thumb.shape[0], *w.slide.dimensions, w.stride, w.extract_px)
+        finally:
+            w.close()
+        return thumb, col, row, host
 
     def ms(fn, reps=20):
         for _ in range(3):
@@ -230,9 +241,30 @@ def qc_leg(args, eng, slide, tag, emit, kw):
         b.record()
         b.synchronize()
         return round(a.elapsed_time(b) / reps, 4)
-    emit({'what': 'tissue_mask_parts', 'thumb': list(thumb.shape[:2]), 'grid': [len(row), len(col)], 'threshold': thr,
-          'thumbnail_host_s': [round(t, 4) for t in host], 'tissue_blur_ms': ms(lambda: eng.tissue_blur(d_thumb)),
-          'tissue_cells_ms': ms(lambda: eng.tissue_cells(plane, thr, col, row))})
+
+    up = lambda t: torch.from_numpy(t if t.flags.writeable else t.copy()).to(eng.device)       # noqa: E731
+    plane = thr = None
+    if args.qc != 'off':
+        thumb, col, row, host = thumb_of(lambda w: args.qc_width)
+        d_thumb = up(thumb)
+        plane, hist = eng.tissue_blur(d_thumb)
+        thr = tissue.otsu_threshold(hist.cpu().numpy())
+        emit({'what': 'tissue_mask_parts', 'thumb': list(thumb.shape[:2]), 'grid': [len(row), len(col)], 'threshold': thr,
+              'thumbnail_host_s': [round(t, 4) for t in host], 'tissue_blur_ms': ms(lambda: eng.tissue_blur(d_thumb)),
+              'tissue_cells_ms': ms(lambda: eng.tissue_cells(plane, thr, col, row))})
+    if args.qc_focus is None:
+        return
+    fthumb, fcol, frow, fhost = thumb_of(lambda w: tissue.focus_width(w.slide.dimensions[0], w.mpp))
+    d_fthumb = up(fthumb)
+    fplane, fcount = eng.tissue_focus(d_fthumb, args.qc_focus)
+    parts = {'what': 'focus_mask_parts', 'thumb': list(fthumb.shape[:2]), 'grid': [len(frow), len(fcol)], 'focus_threshold': args.qc_focus,
+             'focus_share': int(fcount.cpu().numpy()[0]) / float(fthumb.shape[0] * fthumb.shape[1]),
+             'thumbnail_host_s': [round(t, 4) for t in fhost], 'tissue_focus_ms': ms(lambda: eng.tissue_focus(d_fthumb, args.qc_focus))}
+    if plane is None:
+        parts['tissue_cells_ms'] = ms(lambda: eng.tissue_cells(fplane, 0, fcol, frow))
+    else:
+        parts['tissue_cells_union_ms'] = ms(lambda: eng.tissue_cells_union(plane, thr, fplane, col, row))
+    emit(parts)
 
 
 def render_leg(args, eng, emit):
@@ -290,9 +322,13 @@ def main():
     ap.add_argument('--qc', default=None, choices=['off', 'otsu'],
                     help="the tissue-mask leg only: from_slide without ('off') or with the mask, and the mask's own pieces")
     ap.add_argument('--qc-width', type=int, default=2048)
+    ap.add_argument('--qc-focus', type=float, nargs='?', const=0.02, default=None, metavar='THRESHOLD',
+                    help="with --qc: pass focus_threshold too (bare: 0.02) and time the focus mask's own pieces")
     args = ap.parse_args()
+    if args.qc_focus is not None and args.qc is None:
+        ap.error("--qc-focus belongs to the tissue-mask leg: give --qc off (the focus mask alone) or --qc otsu")
     os.makedirs(args.out, exist_ok=True)
-    tag = args.tag or ('render' if args.render else 'qc_' + args.qc if args.qc is not None else
+    tag = args.tag or ('render' if args.render else 'qc_' + args.qc + ('_focus' if args.qc_focus is not None else '') if args.qc is not None else
                        args.resample if args.decode is None else 'decode_' + args.decode)
     slide = args.slide or os.path.join(args.out, 'bench_slide.svs' if args.decode is None else 'bench_slide_jpeg.svs')
     gw, gh = (int(v) for v in args.grid.lower().split('x'))
