@@ -52,6 +52,7 @@ ABI = {
     'bq_tissue_cells': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     'bq_tissue_focus': (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'bq_tissue_cells_union': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    'bq_roi_plane': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     'bq_stream_create_masked': (_i, [_vp, C.POINTER(C.c_uint32), _i, C.POINTER(_vp)]),
     'bq_stream_destroy': (_i, [_vp, _vp]),
     'bq_set_num_cus': (_i, [_vp, _i]),

@@ -2,6 +2,7 @@
 // the Xception launch schedule, the MC-dropout head and event-based per-kernel timing.
 #include "../../include/biscuit_hip.h"
 #include "bq_common.h"
+#include "roi_device.h"
 
 #include <math.h>
 #include <cmath>
@@ -1194,6 +1195,24 @@ int bq_tissue_cells_union(bq_ctx* c, const uint8_t* d_otsu_plane, int Ho, int Wo
     HIPCHK(c, hipMemcpyAsync(d_row, row_ranges, (size_t)gh * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (launch_tissue_cells_union(d_otsu_plane, Ho, Wo, T, d_focus_plane, Hf, Wf, d_xmap, d_ymap, d_col, d_row, gw, gh, d_count, s))
         return fail(c, BQ_ERR_HIP, "tissue cells union launch failed");
+    return BQ_OK;
+}
+
+int bq_roi_plane(bq_ctx* c, const int32_t* edges, int E, const int32_t* starts, int P, const int32_t* xs, int W, const int32_t* ys, int H,
+                 int32_t* d_tables, uint8_t* d_plane, bq_stream_t stream) {
+    if (!c || !d_tables || !d_plane || ((uintptr_t)d_tables & 15)) return fail(c, BQ_ERR_ARG, "bq_roi_plane: bad argument");
+    if (const char* why = bqroi::check_tables(edges, E, starts, P, xs, W, ys, H)) return fail(c, BQ_ERR_ARG, std::string("bq_roi_plane: ") + why);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "roi_plane", 0.0, (double)H * W);
+    int32_t* d_edges = d_tables;                                             // (first: the kernel loads an edge as 16 bytes)
+    int32_t* d_starts = d_edges + (size_t)4 * E;
+    int32_t* d_xs = d_starts + P + 1;
+    int32_t* d_ys = d_xs + W;
+    HIPCHK(c, hipMemcpyAsync(d_edges, edges, (size_t)4 * E * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_starts, starts, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_xs, xs, (size_t)W * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_ys, ys, (size_t)H * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (launch_roi_plane(d_edges, E, d_starts, P, d_xs, d_ys, H, W, d_plane, s)) return fail(c, BQ_ERR_HIP, "roi plane launch failed");
     return BQ_OK;
 }
 

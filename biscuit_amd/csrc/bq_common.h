@@ -156,6 +156,10 @@ int launch_tissue_focus(const uint8_t* thumb, int H, int W, const int* taps, int
                         int* count, hipStream_t s);
 int launch_tissue_cells_union(const uint8_t* otsu, int Ho, int Wo, int T, const uint8_t* focus, int Hf, int Wf, const int* xmap,
                               const int* ymap, const int* col, const int* row, int gw, int gh, int* count, hipStream_t s);
+// kernels_roi.hip: the region-of-interest mask (DESIGN.md "Heatmap input", Region-of-interest mask): polygons -> the plane of the
+// sample points inside any of them (roi_device.h's crossing rule); every table is device memory here, `edges` 16-byte aligned
+int launch_roi_plane(const int* edges, int E, const int* starts, int P, const int* xs, const int* ys, int H, int W, uint8_t* plane,
+                     hipStream_t s);
 int launch_stem1(const void* in_nchw, int n, const float* w27x32, const float* scale,
                  const float* bias, void* out_nhwc, int dtype, hipStream_t s);
 int launch_pool_add(const void* y, const void* res, void* out, int n, int Hi, int Wi, int C,

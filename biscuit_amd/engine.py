@@ -83,6 +83,7 @@ class Engine:
         self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
         self._tissue_host = None         # the range tables of the last tissue_cells call, alive while the stream copies them
         self._tissue_taps = {}           # sigma -> (the Gaussian's taps on the device, r) (tissue_focus)
+        self._roi_host = []              # (event, host tables) of the roi_plane calls the stream may not have passed yet
         self._elt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[dtype]
 
     # shapes of the stored tensors by debug-tap name
@@ -471,6 +472,33 @@ class Engine:
                                                     xmap.ctypes.data, ymap.ctypes.data, col.ctypes.data, gw, row.ctypes.data, gh,
                                                     _ptr(tables), _ptr(count), self._stream()))
         return count
+
+    def roi_plane(self, xs, ys, polygons):
+        """The region-of-interest mask's plane (``bq_roi_plane``, kernels_roi.hip; DESIGN.md "Heatmap input", Region-of-interest
+        mask): ``xs`` int32 [W] / ``ys`` int32 [H], the doubled level-0 coordinates of the sample points (``roi.center_tables`` /
+        ``roi.raster_tables``; host arrays, every entry in [0, 2^29]), and ``polygons``, a list of int [n >= 3, 2] arrays of (x, y)
+        vertices in level-0 pixels (``roi.check_polygons``) -> uint8 [H, W] on the device: 1 where (xs[x], ys[y]) lies inside any
+        polygon (even-odd per polygon, union across polygons), the integers of the numpy restatement.  ValueError for a polygon
+        ``roi.check_polygons`` refuses, a table of another shape or range, and ``H * W >= 2^31``."""
+        from . import roi
+        edges, starts = roi.edge_table(polygons)
+        xs, ys = np.ascontiguousarray(xs, np.int32), np.ascontiguousarray(ys, np.int32)
+        if xs.ndim != 1 or ys.ndim != 1 or len(xs) < 1 or len(ys) < 1 or len(xs) * len(ys) >= 1 << 31:
+            raise ValueError('xs and ys must be int32 [W] and [H] with 1 <= W, H and H * W < 2^31')
+        for name, t in (('xs', xs), ('ys', ys)):
+            if (t < 0).any() or (t > roi.SAMPLE_MAX).any():
+                raise ValueError(f'{name}: a doubled sample coordinate leaves [0, 2^29]')
+        w, h = len(xs), len(ys)
+        tables = torch.empty(edges.size + len(starts) + w + h, dtype=torch.int32, device=self.device)     # (the allocator aligns to 16)
+        plane = torch.empty((h, w), dtype=torch.uint8, device=self.device)
+        self._check(self._lib.bq_roi_plane(self._ctx, edges.ctypes.data, len(edges), starts.ctypes.data, len(starts) - 1, xs.ctypes.data,
+                                           w, ys.ctypes.data, h, _ptr(tables), _ptr(plane), self._stream()))
+        # the host tables must stay valid until the stream has passed the call: each call's are held until an event recorded
+        # behind it has completed (queried, never waited for), so back-to-back calls do not release one another's
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(self.device))
+        self._roi_host = [(e, t) for e, t in self._roi_host if not e.query()] + [(done, (edges, starts, xs, ys))]
+        return plane
 
     def reinhard_fast(self, tiles_u8, target_means, target_stds, out=None):
         """`reinhard_fast` stain normalisation (hp.py:19; results.py:251-252 `wsi_normalizer.rgb_to_rgb`):

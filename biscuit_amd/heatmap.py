@@ -52,6 +52,8 @@ class Heatmap:
     _slide_kw = None
     # the tissue mask ``from_slide(cell_mask=..., qc=...)`` ran under: the bool [gh, gw] mask and what it did; None without one
     cell_mask = qc = None
+    # what ``from_slide(rois=...)`` did: {'method', 'filter', 'polygons', 'vertices', 'cells_dropped'}; None without ROIs
+    roi = None
 
     def __init__(self, engine, tiles, grid, grid_shape=None, mc_n=30, seed=0, batch=256, norm_fit=None, normalizer='reinhard_fast'):
         """tiles: uint8 [T,299,299,3] (host or device); grid: int [T,2] (gx, gy) cell of each tile.  ``norm_fit`` / ``normalizer``:
@@ -96,7 +98,8 @@ class Heatmap:
     @classmethod
     def from_slide(cls, engine, path, tile_px=299, tile_um=302, stride_div=1, mpp=None, resample='gpu', canvas_bytes=256 << 20,
                    grayspace_fraction=None, grayspace_threshold=0.05, decode='host', cell_mask=None, qc=None, qc_width=2048,
-                   qc_fraction=0.6, focus_threshold=None, focus_mpp=4.0, focus_sigma=3.0, **kw):
+                   qc_fraction=0.6, focus_threshold=None, focus_mpp=4.0, focus_sigma=3.0, rois=None, roi_method='auto',
+                   roi_filter_method='center', roi_width=2048, **kw):
         """``sf.Heatmap(slide, model, stride_div=1)`` (results.py:217) for a pyramidal TIFF / SVS slide file: the tile grid of
         ``wsi.WSI(path, tile_px, tile_um, stride_div)`` through the MC-dropout kernels.  (The reader is this build's own --
         ``biscuit_amd/wsi.py`` says what it reads and what about it is unpinned.)
@@ -143,8 +146,22 @@ class Heatmap:
         focus_threshold=0.02`` -- a pixel of the Otsu plane is then bad when it is background or when the focus plane, resized
         onto it by nearest neighbour, says out of focus (``Engine.tissue_cells_union``), and ``qc_fraction`` judges the union.
         ``cell_mask`` still ANDs on top.  ``self.qc`` then also holds ``focus_threshold``, ``focus_width`` and ``focus_share``
-        (out-of-focus pixels / all pixels of the focus thumbnail)."""
-        from . import tissue
+        (out-of-focus pixels / all pixels of the focus thumbnail).
+
+        ``rois`` (``resample='gpu'`` only; default None = off): the pathologist's regions of interest, Slideflow's ROI filter
+        restated from memory in integers, unpinned (DESIGN.md "Heatmap input", Region-of-interest mask) -- the path of a
+        ``ROI_Name,X_base,Y_base`` CSV file (``roi.read_csv``) or a list of int [n, 2] arrays of (x, y) vertices in level-0
+        pixels, one polygon each (even-odd inside a polygon, the union across polygons).  ``roi_method``: 'inside' keeps the
+        cells inside the region, 'outside' the others, 'auto' is 'inside' with ``rois`` and 'ignore' without, 'ignore' does
+        nothing.  ``roi_filter_method='center'`` judges a cell by its centre; a share f in (0, 1] keeps a cell when at least f
+        of its pixels on a ``roi_width``-wide raster of the slide (the thumbnail's geometry; nothing is read) lie inside --
+        for 'outside', outside.  The polygons become a plane on the device (``Engine.roi_plane``; ``roi.py``), a share is counted
+        by ``Engine.tissue_cells``.  The mask ANDs with ``cell_mask``, ``qc`` and ``focus_threshold`` and acts as they do: only
+        bands that hold a kept cell are read, dropped cells hold ``MASKED``, a kept cell's values do not depend on it.
+        ``self.roi = {'method', 'filter', 'polygons', 'vertices', 'cells_dropped'}`` says what it did (the method used; 'center'
+        or the share; the polygons and their vertices; cells this mask alone drops); ``self.qc`` keeps its keys."""
+        import os
+        from . import roi, tissue
         from .wsi import WSI
         if resample not in ('gpu', 'host'):
             raise ValueError(f"resample must be 'gpu' or 'host', not {resample!r}")
@@ -167,6 +184,13 @@ class Heatmap:
             if resample == 'host':
                 raise ValueError("the focus mask steers the streamed read: focus_threshold needs resample='gpu'")
             tissue.check_fraction(qc_fraction)
+        roi_filter, roi_width = roi.check_filter(roi_filter_method), roi.check_width(roi_width)      # (its keywords, on or off)
+        polygons = None
+        if rois is not None:
+            polygons = roi.read_csv(rois) if isinstance(rois, (str, os.PathLike)) else roi.check_polygons(rois)
+        roi_method = roi.check_method(roi_method, polygons is not None)
+        if roi_method != 'ignore' and resample == 'host':
+            raise ValueError("the region-of-interest mask steers the streamed read: rois needs resample='gpu'")
         w = WSI(path, tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
         try:
             if w.grid_w * w.grid_h == 0:
@@ -186,9 +210,17 @@ class Heatmap:
                 elif qc is not None:
                     qc_keep, threshold = cls._otsu_mask(engine, w, int(qc_width), qc_fraction)
                     keep = qc_keep if keep is None else keep & qc_keep
+                roi_info = None
+                if roi_method != 'ignore':
+                    roi_keep = cls._roi_mask(engine, w, polygons, roi_method, roi_filter, roi_width)
+                    roi_info = {'method': roi_method, 'filter': roi_filter, 'polygons': len(polygons),
+                                'vertices': int(sum(len(a) for a in polygons)), 'cells_dropped': int(roi_keep.size - roi_keep.sum())}
+                    keep = roi_keep if keep is None else keep & roi_keep
                 hm = cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, decode=decode, keep=keep, **kw)
                 if keep is not None:
                     hm.qc = dict(hm.qc, method=qc, threshold=threshold, **(focus or {}))
+                if roi_info is not None:
+                    hm.roi = roi_info
             hm.slide_path, (hm.slide_w0, hm.slide_h0), hm.stride, hm.extract_px = path, w.slide.dimensions, w.stride, w.extract_px
             hm._slide_kw = dict(tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
             return hm
@@ -235,6 +267,20 @@ class Heatmap:
             counts = engine.tissue_cells_union(oplane, threshold, fplane, col, row)
         info = {'focus_threshold': float(focus_threshold), 'focus_width': fw, 'focus_share': int(fcount.cpu().numpy()[0]) / float(fh * fw)}
         return tissue.keep_from_counts(counts.cpu().numpy(), col, row, qc_fraction), threshold, info
+
+    @staticmethod
+    def _roi_mask(engine, w, polygons, method, roi_filter, roi_width):
+        """``rois=...`` for the open slide ``w`` -> keep bool [grid_h, grid_w].  'center': the plane of the cells' centres comes
+        back; a share: the plane is made on a ``roi_width``-wide raster and stays on the device, the cells' counts come back."""
+        from . import roi, tissue
+        if roi_filter == 'center':
+            xs, ys = roi.center_tables(w.grid_w, w.grid_h, w.stride, w.extract_px)
+            return roi.keep_from_plane(engine.roi_plane(xs, ys, polygons).cpu().numpy(), method)
+        sw, sh = w.slide.dimensions
+        xs, ys = roi.raster_tables(sw, sh, roi_width)
+        col, row = tissue.cell_ranges(w.grid_w, w.grid_h, len(xs), len(ys), sw, sh, w.stride, w.extract_px)
+        outside = engine.tissue_cells(engine.roi_plane(xs, ys, polygons), 0, col, row).cpu().numpy()
+        return roi.keep_from_share(outside, col, row, roi_filter, method)
 
     @classmethod
     @staticmethod
@@ -464,7 +510,9 @@ def main(argv=None):
     tiles as ``uq_incl/`` / ``uq_excl/`` PNGs named as results.py:259 names them.  ``--qc otsu`` masks the slide's background from
     its thumbnail first (``from_slide(qc='otsu')``): ``heatmap.npz`` then also holds ``cell_mask`` and ``summary.json`` a ``qc``
     entry.  ``--qc-focus [THRESHOLD]`` (bare: 0.02) masks its out-of-focus regions (``from_slide(focus_threshold=...)``), alone or
-    with ``--qc otsu`` (Slideflow's ``qc='both'``), and writes the same two.  ``--render`` adds the pictures of
+    with ``--qc otsu`` (Slideflow's ``qc='both'``), and writes the same two.  ``--rois FILE`` runs only the cells that the polygons of a
+    Slideflow ROI CSV select (``from_slide(rois=...)``; ``--roi-method``, ``--roi-filter``, ``--roi-width``): ``heatmap.npz`` then holds
+    ``cell_mask`` and ``summary.json`` a ``roi`` entry.  ``--render`` adds the pictures of
     ``Heatmap.save`` (results.py:217-227): ``<slide>-raw.png``, ``-0.png``, ``-1.png``, ``-uncertainty.png`` and, with ``--tile-uq``,
     the masked pair under ``high_confidence/``; ``summary.json`` then lists them as ``rendered``."""
     import argparse
@@ -498,6 +546,14 @@ def main(argv=None):
                          "with --qc otsu (Slideflow's qc='both'): adds cell_mask to heatmap.npz and qc to summary.json; default: off")
     ap.add_argument('--qc-focus-mpp', type=float, default=4.0, help='microns per pixel of the thumbnail --qc-focus judges')
     ap.add_argument('--qc-focus-sigma', type=float, default=3.0, help="sigma of --qc-focus's Gaussian, in thumbnail pixels")
+    ap.add_argument('--rois', default=None, metavar='FILE',
+                    help="regions of interest, Slideflow's ROI_Name,X_base,Y_base CSV (from_slide(rois=...)): only the cells the "
+                         'polygons select are run; adds cell_mask to heatmap.npz and roi to summary.json; default: off')
+    ap.add_argument('--roi-method', default='auto', choices=['auto', 'inside', 'outside', 'ignore'],
+                    help="keep the cells inside the regions or outside them; 'auto': inside when --rois is given")
+    ap.add_argument('--roi-filter', default='center', metavar='center|SHARE',
+                    help="judge a cell by its centre, or keep it when at least SHARE (0 < SHARE <= 1) of it lies inside")
+    ap.add_argument('--roi-width', type=int, default=2048, help='width of the raster a --roi-filter SHARE is counted on')
     ap.add_argument('--gpu-decode', action='store_true',
                     help="decode the slide's own JPEG tiles on the device (from_slide(decode='gpu')); the arrays do not change")
     ap.add_argument('--mpp', type=float, default=None, help='microns per pixel, for a file that does not say')
@@ -510,6 +566,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.save_tiles and args.tile_uq is None:
         ap.error('--save-tiles sorts by --tile-uq')
+    roi_filter = args.roi_filter
+    if roi_filter != 'center':
+        try:
+            roi_filter = float(roi_filter)
+        except ValueError:
+            ap.error(f"--roi-filter takes 'center' or a share in (0, 1], not {args.roi_filter!r}")
     from .__main__ import load_model_weights, model_hp_from
     from .engine import Engine
     weights, model_params = load_model_weights(args.model, args.weights)
@@ -523,7 +585,8 @@ def main(argv=None):
                                 grayspace_fraction=args.grayspace_fraction, grayspace_threshold=args.grayspace_threshold,
                                 decode='gpu' if args.gpu_decode else 'host', qc=args.qc, qc_width=args.qc_width,
                                 qc_fraction=args.qc_fraction, focus_threshold=args.qc_focus, focus_mpp=args.qc_focus_mpp,
-                                focus_sigma=args.qc_focus_sigma)
+                                focus_sigma=args.qc_focus_sigma, rois=args.rois, roi_method=args.roi_method,
+                                roi_filter_method=roi_filter, roi_width=args.roi_width)
         torch.cuda.synchronize(eng.device)
         seconds = time.perf_counter() - t0
         rendered = None
@@ -551,7 +614,7 @@ def main(argv=None):
                         Image.fromarray(w._tile(int(gx), int(gy))).save(os.path.join(args.out, name, fname))
             finally:
                 w.close()
-    if args.qc is not None or args.qc_focus is not None:
+    if args.qc is not None or args.qc_focus is not None or hm.roi is not None:
         arrays['cell_mask'] = hm.cell_mask
     np.savez(os.path.join(args.out, 'heatmap.npz'), **arrays)
     run = int(len(hm.grid))
@@ -559,6 +622,8 @@ def main(argv=None):
                'seconds': seconds, 'tiles_per_s': run / seconds if seconds > 0 else None, 'decode_stats': hm.decode_stats}
     if args.qc is not None or args.qc_focus is not None:
         summary['qc'] = hm.qc
+    if hm.roi is not None:
+        summary['roi'] = hm.roi
     if rendered is not None:
         summary['rendered'] = rendered
     with open(os.path.join(args.out, 'summary.json'), 'w') as f:

@@ -43,6 +43,7 @@ ABI = {
     'bqio_resample_ksize': (_i, [_i, _i]),
     'bqio_resample_taps': (_i, [_i, _i, _vp, _vp, _i]),
     'bqio_tile_resample': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
+    'bqio_roi_plane': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
     'bqio_masked_crc32c': (C.c_uint32, [C.c_char_p, C.c_size_t]),
     'bqio_inflate': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t]),
     'bqio_inflate2': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t, C.c_char_p, C.c_size_t, _vp, C.c_size_t,

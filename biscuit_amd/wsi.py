@@ -352,14 +352,16 @@ class WSI:
     with ``sf.WSI(slide, 299, 302, roi_method='ignore')`` (results.py:235).  ``extract_px`` = the tile's width in level-0 pixels
     (``tile_um / mpp``), the grid walks the slide at stride ``extract_px / stride_div`` (border remainders dropped), every tile is read
     from the pyramid level with the largest downsample that still has at least ``tile_px`` pixels per tile and resampled to
-    ``tile_px`` (Pillow LANCZOS).  ``roi_method``: only 'ignore' (what the reference passes) is implemented."""
+    ``tile_px`` (Pillow LANCZOS).  ``roi_method``: only 'ignore' (what the reference passes) is implemented here; regions of interest are
+    ``Heatmap.from_slide(rois=...)``'s."""
 
     READ_LIMIT = 1 << 16                 # pixels ``read_region`` reads at once, per side: ``bands`` splits wider grid rows
 
     @_guard
     def __init__(self, path, tile_px=TILE_PX, tile_um=TILE_UM, stride_div=1, roi_method='ignore', mpp=None):
         if roi_method != 'ignore':
-            raise NotImplementedError("only roi_method='ignore' (results.py:235)")
+            raise NotImplementedError("only roi_method='ignore' (results.py:235): the reader walks the whole grid; the region-of-interest "
+                                      "filter is Heatmap.from_slide(rois=..., roi_method=...)")
         self.slide = TiffSlide(path)
         try:
             self._layout(path, tile_px, tile_um, stride_div, mpp)

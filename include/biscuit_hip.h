@@ -301,6 +301,24 @@ int bq_tissue_cells_union(bq_ctx* ctx, const uint8_t* d_otsu_plane, int Ho, int 
                           const int32_t* xmap, const int32_t* ymap, const int32_t* col_ranges, int gw, const int32_t* row_ranges,
                           int gh, int32_t* d_tables, int32_t* d_count, bq_stream_t stream);
 
+/* The heatmap's region-of-interest mask (kernels_roi.hip; DESIGN.md "Heatmap input", Region-of-interest mask): a pathologist's
+ * polygons -> the grid cells inside them, Slideflow's ROI filter restated in integers (from memory: unpinned against Slideflow and
+ * shapely; pinned to a numpy restatement integer for integer).  bq_roi_plane: d_plane[y][x] (uint8 [H][W]) = 1 iff the sample point
+ * p = (xs[x], ys[y]) is inside any polygon, else 0.  All coordinates are DOUBLED level-0 pixels, so that a pixel centre is an
+ * integer; the kernel does no coordinate arithmetic.  edges int32 [E][4] = (a.x, a.y, b.x, b.y), one row per polygon edge a -> b
+ * (the closing edge included; roi.edge_table); starts int32 [P + 1]: polygon i owns edges [starts[i], starts[i + 1]).  An edge
+ * counts for p iff (a.y > p.y) != (b.y > p.y) and, with d = (b.x - a.x)(p.y - a.y) - (p.x - a.x)(b.y - a.y) in int64, d > 0 when
+ * b.y > a.y and d < 0 when b.y < a.y (csrc/roi_device.h, compiled for host and device): a point on an edge does not count for it,
+ * a horizontal edge never counts.  p is inside a polygon iff an odd number of its edges count (even-odd: self-intersection and zero
+ * area are legal) and inside the region iff inside any polygon (union).  The four tables are HOST memory and are checked here --
+ * 0 < W, H, H * W < 2^31, 3 <= E <= 2^20, starts[0] = 0, starts[P] = E, every polygon at least 3 edges, every edge coordinate in
+ * [-2^28, 2^28], every sample coordinate in [0, 2^29] (which keeps |d| < 2^62) -- then copied into d_tables (device, int32 [4 E +
+ * P + 1 + W + H], 16-byte aligned, caller-owned) on `stream`; they must stay valid until the stream has passed the call.  One
+ * launch.  Allocates nothing; enqueued on `stream` without a host synchronisation; a bad argument is BQ_ERR_ARG with nothing
+ * enqueued. */
+int bq_roi_plane(bq_ctx* ctx, const int32_t* edges, int E, const int32_t* starts, int P, const int32_t* xs, int W, const int32_t* ys,
+                 int H, int32_t* d_tables, uint8_t* d_plane, bq_stream_t stream);
+
 /* Variant for callers that already hold standardised float32 NHWC tiles (the
  * UncertaintyInterface contract, results.py:256-257): converts to planar NCHW. */
 int bq_stage_f32(bq_ctx* ctx, const float* d_tiles_nhwc_f32, int n, void* d_out_nchw,

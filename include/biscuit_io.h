@@ -155,6 +155,15 @@ int bqio_resample_taps(int src_px, int px, int32_t* bounds, int32_t* coef, int k
  * origin beyond +-2^28; n = 0 returns BQIO_OK and touches nothing.  For tests and the sanitizer build. */
 int bqio_tile_resample(const uint8_t* canvas, int H, int W, const int32_t* origin, int n, int src_px, int px, uint8_t* out);
 
+/* The CPU build of bq_roi_plane (include/biscuit_hip.h; csrc/roi_host.cpp over csrc/roi_device.h, the crossing rule and the table
+ * checks the GPU entry is compiled from): plane[y][x] (uint8 [H][W]) = 1 iff the doubled sample point (xs[x], ys[y]) is inside any
+ * polygon of the edge table -- edges int32 [E][4] = (a.x, a.y, b.x, b.y) doubled, starts int32 [P + 1] -- even-odd per polygon,
+ * union across polygons.  BQIO_ERR_ARG, with the plane untouched, for what bq_roi_plane refuses: W or H <= 0, H * W >= 2^31, E
+ * outside 3 .. 2^20, starts that do not run from 0 to E in steps of at least 3, an edge coordinate outside [-2^28, 2^28], a
+ * sample coordinate outside [0, 2^29], a null pointer.  For tests. */
+int bqio_roi_plane(const int32_t* edges, int E, const int32_t* starts, int P, const int32_t* xs, int W, const int32_t* ys, int H,
+                   uint8_t* plane);
+
 /* One JPEG file (as bqio_image_bytes returns it) -> out[tile_px][tile_px][3], the decoder
  * bqio_decode uses, exported for tests.  BQIO_OK / BQIO_ERR_UNSUPPORTED / BQIO_ERR_FORMAT. */
 int bqio_decode_jpeg(const uint8_t* data, size_t len, int tile_px, uint8_t* out);

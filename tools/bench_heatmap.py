@@ -42,7 +42,17 @@ in separate, alternating processes.
 ``--qc-focus [THRESHOLD]`` (with ``--qc``; bare: 0.02) passes ``focus_threshold`` as well and prints, as ``focus_mask_parts``, the
 host seconds of the 4 um / pixel thumbnail and the device milliseconds of ``Engine.tissue_focus`` on it and of
 ``Engine.tissue_cells`` / ``Engine.tissue_cells_union`` behind it.  The tool's slide has no out-of-focus region: what the mask
-skips on a real slide (``qc_report``: ``cells_dropped``, ``bands_skipped_rows``, ``focus_share``) needs ``--slide`` with one."""
+skips on a real slide (``qc_report``: ``cells_dropped``, ``bands_skipped_rows``, ``focus_share``) needs ``--slide`` with one.
+
+    python tools/bench_heatmap.py --out DIR --roi --stride-div 1             # the region-of-interest leg
+
+``--roi`` times ``Engine.roi_plane`` alone (device events around 20 calls, each with its table upload and one launch): on the
+'center' grid of a 100 000 x 80 000 pixel slide (167 x 133 cells of 598 pixels) under a 3 000-vertex cogwheel, on a 2 048-wide raster of
+the same slide under that cogwheel plus 40 small polygons, and on a 2 048 x 2 048 raster under a 10 000-vertex cogwheel (the design's
+worst case); the two rasters next to the wall time of the numpy restatement (``tests/_roi_ref.py``) on the same input, with a check
+that the planes are equal.  Then ``from_slide(rois=...)`` on the tool's slide (a cogwheel over its middle, a share of 0.5 on a
+2 048-wide raster) at the first ``--stride-div`` value next to the seconds of the mask alone (``Heatmap._roi_mask``, every result on
+the host): the share of the masked run that the mask takes."""
 import argparse
 import json
 import os
@@ -267,6 +277,85 @@ def qc_leg(args, eng, slide, tag, emit, kw):
     emit(parts)
 
 
+def roi_leg(args, eng, slide, tag, emit, kw):
+    """``--roi``: the rasteriser alone on three inputs, next to the numpy restatement, then the mask's share of a masked from_slide."""
+    import torch
+    sys.path.insert(0, HERE)
+    from biscuit_amd import roi
+    from biscuit_amd.heatmap import Heatmap
+    from biscuit_amd.wsi import WSI
+    from tests import _roi_ref as ref
+
+    def cog(cx, cy, r_out, r_in, n):
+        k = np.arange(n)
+        t = 2.0 * np.pi * k / n
+        r = np.where((k // 25) % 2 == 0, float(r_out), float(r_in))
+        return np.stack([np.rint(cx + r * np.cos(t)), np.rint(cy + r * np.sin(t))], 1).astype(np.int32)
+
+    def ms(fn, reps=20):
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        b.synchronize()
+        return round(a.elapsed_time(b) / reps, 4)
+
+    rng = np.random.default_rng(args.seed)
+    w0, h0 = 100_000, 80_000
+    ring = cog(w0 // 2, h0 // 2, 0.45 * h0, 0.3 * h0, 3000)
+    small = [np.stack([cx + rng.integers(-3000, 3001, 5), cy + rng.integers(-3000, 3001, 5)], 1).astype(np.int32)
+             for cx, cy in zip(rng.integers(0, w0, 40), rng.integers(0, h0, 40))]
+    gw, gh = (w0 - 598) // 598 + 1, (h0 - 598) // 598 + 1
+    inputs = [('center_grid', roi.center_tables(gw, gh, 598, 598), [ring], False),
+              ('raster_2048', roi.raster_tables(w0, h0, 2048), [ring] + small, True),
+              ('raster_2048x2048_10k_edges', roi.raster_tables(w0, w0, 2048), [cog(w0 // 2, w0 // 2, 0.45 * w0, 0.3 * w0, 10000)], True)]
+    for name, (xs, ys), polys, with_numpy in inputs:
+        d = {'what': 'roi_plane', 'input': name, 'plane': [len(ys), len(xs)], 'polygons': len(polys), 'edges': int(sum(len(a) for a in polys)),
+             'device_ms': ms(lambda: eng.roi_plane(xs, ys, polys))}
+        got = eng.roi_plane(xs, ys, polys).cpu().numpy()
+        d['inside_share'] = round(float(got.mean()), 4)
+        if with_numpy:
+            t0 = time.perf_counter()
+            want = ref.plane(xs, ys, polys)
+            d['numpy_ms'] = round((time.perf_counter() - t0) * 1e3, 1)
+            d['equal'] = bool(np.array_equal(got, want))
+        emit(d)
+    # the mask's share of a masked run, on the tool's slide
+    sd = args.stride_div[0]
+    w = WSI(slide, stride_div=sd)
+    sw, sh = w.slide.dimensions
+    polys = [cog(sw // 2, sh // 2, 0.45 * min(sw, sh), 0.3 * min(sw, sh), 3000)]
+    rkw = dict(rois=polys, roi_filter_method=0.5, roi_width=2048)
+    try:
+        alone = []
+        for r in range(args.runs + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            keep = Heatmap._roi_mask(eng, w, roi.check_polygons(polys), 'inside', 0.5, 2048)
+            torch.cuda.synchronize()
+            if r:
+                alone.append(time.perf_counter() - t0)
+    finally:
+        w.close()
+    times = []
+    for r in range(args.runs + 1):                                          # the first call is the warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        hm = Heatmap.from_slide(eng, slide, stride_div=sd, **rkw, **kw)
+        torch.cuda.synchronize()
+        if r:
+            times.append(time.perf_counter() - t0)
+    assert np.array_equal(hm.cell_mask, keep)
+    np.savez(os.path.join(args.out, f'arrays_{tag}.npz'), logits=hm.logits, uncertainty=hm.uncertainty, cell_mask=hm.cell_mask)
+    med, med_mask = float(np.median(times)), float(np.median(alone))
+    emit({'what': 'from_slide_roi', 'stride_div': sd, 'mc': args.mc, 'cells': int(keep.size), 'tiles_run': int(len(hm.grid)), 'roi_report': hm.roi,
+          'qc_report': hm.qc, 'seconds': [round(t, 4) for t in times], 'median_s': round(med, 4), 'mask_alone_s': [round(t, 5) for t in alone],
+          'mask_share_of_run': round(med_mask / med, 5), 'spread': round((max(times) - min(times)) / med, 4)})
+
+
 def render_leg(args, eng, emit):
     """``--render``: the kernel's milliseconds per picture and the numpy restatement's, same inputs, same bytes."""
     import torch
@@ -324,11 +413,13 @@ def main():
     ap.add_argument('--qc-width', type=int, default=2048)
     ap.add_argument('--qc-focus', type=float, nargs='?', const=0.02, default=None, metavar='THRESHOLD',
                     help="with --qc: pass focus_threshold too (bare: 0.02) and time the focus mask's own pieces")
+    ap.add_argument('--roi', action='store_true',
+                    help="the region-of-interest leg only: Engine.roi_plane next to its numpy restatement, and the mask's share of from_slide(rois=...)")
     args = ap.parse_args()
     if args.qc_focus is not None and args.qc is None:
         ap.error("--qc-focus belongs to the tissue-mask leg: give --qc off (the focus mask alone) or --qc otsu")
     os.makedirs(args.out, exist_ok=True)
-    tag = args.tag or ('render' if args.render else 'qc_' + args.qc + ('_focus' if args.qc_focus is not None else '') if args.qc is not None else
+    tag = args.tag or ('render' if args.render else 'roi' if args.roi else 'qc_' + args.qc + ('_focus' if args.qc_focus is not None else '') if args.qc is not None else
                        args.resample if args.decode is None else 'decode_' + args.decode)
     slide = args.slide or os.path.join(args.out, 'bench_slide.svs' if args.decode is None else 'bench_slide_jpeg.svs')
     gw, gh = (int(v) for v in args.grid.lower().split('x'))
@@ -357,6 +448,10 @@ def main():
         return
     if args.decode is not None:
         decode_leg(args, eng, slide, tag, emit, kw)
+        eng.close()
+        return
+    if args.roi:
+        roi_leg(args, eng, slide, tag, emit, kw)
         eng.close()
         return
     if args.qc is not None:
