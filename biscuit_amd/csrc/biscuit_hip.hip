@@ -1058,6 +1058,34 @@ int bq_jpeg_decode_canvas(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, 
     return BQ_OK;
 }
 
+size_t bq_jpeg_encode_scratch_bytes(int n, int px, int subsampling) { return jpeg_encode_scratch_bytes(n, px, subsampling); }
+
+int bq_jpeg_encode(bq_ctx* c, const uint8_t* d_tiles, int n, int px, int quality, int subsampling, uint8_t* d_out, int64_t cap,
+                   int64_t* d_off, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || cap < 0) return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: bad argument");
+    if (px < 1 || px > 4096 || quality < 1 || quality > 100 || (subsampling != 0 && subsampling != 2))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: outside the encoder's subset (need 1 <= px <= 4096, 1 <= quality <= 100, subsampling 0 = 4:4:4 or 2 = 4:2:0)");
+    if (n == 0) return BQ_OK;
+    if (!d_tiles || !d_off || !d_status || !d_scratch || (!d_out && cap) || ((uintptr_t)d_off & 7) || ((uintptr_t)d_status & 3) ||
+        ((uintptr_t)d_scratch & 15))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: bad argument (null pointer, d_off not 8-byte or d_scratch not 16-byte aligned)");
+    const int m = jpeg_encode_round_tiles(px, subsampling, scratch_bytes);
+    if (m < 1) return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_encode: scratch smaller than one tile's (bq_jpeg_encode_scratch_bytes(1, px, subsampling))");
+    hipStream_t s = (hipStream_t)stream;
+    static const char* const kStage[JPEG_ENC_STAGES] = {"jpeg_encode_pixel", "jpeg_encode_size", "jpeg_encode_pack", "jpeg_encode_stuff"};
+    const double blocks = (double)jpeg_encode_scratch_bytes(1, px, subsampling) / 344.0;       // (for the profile's byte column only: about the blocks of a tile)
+    for (long long t0 = 0; t0 < n; t0 += m) {
+        const int cnt = (int)(n - t0 < m ? n - t0 : m);
+        for (int stage = 0; stage < JPEG_ENC_STAGES; ++stage) {
+            ProfScope ps(c, s, kStage[stage], 0.0, stage == JPEG_ENC_PIXEL ? (double)cnt * px * px * 3.0 : (double)cnt * blocks * 128.0);
+            const int e = launch_jpeg_encode_stage(stage, d_tiles, t0, cnt, m, px, quality, subsampling, d_scratch, d_out, (long long)cap,
+                                                   (long long*)d_off, d_status, s);
+            if (e) return fail(c, BQ_ERR_HIP, std::string("jpeg encode launch: ") + hipGetErrorString((hipError_t)e));
+        }
+    }
+    return BQ_OK;
+}
+
 int bq_tile_resample(bq_ctx* c, const uint8_t* d_canvas, int H, int W, const int32_t* d_origin, int n, int src_px, int px,
                      const int32_t* d_bounds, const int32_t* d_coef, int ksize, uint8_t* d_out, bq_stream_t stream) {
     if (!c || n < 0 || n > (1 << 20) || px <= 0 || px > 4096 || src_px <= 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28) ||

@@ -134,6 +134,14 @@ size_t jpeg_canvas_scratch_bytes(int n, int w, int h);
 int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int w, int h,
                               const int32_t* d_place, uint8_t* d_canvas, int H, int W, const int32_t* clip, int* d_status, void* d_scratch,
                               size_t scratch_bytes, hipStream_t s);
+// kernels_jpeg_encode.hip: n uint8 tiles -> the baseline-JPEG files Pillow writes, back to back (jpeg_encode_device.h), one stage of
+// one round per call so that the entry can time each (bq_jpeg_encode)
+enum { JPEG_ENC_PIXEL = 0, JPEG_ENC_SIZE = 1, JPEG_ENC_PACK = 2, JPEG_ENC_STUFF = 3, JPEG_ENC_STAGES = 4 };
+size_t jpeg_encode_scratch_bytes(int n, int px, int sub);
+int jpeg_encode_round_tiles(int px, int sub, size_t scratch_bytes);         // 0: less than one tile's scratch
+int launch_jpeg_encode_stage(int stage, const uint8_t* d_tiles, long long t0, int cnt, int m, int px, int quality, int sub, void* d_scratch,
+                             uint8_t* d_out, long long cap, long long* d_off, int* d_status, hipStream_t s);
+
 // kernels_resample.hip: the heatmap's tile grid cut from a canvas and resampled as Pillow's LANCZOS does (resample_device.h),
 // and the background filter's grey-pixel count
 int resample_ksize(int src_px, int px);

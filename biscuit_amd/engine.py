@@ -77,7 +77,7 @@ class Engine:
         blob = pack_blob(weights, dtype, self.act_exp)
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
         self._check(self._lib.bq_load_weights(self._ctx, C.cast(buf, C.c_void_p), len(blob)))
-        self._ws = self._inflate_ws = self._jpeg_ws = None        # device buffers grown on demand (``_grown``)
+        self._ws = self._inflate_ws = self._jpeg_ws = self._jpeg_enc_ws = None        # device buffers grown on demand (``_grown``)
         self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
         self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
         self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
@@ -129,7 +129,7 @@ class Engine:
             self._lib.bq_destroy(self._ctx)
             self._ctx = None
             self._resample_taps, self._grayspace_limit = {}, {}
-            self._ws = self._inflate_ws = self._jpeg_ws = None
+            self._ws = self._inflate_ws = self._jpeg_ws = self._jpeg_enc_ws = None
 
     def __del__(self):
         try:
@@ -280,6 +280,44 @@ class Engine:
         """Coefficient space for ``jpeg_decode_canvas`` over ``n`` segments (``bq_jpeg_canvas_scratch_bytes``: 393 KB per 256 x 256
         segment, for 2 048 segments at most; a longer call works in rounds)."""
         return torch.empty(int(self._lib.bq_jpeg_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h))), dtype=torch.uint8,
+                           device=self.device)
+
+    def jpeg_encode(self, tiles, quality=95, subsampling='4:2:0', cap=None, scratch=None):
+        """n tiles encoded as baseline JPEG on the device (``bq_jpeg_encode``, kernels_jpeg_encode.hip): ``tiles`` uint8 NHWC
+        [n, px, px, 3] on this device -> ``(buffer, offsets)``: buffer uint8 [bytes] on the device, offsets int64 [n + 1] on the
+        host; file i = ``buffer[offsets[i]:offsets[i + 1]]``, the bytes Pillow's ``save(buf, 'JPEG', quality=quality,
+        subsampling=subsampling)`` writes ('4:2:0' or '4:4:4').  ``cap``: bytes of the output buffer to try first (None: a
+        guess from the tile size and quality); when the files do not fit (status bit 1) the call is repeated once with the
+        exact total, which the first call's offsets state.  Reading the offsets waits for the stream.  ``scratch``:
+        ``jpeg_encode_scratch(n, px, subsampling)`` or smaller (more rounds), at least one tile's."""
+        from .tfrecord_native import jpeg_subsampling
+        assert tiles.dtype == torch.uint8 and tiles.is_cuda and tiles.is_contiguous() and tiles.dim() == 4
+        assert tiles.shape[1] == tiles.shape[2] and tiles.shape[3] == 3, tuple(tiles.shape)
+        n, px, sub, quality = int(tiles.shape[0]), int(tiles.shape[1]), jpeg_subsampling(subsampling), int(quality)
+        if cap is None:                     # (about 2 bits a sample at quality 95; the retry covers what this misses)
+            cap = n * (1024 + px * px * 3 // (4 if quality < 98 else 2))
+        if scratch is None:
+            scratch = self._grown('_jpeg_enc_ws', int(self._lib.bq_jpeg_encode_scratch_bytes(n, max(px, 1), sub)))
+        off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.jpeg_encode_calls = 0
+        while True:
+            out = torch.empty(max(int(cap), 1), dtype=torch.uint8, device=self.device)
+            self._check(self._lib.bq_jpeg_encode(self._ctx, _ptr(tiles), n, px, quality, sub, _ptr(out), int(cap), _ptr(off), _ptr(status),
+                                                 _ptr(scratch), scratch.numel(), self._stream()))
+            self.jpeg_encode_calls += 1
+            offsets = off.cpu()
+            total = int(offsets[-1])
+            if n == 0 or total <= int(cap):
+                return out[:total], offsets
+            assert self.jpeg_encode_calls == 1 and bool((status & 1).any()), 'bq_jpeg_encode: the exact total did not fit'
+            cap = total
+
+    def jpeg_encode_scratch(self, n, px=TILE_PX, subsampling='4:2:0'):
+        """Scratch for ``jpeg_encode`` over ``n`` tiles (``bq_jpeg_encode_scratch_bytes``: 889 KB per 299-px tile at 4:2:0, for 256
+        tiles at most -- 228 MB; a longer call works in rounds)."""
+        from .tfrecord_native import jpeg_subsampling
+        return torch.empty(int(self._lib.bq_jpeg_encode_scratch_bytes(int(n), int(px), jpeg_subsampling(subsampling))), dtype=torch.uint8,
                            device=self.device)
 
     def tile_resample(self, canvas, origin, src_px, px=TILE_PX, out=None):

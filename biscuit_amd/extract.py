@@ -1,0 +1,177 @@
+"""Tile extraction: a slide file -> one Slideflow tile TFRecord, on the device (DESIGN.md "Tile extraction").
+
+The reference starts with ``extract_tiles(tile_px=299, tile_um=302, qc='both')`` over a cohort; ``extract_slide`` is that step for
+one pyramidal TIFF / SVS file.  It is ``Heatmap.from_slide``'s input half with no network behind it and uses its machinery: the
+masks over the grid (``Heatmap._masks``: the caller's mask, Otsu and focus QC, regions of interest), the band-to-batch loop
+(``Heatmap._batches``: ``WSI.bands``, canvas upload or device decode, ``Engine.tile_resample``, ``Engine.tile_grayspace``) -- and
+then, in place of stain normalisation and ``mc_infer``, ``Engine.jpeg_encode``: the batch leaves the device as the JPEG files
+Pillow would have written for its tiles.  The host frames them as records (``tfrecord.SlideWriter``) and holds no pixels.
+
+    python -m biscuit_amd.extract SLIDE [SLIDE ...] --out DIR [--qc otsu] [--qc-focus] [--rois FILE] [--quality 95] ...
+
+writes ``DIR/SLIDE.tfrecords`` and ``DIR/SLIDE.extract.json`` per slide; ``evaluate()`` reads the TFRecords back, on the host or
+with ``gpu_decode``.
+"""
+import json
+import os
+
+import numpy as np
+
+from . import tfrecord
+
+
+def tile_loc(cells, grid_w, stride, extract_px):
+    """``loc_x`` / ``loc_y`` of row-major grid cells: the tile's centre in level-0 pixels, ``(gx * stride + extract_px // 2, gy *
+    stride + extract_px // 2)`` -- Slideflow's convention restated from memory (unpinned).  -> int64 [n, 2]."""
+    cells = np.asarray(cells, np.int64).reshape(-1)
+    gy, gx = np.divmod(cells, int(grid_w))
+    return np.stack([gx * int(stride) + int(extract_px) // 2, gy * int(stride) + int(extract_px) // 2], 1)
+
+
+class RowMajor:
+    """Records that arrive band by band, written in row-major grid order: ``add`` takes a batch's (cell, file) pairs and the first
+    grid row that may still receive cells; every pending record of an earlier row is then written, sorted by cell.  Holds the
+    encoded records of the bands in flight, never a slide's."""
+
+    def __init__(self, write):
+        self.write, self.pending = write, []
+
+    def add(self, cells, files, open_row_cell):
+        self.pending.extend(zip((int(c) for c in cells), files))
+        self.flush(open_row_cell)
+
+    def flush(self, below=None):
+        self.pending.sort(key=lambda r: r[0])
+        k = len(self.pending) if below is None else sum(1 for c, _ in self.pending if c < below)
+        for c, f in self.pending[:k]:
+            self.write(c, f)
+        del self.pending[:k]
+
+
+def extract_slide(engine, path, out, tile_px=299, tile_um=302, stride_div=1, mpp=None, quality=95, subsampling='4:2:0', decode='host',
+                  canvas_bytes=256 << 20, qc=None, focus_threshold=None, rois=None, cell_mask=None, grayspace_fraction=None, batch=256,
+                  grayspace_threshold=0.05, qc_width=2048, qc_fraction=0.6, focus_mpp=4.0, focus_sigma=3.0, roi_method='auto',
+                  roi_filter_method='center', roi_width=2048):
+    """One slide's tiles -> ``out`` (a ``.tfrecords`` path, or a directory: ``SLIDE.tfrecords`` in it) as JPEG records of
+    (quality, subsampling), plus ``SLIDE.extract.json`` next to it; returns that summary as a dict.
+
+    The grid is ``wsi.WSI(path, tile_px, tile_um, stride_div, mpp)``'s; ``decode``, ``canvas_bytes``, ``cell_mask``, ``qc``,
+    ``focus_threshold``, ``rois``, ``grayspace_fraction`` and their companions are ``Heatmap.from_slide``'s keywords with the same
+    meaning (Slideflow's ``qc='both'`` is ``qc='otsu', focus_threshold=0.02``).  Every record's ``image_raw`` is the file
+    ``tfrecord.encode_image(tile, 'JPEG')`` -- Pillow -- writes for the tile at the default quality 95 / 4:2:0; ``loc_x`` /
+    ``loc_y`` are ``tile_loc``'s; records stand in row-major grid order whatever the banding."""
+    import torch
+    from .heatmap import Heatmap
+    from .tfrecord_native import jpeg_subsampling
+    from .wsi import WSI
+    if decode not in ('host', 'gpu'):
+        raise ValueError(f"decode must be 'host' or 'gpu', not {decode!r}")
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError(f'quality must lie in 1..100, not {quality!r}')
+    jpeg_subsampling(subsampling)
+    polygons, roi_method, roi_filter, roi_width = Heatmap._check_masks(qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma,
+                                                                       rois, roi_method, roi_filter_method, roi_width)
+    name = os.path.splitext(os.path.basename(str(path)))[0]
+    if os.path.isdir(out) or not str(out).endswith('.tfrecords'):
+        os.makedirs(out, exist_ok=True)
+        out = os.path.join(out, name + '.tfrecords')
+    w = WSI(path, tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
+    try:
+        if w.grid_w * w.grid_h == 0:
+            raise ValueError(f'{path}: the slide holds no {tile_um} um tile')
+        keep, threshold, focus, roi_info = Heatmap._masks(engine, w, cell_mask, qc, int(qc_width), qc_fraction, focus_threshold, focus_mpp,
+                                                          focus_sigma, polygons, roi_method, roi_filter, roi_width)
+        stats = {'gpu_bands': 0, 'host_bands': 0, 'segments': 0, 'bands_read': 0, 'gray_dropped': 0}
+        gw = w.grid_w
+        with tfrecord.SlideWriter(out, name) as writer:
+            def write(cell, image):
+                (lx, ly), = tile_loc([cell], gw, w.stride, w.extract_px)
+                writer.write(image, lx, ly)
+            order = RowMajor(write)
+            for tiles, ids, gy0 in Heatmap._batches(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, batch, decode,
+                                                    keep, stats):
+                buf, off = engine.jpeg_encode(tiles, quality, subsampling)
+                data = buf.cpu().numpy()
+                off = off.numpy()
+                order.add(ids, [data[off[i]:off[i + 1]].tobytes() for i in range(len(ids))], gy0 * gw)
+            order.flush()
+            torch.cuda.synchronize(engine.device)
+        masked = 0 if keep is None else int(keep.size - keep.sum())
+        summary = {
+            'slide': str(path), 'tfrecord': out, 'grid_shape': [w.grid_h, w.grid_w], 'tile_px': int(tile_px), 'tile_um': tile_um,
+            'stride_div': int(stride_div), 'stride': int(w.stride), 'extract_px': int(w.extract_px),
+            'cells': int(w.grid_h * w.grid_w), 'cells_kept_by_masks': int(w.grid_h * w.grid_w - masked),
+            'cells_dropped': {'masks': masked, 'roi': None if roi_info is None else roi_info['cells_dropped'],
+                              'grayspace': int(stats['gray_dropped'])},
+            'qc': None if keep is None else dict({'method': qc, 'threshold': threshold, 'bands_read': stats['bands_read'],
+                                                  'bands_skipped_rows': int((~keep.any(1)).sum())}, **(focus or {})),
+            'roi': roi_info,
+            'tiles_written': writer.records, 'bytes_written': writer.nbytes,
+            'decode_stats': {k: stats[k] for k in ('gpu_bands', 'host_bands', 'segments')},
+            'quality': quality, 'subsampling': subsampling if isinstance(subsampling, str) else {0: '4:4:4', 2: '4:2:0'}[subsampling],
+        }
+    finally:
+        w.close()
+    with open(out[:-len('.tfrecords')] + '.extract.json', 'w') as f:
+        json.dump(summary, f, indent=1)
+    return summary
+
+
+def main(argv=None):
+    """Extract the tiles of slide files to Slideflow TFRecords on the GPU (one ``SLIDE.tfrecords`` + ``SLIDE.extract.json`` per slide)."""
+    import argparse
+    import time
+    ap = argparse.ArgumentParser(prog='python -m biscuit_amd.extract', description=main.__doc__)
+    ap.add_argument('slides', metavar='SLIDE', nargs='+', help='pyramidal TIFF / SVS slide files')
+    ap.add_argument('--out', required=True, metavar='DIR')
+    ap.add_argument('--tile-px', type=int, default=299)
+    ap.add_argument('--tile-um', type=float, default=302)
+    ap.add_argument('--stride-div', type=int, default=1)
+    ap.add_argument('--mpp', type=float, default=None, help='microns per pixel, for a file that does not say')
+    ap.add_argument('--batch', type=int, default=256)
+    ap.add_argument('--quality', type=int, default=95, help='JPEG quality, 1..100 (default 95: tfrecord.encode_image)')
+    ap.add_argument('--subsampling', default='4:2:0', choices=['4:2:0', '4:4:4'])
+    ap.add_argument('--gpu-decode', action='store_true', help="decode the slide's own JPEG tiles on the device; the records do not change")
+    ap.add_argument('--grayspace-fraction', type=float, default=None,
+                    help='drop tiles with more than this fraction of grey pixels (Slideflow extracts with 0.6); default: off')
+    ap.add_argument('--grayspace-threshold', type=float, default=0.05)
+    ap.add_argument('--qc', default=None, choices=['otsu'], help="tissue mask from the slide's thumbnail; default: off")
+    ap.add_argument('--qc-width', type=int, default=2048)
+    ap.add_argument('--qc-fraction', type=float, default=0.6)
+    ap.add_argument('--qc-focus', type=float, nargs='?', const=0.02, default=None, metavar='THRESHOLD',
+                    help="focus mask (bare: 0.02), alone or with --qc otsu (Slideflow's qc='both'); default: off")
+    ap.add_argument('--qc-focus-mpp', type=float, default=4.0)
+    ap.add_argument('--qc-focus-sigma', type=float, default=3.0)
+    ap.add_argument('--rois', default=None, metavar='FILE', help="regions of interest, Slideflow's ROI_Name,X_base,Y_base CSV; default: off")
+    ap.add_argument('--roi-method', default='auto', choices=['auto', 'inside', 'outside', 'ignore'])
+    ap.add_argument('--roi-filter', default='center', metavar='center|SHARE')
+    ap.add_argument('--roi-width', type=int, default=2048)
+    args = ap.parse_args(argv)
+    roi_filter = args.roi_filter
+    if roi_filter != 'center':
+        try:
+            roi_filter = float(roi_filter)
+        except ValueError:
+            ap.error(f"--roi-filter takes 'center' or a share in (0, 1], not {args.roi_filter!r}")
+    from .engine import Engine
+    from .weights import synthetic_weights
+    eng = Engine(synthetic_weights(1), max_batch=8, max_mc=2)          # (no network runs here: the context is what is needed)
+    try:
+        for slide in args.slides:
+            t0 = time.perf_counter()
+            s = extract_slide(eng, slide, args.out, tile_px=args.tile_px, tile_um=args.tile_um, stride_div=args.stride_div, mpp=args.mpp,
+                              quality=args.quality, subsampling=args.subsampling, decode='gpu' if args.gpu_decode else 'host',
+                              qc=args.qc, focus_threshold=args.qc_focus, rois=args.rois, grayspace_fraction=args.grayspace_fraction,
+                              batch=args.batch, grayspace_threshold=args.grayspace_threshold, qc_width=args.qc_width,
+                              qc_fraction=args.qc_fraction, focus_mpp=args.qc_focus_mpp, focus_sigma=args.qc_focus_sigma,
+                              roi_method=args.roi_method, roi_filter_method=roi_filter, roi_width=args.roi_width)
+            dt = time.perf_counter() - t0
+            print(json.dumps({'slide': slide, 'tfrecord': s['tfrecord'], 'tiles_written': s['tiles_written'],
+                              'bytes_written': s['bytes_written'], 'seconds': round(dt, 3)}))
+    finally:
+        eng.close()
+
+
+if __name__ == '__main__':
+    main()

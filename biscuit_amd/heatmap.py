@@ -160,8 +160,6 @@ class Heatmap:
         bands that hold a kept cell are read, dropped cells hold ``MASKED``, a kept cell's values do not depend on it.
         ``self.roi = {'method', 'filter', 'polygons', 'vertices', 'cells_dropped'}`` says what it did (the method used; 'center'
         or the share; the polygons and their vertices; cells this mask alone drops); ``self.qc`` keeps its keys."""
-        import os
-        from . import roi, tissue
         from .wsi import WSI
         if resample not in ('gpu', 'host'):
             raise ValueError(f"resample must be 'gpu' or 'host', not {resample!r}")
@@ -171,24 +169,12 @@ class Heatmap:
             raise ValueError(f"decode must be 'host' or 'gpu', not {decode!r}")
         if resample == 'host' and decode == 'gpu':
             raise ValueError("the device decodes into the band's canvas: decode='gpu' needs resample='gpu'")
-        if qc is not None and qc not in tissue.QC_METHODS:
-            raise ValueError(f"qc must be None or one of {tissue.QC_METHODS}, not {qc!r}")
+        polygons, roi_method, roi_filter, roi_width = cls._check_masks(qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma,
+                                                                         rois, roi_method, roi_filter_method, roi_width)
         if resample == 'host' and (qc is not None or cell_mask is not None):
             raise ValueError("the tissue mask steers the streamed read: qc and cell_mask need resample='gpu'")
-        if qc is not None:
-            tissue.check_fraction(qc_fraction)
-            if int(qc_width) < 1:
-                raise ValueError(f'qc_width must be at least 1, not {qc_width!r}')
-        tissue.check_focus(0.0 if focus_threshold is None else focus_threshold, focus_mpp, focus_sigma)      # (its keywords, on or off)
-        if focus_threshold is not None:
-            if resample == 'host':
-                raise ValueError("the focus mask steers the streamed read: focus_threshold needs resample='gpu'")
-            tissue.check_fraction(qc_fraction)
-        roi_filter, roi_width = roi.check_filter(roi_filter_method), roi.check_width(roi_width)      # (its keywords, on or off)
-        polygons = None
-        if rois is not None:
-            polygons = roi.read_csv(rois) if isinstance(rois, (str, os.PathLike)) else roi.check_polygons(rois)
-        roi_method = roi.check_method(roi_method, polygons is not None)
+        if resample == 'host' and focus_threshold is not None:
+            raise ValueError("the focus mask steers the streamed read: focus_threshold needs resample='gpu'")
         if roi_method != 'ignore' and resample == 'host':
             raise ValueError("the region-of-interest mask steers the streamed read: rois needs resample='gpu'")
         w = WSI(path, tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
@@ -199,23 +185,8 @@ class Heatmap:
                 tiles, grid = w.tiles()
                 hm = cls(engine, tiles, grid, grid_shape=(w.grid_h, w.grid_w), **kw)
             else:
-                keep = threshold = None
-                if cell_mask is not None:
-                    keep = tissue.check_mask(cell_mask, w.grid_h, w.grid_w).copy()
-                focus = None
-                if focus_threshold is not None:
-                    qc_keep, threshold, focus = cls._focus_mask(engine, w, qc, int(qc_width), qc_fraction, focus_threshold, focus_mpp,
-                                                                focus_sigma)
-                    keep = qc_keep if keep is None else keep & qc_keep
-                elif qc is not None:
-                    qc_keep, threshold = cls._otsu_mask(engine, w, int(qc_width), qc_fraction)
-                    keep = qc_keep if keep is None else keep & qc_keep
-                roi_info = None
-                if roi_method != 'ignore':
-                    roi_keep = cls._roi_mask(engine, w, polygons, roi_method, roi_filter, roi_width)
-                    roi_info = {'method': roi_method, 'filter': roi_filter, 'polygons': len(polygons),
-                                'vertices': int(sum(len(a) for a in polygons)), 'cells_dropped': int(roi_keep.size - roi_keep.sum())}
-                    keep = roi_keep if keep is None else keep & roi_keep
+                keep, threshold, focus, roi_info = cls._masks(engine, w, cell_mask, qc, int(qc_width), qc_fraction, focus_threshold,
+                                                              focus_mpp, focus_sigma, polygons, roi_method, roi_filter, roi_width)
                 hm = cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, decode=decode, keep=keep, **kw)
                 if keep is not None:
                     hm.qc = dict(hm.qc, method=qc, threshold=threshold, **(focus or {}))
@@ -226,6 +197,53 @@ class Heatmap:
             return hm
         finally:
             w.close()
+
+    @staticmethod
+    def _check_masks(qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma, rois, roi_method, roi_filter_method, roi_width):
+        """The mask keywords of ``from_slide`` (and of ``extract.extract_slide``) checked, on or off: ValueError, or ``(polygons,
+        roi_method, roi_filter, roi_width)`` resolved -- the polygons read, 'auto' decided."""
+        import os
+        from . import roi, tissue
+        if qc is not None and qc not in tissue.QC_METHODS:
+            raise ValueError(f"qc must be None or one of {tissue.QC_METHODS}, not {qc!r}")
+        if qc is not None:
+            tissue.check_fraction(qc_fraction)
+            if int(qc_width) < 1:
+                raise ValueError(f'qc_width must be at least 1, not {qc_width!r}')
+        tissue.check_focus(0.0 if focus_threshold is None else focus_threshold, focus_mpp, focus_sigma)      # (its keywords, on or off)
+        if focus_threshold is not None:
+            tissue.check_fraction(qc_fraction)
+        roi_filter, roi_width = roi.check_filter(roi_filter_method), roi.check_width(roi_width)      # (its keywords, on or off)
+        polygons = None
+        if rois is not None:
+            polygons = roi.read_csv(rois) if isinstance(rois, (str, os.PathLike)) else roi.check_polygons(rois)
+        return polygons, roi.check_method(roi_method, polygons is not None), roi_filter, roi_width
+
+    @classmethod
+    def _masks(cls, engine, w, cell_mask, qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma, polygons, roi_method,
+               roi_filter, roi_width):
+        """The keep mask of the open slide ``w`` from the caller's mask, the tissue / focus QC and the regions of interest, ANDed:
+        ``(keep bool [grid_h, grid_w] or None without any, the Otsu threshold or None, the focus entries of ``qc`` or None, the
+        ``roi`` record or None)``."""
+        from . import tissue
+        keep = threshold = None
+        if cell_mask is not None:
+            keep = tissue.check_mask(cell_mask, w.grid_h, w.grid_w).copy()
+        focus = None
+        if focus_threshold is not None:
+            qc_keep, threshold, focus = cls._focus_mask(engine, w, qc, int(qc_width), qc_fraction, focus_threshold, focus_mpp,
+                                                        focus_sigma)
+            keep = qc_keep if keep is None else keep & qc_keep
+        elif qc is not None:
+            qc_keep, threshold = cls._otsu_mask(engine, w, int(qc_width), qc_fraction)
+            keep = qc_keep if keep is None else keep & qc_keep
+        roi_info = None
+        if roi_method != 'ignore':
+            roi_keep = cls._roi_mask(engine, w, polygons, roi_method, roi_filter, roi_width)
+            roi_info = {'method': roi_method, 'filter': roi_filter, 'polygons': len(polygons),
+                        'vertices': int(sum(len(a) for a in polygons)), 'cells_dropped': int(roi_keep.size - roi_keep.sum())}
+            keep = roi_keep if keep is None else keep & roi_keep
+        return keep, threshold, focus, roi_info
 
     @staticmethod
     def _otsu_mask(engine, w, qc_width, qc_fraction):
@@ -303,39 +321,21 @@ class Heatmap:
         return None if bool(status.any().item()) else canvas
 
     @classmethod
-    def _streamed(cls, engine, w, canvas_bytes, gray_fraction, gray_threshold, mc_n=30, seed=0, batch=256, norm_fit=None,
-                  normalizer='reinhard_fast', decode='host', keep=None):
-        """``from_slide(resample='gpu')``: bands -> batches of exactly the tiles ``Heatmap(engine, *w.tiles())`` would put in
-        each batch (a batch is filled across band boundaries), so an unfiltered slide runs the same launches on the same bytes.
-        ``keep`` (bool [grid_h, grid_w] or None): the tissue mask -- only its bands are read and only its cells are resampled."""
-        from . import stain
-        stain.check(normalizer, norm_fit)
+    def _batches(cls, engine, w, canvas_bytes, gray_fraction, gray_threshold, batch, decode, mask, stats):
+        """The band-to-batch loop of a streamed slide, for ``_streamed`` and for ``extract.extract_slide``: walks ``w.bands``,
+        uploads or device-decodes each band's canvas, fills ONE device batch with ``Engine.tile_resample`` across band boundaries
+        and drops background tiles with ``Engine.tile_grayspace`` if asked.  Yields ``(tiles, ids, gy0)`` for every full batch
+        and the last partial one: a view of the batch buffer (uint8 [n, px, px, 3] on the device, valid until the next step),
+        the tiles' row-major grid indices (int64 [n], the caller's to keep) and the first grid row of the band being read
+        (``WSI.band_rows``, not the rectangle's own: a later column range of the band may start higher up) -- every cell of an
+        earlier row has been yielded by then.  ``stats``: a dict whose 'gpu_bands' / 'host_bands' / 'segments' /
+        'bands_read' / 'gray_dropped' are counted up."""
         if gray_fraction is not None and not 0.0 <= float(gray_fraction) <= 1.0:
             raise ValueError('grayspace_fraction must lie in [0, 1]')
-        hm = cls.__new__(cls)
-        gh, gw, px, dev, batch = w.grid_h, w.grid_w, w.tile_px, engine.device, int(batch)
-        hm.logits = np.full((gh, gw, 2), MASKED, dtype=np.float32)
-        hm.uncertainty = np.full((gh, gw, 2), MASKED, dtype=np.float32)
-        hm.dropped = 0
-        hm.decode_stats = stats = {'gpu_bands': 0, 'host_bands': 0, 'segments': 0}
+        gw, px, dev, batch = w.grid_w, w.tile_px, engine.device, int(batch)
         buf = torch.empty((batch, px, px, 3), dtype=torch.uint8, device=dev)      # the one batch the device holds
         idx = np.empty(batch, np.int64)                                          # its tiles' row-major grid indices
-        kept, fill = [], 0
-
-        def flush(n):
-            cur = stain.normalise(engine, buf[:n], normalizer, norm_fit)
-            mean, std = engine.mc_infer(cur, mc_n, seed, tile_idx=torch.from_numpy(idx[:n]).to(dev))
-            gy, gx = np.divmod(idx[:n], gw)
-            hm.logits[gy, gx] = mean.cpu().numpy()
-            hm.uncertainty[gy, gx] = std.cpu().numpy()
-            kept.append(idx[:n].copy())
-
-        mask = keep                                                          # (`keep` below is the grayspace filter's, per batch)
-        if mask is not None:
-            hm.cell_mask = mask
-            hm.dropped = int(mask.size - mask.sum())
-            hm.qc = {'method': None, 'threshold': None, 'cells_dropped': hm.dropped, 'bands_read': 0,
-                     'bands_skipped_rows': int((~mask.any(1)).sum())}
+        fill = 0
         for gy0, gy1, gx0, gx1, canvas, origin, src_px in w.bands(canvas_bytes, segments=decode == 'gpu', keep=mask):
             d_canvas = None
             if decode == 'gpu' and canvas is not None:
@@ -352,7 +352,7 @@ class Heatmap:
             del canvas, origin                                                   # uploaded: the host holds one canvas at a time
             cell = (np.arange(gy0, gy1, dtype=np.int64)[:, None] * gw + np.arange(gx0, gx1, dtype=np.int64)[None, :]).reshape(-1)
             if mask is not None:
-                hm.qc['bands_read'] += 1
+                stats['bands_read'] += 1
                 pos = np.flatnonzero(mask[gy0:gy1, gx0:gx1].reshape(-1))       # the rectangle's kept cells, row-major
                 if len(pos) < len(cell):
                     d_origin, cell = d_origin[torch.from_numpy(pos).to(dev)], cell[pos]
@@ -369,17 +369,51 @@ class Heatmap:
                         sel = torch.from_numpy(np.flatnonzero(keep)).to(dev)
                         if len(sel):
                             dst[:len(sel)] = dst[sel]                             # (the right side is a copy: no overlap)
-                        hm.dropped += m - len(sel)
+                        stats['gray_dropped'] += m - len(sel)
                         ids = ids[keep]
                 idx[fill:fill + len(ids)] = ids
                 fill += len(ids)
                 a += m
                 if fill == batch:
-                    flush(fill)
+                    yield buf[:fill], idx[:fill].copy(), w.band_rows[0]
                     fill = 0
             del d_canvas
         if fill:
-            flush(fill)
+            yield buf[:fill], idx[:fill].copy(), w.grid_h
+
+    @classmethod
+    def _streamed(cls, engine, w, canvas_bytes, gray_fraction, gray_threshold, mc_n=30, seed=0, batch=256, norm_fit=None,
+                  normalizer='reinhard_fast', decode='host', keep=None):
+        """``from_slide(resample='gpu')``: bands -> batches of exactly the tiles ``Heatmap(engine, *w.tiles())`` would put in
+        each batch (a batch is filled across band boundaries: ``_batches``), so an unfiltered slide runs the same launches on the
+        same bytes.  ``keep`` (bool [grid_h, grid_w] or None): the tissue mask -- only its bands are read and only its cells are
+        resampled."""
+        from . import stain
+        stain.check(normalizer, norm_fit)
+        hm = cls.__new__(cls)
+        gh, gw, dev = w.grid_h, w.grid_w, engine.device
+        hm.logits = np.full((gh, gw, 2), MASKED, dtype=np.float32)
+        hm.uncertainty = np.full((gh, gw, 2), MASKED, dtype=np.float32)
+        hm.dropped = 0
+        stats = {'gpu_bands': 0, 'host_bands': 0, 'segments': 0, 'bands_read': 0, 'gray_dropped': 0}
+        kept = []
+        mask = keep
+        if mask is not None:
+            hm.cell_mask = mask
+            hm.dropped = int(mask.size - mask.sum())
+            hm.qc = {'method': None, 'threshold': None, 'cells_dropped': hm.dropped, 'bands_read': 0,
+                     'bands_skipped_rows': int((~mask.any(1)).sum())}
+        for tiles, ids, _ in cls._batches(engine, w, canvas_bytes, gray_fraction, gray_threshold, batch, decode, mask, stats):
+            cur = stain.normalise(engine, tiles, normalizer, norm_fit)
+            mean, std = engine.mc_infer(cur, mc_n, seed, tile_idx=torch.from_numpy(ids).to(dev))
+            gy, gx = np.divmod(ids, gw)
+            hm.logits[gy, gx] = mean.cpu().numpy()
+            hm.uncertainty[gy, gx] = std.cpu().numpy()
+            kept.append(ids)
+        hm.dropped += stats['gray_dropped']
+        if mask is not None:
+            hm.qc['bands_read'] = stats['bands_read']
+        hm.decode_stats = {k: stats[k] for k in ('gpu_bands', 'host_bands', 'segments')}
         cells = np.concatenate(kept) if kept else np.zeros(0, np.int64)
         hm.grid = np.stack([cells % gw, cells // gw], 1)
         return hm

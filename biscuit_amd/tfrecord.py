@@ -271,3 +271,32 @@ def write_slide(path, slide, tiles, locs=None, fmt='PNG'):
             payload = encode_example(slide, image, int(lx), int(ly))
             head = struct.pack('<Q', len(payload))
             f.write(head + struct.pack('<I', masked_crc(head)) + payload + struct.pack('<I', masked_crc(payload)))
+
+
+class SlideWriter:
+    """One slide's TFRecord file written record by record from already encoded images: ``write_slide``'s bytes without holding
+    the slide's tiles -- what a streaming producer (``extract.extract_slide``) appends to as its batches come off the device.
+    ``records`` / ``nbytes`` count what has been written."""
+
+    def __init__(self, path, slide):
+        self.path, self.slide, self.records, self.nbytes = path, slide, 0, 0
+        self._f = open(path, 'wb')
+
+    def write(self, image_raw, loc_x, loc_y):
+        payload = encode_example(self.slide, bytes(image_raw), int(loc_x), int(loc_y))
+        head = struct.pack('<Q', len(payload))
+        rec = head + struct.pack('<I', masked_crc(head)) + payload + struct.pack('<I', masked_crc(payload))
+        self._f.write(rec)
+        self.records += 1
+        self.nbytes += len(rec)
+
+    def close(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

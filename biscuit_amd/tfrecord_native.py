@@ -44,6 +44,10 @@ ABI = {
     'bqio_resample_taps': (_i, [_i, _i, _vp, _vp, _i]),
     'bqio_tile_resample': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
     'bqio_roi_plane': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    'bqio_jpeg_encode': (_i, [_vp, _i64, _i, _i, _i, _vp, C.c_size_t, _vp, _vp]),
+    'bqio_jpeg_encode_header': (_i, [_i, _i, _i, _vp]),
+    'bqio_jpeg_encode_header_bytes': (C.c_size_t, []),
+    'bqio_jpeg_encode_last_error': (C.c_char_p, []),
     'bqio_masked_crc32c': (C.c_uint32, [C.c_char_p, C.c_size_t]),
     'bqio_inflate': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t]),
     'bqio_inflate2': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t, C.c_char_p, C.c_size_t, _vp, C.c_size_t,
@@ -203,6 +207,50 @@ def jpeg_decode_canvas(scan, desc, tables, seg_w, seg_h, place, canvas, clip, th
     if e != 0:
         raise ValueError(f'bqio_jpeg_decode_canvas: error {e}')
     return status
+
+
+SUBSAMPLING = {'4:4:4': 0, '4:2:0': 2, 0: 0, 2: 2}
+
+
+def jpeg_subsampling(subsampling):
+    """Pillow's number for a ``subsampling`` the encoder takes ('4:4:4' / 0, '4:2:0' / 2); ValueError for any other."""
+    try:
+        return SUBSAMPLING[subsampling]
+    except (KeyError, TypeError):
+        raise ValueError(f"subsampling {subsampling!r}: the encoder takes '4:2:0' and '4:4:4'") from None
+
+
+def jpeg_encode_header(px, quality=95, subsampling='4:2:0'):
+    """The bytes from SOI through the SOS header that every ``px`` tile encoded at (quality, subsampling) starts with
+    (``bqio_jpeg_encode_header``).  ValueError outside the encoder's subset."""
+    out = np.empty(int(lib().bqio_jpeg_encode_header_bytes()), np.uint8)
+    if lib().bqio_jpeg_encode_header(int(px), int(quality), jpeg_subsampling(subsampling), out.ctypes.data) != 0:
+        raise ValueError('bqio_jpeg_encode_header: ' + lib().bqio_jpeg_encode_last_error().decode())
+    return out.tobytes()
+
+
+def jpeg_encode(tiles, quality=95, subsampling='4:2:0', cap=None):
+    """uint8 [n, px, px, 3] -> ``(buffer uint8 [bytes], offsets int64 [n + 1], status int32 [n])``: the files Pillow's
+    ``save(buf, 'JPEG', quality=quality, subsampling=subsampling)`` writes, back to back (``bqio_jpeg_encode``: the device
+    encoder's routines, csrc/jpeg_encode_device.h, on the CPU).  ``cap``: the buffer's size; None sizes it exactly with a first
+    call.  A file that would end beyond ``cap`` is left out and its status is 1.  ValueError outside the encoder's subset.
+    What ``Engine.jpeg_encode`` computes, byte for byte.  For tests."""
+    tiles = np.ascontiguousarray(tiles, np.uint8)
+    assert tiles.ndim == 4 and tiles.shape[1] == tiles.shape[2] and tiles.shape[3] == 3, tiles.shape
+    n, px, sub = tiles.shape[0], tiles.shape[1], jpeg_subsampling(subsampling)
+    off, status = np.zeros(n + 1, np.int64), np.zeros(n, np.int32)
+
+    def call(out, cap):
+        e = lib().bqio_jpeg_encode(tiles.ctypes.data, n, px, int(quality), sub, out.ctypes.data if out is not None else None, cap,
+                                   off.ctypes.data, status.ctypes.data)
+        if e != 0:
+            raise ValueError('bqio_jpeg_encode: ' + lib().bqio_jpeg_encode_last_error().decode())
+    if cap is None:
+        call(None, 0)
+        cap = int(off[-1])
+    out = np.zeros(max(int(cap), 1), np.uint8)
+    call(out, int(cap))
+    return out[:int(cap)], off, status
 
 
 def inflate_fallbacks():

@@ -477,7 +477,11 @@ class WSI:
         "Heatmap input", Tissue mask).  Grid rows without a kept cell are never read and end a band; within a band every column
         range is cut down to the rectangle its kept cells span, so no band is without a kept cell and every band's first and
         last row and first and last column hold one.  The rectangles are disjoint and together hold every kept cell once;
-        ``origin`` still lists every cell of the rectangle in row-major order, kept or not."""
+        ``origin`` still lists every cell of the rectangle in row-major order, kept or not.
+
+        While a band's rectangles are being yielded ``self.band_rows`` holds that band's ``(gy0, gy1)``: every rectangle still to
+        come lies in grid rows >= ``band_rows[0]`` (a rectangle's own first row may be larger than a later one's of the same
+        band)."""
         if keep is not None:
             keep = np.asarray(keep)
             if keep.dtype != np.bool_ or keep.shape != (self.grid_h, self.grid_w):
@@ -503,6 +507,7 @@ class WSI:
                 if h > limit or h * widest * 3 > canvas_bytes:
                     break
                 gy1 += 1
+            self.band_rows = (gy0, gy1)
             for a, b in cols:
                 r0, r1 = gy0, gy1
                 if keep is not None:                                      # the rectangle this column range's kept cells span

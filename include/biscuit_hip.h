@@ -215,6 +215,28 @@ int bq_jpeg_decode_canvas(bq_ctx* ctx, const uint8_t* d_scan, const void* d_desc
                           int seg_h, const int32_t* d_place, uint8_t* d_canvas, int H, int W, int clip_x0, int clip_y0, int clip_x1,
                           int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
 
+/* Output side, JPEG tiles, encoded on the device (kernels_jpeg_encode.hip; DESIGN.md "Tile extraction"): n tiles d_tiles uint8
+ * [n][px][px][3] -- the batch bq_tile_resample fills -- become the COMPLETE baseline-JPEG files Pillow writes for `save(buf, 'JPEG',
+ * quality=quality, subsampling=subsampling)` with everything else at its default (libjpeg's 16-bit BT.601, h2v2 box filter, islow
+ * fDCT, rounded-division quantisers, the Annex K Huffman tables), byte for byte, back to back in d_out: file i = d_out[d_off[i] ..
+ * d_off[i + 1]), d_off int64 [n + 1] (device memory, 8-byte aligned) with d_off[0] = 0.  subsampling: 0 = 4:4:4, 2 = 4:2:0 (Pillow's
+ * numbering); quality 1..100; px 1..4096 -- anything else returns BQ_ERR_ARG with bq_last_error set and launches nothing.  Four
+ * stages, each timed as its own class under bq_profile_*: pixel (one thread per 8 x 8 block: colour, edges, downsampling, fDCT,
+ * quantisation; int16 zigzag coefficients to scratch), size (a block's code length from its coefficients and one neighbour's DC, then
+ * an exclusive scan per tile), pack (every block writes its bits at its bit offset; words shared by two blocks are merged with
+ * atomicOr, the last byte is padded with ones), stuff (0xFF bytes counted per chunk and scanned, the file lengths scanned into
+ * d_off, then header + stuffed segment + EOI copied out).  d_status[i] = 0, or 1 when file i would end beyond `cap` (the bytes of
+ * d_out): that file and the ones behind it are not written, d_off still holds every exact length, so the caller repeats the call
+ * with a buffer that fits (cap = 0 with d_out = NULL sizes a call).  Scratch (16-byte aligned): 128 bytes of coefficients, 4 of
+ * offsets, the worst-case 248 of code and 31 of chunk counts per block, 888 768 bytes per 299-px tile at 4:2:0; bq_jpeg_encode_scratch_bytes(n, px,
+ * subsampling) asks for min(n, 256) tiles' worth and the call works in rounds of as many tiles as d_scratch holds -- one at least,
+ * BQ_ERR_WORKSPACE below that.  The result is bqio_jpeg_encode's byte for byte and does not depend on the rounds.  Everything is
+ * enqueued on `stream`; the library allocates nothing and does not wait for the device; n = 0 returns 0 without a launch.  The
+ * reference's counterpart is Slideflow's extract_tiles writing image_raw. */
+size_t bq_jpeg_encode_scratch_bytes(int n, int px, int subsampling);
+int bq_jpeg_encode(bq_ctx* ctx, const uint8_t* d_tiles, int n, int px, int quality, int subsampling, uint8_t* d_out, int64_t cap,
+                   int64_t* d_off, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
+
 /* The whole-slide heatmap's input stage (kernels_resample.hip; DESIGN.md "Heatmap input"): n tiles cut out of a slide canvas in
  * device memory and resampled to px x px -- what sf.Heatmap's slide reader does per tile on the host (results.py:217).  d_canvas
  * uint8 [H][W][3]; tile t is the src_px x src_px window at (d_origin[2 t], d_origin[2 t + 1]) = (x, y) (int32; windows may

@@ -164,6 +164,21 @@ int bqio_tile_resample(const uint8_t* canvas, int H, int W, const int32_t* origi
 int bqio_roi_plane(const int32_t* edges, int E, const int32_t* starts, int P, const int32_t* xs, int W, const int32_t* ys, int H,
                    uint8_t* plane);
 
+/* The CPU build of bq_jpeg_encode (include/biscuit_hip.h; csrc/jpeg_encode_host.cpp over csrc/jpeg_encode_device.h, the routines
+ * the GPU kernels are compiled from): n tiles uint8 [n][px][px][3] -> the complete baseline-JPEG files Pillow writes for
+ * `save(buf, 'JPEG', quality=quality, subsampling=subsampling)` with everything else at its default, byte for byte, back to back
+ * in `out`: file i = out[off[i] .. off[i + 1]), off int64 [n + 1] with off[0] = 0.  subsampling: 0 = 4:4:4, 2 = 4:2:0 (Pillow's
+ * numbering).  A file that would end beyond `cap` is not written and status[i] = 1 (0 otherwise); off still holds the exact
+ * lengths, so cap = 0 with out = NULL sizes a call.  BQIO_ERR_ARG, with nothing written, outside the subset -- px in 1..4096,
+ * quality in 1..100, the two samplings -- or for a null pointer; bqio_jpeg_encode_last_error() then says which.
+ * bqio_jpeg_encode_header writes the bqio_jpeg_encode_header_bytes() (623) bytes from SOI through the SOS header, which depend
+ * on (px, quality, subsampling) only.  For tests. */
+int bqio_jpeg_encode(const uint8_t* tiles, int64_t n, int px, int quality, int subsampling, uint8_t* out, size_t cap, int64_t* off,
+                     int32_t* status);
+int bqio_jpeg_encode_header(int px, int quality, int subsampling, uint8_t* out);
+size_t bqio_jpeg_encode_header_bytes(void);
+const char* bqio_jpeg_encode_last_error(void);
+
 /* One JPEG file (as bqio_image_bytes returns it) -> out[tile_px][tile_px][3], the decoder
  * bqio_decode uses, exported for tests.  BQIO_OK / BQIO_ERR_UNSUPPORTED / BQIO_ERR_FORMAT. */
 int bqio_decode_jpeg(const uint8_t* data, size_t len, int tile_px, uint8_t* out);
