@@ -761,7 +761,9 @@ bq_ctx* bq_create(int device_id, const bq_config* cfg) {
         // [256,511) linear -> 8-bit sRGB as 255 switching points: entry v-1 is the smallest float32 c for which
         //           clip(trunc(255 * clip(gamma(c), 0, 1)), 0, 255) >= v, gamma(c) = c > 0.0031308 ?
         //           1.055f * float(pow(double(c), 1/2.4)) - 0.055f : 12.92f * c, found by bisection on the
-        //           float bit pattern (the function is monotone)
+        //           float bit pattern over [0, 2] (the function is monotone).  Not over [0, 1]: 1.055f * 1 - 0.055f rounds to the
+        //           float below 1, so c = 1 is level 254 and the last point lies a few ulps ABOVE 1 (oracle/stain.py
+        //           srgb_switch_points states the same search)
         float lut[512];
         for (int v = 0; v < 256; ++v) {
             const double x = (double)v / 255.0;
@@ -776,7 +778,7 @@ bq_ctx* bq_create(int device_id, const bq_config* cfg) {
             return (int)(t < 0.f ? 0.f : (t > 255.f ? 255.f : t));
         };
         for (int v = 1; v <= 255; ++v) {
-            uint32_t lo = 0, hi = 0x3F800000u;               // bit patterns of 0.0f and 1.0f; level(1.0f) = 255
+            uint32_t lo = 0, hi = 0x40000000u;               // bit patterns of 0.0f and 2.0f; level(2.0f) = 255
             while (lo < hi) {
                 const uint32_t mid = lo + (hi - lo) / 2;
                 float f;
@@ -930,8 +932,8 @@ int bq_stain_reinhard_fast(bq_ctx* c, const uint8_t* d_tiles, int n, const float
     if (!c || !d_tiles || !d_out || !target_means3 || !target_stds3 || n < 0)
         return fail(c, BQ_ERR_ARG, "bq_stain_reinhard_fast: bad argument");
     for (int i = 0; i < 3; ++i)
-        if (!(target_stds3[i] == target_stds3[i]) || !(target_means3[i] == target_means3[i]))
-            return fail(c, BQ_ERR_ARG, "bq_stain_reinhard_fast: NaN in the target statistics");
+        if (!std::isfinite(target_stds3[i]) || !std::isfinite(target_means3[i]))      // (a std of 0 or below is defined arithmetic)
+            return fail(c, BQ_ERR_ARG, "bq_stain_reinhard_fast: non-finite target statistics");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(c, s, "stain_reinhard_fast", 300.0 * n * 299 * 299, 3.0 * n * kStaged);
     if (launch_reinhard(d_tiles, n, 299, c->d_srgb_lut, kReinhardConsts, target_means3, target_stds3, d_out, nullptr, s))

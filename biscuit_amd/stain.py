@@ -53,10 +53,22 @@ def macenko_fit(norm_fit):
 
 
 def reinhard_fit(norm_fit):
-    """(target_means, target_stds) of a reinhard_fast ``norm_fit``; ValueError when they are missing."""
+    """(target_means, target_stds), float32 [3] each, of a reinhard_fast ``norm_fit``; ValueError when they are missing, are not three
+    numbers each or hold a value that is not finite in float32.  A std of 0 (every pixel becomes the target mean's colour) or below
+    is legal: defined arithmetic."""
     if not isinstance(norm_fit, dict) or 'target_means' not in norm_fit or 'target_stds' not in norm_fit:
         raise ValueError("a reinhard_fast norm_fit needs 'target_means' and 'target_stds'")
-    return norm_fit['target_means'], norm_fit['target_stds']
+    try:
+        with np.errstate(over='ignore'):
+            means = np.asarray(norm_fit['target_means'], dtype=np.float64).astype(np.float32)
+            stds = np.asarray(norm_fit['target_stds'], dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f'reinhard_fast norm_fit: {e}') from None
+    if means.shape != (3,) or stds.shape != (3,):
+        raise ValueError(f'reinhard_fast norm_fit: target_means and target_stds must be 3 values each, not {means.shape} and {stds.shape}')
+    if not (np.isfinite(means).all() and np.isfinite(stds).all()):
+        raise ValueError('reinhard_fast norm_fit: non-finite value')
+    return means, stds
 
 
 def check(normalizer, norm_fit):
@@ -115,7 +127,7 @@ class ReinhardFast:
         fit = params.get('norm_fit')
         if not fit or 'target_means' not in fit or 'target_stds' not in fit:
             raise ValueError("params.json has no norm_fit with target_means / target_stds")
-        return cls(engine, fit['target_means'], fit['target_stds'])
+        return cls(engine, *reinhard_fit(fit))
 
     def _as_batch(self, image):
         t = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))

@@ -106,7 +106,7 @@ int bq_set_option(bq_ctx* ctx, const char* name, int value);
  * uint8 tile before the standardisation exactly where results.py:251-252 calls
  * interface.wsi_normalizer.rgb_to_rgb(image).  uint8 NHWC [n,px,px,3] -> uint8 NHWC; d_out may equal
  * d_tiles.  target_means3 / target_stds3 are HOST pointers to the model's params.json `norm_fit`
- * (CIE-LAB L, a, b).  The algorithm lives in Slideflow, not in the reference: parity unpinned
+ * (CIE-LAB L, a, b); a NaN or an infinity among them is BQ_ERR_ARG, a std of 0 or below is legal.  The algorithm lives in Slideflow, not in the reference: parity unpinned
  * (oracle/stain.py states the arithmetic both sides implement). */
 int bq_stain_reinhard_fast(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, const float* target_means3,
                            const float* target_stds3, uint8_t* d_out_nhwc, bq_stream_t stream);
