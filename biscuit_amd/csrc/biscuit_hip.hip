@@ -1156,18 +1156,25 @@ int bq_tissue_blur(bq_ctx* c, const uint8_t* d_thumb, int H, int W, const int32_
     return BQ_OK;
 }
 
+// The cells' ranges of a W x H plane, [a, b) pairs: 0 <= a < b <= W for a column, <= H for a row.  -> the refusal's text, or empty.
+static std::string bad_cell_range(const char* plane, const int32_t* col_ranges, int gw, int W, const int32_t* row_ranges, int gh, int H) {
+    for (int i = 0; i < gw; ++i)
+        if (col_ranges[2 * i] < 0 || col_ranges[2 * i] >= col_ranges[2 * i + 1] || col_ranges[2 * i + 1] > W)
+            return std::string("a column range is empty or outside the ") + plane;
+    for (int i = 0; i < gh; ++i)
+        if (row_ranges[2 * i] < 0 || row_ranges[2 * i] >= row_ranges[2 * i + 1] || row_ranges[2 * i + 1] > H)
+            return std::string("a row range is empty or outside the ") + plane;
+    return std::string();
+}
+
 int bq_tissue_cells(bq_ctx* c, const uint8_t* d_plane, int H, int W, int T, const int32_t* col_ranges, int gw, const int32_t* row_ranges,
                     int gh, int32_t* d_ranges, int32_t* d_count, bq_stream_t stream) {
     if (!c || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31) || gw <= 0 || gh <= 0 || gw > (1 << 15) || gh > (1 << 15) || T < 0 || T > 255)
         return fail(c, BQ_ERR_ARG, "bq_tissue_cells: bad argument (need 0 < H, W, H * W < 2^31, 0 < gw, gh <= 32768 and 0 <= T <= 255)");
     if (!d_plane || !col_ranges || !row_ranges || !d_ranges || !d_count || ((uintptr_t)d_ranges & 3) || ((uintptr_t)d_count & 3))
         return fail(c, BQ_ERR_ARG, "bq_tissue_cells: bad argument");
-    for (int i = 0; i < gw; ++i)
-        if (col_ranges[2 * i] < 0 || col_ranges[2 * i] >= col_ranges[2 * i + 1] || col_ranges[2 * i + 1] > W)
-            return fail(c, BQ_ERR_ARG, "bq_tissue_cells: a column range is empty or outside the plane");
-    for (int i = 0; i < gh; ++i)
-        if (row_ranges[2 * i] < 0 || row_ranges[2 * i] >= row_ranges[2 * i + 1] || row_ranges[2 * i + 1] > H)
-            return fail(c, BQ_ERR_ARG, "bq_tissue_cells: a row range is empty or outside the plane");
+    const std::string bad = bad_cell_range("plane", col_ranges, gw, W, row_ranges, gh, H);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, "bq_tissue_cells: " + bad);
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(c, s, "tissue_cells", 0.0, (double)H * W);
     HIPCHK(c, hipMemcpyAsync(d_ranges, col_ranges, (size_t)gw * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -1201,12 +1208,8 @@ int bq_tissue_cells_union(bq_ctx* c, const uint8_t* d_otsu_plane, int Ho, int Wo
     if (!d_otsu_plane || !d_focus_plane || !xmap || !ymap || !col_ranges || !row_ranges || !d_tables || !d_count ||
         ((uintptr_t)d_tables & 3) || ((uintptr_t)d_count & 3))
         return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: bad argument");
-    for (int i = 0; i < gw; ++i)
-        if (col_ranges[2 * i] < 0 || col_ranges[2 * i] >= col_ranges[2 * i + 1] || col_ranges[2 * i + 1] > Wo)
-            return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: a column range is empty or outside the Otsu plane");
-    for (int i = 0; i < gh; ++i)
-        if (row_ranges[2 * i] < 0 || row_ranges[2 * i] >= row_ranges[2 * i + 1] || row_ranges[2 * i + 1] > Ho)
-            return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: a row range is empty or outside the Otsu plane");
+    const std::string bad = bad_cell_range("Otsu plane", col_ranges, gw, Wo, row_ranges, gh, Ho);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: " + bad);
     for (int i = 0; i < Wo; ++i)
         if (xmap[i] < 0 || xmap[i] >= Wf || (i && xmap[i] < xmap[i - 1]))
             return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: the column map leaves the focus plane or decreases");

@@ -81,9 +81,8 @@ class Engine:
         self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
         self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
         self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
-        self._tissue_host = None         # the range tables of the last tissue_cells call, alive while the stream copies them
         self._tissue_taps = {}           # sigma -> (the Gaussian's taps on the device, r) (tissue_focus)
-        self._roi_host = []              # (event, host tables) of the roi_plane calls the stream may not have passed yet
+        self._host_held = []             # (event, host tables) of the calls the stream may not have passed yet (``_hold``)
         self._elt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[dtype]
 
     # shapes of the stored tensors by debug-tap name
@@ -128,7 +127,7 @@ class Engine:
         if getattr(self, '_ctx', None):
             self._lib.bq_destroy(self._ctx)
             self._ctx = None
-            self._resample_taps, self._grayspace_limit = {}, {}
+            self._resample_taps, self._grayspace_limit, self._host_held = {}, {}, []
             self._ws = self._inflate_ws = self._jpeg_ws = self._jpeg_enc_ws = None
 
     def __del__(self):
@@ -145,6 +144,21 @@ class Engine:
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _hold(self, *host):
+        """Keeps the host arrays a call just handed to ``hipMemcpyAsync`` alive until an event recorded behind the call has completed
+        (queried, never waited for), so back-to-back calls do not release one another's."""
+        done = torch.cuda.current_stream(self.device).record_event()
+        self._host_held = [(e, t) for e, t in self._host_held if not e.query()] + [(done, host)]
+
+    @staticmethod
+    def _check_cells(T, col, row, h, w):
+        """ValueError for a threshold outside 0 .. 255 and for a range of ``col`` / ``row`` that is empty or leaves the ``h`` x ``w`` plane."""
+        if not 0 <= int(T) <= 255:
+            raise ValueError(f'T must lie in 0 .. 255, not {T!r}')
+        for name, r, n in (('col', col, w), ('row', row, h)):
+            if (r[:, 0] < 0).any() or (r[:, 0] >= r[:, 1]).any() or (r[:, 1] > n).any():
+                raise ValueError(f'a {name} range is empty or outside the {h} x {w} plane')
 
     def _grown(self, name, need):
         """The cached device buffer ``self.<name>`` (a torch uint8 tensor), ``need`` bytes at least: the old one goes before the larger comes."""
@@ -426,17 +440,13 @@ class Engine:
         col, row = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(row, np.int32)
         if col.ndim != 2 or col.shape[1] != 2 or row.ndim != 2 or row.shape[1] != 2 or len(col) < 1 or len(row) < 1:
             raise ValueError('col and row must be int32 [gw, 2] and [gh, 2]')
-        if not 0 <= int(T) <= 255:
-            raise ValueError(f'T must lie in 0 .. 255, not {T!r}')
-        for name, r, n in (('col', col, w), ('row', row, h)):
-            if (r[:, 0] < 0).any() or (r[:, 0] >= r[:, 1]).any() or (r[:, 1] > n).any():
-                raise ValueError(f'a {name} range is empty or outside the {h} x {w} plane')
+        self._check_cells(T, col, row, h, w)
         gw, gh = len(col), len(row)
         ranges = torch.empty(2 * (gw + gh), dtype=torch.int32, device=self.device)
         count = torch.empty((gh, gw), dtype=torch.int32, device=self.device)
-        self._tissue_host = (col, row)                                      # the host tables live until the stream has copied them
         self._check(self._lib.bq_tissue_cells(self._ctx, _ptr(plane), h, w, int(T), col.ctypes.data, gw, row.ctypes.data, gh,
                                               _ptr(ranges), _ptr(count), self._stream()))
+        self._hold(col, row)
         return count
 
     def tissue_focus(self, thumb_u8, threshold=0.02, sigma=3.0, value=False):
@@ -491,11 +501,7 @@ class Engine:
         gw, gh = len(col), len(row)
         if gw > tissue.MAX_GRID or gh > tissue.MAX_GRID:
             raise ValueError(f'a grid is 1 .. {tissue.MAX_GRID} cells a side, not {gh} x {gw}')
-        if not 0 <= int(T) <= 255:
-            raise ValueError(f'T must lie in 0 .. 255, not {T!r}')
-        for name, r, n in (('col', col, wo), ('row', row, ho)):
-            if (r[:, 0] < 0).any() or (r[:, 0] >= r[:, 1]).any() or (r[:, 1] > n).any():
-                raise ValueError(f'a {name} range is empty or outside the {ho} x {wo} plane')
+        self._check_cells(T, col, row, ho, wo)
         xmap = tissue.plane_map(wo, wf) if xmap is None else np.ascontiguousarray(xmap, np.int32)
         ymap = tissue.plane_map(ho, hf) if ymap is None else np.ascontiguousarray(ymap, np.int32)
         for name, m, n_to, n_from in (('xmap', xmap, wo, wf), ('ymap', ymap, ho, hf)):
@@ -505,10 +511,10 @@ class Engine:
                 raise ValueError(f'{name} leaves the focus plane ({n_from}) or decreases')
         tables = torch.empty(wo + ho + 2 * (gw + gh), dtype=torch.int32, device=self.device)
         count = torch.empty((gh, gw), dtype=torch.int32, device=self.device)
-        self._tissue_host = (col, row, xmap, ymap)                          # the host tables live until the stream has copied them
         self._check(self._lib.bq_tissue_cells_union(self._ctx, _ptr(otsu_plane), ho, wo, int(T), _ptr(focus_plane), hf, wf,
                                                     xmap.ctypes.data, ymap.ctypes.data, col.ctypes.data, gw, row.ctypes.data, gh,
                                                     _ptr(tables), _ptr(count), self._stream()))
+        self._hold(col, row, xmap, ymap)
         return count
 
     def roi_plane(self, xs, ys, polygons):
@@ -531,11 +537,7 @@ class Engine:
         plane = torch.empty((h, w), dtype=torch.uint8, device=self.device)
         self._check(self._lib.bq_roi_plane(self._ctx, edges.ctypes.data, len(edges), starts.ctypes.data, len(starts) - 1, xs.ctypes.data,
                                            w, ys.ctypes.data, h, _ptr(tables), _ptr(plane), self._stream()))
-        # the host tables must stay valid until the stream has passed the call: each call's are held until an event recorded
-        # behind it has completed (queried, never waited for), so back-to-back calls do not release one another's
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream(self.device))
-        self._roi_host = [(e, t) for e, t in self._roi_host if not e.query()] + [(done, (edges, starts, xs, ys))]
+        self._hold(edges, starts, xs, ys)
         return plane
 
     def reinhard_fast(self, tiles_u8, target_means, target_stds, out=None):

@@ -1,9 +1,9 @@
 """Tile extraction: a slide file -> one Slideflow tile TFRecord, on the device (DESIGN.md "Tile extraction").
 
 The reference starts with ``extract_tiles(tile_px=299, tile_um=302, qc='both')`` over a cohort; ``extract_slide`` is that step for
-one pyramidal TIFF / SVS file.  It is ``Heatmap.from_slide``'s input half with no network behind it and uses its machinery: the
-masks over the grid (``Heatmap._masks``: the caller's mask, Otsu and focus QC, regions of interest), the band-to-batch loop
-(``Heatmap._batches``: ``WSI.bands``, canvas upload or device decode, ``Engine.tile_resample``, ``Engine.tile_grayspace``) -- and
+one pyramidal TIFF / SVS file.  It is the slide input stage (``slide_input.py``) with no network behind it: the masks over the grid
+(``MaskSpec`` / ``build_masks``: the caller's mask, Otsu and focus QC, regions of interest), the band-to-batch loop
+(``batches``: ``WSI.bands``, canvas upload or device decode, ``Engine.tile_resample``, ``Engine.tile_grayspace``) -- and
 then, in place of stain normalisation and ``mc_infer``, ``Engine.jpeg_encode``: the batch leaves the device as the JPEG files
 Pillow would have written for its tiles.  The host frames them as records (``tfrecord.SlideWriter``) and holds no pixels.
 
@@ -18,6 +18,7 @@ import os
 import numpy as np
 
 from . import tfrecord
+from .slide_input import DECODE_STATS, MaskSpec, add_mask_arguments, band_stats, batches, build_masks, mask_keywords
 
 
 def tile_loc(cells, grid_w, stride, extract_px):
@@ -61,7 +62,6 @@ def extract_slide(engine, path, out, tile_px=299, tile_um=302, stride_div=1, mpp
     ``tfrecord.encode_image(tile, 'JPEG')`` -- Pillow -- writes for the tile at the default quality 95 / 4:2:0; ``loc_x`` /
     ``loc_y`` are ``tile_loc``'s; records stand in row-major grid order whatever the banding."""
     import torch
-    from .heatmap import Heatmap
     from .tfrecord_native import jpeg_subsampling
     from .wsi import WSI
     if decode not in ('host', 'gpu'):
@@ -70,8 +70,9 @@ def extract_slide(engine, path, out, tile_px=299, tile_um=302, stride_div=1, mpp
     if not 1 <= quality <= 100:
         raise ValueError(f'quality must lie in 1..100, not {quality!r}')
     jpeg_subsampling(subsampling)
-    polygons, roi_method, roi_filter, roi_width = Heatmap._check_masks(qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma,
-                                                                       rois, roi_method, roi_filter_method, roi_width)
+    spec = MaskSpec(cell_mask=cell_mask, qc=qc, qc_width=qc_width, qc_fraction=qc_fraction, focus_threshold=focus_threshold,
+                    focus_mpp=focus_mpp, focus_sigma=focus_sigma, rois=rois, roi_method=roi_method, roi_filter_method=roi_filter_method,
+                    roi_width=roi_width).checked()
     name = os.path.splitext(os.path.basename(str(path)))[0]
     if os.path.isdir(out) or not str(out).endswith('.tfrecords'):
         os.makedirs(out, exist_ok=True)
@@ -80,35 +81,27 @@ def extract_slide(engine, path, out, tile_px=299, tile_um=302, stride_div=1, mpp
     try:
         if w.grid_w * w.grid_h == 0:
             raise ValueError(f'{path}: the slide holds no {tile_um} um tile')
-        keep, threshold, focus, roi_info = Heatmap._masks(engine, w, cell_mask, qc, int(qc_width), qc_fraction, focus_threshold, focus_mpp,
-                                                          focus_sigma, polygons, roi_method, roi_filter, roi_width)
-        stats = {'gpu_bands': 0, 'host_bands': 0, 'segments': 0, 'bands_read': 0, 'gray_dropped': 0}
-        gw = w.grid_w
+        masks, stats, gw = build_masks(engine, w, spec), band_stats(), w.grid_w
         with tfrecord.SlideWriter(out, name) as writer:
             def write(cell, image):
                 (lx, ly), = tile_loc([cell], gw, w.stride, w.extract_px)
                 writer.write(image, lx, ly)
             order = RowMajor(write)
-            for tiles, ids, gy0 in Heatmap._batches(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, batch, decode,
-                                                    keep, stats):
+            for tiles, ids, gy0 in batches(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, batch, decode, masks.keep, stats):
                 buf, off = engine.jpeg_encode(tiles, quality, subsampling)
                 data = buf.cpu().numpy()
                 off = off.numpy()
                 order.add(ids, [data[off[i]:off[i + 1]].tobytes() for i in range(len(ids))], gy0 * gw)
             order.flush()
             torch.cuda.synchronize(engine.device)
-        masked = 0 if keep is None else int(keep.size - keep.sum())
         summary = {
             'slide': str(path), 'tfrecord': out, 'grid_shape': [w.grid_h, w.grid_w], 'tile_px': int(tile_px), 'tile_um': tile_um,
             'stride_div': int(stride_div), 'stride': int(w.stride), 'extract_px': int(w.extract_px),
-            'cells': int(w.grid_h * w.grid_w), 'cells_kept_by_masks': int(w.grid_h * w.grid_w - masked),
-            'cells_dropped': {'masks': masked, 'roi': None if roi_info is None else roi_info['cells_dropped'],
+            'cells': int(w.grid_h * w.grid_w), 'cells_kept_by_masks': int(w.grid_h * w.grid_w - masks.dropped),
+            'cells_dropped': {'masks': masks.dropped, 'roi': None if masks.roi is None else masks.roi['cells_dropped'],
                               'grayspace': int(stats['gray_dropped'])},
-            'qc': None if keep is None else dict({'method': qc, 'threshold': threshold, 'bands_read': stats['bands_read'],
-                                                  'bands_skipped_rows': int((~keep.any(1)).sum())}, **(focus or {})),
-            'roi': roi_info,
-            'tiles_written': writer.records, 'bytes_written': writer.nbytes,
-            'decode_stats': {k: stats[k] for k in ('gpu_bands', 'host_bands', 'segments')},
+            'qc': masks.qc(stats['bands_read']), 'roi': masks.roi, 'tiles_written': writer.records, 'bytes_written': writer.nbytes,
+            'decode_stats': {k: stats[k] for k in DECODE_STATS},
             'quality': quality, 'subsampling': subsampling if isinstance(subsampling, str) else {0: '4:4:4', 2: '4:2:0'}[subsampling],
         }
     finally:
@@ -136,24 +129,9 @@ def main(argv=None):
     ap.add_argument('--grayspace-fraction', type=float, default=None,
                     help='drop tiles with more than this fraction of grey pixels (Slideflow extracts with 0.6); default: off')
     ap.add_argument('--grayspace-threshold', type=float, default=0.05)
-    ap.add_argument('--qc', default=None, choices=['otsu'], help="tissue mask from the slide's thumbnail; default: off")
-    ap.add_argument('--qc-width', type=int, default=2048)
-    ap.add_argument('--qc-fraction', type=float, default=0.6)
-    ap.add_argument('--qc-focus', type=float, nargs='?', const=0.02, default=None, metavar='THRESHOLD',
-                    help="focus mask (bare: 0.02), alone or with --qc otsu (Slideflow's qc='both'); default: off")
-    ap.add_argument('--qc-focus-mpp', type=float, default=4.0)
-    ap.add_argument('--qc-focus-sigma', type=float, default=3.0)
-    ap.add_argument('--rois', default=None, metavar='FILE', help="regions of interest, Slideflow's ROI_Name,X_base,Y_base CSV; default: off")
-    ap.add_argument('--roi-method', default='auto', choices=['auto', 'inside', 'outside', 'ignore'])
-    ap.add_argument('--roi-filter', default='center', metavar='center|SHARE')
-    ap.add_argument('--roi-width', type=int, default=2048)
+    add_mask_arguments(ap)
     args = ap.parse_args(argv)
-    roi_filter = args.roi_filter
-    if roi_filter != 'center':
-        try:
-            roi_filter = float(roi_filter)
-        except ValueError:
-            ap.error(f"--roi-filter takes 'center' or a share in (0, 1], not {args.roi_filter!r}")
+    masks = mask_keywords(ap, args)
     from .engine import Engine
     from .weights import synthetic_weights
     eng = Engine(synthetic_weights(1), max_batch=8, max_mc=2)          # (no network runs here: the context is what is needed)
@@ -162,10 +140,7 @@ def main(argv=None):
             t0 = time.perf_counter()
             s = extract_slide(eng, slide, args.out, tile_px=args.tile_px, tile_um=args.tile_um, stride_div=args.stride_div, mpp=args.mpp,
                               quality=args.quality, subsampling=args.subsampling, decode='gpu' if args.gpu_decode else 'host',
-                              qc=args.qc, focus_threshold=args.qc_focus, rois=args.rois, grayspace_fraction=args.grayspace_fraction,
-                              batch=args.batch, grayspace_threshold=args.grayspace_threshold, qc_width=args.qc_width,
-                              qc_fraction=args.qc_fraction, focus_mpp=args.qc_focus_mpp, focus_sigma=args.qc_focus_sigma,
-                              roi_method=args.roi_method, roi_filter_method=roi_filter, roi_width=args.roi_width)
+                              grayspace_fraction=args.grayspace_fraction, batch=args.batch, grayspace_threshold=args.grayspace_threshold, **masks)
             dt = time.perf_counter() - t0
             print(json.dumps({'slide': slide, 'tfrecord': s['tfrecord'], 'tiles_written': s['tiles_written'],
                               'bytes_written': s['bytes_written'], 'seconds': round(dt, 3)}))

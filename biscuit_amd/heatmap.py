@@ -4,8 +4,8 @@ The reference builds ``sf.Heatmap(slide, model, stride_div=1)`` and masks it wit
 uncertainty threshold (results.py:217-227), then walks the slide's tile grid through
 ``UncertaintyInterface`` and sorts the tiles into ``uq_incl`` / ``uq_excl`` (results.py:234-265).
 This front-end takes the tiles of a grid -- one slide's TFRecord with its ``loc_x`` / ``loc_y``, a region in memory
-(``from_region``), or a pyramidal TIFF / SVS slide file through this build's own reader (``from_slide``, ``biscuit_amd/wsi.py``,
-round 6) -- and lays the same MC-dropout kernels' outputs out as the two grids the reference uses:
+(``from_region``), or a pyramidal TIFF / SVS slide file (``from_slide``: this build's own reader, ``biscuit_amd/wsi.py``, behind the
+slide input stage, ``biscuit_amd/slide_input.py``) -- and lays the same MC-dropout kernels' outputs out as the two grids the reference uses:
 
     hm.logits       [gy, gx, 2]   mean class probabilities over the MC passes
     hm.uncertainty  [gy, gx, 2]   their population std
@@ -20,6 +20,8 @@ side (geometry tables, colour table, checks).
 """
 import numpy as np
 import torch
+
+from .slide_input import DECODE_STATS, MaskSpec, add_mask_arguments, band_stats, batches, build_masks, mask_keywords, upload
 
 MASKED = -1.0
 
@@ -50,10 +52,8 @@ class Heatmap:
     # what ``render`` needs to place the grid on the slide; ``from_slide`` records them, the other constructors have no slide
     slide_path = slide_w0 = slide_h0 = stride = extract_px = None
     _slide_kw = None
-    # the tissue mask ``from_slide(cell_mask=..., qc=...)`` ran under: the bool [gh, gw] mask and what it did; None without one
-    cell_mask = qc = None
-    # what ``from_slide(rois=...)`` did: {'method', 'filter', 'polygons', 'vertices', 'cells_dropped'}; None without ROIs
-    roi = None
+    # what ``from_slide``'s masks did (``slide_input.Masks``): the bool [gh, gw] keep mask, the ``qc`` and the ``roi`` record; None without
+    cell_mask = qc = roi = None
 
     def __init__(self, engine, tiles, grid, grid_shape=None, mc_n=30, seed=0, batch=256, norm_fit=None, normalizer='reinhard_fast'):
         """tiles: uint8 [T,299,299,3] (host or device); grid: int [T,2] (gx, gy) cell of each tile.  ``norm_fit`` / ``normalizer``:
@@ -73,7 +73,7 @@ class Heatmap:
             raise ValueError('grid position outside grid_shape')
         self.grid = grid
         self.dropped = 0                 # tiles a background filter left out (from_slide(grayspace_fraction=...))
-        self.decode_stats = {'gpu_bands': 0, 'host_bands': 0, 'segments': 0}      # (from_slide(resample='gpu') counts its bands)
+        self.decode_stats = dict.fromkeys(DECODE_STATS, 0)                       # (from_slide(resample='gpu') counts its bands)
         self.logits = np.full((gy, gx, 2), MASKED, dtype=np.float32)
         self.uncertainty = np.full((gy, gx, 2), MASKED, dtype=np.float32)
         dev = engine.device
@@ -169,13 +169,14 @@ class Heatmap:
             raise ValueError(f"decode must be 'host' or 'gpu', not {decode!r}")
         if resample == 'host' and decode == 'gpu':
             raise ValueError("the device decodes into the band's canvas: decode='gpu' needs resample='gpu'")
-        polygons, roi_method, roi_filter, roi_width = cls._check_masks(qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma,
-                                                                         rois, roi_method, roi_filter_method, roi_width)
+        spec = MaskSpec(cell_mask=cell_mask, qc=qc, qc_width=qc_width, qc_fraction=qc_fraction, focus_threshold=focus_threshold,
+                        focus_mpp=focus_mpp, focus_sigma=focus_sigma, rois=rois, roi_method=roi_method,
+                        roi_filter_method=roi_filter_method, roi_width=roi_width).checked()
         if resample == 'host' and (qc is not None or cell_mask is not None):
             raise ValueError("the tissue mask steers the streamed read: qc and cell_mask need resample='gpu'")
         if resample == 'host' and focus_threshold is not None:
             raise ValueError("the focus mask steers the streamed read: focus_threshold needs resample='gpu'")
-        if roi_method != 'ignore' and resample == 'host':
+        if spec.roi_method != 'ignore' and resample == 'host':
             raise ValueError("the region-of-interest mask steers the streamed read: rois needs resample='gpu'")
         w = WSI(path, tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
         try:
@@ -185,235 +186,38 @@ class Heatmap:
                 tiles, grid = w.tiles()
                 hm = cls(engine, tiles, grid, grid_shape=(w.grid_h, w.grid_w), **kw)
             else:
-                keep, threshold, focus, roi_info = cls._masks(engine, w, cell_mask, qc, int(qc_width), qc_fraction, focus_threshold,
-                                                              focus_mpp, focus_sigma, polygons, roi_method, roi_filter, roi_width)
-                hm = cls._streamed(engine, w, int(canvas_bytes), grayspace_fraction, grayspace_threshold, decode=decode, keep=keep, **kw)
-                if keep is not None:
-                    hm.qc = dict(hm.qc, method=qc, threshold=threshold, **(focus or {}))
-                if roi_info is not None:
-                    hm.roi = roi_info
+                hm = cls._streamed(engine, w, build_masks(engine, w, spec), int(canvas_bytes), grayspace_fraction, grayspace_threshold,
+                                   decode=decode, **kw)
             hm.slide_path, (hm.slide_w0, hm.slide_h0), hm.stride, hm.extract_px = path, w.slide.dimensions, w.stride, w.extract_px
             hm._slide_kw = dict(tile_px=tile_px, tile_um=tile_um, stride_div=stride_div, mpp=mpp)
             return hm
         finally:
             w.close()
 
-    @staticmethod
-    def _check_masks(qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma, rois, roi_method, roi_filter_method, roi_width):
-        """The mask keywords of ``from_slide`` (and of ``extract.extract_slide``) checked, on or off: ValueError, or ``(polygons,
-        roi_method, roi_filter, roi_width)`` resolved -- the polygons read, 'auto' decided."""
-        import os
-        from . import roi, tissue
-        if qc is not None and qc not in tissue.QC_METHODS:
-            raise ValueError(f"qc must be None or one of {tissue.QC_METHODS}, not {qc!r}")
-        if qc is not None:
-            tissue.check_fraction(qc_fraction)
-            if int(qc_width) < 1:
-                raise ValueError(f'qc_width must be at least 1, not {qc_width!r}')
-        tissue.check_focus(0.0 if focus_threshold is None else focus_threshold, focus_mpp, focus_sigma)      # (its keywords, on or off)
-        if focus_threshold is not None:
-            tissue.check_fraction(qc_fraction)
-        roi_filter, roi_width = roi.check_filter(roi_filter_method), roi.check_width(roi_width)      # (its keywords, on or off)
-        polygons = None
-        if rois is not None:
-            polygons = roi.read_csv(rois) if isinstance(rois, (str, os.PathLike)) else roi.check_polygons(rois)
-        return polygons, roi.check_method(roi_method, polygons is not None), roi_filter, roi_width
-
     @classmethod
-    def _masks(cls, engine, w, cell_mask, qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma, polygons, roi_method,
-               roi_filter, roi_width):
-        """The keep mask of the open slide ``w`` from the caller's mask, the tissue / focus QC and the regions of interest, ANDed:
-        ``(keep bool [grid_h, grid_w] or None without any, the Otsu threshold or None, the focus entries of ``qc`` or None, the
-        ``roi`` record or None)``."""
-        from . import tissue
-        keep = threshold = None
-        if cell_mask is not None:
-            keep = tissue.check_mask(cell_mask, w.grid_h, w.grid_w).copy()
-        focus = None
-        if focus_threshold is not None:
-            qc_keep, threshold, focus = cls._focus_mask(engine, w, qc, int(qc_width), qc_fraction, focus_threshold, focus_mpp,
-                                                        focus_sigma)
-            keep = qc_keep if keep is None else keep & qc_keep
-        elif qc is not None:
-            qc_keep, threshold = cls._otsu_mask(engine, w, int(qc_width), qc_fraction)
-            keep = qc_keep if keep is None else keep & qc_keep
-        roi_info = None
-        if roi_method != 'ignore':
-            roi_keep = cls._roi_mask(engine, w, polygons, roi_method, roi_filter, roi_width)
-            roi_info = {'method': roi_method, 'filter': roi_filter, 'polygons': len(polygons),
-                        'vertices': int(sum(len(a) for a in polygons)), 'cells_dropped': int(roi_keep.size - roi_keep.sum())}
-            keep = roi_keep if keep is None else keep & roi_keep
-        return keep, threshold, focus, roi_info
-
-    @staticmethod
-    def _otsu_mask(engine, w, qc_width, qc_fraction):
-        """``qc='otsu'`` for the open slide ``w``: (keep bool [grid_h, grid_w], the Otsu threshold).  The thumbnail goes up once;
-        256 histogram counts and the cells' counts come back."""
-        from . import tissue
-        thumb = np.ascontiguousarray(w.thumbnail(qc_width))
-        plane, hist = engine.tissue_blur(torch.from_numpy(thumb if thumb.flags.writeable else thumb.copy()).to(engine.device))
-        threshold = tissue.otsu_threshold(hist.cpu().numpy())
-        sw, sh = w.slide.dimensions
-        col, row = tissue.cell_ranges(w.grid_w, w.grid_h, thumb.shape[1], thumb.shape[0], sw, sh, w.stride, w.extract_px)
-        counts = engine.tissue_cells(plane, threshold, col, row).cpu().numpy()
-        return tissue.keep_from_counts(counts, col, row, qc_fraction), threshold
-
-    @staticmethod
-    def _focus_mask(engine, w, qc, qc_width, qc_fraction, focus_threshold, focus_mpp, focus_sigma):
-        """``focus_threshold=...`` for the open slide ``w``, alone (``qc`` None) or with ``qc='otsu'``: (keep bool [grid_h,
-        grid_w], the Otsu threshold or None, the focus entries of ``hm.qc``).  Alone, a cell's out-of-focus pixels are counted
-        over its range of the focus plane; with Otsu, the union is counted over its range of the Otsu plane."""
-        from . import tissue
-
-        def up(a):
-            a = np.ascontiguousarray(a)
-            return torch.from_numpy(a if a.flags.writeable else a.copy()).to(engine.device)
-        sw, sh = w.slide.dimensions
-        fthumb = up(w.thumbnail(tissue.focus_width(sw, w.mpp, focus_mpp)))
-        fh, fw = int(fthumb.shape[0]), int(fthumb.shape[1])
-        fplane, fcount = engine.tissue_focus(fthumb, focus_threshold, focus_sigma)
-        del fthumb
-        threshold = None
-        if qc is None:
-            col, row = tissue.cell_ranges(w.grid_w, w.grid_h, fw, fh, sw, sh, w.stride, w.extract_px)
-            counts = engine.tissue_cells(fplane, 0, col, row)
-        else:
-            othumb = up(w.thumbnail(qc_width))
-            oplane, hist = engine.tissue_blur(othumb)
-            threshold = tissue.otsu_threshold(hist.cpu().numpy())
-            col, row = tissue.cell_ranges(w.grid_w, w.grid_h, int(othumb.shape[1]), int(othumb.shape[0]), sw, sh, w.stride, w.extract_px)
-            counts = engine.tissue_cells_union(oplane, threshold, fplane, col, row)
-        info = {'focus_threshold': float(focus_threshold), 'focus_width': fw, 'focus_share': int(fcount.cpu().numpy()[0]) / float(fh * fw)}
-        return tissue.keep_from_counts(counts.cpu().numpy(), col, row, qc_fraction), threshold, info
-
-    @staticmethod
-    def _roi_mask(engine, w, polygons, method, roi_filter, roi_width):
-        """``rois=...`` for the open slide ``w`` -> keep bool [grid_h, grid_w].  'center': the plane of the cells' centres comes
-        back; a share: the plane is made on a ``roi_width``-wide raster and stays on the device, the cells' counts come back."""
-        from . import roi, tissue
-        if roi_filter == 'center':
-            xs, ys = roi.center_tables(w.grid_w, w.grid_h, w.stride, w.extract_px)
-            return roi.keep_from_plane(engine.roi_plane(xs, ys, polygons).cpu().numpy(), method)
-        sw, sh = w.slide.dimensions
-        xs, ys = roi.raster_tables(sw, sh, roi_width)
-        col, row = tissue.cell_ranges(w.grid_w, w.grid_h, len(xs), len(ys), sw, sh, w.stride, w.extract_px)
-        outside = engine.tissue_cells(engine.roi_plane(xs, ys, polygons), 0, col, row).cpu().numpy()
-        return roi.keep_from_share(outside, col, row, roi_filter, method)
-
-    @classmethod
-    @staticmethod
-    def _decode_band(engine, sg):
-        """A band's canvas decoded on the device from its raw JPEG tiles (``wsi.BandSegments``): extract on the host, upload
-        scan, descriptors, tables and places, fill the canvas with 255, decode, read the status once.  -> the canvas (uint8
-        [H, W, 3] on the device), or None when the extractor refuses a segment or any status is not 0."""
-        from . import tfrecord_native as tn
-        try:
-            scan, desc, tables = tn.extract_jpeg_segments(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h, sg.jpeg_tables)
-        except ValueError:                                                       # (UnsupportedImage is one)
-            return None
-        dev = engine.device
-        canvas = torch.full(tuple(sg.shape) + (3,), 255, dtype=torch.uint8, device=dev)
-        if len(sg) == 0:
-            return canvas
-        status = engine.jpeg_decode_canvas(torch.from_numpy(scan).to(dev), torch.from_numpy(desc.view(np.int32)).to(dev),
-                                           torch.from_numpy(tables).to(dev), sg.seg_w, sg.seg_h, torch.from_numpy(sg.place).to(dev),
-                                           canvas, sg.clip)
-        return None if bool(status.any().item()) else canvas
-
-    @classmethod
-    def _batches(cls, engine, w, canvas_bytes, gray_fraction, gray_threshold, batch, decode, mask, stats):
-        """The band-to-batch loop of a streamed slide, for ``_streamed`` and for ``extract.extract_slide``: walks ``w.bands``,
-        uploads or device-decodes each band's canvas, fills ONE device batch with ``Engine.tile_resample`` across band boundaries
-        and drops background tiles with ``Engine.tile_grayspace`` if asked.  Yields ``(tiles, ids, gy0)`` for every full batch
-        and the last partial one: a view of the batch buffer (uint8 [n, px, px, 3] on the device, valid until the next step),
-        the tiles' row-major grid indices (int64 [n], the caller's to keep) and the first grid row of the band being read
-        (``WSI.band_rows``, not the rectangle's own: a later column range of the band may start higher up) -- every cell of an
-        earlier row has been yielded by then.  ``stats``: a dict whose 'gpu_bands' / 'host_bands' / 'segments' /
-        'bands_read' / 'gray_dropped' are counted up."""
-        if gray_fraction is not None and not 0.0 <= float(gray_fraction) <= 1.0:
-            raise ValueError('grayspace_fraction must lie in [0, 1]')
-        gw, px, dev, batch = w.grid_w, w.tile_px, engine.device, int(batch)
-        buf = torch.empty((batch, px, px, 3), dtype=torch.uint8, device=dev)      # the one batch the device holds
-        idx = np.empty(batch, np.int64)                                          # its tiles' row-major grid indices
-        fill = 0
-        for gy0, gy1, gx0, gx1, canvas, origin, src_px in w.bands(canvas_bytes, segments=decode == 'gpu', keep=mask):
-            d_canvas = None
-            if decode == 'gpu' and canvas is not None:
-                d_canvas = cls._decode_band(engine, canvas)
-                if d_canvas is not None:
-                    stats['gpu_bands'] += 1
-                    stats['segments'] += len(canvas)
-            if d_canvas is None:
-                if decode == 'gpu':
-                    canvas = w.band(gy0, gy1, gx0, gx1)[0]                       # the host's pixels, or the host's SlideError
-                d_canvas = torch.from_numpy(canvas).to(dev)
-                stats['host_bands'] += 1
-            d_origin = torch.from_numpy(origin).to(dev)
-            del canvas, origin                                                   # uploaded: the host holds one canvas at a time
-            cell = (np.arange(gy0, gy1, dtype=np.int64)[:, None] * gw + np.arange(gx0, gx1, dtype=np.int64)[None, :]).reshape(-1)
-            if mask is not None:
-                stats['bands_read'] += 1
-                pos = np.flatnonzero(mask[gy0:gy1, gx0:gx1].reshape(-1))       # the rectangle's kept cells, row-major
-                if len(pos) < len(cell):
-                    d_origin, cell = d_origin[torch.from_numpy(pos).to(dev)], cell[pos]
-            a = 0
-            while a < len(cell):
-                m = min(len(cell) - a, batch - fill)
-                dst = buf[fill:fill + m]
-                engine.tile_resample(d_canvas, d_origin[a:a + m], src_px, px, out=dst)
-                ids = cell[a:a + m]
-                if gray_fraction is not None:
-                    grey = engine.tile_grayspace(dst, gray_threshold).cpu().numpy()
-                    keep = ~(grey / float(px * px) > float(gray_fraction))
-                    if not keep.all():
-                        sel = torch.from_numpy(np.flatnonzero(keep)).to(dev)
-                        if len(sel):
-                            dst[:len(sel)] = dst[sel]                             # (the right side is a copy: no overlap)
-                        stats['gray_dropped'] += m - len(sel)
-                        ids = ids[keep]
-                idx[fill:fill + len(ids)] = ids
-                fill += len(ids)
-                a += m
-                if fill == batch:
-                    yield buf[:fill], idx[:fill].copy(), w.band_rows[0]
-                    fill = 0
-            del d_canvas
-        if fill:
-            yield buf[:fill], idx[:fill].copy(), w.grid_h
-
-    @classmethod
-    def _streamed(cls, engine, w, canvas_bytes, gray_fraction, gray_threshold, mc_n=30, seed=0, batch=256, norm_fit=None,
-                  normalizer='reinhard_fast', decode='host', keep=None):
+    def _streamed(cls, engine, w, masks, canvas_bytes, gray_fraction, gray_threshold, mc_n=30, seed=0, batch=256, norm_fit=None,
+                  normalizer='reinhard_fast', decode='host'):
         """``from_slide(resample='gpu')``: bands -> batches of exactly the tiles ``Heatmap(engine, *w.tiles())`` would put in
-        each batch (a batch is filled across band boundaries: ``_batches``), so an unfiltered slide runs the same launches on the
-        same bytes.  ``keep`` (bool [grid_h, grid_w] or None): the tissue mask -- only its bands are read and only its cells are
-        resampled."""
+        each batch (a batch is filled across band boundaries: ``slide_input.batches``), so an unfiltered slide runs the same
+        launches on the same bytes.  ``masks`` (``slide_input.Masks``): only its kept cells are read and run; ``hm.qc`` / ``hm.roi``."""
         from . import stain
         stain.check(normalizer, norm_fit)
         hm = cls.__new__(cls)
         gh, gw, dev = w.grid_h, w.grid_w, engine.device
         hm.logits = np.full((gh, gw, 2), MASKED, dtype=np.float32)
         hm.uncertainty = np.full((gh, gw, 2), MASKED, dtype=np.float32)
-        hm.dropped = 0
-        stats = {'gpu_bands': 0, 'host_bands': 0, 'segments': 0, 'bands_read': 0, 'gray_dropped': 0}
-        kept = []
-        mask = keep
-        if mask is not None:
-            hm.cell_mask = mask
-            hm.dropped = int(mask.size - mask.sum())
-            hm.qc = {'method': None, 'threshold': None, 'cells_dropped': hm.dropped, 'bands_read': 0,
-                     'bands_skipped_rows': int((~mask.any(1)).sum())}
-        for tiles, ids, _ in cls._batches(engine, w, canvas_bytes, gray_fraction, gray_threshold, batch, decode, mask, stats):
+        hm.cell_mask = masks.keep
+        stats, kept = band_stats(), []
+        for tiles, ids, _ in batches(engine, w, canvas_bytes, gray_fraction, gray_threshold, batch, decode, masks.keep, stats):
             cur = stain.normalise(engine, tiles, normalizer, norm_fit)
             mean, std = engine.mc_infer(cur, mc_n, seed, tile_idx=torch.from_numpy(ids).to(dev))
             gy, gx = np.divmod(ids, gw)
             hm.logits[gy, gx] = mean.cpu().numpy()
             hm.uncertainty[gy, gx] = std.cpu().numpy()
             kept.append(ids)
-        hm.dropped += stats['gray_dropped']
-        if mask is not None:
-            hm.qc['bands_read'] = stats['bands_read']
-        hm.decode_stats = {k: stats[k] for k in ('gpu_bands', 'host_bands', 'segments')}
+        hm.dropped = masks.dropped + stats['gray_dropped']
+        hm.qc, hm.roi = masks.qc(stats['bands_read'], cells_dropped=True), masks.roi
+        hm.decode_stats = {k: stats[k] for k in DECODE_STATS}
         cells = np.concatenate(kept) if kept else np.zeros(0, np.int64)
         hm.grid = np.stack([cells % gw, cells // gw], 1)
         return hm
@@ -469,13 +273,8 @@ class Heatmap:
             raise ValueError('thumb must be uint8 [H, W, 3]')
         gh, gw = values.shape
         col, row = R.render_tables(gw, gh, thumb.shape[1], thumb.shape[0], interpolation=interpolation, **geom)
-        dev = engine.device
-
-        def up(a):
-            a = np.ascontiguousarray(a)
-            return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)              # (a Pillow array is read-only)
-        d_thumb = up(thumb)
-        out = engine.heatmap_render(up(values), up(col), up(row), up(lut), d_thumb, vmin=vmin, vmax=vmax, alpha=alpha,
+        d_thumb, d_values, d_col, d_row, d_lut = (upload(a, engine.device) for a in (thumb, values, col, row, lut))
+        out = engine.heatmap_render(d_values, d_col, d_row, d_lut, d_thumb, vmin=vmin, vmax=vmax, alpha=alpha,
                                     interpolation=interpolation, out=d_thumb)
         return out.cpu().numpy()
 
@@ -541,14 +340,12 @@ def main(argv=None):
     """``python -m biscuit_amd.heatmap SLIDE --out DIR``: the UQ heatmap of one slide file (results.py:216-265) on disk --
     ``DIR/heatmap.npz`` (``logits``, ``uncertainty``, ``grid``; with ``--tile-uq`` also ``uq_mask`` and ``masked_logits``, the
     logits with the uncertain cells set to -1 as results.py:222-225 does), ``DIR/summary.json`` and, with ``--save-tiles``, the
-    tiles as ``uq_incl/`` / ``uq_excl/`` PNGs named as results.py:259 names them.  ``--qc otsu`` masks the slide's background from
-    its thumbnail first (``from_slide(qc='otsu')``): ``heatmap.npz`` then also holds ``cell_mask`` and ``summary.json`` a ``qc``
-    entry.  ``--qc-focus [THRESHOLD]`` (bare: 0.02) masks its out-of-focus regions (``from_slide(focus_threshold=...)``), alone or
-    with ``--qc otsu`` (Slideflow's ``qc='both'``), and writes the same two.  ``--rois FILE`` runs only the cells that the polygons of a
-    Slideflow ROI CSV select (``from_slide(rois=...)``; ``--roi-method``, ``--roi-filter``, ``--roi-width``): ``heatmap.npz`` then holds
-    ``cell_mask`` and ``summary.json`` a ``roi`` entry.  ``--render`` adds the pictures of
-    ``Heatmap.save`` (results.py:217-227): ``<slide>-raw.png``, ``-0.png``, ``-1.png``, ``-uncertainty.png`` and, with ``--tile-uq``,
-    the masked pair under ``high_confidence/``; ``summary.json`` then lists them as ``rendered``."""
+    tiles as ``uq_incl/`` / ``uq_excl/`` PNGs named as results.py:259 names them.  Under the mask flags (``--qc otsu``, ``--qc-focus
+    [THRESHOLD]``, ``--rois FILE`` and their companions: ``from_slide``'s mask keywords) only the kept cells are read and run:
+    ``heatmap.npz`` then also holds ``cell_mask``, and ``summary.json`` a ``qc`` entry (``--qc``, ``--qc-focus``; Slideflow's
+    ``qc='both'`` is both) and a ``roi`` entry (``--rois``).  ``--render`` adds the pictures of ``Heatmap.save`` (results.py:217-227):
+    ``<slide>-raw.png``, ``-0.png``, ``-1.png``, ``-uncertainty.png`` and, with ``--tile-uq``, the masked pair under
+    ``high_confidence/``; ``summary.json`` then lists them as ``rendered``."""
     import argparse
     import json
     import os
@@ -569,25 +366,7 @@ def main(argv=None):
     ap.add_argument('--grayspace-fraction', type=float, default=None,
                     help='drop tiles with more than this fraction of grey pixels (Slideflow extracts with 0.6); default: off')
     ap.add_argument('--grayspace-threshold', type=float, default=0.05)
-    ap.add_argument('--qc', default=None, choices=['otsu'],
-                    help="tissue mask from the slide's thumbnail before anything is read at full resolution (from_slide(qc=...)): "
-                         'adds cell_mask to heatmap.npz and qc to summary.json; default: off')
-    ap.add_argument('--qc-width', type=int, default=2048, help='width of the thumbnail --qc judges')
-    ap.add_argument('--qc-fraction', type=float, default=0.6,
-                    help='--qc drops a cell with more than this fraction of background pixels')
-    ap.add_argument('--qc-focus', type=float, nargs='?', const=0.02, default=None, metavar='THRESHOLD',
-                    help="focus mask from the slide's 4 um / pixel thumbnail (from_slide(focus_threshold=...); bare: 0.02), alone or "
-                         "with --qc otsu (Slideflow's qc='both'): adds cell_mask to heatmap.npz and qc to summary.json; default: off")
-    ap.add_argument('--qc-focus-mpp', type=float, default=4.0, help='microns per pixel of the thumbnail --qc-focus judges')
-    ap.add_argument('--qc-focus-sigma', type=float, default=3.0, help="sigma of --qc-focus's Gaussian, in thumbnail pixels")
-    ap.add_argument('--rois', default=None, metavar='FILE',
-                    help="regions of interest, Slideflow's ROI_Name,X_base,Y_base CSV (from_slide(rois=...)): only the cells the "
-                         'polygons select are run; adds cell_mask to heatmap.npz and roi to summary.json; default: off')
-    ap.add_argument('--roi-method', default='auto', choices=['auto', 'inside', 'outside', 'ignore'],
-                    help="keep the cells inside the regions or outside them; 'auto': inside when --rois is given")
-    ap.add_argument('--roi-filter', default='center', metavar='center|SHARE',
-                    help="judge a cell by its centre, or keep it when at least SHARE (0 < SHARE <= 1) of it lies inside")
-    ap.add_argument('--roi-width', type=int, default=2048, help='width of the raster a --roi-filter SHARE is counted on')
+    add_mask_arguments(ap)
     ap.add_argument('--gpu-decode', action='store_true',
                     help="decode the slide's own JPEG tiles on the device (from_slide(decode='gpu')); the arrays do not change")
     ap.add_argument('--mpp', type=float, default=None, help='microns per pixel, for a file that does not say')
@@ -600,12 +379,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.save_tiles and args.tile_uq is None:
         ap.error('--save-tiles sorts by --tile-uq')
-    roi_filter = args.roi_filter
-    if roi_filter != 'center':
-        try:
-            roi_filter = float(roi_filter)
-        except ValueError:
-            ap.error(f"--roi-filter takes 'center' or a share in (0, 1], not {args.roi_filter!r}")
+    masks = mask_keywords(ap, args)
     from .__main__ import load_model_weights, model_hp_from
     from .engine import Engine
     weights, model_params = load_model_weights(args.model, args.weights)
@@ -617,10 +391,7 @@ def main(argv=None):
         hm = Heatmap.from_slide(eng, args.slide, stride_div=args.stride_div, mpp=args.mpp, mc_n=mc, seed=args.seed, batch=args.batch,
                                 norm_fit=norm_fit, normalizer=hp.normalizer or 'reinhard_fast',
                                 grayspace_fraction=args.grayspace_fraction, grayspace_threshold=args.grayspace_threshold,
-                                decode='gpu' if args.gpu_decode else 'host', qc=args.qc, qc_width=args.qc_width,
-                                qc_fraction=args.qc_fraction, focus_threshold=args.qc_focus, focus_mpp=args.qc_focus_mpp,
-                                focus_sigma=args.qc_focus_sigma, rois=args.rois, roi_method=args.roi_method,
-                                roi_filter_method=roi_filter, roi_width=args.roi_width)
+                                decode='gpu' if args.gpu_decode else 'host', **masks)
         torch.cuda.synchronize(eng.device)
         seconds = time.perf_counter() - t0
         rendered = None

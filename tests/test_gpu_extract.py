@@ -72,7 +72,7 @@ def test_records_are_pillows_files_in_row_major_order_whatever_the_banding(eng, 
 
 def test_masks_write_exactly_the_kept_cells(eng, tmp_path):
     from biscuit_amd.extract import extract_slide, tile_loc
-    from biscuit_amd.heatmap import Heatmap
+    from biscuit_amd.slide_input import MaskSpec, otsu_mask
     from biscuit_amd.wsi import WSI
     a = _img(2400, 1800, 5)
     a[:, 1196:] = 255                                                        # grid columns 2 and 3 of the 4 x 3 grid are glass
@@ -92,7 +92,7 @@ def test_masks_write_exactly_the_kept_cells(eng, tmp_path):
     check(extract_slide(eng, path, str(tmp_path / 'mine'), batch=16, cell_mask=mine, canvas_bytes=1), mine)
     w = WSI(path)
     try:
-        otsu, _ = Heatmap._otsu_mask(eng, w, 2048, 0.6)
+        otsu, _ = otsu_mask(eng, w, MaskSpec(qc_width=2048, qc_fraction=0.6))
     finally:
         w.close()
     assert otsu[:, :2].all() and not otsu[:, 2:].any()

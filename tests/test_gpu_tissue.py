@@ -1,5 +1,5 @@
 """The heatmap's tissue mask on the device (DESIGN.md "Heatmap input", Tissue mask): ``Engine.tissue_blur`` and ``Engine.tissue_cells``
-against the numpy restatement (tests/_tissue_ref.py) integer for integer, their refusals, ``Heatmap.from_slide(qc='otsu')`` against
+against the numpy restatement (tests/_tissue_ref.py) integer for integer, their refusals, the lifetime of their host tables, ``Heatmap.from_slide(qc='otsu')`` against
 the unmasked run bit for bit, and the command line: ``-m gpu``."""
 import json
 import os
@@ -133,6 +133,38 @@ def test_bad_arguments(eng):
     for bad in (thumb[:, :, :2], thumb.to(torch.int32), thumb[:0]):
         with pytest.raises(ValueError):
             eng.tissue_blur(bad)
+
+
+def test_tables_outlive_their_calls(eng):
+    """The engine's contract for the host tables it hands to the stream (``Engine._hold``): eight ``tissue_cells`` /
+    ``tissue_cells_union`` calls and two ``roi_plane`` calls on one stream with nothing in between that waits, every call with tables
+    of its own.  The caller's are int64, so the int32 copies the stream reads are referenced by the engine alone."""
+    import torch
+    from tests import _focus_ref as F
+    from tests import _roi_ref as R
+    rng = np.random.default_rng(20)
+    otsu, focus = rng.integers(0, 256, (48, 64), dtype=np.uint8), rng.integers(0, 2, (24, 32), dtype=np.uint8)
+    d_otsu, d_focus = torch.from_numpy(otsu).to(eng.device), torch.from_numpy(focus).to(eng.device)
+
+    def ranges(cells, n):
+        a = rng.integers(0, n, cells)
+        return np.stack([a, rng.integers(a + 1, n + 1)], 1).astype(np.int64)
+    cases = [(int(rng.integers(0, 256)), ranges(4, 64), ranges(3, 48)) for _ in range(8)]
+    triangle = [np.array([[3, 2], [90, 20], [30, 70]])]
+    samples = [(rng.integers(0, 200, 7).astype(np.int64), rng.integers(0, 160, 5).astype(np.int64)) for _ in range(2)]
+    torch.cuda.synchronize(eng.device)
+    got, planes = [], []
+    for i, (thr, col, row) in enumerate(cases):
+        got.append(eng.tissue_cells(d_otsu, thr, col, row) if i % 2 == 0 else eng.tissue_cells_union(d_otsu, thr, d_focus, col, row))
+        if i in (2, 5):
+            planes.append(eng.roi_plane(*samples[len(planes)], triangle))
+    torch.cuda.synchronize(eng.device)
+    for i, (thr, col, row) in enumerate(cases):
+        want = T.cell_counts(otsu, thr, col, row) if i % 2 == 0 else F.union_counts(otsu, thr, focus, col, row)
+        assert got[i].shape == (3, 4) and np.array_equal(got[i].cpu().numpy(), want), i
+    for (xs, ys), plane in zip(samples, planes):
+        assert plane.shape == (5, 7) and np.array_equal(plane.cpu().numpy(), R.plane(xs, ys, triangle))
+    assert len({g.cpu().numpy().tobytes() for g in got}) == 8 and all(0 < int(p.sum()) < 35 for p in planes)      # (no two alike, none trivial)
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------------------

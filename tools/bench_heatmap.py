@@ -51,7 +51,7 @@ skips on a real slide (``qc_report``: ``cells_dropped``, ``bands_skipped_rows``,
 the same slide under that cogwheel plus 40 small polygons, and on a 2 048 x 2 048 raster under a 10 000-vertex cogwheel (the design's
 worst case); the two rasters next to the wall time of the numpy restatement (``tests/_roi_ref.py``) on the same input, with a check
 that the planes are equal.  Then ``from_slide(rois=...)`` on the tool's slide (a cogwheel over its middle, a share of 0.5 on a
-2 048-wide raster) at the first ``--stride-div`` value next to the seconds of the mask alone (``Heatmap._roi_mask``, every result on
+2 048-wide raster) at the first ``--stride-div`` value next to the seconds of the mask alone (``slide_input.roi_mask``, every result on
 the host): the share of the masked run that the mask takes."""
 import argparse
 import json
@@ -283,6 +283,7 @@ def roi_leg(args, eng, slide, tag, emit, kw):
     sys.path.insert(0, HERE)
     from biscuit_amd import roi
     from biscuit_amd.heatmap import Heatmap
+    from biscuit_amd.slide_input import MaskSpec, roi_mask
     from biscuit_amd.wsi import WSI
     from tests import _roi_ref as ref
 
@@ -329,12 +330,13 @@ def roi_leg(args, eng, slide, tag, emit, kw):
     sw, sh = w.slide.dimensions
     polys = [cog(sw // 2, sh // 2, 0.45 * min(sw, sh), 0.3 * min(sw, sh), 3000)]
     rkw = dict(rois=polys, roi_filter_method=0.5, roi_width=2048)
+    spec = MaskSpec(**rkw).checked()                                        # ('auto' is 'inside' with polygons)
     try:
         alone = []
         for r in range(args.runs + 1):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            keep = Heatmap._roi_mask(eng, w, roi.check_polygons(polys), 'inside', 0.5, 2048)
+            keep = roi_mask(eng, w, spec)
             torch.cuda.synchronize()
             if r:
                 alone.append(time.perf_counter() - t0)
