@@ -1,23 +1,17 @@
-// C ABI of libbiscuit_hip.so (see include/biscuit_hip.h): context, BQW1 weight blob,
-// the Xception launch schedule, the MC-dropout head and event-based per-kernel timing.
-#include "../../include/biscuit_hip.h"
-#include "bq_common.h"
-#include "roi_device.h"
+// The network side of libbiscuit_hip.so's C ABI (include/biscuit_hip.h): the context (create, destroy, errors, options, masked
+// streams, tile indices), the BQW1 weight blob, the Xception launch schedule and its walker (backbone, MC-dropout head, bq_mc_infer,
+// the debug taps, bq_describe_schedule) and event-based per-kernel timing.  A tool's entry point stands beside its kernel, in
+// kernels_*.hip; bq_ctx.h is what they share with this file.
+#include "bq_ctx.h"
 
 #include <math.h>
 #include <cmath>
 #include <stdlib.h>
 #include <string.h>
 
-#include <map>
-#include <string>
-#include <vector>
-
 namespace {
 
 std::string g_create_error;
-
-struct Blob { const unsigned char* p = nullptr; size_t n = 0; };
 
 constexpr int pad16(int c) { return (c + 15) / 16 * 16; }
 
@@ -68,90 +62,38 @@ const Layer kLayers[] = {
 #undef SHORTCUT
 #undef ENTRY
 #undef MIDDLE
-constexpr int kNumLayers = sizeof kLayers / sizeof kLayers[0];
+static_assert(sizeof kLayers / sizeof kLayers[0] == kNumLayers, "bq_ctx.h sizes bq_ctx::layers by kNumLayers");
 // first rows of the blocks the walker names: three rows per block up to block 13 (a strided block's third is its shortcut)
 constexpr int kConv2 = 0, kBlock2 = 1, kBlock5 = 10, kBlock13 = 34, kBlock14 = 37;
-static_assert(kNumLayers == 39, "block1_conv2, 34 separable convolutions, 4 shortcuts");
-
-struct GemmLayer {   // what the blob holds for row i of kLayers
-    const void* wp = nullptr;
-    const void* wp16 = nullptr;   // the same weights in 16x16x32 fragment order (kernels_wide / stream / exit.hip)
-    const float* scale = nullptr;
-    const float* bias = nullptr;
-    const float* dw = nullptr;
-    int nfp = 0;             // padded n-frags in wp
-};
-
-
-struct HeadLayer {
-    const void* wh = nullptr; const void* wl = nullptr; const float* bias = nullptr; int k = 0;
-    int wexp = 0;                  // "hidden_N/wexp" of the blob: wh / wl hold W * 2^-wexp (weights.py: head_weight_exponent)
-};
-
-struct ProfRec { int cls; hipEvent_t a, b; };
 
 }  // namespace
-
-struct bq_ctx {
-    bq_config cfg{};
-    int device = 0;
-    std::string err;
-    unsigned char* d_blob = nullptr;
-    size_t blob_bytes = 0;
-    std::map<std::string, Blob> entries;
-    GemmLayer layers[kNumLayers];   // by row of kLayers
-    const float* stem_w = nullptr; const float* stem_s = nullptr; const float* stem_b = nullptr;
-    const void* front_ws16 = nullptr;   // "block1_conv1/w16" + "block1_conv2/wp16": the fused front kernel (kernels_front.hip)
-    const void* front_wc16 = nullptr;
-    const float* logits_w = nullptr; const float* logits_b = nullptr;
-    HeadLayer head[2];             // hidden_0, hidden_1: weights split into two halves (kernels_head.hip)
-    unsigned drop_thresh = 0;      // the dropout contract of oracle/philox.py from the rate as a double (bq_set_dropout):
-    float drop_scale = 1.f;        // keep = r >= floor(rate * 2^32), y = x * fp32(1 / (1 - rate))
-    bool loaded = false;
-    int num_cus = 256;
-    float* d_srgb_lut = nullptr;   // tables of the Reinhard normaliser
-    const long long* d_tile0 = nullptr;   // bq_set_tile_index_ptr
-    const long long* d_tile_idx = nullptr;   // bq_set_tile_index_array
-    int inflate_variant = 5;       // bq_set_option("inflate_variant"): 5 = rounds of a literal-only fast phase + a general phase (LDS), 0 = the
-                                   // kernel without LDS, tables in global memory (kernels_inflate.hip; profiles/r05_inflate.txt)
-    float feat_mul = 1.f;          // "act/feat_mul" of the blob: 2^k of the pooled tensor's activation exponent (weights.py: pack_blob)
-    double* d_stage_stats = nullptr;   // 2 x 64-bit integer sums per tile for the staging kernel pair
-    // profiling
-    bool prof = false;
-    std::vector<std::string> prof_names;
-    std::vector<double> prof_flops, prof_bytes;
-    std::vector<int64_t> prof_launches;
-    std::vector<double> prof_ms;
-    std::vector<ProfRec> prof_recs;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-};
-
-namespace {
 
 int fail(bq_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg; else g_create_error = msg;
     return code;
 }
 
-#define HIPCHK(c, expr)                                                                 \
-    do {                                                                                \
-        hipError_t _e = (hipError_t)(expr);                                             \
-        if (_e != hipSuccess)                                                           \
-            return fail((c), BQ_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
+int prof_class(bq_ctx* c, const std::string& name, double flops, double bytes) {
+    int k = -1;
+    for (size_t i = 0; i < c->prof_names.size(); ++i)
+        if (c->prof_names[i] == name) { k = (int)i; break; }
+    if (k < 0) {
+        c->prof_names.push_back(name);
+        c->prof_flops.push_back(0.0);
+        c->prof_bytes.push_back(0.0);
+        c->prof_launches.push_back(0);
+        c->prof_ms.push_back(0.0);
+        k = (int)c->prof_names.size() - 1;
+    }
+    c->prof_flops[k] += flops;
+    c->prof_bytes[k] += bytes;
+    return k;
+}
 
-struct DeviceGuard {
-    int prev = -1; bool ok = false;
-    explicit DeviceGuard(int dev) { ok = hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess; }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
+namespace {
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline bool is16(int dtype) { return dtype == BQ_DTYPE_BF16 || dtype == BQ_DTYPE_F16; }
-inline size_t esize(const bq_ctx* c) { return is16(c->cfg.dtype) ? 2 : 4; }
 
-constexpr long long kStaged = 3LL * 299 * 299;
 constexpr long long kMaxAct = 147LL * 147 * 128;
 constexpr long long kMaxRes = 74LL * 74 * 128;
 
@@ -184,50 +126,6 @@ WsLayout ws_layout(const bq_ctx* c, int n, int mc) {
     L.total = off;
     return L;
 }
-
-// ---- profiling -----------------------------------------------------------------
-// A class sums the algorithmic FLOPs and bytes of its launches: the instances of one class differ (8 of the 25
-// 728 -> 728 layers read a residual, 406 against 270 MB), and bq_profile_read reports the launch-weighted average.
-int prof_class(bq_ctx* c, const std::string& name, double flops, double bytes) {
-    int k = -1;
-    for (size_t i = 0; i < c->prof_names.size(); ++i)
-        if (c->prof_names[i] == name) { k = (int)i; break; }
-    if (k < 0) {
-        c->prof_names.push_back(name);
-        c->prof_flops.push_back(0.0);
-        c->prof_bytes.push_back(0.0);
-        c->prof_launches.push_back(0);
-        c->prof_ms.push_back(0.0);
-        k = (int)c->prof_names.size() - 1;
-    }
-    c->prof_flops[k] += flops;
-    c->prof_bytes[k] += bytes;
-    return k;
-}
-
-struct ProfScope {
-    bq_ctx* c; hipStream_t s; int cls = -1; hipEvent_t a = nullptr, b = nullptr;
-    ProfScope(bq_ctx* c_, hipStream_t s_, const std::string& name, double flops, double bytes)
-        : c(c_), s(s_) {
-        if (!c->prof) return;
-        if (c->ev_used + 2 > c->ev_pool.size()) {
-            for (int i = 0; i < 256; ++i) {
-                hipEvent_t e;
-                if (hipEventCreate(&e) != hipSuccess) return;
-                c->ev_pool.push_back(e);
-            }
-        }
-        cls = prof_class(c, name, flops, bytes);
-        a = c->ev_pool[c->ev_used++];
-        b = c->ev_pool[c->ev_used++];
-        (void)hipEventRecord(a, s);
-    }
-    ~ProfScope() {
-        if (cls < 0) return;
-        (void)hipEventRecord(b, s);
-        c->prof_recs.push_back({cls, a, b});
-    }
-};
 
 // ---- routes: which kernel family runs a layer ------------------------------------------
 int pick_shape(const bq_ctx* c, int prod, int nfp) {
@@ -394,7 +292,6 @@ int tap_nhwc(const Walk& w, const char* name, const void* buf, int H, int C, int
     return 1;
 }
 
-#define RUN(expr) do { int _r = (expr); if (_r != BQ_OK) return _r; } while (0)
 #define TAP_AT(name, buf, H, C, ld) \
     do { int _t = tap_nhwc(w, name, buf, H, C, ld); if (_t) return _t < 0 ? _t : BQ_OK; } while (0)
 // row li's output under `name`: the row's own, or that of the block output it completes
@@ -724,6 +621,25 @@ int register_gemm_layer(bq_ctx* c, int li, int vec, int elt) {
     return BQ_OK;
 }
 
+// Behind a network call's own argument check: the weights are loaded and the workspace holds n tiles x mc passes.  *L: its layout.
+int ready(bq_ctx* c, int n, int mc, size_t ws_bytes, WsLayout* L) {
+    if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
+    *L = ws_layout(c, n, mc);
+    if (ws_bytes < L->total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
+    return BQ_OK;
+}
+
+// bq_debug_activation (d_in: the staged tensor) and bq_debug_activation_u8 (d_tiles), behind their argument checks
+int64_t debug_tap(bq_ctx* c, const char* name, const void* d_in, const uint8_t* d_tiles, int n, void* d_ws, size_t ws_bytes, float* d_out,
+                  size_t out_elems, bq_stream_t stream) {
+    WsLayout L;
+    RUN(ready(c, n, 1, ws_bytes, &L));
+    Tap t; t.want = name; t.out = d_out; t.out_elems = out_elems;
+    unsigned char* ws = (unsigned char*)d_ws;
+    const int r = backbone_impl({c, n, (hipStream_t)stream, &t, nullptr}, d_in, (float*)(ws + L.feat), ws, d_tiles);
+    return r != BQ_OK ? r : t.written;
+}
+
 }  // namespace
 
 // =================================================================== C ABI
@@ -756,44 +672,10 @@ bq_ctx* bq_create(int device_id, const bq_config* cfg) {
     set_dropout(c, (double)cfg->dropout);
     c->device = device_id;
     c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    {   // tables of the Reinhard normaliser (oracle/stain.py states the same arithmetic):
-        // [0,256)   sRGB -> linear, float64 evaluation rounded to float32
-        // [256,511) linear -> 8-bit sRGB as 255 switching points: entry v-1 is the smallest float32 c for which
-        //           clip(trunc(255 * clip(gamma(c), 0, 1)), 0, 255) >= v, gamma(c) = c > 0.0031308 ?
-        //           1.055f * float(pow(double(c), 1/2.4)) - 0.055f : 12.92f * c, found by bisection on the
-        //           float bit pattern over [0, 2] (the function is monotone).  Not over [0, 1]: 1.055f * 1 - 0.055f rounds to the
-        //           float below 1, so c = 1 is level 254 and the last point lies a few ulps ABOVE 1 (oracle/stain.py
-        //           srgb_switch_points states the same search)
-        float lut[512];
-        for (int v = 0; v < 256; ++v) {
-            const double x = (double)v / 255.0;
-            lut[v] = (float)(x > 0.04045 ? std::pow((x + 0.055) / 1.055, 2.4) : x / 12.92);
-        }
-        auto level = [](float cf) {
-            float g;
-            if (cf > 0.0031308f) { const float p = (float)std::pow((double)cf, 1.0 / 2.4); g = 1.055f * p - 0.055f; }
-            else g = cf * 12.92f;
-            g = g < 0.f ? 0.f : (g > 1.f ? 1.f : g);
-            const float t = truncf(g * 255.0f);
-            return (int)(t < 0.f ? 0.f : (t > 255.f ? 255.f : t));
-        };
-        for (int v = 1; v <= 255; ++v) {
-            uint32_t lo = 0, hi = 0x40000000u;               // bit patterns of 0.0f and 2.0f; level(2.0f) = 255
-            while (lo < hi) {
-                const uint32_t mid = lo + (hi - lo) / 2;
-                float f;
-                memcpy(&f, &mid, 4);
-                if (level(f) >= v) hi = mid; else lo = mid + 1;
-            }
-            memcpy(&lut[256 + v - 1], &lo, 4);
-        }
-        lut[511] = 0.f;
-        if (hipMalloc(&c->d_srgb_lut, sizeof lut) != hipSuccess ||
-            hipMemcpy(c->d_srgb_lut, lut, sizeof lut, hipMemcpyHostToDevice) != hipSuccess) {
-            g_create_error = "cannot allocate the sRGB tables";
-            delete c;
-            return nullptr;
-        }
+    if (!reinhard_tables(&c->d_srgb_lut)) {
+        g_create_error = "cannot allocate the sRGB tables";
+        delete c;
+        return nullptr;
     }
     if (hipMalloc(&c->d_stage_stats, (size_t)(cfg->max_batch > 0 ? cfg->max_batch : 1) * 16) != hipSuccess) {
         g_create_error = "cannot allocate the staging statistics";
@@ -907,354 +789,6 @@ int bq_load_weights(bq_ctx* c, const void* host_blob, size_t nbytes) {
     return BQ_OK;
 }
 
-int bq_stage(bq_ctx* c, const uint8_t* d_tiles, int n, void* d_out, bq_stream_t stream) {
-    if (!c || !d_tiles || !d_out || n < 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_stage: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "stage_u8_standardize", 4.0 * n * kStaged, (double)n * kStaged * (1.0 + esize(c)));
-    if (launch_stage_u8(d_tiles, n, 299, d_out, c->cfg.dtype, c->d_stage_stats, s))
-        return fail(c, BQ_ERR_HIP, "stage launch failed");
-    return BQ_OK;
-}
-
-namespace {
-// float32 colour constants of the Reinhard normaliser: XYZ<-RGB, RGB<-XYZ (its float64 inverse rounded),
-// D65 white (oracle/stain.py: constants())
-const float kReinhardConsts[21] = {
-    0.412452996f, 0.357580006f, 0.180423006f, 0.212670997f, 0.715160012f, 0.0721689984f, 0.0193339996f,
-    0.119193003f, 0.950227022f,
-    3.24048138f, -1.53715158f, -0.498536319f, -0.969254971f, 1.87599003f, 0.0415559262f, 0.0556466393f,
-    -0.204041332f, 1.05731106f,
-    0.950469971f, 1.0f, 1.08882999f};
-}  // namespace
-
-int bq_stain_reinhard_fast(bq_ctx* c, const uint8_t* d_tiles, int n, const float* target_means3,
-                           const float* target_stds3, uint8_t* d_out, bq_stream_t stream) {
-    if (!c || !d_tiles || !d_out || !target_means3 || !target_stds3 || n < 0)
-        return fail(c, BQ_ERR_ARG, "bq_stain_reinhard_fast: bad argument");
-    for (int i = 0; i < 3; ++i)
-        if (!std::isfinite(target_stds3[i]) || !std::isfinite(target_means3[i]))      // (a std of 0 or below is defined arithmetic)
-            return fail(c, BQ_ERR_ARG, "bq_stain_reinhard_fast: non-finite target statistics");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "stain_reinhard_fast", 300.0 * n * 299 * 299, 3.0 * n * kStaged);
-    if (launch_reinhard(d_tiles, n, 299, c->d_srgb_lut, kReinhardConsts, target_means3, target_stds3, d_out, nullptr, s))
-        return fail(c, BQ_ERR_HIP, "reinhard launch failed");
-    return BQ_OK;
-}
-
-int bq_stain_lab_stats(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_stats6, bq_stream_t stream) {
-    if (!c || !d_tiles || !d_stats6 || n < 0) return fail(c, BQ_ERR_ARG, "bq_stain_lab_stats: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    if (launch_reinhard(d_tiles, n, 299, c->d_srgb_lut, kReinhardConsts, nullptr, nullptr, nullptr, d_stats6, s))
-        return fail(c, BQ_ERR_HIP, "lab stats launch failed");
-    return BQ_OK;
-}
-
-int bq_stain_macenko(bq_ctx* c, const uint8_t* d_tiles, int n, const float* he_ref6, const float* maxc_ref2,
-                     uint8_t* d_out, int* d_status, bq_stream_t stream) {
-    if (!c || !d_tiles || !d_out || !he_ref6 || !maxc_ref2 || n < 0)
-        return fail(c, BQ_ERR_ARG, "bq_stain_macenko: bad argument");
-    for (int i = 0; i < 6; ++i)
-        if (!std::isfinite(he_ref6[i])) return fail(c, BQ_ERR_ARG, "bq_stain_macenko: non-finite stain matrix");
-    for (int i = 0; i < 2; ++i)
-        if (!std::isfinite(maxc_ref2[i]) || !(maxc_ref2[i] > 0.f))
-            return fail(c, BQ_ERR_ARG, "bq_stain_macenko: target concentrations must be finite and > 0");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "stain_macenko", 400.0 * n * 299 * 299, 3.0 * n * kStaged);
-    if (launch_macenko(d_tiles, n, 299, he_ref6, maxc_ref2, d_out, nullptr, d_status, 1, s))
-        return fail(c, BQ_ERR_HIP, "macenko launch failed");
-    return BQ_OK;
-}
-
-int bq_stain_macenko_stats(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_stats8, int* d_status2, bq_stream_t stream) {
-    if (!c || !d_tiles || !d_stats8 || n < 0) return fail(c, BQ_ERR_ARG, "bq_stain_macenko_stats: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "stain_macenko_stats", 350.0 * n * 299 * 299, 1.0 * n * kStaged);
-    if (launch_macenko(d_tiles, n, 299, nullptr, nullptr, nullptr, d_stats8, d_status2, 2, s))
-        return fail(c, BQ_ERR_HIP, "macenko stats launch failed");
-    return BQ_OK;
-}
-
-size_t bq_range_ws_bytes(int n) { return n < 0 ? 0 : range_ws_bytes(n); }
-
-int bq_range_key(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_key, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
-    if (!c || n < 0 || (n > 0 && (!d_tiles || !d_key || !d_ws))) return fail(c, BQ_ERR_ARG, "bq_range_key: bad argument");
-    if (ws_bytes < range_ws_bytes(n)) return fail(c, BQ_ERR_ARG, "bq_range_key: scratch smaller than bq_range_ws_bytes(n)");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "range_key", 2.0 * n * kStaged, (double)n * kStaged);
-    if (launch_range_key(d_tiles, n, 299, d_ws, d_key, s)) return fail(c, BQ_ERR_HIP, "range key launch failed");
-    return BQ_OK;
-}
-
-int bq_range_screen(bq_ctx* c, const uint8_t* d_tiles, int n, int64_t tile_idx0, const int64_t* d_tile_idx, float* d_cand_key,
-                    int64_t* d_cand_idx, uint8_t* d_cand_tiles, int k, int filled, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
-    if (!c || n < 0 || n > 2048 || (n > 0 && (!d_tiles || !d_cand_key || !d_cand_idx || !d_cand_tiles || !d_ws)))
-        return fail(c, BQ_ERR_ARG, "bq_range_screen: bad argument");
-    if (k < 1 || k > range_max_slots() || filled < 0 || filled > k)
-        return fail(c, BQ_ERR_ARG, "bq_range_screen: need 1 <= k <= " + std::to_string(range_max_slots()) + " and 0 <= filled <= k");
-    if (ws_bytes < range_ws_bytes(n)) return fail(c, BQ_ERR_ARG, "bq_range_screen: scratch smaller than bq_range_ws_bytes(n)");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "range_screen", 2.0 * n * kStaged, (double)n * kStaged);
-    if (launch_range_screen(d_tiles, n, 299, (long long)tile_idx0, reinterpret_cast<const long long*>(d_tile_idx), d_cand_key,
-                            reinterpret_cast<long long*>(d_cand_idx), d_cand_tiles, k, filled, d_ws, s))
-        return fail(c, BQ_ERR_HIP, "range screen launch failed");
-    return BQ_OK;
-}
-
-int bq_png_unfilter(bq_ctx* c, const uint8_t* d_rows, int n, int px, uint8_t* d_out, bq_stream_t stream) {
-    if (!c || !d_rows || !d_out || n < 0 || px <= 0) return fail(c, BQ_ERR_ARG, "bq_png_unfilter: bad argument");
-    if (launch_png_unfilter(d_rows, n, px, d_out, (hipStream_t)stream)) return fail(c, BQ_ERR_HIP, "png unfilter launch failed");
-    return BQ_OK;
-}
-
-size_t bq_png_inflate_scratch_bytes(int n) { return inflate_scratch_bytes(n); }
-
-int bq_png_inflate(bq_ctx* c, const uint8_t* d_z, const uint32_t* d_off, const uint32_t* d_len, int n, int px, uint8_t* d_rows,
-                   size_t rows_stride, void* d_scratch, size_t scratch_bytes, int32_t* d_status, bq_stream_t stream) {
-    if (!c || !d_z || !d_off || !d_len || !d_rows || !d_scratch || !d_status || n < 0 || px <= 0 || px > 4096)
-        return fail(c, BQ_ERR_ARG, "bq_png_inflate: bad argument");
-    const size_t row_bytes = (size_t)px * (3 * (size_t)px + 1);
-    if (rows_stride < row_bytes + 4 || (rows_stride & 3) || rows_stride > 0xffffffffull) return fail(c, BQ_ERR_ARG, "bq_png_inflate: rows_stride must be a multiple of 4, >= px (1 + 3 px) + 4");
-    if (scratch_bytes < inflate_scratch_bytes(n)) return fail(c, BQ_ERR_WORKSPACE, "bq_png_inflate: scratch too small");
-    ProfScope ps(c, (hipStream_t)stream, "png_inflate", 0.0, (double)n * row_bytes * 2.0);
-    const int e = launch_inflate(d_z, d_off, d_len, n, d_rows, (unsigned)row_bytes, (unsigned)rows_stride, d_scratch, d_status, (hipStream_t)stream,
-                                 c->inflate_variant, (unsigned)(1 + 3 * px));
-    if (e) return fail(c, BQ_ERR_HIP, std::string("png inflate launch: ") + hipGetErrorString((hipError_t)e));
-    return BQ_OK;
-}
-
-size_t bq_jpeg_scratch_bytes(int n, int px) { return jpeg_scratch_bytes(n, px); }
-
-int bq_jpeg_decode(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px,
-                   uint8_t* d_out, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
-    if (!c || n < 0 || px <= 0 || px > 4096 || n_tables < 0) return fail(c, BQ_ERR_ARG, "bq_jpeg_decode: bad argument");
-    if (n == 0) return BQ_OK;
-    if (!d_scan || !d_desc || !d_tables || n_tables == 0 || !d_out || !d_status || !d_scratch || ((uintptr_t)d_tables & 3) ||
-        ((uintptr_t)d_scan & 15) || ((uintptr_t)d_desc & 3))
-        return fail(c, BQ_ERR_ARG, "bq_jpeg_decode: bad argument");
-    if (scratch_bytes < jpeg_scratch_bytes(n, px)) return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_decode: scratch too small");
-    ProfScope ps(c, (hipStream_t)stream, "jpeg_decode", 0.0, (double)n * px * px * 3.0);
-    const int e = launch_jpeg_decode(d_scan, d_desc, d_tables, n_tables, n, px, d_out, d_status, d_scratch, scratch_bytes, (hipStream_t)stream);
-    if (e) return fail(c, BQ_ERR_HIP, std::string("jpeg decode launch: ") + hipGetErrorString((hipError_t)e));
-    return BQ_OK;
-}
-
-size_t bq_jpeg_canvas_scratch_bytes(int n, int seg_w, int seg_h) { return jpeg_canvas_scratch_bytes(n, seg_w, seg_h); }
-
-int bq_jpeg_decode_canvas(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int seg_w,
-                          int seg_h, const int32_t* d_place, uint8_t* d_canvas, int H, int W, int clip_x0, int clip_y0, int clip_x1,
-                          int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
-    if (!c || n < 0 || seg_w <= 0 || seg_w > 4096 || seg_h <= 0 || seg_h > 4096 || n_tables < 0 || H <= 0 || W <= 0 || H > (1 << 28) ||
-        W > (1 << 28))
-        return fail(c, BQ_ERR_ARG, "bq_jpeg_decode_canvas: bad argument (need 0 < seg_w, seg_h <= 4096 and 0 < H, W <= 2^28)");
-    if (n == 0) return BQ_OK;
-    if (!d_scan || !d_desc || !d_tables || n_tables == 0 || !d_place || !d_canvas || !d_status || !d_scratch || ((uintptr_t)d_tables & 3) ||
-        ((uintptr_t)d_scan & 15) || ((uintptr_t)d_desc & 3) || ((uintptr_t)d_place & 3))
-        return fail(c, BQ_ERR_ARG, "bq_jpeg_decode_canvas: bad argument");
-    if (scratch_bytes < jpeg_canvas_scratch_bytes(1, seg_w, seg_h))
-        return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_decode_canvas: scratch smaller than one segment's (bq_jpeg_canvas_scratch_bytes(1, seg_w, seg_h))");
-    const int32_t clip[4] = {clip_x0, clip_y0, clip_x1, clip_y1};
-    ProfScope ps(c, (hipStream_t)stream, "jpeg_decode_canvas", 0.0, (double)n * seg_w * seg_h * 3.0);
-    const int e = launch_jpeg_decode_canvas(d_scan, d_desc, d_tables, n_tables, n, seg_w, seg_h, d_place, d_canvas, H, W, clip, d_status,
-                                            d_scratch, scratch_bytes, (hipStream_t)stream);
-    if (e) return fail(c, BQ_ERR_HIP, std::string("jpeg canvas decode launch: ") + hipGetErrorString((hipError_t)e));
-    return BQ_OK;
-}
-
-size_t bq_jpeg_encode_scratch_bytes(int n, int px, int subsampling) { return jpeg_encode_scratch_bytes(n, px, subsampling); }
-
-int bq_jpeg_encode(bq_ctx* c, const uint8_t* d_tiles, int n, int px, int quality, int subsampling, uint8_t* d_out, int64_t cap,
-                   int64_t* d_off, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
-    if (!c || n < 0 || cap < 0) return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: bad argument");
-    if (px < 1 || px > 4096 || quality < 1 || quality > 100 || (subsampling != 0 && subsampling != 2))
-        return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: outside the encoder's subset (need 1 <= px <= 4096, 1 <= quality <= 100, subsampling 0 = 4:4:4 or 2 = 4:2:0)");
-    if (n == 0) return BQ_OK;
-    if (!d_tiles || !d_off || !d_status || !d_scratch || (!d_out && cap) || ((uintptr_t)d_off & 7) || ((uintptr_t)d_status & 3) ||
-        ((uintptr_t)d_scratch & 15))
-        return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: bad argument (null pointer, d_off not 8-byte or d_scratch not 16-byte aligned)");
-    const int m = jpeg_encode_round_tiles(px, subsampling, scratch_bytes);
-    if (m < 1) return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_encode: scratch smaller than one tile's (bq_jpeg_encode_scratch_bytes(1, px, subsampling))");
-    hipStream_t s = (hipStream_t)stream;
-    static const char* const kStage[JPEG_ENC_STAGES] = {"jpeg_encode_pixel", "jpeg_encode_size", "jpeg_encode_pack", "jpeg_encode_stuff"};
-    const double blocks = (double)jpeg_encode_scratch_bytes(1, px, subsampling) / 344.0;       // (for the profile's byte column only: about the blocks of a tile)
-    for (long long t0 = 0; t0 < n; t0 += m) {
-        const int cnt = (int)(n - t0 < m ? n - t0 : m);
-        for (int stage = 0; stage < JPEG_ENC_STAGES; ++stage) {
-            ProfScope ps(c, s, kStage[stage], 0.0, stage == JPEG_ENC_PIXEL ? (double)cnt * px * px * 3.0 : (double)cnt * blocks * 128.0);
-            const int e = launch_jpeg_encode_stage(stage, d_tiles, t0, cnt, m, px, quality, subsampling, d_scratch, d_out, (long long)cap,
-                                                   (long long*)d_off, d_status, s);
-            if (e) return fail(c, BQ_ERR_HIP, std::string("jpeg encode launch: ") + hipGetErrorString((hipError_t)e));
-        }
-    }
-    return BQ_OK;
-}
-
-int bq_tile_resample(bq_ctx* c, const uint8_t* d_canvas, int H, int W, const int32_t* d_origin, int n, int src_px, int px,
-                     const int32_t* d_bounds, const int32_t* d_coef, int ksize, uint8_t* d_out, bq_stream_t stream) {
-    if (!c || n < 0 || n > (1 << 20) || px <= 0 || px > 4096 || src_px <= 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28) ||
-        (int64_t)src_px > 8ll * px || (int64_t)px > 8ll * src_px)
-        return fail(c, BQ_ERR_ARG, "bq_tile_resample: bad argument (need 0 < px <= 4096, px / 8 <= src_px <= 8 px, 0 <= n <= 2^20, H, W <= 2^28)");
-    if (n == 0) return BQ_OK;
-    if (!d_canvas || !d_origin || !d_out || ((uintptr_t)d_origin & 3)) return fail(c, BQ_ERR_ARG, "bq_tile_resample: bad argument");
-    if (src_px != px) {
-        if (!d_bounds || !d_coef || ((uintptr_t)d_bounds & 3) || ((uintptr_t)d_coef & 3) || ksize != resample_ksize(src_px, px))
-            return fail(c, BQ_ERR_ARG, "bq_tile_resample: the tap tables are not bqio_resample_taps(src_px, px)'s");
-        int rows = 0;
-        if (!resample_strip_rows(src_px, px, ksize, &rows))
-            return fail(c, BQ_ERR_ARG, "bq_tile_resample: the taps of one output row do not fit the kernel's LDS at this px and ratio");
-    }
-    if (resample_grid(n, src_px, px, ksize) > 0x7fffffffll)
-        return fail(c, BQ_ERR_ARG, "bq_tile_resample: n x strips of output rows exceeds 2^31 - 1 workgroups; split the call");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "tile_resample", 2.0 * 2 * 3 * (double)n * px * px * (src_px == px ? 0 : ksize),
-                 (double)n * 3 * ((double)src_px * src_px + (double)px * px));
-    if (launch_tile_resample(d_canvas, H, W, d_origin, n, src_px, px, d_bounds, d_coef, ksize, d_out, s))
-        return fail(c, BQ_ERR_HIP, "tile resample launch failed");
-    return BQ_OK;
-}
-
-int bq_tile_grayspace(bq_ctx* c, const uint8_t* d_tiles, int n, int px, const int32_t* d_limit256, int32_t* d_count, bq_stream_t stream) {
-    if (!c || n < 0 || px <= 0 || px > 4096) return fail(c, BQ_ERR_ARG, "bq_tile_grayspace: bad argument");
-    if (n == 0) return BQ_OK;
-    if (!d_tiles || !d_limit256 || !d_count || ((uintptr_t)d_limit256 & 3) || ((uintptr_t)d_count & 3))
-        return fail(c, BQ_ERR_ARG, "bq_tile_grayspace: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "tile_grayspace", 6.0 * n * px * px, 3.0 * n * px * px);
-    if (launch_tile_grayspace(d_tiles, n, px, d_limit256, d_count, s)) return fail(c, BQ_ERR_HIP, "grayspace launch failed");
-    return BQ_OK;
-}
-
-int bq_heatmap_render(bq_ctx* c, const float* d_values, int gh, int gw, const int32_t* d_col, const int32_t* d_row, int interpolation,
-                      const uint8_t* d_lut, const uint8_t* d_thumb, uint8_t* d_out, int H, int W, float vmin, float inv_span, int A,
-                      bq_stream_t stream) {
-    if (!c || gh <= 0 || gw <= 0 || gh > (1 << 15) || gw > (1 << 15) || H <= 0 || W <= 0 || H > 16384 || W > 16384)
-        return fail(c, BQ_ERR_ARG, "bq_heatmap_render: bad argument (need 0 < gh, gw <= 32768 and 0 < H, W <= 16384)");
-    if (interpolation != 0 && interpolation != 1) return fail(c, BQ_ERR_ARG, "bq_heatmap_render: interpolation must be 0 (none) or 1 (bicubic)");
-    if (!(A >= 0 && A <= 256) || !std::isfinite(vmin) || !std::isnormal(inv_span) || !(inv_span > 0.0f))
-        return fail(c, BQ_ERR_ARG, "bq_heatmap_render: bad argument (need 0 <= A <= 256, vmin finite, inv_span a normal positive float)");
-    if (!d_values || !d_col || !d_row || !d_lut || !d_thumb || !d_out || ((uintptr_t)d_values & 3) || ((uintptr_t)d_col & 3) ||
-        ((uintptr_t)d_row & 3))
-        return fail(c, BQ_ERR_ARG, "bq_heatmap_render: bad argument");
-    const size_t bytes = (size_t)3 * H * W;
-    if (d_out != d_thumb && d_out < d_thumb + bytes && d_thumb < d_out + bytes)
-        return fail(c, BQ_ERR_ARG, "bq_heatmap_render: out must be the thumbnail itself or not overlap it");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "heatmap_render", 0.0, 2.0 * (double)bytes);
-    if (launch_heatmap_render(d_values, gh, gw, d_col, d_row, interpolation, d_lut, d_thumb, d_out, H, W, vmin, inv_span, A, s))
-        return fail(c, BQ_ERR_HIP, "heatmap render launch failed");
-    return BQ_OK;
-}
-
-int bq_tissue_blur(bq_ctx* c, const uint8_t* d_thumb, int H, int W, const int32_t* d_sdiv256, uint8_t* d_plane, int32_t* d_hist,
-                   bq_stream_t stream) {
-    if (!c || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31))
-        return fail(c, BQ_ERR_ARG, "bq_tissue_blur: bad argument (need 0 < H, W and H * W < 2^31)");
-    if (!d_thumb || !d_sdiv256 || !d_plane || !d_hist || ((uintptr_t)d_sdiv256 & 3) || ((uintptr_t)d_hist & 3))
-        return fail(c, BQ_ERR_ARG, "bq_tissue_blur: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "tissue_blur", 0.0, 4.0 * (double)H * W);
-    if (launch_tissue_blur(d_thumb, H, W, d_sdiv256, d_plane, d_hist, s)) return fail(c, BQ_ERR_HIP, "tissue blur launch failed");
-    return BQ_OK;
-}
-
-// The cells' ranges of a W x H plane, [a, b) pairs: 0 <= a < b <= W for a column, <= H for a row.  -> the refusal's text, or empty.
-static std::string bad_cell_range(const char* plane, const int32_t* col_ranges, int gw, int W, const int32_t* row_ranges, int gh, int H) {
-    for (int i = 0; i < gw; ++i)
-        if (col_ranges[2 * i] < 0 || col_ranges[2 * i] >= col_ranges[2 * i + 1] || col_ranges[2 * i + 1] > W)
-            return std::string("a column range is empty or outside the ") + plane;
-    for (int i = 0; i < gh; ++i)
-        if (row_ranges[2 * i] < 0 || row_ranges[2 * i] >= row_ranges[2 * i + 1] || row_ranges[2 * i + 1] > H)
-            return std::string("a row range is empty or outside the ") + plane;
-    return std::string();
-}
-
-int bq_tissue_cells(bq_ctx* c, const uint8_t* d_plane, int H, int W, int T, const int32_t* col_ranges, int gw, const int32_t* row_ranges,
-                    int gh, int32_t* d_ranges, int32_t* d_count, bq_stream_t stream) {
-    if (!c || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31) || gw <= 0 || gh <= 0 || gw > (1 << 15) || gh > (1 << 15) || T < 0 || T > 255)
-        return fail(c, BQ_ERR_ARG, "bq_tissue_cells: bad argument (need 0 < H, W, H * W < 2^31, 0 < gw, gh <= 32768 and 0 <= T <= 255)");
-    if (!d_plane || !col_ranges || !row_ranges || !d_ranges || !d_count || ((uintptr_t)d_ranges & 3) || ((uintptr_t)d_count & 3))
-        return fail(c, BQ_ERR_ARG, "bq_tissue_cells: bad argument");
-    const std::string bad = bad_cell_range("plane", col_ranges, gw, W, row_ranges, gh, H);
-    if (!bad.empty()) return fail(c, BQ_ERR_ARG, "bq_tissue_cells: " + bad);
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "tissue_cells", 0.0, (double)H * W);
-    HIPCHK(c, hipMemcpyAsync(d_ranges, col_ranges, (size_t)gw * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_ranges + 2 * gw, row_ranges, (size_t)gh * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (launch_tissue_cells(d_plane, H, W, T, d_ranges, d_ranges + 2 * gw, gw, gh, d_count, s))
-        return fail(c, BQ_ERR_HIP, "tissue cells launch failed");
-    return BQ_OK;
-}
-
-int bq_tissue_focus(bq_ctx* c, const uint8_t* d_thumb, int H, int W, const int32_t* d_taps, int r, int thr, int32_t* d_work,
-                    int32_t* d_value_or_null, uint8_t* d_plane, int32_t* d_count, bq_stream_t stream) {
-    if (!c || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31) || r < 1 || r > 16 || thr < 0)
-        return fail(c, BQ_ERR_ARG, "bq_tissue_focus: bad argument (need 0 < H, W, H * W < 2^31, 1 <= r <= 16 and 0 <= thr)");
-    if (!d_thumb || !d_taps || !d_work || !d_plane || !d_count || ((uintptr_t)d_taps & 3) || ((uintptr_t)d_work & 3) ||
-        ((uintptr_t)d_value_or_null & 3) || ((uintptr_t)d_count & 3))
-        return fail(c, BQ_ERR_ARG, "bq_tissue_focus: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "tissue_focus", 2.0 * 2 * (2.0 * r + 1) * (double)H * W, (d_value_or_null ? 16.0 : 12.0) * (double)H * W);
-    if (launch_tissue_focus(d_thumb, H, W, d_taps, r, thr, d_work, d_value_or_null, d_plane, d_count, s))
-        return fail(c, BQ_ERR_HIP, "tissue focus launch failed");
-    return BQ_OK;
-}
-
-int bq_tissue_cells_union(bq_ctx* c, const uint8_t* d_otsu_plane, int Ho, int Wo, int T, const uint8_t* d_focus_plane, int Hf, int Wf,
-                          const int32_t* xmap, const int32_t* ymap, const int32_t* col_ranges, int gw, const int32_t* row_ranges, int gh,
-                          int32_t* d_tables, int32_t* d_count, bq_stream_t stream) {
-    if (!c || Ho <= 0 || Wo <= 0 || (int64_t)Ho * Wo >= (1ll << 31) || Hf <= 0 || Wf <= 0 || (int64_t)Hf * Wf >= (1ll << 31) || gw <= 0 ||
-        gh <= 0 || gw > (1 << 15) || gh > (1 << 15) || T < 0 || T > 255)
-        return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: bad argument (need 0 < H, W and H * W < 2^31 for both planes, 0 < gw, gh <= "
-                                   "32768 and 0 <= T <= 255)");
-    if (!d_otsu_plane || !d_focus_plane || !xmap || !ymap || !col_ranges || !row_ranges || !d_tables || !d_count ||
-        ((uintptr_t)d_tables & 3) || ((uintptr_t)d_count & 3))
-        return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: bad argument");
-    const std::string bad = bad_cell_range("Otsu plane", col_ranges, gw, Wo, row_ranges, gh, Ho);
-    if (!bad.empty()) return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: " + bad);
-    for (int i = 0; i < Wo; ++i)
-        if (xmap[i] < 0 || xmap[i] >= Wf || (i && xmap[i] < xmap[i - 1]))
-            return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: the column map leaves the focus plane or decreases");
-    for (int i = 0; i < Ho; ++i)
-        if (ymap[i] < 0 || ymap[i] >= Hf || (i && ymap[i] < ymap[i - 1]))
-            return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: the row map leaves the focus plane or decreases");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "tissue_cells_union", 0.0, 2.0 * (double)Ho * Wo);
-    int32_t* d_xmap = d_tables;
-    int32_t* d_ymap = d_xmap + Wo;
-    int32_t* d_col = d_ymap + Ho;
-    int32_t* d_row = d_col + 2 * gw;
-    HIPCHK(c, hipMemcpyAsync(d_xmap, xmap, (size_t)Wo * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_ymap, ymap, (size_t)Ho * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_col, col_ranges, (size_t)gw * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_row, row_ranges, (size_t)gh * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (launch_tissue_cells_union(d_otsu_plane, Ho, Wo, T, d_focus_plane, Hf, Wf, d_xmap, d_ymap, d_col, d_row, gw, gh, d_count, s))
-        return fail(c, BQ_ERR_HIP, "tissue cells union launch failed");
-    return BQ_OK;
-}
-
-int bq_roi_plane(bq_ctx* c, const int32_t* edges, int E, const int32_t* starts, int P, const int32_t* xs, int W, const int32_t* ys, int H,
-                 int32_t* d_tables, uint8_t* d_plane, bq_stream_t stream) {
-    if (!c || !d_tables || !d_plane || ((uintptr_t)d_tables & 15)) return fail(c, BQ_ERR_ARG, "bq_roi_plane: bad argument");
-    if (const char* why = bqroi::check_tables(edges, E, starts, P, xs, W, ys, H)) return fail(c, BQ_ERR_ARG, std::string("bq_roi_plane: ") + why);
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "roi_plane", 0.0, (double)H * W);
-    int32_t* d_edges = d_tables;                                             // (first: the kernel loads an edge as 16 bytes)
-    int32_t* d_starts = d_edges + (size_t)4 * E;
-    int32_t* d_xs = d_starts + P + 1;
-    int32_t* d_ys = d_xs + W;
-    HIPCHK(c, hipMemcpyAsync(d_edges, edges, (size_t)4 * E * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_starts, starts, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_xs, xs, (size_t)W * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_ys, ys, (size_t)H * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (launch_roi_plane(d_edges, E, d_starts, P, d_xs, d_ys, H, W, d_plane, s)) return fail(c, BQ_ERR_HIP, "roi plane launch failed");
-    return BQ_OK;
-}
-
-int bq_png_unfilter_strided(bq_ctx* c, const uint8_t* d_rows, size_t rows_stride, int n, int px, uint8_t* d_out, bq_stream_t stream) {
-    if (!c || !d_rows || !d_out || n < 0 || px <= 0) return fail(c, BQ_ERR_ARG, "bq_png_unfilter_strided: bad argument");
-    if (launch_png_unfilter(d_rows, n, px, d_out, (hipStream_t)stream, rows_stride)) return fail(c, BQ_ERR_HIP, "png unfilter launch failed");
-    return BQ_OK;
-}
-
 int bq_stream_create_masked(bq_ctx* c, const uint32_t* cu_mask, int mask_words, bq_stream_t* out) {
     if (!c || !cu_mask || mask_words <= 0 || !out) return fail(c, BQ_ERR_ARG, "bq_stream_create_masked: bad argument");
     hipStream_t s = nullptr;
@@ -1288,19 +822,11 @@ int bq_stream_destroy(bq_ctx* c, bq_stream_t stream) {
     return BQ_OK;
 }
 
-int bq_stage_f32(bq_ctx* c, const float* d_tiles, int n, void* d_out, bq_stream_t stream) {
-    if (!c || !d_tiles || !d_out || n < 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_stage_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "stage_f32_to_planar", 0.0, (double)n * kStaged * (4.0 + esize(c)));
-    if (launch_stage_f32(d_tiles, n, 299, d_out, c->cfg.dtype, s)) return fail(c, BQ_ERR_HIP, "stage launch failed");
-    return BQ_OK;
-}
-
 int bq_backbone(bq_ctx* c, const void* d_in, int n, float* d_feat, void* d_ws, size_t ws_bytes,
                 bq_stream_t stream) {
     if (!c || !d_in || !d_feat || !d_ws || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_backbone: bad argument");
-    if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
-    if (ws_bytes < ws_layout(c, n, 1).total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
+    WsLayout L;
+    RUN(ready(c, n, 1, ws_bytes, &L));
     return backbone_impl({c, n, (hipStream_t)stream, nullptr, nullptr}, d_in, d_feat, (unsigned char*)d_ws);
 }
 
@@ -1310,8 +836,8 @@ int bq_mc_head(bq_ctx* c, const float* d_feat, int n, int64_t tile_idx0, int mc_
     if (!c || !d_feat || !d_state || !d_ws || n <= 0 || mc_n <= 0 || n > c->cfg.max_batch ||
         mc_n > c->cfg.max_mc || pass0 < 0 || (finalize && (!d_mean2 || !d_std2)))
         return fail(c, BQ_ERR_ARG, "bq_mc_head: bad argument");
-    if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
-    if (ws_bytes < ws_layout(c, n, mc_n).total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
+    WsLayout L;
+    RUN(ready(c, n, mc_n, ws_bytes, &L));
     return head_impl(c, d_feat, n, tile_idx0, mc_n, pass0, seed, init, finalize, d_state, d_mean2, d_std2,
                      (unsigned char*)d_ws, (hipStream_t)stream);
 }
@@ -1346,9 +872,8 @@ int bq_mc_infer(bq_ctx* c, const uint8_t* d_tiles, int n, int64_t tile_idx0, int
     if (!c || !d_tiles || !d_mean2 || !d_std2 || !d_ws || n <= 0 || mc_n <= 0 || n > c->cfg.max_batch ||
         mc_n > c->cfg.max_mc || (mc_mode != BQ_MC_HEAD && mc_mode != BQ_MC_FULL))
         return fail(c, BQ_ERR_ARG, "bq_mc_infer: bad argument");
-    if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
-    const WsLayout L = ws_layout(c, n, mc_n);
-    if (ws_bytes < L.total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
+    WsLayout L;
+    RUN(ready(c, n, mc_n, ws_bytes, &L));
     unsigned char* ws = (unsigned char*)d_ws;
     hipStream_t s = (hipStream_t)stream;
     float* feat = (float*)(ws + L.feat);
@@ -1367,47 +892,9 @@ int bq_mc_infer(bq_ctx* c, const uint8_t* d_tiles, int n, int64_t tile_idx0, int
 
 int bq_backbone_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_feat, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
     if (!c || !d_tiles || !d_feat || !d_ws || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_backbone_u8: bad argument");
-    if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
-    const WsLayout L = ws_layout(c, n, 1);
-    if (ws_bytes < L.total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
+    WsLayout L;
+    RUN(ready(c, n, 1, ws_bytes, &L));
     return features_from_u8(c, d_tiles, n, d_feat, (unsigned char*)d_ws, L, stream);
-}
-
-int bq_slide_reduce(bq_ctx* c, const float* d_mean2, const float* d_std2, const int32_t* d_slide_idx, int n,
-                    int n_slides, float tile_uq, int64_t* d_acc_pred, int64_t* d_acc_unc, int32_t* d_count,
-                    bq_stream_t stream) {
-    if (!c || !d_mean2 || !d_std2 || !d_slide_idx || !d_acc_pred || !d_acc_unc || !d_count || n < 0 || n_slides <= 0)
-        return fail(c, BQ_ERR_ARG, "bq_slide_reduce: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "slide_reduce", 2.0 * n, 20.0 * n);
-    if (launch_slide_reduce(d_mean2, d_std2, d_slide_idx, n, n_slides, tile_uq, (long long*)d_acc_pred,
-                            (long long*)d_acc_unc, d_count, s))
-        return fail(c, BQ_ERR_HIP, "slide_reduce launch failed");
-    return BQ_OK;
-}
-
-int bq_slide_finish(bq_ctx* c, const int64_t* d_acc_pred, const int64_t* d_acc_unc, const int32_t* d_count,
-                    int n_slides, double* d_mean_pred, double* d_mean_unc, bq_stream_t stream) {
-    if (!c || !d_acc_pred || !d_acc_unc || !d_count || !d_mean_pred || !d_mean_unc || n_slides <= 0)
-        return fail(c, BQ_ERR_ARG, "bq_slide_finish: bad argument");
-    if (launch_slide_finish((const long long*)d_acc_pred, (const long long*)d_acc_unc, d_count, n_slides,
-                            d_mean_pred, d_mean_unc, (hipStream_t)stream))
-        return fail(c, BQ_ERR_HIP, "slide_finish launch failed");
-    return BQ_OK;
-}
-
-size_t bq_roc_workspace_bytes(int64_t n) { return roc_workspace_bytes((long long)n); }
-
-int bq_roc_youden(bq_ctx* c, const double* d_score, const uint8_t* d_label, int64_t n, void* d_ws, size_t ws_bytes,
-                  double* d_out6, bq_stream_t stream) {
-    if (!c || !d_score || !d_label || !d_ws || !d_out6 || n <= 0 || n > 0x7fffffffLL)
-        return fail(c, BQ_ERR_ARG, "bq_roc_youden: bad argument");
-    if (ws_bytes < roc_workspace_bytes(n)) return fail(c, BQ_ERR_ARG, "bq_roc_youden: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps(c, s, "roc_youden", 4.0 * n, 60.0 * n);
-    const int e = launch_roc_youden(d_score, d_label, (long long)n, (unsigned char*)d_ws, ws_bytes, d_out6, s);
-    if (e) return fail(c, BQ_ERR_HIP, std::string("roc_youden: ") + hipGetErrorString((hipError_t)e));
-    return BQ_OK;
 }
 
 int bq_profile_enable(bq_ctx* c, int on) {
@@ -1448,27 +935,13 @@ int bq_profile_read(bq_ctx* c, bq_prof_entry* out, int max_entries) {
 int64_t bq_debug_activation(bq_ctx* c, const char* name, const void* d_in, int n, void* d_ws, size_t ws_bytes,
                             float* d_out, size_t out_elems, bq_stream_t stream) {
     if (!c || !name || !d_in || !d_ws || !d_out || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_debug_activation: bad argument");
-    if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
-    const WsLayout L = ws_layout(c, n, 1);
-    if (ws_bytes < L.total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
-    Tap t; t.want = name; t.out = d_out; t.out_elems = out_elems;
-    unsigned char* ws = (unsigned char*)d_ws;
-    const int r = backbone_impl({c, n, (hipStream_t)stream, &t, nullptr}, d_in, (float*)(ws + L.feat), ws);
-    if (r != BQ_OK) return r;
-    return t.written;
+    return debug_tap(c, name, d_in, nullptr, n, d_ws, ws_bytes, d_out, out_elems, stream);
 }
 
 int64_t bq_debug_activation_u8(bq_ctx* c, const char* name, const uint8_t* d_tiles, int n, void* d_ws, size_t ws_bytes,
                                float* d_out, size_t out_elems, bq_stream_t stream) {
     if (!c || !name || !d_tiles || !d_ws || !d_out || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_debug_activation_u8: bad argument");
-    if (!c->loaded) return fail(c, BQ_ERR_WEIGHTS, "weights not loaded");
-    const WsLayout L = ws_layout(c, n, 1);
-    if (ws_bytes < L.total) return fail(c, BQ_ERR_WORKSPACE, "workspace too small");
-    Tap t; t.want = name; t.out = d_out; t.out_elems = out_elems;
-    unsigned char* ws = (unsigned char*)d_ws;
-    const int r = backbone_impl({c, n, (hipStream_t)stream, &t, nullptr}, nullptr, (float*)(ws + L.feat), ws, d_tiles);
-    if (r != BQ_OK) return r;
-    return t.written;
+    return debug_tap(c, name, nullptr, d_tiles, n, d_ws, ws_bytes, d_out, out_elems, stream);
 }
 
 // The routes of one walk as text, one "<layer or block output> <route>" line per step, through the walker and choose_route of

@@ -99,75 +99,10 @@ int launch_tile_conv(int dtype, const void* in, const void* wp, const float* sca
                      int W, int Hi, int Wi, int relu, int num_cus, hipStream_t s);
 
 // ---- small kernels (kernels_misc.hip) ----------------------------------------------
-int launch_stage_u8(const uint8_t* tiles, int n, int px, void* out, int dtype, double* stats_scratch,
-                    hipStream_t s);
-int launch_reinhard(const uint8_t* tiles, int n, int px, const float* d_lut, const float* consts27,
-                    const float* tgt_mean, const float* tgt_std, uint8_t* dst, float* d_stats, hipStream_t s);
 int launch_stage_stats(const uint8_t* tiles, int n, int px, double* stats_scratch, hipStream_t s);
-// kernels_stain.hip: Macenko stain normalisation, one workgroup per tile (dst may be null: statistics only, or == tiles)
-int launch_macenko(const uint8_t* tiles, int n, int px, const float* he_ref6, const float* maxc_ref2, uint8_t* dst,
-                   float* d_stats8, int* d_status, int status_stride, hipStream_t s);
-// kernels_screen.hip: the f16 range screen's key (bq_range_key) and its top-k candidate slots (bq_range_screen)
-size_t range_ws_bytes(int n);
-int range_max_slots();
-size_t range_select_lds(int filled, int n);
-int launch_range_key(const uint8_t* tiles, int n, int px, void* ws, float* key, hipStream_t s);
-int launch_range_screen(const uint8_t* tiles, int n, int px, long long tile_idx0, const long long* tile_idx, float* cand_key,
-                        long long* cand_idx, uint8_t* cand_tiles, int k, int filled, void* ws, hipStream_t s);
 int launch_front(int dtype, const uint8_t* tiles, const unsigned long long* stats, const void* ws16, const float* s_scale,
                  const float* s_bias, const void* wc16, const float* c_scale, const float* c_bias, void* out, int n, int num_cus,
                  hipStream_t s);
-int launch_stage_f32(const float* tiles, int n, int px, void* out, int dtype, hipStream_t s);
-// kernels_png.hip: PNG scanline un-filtering (rows: [n][px][1 + 3 px] filter byte + filtered RGB bytes -> out uint8 NHWC)
-int launch_png_unfilter(const unsigned char* rows, int n, int px, unsigned char* out, hipStream_t s, size_t in_stride = 0);
-// kernels_inflate.hip: n zlib streams (packed, 16-byte aligned starts) -> n x out_len bytes, Adler-32 verified; status 0 = ok
-size_t inflate_scratch_bytes(int n);
-int launch_inflate(const unsigned char* d_z, const unsigned* d_off, const unsigned* d_len, int n, unsigned char* d_out, unsigned out_len,
-                   unsigned out_stride, void* d_scratch, int* d_status, hipStream_t s, int variant = 0, unsigned row_len = 0);
-// (row_len != 0: the outputs are PNG scanlines of that length; a filter-type byte above 4 is flagged too)
-// kernels_jpeg.hip: n baseline-JPEG tiles as bqio_extract_jpeg packs them -> uint8 NHWC, status 0 = decoded (jpeg_device.h)
-size_t jpeg_scratch_bytes(int n, int px);
-int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px, uint8_t* d_out,
-                       int* d_status, void* d_scratch, size_t scratch_bytes, hipStream_t s);
-// the same for a TIFF page's own w x h segments, written into their places in a canvas uint8 [H][W][3] (clip: host memory)
-size_t jpeg_canvas_scratch_bytes(int n, int w, int h);
-int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int w, int h,
-                              const int32_t* d_place, uint8_t* d_canvas, int H, int W, const int32_t* clip, int* d_status, void* d_scratch,
-                              size_t scratch_bytes, hipStream_t s);
-// kernels_jpeg_encode.hip: n uint8 tiles -> the baseline-JPEG files Pillow writes, back to back (jpeg_encode_device.h), one stage of
-// one round per call so that the entry can time each (bq_jpeg_encode)
-enum { JPEG_ENC_PIXEL = 0, JPEG_ENC_SIZE = 1, JPEG_ENC_PACK = 2, JPEG_ENC_STUFF = 3, JPEG_ENC_STAGES = 4 };
-size_t jpeg_encode_scratch_bytes(int n, int px, int sub);
-int jpeg_encode_round_tiles(int px, int sub, size_t scratch_bytes);         // 0: less than one tile's scratch
-int launch_jpeg_encode_stage(int stage, const uint8_t* d_tiles, long long t0, int cnt, int m, int px, int quality, int sub, void* d_scratch,
-                             uint8_t* d_out, long long cap, long long* d_off, int* d_status, hipStream_t s);
-
-// kernels_resample.hip: the heatmap's tile grid cut from a canvas and resampled as Pillow's LANCZOS does (resample_device.h),
-// and the background filter's grey-pixel count
-int resample_ksize(int src_px, int px);
-int resample_strip_rows(int src_px, int px, int ksize, int* max_rows);      // 0: the ratio's taps do not fit the kernel's LDS
-long long resample_grid(int n, int src_px, int px, int ksize);
-int launch_tile_resample(const uint8_t* canvas, int H, int W, const int* origin, int n, int src_px, int px, const int* bounds,
-                         const int* coef, int ksize, uint8_t* out, hipStream_t s);
-int launch_tile_grayspace(const uint8_t* tiles, int n, int px, const int* limit256, int* count, hipStream_t s);
-// kernels_render.hip: one plane of the heatmap grid drawn over the slide's thumbnail through a colour table (DESIGN.md "Heatmap output")
-int launch_heatmap_render(const float* values, int gh, int gw, const int32_t* col, const int32_t* row, int bicubic, const uint8_t* lut,
-                          const uint8_t* thumb, uint8_t* out, int H, int W, float vmin, float inv, int A, hipStream_t s);
-// kernels_tissue.hip: the tissue mask on the slide's thumbnail (DESIGN.md "Heatmap input", Tissue mask): the 7 x 7 median of the
-// 8-bit saturation with its histogram, and the background pixels of every grid cell
-int launch_tissue_blur(const uint8_t* thumb, int H, int W, const int* sdiv256, uint8_t* plane, int* hist, hipStream_t s);
-int launch_tissue_cells(const uint8_t* plane, int H, int W, int T, const int* col, const int* row, int gw, int gh, int* count,
-                        hipStream_t s);
-// kernels_focus.hip: the focus mask on a 4 um / pixel thumbnail (DESIGN.md "Heatmap input", Focus mask): gray, |Laplacian| and a
-// separable Gaussian in integers with one threshold, and every grid cell's pixels that are background or out of focus
-int launch_tissue_focus(const uint8_t* thumb, int H, int W, const int* taps, int r, int thr, int* work, int* value, uint8_t* plane,
-                        int* count, hipStream_t s);
-int launch_tissue_cells_union(const uint8_t* otsu, int Ho, int Wo, int T, const uint8_t* focus, int Hf, int Wf, const int* xmap,
-                              const int* ymap, const int* col, const int* row, int gw, int gh, int* count, hipStream_t s);
-// kernels_roi.hip: the region-of-interest mask (DESIGN.md "Heatmap input", Region-of-interest mask): polygons -> the plane of the
-// sample points inside any of them (roi_device.h's crossing rule); every table is device memory here, `edges` 16-byte aligned
-int launch_roi_plane(const int* edges, int E, const int* starts, int P, const int* xs, const int* ys, int H, int W, uint8_t* plane,
-                     hipStream_t s);
 int launch_stem1(const void* in_nchw, int n, const float* w27x32, const float* scale,
                  const float* bias, void* out_nhwc, int dtype, hipStream_t s);
 int launch_pool_add(const void* y, const void* res, void* out, int n, int Hi, int Wi, int C,
@@ -181,14 +116,6 @@ int launch_head_final(const float* h1, int n, int mc_n, int pass0, long long til
                       unsigned seed_lo, unsigned seed_hi, unsigned thresh, float dscale,
                       const float* w2, const float* b2, int init, int finalize, float* state,
                       float* mean2, float* std2, hipStream_t s);
-int launch_slide_reduce(const float* mean2, const float* std2, const int32_t* slide_idx, int n,
-                        int n_slides, float tile_uq, long long* acc_pred, long long* acc_unc,
-                        int32_t* count, hipStream_t s);
-size_t roc_workspace_bytes(long long n);
-int launch_roc_youden(const double* score, const unsigned char* label, long long n, unsigned char* ws, size_t ws_bytes,
-                      double* out, hipStream_t s);
-int launch_slide_finish(const long long* acc_pred, const long long* acc_unc, const int32_t* count,
-                        int n_slides, double* mean_pred, double* mean_unc, hipStream_t s);
 int launch_to_f32_nhwc(const void* x, long long rows, int C, int ld, float* out, int dtype,
                        hipStream_t s);
 int launch_nchw_to_f32_nhwc(const void* x, int n, int C, int HW, float* out, int dtype,

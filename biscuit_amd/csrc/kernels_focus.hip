@@ -23,7 +23,7 @@
 // bad iff otsu <= T or focus[ymap[y]][xmap[x]] == 0, the focus plane [Hf][Wf] resized onto the Otsu plane by the two host tables
 // (nearest neighbour).  Ranges and maps are checked on the host before they are uploaded (bq_tissue_cells_union); the kernel
 // clamps them all the same.
-#include "bq_common.h"
+#include "bq_ctx.h"
 
 namespace {
 
@@ -147,8 +147,8 @@ __global__ void __launch_bounds__(FC_NT) focus_union_kernel(const uint8_t* __res
 
 }  // namespace
 
-int launch_tissue_focus(const uint8_t* thumb, int H, int W, const int* taps, int r, int thr, int* work, int* value, uint8_t* plane,
-                        int* count, hipStream_t s) {
+static int launch_tissue_focus(const uint8_t* thumb, int H, int W, const int* taps, int r, int thr, int* work, int* value, uint8_t* plane,
+                               int* count, hipStream_t s) {
     if (r < 1 || r > FC_MAXR) return (int)hipErrorInvalidValue;
     if (const hipError_t e = hipMemsetAsync(count, 0, sizeof(int), s)) return (int)e;
     const int rx = (W + FC_TW - 1) / FC_TW, cx = (W + FC_CW - 1) / FC_CW;
@@ -164,10 +164,61 @@ int launch_tissue_focus(const uint8_t* thumb, int H, int W, const int* taps, int
     return (int)hipGetLastError();
 }
 
-int launch_tissue_cells_union(const uint8_t* otsu, int Ho, int Wo, int T, const uint8_t* focus, int Hf, int Wf, const int* xmap,
-                              const int* ymap, const int* col, const int* row, int gw, int gh, int* count, hipStream_t s) {
+static int launch_tissue_cells_union(const uint8_t* otsu, int Ho, int Wo, int T, const uint8_t* focus, int Hf, int Wf, const int* xmap,
+                                     const int* ymap, const int* col, const int* row, int gw, int gh, int* count, hipStream_t s) {
     const int ncell = gw * gh;
     hipLaunchKernelGGL(focus_union_kernel, dim3((unsigned)((ncell + FC_CELLS - 1) / FC_CELLS)), dim3(FC_NT), 0, s, otsu, Ho, Wo, T, focus,
                        Hf, Wf, xmap, ymap, col, row, gw, ncell, count);
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+int bq_tissue_focus(bq_ctx* c, const uint8_t* d_thumb, int H, int W, const int32_t* d_taps, int r, int thr, int32_t* d_work,
+                    int32_t* d_value_or_null, uint8_t* d_plane, int32_t* d_count, bq_stream_t stream) {
+    if (!c || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31) || r < 1 || r > 16 || thr < 0)
+        return fail(c, BQ_ERR_ARG, "bq_tissue_focus: bad argument (need 0 < H, W, H * W < 2^31, 1 <= r <= 16 and 0 <= thr)");
+    if (!d_thumb || !d_taps || !d_work || !d_plane || !d_count || ((uintptr_t)d_taps & 3) || ((uintptr_t)d_work & 3) ||
+        ((uintptr_t)d_value_or_null & 3) || ((uintptr_t)d_count & 3))
+        return fail(c, BQ_ERR_ARG, "bq_tissue_focus: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tissue_focus", 2.0 * 2 * (2.0 * r + 1) * (double)H * W, (d_value_or_null ? 16.0 : 12.0) * (double)H * W);
+    if (launch_tissue_focus(d_thumb, H, W, d_taps, r, thr, d_work, d_value_or_null, d_plane, d_count, s))
+        return fail(c, BQ_ERR_HIP, "tissue focus launch failed");
+    return BQ_OK;
+}
+
+int bq_tissue_cells_union(bq_ctx* c, const uint8_t* d_otsu_plane, int Ho, int Wo, int T, const uint8_t* d_focus_plane, int Hf, int Wf,
+                          const int32_t* xmap, const int32_t* ymap, const int32_t* col_ranges, int gw, const int32_t* row_ranges, int gh,
+                          int32_t* d_tables, int32_t* d_count, bq_stream_t stream) {
+    if (!c || Ho <= 0 || Wo <= 0 || (int64_t)Ho * Wo >= (1ll << 31) || Hf <= 0 || Wf <= 0 || (int64_t)Hf * Wf >= (1ll << 31) || gw <= 0 ||
+        gh <= 0 || gw > (1 << 15) || gh > (1 << 15) || T < 0 || T > 255)
+        return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: bad argument (need 0 < H, W and H * W < 2^31 for both planes, 0 < gw, gh <= "
+                                   "32768 and 0 <= T <= 255)");
+    if (!d_otsu_plane || !d_focus_plane || !xmap || !ymap || !col_ranges || !row_ranges || !d_tables || !d_count ||
+        ((uintptr_t)d_tables & 3) || ((uintptr_t)d_count & 3))
+        return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: bad argument");
+    const std::string bad = bad_cell_range("Otsu plane", col_ranges, gw, Wo, row_ranges, gh, Ho);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: " + bad);
+    for (int i = 0; i < Wo; ++i)
+        if (xmap[i] < 0 || xmap[i] >= Wf || (i && xmap[i] < xmap[i - 1]))
+            return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: the column map leaves the focus plane or decreases");
+    for (int i = 0; i < Ho; ++i)
+        if (ymap[i] < 0 || ymap[i] >= Hf || (i && ymap[i] < ymap[i - 1]))
+            return fail(c, BQ_ERR_ARG, "bq_tissue_cells_union: the row map leaves the focus plane or decreases");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tissue_cells_union", 0.0, 2.0 * (double)Ho * Wo);
+    int32_t* d_xmap = d_tables;
+    int32_t* d_ymap = d_xmap + Wo;
+    int32_t* d_col = d_ymap + Ho;
+    int32_t* d_row = d_col + 2 * gw;
+    HIPCHK(c, hipMemcpyAsync(d_xmap, xmap, (size_t)Wo * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_ymap, ymap, (size_t)Ho * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_col, col_ranges, (size_t)gw * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_row, row_ranges, (size_t)gh * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (launch_tissue_cells_union(d_otsu_plane, Ho, Wo, T, d_focus_plane, Hf, Wf, d_xmap, d_ymap, d_col, d_row, gw, gh, d_count, s))
+        return fail(c, BQ_ERR_HIP, "tissue cells union launch failed");
+    return BQ_OK;
+}
+
+}  // extern "C"

@@ -19,7 +19,7 @@
 //  * output: literals are collected into a dword per lane and stored when it is full; a match copies from the lane's own output.
 // Results are zlib's: a stream is accepted iff it is well-formed and inflates to exactly the expected number of bytes; the Adler-32
 // trailer is checked by a second small kernel (one wave per stream) so that "accepted" means what uncompress() means.
-#include "bq_common.h"
+#include "bq_ctx.h"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -603,12 +603,12 @@ __global__ void __launch_bounds__(64) adler_kernel(const InflateParams p) {
 
 }  // namespace
 
-size_t inflate_scratch_bytes(int n) { return (size_t)(n > 0 ? n : 0) * SCR_WORDS * 4; }
+static size_t inflate_scratch_bytes(int n) { return (size_t)(n > 0 ? n : 0) * SCR_WORDS * 4; }
 
 // n zlib streams -> n x out_len bytes.  d_z / d_off / d_len: the packed input (see InflateParams); d_out: [n][out_stride] with
 // out_stride >= out_len + 4 and a multiple of 4; d_scratch: inflate_scratch_bytes(n); d_status: [n] (0 = inflated and verified).
-int launch_inflate(const unsigned char* d_z, const unsigned* d_off, const unsigned* d_len, int n, unsigned char* d_out, unsigned out_len,
-                   unsigned out_stride, void* d_scratch, int* d_status, hipStream_t s, int variant, unsigned row_len) {
+static int launch_inflate(const unsigned char* d_z, const unsigned* d_off, const unsigned* d_len, int n, unsigned char* d_out, unsigned out_len,
+                          unsigned out_stride, void* d_scratch, int* d_status, hipStream_t s, int variant, unsigned row_len) {
     if (n <= 0) return 0;
     if (out_stride < out_len + 4 || (out_stride & 3)) return (int)hipErrorInvalidValue;
     InflateParams p;
@@ -627,3 +627,23 @@ int launch_inflate(const unsigned char* d_z, const unsigned* d_off, const unsign
     hipLaunchKernelGGL(adler_kernel, dim3(n), dim3(64), 0, s, p);
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+size_t bq_png_inflate_scratch_bytes(int n) { return inflate_scratch_bytes(n); }
+
+int bq_png_inflate(bq_ctx* c, const uint8_t* d_z, const uint32_t* d_off, const uint32_t* d_len, int n, int px, uint8_t* d_rows,
+                   size_t rows_stride, void* d_scratch, size_t scratch_bytes, int32_t* d_status, bq_stream_t stream) {
+    if (!c || !d_z || !d_off || !d_len || !d_rows || !d_scratch || !d_status || n < 0 || px <= 0 || px > 4096)
+        return fail(c, BQ_ERR_ARG, "bq_png_inflate: bad argument");
+    const size_t row_bytes = (size_t)px * (3 * (size_t)px + 1);
+    if (rows_stride < row_bytes + 4 || (rows_stride & 3) || rows_stride > 0xffffffffull) return fail(c, BQ_ERR_ARG, "bq_png_inflate: rows_stride must be a multiple of 4, >= px (1 + 3 px) + 4");
+    if (scratch_bytes < inflate_scratch_bytes(n)) return fail(c, BQ_ERR_WORKSPACE, "bq_png_inflate: scratch too small");
+    ProfScope ps(c, (hipStream_t)stream, "png_inflate", 0.0, (double)n * row_bytes * 2.0);
+    const int e = launch_inflate(d_z, d_off, d_len, n, d_rows, (unsigned)row_bytes, (unsigned)rows_stride, d_scratch, d_status, (hipStream_t)stream,
+                                 c->inflate_variant, (unsigned)(1 + 3 * px));
+    if (e) return fail(c, BQ_ERR_HIP, std::string("png inflate launch: ") + hipGetErrorString((hipError_t)e));
+    return BQ_OK;
+}
+
+}  // extern "C"

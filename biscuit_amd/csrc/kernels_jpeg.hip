@@ -21,7 +21,7 @@
 //            (place_window of jpeg_device.h, the host's statement too), row by row, in groups of four flat canvas pixels -- 12
 //            bytes at a multiple of 12, so three aligned dword stores wherever the whole group belongs to the row, byte stores
 //            at a row's ragged ends (the pitch 3 W is no multiple of 4 in general).  Nothing outside a window is written.
-#include "bq_common.h"
+#include "bq_ctx.h"
 #include "jpeg_device.h"
 
 namespace {
@@ -173,14 +173,14 @@ __global__ void __launch_bounds__(JP_NT) jpeg_place_kernel(const JpegParams p, c
 
 }  // namespace
 
-size_t jpeg_scratch_bytes(int n, int px) {
+static size_t jpeg_scratch_bytes(int n, int px) {
     if (n <= 0 || px <= 0) return 0;
     return (size_t)(n < JPEG_ROUND ? n : JPEG_ROUND) * bqjd::tile_coef_bytes(px);
 }
 
 // n tiles as bqio_extract_jpeg packed them -> uint8 NHWC + status, in rounds of as many tiles as d_scratch holds.
-int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px, uint8_t* d_out,
-                       int* d_status, void* d_scratch, size_t scratch_bytes, hipStream_t s) {
+static int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px, uint8_t* d_out,
+                              int* d_status, void* d_scratch, size_t scratch_bytes, hipStream_t s) {
     if (n <= 0) return 0;
     const size_t per = bqjd::tile_coef_bytes(px);
     size_t m = scratch_bytes / per;
@@ -207,16 +207,16 @@ int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_
     return (int)hipGetLastError();
 }
 
-size_t jpeg_canvas_scratch_bytes(int n, int w, int h) {
+static size_t jpeg_canvas_scratch_bytes(int n, int w, int h) {
     if (n <= 0 || w <= 0 || h <= 0) return 0;
     return (size_t)(n < JPEG_ROUND ? n : JPEG_ROUND) * bqjd::tile_coef_bytes(w, h);
 }
 
 // n segments of w x h as bqio_extract_jpeg_segments packed them -> their windows in the canvas + status, in rounds of as many
 // segments as d_scratch holds (at least one).
-int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int w, int h,
-                              const int32_t* d_place, uint8_t* d_canvas, int H, int W, const int32_t* clip, int* d_status, void* d_scratch,
-                              size_t scratch_bytes, hipStream_t s) {
+static int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int w, int h,
+                                     const int32_t* d_place, uint8_t* d_canvas, int H, int W, const int32_t* clip, int* d_status, void* d_scratch,
+                                     size_t scratch_bytes, hipStream_t s) {
     if (n <= 0) return 0;
     const size_t per = bqjd::tile_coef_bytes(w, h);
     size_t m = scratch_bytes / per;
@@ -246,3 +246,45 @@ int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, const v
     }
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+size_t bq_jpeg_scratch_bytes(int n, int px) { return jpeg_scratch_bytes(n, px); }
+
+int bq_jpeg_decode(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px,
+                   uint8_t* d_out, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || px <= 0 || px > 4096 || n_tables < 0) return fail(c, BQ_ERR_ARG, "bq_jpeg_decode: bad argument");
+    if (n == 0) return BQ_OK;
+    if (!d_scan || !d_desc || !d_tables || n_tables == 0 || !d_out || !d_status || !d_scratch || ((uintptr_t)d_tables & 3) ||
+        ((uintptr_t)d_scan & 15) || ((uintptr_t)d_desc & 3))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_decode: bad argument");
+    if (scratch_bytes < jpeg_scratch_bytes(n, px)) return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_decode: scratch too small");
+    ProfScope ps(c, (hipStream_t)stream, "jpeg_decode", 0.0, (double)n * px * px * 3.0);
+    const int e = launch_jpeg_decode(d_scan, d_desc, d_tables, n_tables, n, px, d_out, d_status, d_scratch, scratch_bytes, (hipStream_t)stream);
+    if (e) return fail(c, BQ_ERR_HIP, std::string("jpeg decode launch: ") + hipGetErrorString((hipError_t)e));
+    return BQ_OK;
+}
+
+size_t bq_jpeg_canvas_scratch_bytes(int n, int seg_w, int seg_h) { return jpeg_canvas_scratch_bytes(n, seg_w, seg_h); }
+
+int bq_jpeg_decode_canvas(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int seg_w,
+                          int seg_h, const int32_t* d_place, uint8_t* d_canvas, int H, int W, int clip_x0, int clip_y0, int clip_x1,
+                          int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || seg_w <= 0 || seg_w > 4096 || seg_h <= 0 || seg_h > 4096 || n_tables < 0 || H <= 0 || W <= 0 || H > (1 << 28) ||
+        W > (1 << 28))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_decode_canvas: bad argument (need 0 < seg_w, seg_h <= 4096 and 0 < H, W <= 2^28)");
+    if (n == 0) return BQ_OK;
+    if (!d_scan || !d_desc || !d_tables || n_tables == 0 || !d_place || !d_canvas || !d_status || !d_scratch || ((uintptr_t)d_tables & 3) ||
+        ((uintptr_t)d_scan & 15) || ((uintptr_t)d_desc & 3) || ((uintptr_t)d_place & 3))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_decode_canvas: bad argument");
+    if (scratch_bytes < jpeg_canvas_scratch_bytes(1, seg_w, seg_h))
+        return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_decode_canvas: scratch smaller than one segment's (bq_jpeg_canvas_scratch_bytes(1, seg_w, seg_h))");
+    const int32_t clip[4] = {clip_x0, clip_y0, clip_x1, clip_y1};
+    ProfScope ps(c, (hipStream_t)stream, "jpeg_decode_canvas", 0.0, (double)n * seg_w * seg_h * 3.0);
+    const int e = launch_jpeg_decode_canvas(d_scan, d_desc, d_tables, n_tables, n, seg_w, seg_h, d_place, d_canvas, H, W, clip, d_status,
+                                            d_scratch, scratch_bytes, (hipStream_t)stream);
+    if (e) return fail(c, BQ_ERR_HIP, std::string("jpeg canvas decode launch: ") + hipGetErrorString((hipError_t)e));
+    return BQ_OK;
+}
+
+}  // extern "C"

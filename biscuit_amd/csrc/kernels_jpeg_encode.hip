@@ -19,7 +19,7 @@
 // A tile costs Layout::per_tile() bytes of scratch (889 KB at 299 px / 4:2:0, of which 536 KB are the worst-case unstuffed code); a call
 // works in rounds of as many tiles as the caller's scratch holds.  The tables (2.4 KB) and the header (623 bytes) are kernel
 // arguments: nothing is allocated or copied, and nothing waits for the device.
-#include "bq_common.h"
+#include "bq_ctx.h"
 #include "jpeg_encode_device.h"
 
 namespace {
@@ -196,20 +196,21 @@ __global__ void __launch_bounds__(NT) jenc_copy_kernel(const EncParams p, const 
 
 }  // namespace
 
-size_t jpeg_encode_scratch_bytes(int n, int px, int sub) {
+static size_t jpeg_encode_scratch_bytes(int n, int px, int sub) {
     if (n <= 0 || !bqje::valid_args(px, 1, sub)) return 0;
     return (size_t)(n < ENC_ROUND ? n : ENC_ROUND) * layout_of(bqje::geom_of(px, sub)).per_tile();
 }
 
-int jpeg_encode_round_tiles(int px, int sub, size_t scratch_bytes) {
+static int jpeg_encode_round_tiles(int px, int sub, size_t scratch_bytes) {
     size_t m = scratch_bytes / layout_of(bqje::geom_of(px, sub)).per_tile();
     if (m > 32768) m = 32768;            // (the per-block kernels' grids count tiles in y)
     return (int)m;
 }
 
-// One stage of one round: tiles [t0, t0 + cnt) of the call, in a scratch laid out for m tiles (cnt <= m).
-int launch_jpeg_encode_stage(int stage, const uint8_t* d_tiles, long long t0, int cnt, int m, int px, int quality, int sub, void* d_scratch,
-                             uint8_t* d_out, long long cap, long long* d_off, int* d_status, hipStream_t s) {
+enum { JPEG_ENC_PIXEL = 0, JPEG_ENC_SIZE = 1, JPEG_ENC_PACK = 2, JPEG_ENC_STUFF = 3, JPEG_ENC_STAGES = 4 };
+// One stage of one round, so that bq_jpeg_encode can time each: tiles [t0, t0 + cnt) of the call, in a scratch laid out for m tiles (cnt <= m).
+static int launch_jpeg_encode_stage(int stage, const uint8_t* d_tiles, long long t0, int cnt, int m, int px, int quality, int sub, void* d_scratch,
+                                    uint8_t* d_out, long long cap, long long* d_off, int* d_status, hipStream_t s) {
     bqje::Tables T;
     bqje::Header H;
     bqje::build_tables(px, quality, sub, T, H);
@@ -251,3 +252,35 @@ int launch_jpeg_encode_stage(int stage, const uint8_t* d_tiles, long long t0, in
     }
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+size_t bq_jpeg_encode_scratch_bytes(int n, int px, int subsampling) { return jpeg_encode_scratch_bytes(n, px, subsampling); }
+
+int bq_jpeg_encode(bq_ctx* c, const uint8_t* d_tiles, int n, int px, int quality, int subsampling, uint8_t* d_out, int64_t cap,
+                   int64_t* d_off, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || cap < 0) return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: bad argument");
+    if (px < 1 || px > 4096 || quality < 1 || quality > 100 || (subsampling != 0 && subsampling != 2))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: outside the encoder's subset (need 1 <= px <= 4096, 1 <= quality <= 100, subsampling 0 = 4:4:4 or 2 = 4:2:0)");
+    if (n == 0) return BQ_OK;
+    if (!d_tiles || !d_off || !d_status || !d_scratch || (!d_out && cap) || ((uintptr_t)d_off & 7) || ((uintptr_t)d_status & 3) ||
+        ((uintptr_t)d_scratch & 15))
+        return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: bad argument (null pointer, d_off not 8-byte or d_scratch not 16-byte aligned)");
+    const int m = jpeg_encode_round_tiles(px, subsampling, scratch_bytes);
+    if (m < 1) return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_encode: scratch smaller than one tile's (bq_jpeg_encode_scratch_bytes(1, px, subsampling))");
+    hipStream_t s = (hipStream_t)stream;
+    static const char* const kStage[JPEG_ENC_STAGES] = {"jpeg_encode_pixel", "jpeg_encode_size", "jpeg_encode_pack", "jpeg_encode_stuff"};
+    const double blocks = (double)jpeg_encode_scratch_bytes(1, px, subsampling) / 344.0;       // (for the profile's byte column only: about the blocks of a tile)
+    for (long long t0 = 0; t0 < n; t0 += m) {
+        const int cnt = (int)(n - t0 < m ? n - t0 : m);
+        for (int stage = 0; stage < JPEG_ENC_STAGES; ++stage) {
+            ProfScope ps(c, s, kStage[stage], 0.0, stage == JPEG_ENC_PIXEL ? (double)cnt * px * px * 3.0 : (double)cnt * blocks * 128.0);
+            const int e = launch_jpeg_encode_stage(stage, d_tiles, t0, cnt, m, px, quality, subsampling, d_scratch, d_out, (long long)cap,
+                                                   (long long*)d_off, d_status, s);
+            if (e) return fail(c, BQ_ERR_HIP, std::string("jpeg encode launch: ") + hipGetErrorString((hipError_t)e));
+        }
+    }
+    return BQ_OK;
+}
+
+}  // extern "C"

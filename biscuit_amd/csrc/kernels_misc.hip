@@ -1,7 +1,7 @@
 // HBM-bound kernels around the MFMA path: tile staging (K0), the 3->32 stem conv (K1a),
 // max-pool + residual add (K4), global average pool (K5), the MC head's last layer with
-// softmax + Welford fold (K6 tail) and the slide-level segmented reduce (K7).
-#include "bq_common.h"
+// softmax + Welford fold (K6 tail) and the slide-level segmented reduce (K7); the entry points of K0 and K7 at the end.
+#include "bq_ctx.h"
 
 namespace {
 
@@ -403,7 +403,7 @@ inline int grid_for(long long total, int block) { return (int)((total + block - 
     } while (0)
 
 // stats_scratch: 2 x 64-bit per tile, zeroed here
-int launch_stage_u8(const uint8_t* tiles, int n, int px, void* out, int dtype, double* stats_scratch, hipStream_t s) {
+static int launch_stage_u8(const uint8_t* tiles, int n, int px, void* out, int dtype, double* stats_scratch, hipStream_t s) {
     if (n <= 0) return 0;
     unsigned long long* st = reinterpret_cast<unsigned long long*>(stats_scratch);
     hipError_t e = hipMemsetAsync(st, 0, (size_t)n * 16, s);
@@ -425,7 +425,7 @@ int launch_stage_stats(const uint8_t* tiles, int n, int px, double* stats_scratc
     return (int)hipGetLastError();
 }
 
-int launch_stage_f32(const float* tiles, int n, int px, void* out, int dtype, hipStream_t s) {
+static int launch_stage_f32(const float* tiles, int n, int px, void* out, int dtype, hipStream_t s) {
     if (n <= 0) return 0;
     const long long total = (long long)n * px * px;
     BQ_DISPATCH_T(dtype,
@@ -481,9 +481,9 @@ int launch_head_final(const float* h1, int n, int mc_n, int pass0, long long til
     return (int)hipGetLastError();
 }
 
-int launch_slide_reduce(const float* mean2, const float* std2, const int32_t* slide_idx, int n,
-                        int n_slides, float tile_uq, long long* acc_pred, long long* acc_unc,
-                        int32_t* count, hipStream_t s) {
+static int launch_slide_reduce(const float* mean2, const float* std2, const int32_t* slide_idx, int n,
+                               int n_slides, float tile_uq, long long* acc_pred, long long* acc_unc,
+                               int32_t* count, hipStream_t s) {
     if (n <= 0) return 0;
     const int use_uq = (tile_uq == tile_uq) && tile_uq != 0.f;  // NaN / 0 disable the filter
     hipLaunchKernelGGL(slide_reduce_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, mean2, std2, slide_idx,
@@ -492,8 +492,8 @@ int launch_slide_reduce(const float* mean2, const float* std2, const int32_t* sl
     return (int)hipGetLastError();
 }
 
-int launch_slide_finish(const long long* acc_pred, const long long* acc_unc, const int32_t* count,
-                        int n_slides, double* mean_pred, double* mean_unc, hipStream_t s) {
+static int launch_slide_finish(const long long* acc_pred, const long long* acc_unc, const int32_t* count,
+                               int n_slides, double* mean_pred, double* mean_unc, hipStream_t s) {
     if (n_slides <= 0) return 0;
     hipLaunchKernelGGL(slide_finish_kernel, dim3(grid_for(n_slides, 256)), dim3(256), 0, s, acc_pred,
                        acc_unc, count, n_slides, mean_pred, mean_unc);
@@ -516,181 +516,46 @@ int launch_nchw_to_f32_nhwc(const void* x, int n, int C, int HW, float* out, int
     return (int)hipGetLastError();
 }
 
-// ---- K0 (optional front half): Reinhard-fast stain normalisation -------------------------------
-// hp.py:19 normalizer='reinhard_fast', applied to the uint8 tile before the standardisation
-// (results.py:251-256).  One workgroup per tile: pass 1 converts every pixel to CIE-LAB and reduces
-// the six channel statistics in float64 (fixed thread map and tree: bit-reproducible); pass 2
-// re-reads the (L2-resident) tile, converts again, applies (lab - mu) * (target_std / sd) + target_mean,
-// converts back and stores uint8.  The precision contract (float64 for cbrt / pow / the statistics,
-// one float32 rounding per other operation, no FMA contraction) is written out in oracle/stain.py;
-// it makes the uint8 result comparable bit for bit.
-namespace {
+extern "C" {
 
-struct ReinhardConst {
-    float m[9];        // XYZ from linear RGB
-    float minv[9];     // linear RGB from XYZ
-    float white[3];
-    float rwhite[3];   // RN(1 / white): see divc
-    float tgt_mean[3];
-    float tgt_std[3];
-};
-
-struct Lab { float L, a, b; };
-
-// x / c for a constant c, correctly rounded, in three operations instead of the ~10 of the IEEE division sequence (nine divisions by
-// constants per pixel and pass): q = x * rc with rc = RN(1 / c), the exact residual by fma, one correction -- Markstein's theorem:
-// RN(x / c) whenever rc is the correctly rounded reciprocal and c's significand is not all ones (0.95047, 1.08883, 116, 500, 200,
-// 7.787: checked against the division itself on 56 M values, experiments/r06.md).  The contract of oracle/stain.py -- one float32
-// rounding per operation -- is kept to the bit.
-__device__ __forceinline__ float divc(float x, float c, float rc) {
-    const float q = x * rc;
-    const float r = __builtin_fmaf(-q, c, x);
-    return __builtin_fmaf(r, rc, q);
+int bq_stage(bq_ctx* c, const uint8_t* d_tiles, int n, void* d_out, bq_stream_t stream) {
+    if (!c || !d_tiles || !d_out || n < 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_stage: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "stage_u8_standardize", 4.0 * n * kStaged, (double)n * kStaged * (1.0 + esize(c)));
+    if (launch_stage_u8(d_tiles, n, 299, d_out, c->cfg.dtype, c->d_stage_stats, s))
+        return fail(c, BQ_ERR_HIP, "stage launch failed");
+    return BQ_OK;
 }
 
-// cbrt of a float32 t in (0.008856, ~1.1], "evaluated in float64 and rounded to float32" (the contract of oracle/stain.py), without
-// the library's cbrt(double) (~80 double-precision operations): a float32 seed exp2(log2(t) / 3) (relative error ~1e-6), then two
-// Newton steps y -= (y^3 - t) * r in float64 with ONE approximate reciprocal r ~ 1 / (3 y0^2) taken in float32 -- the error contracts
-// by ~1e-6 per step, to the last bits of a double.  The float32 rounding of that differs from the rounding of the exact cube root only
-// where the root lies within ~2e-16 (relative) of a float32 rounding boundary: one evaluation in ~3e8.
-__device__ __forceinline__ float cbrt_f64_rounded(float t) {
-    const float y0 = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(t) * (1.0f / 3.0f));
-    const double r = (double)__builtin_amdgcn_rcpf(3.0f * y0 * y0);
-    const double td = (double)t;
-    double y = (double)y0;
-    y = __builtin_fma(-(__builtin_fma(y * y, y, -td)), r, y);
-    y = __builtin_fma(-(__builtin_fma(y * y, y, -td)), r, y);
-    return (float)y;
+int bq_stage_f32(bq_ctx* c, const float* d_tiles, int n, void* d_out, bq_stream_t stream) {
+    if (!c || !d_tiles || !d_out || n < 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_stage_f32: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "stage_f32_to_planar", 0.0, (double)n * kStaged * (4.0 + esize(c)));
+    if (launch_stage_f32(d_tiles, n, 299, d_out, c->cfg.dtype, s)) return fail(c, BQ_ERR_HIP, "stage launch failed");
+    return BQ_OK;
 }
 
-#pragma clang fp contract(off)
-__device__ __forceinline__ Lab rgb_to_lab(const float* __restrict__ lut, const ReinhardConst& k, unsigned r8,
-                                          unsigned g8, unsigned b8) {
-    const float r = lut[r8], g = lut[g8], b = lut[b8];
-    float f[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float xyz = (k.m[3 * i] * r + k.m[3 * i + 1] * g) + k.m[3 * i + 2] * b;
-        const float t = divc(xyz, k.white[i], k.rwhite[i]);
-        f[i] = t > 0.008856f ? cbrt_f64_rounded(t) : 7.787f * t + (float)(16.0 / 116.0);
-    }
-    Lab o;
-    o.L = 116.0f * f[1] - 16.0f;
-    o.a = 500.0f * (f[0] - f[1]);
-    o.b = 200.0f * (f[1] - f[2]);
-    return o;
+int bq_slide_reduce(bq_ctx* c, const float* d_mean2, const float* d_std2, const int32_t* d_slide_idx, int n,
+                    int n_slides, float tile_uq, int64_t* d_acc_pred, int64_t* d_acc_unc, int32_t* d_count,
+                    bq_stream_t stream) {
+    if (!c || !d_mean2 || !d_std2 || !d_slide_idx || !d_acc_pred || !d_acc_unc || !d_count || n < 0 || n_slides <= 0)
+        return fail(c, BQ_ERR_ARG, "bq_slide_reduce: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "slide_reduce", 2.0 * n, 20.0 * n);
+    if (launch_slide_reduce(d_mean2, d_std2, d_slide_idx, n, n_slides, tile_uq, (long long*)d_acc_pred,
+                            (long long*)d_acc_unc, d_count, s))
+        return fail(c, BQ_ERR_HIP, "slide_reduce launch failed");
+    return BQ_OK;
 }
 
-#pragma clang fp contract(off)
-__device__ __forceinline__ void lab_to_rgb8(const ReinhardConst& k, const float* __restrict__ thr, float L, float a,
-                                            float b, uint8_t* out) {
-    const float fy = divc(L + 16.0f, 116.0f, 1.0f / 116.0f);
-    const float fx = divc(a, 500.0f, 1.0f / 500.0f) + fy;
-    const float fz = fy - divc(b, 200.0f, 1.0f / 200.0f);
-    const float fv[3] = {fx, fy, fz};
-    float xyz[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float v = fv[i];
-        const float t = v > 0.2068966f ? (v * v) * v : divc(v - (float)(16.0 / 116.0), 7.787f, 1.0f / 7.787f);
-        xyz[i] = t * k.white[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float c = (k.minv[3 * i] * xyz[0] + k.minv[3 * i + 1] * xyz[1]) + k.minv[3 * i + 2] * xyz[2];
-        // out = clip(trunc(255 * clip(gamma(c), 0, 1)), 0, 255) is a monotone step function of c: the host evaluates the reference
-        // formula (float64 power rounded to float32, then float32 steps) once per output level and hands over the 255 switching
-        // points: thr[v-1] = smallest float32 c whose output is >= v.  Round 6: a fast float32 gamma gives the level to within one,
-        // and two corrections against the switching points (two pairs of independent LDS reads) make it the formula's own result --
-        // rounds 2-5 ran a bisection, eight DEPENDENT LDS reads per channel, which was most of this kernel's time.
-        const float gam = c > 0.0031308f ? 1.055f * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(c) * (float)(1.0 / 2.4)) - 0.055f : 12.92f * c;
-        int lo = gam > 0.f ? (int)(255.0f * fminf(gam, 1.0f)) : 0;          // (NaN -> 0, like the clip; and it stays 0 below)
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const float t_hi = thr[lo < 255 ? lo : 254], t_lo = thr[lo > 0 ? lo - 1 : 0];
-            const int up = (lo < 255 && c >= t_hi) ? 1 : 0;
-            const int dn = (lo > 0 && !(c >= t_lo)) ? 1 : 0;
-            lo += up - dn;
-        }
-        out[i] = (uint8_t)lo;
-    }
+int bq_slide_finish(bq_ctx* c, const int64_t* d_acc_pred, const int64_t* d_acc_unc, const int32_t* d_count,
+                    int n_slides, double* d_mean_pred, double* d_mean_unc, bq_stream_t stream) {
+    if (!c || !d_acc_pred || !d_acc_unc || !d_count || !d_mean_pred || !d_mean_unc || n_slides <= 0)
+        return fail(c, BQ_ERR_ARG, "bq_slide_finish: bad argument");
+    if (launch_slide_finish((const long long*)d_acc_pred, (const long long*)d_acc_unc, d_count, n_slides,
+                            d_mean_pred, d_mean_unc, (hipStream_t)stream))
+        return fail(c, BQ_ERR_HIP, "slide_finish launch failed");
+    return BQ_OK;
 }
 
-// stats_out (optional): [n][6] = mean L, a, b, std L, a, b.  dst may be null (statistics only) or == src.
-// One workgroup of 1 024 threads per tile (round 6: 512 left every SIMD with two waves and the kernel waiting on its own LDS reads).
-constexpr int RH_NT = 1024;
-__global__ void __launch_bounds__(RH_NT) reinhard_kernel(const uint8_t* __restrict__ tiles, int px,
-                                                         const float* __restrict__ lut, const ReinhardConst k,
-                                                         uint8_t* dst, float* __restrict__ stats_out) {
-    const int npix = px * px;
-    const uint8_t* src = tiles + (size_t)blockIdx.x * npix * 3;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    __shared__ float slut[256];
-    __shared__ float sthr[256];
-    __shared__ double red[6][RH_NT / 64];
-    __shared__ float stat[6];
-    for (int i = tid; i < 256; i += nt) { slut[i] = lut[i]; sthr[i] = lut[256 + i]; }
-    __syncthreads();
-
-    double s[6] = {0, 0, 0, 0, 0, 0};
-    for (int i = tid; i < npix; i += nt) {
-        const Lab v = rgb_to_lab(slut, k, src[3 * i], src[3 * i + 1], src[3 * i + 2]);
-        s[0] += (double)v.L; s[1] += (double)v.a; s[2] += (double)v.b;
-        s[3] += (double)v.L * (double)v.L; s[4] += (double)v.a * (double)v.a; s[5] += (double)v.b * (double)v.b;
-    }
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[q] += __shfl_xor(s[q], o);
-        if ((tid & 63) == 0) red[q][tid >> 6] = s[q];
-    }
-    __syncthreads();
-    if (tid < 3) {
-        double a = 0, b = 0;
-        for (int i = 0; i < nt / 64; ++i) { a += red[tid][i]; b += red[tid + 3][i]; }
-        const double mu = a / (double)npix;
-        double var = b / (double)npix - mu * mu;
-        if (var < 0) var = 0;
-        stat[tid] = (float)mu;
-        stat[tid + 3] = (float)sqrt(var);
-        if (stats_out) {
-            stats_out[(size_t)blockIdx.x * 6 + tid] = (float)mu;
-            stats_out[(size_t)blockIdx.x * 6 + tid + 3] = (float)sqrt(var);
-        }
-    }
-    __syncthreads();
-    if (!dst) return;
-    uint8_t* o = dst + (size_t)blockIdx.x * npix * 3;
-    float sc[3];
-    {
-#pragma clang fp contract(off)
-        sc[0] = k.tgt_std[0] / stat[3]; sc[1] = k.tgt_std[1] / stat[4]; sc[2] = k.tgt_std[2] / stat[5];
-    }
-    for (int i = tid; i < npix; i += nt) {
-#pragma clang fp contract(off)
-        const Lab v = rgb_to_lab(slut, k, src[3 * i], src[3 * i + 1], src[3 * i + 2]);
-        const float L = (v.L - stat[0]) * sc[0] + k.tgt_mean[0];
-        const float a = (v.a - stat[1]) * sc[1] + k.tgt_mean[1];
-        const float b = (v.b - stat[2]) * sc[2] + k.tgt_mean[2];
-        uint8_t rgb[3];
-        lab_to_rgb8(k, sthr, L, a, b, rgb);
-        o[3 * i] = rgb[0]; o[3 * i + 1] = rgb[1]; o[3 * i + 2] = rgb[2];
-    }
-}
-
-}  // namespace
-
-int launch_reinhard(const uint8_t* tiles, int n, int px, const float* d_lut, const float* consts27,
-                    const float* tgt_mean, const float* tgt_std, uint8_t* dst, float* d_stats, hipStream_t s) {
-    if (n <= 0) return 0;
-    ReinhardConst k;
-    for (int i = 0; i < 9; ++i) { k.m[i] = consts27[i]; k.minv[i] = consts27[9 + i]; }
-    for (int i = 0; i < 3; ++i) {
-        k.white[i] = consts27[18 + i];
-        k.rwhite[i] = 1.0f / consts27[18 + i];
-        k.tgt_mean[i] = tgt_mean ? tgt_mean[i] : 0.f;
-        k.tgt_std[i] = tgt_std ? tgt_std[i] : 1.f;
-    }
-    hipLaunchKernelGGL(reinhard_kernel, dim3(n), dim3(RH_NT), 0, s, tiles, px, d_lut, k, dst, d_stats);
-    return (int)hipGetLastError();
-}
+}  // extern "C"

@@ -12,7 +12,7 @@
 // Input: what libbiscuit_io's bqio_decode_rows leaves in (pinned) host memory -- per tile px rows of 1 filter-type byte +
 // 3 px filtered bytes, exactly the inflated IDAT stream of an 8-bit RGB, non-interlaced PNG (tiles of any other kind are
 // un-filtered by the reader and arrive as filter type 0).  Output: uint8 NHWC [n][px][px][3], what bq_stage takes.
-#include "bq_common.h"
+#include "bq_ctx.h"
 
 namespace {
 
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(NTHR) png_unfilter_kernel(const unsigned char*
 }  // namespace
 
 // in_stride: bytes between the row data of consecutive tiles (0: packed, px * (1 + 3 px); the device inflate pads to a dword)
-int launch_png_unfilter(const unsigned char* rows, int n, int px, unsigned char* out, hipStream_t s, size_t in_stride) {
+static int launch_png_unfilter(const unsigned char* rows, int n, int px, unsigned char* out, hipStream_t s, size_t in_stride = 0) {
     if (n <= 0) return 0;
     if (in_stride == 0) in_stride = (size_t)px * (3 * px + 1);
     if (in_stride < (size_t)px * (3 * px + 1)) return (int)hipErrorInvalidValue;
@@ -174,3 +174,19 @@ int launch_png_unfilter(const unsigned char* rows, int n, int px, unsigned char*
     hipLaunchKernelGGL(png_unfilter_kernel, dim3(n), dim3(NTHR), lds, s, rows, out, px, in_stride);
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+int bq_png_unfilter(bq_ctx* c, const uint8_t* d_rows, int n, int px, uint8_t* d_out, bq_stream_t stream) {
+    if (!c || !d_rows || !d_out || n < 0 || px <= 0) return fail(c, BQ_ERR_ARG, "bq_png_unfilter: bad argument");
+    if (launch_png_unfilter(d_rows, n, px, d_out, (hipStream_t)stream)) return fail(c, BQ_ERR_HIP, "png unfilter launch failed");
+    return BQ_OK;
+}
+
+int bq_png_unfilter_strided(bq_ctx* c, const uint8_t* d_rows, size_t rows_stride, int n, int px, uint8_t* d_out, bq_stream_t stream) {
+    if (!c || !d_rows || !d_out || n < 0 || px <= 0) return fail(c, BQ_ERR_ARG, "bq_png_unfilter_strided: bad argument");
+    if (launch_png_unfilter(d_rows, n, px, d_out, (hipStream_t)stream, rows_stride)) return fail(c, BQ_ERR_HIP, "png unfilter launch failed");
+    return BQ_OK;
+}
+
+}  // extern "C"

@@ -14,9 +14,10 @@
 // staged by a pre-pass: no scratch, one launch.
 // The tables are caller-owned device memory: a cell index read from them is clamped to the grid (negative = no cell in the first
 // column of an entry), so a damaged table gives wrong colours, never an access out of bounds.
-#include "bq_common.h"
+#include "bq_ctx.h"
 
 #include <math.h>
+#include <cmath>
 
 namespace {
 
@@ -141,8 +142,8 @@ __global__ void __launch_bounds__(RD_NT) render_kernel(const RenderParams p) {
 
 }  // namespace
 
-int launch_heatmap_render(const float* values, int gh, int gw, const int32_t* col, const int32_t* row, int bicubic, const uint8_t* lut,
-                          const uint8_t* thumb, uint8_t* out, int H, int W, float vmin, float inv, int A, hipStream_t s) {
+static int launch_heatmap_render(const float* values, int gh, int gw, const int32_t* col, const int32_t* row, int bicubic, const uint8_t* lut,
+                                 const uint8_t* thumb, uint8_t* out, int H, int W, float vmin, float inv, int A, hipStream_t s) {
     RenderParams p;
     p.values = values; p.col = col; p.row = row; p.lut = lut; p.thumb = thumb; p.out = out;
     p.gh = gh; p.gw = gw; p.H = H; p.W = W; p.A = A; p.vmin = vmin; p.inv = inv;
@@ -152,3 +153,28 @@ int launch_heatmap_render(const float* values, int gh, int gw, const int32_t* co
     else hipLaunchKernelGGL(render_kernel<false>, grid, dim3(RD_NT), 0, s, p);
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+int bq_heatmap_render(bq_ctx* c, const float* d_values, int gh, int gw, const int32_t* d_col, const int32_t* d_row, int interpolation,
+                      const uint8_t* d_lut, const uint8_t* d_thumb, uint8_t* d_out, int H, int W, float vmin, float inv_span, int A,
+                      bq_stream_t stream) {
+    if (!c || gh <= 0 || gw <= 0 || gh > (1 << 15) || gw > (1 << 15) || H <= 0 || W <= 0 || H > 16384 || W > 16384)
+        return fail(c, BQ_ERR_ARG, "bq_heatmap_render: bad argument (need 0 < gh, gw <= 32768 and 0 < H, W <= 16384)");
+    if (interpolation != 0 && interpolation != 1) return fail(c, BQ_ERR_ARG, "bq_heatmap_render: interpolation must be 0 (none) or 1 (bicubic)");
+    if (!(A >= 0 && A <= 256) || !std::isfinite(vmin) || !std::isnormal(inv_span) || !(inv_span > 0.0f))
+        return fail(c, BQ_ERR_ARG, "bq_heatmap_render: bad argument (need 0 <= A <= 256, vmin finite, inv_span a normal positive float)");
+    if (!d_values || !d_col || !d_row || !d_lut || !d_thumb || !d_out || ((uintptr_t)d_values & 3) || ((uintptr_t)d_col & 3) ||
+        ((uintptr_t)d_row & 3))
+        return fail(c, BQ_ERR_ARG, "bq_heatmap_render: bad argument");
+    const size_t bytes = (size_t)3 * H * W;
+    if (d_out != d_thumb && d_out < d_thumb + bytes && d_thumb < d_out + bytes)
+        return fail(c, BQ_ERR_ARG, "bq_heatmap_render: out must be the thumbnail itself or not overlap it");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "heatmap_render", 0.0, 2.0 * (double)bytes);
+    if (launch_heatmap_render(d_values, gh, gw, d_col, d_row, interpolation, d_lut, d_thumb, d_out, H, W, vmin, inv_span, A, s))
+        return fail(c, BQ_ERR_HIP, "heatmap render launch failed");
+    return BQ_OK;
+}
+
+}  // extern "C"

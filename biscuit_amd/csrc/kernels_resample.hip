@@ -14,7 +14,7 @@
 // the canvas read as 255; a tile whose window lies inside the canvas takes the loop without the bounds checks (wave-uniform).
 // The tables are caller-owned device memory: every window read from them is clamped (resample_device.h: window) and every LDS
 // row index is held inside the strip's rows, so a damaged table gives wrong bytes, never an access out of bounds.
-#include "bq_common.h"
+#include "bq_ctx.h"
 #include "resample_device.h"
 
 #include <math.h>
@@ -120,11 +120,11 @@ __global__ void __launch_bounds__(RS_NT) grayspace_kernel(const uint8_t* __restr
 
 }  // namespace
 
-int resample_ksize(int src_px, int px) { return bqrs::ksize_of(src_px, px); }      // for bq_tile_resample's argument check
+static int resample_ksize(int src_px, int px) { return bqrs::ksize_of(src_px, px); }      // for bq_tile_resample's argument check
 
 // Output rows per strip for this ratio, or 0 when even one row's taps do not fit the LDS budget.  The rows a strip of R output
 // rows reads: first(r0 + R - 1) - first(r0) <= ceil((R - 1) scale) + 1, plus at most ksize taps of the last row.
-int resample_strip_rows(int src_px, int px, int ksize, int* max_rows) {
+static int resample_strip_rows(int src_px, int px, int ksize, int* max_rows) {
     const int cap = RS_LDS / (3 * px);
     const double scale = (double)src_px / px;
     for (int R = RS_MAX_R; R >= 1; --R) {
@@ -135,15 +135,15 @@ int resample_strip_rows(int src_px, int px, int ksize, int* max_rows) {
 }
 
 // Workgroups a call launches (one grid dimension): n x strips, or n x blocks of 16 rows for the copy; 0 when the ratio does not fit.
-long long resample_grid(int n, int src_px, int px, int ksize) {
+static long long resample_grid(int n, int src_px, int px, int ksize) {
     if (src_px == px) return (long long)n * ((px + 15) / 16);
     int rows = 0;
     const int R = resample_strip_rows(src_px, px, ksize, &rows);
     return R > 0 ? (long long)n * ((px + R - 1) / R) : 0;
 }
 
-int launch_tile_resample(const uint8_t* canvas, int H, int W, const int* origin, int n, int src_px, int px, const int* bounds,
-                         const int* coef, int ksize, uint8_t* out, hipStream_t s) {
+static int launch_tile_resample(const uint8_t* canvas, int H, int W, const int* origin, int n, int src_px, int px, const int* bounds,
+                                const int* coef, int ksize, uint8_t* out, hipStream_t s) {
     if (n <= 0) return 0;
     if (src_px == px) {
         const int rows = 16, blocks = (px + rows - 1) / rows;
@@ -159,8 +159,47 @@ int launch_tile_resample(const uint8_t* canvas, int H, int W, const int* origin,
     return (int)hipGetLastError();
 }
 
-int launch_tile_grayspace(const uint8_t* tiles, int n, int px, const int* limit256, int* count, hipStream_t s) {
+static int launch_tile_grayspace(const uint8_t* tiles, int n, int px, const int* limit256, int* count, hipStream_t s) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(grayspace_kernel, dim3(n), dim3(RS_NT), 0, s, tiles, px * px, limit256, count);
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+int bq_tile_resample(bq_ctx* c, const uint8_t* d_canvas, int H, int W, const int32_t* d_origin, int n, int src_px, int px,
+                     const int32_t* d_bounds, const int32_t* d_coef, int ksize, uint8_t* d_out, bq_stream_t stream) {
+    if (!c || n < 0 || n > (1 << 20) || px <= 0 || px > 4096 || src_px <= 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28) ||
+        (int64_t)src_px > 8ll * px || (int64_t)px > 8ll * src_px)
+        return fail(c, BQ_ERR_ARG, "bq_tile_resample: bad argument (need 0 < px <= 4096, px / 8 <= src_px <= 8 px, 0 <= n <= 2^20, H, W <= 2^28)");
+    if (n == 0) return BQ_OK;
+    if (!d_canvas || !d_origin || !d_out || ((uintptr_t)d_origin & 3)) return fail(c, BQ_ERR_ARG, "bq_tile_resample: bad argument");
+    if (src_px != px) {
+        if (!d_bounds || !d_coef || ((uintptr_t)d_bounds & 3) || ((uintptr_t)d_coef & 3) || ksize != resample_ksize(src_px, px))
+            return fail(c, BQ_ERR_ARG, "bq_tile_resample: the tap tables are not bqio_resample_taps(src_px, px)'s");
+        int rows = 0;
+        if (!resample_strip_rows(src_px, px, ksize, &rows))
+            return fail(c, BQ_ERR_ARG, "bq_tile_resample: the taps of one output row do not fit the kernel's LDS at this px and ratio");
+    }
+    if (resample_grid(n, src_px, px, ksize) > 0x7fffffffll)
+        return fail(c, BQ_ERR_ARG, "bq_tile_resample: n x strips of output rows exceeds 2^31 - 1 workgroups; split the call");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tile_resample", 2.0 * 2 * 3 * (double)n * px * px * (src_px == px ? 0 : ksize),
+                 (double)n * 3 * ((double)src_px * src_px + (double)px * px));
+    if (launch_tile_resample(d_canvas, H, W, d_origin, n, src_px, px, d_bounds, d_coef, ksize, d_out, s))
+        return fail(c, BQ_ERR_HIP, "tile resample launch failed");
+    return BQ_OK;
+}
+
+int bq_tile_grayspace(bq_ctx* c, const uint8_t* d_tiles, int n, int px, const int32_t* d_limit256, int32_t* d_count, bq_stream_t stream) {
+    if (!c || n < 0 || px <= 0 || px > 4096) return fail(c, BQ_ERR_ARG, "bq_tile_grayspace: bad argument");
+    if (n == 0) return BQ_OK;
+    if (!d_tiles || !d_limit256 || !d_count || ((uintptr_t)d_limit256 & 3) || ((uintptr_t)d_count & 3))
+        return fail(c, BQ_ERR_ARG, "bq_tile_grayspace: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tile_grayspace", 6.0 * n * px * px, 3.0 * n * px * px);
+    if (launch_tile_grayspace(d_tiles, n, px, d_limit256, d_count, s)) return fail(c, BQ_ERR_HIP, "grayspace launch failed");
+    return BQ_OK;
+}
+
+}  // extern "C"

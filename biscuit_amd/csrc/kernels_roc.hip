@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "bq_common.h"
+#include "bq_ctx.h"
 
 namespace {
 
@@ -74,7 +74,7 @@ struct U8ToU32 {
 
 }  // namespace
 
-size_t roc_workspace_bytes(long long n) {
+static size_t roc_workspace_bytes(long long n) {
     if (n <= 0) return 0;
     size_t sort_b = 0, scan_b = 0, red_b = 0;
     (void)rocprim::radix_sort_pairs_desc(nullptr, sort_b, (double*)nullptr, (double*)nullptr, (unsigned char*)nullptr,
@@ -90,8 +90,8 @@ size_t roc_workspace_bytes(long long n) {
 }
 
 // score [n] float64, label [n] uint8 (non-zero = positive), all on the device; out [6] float64 on the device.
-int launch_roc_youden(const double* score, const unsigned char* label, long long n, unsigned char* ws, size_t ws_bytes,
-                      double* out, hipStream_t s) {
+static int launch_roc_youden(const double* score, const unsigned char* label, long long n, unsigned char* ws, size_t ws_bytes,
+                             double* out, hipStream_t s) {
     if (n <= 0) return (int)hipErrorInvalidValue;
     if (ws_bytes < roc_workspace_bytes(n)) return (int)hipErrorInvalidValue;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -123,3 +123,21 @@ int launch_roc_youden(const double* score, const unsigned char* label, long long
     hipLaunchKernelGGL(roc_finish_kernel, dim3(1), dim3(1), 0, s, best, k_sorted, cum, n, out);
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+size_t bq_roc_workspace_bytes(int64_t n) { return roc_workspace_bytes((long long)n); }
+
+int bq_roc_youden(bq_ctx* c, const double* d_score, const uint8_t* d_label, int64_t n, void* d_ws, size_t ws_bytes,
+                  double* d_out6, bq_stream_t stream) {
+    if (!c || !d_score || !d_label || !d_ws || !d_out6 || n <= 0 || n > 0x7fffffffLL)
+        return fail(c, BQ_ERR_ARG, "bq_roc_youden: bad argument");
+    if (ws_bytes < roc_workspace_bytes(n)) return fail(c, BQ_ERR_ARG, "bq_roc_youden: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "roc_youden", 4.0 * n, 60.0 * n);
+    const int e = launch_roc_youden(d_score, d_label, (long long)n, (unsigned char*)d_ws, ws_bytes, d_out6, s);
+    if (e) return fail(c, BQ_ERR_HIP, std::string("roc_youden: ") + hipGetErrorString((hipError_t)e));
+    return BQ_OK;
+}
+
+}  // extern "C"

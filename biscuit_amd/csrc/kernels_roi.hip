@@ -18,7 +18,7 @@
 // Stores: a thread's four pixels are one ALIGNED dword of the plane -- the pixel groups of a row start at -(address of the row
 // & 3), not at 0 -- stored as a dword when all four lie in the row and byte by byte at the row's two ends.  The sample tables and
 // the polygon starts are checked on the host before they are uploaded (bq_roi_plane); indices are clamped here all the same.
-#include "bq_common.h"
+#include "bq_ctx.h"
 #include "roi_device.h"
 
 namespace {
@@ -95,8 +95,8 @@ __global__ void __launch_bounds__(RO_NT) roi_plane_kernel(const int4* __restrict
 
 }  // namespace
 
-int launch_roi_plane(const int* edges, int E, const int* starts, int P, const int* xs, const int* ys, int H, int W, uint8_t* plane,
-                     hipStream_t s) {
+static int launch_roi_plane(const int* edges, int E, const int* starts, int P, const int* xs, const int* ys, int H, int W, uint8_t* plane,
+                            hipStream_t s) {
     if (E < 1 || P < 1 || H < 1 || W < 1 || ((uintptr_t)edges & 15)) return (int)hipErrorInvalidValue;
     const long long groups = ((long long)W + 2 * (RO_PPT - 1)) / RO_PPT;      // ceil((W + 3) / 4): any misalignment
     const long long bx = (groups + RO_NT - 1) / RO_NT;      // (W < 2^31: below 2^21)
@@ -105,3 +105,25 @@ int launch_roi_plane(const int* edges, int E, const int* starts, int P, const in
                        P, xs, ys, H, W, plane);
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+int bq_roi_plane(bq_ctx* c, const int32_t* edges, int E, const int32_t* starts, int P, const int32_t* xs, int W, const int32_t* ys, int H,
+                 int32_t* d_tables, uint8_t* d_plane, bq_stream_t stream) {
+    if (!c || !d_tables || !d_plane || ((uintptr_t)d_tables & 15)) return fail(c, BQ_ERR_ARG, "bq_roi_plane: bad argument");
+    if (const char* why = bqroi::check_tables(edges, E, starts, P, xs, W, ys, H)) return fail(c, BQ_ERR_ARG, std::string("bq_roi_plane: ") + why);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "roi_plane", 0.0, (double)H * W);
+    int32_t* d_edges = d_tables;                                             // (first: the kernel loads an edge as 16 bytes)
+    int32_t* d_starts = d_edges + (size_t)4 * E;
+    int32_t* d_xs = d_starts + P + 1;
+    int32_t* d_ys = d_xs + W;
+    HIPCHK(c, hipMemcpyAsync(d_edges, edges, (size_t)4 * E * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_starts, starts, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_xs, xs, (size_t)W * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_ys, ys, (size_t)H * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (launch_roi_plane(d_edges, E, d_starts, P, d_xs, d_ys, H, W, d_plane, s)) return fail(c, BQ_ERR_HIP, "roi plane launch failed");
+    return BQ_OK;
+}
+
+}  // extern "C"

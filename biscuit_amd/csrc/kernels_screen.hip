@@ -12,7 +12,7 @@
 //   range_select_kernel  one workgroup: the batch's keys merged with the k slots, survivors keep their slot, newly admitted tiles
 //                        take the freed ones in rank order; writes the copy plan
 //   range_copy_kernel    the bytes of each newly admitted tile into its slot (blocks of untouched slots return at once)
-#include "bq_common.h"
+#include "bq_ctx.h"
 
 namespace {
 
@@ -188,16 +188,12 @@ __global__ void __launch_bounds__(kScreenNT) range_copy_kernel(const uint8_t* __
 
 }  // namespace
 
-size_t range_ws_bytes(int n) {
+static size_t range_ws_bytes(int n) {
     const size_t parts = (size_t)(n > 0 ? n : 0) * kScreenSlices * sizeof(RangePart);
     return ((parts + 255) & ~(size_t)255) + 256;          // + the copy plan (int [kMaxSlots])
 }
 
-int range_max_slots() { return kMaxSlots; }
-
-size_t range_select_lds(int filled, int n) { return (size_t)(filled + n) * sizeof(Entry); }
-
-int launch_range_key(const uint8_t* tiles, int n, int px, void* ws, float* key, hipStream_t s) {
+static int launch_range_key(const uint8_t* tiles, int n, int px, void* ws, float* key, hipStream_t s) {
     if (n <= 0) return 0;
     RangePart* parts = reinterpret_cast<RangePart*>(ws);
     hipLaunchKernelGGL(range_stats_kernel, dim3(n * kScreenSlices), dim3(kScreenNT), 0, s, tiles, px, parts);
@@ -205,15 +201,45 @@ int launch_range_key(const uint8_t* tiles, int n, int px, void* ws, float* key, 
     return (int)hipGetLastError();
 }
 
-int launch_range_screen(const uint8_t* tiles, int n, int px, long long tile_idx0, const long long* tile_idx, float* cand_key,
-                        long long* cand_idx, uint8_t* cand_tiles, int k, int filled, void* ws, hipStream_t s) {
+static int launch_range_screen(const uint8_t* tiles, int n, int px, long long tile_idx0, const long long* tile_idx, float* cand_key,
+                               long long* cand_idx, uint8_t* cand_tiles, int k, int filled, void* ws, hipStream_t s) {
     if (n <= 0) return 0;
     RangePart* parts = reinterpret_cast<RangePart*>(ws);
     const size_t pb = (size_t)n * kScreenSlices * sizeof(RangePart);
     int* plan = reinterpret_cast<int*>((unsigned char*)ws + ((pb + 255) & ~(size_t)255));
     hipLaunchKernelGGL(range_stats_kernel, dim3(n * kScreenSlices), dim3(kScreenNT), 0, s, tiles, px, parts);
-    hipLaunchKernelGGL(range_select_kernel, dim3(1), dim3(kSelectNT), range_select_lds(filled, n), s, parts, n, px, tile_idx0,
+    hipLaunchKernelGGL(range_select_kernel, dim3(1), dim3(kSelectNT), (size_t)(filled + n) * sizeof(Entry), s, parts, n, px, tile_idx0,
                        tile_idx, cand_key, cand_idx, k, filled, plan);
     hipLaunchKernelGGL(range_copy_kernel, dim3(k * kCopySlices), dim3(kScreenNT), 0, s, tiles, px, plan, cand_tiles);
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+size_t bq_range_ws_bytes(int n) { return n < 0 ? 0 : range_ws_bytes(n); }
+
+int bq_range_key(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_key, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || (n > 0 && (!d_tiles || !d_key || !d_ws))) return fail(c, BQ_ERR_ARG, "bq_range_key: bad argument");
+    if (ws_bytes < range_ws_bytes(n)) return fail(c, BQ_ERR_ARG, "bq_range_key: scratch smaller than bq_range_ws_bytes(n)");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "range_key", 2.0 * n * kStaged, (double)n * kStaged);
+    if (launch_range_key(d_tiles, n, 299, d_ws, d_key, s)) return fail(c, BQ_ERR_HIP, "range key launch failed");
+    return BQ_OK;
+}
+
+int bq_range_screen(bq_ctx* c, const uint8_t* d_tiles, int n, int64_t tile_idx0, const int64_t* d_tile_idx, float* d_cand_key,
+                    int64_t* d_cand_idx, uint8_t* d_cand_tiles, int k, int filled, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    if (!c || n < 0 || n > 2048 || (n > 0 && (!d_tiles || !d_cand_key || !d_cand_idx || !d_cand_tiles || !d_ws)))
+        return fail(c, BQ_ERR_ARG, "bq_range_screen: bad argument");
+    if (k < 1 || k > kMaxSlots || filled < 0 || filled > k)
+        return fail(c, BQ_ERR_ARG, "bq_range_screen: need 1 <= k <= " + std::to_string(kMaxSlots) + " and 0 <= filled <= k");
+    if (ws_bytes < range_ws_bytes(n)) return fail(c, BQ_ERR_ARG, "bq_range_screen: scratch smaller than bq_range_ws_bytes(n)");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "range_screen", 2.0 * n * kStaged, (double)n * kStaged);
+    if (launch_range_screen(d_tiles, n, 299, (long long)tile_idx0, reinterpret_cast<const long long*>(d_tile_idx), d_cand_key,
+                            reinterpret_cast<long long*>(d_cand_idx), d_cand_tiles, k, filled, d_ws, s))
+        return fail(c, BQ_ERR_HIP, "range screen launch failed");
+    return BQ_OK;
+}
+
+}  // extern "C"

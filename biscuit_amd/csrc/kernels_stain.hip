@@ -22,7 +22,9 @@
 // Degenerate tiles: status 1 = n_tissue < 2, 2 = |det(HE^T HE)| < 1e-12, 3 = a maxC <= 0 or a non-finite
 // intermediate; such a tile passes through unchanged (copied when dst != src).  dst may equal src: every pixel is read and
 // written by one thread in the last pass, after every read of the others.
-#include "bq_common.h"
+#include "bq_ctx.h"
+
+#include <cmath>
 
 namespace {
 
@@ -432,8 +434,8 @@ __global__ void __launch_bounds__(MK_NT) macenko_kernel(const uint8_t* tiles, in
 
 }  // namespace
 
-int launch_macenko(const uint8_t* tiles, int n, int px, const float* he_ref6, const float* maxc_ref2, uint8_t* dst,
-                   float* d_stats8, int* d_status, int status_stride, hipStream_t s) {
+static int launch_macenko(const uint8_t* tiles, int n, int px, const float* he_ref6, const float* maxc_ref2, uint8_t* dst,
+                          float* d_stats8, int* d_status, int status_stride, hipStream_t s) {
     if (n <= 0) return 0;
     MacenkoRef ref;
     for (int i = 0; i < 6; ++i) ref.he[i] = he_ref6 ? he_ref6[i] : 0.f;
@@ -441,3 +443,32 @@ int launch_macenko(const uint8_t* tiles, int n, int px, const float* he_ref6, co
     hipLaunchKernelGGL(macenko_kernel, dim3(n), dim3(MK_NT), 0, s, tiles, px, ref, dst, d_stats8, d_status, status_stride);
     return (int)hipGetLastError();
 }
+
+extern "C" {
+
+int bq_stain_macenko(bq_ctx* c, const uint8_t* d_tiles, int n, const float* he_ref6, const float* maxc_ref2,
+                     uint8_t* d_out, int* d_status, bq_stream_t stream) {
+    if (!c || !d_tiles || !d_out || !he_ref6 || !maxc_ref2 || n < 0)
+        return fail(c, BQ_ERR_ARG, "bq_stain_macenko: bad argument");
+    for (int i = 0; i < 6; ++i)
+        if (!std::isfinite(he_ref6[i])) return fail(c, BQ_ERR_ARG, "bq_stain_macenko: non-finite stain matrix");
+    for (int i = 0; i < 2; ++i)
+        if (!std::isfinite(maxc_ref2[i]) || !(maxc_ref2[i] > 0.f))
+            return fail(c, BQ_ERR_ARG, "bq_stain_macenko: target concentrations must be finite and > 0");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "stain_macenko", 400.0 * n * 299 * 299, 3.0 * n * kStaged);
+    if (launch_macenko(d_tiles, n, 299, he_ref6, maxc_ref2, d_out, nullptr, d_status, 1, s))
+        return fail(c, BQ_ERR_HIP, "macenko launch failed");
+    return BQ_OK;
+}
+
+int bq_stain_macenko_stats(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_stats8, int* d_status2, bq_stream_t stream) {
+    if (!c || !d_tiles || !d_stats8 || n < 0) return fail(c, BQ_ERR_ARG, "bq_stain_macenko_stats: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "stain_macenko_stats", 350.0 * n * 299 * 299, 1.0 * n * kStaged);
+    if (launch_macenko(d_tiles, n, 299, nullptr, nullptr, nullptr, d_stats8, d_status2, 2, s))
+        return fail(c, BQ_ERR_HIP, "macenko stats launch failed");
+    return BQ_OK;
+}
+
+}  // extern "C"

@@ -13,7 +13,7 @@
 // tissue_cells_kernel: one wave per grid cell counts the cell's background pixels (plane <= T) over its column x row range of
 // the plane and reduces across the wave.  Cells may overlap and may be one pixel wide.  The ranges are checked on the host
 // before they are uploaded (bq_tissue_cells); the kernel clamps them to the plane all the same.
-#include "bq_common.h"
+#include "bq_ctx.h"
 
 namespace {
 
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(TS_NT) tissue_cells_kernel(const uint8_t* __re
 
 }  // namespace
 
-int launch_tissue_blur(const uint8_t* thumb, int H, int W, const int* sdiv256, uint8_t* plane, int* hist, hipStream_t s) {
+static int launch_tissue_blur(const uint8_t* thumb, int H, int W, const int* sdiv256, uint8_t* plane, int* hist, hipStream_t s) {
     if (const hipError_t e = hipMemsetAsync(hist, 0, 256 * sizeof(int), s)) return (int)e;
     const int tiles_x = (W + TS_TW - 1) / TS_TW, tiles_y = (H + TS_TH - 1) / TS_TH;
     const long long blocks = (long long)tiles_x * tiles_y;                   // (H W < 2^31: below 2^29)
@@ -99,10 +99,54 @@ int launch_tissue_blur(const uint8_t* thumb, int H, int W, const int* sdiv256, u
     return (int)hipGetLastError();
 }
 
-int launch_tissue_cells(const uint8_t* plane, int H, int W, int T, const int* col, const int* row, int gw, int gh, int* count,
-                        hipStream_t s) {
+static int launch_tissue_cells(const uint8_t* plane, int H, int W, int T, const int* col, const int* row, int gw, int gh, int* count,
+                               hipStream_t s) {
     const int ncell = gw * gh;
     hipLaunchKernelGGL(tissue_cells_kernel, dim3((unsigned)((ncell + TS_CELLS - 1) / TS_CELLS)), dim3(TS_NT), 0, s, plane, H, W, T, col,
                        row, gw, ncell, count);
     return (int)hipGetLastError();
 }
+
+// (bq_ctx.h: shared with bq_tissue_cells_union)
+std::string bad_cell_range(const char* plane, const int32_t* col_ranges, int gw, int W, const int32_t* row_ranges, int gh, int H) {
+    for (int i = 0; i < gw; ++i)
+        if (col_ranges[2 * i] < 0 || col_ranges[2 * i] >= col_ranges[2 * i + 1] || col_ranges[2 * i + 1] > W)
+            return std::string("a column range is empty or outside the ") + plane;
+    for (int i = 0; i < gh; ++i)
+        if (row_ranges[2 * i] < 0 || row_ranges[2 * i] >= row_ranges[2 * i + 1] || row_ranges[2 * i + 1] > H)
+            return std::string("a row range is empty or outside the ") + plane;
+    return std::string();
+}
+
+extern "C" {
+
+int bq_tissue_blur(bq_ctx* c, const uint8_t* d_thumb, int H, int W, const int32_t* d_sdiv256, uint8_t* d_plane, int32_t* d_hist,
+                   bq_stream_t stream) {
+    if (!c || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31))
+        return fail(c, BQ_ERR_ARG, "bq_tissue_blur: bad argument (need 0 < H, W and H * W < 2^31)");
+    if (!d_thumb || !d_sdiv256 || !d_plane || !d_hist || ((uintptr_t)d_sdiv256 & 3) || ((uintptr_t)d_hist & 3))
+        return fail(c, BQ_ERR_ARG, "bq_tissue_blur: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tissue_blur", 0.0, 4.0 * (double)H * W);
+    if (launch_tissue_blur(d_thumb, H, W, d_sdiv256, d_plane, d_hist, s)) return fail(c, BQ_ERR_HIP, "tissue blur launch failed");
+    return BQ_OK;
+}
+
+int bq_tissue_cells(bq_ctx* c, const uint8_t* d_plane, int H, int W, int T, const int32_t* col_ranges, int gw, const int32_t* row_ranges,
+                    int gh, int32_t* d_ranges, int32_t* d_count, bq_stream_t stream) {
+    if (!c || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31) || gw <= 0 || gh <= 0 || gw > (1 << 15) || gh > (1 << 15) || T < 0 || T > 255)
+        return fail(c, BQ_ERR_ARG, "bq_tissue_cells: bad argument (need 0 < H, W, H * W < 2^31, 0 < gw, gh <= 32768 and 0 <= T <= 255)");
+    if (!d_plane || !col_ranges || !row_ranges || !d_ranges || !d_count || ((uintptr_t)d_ranges & 3) || ((uintptr_t)d_count & 3))
+        return fail(c, BQ_ERR_ARG, "bq_tissue_cells: bad argument");
+    const std::string bad = bad_cell_range("plane", col_ranges, gw, W, row_ranges, gh, H);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, "bq_tissue_cells: " + bad);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(c, s, "tissue_cells", 0.0, (double)H * W);
+    HIPCHK(c, hipMemcpyAsync(d_ranges, col_ranges, (size_t)gw * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_ranges + 2 * gw, row_ranges, (size_t)gh * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (launch_tissue_cells(d_plane, H, W, T, d_ranges, d_ranges + 2 * gw, gw, gh, d_count, s))
+        return fail(c, BQ_ERR_HIP, "tissue cells launch failed");
+    return BQ_OK;
+}
+
+}  // extern "C"

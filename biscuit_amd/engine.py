@@ -77,12 +77,7 @@ class Engine:
         blob = pack_blob(weights, dtype, self.act_exp)
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
         self._check(self._lib.bq_load_weights(self._ctx, C.cast(buf, C.c_void_p), len(blob)))
-        self._ws = self._inflate_ws = self._jpeg_ws = self._jpeg_enc_ws = None        # device buffers grown on demand (``_grown``)
-        self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
-        self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
-        self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
-        self._tissue_taps = {}           # sigma -> (the Gaussian's taps on the device, r) (tissue_focus)
-        self._host_held = []             # (event, host tables) of the calls the stream may not have passed yet (``_hold``)
+        self._drop_caches()
         self._elt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[dtype]
 
     # shapes of the stored tensors by debug-tap name
@@ -127,8 +122,16 @@ class Engine:
         if getattr(self, '_ctx', None):
             self._lib.bq_destroy(self._ctx)
             self._ctx = None
-            self._resample_taps, self._grayspace_limit, self._host_held = {}, {}, []
-            self._ws = self._inflate_ws = self._jpeg_ws = self._jpeg_enc_ws = None
+            self._drop_caches()
+
+    def _drop_caches(self):
+        """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
+        self._ws = self._inflate_ws = self._jpeg_ws = self._jpeg_enc_ws = None        # device buffers grown on demand (``_scratch``)
+        self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
+        self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
+        self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
+        self._tissue_taps = {}           # sigma -> (the Gaussian's taps on the device, r) (tissue_focus)
+        self._host_held = []             # (event, host tables) of the calls the stream may not have passed yet (``_hold``)
 
     def __del__(self):
         try:
@@ -160,16 +163,58 @@ class Engine:
             if (r[:, 0] < 0).any() or (r[:, 0] >= r[:, 1]).any() or (r[:, 1] > n).any():
                 raise ValueError(f'a {name} range is empty or outside the {h} x {w} plane')
 
-    def _grown(self, name, need):
-        """The cached device buffer ``self.<name>`` (a torch uint8 tensor), ``need`` bytes at least: the old one goes before the larger comes."""
+    def _on_device(self, name, t):
+        if not t.is_cuda or t.device != self.device:
+            raise ValueError(f'{name} must be on {self.device}, not {t.device}')
+
+    def _thumb_hw(self, thumb, same_device=False):
+        """(H, W) of a thumbnail, uint8 [H, W, 3] with ``H * W < 2^31``; ValueError otherwise (``same_device``: and for one elsewhere)."""
+        if not (torch.is_tensor(thumb) and thumb.dtype == torch.uint8 and thumb.dim() == 3 and thumb.shape[2] == 3):
+            raise ValueError('thumb must be uint8 [H, W, 3]')
+        if same_device:
+            self._on_device('thumb', thumb)
+        assert thumb.is_cuda and thumb.is_contiguous()
+        h, w = int(thumb.shape[0]), int(thumb.shape[1])
+        if h < 1 or w < 1 or h * w >= 1 << 31:
+            raise ValueError(f'a thumbnail has 1 <= H, W and H * W < 2^31, not {h} x {w}')
+        return h, w
+
+    def _plane_hw(self, name, plane, same_device=False):
+        """(H, W) of a mask's plane, uint8 [H, W] and not empty; ValueError otherwise (``same_device``: and for one elsewhere)."""
+        if not (torch.is_tensor(plane) and plane.dtype == torch.uint8 and plane.dim() == 2 and plane.numel() > 0):
+            raise ValueError(f'{name} must be uint8 [H, W]')
+        if same_device:
+            self._on_device(name, plane)
+        assert plane.is_cuda and plane.is_contiguous()
+        return int(plane.shape[0]), int(plane.shape[1])
+
+    @staticmethod
+    def _cell_tables(col, row):
+        """The cells' ranges as contiguous int32 [gw, 2] / [gh, 2] host arrays; ValueError for another shape."""
+        col, row = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(row, np.int32)
+        if col.ndim != 2 or col.shape[1] != 2 or row.ndim != 2 or row.shape[1] != 2 or len(col) < 1 or len(row) < 1:
+            raise ValueError('col and row must be int32 [gw, 2] and [gh, 2]')
+        return col, row
+
+    def _scratch(self, name, need, given=None):
+        """A call's scratch, ``need`` bytes: what the caller gave (launches that may overlap on different streams bring their own),
+        or the cached device buffer ``self.<name>`` (a torch uint8 tensor), where the old one goes before a larger one comes."""
+        if given is not None:
+            return given
         if getattr(self, name) is None or getattr(self, name).numel() < need:
             setattr(self, name, None)
-            setattr(self, name, torch.empty(need, dtype=torch.uint8, device=self.device))
+            setattr(self, name, torch.empty(int(need), dtype=torch.uint8, device=self.device))
         return getattr(self, name)
 
     def _ws_for(self, n, mc_n):
         """Caller-owned device workspace (a torch uint8 tensor), grown on demand."""
-        return self._grown('_ws', self._lib.bq_workspace_bytes(self._ctx, int(n), int(mc_n)))
+        return self._scratch('_ws', self._lib.bq_workspace_bytes(self._ctx, int(n), int(mc_n)))
+
+    def _mean_std(self, n, out):
+        """The (mean, std) pair of a call, float32 [n, 2] each on the device: ``out`` when the caller gave one."""
+        if out is not None:
+            return out
+        return tuple(torch.empty((n, 2), dtype=torch.float32, device=self.device) for _ in range(2))
 
     def set_num_cus(self, n):
         """Size the persistent kernels' grids for ``n`` compute units (``bq_set_num_cus``; 0: the whole device): what a context
@@ -214,8 +259,7 @@ class Engine:
         rows = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         need = int(self._lib.bq_png_inflate_scratch_bytes(n))
-        if scratch is None:                 # (launches that may overlap on different streams bring their own: ``inflate_scratch``)
-            scratch = self._grown('_inflate_ws', need)
+        scratch = self._scratch('_inflate_ws', need, scratch)         # (a caller's own: ``inflate_scratch(n)``)
         assert scratch.numel() >= need
         self._check(self._lib.bq_png_inflate(self._ctx, _ptr(z), _ptr(off), _ptr(length), n, px, _ptr(rows), stride,
                                              _ptr(scratch), scratch.numel(), _ptr(status), self._stream()))
@@ -252,8 +296,7 @@ class Engine:
         out = torch.empty((n, px, px, 3), dtype=torch.uint8, device=self.device)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         need = int(self._lib.bq_jpeg_scratch_bytes(n, px))
-        if scratch is None:
-            scratch = self._grown('_jpeg_ws', need)
+        scratch = self._scratch('_jpeg_ws', need, scratch)
         assert scratch.numel() >= need
         self._check(self._lib.bq_jpeg_decode(self._ctx, _ptr(scan), _ptr(desc), _ptr(tables), int(tables.shape[0]), n, px, _ptr(out),
                                              _ptr(status), _ptr(scratch), scratch.numel(), self._stream()))
@@ -281,8 +324,7 @@ class Engine:
         assert canvas.dtype == torch.uint8 and canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == 3 and canvas.shape[2] == 3
         x0, y0, x1, y1 = (int(v) for v in clip)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
-        if scratch is None:
-            scratch = self._grown('_jpeg_ws', int(self._lib.bq_jpeg_canvas_scratch_bytes(n, seg_w, seg_h)))
+        scratch = self._scratch('_jpeg_ws', int(self._lib.bq_jpeg_canvas_scratch_bytes(n, seg_w, seg_h)), scratch)
         assert scratch.is_cuda and scratch.is_contiguous()
         self._check(self._lib.bq_jpeg_decode_canvas(self._ctx, _ptr(scan), _ptr(desc), _ptr(tables), int(tables.shape[0]), n, seg_w, seg_h,
                                                     _ptr(place), _ptr(canvas), int(canvas.shape[0]), int(canvas.shape[1]), x0, y0, x1, y1,
@@ -310,8 +352,7 @@ class Engine:
         n, px, sub, quality = int(tiles.shape[0]), int(tiles.shape[1]), jpeg_subsampling(subsampling), int(quality)
         if cap is None:                     # (about 2 bits a sample at quality 95; the retry covers what this misses)
             cap = n * (1024 + px * px * 3 // (4 if quality < 98 else 2))
-        if scratch is None:
-            scratch = self._grown('_jpeg_enc_ws', int(self._lib.bq_jpeg_encode_scratch_bytes(n, max(px, 1), sub)))
+        scratch = self._scratch('_jpeg_enc_ws', int(self._lib.bq_jpeg_encode_scratch_bytes(n, max(px, 1), sub)), scratch)
         off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
         status = torch.zeros(n, dtype=torch.int32, device=self.device)
         self.jpeg_encode_calls = 0
@@ -413,12 +454,7 @@ class Engine:
         slide's thumbnail uint8 [H, W, 3] on this device -> (plane uint8 [H, W], the 7 x 7 median of its 8-bit saturation with a
         replicated border, and hist int32 [256], the plane's histogram), both on the device, the integers of the numpy
         restatement.  ``H * W < 2^31``; H or W below 7 are legal."""
-        if not (torch.is_tensor(thumb_u8) and thumb_u8.dtype == torch.uint8 and thumb_u8.dim() == 3 and thumb_u8.shape[2] == 3):
-            raise ValueError('thumb must be uint8 [H, W, 3]')
-        assert thumb_u8.is_cuda and thumb_u8.is_contiguous()
-        h, w = int(thumb_u8.shape[0]), int(thumb_u8.shape[1])
-        if h < 1 or w < 1 or h * w >= 1 << 31:
-            raise ValueError(f'a thumbnail has 1 <= H, W and H * W < 2^31, not {h} x {w}')
+        h, w = self._thumb_hw(thumb_u8)
         if self._tissue_sdiv is None:
             from . import tissue
             self._tissue_sdiv = torch.from_numpy(tissue.sdiv_table()).to(self.device)
@@ -433,13 +469,8 @@ class Engine:
         threshold ``T`` in 0 .. 255 and the cells' ranges ``col`` int32 [gw, 2] / ``row`` int32 [gh, 2] in plane pixels
         (``tissue.cell_ranges``; host arrays) -> int32 [gh, gw] on the device: the pixels with ``plane <= T`` in every cell.
         ValueError for a range that is empty or leaves the plane."""
-        if not (torch.is_tensor(plane) and plane.dtype == torch.uint8 and plane.dim() == 2 and plane.numel() > 0):
-            raise ValueError('plane must be uint8 [H, W]')
-        assert plane.is_cuda and plane.is_contiguous()
-        h, w = int(plane.shape[0]), int(plane.shape[1])
-        col, row = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(row, np.int32)
-        if col.ndim != 2 or col.shape[1] != 2 or row.ndim != 2 or row.shape[1] != 2 or len(col) < 1 or len(row) < 1:
-            raise ValueError('col and row must be int32 [gw, 2] and [gh, 2]')
+        h, w = self._plane_hw('plane', plane)
+        col, row = self._cell_tables(col, row)
         self._check_cells(T, col, row, h, w)
         gw, gh = len(col), len(row)
         ranges = torch.empty(2 * (gw + gh), dtype=torch.int32, device=self.device)
@@ -457,14 +488,7 @@ class Engine:
         out of focus iff ``V <= floor(threshold * FOCUS_SCALE)``.  ``H * W < 2^31``; H or W below the radius are legal.
         ValueError as ``tissue.check_focus``."""
         from . import tissue
-        if not (torch.is_tensor(thumb_u8) and thumb_u8.dtype == torch.uint8 and thumb_u8.dim() == 3 and thumb_u8.shape[2] == 3):
-            raise ValueError('thumb must be uint8 [H, W, 3]')
-        if not thumb_u8.is_cuda or thumb_u8.device != self.device:
-            raise ValueError(f'thumb must be on {self.device}, not {thumb_u8.device}')
-        assert thumb_u8.is_contiguous()
-        h, w = int(thumb_u8.shape[0]), int(thumb_u8.shape[1])
-        if h < 1 or w < 1 or h * w >= 1 << 31:
-            raise ValueError(f'a thumbnail has 1 <= H, W and H * W < 2^31, not {h} x {w}')
+        h, w = self._thumb_hw(thumb_u8, same_device=True)
         thr = tissue.focus_units(threshold)
         key = float(sigma)
         if key not in self._tissue_taps:
@@ -487,17 +511,9 @@ class Engine:
         focus plane over the Otsu plane; None: ``tissue.plane_map``'s nearest-neighbour resize.  ValueError for a range that is
         empty or leaves the plane, and for a map of the wrong length, outside the focus plane or decreasing."""
         from . import tissue
-        for name, p in (('otsu_plane', otsu_plane), ('focus_plane', focus_plane)):
-            if not (torch.is_tensor(p) and p.dtype == torch.uint8 and p.dim() == 2 and p.numel() > 0):
-                raise ValueError(f'{name} must be uint8 [H, W]')
-            if not p.is_cuda or p.device != self.device:
-                raise ValueError(f'{name} must be on {self.device}, not {p.device}')
-            assert p.is_contiguous()
-        ho, wo = int(otsu_plane.shape[0]), int(otsu_plane.shape[1])
-        hf, wf = int(focus_plane.shape[0]), int(focus_plane.shape[1])
-        col, row = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(row, np.int32)
-        if col.ndim != 2 or col.shape[1] != 2 or row.ndim != 2 or row.shape[1] != 2 or len(col) < 1 or len(row) < 1:
-            raise ValueError('col and row must be int32 [gw, 2] and [gh, 2]')
+        ho, wo = self._plane_hw('otsu_plane', otsu_plane, same_device=True)
+        hf, wf = self._plane_hw('focus_plane', focus_plane, same_device=True)
+        col, row = self._cell_tables(col, row)
         gw, gh = len(col), len(row)
         if gw > tissue.MAX_GRID or gh > tissue.MAX_GRID:
             raise ValueError(f'a grid is 1 .. {tissue.MAX_GRID} cells a side, not {gh} x {gw}')
@@ -621,11 +637,8 @@ class Engine:
         n = feat.shape[0]
         ws = self._ws_for(n, mc_n)
         state = torch.empty((n, 5), dtype=torch.float32, device=self.device)
-        if out is None:
-            mean = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-            std = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-        else:
-            mean, std = out
+        mean, std = self._mean_std(n, out)
+        if out is not None:
             assert mean.is_contiguous() and std.is_contiguous() and mean.shape == (n, 2) and std.shape == (n, 2)
         with self._tile_index_array(tile_idx, n):
             self._check(self._lib.bq_mc_head(self._ctx, _ptr(feat), n, int(tile_idx0), int(mc_n), 0,
@@ -665,11 +678,7 @@ class Engine:
         assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous()
         n = tiles_u8.shape[0]
         ws = self._ws_for(n, mc_n)
-        if out is None:
-            mean = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-            std = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-        else:
-            mean, std = out
+        mean, std = self._mean_std(n, out)
         mode = _lib.BQ_MC_HEAD if mc_mode == 'head' else _lib.BQ_MC_FULL
         with self._tile_index_array(tile_idx, n):
             self._check(self._lib.bq_mc_infer(self._ctx, _ptr(tiles_u8), n, int(tile_idx0), int(mc_n),
@@ -729,27 +738,20 @@ class Engine:
     def debug_activation(self, name, staged, shape_hwc, true_scale=True):
         """The named activation as fp32 [n,H,W,C]; with activation exponents (``act_exp``) the stored tensor times 2^k, i.e. the
         network's values, unless ``true_scale=False``."""
-        n = staged.shape[0]
-        ws = self._ws_for(n, 1)
-        h, w, c = shape_hwc
-        out = torch.empty((n, h, w, c), dtype=torch.float32, device=self.device)
-        rc = self._lib.bq_debug_activation(self._ctx, name.encode(), _ptr(staged), n, _ptr(ws), ws.numel(),
-                                           _ptr(out), out.numel(), self._stream())
-        self._check(rc)
-        assert rc == out.numel(), (rc, out.numel())
-        k = self._tap_exp.get(name, 0)
-        return out * float(2.0 ** k) if (k and true_scale) else out
+        return self._debug_tap(self._lib.bq_debug_activation, name, staged, shape_hwc, true_scale)
 
     def debug_activation_u8(self, name, tiles_u8, shape_hwc, true_scale=True):
         """The same tap on the path ``mc_infer`` takes in a 16-bit context: uint8 tiles [n,299,299,3] through the fused front
         kernel (standardise + block1_conv1 + block1_conv2 in one launch), then the network up to ``name``."""
         assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous()
-        n = tiles_u8.shape[0]
+        return self._debug_tap(self._lib.bq_debug_activation_u8, name, tiles_u8, shape_hwc, true_scale)
+
+    def _debug_tap(self, entry, name, src, shape_hwc, true_scale):
+        n = src.shape[0]
         ws = self._ws_for(n, 1)
         h, w, c = shape_hwc
         out = torch.empty((n, h, w, c), dtype=torch.float32, device=self.device)
-        rc = self._lib.bq_debug_activation_u8(self._ctx, name.encode(), _ptr(tiles_u8), n, _ptr(ws), ws.numel(),
-                                              _ptr(out), out.numel(), self._stream())
+        rc = entry(self._ctx, name.encode(), _ptr(src), n, _ptr(ws), ws.numel(), _ptr(out), out.numel(), self._stream())
         self._check(rc)
         assert rc == out.numel(), (rc, out.numel())
         k = self._tap_exp.get(name, 0)
@@ -776,33 +778,30 @@ class Engine:
         through tapped layers and returns ``{'max_abs': {layer: value}, 'saturated': {layer: count}, 'headroom': min over
         layers of limit / max_abs}``; a caller loading real weights should call it once (the CLI does, on its first tiles)
         and fall back to bf16 or fp32 if anything saturates.  Meaningless (inf headroom) for the other storage types."""
-        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda
-        t = tiles_u8[:min(8, tiles_u8.shape[0], self.max_batch)].contiguous()
         out = {'max_abs': {}, 'saturated': {}, 'headroom': float('inf'), 'dtype': self.dtype}
-        if self.dtype != 'f16' or t.shape[0] == 0:
-            return out
-        for name, shp in self.HEADROOM_TAPS:
-            a = self.debug_activation_u8(name, t, shp, true_scale=False)       # as stored: what the range limit applies to
-            m = float(a.abs().max())
+        for name, a in self._headroom_taps(tiles_u8):
+            m = float(a.max())
             out['max_abs'][name] = m
-            out['saturated'][name] = int((a.abs() >= limit).sum())
+            out['saturated'][name] = int((a >= limit).sum())
             out['headroom'] = min(out['headroom'], limit / max(m, 1e-30))
         return out
+
+    def _headroom_taps(self, tiles_u8):
+        """The tap loop of both monitors: (layer, |activation| as stored -- what the range limit applies to) for every one of
+        ``HEADROOM_TAPS`` on up to eight of ``tiles_u8``; nothing for the other storage types or without tiles."""
+        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda
+        t = tiles_u8[:min(8, tiles_u8.shape[0], self.max_batch)].contiguous()
+        if self.dtype == 'f16' and t.shape[0] > 0:
+            for name, shp in self.HEADROOM_TAPS:
+                yield name, self.debug_activation_u8(name, t, shp, true_scale=False).abs_()
 
     def f16_headroom_async(self, tiles_u8, limit=65504.0):
         """``f16_headroom`` without a host synchronisation, for a monitor inside a running loop (``inference.evaluate``'s
         ``headroom_every``): the eight taps on up to eight of ``tiles_u8``, everything enqueued on the current stream; returns a
         device tensor float32 [8, 2] -- per tap (max |activation| as stored, number of values at the clamp) -- that the caller
         copies out and looks at later.  None for the other storage types."""
-        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda
-        t = tiles_u8[:min(8, tiles_u8.shape[0], self.max_batch)].contiguous()
-        if self.dtype != 'f16' or t.shape[0] == 0:
-            return None
-        rows = []
-        for name, shp in self.HEADROOM_TAPS:
-            a = self.debug_activation_u8(name, t, shp, true_scale=False).abs_()
-            rows.append(torch.stack([a.max(), (a >= limit).sum().to(torch.float32)]))
-        return torch.stack(rows)
+        rows = [torch.stack([a.max(), (a >= limit).sum().to(torch.float32)]) for _, a in self._headroom_taps(tiles_u8)]
+        return torch.stack(rows) if rows else None
 
     def range_key(self, tiles_u8):
         """The range screen's key of every tile (``bq_range_key``): uint8 NHWC [n,299,299,3] (device, any byte offset) -> float32
@@ -958,21 +957,13 @@ class EnginePool:
                 raise BiscuitHipError(f'reserve_cus must lie in [8, {ncu_all // 2}]')
             self.decode_streams = [_mask_stream(self.engines[0], range(ncu, ncu_all), ncu_all) for _ in range(max(1, self._n_decode_streams))]
         for k in range(nst):
-            eng = self.engines[k]
-            bits = [0] * ((ncu_all + 31) // 32)
-            for cu in range(ncu):
-                if split == 'contig':
-                    mine = cu * nst // ncu == k
-                elif split == 'xcd':              # bit i -> XCD i % 8 (experiment)
-                    mine = (cu % 8) * nst // 8 == k
-                else:
-                    mine = (cu % nst) == k
-                if mine:
-                    bits[cu // 32] |= 1 << (cu % 32)
-            arr = (C.c_uint32 * len(bits))(*bits)
-            h = C.c_void_p()
-            eng._check(eng._lib.bq_stream_create_masked(eng._ctx, arr, len(bits), C.byref(h)))
-            streams.append(torch.cuda.ExternalStream(h.value, device=dev))
+            if split == 'contig':
+                mine = [cu for cu in range(ncu) if cu * nst // ncu == k]
+            elif split == 'xcd':              # bit i -> XCD i % 8 (experiment)
+                mine = [cu for cu in range(ncu) if (cu % 8) * nst // 8 == k]
+            else:
+                mine = [cu for cu in range(ncu) if cu % nst == k]
+            streams.append(_mask_stream(self.engines[k], mine, ncu_all))
         return streams
 
     def close(self):

@@ -25,6 +25,9 @@
  * synchronisation (except bq_profile_read).  Return 0 on success, <0 on error; the
  * message is available from bq_last_error.  One context per device per process; a
  * context is not re-entrant.  No C++ exception crosses this boundary.
+ *
+ * Where the definitions are: the context, the weights, the network calls and the profile in csrc/biscuit_hip.hip; every other
+ * entry point in the csrc/kernels_*.hip of the kernel it launches (csrc/bq_ctx.h is the context they share).
  */
 #ifndef BISCUIT_HIP_H
 #define BISCUIT_HIP_H
@@ -102,7 +105,7 @@ int bq_set_num_cus(bq_ctx* ctx, int n);
  * buffer (global memory / L2): the fallback, 2-3 x slower (profiles/r05_inflate.txt).  Anything else: BQ_ERR_ARG. */
 int bq_set_option(bq_ctx* ctx, const char* name, int value);
 
-/* K0, optional front half: the `reinhard_fast` stain normaliser hp.py:19 selects, applied to the
+/* K0, optional front half (kernels_reinhard.hip): the `reinhard_fast` stain normaliser hp.py:19 selects, applied to the
  * uint8 tile before the standardisation exactly where results.py:251-252 calls
  * interface.wsi_normalizer.rgb_to_rgb(image).  uint8 NHWC [n,px,px,3] -> uint8 NHWC; d_out may equal
  * d_tiles.  target_means3 / target_stds3 are HOST pointers to the model's params.json `norm_fit`

@@ -36,6 +36,22 @@ def test_abi_symbols_exported():
             Engine({}, dtype='bf16')
 
 
+def test_the_library_defines_exactly_the_abi():
+    """The dynamic symbols of libbiscuit_hip.so that begin with ``bq_`` are the ABI and nothing else, whichever file of csrc/
+    defines each: an entry point that a move lost, or a helper that took the prefix, shows here without a GPU."""
+    import shutil
+    import subprocess
+    from biscuit_amd import _lib
+    rocm = os.environ.get('ROCM_PATH', '/opt/rocm')
+    tools = [shutil.which('nm'), shutil.which('llvm-nm'), os.path.join(rocm, 'llvm', 'bin', 'llvm-nm')]
+    nm = next((t for t in tools if t and os.path.exists(t)), None)
+    assert nm, 'neither nm nor llvm-nm found: the exported symbols cannot be listed'
+    out = subprocess.run([nm, '-D', '--defined-only', _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    defined = {line.split()[-1].split('@')[0] for line in out.splitlines() if line.split()}
+    exported = {s for s in defined if s.startswith('bq_')}
+    assert exported == set(_lib.ABI), exported ^ set(_lib.ABI)
+
+
 def test_missing_library_is_an_error(tmp_path):
     from biscuit_amd import _lib
     with pytest.raises(ImportError):
