@@ -27,8 +27,35 @@ def canonical(E):
     return E
 
 
-def stats(img, canonicalise=True):
-    """dict(status, n_tissue, HE [3,2] or None, maxC [2] or None, C [2,N] or None) of one tile."""
+def pinv2(HE):
+    """(det(HE^T HE), pinv(HE) [2,3] = (HE^T HE)^-1 HE^T) in float64, the closed form the kernel states."""
+    M = HE.T.dot(HE)
+    det = M[0, 0] * M[1, 1] - M[0, 1] * M[1, 0]
+    with np.errstate(all='ignore'):
+        P = np.array([[M[1, 1], -M[0, 1]], [-M[1, 0], M[0, 0]]]).dot(HE.T) / det
+    return det, P
+
+
+def _project32(OD, A):
+    """[N,k] float32: OD [N,3] and A [3,k] rounded to float32, each product and each sum rounded to float32, left to right."""
+    x, a = OD.astype(np.float32), A.astype(np.float32)
+    return (x[:, 0:1] * a[0] + x[:, 1:2] * a[1]) + x[:, 2:3] * a[2]
+
+
+def concentrations(OD, HE, per_pixel=np.float64):
+    """[2,N]: lstsq(HE, OD) in float64, or under the kernel's precision contract (per_pixel=np.float32): pinv(HE) in float64,
+    rounded to float32, applied in float32."""
+    if per_pixel is np.float64:
+        return np.linalg.lstsq(HE, OD.T, rcond=None)[0]
+    return _project32(OD, pinv2(HE)[1].T).T
+
+
+def stats(img, canonicalise=True, per_pixel=np.float64):
+    """dict(status, n_tissue, HE [3,2] or None, maxC [2] or None, C [2,N] or None, phi [n_tissue], E [3,2], evals [3],
+    minPhi, maxPhi) of one tile.  per_pixel=np.float32 follows the kernel's precision contract: the OD table, E and pinv(HE)
+    rounded to float32, products, sums and arctan2 in float32, everything else (the tissue statistics, the eigenproblem, the
+    percentile interpolation, HE, pinv) in float64."""
+    assert per_pixel in (np.float64, np.float32)
     OD = optical_density(img)
     ODhat = OD[~np.any(OD < S.MACENKO_BETA, axis=1)]
     res = {'status': OK, 'n_tissue': int(ODhat.shape[0]), 'HE': None, 'maxC': None, 'C': None}
@@ -36,24 +63,30 @@ def stats(img, canonicalise=True):
         res['status'] = FEW_TISSUE
         return res
     with np.errstate(all='ignore'):
-        _, V = np.linalg.eigh(np.cov(ODhat.T))
+        evals, V = np.linalg.eigh(np.cov(ODhat.T))
         E = V[:, 1:3]
         if canonicalise:
             E = canonical(E)
-        That = ODhat.dot(E)
-        phi = np.arctan2(That[:, 1], That[:, 0])
+        if per_pixel is np.float64:
+            That = ODhat.dot(E)
+            phi = np.arctan2(That[:, 1], That[:, 0])
+        else:
+            That = _project32(ODhat, E)
+            phi = np.arctan2(That[:, 1], That[:, 0]).astype(np.float64)
         minPhi = np.percentile(phi, S.MACENKO_ALPHA)
         maxPhi = np.percentile(phi, 100 - S.MACENKO_ALPHA)
+        res.update(phi=phi, E=E, evals=evals, minPhi=float(minPhi), maxPhi=float(maxPhi))
         vMin = E.dot(np.array([np.cos(minPhi), np.sin(minPhi)]))
         vMax = E.dot(np.array([np.cos(maxPhi), np.sin(maxPhi)]))
         HE = np.array((vMin, vMax)).T if vMin[0] > vMax[0] else np.array((vMax, vMin)).T
         res['HE'] = HE
         M = HE.T.dot(HE)
         det = M[0, 0] * M[1, 1] - M[0, 1] * M[1, 0]
+        res['det'] = float(det)
         if abs(det) < S.MACENKO_DET_MIN:
             res['status'] = SINGULAR
             return res
-        C = np.linalg.lstsq(HE, OD.T, rcond=None)[0]
+        C = concentrations(OD, HE, per_pixel).astype(np.float64)
         maxC = np.array([np.percentile(C[0, :], S.MACENKO_CONC_PCT), np.percentile(C[1, :], S.MACENKO_CONC_PCT)])
     res['maxC'], res['C'] = maxC, C
     if not (np.isfinite(HE).all() and np.isfinite(maxC).all() and (maxC > 0).all()):
@@ -61,15 +94,31 @@ def stats(img, canonicalise=True):
     return res
 
 
+def transform(img, HE, maxC, he_ref=HE_REF, maxc_ref=MAXC_REF, per_pixel=np.float64):
+    """uint8 tile: ``img`` normalised to the fit (he_ref, maxc_ref) given its statistics HE [3,2] and maxC [2].
+    per_pixel=np.float32: the kernel's precision contract (he_ref, maxc_ref and the scale maxc_ref / maxC as float32)."""
+    OD = optical_density(img)
+    HE, maxC = np.asarray(HE, np.float64), np.asarray(maxC, np.float64)
+    with np.errstate(over='ignore'):
+        if per_pixel is np.float64:
+            C2 = concentrations(OD, HE) / (maxC / np.asarray(maxc_ref, np.float64))[:, None]
+            Inorm = S.MACENKO_IO * np.exp(-np.asarray(he_ref, np.float64).dot(C2))
+        else:
+            f = np.float32
+            scale = (np.asarray(maxc_ref, f).astype(np.float64) / maxC).astype(f)
+            C2 = concentrations(OD, HE, f) * scale[:, None]
+            h = np.asarray(he_ref, f)
+            Inorm = f(S.MACENKO_IO) * np.exp(-(h[:, 0:1] * C2[0] + h[:, 1:2] * C2[1]))
+    Inorm[Inorm > 255] = S.MACENKO_OVER_TO
+    return np.reshape(Inorm.T, img.shape).astype(np.uint8)
+
+
 def normalise(img, he_ref=HE_REF, maxc_ref=MAXC_REF):
     """(uint8 tile, status): the tile normalised to the fit (he_ref, maxc_ref), or unchanged when degenerate."""
     st = stats(img)
     if st['status'] != OK:
         return img.copy(), st['status']
-    C2 = st['C'] / (st['maxC'] / np.asarray(maxc_ref, np.float64))[:, None]
-    Inorm = S.MACENKO_IO * np.exp(-np.asarray(he_ref, np.float64).dot(C2))
-    Inorm[Inorm > 255] = S.MACENKO_OVER_TO
-    return np.reshape(Inorm.T, img.shape).astype(np.uint8), OK
+    return transform(img, st['HE'], st['maxC'], he_ref, maxc_ref), OK
 
 
 def angle_deg(a, b):
