@@ -126,7 +126,7 @@ class Engine:
 
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
-        self._ws = self._inflate_ws = self._jpeg_ws = self._jpeg_enc_ws = None        # device buffers grown on demand (``_scratch``)
+        self._ws = self._inflate_ws = self._jpeg_ws = self._jpeg_enc_ws = self._png_enc_ws = None        # device buffers grown on demand (``_scratch``)
         self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
         self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
         self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
@@ -374,6 +374,41 @@ class Engine:
         from .tfrecord_native import jpeg_subsampling
         return torch.empty(int(self._lib.bq_jpeg_encode_scratch_bytes(int(n), int(px), jpeg_subsampling(subsampling))), dtype=torch.uint8,
                            device=self.device)
+
+    def png_encode(self, tiles, cap=None, scratch=None):
+        """n tiles encoded as PNG on the device (``bq_png_encode``, kernels_png_encode.hip): ``tiles`` uint8 NHWC [n, px, px, 3]
+        on this device -> ``(buffer, offsets)``: buffer uint8 [bytes] on the device, offsets int64 [n + 1] on the host; file i =
+        ``buffer[offsets[i]:offsets[i + 1]]``, a complete PNG whose filtered rows are Pillow's and whose deflate stream is
+        the library's own (``tfrecord_native.png_encode`` writes the same bytes on the CPU).  Lossless, no settings.  ``cap``:
+        bytes of the output buffer to try first (None: half the raw size, which a tissue tile stays under); when the files
+        do not fit (status bit 1) the call is repeated once with the exact total, which the first call's offsets state.
+        Reading the offsets waits for the stream.  ``scratch``: ``png_encode_scratch(n, px)`` or smaller (more rounds), at least
+        one tile's."""
+        assert tiles.dtype == torch.uint8 and tiles.is_cuda and tiles.is_contiguous() and tiles.dim() == 4
+        assert tiles.shape[1] == tiles.shape[2] and tiles.shape[3] == 3, tuple(tiles.shape)
+        n, px = int(tiles.shape[0]), int(tiles.shape[1])
+        if cap is None:
+            cap = n * (1024 + px * px * 3 // 2)
+        scratch = self._scratch('_png_enc_ws', int(self._lib.bq_png_encode_scratch_bytes(n, max(px, 1))), scratch)
+        off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.png_encode_calls = 0
+        while True:
+            out = torch.empty(max(int(cap), 1), dtype=torch.uint8, device=self.device)
+            self._check(self._lib.bq_png_encode(self._ctx, _ptr(tiles), n, px, _ptr(out), int(cap), _ptr(off), _ptr(status), _ptr(scratch),
+                                                scratch.numel(), self._stream()))
+            self.png_encode_calls += 1
+            offsets = off.cpu()
+            total = int(offsets[-1])
+            if n == 0 or total <= int(cap):
+                return out[:total], offsets
+            assert self.png_encode_calls == 1 and bool((status & 1).any()), 'bq_png_encode: the exact total did not fit'
+            cap = total
+
+    def png_encode_scratch(self, n, px=TILE_PX):
+        """Scratch for ``png_encode`` over ``n`` tiles (``bq_png_encode_scratch_bytes``: 1.71 MB per 299-px tile, for 128 tiles at
+        most -- 218 MB; a longer call works in rounds)."""
+        return torch.empty(int(self._lib.bq_png_encode_scratch_bytes(int(n), int(px))), dtype=torch.uint8, device=self.device)
 
     def tile_resample(self, canvas, origin, src_px, px=TILE_PX, out=None):
         """The heatmap's tile grid cut from a slide canvas and resampled on the device (``bq_tile_resample``,

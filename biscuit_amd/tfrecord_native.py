@@ -48,6 +48,8 @@ ABI = {
     'bqio_jpeg_encode_header': (_i, [_i, _i, _i, _vp]),
     'bqio_jpeg_encode_header_bytes': (C.c_size_t, []),
     'bqio_jpeg_encode_last_error': (C.c_char_p, []),
+    'bqio_png_encode': (_i, [_vp, _i64, _i, _vp, C.c_size_t, _vp, _vp]),
+    'bqio_png_encode_last_error': (C.c_char_p, []),
     'bqio_masked_crc32c': (C.c_uint32, [C.c_char_p, C.c_size_t]),
     'bqio_inflate': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t]),
     'bqio_inflate2': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t, C.c_char_p, C.c_size_t, _vp, C.c_size_t,
@@ -245,6 +247,30 @@ def jpeg_encode(tiles, quality=95, subsampling='4:2:0', cap=None):
                                    off.ctypes.data, status.ctypes.data)
         if e != 0:
             raise ValueError('bqio_jpeg_encode: ' + lib().bqio_jpeg_encode_last_error().decode())
+    if cap is None:
+        call(None, 0)
+        cap = int(off[-1])
+    out = np.zeros(max(int(cap), 1), np.uint8)
+    call(out, int(cap))
+    return out[:int(cap)], off, status
+
+
+def png_encode(tiles, cap=None):
+    """uint8 [n, px, px, 3] -> ``(buffer uint8 [bytes], offsets int64 [n + 1], status int32 [n])``: complete PNG files back to
+    back (``bqio_png_encode``: the device encoder's routines, csrc/png_encode_device.h, on the CPU).  The filtered rows are
+    Pillow's; the deflate stream is the project's own.  ``cap``: the buffer's size; None sizes it exactly with a first call.  A
+    file that would end beyond ``cap`` is left out and its status is 1.  ValueError outside 1 <= px <= 4096.  What
+    ``Engine.png_encode`` computes, byte for byte.  For tests."""
+    tiles = np.ascontiguousarray(tiles, np.uint8)
+    assert tiles.ndim == 4 and tiles.shape[1] == tiles.shape[2] and tiles.shape[3] == 3, tiles.shape
+    n, px = tiles.shape[0], tiles.shape[1]
+    off, status = np.zeros(n + 1, np.int64), np.zeros(n, np.int32)
+
+    def call(out, cap):
+        e = lib().bqio_png_encode(tiles.ctypes.data, n, px, out.ctypes.data if out is not None else None, cap, off.ctypes.data,
+                                  status.ctypes.data)
+        if e != 0:
+            raise ValueError('bqio_png_encode: ' + lib().bqio_png_encode_last_error().decode())
     if cap is None:
         call(None, 0)
         cap = int(off[-1])

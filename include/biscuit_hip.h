@@ -240,6 +240,30 @@ size_t bq_jpeg_encode_scratch_bytes(int n, int px, int subsampling);
 int bq_jpeg_encode(bq_ctx* ctx, const uint8_t* d_tiles, int n, int px, int quality, int subsampling, uint8_t* d_out, int64_t cap,
                    int64_t* d_off, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
 
+/* Output side, PNG tiles, encoded on the device (kernels_png_encode.hip; DESIGN.md "Tile extraction"): n tiles d_tiles uint8
+ * [n][px][px][3] become COMPLETE PNG files -- signature, IHDR (8-bit, colour type 2, no interlace), IDAT chunks of 8 192 bytes
+ * that together hold one zlib stream (32 KB window, Adler-32), IEND, a CRC-32 on every chunk, no ancillary chunk -- back to back in
+ * d_out: file i = d_out[d_off[i] .. d_off[i + 1]), d_off int64 [n + 1] (device memory, 8-byte aligned) with d_off[0] = 0.  The
+ * filtered scanlines are the ones Pillow writes, byte for byte (per row None, Up, Sub, Paeth in that order by the sum of |int8|,
+ * strictly smaller wins); the deflate stream is this library's own: blocks of 16 384 filtered bytes that share nothing, greedy
+ * matching against a 3-byte hash table in groups of 64 positions (a match is taken from 5 bytes on), per block the smallest of
+ * dynamic, fixed and stored.  There is no quality: a tile has exactly one encoding, bqio_png_encode's byte for byte, whatever n,
+ * the tile's place in the batch or the scratch size.  px 1..4096 -- anything else returns BQ_ERR_ARG with bq_last_error set and
+ * launches nothing.  Four stages, each timed as its own class under bq_profile_*: filter (one wave per row: scores, choice,
+ * filtered bytes, Adler sums), match (one wave per block: tokens and histogram), code (one wave per block: length-limited Huffman
+ * lengths, header, the three sizes; one wave per tile: bit offsets), pack (every token's bits at its own offset through atomicOr,
+ * the file lengths scanned into d_off, the zlib bytes copied between the chunk frames, one wave per chunk for its CRC).
+ * d_status[i] = 0, or 1 when file i would end beyond `cap` (the bytes of d_out): that file and the ones behind it are not written,
+ * d_off still holds every exact length, so the caller repeats the call with a buffer that fits (cap = 0 with d_out = NULL sizes a
+ * call).  A file is at most L + L / 256 + 128 bytes, L = px (1 + 3 px).  Scratch (16-byte aligned): the filtered stream, 4 bytes of
+ * token per input byte, codes, headers and the deflate buffer, 1 707 536 bytes per 299-px tile; bq_png_encode_scratch_bytes(n, px)
+ * asks for min(n, 128) tiles' worth and the call works in rounds of as many tiles as d_scratch holds -- one at least,
+ * BQ_ERR_WORKSPACE below that.  Everything is enqueued on `stream`; the library allocates nothing and does not wait for the
+ * device; n = 0 returns 0 without a launch.  The reference's counterpart is extract_tiles(img_format='png'). */
+size_t bq_png_encode_scratch_bytes(int n, int px);
+int bq_png_encode(bq_ctx* ctx, const uint8_t* d_tiles, int n, int px, uint8_t* d_out, int64_t cap, int64_t* d_off, int32_t* d_status,
+                  void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
+
 /* The whole-slide heatmap's input stage (kernels_resample.hip; DESIGN.md "Heatmap input"): n tiles cut out of a slide canvas in
  * device memory and resampled to px x px -- what sf.Heatmap's slide reader does per tile on the host (results.py:217).  d_canvas
  * uint8 [H][W][3]; tile t is the src_px x src_px window at (d_origin[2 t], d_origin[2 t + 1]) = (x, y) (int32; windows may

@@ -179,6 +179,17 @@ int bqio_jpeg_encode_header(int px, int quality, int subsampling, uint8_t* out);
 size_t bqio_jpeg_encode_header_bytes(void);
 const char* bqio_jpeg_encode_last_error(void);
 
+/* The CPU build of bq_png_encode (include/biscuit_hip.h; csrc/png_encode_host.cpp over csrc/png_encode_device.h, the routines the
+ * GPU kernels are compiled from): n tiles uint8 [n][px][px][3] -> complete PNG files (signature, IHDR 8-bit colour type 2, IDAT
+ * chunks of 8 192 zlib bytes, IEND), back to back in `out`: file i = out[off[i] .. off[i + 1]), off int64 [n + 1] with off[0] =
+ * 0.  The filtered rows are Pillow's byte for byte; the deflate stream is this project's (blocks of 16 384 input bytes, greedy
+ * hash matching in groups of 64, per-block dynamic / fixed / stored) and is what bq_png_encode writes, byte for byte.  There is no
+ * quality: a tile has one encoding.  A file that would end beyond `cap` is not written and status[i] = 1 (0 otherwise); off still
+ * holds the exact lengths, so cap = 0 with out = NULL sizes a call.  BQIO_ERR_ARG, with nothing written, for px outside 1..4096 or
+ * a null pointer; bqio_png_encode_last_error() then says which.  For tests. */
+int bqio_png_encode(const uint8_t* tiles, int64_t n, int px, uint8_t* out, size_t cap, int64_t* off, int32_t* status);
+const char* bqio_png_encode_last_error(void);
+
 /* One JPEG file (as bqio_image_bytes returns it) -> out[tile_px][tile_px][3], the decoder
  * bqio_decode uses, exported for tests.  BQIO_OK / BQIO_ERR_UNSUPPORTED / BQIO_ERR_FORMAT. */
 int bqio_decode_jpeg(const uint8_t* data, size_t len, int tile_px, uint8_t* out);
