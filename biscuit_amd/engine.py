@@ -126,7 +126,7 @@ class Engine:
 
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
-        self._ws = self._inflate_ws = self._jpeg_ws = self._jpeg_enc_ws = self._png_enc_ws = None        # device buffers grown on demand (``_scratch``)
+        self._ws = self._inflate_ws = self._jpeg_ws = self._j2k_ws = self._jpeg_enc_ws = self._png_enc_ws = None        # device buffers grown on demand (``_scratch``)
         self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
         self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
         self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
@@ -336,6 +336,36 @@ class Engine:
         """Coefficient space for ``jpeg_decode_canvas`` over ``n`` segments (``bq_jpeg_canvas_scratch_bytes``: 393 KB per 256 x 256
         segment, for 2 048 segments at most; a longer call works in rounds)."""
         return torch.empty(int(self._lib.bq_jpeg_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h))), dtype=torch.uint8,
+                           device=self.device)
+
+    def j2k_decode_canvas(self, desc, blocks, cw, seg_w, seg_h, place, canvas, clip, ycc=False, scratch=None):
+        """A slide page's own JPEG 2000 tiles decoded on the device INTO a canvas (``bq_j2k_decode_canvas``, kernels_j2k.hip: tier
+        1 a lane per code block, the inverse wavelet transform a workgroup per segment and component, then a colour-and-place
+        kernel): ``desc`` int32 [n, 32], ``blocks`` int32 [k, 12] and ``cw`` uint8 [bytes] as ``tfrecord_native.j2k_extract``
+        packed the ``seg_w`` x ``seg_h`` segments; ``place``, ``canvas`` and ``clip`` as ``jpeg_decode_canvas`` takes them;
+        ``ycc``: the samples are YCbCr (TIFF compression 33003) -- all tensors on this device.  Returns status int32 [n] on the
+        device, 0 where the segment decoded; any other segment wrote nothing.  ``scratch``: at least one segment's
+        (``j2k_canvas_scratch(n, seg_w, seg_h)`` holds a whole round); the call works in rounds of as many as it holds."""
+        n, seg_w, seg_h = int(desc.shape[0]), int(seg_w), int(seg_h)
+        assert desc.dtype == torch.int32 and desc.is_cuda and desc.is_contiguous() and tuple(desc.shape) == (n, 32)
+        assert blocks.dtype == torch.int32 and blocks.is_cuda and blocks.is_contiguous() and blocks.dim() == 2 and blocks.shape[1] == 12
+        assert cw.dtype == torch.uint8 and cw.is_cuda and cw.is_contiguous()
+        assert place.dtype == torch.int32 and place.is_cuda and place.is_contiguous() and tuple(place.shape) == (n, 2)
+        assert canvas.dtype == torch.uint8 and canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == 3 and canvas.shape[2] == 3
+        x0, y0, x1, y1 = (int(v) for v in clip)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        scratch = self._scratch('_j2k_ws', int(self._lib.bq_j2k_canvas_scratch_bytes(n, seg_w, seg_h)), scratch)
+        assert scratch.is_cuda and scratch.is_contiguous()
+        self._check(self._lib.bq_j2k_decode_canvas(self._ctx, _ptr(desc), n, _ptr(blocks), int(blocks.shape[0]), _ptr(cw), cw.numel(),
+                                                   seg_w, seg_h, int(bool(ycc)), _ptr(place), _ptr(canvas), int(canvas.shape[0]),
+                                                   int(canvas.shape[1]), x0, y0, x1, y1, _ptr(status), _ptr(scratch),
+                                                   scratch.numel() * scratch.element_size(), self._stream()))
+        return status
+
+    def j2k_canvas_scratch(self, n, seg_w, seg_h):
+        """Plane space for ``j2k_decode_canvas`` over ``n`` segments (``bq_j2k_canvas_scratch_bytes``: 24 bytes a pixel, 1.5 MB per
+        256 x 256 segment, for 256 segments at most; a longer call works in rounds)."""
+        return torch.empty(int(self._lib.bq_j2k_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h))), dtype=torch.uint8,
                            device=self.device)
 
     def jpeg_encode(self, tiles, quality=95, subsampling='4:2:0', cap=None, scratch=None):

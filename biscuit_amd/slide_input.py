@@ -145,10 +145,12 @@ def band_stats():
 
 
 def decode_band(engine, sg):
-    """A band's canvas decoded on the device from its raw JPEG tiles (``wsi.BandSegments``): extract on the host, upload
-    scan, descriptors, tables and places, fill the canvas with 255, decode, read the status once.  -> the canvas (uint8
-    [H, W, 3] on the device), or None when the extractor refuses a segment or any status is not 0."""
+    """A band's canvas decoded on the device from its raw JPEG or JPEG 2000 tiles (``wsi.BandSegments``, by its ``codec``):
+    extract on the host, upload what the extractor packed and the places, fill the canvas with 255, decode, read the status
+    once.  -> the canvas (uint8 [H, W, 3] on the device), or None when the extractor refuses a segment or any status is not 0."""
     from . import tfrecord_native as tn
+    if sg.codec == 'j2k':
+        return decode_band_j2k(engine, sg)
     try:
         scan, desc, tables = tn.extract_jpeg_segments(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h, sg.jpeg_tables)
     except ValueError:                                                       # (UnsupportedImage is one)
@@ -160,6 +162,25 @@ def decode_band(engine, sg):
     status = engine.jpeg_decode_canvas(torch.from_numpy(scan).to(dev), torch.from_numpy(desc.view(np.int32)).to(dev),
                                        torch.from_numpy(tables).to(dev), sg.seg_w, sg.seg_h, torch.from_numpy(sg.place).to(dev),
                                        canvas, sg.clip)
+    return None if bool(status.any().item()) else canvas
+
+
+def decode_band_j2k(engine, sg):
+    """``decode_band`` for JPEG 2000 segments: tier 2 on the host (``tfrecord_native.j2k_extract``), the rest on the device
+    (``Engine.j2k_decode_canvas``)."""
+    from . import tfrecord_native as tn
+    if sg.seg_w > 512 or sg.seg_h > 512:
+        return None
+    try:
+        desc, blocks, cw = tn.j2k_extract(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h)
+    except ValueError:                                                       # outside the device's subset, or damaged
+        return None
+    dev = engine.device
+    canvas = torch.full(tuple(sg.shape) + (3,), 255, dtype=torch.uint8, device=dev)
+    if len(sg) == 0:
+        return canvas
+    status = engine.j2k_decode_canvas(torch.from_numpy(desc).to(dev), torch.from_numpy(blocks).to(dev), torch.from_numpy(cw).to(dev),
+                                      sg.seg_w, sg.seg_h, torch.from_numpy(sg.place).to(dev), canvas, sg.clip, ycc=sg.ycc)
     return None if bool(status.any().item()) else canvas
 
 

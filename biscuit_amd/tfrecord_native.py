@@ -40,6 +40,12 @@ ABI = {
     'bqio_extract_jpeg_segments': (_i, [_vp, C.c_size_t, _vp, _vp, _i64, _vp, C.c_size_t, _i, _i, _vp, C.c_size_t, _vp, _vp, _i,
                                         C.POINTER(_i), C.POINTER(C.c_size_t), _i, C.POINTER(_i64)]),
     'bqio_jpeg_decode_canvas': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i]),
+    'bqio_j2k_seg_bytes': (C.c_size_t, []),
+    'bqio_j2k_block_bytes': (C.c_size_t, []),
+    'bqio_j2k_extract': (_i, [_vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _vp, _vp, _i64, _vp, C.c_size_t, C.POINTER(_i64),
+                              C.POINTER(C.c_size_t), _i]),
+    'bqio_j2k_decode_canvas': (_i, [_vp, _i, _vp, _i64, _vp, C.c_size_t, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i]),
+    'bqio_ycc_to_rgb': (None, [_vp, _vp, C.c_size_t]),
     'bqio_resample_ksize': (_i, [_i, _i]),
     'bqio_resample_taps': (_i, [_i, _i, _vp, _vp, _i]),
     'bqio_tile_resample': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
@@ -209,6 +215,77 @@ def jpeg_decode_canvas(scan, desc, tables, seg_w, seg_h, place, canvas, clip, th
     if e != 0:
         raise ValueError(f'bqio_jpeg_decode_canvas: error {e}')
     return status
+
+
+J2K_SUBSET, J2K_DAMAGED = 32, 64        # a segment's status from ``j2k_extract`` (csrc/j2k_device.h); 16: refused by the decoder
+
+
+def j2k_extract(data, offsets, lengths, seg_w, seg_h, threads=None, strict=True):
+    """A TIFF page's raw JPEG 2000 segments packed for the device decoder (``bqio_j2k_extract``, tier 2 of the codec): ``data``
+    uint8 [bytes], segment i = ``data[offsets[i]:offsets[i] + lengths[i]]``, every one a codestream of ``seg_w`` x ``seg_h``
+    pixels -> ``(desc int32 [n, 32], blocks int32 [k, 12], cw uint8 [bytes])``: a descriptor per segment (``desc[:, 0]`` its
+    status), a row per code block and the blocks' codewords.  ``strict``: raise ``UnsupportedImage`` (``.index`` = the first
+    such segment) when a segment is outside the device decoder's subset or damaged; otherwise such a segment keeps its status
+    (``J2K_SUBSET`` / ``J2K_DAMAGED``), has no blocks, and the decoder writes nothing for it."""
+    data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+    off, ln = np.ascontiguousarray(offsets, np.uint64).reshape(-1), np.ascontiguousarray(lengths, np.uint64).reshape(-1)
+    n = len(off)
+    assert len(ln) == n and lib().bqio_j2k_seg_bytes() == 128 and lib().bqio_j2k_block_bytes() == 48
+    desc = np.zeros((n, 32), np.int32)
+    nb, used = C.c_int64(0), C.c_size_t(0)
+    # one call parses and fills: room for the rows of 32 x 32 blocks and some, and for the codewords, which are the segments' own
+    # bytes plus at most 7 of padding a block; smaller blocks than guessed: once more, with the sizes the first call stated
+    cap_b = n * 3 * (-(-int(seg_w) // 32) * -(-int(seg_h) // 32) + 40)
+    cap_c = int(ln.sum()) + 8 * cap_b
+    while True:
+        blocks, cw = np.empty((cap_b, 12), np.int32), np.empty(cap_c, np.uint8)
+        e = lib().bqio_j2k_extract(data.ctypes.data, data.size, off.ctypes.data, ln.ctypes.data, n, int(seg_w), int(seg_h),
+                                   desc.ctypes.data, blocks.ctypes.data, cap_b, cw.ctypes.data, cap_c, C.byref(nb), C.byref(used),
+                                   threads or default_threads())
+        if e == -1 and (nb.value > cap_b or used.value > cap_c):
+            cap_b, cap_c = max(cap_b, nb.value), max(cap_c, used.value)
+            continue
+        if e != 0:
+            raise ValueError(f'bqio_j2k_extract: error {e}')
+        break
+    bad = np.flatnonzero(desc[:, 0])
+    if strict and len(bad):
+        raise UnsupportedImage(int(bad[0]))
+    blocks, cw = blocks[:nb.value], cw[:used.value]
+    return desc, blocks, cw
+
+
+def j2k_decode_canvas(desc, blocks, cw, seg_w, seg_h, place, canvas, clip, ycc=False, threads=None, t1=False):
+    """The device JPEG 2000 decoder's routines (csrc/j2k_device.h) on the CPU (``bqio_j2k_decode_canvas``): the segments
+    ``j2k_extract`` packed, written INTO ``canvas`` (uint8 [H, W, 3], C-contiguous, modified in place) at ``place`` int32 [n, 2]
+    (x, y), clipped to ``clip`` = (x0, y0, x1, y1); ``ycc``: the samples are YCbCr (TIFF compression 33003) and are converted.
+    -> status int32 [n] (``t1=True``: ``(status, int32 [n, 3, seg_h, seg_w])`` with tier 1's output, doubled quantiser indices
+    in sub-band layout).  What ``Engine.j2k_decode_canvas`` computes, byte for byte and status for status.  For tests."""
+    desc, blocks = np.ascontiguousarray(desc, np.int32), np.ascontiguousarray(blocks, np.int32).reshape(-1, 12)
+    cw = np.ascontiguousarray(cw, np.uint8)
+    place = np.ascontiguousarray(place, np.int32).reshape(-1, 2)
+    clip = np.ascontiguousarray(clip, np.int32).reshape(4)
+    n = desc.shape[0]
+    assert desc.shape == (n, 32) and place.shape == (n, 2)
+    assert canvas.dtype == np.uint8 and canvas.ndim == 3 and canvas.shape[2] == 3 and canvas.flags.c_contiguous and canvas.flags.writeable
+    status = np.zeros(n, np.int32)
+    planes = np.zeros((n, 3, int(seg_h), int(seg_w)), np.int32) if t1 else None
+    e = lib().bqio_j2k_decode_canvas(desc.ctypes.data, n, blocks.ctypes.data, len(blocks), cw.ctypes.data, cw.size, int(seg_w), int(seg_h),
+                                     int(bool(ycc)), place.ctypes.data, canvas.ctypes.data, canvas.shape[0], canvas.shape[1],
+                                     clip.ctypes.data, status.ctypes.data, planes.ctypes.data if t1 else None,
+                                     threads or default_threads())
+    if e != 0:
+        raise ValueError(f'bqio_j2k_decode_canvas: error {e}')
+    return (status, planes) if t1 else status
+
+
+def ycc_to_rgb(a):
+    """uint8 [..., 3] full-range YCbCr -> RGB with the bytes of Pillow's ``convert('RGB')`` (csrc/j2k_ycc.h)."""
+    a = np.ascontiguousarray(a, np.uint8)
+    assert a.shape[-1] == 3
+    out = np.empty_like(a)
+    lib().bqio_ycc_to_rgb(a.ctypes.data, out.ctypes.data, a.size // 3)
+    return out
 
 
 SUBSAMPLING = {'4:4:4': 0, '4:2:0': 2, 0: 0, 2: 2}

@@ -4,10 +4,18 @@ of a whole-slide image at a tile width in MICRONS, each tile resampled to ``tile
 libvips or OpenSlide (none of which exists here).
 
 What is read: classic TIFF and BigTIFF, little or big endian; 8-bit RGB / YCbCr pages in chunky layout, stored as strips or tiles;
-compression none (1), zlib / Adobe deflate (8, 32946; horizontal predictor 2 supported) and JPEG (7: abbreviated streams + the page's
-``JPEGTables``, decoded by Pillow's libjpeg).  That covers Aperio SVS written with JPEG tiles and generic pyramidal TIFFs (``vips
-tiffsave --pyramid``, Pillow); JPEG 2000 SVS (33003 / 33005), LZW and planar layouts are refused with a message, not mis-read.
+compression none (1), zlib / Adobe deflate (8, 32946; horizontal predictor 2 supported), JPEG (7: abbreviated streams + the page's
+``JPEGTables``, decoded by Pillow's libjpeg) and JPEG 2000 (Aperio's 33003 and 33005, and 34712: one codestream or JP2 file per
+segment, decoded by Pillow's OpenJPEG).  That covers Aperio SVS written with JPEG or JPEG 2000 tiles and generic pyramidal TIFFs
+(``vips tiffsave --pyramid``, Pillow); LZW and planar layouts are refused with a message, not mis-read.
 Microns per pixel come from the Aperio description (``MPP = 0.2520``) or from XResolution / ResolutionUnit.
+
+JPEG 2000: a 33005 / 34712 segment's samples are RGB (a multiple-component transform inside the codestream is the decoder's to
+undo); a 33003 segment's three components are taken as full-range YCbCr and converted with the bytes of Pillow's own
+``Image.merge('YCbCr', ...).convert('RGB')`` (stated for the device and the CPU build in csrc/j2k_ycc.h, pinned against Pillow
+over all 2^24 triples in tests/test_j2k.py).  UNPINNED: whether that is the conversion Aperio's ImageScope and OpenSlide apply to
+33003 tiles -- no real slide and no OpenSlide exist here.  Every JPEG 2000 level is probed at open time: the first segment's main
+header (SOC, SIZ, COD, QCD) must state three 8-bit unsigned components and an image no smaller than the page's tile.
 
 PARITY UNPINNED (like everything on the producer side): Slideflow's reader is not available, no real slide exists here, and the kernel
 libvips uses to shrink a region to ``tile_px`` is not reproduced -- tiles are resampled with Pillow's LANCZOS.  What IS pinned
@@ -45,6 +53,51 @@ def _guard(fn):
 
 _TYPES = {1: ('B', 1), 2: ('c', 1), 3: ('H', 2), 4: ('I', 4), 5: ('II', 8), 6: ('b', 1), 7: ('B', 1), 8: ('h', 2), 9: ('i', 4),
           10: ('ii', 8), 11: ('f', 4), 12: ('d', 8), 13: ('I', 4), 16: ('Q', 8), 17: ('q', 8), 18: ('Q', 8)}
+
+
+J2K_COMPRESSIONS = (33003, 33005, 34712)   # Aperio: YCbCr components, RGB components; 34712: the registered JP2000 tag
+
+
+def j2k_probe(raw, tw, th):
+    """The main header of a JPEG 2000 segment (raw codestream or JP2 file), as far as the reader depends on it: SOC, SIZ, then
+    marker segments up to the first tile part with a COD and a QCD among them; three 8-bit unsigned components, an image of at
+    least ``tw`` x ``th``.  ``SlideError`` otherwise."""
+    def bad(why):
+        return SlideError(f'JPEG 2000 tile does not open: {why}')
+    at = 0
+    if raw[:12] == b'\0\0\0\x0cjP  \r\n\x87\n':                        # a JP2 file: the codestream starts its jp2c box
+        at = raw.find(b'jp2c\xff\x4f\xff\x51')
+        if at < 0:
+            raise bad('a JP2 file without a codestream box')
+        at += 4
+    if raw[at:at + 4] != b'\xff\x4f\xff\x51':
+        raise bad('no SOC and SIZ markers')
+    pos, seen = at + 2, set()
+    while True:
+        if pos + 4 > len(raw):
+            raise bad('the main header is cut off')
+        marker, length = struct.unpack('>HH', raw[pos:pos + 4])
+        if marker in (0xFF90, 0xFF93):
+            break
+        if marker < 0xFF30 or length < 2 or pos + 2 + length > len(raw):
+            raise bad(f'marker {marker:04X} with length {length} in the main header')
+        body = raw[pos + 4:pos + 2 + length]
+        if marker == 0xFF51:
+            if len(body) < 36 + 3:
+                raise bad('a short SIZ')
+            _, xs, ys, xo, yo = struct.unpack('>HIIII', body[:18])
+            comps = struct.unpack('>H', body[34:36])[0]
+            if len(body) != 36 + 3 * comps:
+                raise bad('a SIZ of the wrong length')
+            if comps != 3 or any(body[36 + 3 * c] != 7 for c in range(3)):
+                raise SlideError(f'JPEG 2000 tile with {comps} components of depths {[(body[36 + 3 * c] & 127) + 1 for c in range(min(comps, 4))]}: '
+                                 'only three 8-bit unsigned components are supported')
+            if xs - xo < tw or ys - yo < th:
+                raise SlideError(f'JPEG 2000 tile of {xs - xo} x {ys - yo} pixels is smaller than the page\'s {tw} x {th} tile')
+        seen.add(marker)
+        pos += 2 + length
+    if not {0xFF51, 0xFF52, 0xFF5C} <= seen:
+        raise bad('SIZ, COD or QCD missing from the main header')
 
 
 class _Page:
@@ -85,11 +138,9 @@ class _Page:
     def check(self):
         if self.planar != 1:
             raise SlideError('planar (separate-plane) TIFF pages are not supported')
-        if self.compression in (33003, 33005, 34712):
-            raise SlideError('JPEG 2000 compressed slide: not supported (no decoder in this image)')
         if self.compression == 5:
             raise SlideError('LZW-compressed TIFF: not supported (deflate, JPEG and uncompressed are)')
-        if self.compression not in (1, 7, 8, 32946):
+        if self.compression not in (1, 7, 8, 32946) + J2K_COMPRESSIONS:
             raise SlideError(f'TIFF compression {self.compression} is not supported')
         if len(self.offsets) != len(self.counts) or len(self.offsets) < self.across * self.down:
             raise SlideError('TIFF page: strip / tile tables do not cover the image')
@@ -102,12 +153,15 @@ class BandSegments:
     segment's top-left pixel (negative where the segment starts left of / above the canvas); ``clip`` = (x0, y0, x1, y1), the
     level's image extent in canvas coordinates, cut to the canvas -- what a segment holds beyond it is padding; ``seg_w``,
     ``seg_h`` the page's tile size; ``jpeg_tables`` the page's ``JPEGTables`` bytes or None.  Decoding every segment as
-    ``TiffSlide._jpeg`` reads it into a white canvas, inside ``clip`` only, gives ``WSI.band``'s canvas."""
-    __slots__ = ('shape', 'data', 'offsets', 'lengths', 'place', 'clip', 'seg_w', 'seg_h', 'jpeg_tables')
+    ``TiffSlide._jpeg`` reads it into a white canvas, inside ``clip`` only, gives ``WSI.band``'s canvas.  ``codec``: 'jpeg', or
+    'j2k' where the segments are JPEG 2000 codestreams (``TiffSlide._j2k`` reads them); ``ycc``: their three components are
+    YCbCr, to be converted as the reader does (compression 33003)."""
+    __slots__ = ('shape', 'data', 'offsets', 'lengths', 'place', 'clip', 'seg_w', 'seg_h', 'jpeg_tables', 'codec', 'ycc')
 
-    def __init__(self, **kw):
-        for k in self.__slots__:
+    def __init__(self, codec='jpeg', ycc=False, **kw):
+        for k in self.__slots__[:-2]:
             setattr(self, k, kw[k])
+        self.codec, self.ycc = codec, bool(ycc)
 
     def __len__(self):
         return len(self.offsets)
@@ -169,8 +223,10 @@ class TiffSlide:
             named = re.search(r'\b(label|macro)\b', p.description, re.I) is not None
             if same and not named and (p.tiled or not base.tiled):
                 levels.append(p)
-        for p in levels:
+        for li, p in enumerate(levels):
             p.check()
+            if p.compression in J2K_COMPRESSIONS:
+                j2k_probe(self._raw_segment(p, 0, li), p.tw, p.th)
         self.levels = levels
         self.dimensions = (base.width, base.height)
         self.level_dimensions = [(p.width, p.height) for p in levels]
@@ -231,6 +287,17 @@ class TiffSlide:
         return None
 
     # ---- pixels ------------------------------------------------------------------------------------------------------
+    def _raw_segment(self, p, index, li):
+        """The bytes of strip / tile ``index`` of page ``p`` (level ``li``, for the message), which must lie inside the file."""
+        off, cnt = int(p.offsets[index]), int(p.counts[index])
+        if cnt > self._size or off + cnt > self._size:
+            raise SlideError(f'{self.path}: segment {index} of level {li} claims more bytes than the file holds')
+        self._f.seek(off)
+        raw = self._f.read(cnt)
+        if len(raw) != cnt:
+            raise SlideError(f'{self.path}: segment {index} of level {li} runs past the end of the file')
+        return raw
+
     @_guard
     def _segment(self, li, index):
         """Strip / tile ``index`` of level ``li`` decoded to uint8 [th, tw, 3] (a last strip may be shorter)."""
@@ -238,15 +305,17 @@ class TiffSlide:
         if key in self._cache:
             return self._cache[key]
         p = self.levels[li]
-        if int(p.counts[index]) > self._size:
-            raise SlideError(f'{self.path}: segment {index} of level {li} claims more bytes than the file holds')
-        self._f.seek(int(p.offsets[index]))
-        raw = self._f.read(int(p.counts[index]))
+        raw = self._raw_segment(p, index, li)
         rows = p.th if p.tiled else min(p.th, p.height - (index * p.th))
         if p.compression == 7:
             img = self._jpeg(p, raw)
             if img.shape[0] < rows or img.shape[1] < p.tw:
                 raise SlideError(f'{self.path}: JPEG segment {index} of level {li} is smaller than its tile')
+            img = img[:rows, :p.tw]
+        elif p.compression in J2K_COMPRESSIONS:
+            img = self._j2k(p, raw)
+            if img.shape[0] < rows or img.shape[1] < p.tw:
+                raise SlideError(f'{self.path}: JPEG 2000 segment {index} of level {li} is smaller than its tile')
             img = img[:rows, :p.tw]
         else:
             if p.compression in (8, 32946):
@@ -283,6 +352,25 @@ class TiffSlide:
         except (OSError, SyntaxError) as e:
             raise SlideError(f'{self.path}: a JPEG tile does not decode: {e}') from None
 
+    def _j2k(self, p, raw):
+        """One JPEG 2000 segment -> uint8 [h, w, 3] RGB.  Pillow opens a three-component codestream without a colour box as
+        'RGB' and leaves the samples as they are: a 33003 segment's are YCbCr and are converted here (the module's header)."""
+        from PIL import Image
+        try:
+            im = Image.open(io.BytesIO(raw))
+            if im.format != 'JPEG2000':
+                raise SlideError(f'{self.path}: a JPEG 2000 tile holds a {im.format} image')
+            if im.mode == 'YCbCr':                                       # (a JP2 file that says so: Pillow converts)
+                return np.asarray(im.convert('RGB'))
+            if im.mode != 'RGB':
+                raise SlideError(f'{self.path}: a JPEG 2000 tile decodes to mode {im.mode}, not to three 8-bit components')
+            a = np.asarray(im)
+        except (OSError, SyntaxError) as e:
+            raise SlideError(f'{self.path}: a JPEG 2000 tile does not decode: {e}') from None
+        if p.compression == 33003:
+            a = np.asarray(Image.merge('YCbCr', [Image.fromarray(np.ascontiguousarray(a[:, :, c])) for c in range(3)]).convert('RGB'))
+        return a
+
     @_guard
     def read_region(self, level, x, y, w, h):
         p = self.levels[level]
@@ -304,12 +392,12 @@ class TiffSlide:
 
     @_guard
     def region_segments(self, level, x, y, w, h):
-        """The raw JPEG tiles ``read_region(level, x, y, w, h)`` would decode, as a ``BandSegments`` over the same [h, w] canvas,
-        or None when the level is not a tiled JPEG page (compression 7 with TileWidth / TileLength: strips, deflate and
-        uncompressed pages stay on ``read_region``).  Read through ``_segment``'s bounds checks -- a byte count beyond the
+        """The raw JPEG or JPEG 2000 tiles ``read_region(level, x, y, w, h)`` would decode, as a ``BandSegments`` over the same
+        [h, w] canvas (its ``codec`` says which), or None when the level is not a tiled JPEG / JPEG 2000 page (compression 7,
+        33003, 33005 or 34712 with TileWidth / TileLength: strips, deflate and uncompressed pages stay on ``read_region``).  Read through ``_segment``'s bounds checks -- a byte count beyond the
         file's size, a segment that does not lie inside the file, more segment bytes than the file holds: ``SlideError``."""
         p = self.levels[level]
-        if not (p.tiled and p.compression == 7):
+        if not (p.tiled and (p.compression == 7 or p.compression in J2K_COMPRESSIONS)):
             return None
         if not (0 < w <= 1 << 16 and 0 < h <= 1 << 16):
             raise SlideError(f'region of {w} x {h} pixels')
@@ -319,15 +407,10 @@ class TiffSlide:
             for ty in range(y0 // p.th, (y1 - 1) // p.th + 1):
                 for tx in range(x0 // p.tw, (x1 - 1) // p.tw + 1):
                     index = ty * p.across + tx
-                    off, cnt = int(p.offsets[index]), int(p.counts[index])
-                    total += cnt
-                    if cnt > self._size or off + cnt > self._size or total > self._size:
+                    total += int(p.counts[index])
+                    if total > self._size:
                         raise SlideError(f'{self.path}: segment {index} of level {level} claims more bytes than the file holds')
-                    self._f.seek(off)
-                    raw = self._f.read(cnt)
-                    if len(raw) != cnt:
-                        raise SlideError(f'{self.path}: segment {index} of level {level} runs past the end of the file')
-                    chunks.append(raw)
+                    chunks.append(self._raw_segment(p, index, level))
                     place.append((tx * p.tw - x, ty * p.th - y))
         lengths = np.array([len(c) for c in chunks], np.uint64)
         offsets = np.zeros(len(chunks), np.uint64)
@@ -335,7 +418,8 @@ class TiffSlide:
         return BandSegments(shape=(h, w), data=np.frombuffer(b''.join(chunks), np.uint8), offsets=offsets, lengths=lengths,
                             place=np.array(place, np.int32).reshape(-1, 2),
                             clip=(max(0, -x), max(0, -y), min(w, p.width - x), min(h, p.height - y)),
-                            seg_w=p.tw, seg_h=p.th, jpeg_tables=p.jpeg_tables)
+                            seg_w=p.tw, seg_h=p.th, jpeg_tables=p.jpeg_tables, codec='jpeg' if p.compression == 7 else 'j2k',
+                            ycc=p.compression == 33003)
 
     def close(self):
         self._f.close()

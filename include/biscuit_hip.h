@@ -218,6 +218,25 @@ int bq_jpeg_decode_canvas(bq_ctx* ctx, const uint8_t* d_scan, const void* d_desc
                           int seg_h, const int32_t* d_place, uint8_t* d_canvas, int H, int W, int clip_x0, int clip_y0, int clip_x1,
                           int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
 
+/* A TIFF page's JPEG 2000 tiles (compression 33003 / 33005 / 34712) decoded on the device into a slide canvas (kernels_j2k.hip;
+ * DESIGN.md "Heatmap input", JPEG 2000 tiles): the counterpart of bq_jpeg_decode_canvas.  n segments of seg_w x seg_h (each <= 512)
+ * as libbiscuit_io's bqio_j2k_extract packs them -- d_seg (n descriptors of 128 bytes), d_blocks (n_blocks code-block rows of 48
+ * bytes), d_bytes (n_bytes of codewords), all device memory, 4-byte aligned -- go through tier 1 (a lane per code block),
+ * dequantisation and the inverse 5/3 or 9/7 transform (a workgroup per segment and component) and a store kernel (inverse RCT /
+ * ICT, rounding, level shift, clamp; ycc != 0: the full-range YCbCr -> RGB of csrc/j2k_ycc.h) that writes d_canvas uint8
+ * [H][W][3] exactly as bq_jpeg_decode_canvas does: at d_place[i] = (x, y), inside the canvas and the clip rectangle only.
+ * d_status int32 [n]: 0, the extractor's status (32: outside the subset, 64: damaged) or 16 for a descriptor or block row
+ * that fails the decoder's own bounds checks; a segment whose status is not 0 writes nothing.  The result is
+ * bqio_j2k_decode_canvas's byte for byte and status for status.  Scratch: 24 bytes per pixel of a segment (1 572 864 at
+ * 256 x 256); bq_j2k_canvas_scratch_bytes(n, seg_w, seg_h) asks for min(n, 256) segments' worth, and the call works in rounds
+ * of as many segments as d_scratch holds -- one at least, BQ_ERR_WORKSPACE below that -- without a host synchronisation;
+ * n = 0 returns 0 without a launch. */
+size_t bq_j2k_canvas_scratch_bytes(int n, int seg_w, int seg_h);
+int bq_j2k_decode_canvas(bq_ctx* ctx, const void* d_seg, int n, const void* d_blocks, int64_t n_blocks, const uint8_t* d_bytes,
+                         size_t n_bytes, int seg_w, int seg_h, int ycc, const int32_t* d_place, uint8_t* d_canvas, int H, int W,
+                         int clip_x0, int clip_y0, int clip_x1, int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes,
+                         bq_stream_t stream);
+
 /* Output side, JPEG tiles, encoded on the device (kernels_jpeg_encode.hip; DESIGN.md "Tile extraction"): n tiles d_tiles uint8
  * [n][px][px][3] -- the batch bq_tile_resample fills -- become the COMPLETE baseline-JPEG files Pillow writes for `save(buf, 'JPEG',
  * quality=quality, subsampling=subsampling)` with everything else at its default (libjpeg's 16-bit BT.601, h2v2 box filter, islow

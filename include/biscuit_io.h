@@ -136,6 +136,39 @@ int bqio_extract_jpeg_segments(const uint8_t* data, size_t data_len, const uint6
 int bqio_jpeg_decode_canvas(const uint8_t* scan, const uint32_t* desc, const void* tables, int n_tables, int n, int seg_w, int seg_h,
                             const int32_t* place, uint8_t* canvas, int H, int W, const int32_t* clip, int32_t* status, int n_threads);
 
+/* ---- a TIFF page's JPEG 2000 tiles for the DEVICE decoder (libbiscuit_hip: bq_j2k_decode_canvas; csrc/j2k_host.cpp,
+ * csrc/j2k_device.h; DESIGN.md "Heatmap input", JPEG 2000 tiles) ----
+ * bqio_j2k_extract is tier 2 of the codec: segment i = data[off[i], off[i] + len[i]) (all inside data_len bytes, or
+ * BQIO_ERR_ARG) is a raw codestream of seg_w x seg_h pixels.  Its main header, tile-part headers and packet headers are
+ * walked; out come a descriptor per segment (seg_desc: n * bqio_j2k_seg_bytes() bytes: status, size, levels, transform, MCT
+ * flag, half step sizes per sub-band, guard bits), a row per code block with at least one coding pass (blocks: rows of
+ * bqio_j2k_block_bytes() bytes: segment, component, sub-band, rectangle in the component's plane, Mb, missing bit-planes,
+ * passes, offset and length of its codeword) and the codewords (bytes: each 4-aligned, FF FF FF FF behind it).  The subset:
+ * one tile, three 8-bit unsigned components without sub-sampling, code-block style 0, blocks up to 64 x 64, 0..6 levels, 5/3
+ * without or 9/7 with scalar-expounded quantisation, no SOP / EPH / ROI / POC / PPM / PPT / COC / QCC, at most 512 x 512.  A
+ * segment outside it, or damaged, has a non-zero status in its descriptor (32: outside the subset, 64: damaged) and no
+ * blocks; the call still returns BQIO_OK.  *n_blocks and *n_bytes are always set; blocks == bytes == NULL: a probe that
+ * writes the descriptors and the two sizes only; a cap that is too small: BQIO_ERR_ARG. */
+size_t bqio_j2k_seg_bytes(void);
+size_t bqio_j2k_block_bytes(void);
+int bqio_j2k_extract(const uint8_t* data, size_t data_len, const uint64_t* off, const uint64_t* len, int64_t n, int seg_w, int seg_h,
+                     int32_t* seg_desc, int32_t* blocks, int64_t blocks_cap, uint8_t* bytes, size_t bytes_cap, int64_t* n_blocks,
+                     size_t* n_bytes, int n_threads);
+
+/* The CPU statement of bq_j2k_decode_canvas over the same routines (csrc/j2k_device.h: t1_block, dequant_sample, synth_row /
+ * synth_col, finish_pixel, place_window): what bqio_j2k_extract packed, decoded INTO canvas (uint8 [H][W][3]) at place[i] =
+ * (x, y), inside clip = (x0, y0, x1, y1) only; ycc != 0: the samples are full-range YCbCr and are converted with Pillow's bytes
+ * (csrc/j2k_ycc.h).  status[i] = 0, the descriptor's status, or 16 for a descriptor or block row that fails the decoder's own
+ * checks; a segment whose status is not 0 writes nothing.  t1_out (NULL: none): int32 [n][3][seg_h][seg_w], tier 1's output in
+ * the planes' sub-band layout -- signed quantiser indices times two, plus the half of the last decoded bit-plane.  For tests,
+ * the sanitizer build and the fuzzer. */
+int bqio_j2k_decode_canvas(const int32_t* seg_desc, int n, const int32_t* blocks, int64_t n_blocks, const uint8_t* bytes, size_t n_bytes,
+                           int seg_w, int seg_h, int ycc, const int32_t* place, uint8_t* canvas, int H, int W, const int32_t* clip,
+                           int32_t* status, int32_t* t1_out, int n_threads);
+
+/* pixels full-range YCbCr triples -> RGB with the bytes of Pillow's convert('RGB') (csrc/j2k_ycc.h); in place allowed. */
+void bqio_ycc_to_rgb(const uint8_t* ycc, uint8_t* rgb, size_t pixels);
+
 /* ---- tile resampling for the whole-slide heatmap (csrc/resample_host.cpp, csrc/resample_device.h) ----
  * The tap tables of Pillow's 8-bit resampler for Image.resize((px, px), Image.LANCZOS) of a src_px x src_px image: per output
  * coordinate i, bounds[2 i] = first source coordinate, bounds[2 i + 1] = number of taps, coef[i * ksize + j] = tap j with 22
