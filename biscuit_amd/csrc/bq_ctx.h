@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/biscuit_hip.h"
 #include "bq_common.h"
+#include "bq_rounds.h"
 
 #include <map>
 #include <string>
@@ -119,6 +120,17 @@ struct ProfScope {
         c->prof_recs.push_back({cls, a, b});
     }
 };
+
+// ---- what the tile codecs share: rounds (bq_rounds.h: round_items, round_cap) and the encoders' arguments --------
+// The pointers of bq_jpeg_encode / bq_png_encode (`entry`), which share their output contract: tiles in, files packed into
+// d_out[cap] at d_off[n + 1].  -> the refusal's text, or empty.
+inline std::string bad_encode_args(const char* entry, const void* d_tiles, const void* d_out, int64_t cap, const void* d_off,
+                                   const void* d_status, const void* d_scratch) {
+    if (d_tiles && d_off && d_status && d_scratch && (d_out || !cap) && !((uintptr_t)d_off & 7) && !((uintptr_t)d_status & 3) &&
+        !((uintptr_t)d_scratch & 15))
+        return "";
+    return std::string(entry) + ": bad argument (null pointer, d_off not 8-byte or d_scratch not 16-byte aligned)";
+}
 
 // ---- what two files share -------------------------------------------------------
 // kernels_reinhard.hip: the normaliser's sRGB tables on the current device, once per context (bq_create); false: no memory

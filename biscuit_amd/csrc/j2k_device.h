@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "canvas_place.h"
 #include "j2k_ycc.h"
 
 #if defined(__HIPCC__)
@@ -410,20 +411,8 @@ BQK_HD void finish_pixel(int32_t c0, int32_t c1, int32_t c2, const Seg& s, int y
     else { rgb[0] = (uint8_t)v[0]; rgb[1] = (uint8_t)v[1]; rgb[2] = (uint8_t)v[2]; }
 }
 
-// ---- which pixels of a segment a canvas shows (as jpeg_device.h's place_window) ---------------------------------------------
-struct Window { int x0, y0, x1, y1; };   // in segment coordinates, half open
-
-BQK_HD bool place_window(int px, int py, int w, int h, int H, int W, const int32_t* clip, Window& o) {
-    int64_t cx0 = clip[0] > 0 ? clip[0] : 0, cy0 = clip[1] > 0 ? clip[1] : 0;
-    int64_t cx1 = clip[2] < W ? clip[2] : W, cy1 = clip[3] < H ? clip[3] : H;
-    int64_t x0 = cx0 - px, y0 = cy0 - py, x1 = cx1 - px, y1 = cy1 - py;
-    if (x0 < 0) x0 = 0;
-    if (y0 < 0) y0 = 0;
-    if (x1 > w) x1 = w;
-    if (y1 > h) y1 = h;
-    if (x1 <= x0 || y1 <= y0) return false;
-    o.x0 = (int)x0; o.y0 = (int)y0; o.x1 = (int)x1; o.y1 = (int)y1;
-    return true;
-}
+// ---- which pixels of a segment a canvas shows: canvas_place.h ---------------------------------------------------------------
+using bqcanvas::Window;
+using bqcanvas::place_window;
 
 }  // namespace bqj2k

@@ -401,8 +401,8 @@ int bqio_j2k_extract(const uint8_t* data, size_t data_len, const uint64_t* off, 
 int bqio_j2k_decode_canvas(const int32_t* seg_desc, int n, const int32_t* blocks, int64_t n_blocks, const uint8_t* bytes, size_t n_bytes,
                            int seg_w, int seg_h, int ycc, const int32_t* place, uint8_t* canvas, int H, int W, const int32_t* clip,
                            int32_t* status, int32_t* t1_out, int n_threads) {
-    if (n < 0 || n_blocks < 0 || seg_w <= 0 || seg_h <= 0 || seg_w > MAX_SIDE || seg_h > MAX_SIDE || H <= 0 || W <= 0 || H > (1 << 28) ||
-        W > (1 << 28) || !canvas || !clip || (n && (!seg_desc || !place || !status)) || (n_blocks && (!blocks || !bytes)))
+    if (n < 0 || n_blocks < 0 || seg_w <= 0 || seg_h <= 0 || seg_w > MAX_SIDE || seg_h > MAX_SIDE || !bqcanvas::canvas_args_ok(H, W) ||
+        !canvas || !clip || (n && (!seg_desc || !place || !status)) || (n_blocks && (!blocks || !bytes)))
         return BQIO_ERR_ARG;
     const size_t plane = (size_t)seg_w * seg_h;
     run_threads(n, n_threads, [&](int i) {

@@ -21,10 +21,12 @@
 // sampling.  Reads do not depend on the geometry.  The pixel stage reads samples (y, x) with y < h <= 8 bh[c] and x < w <=
 // 8 bw[c] only (chroma: y < ch, x < cw), which lie in the same planes.
 //
-// place_window below states, once for the host and the device, which pixels of a segment a canvas shows.
+// Which pixels of a segment a canvas shows is canvas_place.h's statement (place_window), brought into this namespace below.
 #pragma once
 #include <stdint.h>
 #include <string.h>
+
+#include "canvas_place.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -337,22 +339,9 @@ BQJ_HD void pixel_rgb(const uint8_t* tile, const Geom& G, int y, int x, uint8_t*
     rgb[2] = clamp8(Y + ((116130 * cb + 32768) >> 16));
 }
 
-// ---- a segment's place in a canvas --------------------------------------------------------------------------------------
-// A canvas is uint8 [H][W][3]; a seg_w x seg_h segment lies with its top-left pixel at canvas position (px, py), which may be
-// negative or beyond the canvas; clip = {x0, y0, x1, y1} is a rectangle in canvas coordinates (the level's image extent: what a
-// border segment holds beyond it is padding and is never shown).  The window [x0, x1) x [y0, y1) of the SEGMENT's own pixels
-// that lie inside both the canvas and the rectangle: exactly those are written, pixel (y, x) to canvas pixel (py + y, px + x).
-// false: none.  64-bit sums, so that no place or rectangle overflows.
-struct Window { int x0, y0, x1, y1; };
-BQJ_HD bool place_window(int px, int py, int seg_w, int seg_h, int H, int W, const int32_t* clip, Window& w) {
-    auto lo = [](int64_t a, int64_t b) { return a > b ? a : b; };
-    auto hi = [](int64_t a, int64_t b) { return a < b ? a : b; };
-    const int64_t cx0 = lo(clip[0], 0), cy0 = lo(clip[1], 0), cx1 = hi(clip[2], W), cy1 = hi(clip[3], H);
-    const int64_t x0 = lo(cx0 - px, 0), y0 = lo(cy0 - py, 0), x1 = hi(cx1 - px, seg_w), y1 = hi(cy1 - py, seg_h);
-    if (x1 <= x0 || y1 <= y0) return false;
-    w.x0 = (int)x0; w.y0 = (int)y0; w.x1 = (int)x1; w.y1 = (int)y1;
-    return true;
-}
+// ---- a segment's place in a canvas: canvas_place.h states which of its pixels the canvas shows -----------------------------
+using bqcanvas::Window;
+using bqcanvas::place_window;
 
 // The window of one decoded segment (planes: its blocks after idct_in_place) written into the canvas, pixel by pixel: the host's
 // form of the colour-and-place stage (the kernel of kernels_jpeg.hip writes the same pixels four at a time).

@@ -110,7 +110,7 @@ size_t seg_scratch_bytes(int w, int h) { return (size_t)w * h * 3 * 4 * 2; }
 
 size_t j2k_canvas_scratch_bytes(int n, int w, int h) {
     if (n <= 0 || w <= 0 || h <= 0) return 0;
-    return (size_t)(n < J2K_ROUND ? n : J2K_ROUND) * seg_scratch_bytes(w, h);
+    return round_cap(n, J2K_ROUND) * seg_scratch_bytes(w, h);
 }
 
 }  // namespace
@@ -122,17 +122,16 @@ size_t bq_j2k_canvas_scratch_bytes(int n, int seg_w, int seg_h) { return j2k_can
 int bq_j2k_decode_canvas(bq_ctx* c, const void* d_seg, int n, const void* d_blocks, int64_t n_blocks, const uint8_t* d_bytes, size_t n_bytes,
                          int seg_w, int seg_h, int ycc, const int32_t* d_place, uint8_t* d_canvas, int H, int W, int clip_x0, int clip_y0,
                          int clip_x1, int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
-    if (!c || n < 0 || n_blocks < 0 || n_blocks > (1ll << 30) || seg_w <= 0 || seg_w > MAX_SIDE || seg_h <= 0 || seg_h > MAX_SIDE || H <= 0 ||
-        W <= 0 || H > (1 << 28) || W > (1 << 28))
+    if (!c || n < 0 || n_blocks < 0 || n_blocks > (1ll << 30) || seg_w <= 0 || seg_w > MAX_SIDE || seg_h <= 0 || seg_h > MAX_SIDE ||
+        !bqcanvas::canvas_args_ok(H, W))
         return fail(c, BQ_ERR_ARG, "bq_j2k_decode_canvas: bad argument (need 0 < seg_w, seg_h <= 512 and 0 < H, W <= 2^28)");
     if (n == 0) return BQ_OK;
     if (!d_seg || (n_blocks && (!d_blocks || !d_bytes)) || !d_place || !d_canvas || !d_status || !d_scratch || ((uintptr_t)d_seg & 3) ||
         ((uintptr_t)d_blocks & 3) || ((uintptr_t)d_place & 3) || ((uintptr_t)d_scratch & 3))
         return fail(c, BQ_ERR_ARG, "bq_j2k_decode_canvas: bad argument");
     const size_t per = seg_scratch_bytes(seg_w, seg_h);
-    size_t m = scratch_bytes / per;
+    const size_t m = round_items(scratch_bytes, per, 1);
     if (m < 1) return fail(c, BQ_ERR_WORKSPACE, "bq_j2k_decode_canvas: scratch smaller than one segment's (bq_j2k_canvas_scratch_bytes(1, seg_w, seg_h))");
-    if (m > 32768) m = 32768;            // (the transform and store kernels' grids count segments in y)
     hipStream_t s = (hipStream_t)stream;
     J2kParams p;
     p.seg = reinterpret_cast<const Seg*>(d_seg); p.blocks = reinterpret_cast<const Block*>(d_blocks); p.bytes = d_bytes;

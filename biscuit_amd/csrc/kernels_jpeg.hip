@@ -13,12 +13,12 @@
 //
 // Integer arithmetic throughout; the result is held to Pillow's bytes (tests/test_gpu_jpeg.py), not to a tolerance.
 // A tile costs tile_coef_bytes(px) of scratch (554 KB at 299 px, sized for 4:4:4), so a call works in rounds of as many
-// tiles as the caller's scratch holds (jpeg_round_tiles).
+// tiles as the caller's scratch holds (round_items of bq_rounds.h).
 //
 // bq_jpeg_decode_canvas: a TIFF page's own w x h segments (bqio_extract_jpeg_segments) through the same entropy and idct kernels
 // -- they need the (w, h) geometry and nothing else -- and, in place of `colour`,
 //   place    four pixels of the CANVAS per thread: the window of each segment that the canvas and the clip rectangle show
-//            (place_window of jpeg_device.h, the host's statement too), row by row, in groups of four flat canvas pixels -- 12
+//            (place_window of canvas_place.h, the host's statement too), row by row, in groups of four flat canvas pixels -- 12
 //            bytes at a multiple of 12, so three aligned dword stores wherever the whole group belongs to the row, byte stores
 //            at a row's ragged ends (the pitch 3 W is no multiple of 4 in general).  Nothing outside a window is written.
 #include "bq_ctx.h"
@@ -74,6 +74,23 @@ __global__ void __launch_bounds__(JP_NT) jpeg_idct_kernel(const JpegParams p) {
     if (!bqjd::idct_in_place(p.coef + (size_t)i * p.tile_i16 + (size_t)b * 64)) atomicOr(&p.status[i], (int)bqjd::ST_RANGE);
 }
 
+// The group of four flat pixels that starts at pixel a = 4 q, b[12] their bytes, to o = base + 12 q: three dword stores where
+// the whole group lies in [P0, P1) (`all`) and o is aligned, otherwise byte stores of the pixels that do lie in it.
+__device__ __forceinline__ void store_group(uint8_t* o, const uint8_t (&b)[12], bool all, long long a, long long P0, long long P1) {
+    if (all && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+        uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            o4[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) | ((uint32_t)b[4 * k + 3] << 24);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long P = a + j;
+            if (P >= P0 && P < P1) { o[3 * j] = b[3 * j]; o[3 * j + 1] = b[3 * j + 1]; o[3 * j + 2] = b[3 * j + 2]; }
+        }
+    }
+}
+
 __global__ void __launch_bounds__(JP_NT) jpeg_colour_kernel(const JpegParams p) {
     const long long q = p.p0 / 4 + (long long)blockIdx.x * JP_NT + threadIdx.x;     // group of four pixels of the call's output
     const long long a = q * 4;
@@ -105,19 +122,7 @@ __global__ void __launch_bounds__(JP_NT) jpeg_colour_kernel(const JpegParams p) 
         }
         if (++x == px) { x = 0; if (++y == px) { y = 0; ++tile; } }
     }
-    uint8_t* o = p.out + 12 * q;
-    if (all && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-        uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            o4[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) | ((uint32_t)b[4 * k + 3] << 24);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long long P = a + j;
-            if (P >= p.p0 && P < p.p1) { o[3 * j] = b[3 * j]; o[3 * j + 1] = b[3 * j + 1]; o[3 * j + 2] = b[3 * j + 2]; }
-        }
-    }
+    store_group(p.out + 12 * q, b, all, a, p.p0, p.p1);
 }
 
 struct PlaceParams {
@@ -156,78 +161,31 @@ __global__ void __launch_bounds__(JP_NT) jpeg_place_kernel(const JpegParams p, c
         b[3 * j] = b[3 * j + 1] = b[3 * j + 2] = 0;
         if (valid) bqjd::pixel_rgb(planes, G, y, w.x0 + (int)(P - P0), b + 3 * j);
     }
-    uint8_t* o = c.canvas + 12 * q;
-    if (all && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-        uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            o4[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) | ((uint32_t)b[4 * k + 3] << 24);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long long P = a + j;
-            if (P >= P0 && P < P1) { o[3 * j] = b[3 * j]; o[3 * j + 1] = b[3 * j + 1]; o[3 * j + 2] = b[3 * j + 2]; }
-        }
-    }
+    store_group(c.canvas + 12 * q, b, all, a, P0, P1);
 }
 
 }  // namespace
 
 static size_t jpeg_scratch_bytes(int n, int px) {
     if (n <= 0 || px <= 0) return 0;
-    return (size_t)(n < JPEG_ROUND ? n : JPEG_ROUND) * bqjd::tile_coef_bytes(px);
-}
-
-// n tiles as bqio_extract_jpeg packed them -> uint8 NHWC + status, in rounds of as many tiles as d_scratch holds.
-static int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px, uint8_t* d_out,
-                              int* d_status, void* d_scratch, size_t scratch_bytes, hipStream_t s) {
-    if (n <= 0) return 0;
-    const size_t per = bqjd::tile_coef_bytes(px);
-    size_t m = scratch_bytes / per;
-    if (m < 1) return (int)hipErrorInvalidValue;
-    if (m > 32768) m = 32768;            // (the idct kernel's grid counts tiles in y)
-    if (m >= JE_NT) m &= ~(size_t)(JE_NT - 1);
-    const long long ppt = (long long)px * px;
-    for (long long t0 = 0; t0 < n; t0 += (long long)m) {
-        const int cnt = (int)(n - t0 < (long long)m ? n - t0 : (long long)m);
-        JpegParams p;
-        p.scan = d_scan;
-        p.desc = reinterpret_cast<const bqjd::Desc*>(d_desc) + t0;
-        p.tables = reinterpret_cast<const bqjd::TableSet*>(d_tables);
-        p.n_tables = n_tables; p.n = cnt; p.w = p.h = px;
-        p.coef = reinterpret_cast<int16_t*>(d_scratch); p.tile_i16 = per / 2;
-        p.status = d_status + t0; p.out = d_out;
-        p.p0 = t0 * ppt; p.p1 = (t0 + cnt) * ppt; p.t0 = t0;
-        if (const hipError_t e = hipMemsetAsync(d_scratch, 0, (size_t)cnt * per, s)) return (int)e;
-        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((cnt + JE_NT - 1) / JE_NT), dim3(JE_NT), 0, s, p);
-        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((bqjd::tile_blocks(px) + JP_NT - 1) / JP_NT, cnt), dim3(JP_NT), 0, s, p);
-        const long long groups = (p.p1 + 3) / 4 - p.p0 / 4;
-        hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((groups + JP_NT - 1) / JP_NT)), dim3(JP_NT), 0, s, p);
-    }
-    return (int)hipGetLastError();
+    return round_cap(n, JPEG_ROUND) * bqjd::tile_coef_bytes(px);
 }
 
 static size_t jpeg_canvas_scratch_bytes(int n, int w, int h) {
     if (n <= 0 || w <= 0 || h <= 0) return 0;
-    return (size_t)(n < JPEG_ROUND ? n : JPEG_ROUND) * bqjd::tile_coef_bytes(w, h);
+    return round_cap(n, JPEG_ROUND) * bqjd::tile_coef_bytes(w, h);
 }
 
-// n segments of w x h as bqio_extract_jpeg_segments packed them -> their windows in the canvas + status, in rounds of as many
-// segments as d_scratch holds (at least one).
-static int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int w, int h,
-                                     const int32_t* d_place, uint8_t* d_canvas, int H, int W, const int32_t* clip, int* d_status, void* d_scratch,
-                                     size_t scratch_bytes, hipStream_t s) {
+// What both entries do with n packed w x h tiles, in rounds of as many as d_scratch holds (whole workgroups of the entropy
+// kernel, once it holds one): the round's JpegParams, the scratch zeroed, the entropy and idct kernels, and then last(p, cnt),
+// the entry's own kernel over the round's samples.  `last` may set out, p0 and p1 first: only its kernel reads them.
+template <typename Last>
+static int launch_jpeg_rounds(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int w, int h, int* d_status,
+                              void* d_scratch, size_t scratch_bytes, hipStream_t s, Last last) {
     if (n <= 0) return 0;
     const size_t per = bqjd::tile_coef_bytes(w, h);
-    size_t m = scratch_bytes / per;
+    const size_t m = round_items(scratch_bytes, per, JE_NT);
     if (m < 1) return (int)hipErrorInvalidValue;
-    if (m > 32768) m = 32768;            // (the idct and place kernels' grids count segments in y)
-    if (m >= JE_NT) m &= ~(size_t)(JE_NT - 1);
-    PlaceParams c;
-    c.canvas = d_canvas; c.H = H; c.W = W;
-    for (int k = 0; k < 4; ++k) c.clip[k] = clip[k];
-    c.groups = (w + 3) / 4 + 1;
-    const unsigned place_blocks = (unsigned)(((long long)h * c.groups + JP_NT - 1) / JP_NT);
     for (long long t0 = 0; t0 < n; t0 += (long long)m) {
         const int cnt = (int)(n - t0 < (long long)m ? n - t0 : (long long)m);
         JpegParams p;
@@ -238,13 +196,38 @@ static int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, 
         p.coef = reinterpret_cast<int16_t*>(d_scratch); p.tile_i16 = per / 2;
         p.status = d_status + t0; p.out = nullptr;
         p.p0 = p.p1 = 0; p.t0 = t0;
-        c.place = d_place + 2 * t0;
         if (const hipError_t e = hipMemsetAsync(d_scratch, 0, (size_t)cnt * per, s)) return (int)e;
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((cnt + JE_NT - 1) / JE_NT), dim3(JE_NT), 0, s, p);
         hipLaunchKernelGGL(jpeg_idct_kernel, dim3((bqjd::tile_blocks(w, h) + JP_NT - 1) / JP_NT, cnt), dim3(JP_NT), 0, s, p);
-        hipLaunchKernelGGL(jpeg_place_kernel, dim3(place_blocks, cnt), dim3(JP_NT), 0, s, p, c);
+        last(p, cnt);
     }
     return (int)hipGetLastError();
+}
+
+// n tiles as bqio_extract_jpeg packed them -> uint8 NHWC + status
+static int launch_jpeg_decode(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int px, uint8_t* d_out,
+                              int* d_status, void* d_scratch, size_t scratch_bytes, hipStream_t s) {
+    const long long ppt = (long long)px * px;
+    return launch_jpeg_rounds(d_scan, d_desc, d_tables, n_tables, n, px, px, d_status, d_scratch, scratch_bytes, s, [&](JpegParams& p, int cnt) {
+        p.out = d_out; p.p0 = p.t0 * ppt; p.p1 = (p.t0 + cnt) * ppt;
+        const long long groups = (p.p1 + 3) / 4 - p.p0 / 4;
+        hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((groups + JP_NT - 1) / JP_NT)), dim3(JP_NT), 0, s, p);
+    });
+}
+
+// n segments of w x h as bqio_extract_jpeg_segments packed them -> their windows in the canvas + status
+static int launch_jpeg_decode_canvas(const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int w, int h,
+                                     const int32_t* d_place, uint8_t* d_canvas, int H, int W, const int32_t* clip, int* d_status, void* d_scratch,
+                                     size_t scratch_bytes, hipStream_t s) {
+    PlaceParams c;
+    c.canvas = d_canvas; c.H = H; c.W = W;
+    for (int k = 0; k < 4; ++k) c.clip[k] = clip[k];
+    c.groups = (w + 3) / 4 + 1;
+    const unsigned place_blocks = (unsigned)(((long long)h * c.groups + JP_NT - 1) / JP_NT);
+    return launch_jpeg_rounds(d_scan, d_desc, d_tables, n_tables, n, w, h, d_status, d_scratch, scratch_bytes, s, [&](JpegParams& p, int cnt) {
+        c.place = d_place + 2 * p.t0;
+        hipLaunchKernelGGL(jpeg_place_kernel, dim3(place_blocks, cnt), dim3(JP_NT), 0, s, p, c);
+    });
 }
 
 extern "C" {
@@ -270,8 +253,7 @@ size_t bq_jpeg_canvas_scratch_bytes(int n, int seg_w, int seg_h) { return jpeg_c
 int bq_jpeg_decode_canvas(bq_ctx* c, const uint8_t* d_scan, const void* d_desc, const void* d_tables, int n_tables, int n, int seg_w,
                           int seg_h, const int32_t* d_place, uint8_t* d_canvas, int H, int W, int clip_x0, int clip_y0, int clip_x1,
                           int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream) {
-    if (!c || n < 0 || seg_w <= 0 || seg_w > 4096 || seg_h <= 0 || seg_h > 4096 || n_tables < 0 || H <= 0 || W <= 0 || H > (1 << 28) ||
-        W > (1 << 28))
+    if (!c || n < 0 || seg_w <= 0 || seg_w > 4096 || seg_h <= 0 || seg_h > 4096 || n_tables < 0 || !bqcanvas::canvas_args_ok(H, W))
         return fail(c, BQ_ERR_ARG, "bq_jpeg_decode_canvas: bad argument (need 0 < seg_w, seg_h <= 4096 and 0 < H, W <= 2^28)");
     if (n == 0) return BQ_OK;
     if (!d_scan || !d_desc || !d_tables || n_tables == 0 || !d_place || !d_canvas || !d_status || !d_scratch || ((uintptr_t)d_tables & 3) ||

@@ -19,6 +19,7 @@
 // A tile costs Layout::per_tile() bytes of scratch (889 KB at 299 px / 4:2:0, of which 536 KB are the worst-case unstuffed code); a call
 // works in rounds of as many tiles as the caller's scratch holds.  The tables (2.4 KB) and the header (623 bytes) are kernel
 // arguments: nothing is allocated or copied, and nothing waits for the device.
+#include "block_scan.h"
 #include "bq_ctx.h"
 #include "jpeg_encode_device.h"
 
@@ -65,22 +66,6 @@ struct EncParams {
 __device__ uint32_t& meta_ulen(const EncParams& p, int i) { return *reinterpret_cast<uint32_t*>(p.meta + (size_t)i * 16); }
 __device__ long long& meta_flen(const EncParams& p, int i) { return *reinterpret_cast<long long*>(p.meta + (size_t)i * 16 + 8); }
 
-// Inclusive scan of one value per thread over the workgroup; `sh` holds NT values.  All threads call it.
-template <typename V>
-__device__ V block_scan(V v, V* sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < NT; d <<= 1) {
-        const V a = t >= d ? sh[t - d] : (V)0;
-        __syncthreads();
-        sh[t] += a;
-        __syncthreads();
-    }
-    const V r = sh[t];
-    return r;
-}
-
 __global__ void __launch_bounds__(NT) jenc_pixel_kernel(const EncParams p, const bqje::Tables T) {
     // Both quantiser tables in LDS: which one a thread divides by depends on its block, and 64 + 64 entries held in SGPRs for a
     // per-lane choice do not fit beside the rest (they spilled).
@@ -111,7 +96,7 @@ __global__ void __launch_bounds__(NT) jenc_scan_kernel(const EncParams p) {
     for (uint32_t base = 0; base < p.G.nblk; base += NT) {
         const uint32_t b = base + threadIdx.x;
         const uint32_t v = b < p.G.nblk ? bits[b] : 0;
-        const uint32_t incl = block_scan(v, sh);
+        const uint32_t incl = block_scan<NT>(v, sh);
         if (b < p.G.nblk) bits[b] = carry + incl - v;
         carry += sh[NT - 1];
         __syncthreads();
@@ -149,7 +134,7 @@ __global__ void __launch_bounds__(NT) jenc_ff_kernel(const EncParams p) {
             v = ff_in_word(a.x) + ff_in_word(a.y) + ff_in_word(a.z) + ff_in_word(a.w) + ff_in_word(d.x) + ff_in_word(d.y) +
                 ff_in_word(d.z) + ff_in_word(d.w);
         }
-        const uint32_t incl = block_scan(v, sh);
+        const uint32_t incl = block_scan<NT>(v, sh);
         if (c < nch) pre[c] = carry + incl - v;
         carry += sh[NT - 1];
         __syncthreads();
@@ -160,16 +145,7 @@ __global__ void __launch_bounds__(NT) jenc_ff_kernel(const EncParams p) {
 // file lengths -> d_off[t0 + 1 .. t0 + n], continuing from d_off[t0]; one workgroup
 __global__ void __launch_bounds__(NT) jenc_offsets_kernel(const EncParams p) {
     __shared__ long long sh[NT];
-    long long carry = p.t0 ? p.off[p.t0] : 0;
-    if (p.t0 == 0 && threadIdx.x == 0) p.off[0] = 0;
-    for (int base = 0; base < p.n; base += NT) {
-        const int i = base + (int)threadIdx.x;
-        const long long v = i < p.n ? meta_flen(p, i) : 0;
-        const long long incl = block_scan(v, sh);
-        if (i < p.n) p.off[p.t0 + i + 1] = carry + incl;
-        carry += sh[NT - 1];
-        __syncthreads();
-    }
+    offsets_scan<NT>(p.off, p.t0, p.n, [&](int i) { return meta_flen(p, i); }, sh);
 }
 
 // header + stuffed segment + EOI of tile i at out + off[i], when it ends inside `cap`
@@ -198,13 +174,7 @@ __global__ void __launch_bounds__(NT) jenc_copy_kernel(const EncParams p, const 
 
 static size_t jpeg_encode_scratch_bytes(int n, int px, int sub) {
     if (n <= 0 || !bqje::valid_args(px, 1, sub)) return 0;
-    return (size_t)(n < ENC_ROUND ? n : ENC_ROUND) * layout_of(bqje::geom_of(px, sub)).per_tile();
-}
-
-static int jpeg_encode_round_tiles(int px, int sub, size_t scratch_bytes) {
-    size_t m = scratch_bytes / layout_of(bqje::geom_of(px, sub)).per_tile();
-    if (m > 32768) m = 32768;            // (the per-block kernels' grids count tiles in y)
-    return (int)m;
+    return round_cap(n, ENC_ROUND) * layout_of(bqje::geom_of(px, sub)).per_tile();
 }
 
 enum { JPEG_ENC_PIXEL = 0, JPEG_ENC_SIZE = 1, JPEG_ENC_PACK = 2, JPEG_ENC_STUFF = 3, JPEG_ENC_STAGES = 4 };
@@ -263,10 +233,9 @@ int bq_jpeg_encode(bq_ctx* c, const uint8_t* d_tiles, int n, int px, int quality
     if (px < 1 || px > 4096 || quality < 1 || quality > 100 || (subsampling != 0 && subsampling != 2))
         return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: outside the encoder's subset (need 1 <= px <= 4096, 1 <= quality <= 100, subsampling 0 = 4:4:4 or 2 = 4:2:0)");
     if (n == 0) return BQ_OK;
-    if (!d_tiles || !d_off || !d_status || !d_scratch || (!d_out && cap) || ((uintptr_t)d_off & 7) || ((uintptr_t)d_status & 3) ||
-        ((uintptr_t)d_scratch & 15))
-        return fail(c, BQ_ERR_ARG, "bq_jpeg_encode: bad argument (null pointer, d_off not 8-byte or d_scratch not 16-byte aligned)");
-    const int m = jpeg_encode_round_tiles(px, subsampling, scratch_bytes);
+    const std::string bad = bad_encode_args("bq_jpeg_encode", d_tiles, d_out, cap, d_off, d_status, d_scratch);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    const int m = (int)round_items(scratch_bytes, layout_of(bqje::geom_of(px, subsampling)).per_tile(), 1);
     if (m < 1) return fail(c, BQ_ERR_WORKSPACE, "bq_jpeg_encode: scratch smaller than one tile's (bq_jpeg_encode_scratch_bytes(1, px, subsampling))");
     hipStream_t s = (hipStream_t)stream;
     static const char* const kStage[JPEG_ENC_STAGES] = {"jpeg_encode_pixel", "jpeg_encode_size", "jpeg_encode_pack", "jpeg_encode_stuff"};

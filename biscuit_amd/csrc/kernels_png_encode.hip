@@ -16,6 +16,7 @@
 //
 // A tile costs Layout::per_tile() bytes of scratch (1.71 MB at 299 px, of which 1.11 MB are the tokens' worst case); a call works
 // in rounds of as many tiles as the caller's scratch holds.  Nothing is allocated or copied, and nothing waits for the device.
+#include "block_scan.h"
 #include "bq_ctx.h"
 #include "png_encode_device.h"
 
@@ -84,22 +85,6 @@ __device__ uint32_t wave_scan(uint32_t v, int lane) {
         if (lane >= d) v += a;
     }
     return v;
-}
-
-// Inclusive scan of one value per thread over the workgroup; `sh` holds NT values.  All threads call it.
-template <typename V>
-__device__ V block_scan(V v, V* sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < NT; d <<= 1) {
-        const V a = t >= d ? sh[t - d] : (V)0;
-        __syncthreads();
-        sh[t] += a;
-        __syncthreads();
-    }
-    const V r = sh[t];
-    return r;
 }
 
 // ---- filter: one wave per row -----------------------------------------------------------------------------------------------
@@ -308,16 +293,7 @@ __global__ void __launch_bounds__(WAVE) penc_pack_kernel(const EncParams p) {
 // file lengths -> d_off[t0 + 1 .. t0 + n], continuing from d_off[t0]; one workgroup
 __global__ void __launch_bounds__(NT) penc_offsets_kernel(const EncParams p) {
     __shared__ long long sh[NT];
-    long long carry = p.t0 ? p.off[p.t0] : 0;
-    if (p.t0 == 0 && threadIdx.x == 0) p.off[0] = 0;
-    for (int base = 0; base < p.n; base += NT) {
-        const int i = base + (int)threadIdx.x;
-        const long long v = i < p.n ? meta_flen(p, i) : 0;
-        const long long incl = block_scan(v, sh);
-        if (i < p.n) p.off[p.t0 + i + 1] = carry + incl;
-        carry += sh[NT - 1];
-        __syncthreads();
-    }
+    offsets_scan<NT>(p.off, p.t0, p.n, [&](int i) { return meta_flen(p, i); }, sh);
 }
 
 // signature + IHDR, the zlib bytes at their places between the chunk frames, IEND of tile i at out + off[i], when it ends inside `cap`
@@ -360,13 +336,7 @@ __global__ void __launch_bounds__(WAVE) penc_crc_kernel(const EncParams p) {
 
 static size_t png_encode_scratch_bytes(int n, int px) {
     if (n <= 0 || !bqpe::valid_px(px)) return 0;
-    return (size_t)(n < ENC_ROUND ? n : ENC_ROUND) * layout_of(bqpe::geom_of(px)).per_tile();
-}
-
-static int png_encode_round_tiles(int px, size_t scratch_bytes) {
-    size_t m = scratch_bytes / layout_of(bqpe::geom_of(px)).per_tile();
-    if (m > 32768) m = 32768;            // (the per-block kernels' grids count tiles in y)
-    return (int)m;
+    return round_cap(n, ENC_ROUND) * layout_of(bqpe::geom_of(px)).per_tile();
 }
 
 enum { PNG_ENC_FILTER = 0, PNG_ENC_MATCH = 1, PNG_ENC_CODE = 2, PNG_ENC_PACK = 3, PNG_ENC_STAGES = 4 };
@@ -430,10 +400,9 @@ int bq_png_encode(bq_ctx* c, const uint8_t* d_tiles, int n, int px, uint8_t* d_o
     if (!c || n < 0 || cap < 0) return fail(c, BQ_ERR_ARG, "bq_png_encode: bad argument");
     if (!bqpe::valid_px(px)) return fail(c, BQ_ERR_ARG, "bq_png_encode: outside the encoder's subset (need 1 <= px <= 4096)");
     if (n == 0) return BQ_OK;
-    if (!d_tiles || !d_off || !d_status || !d_scratch || (!d_out && cap) || ((uintptr_t)d_off & 7) || ((uintptr_t)d_status & 3) ||
-        ((uintptr_t)d_scratch & 15))
-        return fail(c, BQ_ERR_ARG, "bq_png_encode: bad argument (null pointer, d_off not 8-byte or d_scratch not 16-byte aligned)");
-    const int m = png_encode_round_tiles(px, scratch_bytes);
+    const std::string bad = bad_encode_args("bq_png_encode", d_tiles, d_out, cap, d_off, d_status, d_scratch);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    const int m = (int)round_items(scratch_bytes, layout_of(bqpe::geom_of(px)).per_tile(), 1);
     if (m < 1) return fail(c, BQ_ERR_WORKSPACE, "bq_png_encode: scratch smaller than one tile's (bq_png_encode_scratch_bytes(1, px))");
     hipStream_t s = (hipStream_t)stream;
     static const char* const kStage[PNG_ENC_STAGES] = {"png_encode_filter", "png_encode_match", "png_encode_code", "png_encode_pack"};

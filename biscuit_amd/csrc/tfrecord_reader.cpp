@@ -931,8 +931,8 @@ int bqio_jpeg_decode_extracted(const uint8_t* scan, const uint32_t* desc, const 
 
 int bqio_jpeg_decode_canvas(const uint8_t* scan, const uint32_t* desc, const void* tables, int n_tables, int n, int seg_w, int seg_h,
                             const int32_t* place, uint8_t* canvas, int H, int W, const int32_t* clip, int32_t* status, int n_threads) {
-    if (n < 0 || seg_w <= 0 || seg_h <= 0 || seg_w > 4096 || seg_h > 4096 || n_tables < 0 || H <= 0 || W <= 0 || H > (1 << 28) ||
-        W > (1 << 28) || !canvas || !clip || (n && (!scan || !desc || !place || !status)) || (n_tables && !tables))
+    if (n < 0 || seg_w <= 0 || seg_h <= 0 || seg_w > 4096 || seg_h > 4096 || n_tables < 0 || !bqcanvas::canvas_args_ok(H, W) || !canvas ||
+        !clip || (n && (!scan || !desc || !place || !status)) || (n_tables && !tables))
         return BQIO_ERR_ARG;
     if (n_threads < 1) n_threads = 1;
     if (n_threads > n) n_threads = n ? n : 1;

@@ -206,6 +206,38 @@ class Engine:
             setattr(self, name, torch.empty(int(need), dtype=torch.uint8, device=self.device))
         return getattr(self, name)
 
+    def _bytes(self, n):
+        """``n`` bytes on this device that the caller owns: what the ``*_scratch`` methods hand out."""
+        return torch.empty(int(n), dtype=torch.uint8, device=self.device)
+
+    @staticmethod
+    def _canvas_args(n, place, canvas, clip):
+        """What the canvas decoders take alike: ``place`` int32 [n, 2], ``canvas`` uint8 [H, W, 3] -> the clip rectangle's four ints."""
+        assert place.dtype == torch.int32 and place.is_cuda and place.is_contiguous() and tuple(place.shape) == (n, 2)
+        assert canvas.dtype == torch.uint8 and canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == 3 and canvas.shape[2] == 3
+        return tuple(int(v) for v in clip)
+
+    def _encode(self, entry, scratch_attr, counter_attr, tiles, cap, scratch, scratch_bytes, *mid_args):
+        """The encoders' call: ``bq_<entry>(ctx, tiles, n, px, *mid_args, out, cap, off, status, scratch, ...)`` with ``cap`` bytes of
+        output, and once more with the exact total -- which the first call's offsets state -- when the files did not fit (status
+        bit 1).  ``counter_attr`` counts the calls.  -> ``(buffer[:total], offsets on the host)``."""
+        n, px = int(tiles.shape[0]), int(tiles.shape[1])
+        scratch = self._scratch(scratch_attr, int(scratch_bytes), scratch)
+        off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        setattr(self, counter_attr, 0)
+        while True:
+            out = torch.empty(max(int(cap), 1), dtype=torch.uint8, device=self.device)
+            self._check(getattr(self._lib, 'bq_' + entry)(self._ctx, _ptr(tiles), n, px, *mid_args, _ptr(out), int(cap), _ptr(off),
+                                                          _ptr(status), _ptr(scratch), scratch.numel(), self._stream()))
+            setattr(self, counter_attr, getattr(self, counter_attr) + 1)
+            offsets = off.cpu()
+            total = int(offsets[-1])
+            if n == 0 or total <= int(cap):
+                return out[:total], offsets
+            assert getattr(self, counter_attr) == 1 and bool((status & 1).any()), f'bq_{entry}: the exact total did not fit'
+            cap = total
+
     def _ws_for(self, n, mc_n):
         """Caller-owned device workspace (a torch uint8 tensor), grown on demand."""
         return self._scratch('_ws', self._lib.bq_workspace_bytes(self._ctx, int(n), int(mc_n)))
@@ -267,7 +299,7 @@ class Engine:
 
     def inflate_scratch(self, n):
         """Table space for ``png_inflate`` over up to ``n`` streams (one buffer per launch that may be in flight)."""
-        return torch.empty(int(self._lib.bq_png_inflate_scratch_bytes(int(n))), dtype=torch.uint8, device=self.device)
+        return self._bytes(self._lib.bq_png_inflate_scratch_bytes(int(n)))
 
     def png_unfilter_strided(self, rows, px=TILE_PX):
         """``png_inflate``'s rows [n, stride] -> uint8 NHWC [n,px,px,3] (``bq_png_unfilter_strided``)."""
@@ -305,7 +337,7 @@ class Engine:
     def jpeg_scratch(self, n, px=TILE_PX):
         """Coefficient space for ``jpeg_decode`` over ``n`` tiles (``bq_jpeg_scratch_bytes``: 554 KB per 299-px tile, for 2 048
         tiles at most -- 1.14 GB; a longer call works in rounds)."""
-        return torch.empty(int(self._lib.bq_jpeg_scratch_bytes(int(n), int(px))), dtype=torch.uint8, device=self.device)
+        return self._bytes(self._lib.bq_jpeg_scratch_bytes(int(n), int(px)))
 
     def jpeg_decode_canvas(self, scan, desc, tables, seg_w, seg_h, place, canvas, clip, scratch=None):
         """A slide page's own JPEG tiles decoded on the device INTO a canvas (``bq_jpeg_decode_canvas``, kernels_jpeg.hip: the
@@ -320,9 +352,7 @@ class Engine:
         n, seg_w, seg_h = int(desc.shape[0]), int(seg_w), int(seg_h)
         assert desc.is_cuda and desc.is_contiguous() and desc.element_size() == 4 and tuple(desc.shape) == (n, 4)
         assert tables.dtype == torch.uint8 and tables.is_cuda and tables.is_contiguous() and tables.dim() == 2
-        assert place.dtype == torch.int32 and place.is_cuda and place.is_contiguous() and tuple(place.shape) == (n, 2)
-        assert canvas.dtype == torch.uint8 and canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == 3 and canvas.shape[2] == 3
-        x0, y0, x1, y1 = (int(v) for v in clip)
+        x0, y0, x1, y1 = self._canvas_args(n, place, canvas, clip)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         scratch = self._scratch('_jpeg_ws', int(self._lib.bq_jpeg_canvas_scratch_bytes(n, seg_w, seg_h)), scratch)
         assert scratch.is_cuda and scratch.is_contiguous()
@@ -335,8 +365,7 @@ class Engine:
     def jpeg_canvas_scratch(self, n, seg_w, seg_h):
         """Coefficient space for ``jpeg_decode_canvas`` over ``n`` segments (``bq_jpeg_canvas_scratch_bytes``: 393 KB per 256 x 256
         segment, for 2 048 segments at most; a longer call works in rounds)."""
-        return torch.empty(int(self._lib.bq_jpeg_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h))), dtype=torch.uint8,
-                           device=self.device)
+        return self._bytes(self._lib.bq_jpeg_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h)))
 
     def j2k_decode_canvas(self, desc, blocks, cw, seg_w, seg_h, place, canvas, clip, ycc=False, scratch=None):
         """A slide page's own JPEG 2000 tiles decoded on the device INTO a canvas (``bq_j2k_decode_canvas``, kernels_j2k.hip: tier
@@ -350,9 +379,7 @@ class Engine:
         assert desc.dtype == torch.int32 and desc.is_cuda and desc.is_contiguous() and tuple(desc.shape) == (n, 32)
         assert blocks.dtype == torch.int32 and blocks.is_cuda and blocks.is_contiguous() and blocks.dim() == 2 and blocks.shape[1] == 12
         assert cw.dtype == torch.uint8 and cw.is_cuda and cw.is_contiguous()
-        assert place.dtype == torch.int32 and place.is_cuda and place.is_contiguous() and tuple(place.shape) == (n, 2)
-        assert canvas.dtype == torch.uint8 and canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == 3 and canvas.shape[2] == 3
-        x0, y0, x1, y1 = (int(v) for v in clip)
+        x0, y0, x1, y1 = self._canvas_args(n, place, canvas, clip)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         scratch = self._scratch('_j2k_ws', int(self._lib.bq_j2k_canvas_scratch_bytes(n, seg_w, seg_h)), scratch)
         assert scratch.is_cuda and scratch.is_contiguous()
@@ -365,8 +392,7 @@ class Engine:
     def j2k_canvas_scratch(self, n, seg_w, seg_h):
         """Plane space for ``j2k_decode_canvas`` over ``n`` segments (``bq_j2k_canvas_scratch_bytes``: 24 bytes a pixel, 1.5 MB per
         256 x 256 segment, for 256 segments at most; a longer call works in rounds)."""
-        return torch.empty(int(self._lib.bq_j2k_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h))), dtype=torch.uint8,
-                           device=self.device)
+        return self._bytes(self._lib.bq_j2k_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h)))
 
     def jpeg_encode(self, tiles, quality=95, subsampling='4:2:0', cap=None, scratch=None):
         """n tiles encoded as baseline JPEG on the device (``bq_jpeg_encode``, kernels_jpeg_encode.hip): ``tiles`` uint8 NHWC
@@ -382,28 +408,14 @@ class Engine:
         n, px, sub, quality = int(tiles.shape[0]), int(tiles.shape[1]), jpeg_subsampling(subsampling), int(quality)
         if cap is None:                     # (about 2 bits a sample at quality 95; the retry covers what this misses)
             cap = n * (1024 + px * px * 3 // (4 if quality < 98 else 2))
-        scratch = self._scratch('_jpeg_enc_ws', int(self._lib.bq_jpeg_encode_scratch_bytes(n, max(px, 1), sub)), scratch)
-        off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-        status = torch.zeros(n, dtype=torch.int32, device=self.device)
-        self.jpeg_encode_calls = 0
-        while True:
-            out = torch.empty(max(int(cap), 1), dtype=torch.uint8, device=self.device)
-            self._check(self._lib.bq_jpeg_encode(self._ctx, _ptr(tiles), n, px, quality, sub, _ptr(out), int(cap), _ptr(off), _ptr(status),
-                                                 _ptr(scratch), scratch.numel(), self._stream()))
-            self.jpeg_encode_calls += 1
-            offsets = off.cpu()
-            total = int(offsets[-1])
-            if n == 0 or total <= int(cap):
-                return out[:total], offsets
-            assert self.jpeg_encode_calls == 1 and bool((status & 1).any()), 'bq_jpeg_encode: the exact total did not fit'
-            cap = total
+        return self._encode('jpeg_encode', '_jpeg_enc_ws', 'jpeg_encode_calls', tiles, cap, scratch,
+                            self._lib.bq_jpeg_encode_scratch_bytes(n, max(px, 1), sub), quality, sub)
 
     def jpeg_encode_scratch(self, n, px=TILE_PX, subsampling='4:2:0'):
         """Scratch for ``jpeg_encode`` over ``n`` tiles (``bq_jpeg_encode_scratch_bytes``: 889 KB per 299-px tile at 4:2:0, for 256
         tiles at most -- 228 MB; a longer call works in rounds)."""
         from .tfrecord_native import jpeg_subsampling
-        return torch.empty(int(self._lib.bq_jpeg_encode_scratch_bytes(int(n), int(px), jpeg_subsampling(subsampling))), dtype=torch.uint8,
-                           device=self.device)
+        return self._bytes(self._lib.bq_jpeg_encode_scratch_bytes(int(n), int(px), jpeg_subsampling(subsampling)))
 
     def png_encode(self, tiles, cap=None, scratch=None):
         """n tiles encoded as PNG on the device (``bq_png_encode``, kernels_png_encode.hip): ``tiles`` uint8 NHWC [n, px, px, 3]
@@ -419,26 +431,13 @@ class Engine:
         n, px = int(tiles.shape[0]), int(tiles.shape[1])
         if cap is None:
             cap = n * (1024 + px * px * 3 // 2)
-        scratch = self._scratch('_png_enc_ws', int(self._lib.bq_png_encode_scratch_bytes(n, max(px, 1))), scratch)
-        off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-        status = torch.zeros(n, dtype=torch.int32, device=self.device)
-        self.png_encode_calls = 0
-        while True:
-            out = torch.empty(max(int(cap), 1), dtype=torch.uint8, device=self.device)
-            self._check(self._lib.bq_png_encode(self._ctx, _ptr(tiles), n, px, _ptr(out), int(cap), _ptr(off), _ptr(status), _ptr(scratch),
-                                                scratch.numel(), self._stream()))
-            self.png_encode_calls += 1
-            offsets = off.cpu()
-            total = int(offsets[-1])
-            if n == 0 or total <= int(cap):
-                return out[:total], offsets
-            assert self.png_encode_calls == 1 and bool((status & 1).any()), 'bq_png_encode: the exact total did not fit'
-            cap = total
+        return self._encode('png_encode', '_png_enc_ws', 'png_encode_calls', tiles, cap, scratch,
+                            self._lib.bq_png_encode_scratch_bytes(n, max(px, 1)))
 
     def png_encode_scratch(self, n, px=TILE_PX):
         """Scratch for ``png_encode`` over ``n`` tiles (``bq_png_encode_scratch_bytes``: 1.71 MB per 299-px tile, for 128 tiles at
         most -- 218 MB; a longer call works in rounds)."""
-        return torch.empty(int(self._lib.bq_png_encode_scratch_bytes(int(n), int(px))), dtype=torch.uint8, device=self.device)
+        return self._bytes(self._lib.bq_png_encode_scratch_bytes(int(n), int(px)))
 
     def tile_resample(self, canvas, origin, src_px, px=TILE_PX, out=None):
         """The heatmap's tile grid cut from a slide canvas and resampled on the device (``bq_tile_resample``,

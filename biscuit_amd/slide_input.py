@@ -7,6 +7,8 @@ import os
 import numpy as np
 import torch
 
+from . import tfrecord_native as tn
+
 DECODE_STATS = ('gpu_bands', 'host_bands', 'segments')      # bands the device decoded, bands the host read, segments decoded
 
 
@@ -144,43 +146,39 @@ def band_stats():
     return dict.fromkeys(DECODE_STATS + ('bands_read', 'gray_dropped'), 0)
 
 
+def _pack_jpeg(sg):
+    scan, desc, tables = tn.extract_jpeg_segments(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h, sg.jpeg_tables)
+    return scan, desc.view(np.int32), tables
+
+
+# ``BandSegments.codec`` -> how ``decode_band`` decodes such a band: the host's extractor (-> the packed arrays the engine call
+# takes first, or ValueError -- UnsupportedImage is one -- for a segment it refuses), the ``Engine`` method, the keywords the
+# method takes from the segments beside the common ones, and the longest side of a segment the device decoder takes (None: any).
+BAND_CODECS = {
+    'jpeg': (_pack_jpeg, 'jpeg_decode_canvas', lambda sg: {}, None),
+    'j2k': (lambda sg: tn.j2k_extract(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h), 'j2k_decode_canvas',
+            lambda sg: {'ycc': sg.ycc}, tn.J2K_MAX_SIDE),
+}
+
+
 def decode_band(engine, sg):
-    """A band's canvas decoded on the device from its raw JPEG or JPEG 2000 tiles (``wsi.BandSegments``, by its ``codec``):
-    extract on the host, upload what the extractor packed and the places, fill the canvas with 255, decode, read the status
-    once.  -> the canvas (uint8 [H, W, 3] on the device), or None when the extractor refuses a segment or any status is not 0."""
-    from . import tfrecord_native as tn
-    if sg.codec == 'j2k':
-        return decode_band_j2k(engine, sg)
+    """A band's canvas decoded on the device from its raw JPEG or JPEG 2000 tiles (``wsi.BandSegments``, by its row of
+    ``BAND_CODECS``): extract on the host, upload what the extractor packed and the places, fill the canvas with 255, decode, read
+    the status once.  -> the canvas (uint8 [H, W, 3] on the device), or None when a segment is larger than the device decoder
+    takes, the extractor refuses one, or any status is not 0."""
+    extract, entry, keywords, max_side = BAND_CODECS[sg.codec]
+    if max_side and max(sg.seg_w, sg.seg_h) > max_side:
+        return None
     try:
-        scan, desc, tables = tn.extract_jpeg_segments(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h, sg.jpeg_tables)
-    except ValueError:                                                       # (UnsupportedImage is one)
+        packed = extract(sg)
+    except ValueError:
         return None
     dev = engine.device
     canvas = torch.full(tuple(sg.shape) + (3,), 255, dtype=torch.uint8, device=dev)
     if len(sg) == 0:
         return canvas
-    status = engine.jpeg_decode_canvas(torch.from_numpy(scan).to(dev), torch.from_numpy(desc.view(np.int32)).to(dev),
-                                       torch.from_numpy(tables).to(dev), sg.seg_w, sg.seg_h, torch.from_numpy(sg.place).to(dev),
-                                       canvas, sg.clip)
-    return None if bool(status.any().item()) else canvas
-
-
-def decode_band_j2k(engine, sg):
-    """``decode_band`` for JPEG 2000 segments: tier 2 on the host (``tfrecord_native.j2k_extract``), the rest on the device
-    (``Engine.j2k_decode_canvas``)."""
-    from . import tfrecord_native as tn
-    if sg.seg_w > 512 or sg.seg_h > 512:
-        return None
-    try:
-        desc, blocks, cw = tn.j2k_extract(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h)
-    except ValueError:                                                       # outside the device's subset, or damaged
-        return None
-    dev = engine.device
-    canvas = torch.full(tuple(sg.shape) + (3,), 255, dtype=torch.uint8, device=dev)
-    if len(sg) == 0:
-        return canvas
-    status = engine.j2k_decode_canvas(torch.from_numpy(desc).to(dev), torch.from_numpy(blocks).to(dev), torch.from_numpy(cw).to(dev),
-                                      sg.seg_w, sg.seg_h, torch.from_numpy(sg.place).to(dev), canvas, sg.clip, ycc=sg.ycc)
+    status = getattr(engine, entry)(*(torch.from_numpy(a).to(dev) for a in packed), sg.seg_w, sg.seg_h, torch.from_numpy(sg.place).to(dev),
+                                    canvas, sg.clip, **keywords(sg))
     return None if bool(status.any().item()) else canvas
 
 

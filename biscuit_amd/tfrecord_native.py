@@ -197,18 +197,24 @@ def extract_jpeg_segments(data, offsets, lengths, seg_w, seg_h, jpeg_tables=None
         return scan[:used.value], desc, tables[:nt.value].copy()
 
 
+def _canvas_arrays(n, place, canvas, clip):
+    """What the CPU canvas decoders take alike -> ``(place int32 [n, 2], clip int32 [4], status int32 [n] of zeros)``."""
+    place = np.ascontiguousarray(place, np.int32).reshape(-1, 2)
+    clip = np.ascontiguousarray(clip, np.int32).reshape(4)
+    assert place.shape == (n, 2)
+    assert canvas.dtype == np.uint8 and canvas.ndim == 3 and canvas.shape[2] == 3 and canvas.flags.c_contiguous and canvas.flags.writeable
+    return place, clip, np.zeros(n, np.int32)
+
+
 def jpeg_decode_canvas(scan, desc, tables, seg_w, seg_h, place, canvas, clip, threads=None):
     """The device canvas decoder's routines (csrc/jpeg_device.h) on the CPU (``bqio_jpeg_decode_canvas``): the segments
     ``extract_jpeg_segments`` packed, written INTO ``canvas`` (uint8 [H, W, 3], C-contiguous, modified in place) at ``place`` int32
     [n, 2] (x, y), clipped to ``clip`` = (x0, y0, x1, y1) in canvas coordinates.  -> status int32 [n].  What
     ``Engine.jpeg_decode_canvas`` computes, byte for byte and status for status.  For tests."""
     scan, desc, tables = np.ascontiguousarray(scan, np.uint8), np.ascontiguousarray(desc, np.uint32), np.ascontiguousarray(tables, np.uint8)
-    place = np.ascontiguousarray(place, np.int32).reshape(-1, 2)
-    clip = np.ascontiguousarray(clip, np.int32).reshape(4)
     n = desc.shape[0]
-    assert desc.shape == (n, 4) and place.shape == (n, 2) and tables.size % jpeg_table_bytes() == 0
-    assert canvas.dtype == np.uint8 and canvas.ndim == 3 and canvas.shape[2] == 3 and canvas.flags.c_contiguous and canvas.flags.writeable
-    status = np.zeros(n, np.int32)
+    assert desc.shape == (n, 4) and tables.size % jpeg_table_bytes() == 0
+    place, clip, status = _canvas_arrays(n, place, canvas, clip)
     e = lib().bqio_jpeg_decode_canvas(scan.ctypes.data, desc.ctypes.data, tables.ctypes.data, tables.size // jpeg_table_bytes(), n,
                                       int(seg_w), int(seg_h), place.ctypes.data, canvas.ctypes.data, canvas.shape[0], canvas.shape[1],
                                       clip.ctypes.data, status.ctypes.data, threads or default_threads())
@@ -218,6 +224,7 @@ def jpeg_decode_canvas(scan, desc, tables, seg_w, seg_h, place, canvas, clip, th
 
 
 J2K_SUBSET, J2K_DAMAGED = 32, 64        # a segment's status from ``j2k_extract`` (csrc/j2k_device.h); 16: refused by the decoder
+J2K_MAX_SIDE = 512                      # the longest segment side the JPEG 2000 decoder takes (MAX_SIDE of csrc/j2k_device.h)
 
 
 def j2k_extract(data, offsets, lengths, seg_w, seg_h, threads=None, strict=True):
@@ -263,12 +270,9 @@ def j2k_decode_canvas(desc, blocks, cw, seg_w, seg_h, place, canvas, clip, ycc=F
     in sub-band layout).  What ``Engine.j2k_decode_canvas`` computes, byte for byte and status for status.  For tests."""
     desc, blocks = np.ascontiguousarray(desc, np.int32), np.ascontiguousarray(blocks, np.int32).reshape(-1, 12)
     cw = np.ascontiguousarray(cw, np.uint8)
-    place = np.ascontiguousarray(place, np.int32).reshape(-1, 2)
-    clip = np.ascontiguousarray(clip, np.int32).reshape(4)
     n = desc.shape[0]
-    assert desc.shape == (n, 32) and place.shape == (n, 2)
-    assert canvas.dtype == np.uint8 and canvas.ndim == 3 and canvas.shape[2] == 3 and canvas.flags.c_contiguous and canvas.flags.writeable
-    status = np.zeros(n, np.int32)
+    assert desc.shape == (n, 32)
+    place, clip, status = _canvas_arrays(n, place, canvas, clip)
     planes = np.zeros((n, 3, int(seg_h), int(seg_w)), np.int32) if t1 else None
     e = lib().bqio_j2k_decode_canvas(desc.ctypes.data, n, blocks.ctypes.data, len(blocks), cw.ctypes.data, cw.size, int(seg_w), int(seg_h),
                                      int(bool(ycc)), place.ctypes.data, canvas.ctypes.data, canvas.shape[0], canvas.shape[1],
@@ -308,28 +312,33 @@ def jpeg_encode_header(px, quality=95, subsampling='4:2:0'):
     return out.tobytes()
 
 
-def jpeg_encode(tiles, quality=95, subsampling='4:2:0', cap=None):
-    """uint8 [n, px, px, 3] -> ``(buffer uint8 [bytes], offsets int64 [n + 1], status int32 [n])``: the files Pillow's
-    ``save(buf, 'JPEG', quality=quality, subsampling=subsampling)`` writes, back to back (``bqio_jpeg_encode``: the device
-    encoder's routines, csrc/jpeg_encode_device.h, on the CPU).  ``cap``: the buffer's size; None sizes it exactly with a first
-    call.  A file that would end beyond ``cap`` is left out and its status is 1.  ValueError outside the encoder's subset.
-    What ``Engine.jpeg_encode`` computes, byte for byte.  For tests."""
+def _encode_sized(name, tiles, cap, *mid_args):
+    """The CPU encoders' calls ``bqio_<name>(tiles, n, px, *mid_args, out, cap, off, status)``: with ``cap`` None a first one without
+    a buffer, which states the exact size, then the one that writes.  -> ``(buffer[:cap], offsets, status)``."""
     tiles = np.ascontiguousarray(tiles, np.uint8)
     assert tiles.ndim == 4 and tiles.shape[1] == tiles.shape[2] and tiles.shape[3] == 3, tiles.shape
-    n, px, sub = tiles.shape[0], tiles.shape[1], jpeg_subsampling(subsampling)
+    n, px = tiles.shape[0], tiles.shape[1]
     off, status = np.zeros(n + 1, np.int64), np.zeros(n, np.int32)
 
     def call(out, cap):
-        e = lib().bqio_jpeg_encode(tiles.ctypes.data, n, px, int(quality), sub, out.ctypes.data if out is not None else None, cap,
-                                   off.ctypes.data, status.ctypes.data)
-        if e != 0:
-            raise ValueError('bqio_jpeg_encode: ' + lib().bqio_jpeg_encode_last_error().decode())
+        if getattr(lib(), 'bqio_' + name)(tiles.ctypes.data, n, px, *mid_args, out.ctypes.data if out is not None else None, cap,
+                                          off.ctypes.data, status.ctypes.data) != 0:
+            raise ValueError(f'bqio_{name}: ' + getattr(lib(), f'bqio_{name}_last_error')().decode())
     if cap is None:
         call(None, 0)
         cap = int(off[-1])
     out = np.zeros(max(int(cap), 1), np.uint8)
     call(out, int(cap))
     return out[:int(cap)], off, status
+
+
+def jpeg_encode(tiles, quality=95, subsampling='4:2:0', cap=None):
+    """uint8 [n, px, px, 3] -> ``(buffer uint8 [bytes], offsets int64 [n + 1], status int32 [n])``: the files Pillow's
+    ``save(buf, 'JPEG', quality=quality, subsampling=subsampling)`` writes, back to back (``bqio_jpeg_encode``: the device
+    encoder's routines, csrc/jpeg_encode_device.h, on the CPU).  ``cap``: the buffer's size; None sizes it exactly with a first
+    call.  A file that would end beyond ``cap`` is left out and its status is 1.  ValueError outside the encoder's subset.
+    What ``Engine.jpeg_encode`` computes, byte for byte.  For tests."""
+    return _encode_sized('jpeg_encode', tiles, cap, int(quality), jpeg_subsampling(subsampling))
 
 
 def png_encode(tiles, cap=None):
@@ -338,22 +347,7 @@ def png_encode(tiles, cap=None):
     Pillow's; the deflate stream is the project's own.  ``cap``: the buffer's size; None sizes it exactly with a first call.  A
     file that would end beyond ``cap`` is left out and its status is 1.  ValueError outside 1 <= px <= 4096.  What
     ``Engine.png_encode`` computes, byte for byte.  For tests."""
-    tiles = np.ascontiguousarray(tiles, np.uint8)
-    assert tiles.ndim == 4 and tiles.shape[1] == tiles.shape[2] and tiles.shape[3] == 3, tiles.shape
-    n, px = tiles.shape[0], tiles.shape[1]
-    off, status = np.zeros(n + 1, np.int64), np.zeros(n, np.int32)
-
-    def call(out, cap):
-        e = lib().bqio_png_encode(tiles.ctypes.data, n, px, out.ctypes.data if out is not None else None, cap, off.ctypes.data,
-                                  status.ctypes.data)
-        if e != 0:
-            raise ValueError('bqio_png_encode: ' + lib().bqio_png_encode_last_error().decode())
-    if cap is None:
-        call(None, 0)
-        cap = int(off[-1])
-    out = np.zeros(max(int(cap), 1), np.uint8)
-    call(out, int(cap))
-    return out[:int(cap)], off, status
+    return _encode_sized('png_encode', tiles, cap)
 
 
 def inflate_fallbacks():
@@ -437,6 +431,16 @@ class NativeReader:
         e = self._lib.bqio_probe(self._h, first, count, tile_px, C.byref(bad))
         return None if e == 0 else int(bad.value)
 
+    def _raise(self, e, bad, tile_px, full=None):
+        """The end of a reading call that answered ``e``: nothing for 0, otherwise the exception of the code -- ``full`` (a
+        MemoryError: the caller's buffer was too small) in place of the plain ``IOError`` where the caller found that."""
+        if e == ERR_UNSUPPORTED:
+            raise UnsupportedImage(bad.value)
+        if e == ERR_FORMAT:       # same exception the Python reader raises for a tile of the wrong size
+            raise ValueError(f'{self.path}: record {bad.value}: tile size differs from {(tile_px, tile_px, 3)}')
+        if e != 0:
+            raise full or IOError(f'{self.path}: {self._lib.bqio_last_error(self._h).decode()} (record {bad.value})')
+
     def extract_z(self, first, count, tile_px, out_z, off, length, threads=None):
         """The zlib streams of records [first, first + count) packed into ``out_z`` (uint8 array, usually pinned) for the device
         inflate (``Engine.png_inflate``): ``off`` / ``length`` (uint32 [count]) receive every stream's offset (a multiple of 16)
@@ -449,14 +453,8 @@ class NativeReader:
         bad = _i64(-1)
         e = self._lib.bqio_extract_z(self._h, first, count, tile_px, out_z.ctypes.data, out_z.size, off.ctypes.data,
                                      length.ctypes.data, loc.ctypes.data, C.byref(used), threads or default_threads(), C.byref(bad))
-        if e == ERR_UNSUPPORTED:
-            raise UnsupportedImage(bad.value)
-        if e == ERR_FORMAT:
-            raise ValueError(f'{self.path}: record {bad.value}: tile size differs from {(tile_px, tile_px, 3)}')
-        if e != 0 and used.value > out_z.size:
-            raise MemoryError(f'extract_z: {used.value} bytes needed, {out_z.size} given', used.value)
-        if e != 0:
-            raise IOError(f'{self.path}: {self._lib.bqio_last_error(self._h).decode()} (record {bad.value})')
+        full = used.value > out_z.size and MemoryError(f'extract_z: {used.value} bytes needed, {out_z.size} given', used.value)
+        self._raise(e, bad, tile_px, full)
         return int(used.value), loc
 
     def extract_jpeg(self, first, count, tile_px, out_scan, desc, tables, threads=None):
@@ -478,15 +476,9 @@ class NativeReader:
             args = (out_scan.ctypes.data, out_scan.size, desc.ctypes.data, tables.ctypes.data, tables.size // jpeg_table_bytes())
         e = self._lib.bqio_extract_jpeg(self._h, first, count, tile_px, *args, C.byref(nt), loc.ctypes.data, C.byref(used),
                                         threads or default_threads(), C.byref(bad))
-        if e == ERR_UNSUPPORTED:
-            raise UnsupportedImage(bad.value)
-        if e == ERR_FORMAT:
-            raise ValueError(f'{self.path}: record {bad.value}: tile size differs from {(tile_px, tile_px, 3)}')
-        if e != 0 and bad.value < 0 and out_scan is not None and (used.value > args[1] or nt.value > args[4]):
-            raise MemoryError(f'extract_jpeg: {used.value} bytes and {nt.value} table sets needed, {args[1]} and {args[4]} given',
-                              used.value, nt.value)
-        if e != 0:
-            raise IOError(f'{self.path}: {self._lib.bqio_last_error(self._h).decode()} (record {bad.value})')
+        full = bad.value < 0 and out_scan is not None and (used.value > args[1] or nt.value > args[4]) and MemoryError(
+            f'extract_jpeg: {used.value} bytes and {nt.value} table sets needed, {args[1]} and {args[4]} given', used.value, nt.value)
+        self._raise(e, bad, tile_px, full)
         return int(used.value), int(nt.value), loc
 
     def decode(self, first=0, count=None, tile_px=299, out=None, threads=None, rows=False):
@@ -504,10 +496,5 @@ class NativeReader:
         bad = _i64(-1)
         fn = self._lib.bqio_decode_rows if rows else self._lib.bqio_decode
         e = fn(self._h, first, count, tile_px, out.ctypes.data, loc.ctypes.data, threads or default_threads(), C.byref(bad))
-        if e == ERR_UNSUPPORTED:
-            raise UnsupportedImage(bad.value)
-        if e == ERR_FORMAT:       # same exception the Python reader raises for a tile of the wrong size
-            raise ValueError(f'{self.path}: record {bad.value}: tile size differs from {(tile_px, tile_px, 3)}')
-        if e != 0:
-            raise IOError(f'{self.path}: {self._lib.bqio_last_error(self._h).decode()} (record {bad.value})')
+        self._raise(e, bad, tile_px)
         return out, loc

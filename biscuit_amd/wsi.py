@@ -107,6 +107,9 @@ class _Page:
         self.width, self.height = int(g(256)[0]), int(g(257)[0])
         self.bits = tuple(g(258, (1,)))
         self.compression = int(g(259, (1,))[0])
+        # the image codec of the segments, where they are images; ycc: a JPEG 2000 segment's components are YCbCr (33003)
+        self.codec = 'jpeg' if self.compression == 7 else 'j2k' if self.compression in J2K_COMPRESSIONS else None
+        self.ycc = self.compression == 33003
         self.photometric = int(g(262, (2,))[0])
         self.samples = int(g(277, (1,))[0])
         self.planar = int(g(284, (1,))[0])
@@ -225,7 +228,7 @@ class TiffSlide:
                 levels.append(p)
         for li, p in enumerate(levels):
             p.check()
-            if p.compression in J2K_COMPRESSIONS:
+            if p.codec == 'j2k':
                 j2k_probe(self._raw_segment(p, 0, li), p.tw, p.th)
         self.levels = levels
         self.dimensions = (base.width, base.height)
@@ -307,15 +310,11 @@ class TiffSlide:
         p = self.levels[li]
         raw = self._raw_segment(p, index, li)
         rows = p.th if p.tiled else min(p.th, p.height - (index * p.th))
-        if p.compression == 7:
-            img = self._jpeg(p, raw)
+        if p.codec:
+            img = (self._jpeg if p.codec == 'jpeg' else self._j2k)(p, raw)
             if img.shape[0] < rows or img.shape[1] < p.tw:
-                raise SlideError(f'{self.path}: JPEG segment {index} of level {li} is smaller than its tile')
-            img = img[:rows, :p.tw]
-        elif p.compression in J2K_COMPRESSIONS:
-            img = self._j2k(p, raw)
-            if img.shape[0] < rows or img.shape[1] < p.tw:
-                raise SlideError(f'{self.path}: JPEG 2000 segment {index} of level {li} is smaller than its tile')
+                name = 'JPEG' if p.codec == 'jpeg' else 'JPEG 2000'
+                raise SlideError(f'{self.path}: {name} segment {index} of level {li} is smaller than its tile')
             img = img[:rows, :p.tw]
         else:
             if p.compression in (8, 32946):
@@ -367,7 +366,7 @@ class TiffSlide:
             a = np.asarray(im)
         except (OSError, SyntaxError) as e:
             raise SlideError(f'{self.path}: a JPEG 2000 tile does not decode: {e}') from None
-        if p.compression == 33003:
+        if p.ycc:
             a = np.asarray(Image.merge('YCbCr', [Image.fromarray(np.ascontiguousarray(a[:, :, c])) for c in range(3)]).convert('RGB'))
         return a
 
@@ -397,7 +396,7 @@ class TiffSlide:
         33003, 33005 or 34712 with TileWidth / TileLength: strips, deflate and uncompressed pages stay on ``read_region``).  Read through ``_segment``'s bounds checks -- a byte count beyond the
         file's size, a segment that does not lie inside the file, more segment bytes than the file holds: ``SlideError``."""
         p = self.levels[level]
-        if not (p.tiled and (p.compression == 7 or p.compression in J2K_COMPRESSIONS)):
+        if not (p.tiled and p.codec):
             return None
         if not (0 < w <= 1 << 16 and 0 < h <= 1 << 16):
             raise SlideError(f'region of {w} x {h} pixels')
@@ -418,8 +417,7 @@ class TiffSlide:
         return BandSegments(shape=(h, w), data=np.frombuffer(b''.join(chunks), np.uint8), offsets=offsets, lengths=lengths,
                             place=np.array(place, np.int32).reshape(-1, 2),
                             clip=(max(0, -x), max(0, -y), min(w, p.width - x), min(h, p.height - y)),
-                            seg_w=p.tw, seg_h=p.th, jpeg_tables=p.jpeg_tables, codec='jpeg' if p.compression == 7 else 'j2k',
-                            ycc=p.compression == 33003)
+                            seg_w=p.tw, seg_h=p.th, jpeg_tables=p.jpeg_tables, codec=p.codec, ycc=p.ycc)
 
     def close(self):
         self._f.close()

@@ -1,6 +1,8 @@
 // A program of its own over csrc/png_encode_device.h, for a build with -fsanitize=address,undefined (tests/test_png_encode.py
 // builds and runs it): flats, an LCG noise tile and a ramp at 1, 5, 74 and 299 px through the header's serial encoder; every
 // file's chunks are walked (CRC-32 through zlib's crc32), the IDAT payloads inflated with zlib and un-filtered back to the tile.
+// And the round rule the encoder's entry point shares with the other codecs (csrc/bq_rounds.h) against the expression it replaced.
+#include "bq_rounds.h"
 #include "png_encode_device.h"
 
 #include <zlib.h>
@@ -64,9 +66,25 @@ static int check(const std::vector<uint8_t>& tile, int px, int kind) {
     return 0;
 }
 
+// round_items over scratch sizes around one item, around `align` items and beyond the cap, for the aligns and per-item sizes in use
+static int check_rounds() {
+    for (size_t per : {(size_t)1, (size_t)7, (size_t)393216})
+        for (size_t align : {(size_t)1, (size_t)64})
+            for (size_t s : {(size_t)0, per - 1, per, 63 * per, 64 * per, 100 * per, 40000 * per}) {
+                size_t m = s / per;
+                if (m > 32768) m = 32768;
+                if (m >= align) m &= ~(align - 1);
+                if (round_items(s, per, align) != m) {
+                    std::printf("FAILED: round_items(%zu, %zu, %zu) = %zu, not %zu\n", s, per, align, round_items(s, per, align), m);
+                    return 1;
+                }
+            }
+    return round_cap(3, 256) == 3 && round_cap(256, 256) == 256 && round_cap(300, 256) == 256 ? 0 : 1;
+}
+
 int main() {
     const int sizes[4] = {1, 5, 74, 299};
-    int bad = 0, files = 0;
+    int bad = check_rounds(), files = 0;
     for (int px : sizes) {
         std::vector<uint8_t> t((size_t)px * px * 3);
         for (int kind = 0; kind < 5; ++kind) {

@@ -13,6 +13,7 @@ from biscuit_amd.synthetic import make_tiles
 from biscuit_amd.weights import synthetic_weights
 from biscuit_amd.wsi import TiffSlide
 from tests import _jpeg_cases as jc
+from tests import _j2k_cases as j2c
 from tests import _jpeg_encode_cases as ec
 from tests import _roi_ref as roi_ref
 from tests import _wsi_jpeg_cases as wj
@@ -23,7 +24,8 @@ pytestmark = pytest.mark.gpu
 # every class a tool's entry point opens; bq_stain_lab_stats, bq_png_unfilter, bq_png_unfilter_strided and bq_slide_finish open none
 TOOL_CLASSES = {'stage_u8_standardize', 'stage_f32_to_planar', 'stain_reinhard_fast', 'stain_macenko', 'stain_macenko_stats',
                 'range_key', 'range_screen', 'png_inflate', 'jpeg_decode', 'jpeg_decode_canvas', 'jpeg_encode_pixel',
-                'jpeg_encode_size', 'jpeg_encode_pack', 'jpeg_encode_stuff', 'tile_resample', 'tile_grayspace', 'heatmap_render',
+                'jpeg_encode_size', 'jpeg_encode_pack', 'jpeg_encode_stuff', 'png_encode_filter', 'png_encode_match', 'png_encode_code',
+                'png_encode_pack', 'j2k_t1', 'j2k_idwt', 'j2k_store', 'tile_resample', 'tile_grayspace', 'heatmap_render',
                 'tissue_blur', 'tissue_cells', 'tissue_focus', 'tissue_cells_union', 'roi_plane', 'slide_reduce', 'roc_youden'}
 
 
@@ -64,6 +66,21 @@ def _jpeg_tools(eng, tmp_path):
         assert len(sg) == 1 and int(status[0]) == 0 and np.array_equal(canvas.cpu().numpy(), s.read_region(0, 0, 0, 16, 16))
     buf, off = eng.jpeg_encode(_up(eng, ec.tile(8, 'noise')[None].copy()), 95, '4:2:0')
     assert ec.split(buf.cpu().numpy(), off) == [ec.pillow(8, 'noise', 95, '4:2:0')]
+
+
+def _png_encode_and_j2k_tools(eng):
+    """One 8-px tile encoded as PNG, one lossless 16 x 16 JPEG 2000 segment decoded into a canvas."""
+    tile = ec.tile(8, 'noise')[None].copy()
+    buf, off = eng.png_encode(_up(eng, tile))
+    want, want_off, _ = tn.png_encode(tile)
+    assert np.array_equal(off.numpy(), want_off) and np.array_equal(buf.cpu().numpy(), want)
+    a = _img(16, 16, 11)
+    raw = j2c.encode(a, False, num_resolutions=2, mct=1)
+    desc, blocks, cw = tn.j2k_extract(np.frombuffer(raw, np.uint8), [0], [len(raw)], 16, 16)
+    canvas = torch.full((16, 16, 3), 255, dtype=torch.uint8, device=eng.device)
+    status = eng.j2k_decode_canvas(_up(eng, desc), _up(eng, blocks), _up(eng, cw), 16, 16, _up(eng, np.zeros((1, 2), np.int32)), canvas,
+                                   (0, 0, 16, 16))
+    assert int(status[0]) == 0 and np.array_equal(canvas.cpu().numpy(), a)
 
 
 def _heatmap_tools(eng):
@@ -108,6 +125,7 @@ def test_every_tool_opens_its_profiling_class_and_no_other(tmp_path):
         RangeScreen(eng, k=1).update(tiles)
         _png_tools(eng)
         _jpeg_tools(eng, tmp_path)
+        _png_encode_and_j2k_tools(eng)
         _heatmap_tools(eng)
         _mask_tools(eng)
         mean = _up(eng, np.array([[0.25, 0.75]], np.float32))
@@ -139,8 +157,10 @@ def test_close_lets_go_of_every_device_tensor(tmp_path):
     _mask_tools(eng)                # _tissue_sdiv, _tissue_taps, _host_held
     _png_tools(eng)                 # _inflate_ws
     _jpeg_tools(eng, tmp_path)      # _jpeg_ws, _jpeg_enc_ws
+    _png_encode_and_j2k_tools(eng)  # _png_enc_ws, _j2k_ws
     held = {k: len(_device_tensors(v)) for k, v in vars(eng).items() if _device_tensors(v)}
-    assert {'_resample_taps', '_grayspace_limit', '_tissue_sdiv', '_tissue_taps', '_inflate_ws', '_jpeg_ws', '_jpeg_enc_ws'} <= set(held), held
+    assert {'_resample_taps', '_grayspace_limit', '_tissue_sdiv', '_tissue_taps', '_inflate_ws', '_jpeg_ws', '_jpeg_enc_ws', '_png_enc_ws',
+            '_j2k_ws'} <= set(held), held
     eng.close()
     assert {k: v for k, v in vars(eng).items() if _device_tensors(v)} == {}
     eng.close()

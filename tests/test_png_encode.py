@@ -173,7 +173,8 @@ def test_bad_arguments_are_refused(px):
 @pytest.mark.skipif(shutil.which('g++') is None, reason='no g++')
 def test_selfcheck_under_the_sanitizers(tmp_path):
     """tests/png_encode_selfcheck.cpp -- the header's routines over flats, noise and a ramp at 1, 5, 74 and 299 px, inflated with
-    zlib -- built with AddressSanitizer and UBSan as a program of its own and run."""
+    zlib, and ``round_items`` (csrc/bq_rounds.h) against the expression it replaced -- built with AddressSanitizer and UBSan as a
+    program of its own and run."""
     exe = str(tmp_path / 'png_encode_selfcheck')
     build = subprocess.run(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
                             '-I', os.path.join(ROOT, 'biscuit_amd', 'csrc'), os.path.join(ROOT, 'tests', 'png_encode_selfcheck.cpp'),
