@@ -173,8 +173,10 @@ int bq_png_unfilter(bq_ctx* ctx, const uint8_t* d_rows, int n, int px, uint8_t* 
  * i * rows_stride (rows_stride a multiple of 4, >= px (1 + 3 px) + 4), one stream per lane.  d_status[i] = 0 iff stream i is a
  * well-formed zlib stream that inflates to exactly px (1 + 3 px) bytes with a matching Adler-32 (what zlib's uncompress() accepts)
  * and every row's filter-type byte is 0..4 (what a PNG decoder accepts);
- * any other value: the tile's rows are undefined and the caller decodes that record on the host.  d_scratch: table space,
- * bq_png_inflate_scratch_bytes(n).  Follow with bq_png_unfilter_strided.  No reference counterpart (tf.io.decode_png under tf.data). */
+ * any other value: the tile's rows are undefined and the caller decodes that record on the host.  The bytes of a stride behind
+ * its px (1 + 3 px) row bytes are unspecified (the literal collector stores whole dwords; bq_png_unfilter_strided does not read
+ * them): the one output region of this header that is.  d_scratch: table space,
+ * bq_png_inflate_scratch_bytes(n), contents unspecified on entry like every scratch buffer and workspace here.  Follow with bq_png_unfilter_strided.  No reference counterpart (tf.io.decode_png under tf.data). */
 size_t bq_png_inflate_scratch_bytes(int n);
 int bq_png_inflate(bq_ctx* ctx, const uint8_t* d_z, const uint32_t* d_off, const uint32_t* d_len, int n, int px, uint8_t* d_rows,
                    size_t rows_stride, void* d_scratch, size_t scratch_bytes, int32_t* d_status, bq_stream_t stream);

@@ -38,40 +38,56 @@ def _up(eng, a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(eng.device)
 
 
-def _png_tools(eng, px=8):
+# The helpers return what their calls wrote as host arrays -- the documented result regions only: inflated rows up to px (1 + 3 px)
+# bytes (the stride's padding is unspecified, include/biscuit_hip.h), encoder bytes up to the last offset, canvases whole (the
+# caller fills them first).  ``own_scratch``: every call that takes ``scratch=`` gets one of the size its ``*_scratch`` method
+# states (tests/test_gpu_poison_tools.py runs them with allocations that are poisoned and guarded).
+def _host(*tensors):
+    return [t.cpu().numpy() for t in tensors]
+
+
+def _png_tools(eng, px=8, own_scratch=False):
     """One zlib stream of px scanlines (filter type 0) through the inflate and both un-filter entries."""
     raw = np.random.default_rng(1).integers(0, 256, (px, 1 + 3 * px), dtype=np.uint8)
     raw[:, 0] = 0
     z = zlib.compress(raw.tobytes(), 6)
     buf = np.frombuffer(z + b'\0' * ((-(len(z) + 32)) % 16 + 32), np.uint8).copy()
-    rows, status = eng.png_inflate(_up(eng, buf), _up(eng, np.zeros(1, np.int32)), _up(eng, np.array([len(z)], np.int32)), px)
+    rows, status = eng.png_inflate(_up(eng, buf), _up(eng, np.zeros(1, np.int32)), _up(eng, np.array([len(z)], np.int32)), px,
+                                   scratch=eng.inflate_scratch(1) if own_scratch else None)
     tiles = eng.png_unfilter_strided(rows, px)
     assert int(status[0]) == 0 and np.array_equal(tiles.cpu().numpy()[0], raw[:, 1:].reshape(px, px, 3))
-    assert torch.equal(eng.png_unfilter(_up(eng, raw[None])), tiles)
+    plain = eng.png_unfilter(_up(eng, raw[None]))
+    assert torch.equal(plain, tiles)
+    assert np.array_equal(rows[0, :raw.size].cpu().numpy(), raw.reshape(-1))
+    return _host(rows[:, :px * (1 + 3 * px)], status, tiles, plain)
 
 
-def _jpeg_tools(eng, tmp_path):
+def _jpeg_tools(eng, tmp_path, own_scratch=False):
     """One 17-px tile decoded, one 16 x 16 segment decoded into a canvas, one 8-px tile encoded."""
     raw = jc.matrix(17)[0][0]
     scan, desc, tables = jc.extract_each(tmp_path, [raw], 17)[0]
-    tiles, status = eng.jpeg_decode(_up(eng, scan), _up(eng, desc.view(np.int32)), _up(eng, tables), 17)
+    tiles, status = eng.jpeg_decode(_up(eng, scan), _up(eng, desc.view(np.int32)), _up(eng, tables), 17,
+                                    scratch=eng.jpeg_scratch(1, 17) if own_scratch else None)
     assert int(status[0]) == 0 and np.array_equal(tiles.cpu().numpy()[0], jc.pillow(raw))
     path = wj.write_slide(tmp_path / 's.tif', [wj.page(_img(16, 16, 11), 16, 16, wj.SAMPLINGS['420'])])
     with TiffSlide(path) as s:
         sg = s.region_segments(0, 0, 0, 16, 16)
         scan, desc, tables = tn.extract_jpeg_segments(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h, sg.jpeg_tables)
         canvas = torch.full((16, 16, 3), 255, dtype=torch.uint8, device=eng.device)
-        status = eng.jpeg_decode_canvas(_up(eng, scan), _up(eng, desc.view(np.int32)), _up(eng, tables), sg.seg_w, sg.seg_h,
-                                        _up(eng, sg.place), canvas, sg.clip)
-        assert len(sg) == 1 and int(status[0]) == 0 and np.array_equal(canvas.cpu().numpy(), s.read_region(0, 0, 0, 16, 16))
-    buf, off = eng.jpeg_encode(_up(eng, ec.tile(8, 'noise')[None].copy()), 95, '4:2:0')
+        seg_status = eng.jpeg_decode_canvas(_up(eng, scan), _up(eng, desc.view(np.int32)), _up(eng, tables), sg.seg_w, sg.seg_h,
+                                            _up(eng, sg.place), canvas, sg.clip,
+                                            scratch=eng.jpeg_canvas_scratch(1, sg.seg_w, sg.seg_h) if own_scratch else None)
+        assert len(sg) == 1 and int(seg_status[0]) == 0 and np.array_equal(canvas.cpu().numpy(), s.read_region(0, 0, 0, 16, 16))
+    buf, off = eng.jpeg_encode(_up(eng, ec.tile(8, 'noise')[None].copy()), 95, '4:2:0',
+                               scratch=eng.jpeg_encode_scratch(1, 8, '4:2:0') if own_scratch else None)
     assert ec.split(buf.cpu().numpy(), off) == [ec.pillow(8, 'noise', 95, '4:2:0')]
+    return _host(tiles, status, canvas, seg_status, buf[:int(off[-1])], off)
 
 
-def _png_encode_and_j2k_tools(eng):
+def _png_encode_and_j2k_tools(eng, own_scratch=False):
     """One 8-px tile encoded as PNG, one lossless 16 x 16 JPEG 2000 segment decoded into a canvas."""
     tile = ec.tile(8, 'noise')[None].copy()
-    buf, off = eng.png_encode(_up(eng, tile))
+    buf, off = eng.png_encode(_up(eng, tile), scratch=eng.png_encode_scratch(1, 8) if own_scratch else None)
     want, want_off, _ = tn.png_encode(tile)
     assert np.array_equal(off.numpy(), want_off) and np.array_equal(buf.cpu().numpy(), want)
     a = _img(16, 16, 11)
@@ -79,20 +95,23 @@ def _png_encode_and_j2k_tools(eng):
     desc, blocks, cw = tn.j2k_extract(np.frombuffer(raw, np.uint8), [0], [len(raw)], 16, 16)
     canvas = torch.full((16, 16, 3), 255, dtype=torch.uint8, device=eng.device)
     status = eng.j2k_decode_canvas(_up(eng, desc), _up(eng, blocks), _up(eng, cw), 16, 16, _up(eng, np.zeros((1, 2), np.int32)), canvas,
-                                   (0, 0, 16, 16))
+                                   (0, 0, 16, 16), scratch=eng.j2k_canvas_scratch(1, 16, 16) if own_scratch else None)
     assert int(status[0]) == 0 and np.array_equal(canvas.cpu().numpy(), a)
+    return _host(buf[:int(off[-1])], off, canvas, status)
 
 
 def _heatmap_tools(eng):
     """A 16-px window resampled to 8 px, its grey pixels counted, and a one-cell heatmap drawn over a 3 x 5 thumbnail."""
     canvas = _up(eng, np.random.default_rng(2).integers(0, 256, (20, 24, 3), dtype=np.uint8))
     tiles = eng.tile_resample(canvas, _up(eng, np.array([[3, 2]], np.int32)), 16, 8)
-    assert tuple(tiles.shape) == (1, 8, 8, 3) and tuple(eng.tile_grayspace(tiles).shape) == (1,)
+    gray = eng.tile_grayspace(tiles)
+    assert tuple(tiles.shape) == (1, 8, 8, 3) and tuple(gray.shape) == (1,)
     thumb = _up(eng, np.full((3, 5, 3), 100, np.uint8))
     from biscuit_amd.render import PRGN_TRUNC
     out = eng.heatmap_render(_up(eng, np.full((1, 1), 0.5, np.float32)), _up(eng, np.zeros(5, np.int32)), _up(eng, np.zeros(3, np.int32)),
                              _up(eng, PRGN_TRUNC), thumb)
     assert out.shape == thumb.shape
+    return _host(tiles, gray, out)
 
 
 def _mask_tools(eng):
@@ -104,9 +123,12 @@ def _mask_tools(eng):
     below = eng.tissue_cells(plane, 255, col, row)
     focus, n_out = eng.tissue_focus(thumb)
     assert int(below[0, 0]) == 35 and int(n_out[0]) == int((focus == 0).sum())
-    assert int(eng.tissue_cells_union(plane, 0, focus, col, row)[0, 0]) >= int(n_out[0])
+    union = eng.tissue_cells_union(plane, 0, focus, col, row)
+    assert int(union[0, 0]) >= int(n_out[0])
     xs, ys, triangle = np.array([2, 6, 14], np.int32), np.array([2, 10], np.int32), [np.array([[0, 0], [8, 0], [0, 8]], np.int32)]
-    assert np.array_equal(eng.roi_plane(xs, ys, triangle).cpu().numpy(), roi_ref.plane(xs, ys, triangle))
+    roi = eng.roi_plane(xs, ys, triangle)
+    assert np.array_equal(roi.cpu().numpy(), roi_ref.plane(xs, ys, triangle))
+    return _host(plane, hist, below, focus, n_out, union, roi)
 
 
 def test_every_tool_opens_its_profiling_class_and_no_other(tmp_path):

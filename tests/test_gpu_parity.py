@@ -149,6 +149,46 @@ def layer_rms_ulps(k):
 FEAT_MAXABS_ULPS = 1.0      # pooled features average 100 pixels: measured 0.3-0.4
 
 
+@pytest.mark.parametrize('fill', ['nan', 'inf'])
+@pytest.mark.parametrize('dtype', ['f32', 'bf16', 'f16'])
+def test_every_layer_against_oracle_on_a_poisoned_workspace(engines, layer_refs, tiles, dtype, fill):
+    """``test_every_layer_against_oracle`` on memory whose contents are unspecified, as the contract has it (DESIGN.md "Buffer
+    contract"): in front of every tap call and of ``backbone`` the workspace is replaced by a guarded one of exactly
+    ``bq_workspace_bytes`` bytes holding NaN (every byte 0xFF) or +Inf of the storage type.  The same two tiles, the same
+    references, the same bounds -- tests/test_gpu_poison.py holds the kernels to their own results on zeroed memory, this test
+    holds those to the oracle --, and no write outside the workspace."""
+    from tests import _poison as P
+    t2 = tiles[:2]
+    taps, feat_ref = layer_refs(dtype)
+    eng = engines[dtype]
+    staged = eng.stage(dev(t2))
+    try:
+        for k, (name, shp) in enumerate(TAPS):
+            check = P.poison_workspace(eng, 2, 1, fill)
+            at = eng._ws.data_ptr()
+            got = eng.debug_activation(name, staged, shp).cpu().numpy()
+            assert eng._ws.data_ptr() == at and P.holds(eng._ws[:4096], fill, dtype)      # (the poisoned one was used; its first pad is nobody's)
+            check()
+            ref = taps[name].permute(0, 2, 3, 1).numpy()
+            d = np.abs(got - ref)
+            assert not np.isnan(got).any(), name
+            if dtype == 'f32':
+                assert d.max() < 2e-4, (name, d.max())
+            else:
+                ulp = ULP[dtype] * np.abs(ref).max()
+                rms = np.sqrt((d ** 2).mean()) / np.sqrt((ref ** 2).mean())
+                assert d.max() < layer_maxabs_ulps(k) * ulp, (name, d.max() / ulp, layer_maxabs_ulps(k))
+                assert rms < layer_rms_ulps(k) * ULP[dtype], (name, rms / ULP[dtype], layer_rms_ulps(k))
+        check = P.poison_workspace(eng, 2, 1, fill)
+        feat = eng.backbone(staged).cpu().numpy()
+        check()
+        fr = feat_ref.numpy()
+        tol = 1e-4 if dtype == 'f32' else FEAT_MAXABS_ULPS * ULP[dtype] * np.abs(fr).max()
+        assert not np.isnan(feat).any() and np.abs(feat - fr).max() < tol
+    finally:
+        eng._ws = None              # the module's other tests grow their own
+
+
 def _without_16x16_copies(blob):
     """The BQW1 blob re-serialised without its "<layer>/wp16" and "block1_conv1/w16" entries, as bq_load_weights reads it: a
     16-byte header, 64-byte directory entries ``name[48], off, len``, payloads at 256-aligned offsets."""
