@@ -85,6 +85,11 @@ ABI = {
     'bq_debug_activation': (_i64, [_vp, C.c_char_p, _vp, _i, _vp, _sz, _vp, _sz, _vp]),
     'bq_debug_activation_u8': (_i64, [_vp, C.c_char_p, _vp, _i, _vp, _sz, _vp, _sz, _vp]),
     'bq_describe_schedule': (_i, [_vp, _i, _i, C.c_char_p, C.c_char_p, _sz]),
+    'bq_knn_workspace_bytes': (_sz, [_i64, _i, _i]),
+    'bq_knn': (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'bq_umap_smooth_scratch_bytes': (_sz, [_i64]),
+    'bq_umap_smooth': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'bq_umap_epoch': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _u64, _i, _vp]),
 }
 
 

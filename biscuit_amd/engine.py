@@ -127,6 +127,7 @@ class Engine:
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
         self._ws = self._inflate_ws = self._jpeg_ws = self._j2k_ws = self._jpeg_enc_ws = self._png_enc_ws = None        # device buffers grown on demand (``_scratch``)
+        self._knn_ws = self._umap_ws = None
         self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
         self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
         self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
@@ -619,6 +620,68 @@ class Engine:
                                            w, ys.ctypes.data, h, _ptr(tables), _ptr(plane), self._stream()))
         self._hold(edges, starts, xs, ys)
         return plane
+
+    # ------------------------------------------------------------------ the feature map (DESIGN.md "Feature map (Figure 6)")
+    def knn(self, x, k, scratch=None):
+        """Exact ``k`` nearest neighbours of the rows of ``x`` fp32 [n, D] on this device (``bq_knn``, kernels_knn.hip; D a multiple
+        of 16, 1 <= k <= 64, k <= n) -> ``(idx int32 [n, k], dist fp32 [n, k])``: Euclidean distances, every row sorted by
+        (distance, index) ascending, the row itself a candidate like any other.  ``scratch``: ``knn_scratch(n, D, k)`` or larger.
+        ValueError for a shape or a ``k`` the entry refuses."""
+        if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 2):
+            raise ValueError('x must be fp32 [n, D]')
+        self._on_device('x', x)
+        assert x.is_contiguous()
+        n, d, k = int(x.shape[0]), int(x.shape[1]), int(k)
+        need = int(self._lib.bq_knn_workspace_bytes(n, d, k))
+        if need == 0:
+            raise ValueError(f'knn takes 1 <= k <= 64, k <= n and D a multiple of 16, not n = {n}, D = {d}, k = {k}')
+        scratch = self._scratch('_knn_ws', need, scratch)
+        assert scratch.numel() >= need
+        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        dist = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        self._check(self._lib.bq_knn(self._ctx, _ptr(x), n, d, k, _ptr(idx), _ptr(dist), _ptr(scratch), scratch.numel(), self._stream()))
+        return idx, dist
+
+    def knn_scratch(self, n, d, k):
+        """Candidate lists for ``knn`` over ``n`` rows (one buffer per launch that may be in flight)."""
+        return self._bytes(self._lib.bq_knn_workspace_bytes(int(n), int(d), int(k)))
+
+    def umap_smooth(self, idx, dist, scratch=None):
+        """The fuzzy graph's rows from ``knn``'s table (``bq_umap_smooth``, kernels_umap.hip) -> ``(rho [n], sigma [n], w [n, k])``
+        fp32 on the device: the membership weight of every (row, neighbour), 0 for the row itself."""
+        if not (torch.is_tensor(idx) and torch.is_tensor(dist) and idx.dtype == torch.int32 and dist.dtype == torch.float32 and
+                idx.dim() == 2 and idx.shape == dist.shape and idx.shape[0] >= 1 and 1 <= idx.shape[1] <= 64):
+            raise ValueError('idx int32 [n, k] and dist fp32 [n, k] with 1 <= n and 1 <= k <= 64')
+        self._on_device('idx', idx)
+        self._on_device('dist', dist)
+        assert idx.is_contiguous() and dist.is_contiguous()
+        n, k = int(idx.shape[0]), int(idx.shape[1])
+        scratch = self._scratch('_umap_ws', int(self._lib.bq_umap_smooth_scratch_bytes(n)), scratch)
+        rho = torch.empty(n, dtype=torch.float32, device=self.device)
+        sigma = torch.empty(n, dtype=torch.float32, device=self.device)
+        w = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        self._check(self._lib.bq_umap_smooth(self._ctx, _ptr(idx), _ptr(dist), n, k, _ptr(rho), _ptr(sigma), _ptr(w), _ptr(scratch),
+                                             scratch.numel(), self._stream()))
+        return rho, sigma, w
+
+    def umap_epoch(self, prev, graph, epoch, alpha, a, b, seed, out=None, block=0):
+        """One epoch (1-based) of the layout in gather form (``bq_umap_epoch``, kernels_umap.hip): ``prev`` fp32 [n, 2], ``graph`` the
+        symmetric CSR on this device as ``(indptr int64 [n + 1], nbr int32 [nnz], eps fp32 [nnz], next fp32 [nnz])`` --
+        ``umap.graph_to_device`` checks and uploads one; ``next`` is advanced in place -- -> the new positions fp32 [n, 2] (``out``,
+        another tensor than ``prev``).  ``block``: threads per workgroup (0: 64); the result does not depend on it."""
+        indptr, nbr, eps, nxt = graph
+        n = int(prev.shape[0])
+        assert prev.dtype == torch.float32 and prev.is_cuda and prev.is_contiguous() and tuple(prev.shape) == (n, 2)
+        assert indptr.dtype == torch.int64 and indptr.is_cuda and indptr.is_contiguous() and indptr.numel() == n + 1
+        assert nbr.dtype == torch.int32 and eps.dtype == torch.float32 and nxt.dtype == torch.float32
+        assert nbr.is_cuda and eps.is_cuda and nxt.is_cuda and nbr.is_contiguous() and eps.is_contiguous() and nxt.is_contiguous()
+        assert nbr.numel() == eps.numel() == nxt.numel()
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, 2)
+        self._check(self._lib.bq_umap_epoch(self._ctx, _ptr(prev), _ptr(out), n, _ptr(indptr), _ptr(nbr), _ptr(eps), _ptr(nxt), int(epoch),
+                                            float(alpha), float(a), float(b), int(seed) & (2 ** 64 - 1), int(block), self._stream()))
+        return out
 
     def reinhard_fast(self, tiles_u8, target_means, target_stds, out=None):
         """`reinhard_fast` stain normalisation (hp.py:19; results.py:251-252 `wsi_normalizer.rgb_to_rgb`):

@@ -70,6 +70,10 @@ ABI = {
     'bqio_table_append_file': (_i, [_vp, C.c_char_p, _i64, _i64]),
     'bqio_table_close': (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     'bqio_format_f64': (_i, [C.c_double, C.c_char_p, _i]),
+    # the CPU builds of the feature map's entries (biscuit_amd/umap.py)
+    'bqio_knn': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'bqio_umap_smooth': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'bqio_umap_epoch': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_float, C.c_float, C.c_float, C.c_uint64]),
 }
 
 

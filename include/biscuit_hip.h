@@ -503,6 +503,44 @@ int64_t bq_debug_activation_u8(bq_ctx* ctx, const char* name, const uint8_t* d_t
  * text's length, or <0. */
 int bq_describe_schedule(bq_ctx* ctx, int n, int from_u8, const char* name, char* out, size_t cap);
 
+/* The feature map (kernels_knn.hip, kernels_umap.hip; DESIGN.md "Feature map (Figure 6)"): exact nearest neighbours, the fuzzy
+ * graph's rows and the layout's epochs of UMAP, restated from memory (unpinned against umap-learn; pinned to a float64 numpy
+ * restatement, tests/_umap_ref.py).  The per-row arithmetic is csrc/umap_device.h, compiled for host and device.
+ *
+ * bq_knn: d_x fp32 [n][D] (16-byte aligned, D a multiple of 16, 16 .. 2^20) -> d_idx int32 [n][k] and d_dist fp32 [n][k], the k
+ * nearest rows of every row by Euclidean distance, each row sorted by (distance, index) ascending; the row itself is a candidate
+ * like any other, so it is normally rank 0.  1 <= k <= 64, k <= n, n <= 2^31 / 160: anything else is BQ_ERR_ARG.  A pruning pass
+ * in the GEMM form on the fp32 matrix instruction keeps 2 (k + 16) candidates per row; they are ranked again by the direct form
+ * sum (x - y)^2 in fp32, and that is the distance returned (its square root, correctly rounded).  The n x n matrix is never
+ * stored.  d_ws: bq_knn_workspace_bytes(n, D, k) bytes (0 for arguments the call refuses), 16-byte aligned, caller-owned,
+ * contents unspecified on entry; BQ_ERR_WORKSPACE below that.  No atomics: the same bits every run.
+ *
+ * bq_umap_smooth: the table of bq_knn -> d_rho [n], d_sigma [n] and the membership weights d_w [n][k] (local connectivity 1,
+ * bandwidth 1): rho the smallest non-zero distance of the row, sigma by 64 bisection steps for sum_{j >= 1} exp(-max(0, d_j -
+ * rho) / sigma) = log2(k), floored at 1e-3 x the row's mean distance (x the mean of all distances where rho = 0); w = 0 for the
+ * row itself, 1 where d - rho <= 0, else exp(-(d - rho) / sigma).  d_scratch: bq_umap_smooth_scratch_bytes(n) bytes, 8-byte
+ * aligned.
+ *
+ * bq_umap_epoch: one epoch (1-based) of the layout in gather form.  The graph is a symmetric CSR on the device -- d_indptr int64
+ * [n + 1] from 0, non-decreasing; d_nbr int32 [nnz] in 0 .. n - 1, ascending within a row (the caller's to guarantee: nothing
+ * here reads them back); d_eps fp32 [nnz] epochs per sample; d_next fp32 [nnz] the epoch of the next sample, advanced here.
+ * Vertex i reads d_prev fp32 [n][2] and writes d_out[i] (d_out != d_prev): for every edge of its row with next <= epoch the
+ * attractive step, then 5 repulsive steps against vertices drawn by Philox4x32-10 (key seed; counter epoch, vertex, slot in
+ * the row, draw), every component clipped to +-4 and scaled by alpha.  block: threads per workgroup, a multiple of 64 up to
+ * 1024 (0: 64); the result does not depend on it.
+ *
+ * All three allocate nothing and are enqueued on `stream` without a host synchronisation; a bad argument is BQ_ERR_ARG with
+ * nothing enqueued. */
+size_t bq_knn_workspace_bytes(int64_t n, int D, int k);
+int bq_knn(bq_ctx* ctx, const float* d_x, int64_t n, int D, int k, int32_t* d_idx, float* d_dist, void* d_ws, size_t ws_bytes,
+           bq_stream_t stream);
+size_t bq_umap_smooth_scratch_bytes(int64_t n);
+int bq_umap_smooth(bq_ctx* ctx, const int32_t* d_idx, const float* d_dist, int64_t n, int k, float* d_rho, float* d_sigma, float* d_w,
+                   void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
+int bq_umap_epoch(bq_ctx* ctx, const float* d_prev, float* d_out, int64_t n, const int64_t* d_indptr, const int32_t* d_nbr,
+                  const float* d_eps, float* d_next, int epoch, float alpha, float a, float b, uint64_t seed, int block,
+                  bq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -279,6 +279,16 @@ int bqio_table_close(bqio_table* t, int64_t* rows, int64_t* bytes);
 /* repr(float) of one double into out (NUL-terminated), exported for tests.  Returns its length or BQIO_ERR_ARG. */
 int bqio_format_f64(double v, char* out, int cap);
 
+/* The CPU builds of the feature map's three entries (include/biscuit_hip.h: bq_knn, bq_umap_smooth, bq_umap_epoch;
+ * csrc/umap_host.cpp over csrc/umap_device.h, the per-row arithmetic the GPU kernels are compiled from), on host memory with the
+ * same shapes and types.  bqio_knn ranks all n rows by the direct form sum (x - y)^2 -- no pruning pass --, so it is what the
+ * device returns wherever its pruning loses no neighbour.  bqio_umap_epoch checks the CSR (indptr from 0 and non-decreasing,
+ * neighbours in 0 .. n - 1).  BQIO_ERR_ARG for what the GPU entries refuse.  For tests. */
+int bqio_knn(const float* X, int n, int D, int k, int32_t* idx, float* dist);
+int bqio_umap_smooth(const int32_t* idx, const float* dist, int n, int k, float* rho, float* sigma, float* w);
+int bqio_umap_epoch(const float* prev, float* out, int n, const int64_t* indptr, const int32_t* nbr, const float* eps, float* next,
+                    int epoch, float alpha, float a, float b, uint64_t seed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,194 @@
+"""The feature map's host side (DESIGN.md "Feature map (Figure 6)"): the CPU builds of the three device entries (libbiscuit_io:
+csrc/umap_host.cpp over csrc/umap_device.h, the arithmetic the kernels compile) and the numpy host stages of biscuit_amd/umap.py,
+against the float64 restatement tests/_umap_ref.py.  No GPU."""
+import numpy as np
+import pytest
+
+from biscuit_amd import tfrecord_native as tn
+from biscuit_amd import umap
+from tests import _umap_cases as cases
+from tests import _umap_ref as ref
+
+pytestmark = pytest.mark.skipif(not tn.available(), reason='libbiscuit_io.so not built')
+
+# The largest difference between the fp32 CPU build and the float64 restatement after the three epochs of ``epoch_case`` below,
+# measured on the CPU: 5.5e-5, 4.0e-4, 1.41e-2 after epochs 1, 2, 3 (positions span +-10; two vertices that come close repel
+# with a slope of up to 2 b / 0.001, which is what multiplies a rounding error from one epoch to the next).  The kernels are held
+# to 4 x this (tests/test_gpu_umap.py): device powf / expf differ from libm by a few ulp.
+EPOCH_HOST_ERR = 1.41e-2
+EPOCH_SEED = 7
+
+
+def epoch_case():
+    """The cluster case's graph at 15 neighbours and 200 epochs from the float64 table, its PCA start and the constants."""
+    d2 = ref.case_sqdist('cluster', 0)
+    idx = ref.knn(d2, 15)
+    dist = np.sqrt(np.take_along_axis(d2, idx, 1))
+    _, _, w, _ = ref.smooth(idx, dist)
+    indptr, nbr, eps = umap.fuzzy_graph(idx, w, 200)
+    a, b = umap.fit_ab(0.1)
+    return indptr, nbr, eps, umap.pca_init(cases.cluster(0)), a, b
+
+
+def epochs_f64(indptr, nbr, eps, init, a, b, n=3):
+    cur, nxt = init.astype(np.float64), eps.astype(np.float64)
+    for ep in range(1, n + 1):
+        cur = ref.epoch(cur, indptr, nbr, eps.astype(np.float64), nxt, ep, 1.0 - (ep - 1) / 200.0, a, b, EPOCH_SEED)
+    return cur, nxt
+
+
+@pytest.mark.parametrize('min_dist', sorted(ref.AB))
+def test_the_curve_fit_reproduces_the_known_constants(min_dist):
+    a, b = umap.fit_ab(min_dist)
+    assert abs(a - ref.AB[min_dist][0]) < 1e-4 and abs(b - ref.AB[min_dist][1]) < 1e-4, (a, b)
+
+
+def test_epoch_counts():
+    assert [umap.n_epochs_for(n) for n in (1, 10000, 10001, 100000)] == [500, 500, 200, 200]
+
+
+def test_knn_integer_case_is_the_oracle_exactly():
+    x, d2 = cases.integer(), ref.case_sqdist('integer')
+    assert d2.max() < 2 ** 24 and (d2 == np.round(d2)).all()
+    for k in (15, 50):
+        idx, dist = umap.knn_host(x, k)
+        want = ref.knn(d2, k)
+        assert np.array_equal(idx, want)
+        assert np.array_equal(dist, np.sqrt(np.take_along_axis(d2, want, 1)).astype(np.float32))
+    assert idx[3, :3].tolist() == [3, 7, 200] and idx[200, :3].tolist() == [3, 7, 200] and not dist[7, :3].any()   # ties by the lower index
+    s = np.sort(d2, axis=1)[:, :50]
+    assert (np.diff(s, axis=1) == 0).sum() > 3                     # (and ties between other rows than the copies)
+
+
+@pytest.mark.parametrize('name,seed', [('cluster', s) for s in cases.CLUSTER_SEEDS] + [('near_duplicate', 0)])
+def test_knn_cluster_cases(name, seed):
+    x, d2 = cases.get(name, seed), ref.case_sqdist(name, seed)
+    idx, dist = umap.knn_host(x, 15)
+    rel = ref.check_table(d2, idx, dist, cases.D)
+    print(f'{name} {seed}: largest relative error of a squared distance {rel:.3e} (eps {ref.eps_for(cases.D):.3e})')
+    decided = ref.decided(d2, 15, cases.D)
+    assert np.array_equal(np.sort(idx[decided], 1), np.sort(ref.knn(d2, 15)[decided], 1))
+
+
+def test_near_duplicates_are_where_the_gemm_form_fails():
+    """The case does what it is for: the fp32 GEMM form's distance of a replaced row to its source is off by more than eps."""
+    x, d2 = cases.near_duplicate(), ref.case_sqdist('near_duplicate')
+    nn = ref.knn(d2, 2)[:, 1]
+    close = np.nonzero(d2[np.arange(len(x)), nn] < 1.0)[0]
+    assert len(close) >= 32
+    sq = (x * x).sum(1, dtype=np.float32)
+    gemm = (sq[close] + sq[nn[close]] - np.float32(2) * np.einsum('ij,ij->i', x[close], x[nn[close]]).astype(np.float32)).astype(np.float64)
+    true = d2[close, nn[close]]
+    assert (np.abs(gemm - true) > ref.eps_for(cases.D) * true).mean() > 0.5
+
+
+@pytest.mark.parametrize('n,d,k', cases.SMALL)
+def test_knn_small_shapes(n, d, k):
+    x = cases.small(n, d)
+    idx, dist = umap.knn_host(x, k)
+    ref.check_table(ref.sqdist(x), idx, dist, d)
+    assert (idx[:, 0] == np.arange(n)).all() and not dist[:, 0].any()
+
+
+@pytest.mark.parametrize('n,d,k', [(5, 48, 6), (5, 48, 0), (70, 48, 65), (5, 40, 2), (0, 48, 1)])
+def test_knn_refuses(n, d, k):
+    with pytest.raises(ValueError, match='error -1'):
+        umap.knn_host(np.zeros((n, d), np.float32), k)
+
+
+def test_smoothing():
+    idx, dist = cases.smoothing_table(15)
+    rho, sigma, w = umap.smooth_host(idx, dist)
+    r_rho, r_sigma, r_w, floored = ref.smooth(idx, dist)
+    assert floored[-3:].all() and not floored[:-3].any()
+    assert r_rho[-3] == 2.5 and r_rho[-2] == 1.0 and r_rho[-1] == 0.0
+    k = idx.shape[1]
+    for i in np.nonzero(~floored)[0]:
+        assert abs(ref.smooth_sum(dist[i], float(rho[i]), float(sigma[i])) - np.log2(k)) <= 1e-5 + k * 2.0 ** -20, i
+    assert np.array_equal(rho, r_rho.astype(np.float32))
+    np.testing.assert_allclose(sigma[floored], r_sigma[floored], rtol=1e-5)
+    np.testing.assert_allclose(w, r_w, rtol=1e-5, atol=1e-30)
+    assert not w[np.arange(len(idx)), 0].any()                      # the row itself
+    assert sigma[-1] == np.float32(1e-3) * np.float32(dist.astype(np.float64).mean())      # rho = 0: the global mean's floor
+
+
+def test_graph_is_the_dense_symmetrisation():
+    idx, dist = cases.smoothing_table(15)
+    idx, dist = idx[:64], dist[:64]
+    _, _, w, _ = ref.smooth(idx, dist)
+    sub = idx < 64                                                  # (edges inside the 64 rows, so that the graph is closed)
+    w = np.where(sub, w, 0.0)
+    idx = np.where(sub, idx, np.arange(64)[:, None])               # (the others point at the row itself, weight 0)
+    for n_epochs in (200, 10):
+        indptr, nbr, eps = umap.fuzzy_graph(idx, w, n_epochs)
+        r_indptr, r_nbr, r_eps = ref.graph(idx, w, n_epochs)
+        assert np.array_equal(indptr, r_indptr) and np.array_equal(nbr, r_nbr)
+        np.testing.assert_allclose(eps, r_eps, rtol=1e-6)
+        assert eps.min() == 1.0 and eps.max() <= n_epochs
+        umap.check_graph(64, indptr, nbr, eps)
+        for i in range(64):                                         # rows sorted, both directions stored
+            row = nbr[indptr[i]:indptr[i + 1]]
+            assert (np.diff(row) > 0).all() and all(i in nbr[indptr[j]:indptr[j + 1]] for j in row)
+    with pytest.raises(ValueError):
+        umap.check_graph(64, indptr, nbr + 60, eps)
+
+
+def test_pca_start():
+    x = cases.cluster(1)
+    y = umap.pca_init(x)
+    assert y.shape == (600, 2) and y.dtype == np.float32 and np.abs(y).max() == 10.0
+    for c in range(2):
+        assert y[np.abs(y[:, c]).argmax(), c] > 0
+    xc = x.astype(np.float64) - x.astype(np.float64).mean(0)
+    _, s, vt = np.linalg.svd(xc, full_matrices=False)
+    want = xc @ vt[:2].T
+    assert np.allclose(np.abs(y / np.abs(y).max() * np.abs(want).max()), np.abs(want), atol=1e-4 * np.abs(want).max())
+    small = umap.pca_init(x[:5, :64])                               # fewer rows than columns: the Gram side
+    assert small.shape == (5, 2) and np.isfinite(small).all()
+
+
+def test_three_epochs_against_float64():
+    indptr, nbr, eps, init, a, b = epoch_case()
+    want, want_next = epochs_f64(indptr, nbr, eps, init, a, b)
+    cur, nxt = init.copy(), eps.copy()
+    for ep in range(1, 4):
+        cur = umap.epoch_host(cur, indptr, nbr, eps, nxt, ep, 1.0 - (ep - 1) / 200.0, a, b, EPOCH_SEED)
+    err = float(np.abs(cur - want).max())
+    print(f'CPU build against float64 after three epochs: {err:.3e} (recorded {EPOCH_HOST_ERR:.3e})')
+    assert np.abs(want - init).max() > 1.0                          # the epochs moved something
+    assert err <= 4 * EPOCH_HOST_ERR
+    np.testing.assert_allclose(nxt, want_next, rtol=1e-6)
+    again, nxt2 = init.copy(), eps.copy()
+    for ep in range(1, 4):
+        again = umap.epoch_host(again, indptr, nbr, eps, nxt2, ep, 1.0 - (ep - 1) / 200.0, a, b, EPOCH_SEED)
+    assert np.array_equal(again.view(np.uint32), cur.view(np.uint32))
+
+
+def test_epoch_refuses_a_broken_graph():
+    indptr, nbr, eps, init, a, b = epoch_case()
+    with pytest.raises(ValueError, match='error -1'):
+        umap.epoch_host(init, indptr, nbr + 600, eps, eps.copy(), 1, 1.0, a, b, 0)
+
+
+def test_mosaic_assignment_and_table_columns(tmp_path):
+    from biscuit_amd import featuremap as fm
+    xy = np.array([[0.0, 0.0], [4.0, 2.0], [0.4, 0.1], [3.9, 1.9], [2.1, 1.0], [0.5, 0.5]], np.float32)
+    cells, (ny, nx) = fm.mosaic_cells(xy, 4)
+    assert (ny, nx) == (2, 4)                                       # cells of side 1: x in 0 .. 4, y in 0 .. 2 from the top
+    # (3.9, 1.9) lies nearer (3.5, 1.5) than (4, 2) does; (0.5, 0.5) is a centre; (2.1, 1.0) sits on a boundary: the lower row's
+    assert cells == [(3, 0, 3), (0, 1, 5), (2, 1, 4)]
+    assert fm.mosaic_cells(xy[:1], 3) == ([(0, 0, 0)], (1, 3))
+    with pytest.raises(ValueError):
+        fm.mosaic_cells(xy, 0)
+    m = fm.FeatureMap(['s'] * 3 + ['t'] * 3, np.arange(6) % 3, np.arange(12).reshape(6, 2), np.zeros((6, 2048), np.float32),
+                      np.tile(np.float32([0.25, 0.75]), (6, 1)), np.float32([[0.01, 0.25 * i] for i in range(6)]))
+    with pytest.raises(ValueError):
+        m.frame()
+    m.xy = xy
+    df = m.frame('brca', tile_uq=0.5)
+    assert list(df.columns) == ['slide', 'loc_x', 'loc_y', 'x', 'y', 'brca-y_pred1', 'brca-uncertainty1', 'confident']
+    assert df['confident'].tolist() == [True, True, False, False, False, False]      # strictly below the threshold: 0.5 is not
+    assert m.frame('brca')['confident'].all()
+    m.labels = {'s': 1}
+    assert m.frame()['label'].tolist() == [1, 1, 1, '', '', '']
+    assert [p.split('/')[-1] for p in m.save(str(tmp_path))] == ['umap.csv']
