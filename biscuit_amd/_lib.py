@@ -47,6 +47,8 @@ ABI = {
     'bq_jpeg_decode_canvas': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'bq_j2k_canvas_scratch_bytes': (_sz, [_i, _i, _i]),
     'bq_j2k_decode_canvas': (_i, [_vp, _vp, _i, _vp, _i64, _vp, _sz, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'bq_lzw_canvas_scratch_bytes': (_sz, [_i, _i, _i]),
+    'bq_lzw_decode_canvas': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'bq_jpeg_encode_scratch_bytes': (_sz, [_i, _i, _i]),
     'bq_jpeg_encode': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     'bq_png_encode_scratch_bytes': (_sz, [_i, _i]),

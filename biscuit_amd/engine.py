@@ -127,7 +127,7 @@ class Engine:
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
         self._ws = self._inflate_ws = self._jpeg_ws = self._j2k_ws = self._jpeg_enc_ws = self._png_enc_ws = None        # device buffers grown on demand (``_scratch``)
-        self._knn_ws = self._umap_ws = None
+        self._knn_ws = self._umap_ws = self._lzw_ws = None
         self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
         self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
         self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
@@ -394,6 +394,34 @@ class Engine:
         """Plane space for ``j2k_decode_canvas`` over ``n`` segments (``bq_j2k_canvas_scratch_bytes``: 24 bytes a pixel, 1.5 MB per
         256 x 256 segment, for 256 segments at most; a longer call works in rounds)."""
         return self._bytes(self._lib.bq_j2k_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h)))
+
+    def lzw_decode_canvas(self, data, desc, seg_w, seg_h, place, canvas, clip, predictor=1, scratch=None):
+        """A slide page's own LZW tiles decoded on the device INTO a canvas (``bq_lzw_decode_canvas``, kernels_lzw.hip: the code
+        chain a wave per segment, strings copied out of the segment's earlier output 64 bytes a step, then a kernel that undoes
+        the predictor and places the rows): ``data`` uint8 [bytes] and ``desc`` int32 / uint32 [n, 2] of (offset, length) as
+        ``tfrecord_native.lzw_pack`` packed the ``seg_w`` x ``seg_h`` segments; ``place``, ``canvas`` and ``clip`` as
+        ``jpeg_decode_canvas`` takes them; ``predictor`` the page's (1: none, 2: horizontal differencing) -- all tensors on this
+        device.  Returns status int32 [n] on the device, 0 where the segment decoded (``tfrecord_native.LZW_*`` bits otherwise);
+        any other segment wrote nothing.  ``scratch``: at least one segment's (``lzw_canvas_scratch(n, seg_w, seg_h)`` holds a
+        whole round); the call works in rounds of as many as it holds."""
+        n, seg_w, seg_h = int(desc.shape[0]), int(seg_w), int(seg_h)
+        assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+        assert desc.is_cuda and desc.is_contiguous() and desc.element_size() == 4 and tuple(desc.shape) == (n, 2)
+        if int(predictor) not in (1, 2):
+            raise ValueError(f'predictor must be 1 or 2, not {predictor!r}')
+        x0, y0, x1, y1 = self._canvas_args(n, place, canvas, clip)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        scratch = self._scratch('_lzw_ws', int(self._lib.bq_lzw_canvas_scratch_bytes(n, seg_w, seg_h)), scratch)
+        assert scratch.is_cuda and scratch.is_contiguous()
+        self._check(self._lib.bq_lzw_decode_canvas(self._ctx, _ptr(data), _ptr(desc), n, seg_w, seg_h, int(predictor), _ptr(place),
+                                                   _ptr(canvas), int(canvas.shape[0]), int(canvas.shape[1]), x0, y0, x1, y1, _ptr(status),
+                                                   _ptr(scratch), scratch.numel() * scratch.element_size(), self._stream()))
+        return status
+
+    def lzw_canvas_scratch(self, n, seg_w, seg_h):
+        """Output space for ``lzw_decode_canvas`` over ``n`` segments (``bq_lzw_canvas_scratch_bytes``: 3 bytes a pixel, 196 608
+        per 256 x 256 segment, for 1 024 segments at most; a longer call works in rounds)."""
+        return self._bytes(self._lib.bq_lzw_canvas_scratch_bytes(int(n), int(seg_w), int(seg_h)))
 
     def jpeg_encode(self, tiles, quality=95, subsampling='4:2:0', cap=None, scratch=None):
         """n tiles encoded as baseline JPEG on the device (``bq_jpeg_encode``, kernels_jpeg_encode.hip): ``tiles`` uint8 NHWC

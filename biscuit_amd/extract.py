@@ -138,7 +138,7 @@ def main(argv=None):
     ap.add_argument('--img-format', default='jpg', choices=list(IMG_FORMATS), help="the records' image format (default jpg; png is lossless)")
     ap.add_argument('--quality', type=int, default=None, help='JPEG quality, 1..100 (default 95: tfrecord.encode_image); jpg only')
     ap.add_argument('--subsampling', default=None, choices=['4:2:0', '4:4:4'], help='JPEG chroma subsampling (default 4:2:0); jpg only')
-    ap.add_argument('--gpu-decode', action='store_true', help="decode the slide's own JPEG or JPEG 2000 tiles on the device; the records do not change")
+    ap.add_argument('--gpu-decode', action='store_true', help="decode the slide's own JPEG, JPEG 2000 or LZW tiles on the device; the records do not change")
     ap.add_argument('--grayspace-fraction', type=float, default=None,
                     help='drop tiles with more than this fraction of grey pixels (Slideflow extracts with 0.6); default: off')
     ap.add_argument('--grayspace-threshold', type=float, default=0.05)

@@ -122,9 +122,11 @@ class Heatmap:
         and decoded on the device straight into the band's canvas (``Engine.jpeg_decode_canvas``): the same bytes, so the same
         arrays.  A tiled JPEG 2000 page (compression 33003 / 33005 / 34712) goes the same way through
         ``tfrecord_native.j2k_extract`` and ``Engine.j2k_decode_canvas``: the same bytes for reversible tiles; for irreversible
-        ones the bytes of the decoder's CPU statement, which tests/test_j2k.py holds within one level of OpenJPEG's.  A band goes through ``read_region`` as before -- the pixels and any ``SlideError`` are then the host's -- when
+        ones the bytes of the decoder's CPU statement, which tests/test_j2k.py holds within one level of OpenJPEG's.  A tiled LZW
+        page (compression 5, tiles up to 1024 pixels a side) is only packed on the host (``tfrecord_native.lzw_pack``) and decoded
+        by ``Engine.lzw_decode_canvas``: the host decoder's bytes, which are libtiff's.  A band goes through ``read_region`` as before -- the pixels and any ``SlideError`` are then the host's -- when
         the extractor refuses one of its segments, when a segment's device status is not 0, or when the level is not a tiled
-        JPEG or JPEG 2000 page.  ``self.decode_stats = {'gpu_bands', 'host_bands', 'segments'}`` counts the bands either way took and the
+        JPEG, JPEG 2000 or LZW page.  ``self.decode_stats = {'gpu_bands', 'host_bands', 'segments'}`` counts the bands either way took and the
         segments the device decoded.
 
         ``cell_mask`` / ``qc`` (``resample='gpu'`` only; default None = off): a keep mask over the grid, applied BEFORE anything
@@ -370,7 +372,7 @@ def main(argv=None):
     ap.add_argument('--grayspace-threshold', type=float, default=0.05)
     add_mask_arguments(ap)
     ap.add_argument('--gpu-decode', action='store_true',
-                    help="decode the slide's own JPEG or JPEG 2000 tiles on the device (from_slide(decode='gpu')); the arrays do not change")
+                    help="decode the slide's own JPEG, JPEG 2000 or LZW tiles on the device (from_slide(decode='gpu')); the arrays do not change")
     ap.add_argument('--mpp', type=float, default=None, help='microns per pixel, for a file that does not say')
     ap.add_argument('--save-tiles', action='store_true', help='write the tiles to uq_incl/ and uq_excl/ (needs --tile-uq)')
     ap.add_argument('--render', action='store_true',

@@ -151,6 +151,11 @@ def _pack_jpeg(sg):
     return scan, desc.view(np.int32), tables
 
 
+def _pack_lzw(sg):
+    packed, desc = tn.lzw_pack(sg.data, sg.offsets, sg.lengths)
+    return packed, desc.view(np.int32)
+
+
 # ``BandSegments.codec`` -> how ``decode_band`` decodes such a band: the host's extractor (-> the packed arrays the engine call
 # takes first, or ValueError -- UnsupportedImage is one -- for a segment it refuses), the ``Engine`` method, the keywords the
 # method takes from the segments beside the common ones, and the longest side of a segment the device decoder takes (None: any).
@@ -158,11 +163,12 @@ BAND_CODECS = {
     'jpeg': (_pack_jpeg, 'jpeg_decode_canvas', lambda sg: {}, None),
     'j2k': (lambda sg: tn.j2k_extract(sg.data, sg.offsets, sg.lengths, sg.seg_w, sg.seg_h), 'j2k_decode_canvas',
             lambda sg: {'ycc': sg.ycc}, tn.J2K_MAX_SIDE),
+    'lzw': (_pack_lzw, 'lzw_decode_canvas', lambda sg: {'predictor': sg.predictor}, tn.LZW_MAX_SIDE),
 }
 
 
 def decode_band(engine, sg):
-    """A band's canvas decoded on the device from its raw JPEG or JPEG 2000 tiles (``wsi.BandSegments``, by its row of
+    """A band's canvas decoded on the device from its raw JPEG, JPEG 2000 or LZW tiles (``wsi.BandSegments``, by its row of
     ``BAND_CODECS``): extract on the host, upload what the extractor packed and the places, fill the canvas with 255, decode, read
     the status once.  -> the canvas (uint8 [H, W, 3] on the device), or None when a segment is larger than the device decoder
     takes, the extractor refuses one, or any status is not 0."""

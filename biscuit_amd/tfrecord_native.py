@@ -46,6 +46,9 @@ ABI = {
                               C.POINTER(C.c_size_t), _i]),
     'bqio_j2k_decode_canvas': (_i, [_vp, _i, _vp, _i64, _vp, C.c_size_t, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i]),
     'bqio_ycc_to_rgb': (None, [_vp, _vp, C.c_size_t]),
+    'bqio_lzw_decode': (_i, [_vp, C.c_size_t, _i, _i, _i, _vp]),
+    'bqio_lzw_max_side': (_i, []),
+    'bqio_lzw_decode_canvas': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i]),
     'bqio_resample_ksize': (_i, [_i, _i]),
     'bqio_resample_taps': (_i, [_i, _i, _vp, _vp, _i]),
     'bqio_tile_resample': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
@@ -294,6 +297,59 @@ def ycc_to_rgb(a):
     out = np.empty_like(a)
     lib().bqio_ycc_to_rgb(a.ctypes.data, out.ctypes.data, a.size // 3)
     return out
+
+
+# a segment's status from the LZW decoders, bits (csrc/lzw_device.h): the first code is not ClearCode; a code beyond the next free
+# index; the data or EndOfInformation before the segment is full; the table at its end without a ClearCode; a refused descriptor
+LZW_HEAD, LZW_CODE, LZW_SHORT, LZW_FULL, LZW_DESC = 1, 2, 4, 8, 16
+LZW_MAX_SIDE = 1024                     # the longest segment side the device LZW decoder takes (MAX_SIDE of csrc/lzw_device.h)
+
+
+def lzw_decode(raw, rows, seg_w, predictor=1):
+    """One TIFF LZW strip or tile -> ``(pixels uint8 [rows, seg_w, 3], status)`` through ``bqio_lzw_decode``: the bytes libtiff
+    gives with ``predictor`` (1 or 2) undone and status 0, or a status of ``LZW_*`` bits and no image."""
+    raw = np.frombuffer(bytes(raw), np.uint8)
+    out = np.empty((int(rows), int(seg_w), 3), np.uint8)
+    st = lib().bqio_lzw_decode(raw.ctypes.data if raw.size else None, raw.size, int(rows), int(seg_w), int(predictor), out.ctypes.data)
+    if st < 0:
+        raise ValueError(f'bqio_lzw_decode: error {st}')
+    return out, int(st)
+
+
+def lzw_pack(data, offsets, lengths):
+    """A TIFF page's raw LZW segments packed for the device decoder, in numpy -- nothing is parsed: segment i =
+    ``data[offsets[i]:offsets[i] + lengths[i]]`` -> ``(packed uint8 [bytes], desc uint32 [n, 2] of (offset, length))``, every
+    segment at a multiple of 16 with zeros behind it.  ``ValueError`` for a band whose packed bytes do not fit 32-bit offsets."""
+    data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+    off, ln = np.ascontiguousarray(offsets, np.uint64).reshape(-1).astype(np.int64), np.ascontiguousarray(lengths, np.uint64).reshape(-1).astype(np.int64)
+    assert len(off) == len(ln) and (len(ln) == 0 or (off.min() >= 0 and ln.min() >= 0 and int((off + ln).max()) <= data.size))
+    room = (ln + 15 + 16) // 16 * 16                                          # at least 16 zero bytes behind every segment
+    at = np.zeros(len(ln), np.int64)
+    at[1:] = np.cumsum(room)[:-1]
+    total = int(room.sum())
+    if total >= 1 << 32 or (len(ln) and int(ln.max()) > 1 << 28):
+        raise ValueError(f'an LZW band of {total} packed bytes does not fit the device decoder\'s 32-bit offsets')
+    packed = np.zeros(total, np.uint8)
+    for a, o, k in zip(at, off, ln):
+        packed[a:a + k] = data[o:o + k]
+    return packed, np.stack([at, ln], 1).astype(np.uint32).reshape(-1, 2)
+
+
+def lzw_decode_canvas(packed, desc, seg_w, seg_h, place, canvas, clip, predictor=1, threads=None):
+    """The device LZW decoder's routines (csrc/lzw_device.h) on the CPU (``bqio_lzw_decode_canvas``): the segments ``lzw_pack``
+    packed, written INTO ``canvas`` (uint8 [H, W, 3], C-contiguous, modified in place) at ``place`` int32 [n, 2] (x, y), clipped
+    to ``clip`` = (x0, y0, x1, y1).  -> status int32 [n].  What ``Engine.lzw_decode_canvas`` computes, byte for byte and status
+    for status.  For tests."""
+    packed, desc = np.ascontiguousarray(packed, np.uint8), np.ascontiguousarray(desc, np.uint32).reshape(-1, 2)
+    n = desc.shape[0]
+    assert n == 0 or int((desc[:, 0].astype(np.int64) + desc[:, 1]).max()) <= packed.size
+    place, clip, status = _canvas_arrays(n, place, canvas, clip)
+    e = lib().bqio_lzw_decode_canvas(packed.ctypes.data, desc.ctypes.data, n, int(seg_w), int(seg_h), int(predictor), place.ctypes.data,
+                                     canvas.ctypes.data, canvas.shape[0], canvas.shape[1], clip.ctypes.data, status.ctypes.data,
+                                     threads or default_threads())
+    if e != 0:
+        raise ValueError(f'bqio_lzw_decode_canvas: error {e}')
+    return status
 
 
 SUBSAMPLING = {'4:4:4': 0, '4:2:0': 2, 0: 0, 2: 2}

@@ -4,10 +4,12 @@ of a whole-slide image at a tile width in MICRONS, each tile resampled to ``tile
 libvips or OpenSlide (none of which exists here).
 
 What is read: classic TIFF and BigTIFF, little or big endian; 8-bit RGB / YCbCr pages in chunky layout, stored as strips or tiles;
-compression none (1), zlib / Adobe deflate (8, 32946; horizontal predictor 2 supported), JPEG (7: abbreviated streams + the page's
-``JPEGTables``, decoded by Pillow's libjpeg) and JPEG 2000 (Aperio's 33003 and 33005, and 34712: one codestream or JP2 file per
+compression none (1), zlib / Adobe deflate (8, 32946; horizontal predictor 2 supported), LZW (5: TIFF 6.0 streams as libtiff
+writes them, predictor 1 or 2, decoded by libbiscuit_io's ``bqio_lzw_decode``, which tests/test_lzw.py holds against libtiff byte for
+byte), JPEG (7: abbreviated streams + the page's ``JPEGTables``, decoded by Pillow's libjpeg) and JPEG 2000 (Aperio's 33003 and 33005, and 34712: one codestream or JP2 file per
 segment, decoded by Pillow's OpenJPEG).  That covers Aperio SVS written with JPEG or JPEG 2000 tiles and generic pyramidal TIFFs
-(``vips tiffsave --pyramid``, Pillow); LZW and planar layouts are refused with a message, not mis-read.
+(``vips tiffsave --pyramid``, Pillow, the libtiff tools' and Bio-Formats' LZW pyramids); old-style (pre-6.0) LZW and planar layouts
+are refused with a message, not mis-read.  Every LZW level is probed at open time: its first segment must begin with ClearCode.
 Microns per pixel come from the Aperio description (``MPP = 0.2520``) or from XResolution / ResolutionUnit.
 
 JPEG 2000: a 33005 / 34712 segment's samples are RGB (a multiple-component transform inside the codestream is the decoder's to
@@ -100,6 +102,18 @@ def j2k_probe(raw, tw, th):
         raise bad('SIZ, COD or QCD missing from the main header')
 
 
+def lzw_probe(raw, path, li):
+    """The first segment of an LZW level, as far as the reader depends on it at open time: the decoder is built, and the stream
+    begins with ClearCode (TIFF 6.0, codes MSB first).  ``SlideError`` otherwise."""
+    from . import tfrecord_native as tn
+    if not tn.available():
+        raise SlideError(f'{path}: level {li} is LZW-compressed, and libbiscuit_io, which decodes it, is not built (make -C biscuit_amd/csrc)')
+    if len(raw) < 2 or raw[0] != 0x80 or raw[1] & 0x80:
+        old = len(raw) >= 2 and raw[0] == 0 and raw[1] & 1
+        raise SlideError(f'{path}: LZW level {li} does not begin with ClearCode: '
+                         + ('an old-style (pre-6.0, bit-reversed) stream, which is not supported' if old else 'damaged'))
+
+
 class _Page:
     """One IFD that holds an 8-bit RGB / YCbCr image."""
     def __init__(self, tags):
@@ -108,7 +122,8 @@ class _Page:
         self.bits = tuple(g(258, (1,)))
         self.compression = int(g(259, (1,))[0])
         # the image codec of the segments, where they are images; ycc: a JPEG 2000 segment's components are YCbCr (33003)
-        self.codec = 'jpeg' if self.compression == 7 else 'j2k' if self.compression in J2K_COMPRESSIONS else None
+        # ('lzw': not images but byte streams; named here because such tiles, too, decode on the device -- ``region_segments``)
+        self.codec = {7: 'jpeg', 5: 'lzw'}.get(self.compression, 'j2k' if self.compression in J2K_COMPRESSIONS else None)
         self.ycc = self.compression == 33003
         self.photometric = int(g(262, (2,))[0])
         self.samples = int(g(277, (1,))[0])
@@ -141,9 +156,11 @@ class _Page:
     def check(self):
         if self.planar != 1:
             raise SlideError('planar (separate-plane) TIFF pages are not supported')
-        if self.compression == 5:
-            raise SlideError('LZW-compressed TIFF: not supported (deflate, JPEG and uncompressed are)')
-        if self.compression not in (1, 7, 8, 32946) + J2K_COMPRESSIONS:
+        if self.compression == 5 and self.predictor not in (1, 2):
+            raise SlideError(f'LZW-compressed TIFF with predictor {self.predictor}: only 1 (none) and 2 (horizontal) are supported')
+        if self.compression == 5 and self.photometric == 6:
+            raise SlideError('LZW-compressed YCbCr TIFF pages are not supported')
+        if self.compression not in (1, 5, 7, 8, 32946) + J2K_COMPRESSIONS:
             raise SlideError(f'TIFF compression {self.compression} is not supported')
         if len(self.offsets) != len(self.counts) or len(self.offsets) < self.across * self.down:
             raise SlideError('TIFF page: strip / tile tables do not cover the image')
@@ -157,14 +174,16 @@ class BandSegments:
     level's image extent in canvas coordinates, cut to the canvas -- what a segment holds beyond it is padding; ``seg_w``,
     ``seg_h`` the page's tile size; ``jpeg_tables`` the page's ``JPEGTables`` bytes or None.  Decoding every segment as
     ``TiffSlide._jpeg`` reads it into a white canvas, inside ``clip`` only, gives ``WSI.band``'s canvas.  ``codec``: 'jpeg', or
-    'j2k' where the segments are JPEG 2000 codestreams (``TiffSlide._j2k`` reads them); ``ycc``: their three components are
-    YCbCr, to be converted as the reader does (compression 33003)."""
-    __slots__ = ('shape', 'data', 'offsets', 'lengths', 'place', 'clip', 'seg_w', 'seg_h', 'jpeg_tables', 'codec', 'ycc')
+    'j2k' where the segments are JPEG 2000 codestreams (``TiffSlide._j2k`` reads them), 'lzw' where they are TIFF LZW streams of
+    ``seg_w`` x ``seg_h`` RGB pixels (``tfrecord_native.lzw_decode`` reads them); ``ycc``: a JPEG 2000 segment's three components
+    are YCbCr, to be converted as the reader does (compression 33003); ``predictor``: an LZW page's (1: none, 2: horizontal
+    differencing per sample)."""
+    __slots__ = ('shape', 'data', 'offsets', 'lengths', 'place', 'clip', 'seg_w', 'seg_h', 'jpeg_tables', 'codec', 'ycc', 'predictor')
 
-    def __init__(self, codec='jpeg', ycc=False, **kw):
-        for k in self.__slots__[:-2]:
+    def __init__(self, codec='jpeg', ycc=False, predictor=1, **kw):
+        for k in self.__slots__[:-3]:
             setattr(self, k, kw[k])
-        self.codec, self.ycc = codec, bool(ycc)
+        self.codec, self.ycc, self.predictor = codec, bool(ycc), int(predictor)
 
     def __len__(self):
         return len(self.offsets)
@@ -230,6 +249,8 @@ class TiffSlide:
             p.check()
             if p.codec == 'j2k':
                 j2k_probe(self._raw_segment(p, 0, li), p.tw, p.th)
+            if p.codec == 'lzw':
+                lzw_probe(self._raw_segment(p, 0, li), path, li)
         self.levels = levels
         self.dimensions = (base.width, base.height)
         self.level_dimensions = [(p.width, p.height) for p in levels]
@@ -310,7 +331,9 @@ class TiffSlide:
         p = self.levels[li]
         raw = self._raw_segment(p, index, li)
         rows = p.th if p.tiled else min(p.th, p.height - (index * p.th))
-        if p.codec:
+        if p.codec == 'lzw':
+            img = self._lzw(p, raw, rows, li, index)
+        elif p.codec:
             img = (self._jpeg if p.codec == 'jpeg' else self._j2k)(p, raw)
             if img.shape[0] < rows or img.shape[1] < p.tw:
                 name = 'JPEG' if p.codec == 'jpeg' else 'JPEG 2000'
@@ -335,6 +358,22 @@ class TiffSlide:
         if len(self._cache) > 64:
             self._cache.pop(next(iter(self._cache)))
         self._cache[key] = img
+        return img
+
+    _LZW_WHY = ((1, 'it does not begin with ClearCode'), (2, 'a code beyond the table'), (4, 'the data ends before the segment is full'),
+                (8, 'the table overflows without a ClearCode'), (16, 'a stream too long'))
+
+    def _lzw(self, p, raw, rows, li, index):
+        """One LZW segment -> uint8 [rows, tw, 3], the page's predictor undone (``bqio_lzw_decode``)."""
+        from . import tfrecord_native as tn
+        if not tn.available():
+            raise SlideError(f'{self.path}: level {li} is LZW-compressed, and libbiscuit_io, which decodes it, is not built')
+        if rows * p.tw * 3 > 1 << 30:
+            raise SlideError(f'{self.path}: LZW segment {index} of level {li} of {p.tw} x {rows} pixels is larger than the reader takes')
+        img, status = tn.lzw_decode(raw, rows, p.tw, p.predictor)
+        if status:
+            why = ', '.join(t for bit, t in self._LZW_WHY if status & bit)
+            raise SlideError(f'{self.path}: damaged LZW segment {index} of level {li}: {why} (status {status})')
         return img
 
     def _jpeg(self, p, raw):
@@ -391,9 +430,9 @@ class TiffSlide:
 
     @_guard
     def region_segments(self, level, x, y, w, h):
-        """The raw JPEG or JPEG 2000 tiles ``read_region(level, x, y, w, h)`` would decode, as a ``BandSegments`` over the same
-        [h, w] canvas (its ``codec`` says which), or None when the level is not a tiled JPEG / JPEG 2000 page (compression 7,
-        33003, 33005 or 34712 with TileWidth / TileLength: strips, deflate and uncompressed pages stay on ``read_region``).  Read through ``_segment``'s bounds checks -- a byte count beyond the
+        """The raw JPEG, JPEG 2000 or LZW tiles ``read_region(level, x, y, w, h)`` would decode, as a ``BandSegments`` over the same
+        [h, w] canvas (its ``codec`` says which), or None when the level is not a tiled JPEG / JPEG 2000 / LZW page (compression 7,
+        33003, 33005, 34712 or 5 with TileWidth / TileLength: strips, deflate and uncompressed pages stay on ``read_region``).  Read through ``_segment``'s bounds checks -- a byte count beyond the
         file's size, a segment that does not lie inside the file, more segment bytes than the file holds: ``SlideError``."""
         p = self.levels[level]
         if not (p.tiled and p.codec):
@@ -417,7 +456,7 @@ class TiffSlide:
         return BandSegments(shape=(h, w), data=np.frombuffer(b''.join(chunks), np.uint8), offsets=offsets, lengths=lengths,
                             place=np.array(place, np.int32).reshape(-1, 2),
                             clip=(max(0, -x), max(0, -y), min(w, p.width - x), min(h, p.height - y)),
-                            seg_w=p.tw, seg_h=p.th, jpeg_tables=p.jpeg_tables, codec=p.codec, ycc=p.ycc)
+                            seg_w=p.tw, seg_h=p.th, jpeg_tables=p.jpeg_tables, codec=p.codec, ycc=p.ycc, predictor=p.predictor)
 
     def close(self):
         self._f.close()

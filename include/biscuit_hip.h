@@ -239,6 +239,26 @@ int bq_j2k_decode_canvas(bq_ctx* ctx, const void* d_seg, int n, const void* d_bl
                          int clip_x0, int clip_y0, int clip_x1, int clip_y1, int32_t* d_status, void* d_scratch, size_t scratch_bytes,
                          bq_stream_t stream);
 
+/* A TIFF page's LZW tiles (compression 5, predictor 1 or 2) decoded on the device into a slide canvas (kernels_lzw.hip; DESIGN.md
+ * "Heatmap input", LZW tiles): the counterpart of bq_jpeg_decode_canvas.  Nothing is parsed on the host: d_data holds the n
+ * segments of seg_w x seg_h (each <= 1024) as the file has them, segment i at d_desc[i] = (offset, length) -- two uint32, the
+ * offset a multiple of 16, readable zero bytes behind every segment up to the next multiple of 16.  lzw_decode (a wave per
+ * segment; the stream is the statement of csrc/lzw_device.h) leaves the unpredicted bytes in d_scratch; lzw_place (a wave per
+ * segment row) undoes predictor 2 -- the running sum per sample modulo 256 -- and writes d_canvas uint8 [H][W][3] exactly as
+ * bq_jpeg_decode_canvas does: at d_place[i] = (x, y), inside the canvas and the clip rectangle only, in its store shape.
+ * d_status int32 [n]: 0 = decoded; otherwise bits -- 1 the first code is not ClearCode, 2 a code beyond the next free index,
+ * 4 the data ends or EndOfInformation arrives before seg_w * seg_h * 3 bytes, 8 the table ran to its end without a ClearCode,
+ * 16 a descriptor that fails the decoder's checks (offset not a multiple of 16, length above 2^28) -- and such a segment
+ * writes nothing.  The result is bqio_lzw_decode_canvas's byte for byte and status for status.  Scratch: seg_w * seg_h * 3
+ * bytes per segment rounded up to 16 (196 608 at 256 x 256); bq_lzw_canvas_scratch_bytes(n, seg_w, seg_h) asks for
+ * min(n, 1024) segments' worth, and the call works in rounds of as many segments as d_scratch holds -- one at least,
+ * BQ_ERR_WORKSPACE below that -- without a host synchronisation; no result depends on what the scratch held; n = 0 returns 0
+ * without a launch. */
+size_t bq_lzw_canvas_scratch_bytes(int n, int seg_w, int seg_h);
+int bq_lzw_decode_canvas(bq_ctx* ctx, const uint8_t* d_data, const void* d_desc, int n, int seg_w, int seg_h, int predictor,
+                         const int32_t* d_place, uint8_t* d_canvas, int H, int W, int clip_x0, int clip_y0, int clip_x1, int clip_y1,
+                         int32_t* d_status, void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
+
 /* Output side, JPEG tiles, encoded on the device (kernels_jpeg_encode.hip; DESIGN.md "Tile extraction"): n tiles d_tiles uint8
  * [n][px][px][3] -- the batch bq_tile_resample fills -- become the COMPLETE baseline-JPEG files Pillow writes for `save(buf, 'JPEG',
  * quality=quality, subsampling=subsampling)` with everything else at its default (libjpeg's 16-bit BT.601, h2v2 box filter, islow

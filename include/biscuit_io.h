@@ -169,6 +169,24 @@ int bqio_j2k_decode_canvas(const int32_t* seg_desc, int n, const int32_t* blocks
 /* pixels full-range YCbCr triples -> RGB with the bytes of Pillow's convert('RGB') (csrc/j2k_ycc.h); in place allowed. */
 void bqio_ycc_to_rgb(const uint8_t* ycc, uint8_t* rgb, size_t pixels);
 
+/* ---- TIFF pages with LZW compression (csrc/lzw_host.cpp, csrc/lzw_device.h; DESIGN.md "Heatmap input", LZW tiles) ----
+ * bqio_lzw_decode is the slide reader's segment decoder: raw[len], one strip or tile as libtiff writes it (TIFF 6.0 LZW: codes
+ * MSB first, ClearCode 256 first, early change), -> out uint8 [rows][seg_w][3] with the predictor undone (predictor 1: none,
+ * 2: horizontal differencing per sample modulo 256).  Returns 0 and the pixels libtiff gives, or a status > 0 -- bits: 1 the
+ * first code is not ClearCode (old-style or damaged), 2 a code beyond the next free index, 4 the data ends or EndOfInformation
+ * arrives before rows * seg_w * 3 bytes, 8 the table ran to its end (libtiff's: index 5119) without a ClearCode, 16 a stream
+ * of more than 2^28 bytes -- after which out is no image; BQIO_ERR_ARG (< 0) for an argument outside rows <= 2^15, seg_w <=
+ * 2^20, rows * seg_w * 3 <= 2^30, predictor 1 or 2. */
+int bqio_lzw_decode(const uint8_t* raw, size_t len, int rows, int seg_w, int predictor, uint8_t* out);
+/* The longest segment side bq_lzw_decode_canvas and bqio_lzw_decode_canvas take (1024). */
+int bqio_lzw_max_side(void);
+/* The CPU statement of bq_lzw_decode_canvas over the same routines: n segments of seg_w x seg_h (each <= 1024), segment i =
+ * data[desc[2 i] .. + desc[2 i + 1]) with desc[2 i] a multiple of 16 (status 16 otherwise), decoded INTO canvas (uint8 [H][W][3])
+ * at place[i] = (x, y), inside clip = (x0, y0, x1, y1) only.  status[i] as bqio_lzw_decode; a segment whose status is not 0
+ * writes nothing.  What bq_lzw_decode_canvas computes, byte for byte and status for status.  For tests. */
+int bqio_lzw_decode_canvas(const uint8_t* data, const uint32_t* desc, int n, int seg_w, int seg_h, int predictor, const int32_t* place,
+                           uint8_t* canvas, int H, int W, const int32_t* clip, int32_t* status, int n_threads);
+
 /* ---- tile resampling for the whole-slide heatmap (csrc/resample_host.cpp, csrc/resample_device.h) ----
  * The tap tables of Pillow's 8-bit resampler for Image.resize((px, px), Image.LANCZOS) of a src_px x src_px image: per output
  * coordinate i, bounds[2 i] = first source coordinate, bounds[2 i + 1] = number of taps, coef[i * ksize + j] = tap j with 22
