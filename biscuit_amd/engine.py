@@ -124,14 +124,16 @@ class Engine:
             self._ctx = None
             self._drop_caches()
 
+    def drop_scratch(self):
+        """Lets go of every device buffer grown on demand -- the network's workspace and each tool's scratch -- and of nothing else;
+        the next call that wants one allocates it again."""
+        self._ws = None                  # the network's workspace (``_ws_for``)
+        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap
+
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
-        self._ws = self._inflate_ws = self._jpeg_ws = self._j2k_ws = self._jpeg_enc_ws = self._png_enc_ws = None        # device buffers grown on demand (``_scratch``)
-        self._knn_ws = self._umap_ws = self._lzw_ws = None
-        self._resample_taps = {}         # (src_px, px) -> (bounds, coef) on the device (tile_resample)
-        self._grayspace_limit = {}       # threshold -> limit[256] on the device (tile_grayspace)
-        self._tissue_sdiv = None         # sdiv[256] on the device (tissue_blur)
-        self._tissue_taps = {}           # sigma -> (the Gaussian's taps on the device, r) (tissue_focus)
+        self.drop_scratch()
+        self._tables = {}                # (tool, key) -> the tool's table(s) of that key on the device (``_table``)
         self._host_held = []             # (event, host tables) of the calls the stream may not have passed yet (``_hold``)
 
     def __del__(self):
@@ -199,13 +201,24 @@ class Engine:
 
     def _scratch(self, name, need, given=None):
         """A call's scratch, ``need`` bytes: what the caller gave (launches that may overlap on different streams bring their own),
-        or the cached device buffer ``self.<name>`` (a torch uint8 tensor), where the old one goes before a larger one comes."""
+        or the cached device buffer of the family ``name`` (a torch uint8 tensor), where the old one goes before a larger one comes."""
         if given is not None:
             return given
-        if getattr(self, name) is None or getattr(self, name).numel() < need:
-            setattr(self, name, None)
-            setattr(self, name, torch.empty(int(need), dtype=torch.uint8, device=self.device))
-        return getattr(self, name)
+        if name not in self._tool_ws or self._tool_ws[name].numel() < need:
+            self._tool_ws.pop(name, None)
+            self._tool_ws[name] = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+        return self._tool_ws[name]
+
+    def _table(self, tool, key, build):
+        """A tool's table(s) on the device: ``build()`` -> numpy array(s), built and uploaded once per ``(tool, key)`` and kept; a
+        ``build`` that refuses its key stores nothing.  Later calls are one lookup."""
+        held = self._tables.get((tool, key))
+        if held is None:
+            host = build()
+            held = (torch.from_numpy(host).to(self.device) if isinstance(host, np.ndarray)
+                    else tuple(torch.from_numpy(a).to(self.device) for a in host))
+            self._tables[(tool, key)] = held
+        return held
 
     def _bytes(self, n):
         """``n`` bytes on this device that the caller owns: what the ``*_scratch`` methods hand out."""
@@ -218,12 +231,25 @@ class Engine:
         assert canvas.dtype == torch.uint8 and canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == 3 and canvas.shape[2] == 3
         return tuple(int(v) for v in clip)
 
-    def _encode(self, entry, scratch_attr, counter_attr, tiles, cap, scratch, scratch_bytes, *mid_args):
+    def _decode_canvas(self, entry, family, head_args, n, seg_w, seg_h, place, canvas, clip, scratch):
+        """The canvas decoders' call: ``bq_<entry>_decode_canvas(ctx, *head_args, place, canvas, H, W, clip, status, scratch, bytes,
+        stream)`` -- ``head_args`` the codec's own leading arguments in its header's order -- with the scratch of ``family`` sized by
+        ``bq_<entry>_canvas_scratch_bytes(n, seg_w, seg_h)`` unless the caller brought one.  -> status int32 [n] on the device."""
+        x0, y0, x1, y1 = self._canvas_args(n, place, canvas, clip)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        scratch = self._scratch(family, int(getattr(self._lib, f'bq_{entry}_canvas_scratch_bytes')(n, seg_w, seg_h)), scratch)
+        assert scratch.is_cuda and scratch.is_contiguous()
+        self._check(getattr(self._lib, f'bq_{entry}_decode_canvas')(self._ctx, *head_args, _ptr(place), _ptr(canvas), int(canvas.shape[0]),
+                                                                    int(canvas.shape[1]), x0, y0, x1, y1, _ptr(status), _ptr(scratch),
+                                                                    scratch.numel() * scratch.element_size(), self._stream()))
+        return status
+
+    def _encode(self, entry, counter_attr, tiles, cap, scratch, scratch_bytes, *mid_args):
         """The encoders' call: ``bq_<entry>(ctx, tiles, n, px, *mid_args, out, cap, off, status, scratch, ...)`` with ``cap`` bytes of
         output, and once more with the exact total -- which the first call's offsets state -- when the files did not fit (status
-        bit 1).  ``counter_attr`` counts the calls.  -> ``(buffer[:total], offsets on the host)``."""
+        bit 1).  The scratch is the family ``entry``'s; ``counter_attr`` counts the calls.  -> ``(buffer[:total], offsets on the host)``."""
         n, px = int(tiles.shape[0]), int(tiles.shape[1])
-        scratch = self._scratch(scratch_attr, int(scratch_bytes), scratch)
+        scratch = self._scratch(entry, int(scratch_bytes), scratch)
         off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
         status = torch.zeros(n, dtype=torch.int32, device=self.device)
         setattr(self, counter_attr, 0)
@@ -241,7 +267,11 @@ class Engine:
 
     def _ws_for(self, n, mc_n):
         """Caller-owned device workspace (a torch uint8 tensor), grown on demand."""
-        return self._scratch('_ws', self._lib.bq_workspace_bytes(self._ctx, int(n), int(mc_n)))
+        need = self._lib.bq_workspace_bytes(self._ctx, int(n), int(mc_n))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+        return self._ws
 
     def _mean_std(self, n, out):
         """The (mean, std) pair of a call, float32 [n, 2] each on the device: ``out`` when the caller gave one."""
@@ -292,7 +322,7 @@ class Engine:
         rows = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         need = int(self._lib.bq_png_inflate_scratch_bytes(n))
-        scratch = self._scratch('_inflate_ws', need, scratch)         # (a caller's own: ``inflate_scratch(n)``)
+        scratch = self._scratch('inflate', need, scratch)         # (a caller's own: ``inflate_scratch(n)``)
         assert scratch.numel() >= need
         self._check(self._lib.bq_png_inflate(self._ctx, _ptr(z), _ptr(off), _ptr(length), n, px, _ptr(rows), stride,
                                              _ptr(scratch), scratch.numel(), _ptr(status), self._stream()))
@@ -329,7 +359,7 @@ class Engine:
         out = torch.empty((n, px, px, 3), dtype=torch.uint8, device=self.device)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         need = int(self._lib.bq_jpeg_scratch_bytes(n, px))
-        scratch = self._scratch('_jpeg_ws', need, scratch)
+        scratch = self._scratch('jpeg', need, scratch)
         assert scratch.numel() >= need
         self._check(self._lib.bq_jpeg_decode(self._ctx, _ptr(scan), _ptr(desc), _ptr(tables), int(tables.shape[0]), n, px, _ptr(out),
                                              _ptr(status), _ptr(scratch), scratch.numel(), self._stream()))
@@ -353,15 +383,8 @@ class Engine:
         n, seg_w, seg_h = int(desc.shape[0]), int(seg_w), int(seg_h)
         assert desc.is_cuda and desc.is_contiguous() and desc.element_size() == 4 and tuple(desc.shape) == (n, 4)
         assert tables.dtype == torch.uint8 and tables.is_cuda and tables.is_contiguous() and tables.dim() == 2
-        x0, y0, x1, y1 = self._canvas_args(n, place, canvas, clip)
-        status = torch.empty(n, dtype=torch.int32, device=self.device)
-        scratch = self._scratch('_jpeg_ws', int(self._lib.bq_jpeg_canvas_scratch_bytes(n, seg_w, seg_h)), scratch)
-        assert scratch.is_cuda and scratch.is_contiguous()
-        self._check(self._lib.bq_jpeg_decode_canvas(self._ctx, _ptr(scan), _ptr(desc), _ptr(tables), int(tables.shape[0]), n, seg_w, seg_h,
-                                                    _ptr(place), _ptr(canvas), int(canvas.shape[0]), int(canvas.shape[1]), x0, y0, x1, y1,
-                                                    _ptr(status), _ptr(scratch), scratch.numel() * scratch.element_size(),
-                                                    self._stream()))
-        return status
+        return self._decode_canvas('jpeg', 'jpeg', (_ptr(scan), _ptr(desc), _ptr(tables), int(tables.shape[0]), n, seg_w, seg_h),
+                                   n, seg_w, seg_h, place, canvas, clip, scratch)
 
     def jpeg_canvas_scratch(self, n, seg_w, seg_h):
         """Coefficient space for ``jpeg_decode_canvas`` over ``n`` segments (``bq_jpeg_canvas_scratch_bytes``: 393 KB per 256 x 256
@@ -380,15 +403,8 @@ class Engine:
         assert desc.dtype == torch.int32 and desc.is_cuda and desc.is_contiguous() and tuple(desc.shape) == (n, 32)
         assert blocks.dtype == torch.int32 and blocks.is_cuda and blocks.is_contiguous() and blocks.dim() == 2 and blocks.shape[1] == 12
         assert cw.dtype == torch.uint8 and cw.is_cuda and cw.is_contiguous()
-        x0, y0, x1, y1 = self._canvas_args(n, place, canvas, clip)
-        status = torch.empty(n, dtype=torch.int32, device=self.device)
-        scratch = self._scratch('_j2k_ws', int(self._lib.bq_j2k_canvas_scratch_bytes(n, seg_w, seg_h)), scratch)
-        assert scratch.is_cuda and scratch.is_contiguous()
-        self._check(self._lib.bq_j2k_decode_canvas(self._ctx, _ptr(desc), n, _ptr(blocks), int(blocks.shape[0]), _ptr(cw), cw.numel(),
-                                                   seg_w, seg_h, int(bool(ycc)), _ptr(place), _ptr(canvas), int(canvas.shape[0]),
-                                                   int(canvas.shape[1]), x0, y0, x1, y1, _ptr(status), _ptr(scratch),
-                                                   scratch.numel() * scratch.element_size(), self._stream()))
-        return status
+        return self._decode_canvas('j2k', 'j2k', (_ptr(desc), n, _ptr(blocks), int(blocks.shape[0]), _ptr(cw), cw.numel(), seg_w, seg_h,
+                                                  int(bool(ycc))), n, seg_w, seg_h, place, canvas, clip, scratch)
 
     def j2k_canvas_scratch(self, n, seg_w, seg_h):
         """Plane space for ``j2k_decode_canvas`` over ``n`` segments (``bq_j2k_canvas_scratch_bytes``: 24 bytes a pixel, 1.5 MB per
@@ -409,14 +425,8 @@ class Engine:
         assert desc.is_cuda and desc.is_contiguous() and desc.element_size() == 4 and tuple(desc.shape) == (n, 2)
         if int(predictor) not in (1, 2):
             raise ValueError(f'predictor must be 1 or 2, not {predictor!r}')
-        x0, y0, x1, y1 = self._canvas_args(n, place, canvas, clip)
-        status = torch.empty(n, dtype=torch.int32, device=self.device)
-        scratch = self._scratch('_lzw_ws', int(self._lib.bq_lzw_canvas_scratch_bytes(n, seg_w, seg_h)), scratch)
-        assert scratch.is_cuda and scratch.is_contiguous()
-        self._check(self._lib.bq_lzw_decode_canvas(self._ctx, _ptr(data), _ptr(desc), n, seg_w, seg_h, int(predictor), _ptr(place),
-                                                   _ptr(canvas), int(canvas.shape[0]), int(canvas.shape[1]), x0, y0, x1, y1, _ptr(status),
-                                                   _ptr(scratch), scratch.numel() * scratch.element_size(), self._stream()))
-        return status
+        return self._decode_canvas('lzw', 'lzw', (_ptr(data), _ptr(desc), n, seg_w, seg_h, int(predictor)),
+                                   n, seg_w, seg_h, place, canvas, clip, scratch)
 
     def lzw_canvas_scratch(self, n, seg_w, seg_h):
         """Output space for ``lzw_decode_canvas`` over ``n`` segments (``bq_lzw_canvas_scratch_bytes``: 3 bytes a pixel, 196 608
@@ -437,7 +447,7 @@ class Engine:
         n, px, sub, quality = int(tiles.shape[0]), int(tiles.shape[1]), jpeg_subsampling(subsampling), int(quality)
         if cap is None:                     # (about 2 bits a sample at quality 95; the retry covers what this misses)
             cap = n * (1024 + px * px * 3 // (4 if quality < 98 else 2))
-        return self._encode('jpeg_encode', '_jpeg_enc_ws', 'jpeg_encode_calls', tiles, cap, scratch,
+        return self._encode('jpeg_encode', 'jpeg_encode_calls', tiles, cap, scratch,
                             self._lib.bq_jpeg_encode_scratch_bytes(n, max(px, 1), sub), quality, sub)
 
     def jpeg_encode_scratch(self, n, px=TILE_PX, subsampling='4:2:0'):
@@ -460,7 +470,7 @@ class Engine:
         n, px = int(tiles.shape[0]), int(tiles.shape[1])
         if cap is None:
             cap = n * (1024 + px * px * 3 // 2)
-        return self._encode('png_encode', '_png_enc_ws', 'png_encode_calls', tiles, cap, scratch,
+        return self._encode('png_encode', 'png_encode_calls', tiles, cap, scratch,
                             self._lib.bq_png_encode_scratch_bytes(n, max(px, 1)))
 
     def png_encode_scratch(self, n, px=TILE_PX):
@@ -484,12 +494,8 @@ class Engine:
         bounds = coef = None
         k = 0
         if src_px != px:
-            cache = self._resample_taps
-            if (src_px, px) not in cache:
-                from . import resample
-                b, c = resample.taps(src_px, px)
-                cache[(src_px, px)] = (torch.from_numpy(b).to(self.device), torch.from_numpy(c).to(self.device))
-            bounds, coef = cache[(src_px, px)]
+            from . import resample
+            bounds, coef = self._table('tile_resample', (src_px, px), lambda: resample.taps(src_px, px))
             k = int(coef.shape[1])
         self._check(self._lib.bq_tile_resample(self._ctx, _ptr(canvas), int(canvas.shape[0]), int(canvas.shape[1]), _ptr(origin), n,
                                                src_px, px, _ptr(bounds), _ptr(coef), k, _ptr(out), self._stream()))
@@ -501,14 +507,12 @@ class Engine:
         turns it into the integer table the kernel compares against)."""
         assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous() and tiles_u8.dim() == 4
         assert tiles_u8.shape[1] == tiles_u8.shape[2] and tiles_u8.shape[3] == 3
-        cache = self._grayspace_limit
+        from . import resample
         key = float(threshold)
-        if key not in cache:
-            from . import resample
-            cache[key] = torch.from_numpy(resample.grayspace_limit(key)).to(self.device)
+        limit = self._table('tile_grayspace', key, lambda: resample.grayspace_limit(key))
         n = int(tiles_u8.shape[0])
         count = torch.empty(n, dtype=torch.int32, device=self.device)
-        self._check(self._lib.bq_tile_grayspace(self._ctx, _ptr(tiles_u8), n, int(tiles_u8.shape[1]), _ptr(cache[key]), _ptr(count),
+        self._check(self._lib.bq_tile_grayspace(self._ctx, _ptr(tiles_u8), n, int(tiles_u8.shape[1]), _ptr(limit), _ptr(count),
                                                 self._stream()))
         return count
 
@@ -548,13 +552,11 @@ class Engine:
         replicated border, and hist int32 [256], the plane's histogram), both on the device, the integers of the numpy
         restatement.  ``H * W < 2^31``; H or W below 7 are legal."""
         h, w = self._thumb_hw(thumb_u8)
-        if self._tissue_sdiv is None:
-            from . import tissue
-            self._tissue_sdiv = torch.from_numpy(tissue.sdiv_table()).to(self.device)
+        from . import tissue
+        sdiv = self._table('tissue_blur', None, tissue.sdiv_table)
         plane = torch.empty((h, w), dtype=torch.uint8, device=self.device)
         hist = torch.empty(256, dtype=torch.int32, device=self.device)
-        self._check(self._lib.bq_tissue_blur(self._ctx, _ptr(thumb_u8), h, w, _ptr(self._tissue_sdiv), _ptr(plane), _ptr(hist),
-                                             self._stream()))
+        self._check(self._lib.bq_tissue_blur(self._ctx, _ptr(thumb_u8), h, w, _ptr(sdiv), _ptr(plane), _ptr(hist), self._stream()))
         return plane, hist
 
     def tissue_cells(self, plane, T, col, row):
@@ -584,10 +586,8 @@ class Engine:
         h, w = self._thumb_hw(thumb_u8, same_device=True)
         thr = tissue.focus_units(threshold)
         key = float(sigma)
-        if key not in self._tissue_taps:
-            taps = tissue.focus_taps(key)
-            self._tissue_taps[key] = (torch.from_numpy(taps).to(self.device), (len(taps) - 1) // 2)
-        d_taps, r = self._tissue_taps[key]
+        d_taps = self._table('tissue_focus', key, lambda: tissue.focus_taps(key))
+        r = (d_taps.numel() - 1) // 2
         work = torch.empty((h, w), dtype=torch.int32, device=self.device)
         v = torch.empty((h, w), dtype=torch.int32, device=self.device) if value else None
         plane = torch.empty((h, w), dtype=torch.uint8, device=self.device)
@@ -663,7 +663,7 @@ class Engine:
         need = int(self._lib.bq_knn_workspace_bytes(n, d, k))
         if need == 0:
             raise ValueError(f'knn takes 1 <= k <= 64, k <= n and D a multiple of 16, not n = {n}, D = {d}, k = {k}')
-        scratch = self._scratch('_knn_ws', need, scratch)
+        scratch = self._scratch('knn', need, scratch)
         assert scratch.numel() >= need
         idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
         dist = torch.empty((n, k), dtype=torch.float32, device=self.device)
@@ -684,7 +684,7 @@ class Engine:
         self._on_device('dist', dist)
         assert idx.is_contiguous() and dist.is_contiguous()
         n, k = int(idx.shape[0]), int(idx.shape[1])
-        scratch = self._scratch('_umap_ws', int(self._lib.bq_umap_smooth_scratch_bytes(n)), scratch)
+        scratch = self._scratch('umap', int(self._lib.bq_umap_smooth_scratch_bytes(n)), scratch)
         rho = torch.empty(n, dtype=torch.float32, device=self.device)
         sigma = torch.empty(n, dtype=torch.float32, device=self.device)
         w = torch.empty((n, k), dtype=torch.float32, device=self.device)

@@ -1,6 +1,6 @@
 """What must not move when a tool's entry point moves to the file of its kernel: the profiling class each ``bq_*`` call opens, and
-``Engine.close()`` letting go of every device tensor, whichever tool cached it.  One call of each tool at the smallest case its own
-test file uses: ``-m gpu``."""
+``Engine.close()`` letting go of every device tensor, whichever tool cached it.  One call of every tool at the smallest case its own
+test file uses -- the feature map's three have theirs in tests/test_gpu_poison_umap.py: ``-m gpu``."""
 import zlib
 
 import numpy as np
@@ -15,6 +15,7 @@ from biscuit_amd.wsi import TiffSlide
 from tests import _jpeg_cases as jc
 from tests import _j2k_cases as j2c
 from tests import _jpeg_encode_cases as ec
+from tests import _lzw_cases as lc
 from tests import _roi_ref as roi_ref
 from tests import _wsi_jpeg_cases as wj
 from tests.test_wsi import _img
@@ -25,7 +26,7 @@ pytestmark = pytest.mark.gpu
 TOOL_CLASSES = {'stage_u8_standardize', 'stage_f32_to_planar', 'stain_reinhard_fast', 'stain_macenko', 'stain_macenko_stats',
                 'range_key', 'range_screen', 'png_inflate', 'jpeg_decode', 'jpeg_decode_canvas', 'jpeg_encode_pixel',
                 'jpeg_encode_size', 'jpeg_encode_pack', 'jpeg_encode_stuff', 'png_encode_filter', 'png_encode_match', 'png_encode_code',
-                'png_encode_pack', 'j2k_t1', 'j2k_idwt', 'j2k_store', 'tile_resample', 'tile_grayspace', 'heatmap_render',
+                'png_encode_pack', 'j2k_t1', 'j2k_idwt', 'j2k_store', 'lzw_decode', 'lzw_place', 'tile_resample', 'tile_grayspace', 'heatmap_render',
                 'tissue_blur', 'tissue_cells', 'tissue_focus', 'tissue_cells_union', 'roi_plane', 'slide_reduce', 'roc_youden'}
 
 
@@ -100,6 +101,27 @@ def _png_encode_and_j2k_tools(eng, own_scratch=False):
     return _host(buf[:int(off[-1])], off, canvas, status)
 
 
+def _lzw_segments(k):
+    """``k`` 16 x 16 noise segments with predictor 2, packed for the decoder -> ``((data, desc), [pixels])``."""
+    tiles = [lc.content('noise', 16, 16, seed) for seed in range(k)]
+    raws = [lc.encode(lc.difference(t).tobytes()) for t in tiles]
+    ln = [len(r) for r in raws]
+    return tn.lzw_pack(np.frombuffer(b''.join(raws), np.uint8), np.cumsum([0] + ln[:-1]), ln), tiles
+
+
+def _lzw_tool(eng, own_scratch=False):
+    """One 16 x 16 LZW segment (noise, predictor 2) decoded into a white canvas: the CPU statement's bytes, and the pixels."""
+    (data, desc), (a,) = _lzw_segments(1)
+    place = np.zeros((1, 2), np.int32)
+    want = np.full((16, 16, 3), 255, np.uint8)
+    want_status = tn.lzw_decode_canvas(data, desc, 16, 16, place, want, (0, 0, 16, 16), predictor=2)
+    canvas = torch.full((16, 16, 3), 255, dtype=torch.uint8, device=eng.device)
+    status = eng.lzw_decode_canvas(_up(eng, data), _up(eng, desc.view(np.int32)), 16, 16, _up(eng, place), canvas, (0, 0, 16, 16), predictor=2,
+                                   scratch=eng.lzw_canvas_scratch(1, 16, 16) if own_scratch else None)
+    assert int(status[0]) == 0 == int(want_status[0]) and np.array_equal(canvas.cpu().numpy(), want) and np.array_equal(want, a)
+    return _host(canvas, status)
+
+
 def _heatmap_tools(eng):
     """A 16-px window resampled to 8 px, its grey pixels counted, and a one-cell heatmap drawn over a 3 x 5 thumbnail."""
     canvas = _up(eng, np.random.default_rng(2).integers(0, 256, (20, 24, 3), dtype=np.uint8))
@@ -148,6 +170,7 @@ def test_every_tool_opens_its_profiling_class_and_no_other(tmp_path):
         _png_tools(eng)
         _jpeg_tools(eng, tmp_path)
         _png_encode_and_j2k_tools(eng)
+        _lzw_tool(eng)
         _heatmap_tools(eng)
         _mask_tools(eng)
         mean = _up(eng, np.array([[0.25, 0.75]], np.float32))
@@ -175,14 +198,16 @@ def _device_tensors(x):
 def test_close_lets_go_of_every_device_tensor(tmp_path):
     """Every cache of the engine touched -- the grown scratch buffers and the per-tool tables --, then ``close()`` twice."""
     eng = _engine()
-    _heatmap_tools(eng)             # _resample_taps (src_px != px), _grayspace_limit
-    _mask_tools(eng)                # _tissue_sdiv, _tissue_taps, _host_held
-    _png_tools(eng)                 # _inflate_ws
-    _jpeg_tools(eng, tmp_path)      # _jpeg_ws, _jpeg_enc_ws
-    _png_encode_and_j2k_tools(eng)  # _png_enc_ws, _j2k_ws
-    held = {k: len(_device_tensors(v)) for k, v in vars(eng).items() if _device_tensors(v)}
-    assert {'_resample_taps', '_grayspace_limit', '_tissue_sdiv', '_tissue_taps', '_inflate_ws', '_jpeg_ws', '_jpeg_enc_ws', '_png_enc_ws',
-            '_j2k_ws'} <= set(held), held
+    _heatmap_tools(eng)             # tables: tile_resample (src_px != px), tile_grayspace
+    _mask_tools(eng)                # tables: tissue_blur, tissue_focus; _host_held
+    _png_tools(eng)                 # scratch: inflate
+    _jpeg_tools(eng, tmp_path)      # scratch: jpeg, jpeg_encode
+    _png_encode_and_j2k_tools(eng)  # scratch: png_encode, j2k
+    _lzw_tool(eng)                  # scratch: lzw
+    tables = {tool for (tool, key), v in eng._tables.items() if _device_tensors(v)}
+    scratch = {family for family, v in eng._tool_ws.items() if _device_tensors(v)}
+    assert {'tile_resample', 'tile_grayspace', 'tissue_blur', 'tissue_focus'} <= tables, tables
+    assert {'inflate', 'jpeg', 'jpeg_encode', 'png_encode', 'j2k', 'lzw'} <= scratch, scratch
     eng.close()
     assert {k: v for k, v in vars(eng).items() if _device_tensors(v)} == {}
     eng.close()

@@ -138,8 +138,8 @@ def test_bad_arguments(eng):
     thumb = torch.zeros((8, 9, 3), dtype=torch.uint8, device=dev)
     plane, count = eng.tissue_focus(thumb)
     assert int(count.cpu().numpy()[0]) == 72 and not plane.any().item()
-    taps, r = eng._tissue_taps[3.0]
-    assert r == 12 and taps.cpu().numpy().tolist() == F.taps()
+    taps = eng._tables['tissue_focus', 3.0]
+    assert (taps.numel() - 1) // 2 == 12 and taps.cpu().numpy().tolist() == F.taps()
     work = torch.zeros((8, 9), dtype=torch.int32, device=dev)
     value = torch.full((8, 9), -7, dtype=torch.int32, device=dev)
     cnt = torch.full((1,), -7, dtype=torch.int32, device=dev)
@@ -161,7 +161,7 @@ def test_bad_arguments(eng):
     for kw in (dict(sigma=4.2), dict(sigma=0.0), dict(threshold=-0.5), dict(threshold=float('nan'))):        # r = 17, r = 0
         with pytest.raises(ValueError):
             eng.tissue_focus(thumb, **kw)
-    assert 4.2 not in eng._tissue_taps and 0.0 not in eng._tissue_taps
+    assert ('tissue_focus', 4.2) not in eng._tables and ('tissue_focus', 0.0) not in eng._tables
 
     otsu = torch.zeros((8, 9), dtype=torch.uint8, device=dev)
     fplane = torch.ones((4, 5), dtype=torch.uint8, device=dev)

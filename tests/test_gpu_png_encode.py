@@ -114,10 +114,10 @@ def test_close_releases_the_scratch():
     e = Engine(synthetic_weights(1), dtype='f16', max_batch=8, max_mc=2)
     try:
         e.png_encode(torch.zeros((2, 8, 8, 3), dtype=torch.uint8, device='cuda'))
-        assert e._png_enc_ws is not None and e._png_enc_ws.is_cuda
+        assert e._tool_ws['png_encode'].is_cuda
     finally:
         e.close()
-    assert e._png_enc_ws is None
+    assert e._tool_ws == {} and e._ws is None
 
 
 @pytest.mark.parametrize('px', [5, 74, 299])

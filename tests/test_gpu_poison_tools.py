@@ -47,7 +47,7 @@ def under_every_fill(eng, fn):
     results = []
     for fill in P.BYTE_FILLS:
         torch.cuda.synchronize(eng.device)
-        eng._ws = eng._inflate_ws = eng._jpeg_ws = eng._j2k_ws = eng._jpeg_enc_ws = eng._png_enc_ws = None
+        eng.drop_scratch()
         proxy = P.poisoned_torch(fill)
         with pytest.MonkeyPatch.context() as mp:
             mp.setattr(engine_mod, 'torch', proxy)
@@ -102,6 +102,11 @@ def test_jpeg_tools(eng, tmp_path):
 def test_png_encode_and_j2k_tools(eng):
     under_every_fill(eng, lambda: homes._png_encode_and_j2k_tools(eng, own_scratch=True))
     under_every_fill(eng, lambda: homes._png_encode_and_j2k_tools(eng))
+
+
+def test_lzw_tool(eng):
+    under_every_fill(eng, lambda: homes._lzw_tool(eng, own_scratch=True))
+    under_every_fill(eng, lambda: homes._lzw_tool(eng))
 
 
 def test_heatmap_tools(eng):
@@ -192,6 +197,23 @@ def test_j2k_decode_in_rounds(eng):
         canvas = torch.full((24, 70, 3), 255, dtype=torch.uint8, device=eng.device)
         status = eng.j2k_decode_canvas(*(up(eng, a) for a in packed), 32, 16, up(eng, place), canvas, (1, 0, 69, 23),
                                        scratch=eng.j2k_canvas_scratch(2, 32, 16))
+        return host(canvas, status)
+    canvas, status = under_every_fill(eng, call)
+    assert np.array_equal(status, want_status) and not status.any() and np.array_equal(canvas, want)
+
+
+def test_lzw_decode_in_rounds(eng):
+    """Three 16 x 16 segments with scratch for one: three rounds, each over the bytes the round before left; the CPU statement's bytes."""
+    (data, desc), tiles = homes._lzw_segments(3)
+    place = np.array([[0, 0], [16, 0], [32, 0]], np.int32)
+    want = np.full((16, 48, 3), 255, np.uint8)
+    want_status = tn.lzw_decode_canvas(data, desc, 16, 16, place, want, (0, 0, 48, 16), predictor=2)
+    assert np.array_equal(want, np.concatenate(tiles, 1))
+
+    def call():
+        canvas = torch.full((16, 48, 3), 255, dtype=torch.uint8, device=eng.device)
+        status = eng.lzw_decode_canvas(up(eng, data), up(eng, desc.view(np.int32)), 16, 16, up(eng, place), canvas, (0, 0, 48, 16), predictor=2,
+                                       scratch=eng.lzw_canvas_scratch(1, 16, 16))
         return host(canvas, status)
     canvas, status = under_every_fill(eng, call)
     assert np.array_equal(status, want_status) and not status.any() and np.array_equal(canvas, want)

@@ -46,7 +46,7 @@ def test_results_do_not_depend_on_stale_bytes(eng, own_scratch):
     assert np.isfinite(clean[5]).all() and (clean[0][:, 0] == np.arange(257)).all()
     for fill in P.BYTE_FILLS:
         torch.cuda.synchronize(eng.device)
-        eng._knn_ws = eng._umap_ws = None
+        eng.drop_scratch()
         proxy = P.poisoned_torch(fill)
         with pytest.MonkeyPatch.context() as mp:
             mp.setattr(engine_mod, 'torch', proxy)
@@ -73,7 +73,6 @@ def test_exactly_the_three_new_classes():
 def test_close_lets_go_of_the_scratch():
     eng = _engine()
     all_three(eng)
-    held = {k for k, v in vars(eng).items() if _device_tensors(v)}
-    assert {'_knn_ws', '_umap_ws'} <= held, held
+    assert {'knn', 'umap'} <= {k for k, v in eng._tool_ws.items() if _device_tensors(v)}, eng._tool_ws.keys()
     eng.close()
     assert {k: v for k, v in vars(eng).items() if _device_tensors(v)} == {}

@@ -101,7 +101,7 @@ def test_bad_arguments(eng):
     dev = eng.device
     thumb = torch.zeros((8, 9, 3), dtype=torch.uint8, device=dev)
     plane, hist = eng.tissue_blur(thumb)
-    sdiv = eng._tissue_sdiv
+    sdiv = eng._tables['tissue_blur', None]
     st = torch.cuda.current_stream(dev).cuda_stream
     p = lambda t: t.data_ptr()                                               # noqa: E731
     blur = lambda th, h, w, sd, pl, hi: eng._lib.bq_tissue_blur(eng._ctx, th, h, w, sd, pl, hi, st)      # noqa: E731

@@ -36,6 +36,14 @@ def test_abi_symbols_exported():
             Engine({}, dtype='bf16')
 
 
+def test_abi_types_are_the_headers():
+    """Every restype and argtype of ``_lib.ABI`` has the width class of the prototype's type at that position: a wrong width in
+    one of these lists would corrupt memory on the device, not fail a test."""
+    from biscuit_amd import _lib
+    from tests._abi_types import assert_abi_matches_header
+    assert_abi_matches_header(_lib.ABI, os.path.join(ROOT, 'include', 'biscuit_hip.h'))
+
+
 def test_the_library_defines_exactly_the_abi():
     """The dynamic symbols of libbiscuit_hip.so that begin with ``bq_`` are the ABI and nothing else, whichever file of csrc/
     defines each: an entry point that a move lost, or a helper that took the prefix, shows here without a GPU."""

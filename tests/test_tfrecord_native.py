@@ -29,6 +29,12 @@ def test_header_symbols_exported():
     tn.load()        # every declared symbol resolves
 
 
+def test_abi_types_are_the_headers():
+    """Every restype and argtype of ``tfrecord_native.ABI`` has the width class of the prototype's type at that position."""
+    from tests._abi_types import assert_abi_matches_header
+    assert_abi_matches_header(tn.ABI, os.path.join(os.path.dirname(tn.LIB_PATH), '..', 'include', 'biscuit_io.h'))
+
+
 def test_crc_matches_python():
     for data in (b'', b'a', b'123456789', bytes(range(256)) * 7 + b'xyz'):
         assert tn.lib().bqio_masked_crc32c(data, len(data)) == tfr.masked_crc(data)
