@@ -92,6 +92,11 @@ ABI = {
     'bq_umap_smooth_scratch_bytes': (_sz, [_i64]),
     'bq_umap_smooth': (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'bq_umap_epoch': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _u64, _i, _vp]),
+    'bq_uq_chunk_rows': (_i64, [_i64]),
+    'bq_uq_kde_workspace_bytes': (_sz, [_i64, _i]),
+    'bq_uq_kde': (_i, [_vp, _vp, _vp, _i64, _i, C.c_double, _vp, _vp, _sz, _vp]),
+    'bq_uq_loess_workspace_bytes': (_sz, [_i64, _i]),
+    'bq_uq_loess': (_i, [_vp, _vp, _vp, _i64, _i, C.c_double, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -128,7 +128,7 @@ class Engine:
         """Lets go of every device buffer grown on demand -- the network's workspace and each tool's scratch -- and of nothing else;
         the next call that wants one allocates it again."""
         self._ws = None                  # the network's workspace (``_ws_for``)
-        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap
+        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq
 
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
@@ -889,6 +889,86 @@ class Engine:
         if o[4] == 0 or o[5] == 0:
             raise ValueError('ROC undefined: only one class present')
         return float(o[0]), {'j': float(o[1]), 'tpr': float(o[2]), 'fpr': float(o[3]), 'n_pos': int(o[4]), 'n_neg': int(o[5])}
+
+    # ------------------------------------------------------------------ UQ calibration (kernels_calib.hip)
+    UQ_MAX_GRID = 1024
+
+    def _uq_inputs(self, tool, x, correct, grid):
+        """``(x float64 [n], correct uint8 [n])`` on this device from arrays or tensors, as ``youden`` takes them; ValueError for
+        an empty input, a length mismatch, a non-finite ``x`` or a ``grid`` outside 2 .. 1024."""
+        if torch.is_tensor(x):
+            xd = x.to(device=self.device, dtype=torch.float64).contiguous().reshape(-1)
+            finite = bool(torch.isfinite(xd).all())
+        else:
+            xh = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            finite = bool(np.isfinite(xh).all())
+            xd = torch.from_numpy(xh).to(self.device)
+        if torch.is_tensor(correct):
+            cd = (correct != 0).to(device=self.device, dtype=torch.uint8).contiguous().reshape(-1)
+        else:
+            cd = torch.from_numpy(np.ascontiguousarray(np.asarray(correct) != 0).reshape(-1).view(np.uint8)).to(self.device)
+        n = int(xd.numel())
+        if n == 0 or cd.numel() != n or n >= 1 << 31:
+            raise ValueError(f'{tool}: empty input, length mismatch or more than 2^31 - 1 rows')
+        if not finite:
+            raise ValueError(f'{tool}: uncertainty must be finite')
+        if not 2 <= int(grid) <= self.UQ_MAX_GRID:
+            raise ValueError(f'{tool}: grid must lie in 2 .. {self.UQ_MAX_GRID}, not {grid!r}')
+        return xd, cd, n
+
+    def uq_chunk_rows(self, n):
+        """Rows of one chunk of the calibration sums over ``n`` rows (``bq_uq_chunk_rows``): the order of summation is fixed by it."""
+        return int(self._lib.bq_uq_chunk_rows(int(n)))
+
+    def uq_kde_scratch(self, n, grid=200):
+        """Scratch for ``uq_kde`` over ``n`` rows (one buffer per launch that may be in flight)."""
+        return self._bytes(self._lib.bq_uq_kde_workspace_bytes(int(n), int(grid)))
+
+    def uq_loess_scratch(self, n, grid=200):
+        """Scratch for ``uq_loess`` over ``n`` rows (one buffer per launch that may be in flight)."""
+        return self._bytes(self._lib.bq_uq_loess_workspace_bytes(int(n), int(grid)))
+
+    def uq_kde(self, x, correct, grid=200, cut=3.0, scratch=None):
+        """Gaussian kernel density of the uncertainty ``x`` per group of ``correct`` over every row (``bq_uq_kde``): Scott's
+        bandwidth, ``grid`` support points from ``min - cut bw`` to ``max + cut bw``.  Arrays or tensors.  -> host float64 arrays
+        ``{'support' [2, grid], 'density' [2, grid], 'n' [2], 'min', 'max', 'mean', 'std', 'bw' [2], 'valid' bool [2]}``, index 0
+        the incorrect and 1 the correct rows; the density integrates to 1 per group (``scipy.stats.gaussian_kde``); a group
+        with fewer than two rows or no spread is not ``valid`` and its curve is NaN.  ValueError for a non-finite ``x``."""
+        xd, cd, n = self._uq_inputs('uq_kde', x, correct, grid)
+        grid, cut = int(grid), float(cut)
+        if not 0.0 <= cut <= 1e6:
+            raise ValueError(f'uq_kde: cut must lie in 0 .. 1e6, not {cut!r}')
+        need = int(self._lib.bq_uq_kde_workspace_bytes(n, grid))
+        scratch = self._scratch('uq', need, scratch)
+        assert scratch.is_cuda and scratch.numel() >= need
+        out = torch.empty(4 * grid + 16, dtype=torch.float64, device=self.device)
+        self._check(self._lib.bq_uq_kde(self._ctx, _ptr(xd), _ptr(cd), n, grid, cut, _ptr(out), _ptr(scratch), scratch.numel(), self._stream()))
+        o = out.cpu().numpy()
+        st = o[4 * grid:].reshape(2, 8)
+        return {'support': o[:2 * grid].reshape(2, grid).copy(), 'density': o[2 * grid:4 * grid].reshape(2, grid).copy(),
+                'n': st[:, 0].astype(np.int64), 'min': st[:, 1].copy(), 'max': st[:, 2].copy(), 'mean': st[:, 3].copy(),
+                'std': st[:, 4].copy(), 'bw': st[:, 5].copy(), 'valid': st[:, 6] != 0}
+
+    def uq_loess(self, x, correct, grid=200, span=0.75, scratch=None):
+        """Local quadratic regression of ``correct`` on the uncertainty ``x`` over every row, fitted at ``grid`` vertices from
+        ``min x`` to ``max x`` (``bq_uq_loess``): window of ``floor(span n + 1e-5)`` rows, tricube weights.  Arrays or tensors.
+        -> host float64 arrays ``{'vertex', 'fit', 'l2', 'lam', 'h'}`` [grid] and the scalars ``'nu'``, ``'rss'``,
+        ``'degenerate'``, ``'q'``, ``'n'``; a degenerate vertex has NaN ``fit``, ``l2`` and ``lam``.  ValueError for a non-finite
+        ``x`` or a span whose window holds no row or more than all of them."""
+        xd, cd, n = self._uq_inputs('uq_loess', x, correct, grid)
+        grid, span = int(grid), float(span)
+        q = int(np.floor(span * n + 1e-5)) if span > 0 else 0
+        if not 1 <= q <= n:
+            raise ValueError(f'uq_loess: the window of span {span!r} over {n} rows holds {q} rows; it must hold 1 .. {n}')
+        need = int(self._lib.bq_uq_loess_workspace_bytes(n, grid))
+        scratch = self._scratch('uq', need, scratch)
+        assert scratch.is_cuda and scratch.numel() >= need
+        out = torch.empty(5 * grid + 4, dtype=torch.float64, device=self.device)
+        self._check(self._lib.bq_uq_loess(self._ctx, _ptr(xd), _ptr(cd), n, grid, span, _ptr(out), _ptr(scratch), scratch.numel(), self._stream()))
+        o = out.cpu().numpy()
+        res = {k: o[i * grid:(i + 1) * grid].copy() for i, k in enumerate(('vertex', 'fit', 'l2', 'lam', 'h'))}
+        res.update(nu=float(o[5 * grid]), rss=float(o[5 * grid + 1]), degenerate=int(o[5 * grid + 2]), q=int(o[5 * grid + 3]), n=n)
+        return res
 
     def debug_activation(self, name, staged, shape_hwc, true_scale=True):
         """The named activation as fp32 [n,H,W,C]; with activation exponents (``act_exp``) the stored tensor times 2^k, i.e. the

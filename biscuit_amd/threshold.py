@@ -13,9 +13,12 @@ appearance; ``y_true`` group mean truncated to uint8; strict ``<`` UQ filters; a
 threshold disables a filter; ``>=`` in group binarisation vs ``>`` in ``apply``; with
 ``slide_uq`` not 'detect', ``detect`` reports 0.5.  One deliberate difference: a frame
 missing required columns raises ``ValueError`` (the reference intends that but trips an
-``UnboundLocalError`` first, ``threshold.py:184-186``).  Plotting is out of scope.
+``UnboundLocalError`` first, ``threshold.py:184-186``).  Drawing is out of scope; the data behind the reference's
+diagnostic figure is not: ``plot_uncertainty`` returns it (``calibration.py``), and ``apply`` / ``detect`` save it where the reference
+draws when ``plot`` names a directory.
 """
 import logging
+import os
 import warnings
 
 import numpy as np
@@ -43,13 +46,18 @@ class _RocUndefined(ValueError):
 _DEVICE = {'engine': None, 'min_rows': 0}
 
 
-def use_device(engine, min_rows=100_000):
+def use_device(engine, min_rows=100_000, calibration_min_rows=None):
     """Route the Youden threshold searches of tables with at least ``min_rows`` rows to
     ``engine.youden`` (``bq_roc_youden``: sort + scan + first-maximum reduce on the GPU, the same threshold
     value; ``tests/test_gpu_parity.py`` checks it against this module's scikit-learn path).  ``None``
-    switches back to the host.  The cohort-wide tile table is 1.6 M rows at BASELINE config 3."""
+    switches back to the host.  The cohort-wide tile table is 1.6 M rows at BASELINE config 3.
+    The calibration data (``plot_uncertainty``, ``calibration.py``) of a table with at least ``calibration_min_rows`` rows goes
+    to ``engine.uq_kde`` / ``engine.uq_loess``; by default the smaller of ``min_rows`` and ``calibration.DEFAULT_MIN_ROWS``."""
+    from . import calibration
     _DEVICE['engine'] = engine
     _DEVICE['min_rows'] = int(min_rows)
+    _DEVICE['calibration_min_rows'] = int(min(int(min_rows), calibration.DEFAULT_MIN_ROWS) if calibration_min_rows is None
+                                          else calibration_min_rows)
 
 
 def _youden_threshold(y_true, y_score):
@@ -86,6 +94,24 @@ def auc(y_true, y_pred):
         except ValueError:
             log.warning('Unable to calculate ROC')
             return np.nan
+
+
+def plot_uncertainty(df, kind, threshold=None, title=None):
+    """The data of the reference's figure of predictions against uncertainty (``threshold.py:15-122``) over every row of ``df``
+    (columns ``uncertainty``, ``correct``, ``y_pred``): the ``calibration.Calibration`` of ``uncertainty_calibration``, ``title``
+    kept in its summary, where the reference draws and returns None."""
+    from . import calibration
+    return calibration.uncertainty_calibration(df, kind, threshold, title=title)
+
+
+def _plot_target(plot):
+    """``plot`` of ``apply`` / ``detect``: falsy -> None; a directory (str or os.PathLike) -> where the calibration data is saved;
+    anything else -- True -- asks for a drawing, which stays out of scope."""
+    if isinstance(plot, (str, os.PathLike)):
+        return os.fspath(plot)
+    if plot:
+        raise NotImplementedError('plotting is outside the hot path (threshold.py:15-122)')
+    return None
 
 
 def process_tile_predictions(df, pred_thresh=0.5, patients=None):
@@ -187,8 +213,7 @@ def apply(df, tile_uq, slide_uq, tile_pred=0.5, slide_pred=0.5, plot=False,
     (``threshold.py:248-361``).  Returns (metrics dict, thresholded group frame)."""
     assert keep in ('high_confidence', 'low_confidence')
     assert not (level == 'patient' and patients is None)
-    if plot:
-        raise NotImplementedError('plotting is outside the hot path (threshold.py:15-122)')
+    plot = _plot_target(plot)
     if patients:
         df['patient'] = df['slide'].map(patients)
     df, _ = process_tile_predictions(df, pred_thresh=tile_pred, patients=patients)
@@ -200,6 +225,8 @@ def apply(df, tile_uq, slide_uq, tile_pred=0.5, slide_pred=0.5, plot=False,
     except errors.ROCFailedError:
         log.error('Unable to process slide predictions')
         return {k: None for k in ('auc', 'percent_incl', 'acc', 'sensitivity', 'specificity')}, None
+    if plot:
+        plot_uncertainty(s_df, threshold=slide_uq, kind=level, title=title).save(plot)
     if slide_uq:
         if keep == 'high_confidence':
             s_df = s_df.loc[s_df['uncertainty'] < slide_uq]
@@ -213,8 +240,7 @@ def detect(df, tile_uq='detect', slide_uq='detect', tile_pred='detect', slide_pr
     """Detect optimal tile- and slide-level uncertainty thresholds
     (``threshold.py:364-475``).  Returns (thresholds dict, slide-level AUROC)."""
     empty = {k: None for k in ('tile_uq', 'slide_uq', 'tile_pred', 'slide_pred')}
-    if plot:
-        raise NotImplementedError('plotting is outside the hot path')
+    plot = _plot_target(plot)
     try:
         df, detected_tile_pred = process_tile_predictions(df, pred_thresh=tile_pred, patients=patients)
     except errors.PredsContainNaNError:
@@ -242,9 +268,13 @@ def detect(df, tile_uq='detect', slide_uq='detect', tile_pred='detect', slide_pr
             slide_uq = None
         else:
             slide_uq = _youden_threshold(s_df['incorrect'].to_numpy(), s_df['uncertainty'].to_numpy())
+            if plot:
+                plot_uncertainty(s_df, threshold=slide_uq, kind='slide').save(plot)
             s_df = s_df[s_df['uncertainty'] < slide_uq]
     else:
         slide_uq = 0.5
+        if plot:
+            plot_uncertainty(s_df, threshold=slide_uq, kind='slide').save(plot)
     a = auc(s_df['y_true'].to_numpy(), s_df['y_pred'].to_numpy())
     return {'tile_uq': tile_uq, 'slide_uq': slide_uq, 'tile_pred': tile_pred,
             'slide_pred': slide_pred}, a

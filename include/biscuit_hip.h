@@ -561,6 +561,33 @@ int bq_umap_epoch(bq_ctx* ctx, const float* d_prev, float* d_out, int64_t n, con
                   const float* d_eps, float* d_next, int epoch, float alpha, float a, float b, uint64_t seed, int block,
                   bq_stream_t stream);
 
+/* The data behind the UQ calibration figure over every row of a tile table (kernels_calib.hip; DESIGN.md section 7 "UQ
+ * calibration"; biscuit/threshold.py:15-122): d_x float64 [n] the uncertainty (finite: the caller checks), d_correct uint8 [n]
+ * (non-zero = correct), in any order; 1 <= n <= 2^31 - 1, 2 <= grid <= 1024.  All arithmetic is float64; the rows are summed in
+ * chunks of bq_uq_chunk_rows(n) and the chunks in order, without atomics: the same bits every call.
+ *
+ * bq_uq_kde: the Gaussian kernel density of x per group g (0 = incorrect, 1 = correct) with Scott's bandwidth bw = std(ddof 1)
+ * n_g^(-1/5) at grid points linspace(min_g - cut bw, max_g + cut bw, grid).  d_out float64 [4 grid + 16] = support [2][grid],
+ * density [2][grid] (integrating to 1 per group: scipy.stats.gaussian_kde), stat [2][8] = n_g, min, max, mean, std, bw, valid,
+ * 1 / (n_g bw sqrt(2 pi)).  A group with n_g < 2 or std = 0 has valid = 0 and NaN support and density.
+ *
+ * bq_uq_loess: local quadratic regression of y = (correct != 0) on x at the vertices linspace(min x, max x, grid): window of
+ * q = floor(span n + 1e-5) rows (1 <= q <= n), tricube weights.  d_out float64 [5 grid + 4] = vertex, fit, l2 (squared norm of
+ * the smoother's row), lam (self-influence at the vertex), h (the window's half-width), each [grid], then nu = sum_i lam~(x_i),
+ * rss = sum_i (y_i - fit~(x_i))^2 (~: linear interpolation over the vertices), the number of degenerate vertices, q.  A
+ * degenerate vertex (h = 0, or fewer than three distinct x inside the window) has NaN fit, l2 and lam.
+ *
+ * d_ws: bq_uq_*_workspace_bytes(n, grid) bytes (0 for arguments the call refuses), 256-byte aligned, caller-owned, contents
+ * unspecified on entry; BQ_ERR_WORKSPACE below that.  Both allocate nothing and are enqueued on `stream` without a host
+ * synchronisation; a bad argument is BQ_ERR_ARG with nothing enqueued. */
+int64_t bq_uq_chunk_rows(int64_t n);
+size_t bq_uq_kde_workspace_bytes(int64_t n, int grid);
+int bq_uq_kde(bq_ctx* ctx, const double* d_x, const uint8_t* d_correct, int64_t n, int grid, double cut, double* d_out, void* d_ws,
+              size_t ws_bytes, bq_stream_t stream);
+size_t bq_uq_loess_workspace_bytes(int64_t n, int grid);
+int bq_uq_loess(bq_ctx* ctx, const double* d_x, const uint8_t* d_correct, int64_t n, int grid, double span, double* d_out, void* d_ws,
+                size_t ws_bytes, bq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
