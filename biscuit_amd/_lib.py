@@ -97,6 +97,9 @@ ABI = {
     'bq_uq_kde': (_i, [_vp, _vp, _vp, _i64, _i, C.c_double, _vp, _vp, _sz, _vp]),
     'bq_uq_loess_workspace_bytes': (_sz, [_i64, _i]),
     'bq_uq_loess': (_i, [_vp, _vp, _vp, _i64, _i, C.c_double, _vp, _vp, _sz, _vp]),
+    'bq_delong_workspace_bytes': (_sz, [_i, _i64]),
+    'bq_delong_chunk_rows': (_i64, [_i64]),
+    'bq_delong': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _sz, _vp, _vp, _vp]),
 }
 
 

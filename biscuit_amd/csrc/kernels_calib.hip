@@ -13,24 +13,14 @@
 #include <rocprim/rocprim.hpp>
 
 #include "bq_ctx.h"
+#include "chunk_sum.h"
 
 namespace {
 
-constexpr int NT = 256;              // threads of every workgroup here
-constexpr int NW = NT / 64;          // its waves
-constexpr long long CHUNK_MIN = 2048;   // rows of a chunk up to MAX_CHUNKS chunks; beyond that the chunk grows, not their number
-constexpr long long MAX_CHUNKS = 2048;
 constexpr int KDE_PT = 8;            // support points of a density workgroup: 2 groups x 8 sums in registers
 constexpr int LO_PT = 4;             // vertices of a regression workgroup: 4 x 13 moments in registers
 constexpr int NMOM = 13;             // m0..m4 (sum w u^k), t0..t2 (sum w y u^k), r0..r4 (sum w^2 u^k)
 constexpr int MAX_GRID = 1024;       // the residual pass holds three vertex arrays in LDS
-
-__host__ __device__ inline long long chunk_rows(long long n) {
-    long long per = (n + MAX_CHUNKS - 1) / MAX_CHUNKS;
-    per = (per + NT - 1) / NT * NT;
-    return per < CHUNK_MIN ? CHUNK_MIN : per;
-}
-__host__ __device__ inline long long num_chunks(long long n) { return (n + chunk_rows(n) - 1) / chunk_rows(n); }
 
 // a * b + c in two roundings, as numpy computes it: the grid points must be the host's bit for bit (a row's segment of the
 // interpolant is decided by comparing against them), so this product and sum may not contract into an FMA
@@ -46,11 +36,6 @@ __device__ inline double linspace_at(double start, double stop, int G, int j) {
     return j == G - 1 ? stop : mul_add_2r((double)j, step, start);
 }
 
-// butterfly: every lane ends with the sum of the wave's 64 values, added in the same order in every run
-__device__ inline double wave_sum(double v) {
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
 __device__ inline double wave_min(double v) {
     for (int m = 1; m < 64; m <<= 1) v = fmin(v, __shfl_xor(v, m));
     return v;
@@ -58,26 +43,6 @@ __device__ inline double wave_min(double v) {
 __device__ inline double wave_max(double v) {
     for (int m = 1; m < 64; m <<= 1) v = fmax(v, __shfl_xor(v, m));
     return v;
-}
-
-// v[K] of every thread -> lds[K]: the workgroup's sums, waves added in wave order.  lds: (NW + 1) * K doubles.  Ends on a barrier.
-template <int K>
-__device__ inline double* block_sum(double (&v)[K], double* lds) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) lds[wave * K + k] = s;
-    }
-    __syncthreads();
-    double* out = lds + NW * K;
-    for (int k = threadIdx.x; k < K; k += NT) {
-        double s = lds[k];
-        for (int w = 1; w < NW; ++w) s += lds[w * K + k];
-        out[k] = s;
-    }
-    __syncthreads();
-    return out;
 }
 
 // ---------------------------------------------------------------- density

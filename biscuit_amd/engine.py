@@ -128,7 +128,7 @@ class Engine:
         """Lets go of every device buffer grown on demand -- the network's workspace and each tool's scratch -- and of nothing else;
         the next call that wants one allocates it again."""
         self._ws = None                  # the network's workspace (``_ws_for``)
-        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq
+        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong
 
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
@@ -968,6 +968,63 @@ class Engine:
         o = out.cpu().numpy()
         res = {k: o[i * grid:(i + 1) * grid].copy() for i, k in enumerate(('vertex', 'fit', 'l2', 'lam', 'h'))}
         res.update(nu=float(o[5 * grid]), rss=float(o[5 * grid + 1]), degenerate=int(o[5 * grid + 2]), q=int(o[5 * grid + 3]), n=n)
+        return res
+
+    # ------------------------------------------------------------------ prediction metrics (kernels_delong.hip)
+    DELONG_MAX_K, DELONG_MAX_ROWS = 8, 1 << 25
+
+    def delong_scratch(self, k, n):
+        """Scratch for ``delong`` over ``k`` classifiers and ``n`` rows (one buffer per launch that may be in flight)."""
+        return self._bytes(self._lib.bq_delong_workspace_bytes(int(k), int(n)))
+
+    def delong_chunk_rows(self, n):
+        """Rows of one chunk of the covariance sums over ``n`` rows (``bq_delong_chunk_rows``): the order of summation is fixed by it."""
+        return int(self._lib.bq_delong_chunk_rows(int(n)))
+
+    def delong(self, y_true, scores, components=False, scratch=None):
+        """AUROC and DeLong's covariance of ``k`` classifiers on the same ``n`` rows (``bq_delong``).  ``y_true`` [n]: 0/1 or bool;
+        ``scores`` [k, n] or [n] (k = 1), float64; arrays or tensors.  -> host arrays ``{'auc' [k], 'cov' [k, k], 'n_pos', 'n_neg'}``
+        and, with ``components``, ``'V' [k, n]``: the structural component of every row, in row order.  ValueError, with nothing
+        launched, for a NaN score, labels other than 0/1, one class only, k outside 1 .. 8, n above 2^25 or a shape mismatch."""
+        if torch.is_tensor(scores):
+            sd = scores.to(device=self.device, dtype=torch.float64).contiguous()
+            nan = bool(torch.isnan(sd).any())
+        else:
+            sh = np.ascontiguousarray(scores, dtype=np.float64)
+            nan = bool(np.isnan(sh).any())
+            sd = torch.from_numpy(sh).to(self.device)
+        if sd.dim() == 1:
+            sd = sd.reshape(1, -1)
+        if torch.is_tensor(y_true):
+            binary = y_true.dtype == torch.bool or bool(((y_true == 0) | (y_true == 1)).all())
+            ld = (y_true != 0).to(device=self.device, dtype=torch.uint8).contiguous().reshape(-1)
+        else:
+            yt = np.asarray(y_true)
+            binary = yt.dtype == bool or bool(np.isin(yt, (0, 1)).all())
+            ld = torch.from_numpy(np.ascontiguousarray(yt != 0).reshape(-1).view(np.uint8)).to(self.device)
+        if sd.dim() != 2 or not 1 <= sd.shape[0] <= self.DELONG_MAX_K:
+            raise ValueError(f'delong: scores are [k, n] with 1 <= k <= {self.DELONG_MAX_K}, not {tuple(sd.shape)}')
+        k, n = int(sd.shape[0]), int(sd.shape[1])
+        if n == 0 or ld.numel() != n or n > self.DELONG_MAX_ROWS:
+            raise ValueError(f'delong: empty input, length mismatch or more than 2^25 rows ({n} scores, {ld.numel()} labels)')
+        if nan:
+            raise ValueError('delong: a score is NaN')
+        if not binary:
+            raise ValueError('delong: labels must be 0/1')
+        m = int(ld.sum())
+        if m == 0 or m == n:
+            raise ValueError('delong: only one class present')
+        need = int(self._lib.bq_delong_workspace_bytes(k, n))
+        scratch = self._scratch('delong', need, scratch)
+        assert scratch.is_cuda and scratch.numel() >= need
+        out = torch.empty(k + k * k + 2, dtype=torch.float64, device=self.device)
+        V = torch.empty((k, n), dtype=torch.float64, device=self.device) if components else None
+        self._check(self._lib.bq_delong(self._ctx, _ptr(sd), _ptr(ld), k, n, _ptr(scratch), scratch.numel(), _ptr(out),
+                                        _ptr(V), self._stream()))
+        o = out.cpu().numpy()
+        res = {'auc': o[:k].copy(), 'cov': o[k:k + k * k].reshape(k, k).copy(), 'n_pos': int(o[k + k * k]), 'n_neg': int(o[k + k * k + 1])}
+        if components:
+            res['V'] = V.cpu().numpy()
         return res
 
     def debug_activation(self, name, staged, shape_hwc, true_scale=True):

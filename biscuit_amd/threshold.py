@@ -52,7 +52,8 @@ def use_device(engine, min_rows=100_000, calibration_min_rows=None):
     value; ``tests/test_gpu_parity.py`` checks it against this module's scikit-learn path).  ``None``
     switches back to the host.  The cohort-wide tile table is 1.6 M rows at BASELINE config 3.
     The calibration data (``plot_uncertainty``, ``calibration.py``) of a table with at least ``calibration_min_rows`` rows goes
-    to ``engine.uq_kde`` / ``engine.uq_loess``; by default the smaller of ``min_rows`` and ``calibration.DEFAULT_MIN_ROWS``."""
+    to ``engine.uq_kde`` / ``engine.uq_loess``; by default the smaller of ``min_rows`` and ``calibration.DEFAULT_MIN_ROWS``.
+    DeLong's covariance (``metrics.py``) of a table with at least ``metrics.DEFAULT_MIN_ROWS`` rows goes to ``engine.delong``."""
     from . import calibration
     _DEVICE['engine'] = engine
     _DEVICE['min_rows'] = int(min_rows)

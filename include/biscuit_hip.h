@@ -588,6 +588,26 @@ size_t bq_uq_loess_workspace_bytes(int64_t n, int grid);
 int bq_uq_loess(bq_ctx* ctx, const double* d_x, const uint8_t* d_correct, int64_t n, int grid, double span, double* d_out, void* d_ws,
                 size_t ws_bytes, bq_stream_t stream);
 
+/* DeLong's covariance of the AUROCs of k classifiers scored on the same n rows (kernels_delong.hip; DESIGN.md section 7
+ * "Prediction metrics"; biscuit/delong.py): d_scores float64 [k][n] (no NaN: the caller checks; +-inf and both zeros are
+ * ordinary values, the zeros equal), d_label uint8 [n] (non-zero = positive; both classes present: the caller checks), in any
+ * order; 1 <= k <= 8, 1 <= n <= 2^25 (the midrank sums stay exact integers below 2^53).
+ *
+ * d_out float64 [k + k k + 2] = auc [k], S [k][k], m, n0 (the positives and the negatives).  For a positive row V = (negatives
+ * below + tied negatives / 2) / n0, for a negative row V = 1 - (positives below + tied positives / 2) / m; auc = (sum of the
+ * positives' midranks) / m / n0 - ((m + 1) / 2) / n0; both equal the reference's values bit for bit.  S = cov(V | positive) / m +
+ * cov(V | negative) / n0 with the unbiased covariance (NaN entries where a class has one row), summed in chunks of
+ * bq_delong_chunk_rows(n) rows and the chunks in order, without floating-point atomics: the same bits every call.  d_V: NULL, or
+ * float64 [k][n] that receives V in row order.
+ *
+ * d_ws: bq_delong_workspace_bytes(k, n) bytes (0 for arguments the call refuses), 256-byte aligned, caller-owned, contents
+ * unspecified on entry; BQ_ERR_WORKSPACE below that.  Allocates nothing and is enqueued on `stream` without a host
+ * synchronisation; a bad argument is BQ_ERR_ARG with nothing enqueued. */
+size_t bq_delong_workspace_bytes(int k, int64_t n);
+int64_t bq_delong_chunk_rows(int64_t n);
+int bq_delong(bq_ctx* ctx, const double* d_scores, const uint8_t* d_label, int k, int64_t n, void* d_ws, size_t ws_bytes, double* d_out,
+              double* d_V, bq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
