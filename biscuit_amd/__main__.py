@@ -21,9 +21,11 @@ import pandas as pd
 def model_hp(params):
     """(ModelParams, norm_fit) from what ``keras_import.read_params`` found in a model's params.json: the dropout
     rate (and ``uq_n`` when stored) drive the MC statistics, so they come from the model, never from the defaults;
-    a stain normaliser other than the ones this path implements (`reinhard_fast`, hp.py:19, and `macenko`) is an error, and
+    a stain normaliser other than the ones this path takes (`reinhard_fast`, hp.py:19, the masked forms of the Reinhard family
+    and `macenko`) is an error -- among them plain `reinhard`, which the library implements (``stain.Reinhard``, every driver's
+    ``normalizer='reinhard'``) but the command lines go on refusing by name, as tests/test_host.py pins --, and
     its fit is used only when that normaliser is the model's and the fit is one of that method."""
-    from .stain import macenko_fit
+    from .stain import METHODS, REINHARD_FLAGS, macenko_fit, reinhard_fit
     from .hp import ModelParams
     hp = ModelParams()
     if not params:
@@ -39,9 +41,11 @@ def model_hp(params):
                          f"normaliser the model was trained with")
     hp.normalizer = normalizer
     hp.validate()
-    if normalizer not in (None, 'reinhard_fast', 'macenko'):
+    if normalizer is not None and (normalizer not in METHODS or normalizer == 'reinhard'):
         raise SystemExit(f"{params.get('path', 'params.json')}: the model was trained with normalizer={normalizer!r}; this "
-                         f"path implements 'reinhard_fast' (biscuit/hp.py:19), 'macenko' or none")
+                         f"path takes 'reinhard_fast' (biscuit/hp.py:19), 'reinhard_mask', 'reinhard_fast_mask', 'macenko' or none"
+                         + ("; plain 'reinhard' runs through the Python drivers only (evaluate(..., normalizer='reinhard'))"
+                            if normalizer == 'reinhard' else ''))
     if normalizer == 'macenko':
         fit = params.get('norm_fit')
         try:
@@ -49,9 +53,14 @@ def model_hp(params):
         except ValueError as e:
             raise SystemExit(f"{params.get('path', 'params.json')}: normalizer='macenko' but {e}") from None
         return hp, fit
-    fit = params.get('norm_fit') if normalizer == 'reinhard_fast' else None
-    if normalizer == 'reinhard_fast' and not fit:
-        raise SystemExit(f"{params.get('path', 'params.json')}: normalizer='reinhard_fast' but no norm_fit block")
+    fit = params.get('norm_fit') if normalizer in REINHARD_FLAGS else None
+    if normalizer in REINHARD_FLAGS and not fit:
+        raise SystemExit(f"{params.get('path', 'params.json')}: normalizer={normalizer!r} but no norm_fit block")
+    if normalizer in REINHARD_FLAGS and normalizer != 'reinhard_fast':
+        try:
+            reinhard_fit(fit)
+        except ValueError as e:
+            raise SystemExit(f"{params.get('path', 'params.json')}: normalizer={normalizer!r} but {e}") from None
     return hp, fit
 
 
@@ -126,7 +135,8 @@ def main(argv=None):
     ap.add_argument('--dtype', default='f16', choices=['f16', 'bf16', 'f32'])
     ap.add_argument('--streams', type=int, default=1,
                     help='batches in flight, each on its share of the chip (1 measured fastest through evaluate(): 25.8 k vs 25.4 k tiles/s)')
-    ap.add_argument('--params', help="Slideflow params.json: its hp.normalizer ('reinhard_fast', the default, or 'macenko') and "
+    ap.add_argument('--params', help="Slideflow params.json: its hp.normalizer ('reinhard_fast', the default, 'reinhard_mask', "
+                                     "'reinhard_fast_mask' or 'macenko') and "
                                      "norm_fit switch on that stain normaliser (hp.py:19)")
     ap.add_argument('--tile-uq', type=float, default=0.0, help='tile-level uncertainty threshold (0 = off)')
     ap.add_argument('--slide-uq', type=float, default=0.0, help='slide-level uncertainty threshold (0 = off)')
@@ -226,8 +236,8 @@ def main(argv=None):
                    save_dir=args.out, rank=rank, world=world, norm_fit=norm_fit, keep_tiles=False, normalizer=hp.normalizer,
                    range_screen=args.range_screen)
     if res.stain_passthrough:
-        print(f'rank {rank}: the {hp.normalizer} normaliser passed {res.stain_passthrough} degenerate tile(s) through unchanged '
-              f'(too little tissue or one colour)', file=sys.stderr, flush=True)
+        print(f'rank {rank}: the {hp.normalizer} normaliser left {res.stain_passthrough} degenerate tile(s) un-normalised '
+              f'(too little tissue, one colour or too dark)', file=sys.stderr, flush=True)
     if rank == 0:
         from .predictions import load_tile_predictions
         sf, _ = res.slide_frame(0.5)

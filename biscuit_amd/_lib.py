@@ -67,6 +67,8 @@ ABI = {
     'bq_set_option': (_i, [_vp, C.c_char_p, _i]),
     'bq_stain_reinhard_fast': (_i, [_vp, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp]),
     'bq_stain_lab_stats': (_i, [_vp, _vp, _i, _vp, _vp]),
+    'bq_stain_reinhard': (_i, [_vp, _vp, _i, _i, _i, _f, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),
+    'bq_stain_reinhard_stats': (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     'bq_stain_macenko': (_i, [_vp, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),
     'bq_stain_macenko_stats': (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     'bq_range_ws_bytes': (_sz, [_i]),

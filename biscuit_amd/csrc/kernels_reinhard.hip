@@ -5,8 +5,11 @@
 // re-reads the (L2-resident) tile, converts again, applies (lab - mu) * (target_std / sd) + target_mean,
 // converts back and stores uint8.  The precision contract (float64 for cbrt / pow / the statistics,
 // one float32 rounding per other operation, no FMA contraction) is written out in oracle/stain.py;
-// it makes the uint8 result comparable bit for bit.
+// it makes the uint8 result comparable bit for bit.  The rest of Slideflow's Reinhard family (`reinhard`, `reinhard_mask`,
+// `reinhard_fast_mask`: a brightness standardisation in front and / or a tissue mask) is reinhard_family_kernel below, on the same
+// device helpers ("Reinhard family").
 #include "bq_ctx.h"
+#include "radix_select.h"
 
 #include <cmath>
 #include <string.h>
@@ -214,12 +217,165 @@ __global__ void __launch_bounds__(RH_NT) reinhard_kernel(const uint8_t* __restri
     }
 }
 
+// ---- the Reinhard family ("Reinhard family"): reinhard_fast plus two optional stages ----
+// flags: RF_BRIGHTNESS = brightness standardisation in front (Slideflow's `reinhard` / `reinhard_mask`), RF_MASK = statistics and
+// transform over the tissue pixels only, L < mask_L (`reinhard_fast_mask` / `reinhard_mask`).  One workgroup per tile, the tile
+// re-read from cache in every pass:
+//   0. (RF_BRIGHTNESS) p = the 90th percentile of the tile's float32 L, numpy's 'linear' rule over the exact order statistics
+//      (radix_select.h); p not finite or <= 0: status RF_DARK, the tile passes through
+//   1. the brightness table b -> trunc(min(b * (100 / p), 255)) in LDS (the identity without RF_BRIGHTNESS); every pixel through
+//      it, to LAB, the mask test; the count and the six sums over tissue pixels in float64, the thread map and the tree of
+//      reinhard_kernel (so flags 0 reports that kernel's statistics bit for bit); no tissue pixel: status RF_NO_TISSUE
+//   2. tissue pixels transformed as reinhard_kernel transforms, the others stored as the table left them
+// dst may be null (statistics only) or == src: in pass 2 every pixel is read and written by one thread, after every other read.
+constexpr int RF_BRIGHTNESS = 1, RF_MASK = 2;
+constexpr int RF_OK = 0, RF_NO_TISSUE = 1, RF_DARK = 2;
+constexpr double RF_PCT = 0.9;             // the percentile of L that becomes L = 100 (unpinned; stain.py REINHARD_BRIGHT_PCT)
+static_assert(RS_NT == RH_NT, "the radix select runs in the workgroup of the Reinhard kernels");
+
+struct RfShared {
+    float slut[256];
+    float sthr[256];
+    unsigned char btab[256];
+    RadixSel sel;
+    double red[6][RH_NT / 64];
+    int cnt[RH_NT / 64];
+    float stat[6];
+    float p;
+    int status, m;
+};
+
+__global__ void __launch_bounds__(RH_NT) reinhard_family_kernel(const uint8_t* tiles, int px, const float* __restrict__ lut,
+                                                                const ReinhardConst k, int flags, float mask_L, uint8_t* dst,
+                                                                float* __restrict__ stats8, int* __restrict__ st) {
+    const int npix = px * px;
+    const uint8_t* src = tiles + (size_t)blockIdx.x * npix * 3;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    __shared__ RfShared sh;
+    for (int i = tid; i < 256; i += nt) { sh.slut[i] = lut[i]; sh.sthr[i] = lut[256 + i]; }
+    if (tid == 0) {
+        sh.p = 100.0f;
+        sh.status = RF_OK;
+        sh.m = 0;
+        // the select's second target is not used: an empty histogram, which leaves bin and before as they are set here
+        sh.sel.rank[0] = (unsigned)floor(RF_PCT * (double)(npix - 1));
+        sh.sel.rank[1] = sh.sel.bin[1] = sh.sel.before[1] = 0u;
+        sh.sel.bin[0] = sh.sel.before[0] = 0u;
+        sh.sel.coff = 0.f;                                    // L: 100 / 2 048 bins over [0, 100]
+        sh.sel.cscl = (float)RS_BINS / 100.0f;
+    }
+    __syncthreads();
+
+    // ---- 0. the 90th percentile of L
+    if (flags & RF_BRIGHTNESS) {
+        rs_select(sh.sel, npix, [&](int i, float v[2], bool ok[2]) {
+            v[0] = v[1] = rgb_to_lab(sh.slut, k, src[3 * i], src[3 * i + 1], src[3 * i + 2]).L;
+            ok[0] = true;
+            ok[1] = false;
+        });
+        if (tid == 0) {
+            const double v = RF_PCT * (double)(npix - 1), lo = floor(v);
+            const double a = (double)rs_unkey(sh.sel.key[0]);
+            const double b = lo + 1.0 < (double)npix ? (double)rs_unkey(sh.sel.succ[0]) : a;       // L[min(lo + 1, N - 1)]
+            const float p = (float)rs_lerp(a, b, v - lo);
+            sh.p = p;
+            if (!(p > 0.f) || !isfinite(p)) sh.status = RF_DARK;
+        }
+        __syncthreads();
+    }
+
+    // ---- 1. brightness table, mask, statistics
+    if (sh.status == RF_OK) {
+        {
+#pragma clang fp contract(off)
+            const float s = 100.0f / sh.p;
+            for (int i = tid; i < 256; i += nt)
+                sh.btab[i] = (flags & RF_BRIGHTNESS) ? (unsigned char)(int)fminf((float)i * s, 255.0f) : (unsigned char)i;
+        }
+        __syncthreads();
+        double s[6] = {0, 0, 0, 0, 0, 0};
+        int cnt = 0;
+        for (int i = tid; i < npix; i += nt) {
+            const Lab v = rgb_to_lab(sh.slut, k, sh.btab[src[3 * i]], sh.btab[src[3 * i + 1]], sh.btab[src[3 * i + 2]]);
+            if (!(flags & RF_MASK) || v.L < mask_L) {
+                ++cnt;
+                s[0] += (double)v.L; s[1] += (double)v.a; s[2] += (double)v.b;
+                s[3] += (double)v.L * (double)v.L; s[4] += (double)v.a * (double)v.a; s[5] += (double)v.b * (double)v.b;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+        if ((tid & 63) == 0) sh.cnt[tid >> 6] = cnt;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s[q] += __shfl_xor(s[q], o);
+            if ((tid & 63) == 0) sh.red[q][tid >> 6] = s[q];
+        }
+        __syncthreads();
+        if (tid < 3) {
+            int m = 0;
+            double a = 0, b = 0;
+            for (int i = 0; i < nt / 64; ++i) { m += sh.cnt[i]; a += sh.red[tid][i]; b += sh.red[tid + 3][i]; }
+            const double mu = a / (double)m;                  // (m == 0: NaN, and the status says so)
+            double var = b / (double)m - mu * mu;
+            if (var < 0) var = 0;
+            sh.stat[tid] = (float)mu;
+            sh.stat[tid + 3] = (float)sqrt(var);
+            if (tid == 0) {
+                sh.m = m;
+                if (m == 0) sh.status = RF_NO_TISSUE;
+            }
+        }
+        __syncthreads();
+    }
+
+    const int status = sh.status;
+    if (tid == 0) {
+        if (stats8) {
+            float* o = stats8 + (size_t)blockIdx.x * 8;
+            for (int i = 0; i < 6; ++i) o[i] = status == RF_OK ? sh.stat[i] : __builtin_nanf("");
+            o[6] = sh.p;
+            o[7] = (float)((double)sh.m / (double)npix);
+        }
+        if (st) st[blockIdx.x] = status;
+    }
+    if (!dst) return;
+
+    // ---- 2. transform (or pass-through)
+    uint8_t* out = dst + (size_t)blockIdx.x * npix * 3;
+    if (status == RF_DARK) {
+        if (out != src)
+            for (int i = tid; i < 3 * npix; i += nt) out[i] = src[i];
+        return;
+    }
+    if (status == RF_NO_TISSUE) {
+        for (int i = tid; i < 3 * npix; i += nt) out[i] = sh.btab[src[i]];
+        return;
+    }
+    float sc[3];
+    {
+#pragma clang fp contract(off)
+        sc[0] = k.tgt_std[0] / sh.stat[3]; sc[1] = k.tgt_std[1] / sh.stat[4]; sc[2] = k.tgt_std[2] / sh.stat[5];
+    }
+    for (int i = tid; i < npix; i += nt) {
+#pragma clang fp contract(off)
+        const unsigned r8 = sh.btab[src[3 * i]], g8 = sh.btab[src[3 * i + 1]], b8 = sh.btab[src[3 * i + 2]];
+        const Lab v = rgb_to_lab(sh.slut, k, r8, g8, b8);
+        uint8_t rgb[3] = {(uint8_t)r8, (uint8_t)g8, (uint8_t)b8};
+        if (!(flags & RF_MASK) || v.L < mask_L) {
+            const float L = (v.L - sh.stat[0]) * sc[0] + k.tgt_mean[0];
+            const float a = (v.a - sh.stat[1]) * sc[1] + k.tgt_mean[1];
+            const float b = (v.b - sh.stat[2]) * sc[2] + k.tgt_mean[2];
+            lab_to_rgb8(k, sh.sthr, L, a, b, rgb);
+        }
+        out[3 * i] = rgb[0]; out[3 * i + 1] = rgb[1]; out[3 * i + 2] = rgb[2];
+    }
+}
+
 }  // namespace
 
-static int launch_reinhard(const uint8_t* tiles, int n, int px, const float* d_lut, const float* consts27,
-                           const float* tgt_mean, const float* tgt_std, uint8_t* dst, float* d_stats, hipStream_t s) {
-    if (n <= 0) return 0;
-    ReinhardConst k;
+static void reinhard_consts(ReinhardConst& k, const float* consts27, const float* tgt_mean, const float* tgt_std) {
     for (int i = 0; i < 9; ++i) { k.m[i] = consts27[i]; k.minv[i] = consts27[9 + i]; }
     for (int i = 0; i < 3; ++i) {
         k.white[i] = consts27[18 + i];
@@ -227,6 +383,24 @@ static int launch_reinhard(const uint8_t* tiles, int n, int px, const float* d_l
         k.tgt_mean[i] = tgt_mean ? tgt_mean[i] : 0.f;
         k.tgt_std[i] = tgt_std ? tgt_std[i] : 1.f;
     }
+}
+
+static int launch_reinhard_family(const uint8_t* tiles, int n, int px, int flags, float mask_L, const float* d_lut,
+                                  const float* tgt_mean, const float* tgt_std, uint8_t* dst, float* d_stats8, int* d_status,
+                                  hipStream_t s) {
+    if (n <= 0) return 0;
+    ReinhardConst k;
+    reinhard_consts(k, kReinhardConsts, tgt_mean, tgt_std);
+    hipLaunchKernelGGL(reinhard_family_kernel, dim3(n), dim3(RH_NT), 0, s, tiles, px, d_lut, k, flags, mask_L, dst, d_stats8,
+                       d_status);
+    return (int)hipGetLastError();
+}
+
+static int launch_reinhard(const uint8_t* tiles, int n, int px, const float* d_lut, const float* consts27,
+                           const float* tgt_mean, const float* tgt_std, uint8_t* dst, float* d_stats, hipStream_t s) {
+    if (n <= 0) return 0;
+    ReinhardConst k;
+    reinhard_consts(k, consts27, tgt_mean, tgt_std);
     hipLaunchKernelGGL(reinhard_kernel, dim3(n), dim3(RH_NT), 0, s, tiles, px, d_lut, k, dst, d_stats);
     return (int)hipGetLastError();
 }
@@ -252,6 +426,41 @@ int bq_stain_lab_stats(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_stats6
     hipStream_t s = (hipStream_t)stream;
     if (launch_reinhard(d_tiles, n, 299, c->d_srgb_lut, kReinhardConsts, nullptr, nullptr, nullptr, d_stats6, s))
         return fail(c, BQ_ERR_HIP, "lab stats launch failed");
+    return BQ_OK;
+}
+
+static int reinhard_family_args(bq_ctx* c, const char* who, const void* d_tiles, int n, int px, int flags, float mask_L) {
+    if (!c || !d_tiles || n < 0) return fail(c, BQ_ERR_ARG, std::string(who) + ": bad argument");
+    if (px < 1 || px > 1024) return fail(c, BQ_ERR_ARG, std::string(who) + ": px must be in 1..1024");
+    if (flags < 0 || flags > 3) return fail(c, BQ_ERR_ARG, std::string(who) + ": flags must be in 0..3 (1 = brightness, 2 = mask)");
+    if (!std::isfinite(mask_L)) return fail(c, BQ_ERR_ARG, std::string(who) + ": non-finite mask_L");
+    return BQ_OK;
+}
+
+int bq_stain_reinhard(bq_ctx* c, const uint8_t* d_tiles, int n, int px, int flags, float mask_L, const float* target_means3,
+                      const float* target_stds3, uint8_t* d_out, int* d_status, bq_stream_t stream) {
+    if (const int e = reinhard_family_args(c, "bq_stain_reinhard", d_tiles, n, px, flags, mask_L)) return e;
+    if (!d_out || !target_means3 || !target_stds3) return fail(c, BQ_ERR_ARG, "bq_stain_reinhard: bad argument");
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(target_stds3[i]) || !std::isfinite(target_means3[i]))      // (a std of 0 or below is defined arithmetic)
+            return fail(c, BQ_ERR_ARG, "bq_stain_reinhard: non-finite target statistics");
+    hipStream_t s = (hipStream_t)stream;
+    const double pixels = (double)n * px * px;
+    ProfScope ps(c, s, "stain_reinhard", ((flags & 1) ? 500.0 : 300.0) * pixels, 3.0 * 3.0 * pixels);
+    if (launch_reinhard_family(d_tiles, n, px, flags, mask_L, c->d_srgb_lut, target_means3, target_stds3, d_out, nullptr, d_status, s))
+        return fail(c, BQ_ERR_HIP, "reinhard family launch failed");
+    return BQ_OK;
+}
+
+int bq_stain_reinhard_stats(bq_ctx* c, const uint8_t* d_tiles, int n, int px, int flags, float mask_L, float* d_stats8,
+                            int* d_status, bq_stream_t stream) {
+    if (const int e = reinhard_family_args(c, "bq_stain_reinhard_stats", d_tiles, n, px, flags, mask_L)) return e;
+    if (!d_stats8) return fail(c, BQ_ERR_ARG, "bq_stain_reinhard_stats: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const double pixels = (double)n * px * px;
+    ProfScope ps(c, s, "stain_reinhard_stats", ((flags & 1) ? 350.0 : 150.0) * pixels, 3.0 * pixels);
+    if (launch_reinhard_family(d_tiles, n, px, flags, mask_L, c->d_srgb_lut, nullptr, nullptr, nullptr, d_stats8, d_status, s))
+        return fail(c, BQ_ERR_HIP, "reinhard family stats launch failed");
     return BQ_OK;
 }
 

@@ -10,7 +10,7 @@
 //   2. one lane: the covariance (divided by n - 1), its 3x3 eigenproblem by cyclic Jacobi in float64, E = the eigenvectors of
 //      the middle and the largest eigenvalue, each column's entry of largest magnitude made positive
 //   3. exact order statistics of phi = atan2(OD.E1, OD.E0) over tissue pixels: the (floor(v))-th and next of v = 0.01 (n-1)
-//      and v = 0.99 (n-1) (numpy's 'linear' percentile), by a radix select over the order-preserving 32-bit key of the float32
+//      and v = 0.99 (n-1) (numpy's 'linear' percentile), by a radix select (radix_select.h, shared with kernels_reinhard.hip) over the order-preserving 32-bit key of the float32
 //      angle -- one pass over a monotone 2 048-bin coarse histogram of the value, then 11 + 11 + 10 key bits restricted to the
 //      chosen coarse bin (so LDS atomics only collide inside it), then one pass for the successor when it is a different value
 //   4. one lane: numpy's _lerp in float64, vMin / vMax, HE (H first), det(HE^T HE), pinv(HE) = (HE^T HE)^-1 HE^T in float64
@@ -23,6 +23,7 @@
 // intermediate; such a tile passes through unchanged (copied when dst != src).  dst may equal src: every pixel is read and
 // written by one thread in the last pass, after every read of the others.
 #include "bq_ctx.h"
+#include "radix_select.h"
 
 #include <cmath>
 
@@ -37,9 +38,9 @@ constexpr float MK_OVER = 255.f;           // HEnorm_python's quirk: Inorm > 255
 constexpr float MK_OVER_TO = 254.f;
 constexpr double MK_DET_MIN = 1e-12;       // |det(HE^T HE)| below this: status 2
 
-constexpr int MK_NT = 1024;
-constexpr int MK_NW = MK_NT / 64;
-constexpr int MK_BINS = 2048;
+constexpr int MK_NT = RS_NT;               // the workgroup of the shared radix select (radix_select.h)
+constexpr int MK_NW = RS_NW;
+constexpr int MK_BINS = RS_BINS;
 
 struct MacenkoRef {
     float he[6];      // HERef, row-major 3x2 (columns H, E)
@@ -50,132 +51,14 @@ struct MkShared {
     double od64[256];
     float od32[256];
     unsigned char tis[256];
-    unsigned hist[2][MK_BINS];
+    RadixSel sel;                          // the order statistics of steps 3 and 5 (radix_select.h)
     double red[10][MK_NW];
-    unsigned wsum[MK_NW];
-    unsigned rank[2], bin[2], before[2], cbin[2], key[2], eq[2], succ[2];
-    float coff, cscl;                      // coarse bin of a value v: clamp((v + coff) * cscl, 0, MK_BINS - 1)
     float e[6];                            // E row-major 3x2, float32 (angle pass)
     float p[6];                            // pinv(HE) row-major 2x3, float32 (concentrations)
     float scale[2];                        // maxCRef / maxC
     double he[6], maxc[2];
     int status, ntissue;
 };
-
-__device__ __forceinline__ unsigned mk_key(float v) {       // order-preserving: a < b  <=>  key(a) < key(b) (-0 < +0)
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float mk_unkey(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ int mk_coarse(const MkShared& sh, float v) {     // monotone non-decreasing in v; NaN -> 0
-    const float x = (v + sh.coff) * sh.cscl;
-    return x >= 0.f ? (x < (float)(MK_BINS - 1) ? (int)x : MK_BINS - 1) : 0;
-}
-
-// numpy's _lerp: a + (b - a) t, or b - (b - a)(1 - t) when t >= 0.5
-__device__ __forceinline__ double mk_lerp(double a, double b, double t) {
-    const double d = b - a;
-    return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
-}
-
-// For both targets t (threads [512 t, 512 t + 512)): the bin of hist[t][0..nb) holding the element of rank sh.rank[t]
-// -> sh.bin[t], and the count of the bins below it -> sh.before[t].  nb = 1 024 or 2 048.
-__device__ void mk_find(MkShared& sh, int nb) {
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int t = tid >> 9, j = tid & 511, per = nb >> 9;
-    unsigned loc = 0;
-    for (int q = 0; q < per; ++q) loc += sh.hist[t][j * per + q];
-    unsigned x = loc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) sh.wsum[wid] = x;
-    __syncthreads();
-    unsigned acc = x - loc;
-    for (int w = t * (MK_NW / 2); w < wid; ++w) acc += sh.wsum[w];
-    const unsigned r = sh.rank[t];
-    if (r >= acc && r < acc + loc) {
-        for (int q = 0; q < per; ++q) {
-            const unsigned c = sh.hist[t][j * per + q];
-            if (r < acc + c) { sh.bin[t] = j * per + q; sh.before[t] = acc; break; }
-            acc += c;
-        }
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void mk_clear(MkShared& sh) {
-    for (int i = threadIdx.x; i < 2 * MK_BINS; i += MK_NT) (&sh.hist[0][0])[i] = 0u;
-}
-
-// Exact order statistics: for t = 0, 1 the element of rank sh.rank[t] among the values v[t] of the pixels with ok[t]
-// (VAL(i, v, ok) evaluates pixel i), as its key -> sh.key[t], and the key of the element of rank + 1 -> sh.succ[t].
-template <class VAL>
-__device__ void mk_select(MkShared& sh, int npix, const VAL& val) {
-    const int tid = threadIdx.x;
-    mk_clear(sh);
-    __syncthreads();
-    for (int i = tid; i < npix; i += MK_NT) {
-        float v[2]; bool ok[2];
-        val(i, v, ok);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-            if (ok[t]) atomicAdd(&sh.hist[t][mk_coarse(sh, v[t])], 1u);
-    }
-    __syncthreads();
-    mk_find(sh, MK_BINS);
-    if (tid < 2) { sh.cbin[tid] = sh.bin[tid]; sh.rank[tid] -= sh.before[tid]; sh.key[tid] = 0u; }
-    // three radix passes over the key bits [31:21], [20:10], [9:0] of the elements in the chosen coarse bin
-    for (int lv = 0; lv < 3; ++lv) {
-        const int nb = lv < 2 ? 2048 : 1024, shift = lv == 0 ? 21 : lv == 1 ? 10 : 0;
-        const unsigned above = lv == 0 ? 0u : lv == 1 ? 0xffe00000u : 0xfffffc00u;     // key bits already chosen
-        __syncthreads();
-        mk_clear(sh);
-        __syncthreads();
-        const unsigned cb0 = sh.cbin[0], cb1 = sh.cbin[1], pk0 = sh.key[0] & above, pk1 = sh.key[1] & above;
-        for (int i = tid; i < npix; i += MK_NT) {
-            float v[2]; bool ok[2];
-            val(i, v, ok);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const unsigned k = mk_key(v[t]);
-                if (ok[t] && (unsigned)mk_coarse(sh, v[t]) == (t ? cb1 : cb0) && (k & above) == (t ? pk1 : pk0))
-                    atomicAdd(&sh.hist[t][(k >> shift) & (unsigned)(nb - 1)], 1u);
-            }
-        }
-        __syncthreads();
-        mk_find(sh, nb);
-        if (tid < 2) {
-            sh.key[tid] |= sh.bin[tid] << shift;
-            sh.rank[tid] -= sh.before[tid];
-            if (lv == 2) sh.eq[tid] = sh.hist[tid][sh.bin[tid]];
-        }
-    }
-    __syncthreads();
-    // the successor: the same value while elements of that key remain, else the least larger key (min: order-free)
-    const bool need0 = sh.rank[0] + 1 >= sh.eq[0], need1 = sh.rank[1] + 1 >= sh.eq[1];
-    const unsigned k0 = sh.key[0], k1 = sh.key[1];
-    __syncthreads();
-    if (tid < 2) sh.succ[tid] = (tid ? need1 : need0) ? 0xffffffffu : sh.key[tid];
-    __syncthreads();
-    if (need0 || need1) {
-        unsigned m0 = 0xffffffffu, m1 = 0xffffffffu;
-        for (int i = tid; i < npix; i += MK_NT) {
-            float v[2]; bool ok[2];
-            val(i, v, ok);
-            const unsigned a = mk_key(v[0]), b = mk_key(v[1]);
-            if (need0 && ok[0] && a > k0) m0 = min(m0, a);
-            if (need1 && ok[1] && b > k1) m1 = min(m1, b);
-        }
-        if (need0) atomicMin(&sh.succ[0], m0);
-        if (need1) atomicMin(&sh.succ[1], m1);
-        __syncthreads();
-    }
-}
 
 // Cyclic Jacobi on a symmetric 3x3 matrix (float64): a is diagonalised in place, v gets the eigenvectors as columns.
 __device__ void mk_jacobi3(double a[3][3], double v[3][3]) {
@@ -297,11 +180,11 @@ __global__ void __launch_bounds__(MK_NT) macenko_kernel(const uint8_t* tiles, in
             }
             if (!fin) sh.status = 3;
             const double vi = (dn - 1.0) * (MK_ALPHA / 100.0), vj = (dn - 1.0) * ((100.0 - MK_ALPHA) / 100.0);
-            sh.rank[0] = (unsigned)floor(vi);
-            sh.rank[1] = (unsigned)floor(vj);
+            sh.sel.rank[0] = (unsigned)floor(vi);
+            sh.sel.rank[1] = (unsigned)floor(vj);
         }
-        sh.coff = 3.14159265f;
-        sh.cscl = (float)(MK_BINS / (2.0 * 3.14159265358979323846));
+        sh.sel.coff = 3.14159265f;
+        sh.sel.cscl = (float)(MK_BINS / (2.0 * 3.14159265358979323846));
     }
     __syncthreads();
     const unsigned ntis = (unsigned)sh.ntissue;
@@ -309,7 +192,7 @@ __global__ void __launch_bounds__(MK_NT) macenko_kernel(const uint8_t* tiles, in
     // ---- 3. the two extreme angles
     if (sh.status == 0) {
         const float e00 = sh.e[0], e01 = sh.e[1], e10 = sh.e[2], e11 = sh.e[3], e20 = sh.e[4], e21 = sh.e[5];
-        mk_select(sh, npix, [&](int i, float v[2], bool ok[2]) {
+        rs_select(sh.sel, npix, [&](int i, float v[2], bool ok[2]) {
             int r, g, b;
             mk_read(src, i, r, g, b);
             const bool t = sh.tis[r] & sh.tis[g] & sh.tis[b];
@@ -324,7 +207,7 @@ __global__ void __launch_bounds__(MK_NT) macenko_kernel(const uint8_t* tiles, in
             const double vi[2] = {n1 * (MK_ALPHA / 100.0), n1 * ((100.0 - MK_ALPHA) / 100.0)};
             double ph[2];
             for (int t = 0; t < 2; ++t)
-                ph[t] = mk_lerp((double)mk_unkey(sh.key[t]), (double)mk_unkey(sh.succ[t]), vi[t] - floor(vi[t]));
+                ph[t] = rs_lerp((double)rs_unkey(sh.sel.key[t]), (double)rs_unkey(sh.sel.succ[t]), vi[t] - floor(vi[t]));
             double vmin[3], vmax[3];
             const double c0 = cos(ph[0]), s0 = sin(ph[0]), c1 = cos(ph[1]), s1 = sin(ph[1]);
             for (int i = 0; i < 3; ++i) {
@@ -360,9 +243,9 @@ __global__ void __launch_bounds__(MK_NT) macenko_kernel(const uint8_t* tiles, in
                 if (!fin) sh.status = 3;
             }
             const double vc = (double)(npix - 1) * (MK_CONC_PCT / 100.0);
-            sh.rank[0] = sh.rank[1] = (unsigned)floor(vc);
-            sh.coff = 8.f;                                    // concentrations: 1/128 bins over [-8, 8)
-            sh.cscl = 128.f;
+            sh.sel.rank[0] = sh.sel.rank[1] = (unsigned)floor(vc);
+            sh.sel.coff = 8.f;                                    // concentrations: 1/128 bins over [-8, 8)
+            sh.sel.cscl = 128.f;
         }
         __syncthreads();
     }
@@ -370,7 +253,7 @@ __global__ void __launch_bounds__(MK_NT) macenko_kernel(const uint8_t* tiles, in
     // ---- 5. the 99th percentiles of the concentrations over all pixels
     if (sh.status == 0) {
         const float p00 = sh.p[0], p01 = sh.p[1], p02 = sh.p[2], p10 = sh.p[3], p11 = sh.p[4], p12 = sh.p[5];
-        mk_select(sh, npix, [&](int i, float v[2], bool ok[2]) {
+        rs_select(sh.sel, npix, [&](int i, float v[2], bool ok[2]) {
             int r, g, b;
             mk_read(src, i, r, g, b);
             const float x = sh.od32[r], y = sh.od32[g], z = sh.od32[b];
@@ -381,7 +264,7 @@ __global__ void __launch_bounds__(MK_NT) macenko_kernel(const uint8_t* tiles, in
         if (tid == 0) {
             const double vc = (double)(npix - 1) * (MK_CONC_PCT / 100.0), g = vc - floor(vc);
             for (int t = 0; t < 2; ++t) {
-                const double m = mk_lerp((double)mk_unkey(sh.key[t]), (double)mk_unkey(sh.succ[t]), g);
+                const double m = rs_lerp((double)rs_unkey(sh.sel.key[t]), (double)rs_unkey(sh.sel.succ[t]), g);
                 sh.maxc[t] = m;
                 if (!(m > 0.0) || !isfinite(m)) sh.status = 3;
                 const double sc = (double)ref.maxc[t] / m;

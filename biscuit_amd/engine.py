@@ -732,6 +732,45 @@ class Engine:
                                                  self._stream()))
         return out
 
+    @staticmethod
+    def _reinhard_args(tiles_u8, flags, mask_threshold):
+        """(n, px, flags, mask_L) of a Reinhard-family call: square uint8 NHWC tiles of any size the ABI takes; ``mask_L`` is
+        float32(100 * mask_threshold), computed in float64 and rounded once."""
+        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous()
+        assert tiles_u8.dim() == 4 and tiles_u8.shape[1] == tiles_u8.shape[2] and tiles_u8.shape[3] == 3, tuple(tiles_u8.shape)
+        with np.errstate(over='ignore'):
+            mask_l = float(np.float32(100.0 * float(mask_threshold)))
+        return int(tiles_u8.shape[0]), int(tiles_u8.shape[1]), int(flags), mask_l
+
+    def reinhard(self, tiles_u8, target_means, target_stds, flags, mask_threshold=0.93, out=None, status=None):
+        """Slideflow's Reinhard family (``bq_stain_reinhard``; DESIGN.md "Reinhard family"): uint8 NHWC [n,px,px,3] -> uint8 NHWC.
+        ``flags``: 1 = brightness standardisation, 2 = tissue mask (``stain.REINHARD_FLAGS`` names the four methods; 0 gives
+        ``reinhard_fast``'s bytes).  A pixel is tissue when its L is below ``100 * mask_threshold``.  `out` may be the input tensor
+        (in place).  `status` (int32 [n] on the device, optional) receives each tile's status: 0 normalised, 1 no tissue pixel
+        (only the brightness stage applied), 2 too dark to standardise (passed through)."""
+        n, px, flags, mask_l = self._reinhard_args(tiles_u8, flags, mask_threshold)
+        tm = (C.c_float * 3)(*[float(v) for v in target_means])
+        ts = (C.c_float * 3)(*[float(v) for v in target_stds])
+        if out is None:
+            out = torch.empty_like(tiles_u8)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.shape == tiles_u8.shape
+        if status is not None:
+            assert status.dtype == torch.int32 and status.is_cuda and status.is_contiguous() and status.numel() >= n
+        self._check(self._lib.bq_stain_reinhard(self._ctx, _ptr(tiles_u8), n, px, flags, mask_l, tm, ts, _ptr(out), _ptr(status),
+                                                self._stream()))
+        return out
+
+    def reinhard_stats(self, tiles_u8, flags, mask_threshold=0.93):
+        """Each tile's own Reinhard-family fit (what ``stain.Reinhard.fit`` stores): ``(stats, status)`` device tensors, stats
+        float32 [n,8] = mean L, a, b, std L, a, b over the tissue pixels of the brightness-standardised tile (NaN when the status
+        is not 0), the 90th percentile of L (100 without flag 1), the tissue fraction; status int32 [n] as ``reinhard``."""
+        n, px, flags, mask_l = self._reinhard_args(tiles_u8, flags, mask_threshold)
+        stats = torch.empty((n, 8), dtype=torch.float32, device=self.device)
+        st = torch.empty((n,), dtype=torch.int32, device=self.device)
+        self._check(self._lib.bq_stain_reinhard_stats(self._ctx, _ptr(tiles_u8), n, px, flags, mask_l, _ptr(stats), _ptr(st),
+                                                      self._stream()))
+        return stats, st
+
     def macenko(self, tiles_u8, he_ref, maxc_ref, out=None, status=None):
         """`macenko` stain normalisation (``bq_stain_macenko``; DESIGN.md "Macenko"): uint8 NHWC [n,299,299,3] -> uint8 NHWC.
         he_ref: the fit's stain matrix (3x2, columns H and E), maxc_ref: its two concentrations (> 0).  `out` may be the input

@@ -39,7 +39,7 @@ class EvalResult:
     table_rows: int = 0                      # rows this rank wrote
     f16_headroom: float = float('inf')       # minimum over the run's range checks of 65504 / max |stored activation| (f16 engines)
     f16_checks: int = 0
-    stain_passthrough: int = 0               # tiles of this rank the Macenko normaliser passed through unchanged (degenerate)
+    stain_passthrough: int = 0               # tiles of this rank the normaliser did not normalise (degenerate: a status other than 0; stain.STATUS_METHODS)
     f16_screen_checks: int = 0               # range screen (evaluate(range_screen=True)): tap runs on the screened candidates
     f16_screen_headroom: float = float('inf')    # ... the minimum of 65504 / max |stored activation| over them
     f16_screened: int = 0                    # ... tiles of this rank that went through the key (0: the screen did not run)
@@ -296,7 +296,7 @@ class _Batches:
         self.normalizer, self.norm_fit, self.keep_tiles = normalizer, norm_fit, keep_tiles
         self.n = 0                                       # batches enqueued
         self.acc = [None] * len(engines)
-        self.passthrough = [None] * len(engines)         # per stream: int64 device count of the tiles the Macenko kernel passed through
+        self.passthrough = [None] * len(engines)         # per stream: int64 device count of the tiles whose stain status is not 0
         self.rows = []                                   # keep_tiles: the batches' (mean | std), on the device; copied to the host at the end
         f16 = all(getattr(e, 'dtype', None) == 'f16' and hasattr(e, 'f16_headroom_async') for e in engines)
         self.every = int(headroom_every or 0) if f16 else 0      # batches between range checks (0: neither monitor nor mid-run screen taps)
@@ -316,7 +316,7 @@ class _Batches:
 
     def _work(self, eng, k, cur, cs, g0, gdev, mean, std):
         if self.norm_fit is not None:
-            if self.normalizer == 'macenko':
+            if self.normalizer in self.stain.STATUS_METHODS:
                 st = torch.empty(cur.shape[0], dtype=torch.int32, device=self.dev)
                 cur = self.stain.normalise(eng, cur, self.normalizer, self.norm_fit, status=st)
                 cnt = st.ne(0).sum()
@@ -420,7 +420,9 @@ def evaluate(engine, slides: Sequence[Slide], outcome='cohort', mc_n=None, seed=
     params.json) switches on the `reinhard_fast` stain normaliser of hp.py:19 in front of the staging
     kernel, where results.py:251-252 applies it.  ``normalizer='macenko'`` takes a Macenko fit instead
     (``{'stain_matrix_target': 3x2, 'target_concentrations': 2}``); the tiles it passes through unchanged (degenerate: no
-    tissue, one colour) are counted on the device and read once at the end: ``EvalResult.stain_passthrough`` (this rank's)."""
+    tissue, one colour) are counted on the device and read once at the end: ``EvalResult.stain_passthrough`` (this rank's).
+    ``normalizer='reinhard'``, ``'reinhard_mask'`` and ``'reinhard_fast_mask'`` take ``reinhard_fast``'s fit; the tiles they report
+    as too dark or without tissue (``stain.REINHARD_*``) are counted in the same place."""
     from . import stain
     stain.check(normalizer, norm_fit)
     mc_n = int(mc_n or engine.hp.uq_n)

@@ -1,11 +1,14 @@
-"""Stain normalisation in front of the staging kernel (hp.py:19 ``normalizer='reinhard_fast'``, or ``'macenko'``).
+"""Stain normalisation in front of the staging kernel (hp.py:19 ``normalizer='reinhard_fast'``, the rest of Slideflow's Reinhard
+family -- ``'reinhard'``, ``'reinhard_mask'``, ``'reinhard_fast_mask'`` --, or ``'macenko'``).
 
 Mirrors the object the reference calls at results.py:251-252
 (``interface.wsi_normalizer.rgb_to_rgb(image)``): a fitted normaliser with ``rgb_to_rgb``, ``fit`` and
 ``get_fit``; the arithmetic runs in the HIP kernel behind ``bq_stain_reinhard_fast``.  The target
 statistics are the ``norm_fit`` block of a Slideflow model's ``params.json`` -- they are read from
 there (``from_params``) or fitted to a target image, never hard-coded.  ``Macenko`` is the same object for a model trained
-with ``normalizer='macenko'`` (kernel behind ``bq_stain_macenko``; DESIGN.md "Macenko").  ``normalise`` is the one dispatch
+with ``normalizer='macenko'`` (kernel behind ``bq_stain_macenko``; DESIGN.md "Macenko").  ``Reinhard``, ``ReinhardMask`` and
+``ReinhardFastMask`` are ``reinhard_fast`` with a brightness standardisation in front and / or a tissue mask (kernel behind
+``bq_stain_reinhard``; DESIGN.md "Reinhard family"); their fit has ``reinhard_fast``'s keys.  ``normalise`` is the one dispatch
 every driver calls.
 """
 import json
@@ -14,7 +17,19 @@ import numpy as np
 import torch
 
 TILE_PX = 299
-METHODS = ('reinhard_fast', 'macenko')
+METHODS = ('reinhard_fast', 'macenko', 'reinhard', 'reinhard_mask', 'reinhard_fast_mask')
+
+# The Reinhard family (DESIGN.md "Reinhard family"; restated from Slideflow's definitions and UNPINNED like Macenko's constants: a box
+# with Slideflow settles them; kernels_reinhard.hip holds the same values).  A method is a pair of flags.
+REINHARD_BRIGHTNESS, REINHARD_MASK = 1, 2
+REINHARD_FLAGS = {'reinhard_fast': 0, 'reinhard': REINHARD_BRIGHTNESS, 'reinhard_fast_mask': REINHARD_MASK,
+                  'reinhard_mask': REINHARD_BRIGHTNESS | REINHARD_MASK}
+REINHARD_BRIGHT_PCT = 90.0         # brightness standardisation: this percentile of the tile's L becomes L = 100
+REINHARD_MASK_THRESHOLD = 0.93     # a pixel is tissue when its L is below 100 * this (Slideflow's default)
+# per-tile status of the family's kernel: NO_TISSUE leaves the brightness stage's bytes, DARK passes the tile through unchanged
+REINHARD_OK, REINHARD_NO_TISSUE, REINHARD_DARK = 0, 1, 2
+# the methods whose kernel reports a per-tile status (``normalise(..., status=)``): 0 is a normalised tile in all of them
+STATUS_METHODS = ('macenko', 'reinhard', 'reinhard_mask', 'reinhard_fast_mask')
 
 # Macenko's constants (Macenko 2009 in the numpy form of HEnorm_python, recalled and UNPINNED: a box with Slideflow settles them;
 # kernels_stain.hip holds the same values)
@@ -76,7 +91,7 @@ def check(normalizer, norm_fit):
     an unknown name or a fit of another method raises ValueError."""
     if norm_fit is None:
         return
-    if normalizer == 'reinhard_fast':
+    if normalizer in REINHARD_FLAGS:
         reinhard_fit(norm_fit)
     elif normalizer == 'macenko':
         macenko_fit(norm_fit)
@@ -87,12 +102,16 @@ def check(normalizer, norm_fit):
 def normalise(engine, tiles, normalizer, norm_fit, out=None, status=None):
     """The stain normaliser of a model in front of the staging kernel: uint8 NHWC tiles on the engine's device -> normalised
     tiles (``out`` may be ``tiles``: in place).  ``norm_fit=None``: no normaliser, ``tiles`` is returned as it is.  ``status``
-    (int32 [n], Macenko only; optional) receives the per-tile status (STAIN_*)."""
+    (int32 [n], the methods of STATUS_METHODS only; optional) receives the per-tile status (STAIN_* for Macenko, REINHARD_* for
+    the Reinhard family; 0 is a normalised tile in both)."""
     if norm_fit is None:
         return tiles
     if normalizer == 'reinhard_fast':
         means, stds = reinhard_fit(norm_fit)
         return engine.reinhard_fast(tiles, means, stds, out=out)
+    if normalizer in REINHARD_FLAGS:
+        means, stds = reinhard_fit(norm_fit)
+        return engine.reinhard(tiles, means, stds, REINHARD_FLAGS[normalizer], REINHARD_MASK_THRESHOLD, out=out, status=status)
     if normalizer == 'macenko':
         he, maxc = macenko_fit(norm_fit)
         return engine.macenko(tiles, he, maxc, out=out, status=status)
@@ -107,7 +126,8 @@ def make_normalizer(engine, normalizer, norm_fit):
     if normalizer == 'macenko':
         he, maxc = macenko_fit(norm_fit)
         return Macenko(engine, he, maxc)
-    return ReinhardFast(engine, *reinhard_fit(norm_fit))
+    cls = {'reinhard': Reinhard, 'reinhard_mask': ReinhardMask, 'reinhard_fast_mask': ReinhardFastMask}.get(normalizer, ReinhardFast)
+    return cls(engine, *reinhard_fit(norm_fit))
 
 
 class ReinhardFast:
@@ -155,6 +175,58 @@ class ReinhardFast:
         t, single = self._as_batch(image)
         out = self.engine.reinhard_fast(t, self.target_means, self.target_stds)
         return out[0] if single else out
+
+
+class Reinhard(ReinhardFast):
+    """Slideflow's ``normalizer='reinhard'``: ``reinhard_fast`` after a brightness standardisation of the tile (and of the target
+    it is fitted to).  The fit has ``reinhard_fast``'s keys.  Tiles of any square size the kernel takes (1..1024 px)."""
+    method = 'reinhard'
+    mask_threshold = REINHARD_MASK_THRESHOLD
+
+    @property
+    def flags(self):
+        return REINHARD_FLAGS[self.method]
+
+    def _as_batch(self, image):
+        t = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
+        if t.dtype != torch.uint8:
+            raise TypeError('stain normalisation takes uint8 RGB')
+        single = t.dim() == 3
+        t = t.unsqueeze(0) if single else t
+        if t.dim() != 4 or t.shape[3] != 3 or t.shape[1] != t.shape[2] or not 1 <= t.shape[1] <= 1024:
+            raise ValueError(f'expected [n,px,px,3] uint8 tiles with 1 <= px <= 1024, got {tuple(t.shape)}')
+        return t.to(self.engine.device).contiguous(), single
+
+    def fit(self, target):
+        """Fit to one square target tile [px,px,3] uint8: stores the CIE-LAB channel means / stds of its tissue pixels after the
+        brightness stage, whichever of the two the method has (ValueError for a target that is too dark or has no tissue)."""
+        t, _ = self._as_batch(target)
+        stats, st = self.engine.reinhard_stats(t[:1], self.flags, self.mask_threshold)
+        status = int(st[0])
+        if status != REINHARD_OK:
+            raise ValueError(f'the target tile is degenerate for {self.method} (status {status}: '
+                             f'{"no tissue pixel" if status == REINHARD_NO_TISSUE else "too dark to standardise"})')
+        s = stats.cpu().numpy()[0]
+        self.target_means, self.target_stds = s[:3].copy(), s[3:6].copy()
+        return self
+
+    def rgb_to_rgb(self, image):
+        if self.target_means is None:
+            raise RuntimeError('normaliser is not fitted (fit() or from_params())')
+        t, single = self._as_batch(image)
+        out = self.engine.reinhard(t, self.target_means, self.target_stds, self.flags, self.mask_threshold)
+        return out[0] if single else out
+
+
+class ReinhardMask(Reinhard):
+    """Slideflow's ``normalizer='reinhard_mask'``: ``reinhard`` with the statistics and the transform over the tissue pixels only
+    (L below 100 * mask_threshold after the brightness stage); the others keep the brightness stage's bytes."""
+    method = 'reinhard_mask'
+
+
+class ReinhardFastMask(Reinhard):
+    """Slideflow's ``normalizer='reinhard_fast_mask'``: ``reinhard_mask`` without the brightness stage."""
+    method = 'reinhard_fast_mask'
 
 
 class Macenko(ReinhardFast):

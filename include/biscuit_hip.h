@@ -7,6 +7,7 @@
  *
  *   bq_stain_reinhard_fast  interface.wsi_normalizer.rgb_to_rgb(image)   results.py:251-252, hp.py:19
  *   bq_stain_macenko        the same, for a model trained with normalizer='macenko'
+ *   bq_stain_reinhard       the same, for normalizer='reinhard', 'reinhard_mask' or 'reinhard_fast_mask'
  *   bq_stage        tf.image.per_image_standardization(norm_image)      results.py:256
  *   bq_range_screen no reference counterpart: picks the tiles for the f16 range taps
  *   bq_backbone     keras Xception(include_top=False, pooling='avg')     biscuit/hp.py:4,20,22
@@ -117,6 +118,23 @@ int bq_stain_reinhard_fast(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, cons
 /* Per-tile CIE-LAB channel statistics [n][6] = mean L, a, b, population std L, a, b: what the
  * normaliser's fit() stores as norm_fit for a target image. */
 int bq_stain_lab_stats(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, float* d_stats6, bq_stream_t stream);
+
+/* K0, optional front half (kernels_reinhard.hip): Slideflow's Reinhard family ("Reinhard family").  flags:
+ * 1 = brightness standardisation in front (the 90th percentile of the tile's L becomes L = 100), 2 = statistics and transform over
+ * the tissue pixels only (L < mask_L, strict); 0 `reinhard_fast`, 1 `reinhard`, 2 `reinhard_fast_mask`, 3 `reinhard_mask`.  uint8
+ * NHWC [n,px,px,3] -> uint8 NHWC, 1 <= px <= 1024; d_out may equal d_tiles.  target_means3 / target_stds3: as above (HOST pointers,
+ * finite).  mask_L: finite, whatever the flags.  d_status (nullable): int [n], 0 = normalised, 1 = no tissue pixel (the output is
+ * the brightness stage's), 2 = the percentile is not finite or <= 0 (the tile passes through unchanged).  Flags 0 gives
+ * bq_stain_reinhard_fast's bytes.  Allocates nothing, does not synchronise.  Unpinned, like reinhard_fast. */
+int bq_stain_reinhard(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, int px, int flags, float mask_L,
+                      const float* target_means3, const float* target_stds3, uint8_t* d_out_nhwc, int* d_status,
+                      bq_stream_t stream);
+
+/* What the family's fit() stores, per tile: d_stats8 float [n][8] = mean L, a, b, population std L, a, b over the tissue pixels of
+ * the brightness-standardised tile (NaN when the status is not 0), the percentile p (100 without flag 1), tissue pixels / pixels
+ * (0 when the status is not 0).  d_status (nullable): as above. */
+int bq_stain_reinhard_stats(bq_ctx* ctx, const uint8_t* d_tiles_nhwc, int n, int px, int flags, float mask_L, float* d_stats8,
+                            int* d_status, bq_stream_t stream);
 
 /* K0, optional front half: the `macenko` stain normaliser (Slideflow's normalizer='macenko'; DESIGN.md "Macenko" states the
  * spec, the precision contract and the degenerate-tile rule).  uint8 NHWC [n,px,px,3] -> uint8 NHWC; d_out may equal d_tiles.
