@@ -196,7 +196,8 @@ Route choose_route(const bq_ctx* c, int li, int n, bool from_u8, const char* tap
         if (!has_front(c)) return error(BQ_ERR_ARG, "the fused front kernel needs a 16-bit context with its weights loaded");
         if (wants(tap, "staged", "block1_conv1"))
             return error(BQ_ERR_ARG, "the fused front kernel does not materialise the staged tile or block1_conv1");
-        return conv(R_FRONT);
+        if (front_supported(dtype, n)) return conv(R_FRONT);
+        // a batch beyond the front kernel's 32-bit offsets: the walker stages the tiles and block1_conv2 takes the float entry's route
     }
     if (L.prod == PROD_S2) {   // a block's end
         const Layer& L2 = kLayers[li - 1];   // the block's last separable convolution is the row in front of its shortcut
@@ -490,6 +491,10 @@ int backbone_impl(const Walk& w, const void* in_nchw, float* feat, unsigned char
     if (front.kind == R_FRONT) {
         RUN(launch_front_route(w, u8, B));
     } else {
+        if (u8) {   // the uint8 entry past the front kernel's limit: stage the tiles, go on as the float entry does
+            in_nchw = at(L.staged);
+            if (!w.plan) RUN(bq_stage(c, u8, n, at(L.staged), (bq_stream_t)s));
+        }
         if (wants(w.want(), "staged")) {
             if (w.plan) { w.tap->written = 0; return BQ_OK; }
             if ((size_t)n * kStaged > w.tap->out_elems) return fail(c, BQ_ERR_ARG, "debug output too small");
@@ -855,8 +860,8 @@ int bq_set_tile_index_array(bq_ctx* c, const int64_t* d_tile_idx) {
 }
 
 // uint8 tiles -> pooled features, the kernels bq_mc_infer runs: in a 16-bit context with the front weights loaded staging +
-// block1_conv1 + block1_conv2 are ONE kernel straight from the bytes (kernels_front.hip), otherwise bq_stage + the backbone on
-// the planar tensor.  bq_mc_infer and bq_backbone_u8 share it, so a tile's features do not depend on which of the two a
+// block1_conv1 + block1_conv2 are ONE kernel straight from the bytes (kernels_front.hip) -- up to front_supported's batch, beyond
+// it the walker stages the tiles itself --, otherwise bq_stage + the backbone on the planar tensor.  bq_mc_infer and bq_backbone_u8 share it, so a tile's features do not depend on which of the two a
 // caller used for its batch.
 static int features_from_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* feat, unsigned char* ws, const WsLayout& L,
                             bq_stream_t stream) {

@@ -100,6 +100,9 @@ int launch_tile_conv(int dtype, const void* in, const void* wp, const float* sca
 
 // ---- small kernels (kernels_misc.hip) ----------------------------------------------
 int launch_stage_stats(const uint8_t* tiles, int n, int px, double* stats_scratch, hipStream_t s);
+// kernels_front.hip: a route predicate like stream_supported / tail_supported / wide_supported / exit_supported above (the tile
+// kernel, kernels_tile.hip, has none: it indexes with 64 bits and its int counts hold up to n = 11 million images)
+bool front_supported(int dtype, long long n);
 int launch_front(int dtype, const uint8_t* tiles, const unsigned long long* stats, const void* ws16, const float* s_scale,
                  const float* s_bias, const void* wc16, const float* c_scale, const float* c_bias, void* out, int n, int num_cus,
                  hipStream_t s);

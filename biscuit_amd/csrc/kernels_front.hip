@@ -344,12 +344,18 @@ int launch_front_t(const uint8_t* tiles, const unsigned long long* stats, const 
 
 }  // namespace
 
+// The kernel stores block1_conv2's output (147 x 147 x 64) through a raw buffer with 32-bit byte offsets, and 0xffffff00 is the
+// offset of the stores the hardware is to drop: the tensor must end at or below it (n <= 1 552).
+bool front_supported(int dtype, long long n) {
+    return dtype != 0 && n > 0 && n * CO * CO * 64 * 2 <= 0xffffff00ll;
+}
+
 // stats: [n][2] 64-bit integer sums of the tiles' bytes (launch_stage_stats); ws16: "block1_conv1/w16"; wc16: "block1_conv2/wp16"
 int launch_front(int dtype, const uint8_t* tiles, const unsigned long long* stats, const void* ws16, const float* s_scale,
                  const float* s_bias, const void* wc16, const float* c_scale, const float* c_bias, void* out, int n, int num_cus,
                  hipStream_t s) {
     if (n <= 0) return 0;
-    if (dtype == 0 || (long long)n * CO * CO * 64 * 2 > 0xffffff00ll) return (int)hipErrorInvalidValue;
+    if (!front_supported(dtype, n)) return (int)hipErrorInvalidValue;
     return dtype == 2 ? launch_front_t<f16_t>(tiles, stats, ws16, s_scale, s_bias, wc16, c_scale, c_bias, out, n, num_cus, s)
                       : launch_front_t<bf16_t>(tiles, stats, ws16, s_scale, s_bias, wc16, c_scale, c_bias, out, n, num_cus, s);
 }

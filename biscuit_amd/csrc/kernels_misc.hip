@@ -371,26 +371,33 @@ __global__ void slide_finish_kernel(const long long* acc_pred, const long long* 
 template <typename T>
 __global__ void to_f32_nhwc_kernel(const T* __restrict__ x, long long rows, int C, int ld,
                                    float* __restrict__ out) {
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= rows * C) return;
-    const long long r = gid / C;
-    const int c = (int)(gid - r * C);
-    out[gid] = to_f32<T>(x[r * ld + c]);
+    // grid-stride: a launch has fewer than 2^32 threads (the runtime truncates a larger one), a tap can have more elements --
+    // 147 x 147 x 128 from n = 1 553
+    for (long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x; gid < rows * C; gid += (long long)gridDim.x * blockDim.x) {
+        const long long r = gid / C;
+        const int c = (int)(gid - r * C);
+        out[gid] = to_f32<T>(x[r * ld + c]);
+    }
 }
 
 template <typename T>
 __global__ void nchw_to_f32_nhwc_kernel(const T* __restrict__ x, int n, int C, int HW,
                                         float* __restrict__ out) {
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= (long long)n * C * HW) return;
-    const int c = (int)(gid % C);
-    const long long pix = gid / C;
-    const int p = (int)(pix % HW);
-    const long long img = pix / HW;
-    out[gid] = to_f32<T>(x[(img * C + c) * HW + p]);
+    for (long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x; gid < (long long)n * C * HW; gid += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(gid % C);
+        const long long pix = gid / C;
+        const int p = (int)(pix % HW);
+        const long long img = pix / HW;
+        out[gid] = to_f32<T>(x[(img * C + c) * HW + p]);
+    }
 }
 
 inline int grid_for(long long total, int block) { return (int)((total + block - 1) / block); }
+// of a grid-stride kernel: at most 2^30 threads per launch
+inline int grid_stride_for(long long total, int block) {
+    const long long g = (total + block - 1) / block, cap = (1ll << 30) / block;
+    return (int)(g < cap ? g : cap);
+}
 
 }  // namespace
 
@@ -503,7 +510,7 @@ static int launch_slide_finish(const long long* acc_pred, const long long* acc_u
 int launch_to_f32_nhwc(const void* x, long long rows, int C, int ld, float* out, int dtype, hipStream_t s) {
     const long long total = rows * C;
     BQ_DISPATCH_T(dtype,
-                  hipLaunchKernelGGL(to_f32_nhwc_kernel<T_>, dim3(grid_for(total, 256)), dim3(256), 0, s,
+                  hipLaunchKernelGGL(to_f32_nhwc_kernel<T_>, dim3(grid_stride_for(total, 256)), dim3(256), 0, s,
                                      (const T_*)x, rows, C, ld, out));
     return (int)hipGetLastError();
 }
@@ -511,7 +518,7 @@ int launch_to_f32_nhwc(const void* x, long long rows, int C, int ld, float* out,
 int launch_nchw_to_f32_nhwc(const void* x, int n, int C, int HW, float* out, int dtype, hipStream_t s) {
     const long long total = (long long)n * C * HW;
     BQ_DISPATCH_T(dtype,
-                  hipLaunchKernelGGL(nchw_to_f32_nhwc_kernel<T_>, dim3(grid_for(total, 256)), dim3(256), 0,
+                  hipLaunchKernelGGL(nchw_to_f32_nhwc_kernel<T_>, dim3(grid_stride_for(total, 256)), dim3(256), 0,
                                      s, (const T_*)x, n, C, HW, out));
     return (int)hipGetLastError();
 }

@@ -16,8 +16,8 @@ and launch (batch 256, ``synthetic_weights(1, hard=True)``), kernel names and ca
 * f32: 40 gemm_fused_kernel launches for the 39 layers (block14_sepconv2, K = 1536, is split in two), four pool_add_kernel, one
   gap_kernel.
 
-A route that needs a batch beyond the 32-bit offset limits (n > 776 at 147 x 147 x 128 in 16 bits) was not observed on a device.
-Its DECISION is asserted (``test_16_bit_schedule_beyond_the_32_bit_limits``): the lists are those of the commit that still had the
+A route that needs a batch beyond the 32-bit offset limits (n > 776 at 147 x 147 x 128 in 16 bits) was not observed in that trace
+(tests/test_gpu_batch_limits.py runs those batches).  Its DECISION is asserted (``test_16_bit_schedule_beyond_the_32_bit_limits``): the lists are those of the commit that still had the
 TILE kinds 1-3, RESPOOL and PIPE routes for n = 777 and n = 1532, read off its ``choose_route`` and the limits of
 ``stream_supported`` / ``tail_supported`` / ``wide_supported`` (profiles/fallback_removal.txt), with each row that named one of
 those routes replaced by FUSED_GEMM -- and block 2's RESPOOL end by CONV_THEN_POOL FUSED_GEMM; every other row as it was.
@@ -71,12 +71,28 @@ SCHEDULE_16_N777 = ([('block1_conv2', 'FRONT'),
 SCHEDULE_16_N1532 = (SCHEDULE_16_N777[:4] +
                      [('block3_sepconv1', FUSED), ('block3_sepconv2', FUSED), ('block3_out', 'POOL_GEMM')] + SCHEDULE_16[5:])
 
+# n = 1553: block1_conv2's output (147 x 147 x 64) passes the front kernel's; the uint8 entry stages the tiles and walks the float
+# entry's routes (the tile kernel indexes with 64 bits: it has no limit of its own)
+SCHEDULE_16_N1553 = [('block1_conv2', 'TILE kind=0')] + SCHEDULE_16_N1532[1:]
+
 
 def test_16_bit_schedule_beyond_the_32_bit_limits(weights):
     eng = Engine(weights, dtype='f16', max_batch=1532)      # (the workspace grows on demand; a schedule allocates nothing)
     try:
         assert eng.schedule(777) == SCHEDULE_16_N777
         assert eng.schedule(1532) == SCHEDULE_16_N1532
+    finally:
+        eng.close()
+
+
+def test_16_bit_schedule_beyond_the_front_kernel(weights):
+    eng = Engine(weights, dtype='f16', max_batch=1553)
+    try:
+        assert eng.schedule(1552) == SCHEDULE_16_N1532
+        assert eng.schedule(1553) == SCHEDULE_16_N1553 == eng.schedule(1553, u8=False)
+        for tap in ('staged', 'block1_conv1'):               # the uint8 entry refuses them at every batch
+            with pytest.raises(BiscuitHipError, match='does not materialise'):
+                eng.schedule(1553, tap=tap)
     finally:
         eng.close()
 
