@@ -102,6 +102,11 @@ ABI = {
     'bq_delong_workspace_bytes': (_sz, [_i, _i64]),
     'bq_delong_chunk_rows': (_i64, [_i64]),
     'bq_delong': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _sz, _vp, _vp, _vp]),
+    'bq_head_train_workspace_bytes': (_sz, [_i]),
+    'bq_head_grad': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i, _i64, _u64, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    'bq_head_adam': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
+    'bq_head_train_steps': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i64, _u64, C.c_double,
+                                 C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
 }
 
 

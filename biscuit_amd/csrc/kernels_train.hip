@@ -1,0 +1,553 @@
+// Training the MC-dropout head on cached features (DESIGN.md section 7 "Head training"): one step is the gradient of the mean sparse
+// categorical cross-entropy of n <= 1024 gathered feature rows through
+//     x [n][2048] -> drop -> Dense 1024 + ReLU -> drop -> Dense 1024 + ReLU -> drop -> Dense 2 -> softmax
+// (bq_head_grad) and one fused Keras-Adam pass over the P = 3 149 826 parameters (bq_head_adam); bq_head_train_steps is those two in a
+// loop, one linear chain of launches on one stream.  The keep masks are the contract of oracle/philox.py -- counter (unit / 4, layer,
+// step, row index in the feature cache), key seed -- drawn by bq_common.h's philox4x32_10 wherever a dropped operand is formed, forward
+// and backward: no mask and no copied batch is stored.  State is plain fp32 [K][N] tensors in the caller's arrays (the packed hi / lo
+// fragments of the inference head, kernels_head.hip, are not touched).
+//
+// The five GEMMs -- two forward, dx = dz W^T, and dW = drop(x)^T dz of both hidden layers with K = n -- run on the exact f32-input
+// MFMA (v_mfma_f32_32x32x2_f32: an fmaf chain in k order, one rounding per product) from 64 x 64 x 32 LDS tiles, four waves of one 32 x 32
+// output tile each (four accumulators: the groups of 8 k of a chunk sum separately and are added pairwise at the end); the operands come in either orientation, "k contiguous" (read as ds_read_b128 from rows of 36 floats: the sixteen
+// lanes of a read group then cover all 64 banks) or "row contiguous" (four ds_read_b32 of 32 consecutive floats).  Inside a group of 8 k
+// the lane half h takes k = 4 h + t in MFMA t, for both operands alike: a fixed order.  The [., 2] logits layer, its softmax, the loss
+// and its gradients stay on the vector ALU; the softmax and the loss of a row are evaluated in float64 from the fp32 logits and the
+// rows' losses are summed in float64, so the loss carries one rounding beyond the logits' own.
+//
+// Every sum runs in a fixed order -- the MFMA chains, dW over the batch (the K loop), the bias column sums and the loss (eight row
+// groups, then the groups in order), the logits' dot products (an xor tree and four waves in order) -- and there are no floating-point atomics: a repeated
+// call gives the same bits.  ReLU's derivative is 0 at 0.  A feature that is not finite reaches the first GEMM as NaN whether its unit is
+// kept or dropped, a row index outside the cache or a label above 1 likewise: the loss is then NaN, never a plausible number.
+//
+// Adam evaluates the update of an element in float64 from its fp32 state and rounds once per stored value, so m', v' and w' are the
+// correctly rounded values of the Keras formulas; an element with g = 0 and m = v = 0 keeps its bits.
+#include <cmath>
+#include <hip/hip_runtime.h>
+
+#include "bq_ctx.h"
+
+namespace {
+
+constexpr int D_IN = 2048, D_H = 1024, D_OUT = 2;
+constexpr long long OFF_W0 = 0, OFF_B0 = OFF_W0 + (long long)D_IN * D_H, OFF_W1 = OFF_B0 + D_H, OFF_B1 = OFF_W1 + (long long)D_H * D_H,
+                    OFF_W2 = OFF_B1 + D_H, OFF_B2 = OFF_W2 + D_H * D_OUT, P_TOTAL = OFF_B2 + D_OUT;
+static_assert(P_TOTAL == 3149826, "the head's parameter count");
+constexpr int MAX_N = 1024;
+
+constexpr int TM = 64, TN = 64, TK = 32;        // the workgroup's tile
+constexpr int KSTR = TK + 4;                    // floats of a k-contiguous row in LDS
+constexpr int TILE_FLOATS = TM * KSTR;          // >= TK * TM, the row-contiguous image
+
+struct Drop {
+    unsigned layer, step, seed_lo, seed_hi, thresh;
+    float scale;
+};
+
+// Inverted dropout of the four units 4 g .. 4 g + 3 of the row whose Philox tile counter is ctr; a value that is not finite becomes NaN
+// whether kept or not.
+__device__ __forceinline__ float4 drop4(float4 v, unsigned g, unsigned ctr, const Drop& d) {
+    unsigned r[4];
+    philox4x32_10(g, d.layer, d.step, ctr, d.seed_lo, d.seed_hi, r);
+    const float nan = __builtin_nanf("");
+    float4 o;
+    o.x = __builtin_isfinite(v.x) ? (r[0] >= d.thresh ? v.x * d.scale : 0.f) : nan;
+    o.y = __builtin_isfinite(v.y) ? (r[1] >= d.thresh ? v.y * d.scale : 0.f) : nan;
+    o.z = __builtin_isfinite(v.z) ? (r[2] >= d.thresh ? v.z * d.scale : 0.f) : nan;
+    o.w = __builtin_isfinite(v.w) ? (r[3] >= d.thresh ? v.w * d.scale : 0.f) : nan;
+    return o;
+}
+
+// ReLU that keeps NaN, as the inference head's
+__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
+enum AMode : int { A_DROP_K = 0, A_PLAIN_K = 1, A_DROP_T = 2 };   // drop(src)[m][k]; src[m][k]; drop(src)[k = batch row][m = unit]
+enum BMode : int { B_ROWS = 0, B_KCONT = 1 };                     // b[k][n]; b[n][k]
+enum Epi : int { EPI_RELU = 0, EPI_DX = 1, EPI_STORE = 2 };
+
+struct TrainGemm {
+    const float* a;             // A's source, rows of lda floats
+    const float* b;             // B's source, rows of ldb floats
+    float* out;                 // [M][ldo]
+    const float* bias;          // EPI_RELU: [N]
+    const float* h;             // EPI_DX: the layer's own forward output [M][ldo]
+    const long long* rows;      // [batch]: the rows' indices in the feature cache, the Philox tile counters
+    long long n_feat;           // rows of the feature cache (gather)
+    int gather;                 // A's rows are a[rows[i]] (the feature cache) instead of a[i]
+    int lda, ldb, ldo;
+    int M, N, K;                // M rows x N columns, K summed; N a multiple of 64; K a multiple of 32 unless A_DROP_T (then any, = batch)
+    Drop drop;                  // of A (A_DROP_*) or of the epilogue (EPI_DX)
+};
+
+// source row of batch row i, or null for one outside the cache
+__device__ __forceinline__ const float* a_row(const TrainGemm& p, int i, unsigned& ctr) {
+    const long long r = p.rows[i];
+    ctr = (unsigned)r;
+    if (!p.gather) return p.a + (size_t)i * p.lda;
+    return (r >= 0 && r < p.n_feat) ? p.a + (size_t)r * p.lda : nullptr;
+}
+
+template <int AM, int BM, int EPI>
+__global__ void __launch_bounds__(256) train_gemm_kernel(const TrainGemm p) {
+    __shared__ __attribute__((aligned(16))) float As[TILE_FLOATS];
+    __shared__ __attribute__((aligned(16))) float Bs[TILE_FLOATS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r32 = lane & 31, h = lane >> 5;
+    const int wm = wave & 1, wn = wave >> 1;
+    const int n0 = blockIdx.x * TN, m0 = blockIdx.y * TM;
+    const float nan = __builtin_nanf("");
+
+    // what this thread brings in per chunk: two float4 of each operand
+    // k-contiguous image [64 rows][32 k]: float4 f -> row f >> 3, k 4 (f & 7); row-contiguous [32 k][64 rows]: k f >> 4, row 4 (f & 15)
+    const float* arow[2] = {nullptr, nullptr};
+    unsigned actr[2] = {0u, 0u};
+    bool alive[2] = {false, false};
+    if (AM != A_DROP_T) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int m = m0 + ((tid + i * 256) >> 3);
+            alive[i] = m < p.M;
+            if (alive[i]) arow[i] = a_row(p, m, actr[i]);
+        }
+    }
+    float4 ra0, ra1, rb0, rb1;
+    auto fetch = [&](int k0, int i, float4& ra, float4& rb) {
+        {
+            const int f = tid + i * 256;
+            if (AM == A_DROP_T) {
+                const int kk = k0 + (f >> 4), u = m0 + (f & 15) * 4;       // batch row, first of four units (u + 3 < M: M a multiple of 64)
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (kk < p.K) {
+                    unsigned ctr;
+                    const float* src = a_row(p, kk, ctr);
+                    v = src ? *reinterpret_cast<const float4*>(src + u) : make_float4(nan, nan, nan, nan);
+                    v = drop4(v, (unsigned)(u >> 2), ctr, p.drop);
+                }
+                ra = v;
+            } else {
+                const int k = k0 + (f & 7) * 4;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (alive[i]) {
+                    v = arow[i] ? *reinterpret_cast<const float4*>(arow[i] + k) : make_float4(nan, nan, nan, nan);
+                    if (AM == A_DROP_K) v = drop4(v, (unsigned)(k >> 2), actr[i], p.drop);
+                }
+                ra = v;
+            }
+            if (BM == B_ROWS) {
+                const int kk = k0 + (f >> 4), n = n0 + (f & 15) * 4;
+                rb = kk < p.K ? *reinterpret_cast<const float4*>(p.b + (size_t)kk * p.ldb + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                const int n = n0 + (f >> 3), k = k0 + (f & 7) * 4;
+                rb = *reinterpret_cast<const float4*>(p.b + (size_t)n * p.ldb + k);
+            }
+        }
+    };
+    auto stash = [&](int i, const float4& ra, const float4& rb) {
+        {
+            const int f = tid + i * 256;
+            if (AM == A_DROP_T) *reinterpret_cast<float4*>(As + (f >> 4) * TM + (f & 15) * 4) = ra;
+            else *reinterpret_cast<float4*>(As + (f >> 3) * KSTR + (f & 7) * 4) = ra;
+            if (BM == B_ROWS) *reinterpret_cast<float4*>(Bs + (f >> 4) * TN + (f & 15) * 4) = rb;
+            else *reinterpret_cast<float4*>(Bs + (f >> 3) * KSTR + (f & 7) * 4) = rb;
+        }
+    };
+
+    // four accumulators, one per group of 8 k of a chunk: four interleaved partial sums of K / 4 terms each, added pairwise at the end
+    // (a shorter chain per sum than one accumulator over all of K)
+    f32x16 acc4[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc4[j][e] = 0.f;
+
+    fetch(0, 0, ra0, rb0);
+    fetch(0, 1, ra1, rb1);
+    for (int k0 = 0; k0 < p.K; k0 += TK) {
+        stash(0, ra0, rb0);
+        stash(1, ra1, rb1);
+        __syncthreads();
+        if (k0 + TK < p.K) {
+            fetch(k0 + TK, 0, ra0, rb0);
+            fetch(k0 + TK, 1, ra1, rb1);
+        }
+#pragma unroll
+        for (int j = 0; j < TK / 8; ++j) {
+            const int kb = 8 * j + 4 * h;
+            float a[4], b[4];
+            if (AM == A_DROP_T) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) a[t] = As[(kb + t) * TM + wm * 32 + r32];
+            } else {
+                const float4 v = *reinterpret_cast<const float4*>(As + (wm * 32 + r32) * KSTR + kb);
+                a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+            }
+            if (BM == B_ROWS) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) b[t] = Bs[(kb + t) * TN + wn * 32 + r32];
+            } else {
+                const float4 v = *reinterpret_cast<const float4*>(Bs + (wn * 32 + r32) * KSTR + kb);
+                b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w;
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t)     // EPI_DX takes the transposed tile: a lane then holds groups of four units of one batch row
+                acc4[j] = EPI == EPI_DX ? __builtin_amdgcn_mfma_f32_32x32x2f32(b[t], a[t], acc4[j], 0, 0, 0)
+                                        : __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc4[j], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = (acc4[0][e] + acc4[1][e]) + (acc4[2][e] + acc4[3][e]);
+    // D: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+    if (EPI == EPI_DX) {        // transposed: column = the batch row, rows = units 8 q + 4 h .. + 3, one Philox draw per group
+        const int m = m0 + wm * 32 + r32;
+        if (m < p.M) {
+            const unsigned ctr = (unsigned)p.rows[m];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int n = n0 + wn * 32 + 8 * q + 4 * h;
+                const size_t o = (size_t)m * p.ldo + n;
+                const float4 hv = *reinterpret_cast<const float4*>(p.h + o);
+                unsigned r[4];
+                philox4x32_10((unsigned)(n >> 2), p.drop.layer, p.drop.step, ctr, p.drop.seed_lo, p.drop.seed_hi, r);
+                float4 v;
+                v.x = (hv.x > 0.f && r[0] >= p.drop.thresh) ? acc[4 * q + 0] * p.drop.scale : 0.f;
+                v.y = (hv.y > 0.f && r[1] >= p.drop.thresh) ? acc[4 * q + 1] * p.drop.scale : 0.f;
+                v.z = (hv.z > 0.f && r[2] >= p.drop.thresh) ? acc[4 * q + 2] * p.drop.scale : 0.f;
+                v.w = (hv.w > 0.f && r[3] >= p.drop.thresh) ? acc[4 * q + 3] * p.drop.scale : 0.f;
+                *reinterpret_cast<float4*>(p.out + o) = v;
+            }
+        }
+    } else {
+        const int n = n0 + wn * 32 + r32;
+        const float bias = EPI == EPI_RELU ? p.bias[n] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int m = m0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const float v = acc[e];
+            if (m < p.M) p.out[(size_t)m * p.ldo + n] = EPI == EPI_RELU ? relu_nan(v + bias) : v;
+        }
+    }
+}
+
+// the sum over a workgroup of 256 threads, the same order every time: an xor tree in each wave, then the four waves in order
+__device__ __forceinline__ float block_sum_256(float v, float* lds) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// A workgroup per batch row: logits = drop(h1) W2 + b2, softmax, the row's loss, dlog = (p - onehot) / n, and
+// dz1 = (h1 > 0 and kept) ? scale (dlog . W2[k]) : 0.
+__global__ void __launch_bounds__(256) train_logits_kernel(const float* __restrict__ h1, const float* __restrict__ w2,
+                                                           const float* __restrict__ b2, const long long* __restrict__ rows,
+                                                           const unsigned char* __restrict__ label, int n, Drop d,
+                                                           float* __restrict__ dz1, float* __restrict__ dlog, double* __restrict__ rowloss) {
+    __shared__ float lds[4];
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const unsigned ctr = (unsigned)rows[m];
+    const float4 hv = *reinterpret_cast<const float4*>(h1 + (size_t)m * D_H + tid * 4);
+    const float4 u = drop4(hv, (unsigned)tid, ctr, d);
+    const float4 wa = *reinterpret_cast<const float4*>(w2 + tid * 8), wb = *reinterpret_cast<const float4*>(w2 + tid * 8 + 4);
+    // units 4 tid .. 4 tid + 3: (wa.x, wa.y), (wa.z, wa.w), (wb.x, wb.y), (wb.z, wb.w)
+    const float s0 = fmaf(u.w, wb.z, fmaf(u.z, wb.x, fmaf(u.y, wa.z, u.x * wa.x)));
+    const float s1 = fmaf(u.w, wb.w, fmaf(u.z, wb.y, fmaf(u.y, wa.w, u.x * wa.y)));
+    const float z0 = block_sum_256(s0, lds) + b2[0];
+    const float z1 = block_sum_256(s1, lds) + b2[1];
+    const unsigned y = label[m];
+    // the softmax and the row's loss in float64 from the fp32 logits, each rounded once (a few operations per row)
+    const double zd0 = (double)z0, zd1 = (double)z1, mx = fmax(zd0, zd1);
+    const double e0 = exp(zd0 - mx), e1 = exp(zd1 - mx), sum = e0 + e1;
+    double p0 = e0 / sum, p1 = e1 / sum;
+    double loss = log(sum) - ((y ? zd1 : zd0) - mx);
+    if (y > 1u || z0 != z0 || z1 != z1) { loss = __builtin_nan(""); p0 = loss; p1 = loss; }
+    const float g0 = (float)((p0 - (y == 0u ? 1.0 : 0.0)) / (double)n), g1 = (float)((p1 - (y == 1u ? 1.0 : 0.0)) / (double)n);
+    if (tid == 0) {
+        dlog[2 * m] = g0;
+        dlog[2 * m + 1] = g1;
+        rowloss[m] = loss;
+    }
+    unsigned r[4];
+    philox4x32_10((unsigned)tid, d.layer, d.step, ctr, d.seed_lo, d.seed_hi, r);
+    float4 o;
+    o.x = (hv.x > 0.f && r[0] >= d.thresh) ? d.scale * fmaf(g1, wa.y, g0 * wa.x) : 0.f;
+    o.y = (hv.y > 0.f && r[1] >= d.thresh) ? d.scale * fmaf(g1, wa.w, g0 * wa.z) : 0.f;
+    o.z = (hv.z > 0.f && r[2] >= d.thresh) ? d.scale * fmaf(g1, wb.y, g0 * wb.x) : 0.f;
+    o.w = (hv.w > 0.f && r[3] >= d.thresh) ? d.scale * fmaf(g1, wb.w, g0 * wb.z) : 0.f;
+    if (g0 != g0 || g1 != g1) o = make_float4(g0, g0, g0, g0);       // a NaN row stays NaN where its ReLU would have cut it
+    *reinterpret_cast<float4*>(dz1 + (size_t)m * D_H + tid * 4) = o;
+}
+
+// The small sums over the batch.  A workgroup is 8 row groups x 32 lanes: row group q sums the rows q, q + 8, ... in order, then the
+// eight partial sums are added in the order of q -- a fixed order.  Workgroups 0-7: the logits kernel's gradient, a lane per group of four
+// units (g_w2[k][c] = sum_i drop(h1)[i][k] dlog[i][c]).  Workgroup 8: the logits bias gradient and the loss (the rows' losses summed in
+// float64, rounded once).  Workgroups 9-40 and 41-72: the column sums of dz1 and dz0, the hidden layers' bias gradients, a lane per column.
+constexpr int SUM_BLOCKS = 8 + 1 + 2 * (D_H / 32);
+__global__ void __launch_bounds__(256) train_sums_kernel(const float* __restrict__ h1, const float* __restrict__ dz1,
+                                                         const float* __restrict__ dz0, const float* __restrict__ dlog,
+                                                         const double* __restrict__ rowloss, const long long* __restrict__ rows, int n, Drop d,
+                                                         float* __restrict__ g_w2, float* __restrict__ g_b2, float* __restrict__ g_b1,
+                                                         float* __restrict__ g_b0, float* __restrict__ loss) {
+    __shared__ float part[8][32][9];                 // (9: the eight values of a lane on distinct banks)
+    __shared__ double lpart[8][32];
+    const int q = threadIdx.x >> 5, c = threadIdx.x & 31, b = blockIdx.x;
+    if (b < 8) {
+        const int ug = b * 32 + c;                   // units 4 ug .. 4 ug + 3
+        float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int i = q; i < n; i += 8) {
+            const float4 u = drop4(*reinterpret_cast<const float4*>(h1 + (size_t)i * D_H + ug * 4), (unsigned)ug, (unsigned)rows[i], d);
+            const float g0 = dlog[2 * i], g1 = dlog[2 * i + 1];
+            a[0] = fmaf(u.x, g0, a[0]); a[1] = fmaf(u.x, g1, a[1]);
+            a[2] = fmaf(u.y, g0, a[2]); a[3] = fmaf(u.y, g1, a[3]);
+            a[4] = fmaf(u.z, g0, a[4]); a[5] = fmaf(u.z, g1, a[5]);
+            a[6] = fmaf(u.w, g0, a[6]); a[7] = fmaf(u.w, g1, a[7]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) part[q][c][e] = a[e];
+        __syncthreads();
+        if (q == 0) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float s = part[0][c][e];
+                for (int k = 1; k < 8; ++k) s += part[k][c][e];
+                g_w2[ug * 8 + e] = s;
+            }
+        }
+    } else if (b == 8) {
+        float s0 = 0.f, s1 = 0.f;
+        double l = 0.0;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            s0 += dlog[2 * i];
+            s1 += dlog[2 * i + 1];
+            l += rowloss[i];
+        }
+        part[q][c][0] = s0;
+        part[q][c][1] = s1;
+        lpart[q][c] = l;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            s0 = 0.f; s1 = 0.f; l = 0.0;
+            for (int t = 0; t < 256; ++t) {
+                s0 += part[t >> 5][t & 31][0];
+                s1 += part[t >> 5][t & 31][1];
+                l += lpart[t >> 5][t & 31];
+            }
+            g_b2[0] = s0;
+            g_b2[1] = s1;
+            loss[0] = (float)(l / (double)n);
+        }
+    } else {
+        const bool first = b < 9 + D_H / 32;
+        const int col = (b - (first ? 9 : 9 + D_H / 32)) * 32 + c;
+        const float* dz = first ? dz1 : dz0;
+        float s = 0.f;
+        for (int i = q; i < n; i += 8) s += dz[(size_t)i * D_H + col];
+        part[q][c][0] = s;
+        __syncthreads();
+        if (q == 0) {
+            s = part[0][c][0];
+            for (int k = 1; k < 8; ++k) s += part[k][c][0];
+            (first ? g_b1 : g_b0)[col] = s;
+        }
+    }
+}
+
+// Keras Adam of one element, t = step + 1 folded into alpha = lr sqrt(1 - b2^t) / (1 - b1^t) on the host
+__global__ void __launch_bounds__(256) train_adam_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
+                                                         const float* __restrict__ g, long long count, double b1, double b2, double eps,
+                                                         double alpha) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const double gi = (double)g[i];
+    const double mi = b1 * (double)m[i] + (1.0 - b1) * gi;
+    const double vi = b2 * (double)v[i] + (1.0 - b2) * (gi * gi);
+    m[i] = (float)mi;
+    v[i] = (float)vi;
+    w[i] = (float)((double)w[i] - alpha * (mi / (sqrt(vi) + eps)));
+}
+
+inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// h0 | h1 | dz1 | dz0, each [n][1024] | dlog [n][2] | rowloss f64 [n]
+size_t train_workspace_bytes(int n) {
+    if (n < 1 || n > MAX_N) return 0;
+    return 4 * al((size_t)n * D_H * 4) + al((size_t)n * 2 * 4) + al((size_t)n * 8);
+}
+
+template <int AM, int BM, int EPI>
+void launch_gemm(const TrainGemm& p, hipStream_t s) {
+    hipLaunchKernelGGL((train_gemm_kernel<AM, BM, EPI>), dim3(p.N / TN, (p.M + TM - 1) / TM), dim3(256), 0, s, p);
+}
+
+struct GradArgs {
+    const float* params; const float* feats; long long n_feat; const long long* rows; const unsigned char* labels; int n;
+    long long step; uint64_t seed; unsigned thresh; float scale; float* grad; float* loss; void* ws;
+};
+
+std::string bad_grad_args(const char* entry, const void* params, const void* feats, int64_t n_feat, const void* rows, const void* labels, int n,
+                          int64_t step, double rate, const void* grad, const void* loss, const void* ws) {
+    const std::string e(entry);
+    if (n < 1 || n > MAX_N) return e + ": 1 <= n <= 1024";
+    if (n_feat < 1 || step < 0 || step > 0xffffffffLL) return e + ": an empty feature cache, or a step outside 0 .. 2^32 - 1";
+    if (!(rate >= 0.0) || !(rate < 1.0)) return e + ": the rate must lie in [0, 1)";
+    if (!params || !feats || !rows || !labels || !grad || !loss || !ws || ((uintptr_t)params & 15) || ((uintptr_t)feats & 15) ||
+        ((uintptr_t)grad & 15) || ((uintptr_t)rows & 7) || ((uintptr_t)loss & 3) || ((uintptr_t)ws & 255))
+        return e + ": bad argument (null pointer, params, feats or grad not 16-byte, rows not 8-byte or the workspace not 256-byte aligned)";
+    return "";
+}
+
+// The seven launches of one gradient, each a profiling class of its own (Adam's is the eighth of a step).
+int enqueue_grad(bq_ctx* c, const GradArgs& a, hipStream_t s) {
+    const int n = a.n;
+    unsigned char* p = (unsigned char*)a.ws;
+    float* h0 = (float*)p; p += al((size_t)n * D_H * 4);
+    float* h1 = (float*)p; p += al((size_t)n * D_H * 4);
+    float* dz1 = (float*)p; p += al((size_t)n * D_H * 4);
+    float* dz0 = (float*)p; p += al((size_t)n * D_H * 4);
+    float* dlog = (float*)p; p += al((size_t)n * 2 * 4);
+    double* rowloss = (double*)p;
+    const float* W0 = a.params + OFF_W0; const float* b0 = a.params + OFF_B0;
+    const float* W1 = a.params + OFF_W1; const float* b1 = a.params + OFF_B1;
+    const float* W2 = a.params + OFF_W2; const float* b2 = a.params + OFF_B2;
+    Drop d{0u, (unsigned)a.step, (unsigned)(a.seed & 0xffffffffu), (unsigned)(a.seed >> 32), a.thresh, a.scale};
+    const double fn = (double)n;
+    TrainGemm g{};
+    g.rows = a.rows; g.n_feat = a.n_feat;
+    {   // h0 = relu(drop_0(x[rows]) W0 + b0)
+        ProfScope ps(c, s, "head_train_fwd0", 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_IN + (double)D_IN * D_H + fn * D_H));
+        TrainGemm q = g;
+        q.a = a.feats; q.lda = D_IN; q.gather = 1; q.b = W0; q.ldb = D_H; q.out = h0; q.ldo = D_H; q.bias = b0;
+        q.M = n; q.N = D_H; q.K = D_IN; q.drop = d; q.drop.layer = 0u;
+        launch_gemm<A_DROP_K, B_ROWS, EPI_RELU>(q, s);
+    }
+    {   // h1 = relu(drop_1(h0) W1 + b1)
+        ProfScope ps(c, s, "head_train_fwd1", 2.0 * fn * D_H * D_H, 4.0 * (2.0 * fn * D_H + (double)D_H * D_H));
+        TrainGemm q = g;
+        q.a = h0; q.lda = D_H; q.gather = 0; q.b = W1; q.ldb = D_H; q.out = h1; q.ldo = D_H; q.bias = b1;
+        q.M = n; q.N = D_H; q.K = D_H; q.drop = d; q.drop.layer = 1u;
+        launch_gemm<A_DROP_K, B_ROWS, EPI_RELU>(q, s);
+    }
+    Drop d2 = d; d2.layer = 2u;
+    {   // logits, softmax, loss per row, dlog, dz1
+        ProfScope ps(c, s, "head_train_logits", 8.0 * fn * D_H, 4.0 * (2.0 * fn * D_H + 2.0 * D_H));
+        hipLaunchKernelGGL(train_logits_kernel, dim3(n), dim3(256), 0, s, h1, W2, b2, a.rows, a.labels, n, d2, dz1, dlog, rowloss);
+    }
+    {   // dz0 = (h0 > 0 and kept_1) ? scale (dz1 W1^T) : 0
+        ProfScope ps(c, s, "head_train_dx1", 2.0 * fn * D_H * D_H, 4.0 * (3.0 * fn * D_H + (double)D_H * D_H));
+        TrainGemm q = g;
+        q.a = dz1; q.lda = D_H; q.gather = 0; q.b = W1; q.ldb = D_H; q.out = dz0; q.ldo = D_H; q.h = h0;
+        q.M = n; q.N = D_H; q.K = D_H; q.drop = d; q.drop.layer = 1u;
+        launch_gemm<A_PLAIN_K, B_KCONT, EPI_DX>(q, s);
+    }
+    {   // g_W1 = drop_1(h0)^T dz1
+        ProfScope ps(c, s, "head_train_dw1", 2.0 * fn * D_H * D_H, 4.0 * (2.0 * fn * D_H + (double)D_H * D_H));
+        TrainGemm q = g;
+        q.a = h0; q.lda = D_H; q.gather = 0; q.b = dz1; q.ldb = D_H; q.out = a.grad + OFF_W1; q.ldo = D_H;
+        q.M = D_H; q.N = D_H; q.K = n; q.drop = d; q.drop.layer = 1u;
+        launch_gemm<A_DROP_T, B_ROWS, EPI_STORE>(q, s);
+    }
+    {   // g_W0 = drop_0(x[rows])^T dz0
+        ProfScope ps(c, s, "head_train_dw0", 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_IN + fn * D_H + (double)D_IN * D_H));
+        TrainGemm q = g;
+        q.a = a.feats; q.lda = D_IN; q.gather = 1; q.b = dz0; q.ldb = D_H; q.out = a.grad + OFF_W0; q.ldo = D_H;
+        q.M = D_IN; q.N = D_H; q.K = n; q.drop = d; q.drop.layer = 0u;
+        launch_gemm<A_DROP_T, B_ROWS, EPI_STORE>(q, s);
+    }
+    {   // g_W2, g_b2, the loss, g_b1, g_b0
+        ProfScope ps(c, s, "head_train_sums", 4.0 * fn * D_H + 2.0 * fn * D_H, 4.0 * 3.0 * fn * D_H);
+        hipLaunchKernelGGL(train_sums_kernel, dim3(SUM_BLOCKS), dim3(256), 0, s, h1, dz1, dz0, dlog, rowloss, a.rows, n, d2, a.grad + OFF_W2,
+                           a.grad + OFF_B2, a.grad + OFF_B1, a.grad + OFF_B0, a.loss);
+    }
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+std::string bad_adam_args(const char* entry, const void* params, const void* m, const void* v, const void* grad, int64_t step, double lr,
+                          double b1, double b2, double eps) {
+    const std::string e(entry);
+    if (!params || !m || !v || !grad || (((uintptr_t)params | (uintptr_t)m | (uintptr_t)v | (uintptr_t)grad) & 3))
+        return e + ": bad argument (null or misaligned pointer)";
+    if (step < 0 || step > 0xffffffffLL || !std::isfinite(lr) || !(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0) || !(eps > 0.0) ||
+        !std::isfinite(eps))
+        return e + ": a step outside 0 .. 2^32 - 1, a learning rate that is not finite, b1 or b2 outside [0, 1), or eps <= 0";
+    return "";
+}
+
+int enqueue_adam(bq_ctx* c, float* params, float* m, float* v, const float* grad, long long step, double lr, double b1, double b2, double eps,
+                 hipStream_t s) {
+    const double t = (double)(step + 1);
+    const double alpha = lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
+    ProfScope ps(c, s, "head_train_adam", 12.0 * (double)P_TOTAL, 28.0 * (double)P_TOTAL);
+    hipLaunchKernelGGL(train_adam_kernel, dim3((unsigned)((P_TOTAL + 255) / 256)), dim3(256), 0, s, params, m, v, grad, P_TOTAL, b1, b2, eps,
+                       alpha);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+void dropout_of(double rate, unsigned& thresh, float& scale) {      // set_dropout's rule (biscuit_hip.hip), the contract of oracle/philox.py
+    const double t = std::floor(rate * 4294967296.0);
+    thresh = t > 4294967295.0 ? 4294967295u : (unsigned)t;
+    scale = (float)(1.0 / (1.0 - rate));
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t bq_head_train_workspace_bytes(int n) { return train_workspace_bytes(n); }
+
+int bq_head_grad(bq_ctx* c, const float* d_params, const float* d_feats, int64_t n_feat, const int64_t* d_rows, const uint8_t* d_labels, int n,
+                 int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    if (!c) return fail(c, BQ_ERR_ARG, "bq_head_grad: null context");
+    const std::string bad = bad_grad_args("bq_head_grad", d_params, d_feats, n_feat, d_rows, d_labels, n, step, rate, d_grad, d_loss, d_ws);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < train_workspace_bytes(n)) return fail(c, BQ_ERR_WORKSPACE, "bq_head_grad: workspace below bq_head_train_workspace_bytes(n)");
+    DeviceGuard guard(c->device);
+    GradArgs a{d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, n, (long long)step, seed, 0u, 1.f, d_grad, d_loss, d_ws};
+    dropout_of(rate, a.thresh, a.scale);
+    return enqueue_grad(c, a, (hipStream_t)stream);
+}
+
+int bq_head_adam(bq_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, int64_t step, double lr, double b1, double b2,
+                 double eps, bq_stream_t stream) {
+    if (!c) return fail(c, BQ_ERR_ARG, "bq_head_adam: null context");
+    const std::string bad = bad_adam_args("bq_head_adam", d_params, d_m, d_v, d_grad, step, lr, b1, b2, eps);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    DeviceGuard guard(c->device);
+    return enqueue_adam(c, d_params, d_m, d_v, d_grad, (long long)step, lr, b1, b2, eps, (hipStream_t)stream);
+}
+
+int bq_head_train_steps(bq_ctx* c, float* d_params, float* d_m, float* d_v, float* d_grad, const float* d_feats, int64_t n_feat,
+                        const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n, int64_t step0, uint64_t seed,
+                        double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws, size_t ws_bytes,
+                        bq_stream_t stream) {
+    if (!c) return fail(c, BQ_ERR_ARG, "bq_head_train_steps: null context");
+    if (steps < 1 || steps > (1 << 24) || last_n < 1 || last_n > batch || !h_lr)
+        return fail(c, BQ_ERR_ARG, "bq_head_train_steps: 1 <= steps <= 2^24, 1 <= last_n <= batch and a learning rate per step");
+    std::string bad = bad_grad_args("bq_head_train_steps", d_params, d_feats, n_feat, d_rows, d_labels, batch, step0, rate, d_grad, d_losses, d_ws);
+    if (bad.empty() && step0 + steps > 0x100000000LL) bad = "bq_head_train_steps: the steps pass 2^32";
+    for (int i = 0; bad.empty() && i < steps; ++i) bad = bad_adam_args("bq_head_train_steps", d_params, d_m, d_v, d_grad, step0 + i, h_lr[i], b1, b2, eps);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < train_workspace_bytes(batch))
+        return fail(c, BQ_ERR_WORKSPACE, "bq_head_train_steps: workspace below bq_head_train_workspace_bytes(batch)");
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    GradArgs a{d_params, d_feats, (long long)n_feat, nullptr, nullptr, 0, 0, seed, 0u, 1.f, d_grad, nullptr, d_ws};
+    dropout_of(rate, a.thresh, a.scale);
+    for (int i = 0; i < steps; ++i) {
+        a.rows = (const long long*)d_rows + (size_t)i * batch;
+        a.labels = d_labels + (size_t)i * batch;
+        a.n = i + 1 < steps ? batch : last_n;
+        a.step = (long long)step0 + i;
+        a.loss = d_losses + i;
+        RUN(enqueue_grad(c, a, s));
+        RUN(enqueue_adam(c, d_params, d_m, d_v, d_grad, a.step, h_lr[i], b1, b2, eps, s));
+    }
+    return BQ_OK;
+}
+
+}  // extern "C"

@@ -59,6 +59,8 @@ class Engine:
         if not torch.cuda.is_available():
             raise BiscuitHipError('no HIP device visible: the MI355X path has no CPU fallback')
         self.hp = hp or nature2022()
+        self.weights = weights           # the caller's dict, not a copy: host arrays that live as long as the engine does (``train`` starts a
+                                         # head from them and builds the engine of a trained head around the same backbone)
         self.dtype = dtype
         self.device = torch.device('cuda', torch.cuda.current_device() if device is None else device)
         self.max_batch, self.max_mc = int(max_batch), int(max_mc)
@@ -128,7 +130,7 @@ class Engine:
         """Lets go of every device buffer grown on demand -- the network's workspace and each tool's scratch -- and of nothing else;
         the next call that wants one allocates it again."""
         self._ws = None                  # the network's workspace (``_ws_for``)
-        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong
+        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong, train
 
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
@@ -1065,6 +1067,96 @@ class Engine:
         if components:
             res['V'] = V.cpu().numpy()
         return res
+
+    # ------------------------------------------------------------------ head training (kernels_train.hip)
+    HEAD_PARAMS, HEAD_TRAIN_MAX_ROWS = 3149826, 1024
+
+    def train_scratch(self, n):
+        """A caller's own scratch for ``head_grad`` / ``head_train_steps`` with batches of up to ``n`` rows (``scratch=``): uint8
+        [``bq_head_train_workspace_bytes(n)``] on this device.  Calls that may overlap on different streams each bring one; without
+        one the calls share the engine's cached ``train`` buffer."""
+        return self._bytes(self._lib.bq_head_train_workspace_bytes(int(n)))
+
+    def _train_state(self, *named):
+        for name, t in named:
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == self.HEAD_PARAMS and t.is_contiguous()):
+                raise ValueError(f'{name} must be contiguous float32 [{self.HEAD_PARAMS}]')
+            self._on_device(name, t)
+
+    def _train_batch(self, feats, rows, labels, count):
+        """``feats`` float32 [N, 2048], ``rows`` int64 and ``labels`` uint8, ``count`` of each, all on this device; ValueError otherwise."""
+        if not (torch.is_tensor(feats) and feats.dtype == torch.float32 and feats.dim() == 2 and feats.shape[1] == 2048 and
+                feats.shape[0] >= 1 and feats.is_contiguous()):
+            raise ValueError('feats must be contiguous float32 [N, 2048] with N >= 1')
+        if not (torch.is_tensor(rows) and rows.dtype == torch.int64 and rows.is_contiguous() and rows.numel() == count):
+            raise ValueError(f'rows must be contiguous int64 [{count}]')
+        if not (torch.is_tensor(labels) and labels.dtype == torch.uint8 and labels.is_contiguous() and labels.numel() == count):
+            raise ValueError(f'labels must be contiguous uint8 [{count}]')
+        for name, t in (('feats', feats), ('rows', rows), ('labels', labels)):
+            self._on_device(name, t)
+
+    def head_grad(self, params, feats, rows, labels, step, seed, rate=None, grad=None, scratch=None):
+        """Gradient of the head's mean cross-entropy over the rows ``feats[rows]`` (``bq_head_grad``): ``params`` float32 [P] in the
+        order of ``train.HEAD_TENSORS``, ``feats`` float32 [N, 2048], ``rows`` int64 [n] (also the Philox tile counters), ``labels``
+        uint8 [n] in {0, 1}, 1 <= n <= 1024, all on this device; dropout ``rate`` (the engine's when None) with pass = ``step``.
+        -> ``(grad [P], loss [1])`` on the device.  The engine's own weights play no part."""
+        n = int(rows.numel()) if torch.is_tensor(rows) else -1
+        if not 1 <= n <= self.HEAD_TRAIN_MAX_ROWS:
+            raise ValueError(f'head_grad: 1 <= n <= {self.HEAD_TRAIN_MAX_ROWS} rows, as an int64 tensor')
+        self._train_state(('params', params))
+        self._train_batch(feats, rows, labels, n)
+        if grad is None:
+            grad = torch.empty(self.HEAD_PARAMS, dtype=torch.float32, device=self.device)
+        self._train_state(('grad', grad))
+        rate = float(self.hp.dropout if rate is None else rate)
+        if not 0.0 <= rate < 1.0 or not 0 <= int(step) < 1 << 32:
+            raise ValueError('head_grad: the rate lies in [0, 1) and the step in 0 .. 2^32 - 1')
+        need = int(self._lib.bq_head_train_workspace_bytes(n))
+        scratch = self._scratch('train', need, scratch)
+        assert scratch.is_cuda and scratch.is_contiguous()        # (too small: the library refuses, BQ_ERR_WORKSPACE)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        self._check(self._lib.bq_head_grad(self._ctx, _ptr(params), _ptr(feats), int(feats.shape[0]), _ptr(rows), _ptr(labels), n, int(step),
+                                           int(seed), rate, _ptr(grad), _ptr(loss), _ptr(scratch), scratch.numel(), self._stream()))
+        return grad, loss
+
+    def head_adam(self, params, m, v, grad, step, lr, b1=0.9, b2=0.999, eps=1e-7):
+        """One Keras-Adam pass over the head's parameters in place (``bq_head_adam``), t = ``step`` + 1."""
+        self._train_state(('params', params), ('m', m), ('v', v), ('grad', grad))
+        if not 0 <= int(step) < 1 << 32:
+            raise ValueError('head_adam: the step lies in 0 .. 2^32 - 1')
+        self._check(self._lib.bq_head_adam(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), int(step), float(lr), float(b1), float(b2),
+                                           float(eps), self._stream()))
+
+    def head_train_steps(self, params, m, v, feats, rows, labels, batch, step0, seed, lr, rate=None, b1=0.9, b2=0.999, eps=1e-7,
+                         grad=None, scratch=None):
+        """``S`` = ceil(len(rows) / batch) steps of ``head_grad`` + ``head_adam`` back to back (``bq_head_train_steps``), step
+        ``step0 + i`` over ``rows[i * batch:(i + 1) * batch]`` -- the last batch short when ``len(rows)`` is no multiple of ``batch``
+        -- with the learning rate ``lr[i]`` (a sequence of ``S`` floats).  ``params``, ``m``, ``v`` change in place; -> losses
+        float32 [S] on the device.  The same bits as the single calls."""
+        count = int(rows.numel()) if torch.is_tensor(rows) else 0
+        batch = int(batch)
+        if not 1 <= batch <= self.HEAD_TRAIN_MAX_ROWS or count < 1:
+            raise ValueError(f'head_train_steps: 1 <= batch <= {self.HEAD_TRAIN_MAX_ROWS} and at least one row')
+        steps = -(-count // batch)
+        last_n = count - (steps - 1) * batch
+        self._train_state(('params', params), ('m', m), ('v', v))
+        self._train_batch(feats, rows, labels, count)
+        if grad is None:
+            grad = torch.empty(self.HEAD_PARAMS, dtype=torch.float32, device=self.device)
+        self._train_state(('grad', grad))
+        lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
+        rate = float(self.hp.dropout if rate is None else rate)
+        if len(lr) != steps or not 0.0 <= rate < 1.0 or not 0 <= int(step0) <= (1 << 32) - steps:
+            raise ValueError(f'head_train_steps: {steps} learning rates, a rate in [0, 1) and steps below 2^32')
+        need = int(self._lib.bq_head_train_workspace_bytes(batch))
+        scratch = self._scratch('train', need, scratch)
+        assert scratch.is_cuda and scratch.is_contiguous()        # (too small: the library refuses, BQ_ERR_WORKSPACE)
+        losses = torch.empty(steps, dtype=torch.float32, device=self.device)
+        self._check(self._lib.bq_head_train_steps(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), _ptr(feats), int(feats.shape[0]),
+                                                  _ptr(rows), _ptr(labels), steps, batch, last_n, int(step0), int(seed), rate,
+                                                  lr.ctypes.data_as(C.POINTER(C.c_double)), float(b1), float(b2), float(eps), _ptr(losses),
+                                                  _ptr(scratch), scratch.numel(), self._stream()))
+        return losses
 
     def debug_activation(self, name, staged, shape_hwc, true_scale=True):
         """The named activation as fp32 [n,H,W,C]; with activation exponents (``act_exp``) the stored tensor times 2^k, i.e. the

@@ -93,28 +93,27 @@ def _first_records(slide, count, px):
     return t, np.asarray(loc, np.int64).reshape(-1, 2)
 
 
-def generate_features(engine_or_pool, slides, max_tiles=10, mc_n=None, seed=None, norm_fit=None, normalizer='reinhard_fast', keep_tiles=True):
-    """The first ``max_tiles`` tiles of every slide (0 / None: all) through ``backbone_u8`` and ``mc_head`` -> ``FeatureMap``.  The
-    Philox index of a tile is its index in the UNCLIPPED slide list (``distributed.global_tile_offsets`` of the slides' tile
-    counts), so its numbers are exactly the ones ``evaluate()`` over the same slides gives it."""
+def walk_features(eng, slides, max_tiles, on_batch, norm_fit=None, normalizer='reinhard_fast', keep_tiles=False, batch=None):
+    """``evaluate()``'s input stage over the first ``max_tiles`` tiles of every slide (0 / None: all): decode, stain normaliser,
+    ``backbone_u8`` in batches of at most ``batch`` (the engine's ``max_batch`` when None or larger).  ``on_batch(f, g)`` gets each
+    batch's features fp32 [b, 2048] and global tile indices int64 [b], both on the device, in slide order: a tile's index is its
+    index in the UNCLIPPED slide list (``distributed.global_tile_offsets`` of the slides' tile counts), its Philox tile counter in
+    ``evaluate()``.  -> ``(names, index, loc, tiles)``: per kept tile its slide's name, its record's index in the slide, its
+    location int64 [N, 2], and the tiles as read uint8 [N, px, px, 3] (None unless ``keep_tiles``)."""
     import torch
     from . import distributed as D, stain
     stain.check(normalizer, norm_fit)
-    eng = engine_or_pool.engines[0] if hasattr(engine_or_pool, 'engines') else engine_or_pool
-    mc_n = int(mc_n or eng.hp.uq_n)
-    seed = int(eng.hp.seed if seed is None else seed)
     px = int(eng.hp.tile_px)
+    step = int(eng.max_batch if not batch else min(int(batch), eng.max_batch))
     offsets = D.global_tile_offsets([s.n_tiles for s in slides])
-    names, index, locs, tiles, feats, means, stds = [], [], [], [], [], [], []
+    names, index, locs, tiles = [], [], [], []
 
     def flush(batch_tiles, batch_gidx):
         t = torch.from_numpy(np.concatenate(batch_tiles)).to(eng.device)
         g = torch.from_numpy(np.concatenate(batch_gidx)).to(eng.device)
-        for a in range(0, len(t), eng.max_batch):
-            cur = stain.normalise(eng, t[a:a + eng.max_batch].contiguous(), normalizer, norm_fit)
-            f = eng.backbone_u8(cur)
-            m, s = eng.mc_head(f, mc_n, seed, tile_idx0=0, tile_idx=g[a:a + eng.max_batch].contiguous())
-            feats.append(f.cpu().numpy()); means.append(m.cpu().numpy()); stds.append(s.cpu().numpy())
+        for a in range(0, len(t), step):
+            cur = stain.normalise(eng, t[a:a + step].contiguous(), normalizer, norm_fit)
+            on_batch(eng.backbone_u8(cur), g[a:a + step].contiguous())
 
     pend_t, pend_g, pending = [], [], 0
     for si, s in enumerate(slides):
@@ -128,15 +127,32 @@ def generate_features(engine_or_pool, slides, max_tiles=10, mc_n=None, seed=None
         if keep_tiles:
             tiles.append(t)
         pend_t.append(t); pend_g.append(int(offsets[si]) + np.arange(count, dtype=np.int64)); pending += count
-        if pending >= 4 * eng.max_batch:
+        if pending >= 4 * step:
             flush(pend_t, pend_g)
             pend_t, pend_g, pending = [], [], 0
     if pending:
         flush(pend_t, pend_g)
     cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dt)
-    return FeatureMap(names, cat(index, (0,), np.int64), cat(locs, (0, 2), np.int64), cat(feats, (0, 2048), np.float32),
-                      cat(means, (0, 2), np.float32), cat(stds, (0, 2), np.float32),
-                      cat(tiles, (0, px, px, 3), np.uint8) if keep_tiles else None)
+    return names, cat(index, (0,), np.int64), cat(locs, (0, 2), np.int64), cat(tiles, (0, px, px, 3), np.uint8) if keep_tiles else None
+
+
+def generate_features(engine_or_pool, slides, max_tiles=10, mc_n=None, seed=None, norm_fit=None, normalizer='reinhard_fast', keep_tiles=True):
+    """The first ``max_tiles`` tiles of every slide (0 / None: all) through ``backbone_u8`` and ``mc_head`` -> ``FeatureMap``.  The
+    Philox index of a tile is its index in the UNCLIPPED slide list (``walk_features``), so its numbers are exactly the ones
+    ``evaluate()`` over the same slides gives it."""
+    eng = engine_or_pool.engines[0] if hasattr(engine_or_pool, 'engines') else engine_or_pool
+    mc_n = int(mc_n or eng.hp.uq_n)
+    seed = int(eng.hp.seed if seed is None else seed)
+    feats, means, stds = [], [], []
+
+    def head(f, g):
+        m, s = eng.mc_head(f, mc_n, seed, tile_idx0=0, tile_idx=g)
+        feats.append(f.cpu().numpy()); means.append(m.cpu().numpy()); stds.append(s.cpu().numpy())
+
+    names, index, loc, tiles = walk_features(eng, slides, max_tiles, head, norm_fit, normalizer, keep_tiles)
+    cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dt)
+    return FeatureMap(names, index, loc, cat(feats, (0, 2048), np.float32), cat(means, (0, 2), np.float32), cat(stds, (0, 2), np.float32),
+                      tiles)
 
 
 def embed(engine, features, n_neighbors=50, min_dist=0.1, seed=0, n_epochs=None):

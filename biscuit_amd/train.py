@@ -1,0 +1,521 @@
+"""Training the MC-dropout head on cached features, and nested cross-validation down to BISCUIT's thresholds (DESIGN.md section 7
+"Head training"): what ``Experiment.train_nested_cv`` and ``thresholds_from_nested_cv`` (``experiment.py:924-1090``) do, for the layers
+behind the pooled features only -- Slideflow's ``trainable_layers`` configuration -- with the backbone as imported.
+
+    python -m biscuit_amd.train SLIDE.tfrecords ... --labels CSV --model DIR --out DIR
+
+A cohort's features are computed once (``cache_features``: ``evaluate()``'s input stage, then ``bq_backbone_u8``); each of the
+``outer_k * (1 + inner_k)`` trainings then walks that [N, 2048] array on the device (``Engine.head_train_steps``,
+``csrc/kernels_train.hip``) and writes its validation table ``tile_predictions_val_epoch1.csv`` with the reference's headers, from
+which ``thresholds_from_nested_cv`` takes the thresholds through ``threshold.from_cv`` / ``threshold.apply``.
+
+Restated from memory, unpinned against Slideflow: ``TrainParams``' schedule constants and Keras's Adam defaults, the ``k-fold``
+split strategy (``kfold``), the directory names.  Out of scope: training any backbone layer, augmentation (cached features see
+each tile once, unaugmented), class balancing, early stopping, ``validate_on_batch``, TensorFlow checkpoints, multi-GPU training.
+"""
+import argparse
+import json
+import os
+from dataclasses import dataclass, field
+from statistics import mean
+from typing import Optional
+
+import numpy as np
+
+from . import predictions
+
+# the order of the parameter vector the kernels take (include/biscuit_hip.h: bq_head_grad), row-major [K][N]
+HEAD_TENSORS = (('hidden_0/kernel', (2048, 1024)), ('hidden_0/bias', (1024,)), ('hidden_1/kernel', (1024, 1024)),
+                ('hidden_1/bias', (1024,)), ('logits/kernel', (1024, 2)), ('logits/bias', (2,)))
+HEAD_PARAMS = sum(int(np.prod(s)) for _, s in HEAD_TENSORS)            # 3 149 826
+
+# Keras's Adam defaults and Slideflow's schedule form -- restated from memory, unpinned
+ADAM_BETA_1 = 0.9
+ADAM_BETA_2 = 0.999
+ADAM_EPSILON = 1e-7
+LR_STAIRCASE = True
+
+HEAD_FILE = 'head.npz'
+MANIFEST_FILE = 'slides.json'
+
+
+@dataclass
+class TrainParams:
+    """The training fields of ``biscuit/hp.py:7-18`` that ``hp.ModelParams`` omits (restated from memory, unpinned where Slideflow
+    interprets them: the decay is ``lr * decay ** (step // decay_steps)``, a staircase)."""
+    batch_size: int = 128                    # hp.py:7
+    epochs: list = field(default_factory=lambda: [1])       # hp.py:8
+    optimizer: str = 'Adam'                  # hp.py:14
+    learning_rate: float = 1e-4              # hp.py:15
+    learning_rate_decay_steps: int = 512     # hp.py:16
+    learning_rate_decay: float = 0.98        # hp.py:17
+    dropout: float = 0.1                     # hp.py:11
+    loss: str = 'sparse_categorical_crossentropy'           # hp.py:18
+
+    def validate(self):
+        if self.optimizer != 'Adam' or self.loss != 'sparse_categorical_crossentropy':
+            raise ValueError('the head trainer implements Adam on sparse categorical cross-entropy only')
+        if not 1 <= int(self.batch_size) <= 1024 or not self.epochs or min(self.epochs) < 1:
+            raise ValueError('1 <= batch_size <= 1024 and at least one epoch')
+        if not 0.0 <= self.dropout < 1.0 or not self.learning_rate > 0 or self.learning_rate_decay_steps < 1:
+            raise ValueError('dropout in [0, 1), a positive learning rate and decay steps >= 1')
+        return self
+
+    def learning_rate_at(self, step):
+        """The learning rate of global step ``step`` (0-based), float64."""
+        e = step // self.learning_rate_decay_steps if LR_STAIRCASE else step / self.learning_rate_decay_steps
+        return float(self.learning_rate) * float(self.learning_rate_decay) ** e
+
+
+def flatten_head(w):
+    """The six head tensors of a weight dict -> one float32 vector [P] in ``HEAD_TENSORS`` order."""
+    parts = []
+    for name, shape in HEAD_TENSORS:
+        a = np.asarray(w[name], np.float32)
+        if a.shape != shape:
+            raise ValueError(f'{name}: shape {a.shape}, not {shape}')
+        parts.append(a.reshape(-1))
+    return np.concatenate(parts)
+
+
+def unflatten_head(vec):
+    """A vector [P] -> ``{name: float32 array}`` of the six head tensors (copies)."""
+    vec = np.asarray(vec, np.float32).reshape(-1)
+    if vec.size != HEAD_PARAMS:
+        raise ValueError(f'a head has {HEAD_PARAMS} parameters, not {vec.size}')
+    out, at = {}, 0
+    for name, shape in HEAD_TENSORS:
+        n = int(np.prod(shape))
+        out[name] = vec[at:at + n].reshape(shape).copy()
+        at += n
+    return out
+
+
+def glorot_head(seed):
+    """A seeded Glorot-uniform head, drawn on the host: kernels U(-l, l) with l = sqrt(6 / (fan_in + fan_out)), zero biases."""
+    rng = np.random.default_rng([int(seed), 0x676c6f72])
+    out = {}
+    for name, shape in HEAD_TENSORS:
+        if name.endswith('/kernel'):
+            lim = np.sqrt(6.0 / (shape[0] + shape[1]))
+            out[name] = rng.uniform(-lim, lim, shape).astype(np.float32)
+        else:
+            out[name] = np.zeros(shape, np.float32)
+    return out
+
+
+def save_head(path, head):
+    np.savez(path, **{name: np.asarray(head[name], np.float32) for name, _ in HEAD_TENSORS})
+
+
+def load_head(path):
+    with np.load(path) as z:
+        return {name: z[name] for name, _ in HEAD_TENSORS}
+
+
+# ------------------------------------------------------------------------------------------------------------ feature cache
+@dataclass
+class FeatureCache:
+    """A cohort's pooled features: ``feats`` float32 [N, 2048] (a device tensor; a host array once loaded, until ``to``), per tile
+    ``slide_idx`` int64 [N] into ``slides`` (names, in dataset order) and ``loc`` int64 [N, 2].  A tile's row is its index in the
+    cohort's tile list: its Philox tile counter in ``evaluate()``, in ``predict`` and in training."""
+    feats: object
+    slide_idx: np.ndarray
+    loc: np.ndarray
+    slides: list
+
+    def __len__(self):
+        return len(self.slide_idx)
+
+    def rows_of(self, slides):
+        """The rows of the named slides, ascending."""
+        want = np.zeros(len(self.slides), bool)
+        index = {s: i for i, s in enumerate(self.slides)}
+        for s in slides:
+            want[index[s]] = True
+        return np.flatnonzero(want[self.slide_idx]).astype(np.int64)
+
+    def to(self, device):
+        import torch
+        self.feats = torch.as_tensor(np.asarray(self.feats) if not torch.is_tensor(self.feats) else self.feats).to(device).contiguous()
+        return self
+
+    def save(self, path):
+        f = self.feats.cpu().numpy() if hasattr(self.feats, 'cpu') else np.asarray(self.feats)
+        np.savez(path, feats=f.astype(np.float32), slide_idx=self.slide_idx, loc=self.loc, slides=np.array(self.slides, dtype=str))
+
+    @staticmethod
+    def load(path, device=None):
+        with np.load(path) as z:
+            c = FeatureCache(z['feats'].astype(np.float32), z['slide_idx'].astype(np.int64), z['loc'].astype(np.int64),
+                             [str(s) for s in z['slides']])
+        return c.to(device) if device is not None else c
+
+
+def cache_features(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_fit=None, batch=256):
+    """Every tile of ``slides`` through ``evaluate()``'s input stage -- decode, stain normaliser, ``bq_backbone_u8``
+    (``featuremap.walk_features``) -> ``FeatureCache`` with the features on the engine's device."""
+    import torch
+    from .featuremap import walk_features
+    eng = engine_or_pool.engines[0] if hasattr(engine_or_pool, 'engines') else engine_or_pool
+    parts = []
+    names, _, loc, _ = walk_features(eng, slides, 0, lambda f, g: parts.append(f), norm_fit, normalizer, False, batch)
+    feats = torch.cat(parts) if parts else torch.zeros((0, 2048), dtype=torch.float32, device=eng.device)
+    order = [s.name for s in slides]
+    index = {s: i for i, s in enumerate(order)}
+    if len(index) != len(order):
+        raise ValueError('slide names must be unique')
+    return FeatureCache(feats.contiguous(), np.array([index[n] for n in names], np.int64), loc, order)
+
+
+# ------------------------------------------------------------------------------------------------------------ training
+def train_head(engine, cache, rows, labels, *, init='model', params=None, seed=None):
+    """Train the head on ``cache.feats[rows]`` with ``labels`` (0/1 per row) -> ``(head tensor dict, losses float32 [steps])``.
+    ``init='model'`` starts from the engine's imported head, ``'glorot'`` from ``glorot_head(seed)`` (a dict starts from that).
+    Each epoch walks a permutation from ``numpy.random.default_rng([seed, epoch])`` in batches of ``params.batch_size``, the last one
+    short; the dropout pass counter is the global step.  A loss that is not finite raises ``BiscuitHipError``."""
+    import torch
+    from .engine import BiscuitHipError
+    p = (params or TrainParams()).validate()
+    seed = int(engine.hp.seed if seed is None else seed)
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    labels = np.asarray(labels).reshape(-1)
+    if len(rows) < 1 or len(labels) != len(rows) or not np.isin(labels, (0, 1)).all():
+        raise ValueError('train_head: at least one row and a 0/1 label for each')
+    if rows.min() < 0 or rows.max() >= len(cache):
+        raise ValueError('train_head: a row outside the cache')
+    if isinstance(init, dict):
+        start = init
+    elif init == 'model':
+        start = engine.weights
+    elif init == 'glorot':
+        start = glorot_head(seed)
+    else:
+        raise ValueError("init is 'model', 'glorot' or a head tensor dict")
+    dev = engine.device
+    w = torch.from_numpy(flatten_head(start)).to(dev)
+    m, v, g = torch.zeros_like(w), torch.zeros_like(w), torch.empty_like(w)
+    B = int(p.batch_size)
+    losses, step = [], 0
+    for epoch in range(int(max(p.epochs))):
+        order = np.random.default_rng([seed, epoch]).permutation(len(rows))
+        steps = -(-len(order) // B)
+        lr = [p.learning_rate_at(step + i) for i in range(steps)]
+        out = engine.head_train_steps(w, m, v, cache.feats, torch.from_numpy(rows[order]).to(dev),
+                                      torch.from_numpy(labels[order].astype(np.uint8)).to(dev), B, step, seed, lr, rate=p.dropout,
+                                      b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g)
+        losses.append(out.cpu().numpy())
+        step += steps
+    losses = np.concatenate(losses)
+    if not np.isfinite(losses).all():
+        raise BiscuitHipError(f'train_head: the loss of step {int(np.flatnonzero(~np.isfinite(losses))[0])} is not finite '
+                              '(a feature that is not finite, or a diverged run)')
+    return unflatten_head(w.cpu().numpy()), losses
+
+
+def head_engine(engine, head):
+    """A fresh engine of ``engine``'s configuration whose head is ``head`` (through ``weights.pack_blob``, like any other)."""
+    from .engine import Engine
+    return Engine({**engine.weights, **{name: np.asarray(head[name], np.float32) for name, _ in HEAD_TENSORS}}, hp=engine.hp,
+                  dtype=engine.dtype, max_batch=engine.max_batch, max_mc=engine.max_mc, device=engine.device.index, act_exp=engine.act_exp)
+
+
+def predict(engine, cache, rows, head=None, mc_n=30, seed=None, *, y_true=None, outcome='cohort', save_dir=None,
+            table_name=predictions.VAL_NAME):
+    """The tile table of ``cache``'s rows ``rows`` under ``head`` (None: the engine's own): ``Engine.mc_head`` on the cached features
+    with the rows as per-tile Philox indices, ``mc_n`` passes -> ``predictions.tile_frame``'s DataFrame (Slideflow's headers);
+    written through ``predictions.write_tile_table`` into ``save_dir`` when given.  ``y_true``: 0/1 per slide of the cache (a
+    sequence in ``cache.slides`` order or a dict by name; default 0)."""
+    import torch
+    seed = int(engine.hp.seed if seed is None else seed)
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    if len(rows) and (rows.min() < 0 or rows.max() >= len(cache)):
+        raise ValueError('predict: a row outside the cache')
+    if int(mc_n) > engine.max_mc:
+        raise ValueError(f'predict: mc_n {mc_n} above the engine\'s max_mc {engine.max_mc}')
+    eng = engine if head is None else head_engine(engine, head)
+    try:
+        means, stds = [], []
+        ridx = torch.from_numpy(rows).to(eng.device)
+        for a in range(0, len(rows), eng.max_batch):
+            r = ridx[a:a + eng.max_batch].contiguous()
+            mu, sd = eng.mc_head(cache.feats.index_select(0, r).contiguous(), int(mc_n), seed, tile_idx0=0, tile_idx=r)
+            means.append(mu.cpu().numpy()); stds.append(sd.cpu().numpy())
+    finally:
+        if eng is not engine:
+            eng.close()
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros((0, 2), np.float32)
+    if y_true is None:
+        y_slide = np.zeros(len(cache.slides), np.int64)
+    elif isinstance(y_true, dict):
+        y_slide = np.array([int(y_true[s]) for s in cache.slides], np.int64)
+    else:
+        y_slide = np.asarray(y_true, np.int64)
+    sidx = cache.slide_idx[rows]
+    df = predictions.tile_frame(outcome, [cache.slides[i] for i in sidx], y_slide[sidx], cat(means), cat(stds), cache.loc[rows])
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        predictions.write_tile_table(df, save_dir, table_name, outcome)
+    return df
+
+
+class HeadTrainer:
+    """The trainer ``train_cv`` calls per fold: ``(train_rows, val_rows, seed) -> (validation table, head)`` -- ``train_head`` on
+    the training rows, ``predict`` on the validation rows."""
+
+    def __init__(self, engine, cache, slide_labels, *, params=None, init='model', mc_n=None, outcome='cohort'):
+        self.engine, self.cache, self.params, self.init, self.outcome = engine, cache, params, init, outcome
+        self.mc_n = int(mc_n or engine.hp.uq_n)
+        self.y_slide = np.array([int(slide_labels[s]) for s in cache.slides], np.int64)
+        self.losses = []
+
+    def __call__(self, train_rows, val_rows, seed):
+        head, losses = train_head(self.engine, self.cache, train_rows, self.y_slide[self.cache.slide_idx[train_rows]], init=self.init,
+                                  params=self.params, seed=seed)
+        self.losses.append(losses)
+        return predict(self.engine, self.cache, val_rows, head, self.mc_n, seed, y_true=self.y_slide, outcome=self.outcome), head
+
+
+# ------------------------------------------------------------------------------------------------------------ cross-validation
+def kfold(patients, labels, k, seed):
+    """Slideflow's ``k-fold`` strategy, restated from memory (unpinned): the patients of each class, sorted by name, are shuffled by
+    one generator ``numpy.random.default_rng(seed)`` (classes in sorted order) and dealt round-robin into ``k`` folds, each class
+    starting where the previous one stopped.  ``labels``: patient -> class.  -> ``k`` sorted lists of patients; ValueError unless
+    every class has at least ``k`` patients, so that every class is in every fold."""
+    patients = sorted(set(patients))
+    k = int(k)
+    if k < 2:
+        raise ValueError('k-fold needs k >= 2')
+    rng = np.random.default_rng(seed)
+    folds, at = [[] for _ in range(k)], 0
+    for c in sorted({labels[p] for p in patients}):
+        names = [p for p in patients if labels[p] == c]
+        if len(names) < k:
+            raise ValueError(f'class {c!r} has {len(names)} patients, fewer than k = {k}')
+        for i in rng.permutation(len(names)):
+            folds[at % k].append(names[int(i)])
+            at += 1
+    return [sorted(f) for f in folds]
+
+
+def _patient_labels(slide_labels, patients):
+    """{patient: label}; ValueError for a patient whose slides disagree."""
+    out = {}
+    for s, y in slide_labels.items():
+        p = patients.get(s, s)
+        if out.setdefault(p, y) != y:
+            raise ValueError(f'patient {p!r} has slides of both classes')
+    return out
+
+
+def fold_dir(out, label, k):
+    return os.path.join(out, f'{label}-kfold{k}')
+
+
+def train_cv(cache, slide_labels, out, label, k, trainer, *, patients=None, seed=0, restrict=None, outcome='cohort'):
+    """``k``-fold cross-validation by patient over the cache's labelled slides (``restrict``: only these patients): fold ``j``
+    trains on the other folds' slides and validates on its own -> ``OUT/LABEL-kfoldJ/tile_predictions_val_epoch1.csv`` with
+    ``head.npz`` (when the trainer returns a head) and ``slides.json`` (the training and validation slides) beside it.
+    ``trainer(train_rows, val_rows, seed)`` -> ``(tile table, head or None)``: a ``HeadTrainer``.  -> the fold directories."""
+    patients = patients or {}
+    slide_labels = {s: slide_labels[s] for s in cache.slides if s in slide_labels}
+    plabel = _patient_labels(slide_labels, patients)
+    if restrict is not None:
+        plabel = {p: y for p, y in plabel.items() if p in set(restrict)}
+    folds = kfold(list(plabel), plabel, k, seed)
+    by_patient = {}
+    for s in slide_labels:
+        by_patient.setdefault(patients.get(s, s), []).append(s)
+    dirs = []
+    for j, val_p in enumerate(folds, 1):
+        val_s = sorted(s for p in val_p for s in by_patient[p])
+        train_s = sorted(s for f in folds if f is not val_p for p in f for s in by_patient[p])
+        fold_seed = int(np.random.SeedSequence([*(int(v) for v in np.atleast_1d(seed)), j]).generate_state(1, np.uint32)[0])
+        table, head = trainer(cache.rows_of(train_s), cache.rows_of(val_s), fold_seed)
+        d = fold_dir(out, label, j)
+        os.makedirs(d, exist_ok=True)
+        predictions.write_tile_table(table, d, predictions.VAL_NAME, outcome)
+        if head is not None:
+            save_head(os.path.join(d, HEAD_FILE), head)
+        with open(os.path.join(d, MANIFEST_FILE), 'w') as f:
+            json.dump({'training': train_s, 'validation': val_s}, f)
+        dirs.append(d)
+    return dirs
+
+
+def train_nested_cv(cache, slide_labels, out, label, trainer, *, outer_k=3, inner_k=5, patients=None, seed=0, outcome='cohort'):
+    """``Experiment.train_nested_cv`` (``experiment.py:1053-1090``) and the outer folds it expects: ``LABEL-kfoldK`` for K = 1 ..
+    ``outer_k``, and over the training patients of each an inner ``inner_k``-fold ``LABEL-kK-kfoldJ``.  -> every directory."""
+    patients = patients or {}
+    dirs = train_cv(cache, slide_labels, out, label, outer_k, trainer, patients=patients, seed=seed, outcome=outcome)
+    for K, d in enumerate(list(dirs), 1):
+        with open(os.path.join(d, MANIFEST_FILE)) as f:
+            train_s = json.load(f)['training']
+        dirs += train_cv(cache, slide_labels, out, f'{label}-k{K}', inner_k, trainer, patients=patients, seed=[int(seed), K],
+                         restrict={patients.get(s, s) for s in train_s}, outcome=outcome)
+    return dirs
+
+
+def check_nested_split(slide_labels, patients, outer_k, inner_k, seed):
+    """The splits ``train_nested_cv`` will make, made without training anything: ValueError where a patient has slides of both
+    classes or a class has fewer patients than folds, in the outer split or in any inner one."""
+    patients = patients or {}
+    plabel = _patient_labels(slide_labels, patients)
+    for K, val in enumerate(kfold(list(plabel), plabel, outer_k, seed), 1):
+        inner = {p: y for p, y in plabel.items() if p not in set(val)}
+        try:
+            kfold(list(inner), inner, inner_k, [int(seed), K])
+        except ValueError as e:
+            raise ValueError(f'inner split of outer fold {K}: {e}') from None
+
+
+def _cv_frames(out, label, k, outcome, patients):
+    """``utils.df_from_cv``: the ``k`` validation tables of ``LABEL-kfold1 .. k``, renamed, with a patient column; None when one is
+    missing."""
+    dfs = []
+    for j in range(1, k + 1):
+        path = os.path.join(fold_dir(out, label, j), predictions.VAL_NAME)
+        if not os.path.exists(path):
+            return None
+        df = predictions.load_tile_predictions(path, outcome)
+        if 'patient' not in df.columns:
+            df['patient'] = df['slide'].map(lambda s: patients.get(s, s))
+        dfs.append(df)
+    return dfs
+
+
+def thresholds_from_nested_cv(out, label, *, outcome='cohort', patients=None, outer_k=3, inner_k=5, id=None, threshold_params=None,
+                              slides=()):
+    """``Experiment.thresholds_from_nested_cv`` (``experiment.py:924-1026``) over the tables ``train_nested_cv`` wrote: per outer
+    fold, tile_uq from the inner folds (``threshold.from_cv``), then slide_uq and the prediction thresholds, applied to the outer
+    fold's validation table at the patient and the slide level.  An outer fold whose tables are missing is skipped.  ``patients``:
+    slide -> patient (a slide missing from it is its own patient; ``slides`` names further slides to cover).  -> ``(frame with the
+    columns id, n_slides, fold, uq, patient_auc, patient_uq_perc, slide_auc, slide_uq_perc; {'tile_uq', 'slide_uq', 'slide_pred'}:
+    the folds' means, None without a fold)``."""
+    import pandas as pd
+    from . import threshold
+    patients = dict(patients or {})
+    id = label if id is None else id
+    rows, all_tile, all_slide, all_pred = [], [], [], []
+    for K in range(1, outer_k + 1):
+        val_path = os.path.join(fold_dir(out, label, K), predictions.VAL_NAME)
+        dfs = _cv_frames(out, f'{label}-k{K}', inner_k, outcome, patients)
+        if dfs is None or not os.path.exists(val_path):
+            continue
+        tile_df = predictions.load_tile_predictions(val_path, outcome)
+        pmap = {s: patients.get(s, s) for df in dfs + [tile_df] for s in pd.unique(df['slide'])}
+        pmap.update({s: patients.get(s, s) for s in slides})
+        params = threshold_params if threshold_params is not None else {'tile_pred': 'detect', 'slide_pred': 'detect', 'plot': False,
+                                                                        'patients': pmap}
+        tile_uq = threshold.from_cv(dfs, tile_uq='detect', slide_uq=None, **params)['tile_uq']
+        th = threshold.from_cv(dfs, tile_uq=tile_uq, slide_uq='detect', **params)
+        all_tile.append(tile_uq); all_slide.append(th['slide_uq']); all_pred.append(th['slide_pred'])
+        by_level = {}
+        for level in ('patient', 'slide'):
+            res, _ = threshold.apply(tile_df, plot=False, patients=pmap, level=level, **th)
+            by_level[level] = (res['auc'], res['percent_incl'])
+        manifest = os.path.join(fold_dir(out, label, K), MANIFEST_FILE)
+        n_slides = None
+        if os.path.exists(manifest):
+            with open(manifest) as f:
+                man = json.load(f)
+            n_slides = len(man['training']) + len(man['validation'])
+        rows.append({'id': id, 'n_slides': n_slides, 'fold': K, 'uq': 'include', 'patient_auc': by_level['patient'][0],
+                     'patient_uq_perc': by_level['patient'][1], 'slide_auc': by_level['slide'][0], 'slide_uq_perc': by_level['slide'][1]})
+    frame = pd.DataFrame(rows, columns=['id', 'n_slides', 'fold', 'uq', 'patient_auc', 'patient_uq_perc', 'slide_auc', 'slide_uq_perc'])
+    return frame, {'tile_uq': mean(all_tile) if all_tile else None, 'slide_uq': mean(all_slide) if all_slide else None,
+                   'slide_pred': mean(all_pred) if all_pred else None}
+
+
+# ------------------------------------------------------------------------------------------------------------ command line
+def read_labels(path):
+    """``--labels CSV``: columns slide, label and optionally patient; the two label values, sorted, become 0 and 1.
+    -> ``(slide -> 0/1, slide -> patient, [the two values])``."""
+    import pandas as pd
+    try:
+        df = pd.read_csv(path, dtype=str)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f'--labels {path}: {e}') from None
+    if 'slide' not in df.columns or 'label' not in df.columns:
+        raise SystemExit(f'--labels {path}: needs the columns slide and label')
+    values = sorted(set(df['label']))
+    if len(values) != 2:
+        raise SystemExit(f'--labels {path}: exactly two label values, not {values}')
+    labels = {s: values.index(v) for s, v in zip(df['slide'], df['label'])}
+    patients = dict(zip(df['slide'], df['patient'])) if 'patient' in df.columns else {}
+    return labels, patients, values
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m biscuit_amd.train', description=__doc__.split('\n\n')[0])
+    ap.add_argument('tfrecords', nargs='+', help='Slideflow *.tfrecords, one per slide')
+    ap.add_argument('--labels', required=True, help='CSV with slide,label[,patient]')
+    ap.add_argument('--model', required=True, help='Slideflow model directory: the backbone (and, with --init model, the head to start from)')
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--label', default='EXP', help='experiment label: the prefix of the fold directories')
+    ap.add_argument('--outcome', default='cohort')
+    ap.add_argument('--init', default='model', choices=['model', 'glorot'])
+    ap.add_argument('--epochs', type=int, default=1)
+    ap.add_argument('--outer-k', type=int, default=3)
+    ap.add_argument('--inner-k', type=int, default=5)
+    ap.add_argument('--seed', type=int, default=1234)
+    ap.add_argument('--mc', type=int, default=None, help='MC-dropout passes of the validation tables (default: uq_n of the model, 30)')
+    ap.add_argument('--dtype', default='f16', choices=['f16', 'bf16', 'f32'])
+    args = ap.parse_args(argv)
+    if args.epochs < 1 or args.outer_k < 2 or args.inner_k < 2:
+        raise SystemExit('--epochs >= 1, --outer-k >= 2 and --inner-k >= 2')
+    if not os.path.isdir(args.model):
+        raise SystemExit(f'--model {args.model}: not a directory')
+    missing = [p for p in args.tfrecords if not os.path.exists(p)]
+    if missing:
+        raise SystemExit(f'no such file: {missing[0]}')
+    labels, patients, values = read_labels(args.labels)
+    names = [os.path.splitext(os.path.basename(p))[0] for p in args.tfrecords]
+    unlabelled = [n for n in names if n not in labels]
+    if unlabelled:
+        raise SystemExit(f'--labels {args.labels}: no label for slide {unlabelled[0]!r}')
+    try:
+        check_nested_split({n: labels[n] for n in names}, patients, args.outer_k, args.inner_k, args.seed)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    from .__main__ import load_model_weights, model_hp_from
+    from .engine import Engine
+    from .featuremap import _first_records
+    from .inference import slides_from_tfrecords
+    w, model_params = load_model_weights(args.model, None)
+    hp, norm_fit = model_hp_from(model_params, None)
+    slides = slides_from_tfrecords(list(args.tfrecords), labels, patients or None, gpu_unfilter=False)
+    act_exp = None
+    if args.dtype == 'f16' and any(s.n_tiles for s in slides):
+        first = next(s for s in slides if s.n_tiles)
+        probe, _ = _first_records(first, min(16, first.n_tiles), hp.tile_px)
+        act_exp, _ = Engine.calibrate(w, probe, hp=hp, norm_fit=norm_fit, normalizer=hp.normalizer)
+    mc_n = int(args.mc or hp.uq_n)
+    eng = Engine(w, hp=hp, dtype=args.dtype, max_batch=256, max_mc=mc_n, act_exp=act_exp)
+    try:
+        cache = cache_features(eng, slides, normalizer=hp.normalizer, norm_fit=norm_fit)
+        trainer = HeadTrainer(eng, cache, labels, params=TrainParams(epochs=[args.epochs], dropout=hp.dropout), init=args.init, mc_n=mc_n,
+                              outcome=args.outcome)
+        try:
+            dirs = train_nested_cv(cache, labels, args.out, args.label, trainer, outer_k=args.outer_k, inner_k=args.inner_k,
+                                   patients=patients, seed=args.seed, outcome=args.outcome)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+    finally:
+        eng.close()
+    from .errors import ThresholdError
+    try:
+        frame, th = thresholds_from_nested_cv(args.out, args.label, outcome=args.outcome, patients=patients, outer_k=args.outer_k,
+                                              inner_k=args.inner_k)
+    except ThresholdError as e:
+        raise SystemExit(f'the validation tables are written under {args.out}, but no thresholds: {e} (threshold.from_cv found none in '
+                         'any inner fold of an outer fold: too few slides, or none predicted wrongly)') from None
+    frame.to_csv(os.path.join(args.out, 'nested_cv.csv'), index=False)
+    th = {k: (None if v is None else float(v)) for k, v in th.items()}
+    with open(os.path.join(args.out, 'thresholds.json'), 'w') as f:
+        json.dump({'thresholds': th, 'label_values': values, 'outer_k': args.outer_k, 'inner_k': args.inner_k, 'seed': args.seed}, f, indent=1)
+    print(json.dumps({'tiles': len(cache), 'slides': len(cache.slides), 'folds': len(dirs), 'thresholds': th}))
+
+
+if __name__ == '__main__':
+    main()

@@ -628,6 +628,41 @@ int64_t bq_delong_chunk_rows(int64_t n);
 int bq_delong(bq_ctx* ctx, const double* d_scores, const uint8_t* d_label, int k, int64_t n, void* d_ws, size_t ws_bytes, double* d_out,
               double* d_V, bq_stream_t stream);
 
+/* Training the MC-dropout head on cached features (kernels_train.hip; DESIGN.md section 7 "Head training"): features [.][2048] ->
+ * Dense 1024 + ReLU -> Dense 1024 + ReLU -> Dense 2 -> softmax with inverted dropout on the input of each layer, the head of
+ * bq_mc_head in plain fp32.  d_params, d_m, d_v, d_grad: float32 [P], P = 3 149 826, caller-owned, 16-byte aligned, in the order
+ * hidden_0/kernel [2048][1024], hidden_0/bias [1024], hidden_1/kernel [1024][1024], hidden_1/bias [1024], logits/kernel [1024][2],
+ * logits/bias [2] (row-major [K][N]).  The weights a context loaded are neither read nor changed.
+ *
+ * bq_head_grad: the gradient of the mean sparse categorical cross-entropy over the n rows d_feats[d_rows[i]] (d_feats float32
+ * [n_feat][2048], d_rows int64 [n], d_labels uint8 [n] in {0, 1}; 1 <= n <= 1024; the rows are gathered by the kernels) -> d_grad
+ * [P] and d_loss [1].  The keep mask of unit u of layer l is Philox4x32-10 with counter (u / 4, l, step, d_rows[i]) and key seed,
+ * keep = r >= floor(rate 2^32), scale fp32(1 / (1 - rate)): the contract of bq_mc_head with pass = step and tile = the row's index;
+ * the backward pass draws the masks again.  ReLU's derivative is 0 at 0.  A feature that is not finite, a row index outside
+ * 0 .. n_feat - 1 (never read) or a label above 1 gives a NaN loss.  Every sum runs in a fixed order and there are no floating-point
+ * atomics: the same bits every call.
+ *
+ * bq_head_adam: one pass of Keras Adam over P, t = step + 1: m' = b1 m + (1 - b1) g, v' = b2 v + (1 - b2) g^2,
+ * w' = w - lr sqrt(1 - b2^t) / (1 - b1^t) m' / (sqrt(v') + eps), evaluated in float64 per element and rounded once per stored value.
+ *
+ * bq_head_train_steps: `steps` pairs of the two above, step = step0 + i, over d_rows / d_labels [steps][batch] (the last step takes its
+ * first last_n entries, 1 <= last_n <= batch), learning rate h_lr[i] (host memory, read before the call returns), loss of step i to
+ * d_losses[i]: one linear chain of launches on `stream`, the same bits as the single calls.
+ *
+ * d_ws: bq_head_train_workspace_bytes(n) bytes (n = batch; 0 for an n the calls refuse), 256-byte aligned, caller-owned, contents
+ * unspecified on entry; BQ_ERR_WORKSPACE below that.  All allocate nothing and are enqueued without a host synchronisation; a bad
+ * argument is BQ_ERR_ARG with nothing enqueued. */
+size_t bq_head_train_workspace_bytes(int n);
+int bq_head_grad(bq_ctx* ctx, const float* d_params, const float* d_feats, int64_t n_feat, const int64_t* d_rows, const uint8_t* d_labels,
+                 int n, int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, void* d_ws, size_t ws_bytes,
+                 bq_stream_t stream);
+int bq_head_adam(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, const float* d_grad, int64_t step, double lr, double b1, double b2,
+                 double eps, bq_stream_t stream);
+int bq_head_train_steps(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, float* d_grad, const float* d_feats, int64_t n_feat,
+                        const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n, int64_t step0, uint64_t seed,
+                        double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws, size_t ws_bytes,
+                        bq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

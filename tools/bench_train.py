@@ -1,0 +1,122 @@
+"""Measure head training on an MI355X (DESIGN.md section 7 "Head training"; the record is profiles/train_head.txt):
+
+    python tools/bench_train.py [--steps 200] [--batch 128] [--cache-slides 8] [--cache-tiles 512] [--cv-slides 64] [--cv-tiles 200]
+
+* microseconds per training step at the given batch (wall time of ``Engine.head_train_steps`` over ``--steps`` steps after a warm-up
+  call, one synchronisation at the end), and the split between the launches from the library's own profiling classes;
+* the feature-cache rate: ``train.cache_features`` over resident synthetic slides, tiles per second (host decode is not part of it:
+  the tiles are in memory, as in ``bench.py``);
+* wall time of ``train_nested_cv`` (3 x (1 + 5) trainings with their validation tables) and ``thresholds_from_nested_cv`` over a
+  synthetic cohort of cached features.
+
+Records, not bars: nothing of the kind exists to compare with.  Prints one JSON line per measurement.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from biscuit_amd import train as T                      # noqa: E402
+from biscuit_amd.engine import Engine                   # noqa: E402
+from biscuit_amd.feed import Slide                      # noqa: E402
+from biscuit_amd.synthetic import make_tiles            # noqa: E402
+from biscuit_amd.weights import synthetic_weights       # noqa: E402
+
+
+def bench_steps(eng, steps, batch):
+    dev = eng.device
+    rng = np.random.default_rng(1)
+    feats = torch.from_numpy(np.abs(rng.standard_normal((8192, 2048))).astype(np.float32)).to(dev)
+    rows = torch.from_numpy(rng.integers(0, 8192, steps * batch)).to(dev)
+    labels = torch.from_numpy(rng.integers(0, 2, steps * batch).astype(np.uint8)).to(dev)
+    w = torch.from_numpy(T.flatten_head(T.glorot_head(1))).to(dev)
+    m, v = torch.zeros_like(w), torch.zeros_like(w)
+    lr = [1e-4] * steps
+    eng.head_train_steps(w, m, v, feats, rows, labels, batch, 0, 1, lr)
+    torch.cuda.synchronize(dev)
+    walls = []
+    for r in range(3):
+        t0 = time.perf_counter()
+        eng.head_train_steps(w, m, v, feats, rows, labels, batch, (r + 1) * steps, 1, lr)
+        torch.cuda.synchronize(dev)
+        walls.append((time.perf_counter() - t0) / steps * 1e6)
+    eng.profile_enable(True)
+    eng.head_train_steps(w, m, v, feats, rows, labels, batch, 4 * steps, 1, lr)
+    torch.cuda.synchronize(dev)
+    split = {p.name: round(p.ms / max(p.launches, 1) * 1e3, 2) for p in eng.profile_read() if p.name.startswith('head_train_')}
+    eng.profile_enable(False)
+    grad = sum(us for name, us in split.items() if name != 'head_train_adam')
+    return {'measure': 'train_step', 'batch': batch, 'steps': steps, 'us_per_step_wall_median': round(float(np.median(walls)), 1),
+            'us_per_step_wall_runs': [round(x, 1) for x in walls], 'us_per_launch_by_class': split, 'us_grad_launches': round(grad, 1),
+            'us_adam_launch': split.get('head_train_adam')}
+
+
+def bench_cache(eng, n_slides, n_tiles):
+    tiles = make_tiles(n_tiles, seed=7)
+    slides = [Slide(f's{i}', tiles, n_tiles, y_true=i % 2) for i in range(n_slides)]
+    T.cache_features(eng, slides[:1])
+    torch.cuda.synchronize(eng.device)
+    t0 = time.perf_counter()
+    cache = T.cache_features(eng, slides)
+    torch.cuda.synchronize(eng.device)
+    wall = time.perf_counter() - t0
+    return {'measure': 'feature_cache', 'slides': n_slides, 'tiles': len(cache), 'wall_s': round(wall, 3),
+            'tiles_per_s': round(len(cache) / wall, 1), 'note': 'resident host tiles, upload included, no decode, no stain normaliser'}
+
+
+def bench_cv(eng, n_slides, n_tiles, mc_n):
+    rng = np.random.default_rng(3)
+    slides = [f's{i:03d}' for i in range(n_slides)]
+    labels = {s: i % 2 for i, s in enumerate(slides)}
+    sidx = np.repeat(np.arange(n_slides), n_tiles).astype(np.int64)
+    f = np.abs(rng.standard_normal((len(sidx), 2048))).astype(np.float32)
+    f[sidx % 2 == 1] += np.float32(0.05) * (np.arange(2048) % 2 == 0)
+    loc = np.stack([np.arange(len(sidx)), np.zeros(len(sidx), np.int64)], 1).astype(np.int64)
+    cache = T.FeatureCache(torch.from_numpy(f).to(eng.device), sidx, loc, slides)
+    trainer = T.HeadTrainer(eng, cache, labels, init='glorot', mc_n=mc_n)
+    with tempfile.TemporaryDirectory() as out:
+        t0 = time.perf_counter()
+        dirs = T.train_nested_cv(cache, labels, out, 'EXP', trainer, outer_k=3, inner_k=5, seed=1)
+        torch.cuda.synchronize(eng.device)
+        t_train = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        try:
+            _, th = T.thresholds_from_nested_cv(out, 'EXP', outer_k=3, inner_k=5)
+            th = {k: (None if v is None else float(v)) for k, v in th.items()}
+        except Exception as e:                                  # noqa: BLE001 -- a record of what happened, not a test
+            th = repr(e)
+        t_th = time.perf_counter() - t0
+    return {'measure': 'nested_cv', 'slides': n_slides, 'tiles_per_slide': n_tiles, 'trainings': len(dirs), 'mc_n': mc_n,
+            'steps_total': int(sum(len(x) for x in trainer.losses)), 'train_and_tables_wall_s': round(t_train, 2),
+            'thresholds_wall_s': round(t_th, 2), 'thresholds': th}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    ap.add_argument('--steps', type=int, default=200)
+    ap.add_argument('--batch', type=int, default=128)
+    ap.add_argument('--cache-slides', type=int, default=8)
+    ap.add_argument('--cache-tiles', type=int, default=512)
+    ap.add_argument('--cv-slides', type=int, default=64)
+    ap.add_argument('--cv-tiles', type=int, default=200)
+    ap.add_argument('--mc', type=int, default=30)
+    args = ap.parse_args(argv)
+    eng = Engine(synthetic_weights(1), dtype='f16', max_batch=256, max_mc=args.mc)
+    try:
+        print(json.dumps(bench_steps(eng, args.steps, args.batch)), flush=True)
+        if args.cache_slides > 0:
+            print(json.dumps(bench_cache(eng, args.cache_slides, args.cache_tiles)), flush=True)
+        if args.cv_slides > 0:
+            print(json.dumps(bench_cv(eng, args.cv_slides, args.cv_tiles, args.mc)), flush=True)
+    finally:
+        eng.close()
+
+
+if __name__ == '__main__':
+    main()
