@@ -53,6 +53,8 @@ ABI = {
     'bq_jpeg_encode': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     'bq_png_encode_scratch_bytes': (_sz, [_i, _i]),
     'bq_png_encode': (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    'bq_augment_scratch_bytes': (_sz, [_i, _i]),
+    'bq_augment': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'bq_tile_resample': (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     'bq_tile_grayspace': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'bq_heatmap_render': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _f, _i, _vp]),

@@ -130,7 +130,7 @@ class Engine:
         """Lets go of every device buffer grown on demand -- the network's workspace and each tool's scratch -- and of nothing else;
         the next call that wants one allocates it again."""
         self._ws = None                  # the network's workspace (``_ws_for``)
-        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong, train
+        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong, train, augment
 
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
@@ -479,6 +479,42 @@ class Engine:
         """Scratch for ``png_encode`` over ``n`` tiles (``bq_png_encode_scratch_bytes``: 1.71 MB per 299-px tile, for 128 tiles at
         most -- 218 MB; a longer call works in rounds)."""
         return self._bytes(self._lib.bq_png_encode_scratch_bytes(int(n), int(px)))
+
+    def augment(self, tiles_u8, params, out=None, status=None, scratch=None):
+        """Slideflow's training augmentation 'xyrjb' on the device (``bq_augment``, kernels_augment.hip): ``tiles_u8`` uint8 NHWC
+        [n, px, px, 3] on this device, 8 <= px <= 4096, and ``params`` uint8 [n, 4] = (k, flips, quality, blur) per tile
+        (``augment.draw``) -> ``(tiles, status)``: ``blur(flip_ud(flip_lr(rot90^k(jpeg_quality(tile)))))``, the bytes
+        ``augment.apply_host`` gives, and status int32 [n] on the device (0, or 1 where the JPEG round trip left its exact range).
+        ``params`` on the host is checked (ValueError for a byte out of range) and uploaded; a device tensor is taken as it is,
+        and a row out of range there leaves its tile unchanged with status 2.  ``out`` (must not overlap ``tiles_u8``) and
+        ``status``: tensors to write into.  ``scratch``: ``augment_scratch(n, px)`` or smaller (more rounds), at least one
+        tile's.  The all-zero row is the identity."""
+        from . import augment as A
+        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous() and tiles_u8.dim() == 4
+        assert tiles_u8.shape[1] == tiles_u8.shape[2] and tiles_u8.shape[3] == 3, tuple(tiles_u8.shape)
+        n, px = int(tiles_u8.shape[0]), int(tiles_u8.shape[1])
+        if not A.MIN_PX <= px <= A.MAX_PX:
+            raise ValueError(f'the augmenter takes tiles of {A.MIN_PX} .. {A.MAX_PX} px, not {px}')
+        if not torch.is_tensor(params):
+            params = torch.from_numpy(A.check_params(params, n)).to(self.device)
+        self._on_device('params', params)
+        assert params.dtype == torch.uint8 and params.is_contiguous() and tuple(params.shape) == (n, 4)
+        if out is None:
+            out = torch.empty_like(tiles_u8)
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == tuple(tiles_u8.shape)
+        assert status.dtype == torch.int32 and status.is_cuda and status.is_contiguous() and tuple(status.shape) == (n,)
+        scratch = self._scratch('augment', int(self._lib.bq_augment_scratch_bytes(n, px)), scratch)
+        assert scratch.is_cuda and scratch.is_contiguous()
+        self._check(self._lib.bq_augment(self._ctx, _ptr(tiles_u8), n, px, _ptr(params), _ptr(out), _ptr(status), _ptr(scratch),
+                                         scratch.numel() * scratch.element_size(), self._stream()))
+        return out, status
+
+    def augment_scratch(self, n, px=TILE_PX):
+        """Scratch for ``augment`` over ``n`` tiles (``bq_augment_scratch_bytes``: 1.09 MB per 299-px tile, for 256 tiles at most --
+        279 MB; a longer call works in rounds)."""
+        return self._bytes(self._lib.bq_augment_scratch_bytes(int(n), int(px)))
 
     def tile_resample(self, canvas, origin, src_px, px=TILE_PX, out=None):
         """The heatmap's tile grid cut from a slide canvas and resampled on the device (``bq_tile_resample``,

@@ -59,6 +59,9 @@ ABI = {
     'bqio_jpeg_encode_last_error': (C.c_char_p, []),
     'bqio_png_encode': (_i, [_vp, _i64, _i, _vp, C.c_size_t, _vp, _vp]),
     'bqio_png_encode_last_error': (C.c_char_p, []),
+    'bqio_augment': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i]),
+    'bqio_augment_blur_weights': (_i, [_i, _vp]),
+    'bqio_augment_last_error': (C.c_char_p, []),
     'bqio_masked_crc32c': (C.c_uint32, [C.c_char_p, C.c_size_t]),
     'bqio_inflate': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t]),
     'bqio_inflate2': (_i, [C.c_char_p, C.c_size_t, _vp, C.c_size_t, C.c_char_p, C.c_size_t, _vp, C.c_size_t,

@@ -9,9 +9,15 @@ A cohort's features are computed once (``cache_features``: ``evaluate()``'s inpu
 ``csrc/kernels_train.hip``) and writes its validation table ``tile_predictions_val_epoch1.csv`` with the reference's headers, from
 which ``thresholds_from_nested_cv`` takes the thresholds through ``threshold.from_cv`` / ``threshold.apply``.
 
+Augmentation (``--augment xyrjb``, what ``biscuit/hp.py:23`` trains with): ``cache_features(augment=..., views=V)`` also caches V
+augmented views of every tile -- ``Engine.augment`` (``bq_augment``, ``csrc/kernels_augment.hip``) with the per-tile draws of
+``augment.draw(N, spec, seed, v)`` in front of the stain normaliser -- and epoch ``e`` of a training reads view ``e % V``.
+Validation and ``predict`` read the unaugmented features, as Slideflow validates unaugmented.
+
 Restated from memory, unpinned against Slideflow: ``TrainParams``' schedule constants and Keras's Adam defaults, the ``k-fold``
-split strategy (``kfold``), the directory names.  Out of scope: training any backbone layer, augmentation (cached features see
-each tile once, unaugmented), class balancing, early stopping, ``validate_on_batch``, TensorFlow checkpoints, multi-GPU training.
+split strategy (``kfold``), the directory names, the augmentation's probabilities and order (``augment.py``).  Out of scope:
+training any backbone layer, Slideflow's stain augmentation ``n``, class balancing, early stopping, ``validate_on_batch``,
+TensorFlow checkpoints, multi-GPU training.
 """
 import argparse
 import json
@@ -51,8 +57,11 @@ class TrainParams:
     learning_rate_decay: float = 0.98        # hp.py:17
     dropout: float = 0.1                     # hp.py:11
     loss: str = 'sparse_categorical_crossentropy'           # hp.py:18
+    augment: str = ''                        # hp.py:23 sets 'xyrjb'; '' trains on the unaugmented features, bit for bit as before
 
     def validate(self):
+        from . import augment as A
+        A.parse(self.augment)
         if self.optimizer != 'Adam' or self.loss != 'sparse_categorical_crossentropy':
             raise ValueError('the head trainer implements Adam on sparse categorical cross-entropy only')
         if not 1 <= int(self.batch_size) <= 1024 or not self.epochs or min(self.epochs) < 1:
@@ -118,11 +127,16 @@ def load_head(path):
 class FeatureCache:
     """A cohort's pooled features: ``feats`` float32 [N, 2048] (a device tensor; a host array once loaded, until ``to``), per tile
     ``slide_idx`` int64 [N] into ``slides`` (names, in dataset order) and ``loc`` int64 [N, 2].  A tile's row is its index in the
-    cohort's tile list: its Philox tile counter in ``evaluate()``, in ``predict`` and in training."""
+    cohort's tile list: its Philox tile counter in ``evaluate()``, in ``predict`` and in training.  ``views``: None, or float32
+    [V, N, 2048] beside ``feats`` -- the features of V augmented views of every tile, which only training reads -- with ``augment``
+    (the letters) and ``augment_seed`` that drew them."""
     feats: object
     slide_idx: np.ndarray
     loc: np.ndarray
     slides: list
+    views: object = None
+    augment: str = ''
+    augment_seed: int = 0
 
     def __len__(self):
         return len(self.slide_idx)
@@ -137,35 +151,93 @@ class FeatureCache:
 
     def to(self, device):
         import torch
-        self.feats = torch.as_tensor(np.asarray(self.feats) if not torch.is_tensor(self.feats) else self.feats).to(device).contiguous()
+        on = lambda a: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(device).contiguous()
+        self.feats = on(self.feats)
+        if self.views is not None:
+            self.views = on(self.views)
         return self
 
+    def n_views(self):
+        return 0 if self.views is None else int(self.views.shape[0])
+
     def save(self, path):
-        f = self.feats.cpu().numpy() if hasattr(self.feats, 'cpu') else np.asarray(self.feats)
-        np.savez(path, feats=f.astype(np.float32), slide_idx=self.slide_idx, loc=self.loc, slides=np.array(self.slides, dtype=str))
+        host = lambda a: (a.cpu().numpy() if hasattr(a, 'cpu') else np.asarray(a)).astype(np.float32)
+        extra = {} if self.views is None else {'views': host(self.views), 'augment': np.array(self.augment),
+                                               'augment_seed': np.array(int(self.augment_seed), np.int64)}
+        np.savez(path, feats=host(self.feats), slide_idx=self.slide_idx, loc=self.loc, slides=np.array(self.slides, dtype=str), **extra)
 
     @staticmethod
     def load(path, device=None):
         with np.load(path) as z:
             c = FeatureCache(z['feats'].astype(np.float32), z['slide_idx'].astype(np.int64), z['loc'].astype(np.int64),
                              [str(s) for s in z['slides']])
+            if 'views' in z.files:
+                c.views, c.augment, c.augment_seed = z['views'].astype(np.float32), str(z['augment']), int(z['augment_seed'])
         return c.to(device) if device is not None else c
 
 
-def cache_features(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_fit=None, batch=256):
+def cache_features(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_fit=None, batch=256, augment=None, views=None, seed=0):
     """Every tile of ``slides`` through ``evaluate()``'s input stage -- decode, stain normaliser, ``bq_backbone_u8``
-    (``featuremap.walk_features``) -> ``FeatureCache`` with the features on the engine's device."""
+    (``featuremap.walk_features``) -> ``FeatureCache`` with the features on the engine's device.  ``augment`` (letters out of
+    'xyrjb'; None / '': none) also fills ``views`` [V, N, 2048], V = ``views`` (pass ``max(epochs)``; default 1): view v is every
+    tile through ``Engine.augment`` with row ``augment.draw(N, augment, seed, v)[its row]`` in front of the normaliser, computed
+    from the same decoded batch as the unaugmented features, which stay exactly what they are without ``augment``.  A tile whose
+    JPEG round trip reports its range status raises ``BiscuitHipError``."""
     import torch
+    from . import augment as A
     from .featuremap import walk_features
     eng = engine_or_pool.engines[0] if hasattr(engine_or_pool, 'engines') else engine_or_pool
     parts = []
-    names, _, loc, _ = walk_features(eng, slides, 0, lambda f, g: parts.append(f), norm_fit, normalizer, False, batch)
+    letters = A.parse(augment)
+    V = (1 if views is None else int(views)) if letters else 0
+    if letters and V < 1:
+        raise ValueError('views must be at least 1')
+    prepare, view_parts, statuses = None, [[] for _ in range(V)], []
+    if V:
+        from . import stain
+        n_total = sum(int(s.n_tiles) for s in slides)
+        tables = [torch.from_numpy(A.draw(n_total, letters, seed, v)).to(eng.device) for v in range(V)]
+
+        def prepare(tiles, g):
+            for v in range(V):
+                aug, status = eng.augment(tiles, tables[v].index_select(0, g).contiguous())
+                view_parts[v].append(eng.backbone_u8(stain.normalise(eng, aug, normalizer, norm_fit)))
+                statuses.append(status)
+            return tiles
+    names, _, loc, _ = walk_features(eng, slides, 0, lambda f, g: parts.append(f), norm_fit, normalizer, False, batch, prepare=prepare)
     feats = torch.cat(parts) if parts else torch.zeros((0, 2048), dtype=torch.float32, device=eng.device)
+    if statuses and bool(torch.cat(statuses).ne(0).any()):
+        from .engine import BiscuitHipError
+        raise BiscuitHipError('cache_features: the augmenter reported a tile outside the JPEG round trip\'s exact range')
+    stacked = None
+    if V:
+        stacked = torch.stack([torch.cat(p) if p else torch.zeros((0, 2048), dtype=torch.float32, device=eng.device) for p in view_parts]).contiguous()
     order = [s.name for s in slides]
     index = {s: i for i, s in enumerate(order)}
     if len(index) != len(order):
         raise ValueError('slide names must be unique')
-    return FeatureCache(feats.contiguous(), np.array([index[n] for n in names], np.int64), loc, order)
+    return FeatureCache(feats.contiguous(), np.array([index[n] for n in names], np.int64), loc, order, stacked, letters, int(seed) if V else 0)
+
+
+def cached_features(engine, slides, path, *, augment=None, views=None, seed=0, **kw):
+    """``--cache FILE``: ``cache_features(engine, slides, augment=..., views=..., seed=..., **kw)``, kept in ``path`` (.npz; None: not
+    kept) -- loaded from there when the file exists, with its views, otherwise computed and saved.  SystemExit for a file that holds
+    other slides or was made with another augmentation, number of views or seed."""
+    from . import augment as A
+    letters = A.parse(augment)
+    n_views = (1 if views is None else int(views)) if letters else 0
+    if not path or not os.path.exists(path):
+        cache = cache_features(engine, slides, augment=letters, views=n_views or None, seed=seed, **kw)
+        if path:
+            cache.save(path)
+        return cache
+    cache = FeatureCache.load(path, engine.device)
+    if cache.slides != [s.name for s in slides] or len(cache) != sum(int(s.n_tiles) for s in slides):
+        raise SystemExit(f'--cache {path}: holds other slides than the ones given')
+    if (cache.augment, cache.n_views()) != (letters, n_views) or (letters and cache.augment_seed != int(seed)):
+        raise SystemExit(f'--cache {path}: made with augment {cache.augment!r}, {cache.n_views()} view(s), seed {cache.augment_seed}, '
+                         f'not with {letters!r}, {n_views}, {int(seed)}')
+    return cache
 
 
 # ------------------------------------------------------------------------------------------------------------ training
@@ -173,7 +245,9 @@ def train_head(engine, cache, rows, labels, *, init='model', params=None, seed=N
     """Train the head on ``cache.feats[rows]`` with ``labels`` (0/1 per row) -> ``(head tensor dict, losses float32 [steps])``.
     ``init='model'`` starts from the engine's imported head, ``'glorot'`` from ``glorot_head(seed)`` (a dict starts from that).
     Each epoch walks a permutation from ``numpy.random.default_rng([seed, epoch])`` in batches of ``params.batch_size``, the last one
-    short; the dropout pass counter is the global step.  A loss that is not finite raises ``BiscuitHipError``."""
+    short; the dropout pass counter is the global step.  A cache with ``views`` [V, N, 2048] trains epoch ``e`` on view ``e % V``:
+    the views are read as one [V N, 2048] array at rows ``rows + (e % V) N``, so the kernels are the ones that train without
+    views.  A loss that is not finite raises ``BiscuitHipError``."""
     import torch
     from .engine import BiscuitHipError
     p = (params or TrainParams()).validate()
@@ -197,11 +271,14 @@ def train_head(engine, cache, rows, labels, *, init='model', params=None, seed=N
     m, v, g = torch.zeros_like(w), torch.zeros_like(w), torch.empty_like(w)
     B = int(p.batch_size)
     losses, step = [], 0
+    V, N = (int(cache.views.shape[0]), len(cache)) if getattr(cache, 'views', None) is not None else (0, len(cache))
+    feats = cache.views.reshape(V * N, -1) if V else cache.feats
     for epoch in range(int(max(p.epochs))):
         order = np.random.default_rng([seed, epoch]).permutation(len(rows))
         steps = -(-len(order) // B)
         lr = [p.learning_rate_at(step + i) for i in range(steps)]
-        out = engine.head_train_steps(w, m, v, cache.feats, torch.from_numpy(rows[order]).to(dev),
+        at = rows[order] + (epoch % V) * N if V else rows[order]
+        out = engine.head_train_steps(w, m, v, feats, torch.from_numpy(at).to(dev),
                                       torch.from_numpy(labels[order].astype(np.uint8)).to(dev), B, step, seed, lr, rate=p.dropout,
                                       b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g)
         losses.append(out.cpu().numpy())
@@ -461,9 +538,24 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=1234)
     ap.add_argument('--mc', type=int, default=None, help='MC-dropout passes of the validation tables (default: uq_n of the model, 30)')
     ap.add_argument('--dtype', default='f16', choices=['f16', 'bf16', 'f32'])
+    ap.add_argument('--augment', default='', metavar='SPEC', help="training augmentation, letters out of 'xyrjb' (the paper's models: xyrjb); "
+                    'default: none')
+    ap.add_argument('--views', type=int, default=None, metavar='V', help='augmented views cached per tile; epoch e trains on view e %% V '
+                    '(default: --epochs)')
+    ap.add_argument('--cache', default=None, metavar='FILE', help='the feature cache (.npz): loaded when it exists, otherwise computed and saved')
     args = ap.parse_args(argv)
     if args.epochs < 1 or args.outer_k < 2 or args.inner_k < 2:
         raise SystemExit('--epochs >= 1, --outer-k >= 2 and --inner-k >= 2')
+    from . import augment as A
+    try:
+        letters = A.parse(args.augment)
+    except ValueError as e:
+        raise SystemExit(f'--augment: {e}') from None
+    n_views = (args.epochs if args.views is None else args.views) if letters else 0
+    if letters and n_views < 1:
+        raise SystemExit('--views >= 1')
+    if args.cache and not args.cache.endswith('.npz'):
+        args.cache += '.npz'                 # (the name numpy.savez writes to)
     if not os.path.isdir(args.model):
         raise SystemExit(f'--model {args.model}: not a directory')
     missing = [p for p in args.tfrecords if not os.path.exists(p)]
@@ -493,9 +585,10 @@ def main(argv=None):
     mc_n = int(args.mc or hp.uq_n)
     eng = Engine(w, hp=hp, dtype=args.dtype, max_batch=256, max_mc=mc_n, act_exp=act_exp)
     try:
-        cache = cache_features(eng, slides, normalizer=hp.normalizer, norm_fit=norm_fit)
-        trainer = HeadTrainer(eng, cache, labels, params=TrainParams(epochs=[args.epochs], dropout=hp.dropout), init=args.init, mc_n=mc_n,
-                              outcome=args.outcome)
+        cache = cached_features(eng, slides, args.cache, normalizer=hp.normalizer, norm_fit=norm_fit, augment=letters, views=n_views or None,
+                                seed=args.seed)
+        trainer = HeadTrainer(eng, cache, labels, params=TrainParams(epochs=[args.epochs], dropout=hp.dropout, augment=letters),
+                              init=args.init, mc_n=mc_n, outcome=args.outcome)
         try:
             dirs = train_nested_cv(cache, labels, args.out, args.label, trainer, outer_k=args.outer_k, inner_k=args.inner_k,
                                    patients=patients, seed=args.seed, outcome=args.outcome)
@@ -513,7 +606,8 @@ def main(argv=None):
     frame.to_csv(os.path.join(args.out, 'nested_cv.csv'), index=False)
     th = {k: (None if v is None else float(v)) for k, v in th.items()}
     with open(os.path.join(args.out, 'thresholds.json'), 'w') as f:
-        json.dump({'thresholds': th, 'label_values': values, 'outer_k': args.outer_k, 'inner_k': args.inner_k, 'seed': args.seed}, f, indent=1)
+        json.dump({'thresholds': th, 'label_values': values, 'outer_k': args.outer_k, 'inner_k': args.inner_k, 'seed': args.seed,
+                   'augment': letters, 'views': n_views}, f, indent=1)
     print(json.dumps({'tiles': len(cache), 'slides': len(cache.slides), 'folds': len(dirs), 'thresholds': th}))
 
 

@@ -323,6 +323,30 @@ size_t bq_png_encode_scratch_bytes(int n, int px);
 int bq_png_encode(bq_ctx* ctx, const uint8_t* d_tiles, int n, int px, uint8_t* d_out, int64_t cap, int64_t* d_off, int32_t* d_status,
                   void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
 
+/* Training augmentation on the device (kernels_augment.hip; DESIGN.md section 7 "Training augmentation"): Slideflow's 'xyrjb' with
+ * the random draws made by the caller (biscuit_amd/augment.py: draw).  n tiles d_tiles uint8 [n][px][px][3], 8 <= px <= 4096, and
+ * d_params uint8 [n][4] = (k, flips, quality, blur) per tile, both in device memory ->
+ *     d_out[i] = blur_s( flip_ud^(flips >> 1 & 1)( flip_lr^(flips & 1)( rot90^k( jpeg_q(d_tiles[i]) ))))
+ * as csrc/augment_device.h states each step: jpeg_q the pixels Pillow returns after a JPEG round trip at quality 1..100 and 4:2:0
+ * (0: the tile itself), rot90^k numpy's counter-clockwise quarter turns (k 0..3), the flips x[:, ::-1] (bit 0) and x[::-1] (bit
+ * 1), blur_s an integer separable Gaussian of sigma = 0.5 blur (blur 1..4; 0: the identity).  The result is bqio_augment's byte
+ * for byte and status for status, whatever the rounds and whatever d_scratch and d_out held.  d_status[i] = 0, or 1 where a block
+ * of the round trip left the range in which libjpeg's builds agree (samples clamped).  The parameter bytes are in device memory,
+ * where this call cannot read them without waiting: a row out of range (k or flips > 3, quality > 100, blur > 4) gets status 2
+ * and its tile comes out unchanged (callers with the table on the host check it there: Engine.augment).  Four stages, each
+ * timed as its own class under bq_profile_*: augment_jpeg (quality > 0: one thread per 8 x 8 block, coefficients -> samples in
+ * scratch), augment_place (four output pixels per thread: the inverse dihedral map over those samples or the input tile),
+ * augment_blur_h and augment_blur_v (blur > 0: the row pass into a uint16 plane in scratch, the column pass back into d_out).
+ * d_out must not overlap d_tiles.  Scratch (16-byte aligned): the decoder's planes, 128 bytes per block, and 6 bytes per pixel
+ * rounded up to 16, 1 090 912 bytes per 299-px tile; bq_augment_scratch_bytes(n, px) asks for min(n, 256) tiles' worth and the
+ * call works in rounds of as many tiles as d_scratch holds -- one at least, BQ_ERR_WORKSPACE below that.  px outside 8..4096
+ * returns BQ_ERR_ARG with bq_last_error set and launches nothing.  Everything is enqueued on `stream`; the library allocates
+ * nothing and does not wait for the device; n = 0 returns 0 without a launch.  No atomics and no inline assembly.  The
+ * reference's counterpart is the augment='xyrjb' of biscuit/hp.py:23 inside Slideflow's tf.data pipeline. */
+size_t bq_augment_scratch_bytes(int n, int px);
+int bq_augment(bq_ctx* ctx, const uint8_t* d_tiles, int n, int px, const uint8_t* d_params, uint8_t* d_out, int32_t* d_status,
+               void* d_scratch, size_t scratch_bytes, bq_stream_t stream);
+
 /* The whole-slide heatmap's input stage (kernels_resample.hip; DESIGN.md "Heatmap input"): n tiles cut out of a slide canvas in
  * device memory and resampled to px x px -- what sf.Heatmap's slide reader does per tile on the host (results.py:217).  d_canvas
  * uint8 [H][W][3]; tile t is the src_px x src_px window at (d_origin[2 t], d_origin[2 t + 1]) = (x, y) (int32; windows may

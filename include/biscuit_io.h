@@ -241,6 +241,24 @@ const char* bqio_jpeg_encode_last_error(void);
 int bqio_png_encode(const uint8_t* tiles, int64_t n, int px, uint8_t* out, size_t cap, int64_t* off, int32_t* status);
 const char* bqio_png_encode_last_error(void);
 
+/* The CPU build of bq_augment (include/biscuit_hip.h; csrc/augment_host.cpp over csrc/augment_device.h, the routines the GPU
+ * kernels are compiled from): Slideflow's training augmentation 'xyrjb' with the random draws made by the caller.  n tiles uint8
+ * [n][px][px][3], 8 <= px <= 4096, and params uint8 [n][4] = (k, flips, quality, blur) per tile ->
+ *     out[i] = blur_s( flip_ud^(flips >> 1 & 1)( flip_lr^(flips & 1)( rot90^k( jpeg_q(tiles[i]) ))))
+ * jpeg_q: quality 0 the tile itself, 1..100 the pixels Pillow returns for Image.open(save(tile, 'JPEG', quality=q, subsampling=
+ * '4:2:0')), byte for byte (the encoder's coefficients, dequantised, through the decoder's IDCT, upsampling and colour stage: no
+ * bitstream).  rot90^k: numpy.rot90(x, k), k 0..3; flips bit 0: x[:, ::-1], bit 1: x[::-1].  blur_s: blur 0 the identity, 1..4 a
+ * separable Gaussian of sigma = 0.5 blur in integers (radius int(3 sigma + 0.5), weights that sum to 65536, mirror padding, a
+ * uint16 row pass with 8 fractional bits, one rounding per pass): within one level of the rounded float64 filter.  status[i] =
+ * 0, or 1 where a block of the round trip left the range in which libjpeg's builds agree (its samples are clamped).  `out`
+ * must not overlap `tiles`.  Tiles are shared among `threads` host threads (1..64).  BQIO_ERR_ARG, with nothing written, for px or
+ * a parameter byte out of range, n < 0, a null pointer or overlapping buffers; bqio_augment_last_error() then says which.
+ * bqio_augment_blur_weights writes the 2 r + 1 weights of blur index 1..4 (uint16, 13 entries, zero behind the last) and returns
+ * the radius r.  For tests and as the device entry's timing baseline. */
+int bqio_augment(const uint8_t* tiles, int64_t n, int px, const uint8_t* params, uint8_t* out, int32_t* status, int threads);
+int bqio_augment_blur_weights(int blur, uint16_t* out);
+const char* bqio_augment_last_error(void);
+
 /* One JPEG file (as bqio_image_bytes returns it) -> out[tile_px][tile_px][3], the decoder
  * bqio_decode uses, exported for tests.  BQIO_OK / BQIO_ERR_UNSUPPORTED / BQIO_ERR_FORMAT. */
 int bqio_decode_jpeg(const uint8_t* data, size_t len, int tile_px, uint8_t* out);
