@@ -106,6 +106,8 @@ ABI = {
     'bq_delong': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _sz, _vp, _vp, _vp]),
     'bq_head_train_workspace_bytes': (_sz, [_i]),
     'bq_head_grad': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i, _i64, _u64, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    'bq_head_validate_workspace_bytes': (_sz, [_i]),
+    'bq_head_validate': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i, _i64, _u64, C.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
     'bq_head_adam': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     'bq_head_train_steps': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i64, _u64, C.c_double,
                                  C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),

@@ -22,6 +22,10 @@
 //
 // Adam evaluates the update of an element in float64 from its fp32 state and rounds once per stored value, so m', v' and w' are the
 // correctly rounded values of the Keras formulas; an element with g = 0 and m = v = 0 keeps its bits.
+//
+// bq_head_validate (DESIGN.md section 7 "Training schedule") is the forward half alone over n <= 4096 rows, for the validation checks in
+// the middle of a training: the same two GEMMs (at rate 0 in the A mode that draws nothing), the same logits and float64 row loss, a hit
+// per row, and the two sums in a fixed order.  A row's loss and hit depend on the row only, not on n or on its place in the batch.
 #include <cmath>
 #include <hip/hip_runtime.h>
 
@@ -58,10 +62,18 @@ __device__ __forceinline__ float4 drop4(float4 v, unsigned g, unsigned ctr, cons
     return o;
 }
 
+// what drop4 gives at rate 0 (every unit kept, scale 1), without the draw
+__device__ __forceinline__ float4 finite4(float4 v) {
+    const float nan = __builtin_nanf("");
+    return make_float4(__builtin_isfinite(v.x) ? v.x : nan, __builtin_isfinite(v.y) ? v.y : nan, __builtin_isfinite(v.z) ? v.z : nan,
+                       __builtin_isfinite(v.w) ? v.w : nan);
+}
+
 // ReLU that keeps NaN, as the inference head's
 __device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
 
-enum AMode : int { A_DROP_K = 0, A_PLAIN_K = 1, A_DROP_T = 2 };   // drop(src)[m][k]; src[m][k]; drop(src)[k = batch row][m = unit]
+// drop(src)[m][k]; src[m][k]; drop(src)[k = batch row][m = unit]; A_DROP_K at rate 0 without its draws (bq_head_validate): src[m][k], NaN for not finite
+enum AMode : int { A_DROP_K = 0, A_PLAIN_K = 1, A_DROP_T = 2, A_FINITE_K = 3 };
 enum BMode : int { B_ROWS = 0, B_KCONT = 1 };                     // b[k][n]; b[n][k]
 enum Epi : int { EPI_RELU = 0, EPI_DX = 1, EPI_STORE = 2 };
 
@@ -130,6 +142,7 @@ __global__ void __launch_bounds__(256) train_gemm_kernel(const TrainGemm p) {
                 if (alive[i]) {
                     v = arow[i] ? *reinterpret_cast<const float4*>(arow[i] + k) : make_float4(nan, nan, nan, nan);
                     if (AM == A_DROP_K) v = drop4(v, (unsigned)(k >> 2), actr[i], p.drop);
+                    if (AM == A_FINITE_K) v = finite4(v);
                 }
                 ra = v;
             }
@@ -241,6 +254,31 @@ __device__ __forceinline__ float block_sum_256(float v, float* lds) {
     return ((lds[0] + lds[1]) + lds[2]) + lds[3];
 }
 
+// The logits of one row by a workgroup of 256 threads, thread t on the units 4 t .. 4 t + 3 (hv: the row's h1 there; wa, wb: W2's rows
+// of those units): z = drop(h1) W2 + b2, an fmaf chain per thread, then block_sum_256.  DROP false is rate 0 without the draw.
+template <bool DROP>
+__device__ __forceinline__ void row_logits(float4 hv, float4 wa, float4 wb, const float* __restrict__ b2, unsigned ctr, const Drop& d,
+                                           float* lds, float& z0, float& z1) {
+    const float4 u = DROP ? drop4(hv, (unsigned)threadIdx.x, ctr, d) : finite4(hv);
+    // units 4 tid .. 4 tid + 3: (wa.x, wa.y), (wa.z, wa.w), (wb.x, wb.y), (wb.z, wb.w)
+    const float s0 = fmaf(u.w, wb.z, fmaf(u.z, wb.x, fmaf(u.y, wa.z, u.x * wa.x)));
+    const float s1 = fmaf(u.w, wb.w, fmaf(u.z, wb.y, fmaf(u.y, wa.w, u.x * wa.y)));
+    z0 = block_sum_256(s0, lds) + b2[0];
+    z1 = block_sum_256(s1, lds) + b2[1];
+}
+
+// The softmax and the row's loss in float64 from the fp32 logits, each rounded once (a few operations per row); all NaN for a label
+// above 1 or a logit that is NaN.
+__device__ __forceinline__ double row_loss(float z0, float z1, unsigned y, double& p0, double& p1) {
+    const double zd0 = (double)z0, zd1 = (double)z1, mx = fmax(zd0, zd1);
+    const double e0 = exp(zd0 - mx), e1 = exp(zd1 - mx), sum = e0 + e1;
+    p0 = e0 / sum;
+    p1 = e1 / sum;
+    double loss = log(sum) - ((y ? zd1 : zd0) - mx);
+    if (y > 1u || z0 != z0 || z1 != z1) { loss = __builtin_nan(""); p0 = loss; p1 = loss; }
+    return loss;
+}
+
 // A workgroup per batch row: logits = drop(h1) W2 + b2, softmax, the row's loss, dlog = (p - onehot) / n, and
 // dz1 = (h1 > 0 and kept) ? scale (dlog . W2[k]) : 0.
 __global__ void __launch_bounds__(256) train_logits_kernel(const float* __restrict__ h1, const float* __restrict__ w2,
@@ -251,20 +289,12 @@ __global__ void __launch_bounds__(256) train_logits_kernel(const float* __restri
     const int m = blockIdx.x, tid = threadIdx.x;
     const unsigned ctr = (unsigned)rows[m];
     const float4 hv = *reinterpret_cast<const float4*>(h1 + (size_t)m * D_H + tid * 4);
-    const float4 u = drop4(hv, (unsigned)tid, ctr, d);
     const float4 wa = *reinterpret_cast<const float4*>(w2 + tid * 8), wb = *reinterpret_cast<const float4*>(w2 + tid * 8 + 4);
-    // units 4 tid .. 4 tid + 3: (wa.x, wa.y), (wa.z, wa.w), (wb.x, wb.y), (wb.z, wb.w)
-    const float s0 = fmaf(u.w, wb.z, fmaf(u.z, wb.x, fmaf(u.y, wa.z, u.x * wa.x)));
-    const float s1 = fmaf(u.w, wb.w, fmaf(u.z, wb.y, fmaf(u.y, wa.w, u.x * wa.y)));
-    const float z0 = block_sum_256(s0, lds) + b2[0];
-    const float z1 = block_sum_256(s1, lds) + b2[1];
+    float z0, z1;
+    row_logits<true>(hv, wa, wb, b2, ctr, d, lds, z0, z1);
     const unsigned y = label[m];
-    // the softmax and the row's loss in float64 from the fp32 logits, each rounded once (a few operations per row)
-    const double zd0 = (double)z0, zd1 = (double)z1, mx = fmax(zd0, zd1);
-    const double e0 = exp(zd0 - mx), e1 = exp(zd1 - mx), sum = e0 + e1;
-    double p0 = e0 / sum, p1 = e1 / sum;
-    double loss = log(sum) - ((y ? zd1 : zd0) - mx);
-    if (y > 1u || z0 != z0 || z1 != z1) { loss = __builtin_nan(""); p0 = loss; p1 = loss; }
+    double p0, p1;
+    const double loss = row_loss(z0, z1, y, p0, p1);
     const float g0 = (float)((p0 - (y == 0u ? 1.0 : 0.0)) / (double)n), g1 = (float)((p1 - (y == 1u ? 1.0 : 0.0)) / (double)n);
     if (tid == 0) {
         dlog[2 * m] = g0;
@@ -280,6 +310,58 @@ __global__ void __launch_bounds__(256) train_logits_kernel(const float* __restri
     o.w = (hv.w > 0.f && r[3] >= d.thresh) ? d.scale * fmaf(g1, wb.w, g0 * wb.z) : 0.f;
     if (g0 != g0 || g1 != g1) o = make_float4(g0, g0, g0, g0);       // a NaN row stays NaN where its ReLU would have cut it
     *reinterpret_cast<float4*>(dz1 + (size_t)m * D_H + tid * 4) = o;
+}
+
+// bq_head_validate's row kernel, a workgroup per row: train_logits_kernel's logits and loss, and hit = the larger logit is the label's
+// (a tie goes to class 0; a NaN row hits nothing).  A row's values depend on nothing but the row.  out_loss / out_hit: the caller's, or null.
+template <bool DROP>
+__global__ void __launch_bounds__(256) validate_logits_kernel(const float* __restrict__ h1, const float* __restrict__ w2,
+                                                              const float* __restrict__ b2, const long long* __restrict__ rows,
+                                                              const unsigned char* __restrict__ label, Drop d, double* __restrict__ rowloss,
+                                                              unsigned char* __restrict__ hit, double* __restrict__ out_loss,
+                                                              unsigned char* __restrict__ out_hit) {
+    __shared__ float lds[4];
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const float4 hv = *reinterpret_cast<const float4*>(h1 + (size_t)m * D_H + tid * 4);
+    const float4 wa = *reinterpret_cast<const float4*>(w2 + tid * 8), wb = *reinterpret_cast<const float4*>(w2 + tid * 8 + 4);
+    float z0, z1;
+    row_logits<DROP>(hv, wa, wb, b2, (unsigned)rows[m], d, lds, z0, z1);
+    if (tid == 0) {
+        const unsigned y = label[m];
+        double p0, p1;
+        const double loss = row_loss(z0, z1, y, p0, p1);
+        const unsigned char ok = (loss == loss && (z1 > z0 ? 1u : 0u) == y) ? 1 : 0;
+        rowloss[m] = loss;
+        hit[m] = ok;
+        if (out_loss) out_loss[m] = loss;
+        if (out_hit) out_hit[m] = ok;
+    }
+}
+
+// stats[0] = the sum of the rows' losses, stats[1] = the number of hits: thread t takes the rows t, t + 256, ... in order, then thread
+// 0 the 256 partial sums in order.  One workgroup.
+__global__ void __launch_bounds__(256) validate_sums_kernel(const double* __restrict__ rowloss, const unsigned char* __restrict__ hit, int n,
+                                                            double* __restrict__ stats) {
+    __shared__ double lpart[256];
+    __shared__ unsigned cpart[256];
+    double l = 0.0;
+    unsigned c = 0u;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        l += rowloss[i];
+        c += hit[i];
+    }
+    lpart[threadIdx.x] = l;
+    cpart[threadIdx.x] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        l = 0.0; c = 0u;
+        for (int t = 0; t < 256; ++t) {
+            l += lpart[t];
+            c += cpart[t];
+        }
+        stats[0] = l;
+        stats[1] = (double)c;
+    }
 }
 
 // The small sums over the batch.  A workgroup is 8 row groups x 32 lanes: row group q sums the rows q, q + 8, ... in order, then the
@@ -494,6 +576,53 @@ void dropout_of(double rate, unsigned& thresh, float& scale) {      // set_dropo
     scale = (float)(1.0 / (1.0 - rate));
 }
 
+// bq_head_validate: the forward half of enqueue_grad over up to 4096 rows (the reference's validation_steps x batch_size, 32 x 128:
+// the forward GEMMs then launch 16 x 64 workgroups).  h0 | h1, each [n][1024] | rowloss f64 [n] | hit u8 [n]
+constexpr int VALIDATE_MAX_N = 4096;
+size_t validate_workspace_bytes(int n) {
+    if (n < 1 || n > VALIDATE_MAX_N) return 0;
+    return 2 * al((size_t)n * D_H * 4) + al((size_t)n * 8) + al((size_t)n);
+}
+
+// Four launches, each a profiling class of its own.  DROP false (rate 0): no mask is drawn anywhere.
+template <bool DROP>
+int enqueue_validate(bq_ctx* c, const float* params, const float* feats, long long n_feat, const long long* rows, const unsigned char* labels,
+                     int n, const Drop& d, double* stats, double* out_loss, unsigned char* out_hit, void* ws, hipStream_t s) {
+    constexpr int AM = DROP ? A_DROP_K : A_FINITE_K;
+    unsigned char* p = (unsigned char*)ws;
+    float* h0 = (float*)p; p += al((size_t)n * D_H * 4);
+    float* h1 = (float*)p; p += al((size_t)n * D_H * 4);
+    double* rowloss = (double*)p; p += al((size_t)n * 8);
+    unsigned char* hit = p;
+    const double fn = (double)n;
+    TrainGemm g{};
+    g.rows = rows; g.n_feat = n_feat; g.b = nullptr; g.ldb = D_H; g.ldo = D_H; g.M = n; g.N = D_H; g.drop = d;
+    {   // h0 = relu(drop_0(x[rows]) W0 + b0)
+        ProfScope ps(c, s, "head_validate_fwd0", 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_IN + (double)D_IN * D_H + fn * D_H));
+        TrainGemm q = g;
+        q.a = feats; q.lda = D_IN; q.gather = 1; q.b = params + OFF_W0; q.out = h0; q.bias = params + OFF_B0; q.K = D_IN; q.drop.layer = 0u;
+        launch_gemm<AM, B_ROWS, EPI_RELU>(q, s);
+    }
+    {   // h1 = relu(drop_1(h0) W1 + b1)
+        ProfScope ps(c, s, "head_validate_fwd1", 2.0 * fn * D_H * D_H, 4.0 * (2.0 * fn * D_H + (double)D_H * D_H));
+        TrainGemm q = g;
+        q.a = h0; q.lda = D_H; q.gather = 0; q.b = params + OFF_W1; q.out = h1; q.bias = params + OFF_B1; q.K = D_H; q.drop.layer = 1u;
+        launch_gemm<AM, B_ROWS, EPI_RELU>(q, s);
+    }
+    {   // logits, the row's loss and hit
+        ProfScope ps(c, s, "head_validate_logits", 4.0 * fn * D_H, 4.0 * (fn * D_H + 2.0 * D_H));
+        Drop d2 = d; d2.layer = 2u;
+        hipLaunchKernelGGL((validate_logits_kernel<DROP>), dim3(n), dim3(256), 0, s, h1, params + OFF_W2, params + OFF_B2, rows, labels, d2,
+                           rowloss, hit, out_loss, out_hit);
+    }
+    {   // the two sums
+        ProfScope ps(c, s, "head_validate_sums", fn, 9.0 * fn);
+        hipLaunchKernelGGL(validate_sums_kernel, dim3(1), dim3(256), 0, s, rowloss, hit, n, stats);
+    }
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -510,6 +639,31 @@ int bq_head_grad(bq_ctx* c, const float* d_params, const float* d_feats, int64_t
     GradArgs a{d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, n, (long long)step, seed, 0u, 1.f, d_grad, d_loss, d_ws};
     dropout_of(rate, a.thresh, a.scale);
     return enqueue_grad(c, a, (hipStream_t)stream);
+}
+
+size_t bq_head_validate_workspace_bytes(int n) { return validate_workspace_bytes(n); }
+
+int bq_head_validate(bq_ctx* c, const float* d_params, const float* d_feats, int64_t n_feat, const int64_t* d_rows, const uint8_t* d_labels,
+                     int n, int64_t pass, uint64_t seed, double rate, double* d_stats, double* d_rowloss, uint8_t* d_hit, void* d_ws,
+                     size_t ws_bytes, bq_stream_t stream) {
+    if (!c) return fail(c, BQ_ERR_ARG, "bq_head_validate: null context");
+    if (n < 1 || n > VALIDATE_MAX_N) return fail(c, BQ_ERR_ARG, "bq_head_validate: 1 <= n <= 4096");
+    if (n_feat < 1 || pass < 0 || pass > 0xffffffffLL)
+        return fail(c, BQ_ERR_ARG, "bq_head_validate: an empty feature cache, or a pass outside 0 .. 2^32 - 1");
+    if (!(rate >= 0.0) || !(rate < 1.0)) return fail(c, BQ_ERR_ARG, "bq_head_validate: the rate must lie in [0, 1)");
+    if (!d_params || !d_feats || !d_rows || !d_labels || !d_stats || !d_ws || ((uintptr_t)d_params & 15) || ((uintptr_t)d_feats & 15) ||
+        ((uintptr_t)d_rows & 7) || ((uintptr_t)d_stats & 7) || ((uintptr_t)d_rowloss & 7) || ((uintptr_t)d_ws & 255))
+        return fail(c, BQ_ERR_ARG, "bq_head_validate: bad argument (null pointer, params or feats not 16-byte, rows, stats or rowloss not "
+                                   "8-byte or the workspace not 256-byte aligned)");
+    if (ws_bytes < validate_workspace_bytes(n))
+        return fail(c, BQ_ERR_WORKSPACE, "bq_head_validate: workspace below bq_head_validate_workspace_bytes(n)");
+    DeviceGuard guard(c->device);
+    Drop d{0u, (unsigned)pass, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), 0u, 1.f};
+    dropout_of(rate, d.thresh, d.scale);
+    return rate > 0.0 ? enqueue_validate<true>(c, d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, n, d, d_stats, d_rowloss,
+                                               d_hit, d_ws, (hipStream_t)stream)
+                      : enqueue_validate<false>(c, d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, n, d, d_stats, d_rowloss,
+                                                d_hit, d_ws, (hipStream_t)stream);
 }
 
 int bq_head_adam(bq_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, int64_t step, double lr, double b1, double b2,

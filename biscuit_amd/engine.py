@@ -130,7 +130,7 @@ class Engine:
         """Lets go of every device buffer grown on demand -- the network's workspace and each tool's scratch -- and of nothing else;
         the next call that wants one allocates it again."""
         self._ws = None                  # the network's workspace (``_ws_for``)
-        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong, train, augment
+        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong, train, validate, augment
 
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
@@ -1154,6 +1154,39 @@ class Engine:
         self._check(self._lib.bq_head_grad(self._ctx, _ptr(params), _ptr(feats), int(feats.shape[0]), _ptr(rows), _ptr(labels), n, int(step),
                                            int(seed), rate, _ptr(grad), _ptr(loss), _ptr(scratch), scratch.numel(), self._stream()))
         return grad, loss
+
+    HEAD_VALIDATE_MAX_ROWS = 4096
+
+    def validate_scratch(self, n):
+        """A caller's own scratch for ``head_validate`` over up to ``n`` rows (``scratch=``): uint8
+        [``bq_head_validate_workspace_bytes(n)``] on this device; without one the calls share the engine's cached ``validate`` buffer."""
+        return self._bytes(self._lib.bq_head_validate_workspace_bytes(int(n)))
+
+    def head_validate(self, params, feats, rows, labels, pass_, seed, rate=0.0, rowloss=False, hit=False, scratch=None):
+        """The head ``params`` scored on the rows ``feats[rows]`` (``bq_head_validate``): the forward half of ``head_grad`` in the same
+        arithmetic, 1 <= n <= 4096 rows.  ``rate`` 0 (the default, unlike ``head_grad``'s) is inference mode and draws no mask; a
+        positive rate draws the training masks with pass = ``pass_``.  -> ``(stats, rowloss, hit)`` on the device: ``stats`` float64
+        [2], the sum of the rows' losses and the number of rows whose larger logit is their label's (a tie goes to class 0);
+        ``rowloss`` float64 [n] and ``hit`` uint8 [n] where asked for, else None.  A row that is not finite, lies outside ``feats``
+        or has a label above 1 has a NaN loss and hit 0.  ``params`` is only read; nothing waits for the device."""
+        n = int(rows.numel()) if torch.is_tensor(rows) else -1
+        if not 1 <= n <= self.HEAD_VALIDATE_MAX_ROWS:
+            raise ValueError(f'head_validate: 1 <= n <= {self.HEAD_VALIDATE_MAX_ROWS} rows, as an int64 tensor')
+        self._train_state(('params', params))
+        self._train_batch(feats, rows, labels, n)
+        rate = float(rate)
+        if not 0.0 <= rate < 1.0 or not 0 <= int(pass_) < 1 << 32:
+            raise ValueError('head_validate: the rate lies in [0, 1) and the pass in 0 .. 2^32 - 1')
+        need = int(self._lib.bq_head_validate_workspace_bytes(n))
+        scratch = self._scratch('validate', need, scratch)
+        assert scratch.is_cuda and scratch.is_contiguous()        # (too small: the library refuses, BQ_ERR_WORKSPACE)
+        stats = torch.empty(2, dtype=torch.float64, device=self.device)
+        loss = torch.empty(n, dtype=torch.float64, device=self.device) if rowloss else None
+        hits = torch.empty(n, dtype=torch.uint8, device=self.device) if hit else None
+        self._check(self._lib.bq_head_validate(self._ctx, _ptr(params), _ptr(feats), int(feats.shape[0]), _ptr(rows), _ptr(labels), n,
+                                               int(pass_), int(seed), rate, _ptr(stats), _ptr(loss), _ptr(hits), _ptr(scratch),
+                                               scratch.numel(), self._stream()))
+        return stats, loss, hits
 
     def head_adam(self, params, m, v, grad, step, lr, b1=0.9, b2=0.999, eps=1e-7):
         """One Keras-Adam pass over the head's parameters in place (``bq_head_adam``), t = ``step`` + 1."""

@@ -14,10 +14,16 @@ augmented views of every tile -- ``Engine.augment`` (``bq_augment``, ``csrc/kern
 ``augment.draw(N, spec, seed, v)`` in front of the stain normaliser -- and epoch ``e`` of a training reads view ``e % V``.
 Validation and ``predict`` read the unaugmented features, as Slideflow validates unaugmented.
 
+The reference's schedule (DESIGN.md section 7 "Training schedule"; ``--early-stop``, ``--balance category``, ``--full``): ``fit_head``
+scores validation rows every ``validate_on_batch`` steps on the head as it stands (``Engine.head_validate``, ``bq_head_validate``),
+``EarlyStop`` ends the training when the smoothed accuracy no longer rises, ``balanced_rows`` draws batches balanced by category,
+each fold writes ``results_log.csv``, ``find_cv_early_stop`` reads the folds' stop batches and ``train_full`` trains the model on
+every slide for that many steps.  All of it is off by default.
+
 Restated from memory, unpinned against Slideflow: ``TrainParams``' schedule constants and Keras's Adam defaults, the ``k-fold``
-split strategy (``kfold``), the directory names, the augmentation's probabilities and order (``augment.py``).  Out of scope:
-training any backbone layer, Slideflow's stain augmentation ``n``, class balancing, early stopping, ``validate_on_batch``,
-TensorFlow checkpoints, multi-GPU training.
+split strategy (``kfold``), the directory names, the augmentation's probabilities and order (``augment.py``), the early-stopping
+rule and its defaults, and how balanced batches are drawn.  Out of scope: training any backbone layer, Slideflow's stain
+augmentation ``n``, TensorFlow checkpoints, multi-GPU training.
 """
 import argparse
 import json
@@ -43,6 +49,11 @@ LR_STAIRCASE = True
 
 HEAD_FILE = 'head.npz'
 MANIFEST_FILE = 'slides.json'
+RESULTS_FILE = 'results_log.csv'             # Slideflow's per-model log: what utils.find_cv_early_stop reads
+
+BALANCES = ('none', 'tile', 'slide', 'patient', 'category')
+HEAD_VALIDATE_MAX_ROWS = 4096                # Engine.HEAD_VALIDATE_MAX_ROWS: the rows of one check
+VAL_STREAM = 0x76616c                        # 'val': the stream of the validation rows' order
 
 
 @dataclass
@@ -58,6 +69,24 @@ class TrainParams:
     dropout: float = 0.1                     # hp.py:11
     loss: str = 'sparse_categorical_crossentropy'           # hp.py:18
     augment: str = ''                        # hp.py:23 sets 'xyrjb'; '' trains on the unaugmented features, bit for bit as before
+    # The training schedule (DESIGN.md section 7 "Training schedule"), all off by default.  hp.py:9-10 sets early_stop=True with
+    # method 'accuracy'; experiment.py:1028-1051 passes validate_on_batch=32, validation_steps=32; the other defaults are Slideflow's,
+    # restated from memory, unpinned.
+    early_stop: bool = False                 # hp.py:9
+    early_stop_method: str = 'accuracy'      # hp.py:10; or 'loss'
+    early_stop_patience: int = 0             # epochs before the rule may fire
+    ema_observations: int = 20
+    ema_smoothing: float = 2
+    validate_on_batch: int = 32              # a check every so many steps of an epoch
+    validation_steps: int = 32               # batches of validation rows per check
+    validation_dropout: bool = False         # True: a check draws the training masks; False: inference mode
+    training_balance: str = 'none'           # or 'tile' (the same), 'slide', 'patient', 'category'
+    steps_per_epoch_override: Optional[int] = None
+
+    @classmethod
+    def nature2022(cls, **fields):
+        """The reference's schedule: early stopping by accuracy, batches balanced by category (Slideflow's default)."""
+        return cls(**{'early_stop': True, 'early_stop_method': 'accuracy', 'training_balance': 'category', **fields})
 
     def validate(self):
         from . import augment as A
@@ -68,6 +97,16 @@ class TrainParams:
             raise ValueError('1 <= batch_size <= 1024 and at least one epoch')
         if not 0.0 <= self.dropout < 1.0 or not self.learning_rate > 0 or self.learning_rate_decay_steps < 1:
             raise ValueError('dropout in [0, 1), a positive learning rate and decay steps >= 1')
+        if self.early_stop_method not in ('accuracy', 'loss') or self.training_balance not in BALANCES:
+            raise ValueError(f"early_stop_method is 'accuracy' or 'loss', training_balance one of {BALANCES}")
+        if int(self.early_stop_patience) < 0 or int(self.ema_observations) < 1 or not self.ema_smoothing > 0:
+            raise ValueError('early_stop_patience >= 0, ema_observations >= 1 and ema_smoothing > 0')
+        if int(self.validate_on_batch) < 1 or int(self.validation_steps) < 1:
+            raise ValueError('validate_on_batch >= 1 and validation_steps >= 1')
+        if self.early_stop and int(self.validation_steps) * int(self.batch_size) > HEAD_VALIDATE_MAX_ROWS:
+            raise ValueError(f'a check scores validation_steps x batch_size rows, at most {HEAD_VALIDATE_MAX_ROWS}')
+        if self.steps_per_epoch_override is not None and int(self.steps_per_epoch_override) < 1:
+            raise ValueError('steps_per_epoch_override is None or at least 1')
         return self
 
     def learning_rate_at(self, step):
@@ -240,14 +279,128 @@ def cached_features(engine, slides, path, *, augment=None, views=None, seed=0, *
     return cache
 
 
+# ------------------------------------------------------------------------------------------------------------ the schedule
+class EarlyStop:
+    """Slideflow's early-stopping rule over the values of successive validation checks (restated from memory, unpinned; DESIGN.md
+    section 7 "Training schedule" is the definition).  The first ``ema_observations`` values are collected, and their mean seeds the
+    moving average ``ema`` when the last of them arrives (None until then); from then on ``ema = value k + ema (1 - k)`` with
+    ``k = ema_smoothing / (1 + ema_observations)``.  After every check the averages shift, ``two <- one <- ema``.  ``update`` says
+    stop when ``epoch >= patience``, the average of two checks back exists and the new one has not improved on it: ``ema <= two``
+    for ``'accuracy'``, ``ema >= two`` for ``'loss'``."""
+
+    def __init__(self, method='accuracy', patience=0, ema_observations=20, ema_smoothing=2):
+        if method not in ('accuracy', 'loss') or int(ema_observations) < 1:
+            raise ValueError("method is 'accuracy' or 'loss', ema_observations at least 1")
+        self.method, self.patience, self.observations = method, int(patience), int(ema_observations)
+        self.k = float(ema_smoothing) / (1 + self.observations)
+        self.values, self.ema, self.one, self.two = [], None, None, None
+
+    @classmethod
+    def of(cls, params):
+        return cls(params.early_stop_method, params.early_stop_patience, params.ema_observations, params.ema_smoothing)
+
+    def update(self, value, epoch):
+        value = float(value)
+        if self.ema is None:
+            self.values.append(value)
+            if len(self.values) >= self.observations:
+                self.ema = float(np.mean(self.values))
+        else:
+            self.ema = value * self.k + self.ema * (1 - self.k)
+        stop = self.ema is not None and self.two is not None and int(epoch) >= self.patience and \
+            (self.ema <= self.two if self.method == 'accuracy' else self.ema >= self.two)
+        self.two, self.one = self.one, self.ema
+        return bool(stop)
+
+
+def epoch_order(count, n, seed, epoch):
+    """The first ``n`` entries of an epoch's stream of positions 0 .. count - 1: ``default_rng([seed, epoch]).permutation(count)``
+    -- the whole of it for n = count, as ``train_head`` always walked -- continued past its end with the permutations of
+    ``default_rng([seed, epoch, k])``, k = 1, 2, ..."""
+    parts, k = [], 0
+    while k * count < n:
+        parts.append(np.random.default_rng([int(seed), int(epoch)] + ([k] if k else [])).permutation(int(count)))
+        k += 1
+    return np.concatenate(parts)[:int(n)] if parts else np.zeros(0, np.int64)
+
+
+def slide_probabilities(slide_idx, labels, patients, balance):
+    """``(slides, p)``: the distinct values of ``slide_idx``, ascending, and the probability with which a balanced draw picks each.
+    ``'category'``: every class equally likely and its slides equally likely within it (a slide's class is its first row's label);
+    ``'slide'``: every slide equally likely; ``'patient'``: every patient equally likely and their slides equally likely within them
+    (``patients``: a patient per row; None: every slide is its own patient)."""
+    slides, first = np.unique(slide_idx, return_index=True)
+    if balance == 'slide' or (balance == 'patient' and patients is None):
+        return slides, np.full(len(slides), 1.0 / len(slides))
+    if balance == 'category':
+        group = np.asarray(labels)[first]
+    elif balance == 'patient':
+        group = np.asarray(patients)[first]
+    else:
+        raise ValueError(f"a balanced draw is by 'slide', 'patient' or 'category', not {balance!r}")
+    _, inverse, counts = np.unique(group, return_inverse=True, return_counts=True)
+    return slides, 1.0 / (len(counts) * counts[inverse].astype(np.float64))
+
+
+def balanced_rows(rows, slide_idx, labels, patients, balance, n, seed, epoch, state=None):
+    """``n`` draws for epoch ``epoch`` -> int64 [n] positions into ``rows`` (``slide_idx``, ``labels`` and ``patients`` hold one
+    entry per row).  ``'none'`` and ``'tile'`` are ``epoch_order(len(rows), n, seed, epoch)``.  Otherwise each draw first picks a
+    slide with the fixed probability of ``slide_probabilities`` -- ``default_rng([seed, epoch, 0x62616c]).choice`` -- and then takes
+    that slide's next tile from the slide's own permutation ``default_rng([seed, 0x74696c, slide]).permutation``, walked cyclically:
+    no tile of a slide repeats before all its tiles were drawn.  ``state`` (a dict, changed in place; None: a fresh walk) carries
+    every slide's offset from one epoch to the next."""
+    if balance in ('none', 'tile'):
+        return epoch_order(len(rows), n, seed, epoch)
+    slide_idx = np.asarray(slide_idx, np.int64).reshape(-1)
+    if len(slide_idx) != len(rows) or len(np.asarray(labels).reshape(-1)) != len(rows) or len(rows) < 1:
+        raise ValueError('balanced_rows: a slide and a label for each of at least one row')
+    slides, p = slide_probabilities(slide_idx, labels, patients, balance)
+    picks = np.random.default_rng([int(seed), int(epoch), 0x62616c]).choice(len(slides), size=int(n), p=p)
+    state = {} if state is None else state
+    out = np.empty(int(n), np.int64)
+    for j, s in enumerate(slides):
+        mine = np.flatnonzero(picks == j)
+        if not len(mine):
+            continue
+        at = np.flatnonzero(slide_idx == s)
+        walk = at[np.random.default_rng([int(seed), 0x74696c, int(s)]).permutation(len(at))]
+        start = int(state.get(int(s), 0))
+        out[mine] = walk[(start + np.arange(len(mine))) % len(at)]
+        state[int(s)] = (start + len(mine)) % len(at)
+    return out
+
+
+@dataclass
+class FitResult:
+    """What ``fit_head`` returns: the head tensor dict, the training losses float32 [steps], ``checks`` -- ``(step, val_loss,
+    val_acc, ema)`` per validation check, ``step`` the steps done by then, ``ema`` None before it is seeded --, ``early_stop_batch``
+    (the steps done when the rule fired; None if it never did) and the steps done in all."""
+    head: dict
+    losses: np.ndarray
+    checks: list
+    early_stop_batch: Optional[int]
+    steps: int
+
+
 # ------------------------------------------------------------------------------------------------------------ training
-def train_head(engine, cache, rows, labels, *, init='model', params=None, seed=None):
-    """Train the head on ``cache.feats[rows]`` with ``labels`` (0/1 per row) -> ``(head tensor dict, losses float32 [steps])``.
+def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, slide_idx=None, patients=None, init='model', params=None,
+             seed=None):
+    """Train the head on ``cache.feats[rows]`` with ``labels`` (0/1 per row) under ``params``' schedule -> ``FitResult``.
     ``init='model'`` starts from the engine's imported head, ``'glorot'`` from ``glorot_head(seed)`` (a dict starts from that).
-    Each epoch walks a permutation from ``numpy.random.default_rng([seed, epoch])`` in batches of ``params.batch_size``, the last one
-    short; the dropout pass counter is the global step.  A cache with ``views`` [V, N, 2048] trains epoch ``e`` on view ``e % V``:
-    the views are read as one [V N, 2048] array at rows ``rows + (e % V) N``, so the kernels are the ones that train without
-    views.  A loss that is not finite raises ``BiscuitHipError``."""
+
+    An epoch is ``ceil(len(rows) / batch_size)`` steps over ``len(rows)`` draws, the last batch short, or exactly
+    ``steps_per_epoch_override`` full batches; the draws are ``balanced_rows`` (``slide_idx``: the slide of each row, default the
+    cache's; ``patients``: a patient per row, for ``'patient'``), which without balancing is the permutation of
+    ``default_rng([seed, epoch])``.  The dropout pass counter is the global step.  A cache with ``views`` [V, N, 2048] trains epoch
+    ``e`` on view ``e % V``: the views are read as one [V N, 2048] array at rows ``rows + (e % V) N``.
+
+    With ``val_rows`` / ``val_labels`` an epoch runs as segments of ``validate_on_batch`` steps (the last one short), each one
+    ``Engine.head_train_steps`` call, and after every segment one ``Engine.head_validate`` call scores the next
+    ``min(validation_steps * batch_size, len(val_rows))`` rows of a cyclic walk of ``default_rng([seed, 0x76616c]).permutation(val_rows)``
+    on the unaugmented features, at rate ``dropout`` if ``validation_dropout`` else 0, with pass = the global step; the host reads
+    its 16 bytes, the one synchronisation per check.  The checks change nothing in the training; with ``early_stop`` their accuracy
+    or loss feeds ``EarlyStop``, and the training ends where it says stop.  A training or validation loss that is not finite raises
+    ``BiscuitHipError``."""
     import torch
     from .engine import BiscuitHipError
     p = (params or TrainParams()).validate()
@@ -267,27 +420,72 @@ def train_head(engine, cache, rows, labels, *, init='model', params=None, seed=N
     else:
         raise ValueError("init is 'model', 'glorot' or a head tensor dict")
     dev = engine.device
+    B = int(p.batch_size)
+    validating = val_rows is not None and len(val_rows) > 0
+    if validating:
+        val_rows = np.asarray(val_rows, np.int64).reshape(-1)
+        val_labels = np.asarray(val_labels).reshape(-1)
+        if len(val_labels) != len(val_rows) or not np.isin(val_labels, (0, 1)).all() or val_rows.min() < 0 or val_rows.max() >= len(cache):
+            raise ValueError('fit_head: a 0/1 label for each validation row, every one inside the cache')
+        n_val = min(int(p.validation_steps) * B, len(val_rows))
+        if n_val > HEAD_VALIDATE_MAX_ROWS:
+            raise ValueError(f'a check scores validation_steps x batch_size rows, at most {HEAD_VALIDATE_MAX_ROWS}')
+        # the walk, and its first n_val entries once more behind it: every window of a cyclic walk is then one slice
+        walk = np.random.default_rng([seed, VAL_STREAM]).permutation(len(val_rows))
+        walk = np.concatenate([walk, walk[:n_val]])
+        val_at, val_y = torch.from_numpy(val_rows[walk]).to(dev), torch.from_numpy(val_labels[walk].astype(np.uint8)).to(dev)
+        stopper, val_rate = EarlyStop.of(p), float(p.dropout) if p.validation_dropout else 0.0
+    balanced = p.training_balance not in ('none', 'tile')
+    if balanced:
+        slide_idx = np.asarray(cache.slide_idx[rows] if slide_idx is None else slide_idx, np.int64).reshape(-1)
     w = torch.from_numpy(flatten_head(start)).to(dev)
     m, v, g = torch.zeros_like(w), torch.zeros_like(w), torch.empty_like(w)
-    B = int(p.batch_size)
-    losses, step = [], 0
+    losses, checks, step, stopped, state = [], [], 0, None, {}
     V, N = (int(cache.views.shape[0]), len(cache)) if getattr(cache, 'views', None) is not None else (0, len(cache))
     feats = cache.views.reshape(V * N, -1) if V else cache.feats
     for epoch in range(int(max(p.epochs))):
-        order = np.random.default_rng([seed, epoch]).permutation(len(rows))
+        draws = len(rows) if p.steps_per_epoch_override is None else int(p.steps_per_epoch_override) * B
+        order = balanced_rows(rows, slide_idx, labels, patients, p.training_balance, draws, seed, epoch, state) if balanced \
+            else epoch_order(len(rows), draws, seed, epoch)
         steps = -(-len(order) // B)
-        lr = [p.learning_rate_at(step + i) for i in range(steps)]
         at = rows[order] + (epoch % V) * N if V else rows[order]
-        out = engine.head_train_steps(w, m, v, feats, torch.from_numpy(at).to(dev),
-                                      torch.from_numpy(labels[order].astype(np.uint8)).to(dev), B, step, seed, lr, rate=p.dropout,
-                                      b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g)
-        losses.append(out.cpu().numpy())
-        step += steps
-    losses = np.concatenate(losses)
+        at, y = torch.from_numpy(at).to(dev), torch.from_numpy(labels[order].astype(np.uint8)).to(dev)
+        seg = int(p.validate_on_batch) if validating else steps
+        for a in range(0, steps, seg):
+            b = min(a + seg, steps)
+            lr = [p.learning_rate_at(step + i) for i in range(b - a)]
+            losses.append(engine.head_train_steps(w, m, v, feats, at[a * B:b * B], y[a * B:b * B], B, step, seed, lr, rate=p.dropout,
+                                                  b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g))
+            step += b - a
+            if not validating:
+                continue
+            c0 = len(checks) * n_val % len(val_rows)
+            stats, _, _ = engine.head_validate(w, cache.feats, val_at[c0:c0 + n_val], val_y[c0:c0 + n_val], step, seed, rate=val_rate)
+            stats = stats.cpu().numpy()
+            val_loss, val_acc = float(stats[0]) / n_val, float(stats[1]) / n_val
+            if not np.isfinite(val_loss):
+                raise BiscuitHipError(f'fit_head: the validation loss after step {step} is not finite (a feature that is not finite, '
+                                      'or a diverged run)')
+            stop = stopper.update(val_acc if p.early_stop_method == 'accuracy' else val_loss, epoch)
+            checks.append((step, val_loss, val_acc, stopper.ema))
+            if stop and p.early_stop:
+                stopped = step
+                break
+        if stopped is not None:
+            break
+    losses = np.concatenate([t.cpu().numpy() for t in losses])
     if not np.isfinite(losses).all():
         raise BiscuitHipError(f'train_head: the loss of step {int(np.flatnonzero(~np.isfinite(losses))[0])} is not finite '
                               '(a feature that is not finite, or a diverged run)')
-    return unflatten_head(w.cpu().numpy()), losses
+    return FitResult(unflatten_head(w.cpu().numpy()), losses, checks, stopped, step)
+
+
+def train_head(engine, cache, rows, labels, *, init='model', params=None, seed=None):
+    """``fit_head`` without validation -> ``(head tensor dict, losses float32 [steps])``: under the default schedule each epoch
+    walks a permutation from ``numpy.random.default_rng([seed, epoch])`` in batches of ``params.batch_size``, the last one short, as
+    one ``Engine.head_train_steps`` call per epoch."""
+    fit = fit_head(engine, cache, rows, labels, init=init, params=params, seed=seed)
+    return fit.head, fit.losses
 
 
 def head_engine(engine, head):
@@ -337,20 +535,33 @@ def predict(engine, cache, rows, head=None, mc_n=30, seed=None, *, y_true=None, 
 
 
 class HeadTrainer:
-    """The trainer ``train_cv`` calls per fold: ``(train_rows, val_rows, seed) -> (validation table, head)`` -- ``train_head`` on
-    the training rows, ``predict`` on the validation rows."""
+    """The trainer ``train_cv`` calls per fold: ``(train_rows, val_rows, seed) -> (validation table, head, FitResult)`` --
+    ``fit_head`` on the training rows (with the validation rows for its checks when ``params.early_stop`` is set), ``predict`` on
+    the validation rows.  ``patients`` (slide -> patient; a slide missing from it is its own) serves ``training_balance='patient'``."""
 
-    def __init__(self, engine, cache, slide_labels, *, params=None, init='model', mc_n=None, outcome='cohort'):
+    def __init__(self, engine, cache, slide_labels, *, params=None, init='model', mc_n=None, outcome='cohort', patients=None):
         self.engine, self.cache, self.params, self.init, self.outcome = engine, cache, params, init, outcome
         self.mc_n = int(mc_n or engine.hp.uq_n)
         self.y_slide = np.array([int(slide_labels[s]) for s in cache.slides], np.int64)
-        self.losses = []
+        names = sorted({(patients or {}).get(s, s) for s in cache.slides})
+        self.patient_of_slide = np.array([names.index((patients or {}).get(s, s)) for s in cache.slides], np.int64)
+        self.losses, self.fits = [], []
+
+    def fit(self, train_rows, val_rows, seed, params=None):
+        """``fit_head`` over ``train_rows``; ``val_rows`` (None: no checks) are the rows its validation checks walk."""
+        sidx = self.cache.slide_idx
+        val = {} if val_rows is None else {'val_rows': val_rows, 'val_labels': self.y_slide[sidx[val_rows]]}
+        fit = fit_head(self.engine, self.cache, train_rows, self.y_slide[sidx[train_rows]], slide_idx=sidx[train_rows],
+                       patients=self.patient_of_slide[sidx[train_rows]], init=self.init, params=self.params if params is None else params,
+                       seed=seed, **val)
+        self.losses.append(fit.losses)
+        self.fits.append(fit)
+        return fit
 
     def __call__(self, train_rows, val_rows, seed):
-        head, losses = train_head(self.engine, self.cache, train_rows, self.y_slide[self.cache.slide_idx[train_rows]], init=self.init,
-                                  params=self.params, seed=seed)
-        self.losses.append(losses)
-        return predict(self.engine, self.cache, val_rows, head, self.mc_n, seed, y_true=self.y_slide, outcome=self.outcome), head
+        fit = self.fit(train_rows, val_rows if (self.params or TrainParams()).early_stop else None, seed)
+        table = predict(self.engine, self.cache, val_rows, fit.head, self.mc_n, seed, y_true=self.y_slide, outcome=self.outcome)
+        return table, fit.head, fit
 
 
 # ------------------------------------------------------------------------------------------------------------ cross-validation
@@ -389,11 +600,60 @@ def fold_dir(out, label, k):
     return os.path.join(out, f'{label}-kfold{k}')
 
 
+def write_results_log(path, model_name, fit, epochs):
+    """``results_log.csv`` of one trained model, the file ``utils.find_cv_early_stop`` reads (``utils.py:164-187``): one row with
+    ``model_name`` (ending in ``epoch{E}``), ``steps``, and ``val_loss`` / ``val_acc`` of the last validation check (empty without
+    one); the column ``early_stop_batch`` is there only when the rule fired, since the reference tests for the column itself.  The
+    AUROC / AP columns of Slideflow's log are not written (``metrics.py`` computes those from the tables)."""
+    import pandas as pd
+    last = fit.checks[-1] if fit.checks else (None, None, None, None)
+    row = {'model_name': f'{model_name}-epoch{int(epochs)}', 'steps': int(fit.steps), 'val_loss': last[1], 'val_acc': last[2]}
+    if fit.early_stop_batch is not None:
+        row['early_stop_batch'] = int(fit.early_stop_batch)
+    pd.DataFrame([row]).to_csv(path, index=False)
+
+
+def find_cv_early_stop(out, label, k=3):
+    """``utils.find_cv_early_stop`` (``utils.py:164-187``) over ``OUT/LABEL-kfold1 .. k``: ``round(mean(...))`` of the folds'
+    ``early_stop_batch`` (Python's ``round``: a half goes to the even neighbour), None unless every fold's ``results_log.csv``
+    has the column."""
+    import pandas as pd
+    found = []
+    for j in range(1, int(k) + 1):
+        path = os.path.join(fold_dir(out, label, j), RESULTS_FILE)
+        if not os.path.exists(path):
+            return None
+        res = next(pd.read_csv(path).iterrows())[1]
+        if 'early_stop_batch' in res:
+            found.append(int(res['early_stop_batch']))
+    return round(mean(found)) if found and len(found) == int(k) else None
+
+
+def train_full(cache, slide_labels, out, label, *, stop_batch, trainer, seed=0):
+    """Step 5 of ``Experiment.run`` (``experiment.py:887-905``): the model the paper evaluates, trained on every labelled slide of
+    the cache with ``steps_per_epoch_override=stop_batch`` (what ``find_cv_early_stop`` detected) and no validation, under the
+    ``HeadTrainer``'s other settings -> the directory ``OUT/LABEL_FULL`` with ``head.npz``, ``slides.json`` and ``results_log.csv``."""
+    from dataclasses import replace
+    if int(stop_batch) < 1:
+        raise ValueError('train_full: stop_batch is at least 1')
+    train_s = sorted(s for s in cache.slides if s in slide_labels)
+    params = replace(trainer.params or TrainParams(), early_stop=False, steps_per_epoch_override=int(stop_batch))
+    fit = trainer.fit(cache.rows_of(train_s), None, int(seed), params=params)
+    d = os.path.join(out, f'{label}_FULL')
+    os.makedirs(d, exist_ok=True)
+    save_head(os.path.join(d, HEAD_FILE), fit.head)
+    with open(os.path.join(d, MANIFEST_FILE), 'w') as f:
+        json.dump({'training': train_s, 'validation': []}, f)
+    write_results_log(os.path.join(d, RESULTS_FILE), f'{label}_FULL', fit, max(params.epochs))
+    return d
+
+
 def train_cv(cache, slide_labels, out, label, k, trainer, *, patients=None, seed=0, restrict=None, outcome='cohort'):
     """``k``-fold cross-validation by patient over the cache's labelled slides (``restrict``: only these patients): fold ``j``
     trains on the other folds' slides and validates on its own -> ``OUT/LABEL-kfoldJ/tile_predictions_val_epoch1.csv`` with
     ``head.npz`` (when the trainer returns a head) and ``slides.json`` (the training and validation slides) beside it.
-    ``trainer(train_rows, val_rows, seed)`` -> ``(tile table, head or None)``: a ``HeadTrainer``.  -> the fold directories."""
+    ``trainer(train_rows, val_rows, seed)`` -> ``(tile table, head or None)`` or ``(tile table, head, FitResult)``: a
+    ``HeadTrainer``, whose third value also writes ``results_log.csv`` (``write_results_log``).  -> the fold directories."""
     patients = patients or {}
     slide_labels = {s: slide_labels[s] for s in cache.slides if s in slide_labels}
     plabel = _patient_labels(slide_labels, patients)
@@ -408,12 +668,15 @@ def train_cv(cache, slide_labels, out, label, k, trainer, *, patients=None, seed
         val_s = sorted(s for p in val_p for s in by_patient[p])
         train_s = sorted(s for f in folds if f is not val_p for p in f for s in by_patient[p])
         fold_seed = int(np.random.SeedSequence([*(int(v) for v in np.atleast_1d(seed)), j]).generate_state(1, np.uint32)[0])
-        table, head = trainer(cache.rows_of(train_s), cache.rows_of(val_s), fold_seed)
+        table, head, *fit = trainer(cache.rows_of(train_s), cache.rows_of(val_s), fold_seed)
         d = fold_dir(out, label, j)
         os.makedirs(d, exist_ok=True)
         predictions.write_tile_table(table, d, predictions.VAL_NAME, outcome)
         if head is not None:
             save_head(os.path.join(d, HEAD_FILE), head)
+        if fit:
+            write_results_log(os.path.join(d, RESULTS_FILE), os.path.basename(d), fit[0],
+                              max((getattr(trainer, 'params', None) or TrainParams()).epochs))
         with open(os.path.join(d, MANIFEST_FILE), 'w') as f:
             json.dump({'training': train_s, 'validation': val_s}, f)
         dirs.append(d)
@@ -543,9 +806,21 @@ def main(argv=None):
     ap.add_argument('--views', type=int, default=None, metavar='V', help='augmented views cached per tile; epoch e trains on view e %% V '
                     '(default: --epochs)')
     ap.add_argument('--cache', default=None, metavar='FILE', help='the feature cache (.npz): loaded when it exists, otherwise computed and saved')
+    ap.add_argument('--early-stop', nargs='?', const='accuracy', default=None, choices=['accuracy', 'loss'], metavar='METHOD',
+                    help="stop a training when the smoothed validation accuracy (or 'loss') no longer improves (the paper's models: accuracy)")
+    ap.add_argument('--balance', default='none', choices=list(BALANCES), metavar='KIND',
+                    help="training batches balanced by 'category' (the paper's models), 'patient' or 'slide'; default: none")
+    ap.add_argument('--validate-on-batch', type=int, default=32, metavar='N', help='with --early-stop: a validation check every N steps')
+    ap.add_argument('--validation-steps', type=int, default=32, metavar='N', help='with --early-stop: batches of validation tiles per check')
+    ap.add_argument('--full', action='store_true', help='after the cross-validation, train the model on every slide for the number of '
+                    'steps at which the outer folds stopped early (needs --early-stop) -> OUT/LABEL_FULL')
     args = ap.parse_args(argv)
     if args.epochs < 1 or args.outer_k < 2 or args.inner_k < 2:
         raise SystemExit('--epochs >= 1, --outer-k >= 2 and --inner-k >= 2')
+    if args.validate_on_batch < 1 or args.validation_steps < 1:
+        raise SystemExit('--validate-on-batch >= 1 and --validation-steps >= 1')
+    if args.full and not args.early_stop:
+        raise SystemExit('--full trains for the steps at which the folds stopped early: it needs --early-stop')
     from . import augment as A
     try:
         letters = A.parse(args.augment)
@@ -587,13 +862,24 @@ def main(argv=None):
     try:
         cache = cached_features(eng, slides, args.cache, normalizer=hp.normalizer, norm_fit=norm_fit, augment=letters, views=n_views or None,
                                 seed=args.seed)
-        trainer = HeadTrainer(eng, cache, labels, params=TrainParams(epochs=[args.epochs], dropout=hp.dropout, augment=letters),
-                              init=args.init, mc_n=mc_n, outcome=args.outcome)
         try:
+            params = TrainParams(epochs=[args.epochs], dropout=hp.dropout, augment=letters, early_stop=bool(args.early_stop),
+                                 early_stop_method=args.early_stop or 'accuracy', training_balance=args.balance,
+                                 validate_on_batch=args.validate_on_batch, validation_steps=args.validation_steps).validate()
+            trainer = HeadTrainer(eng, cache, labels, params=params, init=args.init, mc_n=mc_n, outcome=args.outcome, patients=patients)
             dirs = train_nested_cv(cache, labels, args.out, args.label, trainer, outer_k=args.outer_k, inner_k=args.inner_k,
                                    patients=patients, seed=args.seed, outcome=args.outcome)
         except ValueError as e:
             raise SystemExit(str(e)) from None
+        full = None
+        if args.full:
+            stop_batch = find_cv_early_stop(args.out, args.label, k=args.outer_k)
+            if stop_batch is None:
+                print(f'--full: not every one of the {args.outer_k} outer folds stopped early, so no stop batch is detected and no '
+                      'full model is trained')
+            else:
+                full = {'stop_batch': stop_batch, 'dir': train_full(cache, labels, args.out, args.label, stop_batch=stop_batch,
+                                                                    trainer=trainer, seed=args.seed)}
     finally:
         eng.close()
     from .errors import ThresholdError
@@ -605,10 +891,18 @@ def main(argv=None):
                          'any inner fold of an outer fold: too few slides, or none predicted wrongly)') from None
     frame.to_csv(os.path.join(args.out, 'nested_cv.csv'), index=False)
     th = {k: (None if v is None else float(v)) for k, v in th.items()}
+    schedule = {}                            # (only what the new flags asked for: without them the files are what they were)
+    if args.early_stop:
+        schedule.update(early_stop=args.early_stop, validate_on_batch=args.validate_on_batch, validation_steps=args.validation_steps)
+    if args.balance != 'none':
+        schedule['balance'] = args.balance
+    if args.full:
+        schedule['full'] = full
     with open(os.path.join(args.out, 'thresholds.json'), 'w') as f:
         json.dump({'thresholds': th, 'label_values': values, 'outer_k': args.outer_k, 'inner_k': args.inner_k, 'seed': args.seed,
-                   'augment': letters, 'views': n_views}, f, indent=1)
-    print(json.dumps({'tiles': len(cache), 'slides': len(cache.slides), 'folds': len(dirs), 'thresholds': th}))
+                   'augment': letters, 'views': n_views, **schedule}, f, indent=1)
+    print(json.dumps({'tiles': len(cache), 'slides': len(cache.slides), 'folds': len(dirs), 'thresholds': th,
+                      **({'full': full} if args.full else {})}))
 
 
 if __name__ == '__main__':

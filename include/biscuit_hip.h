@@ -675,11 +675,26 @@ int bq_delong(bq_ctx* ctx, const double* d_scores, const uint8_t* d_label, int k
  *
  * d_ws: bq_head_train_workspace_bytes(n) bytes (n = batch; 0 for an n the calls refuse), 256-byte aligned, caller-owned, contents
  * unspecified on entry; BQ_ERR_WORKSPACE below that.  All allocate nothing and are enqueued without a host synchronisation; a bad
- * argument is BQ_ERR_ARG with nothing enqueued. */
+ * argument is BQ_ERR_ARG with nothing enqueued.
+ *
+ * bq_head_validate: the forward half of bq_head_grad on the same d_params, for scoring a head in the middle of its training
+ * (DESIGN.md section 7 "Training schedule"): 1 <= n <= 4096 rows gathered through d_rows, the same arithmetic (the exact-f32 MFMA
+ * GEMMs with their four accumulators, the logits on the vector ALU, softmax and the row's loss in float64 from the fp32 logits).
+ * rate == 0 is inference mode: no mask is drawn; rate > 0 draws the masks of the contract above with pass in the place of step.
+ * -> d_stats [2] float64: the sum of the rows' losses, and the number of rows whose larger logit is their label's (a tie goes to
+ * class 0); d_rowloss float64 [n] and d_hit uint8 [n], each or NULL: the rows' own loss and 0 / 1 hit.  A feature that is not finite,
+ * a row index outside 0 .. n_feat - 1 (never read) or a label above 1 gives that row a NaN loss and a hit of 0, and d_stats[0] is NaN.
+ * Every sum runs in a fixed order without floating-point atomics: the same bits every call; a row's loss and hit do not depend on n
+ * or on the row's place in d_rows.  d_params is only read.  d_ws: bq_head_validate_workspace_bytes(n) bytes (0 for an n the call
+ * refuses), under the rules of the training workspace above, which keeps its own limit of 1024. */
 size_t bq_head_train_workspace_bytes(int n);
 int bq_head_grad(bq_ctx* ctx, const float* d_params, const float* d_feats, int64_t n_feat, const int64_t* d_rows, const uint8_t* d_labels,
                  int n, int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, void* d_ws, size_t ws_bytes,
                  bq_stream_t stream);
+size_t bq_head_validate_workspace_bytes(int n);
+int bq_head_validate(bq_ctx* ctx, const float* d_params, const float* d_feats, int64_t n_feat, const int64_t* d_rows, const uint8_t* d_labels,
+                     int n, int64_t pass, uint64_t seed, double rate, double* d_stats, double* d_rowloss, uint8_t* d_hit, void* d_ws,
+                     size_t ws_bytes, bq_stream_t stream);
 int bq_head_adam(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, const float* d_grad, int64_t step, double lr, double b1, double b2,
                  double eps, bq_stream_t stream);
 int bq_head_train_steps(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, float* d_grad, const float* d_feats, int64_t n_feat,

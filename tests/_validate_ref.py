@@ -1,0 +1,106 @@
+"""Numpy restatement of ``bq_head_validate`` (DESIGN.md section 7 "Training schedule"): the forward half of tests/_train_ref.py row by
+row -- logits, the row's sparse categorical cross-entropy and whether the larger logit is the label's (``numpy.argmax``: a tie goes
+to class 0) -- in float64, and the same formulas with every array float32 (the twin whose distance from float64 the device
+tolerance is derived from).  The keep masks are ``_train_ref.keep_masks`` with step = pass; rate 0 keeps everything at scale 1.
+
+The cases of tests/test_gpu_head_validate.py: a cache of ``ROWS`` rows of ``_train_ref.cache``, ``_train_ref.head()``, one fixed
+order of all the rows and one label per row; the case of n rows is the first n of that order.  A row's logits depend on nothing
+but the row, so each rate is computed once over the cache and cut.
+
+The twin's figure for a mean, or for a single row, is one sample of float32's rounding error and can fall anywhere down to zero
+(an order tried first gave 1.4e-11 for its first row at rate 0.1); eight times such a sample is no yardstick.  ``ORDER_SEED`` is
+therefore the first seed of 0, 1, 2, ... whose order and labels give a twin figure of at least ``twin_floor`` in every case: half
+of sigma / sqrt(n), sigma the root mean square of the twin's own per-row loss error at that rate.  The choice looks at the float64
+and float32 restatements only; the GPU test asserts the floor before it uses a figure.
+"""
+import numpy as np
+
+from oracle import philox
+from tests import _train_ref as R
+
+ROWS = 4096
+NS = (1, 63, 64, 65, 1024, 1025, 4096)
+RATES = (0.0, 0.1, 0.5)
+SEED, PASS = 77, 3
+MARGIN = 1e-5
+ORDER_SEED = 47
+
+
+def logits(feat, w, keeps, rate, dtype=np.float64):
+    """feat [n, 2048] -> the logits [n, 2] in ``dtype`` arithmetic (``_train_ref.loss_and_grad``'s forward)."""
+    t = R.tensors(w, dtype)
+    scale, zero = dtype(philox.dropout_scale(rate)), dtype(0)
+    h = np.asarray(feat, dtype)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for layer, name in enumerate(R.HEAD):
+            z = np.where(keeps[layer], h * scale, zero) @ t[name + '/kernel'] + t[name + '/bias']
+            h = np.where(z < 0, zero, z) if layer < 2 else z
+    return h
+
+
+def row_losses(z, labels):
+    """-log softmax(z)[label] per row, in z's dtype."""
+    zs = z - z.max(axis=1, keepdims=True)
+    return -(zs - np.log(np.exp(zs).sum(axis=1, keepdims=True)))[np.arange(len(z)), np.asarray(labels, np.int64)]
+
+
+def case_rows(order_seed=ORDER_SEED):
+    """(rows int64 [ROWS]: every row of the cache once, the all-zero row 7 second; labels uint8 [ROWS])."""
+    rng = np.random.default_rng([13, ROWS, order_seed])
+    rows = rng.permutation(ROWS).astype(np.int64)
+    at = int(np.flatnonzero(rows == 7)[0])
+    rows[at], rows[1] = rows[1], 7
+    return rows, rng.integers(0, 2, ROWS).astype(np.uint8)
+
+
+_MEMO = {}
+
+
+def inputs():
+    """``(cache float32 [ROWS, 2048], head, rows, labels)``, made once."""
+    if 'in' not in _MEMO:
+        _MEMO['in'] = (R.cache(rows=ROWS), R.head(), *case_rows())
+    return _MEMO['in']
+
+
+def cache_logits(rate):
+    """``(float64, float32)`` logits [ROWS, 2] of every row of the cache in cache order, computed once per rate."""
+    if ('z', rate) not in _MEMO:
+        f, w, _, _ = inputs()
+        keeps = R.keep_masks(SEED, np.arange(ROWS), PASS, rate)
+        _MEMO['z', rate] = (logits(f, w, keeps, rate, np.float64), logits(f, w, keeps, rate, np.float32))
+    return _MEMO['z', rate]
+
+
+def reference(rate, order_seed=ORDER_SEED):
+    """Over all ROWS rows in ``case_rows()`` order: ``{'loss64', 'loss32': the rows' losses, 'hit': uint8, 'margin': |z1 - z0| in
+    float64, 'pred1': the share of rows predicted class 1, 'sigma': the rms of loss32 - loss64}``."""
+    rows, labels = case_rows(order_seed)
+    z64, z32 = (z[rows] for z in cache_logits(rate))
+    pred = z64.argmax(axis=1)
+    l64, l32 = row_losses(z64, labels), row_losses(z32, labels)
+    return {'loss64': l64, 'loss32': l32, 'hit': (pred == labels).astype(np.uint8), 'margin': np.abs(z64[:, 1] - z64[:, 0]),
+            'pred1': float(pred.mean()), 'sigma': float(np.sqrt(np.mean((l32.astype(np.float64) - l64) ** 2)))}
+
+
+def twin(ref, n):
+    """The float32 twin's two figures for the first n rows: ``(R.rel_err of the rows' losses, of their float32 mean)``."""
+    l64, l32 = ref['loss64'][:n], ref['loss32'][:n]
+    return R.rel_err(l32, l64), R.rel_err(l32.mean(dtype=np.float32), l64.mean())
+
+
+def twin_floor(ref, n):
+    """What a twin figure of the first n rows must reach to count as a sample of float32's error: ``(for the rows' losses, for
+    their mean)``, in ``twin``'s units."""
+    l64 = ref['loss64'][:n]
+    half = 0.5 * ref['sigma'] / np.sqrt(n)
+    return (half if n == 1 else 0.5 * ref['sigma']) / float(np.abs(l64).max()), half / abs(float(l64.mean()))
+
+
+def first_order_seed(limit=1000):
+    """The rule ``ORDER_SEED`` was chosen by."""
+    for s in range(limit):
+        refs = [reference(rate, s) for rate in RATES]
+        if all(t >= f for ref in refs for n in NS for t, f in zip(twin(ref, n), twin_floor(ref, n))):
+            return s
+    return None

@@ -4,6 +4,8 @@
 
 * microseconds per training step at the given batch (wall time of ``Engine.head_train_steps`` over ``--steps`` steps after a warm-up
   call, one synchronisation at the end), and the split between the launches from the library's own profiling classes;
+* one validation check of 32 x batch rows in the middle of a training (``Engine.head_validate``), the same rows through
+  ``train.head_engine`` + ``mc_head`` -- the only way to score a head before it --, and the share a check adds to 32 steps;
 * the feature-cache rate: ``train.cache_features`` over resident synthetic slides, tiles per second (host decode is not part of it:
   the tiles are in memory, as in ``bench.py``);
 * wall time of ``train_nested_cv`` (3 x (1 + 5) trainings with their validation tables) and ``thresholds_from_nested_cv`` over a
@@ -55,6 +57,58 @@ def bench_steps(eng, steps, batch):
     return {'measure': 'train_step', 'batch': batch, 'steps': steps, 'us_per_step_wall_median': round(float(np.median(walls)), 1),
             'us_per_step_wall_runs': [round(x, 1) for x in walls], 'us_per_launch_by_class': split, 'us_grad_launches': round(grad, 1),
             'us_adam_launch': split.get('head_train_adam')}
+
+
+def bench_validate(eng, batch, val_steps=32, window=32, repeats=20):
+    """One validation check of ``val_steps * batch`` rows through ``Engine.head_validate`` (the 16 bytes read back, as ``fit_head``
+    does), the same rows through the only route there was before it -- ``train.head_engine`` + ``mc_head`` with one pass, the engine's
+    construction included --, and what a check adds to a window of ``window`` training steps."""
+    dev = eng.device
+    n = val_steps * batch
+    rng = np.random.default_rng(2)
+    feats = torch.from_numpy(np.abs(rng.standard_normal((8192, 2048))).astype(np.float32)).to(dev)
+    rows = torch.from_numpy(rng.permutation(8192)[:n].astype(np.int64)).to(dev)
+    labels = torch.from_numpy(rng.integers(0, 2, n).astype(np.uint8)).to(dev)
+    head = T.glorot_head(1)
+    w = torch.from_numpy(T.flatten_head(head)).to(dev)
+    check = lambda: eng.head_validate(w, feats, rows, labels, 7, 1, rate=0.0)[0].cpu()
+    check()
+    walls = []
+    for _ in range(repeats):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        check()
+        walls.append((time.perf_counter() - t0) * 1e6)
+    eng.profile_enable(True)
+    check()
+    split = {p.name: round(p.ms / max(p.launches, 1) * 1e3, 2) for p in eng.profile_read() if p.name.startswith('head_validate_')}
+    eng.profile_enable(False)
+    m, v = torch.zeros_like(w), torch.zeros_like(w)
+    train_rows, train_labels, lr = rows[:window * batch].contiguous(), labels[:window * batch].contiguous(), [1e-4] * window
+    eng.head_train_steps(w.clone(), m, v, feats, train_rows, train_labels, batch, 0, 1, lr)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    eng.head_train_steps(w.clone(), m, v, feats, train_rows, train_labels, batch, window, 1, lr)
+    torch.cuda.synchronize(dev)
+    window_us = (time.perf_counter() - t0) * 1e6
+    old = []
+    for _ in range(3):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        other = T.head_engine(eng, head)
+        try:
+            for a in range(0, n, other.max_batch):
+                r = rows[a:a + other.max_batch].contiguous()
+                mean, _ = other.mc_head(feats.index_select(0, r).contiguous(), 1, 1, tile_idx0=0, tile_idx=r)
+                mean.cpu()
+        finally:
+            other.close()
+        old.append((time.perf_counter() - t0) * 1e6)
+    us = float(np.median(walls))
+    return {'measure': 'validation_check', 'rows': n, 'batch': batch, 'us_head_validate_wall_median': round(us, 1),
+            'us_head_validate_wall_min_max': [round(min(walls), 1), round(max(walls), 1)], 'us_per_launch_by_class': split,
+            'us_head_engine_mc_head_wall_median': round(float(np.median(old)), 1), 'us_head_engine_mc_head_runs': [round(x, 1) for x in old],
+            'window_steps': window, 'us_window_wall': round(window_us, 1), 'check_share_of_window_and_check': round(us / (us + window_us), 3)}
 
 
 def bench_cache(eng, n_slides, n_tiles):
@@ -110,6 +164,8 @@ def main(argv=None):
     eng = Engine(synthetic_weights(1), dtype='f16', max_batch=256, max_mc=args.mc)
     try:
         print(json.dumps(bench_steps(eng, args.steps, args.batch)), flush=True)
+        if args.batch * 32 <= Engine.HEAD_VALIDATE_MAX_ROWS:
+            print(json.dumps(bench_validate(eng, args.batch)), flush=True)
         if args.cache_slides > 0:
             print(json.dumps(bench_cache(eng, args.cache_slides, args.cache_tiles)), flush=True)
         if args.cv_slides > 0:
