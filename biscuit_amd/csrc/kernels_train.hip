@@ -62,6 +62,19 @@ __device__ __forceinline__ float4 drop4(float4 v, unsigned g, unsigned ctr, cons
     return o;
 }
 
+// The derivative v of drop4's four units through their dropout and the ReLU in front of it, whose output there was h: scale v where
+// the unit was kept and h > 0, else 0.
+__device__ __forceinline__ float4 drop_relu_grad4(float4 h, float4 v, unsigned g, unsigned ctr, const Drop& d) {
+    unsigned r[4];
+    philox4x32_10(g, d.layer, d.step, ctr, d.seed_lo, d.seed_hi, r);
+    float4 o;
+    o.x = (h.x > 0.f && r[0] >= d.thresh) ? v.x * d.scale : 0.f;
+    o.y = (h.y > 0.f && r[1] >= d.thresh) ? v.y * d.scale : 0.f;
+    o.z = (h.z > 0.f && r[2] >= d.thresh) ? v.z * d.scale : 0.f;
+    o.w = (h.w > 0.f && r[3] >= d.thresh) ? v.w * d.scale : 0.f;
+    return o;
+}
+
 // what drop4 gives at rate 0 (every unit kept, scale 1), without the draw
 __device__ __forceinline__ float4 finite4(float4 v) {
     const float nan = __builtin_nanf("");
@@ -221,15 +234,9 @@ __global__ void __launch_bounds__(256) train_gemm_kernel(const TrainGemm p) {
             for (int q = 0; q < 4; ++q) {
                 const int n = n0 + wn * 32 + 8 * q + 4 * h;
                 const size_t o = (size_t)m * p.ldo + n;
-                const float4 hv = *reinterpret_cast<const float4*>(p.h + o);
-                unsigned r[4];
-                philox4x32_10((unsigned)(n >> 2), p.drop.layer, p.drop.step, ctr, p.drop.seed_lo, p.drop.seed_hi, r);
-                float4 v;
-                v.x = (hv.x > 0.f && r[0] >= p.drop.thresh) ? acc[4 * q + 0] * p.drop.scale : 0.f;
-                v.y = (hv.y > 0.f && r[1] >= p.drop.thresh) ? acc[4 * q + 1] * p.drop.scale : 0.f;
-                v.z = (hv.z > 0.f && r[2] >= p.drop.thresh) ? acc[4 * q + 2] * p.drop.scale : 0.f;
-                v.w = (hv.w > 0.f && r[3] >= p.drop.thresh) ? acc[4 * q + 3] * p.drop.scale : 0.f;
-                *reinterpret_cast<float4*>(p.out + o) = v;
+                const float4 dv = make_float4(acc[4 * q + 0], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+                *reinterpret_cast<float4*>(p.out + o) =
+                    drop_relu_grad4(*reinterpret_cast<const float4*>(p.h + o), dv, (unsigned)(n >> 2), ctr, p.drop);
             }
         }
     } else {
@@ -254,19 +261,6 @@ __device__ __forceinline__ float block_sum_256(float v, float* lds) {
     return ((lds[0] + lds[1]) + lds[2]) + lds[3];
 }
 
-// The logits of one row by a workgroup of 256 threads, thread t on the units 4 t .. 4 t + 3 (hv: the row's h1 there; wa, wb: W2's rows
-// of those units): z = drop(h1) W2 + b2, an fmaf chain per thread, then block_sum_256.  DROP false is rate 0 without the draw.
-template <bool DROP>
-__device__ __forceinline__ void row_logits(float4 hv, float4 wa, float4 wb, const float* __restrict__ b2, unsigned ctr, const Drop& d,
-                                           float* lds, float& z0, float& z1) {
-    const float4 u = DROP ? drop4(hv, (unsigned)threadIdx.x, ctr, d) : finite4(hv);
-    // units 4 tid .. 4 tid + 3: (wa.x, wa.y), (wa.z, wa.w), (wb.x, wb.y), (wb.z, wb.w)
-    const float s0 = fmaf(u.w, wb.z, fmaf(u.z, wb.x, fmaf(u.y, wa.z, u.x * wa.x)));
-    const float s1 = fmaf(u.w, wb.w, fmaf(u.z, wb.y, fmaf(u.y, wa.w, u.x * wa.y)));
-    z0 = block_sum_256(s0, lds) + b2[0];
-    z1 = block_sum_256(s1, lds) + b2[1];
-}
-
 // The softmax and the row's loss in float64 from the fp32 logits, each rounded once (a few operations per row); all NaN for a label
 // above 1 or a logit that is NaN.
 __device__ __forceinline__ double row_loss(float z0, float z1, unsigned y, double& p0, double& p1) {
@@ -279,6 +273,33 @@ __device__ __forceinline__ double row_loss(float z0, float z1, unsigned y, doubl
     return loss;
 }
 
+// What both row kernels open with, a workgroup of 256 threads per row, thread t on the units 4 t .. 4 t + 3: the loads (hv: the row's
+// h1 there; wa, wb: W2's rows of those units), the logits z = drop(h1) W2 + b2 -- an fmaf chain per thread, then block_sum_256; DROP
+// false is rate 0 without the draw --, the label y and, in the threads that `score`, row_loss (loss, p0, p1; 0 in the others).
+struct Row { float4 hv, wa, wb; unsigned ctr, y; float z0, z1; double loss, p0, p1; };
+
+template <bool DROP>
+__device__ __forceinline__ Row row_forward(const float* __restrict__ h1, const float* __restrict__ w2, const float* __restrict__ b2,
+                                           const long long* __restrict__ rows, const unsigned char* __restrict__ label, const Drop& d,
+                                           float* lds, bool score) {
+    const int m = blockIdx.x, tid = threadIdx.x;
+    Row r;
+    r.ctr = (unsigned)rows[m];
+    r.hv = *reinterpret_cast<const float4*>(h1 + (size_t)m * D_H + tid * 4);
+    r.wa = *reinterpret_cast<const float4*>(w2 + tid * 8);
+    r.wb = *reinterpret_cast<const float4*>(w2 + tid * 8 + 4);
+    const float4 u = DROP ? drop4(r.hv, (unsigned)tid, r.ctr, d) : finite4(r.hv);
+    // units 4 tid .. 4 tid + 3: (wa.x, wa.y), (wa.z, wa.w), (wb.x, wb.y), (wb.z, wb.w)
+    const float s0 = fmaf(u.w, r.wb.z, fmaf(u.z, r.wb.x, fmaf(u.y, r.wa.z, u.x * r.wa.x)));
+    const float s1 = fmaf(u.w, r.wb.w, fmaf(u.z, r.wb.y, fmaf(u.y, r.wa.w, u.x * r.wa.y)));
+    r.z0 = block_sum_256(s0, lds) + b2[0];
+    r.z1 = block_sum_256(s1, lds) + b2[1];
+    r.y = label[m];
+    r.loss = r.p0 = r.p1 = 0.0;
+    if (score) r.loss = row_loss(r.z0, r.z1, r.y, r.p0, r.p1);
+    return r;
+}
+
 // A workgroup per batch row: logits = drop(h1) W2 + b2, softmax, the row's loss, dlog = (p - onehot) / n, and
 // dz1 = (h1 > 0 and kept) ? scale (dlog . W2[k]) : 0.
 __global__ void __launch_bounds__(256) train_logits_kernel(const float* __restrict__ h1, const float* __restrict__ w2,
@@ -287,27 +308,16 @@ __global__ void __launch_bounds__(256) train_logits_kernel(const float* __restri
                                                            float* __restrict__ dz1, float* __restrict__ dlog, double* __restrict__ rowloss) {
     __shared__ float lds[4];
     const int m = blockIdx.x, tid = threadIdx.x;
-    const unsigned ctr = (unsigned)rows[m];
-    const float4 hv = *reinterpret_cast<const float4*>(h1 + (size_t)m * D_H + tid * 4);
-    const float4 wa = *reinterpret_cast<const float4*>(w2 + tid * 8), wb = *reinterpret_cast<const float4*>(w2 + tid * 8 + 4);
-    float z0, z1;
-    row_logits<true>(hv, wa, wb, b2, ctr, d, lds, z0, z1);
-    const unsigned y = label[m];
-    double p0, p1;
-    const double loss = row_loss(z0, z1, y, p0, p1);
-    const float g0 = (float)((p0 - (y == 0u ? 1.0 : 0.0)) / (double)n), g1 = (float)((p1 - (y == 1u ? 1.0 : 0.0)) / (double)n);
+    const Row r = row_forward<true>(h1, w2, b2, rows, label, d, lds, true);
+    const float g0 = (float)((r.p0 - (r.y == 0u ? 1.0 : 0.0)) / (double)n), g1 = (float)((r.p1 - (r.y == 1u ? 1.0 : 0.0)) / (double)n);
     if (tid == 0) {
         dlog[2 * m] = g0;
         dlog[2 * m + 1] = g1;
-        rowloss[m] = loss;
+        rowloss[m] = r.loss;
     }
-    unsigned r[4];
-    philox4x32_10((unsigned)tid, d.layer, d.step, ctr, d.seed_lo, d.seed_hi, r);
-    float4 o;
-    o.x = (hv.x > 0.f && r[0] >= d.thresh) ? d.scale * fmaf(g1, wa.y, g0 * wa.x) : 0.f;
-    o.y = (hv.y > 0.f && r[1] >= d.thresh) ? d.scale * fmaf(g1, wa.w, g0 * wa.z) : 0.f;
-    o.z = (hv.z > 0.f && r[2] >= d.thresh) ? d.scale * fmaf(g1, wb.y, g0 * wb.x) : 0.f;
-    o.w = (hv.w > 0.f && r[3] >= d.thresh) ? d.scale * fmaf(g1, wb.w, g0 * wb.z) : 0.f;
+    const float4 dv = make_float4(fmaf(g1, r.wa.y, g0 * r.wa.x), fmaf(g1, r.wa.w, g0 * r.wa.z), fmaf(g1, r.wb.y, g0 * r.wb.x),
+                                  fmaf(g1, r.wb.w, g0 * r.wb.z));
+    float4 o = drop_relu_grad4(r.hv, dv, (unsigned)tid, r.ctr, d);
     if (g0 != g0 || g1 != g1) o = make_float4(g0, g0, g0, g0);       // a NaN row stays NaN where its ReLU would have cut it
     *reinterpret_cast<float4*>(dz1 + (size_t)m * D_H + tid * 4) = o;
 }
@@ -321,19 +331,13 @@ __global__ void __launch_bounds__(256) validate_logits_kernel(const float* __res
                                                               unsigned char* __restrict__ hit, double* __restrict__ out_loss,
                                                               unsigned char* __restrict__ out_hit) {
     __shared__ float lds[4];
-    const int m = blockIdx.x, tid = threadIdx.x;
-    const float4 hv = *reinterpret_cast<const float4*>(h1 + (size_t)m * D_H + tid * 4);
-    const float4 wa = *reinterpret_cast<const float4*>(w2 + tid * 8), wb = *reinterpret_cast<const float4*>(w2 + tid * 8 + 4);
-    float z0, z1;
-    row_logits<DROP>(hv, wa, wb, b2, (unsigned)rows[m], d, lds, z0, z1);
-    if (tid == 0) {
-        const unsigned y = label[m];
-        double p0, p1;
-        const double loss = row_loss(z0, z1, y, p0, p1);
-        const unsigned char ok = (loss == loss && (z1 > z0 ? 1u : 0u) == y) ? 1 : 0;
-        rowloss[m] = loss;
+    const int m = blockIdx.x;
+    const Row r = row_forward<DROP>(h1, w2, b2, rows, label, d, lds, threadIdx.x == 0);
+    if (threadIdx.x == 0) {
+        const unsigned char ok = (r.loss == r.loss && (r.z1 > r.z0 ? 1u : 0u) == r.y) ? 1 : 0;
+        rowloss[m] = r.loss;
         hit[m] = ok;
-        if (out_loss) out_loss[m] = loss;
+        if (out_loss) out_loss[m] = r.loss;
         if (out_hit) out_hit[m] = ok;
     }
 }
@@ -453,96 +457,124 @@ __global__ void __launch_bounds__(256) train_adam_kernel(float* __restrict__ w, 
 }
 
 inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
+constexpr int VALIDATE_MAX_N = 4096;            // the reference's validation_steps x batch_size, 32 x 128
 
-// h0 | h1 | dz1 | dz0, each [n][1024] | dlog [n][2] | rowloss f64 [n]
-size_t train_workspace_bytes(int n) {
-    if (n < 1 || n > MAX_N) return 0;
-    return 4 * al((size_t)n * D_H * 4) + al((size_t)n * 2 * 4) + al((size_t)n * 8);
+// The two layouts: the regions in order, each rounded up to 256 bytes, and their total (all a null ws gives).
+struct TrainWs { float *h0, *h1, *dz1, *dz0, *dlog; double* rowloss; size_t total; };
+TrainWs train_ws(void* ws, size_t n) {          // bq_head_grad's: h0 | h1 | dz1 | dz0, each [n][1024] | dlog [n][2] | rowloss f64 [n]
+    uintptr_t p = (uintptr_t)ws;
+    TrainWs w{};
+    w.h0 = (float*)p; p += al(n * D_H * 4);
+    w.h1 = (float*)p; p += al(n * D_H * 4);
+    w.dz1 = (float*)p; p += al(n * D_H * 4);
+    w.dz0 = (float*)p; p += al(n * D_H * 4);
+    w.dlog = (float*)p; p += al(n * 2 * 4);
+    w.rowloss = (double*)p; p += al(n * 8);
+    w.total = p - (uintptr_t)ws;
+    return w;
+}
+struct ValidateWs { float *h0, *h1; double* rowloss; unsigned char* hit; size_t total; };
+ValidateWs validate_ws(void* ws, size_t n) {    // bq_head_validate's: h0 | h1, each [n][1024] | rowloss f64 [n] | hit u8 [n]
+    uintptr_t p = (uintptr_t)ws;
+    ValidateWs w{};
+    w.h0 = (float*)p; p += al(n * D_H * 4);
+    w.h1 = (float*)p; p += al(n * D_H * 4);
+    w.rowloss = (double*)p; p += al(n * 8);
+    w.hit = (unsigned char*)p; p += al(n);
+    w.total = p - (uintptr_t)ws;
+    return w;
 }
 
-template <int AM, int BM, int EPI>
-void launch_gemm(const TrainGemm& p, hipStream_t s) {
-    hipLaunchKernelGGL((train_gemm_kernel<AM, BM, EPI>), dim3(p.N / TN, (p.M + TM - 1) / TM), dim3(256), 0, s, p);
-}
-
-struct GradArgs {
+// What the entries over gathered rows take alike.
+struct Batch {
     const float* params; const float* feats; long long n_feat; const long long* rows; const unsigned char* labels; int n;
-    long long step; uint64_t seed; unsigned thresh; float scale; float* grad; float* loss; void* ws;
+    long long step;             // the Philox pass: bq_head_validate's `pass`
+    double rate; void* ws;
 };
 
-std::string bad_grad_args(const char* entry, const void* params, const void* feats, int64_t n_feat, const void* rows, const void* labels, int n,
-                          int64_t step, double rate, const void* grad, const void* loss, const void* ws) {
+inline bool aligned(const void* p, uintptr_t a) { return p && !((uintptr_t)p & (a - 1)); }
+
+// The refusal of a gathered batch, "" for none.  max_n: the entry's row limit; counter: what the entry calls the Philox pass; own_ok:
+// the pointers that are the entry's own are there and aligned; pointers: the entry's text for one, of the batch or its own, that is not.
+std::string bad_batch(bq_ctx* c, const char* entry, const Batch& b, int max_n, const char* counter, bool own_ok, const char* pointers) {
     const std::string e(entry);
-    if (n < 1 || n > MAX_N) return e + ": 1 <= n <= 1024";
-    if (n_feat < 1 || step < 0 || step > 0xffffffffLL) return e + ": an empty feature cache, or a step outside 0 .. 2^32 - 1";
-    if (!(rate >= 0.0) || !(rate < 1.0)) return e + ": the rate must lie in [0, 1)";
-    if (!params || !feats || !rows || !labels || !grad || !loss || !ws || ((uintptr_t)params & 15) || ((uintptr_t)feats & 15) ||
-        ((uintptr_t)grad & 15) || ((uintptr_t)rows & 7) || ((uintptr_t)loss & 3) || ((uintptr_t)ws & 255))
-        return e + ": bad argument (null pointer, params, feats or grad not 16-byte, rows not 8-byte or the workspace not 256-byte aligned)";
+    if (!c) return e + ": null context";
+    if (b.n < 1 || b.n > max_n) return e + ": 1 <= n <= " + std::to_string(max_n);
+    if (b.n_feat < 1 || b.step < 0 || b.step > 0xffffffffLL) return e + ": an empty feature cache, or a " + counter + " outside 0 .. 2^32 - 1";
+    if (!(b.rate >= 0.0) || !(b.rate < 1.0)) return e + ": the rate must lie in [0, 1)";
+    if (!aligned(b.params, 16) || !aligned(b.feats, 16) || !aligned(b.rows, 8) || !b.labels || !aligned(b.ws, 256) || !own_ok) return e + pointers;
     return "";
 }
 
-// The seven launches of one gradient, each a profiling class of its own (Adam's is the eighth of a step).
-int enqueue_grad(bq_ctx* c, const GradArgs& a, hipStream_t s) {
-    const int n = a.n;
-    unsigned char* p = (unsigned char*)a.ws;
-    float* h0 = (float*)p; p += al((size_t)n * D_H * 4);
-    float* h1 = (float*)p; p += al((size_t)n * D_H * 4);
-    float* dz1 = (float*)p; p += al((size_t)n * D_H * 4);
-    float* dz0 = (float*)p; p += al((size_t)n * D_H * 4);
-    float* dlog = (float*)p; p += al((size_t)n * 2 * 4);
-    double* rowloss = (double*)p;
-    const float* W0 = a.params + OFF_W0; const float* b0 = a.params + OFF_B0;
-    const float* W1 = a.params + OFF_W1; const float* b1 = a.params + OFF_B1;
-    const float* W2 = a.params + OFF_W2; const float* b2 = a.params + OFF_B2;
-    Drop d{0u, (unsigned)a.step, (unsigned)(a.seed & 0xffffffffu), (unsigned)(a.seed >> 32), a.thresh, a.scale};
-    const double fn = (double)n;
-    TrainGemm g{};
-    g.rows = a.rows; g.n_feat = a.n_feat;
+// bq_head_grad's and bq_head_train_steps': grad and loss are their own
+std::string bad_grad_args(bq_ctx* c, const char* entry, const Batch& b, const void* grad, const void* loss) {
+    return bad_batch(c, entry, b, MAX_N, "step", aligned(grad, 16) && aligned(loss, 4),
+                     ": bad argument (null pointer, params, feats or grad not 16-byte, rows not 8-byte or the workspace not 256-byte aligned)");
+}
+
+// The masks of a batch: set_dropout's rule (biscuit_hip.hip), the contract of oracle/philox.py, at pass b.step; the layer is the launch's.
+Drop drop_of(const Batch& b, uint64_t seed) {
+    const double t = std::floor(b.rate * 4294967296.0);
+    return Drop{0u, (unsigned)b.step, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), t > 4294967295.0 ? 4294967295u : (unsigned)t,
+                (float)(1.0 / (1.0 - b.rate))};
+}
+
+struct ASrc { const float* p; int ld, gather; };   // A's source: rows of ld floats, a[rows[i]] (the feature cache) or a[i]
+
+// out [M][1024] = A [M][K] B, every operand in rows of 1024 floats but A; the launch names the orientations and the epilogue, `layer`
+// the mask of A (A_DROP_*) or of the epilogue (EPI_DX), epi the epilogue's operand: the bias (EPI_RELU), the layer's forward output (EPI_DX).
+template <int AM, int BM, int EPI>
+void launch_gemm(const Batch& b, Drop d, unsigned layer, ASrc a, const float* bm, const float* epi, float* out, int M, int K, hipStream_t s) {
+    TrainGemm p{};
+    p.a = a.p; p.lda = a.ld; p.gather = a.gather; p.b = bm; p.ldb = D_H; p.out = out; p.ldo = D_H;
+    p.bias = EPI == EPI_RELU ? epi : nullptr; p.h = EPI == EPI_DX ? epi : nullptr;
+    p.rows = b.rows; p.n_feat = b.n_feat; p.M = M; p.N = D_H; p.K = K; p.drop = d; p.drop.layer = layer;
+    hipLaunchKernelGGL((train_gemm_kernel<AM, BM, EPI>), dim3(p.N / TN, (p.M + TM - 1) / TM), dim3(256), 0, s, p);
+}
+
+// The forward half of a gradient and of a validation, two launches under the profiling classes fwd0 and fwd1.  AM: A_DROP_K, or
+// A_FINITE_K -- rate 0 without its draws.
+template <int AM>
+void enqueue_forward(bq_ctx* c, const Batch& b, const Drop& d, float* h0, float* h1, const char* fwd0, const char* fwd1, hipStream_t s) {
+    const double fn = (double)b.n;
     {   // h0 = relu(drop_0(x[rows]) W0 + b0)
-        ProfScope ps(c, s, "head_train_fwd0", 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_IN + (double)D_IN * D_H + fn * D_H));
-        TrainGemm q = g;
-        q.a = a.feats; q.lda = D_IN; q.gather = 1; q.b = W0; q.ldb = D_H; q.out = h0; q.ldo = D_H; q.bias = b0;
-        q.M = n; q.N = D_H; q.K = D_IN; q.drop = d; q.drop.layer = 0u;
-        launch_gemm<A_DROP_K, B_ROWS, EPI_RELU>(q, s);
+        ProfScope ps(c, s, fwd0, 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_IN + (double)D_IN * D_H + fn * D_H));
+        launch_gemm<AM, B_ROWS, EPI_RELU>(b, d, 0u, ASrc{b.feats, D_IN, 1}, b.params + OFF_W0, b.params + OFF_B0, h0, b.n, D_IN, s);
     }
     {   // h1 = relu(drop_1(h0) W1 + b1)
-        ProfScope ps(c, s, "head_train_fwd1", 2.0 * fn * D_H * D_H, 4.0 * (2.0 * fn * D_H + (double)D_H * D_H));
-        TrainGemm q = g;
-        q.a = h0; q.lda = D_H; q.gather = 0; q.b = W1; q.ldb = D_H; q.out = h1; q.ldo = D_H; q.bias = b1;
-        q.M = n; q.N = D_H; q.K = D_H; q.drop = d; q.drop.layer = 1u;
-        launch_gemm<A_DROP_K, B_ROWS, EPI_RELU>(q, s);
+        ProfScope ps(c, s, fwd1, 2.0 * fn * D_H * D_H, 4.0 * (2.0 * fn * D_H + (double)D_H * D_H));
+        launch_gemm<AM, B_ROWS, EPI_RELU>(b, d, 1u, ASrc{h0, D_H, 0}, b.params + OFF_W1, b.params + OFF_B1, h1, b.n, D_H, s);
     }
+}
+
+// The seven launches of one gradient, each a profiling class of its own (Adam's is the eighth of a step).
+int enqueue_grad(bq_ctx* c, const Batch& b, const Drop& d, float* grad, float* loss, hipStream_t s) {
+    const int n = b.n;
+    const TrainWs w = train_ws(b.ws, n);
+    const double fn = (double)n;
+    enqueue_forward<A_DROP_K>(c, b, d, w.h0, w.h1, "head_train_fwd0", "head_train_fwd1", s);
     Drop d2 = d; d2.layer = 2u;
     {   // logits, softmax, loss per row, dlog, dz1
         ProfScope ps(c, s, "head_train_logits", 8.0 * fn * D_H, 4.0 * (2.0 * fn * D_H + 2.0 * D_H));
-        hipLaunchKernelGGL(train_logits_kernel, dim3(n), dim3(256), 0, s, h1, W2, b2, a.rows, a.labels, n, d2, dz1, dlog, rowloss);
+        hipLaunchKernelGGL(train_logits_kernel, dim3(n), dim3(256), 0, s, w.h1, b.params + OFF_W2, b.params + OFF_B2, b.rows, b.labels, n, d2,
+                           w.dz1, w.dlog, w.rowloss);
     }
     {   // dz0 = (h0 > 0 and kept_1) ? scale (dz1 W1^T) : 0
         ProfScope ps(c, s, "head_train_dx1", 2.0 * fn * D_H * D_H, 4.0 * (3.0 * fn * D_H + (double)D_H * D_H));
-        TrainGemm q = g;
-        q.a = dz1; q.lda = D_H; q.gather = 0; q.b = W1; q.ldb = D_H; q.out = dz0; q.ldo = D_H; q.h = h0;
-        q.M = n; q.N = D_H; q.K = D_H; q.drop = d; q.drop.layer = 1u;
-        launch_gemm<A_PLAIN_K, B_KCONT, EPI_DX>(q, s);
+        launch_gemm<A_PLAIN_K, B_KCONT, EPI_DX>(b, d, 1u, ASrc{w.dz1, D_H, 0}, b.params + OFF_W1, w.h0, w.dz0, n, D_H, s);
     }
     {   // g_W1 = drop_1(h0)^T dz1
         ProfScope ps(c, s, "head_train_dw1", 2.0 * fn * D_H * D_H, 4.0 * (2.0 * fn * D_H + (double)D_H * D_H));
-        TrainGemm q = g;
-        q.a = h0; q.lda = D_H; q.gather = 0; q.b = dz1; q.ldb = D_H; q.out = a.grad + OFF_W1; q.ldo = D_H;
-        q.M = D_H; q.N = D_H; q.K = n; q.drop = d; q.drop.layer = 1u;
-        launch_gemm<A_DROP_T, B_ROWS, EPI_STORE>(q, s);
+        launch_gemm<A_DROP_T, B_ROWS, EPI_STORE>(b, d, 1u, ASrc{w.h0, D_H, 0}, w.dz1, nullptr, grad + OFF_W1, D_H, n, s);
     }
     {   // g_W0 = drop_0(x[rows])^T dz0
         ProfScope ps(c, s, "head_train_dw0", 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_IN + fn * D_H + (double)D_IN * D_H));
-        TrainGemm q = g;
-        q.a = a.feats; q.lda = D_IN; q.gather = 1; q.b = dz0; q.ldb = D_H; q.out = a.grad + OFF_W0; q.ldo = D_H;
-        q.M = D_IN; q.N = D_H; q.K = n; q.drop = d; q.drop.layer = 0u;
-        launch_gemm<A_DROP_T, B_ROWS, EPI_STORE>(q, s);
+        launch_gemm<A_DROP_T, B_ROWS, EPI_STORE>(b, d, 0u, ASrc{b.feats, D_IN, 1}, w.dz0, nullptr, grad + OFF_W0, D_IN, n, s);
     }
     {   // g_W2, g_b2, the loss, g_b1, g_b0
         ProfScope ps(c, s, "head_train_sums", 4.0 * fn * D_H + 2.0 * fn * D_H, 4.0 * 3.0 * fn * D_H);
-        hipLaunchKernelGGL(train_sums_kernel, dim3(SUM_BLOCKS), dim3(256), 0, s, h1, dz1, dz0, dlog, rowloss, a.rows, n, d2, a.grad + OFF_W2,
-                           a.grad + OFF_B2, a.grad + OFF_B1, a.grad + OFF_B0, a.loss);
+        hipLaunchKernelGGL(train_sums_kernel, dim3(SUM_BLOCKS), dim3(256), 0, s, w.h1, w.dz1, w.dz0, w.dlog, w.rowloss, b.rows, n, d2,
+                           grad + OFF_W2, grad + OFF_B2, grad + OFF_B1, grad + OFF_B0, loss);
     }
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
@@ -570,54 +602,23 @@ int enqueue_adam(bq_ctx* c, float* params, float* m, float* v, const float* grad
     return BQ_OK;
 }
 
-void dropout_of(double rate, unsigned& thresh, float& scale) {      // set_dropout's rule (biscuit_hip.hip), the contract of oracle/philox.py
-    const double t = std::floor(rate * 4294967296.0);
-    thresh = t > 4294967295.0 ? 4294967295u : (unsigned)t;
-    scale = (float)(1.0 / (1.0 - rate));
-}
-
-// bq_head_validate: the forward half of enqueue_grad over up to 4096 rows (the reference's validation_steps x batch_size, 32 x 128:
-// the forward GEMMs then launch 16 x 64 workgroups).  h0 | h1, each [n][1024] | rowloss f64 [n] | hit u8 [n]
-constexpr int VALIDATE_MAX_N = 4096;
-size_t validate_workspace_bytes(int n) {
-    if (n < 1 || n > VALIDATE_MAX_N) return 0;
-    return 2 * al((size_t)n * D_H * 4) + al((size_t)n * 8) + al((size_t)n);
-}
-
-// Four launches, each a profiling class of its own.  DROP false (rate 0): no mask is drawn anywhere.
+// bq_head_validate: the forward half of enqueue_grad over up to 4096 rows (the forward GEMMs then launch 16 x 64 workgroups), four
+// launches, each a profiling class of its own.  DROP false (rate 0): no mask is drawn anywhere.
 template <bool DROP>
-int enqueue_validate(bq_ctx* c, const float* params, const float* feats, long long n_feat, const long long* rows, const unsigned char* labels,
-                     int n, const Drop& d, double* stats, double* out_loss, unsigned char* out_hit, void* ws, hipStream_t s) {
-    constexpr int AM = DROP ? A_DROP_K : A_FINITE_K;
-    unsigned char* p = (unsigned char*)ws;
-    float* h0 = (float*)p; p += al((size_t)n * D_H * 4);
-    float* h1 = (float*)p; p += al((size_t)n * D_H * 4);
-    double* rowloss = (double*)p; p += al((size_t)n * 8);
-    unsigned char* hit = p;
+int enqueue_validate(bq_ctx* c, const Batch& b, const Drop& d, double* stats, double* out_loss, unsigned char* out_hit, hipStream_t s) {
+    const int n = b.n;
+    const ValidateWs w = validate_ws(b.ws, n);
     const double fn = (double)n;
-    TrainGemm g{};
-    g.rows = rows; g.n_feat = n_feat; g.b = nullptr; g.ldb = D_H; g.ldo = D_H; g.M = n; g.N = D_H; g.drop = d;
-    {   // h0 = relu(drop_0(x[rows]) W0 + b0)
-        ProfScope ps(c, s, "head_validate_fwd0", 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_IN + (double)D_IN * D_H + fn * D_H));
-        TrainGemm q = g;
-        q.a = feats; q.lda = D_IN; q.gather = 1; q.b = params + OFF_W0; q.out = h0; q.bias = params + OFF_B0; q.K = D_IN; q.drop.layer = 0u;
-        launch_gemm<AM, B_ROWS, EPI_RELU>(q, s);
-    }
-    {   // h1 = relu(drop_1(h0) W1 + b1)
-        ProfScope ps(c, s, "head_validate_fwd1", 2.0 * fn * D_H * D_H, 4.0 * (2.0 * fn * D_H + (double)D_H * D_H));
-        TrainGemm q = g;
-        q.a = h0; q.lda = D_H; q.gather = 0; q.b = params + OFF_W1; q.out = h1; q.bias = params + OFF_B1; q.K = D_H; q.drop.layer = 1u;
-        launch_gemm<AM, B_ROWS, EPI_RELU>(q, s);
-    }
+    enqueue_forward<DROP ? A_DROP_K : A_FINITE_K>(c, b, d, w.h0, w.h1, "head_validate_fwd0", "head_validate_fwd1", s);
     {   // logits, the row's loss and hit
         ProfScope ps(c, s, "head_validate_logits", 4.0 * fn * D_H, 4.0 * (fn * D_H + 2.0 * D_H));
         Drop d2 = d; d2.layer = 2u;
-        hipLaunchKernelGGL((validate_logits_kernel<DROP>), dim3(n), dim3(256), 0, s, h1, params + OFF_W2, params + OFF_B2, rows, labels, d2,
-                           rowloss, hit, out_loss, out_hit);
+        hipLaunchKernelGGL((validate_logits_kernel<DROP>), dim3(n), dim3(256), 0, s, w.h1, b.params + OFF_W2, b.params + OFF_B2, b.rows, b.labels,
+                           d2, w.rowloss, w.hit, out_loss, out_hit);
     }
     {   // the two sums
         ProfScope ps(c, s, "head_validate_sums", fn, 9.0 * fn);
-        hipLaunchKernelGGL(validate_sums_kernel, dim3(1), dim3(256), 0, s, rowloss, hit, n, stats);
+        hipLaunchKernelGGL(validate_sums_kernel, dim3(1), dim3(256), 0, s, w.rowloss, w.hit, n, stats);
     }
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
@@ -627,43 +628,34 @@ int enqueue_validate(bq_ctx* c, const float* params, const float* feats, long lo
 
 extern "C" {
 
-size_t bq_head_train_workspace_bytes(int n) { return train_workspace_bytes(n); }
+size_t bq_head_train_workspace_bytes(int n) { return n < 1 || n > MAX_N ? 0 : train_ws(nullptr, n).total; }
 
 int bq_head_grad(bq_ctx* c, const float* d_params, const float* d_feats, int64_t n_feat, const int64_t* d_rows, const uint8_t* d_labels, int n,
                  int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
-    if (!c) return fail(c, BQ_ERR_ARG, "bq_head_grad: null context");
-    const std::string bad = bad_grad_args("bq_head_grad", d_params, d_feats, n_feat, d_rows, d_labels, n, step, rate, d_grad, d_loss, d_ws);
+    const Batch b{d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, n, (long long)step, rate, d_ws};
+    const std::string bad = bad_grad_args(c, "bq_head_grad", b, d_grad, d_loss);
     if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
-    if (ws_bytes < train_workspace_bytes(n)) return fail(c, BQ_ERR_WORKSPACE, "bq_head_grad: workspace below bq_head_train_workspace_bytes(n)");
+    if (ws_bytes < bq_head_train_workspace_bytes(n)) return fail(c, BQ_ERR_WORKSPACE, "bq_head_grad: workspace below bq_head_train_workspace_bytes(n)");
     DeviceGuard guard(c->device);
-    GradArgs a{d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, n, (long long)step, seed, 0u, 1.f, d_grad, d_loss, d_ws};
-    dropout_of(rate, a.thresh, a.scale);
-    return enqueue_grad(c, a, (hipStream_t)stream);
+    return enqueue_grad(c, b, drop_of(b, seed), d_grad, d_loss, (hipStream_t)stream);
 }
 
-size_t bq_head_validate_workspace_bytes(int n) { return validate_workspace_bytes(n); }
+size_t bq_head_validate_workspace_bytes(int n) { return n < 1 || n > VALIDATE_MAX_N ? 0 : validate_ws(nullptr, n).total; }
 
 int bq_head_validate(bq_ctx* c, const float* d_params, const float* d_feats, int64_t n_feat, const int64_t* d_rows, const uint8_t* d_labels,
                      int n, int64_t pass, uint64_t seed, double rate, double* d_stats, double* d_rowloss, uint8_t* d_hit, void* d_ws,
                      size_t ws_bytes, bq_stream_t stream) {
-    if (!c) return fail(c, BQ_ERR_ARG, "bq_head_validate: null context");
-    if (n < 1 || n > VALIDATE_MAX_N) return fail(c, BQ_ERR_ARG, "bq_head_validate: 1 <= n <= 4096");
-    if (n_feat < 1 || pass < 0 || pass > 0xffffffffLL)
-        return fail(c, BQ_ERR_ARG, "bq_head_validate: an empty feature cache, or a pass outside 0 .. 2^32 - 1");
-    if (!(rate >= 0.0) || !(rate < 1.0)) return fail(c, BQ_ERR_ARG, "bq_head_validate: the rate must lie in [0, 1)");
-    if (!d_params || !d_feats || !d_rows || !d_labels || !d_stats || !d_ws || ((uintptr_t)d_params & 15) || ((uintptr_t)d_feats & 15) ||
-        ((uintptr_t)d_rows & 7) || ((uintptr_t)d_stats & 7) || ((uintptr_t)d_rowloss & 7) || ((uintptr_t)d_ws & 255))
-        return fail(c, BQ_ERR_ARG, "bq_head_validate: bad argument (null pointer, params or feats not 16-byte, rows, stats or rowloss not "
-                                   "8-byte or the workspace not 256-byte aligned)");
-    if (ws_bytes < validate_workspace_bytes(n))
+    const Batch b{d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, n, (long long)pass, rate, d_ws};
+    const std::string bad = bad_batch(c, "bq_head_validate", b, VALIDATE_MAX_N, "pass", aligned(d_stats, 8) && !((uintptr_t)d_rowloss & 7),
+                                      ": bad argument (null pointer, params or feats not 16-byte, rows, stats or rowloss not 8-byte or the "
+                                      "workspace not 256-byte aligned)");
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < bq_head_validate_workspace_bytes(n))
         return fail(c, BQ_ERR_WORKSPACE, "bq_head_validate: workspace below bq_head_validate_workspace_bytes(n)");
     DeviceGuard guard(c->device);
-    Drop d{0u, (unsigned)pass, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), 0u, 1.f};
-    dropout_of(rate, d.thresh, d.scale);
-    return rate > 0.0 ? enqueue_validate<true>(c, d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, n, d, d_stats, d_rowloss,
-                                               d_hit, d_ws, (hipStream_t)stream)
-                      : enqueue_validate<false>(c, d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, n, d, d_stats, d_rowloss,
-                                                d_hit, d_ws, (hipStream_t)stream);
+    const Drop d = drop_of(b, seed);
+    return rate > 0.0 ? enqueue_validate<true>(c, b, d, d_stats, d_rowloss, d_hit, (hipStream_t)stream)
+                      : enqueue_validate<false>(c, b, d, d_stats, d_rowloss, d_hit, (hipStream_t)stream);
 }
 
 int bq_head_adam(bq_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, int64_t step, double lr, double b1, double b2,
@@ -682,24 +674,21 @@ int bq_head_train_steps(bq_ctx* c, float* d_params, float* d_m, float* d_v, floa
     if (!c) return fail(c, BQ_ERR_ARG, "bq_head_train_steps: null context");
     if (steps < 1 || steps > (1 << 24) || last_n < 1 || last_n > batch || !h_lr)
         return fail(c, BQ_ERR_ARG, "bq_head_train_steps: 1 <= steps <= 2^24, 1 <= last_n <= batch and a learning rate per step");
-    std::string bad = bad_grad_args("bq_head_train_steps", d_params, d_feats, n_feat, d_rows, d_labels, batch, step0, rate, d_grad, d_losses, d_ws);
+    Batch b{d_params, d_feats, (long long)n_feat, (const long long*)d_rows, d_labels, batch, (long long)step0, rate, d_ws};
+    std::string bad = bad_grad_args(c, "bq_head_train_steps", b, d_grad, d_losses);
     if (bad.empty() && step0 + steps > 0x100000000LL) bad = "bq_head_train_steps: the steps pass 2^32";
     for (int i = 0; bad.empty() && i < steps; ++i) bad = bad_adam_args("bq_head_train_steps", d_params, d_m, d_v, d_grad, step0 + i, h_lr[i], b1, b2, eps);
     if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
-    if (ws_bytes < train_workspace_bytes(batch))
+    if (ws_bytes < bq_head_train_workspace_bytes(batch))
         return fail(c, BQ_ERR_WORKSPACE, "bq_head_train_steps: workspace below bq_head_train_workspace_bytes(batch)");
     DeviceGuard guard(c->device);
     hipStream_t s = (hipStream_t)stream;
-    GradArgs a{d_params, d_feats, (long long)n_feat, nullptr, nullptr, 0, 0, seed, 0u, 1.f, d_grad, nullptr, d_ws};
-    dropout_of(rate, a.thresh, a.scale);
-    for (int i = 0; i < steps; ++i) {
-        a.rows = (const long long*)d_rows + (size_t)i * batch;
-        a.labels = d_labels + (size_t)i * batch;
-        a.n = i + 1 < steps ? batch : last_n;
-        a.step = (long long)step0 + i;
-        a.loss = d_losses + i;
-        RUN(enqueue_grad(c, a, s));
-        RUN(enqueue_adam(c, d_params, d_m, d_v, d_grad, a.step, h_lr[i], b1, b2, eps, s));
+    for (int i = 0; i < steps; ++i, ++b.step) {
+        b.rows = (const long long*)d_rows + (size_t)i * batch;
+        b.labels = d_labels + (size_t)i * batch;
+        b.n = i + 1 < steps ? batch : last_n;
+        RUN(enqueue_grad(c, b, drop_of(b, seed), d_grad, d_losses + i, s));
+        RUN(enqueue_adam(c, d_params, d_m, d_v, d_grad, b.step, h_lr[i], b1, b2, eps, s));
     }
     return BQ_OK;
 }

@@ -1105,7 +1105,7 @@ class Engine:
         return res
 
     # ------------------------------------------------------------------ head training (kernels_train.hip)
-    HEAD_PARAMS, HEAD_TRAIN_MAX_ROWS = 3149826, 1024
+    HEAD_PARAMS, HEAD_TRAIN_MAX_ROWS, HEAD_VALIDATE_MAX_ROWS = 3149826, 1024, 4096          # (train.py holds copies of these three)
 
     def train_scratch(self, n):
         """A caller's own scratch for ``head_grad`` / ``head_train_steps`` with batches of up to ``n`` rows (``scratch=``): uint8
@@ -1131,6 +1131,17 @@ class Engine:
         for name, t in (('feats', feats), ('rows', rows), ('labels', labels)):
             self._on_device(name, t)
 
+    def _head_open(self, family, need, rate, first, count, scratch, refusal, ok=True):
+        """Where the preamble of the three head calls ends -> ``(rate, scratch)``: ``rate`` as a float (None: the engine's) and the
+        scratch of ``family`` with at least ``need`` bytes (``scratch``: the caller's own); ValueError(``refusal``) unless the rate
+        lies in [0, 1), the Philox passes ``first`` .. ``first + count - 1`` in 0 .. 2^32 - 1 and the call's own ``ok`` holds."""
+        rate = float(self.hp.dropout if rate is None else rate)
+        if not ok or not 0.0 <= rate < 1.0 or not 0 <= int(first) <= (1 << 32) - count:
+            raise ValueError(refusal)
+        scratch = self._scratch(family, int(need), scratch)
+        assert scratch.is_cuda and scratch.is_contiguous()        # (too small: the library refuses, BQ_ERR_WORKSPACE)
+        return rate, scratch
+
     def head_grad(self, params, feats, rows, labels, step, seed, rate=None, grad=None, scratch=None):
         """Gradient of the head's mean cross-entropy over the rows ``feats[rows]`` (``bq_head_grad``): ``params`` float32 [P] in the
         order of ``train.HEAD_TENSORS``, ``feats`` float32 [N, 2048], ``rows`` int64 [n] (also the Philox tile counters), ``labels``
@@ -1144,18 +1155,12 @@ class Engine:
         if grad is None:
             grad = torch.empty(self.HEAD_PARAMS, dtype=torch.float32, device=self.device)
         self._train_state(('grad', grad))
-        rate = float(self.hp.dropout if rate is None else rate)
-        if not 0.0 <= rate < 1.0 or not 0 <= int(step) < 1 << 32:
-            raise ValueError('head_grad: the rate lies in [0, 1) and the step in 0 .. 2^32 - 1')
-        need = int(self._lib.bq_head_train_workspace_bytes(n))
-        scratch = self._scratch('train', need, scratch)
-        assert scratch.is_cuda and scratch.is_contiguous()        # (too small: the library refuses, BQ_ERR_WORKSPACE)
+        rate, scratch = self._head_open('train', self._lib.bq_head_train_workspace_bytes(n), rate, step, 1, scratch,
+                                        'head_grad: the rate lies in [0, 1) and the step in 0 .. 2^32 - 1')
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         self._check(self._lib.bq_head_grad(self._ctx, _ptr(params), _ptr(feats), int(feats.shape[0]), _ptr(rows), _ptr(labels), n, int(step),
                                            int(seed), rate, _ptr(grad), _ptr(loss), _ptr(scratch), scratch.numel(), self._stream()))
         return grad, loss
-
-    HEAD_VALIDATE_MAX_ROWS = 4096
 
     def validate_scratch(self, n):
         """A caller's own scratch for ``head_validate`` over up to ``n`` rows (``scratch=``): uint8
@@ -1174,12 +1179,8 @@ class Engine:
             raise ValueError(f'head_validate: 1 <= n <= {self.HEAD_VALIDATE_MAX_ROWS} rows, as an int64 tensor')
         self._train_state(('params', params))
         self._train_batch(feats, rows, labels, n)
-        rate = float(rate)
-        if not 0.0 <= rate < 1.0 or not 0 <= int(pass_) < 1 << 32:
-            raise ValueError('head_validate: the rate lies in [0, 1) and the pass in 0 .. 2^32 - 1')
-        need = int(self._lib.bq_head_validate_workspace_bytes(n))
-        scratch = self._scratch('validate', need, scratch)
-        assert scratch.is_cuda and scratch.is_contiguous()        # (too small: the library refuses, BQ_ERR_WORKSPACE)
+        rate, scratch = self._head_open('validate', self._lib.bq_head_validate_workspace_bytes(n), float(rate), pass_, 1, scratch,
+                                        'head_validate: the rate lies in [0, 1) and the pass in 0 .. 2^32 - 1')
         stats = torch.empty(2, dtype=torch.float64, device=self.device)
         loss = torch.empty(n, dtype=torch.float64, device=self.device) if rowloss else None
         hits = torch.empty(n, dtype=torch.uint8, device=self.device) if hit else None
@@ -1214,12 +1215,8 @@ class Engine:
             grad = torch.empty(self.HEAD_PARAMS, dtype=torch.float32, device=self.device)
         self._train_state(('grad', grad))
         lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
-        rate = float(self.hp.dropout if rate is None else rate)
-        if len(lr) != steps or not 0.0 <= rate < 1.0 or not 0 <= int(step0) <= (1 << 32) - steps:
-            raise ValueError(f'head_train_steps: {steps} learning rates, a rate in [0, 1) and steps below 2^32')
-        need = int(self._lib.bq_head_train_workspace_bytes(batch))
-        scratch = self._scratch('train', need, scratch)
-        assert scratch.is_cuda and scratch.is_contiguous()        # (too small: the library refuses, BQ_ERR_WORKSPACE)
+        rate, scratch = self._head_open('train', self._lib.bq_head_train_workspace_bytes(batch), rate, step0, steps, scratch,
+                                        f'head_train_steps: {steps} learning rates, a rate in [0, 1) and steps below 2^32', len(lr) == steps)
         losses = torch.empty(steps, dtype=torch.float32, device=self.device)
         self._check(self._lib.bq_head_train_steps(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), _ptr(feats), int(feats.shape[0]),
                                                   _ptr(rows), _ptr(labels), steps, batch, last_n, int(step0), int(seed), rate,

@@ -40,6 +40,9 @@ from . import predictions
 HEAD_TENSORS = (('hidden_0/kernel', (2048, 1024)), ('hidden_0/bias', (1024,)), ('hidden_1/kernel', (1024, 1024)),
                 ('hidden_1/bias', (1024,)), ('logits/kernel', (1024, 2)), ('logits/bias', (2,)))
 HEAD_PARAMS = sum(int(np.prod(s)) for _, s in HEAD_TENSORS)            # 3 149 826
+# the most rows of one gradient and of one validation check: copies of Engine.HEAD_TRAIN_MAX_ROWS / HEAD_VALIDATE_MAX_ROWS, as
+# HEAD_PARAMS is of Engine.HEAD_PARAMS (engine.py loads torch and the library, so neither module imports the other at load)
+HEAD_TRAIN_MAX_ROWS, HEAD_VALIDATE_MAX_ROWS = 1024, 4096
 
 # Keras's Adam defaults and Slideflow's schedule form -- restated from memory, unpinned
 ADAM_BETA_1 = 0.9
@@ -52,7 +55,6 @@ MANIFEST_FILE = 'slides.json'
 RESULTS_FILE = 'results_log.csv'             # Slideflow's per-model log: what utils.find_cv_early_stop reads
 
 BALANCES = ('none', 'tile', 'slide', 'patient', 'category')
-HEAD_VALIDATE_MAX_ROWS = 4096                # Engine.HEAD_VALIDATE_MAX_ROWS: the rows of one check
 VAL_STREAM = 0x76616c                        # 'val': the stream of the validation rows' order
 
 
@@ -93,8 +95,8 @@ class TrainParams:
         A.parse(self.augment)
         if self.optimizer != 'Adam' or self.loss != 'sparse_categorical_crossentropy':
             raise ValueError('the head trainer implements Adam on sparse categorical cross-entropy only')
-        if not 1 <= int(self.batch_size) <= 1024 or not self.epochs or min(self.epochs) < 1:
-            raise ValueError('1 <= batch_size <= 1024 and at least one epoch')
+        if not 1 <= int(self.batch_size) <= HEAD_TRAIN_MAX_ROWS or not self.epochs or min(self.epochs) < 1:
+            raise ValueError(f'1 <= batch_size <= {HEAD_TRAIN_MAX_ROWS} and at least one epoch')
         if not 0.0 <= self.dropout < 1.0 or not self.learning_rate > 0 or self.learning_rate_decay_steps < 1:
             raise ValueError('dropout in [0, 1), a positive learning rate and decay steps >= 1')
         if self.early_stop_method not in ('accuracy', 'loss') or self.training_balance not in BALANCES:
@@ -215,6 +217,11 @@ class FeatureCache:
         return c.to(device) if device is not None else c
 
 
+def view_count(letters, views, default=1):
+    """The augmented views cached per tile: none without augmentation, else ``views``, ``default`` of them when that is None."""
+    return (default if views is None else int(views)) if letters else 0
+
+
 def cache_features(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_fit=None, batch=256, augment=None, views=None, seed=0):
     """Every tile of ``slides`` through ``evaluate()``'s input stage -- decode, stain normaliser, ``bq_backbone_u8``
     (``featuremap.walk_features``) -> ``FeatureCache`` with the features on the engine's device.  ``augment`` (letters out of
@@ -228,7 +235,7 @@ def cache_features(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_f
     eng = engine_or_pool.engines[0] if hasattr(engine_or_pool, 'engines') else engine_or_pool
     parts = []
     letters = A.parse(augment)
-    V = (1 if views is None else int(views)) if letters else 0
+    V = view_count(letters, views)
     if letters and V < 1:
         raise ValueError('views must be at least 1')
     prepare, view_parts, statuses = None, [[] for _ in range(V)], []
@@ -264,7 +271,7 @@ def cached_features(engine, slides, path, *, augment=None, views=None, seed=0, *
     other slides or was made with another augmentation, number of views or seed."""
     from . import augment as A
     letters = A.parse(augment)
-    n_views = (1 if views is None else int(views)) if letters else 0
+    n_views = view_count(letters, views)
     if not path or not os.path.exists(path):
         cache = cache_features(engine, slides, augment=letters, views=n_views or None, seed=seed, **kw)
         if path:
@@ -374,15 +381,34 @@ def balanced_rows(rows, slide_idx, labels, patients, balance, n, seed, epoch, st
 class FitResult:
     """What ``fit_head`` returns: the head tensor dict, the training losses float32 [steps], ``checks`` -- ``(step, val_loss,
     val_acc, ema)`` per validation check, ``step`` the steps done by then, ``ema`` None before it is seeded --, ``early_stop_batch``
-    (the steps done when the rule fired; None if it never did) and the steps done in all."""
+    (the steps done when the rule fired; None if it never did), the steps done in all and the epochs it was trained under
+    (``max(params.epochs)``: what ``results_log.csv`` names the model by)."""
     head: dict
     losses: np.ndarray
     checks: list
     early_stop_batch: Optional[int]
     steps: int
+    epochs: int = 1
 
 
 # ------------------------------------------------------------------------------------------------------------ training
+def _rows_and_labels(cache, rows, labels, bad_labels, bad_rows):
+    """``(rows int64 [n], labels [n])`` of a training or validation set, n >= 1; ValueError with the caller's texts otherwise."""
+    rows, labels = np.asarray(rows, np.int64).reshape(-1), np.asarray(labels).reshape(-1)
+    if len(rows) < 1 or len(labels) != len(rows) or not np.isin(labels, (0, 1)).all():
+        raise ValueError(bad_labels)
+    if rows.min() < 0 or rows.max() >= len(cache):
+        raise ValueError(bad_rows)
+    return rows, labels
+
+
+def _plan_epoch(p, cache, rows, labels, slide_idx, patients, seed, epoch, state):
+    """One epoch's batches end to end -> ``(at int64: rows of the features ``fit_head`` trains on, y uint8)``."""
+    draws = len(rows) if p.steps_per_epoch_override is None else int(p.steps_per_epoch_override) * int(p.batch_size)
+    order = balanced_rows(rows, slide_idx, labels, patients, p.training_balance, draws, seed, epoch, state)
+    return rows[order] + (epoch % (cache.n_views() or 1)) * len(cache), labels[order].astype(np.uint8)
+
+
 def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, slide_idx=None, patients=None, init='model', params=None,
              seed=None):
     """Train the head on ``cache.feats[rows]`` with ``labels`` (0/1 per row) under ``params``' schedule -> ``FitResult``.
@@ -405,12 +431,8 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
     from .engine import BiscuitHipError
     p = (params or TrainParams()).validate()
     seed = int(engine.hp.seed if seed is None else seed)
-    rows = np.asarray(rows, np.int64).reshape(-1)
-    labels = np.asarray(labels).reshape(-1)
-    if len(rows) < 1 or len(labels) != len(rows) or not np.isin(labels, (0, 1)).all():
-        raise ValueError('train_head: at least one row and a 0/1 label for each')
-    if rows.min() < 0 or rows.max() >= len(cache):
-        raise ValueError('train_head: a row outside the cache')
+    rows, labels = _rows_and_labels(cache, rows, labels, 'train_head: at least one row and a 0/1 label for each',
+                                    'train_head: a row outside the cache')
     if isinstance(init, dict):
         start = init
     elif init == 'model':
@@ -419,14 +441,11 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
         start = glorot_head(seed)
     else:
         raise ValueError("init is 'model', 'glorot' or a head tensor dict")
-    dev = engine.device
-    B = int(p.batch_size)
+    dev, B = engine.device, int(p.batch_size)
     validating = val_rows is not None and len(val_rows) > 0
     if validating:
-        val_rows = np.asarray(val_rows, np.int64).reshape(-1)
-        val_labels = np.asarray(val_labels).reshape(-1)
-        if len(val_labels) != len(val_rows) or not np.isin(val_labels, (0, 1)).all() or val_rows.min() < 0 or val_rows.max() >= len(cache):
-            raise ValueError('fit_head: a 0/1 label for each validation row, every one inside the cache')
+        refusal = 'fit_head: a 0/1 label for each validation row, every one inside the cache'
+        val_rows, val_labels = _rows_and_labels(cache, val_rows, val_labels, refusal, refusal)
         n_val = min(int(p.validation_steps) * B, len(val_rows))
         if n_val > HEAD_VALIDATE_MAX_ROWS:
             raise ValueError(f'a check scores validation_steps x batch_size rows, at most {HEAD_VALIDATE_MAX_ROWS}')
@@ -435,21 +454,16 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
         walk = np.concatenate([walk, walk[:n_val]])
         val_at, val_y = torch.from_numpy(val_rows[walk]).to(dev), torch.from_numpy(val_labels[walk].astype(np.uint8)).to(dev)
         stopper, val_rate = EarlyStop.of(p), float(p.dropout) if p.validation_dropout else 0.0
-    balanced = p.training_balance not in ('none', 'tile')
-    if balanced:
+    if p.training_balance not in ('none', 'tile'):
         slide_idx = np.asarray(cache.slide_idx[rows] if slide_idx is None else slide_idx, np.int64).reshape(-1)
     w = torch.from_numpy(flatten_head(start)).to(dev)
     m, v, g = torch.zeros_like(w), torch.zeros_like(w), torch.empty_like(w)
     losses, checks, step, stopped, state = [], [], 0, None, {}
-    V, N = (int(cache.views.shape[0]), len(cache)) if getattr(cache, 'views', None) is not None else (0, len(cache))
-    feats = cache.views.reshape(V * N, -1) if V else cache.feats
+    feats = cache.views.reshape(-1, cache.views.shape[-1]) if cache.n_views() else cache.feats
     for epoch in range(int(max(p.epochs))):
-        draws = len(rows) if p.steps_per_epoch_override is None else int(p.steps_per_epoch_override) * B
-        order = balanced_rows(rows, slide_idx, labels, patients, p.training_balance, draws, seed, epoch, state) if balanced \
-            else epoch_order(len(rows), draws, seed, epoch)
-        steps = -(-len(order) // B)
-        at = rows[order] + (epoch % V) * N if V else rows[order]
-        at, y = torch.from_numpy(at).to(dev), torch.from_numpy(labels[order].astype(np.uint8)).to(dev)
+        at, y = _plan_epoch(p, cache, rows, labels, slide_idx, patients, seed, epoch, state)
+        steps = -(-len(at) // B)
+        at, y = torch.from_numpy(at).to(dev), torch.from_numpy(y).to(dev)
         seg = int(p.validate_on_batch) if validating else steps
         for a in range(0, steps, seg):
             b = min(a + seg, steps)
@@ -477,7 +491,7 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
     if not np.isfinite(losses).all():
         raise BiscuitHipError(f'train_head: the loss of step {int(np.flatnonzero(~np.isfinite(losses))[0])} is not finite '
                               '(a feature that is not finite, or a diverged run)')
-    return FitResult(unflatten_head(w.cpu().numpy()), losses, checks, stopped, step)
+    return FitResult(unflatten_head(w.cpu().numpy()), losses, checks, stopped, step, int(max(p.epochs)))
 
 
 def train_head(engine, cache, rows, labels, *, init='model', params=None, seed=None):
@@ -644,7 +658,7 @@ def train_full(cache, slide_labels, out, label, *, stop_batch, trainer, seed=0):
     save_head(os.path.join(d, HEAD_FILE), fit.head)
     with open(os.path.join(d, MANIFEST_FILE), 'w') as f:
         json.dump({'training': train_s, 'validation': []}, f)
-    write_results_log(os.path.join(d, RESULTS_FILE), f'{label}_FULL', fit, max(params.epochs))
+    write_results_log(os.path.join(d, RESULTS_FILE), f'{label}_FULL', fit, fit.epochs)
     return d
 
 
@@ -653,7 +667,9 @@ def train_cv(cache, slide_labels, out, label, k, trainer, *, patients=None, seed
     trains on the other folds' slides and validates on its own -> ``OUT/LABEL-kfoldJ/tile_predictions_val_epoch1.csv`` with
     ``head.npz`` (when the trainer returns a head) and ``slides.json`` (the training and validation slides) beside it.
     ``trainer(train_rows, val_rows, seed)`` -> ``(tile table, head or None)`` or ``(tile table, head, FitResult)``: a
-    ``HeadTrainer``, whose third value also writes ``results_log.csv`` (``write_results_log``).  -> the fold directories."""
+    ``HeadTrainer``, whose third value also writes ``results_log.csv`` (``write_results_log``) under the model name
+    ``...-epoch{fit.epochs}``: a trainer that builds its own ``FitResult`` sets ``epochs`` there (1 if it does not; the trainer's
+    ``params`` are not looked at).  -> the fold directories."""
     patients = patients or {}
     slide_labels = {s: slide_labels[s] for s in cache.slides if s in slide_labels}
     plabel = _patient_labels(slide_labels, patients)
@@ -675,8 +691,7 @@ def train_cv(cache, slide_labels, out, label, k, trainer, *, patients=None, seed
         if head is not None:
             save_head(os.path.join(d, HEAD_FILE), head)
         if fit:
-            write_results_log(os.path.join(d, RESULTS_FILE), os.path.basename(d), fit[0],
-                              max((getattr(trainer, 'params', None) or TrainParams()).epochs))
+            write_results_log(os.path.join(d, RESULTS_FILE), os.path.basename(d), fit[0], fit[0].epochs)
         with open(os.path.join(d, MANIFEST_FILE), 'w') as f:
             json.dump({'training': train_s, 'validation': val_s}, f)
         dirs.append(d)
@@ -826,7 +841,7 @@ def main(argv=None):
         letters = A.parse(args.augment)
     except ValueError as e:
         raise SystemExit(f'--augment: {e}') from None
-    n_views = (args.epochs if args.views is None else args.views) if letters else 0
+    n_views = view_count(letters, args.views, args.epochs)
     if letters and n_views < 1:
         raise SystemExit('--views >= 1')
     if args.cache and not args.cache.endswith('.npz'):

@@ -27,21 +27,26 @@ def keep_masks(seed, rows, step, rate):
     return [philox.dropout_keep(seed, rows, int(step), layer, n_in, rate) for layer, n_in in enumerate(N_IN)]
 
 
-def loss_and_grad(feat, labels, w, keeps, rate, dtype=np.float64, want_grad=True):
-    """feat [n, 2048] (the gathered rows), labels int [n], w: the six tensors, keeps: ``keep_masks``.  -> ``(loss, {tensor: grad})``
-    in ``dtype`` arithmetic."""
-    t = tensors(w, dtype)
-    scale = dtype(philox.dropout_scale(rate))
-    zero = dtype(0)
-    labels = np.asarray(labels, np.int64)
-    n = len(labels)
-    x = np.asarray(feat, dtype)
+def forward(feat, w, keeps, rate, dtype=np.float64):
+    """The forward pass in ``dtype`` arithmetic, the one ``loss_and_grad`` and tests/_validate_ref.py share: feat [n, 2048] ->
+    ``(tensors(w, dtype), u, h, scale, zero)``, u the three layers' dropped inputs and h = [x, h0, h1, logits]."""
+    t, scale, zero = tensors(w, dtype), dtype(philox.dropout_scale(rate)), dtype(0)
+    u, h = [], [np.asarray(feat, dtype)]
     with np.errstate(invalid='ignore', over='ignore'):
-        u, h = [], [x]
         for layer, name in enumerate(HEAD):
             u.append(np.where(keeps[layer], h[-1] * scale, zero))
             z = u[-1] @ t[name + '/kernel'] + t[name + '/bias']
             h.append(np.where(z < 0, zero, z) if layer < 2 else z)
+    return t, u, h, scale, zero
+
+
+def loss_and_grad(feat, labels, w, keeps, rate, dtype=np.float64, want_grad=True):
+    """feat [n, 2048] (the gathered rows), labels int [n], w: the six tensors, keeps: ``keep_masks``.  -> ``(loss, {tensor: grad})``
+    in ``dtype`` arithmetic."""
+    t, u, h, scale, zero = forward(feat, w, keeps, rate, dtype)
+    labels = np.asarray(labels, np.int64)
+    n = len(labels)
+    with np.errstate(invalid='ignore', over='ignore'):
         z = h[-1]
         zs = z - z.max(axis=1, keepdims=True)
         lse = np.log(np.exp(zs).sum(axis=1, keepdims=True))

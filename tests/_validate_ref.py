@@ -15,7 +15,6 @@ and float32 restatements only; the GPU test asserts the floor before it uses a f
 """
 import numpy as np
 
-from oracle import philox
 from tests import _train_ref as R
 
 ROWS = 4096
@@ -27,15 +26,8 @@ ORDER_SEED = 47
 
 
 def logits(feat, w, keeps, rate, dtype=np.float64):
-    """feat [n, 2048] -> the logits [n, 2] in ``dtype`` arithmetic (``_train_ref.loss_and_grad``'s forward)."""
-    t = R.tensors(w, dtype)
-    scale, zero = dtype(philox.dropout_scale(rate)), dtype(0)
-    h = np.asarray(feat, dtype)
-    with np.errstate(invalid='ignore', over='ignore'):
-        for layer, name in enumerate(R.HEAD):
-            z = np.where(keeps[layer], h * scale, zero) @ t[name + '/kernel'] + t[name + '/bias']
-            h = np.where(z < 0, zero, z) if layer < 2 else z
-    return h
+    """feat [n, 2048] -> the logits [n, 2] in ``dtype`` arithmetic (``_train_ref.forward``)."""
+    return R.forward(feat, w, keeps, rate, dtype)[2][-1]
 
 
 def row_losses(z, labels):

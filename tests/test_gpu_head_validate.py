@@ -155,6 +155,29 @@ def test_sizes_and_refusals(eng, dev):
     torch.cuda.synchronize(eng.device)
     assert stats.tolist() == [7.0, 7.0]                                           # nothing was enqueued
     assert call(64, ws.numel()) == 0
+    al = lambda b: (b + 255) & ~255                 # include/biscuit_hip.h: h0 | h1, each [n][1024] f32 | rowloss f64 [n] | hit u8 [n]
+    for n in (1, 63, 64, 65, 1024, 1025, 4096):
+        assert lib.bq_head_validate_workspace_bytes(n) == 2 * al(n * 1024 * 4) + al(n * 8) + al(n), n
+
+    def refused(code, text, params_at=params.data_ptr(), n_feat=int(feats.shape[0]), n=64, pass_=0, rate=0.0, rowloss_at=0, nbytes=ws.numel()):
+        """One refused call, a branch of the argument check each: the code and the text of ``bq_last_error``."""
+        rc = lib.bq_head_validate(eng._ctx, C.c_void_p(params_at), ptr(feats), n_feat, ptr(rows), ptr(labels), n, pass_, 1, rate, ptr(stats),
+                                  C.c_void_p(rowloss_at), None, ptr(ws), nbytes, eng._stream())
+        assert (rc, lib.bq_last_error(eng._ctx).decode()) == (code, 'bq_head_validate: ' + text)
+
+    stats.fill_(7.0)
+    pointers = ('bad argument (null pointer, params or feats not 16-byte, rows, stats or rowloss not 8-byte or the workspace not 256-byte '
+                'aligned)')
+    refused(-1, '1 <= n <= 4096', n=0)
+    refused(-1, '1 <= n <= 4096', n=4097)
+    refused(-1, 'an empty feature cache, or a pass outside 0 .. 2^32 - 1', n_feat=0)
+    refused(-1, 'an empty feature cache, or a pass outside 0 .. 2^32 - 1', pass_=1 << 32)
+    refused(-1, 'the rate must lie in [0, 1)', rate=1.0)
+    refused(-1, pointers, params_at=params.data_ptr() + 4)
+    refused(-1, pointers, rowloss_at=stats.data_ptr() + 4)
+    refused(-4, 'workspace below bq_head_validate_workspace_bytes(n)', nbytes=need - 1)
+    torch.cuda.synchronize(eng.device)
+    assert stats.tolist() == [7.0, 7.0]                                           # nothing was enqueued
     with pytest.raises(ValueError):
         eng.head_validate(params, feats, rows[:0], labels[:0], 0, 1)
     with pytest.raises(ValueError):

@@ -2,6 +2,7 @@
 restatement of tests/_train_ref.py: a cache of 40 half-normal feature rows (one all zeros) and ``synthetic_weights(1)``'s head with
 eight dead units.  The gradient tolerance is 8 x the float32 twin's own distance from float64 for the same case (the factor covers
 a different summation order over K <= 2048).  ``-m gpu``."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -220,6 +221,67 @@ def test_poisoned_workspace_same_bits_guards_intact(eng, feats, params, seven):
     with pytest.raises(BiscuitHipError, match='workspace'):
         eng.head_train_steps(params.clone(), torch.zeros_like(params), torch.zeros_like(params), feats, up(eng, np.zeros(16, np.int64)),
                              up(eng, np.zeros(16, np.uint8)), 16, 0, 9, [1e-3], scratch=eng._bytes(need - 256))
+
+
+def test_sizes_and_refusals(eng, feats, params):
+    """The workspace's size is the layout of include/biscuit_hip.h, and every branch of the three entries' argument checks refuses
+    with its code and its text (``bq_last_error``); nothing is enqueued."""
+    lib = eng._lib
+    import inspect                                  # the constants that engine.py and train.py each hold a copy of
+    assert (eng.HEAD_PARAMS, eng.HEAD_TRAIN_MAX_ROWS, eng.HEAD_VALIDATE_MAX_ROWS) == (T.HEAD_PARAMS, T.HEAD_TRAIN_MAX_ROWS, T.HEAD_VALIDATE_MAX_ROWS)
+    for call in (eng.head_adam, eng.head_train_steps):
+        d = inspect.signature(call).parameters
+        assert (d['b1'].default, d['b2'].default, d['eps'].default) == (T.ADAM_BETA_1, T.ADAM_BETA_2, T.ADAM_EPSILON)
+    al = lambda b: (b + 255) & ~255                 # h0 | h1 | dz1 | dz0, each [n][1024] f32 | dlog [n][2] f32 | rowloss f64 [n]
+    for n in (1, 63, 64, 65, 1024):
+        assert lib.bq_head_train_workspace_bytes(n) == 4 * al(n * 1024 * 4) + al(n * 2 * 4) + al(n * 8), n
+    assert lib.bq_head_train_workspace_bytes(0) == 0 and lib.bq_head_train_workspace_bytes(1025) == 0
+    rows, labels = up(eng, np.zeros(32, np.int64)), up(eng, np.zeros(32, np.uint8))
+    w, m, v, g = params.clone(), torch.zeros_like(params), torch.zeros_like(params), torch.full_like(params, 7.0)
+    loss = torch.full((2,), 7.0, dtype=torch.float32, device=eng.device)
+    ws, need = eng.train_scratch(16), int(lib.bq_head_train_workspace_bytes(16))
+    lr = (C.c_double * 2)(1e-3, 1e-3)
+    vp = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+
+    def grad(code, text, w_off=0, n_feat=int(feats.shape[0]), n=16, step=0, rate=0.1, nbytes=need):
+        rc = lib.bq_head_grad(eng._ctx, vp(w, w_off), vp(feats), n_feat, vp(rows), vp(labels), n, step, 9, rate, vp(g), vp(loss), vp(ws), nbytes,
+                              eng._stream())
+        assert (rc, lib.bq_last_error(eng._ctx).decode()) == (code, 'bq_head_grad: ' + text)
+
+    def adam(code, text, w_off=0, step=0, b1=0.9):
+        rc = lib.bq_head_adam(eng._ctx, vp(w, w_off), vp(m), vp(v), vp(g), step, 1e-3, b1, 0.999, 1e-7, eng._stream())
+        assert (rc, lib.bq_last_error(eng._ctx).decode()) == (code, 'bq_head_adam: ' + text)
+
+    def steps(code, text, w_off=0, n_feat=int(feats.shape[0]), steps=2, batch=16, last_n=16, step0=0, rate=0.1, b1=0.9, nbytes=need):
+        rc = lib.bq_head_train_steps(eng._ctx, vp(w, w_off), vp(m), vp(v), vp(g), vp(feats), n_feat, vp(rows), vp(labels), steps, batch, last_n,
+                                     step0, 9, rate, lr, b1, 0.999, 1e-7, vp(loss), vp(ws), nbytes, eng._stream())
+        assert (rc, lib.bq_last_error(eng._ctx).decode()) == (code, 'bq_head_train_steps: ' + text)
+
+    cache_or_step = 'an empty feature cache, or a step outside 0 .. 2^32 - 1'
+    pointers = 'bad argument (null pointer, params, feats or grad not 16-byte, rows not 8-byte or the workspace not 256-byte aligned)'
+    adam_values = 'a step outside 0 .. 2^32 - 1, a learning rate that is not finite, b1 or b2 outside [0, 1), or eps <= 0'
+    grad(-1, '1 <= n <= 1024', n=0)
+    grad(-1, '1 <= n <= 1024', n=1025)
+    grad(-1, cache_or_step, n_feat=0)
+    grad(-1, cache_or_step, step=1 << 32)
+    grad(-1, 'the rate must lie in [0, 1)', rate=1.0)
+    grad(-1, pointers, w_off=4)
+    grad(-4, 'workspace below bq_head_train_workspace_bytes(n)', nbytes=need - 1)
+    adam(-1, 'bad argument (null or misaligned pointer)', w_off=2)
+    adam(-1, adam_values, step=1 << 32)
+    adam(-1, adam_values, b1=1.0)
+    steps(-1, '1 <= steps <= 2^24, 1 <= last_n <= batch and a learning rate per step', steps=0)
+    steps(-1, '1 <= steps <= 2^24, 1 <= last_n <= batch and a learning rate per step', last_n=17)
+    steps(-1, '1 <= n <= 1024', batch=1025)
+    steps(-1, cache_or_step, n_feat=0)
+    steps(-1, cache_or_step, step0=1 << 32)
+    steps(-1, 'the steps pass 2^32', step0=(1 << 32) - 1)
+    steps(-1, 'the rate must lie in [0, 1)', rate=1.0)
+    steps(-1, pointers, w_off=4)
+    steps(-1, adam_values, b1=1.0)
+    steps(-4, 'workspace below bq_head_train_workspace_bytes(batch)', nbytes=need - 1)
+    torch.cuda.synchronize(eng.device)
+    assert torch.equal(w, params) and not m.any() and not v.any() and bool((g == 7.0).all()) and loss.tolist() == [7.0, 7.0]
 
 
 # ------------------------------------------------------------------------------------------------ 8. end to end at toy size

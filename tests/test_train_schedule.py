@@ -175,6 +175,20 @@ def test_find_cv_early_stop_over_written_folds(tmp_path):
     assert df['val_loss'].isna().all()
 
 
+def test_results_log_bytes(tmp_path):
+    """The file's bytes, with and without checks and with and without a stop batch."""
+    path = str(tmp_path / 'r.csv')
+    want = {(True, 40): b'model_name,steps,val_loss,val_acc,early_stop_batch\nEXP-kfold2-epoch3,40,0.65,0.625,40\n',
+            (True, None): b'model_name,steps,val_loss,val_acc\nEXP-kfold2-epoch3,40,0.65,0.625\n',
+            (False, 40): b'model_name,steps,val_loss,val_acc,early_stop_batch\nEXP-kfold2-epoch3,40,,,40\n',
+            (False, None): b'model_name,steps,val_loss,val_acc\nEXP-kfold2-epoch3,40,,\n'}
+    for (checked, stop), text in want.items():
+        checks = [(38, 0.7, 0.5, None), (40, 0.65, 0.625, 0.6)] if checked else []
+        T.write_results_log(path, 'EXP-kfold2', T.FitResult({}, np.zeros(40, np.float32), checks, stop, 40), 3)
+        with open(path, 'rb') as f:
+            assert f.read() == text, (checked, stop)
+
+
 # ------------------------------------------------------------------------------------------------ 5. fit_head's row arithmetic
 class _Stub:
     """In the engine's place: records what ``fit_head`` asks for; the validation accuracy of check c is ``accs[c]``."""
