@@ -68,6 +68,36 @@ inline float sqdist_host(const float* x, const float* y, int D) {
     return g[0];
 }
 
+// ---- the GEMM form's error (DESIGN.md "Neighbours": the derivation) -------------------------------------------------------
+// nq, nc: the fp32 sums of squares of two rows of D columns, v = fl(fl(nq + nc) - 2 fl(q.c)), every sum in ANY order, fused or
+// not.  With u = 2^-24, gamma_m = m u / (1 - m u) and S = |q|^2 + |c|^2 exactly: |nq + nc - S| <= gamma_D S, the dot product is
+// off by gamma_D sum |q_i c_i| <= gamma_D S / 2 (doubled: gamma_D S), the two outer roundings add u S (1 + gamma_D) and
+// u |v| <= 2 u S (1 + ...), so |v - d^2| <= gamma_(2D + 4) S; 4 u S more pay for rounding v - E itself.  S is not known, only
+// nq + nc >= S (1 - gamma_D): with g = (2 D + 8) u the coefficient g / (1 - g)^2 >= gamma_(2D + 8) / (1 - gamma_D), times
+// 1 + 2^-18 for the three roundings of E's own arithmetic; 1e-30 covers products that underflow (2 D 2^-126 at most).
+// Valid while nothing overflows: a value that is not finite certifies nothing (kernels_knn.hip).
+BQU_HD float gemm_err_coeff(int D) {
+    const double g = (2.0 * (double)D + 8.0) * 5.9604644775390625e-08;      // (D <= 2^20: g <= 0.126)
+    return (float)(g / ((1.0 - g) * (1.0 - g)) * (1.0 + 3.814697265625e-06) * (1.0 + 1.1920928955078125e-07));      // (and the cast's own rounding)
+}
+
+BQU_HD float gemm_err_with(float nq, float nc, float coeff) {
+    BQU_NO_FMA
+    return (nq + nc) * coeff + 1e-30f;
+}
+
+// E(nq, nc, D) >= |GEMM-form value - exact d^2|
+BQU_HD float gemm_form_err(float nq, float nc, int D) { return gemm_err_with(nq, nc, gemm_err_coeff(D)); }
+
+// The k-th direct-form d2 of a row against the smallest lower bound `floor_` = min (v - E) of the rows that were NOT looked at
+// again: true only where every such row's rounded distance lies STRICTLY above the k-th's, so the (distance, index) order cannot
+// put it into the table.  The direct form is off by relative gamma_(D + 2) <= eps_for(D) / 2 (plus D 2^-149 where squares
+// underflow), and two fp32 roots differ as soon as their squares differ by a factor 1 + 8 u: (2 D + 12) u covers both, in double.
+BQU_HD bool knn_certified(float d2_kth, float floor_, int D) {
+    const double thr = (double)d2_kth * (1.0 + (2.0 * (double)D + 12.0) * 5.9604644775390625e-08) + 1e-30;
+    return thr < (double)floor_;      // (a NaN on either side: not certified)
+}
+
 // ---- Philox4x32-10 (oracle/philox.py), for both sides ---------------------------------------------------------------------
 BQU_HD uint32_t philox_word0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
     for (int i = 0; i < 10; ++i) {

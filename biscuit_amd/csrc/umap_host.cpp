@@ -1,7 +1,8 @@
 // Host side of the feature map (include/biscuit_io.h: bqio_knn, bqio_umap_smooth, bqio_umap_epoch): the CPU builds of bq_knn,
 // bq_umap_smooth and bq_umap_epoch over the per-row arithmetic of umap_device.h -- the one the GPU kernels are compiled from.
-// bqio_knn ranks ALL n rows by the direct form (no pruning pass), so it is what the device returns wherever its GEMM-form
-// pruning loses no neighbour.  Row by row, pair by pair: for tests.
+// bqio_knn ranks ALL n rows by the direct form (no pruning pass): what the device returns on every row, because bq_knn keeps a
+// pruned row only where it proves that no neighbour was lost and ranks all n rows itself elsewhere.  Row by row, pair by pair:
+// for tests.
 #include "../../include/biscuit_io.h"
 #include "umap_device.h"
 
@@ -9,14 +10,23 @@
 
 extern "C" {
 
+int bqio_knn_gemm_bound(const float* nq, const float* nc, int64_t count, int D, float* out) {
+    if (!nq || !nc || !out || count < 0 || D < 1) return BQIO_ERR_ARG;
+    for (int64_t e = 0; e < count; ++e) out[e] = bqumap::gemm_form_err(nq[e], nc[e], D);
+    return BQIO_OK;
+}
+
 int bqio_knn(const float* X, int n, int D, int k, int32_t* idx, float* dist) {
     if (!X || !idx || !dist || bqumap::check_knn(n, D, k)) return BQIO_ERR_ARG;
+    for (size_t e = 0; e < (size_t)n * D; ++e)
+        if (!(fabsf(X[e]) < INFINITY)) return BQIO_ERR_ARG;
     std::vector<float> bd((size_t)k);
     std::vector<int> bi((size_t)k);
     for (int i = 0; i < n; ++i) {
         int have = 0;
         for (int j = 0; j < n; ++j) {
             const float d = sqrtf(bqumap::sqdist_host(X + (size_t)i * D, X + (size_t)j * D, D));      // (the order is the DISTANCE's: two sums may share a root)
+            if (!(d < INFINITY)) continue;      // (a sum that overflowed: no candidate, on the device neither)
             if (have == k && !bqumap::before(d, j, bd[k - 1], bi[k - 1])) continue;
             int at = have < k ? have++ : k - 1;
             while (at > 0 && bqumap::before(d, j, bd[at - 1], bi[at - 1])) {
@@ -28,8 +38,8 @@ int bqio_knn(const float* X, int n, int D, int k, int32_t* idx, float* dist) {
             bi[at] = j;
         }
         for (int j = 0; j < k; ++j) {
-            idx[(size_t)i * k + j] = bi[j];
-            dist[(size_t)i * k + j] = bd[j];
+            idx[(size_t)i * k + j] = j < have ? bi[j] : -1;
+            dist[(size_t)i * k + j] = j < have ? bd[j] : NAN;
         }
     }
     return BQIO_OK;

@@ -691,8 +691,10 @@ class Engine:
     def knn(self, x, k, scratch=None):
         """Exact ``k`` nearest neighbours of the rows of ``x`` fp32 [n, D] on this device (``bq_knn``, kernels_knn.hip; D a multiple
         of 16, 1 <= k <= 64, k <= n) -> ``(idx int32 [n, k], dist fp32 [n, k])``: Euclidean distances, every row sorted by
-        (distance, index) ascending, the row itself a candidate like any other.  ``scratch``: ``knn_scratch(n, D, k)`` or larger.
-        ValueError for a shape or a ``k`` the entry refuses."""
+        (distance, index) ascending, the row itself a candidate like any other: ``umap.knn_host``'s table bit for bit, on every row.
+        ``scratch``: ``knn_scratch(n, D, k)`` or larger; ``knn_exhaustive_rows`` reads from it which rows the pruning pass could
+        not prove.  ValueError for a shape or a ``k`` the entry refuses, and for an ``x`` that is not finite (one host
+        synchronisation to learn it)."""
         if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 2):
             raise ValueError('x must be fp32 [n, D]')
         self._on_device('x', x)
@@ -701,6 +703,8 @@ class Engine:
         need = int(self._lib.bq_knn_workspace_bytes(n, d, k))
         if need == 0:
             raise ValueError(f'knn takes 1 <= k <= 64, k <= n and D a multiple of 16, not n = {n}, D = {d}, k = {k}')
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError('knn takes finite values only: x holds a NaN or an infinity')
         scratch = self._scratch('knn', need, scratch)
         assert scratch.numel() >= need
         idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
@@ -711,6 +715,15 @@ class Engine:
     def knn_scratch(self, n, d, k):
         """Candidate lists for ``knn`` over ``n`` rows (one buffer per launch that may be in flight)."""
         return self._bytes(self._lib.bq_knn_workspace_bytes(int(n), int(d), int(k)))
+
+    def knn_exhaustive_rows(self, n, scratch=None):
+        """Which of the ``n`` rows of the last ``knn`` on ``scratch`` (None: the engine's own) were ranked again over all rows,
+        because the pruning pass's certificate did not cover them: bool [n] on the device, a copy of the flags ``bq_knn`` leaves
+        in the first 4 n bytes of its workspace."""
+        scratch = self._tool_ws.get('knn') if scratch is None else scratch
+        if scratch is None or scratch.numel() < 4 * int(n):
+            raise ValueError('no knn of that many rows has run on this scratch')
+        return scratch[:4 * int(n)].view(torch.int32) != 0
 
     def umap_smooth(self, idx, dist, scratch=None):
         """The fuzzy graph's rows from ``knn``'s table (``bq_umap_smooth``, kernels_umap.hip) -> ``(rho [n], sigma [n], w [n, k])``

@@ -78,6 +78,7 @@ ABI = {
     'bqio_format_f64': (_i, [C.c_double, C.c_char_p, _i]),
     # the CPU builds of the feature map's entries (biscuit_amd/umap.py)
     'bqio_knn': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'bqio_knn_gemm_bound': (_i, [_vp, _vp, _i64, _i, _vp]),
     'bqio_umap_smooth': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'bqio_umap_epoch': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_float, C.c_float, C.c_float, C.c_uint64]),
 }

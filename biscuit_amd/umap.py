@@ -145,14 +145,31 @@ def embed(engine, features, n_neighbors=50, min_dist=0.1, seed=0, n_epochs=None)
 
 # ---- the CPU builds (libbiscuit_io: csrc/umap_host.cpp over csrc/umap_device.h), for tests -------------------------------------------
 def knn_host(x, k):
+    """``Engine.knn``'s table on the host (bqio_knn: all n rows by the direct form).  ValueError for what the device refuses, an
+    ``x`` that is not finite included."""
     from . import tfrecord_native
     x = np.ascontiguousarray(x, np.float32)
     n, d = x.shape
+    if not np.isfinite(x).all():
+        raise ValueError('knn_host takes finite values only: x holds a NaN or an infinity')
     idx, dist = np.empty((n, max(int(k), 0)), np.int32), np.empty((n, max(int(k), 0)), np.float32)
     e = tfrecord_native.lib().bqio_knn(x.ctypes.data, n, d, int(k), idx.ctypes.data, dist.ctypes.data)
     if e != 0:
         raise ValueError(f'bqio_knn(n = {n}, D = {d}, k = {k}): error {e}')
     return idx, dist
+
+
+def gemm_bound(nq, nc, d):
+    """E(nq, nc, D) of csrc/umap_device.h, elementwise over fp32 arrays that broadcast: the worst-case error of the pruning
+    pass's GEMM form (bqio_knn_gemm_bound)."""
+    from . import tfrecord_native
+    nq, nc = np.broadcast_arrays(np.asarray(nq, np.float32), np.asarray(nc, np.float32))
+    nq, nc = np.ascontiguousarray(nq), np.ascontiguousarray(nc)
+    out = np.empty(nq.shape, np.float32)
+    e = tfrecord_native.lib().bqio_knn_gemm_bound(nq.ctypes.data, nc.ctypes.data, nq.size, int(d), out.ctypes.data)
+    if e != 0:
+        raise ValueError(f'bqio_knn_gemm_bound(D = {d}): error {e}')
+    return out
 
 
 def smooth_host(idx, dist):

@@ -573,11 +573,18 @@ int bq_describe_schedule(bq_ctx* ctx, int n, int from_u8, const char* name, char
  *
  * bq_knn: d_x fp32 [n][D] (16-byte aligned, D a multiple of 16, 16 .. 2^20) -> d_idx int32 [n][k] and d_dist fp32 [n][k], the k
  * nearest rows of every row by Euclidean distance, each row sorted by (distance, index) ascending; the row itself is a candidate
- * like any other, so it is normally rank 0.  1 <= k <= 64, k <= n, n <= 2^31 / 160: anything else is BQ_ERR_ARG.  A pruning pass
- * in the GEMM form on the fp32 matrix instruction keeps 2 (k + 16) candidates per row; they are ranked again by the direct form
- * sum (x - y)^2 in fp32, and that is the distance returned (its square root, correctly rounded).  The n x n matrix is never
- * stored.  d_ws: bq_knn_workspace_bytes(n, D, k) bytes (0 for arguments the call refuses), 16-byte aligned, caller-owned,
- * contents unspecified on entry; BQ_ERR_WORKSPACE below that.  No atomics: the same bits every run.
+ * like any other, so it is normally rank 0.  1 <= k <= 64, k <= n, n <= 2^31 / 160: anything else is BQ_ERR_ARG.  The distance
+ * is the direct form sum (x - y)^2 in fp32 in one fixed order, its square root correctly rounded, and the table is the one over
+ * ALL n rows in that arithmetic (bqio_knn's, bit for bit) on every row: a pruning pass in the GEMM form on the fp32 matrix
+ * instruction keeps 2 (k + 16) candidates per row and, with a worst-case bound on its own error, a lower bound on the distance
+ * of everything it dropped; a row whose k-th candidate does not lie strictly below that bound is ranked again over all n rows.
+ * The n x n matrix is never stored.  Precondition: every value of d_x is finite (not checked here: no host synchronisation;
+ * Engine.knn checks).  Where it is broken, a pair whose distance is not finite is no candidate, and a row with fewer than k
+ * candidates ends in d_idx = -1, d_dist = NaN; every element of d_idx and d_dist is written in any case.  d_ws:
+ * bq_knn_workspace_bytes(n, D, k) = 2 pad256(4 n) + 8 n (k + 16) + 8 n bytes, pad256 rounding up to a multiple of 256 (0 for
+ * arguments the call refuses), 16-byte aligned, caller-owned, contents unspecified on entry; BQ_ERR_WORKSPACE below that.  On
+ * return (in stream order) its first n int32 hold 1 for the rows that were ranked again over all rows, 0 for the others.  No
+ * atomics: the same bits every run.
  *
  * bq_umap_smooth: the table of bq_knn -> d_rho [n], d_sigma [n] and the membership weights d_w [n][k] (local connectivity 1,
  * bandwidth 1): rho the smallest non-zero distance of the row, sigma by 64 bisection steps for sum_{j >= 1} exp(-max(0, d_j -

@@ -317,9 +317,13 @@ int bqio_format_f64(double v, char* out, int cap);
 
 /* The CPU builds of the feature map's three entries (include/biscuit_hip.h: bq_knn, bq_umap_smooth, bq_umap_epoch;
  * csrc/umap_host.cpp over csrc/umap_device.h, the per-row arithmetic the GPU kernels are compiled from), on host memory with the
- * same shapes and types.  bqio_knn ranks all n rows by the direct form sum (x - y)^2 -- no pruning pass --, so it is what the
- * device returns wherever its pruning loses no neighbour.  bqio_umap_epoch checks the CSR (indptr from 0 and non-decreasing,
- * neighbours in 0 .. n - 1).  BQIO_ERR_ARG for what the GPU entries refuse.  For tests. */
+ * same shapes and types.  bqio_knn ranks all n rows by the direct form sum (x - y)^2 -- no pruning pass --, and is what the
+ * device returns on every row, bit for bit.  X must be finite: BQIO_ERR_ARG otherwise.  A pair whose fp32 sum overflows is no
+ * candidate; a row with fewer than k candidates ends in idx -1, dist NaN.  bqio_knn_gemm_bound: out[e] = the worst-case bound
+ * E(nq[e], nc[e], D) on |GEMM-form value - exact squared distance| that bq_knn's certificate uses (csrc/umap_device.h:
+ * gemm_form_err), nq and nc the two rows' fp32 sums of squares, `count` pairs.  bqio_umap_epoch checks the CSR (indptr from 0 and non-decreasing, neighbours in
+ * 0 .. n - 1).  BQIO_ERR_ARG for what the GPU entries refuse.  For tests. */
+int bqio_knn_gemm_bound(const float* nq, const float* nc, int64_t count, int D, float* out);
 int bqio_knn(const float* X, int n, int D, int k, int32_t* idx, float* dist);
 int bqio_umap_smooth(const int32_t* idx, const float* dist, int n, int k, float* rho, float* sigma, float* w);
 int bqio_umap_epoch(const float* prev, float* out, int n, const int64_t* indptr, const int32_t* nbr, const float* eps, float* next,

@@ -6,7 +6,8 @@ import numpy as np
 D = 2048
 N_CLUSTER, N_LABELS = 600, 12
 CLUSTER_SEEDS = (0, 1, 2, 3)
-SMALL = ((1, 48, 1), (63, 48, 1), (63, 48, 15), (63, 48, 50), (257, 48, 15), (257, 48, 64), (64, 16, 64))      # (n, D, k)
+# (n, D, k); D = 80 is the smallest D at which the direct form's 64-element step is taken a second time, and cut
+SMALL = ((1, 48, 1), (63, 48, 1), (63, 48, 15), (63, 48, 50), (257, 48, 15), (257, 48, 64), (64, 16, 64), (33, 80, 5))
 
 
 def labels():
@@ -57,8 +58,61 @@ def small(n, d, seed=0):
     return x
 
 
+# ---- tight groups: more rows than a query's candidate lists hold, closer together than the GEMM form's rounding error -------
+# name -> (k's the case is used at, D, the group's rows); the group is where the pruning pass's order is rounding noise
+TIGHT_SCALE = {'tight_lowrank': 1e-3, 'tight_fullrank': 1e-3, 'tight_small': 1e-4}
+TIGHT = {'tight_lowrank': ((15, 50), D, slice(100, 300)), 'tight_fullrank': ((15,), D, slice(100, 196)),
+         'tight_small': ((15,), 48, slice(57, 257))}
+CONTROL = {'wide_control': ((15,), D, slice(100, 300))}
+
+
+def _low_rank_group(rank, scale):
+    """The cluster case with rows 100 .. 299 replaced by ReLU(row 17 + scale N(0, 1)[200, rank] @ M), M standard normal."""
+    x = cluster(0).copy()
+    rng = np.random.default_rng(5)
+    m = rng.normal(0.0, 1.0, (rank, D))
+    x[100:300] = np.maximum(x[17] + scale * rng.normal(0.0, 1.0, (200, rank)) @ m, 0.0).astype(np.float32)
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def tight_lowrank():
+    """200 rows on a 2-dimensional patch around row 17, squared distances of 10^-2 against squared norms of 1.8 10^4: the
+    neighbours inside the patch are well separated (few directions), and the GEMM form cannot tell them apart."""
+    return _low_rank_group(2, TIGHT_SCALE['tight_lowrank'])
+
+
+@functools.lru_cache(maxsize=None)
+def wide_control():
+    """The same on 3 dimensions with three times the spread: wide enough for the GEMM form to keep every true neighbour."""
+    return _low_rank_group(3, 3e-3)
+
+
+@functools.lru_cache(maxsize=None)
+def tight_fullrank():
+    """The cluster case with rows 100 .. 195 replaced by row 17 + 1e-3 N(0, 1) in all 2048 columns: the distances concentrate, so
+    a lost neighbour is only a little further than the k-th."""
+    x = cluster(0).copy()
+    rng = np.random.default_rng(6)
+    x[100:196] = x[17] + (TIGHT_SCALE['tight_fullrank'] * rng.normal(0.0, 1.0, (96, D))).astype(np.float32)
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def tight_small():
+    """257 x 48 (nine query tiles, the last one cut), rows N(0, 1) + 20, the last 200 of them row 3 + 1e-4 N(0, 1)."""
+    rng = np.random.default_rng(8)
+    x = (rng.normal(0.0, 1.0, (257, 48)) + 20.0).astype(np.float32)
+    x[57:] = x[3] + (TIGHT_SCALE['tight_small'] * rng.normal(0.0, 1.0, (200, 48))).astype(np.float32)
+    x.setflags(write=False)
+    return x
+
+
 def get(name, seed=0):
-    return {'cluster': lambda: cluster(seed), 'integer': integer, 'near_duplicate': near_duplicate}[name]()
+    return {'cluster': lambda: cluster(seed), 'integer': integer, 'near_duplicate': near_duplicate, 'tight_lowrank': tight_lowrank,
+            'tight_fullrank': tight_fullrank, 'tight_small': tight_small, 'wide_control': wide_control}[name]()
 
 
 def smoothing_table(k=15):

@@ -156,6 +156,44 @@ def check_table(d2, idx, dist, d):
     return rel
 
 
+K_SLACK = 16
+
+
+def gemm_form(x, chunk=64):
+    """|q|^2 + |c|^2 - 2 q.c of every pair in fp32 throughout, the products accumulated over the columns in chunks of ``chunk``:
+    the pruning pass's form, in numpy's summation order rather than the kernel's.  -> fp32 [n, n]."""
+    x = np.asarray(x, np.float32)
+    sq = (x * x).sum(1, dtype=np.float32)
+    dot = np.zeros((len(x), len(x)), np.float32)
+    for e in range(0, x.shape[1], chunk):
+        dot += x[:, e:e + chunk] @ x[:, e:e + chunk].T
+    return (sq[:, None] + sq[None, :]) - np.float32(2) * dot
+
+
+def pruned_candidates(x, k, chunk=64):
+    """An emulation of the pruning pass as the Neighbours paragraph describes it: candidate c belongs to half (c // 4) % 2; of
+    each half a query keeps the k + K_SLACK smallest by (GEMM-form value, index).  -> bool [n, n], True where the row is looked
+    at again.  It is not the kernel: the matrix instruction sums in another order."""
+    g = gemm_form(x, chunk)
+    n = len(g)
+    keep = np.zeros((n, n), bool)
+    for h in (0, 1):
+        cols = np.nonzero((np.arange(n) // 4) % 2 == h)[0]
+        for q in range(n):
+            keep[q, cols[np.lexsort((cols, g[q, cols]))[:k + K_SLACK]]] = True
+    return keep
+
+
+def lost_rows(d2, keep, k, d):
+    """Rows of which a true neighbour is not kept, and what the best table over the kept rows then holds lies beyond
+    (1 + eps_for(d)) x the k-th float64 squared distance.  -> (bool [n], the worst ratio to the k-th)."""
+    kth = np.sort(d2, axis=1)[:, k - 1]
+    got = np.sort(np.where(keep, d2, np.inf), axis=1)[:, k - 1]
+    lost = got > (1.0 + eps_for(d)) * kth
+    ratio = got / np.maximum(kth, 1e-300)
+    return lost, float(ratio[lost].max()) if lost.any() else 1.0
+
+
 def decided(d2, k, d):
     """Rows whose k-th and (k + 1)-th float64 squared distances lie further apart than eps x the distance: there the neighbour SET
     is the same for every correct fp32 table (all rows when k = n)."""

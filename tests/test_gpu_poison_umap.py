@@ -58,6 +58,34 @@ def test_results_do_not_depend_on_stale_bytes(eng, own_scratch):
             assert a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32)), f'result {k} under 0x{fill:02X} differs from a clean run'
 
 
+@pytest.mark.parametrize('own_scratch', [False, True])
+def test_rows_ranked_again_do_not_depend_on_stale_bytes(eng, own_scratch):
+    """``knn`` alone on the small tight group (257 x 48, k = 15), where most rows are ranked again over all rows: the flags, the
+    halves' floors and the second pass's output under poison."""
+    import biscuit_amd.engine as engine_mod
+    x = up(eng, cases.tight_small())
+
+    def knn(mod):
+        scratch = eng.knn_scratch(257, 48, 15) if own_scratch else None
+        idx, dist = eng.knn(x, 15, scratch=scratch)
+        redone = eng.knn_exhaustive_rows(257, scratch)
+        return [t.cpu().numpy() for t in (idx, dist, redone)]
+    clean = knn(torch)
+    assert clean[2].sum() >= 100 and (clean[0] >= 0).all()
+    for fill in P.BYTE_FILLS:
+        torch.cuda.synchronize(eng.device)
+        eng.drop_scratch()
+        proxy = P.poisoned_torch(fill)
+        with pytest.MonkeyPatch.context() as mp:
+            mp.setattr(engine_mod, 'torch', proxy)
+            out = knn(proxy)
+        torch.cuda.synchronize(eng.device)
+        assert proxy.served >= 3                                    # idx, dist, the scratch
+        proxy.check()
+        for k, (a, b) in enumerate(zip(clean, out)):
+            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8)), f'result {k} under 0x{fill:02X} differs from a clean run'
+
+
 def test_exactly_the_three_new_classes():
     eng = _engine()
     try:

@@ -1,6 +1,7 @@
 """Cost of the feature map's stages (DESIGN.md "Feature map (Figure 6)").  python tools/bench_umap.py [--n 10000 --d 2048 --k 50 --epochs 20]
 
-On ``n`` synthetic cluster points of ``d`` columns: the neighbour search (bq_knn), the membership weights (bq_umap_smooth), the
+On ``n`` synthetic cluster points of ``d`` columns: the neighbour search (bq_knn, and how many rows it ranked again over all
+rows), the membership weights (bq_umap_smooth), the
 host's graph assembly, the host's PCA start, ``--epochs`` epochs of the layout (bq_umap_epoch) and the projected end-to-end time
 at the map's own number of epochs.  Device stages by HIP events after one warm-up call, host stages by the host clock.  One JSON
 line; profiles/umap.txt holds what was measured."""
@@ -45,6 +46,7 @@ def device_ms(fn, reps=1):
 
 res = {'n': args.n, 'd': args.d, 'k': args.k}
 res['knn_ms'], (idx, dist) = device_ms(lambda: eng.knn(x, args.k))
+res['knn_rows_ranked_again'] = int(eng.knn_exhaustive_rows(args.n).sum())      # (the rows the pruning pass could not prove)
 res['smooth_ms'], (_, _, w) = device_ms(lambda: eng.umap_smooth(idx, dist), 5)
 n_epochs = umap.n_epochs_for(args.n)
 t0 = time.perf_counter()
