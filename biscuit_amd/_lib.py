@@ -111,6 +111,14 @@ ABI = {
     'bq_head_adam': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     'bq_head_train_steps': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i64, _u64, C.c_double,
                                  C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    'bq_trunk_u8': (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    'bq_exit_features_workspace_bytes': (_sz, [_i]),
+    'bq_exit_train_workspace_bytes': (_sz, [_i]),
+    'bq_exit_features': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
+    'bq_exit_grad': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i64, _u64, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    'bq_adam_n': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
+    'bq_exit_train_steps': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i64, _u64, C.c_double,
+                                 C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -762,6 +762,15 @@ int bq_load_weights(bq_ctx* c, const void* host_blob, size_t nbytes) {
             if (!(c->feat_mul > 0.f) || !std::isfinite(c->feat_mul)) return fail(c, BQ_ERR_WEIGHTS, "act/feat_mul must be a positive finite number");
         }
     }
+    c->trunk_mul = 1.f;
+    {
+        auto tm = c->entries.find("act/trunk_mul");
+        if (tm != c->entries.end()) {
+            if (tm->second.n < 4) return fail(c, BQ_ERR_WEIGHTS, "bad size for act/trunk_mul");
+            memcpy(&c->trunk_mul, hb + (tm->second.p - c->d_blob), 4);
+            if (!(c->trunk_mul > 0.f) || !std::isfinite(c->trunk_mul)) return fail(c, BQ_ERR_WEIGHTS, "act/trunk_mul must be a positive finite number");
+        }
+    }
     c->front_ws16 = c->front_wc16 = nullptr;
     {
         auto a = c->entries.find("block1_conv1/w16"), b = c->entries.find("block1_conv2/wp16");
@@ -900,6 +909,28 @@ int bq_backbone_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_feat, void
     WsLayout L;
     RUN(ready(c, n, 1, ws_bytes, &L));
     return features_from_u8(c, d_tiles, n, d_feat, (unsigned char*)d_ws, L, stream);
+}
+
+// bq_backbone_u8's walk up to block13_out -- the same launches by the same routes: the tap's name is no layer's, so it moves no
+// route -- written as fp32 NHWC at true scale (the blob's activation exponent of the tensor removed, a power of two).
+int bq_trunk_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_out, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    if (!c || !d_tiles || !d_out || !d_ws || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_trunk_u8: bad argument");
+    WsLayout L;
+    RUN(ready(c, n, 1, ws_bytes, &L));
+    unsigned char* ws = (unsigned char*)d_ws;
+    const long long count = (long long)n * 100 * 1024;
+    Tap t; t.want = "block13_out"; t.out = d_out; t.out_elems = (size_t)count;
+    const Walk w{c, n, (hipStream_t)stream, &t, nullptr};
+    if (has_front(c)) {
+        RUN(backbone_impl(w, nullptr, (float*)(ws + L.feat), ws, d_tiles));
+    } else {
+        void* staged = ws + L.staged;
+        RUN(bq_stage(c, d_tiles, n, staged, stream));
+        RUN(backbone_impl(w, staged, (float*)(ws + L.feat), ws));
+    }
+    if (t.written != count) return fail(c, BQ_ERR_HIP, "bq_trunk_u8: block13_out was not written");
+    if (c->trunk_mul != 1.f && launch_scale_f32(d_out, count, c->trunk_mul, (hipStream_t)stream)) return fail(c, BQ_ERR_HIP, "bq_trunk_u8: scale launch failed");
+    return BQ_OK;
 }
 
 int bq_profile_enable(bq_ctx* c, int on) {

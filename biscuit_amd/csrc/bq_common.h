@@ -123,6 +123,7 @@ int launch_to_f32_nhwc(const void* x, long long rows, int C, int ld, float* out,
                        hipStream_t s);
 int launch_nchw_to_f32_nhwc(const void* x, int n, int C, int HW, float* out, int dtype,
                             hipStream_t s);
+int launch_scale_f32(float* x, long long count, float mul, hipStream_t s);
 
 // ---- device helpers ----------------------------------------------------------------
 #define BQ_FIXED_SHIFT 40

@@ -53,6 +53,7 @@ struct bq_ctx {
     const long long* d_tile_idx = nullptr;   // bq_set_tile_index_array
     int inflate_variant = 5;       // bq_set_option("inflate_variant"): 5 = rounds of a literal-only fast phase + a general phase (LDS), 0 = the
                                    // kernel without LDS, tables in global memory (kernels_inflate.hip; profiles/r05_inflate.txt)
+    float trunk_mul = 1.f;         // "act/trunk_mul" of the blob: 2^k of block13_out's activation exponent (bq_trunk_u8)
     float feat_mul = 1.f;          // "act/feat_mul" of the blob: 2^k of the pooled tensor's activation exponent (weights.py: pack_blob)
     double* d_stage_stats = nullptr;   // 2 x 64-bit integer sums per tile for the staging kernel pair
     // profiling

@@ -515,6 +515,16 @@ int launch_to_f32_nhwc(const void* x, long long rows, int C, int ld, float* out,
     return (int)hipGetLastError();
 }
 
+// x *= mul in place (mul a power of two: exact), grid-stride
+__global__ void scale_f32_kernel(float* __restrict__ x, long long count, float mul) {
+    for (long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x; gid < count; gid += (long long)gridDim.x * blockDim.x) x[gid] *= mul;
+}
+
+int launch_scale_f32(float* x, long long count, float mul, hipStream_t s) {
+    hipLaunchKernelGGL(scale_f32_kernel, dim3(grid_stride_for(count, 256)), dim3(256), 0, s, x, count, mul);
+    return (int)hipGetLastError();
+}
+
 int launch_nchw_to_f32_nhwc(const void* x, int n, int C, int HW, float* out, int dtype, hipStream_t s) {
     const long long total = (long long)n * C * HW;
     BQ_DISPATCH_T(dtype,

@@ -26,6 +26,9 @@
 // bq_head_validate (DESIGN.md section 7 "Training schedule") is the forward half alone over n <= 4096 rows, for the validation checks in
 // the middle of a training: the same two GEMMs (at rate 0 in the A mode that draws nothing), the same logits and float64 row loss, a hit
 // per row, and the two sums in a fixed order.  A row's loss and hit depend on the row only, not on n or on its place in the batch.
+//
+// Exit-flow fine-tuning (bq_exit_*, bq_adam_n; the section at the end of the file) trains Xception's block 14 in front of this head on
+// cached block13_out: its pointwise products are further instantiations of train_gemm_kernel, which is why it lives here.
 #include <cmath>
 #include <hip/hip_runtime.h>
 
@@ -75,6 +78,14 @@ __device__ __forceinline__ float4 drop_relu_grad4(float4 h, float4 v, unsigned g
     return o;
 }
 
+// The derivative v of drop4's four units through their dropout alone: scale v where the unit was kept, else 0.
+__device__ __forceinline__ float4 drop_grad4(float4 v, unsigned g, unsigned ctr, const Drop& d) {
+    unsigned r[4];
+    philox4x32_10(g, d.layer, d.step, ctr, d.seed_lo, d.seed_hi, r);
+    return make_float4(r[0] >= d.thresh ? v.x * d.scale : 0.f, r[1] >= d.thresh ? v.y * d.scale : 0.f,
+                       r[2] >= d.thresh ? v.z * d.scale : 0.f, r[3] >= d.thresh ? v.w * d.scale : 0.f);
+}
+
 // what drop4 gives at rate 0 (every unit kept, scale 1), without the draw
 __device__ __forceinline__ float4 finite4(float4 v) {
     const float nan = __builtin_nanf("");
@@ -86,9 +97,11 @@ __device__ __forceinline__ float4 finite4(float4 v) {
 __device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
 
 // drop(src)[m][k]; src[m][k]; drop(src)[k = batch row][m = unit]; A_DROP_K at rate 0 without its draws (bq_head_validate): src[m][k], NaN for not finite
-enum AMode : int { A_DROP_K = 0, A_PLAIN_K = 1, A_DROP_T = 2, A_FINITE_K = 3 };
+// A_MAT_K / A_MAT_T (exit-flow fine-tuning): a plain matrix src[m][k] / src[k][m] of any number of rows, no row table behind it
+enum AMode : int { A_DROP_K = 0, A_PLAIN_K = 1, A_DROP_T = 2, A_FINITE_K = 3, A_MAT_K = 4, A_MAT_T = 5 };
 enum BMode : int { B_ROWS = 0, B_KCONT = 1 };                     // b[k][n]; b[n][k]
-enum Epi : int { EPI_RELU = 0, EPI_DX = 1, EPI_STORE = 2 };
+// EPI_DX0: EPI_DX without a ReLU in front of the dropout -- the gradient with respect to the head's input
+enum Epi : int { EPI_RELU = 0, EPI_DX = 1, EPI_STORE = 2, EPI_DX0 = 3 };
 
 struct TrainGemm {
     const float* a;             // A's source, rows of lda floats
@@ -100,8 +113,8 @@ struct TrainGemm {
     long long n_feat;           // rows of the feature cache (gather)
     int gather;                 // A's rows are a[rows[i]] (the feature cache) instead of a[i]
     int lda, ldb, ldo;
-    int M, N, K;                // M rows x N columns, K summed; N a multiple of 64; K a multiple of 32 unless A_DROP_T (then any, = batch)
-    Drop drop;                  // of A (A_DROP_*) or of the epilogue (EPI_DX)
+    int M, N, K;                // M rows x N columns, K summed; N a multiple of 64; K a multiple of 32 unless A_DROP_T / A_MAT_T (then any, M a multiple of 64)
+    Drop drop;                  // of A (A_DROP_*) or of the epilogue (EPI_DX, EPI_DX0)
 };
 
 // source row of batch row i, or null for one outside the cache
@@ -121,25 +134,30 @@ __global__ void __launch_bounds__(256) train_gemm_kernel(const TrainGemm p) {
     const int wm = wave & 1, wn = wave >> 1;
     const int n0 = blockIdx.x * TN, m0 = blockIdx.y * TM;
     const float nan = __builtin_nanf("");
+    constexpr bool AT = AM == A_DROP_T || AM == A_MAT_T;          // A comes as [k][m]
+    constexpr bool DXT = EPI == EPI_DX || EPI == EPI_DX0;         // the transposed output tile
 
     // what this thread brings in per chunk: two float4 of each operand
     // k-contiguous image [64 rows][32 k]: float4 f -> row f >> 3, k 4 (f & 7); row-contiguous [32 k][64 rows]: k f >> 4, row 4 (f & 15)
     const float* arow[2] = {nullptr, nullptr};
     unsigned actr[2] = {0u, 0u};
     bool alive[2] = {false, false};
-    if (AM != A_DROP_T) {
+    if (!AT) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int m = m0 + ((tid + i * 256) >> 3);
             alive[i] = m < p.M;
-            if (alive[i]) arow[i] = a_row(p, m, actr[i]);
+            if (alive[i]) arow[i] = AM == A_MAT_K ? p.a + (size_t)m * p.lda : a_row(p, m, actr[i]);
         }
     }
     float4 ra0, ra1, rb0, rb1;
     auto fetch = [&](int k0, int i, float4& ra, float4& rb) {
         {
             const int f = tid + i * 256;
-            if (AM == A_DROP_T) {
+            if (AM == A_MAT_T) {
+                const int kk = k0 + (f >> 4), u = m0 + (f & 15) * 4;
+                ra = kk < p.K ? *reinterpret_cast<const float4*>(p.a + (size_t)kk * p.lda + u) : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else if (AM == A_DROP_T) {
                 const int kk = k0 + (f >> 4), u = m0 + (f & 15) * 4;       // batch row, first of four units (u + 3 < M: M a multiple of 64)
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (kk < p.K) {
@@ -171,7 +189,7 @@ __global__ void __launch_bounds__(256) train_gemm_kernel(const TrainGemm p) {
     auto stash = [&](int i, const float4& ra, const float4& rb) {
         {
             const int f = tid + i * 256;
-            if (AM == A_DROP_T) *reinterpret_cast<float4*>(As + (f >> 4) * TM + (f & 15) * 4) = ra;
+            if (AT) *reinterpret_cast<float4*>(As + (f >> 4) * TM + (f & 15) * 4) = ra;
             else *reinterpret_cast<float4*>(As + (f >> 3) * KSTR + (f & 7) * 4) = ra;
             if (BM == B_ROWS) *reinterpret_cast<float4*>(Bs + (f >> 4) * TN + (f & 15) * 4) = rb;
             else *reinterpret_cast<float4*>(Bs + (f >> 3) * KSTR + (f & 7) * 4) = rb;
@@ -200,7 +218,7 @@ __global__ void __launch_bounds__(256) train_gemm_kernel(const TrainGemm p) {
         for (int j = 0; j < TK / 8; ++j) {
             const int kb = 8 * j + 4 * h;
             float a[4], b[4];
-            if (AM == A_DROP_T) {
+            if (AT) {
 #pragma unroll
                 for (int t = 0; t < 4; ++t) a[t] = As[(kb + t) * TM + wm * 32 + r32];
             } else {
@@ -216,7 +234,7 @@ __global__ void __launch_bounds__(256) train_gemm_kernel(const TrainGemm p) {
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t)     // EPI_DX takes the transposed tile: a lane then holds groups of four units of one batch row
-                acc4[j] = EPI == EPI_DX ? __builtin_amdgcn_mfma_f32_32x32x2f32(b[t], a[t], acc4[j], 0, 0, 0)
+                acc4[j] = DXT ? __builtin_amdgcn_mfma_f32_32x32x2f32(b[t], a[t], acc4[j], 0, 0, 0)
                                         : __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc4[j], 0, 0, 0);
         }
         __syncthreads();
@@ -226,7 +244,7 @@ __global__ void __launch_bounds__(256) train_gemm_kernel(const TrainGemm p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = (acc4[0][e] + acc4[1][e]) + (acc4[2][e] + acc4[3][e]);
     // D: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
-    if (EPI == EPI_DX) {        // transposed: column = the batch row, rows = units 8 q + 4 h .. + 3, one Philox draw per group
+    if (DXT) {                  // transposed: column = the batch row, rows = units 8 q + 4 h .. + 3, one Philox draw per group
         const int m = m0 + wm * 32 + r32;
         if (m < p.M) {
             const unsigned ctr = (unsigned)p.rows[m];
@@ -235,7 +253,8 @@ __global__ void __launch_bounds__(256) train_gemm_kernel(const TrainGemm p) {
                 const int n = n0 + wn * 32 + 8 * q + 4 * h;
                 const size_t o = (size_t)m * p.ldo + n;
                 const float4 dv = make_float4(acc[4 * q + 0], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
-                *reinterpret_cast<float4*>(p.out + o) =
+                if (EPI == EPI_DX0) *reinterpret_cast<float4*>(p.out + o) = drop_grad4(dv, (unsigned)(n >> 2), ctr, p.drop);
+                else *reinterpret_cast<float4*>(p.out + o) =
                     drop_relu_grad4(*reinterpret_cast<const float4*>(p.h + o), dv, (unsigned)(n >> 2), ctr, p.drop);
             }
         }
@@ -490,6 +509,7 @@ struct Batch {
     const float* params; const float* feats; long long n_feat; const long long* rows; const unsigned char* labels; int n;
     long long step;             // the Philox pass: bq_head_validate's `pass`
     double rate; void* ws;
+    int gather = 1;             // feats[rows[i]]; 0 (bq_exit_grad): feats[i], the rows being the Philox counters only
 };
 
 inline bool aligned(const void* p, uintptr_t a) { return p && !((uintptr_t)p & (a - 1)); }
@@ -539,7 +559,7 @@ void enqueue_forward(bq_ctx* c, const Batch& b, const Drop& d, float* h0, float*
     const double fn = (double)b.n;
     {   // h0 = relu(drop_0(x[rows]) W0 + b0)
         ProfScope ps(c, s, fwd0, 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_IN + (double)D_IN * D_H + fn * D_H));
-        launch_gemm<AM, B_ROWS, EPI_RELU>(b, d, 0u, ASrc{b.feats, D_IN, 1}, b.params + OFF_W0, b.params + OFF_B0, h0, b.n, D_IN, s);
+        launch_gemm<AM, B_ROWS, EPI_RELU>(b, d, 0u, ASrc{b.feats, D_IN, b.gather}, b.params + OFF_W0, b.params + OFF_B0, h0, b.n, D_IN, s);
     }
     {   // h1 = relu(drop_1(h0) W1 + b1)
         ProfScope ps(c, s, fwd1, 2.0 * fn * D_H * D_H, 4.0 * (2.0 * fn * D_H + (double)D_H * D_H));
@@ -569,7 +589,7 @@ int enqueue_grad(bq_ctx* c, const Batch& b, const Drop& d, float* grad, float* l
     }
     {   // g_W0 = drop_0(x[rows])^T dz0
         ProfScope ps(c, s, "head_train_dw0", 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_IN + fn * D_H + (double)D_IN * D_H));
-        launch_gemm<A_DROP_T, B_ROWS, EPI_STORE>(b, d, 0u, ASrc{b.feats, D_IN, 1}, w.dz0, nullptr, grad + OFF_W0, D_IN, n, s);
+        launch_gemm<A_DROP_T, B_ROWS, EPI_STORE>(b, d, 0u, ASrc{b.feats, D_IN, b.gather}, w.dz0, nullptr, grad + OFF_W0, D_IN, n, s);
     }
     {   // g_W2, g_b2, the loss, g_b1, g_b0
         ProfScope ps(c, s, "head_train_sums", 4.0 * fn * D_H + 2.0 * fn * D_H, 4.0 * 3.0 * fn * D_H);
@@ -591,12 +611,13 @@ std::string bad_adam_args(const char* entry, const void* params, const void* m, 
     return "";
 }
 
+// one Adam pass over `count` elements under the profiling class `cls` (the head's: P_TOTAL, "head_train_adam")
 int enqueue_adam(bq_ctx* c, float* params, float* m, float* v, const float* grad, long long step, double lr, double b1, double b2, double eps,
-                 hipStream_t s) {
+                 hipStream_t s, long long count = P_TOTAL, const char* cls = "head_train_adam") {
     const double t = (double)(step + 1);
     const double alpha = lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
-    ProfScope ps(c, s, "head_train_adam", 12.0 * (double)P_TOTAL, 28.0 * (double)P_TOTAL);
-    hipLaunchKernelGGL(train_adam_kernel, dim3((unsigned)((P_TOTAL + 255) / 256)), dim3(256), 0, s, params, m, v, grad, P_TOTAL, b1, b2, eps,
+    ProfScope ps(c, s, cls, 12.0 * (double)count, 28.0 * (double)count);
+    hipLaunchKernelGGL(train_adam_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, params, m, v, grad, count, b1, b2, eps,
                        alpha);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
@@ -624,9 +645,417 @@ int enqueue_validate(bq_ctx* c, const Batch& b, const Drop& d, double* stats, do
     return BQ_OK;
 }
 
+// ================================================================================================ exit-flow fine-tuning
+// DESIGN.md section 7 "Exit-flow fine-tuning": block 14 in front of the head, trained with it.  For a tile's cached
+// x = block13_out [10][10][1024], in fp32 and NHWC:
+//     u1 = dw(x, D1)   z1 = u1 P1 [1024 x 1536]   h1 = relu(a1 z1 + b1)
+//     u2 = dw(h1, D2)  z2 = u2 P2 [1536 x 2048]   h2 = relu(a2 z2 + b2)      f = mean over the 100 positions of h2 -> the head above
+// with a = gamma / sqrt(var + eps), b = beta - a mean and the moving statistics frozen.  Only u and z are stored: every reader of h
+// forms relu(fmaf(a, z, b)) again (bn_relu, one function).  The four pointwise products and their four transposes are
+// train_gemm_kernel (A_MAT_K / A_MAT_T: dP = u^T dz sums over K = 100 n rows), as is the head's input gradient (EPI_DX0); the
+// depthwise kernel, its two transposes, the pool and the BN backward are vector-ALU kernels over a tile's 100 positions x 256
+// channels per workgroup, a lane on four consecutive channels (float4), wave q on the positions q, q + 4, ... in order, the four
+// waves' partial sums then added in the order of q.  Sums over the batch (dD, dgamma, dbeta) go through per-tile partials in the
+// workspace and exit_colsum_kernel: eight row groups, then the groups in order.  No floating-point atomics anywhere.
+constexpr int X_POS = 100, X_HW = 10, X_C0 = 1024, X_C1 = 1536, X_C2 = 2048;
+constexpr long long X_ROW = (long long)X_POS * X_C0;            // floats of a tile in the activation cache
+constexpr long long E_D1 = 0, E_P1 = E_D1 + 9 * X_C0, E_G1 = E_P1 + (long long)X_C0 * X_C1, E_B1 = E_G1 + X_C1, E_D2 = E_B1 + X_C1,
+                    E_P2 = E_D2 + 9 * X_C1, E_G2 = E_P2 + (long long)X_C1 * X_C2, E_B2 = E_G2 + X_C2, P_EXIT = E_B2 + X_C2;
+static_assert(P_EXIT == 4748800 && P_EXIT % 4 == 0, "the exit vector's parameter count");
+constexpr long long P_ALL = P_EXIT + P_TOTAL;
+constexpr int S_M1 = 0, S_V1 = X_C1, S_M2 = 2 * X_C1, S_V2 = 2 * X_C1 + X_C2;      // d_bn_stats: mean1 | var1 | mean2 | var2
+constexpr int EXIT_MAX_N = 256;
+constexpr float BN_EPS = 1e-3f;
+
+__device__ __forceinline__ float bn_relu(float z, float a, float b) { return relu_nan(fmaf(a, z, b)); }
+__device__ __forceinline__ float4 bn_relu4(float4 z, float4 a, float4 b) {
+    return make_float4(bn_relu(z.x, a.x, b.x), bn_relu(z.y, a.y, b.y), bn_relu(z.z, a.z, b.z), bn_relu(z.w, a.w, b.w));
+}
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
+    return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
+}
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+// the four waves' partial sums in the order of q
+__device__ __forceinline__ float4 sum_q(const float4* l, int stride) { return add4(add4(add4(l[0], l[stride]), l[2 * stride]), l[3 * stride]); }
+
+// a = gamma / sqrt(var + eps), b = beta - a mean, inv = 1 / sqrt(var + eps) of one layer
+__global__ void __launch_bounds__(256) exit_coef_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        const float* __restrict__ mean, const float* __restrict__ var, int C,
+                                                        float* __restrict__ a, float* __restrict__ b, float* __restrict__ inv) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float sd = sqrtf(var[c] + BN_EPS), ac = gamma[c] / sd;
+    a[c] = ac;
+    b[c] = beta[c] - ac * mean[c];
+    inv[c] = 1.f / sd;
+}
+
+// What a depthwise kernel reads: the activation cache through the row table (a row outside it is never read and reads as NaN, a
+// value that is not finite as NaN), relu(a z + b) of a stored z, or a plain [100 n][C] tensor.
+enum DwIn : int { IN_CACHE = 0, IN_BN = 1, IN_PLAIN = 2 };
+struct DwSrc { const float* p; const long long* rows; long long n_act; const float* a; const float* b; };
+
+template <int IN, int C>
+__device__ __forceinline__ const float* dw_tile(const DwSrc& s, int i) {
+    if (IN != IN_CACHE) return s.p + (size_t)i * X_POS * C;
+    const long long r = s.rows[i];
+    return (r >= 0 && r < s.n_act) ? s.p + (size_t)r * (size_t)X_ROW : nullptr;     // 64-bit: a row is 102 400 floats
+}
+template <int IN, int C>
+__device__ __forceinline__ float4 dw_at(const float* tile, int pos, int c, const float4& a, const float4& b) {
+    if (IN == IN_CACHE && !tile) { const float nan = __builtin_nanf(""); return make_float4(nan, nan, nan, nan); }
+    const float4 v = ld4(tile + (size_t)pos * C + c);
+    return IN == IN_CACHE ? finite4(v) : IN == IN_BN ? bn_relu4(v, a, b) : v;
+}
+
+// out[i][y][x][c] = sum over the taps (ky, kx) in order of in[i][y + ky - 1][x + kx - 1][c] w[ky][kx][c], an fmaf chain; zero padding 1
+// (a tap outside the map adds nothing).  FLIP: the taps reversed -- the transpose, the gradient with respect to the input.
+template <int IN, int C, bool FLIP>
+__global__ void __launch_bounds__(256) exit_dw_kernel(const DwSrc s, const float* __restrict__ w, float* __restrict__ out) {
+    const int i = blockIdx.y, c = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, q = threadIdx.x >> 6;
+    const float* tile = dw_tile<IN, C>(s, i);
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 a = IN == IN_BN ? ld4(s.a + c) : zero, b = IN == IN_BN ? ld4(s.b + c) : zero;
+    float4 wt[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) wt[t] = ld4(w + (size_t)(FLIP ? 8 - t : t) * C + c);
+    for (int pos = q; pos < X_POS; pos += 4) {
+        const int y = pos / X_HW, x = pos - y * X_HW;
+        float4 acc = zero;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int yy = y + ky - 1, xx = x + kx - 1;
+                if (yy >= 0 && yy < X_HW && xx >= 0 && xx < X_HW) acc = fma4(dw_at<IN, C>(tile, yy * X_HW + xx, c, a, b), wt[ky * 3 + kx], acc);
+            }
+        st4(out + ((size_t)i * X_POS + pos) * C + c, acc);
+    }
+}
+
+// part[i][ky][kx][c] = sum over tile i's positions of in[i][y + ky - 1][x + kx - 1][c] du[i][y][x][c]: the depthwise kernel's weight
+// gradient of one tile (exit_colsum_kernel adds the tiles).
+template <int IN, int C>
+__global__ void __launch_bounds__(256) exit_dw_wgrad_kernel(const DwSrc s, const float* __restrict__ du, float* __restrict__ part) {
+    __shared__ float4 lds[4][9][64];
+    const int i = blockIdx.y, cq = threadIdx.x & 63, c = (blockIdx.x * 64 + cq) * 4, q = threadIdx.x >> 6;
+    const float* tile = dw_tile<IN, C>(s, i);
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 a = IN == IN_BN ? ld4(s.a + c) : zero, b = IN == IN_BN ? ld4(s.b + c) : zero;
+    float4 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[t] = zero;
+    for (int pos = q; pos < X_POS; pos += 4) {
+        const int y = pos / X_HW, x = pos - y * X_HW;
+        const float4 g = ld4(du + ((size_t)i * X_POS + pos) * C + c);
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int yy = y + ky - 1, xx = x + kx - 1;
+                if (yy >= 0 && yy < X_HW && xx >= 0 && xx < X_HW)
+                    acc[ky * 3 + kx] = fma4(dw_at<IN, C>(tile, yy * X_HW + xx, c, a, b), g, acc[ky * 3 + kx]);
+            }
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) lds[q][t][cq] = acc[t];
+    __syncthreads();
+    for (int e = threadIdx.x; e < 9 * 64; e += 256) {
+        const int t = e >> 6, k = e & 63;
+        st4(part + ((size_t)i * 9 + t) * C + (blockIdx.x * 64 + k) * 4, sum_q(&lds[0][t][k], 9 * 64));
+    }
+}
+
+// f[i][c] = (sum over tile i's positions of relu(a z2 + b)) / 100
+__global__ void __launch_bounds__(256) exit_pool_kernel(const float* __restrict__ z, const float* __restrict__ a, const float* __restrict__ b,
+                                                        float* __restrict__ f) {
+    __shared__ float4 lds[4][64];
+    const int i = blockIdx.y, cq = threadIdx.x & 63, c = (blockIdx.x * 64 + cq) * 4, q = threadIdx.x >> 6;
+    const float4 av = ld4(a + c), bv = ld4(b + c);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int pos = q; pos < X_POS; pos += 4) acc = add4(acc, bn_relu4(ld4(z + ((size_t)i * X_POS + pos) * X_C2 + c), av, bv));
+    lds[q][cq] = acc;
+    __syncthreads();
+    if (q == 0) {
+        const float4 v = sum_q(&lds[0][cq], 64);
+        st4(f + (size_t)i * X_C2 + c, make_float4(v.x / 100.f, v.y / 100.f, v.z / 100.f, v.w / 100.f));
+    }
+}
+
+// The BN + ReLU backward of one layer over tile i: with h = relu(a z + b) and g = dh [h > 0] (a NaN h keeps its NaN),
+// dz = g a, and the tile's partial sums part[i][0][c] = sum g (z - mean) inv (dgamma), part[i][1][c] = sum g (dbeta).  BCAST: dh is the
+// pool's transpose, df[i][c] / 100 at every position; otherwise dh [100 n][C], which dz may overwrite in place.
+template <bool BCAST, int C>
+__global__ void __launch_bounds__(256) exit_bn_back_kernel(const float* __restrict__ z, const float* dh, const float* __restrict__ a,
+                                                           const float* __restrict__ b, const float* __restrict__ mean,
+                                                           const float* __restrict__ inv, float* dz, float* __restrict__ part) {
+    __shared__ float4 lds[4][2][64];
+    const int i = blockIdx.y, cq = threadIdx.x & 63, c = (blockIdx.x * 64 + cq) * 4, q = threadIdx.x >> 6;
+    const float4 av = ld4(a + c), bv = ld4(b + c), mv = ld4(mean + c), iv = ld4(inv + c);
+    float4 top = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (BCAST) {
+        top = ld4(dh + (size_t)i * C + c);
+        top = make_float4(top.x / 100.f, top.y / 100.f, top.z / 100.f, top.w / 100.f);
+    }
+    float4 sg = make_float4(0.f, 0.f, 0.f, 0.f), sb = sg;
+    for (int pos = q; pos < X_POS; pos += 4) {
+        const size_t o = ((size_t)i * X_POS + pos) * C + c;
+        const float4 zv = ld4(z + o), h = bn_relu4(zv, av, bv), d = BCAST ? top : ld4(dh + o);
+        const float4 g = make_float4(h.x > 0.f ? d.x : (h.x != h.x ? h.x : 0.f), h.y > 0.f ? d.y : (h.y != h.y ? h.y : 0.f),
+                                     h.z > 0.f ? d.z : (h.z != h.z ? h.z : 0.f), h.w > 0.f ? d.w : (h.w != h.w ? h.w : 0.f));
+        st4(dz + o, make_float4(g.x * av.x, g.y * av.y, g.z * av.z, g.w * av.w));
+        sg = fma4(g, make_float4((zv.x - mv.x) * iv.x, (zv.y - mv.y) * iv.y, (zv.z - mv.z) * iv.z, (zv.w - mv.w) * iv.w), sg);
+        sb = add4(sb, g);
+    }
+    lds[q][0][cq] = sg;
+    lds[q][1][cq] = sb;
+    __syncthreads();
+    if (q < 2) st4(part + ((size_t)i * 2 + q) * C + c, sum_q(&lds[0][q][cq], 2 * 64));
+}
+
+// dst[j] = sum over the n rows of src[i][j], j < W (a multiple of 32): a workgroup is 8 row groups x 32 columns, row group q sums the
+// rows q, q + 8, ... in order, then the eight partial sums are added in the order of q.
+__global__ void __launch_bounds__(256) exit_colsum_kernel(const float* __restrict__ src, int n, int W, float* __restrict__ dst) {
+    __shared__ float part[8][33];
+    const int q = threadIdx.x >> 5, l = threadIdx.x & 31, j = blockIdx.x * 32 + l;
+    float s = 0.f;
+    for (int i = q; i < n; i += 8) s += src[(size_t)i * W + j];
+    part[q][l] = s;
+    __syncthreads();
+    if (q == 0) {
+        s = part[0][l];
+        for (int k = 1; k < 8; ++k) s += part[k][l];
+        dst[j] = s;
+    }
+}
+
+// The layout of both exit workspaces, the regions in order, each rounded up to 256 bytes; `train`: the backward regions and the
+// head's own workspace behind the forward ones.  du1 takes du2's place once du2 is spent.
+struct ExitWs {
+    float *a1, *b1, *i1, *a2, *b2, *i2, *u1, *z1, *u2, *z2, *f;           // forward
+    float *df, *dz2, *du, *dz1, *part; void* head;                         // backward
+    size_t total;
+};
+ExitWs exit_ws(void* ws, size_t n, bool train) {
+    uintptr_t p = (uintptr_t)ws;
+    ExitWs w{};
+    auto take = [&](size_t floats) { float* r = (float*)p; p += al(floats * 4); return r; };
+    w.a1 = take(X_C1); w.b1 = take(X_C1); w.i1 = take(X_C1);
+    w.a2 = take(X_C2); w.b2 = take(X_C2); w.i2 = take(X_C2);
+    w.u1 = take(n * X_POS * X_C0); w.z1 = take(n * X_POS * X_C1); w.u2 = take(n * X_POS * X_C1); w.z2 = take(n * X_POS * X_C2);
+    w.f = take(n * X_C2);
+    if (train) {
+        w.df = take(n * X_C2); w.dz2 = take(n * X_POS * X_C2); w.du = take(n * X_POS * X_C1); w.dz1 = take(n * X_POS * X_C1);
+        w.part = take(n * 9 * X_C1);                // (9 C1 >= 9 C0, 2 C2, 2 C1)
+        w.head = (void*)p; p += train_ws(nullptr, n).total;
+    }
+    w.total = p - (uintptr_t)ws;
+    return w;
+}
+
+// a plain product on train_gemm_kernel: out [M][N] = A B; rows, d: of EPI_DX0
+template <int AM, int BM, int EPI>
+void launch_mat(const float* a, int lda, const float* bm, int ldb, float* out, int ldo, int M, int N, int K, hipStream_t s,
+                const long long* rows = nullptr, Drop d = Drop{}) {
+    TrainGemm p{};
+    p.a = a; p.lda = lda; p.b = bm; p.ldb = ldb; p.out = out; p.ldo = ldo; p.rows = rows; p.M = M; p.N = N; p.K = K; p.drop = d;
+    hipLaunchKernelGGL((train_gemm_kernel<AM, BM, EPI>), dim3(N / TN, (M + TM - 1) / TM), dim3(256), 0, s, p);
+}
+
+struct ExitBatch { const float* params; const float* stats; const float* acts; long long n_act; const long long* rows; int n; };
+
+// The forward half, seven launches under the classes `pre`coef, dw1, pw1, dw2, pw2, pool: acts[rows] -> w.f [n][2048] (u and z stay in w).
+void enqueue_exit_forward(bq_ctx* c, const ExitBatch& b, const ExitWs& w, const std::string& pre, hipStream_t s) {
+    const int n = b.n, M = n * X_POS;
+    const double fm = (double)M;
+    const float* e = b.params;
+    {
+        ProfScope ps(c, s, pre + "coef", 8.0 * (X_C1 + X_C2), 28.0 * (X_C1 + X_C2));
+        hipLaunchKernelGGL(exit_coef_kernel, dim3(X_C1 / 256), dim3(256), 0, s, e + E_G1, e + E_B1, b.stats + S_M1, b.stats + S_V1, X_C1, w.a1,
+                           w.b1, w.i1);
+        hipLaunchKernelGGL(exit_coef_kernel, dim3(X_C2 / 256), dim3(256), 0, s, e + E_G2, e + E_B2, b.stats + S_M2, b.stats + S_V2, X_C2, w.a2,
+                           w.b2, w.i2);
+    }
+    {
+        ProfScope ps(c, s, pre + "dw1", 18.0 * fm * X_C0, 8.0 * fm * X_C0);
+        hipLaunchKernelGGL((exit_dw_kernel<IN_CACHE, X_C0, false>), dim3(X_C0 / 256, n), dim3(256), 0, s,
+                           DwSrc{b.acts, b.rows, b.n_act, nullptr, nullptr}, e + E_D1, w.u1);
+    }
+    {
+        ProfScope ps(c, s, pre + "pw1", 2.0 * fm * X_C0 * X_C1, 4.0 * (fm * X_C0 + fm * X_C1 + (double)X_C0 * X_C1));
+        launch_mat<A_MAT_K, B_ROWS, EPI_STORE>(w.u1, X_C0, e + E_P1, X_C1, w.z1, X_C1, M, X_C1, X_C0, s);
+    }
+    {
+        ProfScope ps(c, s, pre + "dw2", 20.0 * fm * X_C1, 8.0 * fm * X_C1);
+        hipLaunchKernelGGL((exit_dw_kernel<IN_BN, X_C1, false>), dim3(X_C1 / 256, n), dim3(256), 0, s, DwSrc{w.z1, nullptr, 0, w.a1, w.b1},
+                           e + E_D2, w.u2);
+    }
+    {
+        ProfScope ps(c, s, pre + "pw2", 2.0 * fm * X_C1 * X_C2, 4.0 * (fm * X_C1 + fm * X_C2 + (double)X_C1 * X_C2));
+        launch_mat<A_MAT_K, B_ROWS, EPI_STORE>(w.u2, X_C1, e + E_P2, X_C2, w.z2, X_C2, M, X_C2, X_C1, s);
+    }
+    {
+        ProfScope ps(c, s, pre + "pool", 3.0 * fm * X_C2, 4.0 * fm * X_C2);
+        hipLaunchKernelGGL(exit_pool_kernel, dim3(X_C2 / 256, n), dim3(256), 0, s, w.z2, w.a2, w.b2, w.f);
+    }
+}
+
+// One gradient over [exit | head]: the forward half, the head's seven launches on w.f (the same kernels as bq_head_grad: its rows
+// are the batch's own, the row table the Philox counters), the head's input gradient, then block 14 backwards.
+int enqueue_exit_grad(bq_ctx* c, const ExitBatch& b, const unsigned char* labels, long long step, uint64_t seed, double rate, void* ws,
+                      float* grad, float* loss, hipStream_t s) {
+    const int n = b.n, M = n * X_POS;
+    const double fm = (double)M, fn = (double)n;
+    const ExitWs w = exit_ws(ws, n, true);
+    const float* e = b.params;
+    enqueue_exit_forward(c, b, w, "exit_train_", s);
+    Batch hb{b.params + P_EXIT, w.f, (long long)n, b.rows, labels, n, step, rate, w.head};
+    hb.gather = 0;
+    const Drop d = drop_of(hb, seed);
+    RUN(enqueue_grad(c, hb, d, grad + P_EXIT, loss, s));
+    const TrainWs hw = train_ws(w.head, n);
+    {   // df = drop_0'(dz0 W0^T)
+        ProfScope ps(c, s, "exit_train_dfeat", 2.0 * fn * D_IN * D_H, 4.0 * (fn * D_H + fn * D_IN + (double)D_IN * D_H));
+        Drop d0 = d; d0.layer = 0u;
+        launch_mat<A_MAT_K, B_KCONT, EPI_DX0>(hw.dz0, D_H, b.params + P_EXIT + OFF_W0, D_H, w.df, D_IN, n, D_IN, D_H, s, b.rows, d0);
+    }
+    {   // dz2, and the tiles' parts of dgamma2 | dbeta2
+        ProfScope ps(c, s, "exit_train_bn2", 8.0 * fm * X_C2, 8.0 * fm * X_C2);
+        hipLaunchKernelGGL((exit_bn_back_kernel<true, X_C2>), dim3(X_C2 / 256, n), dim3(256), 0, s, w.z2, w.df, w.a2, w.b2, b.stats + S_M2,
+                           w.i2, w.dz2, w.part);
+        hipLaunchKernelGGL(exit_colsum_kernel, dim3(2 * X_C2 / 32), dim3(256), 0, s, w.part, n, 2 * X_C2, grad + E_G2);
+    }
+    {   // dP2 = u2^T dz2
+        ProfScope ps(c, s, "exit_train_dp2", 2.0 * fm * X_C1 * X_C2, 4.0 * (fm * X_C1 + fm * X_C2 + (double)X_C1 * X_C2));
+        launch_mat<A_MAT_T, B_ROWS, EPI_STORE>(w.u2, X_C1, w.dz2, X_C2, grad + E_P2, X_C2, X_C1, X_C2, M, s);
+    }
+    {   // du2 = dz2 P2^T
+        ProfScope ps(c, s, "exit_train_du2", 2.0 * fm * X_C1 * X_C2, 4.0 * (fm * X_C1 + fm * X_C2 + (double)X_C1 * X_C2));
+        launch_mat<A_MAT_K, B_KCONT, EPI_STORE>(w.dz2, X_C2, e + E_P2, X_C2, w.du, X_C1, M, X_C1, X_C2, s);
+    }
+    {   // dD2 over h1 = relu(a1 z1 + b1)
+        ProfScope ps(c, s, "exit_train_dd2", 20.0 * fm * X_C1, 8.0 * fm * X_C1);
+        hipLaunchKernelGGL((exit_dw_wgrad_kernel<IN_BN, X_C1>), dim3(X_C1 / 256, n), dim3(256), 0, s, DwSrc{w.z1, nullptr, 0, w.a1, w.b1}, w.du,
+                           w.part);
+        hipLaunchKernelGGL(exit_colsum_kernel, dim3(9 * X_C1 / 32), dim3(256), 0, s, w.part, n, 9 * X_C1, grad + E_D2);
+    }
+    {   // dh1 = dw^T(du2, D2)
+        ProfScope ps(c, s, "exit_train_dh1", 18.0 * fm * X_C1, 8.0 * fm * X_C1);
+        hipLaunchKernelGGL((exit_dw_kernel<IN_PLAIN, X_C1, true>), dim3(X_C1 / 256, n), dim3(256), 0, s, DwSrc{w.du, nullptr, 0, nullptr, nullptr},
+                           e + E_D2, w.dz1);
+    }
+    {   // dz1 in place, and the tiles' parts of dgamma1 | dbeta1
+        ProfScope ps(c, s, "exit_train_bn1", 8.0 * fm * X_C1, 12.0 * fm * X_C1);
+        hipLaunchKernelGGL((exit_bn_back_kernel<false, X_C1>), dim3(X_C1 / 256, n), dim3(256), 0, s, w.z1, w.dz1, w.a1, w.b1, b.stats + S_M1,
+                           w.i1, w.dz1, w.part);
+        hipLaunchKernelGGL(exit_colsum_kernel, dim3(2 * X_C1 / 32), dim3(256), 0, s, w.part, n, 2 * X_C1, grad + E_G1);
+    }
+    {   // dP1 = u1^T dz1
+        ProfScope ps(c, s, "exit_train_dp1", 2.0 * fm * X_C0 * X_C1, 4.0 * (fm * X_C0 + fm * X_C1 + (double)X_C0 * X_C1));
+        launch_mat<A_MAT_T, B_ROWS, EPI_STORE>(w.u1, X_C0, w.dz1, X_C1, grad + E_P1, X_C1, X_C0, X_C1, M, s);
+    }
+    {   // du1 = dz1 P1^T, where du2 was
+        ProfScope ps(c, s, "exit_train_du1", 2.0 * fm * X_C0 * X_C1, 4.0 * (fm * X_C0 + fm * X_C1 + (double)X_C0 * X_C1));
+        launch_mat<A_MAT_K, B_KCONT, EPI_STORE>(w.dz1, X_C1, e + E_P1, X_C1, w.du, X_C0, M, X_C0, X_C1, s);
+    }
+    {   // dD1 over the cached x
+        ProfScope ps(c, s, "exit_train_dd1", 18.0 * fm * X_C0, 8.0 * fm * X_C0);
+        hipLaunchKernelGGL((exit_dw_wgrad_kernel<IN_CACHE, X_C0>), dim3(X_C0 / 256, n), dim3(256), 0, s,
+                           DwSrc{b.acts, b.rows, b.n_act, nullptr, nullptr}, w.du, w.part);
+        hipLaunchKernelGGL(exit_colsum_kernel, dim3(9 * X_C0 / 32), dim3(256), 0, s, w.part, n, 9 * X_C0, grad + E_D1);
+    }
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// The refusal of an exit batch, "" for none; own_ok: the entry's own pointers are there and aligned.
+std::string bad_exit(bq_ctx* c, const char* entry, const ExitBatch& b, const void* ws, bool own_ok) {
+    const std::string e(entry);
+    if (!c) return e + ": null context";
+    if (b.n < 1 || b.n > EXIT_MAX_N) return e + ": 1 <= n <= " + std::to_string(EXIT_MAX_N);
+    if (b.n_act < 1) return e + ": an empty activation cache";
+    if (!aligned(b.params, 16) || !aligned(b.stats, 16) || !aligned(b.acts, 16) || !aligned(b.rows, 8) || !aligned(ws, 256) || !own_ok)
+        return e + ": bad argument (null pointer, params, stats, acts or an output not 16-byte, rows not 8-byte or the workspace not 256-byte aligned)";
+    return "";
+}
+std::string bad_exit_grad(bq_ctx* c, const char* entry, const ExitBatch& b, const void* labels, long long step, double rate, const void* ws,
+                          const void* grad, const void* loss) {
+    const std::string bad = bad_exit(c, entry, b, ws, labels && aligned(grad, 16) && aligned(loss, 4));
+    if (!bad.empty()) return bad;
+    if (step < 0 || step > 0xffffffffLL || !(rate >= 0.0) || !(rate < 1.0))
+        return std::string(entry) + ": a step outside 0 .. 2^32 - 1, or a rate outside [0, 1)";
+    return "";
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t bq_exit_features_workspace_bytes(int n) { return n < 1 || n > EXIT_MAX_N ? 0 : exit_ws(nullptr, n, false).total; }
+size_t bq_exit_train_workspace_bytes(int n) { return n < 1 || n > EXIT_MAX_N ? 0 : exit_ws(nullptr, n, true).total; }
+
+int bq_exit_features(bq_ctx* c, const float* d_exit_params, const float* d_bn_stats, const float* d_acts, int64_t n_act, const int64_t* d_rows,
+                     int n, float* d_feat2048, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    const ExitBatch b{d_exit_params, d_bn_stats, d_acts, (long long)n_act, (const long long*)d_rows, n};
+    const std::string bad = bad_exit(c, "bq_exit_features", b, d_ws, aligned(d_feat2048, 16));
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < bq_exit_features_workspace_bytes(n))
+        return fail(c, BQ_ERR_WORKSPACE, "bq_exit_features: workspace below bq_exit_features_workspace_bytes(n)");
+    DeviceGuard guard(c->device);
+    ExitWs w = exit_ws(d_ws, n, false);
+    w.f = d_feat2048;
+    enqueue_exit_forward(c, b, w, "exit_feat_", (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int bq_exit_grad(bq_ctx* c, const float* d_params, const float* d_bn_stats, const float* d_acts, int64_t n_act, const int64_t* d_rows,
+                 const uint8_t* d_labels, int n, int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, void* d_ws,
+                 size_t ws_bytes, bq_stream_t stream) {
+    const ExitBatch b{d_params, d_bn_stats, d_acts, (long long)n_act, (const long long*)d_rows, n};
+    const std::string bad = bad_exit_grad(c, "bq_exit_grad", b, d_labels, (long long)step, rate, d_ws, d_grad, d_loss);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < bq_exit_train_workspace_bytes(n)) return fail(c, BQ_ERR_WORKSPACE, "bq_exit_grad: workspace below bq_exit_train_workspace_bytes(n)");
+    DeviceGuard guard(c->device);
+    return enqueue_exit_grad(c, b, d_labels, (long long)step, seed, rate, d_ws, d_grad, d_loss, (hipStream_t)stream);
+}
+
+int bq_adam_n(bq_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, int64_t count, int64_t step, double lr, double b1,
+              double b2, double eps, bq_stream_t stream) {
+    if (!c) return fail(c, BQ_ERR_ARG, "bq_adam_n: null context");
+    if (count < 1 || count > (int64_t)0xffffffffLL * 256) return fail(c, BQ_ERR_ARG, "bq_adam_n: 1 <= count <= 256 (2^32 - 1)");
+    const std::string bad = bad_adam_args("bq_adam_n", d_params, d_m, d_v, d_grad, step, lr, b1, b2, eps);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    DeviceGuard guard(c->device);
+    return enqueue_adam(c, d_params, d_m, d_v, d_grad, (long long)step, lr, b1, b2, eps, (hipStream_t)stream, (long long)count, "adam_n");
+}
+
+int bq_exit_train_steps(bq_ctx* c, float* d_params, float* d_m, float* d_v, float* d_grad, const float* d_bn_stats, const float* d_acts,
+                        int64_t n_act, const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n, int64_t step0,
+                        uint64_t seed, double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws,
+                        size_t ws_bytes, bq_stream_t stream) {
+    if (!c) return fail(c, BQ_ERR_ARG, "bq_exit_train_steps: null context");
+    if (steps < 1 || steps > (1 << 24) || last_n < 1 || last_n > batch || !h_lr)
+        return fail(c, BQ_ERR_ARG, "bq_exit_train_steps: 1 <= steps <= 2^24, 1 <= last_n <= batch and a learning rate per step");
+    ExitBatch b{d_params, d_bn_stats, d_acts, (long long)n_act, (const long long*)d_rows, batch};
+    std::string bad = bad_exit_grad(c, "bq_exit_train_steps", b, d_labels, (long long)step0, rate, d_ws, d_grad, d_losses);
+    if (bad.empty() && step0 + steps > 0x100000000LL) bad = "bq_exit_train_steps: the steps pass 2^32";
+    for (int i = 0; bad.empty() && i < steps; ++i) bad = bad_adam_args("bq_exit_train_steps", d_params, d_m, d_v, d_grad, step0 + i, h_lr[i], b1, b2, eps);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < bq_exit_train_workspace_bytes(batch))
+        return fail(c, BQ_ERR_WORKSPACE, "bq_exit_train_steps: workspace below bq_exit_train_workspace_bytes(batch)");
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < steps; ++i) {
+        b.rows = (const long long*)d_rows + (size_t)i * batch;
+        b.n = i + 1 < steps ? batch : last_n;
+        RUN(enqueue_exit_grad(c, b, d_labels + (size_t)i * batch, (long long)step0 + i, seed, rate, d_ws, d_grad, d_losses + i, s));
+        RUN(enqueue_adam(c, d_params, d_m, d_v, d_grad, (long long)step0 + i, h_lr[i], b1, b2, eps, s, P_ALL, "exit_train_adam"));
+    }
+    return BQ_OK;
+}
 
 size_t bq_head_train_workspace_bytes(int n) { return n < 1 || n > MAX_N ? 0 : train_ws(nullptr, n).total; }
 

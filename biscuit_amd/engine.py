@@ -130,7 +130,7 @@ class Engine:
         """Lets go of every device buffer grown on demand -- the network's workspace and each tool's scratch -- and of nothing else;
         the next call that wants one allocates it again."""
         self._ws = None                  # the network's workspace (``_ws_for``)
-        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong, train, validate, augment
+        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong, train, validate, augment, exit_features, exit_train, exit_validate
 
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
@@ -1236,6 +1236,143 @@ class Engine:
                                                   lr.ctypes.data_as(C.POINTER(C.c_double)), float(b1), float(b2), float(eps), _ptr(losses),
                                                   _ptr(scratch), scratch.numel(), self._stream()))
         return losses
+
+    # ------------------------------------------------------------------ exit-flow fine-tuning (kernels_train.hip)
+    EXIT_PARAMS, EXIT_BN_STATS, EXIT_MAX_ROWS, EXIT_ACT_SHAPE = 4748800, 7168, 256, (10, 10, 1024)   # (train.py holds copies)
+    ALL_PARAMS = EXIT_PARAMS + HEAD_PARAMS
+
+    def trunk(self, tiles_u8):
+        """uint8 NHWC tiles (device) -> ``block13_out`` float32 [n, 10, 10, 1024] at true scale (``bq_trunk_u8``): ``backbone_u8``'s
+        launches up to the tensor block 14 reads, what ``train.cache_activations`` keeps per tile."""
+        assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous()
+        n = tiles_u8.shape[0]
+        ws = self._ws_for(n, 1)
+        out = torch.empty((n,) + self.EXIT_ACT_SHAPE, dtype=torch.float32, device=self.device)
+        self._check(self._lib.bq_trunk_u8(self._ctx, _ptr(tiles_u8), n, _ptr(out), _ptr(ws), ws.numel(), self._stream()))
+        return out
+
+    def exit_train_scratch(self, n):
+        """A caller's own scratch for ``exit_grad`` / ``exit_train_steps`` with batches of up to ``n`` rows (``scratch=``); without one
+        the calls share the engine's cached ``exit_train`` buffer."""
+        return self._bytes(self._lib.bq_exit_train_workspace_bytes(int(n)))
+
+    def exit_features_scratch(self, n):
+        """A caller's own scratch for ``exit_features`` over up to ``n`` rows; without one the calls share the cached ``exit_features`` buffer."""
+        return self._bytes(self._lib.bq_exit_features_workspace_bytes(int(n)))
+
+    def _exit_vec(self, count, *named):
+        for name, t in named:
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == count and t.is_contiguous()):
+                raise ValueError(f'{name} must be contiguous float32 [{count}]')
+            self._on_device(name, t)
+
+    def _exit_batch(self, call, bn_stats, acts, rows, labels, count):
+        """``bn_stats`` float32 [7168], ``acts`` float32 [N, 10, 10, 1024], ``rows`` int64 and (unless None) ``labels`` uint8, ``count``
+        of each, all on this device; ValueError otherwise."""
+        self._exit_vec(self.EXIT_BN_STATS, ('bn_stats', bn_stats))
+        if not (torch.is_tensor(acts) and acts.dtype == torch.float32 and acts.dim() == 4 and tuple(acts.shape[1:]) == self.EXIT_ACT_SHAPE and
+                acts.shape[0] >= 1 and acts.is_contiguous()):
+            raise ValueError(f'{call}: acts must be contiguous float32 [N, 10, 10, 1024] with N >= 1')
+        if not (torch.is_tensor(rows) and rows.dtype == torch.int64 and rows.is_contiguous() and rows.numel() == count):
+            raise ValueError(f'{call}: rows must be contiguous int64 [{count}]')
+        if labels is not None and not (torch.is_tensor(labels) and labels.dtype == torch.uint8 and labels.is_contiguous() and
+                                       labels.numel() == count):
+            raise ValueError(f'{call}: labels must be contiguous uint8 [{count}]')
+        for name, t in (('acts', acts), ('rows', rows)) + ((('labels', labels),) if labels is not None else ()):
+            self._on_device(name, t)
+
+    def exit_features(self, exit_params, bn_stats, acts, rows, out=None, scratch=None):
+        """Block 14 and the pool over the rows ``acts[rows]`` (``bq_exit_features``): ``exit_params`` float32 [P_EXIT] in the order of
+        ``train.EXIT_TENSORS``, ``bn_stats`` float32 [7168] (``train.exit_bn_stats``), ``acts`` float32 [N, 10, 10, 1024], ``rows`` int64
+        [n], 1 <= n <= 256 -> float32 [n, 2048] on the device (``out``: written there).  A tile's row depends on the tile and the
+        parameters only."""
+        n = int(rows.numel()) if torch.is_tensor(rows) else -1
+        if not 1 <= n <= self.EXIT_MAX_ROWS:
+            raise ValueError(f'exit_features: 1 <= n <= {self.EXIT_MAX_ROWS} rows, as an int64 tensor')
+        self._exit_vec(self.EXIT_PARAMS, ('exit_params', exit_params))
+        self._exit_batch('exit_features', bn_stats, acts, rows, None, n)
+        if out is None:
+            out = torch.empty((n, 2048), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, 2048)
+        scratch = self._scratch('exit_features', int(self._lib.bq_exit_features_workspace_bytes(n)), scratch)
+        assert scratch.is_cuda and scratch.is_contiguous()
+        self._check(self._lib.bq_exit_features(self._ctx, _ptr(exit_params), _ptr(bn_stats), _ptr(acts), int(acts.shape[0]), _ptr(rows), n,
+                                               _ptr(out), _ptr(scratch), scratch.numel(), self._stream()))
+        return out
+
+    def exit_features_all(self, exit_params, bn_stats, acts, rows):
+        """``exit_features`` over any number of rows, in calls of up to 256 -> float32 [len(rows), 2048]."""
+        out = torch.empty((int(rows.numel()), 2048), dtype=torch.float32, device=self.device)
+        for a in range(0, int(rows.numel()), self.EXIT_MAX_ROWS):
+            self.exit_features(exit_params, bn_stats, acts, rows[a:a + self.EXIT_MAX_ROWS].contiguous(), out=out[a:a + self.EXIT_MAX_ROWS])
+        return out
+
+    def exit_grad(self, params, bn_stats, acts, rows, labels, step, seed, rate=None, grad=None, scratch=None):
+        """Gradient of the mean cross-entropy over the rows ``acts[rows]`` through block 14 and the head (``bq_exit_grad``): ``params``
+        float32 [P_ALL] -- the exit vector, then the head's --, ``labels`` uint8 [n] in {0, 1}, 1 <= n <= 256; dropout ``rate`` (the
+        engine's when None) with pass = ``step`` and the rows as Philox tile counters.  -> ``(grad [P_ALL], loss [1])`` on the device."""
+        n = int(rows.numel()) if torch.is_tensor(rows) else -1
+        if not 1 <= n <= self.EXIT_MAX_ROWS:
+            raise ValueError(f'exit_grad: 1 <= n <= {self.EXIT_MAX_ROWS} rows, as an int64 tensor')
+        self._exit_vec(self.ALL_PARAMS, ('params', params))
+        self._exit_batch('exit_grad', bn_stats, acts, rows, labels, n)
+        if grad is None:
+            grad = torch.empty(self.ALL_PARAMS, dtype=torch.float32, device=self.device)
+        self._exit_vec(self.ALL_PARAMS, ('grad', grad))
+        rate, scratch = self._head_open('exit_train', self._lib.bq_exit_train_workspace_bytes(n), rate, step, 1, scratch,
+                                        'exit_grad: the rate lies in [0, 1) and the step in 0 .. 2^32 - 1')
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        self._check(self._lib.bq_exit_grad(self._ctx, _ptr(params), _ptr(bn_stats), _ptr(acts), int(acts.shape[0]), _ptr(rows), _ptr(labels), n,
+                                           int(step), int(seed), rate, _ptr(grad), _ptr(loss), _ptr(scratch), scratch.numel(), self._stream()))
+        return grad, loss
+
+    def adam_n(self, params, m, v, grad, step, lr, b1=0.9, b2=0.999, eps=1e-7):
+        """One Keras-Adam pass in place over float32 vectors of any one length (``bq_adam_n``: ``head_adam``'s kernel), t = ``step`` + 1."""
+        count = int(params.numel()) if torch.is_tensor(params) else 0
+        if count < 1:
+            raise ValueError('adam_n: at least one parameter')
+        self._exit_vec(count, ('params', params), ('m', m), ('v', v), ('grad', grad))
+        if not 0 <= int(step) < 1 << 32:
+            raise ValueError('adam_n: the step lies in 0 .. 2^32 - 1')
+        self._check(self._lib.bq_adam_n(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), count, int(step), float(lr), float(b1),
+                                        float(b2), float(eps), self._stream()))
+
+    def exit_train_steps(self, params, m, v, bn_stats, acts, rows, labels, batch, step0, seed, lr, rate=None, b1=0.9, b2=0.999, eps=1e-7,
+                         grad=None, scratch=None):
+        """``S`` = ceil(len(rows) / batch) steps of ``exit_grad`` + ``adam_n`` over [P_ALL] back to back (``bq_exit_train_steps``), as
+        ``head_train_steps``: ``params``, ``m``, ``v`` change in place; -> losses float32 [S].  The same bits as the single calls."""
+        count = int(rows.numel()) if torch.is_tensor(rows) else 0
+        batch = int(batch)
+        if not 1 <= batch <= self.EXIT_MAX_ROWS or count < 1:
+            raise ValueError(f'exit_train_steps: 1 <= batch <= {self.EXIT_MAX_ROWS} and at least one row')
+        steps = -(-count // batch)
+        last_n = count - (steps - 1) * batch
+        self._exit_vec(self.ALL_PARAMS, ('params', params), ('m', m), ('v', v))
+        self._exit_batch('exit_train_steps', bn_stats, acts, rows, labels, count)
+        if grad is None:
+            grad = torch.empty(self.ALL_PARAMS, dtype=torch.float32, device=self.device)
+        self._exit_vec(self.ALL_PARAMS, ('grad', grad))
+        lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
+        rate, scratch = self._head_open('exit_train', self._lib.bq_exit_train_workspace_bytes(batch), rate, step0, steps, scratch,
+                                        f'exit_train_steps: {steps} learning rates, a rate in [0, 1) and steps below 2^32', len(lr) == steps)
+        losses = torch.empty(steps, dtype=torch.float32, device=self.device)
+        self._check(self._lib.bq_exit_train_steps(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), _ptr(bn_stats), _ptr(acts),
+                                                  int(acts.shape[0]), _ptr(rows), _ptr(labels), steps, batch, last_n, int(step0), int(seed),
+                                                  rate, lr.ctypes.data_as(C.POINTER(C.c_double)), float(b1), float(b2), float(eps),
+                                                  _ptr(losses), _ptr(scratch), scratch.numel(), self._stream()))
+        return losses
+
+    def exit_validate(self, params, bn_stats, acts, rows, labels, pass_, seed, rowloss=False, hit=False):
+        """``params`` [P_ALL] scored on the rows ``acts[rows]`` in inference mode: ``exit_features`` into scratch, then ``head_validate``
+        at rate 0 on those features with ``rows = arange(n)``, 1 <= n <= 256 -> ``head_validate``'s ``(stats, rowloss, hit)``."""
+        n = int(rows.numel()) if torch.is_tensor(rows) else -1
+        if not 1 <= n <= self.EXIT_MAX_ROWS:
+            raise ValueError(f'exit_validate: 1 <= n <= {self.EXIT_MAX_ROWS} rows, as an int64 tensor')
+        self._exit_vec(self.ALL_PARAMS, ('params', params))
+        feats = self._scratch('exit_validate', n * 2048 * 4).view(torch.float32)[:n * 2048].view(n, 2048)
+        self.exit_features(params[:self.EXIT_PARAMS], bn_stats, acts, rows, out=feats)
+        at = self._table('exit_validate', n, lambda: np.arange(n, dtype=np.int64))
+        return self.head_validate(params[self.EXIT_PARAMS:], feats, at, labels, pass_, seed, rate=0.0, rowloss=rowloss, hit=hit)
 
     def debug_activation(self, name, staged, shape_hwc, true_scale=True):
         """The named activation as fp32 [n,H,W,C]; with activation exponents (``act_exp``) the stored tensor times 2^k, i.e. the

@@ -93,14 +93,17 @@ def _first_records(slide, count, px):
     return t, np.asarray(loc, np.int64).reshape(-1, 2)
 
 
-def walk_features(eng, slides, max_tiles, on_batch, norm_fit=None, normalizer='reinhard_fast', keep_tiles=False, batch=None, prepare=None):
+def walk_features(eng, slides, max_tiles, on_batch, norm_fit=None, normalizer='reinhard_fast', keep_tiles=False, batch=None, prepare=None,
+                  stage=None):
     """``evaluate()``'s input stage over the first ``max_tiles`` tiles of every slide (0 / None: all): decode, stain normaliser,
     ``backbone_u8`` in batches of at most ``batch`` (the engine's ``max_batch`` when None or larger).  ``on_batch(f, g)`` gets each
     batch's features fp32 [b, 2048] and global tile indices int64 [b], both on the device, in slide order: a tile's index is its
     index in the UNCLIPPED slide list (``distributed.global_tile_offsets`` of the slides' tile counts), its Philox tile counter in
     ``evaluate()``.  ``prepare(tiles_u8, g)``, when given, gets each step's uint8 batch and its global indices on the device before
-    the stain normaliser and returns the tiles to go on with (``train.cache_features`` augments there).  -> ``(names, index, loc, tiles)``: per kept tile its slide's name, its record's index in the slide, its
-    location int64 [N, 2], and the tiles as read uint8 [N, px, px, 3] (None unless ``keep_tiles``)."""
+    the stain normaliser and returns the tiles to go on with (``train.cache_features`` augments there).  ``stage``, when given, is
+    called in the place of ``backbone_u8`` and ``on_batch`` gets what it returns (``train.cache_activations``: ``Engine.trunk``).
+    -> ``(names, index, loc, tiles)``: per kept tile its slide's name, its record's index in the slide, its location int64 [N, 2], and
+    the tiles as read uint8 [N, px, px, 3] (None unless ``keep_tiles``)."""
     import torch
     from . import distributed as D, stain
     stain.check(normalizer, norm_fit)
@@ -117,7 +120,7 @@ def walk_features(eng, slides, max_tiles, on_batch, norm_fit=None, normalizer='r
             if prepare is not None:
                 cur = prepare(cur, gi)
             cur = stain.normalise(eng, cur, normalizer, norm_fit)
-            on_batch(eng.backbone_u8(cur), gi)
+            on_batch((stage or eng.backbone_u8)(cur), gi)
 
     pend_t, pend_g, pending = [], [], 0
     for si, s in enumerate(slides):

@@ -22,8 +22,15 @@ every slide for that many steps.  All of it is off by default.
 
 Restated from memory, unpinned against Slideflow: ``TrainParams``' schedule constants and Keras's Adam defaults, the ``k-fold``
 split strategy (``kfold``), the directory names, the augmentation's probabilities and order (``augment.py``), the early-stopping
-rule and its defaults, and how balanced batches are drawn.  Out of scope: training any backbone layer, Slideflow's stain
-augmentation ``n``, TensorFlow checkpoints, multi-GPU training.
+rule and its defaults, and how balanced batches are drawn.
+
+Exit-flow fine-tuning (``--trainable exit``; DESIGN.md section 7 "Exit-flow fine-tuning"): ``cache_activations`` keeps every tile's
+``block13_out`` [10, 10, 1024] on the device (``Engine.trunk``) and each training moves Xception's block 14 together with the head
+(``Engine.exit_train_steps``), batch-norm statistics frozen -- a stated deviation from Slideflow, unpinned.  A fold then also writes
+``exit.npz``; ``exit_engine`` packs the result into an engine.
+
+Out of scope: training blocks 1-13, training-mode BN, Slideflow's stain augmentation ``n``, TensorFlow checkpoints, multi-GPU
+training.
 """
 import argparse
 import json
@@ -43,6 +50,19 @@ HEAD_PARAMS = sum(int(np.prod(s)) for _, s in HEAD_TENSORS)            # 3 149 8
 # the most rows of one gradient and of one validation check: copies of Engine.HEAD_TRAIN_MAX_ROWS / HEAD_VALIDATE_MAX_ROWS, as
 # HEAD_PARAMS is of Engine.HEAD_PARAMS (engine.py loads torch and the library, so neither module imports the other at load)
 HEAD_TRAIN_MAX_ROWS, HEAD_VALIDATE_MAX_ROWS = 1024, 4096
+
+# Exit-flow fine-tuning (DESIGN.md section 7 "Exit-flow fine-tuning"): the trainable exit vector's tensors in its order
+# (include/biscuit_hip.h: bq_exit_grad), the frozen statistics beside it, and copies of Engine.EXIT_PARAMS / EXIT_MAX_ROWS
+_B14 = (('block14_sepconv1', 1024, 1536), ('block14_sepconv2', 1536, 2048))
+EXIT_TENSORS = tuple(t for name, cin, cout in _B14 for t in ((f'{name}/depthwise_kernel', (3, 3, cin, 1)), (f'{name}/pointwise_kernel', (1, 1, cin, cout)),
+                                                              (f'{name}_bn/gamma', (cout,)), (f'{name}_bn/beta', (cout,))))
+EXIT_STATS = tuple(t for name, _, cout in _B14 for t in ((f'{name}_bn/moving_mean', (cout,)), (f'{name}_bn/moving_variance', (cout,))))
+EXIT_PARAMS = sum(int(np.prod(s)) for _, s in EXIT_TENSORS)            # 4 748 800
+EXIT_MAX_ROWS = 256
+ACT_SHAPE = (10, 10, 1024)                   # block13_out of one tile
+ACT_BYTES = 4 * int(np.prod(ACT_SHAPE))      # 409 600
+TRAINABLE = ('head', 'exit')
+EXIT_FILE = 'exit.npz'
 
 # Keras's Adam defaults and Slideflow's schedule form -- restated from memory, unpinned
 ADAM_BETA_1 = 0.9
@@ -84,6 +104,9 @@ class TrainParams:
     validation_dropout: bool = False         # True: a check draws the training masks; False: inference mode
     training_balance: str = 'none'           # or 'tile' (the same), 'slide', 'patient', 'category'
     steps_per_epoch_override: Optional[int] = None
+    # 'head': the three dense layers on cached features; 'exit': block 14 with them, on cached block13_out (an ActivationCache), under
+    # one Adam and one learning rate, batch-norm statistics frozen (DESIGN.md section 7 "Exit-flow fine-tuning"; unpinned)
+    trainable: str = 'head'
 
     @classmethod
     def nature2022(cls, **fields):
@@ -109,6 +132,10 @@ class TrainParams:
             raise ValueError(f'a check scores validation_steps x batch_size rows, at most {HEAD_VALIDATE_MAX_ROWS}')
         if self.steps_per_epoch_override is not None and int(self.steps_per_epoch_override) < 1:
             raise ValueError('steps_per_epoch_override is None or at least 1')
+        if self.trainable not in TRAINABLE:
+            raise ValueError(f'trainable is one of {TRAINABLE}, not {self.trainable!r}')
+        if self.trainable == 'exit' and (int(self.batch_size) > EXIT_MAX_ROWS or self.validation_dropout):
+            raise ValueError(f"trainable='exit': batch_size <= {EXIT_MAX_ROWS}, and validation in inference mode only")
         return self
 
     def learning_rate_at(self, step):
@@ -139,6 +166,51 @@ def unflatten_head(vec):
         out[name] = vec[at:at + n].reshape(shape).copy()
         at += n
     return out
+
+
+def flatten_exit(w):
+    """Block 14's eight trainable tensors of a weight dict -> one float32 vector [P_EXIT] in ``EXIT_TENSORS`` order (the Keras
+    shapes are the vector's own layout: D [3][3][C], P [Cin][Cout])."""
+    parts = []
+    for name, shape in EXIT_TENSORS:
+        a = np.asarray(w[name], np.float32)
+        if a.shape != shape:
+            raise ValueError(f'{name}: shape {a.shape}, not {shape}')
+        parts.append(a.reshape(-1))
+    return np.concatenate(parts)
+
+
+def unflatten_exit(vec):
+    """A vector [P_EXIT] -> ``{name: float32 array}`` of block 14's eight trainable tensors in their Keras shapes (copies)."""
+    vec = np.asarray(vec, np.float32).reshape(-1)
+    if vec.size != EXIT_PARAMS:
+        raise ValueError(f'the exit vector has {EXIT_PARAMS} parameters, not {vec.size}')
+    out, at = {}, 0
+    for name, shape in EXIT_TENSORS:
+        n = int(np.prod(shape))
+        out[name] = vec[at:at + n].reshape(shape).copy()
+        at += n
+    return out
+
+
+def exit_bn_stats(w):
+    """Block 14's frozen moving statistics of a weight dict -> float32 [7168]: mean1, variance1, mean2, variance2."""
+    parts = []
+    for name, shape in EXIT_STATS:
+        a = np.asarray(w[name], np.float32)
+        if a.shape != shape:
+            raise ValueError(f'{name}: shape {a.shape}, not {shape}')
+        parts.append(a)
+    return np.concatenate(parts)
+
+
+def save_exit(path, tensors):
+    np.savez(path, **{name: np.asarray(tensors[name], np.float32) for name, _ in EXIT_TENSORS})
+
+
+def load_exit(path):
+    with np.load(path) as z:
+        return {name: z[name] for name, _ in EXIT_TENSORS}
 
 
 def glorot_head(seed):
@@ -265,25 +337,137 @@ def cache_features(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_f
     return FeatureCache(feats.contiguous(), np.array([index[n] for n in names], np.int64), loc, order, stacked, letters, int(seed) if V else 0)
 
 
-def cached_features(engine, slides, path, *, augment=None, views=None, seed=0, **kw):
+def cached_features(engine, slides, path, *, augment=None, views=None, seed=0, activations=False, **kw):
     """``--cache FILE``: ``cache_features(engine, slides, augment=..., views=..., seed=..., **kw)``, kept in ``path`` (.npz; None: not
     kept) -- loaded from there when the file exists, with its views, otherwise computed and saved.  SystemExit for a file that holds
-    other slides or was made with another augmentation, number of views or seed."""
+    other slides or was made with another augmentation, number of views or seed.  ``activations`` (``--trainable exit``): an
+    ``ActivationCache`` through ``cache_activations`` instead, and SystemExit for a file without activations."""
     from . import augment as A
     letters = A.parse(augment)
     n_views = view_count(letters, views)
     if not path or not os.path.exists(path):
-        cache = cache_features(engine, slides, augment=letters, views=n_views or None, seed=seed, **kw)
+        try:
+            cache = (cache_activations if activations else cache_features)(engine, slides, augment=letters, views=n_views or None, seed=seed, **kw)
+        except ValueError as e:
+            if not activations:
+                raise
+            raise SystemExit(str(e)) from None
         if path:
             cache.save(path)
         return cache
-    cache = FeatureCache.load(path, engine.device)
+    try:
+        cache = (ActivationCache if activations else FeatureCache).load(path, engine.device)
+    except ValueError as e:
+        raise SystemExit(f'--cache {e}') from None
     if cache.slides != [s.name for s in slides] or len(cache) != sum(int(s.n_tiles) for s in slides):
         raise SystemExit(f'--cache {path}: holds other slides than the ones given')
     if (cache.augment, cache.n_views()) != (letters, n_views) or (letters and cache.augment_seed != int(seed)):
         raise SystemExit(f'--cache {path}: made with augment {cache.augment!r}, {cache.n_views()} view(s), seed {cache.augment_seed}, '
                          f'not with {letters!r}, {n_views}, {int(seed)}')
     return cache
+
+
+# ------------------------------------------------------------------------------------------------------------ activation cache
+@dataclass
+class ActivationCache(FeatureCache):
+    """A ``FeatureCache`` that also holds what block 14 reads: ``acts`` float32 [N, 10, 10, 1024] (``block13_out`` per tile, on the
+    device; a host array once loaded, until ``to``) and, with augmentation, ``act_views`` float32 [V, N, 10, 10, 1024] beside
+    ``views``.  ``feats`` / ``views`` are ``Engine.exit_features`` of them under the imported block 14, so everything that reads a
+    ``FeatureCache`` works on it unchanged; ``trainable='exit'`` trains on ``acts``."""
+    acts: object = None
+    act_views: object = None
+
+    def to(self, device):
+        import torch
+        on = lambda a: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(device).contiguous()
+        FeatureCache.to(self, device)
+        self.acts = on(self.acts)
+        if self.act_views is not None:
+            self.act_views = on(self.act_views)
+        return self
+
+    def save(self, path):
+        host = lambda a: (a.cpu().numpy() if hasattr(a, 'cpu') else np.asarray(a)).astype(np.float32)
+        extra = {} if self.views is None else {'views': host(self.views), 'act_views': host(self.act_views), 'augment': np.array(self.augment),
+                                               'augment_seed': np.array(int(self.augment_seed), np.int64)}
+        np.savez(path, feats=host(self.feats), acts=host(self.acts), slide_idx=self.slide_idx, loc=self.loc,
+                 slides=np.array(self.slides, dtype=str), **extra)
+
+    @staticmethod
+    def load(path, device=None):
+        with np.load(path) as z:
+            if 'acts' not in z.files:
+                raise ValueError(f'{path}: a feature cache, not an activation cache (no acts)')
+            c = ActivationCache(z['feats'].astype(np.float32), z['slide_idx'].astype(np.int64), z['loc'].astype(np.int64),
+                                [str(s) for s in z['slides']], acts=z['acts'].astype(np.float32))
+            if 'views' in z.files:
+                c.views, c.act_views = z['views'].astype(np.float32), z['act_views'].astype(np.float32)
+                c.augment, c.augment_seed = str(z['augment']), int(z['augment_seed'])
+        return c.to(device) if device is not None else c
+
+
+def activation_cache_bytes(n_tiles, views=0):
+    """The device bytes of an ``ActivationCache``'s activations: ``n_tiles x 409 600 x (1 + views)``."""
+    return int(n_tiles) * ACT_BYTES * (1 + int(views))
+
+
+def check_activation_memory(n_tiles, views, free_bytes):
+    """ValueError naming both figures when the activations of ``n_tiles`` tiles and ``views`` views do not fit ``free_bytes``."""
+    need = activation_cache_bytes(n_tiles, views)
+    if need > int(free_bytes):
+        raise ValueError(f'cache_activations: {int(n_tiles)} tiles x {ACT_BYTES} bytes x (1 + {int(views)} views) = {need} bytes of '
+                         f'activations, but the device has {int(free_bytes)} bytes free (a host-resident cache is out of scope: fewer '
+                         'tiles, fewer views, or --trainable head)')
+    return need
+
+
+def cache_activations(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_fit=None, batch=256, augment=None, views=None, seed=0):
+    """``cache_features``' walk with ``Engine.trunk`` in the place of ``backbone_u8`` -> ``ActivationCache``: every tile's
+    ``block13_out`` on the engine's device (and V augmented views of it, drawn as ``cache_features`` draws them), and the features
+    ``Engine.exit_features`` gives them under the engine's imported block 14.  Before anything is read the activations' bytes are
+    compared with the device's free memory (``check_activation_memory``)."""
+    import torch
+    from . import augment as A
+    from .featuremap import walk_features
+    eng = engine_or_pool.engines[0] if hasattr(engine_or_pool, 'engines') else engine_or_pool
+    letters = A.parse(augment)
+    V = view_count(letters, views)
+    if letters and V < 1:
+        raise ValueError('views must be at least 1')
+    order = [s.name for s in slides]
+    index = {s: i for i, s in enumerate(order)}
+    if len(index) != len(order):
+        raise ValueError('slide names must be unique')
+    n_total = sum(int(s.n_tiles) for s in slides)
+    check_activation_memory(n_total, V, torch.cuda.mem_get_info(eng.device)[0])
+    acts = torch.empty((n_total,) + ACT_SHAPE, dtype=torch.float32, device=eng.device)
+    act_views = torch.empty((V, n_total) + ACT_SHAPE, dtype=torch.float32, device=eng.device) if V else None
+    prepare, statuses = None, []
+    if V:
+        from . import stain
+        tables = [torch.from_numpy(A.draw(n_total, letters, seed, v)).to(eng.device) for v in range(V)]
+
+        def prepare(tiles, g):
+            for v in range(V):
+                aug, status = eng.augment(tiles, tables[v].index_select(0, g).contiguous())
+                act_views[v].index_copy_(0, g, eng.trunk(stain.normalise(eng, aug, normalizer, norm_fit)))
+                statuses.append(status)
+            return tiles
+    names, _, loc, _ = walk_features(eng, slides, 0, lambda a, g: acts.index_copy_(0, g, a), norm_fit, normalizer, False, batch,
+                                     prepare=prepare, stage=eng.trunk)
+    if statuses and bool(torch.cat(statuses).ne(0).any()):
+        from .engine import BiscuitHipError
+        raise BiscuitHipError('cache_activations: the augmenter reported a tile outside the JPEG round trip\'s exact range')
+    e = torch.from_numpy(flatten_exit(eng.weights)).to(eng.device)
+    stats = torch.from_numpy(exit_bn_stats(eng.weights)).to(eng.device)
+    every = torch.arange(n_total, dtype=torch.int64, device=eng.device)
+    feats = eng.exit_features_all(e, stats, acts, every) if n_total else torch.zeros((0, 2048), dtype=torch.float32, device=eng.device)
+    stacked = None
+    if V:
+        stacked = torch.stack([eng.exit_features_all(e, stats, act_views[v], every) for v in range(V)]).contiguous() if n_total else \
+            torch.zeros((V, 0, 2048), dtype=torch.float32, device=eng.device)
+    return ActivationCache(feats.contiguous(), np.array([index[n] for n in names], np.int64), loc, order, stacked, letters,
+                           int(seed) if V else 0, acts=acts, act_views=act_views)
 
 
 # ------------------------------------------------------------------------------------------------------------ the schedule
@@ -389,6 +573,7 @@ class FitResult:
     early_stop_batch: Optional[int]
     steps: int
     epochs: int = 1
+    exit: Optional[dict] = None              # trainable='exit': block 14's eight trained tensors
 
 
 # ------------------------------------------------------------------------------------------------------------ training
@@ -426,7 +611,14 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
     on the unaugmented features, at rate ``dropout`` if ``validation_dropout`` else 0, with pass = the global step; the host reads
     its 16 bytes, the one synchronisation per check.  The checks change nothing in the training; with ``early_stop`` their accuracy
     or loss feeds ``EarlyStop``, and the training ends where it says stop.  A training or validation loss that is not finite raises
-    ``BiscuitHipError``."""
+    ``BiscuitHipError``.
+
+    With ``params.trainable == 'exit'`` block 14 trains with the head under the same schedule and one Adam: ``cache`` must be an
+    ``ActivationCache`` (``cache_activations``), a segment is one ``Engine.exit_train_steps`` call on ``cache.acts`` (``act_views``
+    as [V N, 10, 10, 1024] when there are views), and a check goes through ``Engine.exit_validate`` on the unaugmented activations
+    at rate 0, in calls of at most 256 rows whose sums are added in order on the device, read once.  Block 14 starts from the
+    engine's imported tensors, or from a dict ``init`` that also carries them (``EXIT_TENSORS``' names, beside the head's); its
+    moving statistics are the engine's and stay.  The result's ``exit`` holds the trained tensors (None for ``'head'``)."""
     import torch
     from .engine import BiscuitHipError
     p = (params or TrainParams()).validate()
@@ -456,10 +648,20 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
         stopper, val_rate = EarlyStop.of(p), float(p.dropout) if p.validation_dropout else 0.0
     if p.training_balance not in ('none', 'tile'):
         slide_idx = np.asarray(cache.slide_idx[rows] if slide_idx is None else slide_idx, np.int64).reshape(-1)
-    w = torch.from_numpy(flatten_head(start)).to(dev)
+    exit_mode = p.trainable == 'exit'
+    if exit_mode:
+        # block 14 starts from `init` where it names its tensors, else from the imported model; its statistics are the engine's, frozen
+        if not isinstance(cache, ActivationCache) or cache.acts is None:
+            raise ValueError("trainable='exit' trains on an ActivationCache (cache_activations), not on a FeatureCache")
+        exit_start = init if isinstance(init, dict) and EXIT_TENSORS[0][0] in init else engine.weights
+        bn_stats = torch.from_numpy(exit_bn_stats(engine.weights)).to(dev)
+        w = torch.from_numpy(np.concatenate([flatten_exit(exit_start), flatten_head(start)])).to(dev)
+        feats = cache.act_views.reshape((-1,) + ACT_SHAPE) if cache.n_views() else cache.acts
+    else:
+        w = torch.from_numpy(flatten_head(start)).to(dev)
+        feats = cache.views.reshape(-1, cache.views.shape[-1]) if cache.n_views() else cache.feats
     m, v, g = torch.zeros_like(w), torch.zeros_like(w), torch.empty_like(w)
     losses, checks, step, stopped, state = [], [], 0, None, {}
-    feats = cache.views.reshape(-1, cache.views.shape[-1]) if cache.n_views() else cache.feats
     for epoch in range(int(max(p.epochs))):
         at, y = _plan_epoch(p, cache, rows, labels, slide_idx, patients, seed, epoch, state)
         steps = -(-len(at) // B)
@@ -468,13 +670,23 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
         for a in range(0, steps, seg):
             b = min(a + seg, steps)
             lr = [p.learning_rate_at(step + i) for i in range(b - a)]
-            losses.append(engine.head_train_steps(w, m, v, feats, at[a * B:b * B], y[a * B:b * B], B, step, seed, lr, rate=p.dropout,
-                                                  b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g))
+            if exit_mode:
+                losses.append(engine.exit_train_steps(w, m, v, bn_stats, feats, at[a * B:b * B], y[a * B:b * B], B, step, seed, lr,
+                                                      rate=p.dropout, b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g))
+            else:
+                losses.append(engine.head_train_steps(w, m, v, feats, at[a * B:b * B], y[a * B:b * B], B, step, seed, lr, rate=p.dropout,
+                                                      b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g))
             step += b - a
             if not validating:
                 continue
             c0 = len(checks) * n_val % len(val_rows)
-            stats, _, _ = engine.head_validate(w, cache.feats, val_at[c0:c0 + n_val], val_y[c0:c0 + n_val], step, seed, rate=val_rate)
+            if exit_mode:            # calls of up to 256 rows, their sums added in order on the device
+                stats = torch.zeros(2, dtype=torch.float64, device=dev)
+                for q in range(c0, c0 + n_val, EXIT_MAX_ROWS):
+                    e = min(q + EXIT_MAX_ROWS, c0 + n_val)
+                    stats += engine.exit_validate(w, bn_stats, cache.acts, val_at[q:e], val_y[q:e], step, seed)[0]
+            else:
+                stats, _, _ = engine.head_validate(w, cache.feats, val_at[c0:c0 + n_val], val_y[c0:c0 + n_val], step, seed, rate=val_rate)
             stats = stats.cpu().numpy()
             val_loss, val_acc = float(stats[0]) / n_val, float(stats[1]) / n_val
             if not np.isfinite(val_loss):
@@ -491,6 +703,9 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
     if not np.isfinite(losses).all():
         raise BiscuitHipError(f'train_head: the loss of step {int(np.flatnonzero(~np.isfinite(losses))[0])} is not finite '
                               '(a feature that is not finite, or a diverged run)')
+    if exit_mode:
+        host = w.cpu().numpy()
+        return FitResult(unflatten_head(host[EXIT_PARAMS:]), losses, checks, stopped, step, int(max(p.epochs)), unflatten_exit(host[:EXIT_PARAMS]))
     return FitResult(unflatten_head(w.cpu().numpy()), losses, checks, stopped, step, int(max(p.epochs)))
 
 
@@ -574,8 +789,44 @@ class HeadTrainer:
 
     def __call__(self, train_rows, val_rows, seed):
         fit = self.fit(train_rows, val_rows if (self.params or TrainParams()).early_stop else None, seed)
-        table = predict(self.engine, self.cache, val_rows, fit.head, self.mc_n, seed, y_true=self.y_slide, outcome=self.outcome)
+        cache = self.cache if fit.exit is None else exit_feature_cache(self.engine, self.cache, fit.exit, val_rows)
+        table = predict(self.engine, cache, val_rows, fit.head, self.mc_n, seed, y_true=self.y_slide, outcome=self.outcome)
         return table, fit.head, fit
+
+
+def exit_feature_cache(engine, cache, exit_tensors, rows):
+    """A ``FeatureCache`` over ``cache``'s tiles whose features at ``rows`` are ``Engine.exit_features`` of the cached activations
+    under ``exit_tensors`` (a trained block 14; its statistics the engine's): what ``predict`` reads after ``trainable='exit'``.
+    The other rows keep the imported block 14's features."""
+    import torch
+    rows = torch.from_numpy(np.asarray(rows, np.int64).reshape(-1)).to(engine.device)
+    feats = cache.feats.clone()
+    if len(rows):
+        e = torch.from_numpy(flatten_exit(exit_tensors)).to(engine.device)
+        stats = torch.from_numpy(exit_bn_stats(engine.weights)).to(engine.device)
+        feats.index_copy_(0, rows, engine.exit_features_all(e, stats, cache.acts, rows))
+    return FeatureCache(feats, cache.slide_idx, cache.loc, cache.slides)
+
+
+def exit_engine(engine, exit_tensors, head, tiles=None, headroom_min=1.0):
+    """A fresh engine of ``engine``'s configuration whose block 14 is ``exit_tensors`` and whose head is ``head`` (through
+    ``weights.pack_blob``, like ``head_engine``), with ``engine``'s activation exponents reused.  The exponents were calibrated on the
+    imported block 14: with ``tiles`` (uint8 [n, 299, 299, 3] on the device) one ``f16_headroom`` check runs on them, and
+    ``F16RangeError`` says so when the trained block 14 saturates f16 or leaves less than ``headroom_min`` x of its range."""
+    from .engine import Engine, F16RangeError
+    w = {**engine.weights, **{name: np.asarray(exit_tensors[name], np.float32) for name, _ in EXIT_TENSORS},
+         **{name: np.asarray(head[name], np.float32) for name, _ in HEAD_TENSORS}}
+    eng = Engine(w, hp=engine.hp, dtype=engine.dtype, max_batch=engine.max_batch, max_mc=engine.max_mc, device=engine.device.index,
+                 act_exp=engine.act_exp)
+    if tiles is not None and len(tiles):
+        room = eng.f16_headroom(tiles)
+        if any(room['saturated'].values()) or room['headroom'] < float(headroom_min):
+            eng.close()
+            worst = max(room['max_abs'], key=room['max_abs'].get)
+            raise F16RangeError(f'exit_engine: the trained block 14 has left the calibrated f16 range ({worst}: max |activation| as stored '
+                                f'{room["max_abs"][worst]:.6g}, headroom {room["headroom"]:.3g}); calibrate again on the trained weights '
+                                '(Engine.calibrate), or use dtype bf16 / f32')
+    return eng
 
 
 # ------------------------------------------------------------------------------------------------------------ cross-validation
@@ -656,6 +907,8 @@ def train_full(cache, slide_labels, out, label, *, stop_batch, trainer, seed=0):
     d = os.path.join(out, f'{label}_FULL')
     os.makedirs(d, exist_ok=True)
     save_head(os.path.join(d, HEAD_FILE), fit.head)
+    if fit.exit is not None:
+        save_exit(os.path.join(d, EXIT_FILE), fit.exit)
     with open(os.path.join(d, MANIFEST_FILE), 'w') as f:
         json.dump({'training': train_s, 'validation': []}, f)
     write_results_log(os.path.join(d, RESULTS_FILE), f'{label}_FULL', fit, fit.epochs)
@@ -690,6 +943,8 @@ def train_cv(cache, slide_labels, out, label, k, trainer, *, patients=None, seed
         predictions.write_tile_table(table, d, predictions.VAL_NAME, outcome)
         if head is not None:
             save_head(os.path.join(d, HEAD_FILE), head)
+        if fit and getattr(fit[0], 'exit', None) is not None:
+            save_exit(os.path.join(d, EXIT_FILE), fit[0].exit)
         if fit:
             write_results_log(os.path.join(d, RESULTS_FILE), os.path.basename(d), fit[0], fit[0].epochs)
         with open(os.path.join(d, MANIFEST_FILE), 'w') as f:
@@ -827,6 +1082,9 @@ def main(argv=None):
                     help="training batches balanced by 'category' (the paper's models), 'patient' or 'slide'; default: none")
     ap.add_argument('--validate-on-batch', type=int, default=32, metavar='N', help='with --early-stop: a validation check every N steps')
     ap.add_argument('--validation-steps', type=int, default=32, metavar='N', help='with --early-stop: batches of validation tiles per check')
+    ap.add_argument('--trainable', default='head', choices=list(TRAINABLE), help="'head' (default): the three dense layers on cached "
+                    "features; 'exit': Xception's block 14 with them, on cached block13_out (409 600 bytes per tile and view on the device), "
+                    'batch-norm statistics frozen; each fold then also writes exit.npz')
     ap.add_argument('--full', action='store_true', help='after the cross-validation, train the model on every slide for the number of '
                     'steps at which the outer folds stopped early (needs --early-stop) -> OUT/LABEL_FULL')
     args = ap.parse_args(argv)
@@ -876,9 +1134,10 @@ def main(argv=None):
     eng = Engine(w, hp=hp, dtype=args.dtype, max_batch=256, max_mc=mc_n, act_exp=act_exp)
     try:
         cache = cached_features(eng, slides, args.cache, normalizer=hp.normalizer, norm_fit=norm_fit, augment=letters, views=n_views or None,
-                                seed=args.seed)
+                                seed=args.seed, activations=args.trainable == 'exit')
         try:
             params = TrainParams(epochs=[args.epochs], dropout=hp.dropout, augment=letters, early_stop=bool(args.early_stop),
+                                 trainable=args.trainable,
                                  early_stop_method=args.early_stop or 'accuracy', training_balance=args.balance,
                                  validate_on_batch=args.validate_on_batch, validation_steps=args.validation_steps).validate()
             trainer = HeadTrainer(eng, cache, labels, params=params, init=args.init, mc_n=mc_n, outcome=args.outcome, patients=patients)

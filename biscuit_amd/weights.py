@@ -325,6 +325,7 @@ def tensor_plan():
 
 
 FEATURE_TENSOR = 'block14_sepconv2'      # what the global average pool reads
+TRUNK_TENSOR = 'block13_out'             # what exit-flow fine-tuning caches per tile (train.cache_activations)
 
 
 def tensor_taps():
@@ -463,6 +464,9 @@ def pack_blob(w, dtype='bf16', act_exp=None):
             add(name + '/wp16', to_bits(pack_fragments16(w[name + '/pointwise_kernel'].reshape(cin, cout), cp, npad)))
         s, b = fold(name)
         add_affine(name, s, b, npad)
+    if act_exp.get(TRUNK_TENSOR, 0):
+        # bq_trunk_u8 writes block13_out at true scale: stored * 2^k (c->trunk_mul)
+        add('act/trunk_mul', np.array([2.0 ** act_exp[TRUNK_TENSOR]], np.float32))
     if act_exp.get(FEATURE_TENSOR, 0):
         # the pooled features return to true scale in the pooling epilogue: means * 2^k (c->feat_mul)
         add('act/feat_mul', np.array([2.0 ** act_exp[FEATURE_TENSOR]], np.float32))

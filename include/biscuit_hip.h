@@ -709,6 +709,48 @@ int bq_head_train_steps(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, fl
                         double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws, size_t ws_bytes,
                         bq_stream_t stream);
 
+/* Exit-flow fine-tuning (kernels_train.hip; DESIGN.md section 7 "Exit-flow fine-tuning"): Xception's block 14 trained together with
+ * the head, on a cache of block13_out.
+ *
+ * bq_trunk_u8: bq_backbone_u8's launches, by the same routes and under the same size limits, up to block13_out -> d_out_f32
+ * [n][10][10][1024], the network's value (the blob's activation exponent of the tensor removed: a power of two, exact).  d_ws:
+ * bq_workspace_bytes(ctx, n, 1).
+ *
+ * The trainable exit vector, float32 [P_EXIT], P_EXIT = 4 748 800, in the order D1 [3][3][1024], P1 [1024][1536], gamma1 [1536],
+ * beta1 [1536], D2 [3][3][1536], P2 [1536][2048], gamma2 [2048], beta2 [2048] (block14_sepconv{1,2}'s depthwise and pointwise
+ * kernels and their BN's gamma and beta); the head's P follow in their order above: P_ALL = 7 898 626.  d_bn_stats, float32 [7168],
+ * only read: moving_mean1 [1536], moving_variance1 [1536], moving_mean2 [2048], moving_variance2 [2048] -- the statistics stay
+ * frozen.  With a = gamma / sqrt(var + 1e-3), b = beta - a mean, dw the 3 x 3 depthwise convolution (zero padding 1, stride 1):
+ *     u1 = dw(x, D1), z1 = u1 P1, h1 = relu(a1 z1 + b1), u2 = dw(h1, D2), z2 = u2 P2, h2 = relu(a2 z2 + b2), f = mean_100 h2
+ * for each row x = d_acts[d_rows[i]] (d_acts float32 [n_act][10][10][1024], offsets in 64 bits), 1 <= n <= 256.
+ *
+ * bq_exit_features: d_exit_params [P_EXIT] -> d_feat2048 [n][2048].  A row of f depends on its tile and the parameters only, not
+ * on n or on its place in d_rows.
+ * bq_exit_grad: d_params [P_ALL] -> d_grad [P_ALL], d_loss [1]: the gradient of bq_head_grad's loss on f (the same kernels, the
+ * Philox counters d_rows[i], layers 0 .. 2: the last P entries and the loss are bit for bit bq_head_grad's on bq_exit_features'
+ * output), carried back through block 14; ReLU's derivative is 0 at 0.  A row index outside 0 .. n_act - 1 (never read), an
+ * activation that is not finite or a label above 1 gives a NaN loss.  The pointwise products run on the exact f32-input MFMA; every
+ * sum has a fixed order and there are no floating-point atomics: the same bits every call.
+ * bq_adam_n: bq_head_adam's pass over `count` elements.
+ * bq_exit_train_steps: bq_head_train_steps' loop of bq_exit_grad + one Adam over P_ALL; the same bits as the single calls.
+ *
+ * d_ws: bq_exit_features_workspace_bytes(n) / bq_exit_train_workspace_bytes(n) bytes (0 for an n the calls refuse), under the rules
+ * of the head's training workspace.  All are one linear chain of launches on `stream`: nothing is captured, allocated or waited for. */
+int bq_trunk_u8(bq_ctx* ctx, const uint8_t* d_tiles_u8, int n, float* d_out_f32, void* d_ws, size_t ws_bytes, bq_stream_t stream);
+size_t bq_exit_features_workspace_bytes(int n);
+size_t bq_exit_train_workspace_bytes(int n);
+int bq_exit_features(bq_ctx* ctx, const float* d_exit_params, const float* d_bn_stats, const float* d_acts, int64_t n_act,
+                     const int64_t* d_rows, int n, float* d_feat2048, void* d_ws, size_t ws_bytes, bq_stream_t stream);
+int bq_exit_grad(bq_ctx* ctx, const float* d_params, const float* d_bn_stats, const float* d_acts, int64_t n_act, const int64_t* d_rows,
+                 const uint8_t* d_labels, int n, int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, void* d_ws,
+                 size_t ws_bytes, bq_stream_t stream);
+int bq_adam_n(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, const float* d_grad, int64_t count, int64_t step, double lr, double b1,
+              double b2, double eps, bq_stream_t stream);
+int bq_exit_train_steps(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, float* d_grad, const float* d_bn_stats, const float* d_acts,
+                        int64_t n_act, const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n, int64_t step0,
+                        uint64_t seed, double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws,
+                        size_t ws_bytes, bq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,8 +151,75 @@ def bench_cv(eng, n_slides, n_tiles, mc_n):
             'thresholds_wall_s': round(t_th, 2), 'thresholds': th}
 
 
+# the share of these figures that ``--exit`` reports (profiles/train_exit.txt): the MI355X's f32 matrix peak and HBM bandwidth
+F32_MATRIX_PEAK, HBM_BYTES_PER_S = 157.3e12, 8.0e12
+EXIT_GEMMS = ('pw1', 'pw2', 'dp1', 'du1', 'dp2', 'du2', 'dfeat')
+EXIT_DEPTHWISE = ('dw1', 'dw2', 'dd1', 'dd2', 'dh1')
+
+
+def bench_exit_steps(eng, steps, batch, tiles=512):
+    """One exit-flow training step (``Engine.exit_train_steps``: block 14 and the head under one Adam) at ``batch``: wall time per
+    step, the library's time per launch class, and from each class's own flop and byte counts the GEMMs' share of the f32 matrix
+    peak and the depthwise kernels' share of the HBM bandwidth."""
+    dev = eng.device
+    rng = np.random.default_rng(1)
+    acts = torch.rand((tiles,) + eng.EXIT_ACT_SHAPE, dtype=torch.float32, device=dev)
+    rows = torch.from_numpy(rng.integers(0, tiles, steps * batch)).to(dev)
+    labels = torch.from_numpy(rng.integers(0, 2, steps * batch).astype(np.uint8)).to(dev)
+    w = torch.from_numpy(np.concatenate([T.flatten_exit(eng.weights), T.flatten_head(T.glorot_head(1))])).to(dev)
+    stats = torch.from_numpy(T.exit_bn_stats(eng.weights)).to(dev)
+    m, v = torch.zeros_like(w), torch.zeros_like(w)
+    lr = [1e-4] * steps
+    eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, 0, 1, lr)
+    torch.cuda.synchronize(dev)
+    walls = []
+    for r in range(3):
+        t0 = time.perf_counter()
+        eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, (r + 1) * steps, 1, lr)
+        torch.cuda.synchronize(dev)
+        walls.append((time.perf_counter() - t0) / steps * 1e6)
+    eng.profile_enable(True)
+    eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, 4 * steps, 1, lr)
+    torch.cuda.synchronize(dev)
+    prof = {p.name: p for p in eng.profile_read() if p.name.startswith(('exit_train_', 'head_train_'))}
+    eng.profile_enable(False)
+    us = {name: round(p.ms / max(p.launches, 1) * 1e3, 2) for name, p in prof.items()}
+    per_s = lambda p: p.ms / max(p.launches, 1) * 1e-3
+    peak = {k: round(prof['exit_train_' + k].flops / per_s(prof['exit_train_' + k]) / F32_MATRIX_PEAK, 3) for k in EXIT_GEMMS}
+    hbm = {k: round(prof['exit_train_' + k].bytes / per_s(prof['exit_train_' + k]) / HBM_BYTES_PER_S, 3) for k in EXIT_DEPTHWISE}
+    return {'measure': 'exit_train_step', 'batch': batch, 'steps': steps, 'us_per_step_wall_median': round(float(np.median(walls)), 1),
+            'us_per_step_wall_runs': [round(x, 1) for x in walls], 'us_per_launch_by_class': us, 'us_launches_total': round(sum(us.values()), 1),
+            'gemm_share_of_f32_matrix_peak': peak, 'depthwise_share_of_hbm_bandwidth': hbm,
+            'workspace_MB': round(eng._lib.bq_exit_train_workspace_bytes(batch) / 1e6, 1)}
+
+
+def bench_exit_cv(eng, n_slides, n_tiles, mc_n, batch):
+    """Wall time of a toy ``train_nested_cv`` with ``trainable='exit'`` over a synthetic activation cache (3 x (1 + 2) trainings)."""
+    rng = np.random.default_rng(3)
+    slides = [f's{i:03d}' for i in range(n_slides)]
+    labels = {s: i % 2 for i, s in enumerate(slides)}
+    sidx = np.repeat(np.arange(n_slides), n_tiles).astype(np.int64)
+    acts = torch.rand((len(sidx),) + eng.EXIT_ACT_SHAPE, dtype=torch.float32, device=eng.device)
+    acts[torch.from_numpy(sidx % 2 == 1).to(eng.device)] += 0.05
+    loc = np.stack([np.arange(len(sidx)), np.zeros(len(sidx), np.int64)], 1).astype(np.int64)
+    e, stats = (torch.from_numpy(a).to(eng.device) for a in (T.flatten_exit(eng.weights), T.exit_bn_stats(eng.weights)))
+    feats = eng.exit_features_all(e, stats, acts, torch.arange(len(sidx), device=eng.device))
+    cache = T.ActivationCache(feats, sidx, loc, slides, acts=acts)
+    trainer = T.HeadTrainer(eng, cache, labels, params=T.TrainParams(batch_size=batch, trainable='exit'), init='glorot', mc_n=mc_n)
+    with tempfile.TemporaryDirectory() as out:
+        t0 = time.perf_counter()
+        dirs = T.train_nested_cv(cache, labels, out, 'EXP', trainer, outer_k=3, inner_k=2, seed=1)
+        torch.cuda.synchronize(eng.device)
+        wall = time.perf_counter() - t0
+    return {'measure': 'exit_nested_cv', 'slides': n_slides, 'tiles_per_slide': n_tiles, 'trainings': len(dirs), 'mc_n': mc_n, 'batch': batch,
+            'steps_total': int(sum(len(x) for x in trainer.losses)), 'train_and_tables_wall_s': round(wall, 2),
+            'activation_cache_MB': round(T.activation_cache_bytes(len(sidx)) / 1e6, 1)}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    ap.add_argument('--exit', action='store_true', help="measure exit-flow fine-tuning (trainable='exit') instead: one step at --batch, "
+                    'and a toy nested CV (profiles/train_exit.txt)')
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--batch', type=int, default=128)
     ap.add_argument('--cache-slides', type=int, default=8)
@@ -163,6 +230,11 @@ def main(argv=None):
     args = ap.parse_args(argv)
     eng = Engine(synthetic_weights(1), dtype='f16', max_batch=256, max_mc=args.mc)
     try:
+        if args.exit:
+            print(json.dumps(bench_exit_steps(eng, min(args.steps, 20), args.batch)), flush=True)
+            if args.cv_slides > 0:
+                print(json.dumps(bench_exit_cv(eng, min(args.cv_slides, 12), min(args.cv_tiles, 64), args.mc, args.batch)), flush=True)
+            return
         print(json.dumps(bench_steps(eng, args.steps, args.batch)), flush=True)
         if args.batch * 32 <= Engine.HEAD_VALIDATE_MAX_ROWS:
             print(json.dumps(bench_validate(eng, args.batch)), flush=True)
