@@ -25,7 +25,14 @@ class BqProfEntry(C.Structure):
                 ('flops', C.c_double), ('bytes', C.c_double)]
 
 
-_vp, _i, _i64, _u64, _sz, _f = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_size_t, C.c_float
+class BqActCache(C.Structure):
+    """``bq_act_cache``: where and in which form an activation cache lies (``type``: a BQ_DTYPE_* value, ``where``: BQ_ACT_*)."""
+    _fields_ = [('p', C.c_void_p), ('n_rows', C.c_int64), ('type', C.c_int), ('mul', C.c_float), ('where', C.c_int)]
+
+
+BQ_ACT_DEVICE, BQ_ACT_HOST = 0, 1
+
+_vp, _i, _i64, _u64, _sz, _f =C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_size_t, C.c_float
 
 # name -> (restype, argtypes): exactly the symbols include/biscuit_hip.h declares
 ABI = {
@@ -119,6 +126,14 @@ ABI = {
     'bq_adam_n': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     'bq_exit_train_steps': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i64, _u64, C.c_double,
                                  C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    'bq_trunk_u8_packed': (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_float), _vp, _sz, _vp]),
+    'bq_host_device_pointer': (_i, [_vp, C.POINTER(_vp)]),
+    'bq_exit_features_staged_workspace_bytes': (_sz, [_i, _i]),
+    'bq_exit_staged_workspace_bytes': (_sz, [_i, _i]),
+    'bq_exit_features_c': (_i, [_vp, _vp, _vp, C.POINTER(BqActCache), _vp, _i, _vp, _vp, _sz, _vp]),
+    'bq_exit_grad_c': (_i, [_vp, _vp, _vp, C.POINTER(BqActCache), _vp, _vp, _i, _i64, _u64, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    'bq_exit_train_steps_c': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BqActCache), _vp, _vp, _i, _i, _i, _i64, _u64, C.c_double,
+                                   C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -257,6 +257,7 @@ std::string route_text(const Route& r) {
 struct Tap {
     const char* want = nullptr;   // requested activation name (null: none)
     float* out = nullptr;
+    void* out16 = nullptr;        // in the place of out: the tensor as it is stored, 16-bit and compact (bq_trunk_u8_packed)
     size_t out_elems = 0;
     int64_t written = -1;
 };
@@ -287,7 +288,7 @@ int tap_nhwc(const Walk& w, const char* name, const void* buf, int H, int C, int
     const long long rows = (long long)w.n * H * H;
     if (w.plan) { t->written = 0; return 1; }
     if ((size_t)(rows * C) > t->out_elems) return fail(w.c, BQ_ERR_ARG, "debug output too small");
-    const int e = launch_to_f32_nhwc(buf, rows, C, ld, t->out, w.c->cfg.dtype, w.s);
+    const int e = t->out16 ? launch_copy16_nhwc(buf, rows, C, ld, t->out16, w.s) : launch_to_f32_nhwc(buf, rows, C, ld, t->out, w.c->cfg.dtype, w.s);
     if (e) return fail(w.c, BQ_ERR_HIP, "debug copy failed");
     t->written = rows * C;
     return 1;
@@ -913,13 +914,16 @@ int bq_backbone_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_feat, void
 
 // bq_backbone_u8's walk up to block13_out -- the same launches by the same routes: the tap's name is no layer's, so it moves no
 // route -- written as fp32 NHWC at true scale (the blob's activation exponent of the tensor removed, a power of two).
-int bq_trunk_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_out, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
-    if (!c || !d_tiles || !d_out || !d_ws || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, "bq_trunk_u8: bad argument");
+// d_out16: the packed form (bq_trunk_u8_packed) -- the tap copies the stored 16-bit tensor and nothing scales it.
+static int trunk_impl(bq_ctx* c, const char* entry, const uint8_t* d_tiles, int n, float* d_out, void* d_out16, void* d_ws, size_t ws_bytes,
+                      bq_stream_t stream) {
+    const std::string e(entry);
+    if (!c || !d_tiles || (!d_out && !d_out16) || !d_ws || n <= 0 || n > c->cfg.max_batch) return fail(c, BQ_ERR_ARG, e + ": bad argument");
     WsLayout L;
     RUN(ready(c, n, 1, ws_bytes, &L));
     unsigned char* ws = (unsigned char*)d_ws;
     const long long count = (long long)n * 100 * 1024;
-    Tap t; t.want = "block13_out"; t.out = d_out; t.out_elems = (size_t)count;
+    Tap t; t.want = "block13_out"; t.out = d_out; t.out16 = d_out16; t.out_elems = (size_t)count;
     const Walk w{c, n, (hipStream_t)stream, &t, nullptr};
     if (has_front(c)) {
         RUN(backbone_impl(w, nullptr, (float*)(ws + L.feat), ws, d_tiles));
@@ -928,9 +932,23 @@ int bq_trunk_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_out, void* d_
         RUN(bq_stage(c, d_tiles, n, staged, stream));
         RUN(backbone_impl(w, staged, (float*)(ws + L.feat), ws));
     }
-    if (t.written != count) return fail(c, BQ_ERR_HIP, "bq_trunk_u8: block13_out was not written");
-    if (c->trunk_mul != 1.f && launch_scale_f32(d_out, count, c->trunk_mul, (hipStream_t)stream)) return fail(c, BQ_ERR_HIP, "bq_trunk_u8: scale launch failed");
+    if (t.written != count) return fail(c, BQ_ERR_HIP, e + ": block13_out was not written");
+    if (!d_out16 && c->trunk_mul != 1.f && launch_scale_f32(d_out, count, c->trunk_mul, (hipStream_t)stream))
+        return fail(c, BQ_ERR_HIP, e + ": scale launch failed");
     return BQ_OK;
+}
+
+int bq_trunk_u8(bq_ctx* c, const uint8_t* d_tiles, int n, float* d_out, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    return trunk_impl(c, "bq_trunk_u8", d_tiles, n, d_out, nullptr, d_ws, ws_bytes, stream);
+}
+
+// The same walk with the tap's copy in the engine's own 16-bit type: what bq_trunk_u8 widens and multiplies by trunk_mul, unwidened.
+int bq_trunk_u8_packed(bq_ctx* c, const uint8_t* d_tiles, int n, void* d_out16, float* mul, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    if (!c || !d_out16 || !mul || ((uintptr_t)d_out16 & 15)) return fail(c, BQ_ERR_ARG, "bq_trunk_u8_packed: bad argument");
+    if (!is16(c->cfg.dtype))
+        return fail(c, BQ_ERR_ARG, "bq_trunk_u8_packed: a float32 engine stores block13_out in 32 bits: a 16-bit copy would not be lossless");
+    *mul = c->trunk_mul;
+    return trunk_impl(c, "bq_trunk_u8_packed", d_tiles, n, nullptr, d_out16, d_ws, ws_bytes, stream);
 }
 
 int bq_profile_enable(bq_ctx* c, int on) {

@@ -124,6 +124,9 @@ int launch_to_f32_nhwc(const void* x, long long rows, int C, int ld, float* out,
 int launch_nchw_to_f32_nhwc(const void* x, int n, int C, int HW, float* out, int dtype,
                             hipStream_t s);
 int launch_scale_f32(float* x, long long count, float mul, hipStream_t s);
+// a 16-bit [rows][C] tensor with rows of ld elements -> compact, as it is stored (bq_trunk_u8_packed); hipErrorInvalidValue unless C and
+// ld are multiples of 8 and both pointers 16-byte aligned
+int launch_copy16_nhwc(const void* x, long long rows, int C, int ld, void* out, hipStream_t s);
 
 // ---- device helpers ----------------------------------------------------------------
 #define BQ_FIXED_SHIFT 40

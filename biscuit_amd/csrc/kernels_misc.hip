@@ -525,6 +525,22 @@ int launch_scale_f32(float* x, long long count, float mul, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
+// out[r][c] = x[r][c] of a 16-bit tensor of either type, rows of ld elements made compact: eight elements, 16 bytes, per load and
+// store (C and ld multiples of 8, both pointers 16-byte aligned), grid-stride
+__global__ void copy16_nhwc_kernel(const uint4* __restrict__ x, long long rows, int C8, int ld8, uint4* __restrict__ out) {
+    for (long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x; gid < rows * C8; gid += (long long)gridDim.x * blockDim.x) {
+        const long long r = gid / C8;
+        out[gid] = x[r * ld8 + (gid - r * C8)];
+    }
+}
+
+int launch_copy16_nhwc(const void* x, long long rows, int C, int ld, void* out, hipStream_t s) {
+    if (C % 8 || ld % 8 || ((uintptr_t)x | (uintptr_t)out) % 16) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(copy16_nhwc_kernel, dim3(grid_stride_for(rows * (C / 8), 256)), dim3(256), 0, s, (const uint4*)x, rows, C / 8, ld / 8,
+                       (uint4*)out);
+    return (int)hipGetLastError();
+}
+
 int launch_nchw_to_f32_nhwc(const void* x, int n, int C, int HW, float* out, int dtype, hipStream_t s) {
     const long long total = (long long)n * C * HW;
     BQ_DISPATCH_T(dtype,

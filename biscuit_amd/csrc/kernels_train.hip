@@ -694,30 +694,68 @@ __global__ void __launch_bounds__(256) exit_coef_kernel(const float* __restrict_
 
 // What a depthwise kernel reads: the activation cache through the row table (a row outside it is never read and reads as NaN, a
 // value that is not finite as NaN), relu(a z + b) of a stored z, or a plain [100 n][C] tensor.
-enum DwIn : int { IN_CACHE = 0, IN_BN = 1, IN_PLAIN = 2 };
+// IN_STAGE: the host tier's staging copy of a float32 cache, the batch's rows in order (exit_gather_kernel has checked the rows: one
+// outside the cache is NaN there).  IN_CACHE_F16 / IN_CACHE_BF16: a cache in the engine's 16-bit type, stored value h, the network's
+// value float(h) mul with mul a power of two -- the float32 cache's number exactly; a null row table: the staging copy, rows in order.
+enum DwIn : int { IN_CACHE = 0, IN_BN = 1, IN_PLAIN = 2, IN_STAGE = 3, IN_CACHE_F16 = 4, IN_CACHE_BF16 = 5 };
 struct DwSrc { const float* p; const long long* rows; long long n_act; const float* a; const float* b; };
+struct DwSrc16 { const unsigned short* p; const long long* rows; long long n_act; float mul; };
+template <int IN> struct DwOf { using Src = DwSrc; using Elt = float; };
+template <> struct DwOf<IN_CACHE_F16> { using Src = DwSrc16; using Elt = unsigned short; };
+template <> struct DwOf<IN_CACHE_BF16> { using Src = DwSrc16; using Elt = unsigned short; };
+constexpr bool dw_is16(int in) { return in == IN_CACHE_F16 || in == IN_CACHE_BF16; }
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 template <int IN, int C>
-__device__ __forceinline__ const float* dw_tile(const DwSrc& s, int i) {
-    if (IN != IN_CACHE) return s.p + (size_t)i * X_POS * C;
-    const long long r = s.rows[i];
-    return (r >= 0 && r < s.n_act) ? s.p + (size_t)r * (size_t)X_ROW : nullptr;     // 64-bit: a row is 102 400 floats
+__device__ __forceinline__ const typename DwOf<IN>::Elt* dw_tile(const typename DwOf<IN>::Src& s, int i) {
+    if constexpr (dw_is16(IN)) {
+        const long long r = s.rows ? s.rows[i] : (long long)i;
+        return (r >= 0 && r < s.n_act) ? s.p + (size_t)r * (size_t)X_ROW : nullptr; // 64-bit: a row is 102 400 elements, 204 800 bytes
+    } else {
+        if (IN != IN_CACHE) return s.p + (size_t)i * X_POS * C;
+        const long long r = s.rows[i];
+        return (r >= 0 && r < s.n_act) ? s.p + (size_t)r * (size_t)X_ROW : nullptr;     // 64-bit: a row is 102 400 floats
+    }
 }
+// a, b: the BN coefficients of IN_BN; a.x of a 16-bit cache: its mul
 template <int IN, int C>
-__device__ __forceinline__ float4 dw_at(const float* tile, int pos, int c, const float4& a, const float4& b) {
-    if (IN == IN_CACHE && !tile) { const float nan = __builtin_nanf(""); return make_float4(nan, nan, nan, nan); }
-    const float4 v = ld4(tile + (size_t)pos * C + c);
-    return IN == IN_CACHE ? finite4(v) : IN == IN_BN ? bn_relu4(v, a, b) : v;
+__device__ __forceinline__ float4 dw_at(const typename DwOf<IN>::Elt* tile, int pos, int c, const float4& a, const float4& b) {
+    if constexpr (dw_is16(IN)) {
+        if (!tile) { const float nan = __builtin_nanf(""); return make_float4(nan, nan, nan, nan); }
+        const unsigned short* p = tile + (size_t)pos * C + c;          // four channels: one 8-byte load
+        float4 v;
+        if (IN == IN_CACHE_F16) {
+            const f16x4 h = *reinterpret_cast<const f16x4*>(p);
+            v = make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
+        } else {
+            const uint2 h = *reinterpret_cast<const uint2*>(p);
+            v = make_float4(__uint_as_float(h.x << 16), __uint_as_float(h.x & 0xffff0000u), __uint_as_float(h.y << 16),
+                            __uint_as_float(h.y & 0xffff0000u));
+        }
+        return finite4(make_float4(v.x * a.x, v.y * a.x, v.z * a.x, v.w * a.x));
+    } else {
+        if (IN == IN_CACHE && !tile) { const float nan = __builtin_nanf(""); return make_float4(nan, nan, nan, nan); }
+        const float4 v = ld4(tile + (size_t)pos * C + c);
+        return IN == IN_CACHE || IN == IN_STAGE ? finite4(v) : IN == IN_BN ? bn_relu4(v, a, b) : v;
+    }
+}
+// a and b of dw_at
+template <int IN>
+__device__ __forceinline__ void dw_coef(const typename DwOf<IN>::Src& s, int c, float4& a, float4& b) {
+    a = b = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (dw_is16(IN)) a.x = s.mul;
+    else if (IN == IN_BN) { a = ld4(s.a + c); b = ld4(s.b + c); }
 }
 
 // out[i][y][x][c] = sum over the taps (ky, kx) in order of in[i][y + ky - 1][x + kx - 1][c] w[ky][kx][c], an fmaf chain; zero padding 1
 // (a tap outside the map adds nothing).  FLIP: the taps reversed -- the transpose, the gradient with respect to the input.
 template <int IN, int C, bool FLIP>
-__global__ void __launch_bounds__(256) exit_dw_kernel(const DwSrc s, const float* __restrict__ w, float* __restrict__ out) {
+__global__ void __launch_bounds__(256) exit_dw_kernel(const typename DwOf<IN>::Src s, const float* __restrict__ w, float* __restrict__ out) {
     const int i = blockIdx.y, c = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, q = threadIdx.x >> 6;
-    const float* tile = dw_tile<IN, C>(s, i);
+    const auto* tile = dw_tile<IN, C>(s, i);
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 a = IN == IN_BN ? ld4(s.a + c) : zero, b = IN == IN_BN ? ld4(s.b + c) : zero;
+    float4 a, b;
+    dw_coef<IN>(s, c, a, b);
     float4 wt[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) wt[t] = ld4(w + (size_t)(FLIP ? 8 - t : t) * C + c);
@@ -738,12 +776,14 @@ __global__ void __launch_bounds__(256) exit_dw_kernel(const DwSrc s, const float
 // part[i][ky][kx][c] = sum over tile i's positions of in[i][y + ky - 1][x + kx - 1][c] du[i][y][x][c]: the depthwise kernel's weight
 // gradient of one tile (exit_colsum_kernel adds the tiles).
 template <int IN, int C>
-__global__ void __launch_bounds__(256) exit_dw_wgrad_kernel(const DwSrc s, const float* __restrict__ du, float* __restrict__ part) {
+__global__ void __launch_bounds__(256) exit_dw_wgrad_kernel(const typename DwOf<IN>::Src s, const float* __restrict__ du,
+                                                            float* __restrict__ part) {
     __shared__ float4 lds[4][9][64];
     const int i = blockIdx.y, cq = threadIdx.x & 63, c = (blockIdx.x * 64 + cq) * 4, q = threadIdx.x >> 6;
-    const float* tile = dw_tile<IN, C>(s, i);
+    const auto* tile = dw_tile<IN, C>(s, i);
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 a = IN == IN_BN ? ld4(s.a + c) : zero, b = IN == IN_BN ? ld4(s.b + c) : zero;
+    float4 a, b;
+    dw_coef<IN>(s, c, a, b);
     float4 acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) acc[t] = zero;
@@ -831,8 +871,25 @@ __global__ void __launch_bounds__(256) exit_colsum_kernel(const float* __restric
     }
 }
 
+// The host tier's gather: stage[i] = cache[rows[i]], whole rows of row16 16-byte pieces, one load and one store each; `cache` is the
+// device pointer of mapped pinned host memory, which this kernel alone reads (once per piece: fine-grained memory is not cached).  A row
+// outside 0 .. n_rows - 1 is never read: its copy is `nan`, the NaN pattern of the cache's type in every element.
+constexpr int GATHER_BLOCKS = 50;
+__global__ void __launch_bounds__(256) exit_gather_kernel(const uint4* __restrict__ cache, long long n_rows, const long long* __restrict__ rows,
+                                                          int row16, unsigned nan, uint4* __restrict__ stage) {
+    const long long r = rows[blockIdx.y];
+    const bool in = r >= 0 && r < n_rows;
+    const uint4* src = cache + (in ? (size_t)r * (size_t)row16 : (size_t)0);      // 64-bit: a row is 204 800 or 409 600 bytes
+    uint4* dst = stage + (size_t)blockIdx.y * (size_t)row16;
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < row16; k += GATHER_BLOCKS * 256) dst[k] = in ? src[k] : make_uint4(nan, nan, nan, nan);
+}
+
+constexpr size_t act_elt_bytes(int type) { return type == BQ_ACT_F32 ? 4 : 2; }
+constexpr size_t act_row_bytes(int type) { return (size_t)X_ROW * act_elt_bytes(type); }
+
 // The layout of both exit workspaces, the regions in order, each rounded up to 256 bytes; `train`: the backward regions and the
-// head's own workspace behind the forward ones.  du1 takes du2's place once du2 is spent.
+// head's own workspace behind the forward ones.  du1 takes du2's place once du2 is spent.  The host tier's staging copy of the
+// batch's rows lies behind either (exit_stage).
 struct ExitWs {
     float *a1, *b1, *i1, *a2, *b2, *i2, *u1, *z1, *u2, *z2, *f;           // forward
     float *df, *dz2, *du, *dz1, *part; void* head;                         // backward
@@ -864,13 +921,49 @@ void launch_mat(const float* a, int lda, const float* bm, int ldb, float* out, i
     hipLaunchKernelGGL((train_gemm_kernel<AM, BM, EPI>), dim3(N / TN, (M + TM - 1) / TM), dim3(256), 0, s, p);
 }
 
-struct ExitBatch { const float* params; const float* stats; const float* acts; long long n_act; const long long* rows; int n; };
+// acts: the cache, n_act rows of `type` (BQ_ACT_*) holding value / mul; stage: null for a cache on the device, the staging copy --
+// n rows of the cache's type -- for one in host memory, which acts then addresses through its mapped device pointer
+struct ExitBatch {
+    const float* params; const float* stats; const void* acts; long long n_act; const long long* rows; int n;
+    int type = BQ_ACT_F32; float mul = 1.f; void* stage = nullptr;
+};
+ExitBatch exit_batch(const float* params, const float* stats, const bq_act_cache& a, const long long* rows, int n) {
+    ExitBatch b{params, stats, a.p, (long long)a.n_rows, rows, n};
+    b.type = a.type; b.mul = a.mul;
+    return b;
+}
 
-// The forward half, seven launches under the classes `pre`coef, dw1, pw1, dw2, pw2, pool: acts[rows] -> w.f [n][2048] (u and z stay in w).
+// The two readers of the cache, exit_dw_kernel (x: the taps) and exit_dw_wgrad_kernel (WGRAD; x: du), by the cache's type and place
+template <int IN, bool WGRAD>
+void launch_cache_reader(const typename DwOf<IN>::Src& src, const float* x, float* out, int n, hipStream_t s) {
+    if (WGRAD) hipLaunchKernelGGL((exit_dw_wgrad_kernel<IN, X_C0>), dim3(X_C0 / 256, n), dim3(256), 0, s, src, x, out);
+    else hipLaunchKernelGGL((exit_dw_kernel<IN, X_C0, false>), dim3(X_C0 / 256, n), dim3(256), 0, s, src, x, out);
+}
+template <bool WGRAD>
+void enqueue_cache_reader(const ExitBatch& b, const float* x, float* out, hipStream_t s) {
+    if (b.type == BQ_ACT_F32) {
+        if (b.stage) launch_cache_reader<IN_STAGE, WGRAD>(DwSrc{(const float*)b.stage, nullptr, 0, nullptr, nullptr}, x, out, b.n, s);
+        else launch_cache_reader<IN_CACHE, WGRAD>(DwSrc{(const float*)b.acts, b.rows, b.n_act, nullptr, nullptr}, x, out, b.n, s);
+        return;
+    }
+    const DwSrc16 src = b.stage ? DwSrc16{(const unsigned short*)b.stage, nullptr, (long long)b.n, b.mul}
+                                : DwSrc16{(const unsigned short*)b.acts, b.rows, b.n_act, b.mul};
+    if (b.type == BQ_ACT_F16) launch_cache_reader<IN_CACHE_F16, WGRAD>(src, x, out, b.n, s);
+    else launch_cache_reader<IN_CACHE_BF16, WGRAD>(src, x, out, b.n, s);
+}
+
+// The forward half, seven launches under the classes `pre`coef, dw1, pw1, dw2, pw2, pool: acts[rows] -> w.f [n][2048] (u and z stay in w);
+// in front of them for a cache in host memory, under exit_gather, the batch's rows into b.stage, which both readers of the cache then read.
 void enqueue_exit_forward(bq_ctx* c, const ExitBatch& b, const ExitWs& w, const std::string& pre, hipStream_t s) {
     const int n = b.n, M = n * X_POS;
     const double fm = (double)M;
     const float* e = b.params;
+    if (b.stage) {
+        const unsigned nan = b.type == BQ_ACT_F32 ? 0x7fc00000u : b.type == BQ_ACT_F16 ? 0x7e007e00u : 0x7fc07fc0u;
+        ProfScope ps(c, s, "exit_gather", 0.0, 2.0 * n * (double)act_row_bytes(b.type));
+        hipLaunchKernelGGL(exit_gather_kernel, dim3(GATHER_BLOCKS, n), dim3(256), 0, s, (const uint4*)b.acts, b.n_act, b.rows,
+                           (int)(act_row_bytes(b.type) / 16), nan, (uint4*)b.stage);
+    }
     {
         ProfScope ps(c, s, pre + "coef", 8.0 * (X_C1 + X_C2), 28.0 * (X_C1 + X_C2));
         hipLaunchKernelGGL(exit_coef_kernel, dim3(X_C1 / 256), dim3(256), 0, s, e + E_G1, e + E_B1, b.stats + S_M1, b.stats + S_V1, X_C1, w.a1,
@@ -879,9 +972,8 @@ void enqueue_exit_forward(bq_ctx* c, const ExitBatch& b, const ExitWs& w, const 
                            w.b2, w.i2);
     }
     {
-        ProfScope ps(c, s, pre + "dw1", 18.0 * fm * X_C0, 8.0 * fm * X_C0);
-        hipLaunchKernelGGL((exit_dw_kernel<IN_CACHE, X_C0, false>), dim3(X_C0 / 256, n), dim3(256), 0, s,
-                           DwSrc{b.acts, b.rows, b.n_act, nullptr, nullptr}, e + E_D1, w.u1);
+        ProfScope ps(c, s, pre + "dw1", 18.0 * fm * X_C0, (4.0 + act_elt_bytes(b.type)) * fm * X_C0);
+        enqueue_cache_reader<false>(b, e + E_D1, w.u1, s);
     }
     {
         ProfScope ps(c, s, pre + "pw1", 2.0 * fm * X_C0 * X_C1, 4.0 * (fm * X_C0 + fm * X_C1 + (double)X_C0 * X_C1));
@@ -961,9 +1053,8 @@ int enqueue_exit_grad(bq_ctx* c, const ExitBatch& b, const unsigned char* labels
         launch_mat<A_MAT_K, B_KCONT, EPI_STORE>(w.dz1, X_C1, e + E_P1, X_C1, w.du, X_C0, M, X_C0, X_C1, s);
     }
     {   // dD1 over the cached x
-        ProfScope ps(c, s, "exit_train_dd1", 18.0 * fm * X_C0, 8.0 * fm * X_C0);
-        hipLaunchKernelGGL((exit_dw_wgrad_kernel<IN_CACHE, X_C0>), dim3(X_C0 / 256, n), dim3(256), 0, s,
-                           DwSrc{b.acts, b.rows, b.n_act, nullptr, nullptr}, w.du, w.part);
+        ProfScope ps(c, s, "exit_train_dd1", 18.0 * fm * X_C0, (4.0 + act_elt_bytes(b.type)) * fm * X_C0);
+        enqueue_cache_reader<true>(b, w.du, w.part, s);
         hipLaunchKernelGGL(exit_colsum_kernel, dim3(9 * X_C0 / 32), dim3(256), 0, s, w.part, n, 9 * X_C0, grad + E_D1);
     }
     HIPCHK(c, hipGetLastError());
@@ -989,37 +1080,102 @@ std::string bad_exit_grad(bq_ctx* c, const char* entry, const ExitBatch& b, cons
     return "";
 }
 
+// The refusal of a cache descriptor, "" for none: a type and a place of the header's, at least one row, and a mul that is a positive
+// finite power of two -- 1 for float32, which is read as it is.
+std::string bad_cache(const char* entry, const bq_act_cache* a) {
+    const std::string e(entry);
+    if (!a) return e + ": null cache descriptor";
+    if (a->type != BQ_ACT_F32 && a->type != BQ_ACT_F16 && a->type != BQ_ACT_BF16) return e + ": the cache's type is none of BQ_ACT_F32 / F16 / BF16";
+    if (a->where != BQ_ACT_DEVICE && a->where != BQ_ACT_HOST) return e + ": the cache's place is neither BQ_ACT_DEVICE nor BQ_ACT_HOST";
+    int ex = 0;
+    if (!(a->mul > 0.f) || !std::isfinite(a->mul) || std::frexp(a->mul, &ex) != 0.5f || (a->type == BQ_ACT_F32 && a->mul != 1.f))
+        return e + ": the cache's mul is a positive finite power of two, and 1 for a float32 cache";
+    return "";
+}
+
+// the workspace of a call on cache `a` over up to n rows: the device tier's, and the staging rows behind it for a cache in host memory
+size_t exit_ws_bytes(const bq_act_cache& a, int n, bool train) {
+    if (n < 1 || n > EXIT_MAX_N) return 0;
+    return exit_ws(nullptr, n, train).total + (a.where == BQ_ACT_HOST ? (size_t)n * act_row_bytes(a.type) : 0);
+}
+// b.stage of a call whose largest batch is n
+void* exit_stage(const bq_act_cache& a, void* ws, int n, bool train) {
+    return a.where == BQ_ACT_HOST ? (unsigned char*)ws + exit_ws(nullptr, n, train).total : nullptr;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t bq_exit_features_workspace_bytes(int n) { return n < 1 || n > EXIT_MAX_N ? 0 : exit_ws(nullptr, n, false).total; }
 size_t bq_exit_train_workspace_bytes(int n) { return n < 1 || n > EXIT_MAX_N ? 0 : exit_ws(nullptr, n, true).total; }
+size_t bq_exit_features_staged_workspace_bytes(int n, int type) {
+    return exit_ws_bytes(bq_act_cache{nullptr, 0, type, 1.f, BQ_ACT_HOST}, type < 0 || type > 2 ? 0 : n, false);
+}
+size_t bq_exit_staged_workspace_bytes(int n, int type) {
+    return exit_ws_bytes(bq_act_cache{nullptr, 0, type, 1.f, BQ_ACT_HOST}, type < 0 || type > 2 ? 0 : n, true);
+}
 
-int bq_exit_features(bq_ctx* c, const float* d_exit_params, const float* d_bn_stats, const float* d_acts, int64_t n_act, const int64_t* d_rows,
-                     int n, float* d_feat2048, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
-    const ExitBatch b{d_exit_params, d_bn_stats, d_acts, (long long)n_act, (const long long*)d_rows, n};
-    const std::string bad = bad_exit(c, "bq_exit_features", b, d_ws, aligned(d_feat2048, 16));
+int bq_host_device_pointer(void* host, void** dev) {
+    if (!host || !dev) return fail(nullptr, BQ_ERR_ARG, "bq_host_device_pointer: null pointer");
+    *dev = nullptr;
+    hipPointerAttribute_t at{};
+    // asked of the runtime first: hipHostGetDevicePointer is only called on memory it says is host memory it registered
+    if (hipPointerGetAttributes(&at, host) != hipSuccess || at.type != hipMemoryTypeHost || hipHostGetDevicePointer(dev, host, 0) != hipSuccess ||
+        !*dev) {
+        (void)hipGetLastError();       // the refusal is this call's answer, not a pending error of the next launch
+        *dev = nullptr;
+        return fail(nullptr, BQ_ERR_ARG, "bq_host_device_pointer: not mapped pinned host memory");
+    }
+    return BQ_OK;
+}
+
+int bq_exit_features_c(bq_ctx* c, const float* d_exit_params, const float* d_bn_stats, const bq_act_cache* cache, const int64_t* d_rows, int n,
+                       float* d_feat2048, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    std::string bad = bad_cache("bq_exit_features", cache);
     if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
-    if (ws_bytes < bq_exit_features_workspace_bytes(n))
-        return fail(c, BQ_ERR_WORKSPACE, "bq_exit_features: workspace below bq_exit_features_workspace_bytes(n)");
+    ExitBatch b = exit_batch(d_exit_params, d_bn_stats, *cache, (const long long*)d_rows, n);
+    bad = bad_exit(c, "bq_exit_features", b, d_ws, aligned(d_feat2048, 16));
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < exit_ws_bytes(*cache, n, false))
+        return fail(c, BQ_ERR_WORKSPACE, std::string("bq_exit_features: workspace below ") +
+                    (cache->where == BQ_ACT_HOST ?"bq_exit_features_staged_workspace_bytes(n, type)" : "bq_exit_features_workspace_bytes(n)"));
     DeviceGuard guard(c->device);
     ExitWs w = exit_ws(d_ws, n, false);
     w.f = d_feat2048;
+    b.stage = exit_stage(*cache, d_ws, n, false);
     enqueue_exit_forward(c, b, w, "exit_feat_", (hipStream_t)stream);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
 
+int bq_exit_features(bq_ctx* c, const float* d_exit_params, const float* d_bn_stats, const float* d_acts, int64_t n_act, const int64_t* d_rows,
+                     int n, float* d_feat2048, void* d_ws, size_t ws_bytes, bq_stream_t stream) {
+    const bq_act_cache cache{d_acts, n_act, BQ_ACT_F32, 1.f, BQ_ACT_DEVICE};
+    return bq_exit_features_c(c, d_exit_params, d_bn_stats, &cache, d_rows, n, d_feat2048, d_ws, ws_bytes, stream);
+}
+
+int bq_exit_grad_c(bq_ctx* c, const float* d_params, const float* d_bn_stats, const bq_act_cache* cache, const int64_t* d_rows,
+                   const uint8_t* d_labels, int n, int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, void* d_ws,
+                   size_t ws_bytes, bq_stream_t stream) {
+    std::string bad = bad_cache("bq_exit_grad", cache);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    ExitBatch b = exit_batch(d_params, d_bn_stats, *cache, (const long long*)d_rows, n);
+    bad = bad_exit_grad(c, "bq_exit_grad", b, d_labels, (long long)step, rate, d_ws, d_grad, d_loss);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < exit_ws_bytes(*cache, n, true))
+        return fail(c, BQ_ERR_WORKSPACE, std::string("bq_exit_grad: workspace below ") +
+                    (cache->where == BQ_ACT_HOST ?"bq_exit_staged_workspace_bytes(n, type)" : "bq_exit_train_workspace_bytes(n)"));
+    DeviceGuard guard(c->device);
+    b.stage = exit_stage(*cache, d_ws, n, true);
+    return enqueue_exit_grad(c, b, d_labels, (long long)step, seed, rate, d_ws, d_grad, d_loss, (hipStream_t)stream);
+}
+
 int bq_exit_grad(bq_ctx* c, const float* d_params, const float* d_bn_stats, const float* d_acts, int64_t n_act, const int64_t* d_rows,
                  const uint8_t* d_labels, int n, int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, void* d_ws,
                  size_t ws_bytes, bq_stream_t stream) {
-    const ExitBatch b{d_params, d_bn_stats, d_acts, (long long)n_act, (const long long*)d_rows, n};
-    const std::string bad = bad_exit_grad(c, "bq_exit_grad", b, d_labels, (long long)step, rate, d_ws, d_grad, d_loss);
-    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
-    if (ws_bytes < bq_exit_train_workspace_bytes(n)) return fail(c, BQ_ERR_WORKSPACE, "bq_exit_grad: workspace below bq_exit_train_workspace_bytes(n)");
-    DeviceGuard guard(c->device);
-    return enqueue_exit_grad(c, b, d_labels, (long long)step, seed, rate, d_ws, d_grad, d_loss, (hipStream_t)stream);
+    const bq_act_cache cache{d_acts, n_act, BQ_ACT_F32, 1.f, BQ_ACT_DEVICE};
+    return bq_exit_grad_c(c, d_params, d_bn_stats, &cache, d_rows, d_labels, n, step, seed, rate, d_grad, d_loss, d_ws, ws_bytes, stream);
 }
 
 int bq_adam_n(bq_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, int64_t count, int64_t step, double lr, double b1,
@@ -1032,22 +1188,26 @@ int bq_adam_n(bq_ctx* c, float* d_params, float* d_m, float* d_v, const float* d
     return enqueue_adam(c, d_params, d_m, d_v, d_grad, (long long)step, lr, b1, b2, eps, (hipStream_t)stream, (long long)count, "adam_n");
 }
 
-int bq_exit_train_steps(bq_ctx* c, float* d_params, float* d_m, float* d_v, float* d_grad, const float* d_bn_stats, const float* d_acts,
-                        int64_t n_act, const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n, int64_t step0,
-                        uint64_t seed, double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws,
-                        size_t ws_bytes, bq_stream_t stream) {
+int bq_exit_train_steps_c(bq_ctx* c, float* d_params, float* d_m, float* d_v, float* d_grad, const float* d_bn_stats, const bq_act_cache* cache,
+                          const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n, int64_t step0, uint64_t seed,
+                          double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws, size_t ws_bytes,
+                          bq_stream_t stream) {
     if (!c) return fail(c, BQ_ERR_ARG, "bq_exit_train_steps: null context");
     if (steps < 1 || steps > (1 << 24) || last_n < 1 || last_n > batch || !h_lr)
         return fail(c, BQ_ERR_ARG, "bq_exit_train_steps: 1 <= steps <= 2^24, 1 <= last_n <= batch and a learning rate per step");
-    ExitBatch b{d_params, d_bn_stats, d_acts, (long long)n_act, (const long long*)d_rows, batch};
-    std::string bad = bad_exit_grad(c, "bq_exit_train_steps", b, d_labels, (long long)step0, rate, d_ws, d_grad, d_losses);
+    std::string bad = bad_cache("bq_exit_train_steps", cache);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    ExitBatch b = exit_batch(d_params, d_bn_stats, *cache, (const long long*)d_rows, batch);
+    bad = bad_exit_grad(c, "bq_exit_train_steps", b, d_labels, (long long)step0, rate, d_ws, d_grad, d_losses);
     if (bad.empty() && step0 + steps > 0x100000000LL) bad = "bq_exit_train_steps: the steps pass 2^32";
     for (int i = 0; bad.empty() && i < steps; ++i) bad = bad_adam_args("bq_exit_train_steps", d_params, d_m, d_v, d_grad, step0 + i, h_lr[i], b1, b2, eps);
     if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
-    if (ws_bytes < bq_exit_train_workspace_bytes(batch))
-        return fail(c, BQ_ERR_WORKSPACE, "bq_exit_train_steps: workspace below bq_exit_train_workspace_bytes(batch)");
+    if (ws_bytes < exit_ws_bytes(*cache, batch, true))
+        return fail(c, BQ_ERR_WORKSPACE, std::string("bq_exit_train_steps: workspace below ") +
+                    (cache->where == BQ_ACT_HOST ? "bq_exit_staged_workspace_bytes(batch, type)" : "bq_exit_train_workspace_bytes(batch)"));
     DeviceGuard guard(c->device);
     hipStream_t s = (hipStream_t)stream;
+    b.stage = exit_stage(*cache, d_ws, batch, true);          // behind the largest step's regions: a short last step uses fewer of them
     for (int i = 0; i < steps; ++i) {
         b.rows = (const long long*)d_rows + (size_t)i * batch;
         b.n = i + 1 < steps ? batch : last_n;
@@ -1055,6 +1215,15 @@ int bq_exit_train_steps(bq_ctx* c, float* d_params, float* d_m, float* d_v, floa
         RUN(enqueue_adam(c, d_params, d_m, d_v, d_grad, (long long)step0 + i, h_lr[i], b1, b2, eps, s, P_ALL, "exit_train_adam"));
     }
     return BQ_OK;
+}
+
+int bq_exit_train_steps(bq_ctx* c, float* d_params, float* d_m, float* d_v, float* d_grad, const float* d_bn_stats, const float* d_acts,
+                        int64_t n_act, const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n, int64_t step0,
+                        uint64_t seed, double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws,
+                        size_t ws_bytes, bq_stream_t stream) {
+    const bq_act_cache cache{d_acts, n_act, BQ_ACT_F32, 1.f, BQ_ACT_DEVICE};
+    return bq_exit_train_steps_c(c, d_params, d_m, d_v, d_grad, d_bn_stats, &cache, d_rows, d_labels, steps, batch, last_n, step0, seed, rate,
+                                 h_lr, b1, b2, eps, d_losses, d_ws, ws_bytes, stream);
 }
 
 size_t bq_head_train_workspace_bytes(int n) { return n < 1 || n > MAX_N ? 0 : train_ws(nullptr, n).total; }

@@ -130,7 +130,7 @@ class Engine:
         """Lets go of every device buffer grown on demand -- the network's workspace and each tool's scratch -- and of nothing else;
         the next call that wants one allocates it again."""
         self._ws = None                  # the network's workspace (``_ws_for``)
-        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong, train, validate, augment, exit_features, exit_train, exit_validate
+        self._tool_ws = {}               # family -> a tool's scratch (``_scratch``): inflate, jpeg, j2k, lzw, jpeg_encode, png_encode, knn, umap, uq, delong, train, validate, augment, exit_features, exit_train, exit_validate, exit_features_staged, exit_train_staged
 
     def _drop_caches(self):
         """Every device tensor the engine keeps between calls, empty: how ``__init__`` declares them and ``close()`` lets them go."""
@@ -1241,24 +1241,72 @@ class Engine:
     EXIT_PARAMS, EXIT_BN_STATS, EXIT_MAX_ROWS, EXIT_ACT_SHAPE = 4748800, 7168, 256, (10, 10, 1024)   # (train.py holds copies)
     ALL_PARAMS = EXIT_PARAMS + HEAD_PARAMS
 
-    def trunk(self, tiles_u8):
+    def trunk(self, tiles_u8, packed=False):
         """uint8 NHWC tiles (device) -> ``block13_out`` float32 [n, 10, 10, 1024] at true scale (``bq_trunk_u8``): ``backbone_u8``'s
-        launches up to the tensor block 14 reads, what ``train.cache_activations`` keeps per tile."""
+        launches up to the tensor block 14 reads, what ``train.cache_activations`` keeps per tile.  ``packed`` (a 16-bit engine's;
+        ValueError on an f32 one): ``(acts16, mul)`` instead (``bq_trunk_u8_packed``) -- the tensor as the engine stores it, in the
+        engine's own 16-bit type, and the power of two with ``acts16.float() * mul`` the unpacked result bit for bit."""
         assert tiles_u8.dtype == torch.uint8 and tiles_u8.is_cuda and tiles_u8.is_contiguous()
         n = tiles_u8.shape[0]
+        if packed and self.dtype == 'f32':
+            raise ValueError('trunk(packed=True): an f32 engine stores block13_out in 32 bits, so a 16-bit copy would not be lossless')
         ws = self._ws_for(n, 1)
-        out = torch.empty((n,) + self.EXIT_ACT_SHAPE, dtype=torch.float32, device=self.device)
+        out = torch.empty((n,) + self.EXIT_ACT_SHAPE, dtype=self._elt if packed else torch.float32, device=self.device)
+        if packed:
+            mul = C.c_float(0.0)
+            self._check(self._lib.bq_trunk_u8_packed(self._ctx, _ptr(tiles_u8), n, _ptr(out), C.byref(mul), _ptr(ws), ws.numel(), self._stream()))
+            return out, float(mul.value)
         self._check(self._lib.bq_trunk_u8(self._ctx, _ptr(tiles_u8), n, _ptr(out), _ptr(ws), ws.numel(), self._stream()))
         return out
 
-    def exit_train_scratch(self, n):
+    def exit_train_scratch(self, n, staged=None):
         """A caller's own scratch for ``exit_grad`` / ``exit_train_steps`` with batches of up to ``n`` rows (``scratch=``); without one
-        the calls share the engine's cached ``exit_train`` buffer."""
-        return self._bytes(self._lib.bq_exit_train_workspace_bytes(int(n)))
+        the calls share the engine's cached ``exit_train`` buffer.  ``staged``: for a cache in pinned host memory of that torch dtype
+        (the staging rows behind the rest; the family ``exit_train_staged``)."""
+        return self._bytes(self._exit_need(True, int(n), staged))
 
-    def exit_features_scratch(self, n):
-        """A caller's own scratch for ``exit_features`` over up to ``n`` rows; without one the calls share the cached ``exit_features`` buffer."""
-        return self._bytes(self._lib.bq_exit_features_workspace_bytes(int(n)))
+    def exit_features_scratch(self, n, staged=None):
+        """A caller's own scratch for ``exit_features`` over up to ``n`` rows; without one the calls share the cached ``exit_features``
+        buffer (``staged``: as ``exit_train_scratch``'s; the family ``exit_features_staged``)."""
+        return self._bytes(self._exit_need(False, int(n), staged))
+
+    ACT_TYPES = {torch.float32: _lib.BQ_DTYPE_F32, torch.bfloat16: _lib.BQ_DTYPE_BF16, torch.float16: _lib.BQ_DTYPE_F16}
+
+    def _exit_need(self, train, n, staged):
+        """The bytes of an exit call's workspace over ``n`` rows; ``staged``: None, or the dtype of a cache in host memory."""
+        if staged is None:
+            return int((self._lib.bq_exit_train_workspace_bytes if train else self._lib.bq_exit_features_workspace_bytes)(n))
+        return int((self._lib.bq_exit_staged_workspace_bytes if train else self._lib.bq_exit_features_staged_workspace_bytes)(n, self.ACT_TYPES[staged]))
+
+    def _act_cache(self, call, acts, act_mul):
+        """What an exit call reads ``acts`` as -> ``(descriptor, staged)``: ``descriptor`` None for a float32 device tensor -- the
+        calls without a descriptor --, else the ``bq_act_cache`` of a 16-bit device tensor or of a pinned host tensor of any of the
+        three types; ``staged`` None on the device, the dtype of a cache in host memory.  ValueError, before anything is launched, for
+        another shape or type, a tensor that is not contiguous, a device tensor elsewhere, a host tensor that is not mapped pinned
+        memory, a 16-bit cache in another type than the engine's own (only its own stored values are the float32 cache's exactly)
+        and an ``act_mul`` that is not a positive finite power of two (1 for float32, which is read as it is)."""
+        if not (torch.is_tensor(acts) and acts.dtype in self.ACT_TYPES and acts.dim() == 4 and tuple(acts.shape[1:]) == self.EXIT_ACT_SHAPE and
+                acts.shape[0] >= 1 and acts.is_contiguous()):
+            raise ValueError(f'{call}: acts must be contiguous float32, float16 or bfloat16 [N, 10, 10, 1024] with N >= 1')
+        mul = float(act_mul)
+        if not (mul > 0.0 and np.isfinite(mul) and np.frexp(mul)[0] == 0.5 and np.float32(mul) == mul and np.isfinite(np.float32(mul))):
+            raise ValueError(f'{call}: act_mul must be a positive finite power of two, not {act_mul!r}')
+        if acts.dtype == torch.float32 and mul != 1.0:
+            raise ValueError(f'{call}: a float32 cache is read as it is: act_mul must be 1, not {act_mul!r}')
+        if acts.dtype != torch.float32 and acts.dtype != self._elt:
+            raise ValueError(f'{call}: a 16-bit cache must be in the engine\'s own type {self._elt} (only its stored values are the float32 '
+                             f'cache\'s exactly), not {acts.dtype}')
+        if acts.is_cuda:
+            self._on_device('acts', acts)
+            if acts.dtype == torch.float32:
+                return None, None
+            return _lib.BqActCache(acts.data_ptr(), int(acts.shape[0]), self.ACT_TYPES[acts.dtype], mul, _lib.BQ_ACT_DEVICE), None
+        dev = C.c_void_p(0)
+        if acts.device.type != 'cpu' or not acts.is_pinned() or self._lib.bq_host_device_pointer(C.c_void_p(acts.data_ptr()), C.byref(dev)) < 0 \
+                or not dev.value:
+            raise ValueError(f'{call}: acts in host memory must be pinned (torch.empty(..., pin_memory=True)): the gather kernel reads them '
+                             'through the mapped device pointer')
+        return _lib.BqActCache(dev.value, int(acts.shape[0]), self.ACT_TYPES[acts.dtype], mul, _lib.BQ_ACT_HOST), acts.dtype
 
     def _exit_vec(self, count, *named):
         for name, t in named:
@@ -1266,64 +1314,76 @@ class Engine:
                 raise ValueError(f'{name} must be contiguous float32 [{count}]')
             self._on_device(name, t)
 
-    def _exit_batch(self, call, bn_stats, acts, rows, labels, count):
-        """``bn_stats`` float32 [7168], ``acts`` float32 [N, 10, 10, 1024], ``rows`` int64 and (unless None) ``labels`` uint8, ``count``
-        of each, all on this device; ValueError otherwise."""
+    def _exit_batch(self, call, bn_stats, acts, rows, labels, count, act_mul=1.0):
+        """``bn_stats`` float32 [7168], ``rows`` int64 and (unless None) ``labels`` uint8, ``count`` of each, all on this device, and
+        ``acts`` [N, 10, 10, 1024] in a form ``_act_cache`` takes; ValueError otherwise -> ``_act_cache``'s pair."""
         self._exit_vec(self.EXIT_BN_STATS, ('bn_stats', bn_stats))
-        if not (torch.is_tensor(acts) and acts.dtype == torch.float32 and acts.dim() == 4 and tuple(acts.shape[1:]) == self.EXIT_ACT_SHAPE and
-                acts.shape[0] >= 1 and acts.is_contiguous()):
-            raise ValueError(f'{call}: acts must be contiguous float32 [N, 10, 10, 1024] with N >= 1')
+        cache = self._act_cache(call, acts, act_mul)
         if not (torch.is_tensor(rows) and rows.dtype == torch.int64 and rows.is_contiguous() and rows.numel() == count):
             raise ValueError(f'{call}: rows must be contiguous int64 [{count}]')
         if labels is not None and not (torch.is_tensor(labels) and labels.dtype == torch.uint8 and labels.is_contiguous() and
                                        labels.numel() == count):
             raise ValueError(f'{call}: labels must be contiguous uint8 [{count}]')
-        for name, t in (('acts', acts), ('rows', rows)) + ((('labels', labels),) if labels is not None else ()):
+        for name, t in (('rows', rows),) + ((('labels', labels),) if labels is not None else ()):
             self._on_device(name, t)
+        return cache
 
-    def exit_features(self, exit_params, bn_stats, acts, rows, out=None, scratch=None):
+    def exit_features(self, exit_params, bn_stats, acts, rows, out=None, scratch=None, act_mul=1.0):
         """Block 14 and the pool over the rows ``acts[rows]`` (``bq_exit_features``): ``exit_params`` float32 [P_EXIT] in the order of
-        ``train.EXIT_TENSORS``, ``bn_stats`` float32 [7168] (``train.exit_bn_stats``), ``acts`` float32 [N, 10, 10, 1024], ``rows`` int64
+        ``train.EXIT_TENSORS``, ``bn_stats`` float32 [7168] (``train.exit_bn_stats``), ``acts`` [N, 10, 10, 1024], ``rows`` int64
         [n], 1 <= n <= 256 -> float32 [n, 2048] on the device (``out``: written there).  A tile's row depends on the tile and the
-        parameters only."""
+        parameters only.  ``acts`` is float32 on this device, the engine's own 16-bit type on this device (``trunk(packed=True)``'s,
+        with its ``mul`` as ``act_mul``: the values are ``acts.float() * act_mul`` and the result has the float32 cache's bits), or a
+        pinned host tensor of either form (``bq_exit_features_c``: the rows are gathered into the scratch first)."""
         n = int(rows.numel()) if torch.is_tensor(rows) else -1
         if not 1 <= n <= self.EXIT_MAX_ROWS:
             raise ValueError(f'exit_features: 1 <= n <= {self.EXIT_MAX_ROWS} rows, as an int64 tensor')
         self._exit_vec(self.EXIT_PARAMS, ('exit_params', exit_params))
-        self._exit_batch('exit_features', bn_stats, acts, rows, None, n)
+        cache, staged = self._exit_batch('exit_features', bn_stats, acts, rows, None, n, act_mul)
         if out is None:
             out = torch.empty((n, 2048), dtype=torch.float32, device=self.device)
         assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, 2048)
-        scratch = self._scratch('exit_features', int(self._lib.bq_exit_features_workspace_bytes(n)), scratch)
+        scratch = self._scratch('exit_features' if staged is None else 'exit_features_staged', self._exit_need(False, n, staged), scratch)
         assert scratch.is_cuda and scratch.is_contiguous()
-        self._check(self._lib.bq_exit_features(self._ctx, _ptr(exit_params), _ptr(bn_stats), _ptr(acts), int(acts.shape[0]), _ptr(rows), n,
-                                               _ptr(out), _ptr(scratch), scratch.numel(), self._stream()))
+        if cache is None:
+            self._check(self._lib.bq_exit_features(self._ctx, _ptr(exit_params), _ptr(bn_stats), _ptr(acts), int(acts.shape[0]), _ptr(rows), n,
+                                                   _ptr(out), _ptr(scratch), scratch.numel(), self._stream()))
+        else:
+            self._check(self._lib.bq_exit_features_c(self._ctx, _ptr(exit_params), _ptr(bn_stats), C.byref(cache), _ptr(rows), n, _ptr(out),
+                                                     _ptr(scratch), scratch.numel(), self._stream()))
         return out
 
-    def exit_features_all(self, exit_params, bn_stats, acts, rows):
+    def exit_features_all(self, exit_params, bn_stats, acts, rows, act_mul=1.0):
         """``exit_features`` over any number of rows, in calls of up to 256 -> float32 [len(rows), 2048]."""
         out = torch.empty((int(rows.numel()), 2048), dtype=torch.float32, device=self.device)
         for a in range(0, int(rows.numel()), self.EXIT_MAX_ROWS):
-            self.exit_features(exit_params, bn_stats, acts, rows[a:a + self.EXIT_MAX_ROWS].contiguous(), out=out[a:a + self.EXIT_MAX_ROWS])
+            self.exit_features(exit_params, bn_stats, acts, rows[a:a + self.EXIT_MAX_ROWS].contiguous(), out=out[a:a + self.EXIT_MAX_ROWS],
+                               act_mul=act_mul)
         return out
 
-    def exit_grad(self, params, bn_stats, acts, rows, labels, step, seed, rate=None, grad=None, scratch=None):
+    def exit_grad(self, params, bn_stats, acts, rows, labels, step, seed, rate=None, grad=None, scratch=None, act_mul=1.0):
         """Gradient of the mean cross-entropy over the rows ``acts[rows]`` through block 14 and the head (``bq_exit_grad``): ``params``
         float32 [P_ALL] -- the exit vector, then the head's --, ``labels`` uint8 [n] in {0, 1}, 1 <= n <= 256; dropout ``rate`` (the
-        engine's when None) with pass = ``step`` and the rows as Philox tile counters.  -> ``(grad [P_ALL], loss [1])`` on the device."""
+        engine's when None) with pass = ``step`` and the rows as Philox tile counters.  -> ``(grad [P_ALL], loss [1])`` on the device.
+        ``acts``, ``act_mul``: as ``exit_features``'."""
         n = int(rows.numel()) if torch.is_tensor(rows) else -1
         if not 1 <= n <= self.EXIT_MAX_ROWS:
             raise ValueError(f'exit_grad: 1 <= n <= {self.EXIT_MAX_ROWS} rows, as an int64 tensor')
         self._exit_vec(self.ALL_PARAMS, ('params', params))
-        self._exit_batch('exit_grad', bn_stats, acts, rows, labels, n)
+        cache, staged = self._exit_batch('exit_grad', bn_stats, acts, rows, labels, n, act_mul)
         if grad is None:
             grad = torch.empty(self.ALL_PARAMS, dtype=torch.float32, device=self.device)
         self._exit_vec(self.ALL_PARAMS, ('grad', grad))
-        rate, scratch = self._head_open('exit_train', self._lib.bq_exit_train_workspace_bytes(n), rate, step, 1, scratch,
-                                        'exit_grad: the rate lies in [0, 1) and the step in 0 .. 2^32 - 1')
+        rate, scratch = self._head_open('exit_train' if staged is None else 'exit_train_staged', self._exit_need(True, n, staged), rate, step, 1,
+                                        scratch, 'exit_grad: the rate lies in [0, 1) and the step in 0 .. 2^32 - 1')
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        self._check(self._lib.bq_exit_grad(self._ctx, _ptr(params), _ptr(bn_stats), _ptr(acts), int(acts.shape[0]), _ptr(rows), _ptr(labels), n,
-                                           int(step), int(seed), rate, _ptr(grad), _ptr(loss), _ptr(scratch), scratch.numel(), self._stream()))
+        if cache is None:
+            self._check(self._lib.bq_exit_grad(self._ctx, _ptr(params), _ptr(bn_stats), _ptr(acts), int(acts.shape[0]), _ptr(rows), _ptr(labels),
+                                               n, int(step), int(seed), rate, _ptr(grad), _ptr(loss), _ptr(scratch), scratch.numel(),
+                                               self._stream()))
+        else:
+            self._check(self._lib.bq_exit_grad_c(self._ctx, _ptr(params), _ptr(bn_stats), C.byref(cache), _ptr(rows), _ptr(labels), n, int(step),
+                                                 int(seed), rate, _ptr(grad), _ptr(loss), _ptr(scratch), scratch.numel(), self._stream()))
         return grad, loss
 
     def adam_n(self, params, m, v, grad, step, lr, b1=0.9, b2=0.999, eps=1e-7):
@@ -1338,9 +1398,10 @@ class Engine:
                                         float(b2), float(eps), self._stream()))
 
     def exit_train_steps(self, params, m, v, bn_stats, acts, rows, labels, batch, step0, seed, lr, rate=None, b1=0.9, b2=0.999, eps=1e-7,
-                         grad=None, scratch=None):
+                         grad=None, scratch=None, act_mul=1.0):
         """``S`` = ceil(len(rows) / batch) steps of ``exit_grad`` + ``adam_n`` over [P_ALL] back to back (``bq_exit_train_steps``), as
-        ``head_train_steps``: ``params``, ``m``, ``v`` change in place; -> losses float32 [S].  The same bits as the single calls."""
+        ``head_train_steps``: ``params``, ``m``, ``v`` change in place; -> losses float32 [S].  The same bits as the single calls.
+        ``acts``, ``act_mul``: as ``exit_features``'; a cache in host memory is gathered once per step."""
         count = int(rows.numel()) if torch.is_tensor(rows) else 0
         batch = int(batch)
         if not 1 <= batch <= self.EXIT_MAX_ROWS or count < 1:
@@ -1348,29 +1409,35 @@ class Engine:
         steps = -(-count // batch)
         last_n = count - (steps - 1) * batch
         self._exit_vec(self.ALL_PARAMS, ('params', params), ('m', m), ('v', v))
-        self._exit_batch('exit_train_steps', bn_stats, acts, rows, labels, count)
+        cache, staged = self._exit_batch('exit_train_steps', bn_stats, acts, rows, labels, count, act_mul)
         if grad is None:
             grad = torch.empty(self.ALL_PARAMS, dtype=torch.float32, device=self.device)
         self._exit_vec(self.ALL_PARAMS, ('grad', grad))
         lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
-        rate, scratch = self._head_open('exit_train', self._lib.bq_exit_train_workspace_bytes(batch), rate, step0, steps, scratch,
-                                        f'exit_train_steps: {steps} learning rates, a rate in [0, 1) and steps below 2^32', len(lr) == steps)
+        rate, scratch = self._head_open('exit_train' if staged is None else 'exit_train_staged', self._exit_need(True, batch, staged), rate, step0,
+                                        steps, scratch, f'exit_train_steps: {steps} learning rates, a rate in [0, 1) and steps below 2^32',
+                                        len(lr) == steps)
         losses = torch.empty(steps, dtype=torch.float32, device=self.device)
-        self._check(self._lib.bq_exit_train_steps(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), _ptr(bn_stats), _ptr(acts),
-                                                  int(acts.shape[0]), _ptr(rows), _ptr(labels), steps, batch, last_n, int(step0), int(seed),
-                                                  rate, lr.ctypes.data_as(C.POINTER(C.c_double)), float(b1), float(b2), float(eps),
-                                                  _ptr(losses), _ptr(scratch), scratch.numel(), self._stream()))
+        tail = (steps, batch, last_n, int(step0), int(seed), rate, lr.ctypes.data_as(C.POINTER(C.c_double)), float(b1), float(b2), float(eps),
+                _ptr(losses), _ptr(scratch), scratch.numel(), self._stream())
+        if cache is None:
+            self._check(self._lib.bq_exit_train_steps(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), _ptr(bn_stats), _ptr(acts),
+                                                      int(acts.shape[0]), _ptr(rows), _ptr(labels), *tail))
+        else:
+            self._check(self._lib.bq_exit_train_steps_c(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), _ptr(bn_stats), C.byref(cache),
+                                                        _ptr(rows), _ptr(labels), *tail))
         return losses
 
-    def exit_validate(self, params, bn_stats, acts, rows, labels, pass_, seed, rowloss=False, hit=False):
+    def exit_validate(self, params, bn_stats, acts, rows, labels, pass_, seed, rowloss=False, hit=False, act_mul=1.0):
         """``params`` [P_ALL] scored on the rows ``acts[rows]`` in inference mode: ``exit_features`` into scratch, then ``head_validate``
-        at rate 0 on those features with ``rows = arange(n)``, 1 <= n <= 256 -> ``head_validate``'s ``(stats, rowloss, hit)``."""
+        at rate 0 on those features with ``rows = arange(n)``, 1 <= n <= 256 -> ``head_validate``'s ``(stats, rowloss, hit)``.
+        ``acts``, ``act_mul``: as ``exit_features``'."""
         n = int(rows.numel()) if torch.is_tensor(rows) else -1
         if not 1 <= n <= self.EXIT_MAX_ROWS:
             raise ValueError(f'exit_validate: 1 <= n <= {self.EXIT_MAX_ROWS} rows, as an int64 tensor')
         self._exit_vec(self.ALL_PARAMS, ('params', params))
         feats = self._scratch('exit_validate', n * 2048 * 4).view(torch.float32)[:n * 2048].view(n, 2048)
-        self.exit_features(params[:self.EXIT_PARAMS], bn_stats, acts, rows, out=feats)
+        self.exit_features(params[:self.EXIT_PARAMS], bn_stats, acts, rows, out=feats, act_mul=act_mul)
         at = self._table('exit_validate', n, lambda: np.arange(n, dtype=np.int64))
         return self.head_validate(params[self.EXIT_PARAMS:], feats, at, labels, pass_, seed, rate=0.0, rowloss=rowloss, hit=hit)
 

@@ -25,7 +25,8 @@ split strategy (``kfold``), the directory names, the augmentation's probabilitie
 rule and its defaults, and how balanced batches are drawn.
 
 Exit-flow fine-tuning (``--trainable exit``; DESIGN.md section 7 "Exit-flow fine-tuning"): ``cache_activations`` keeps every tile's
-``block13_out`` [10, 10, 1024] on the device (``Engine.trunk``) and each training moves Xception's block 14 together with the head
+``block13_out`` [10, 10, 1024] (``Engine.trunk``; ``--act-cache``: float32 or the engine's own 16-bit form on the device, or pinned
+host memory) and each training moves Xception's block 14 together with the head
 (``Engine.exit_train_steps``), batch-norm statistics frozen -- a stated deviation from Slideflow, unpinned.  A fold then also writes
 ``exit.npz``; ``exit_engine`` packs the result into an engine.
 
@@ -337,16 +338,19 @@ def cache_features(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_f
     return FeatureCache(feats.contiguous(), np.array([index[n] for n in names], np.int64), loc, order, stacked, letters, int(seed) if V else 0)
 
 
-def cached_features(engine, slides, path, *, augment=None, views=None, seed=0, activations=False, **kw):
+def cached_features(engine, slides, path, *, augment=None, views=None, seed=0, activations=False, store='f32', **kw):
     """``--cache FILE``: ``cache_features(engine, slides, augment=..., views=..., seed=..., **kw)``, kept in ``path`` (.npz; None: not
     kept) -- loaded from there when the file exists, with its views, otherwise computed and saved.  SystemExit for a file that holds
     other slides or was made with another augmentation, number of views or seed.  ``activations`` (``--trainable exit``): an
-    ``ActivationCache`` through ``cache_activations`` instead, and SystemExit for a file without activations."""
+    ``ActivationCache`` through ``cache_activations`` instead, built under ``store`` (``--act-cache``), and SystemExit for a file
+    without activations; a file that exists keeps the form it was saved in, and goes to pinned host memory for ``store='host'``."""
     from . import augment as A
     letters = A.parse(augment)
     n_views = view_count(letters, views)
     if not path or not os.path.exists(path):
         try:
+            if activations:
+                kw = dict(kw, store=store)
             cache = (cache_activations if activations else cache_features)(engine, slides, augment=letters, views=n_views or None, seed=seed, **kw)
         except ValueError as e:
             if not activations:
@@ -356,7 +360,7 @@ def cached_features(engine, slides, path, *, augment=None, views=None, seed=0, a
             cache.save(path)
         return cache
     try:
-        cache = (ActivationCache if activations else FeatureCache).load(path, engine.device)
+        cache = ActivationCache.load(path, engine.device, host=store == 'host') if activations else FeatureCache.load(path, engine.device)
     except ValueError as e:
         raise SystemExit(f'--cache {e}') from None
     if cache.slides != [s.name for s in slides] or len(cache) != sum(int(s.n_tiles) for s in slides):
@@ -368,64 +372,161 @@ def cached_features(engine, slides, path, *, augment=None, views=None, seed=0, a
 
 
 # ------------------------------------------------------------------------------------------------------------ activation cache
+ACT_STORES = ('f32', 'packed', 'host', 'auto')      # --act-cache (DESIGN.md section 7 "Exit-flow fine-tuning", Sizes)
+ACT_TORCH = {'f16': 'float16', 'bf16': 'bfloat16', 'f32': 'float32'}
+
+
+def _acts_to_numpy(a):
+    """An activation tensor or array -> ``(numpy array, type name)``; bfloat16, which numpy lacks, as its raw ``uint16``."""
+    import torch
+    if not torch.is_tensor(a):
+        a = np.asarray(a)
+        return (a, 'f16') if a.dtype == np.float16 else (a.astype(np.float32), 'f32')
+    a = a.detach().cpu()
+    if a.dtype == torch.bfloat16:
+        return a.contiguous().view(torch.int16).numpy().view(np.uint16), 'bf16'
+    return a.numpy(), ('f16' if a.dtype == torch.float16 else 'f32')
+
+
+def _acts_from_numpy(a, act_type):
+    """``_acts_to_numpy``'s inverse: float32 stays the numpy array it always was; the 16-bit forms become host tensors of their type."""
+    import torch
+    if act_type == 'f32':
+        return a.astype(np.float32)
+    if act_type == 'bf16':
+        return torch.from_numpy(np.ascontiguousarray(a, np.uint16).view(np.int16)).view(torch.bfloat16)
+    if act_type == 'f16':
+        return torch.from_numpy(np.ascontiguousarray(a, np.float16))
+    raise ValueError(f'act_type {act_type!r} is none of f32, f16, bf16')
+
+
 @dataclass
 class ActivationCache(FeatureCache):
-    """A ``FeatureCache`` that also holds what block 14 reads: ``acts`` float32 [N, 10, 10, 1024] (``block13_out`` per tile, on the
-    device; a host array once loaded, until ``to``) and, with augmentation, ``act_views`` float32 [V, N, 10, 10, 1024] beside
-    ``views``.  ``feats`` / ``views`` are ``Engine.exit_features`` of them under the imported block 14, so everything that reads a
-    ``FeatureCache`` works on it unchanged; ``trainable='exit'`` trains on ``acts``."""
+    """A ``FeatureCache`` that also holds what block 14 reads: ``acts`` [N, 10, 10, 1024] (``block13_out`` per tile; a host array
+    once loaded, until ``to``) and, with augmentation, ``act_views`` [V, N, 10, 10, 1024] beside ``views``.  ``feats`` / ``views``
+    are ``Engine.exit_features`` of them under the imported block 14, so everything that reads a ``FeatureCache`` works on it
+    unchanged; ``trainable='exit'`` trains on ``acts``.  The activations are float32 on the device (``store='f32'``), the engine's
+    own 16-bit type on the device (``'packed'``), or either in pinned host memory (``'host'``); a 16-bit tensor holds the engine's
+    stored values and ``act_mul``, a power of two, takes them to the network's: ``acts.float() * act_mul`` is the float32 cache
+    exactly, so whatever is computed from any form has the same bits."""
     acts: object = None
     act_views: object = None
+    act_mul: float = 1.0
 
     def to(self, device):
+        """Features to ``device``; the activations too, in their own type -- unless they lie in pinned host memory, where they stay."""
         import torch
-        on = lambda a: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(device).contiguous()
+
+        def on(a):
+            t = torch.as_tensor(np.asarray(a)) if not torch.is_tensor(a) else a
+            return t if (not t.is_cuda and t.is_pinned()) else t.to(device).contiguous()
         FeatureCache.to(self, device)
         self.acts = on(self.acts)
         if self.act_views is not None:
             self.act_views = on(self.act_views)
         return self
 
+    def pin(self):
+        """The activations into pinned host memory, in their own type (``store='host'`` of a cache that was loaded)."""
+        import torch
+        pinned = lambda a: a if (not a.is_cuda and a.is_pinned()) else torch.empty(a.shape, dtype=a.dtype, pin_memory=True).copy_(a)
+        tensor = lambda a: torch.as_tensor(np.asarray(a)) if not torch.is_tensor(a) else a
+        self.acts = pinned(tensor(self.acts))
+        if self.act_views is not None:
+            self.act_views = pinned(tensor(self.act_views))
+        return self
+
     def save(self, path):
         host = lambda a: (a.cpu().numpy() if hasattr(a, 'cpu') else np.asarray(a)).astype(np.float32)
-        extra = {} if self.views is None else {'views': host(self.views), 'act_views': host(self.act_views), 'augment': np.array(self.augment),
-                                               'augment_seed': np.array(int(self.augment_seed), np.int64)}
-        np.savez(path, feats=host(self.feats), acts=host(self.acts), slide_idx=self.slide_idx, loc=self.loc,
+        acts, act_type = _acts_to_numpy(self.acts)
+        extra = {} if self.views is None else {'views': host(self.views), 'act_views': _acts_to_numpy(self.act_views)[0],
+                                               'augment': np.array(self.augment), 'augment_seed': np.array(int(self.augment_seed), np.int64)}
+        if act_type != 'f32':        # a float32 cache is the file it always was
+            extra.update(act_type=np.array(act_type), act_mul=np.array(float(self.act_mul), np.float64))
+        np.savez(path, feats=host(self.feats), acts=acts, slide_idx=self.slide_idx, loc=self.loc,
                  slides=np.array(self.slides, dtype=str), **extra)
 
     @staticmethod
-    def load(path, device=None):
+    def load(path, device=None, host=False):
+        """``host``: the activations into pinned host memory (``pin``) instead of onto ``device``."""
         with np.load(path) as z:
             if 'acts' not in z.files:
                 raise ValueError(f'{path}: a feature cache, not an activation cache (no acts)')
+            act_type = str(z['act_type']) if 'act_type' in z.files else 'f32'
             c = ActivationCache(z['feats'].astype(np.float32), z['slide_idx'].astype(np.int64), z['loc'].astype(np.int64),
-                                [str(s) for s in z['slides']], acts=z['acts'].astype(np.float32))
+                                [str(s) for s in z['slides']], acts=_acts_from_numpy(z['acts'], act_type),
+                                act_mul=float(z['act_mul']) if 'act_mul' in z.files else 1.0)
             if 'views' in z.files:
-                c.views, c.act_views = z['views'].astype(np.float32), z['act_views'].astype(np.float32)
+                c.views, c.act_views = z['views'].astype(np.float32), _acts_from_numpy(z['act_views'], act_type)
                 c.augment, c.augment_seed = str(z['augment']), int(z['augment_seed'])
+        if host:
+            c.pin()
         return c.to(device) if device is not None else c
 
 
-def activation_cache_bytes(n_tiles, views=0):
-    """The device bytes of an ``ActivationCache``'s activations: ``n_tiles x 409 600 x (1 + views)``."""
-    return int(n_tiles) * ACT_BYTES * (1 + int(views))
+def act_row_bytes(store='f32', dtype='f16'):
+    """The bytes one tile's activations take under ``store``: 409 600 as float32, 204 800 in a 16-bit engine's own type; ``'host'``
+    keeps the 16-bit form of a 16-bit engine (``dtype``) and float32 of an f32 one.  ValueError for ``'packed'`` on an f32 engine."""
+    if store not in ('f32', 'packed', 'host'):
+        raise ValueError(f'store is one of {ACT_STORES}, not {store!r}')
+    if dtype not in ACT_TORCH:
+        raise ValueError(f'dtype is one of {sorted(ACT_TORCH)}, not {dtype!r}')
+    if store == 'packed' and dtype == 'f32':
+        raise ValueError("store='packed' keeps block13_out as the engine stores it, in 16 bits: an f32 engine stores it in 32, so a "
+                         "16-bit cache would not be lossless (use --act-cache f32 or host, or a 16-bit engine)")
+    return ACT_BYTES if store == 'f32' or dtype == 'f32' else ACT_BYTES // 2
 
 
-def check_activation_memory(n_tiles, views, free_bytes):
-    """ValueError naming both figures when the activations of ``n_tiles`` tiles and ``views`` views do not fit ``free_bytes``."""
-    need = activation_cache_bytes(n_tiles, views)
+def activation_cache_bytes(n_tiles, views=0, store='f32', dtype='f16'):
+    """The bytes of an ``ActivationCache``'s activations: ``n_tiles x act_row_bytes(store, dtype) x (1 + views)`` -- 409 600 per
+    tile and view as float32 -- on the device, or for ``'host'`` in pinned host memory."""
+    return int(n_tiles) * act_row_bytes(store, dtype) * (1 + int(views))
+
+
+def check_activation_memory(n_tiles, views, free_bytes, store='f32', dtype='f16'):
+    """ValueError naming both figures when the activations of ``n_tiles`` tiles and ``views`` views under ``store`` do not fit
+    ``free_bytes`` -- the device's, or for ``'host'`` the host's."""
+    need = activation_cache_bytes(n_tiles, views, store, dtype)
     if need > int(free_bytes):
-        raise ValueError(f'cache_activations: {int(n_tiles)} tiles x {ACT_BYTES} bytes x (1 + {int(views)} views) = {need} bytes of '
-                         f'activations, but the device has {int(free_bytes)} bytes free (a host-resident cache is out of scope: fewer '
-                         'tiles, fewer views, or --trainable head)')
+        where, other = ('the host', 'fewer tiles, fewer views') if store == 'host' else \
+            ('the device', ('--act-cache packed (half the bytes, on a 16-bit engine) or ' if store == 'f32' else '') +
+             '--act-cache host (pinned host memory, gathered per step)')
+        raise ValueError(f'cache_activations: {int(n_tiles)} tiles x {act_row_bytes(store, dtype)} bytes x (1 + {int(views)} views) = {need} '
+                         f'bytes of activations, but {where} has {int(free_bytes)} bytes free ({other}, or --trainable head)')
     return need
 
 
-def cache_activations(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_fit=None, batch=256, augment=None, views=None, seed=0):
+def choose_act_store(store, dtype, n_tiles, views, free_bytes, host_free=None):
+    """The store ``cache_activations`` builds -> ``'f32'``, ``'packed'`` or ``'host'``.  ``'auto'`` takes the first of float32 on the
+    device, packed on the device (a 16-bit engine's only) and host that fits -- ``free_bytes`` of the device, ``host_free`` of the
+    host (None: not looked at) -- and the others are themselves; ValueError from ``act_row_bytes`` / ``check_activation_memory``
+    for ``'packed'`` on an f32 engine and for a store that does not fit."""
+    if store not in ACT_STORES:
+        raise ValueError(f'store is one of {ACT_STORES}, not {store!r}')
+    if store == 'auto':
+        fits = lambda st: activation_cache_bytes(n_tiles, views, st, dtype) <= int(free_bytes)
+        store = 'f32' if fits('f32') else 'packed' if dtype != 'f32' and fits('packed') else 'host'
+    check_activation_memory(n_tiles, views, free_bytes if store != 'host' else (1 << 62 if host_free is None else host_free), store, dtype)
+    return store
+
+
+def host_free_bytes():
+    """The host's available physical memory, None where the system does not say."""
+    try:
+        return int(os.sysconf('SC_AVPHYS_PAGES')) * int(os.sysconf('SC_PAGE_SIZE'))
+    except (ValueError, OSError, AttributeError):
+        return None
+
+
+def cache_activations(engine_or_pool, slides, *, normalizer='reinhard_fast', norm_fit=None, batch=256, augment=None, views=None, seed=0,
+                      store='f32'):
     """``cache_features``' walk with ``Engine.trunk`` in the place of ``backbone_u8`` -> ``ActivationCache``: every tile's
-    ``block13_out`` on the engine's device (and V augmented views of it, drawn as ``cache_features`` draws them), and the features
-    ``Engine.exit_features`` gives them under the engine's imported block 14.  Before anything is read the activations' bytes are
-    compared with the device's free memory (``check_activation_memory``)."""
+    ``block13_out`` (and V augmented views of it, drawn as ``cache_features`` draws them), and the features
+    ``Engine.exit_features`` gives them under the engine's imported block 14.  ``store`` (``ACT_STORES``): ``'f32'`` keeps float32
+    on the engine's device; ``'packed'`` the engine's own 16-bit tensor (``trunk(packed=True)``) there, half the bytes and the same
+    numbers; ``'host'`` that form -- float32 on an f32 engine -- in pinned host memory, each batch copied out asynchronously behind
+    the trunk; ``'auto'`` the first of the three that fits (``choose_act_store``; logged).  Before anything is read the activations'
+    bytes are compared with the free memory of their place (``check_activation_memory``)."""
     import torch
     from . import augment as A
     from .featuremap import walk_features
@@ -439,9 +540,33 @@ def cache_activations(engine_or_pool, slides, *, normalizer='reinhard_fast', nor
     if len(index) != len(order):
         raise ValueError('slide names must be unique')
     n_total = sum(int(s.n_tiles) for s in slides)
-    check_activation_memory(n_total, V, torch.cuda.mem_get_info(eng.device)[0])
-    acts = torch.empty((n_total,) + ACT_SHAPE, dtype=torch.float32, device=eng.device)
-    act_views = torch.empty((V, n_total) + ACT_SHAPE, dtype=torch.float32, device=eng.device) if V else None
+    asked, store = store, choose_act_store(store, eng.dtype, n_total, V, torch.cuda.mem_get_info(eng.device)[0], host_free_bytes())
+    if asked == 'auto':
+        import logging
+        logging.getLogger(__name__).info('cache_activations: --act-cache auto took %r (%d bytes)', store,
+                                         activation_cache_bytes(n_total, V, store, eng.dtype))
+    packed = store != 'f32' and eng.dtype != 'f32'
+    place = dict(pin_memory=True) if store == 'host' else dict(device=eng.device)
+    elt = getattr(torch, ACT_TORCH[eng.dtype]) if packed else torch.float32
+    acts = torch.empty((n_total,) + ACT_SHAPE, dtype=elt, **place)
+    act_views = torch.empty((V, n_total) + ACT_SHAPE, dtype=elt, **place) if V else None
+    muls, at = set(), [0] * (V + 1)
+
+    def trunk(tiles):
+        if not packed:
+            return eng.trunk(tiles)
+        a, mul = eng.trunk(tiles, packed=True)
+        muls.add(mul)
+        return a
+
+    def keep(dst, k, g, a):
+        """Batch ``a`` of the walk into ``dst``: at its indices on the device; into host memory behind the batches before it --
+        the walk hands out every tile in order, so the indices are the next ``len(a)`` -- as one asynchronous copy."""
+        if store == 'host':
+            dst[at[k]:at[k] + len(a)].copy_(a, non_blocking=True)
+            at[k] += len(a)
+        else:
+            dst.index_copy_(0, g, a)
     prepare, statuses = None, []
     if V:
         from . import stain
@@ -450,24 +575,27 @@ def cache_activations(engine_or_pool, slides, *, normalizer='reinhard_fast', nor
         def prepare(tiles, g):
             for v in range(V):
                 aug, status = eng.augment(tiles, tables[v].index_select(0, g).contiguous())
-                act_views[v].index_copy_(0, g, eng.trunk(stain.normalise(eng, aug, normalizer, norm_fit)))
+                keep(act_views[v], v + 1, g, trunk(stain.normalise(eng, aug, normalizer, norm_fit)))
                 statuses.append(status)
             return tiles
-    names, _, loc, _ = walk_features(eng, slides, 0, lambda a, g: acts.index_copy_(0, g, a), norm_fit, normalizer, False, batch,
-                                     prepare=prepare, stage=eng.trunk)
+    names, _, loc, _ = walk_features(eng, slides, 0, lambda a, g: keep(acts, 0, g, a), norm_fit, normalizer, False, batch,
+                                     prepare=prepare, stage=trunk)
+    assert store != 'host' or all(k == n_total for k in at), (at, n_total)
     if statuses and bool(torch.cat(statuses).ne(0).any()):
         from .engine import BiscuitHipError
         raise BiscuitHipError('cache_activations: the augmenter reported a tile outside the JPEG round trip\'s exact range')
+    assert len(muls) <= 1, muls
+    mul = muls.pop() if muls else 1.0
     e = torch.from_numpy(flatten_exit(eng.weights)).to(eng.device)
     stats = torch.from_numpy(exit_bn_stats(eng.weights)).to(eng.device)
     every = torch.arange(n_total, dtype=torch.int64, device=eng.device)
-    feats = eng.exit_features_all(e, stats, acts, every) if n_total else torch.zeros((0, 2048), dtype=torch.float32, device=eng.device)
+    feats = eng.exit_features_all(e, stats, acts, every, act_mul=mul) if n_total else torch.zeros((0, 2048), dtype=torch.float32, device=eng.device)
     stacked = None
     if V:
-        stacked = torch.stack([eng.exit_features_all(e, stats, act_views[v], every) for v in range(V)]).contiguous() if n_total else \
+        stacked = torch.stack([eng.exit_features_all(e, stats, act_views[v], every, act_mul=mul) for v in range(V)]).contiguous() if n_total else \
             torch.zeros((V, 0, 2048), dtype=torch.float32, device=eng.device)
     return ActivationCache(feats.contiguous(), np.array([index[n] for n in names], np.int64), loc, order, stacked, letters,
-                           int(seed) if V else 0, acts=acts, act_views=act_views)
+                           int(seed) if V else 0, acts=acts, act_views=act_views, act_mul=mul)
 
 
 # ------------------------------------------------------------------------------------------------------------ the schedule
@@ -615,7 +743,7 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
 
     With ``params.trainable == 'exit'`` block 14 trains with the head under the same schedule and one Adam: ``cache`` must be an
     ``ActivationCache`` (``cache_activations``), a segment is one ``Engine.exit_train_steps`` call on ``cache.acts`` (``act_views``
-    as [V N, 10, 10, 1024] when there are views), and a check goes through ``Engine.exit_validate`` on the unaugmented activations
+    as [V N, 10, 10, 1024] when there are views) in whichever form and place the cache keeps them (``act_mul`` with them), and a check goes through ``Engine.exit_validate`` on the unaugmented activations
     at rate 0, in calls of at most 256 rows whose sums are added in order on the device, read once.  Block 14 starts from the
     engine's imported tensors, or from a dict ``init`` that also carries them (``EXIT_TENSORS``' names, beside the head's); its
     moving statistics are the engine's and stay.  The result's ``exit`` holds the trained tensors (None for ``'head'``)."""
@@ -672,7 +800,8 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
             lr = [p.learning_rate_at(step + i) for i in range(b - a)]
             if exit_mode:
                 losses.append(engine.exit_train_steps(w, m, v, bn_stats, feats, at[a * B:b * B], y[a * B:b * B], B, step, seed, lr,
-                                                      rate=p.dropout, b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g))
+                                                      rate=p.dropout, b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g,
+                                                      act_mul=cache.act_mul))
             else:
                 losses.append(engine.head_train_steps(w, m, v, feats, at[a * B:b * B], y[a * B:b * B], B, step, seed, lr, rate=p.dropout,
                                                       b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g))
@@ -684,7 +813,7 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
                 stats = torch.zeros(2, dtype=torch.float64, device=dev)
                 for q in range(c0, c0 + n_val, EXIT_MAX_ROWS):
                     e = min(q + EXIT_MAX_ROWS, c0 + n_val)
-                    stats += engine.exit_validate(w, bn_stats, cache.acts, val_at[q:e], val_y[q:e], step, seed)[0]
+                    stats += engine.exit_validate(w, bn_stats, cache.acts, val_at[q:e], val_y[q:e], step, seed, act_mul=cache.act_mul)[0]
             else:
                 stats, _, _ = engine.head_validate(w, cache.feats, val_at[c0:c0 + n_val], val_y[c0:c0 + n_val], step, seed, rate=val_rate)
             stats = stats.cpu().numpy()
@@ -804,7 +933,7 @@ def exit_feature_cache(engine, cache, exit_tensors, rows):
     if len(rows):
         e = torch.from_numpy(flatten_exit(exit_tensors)).to(engine.device)
         stats = torch.from_numpy(exit_bn_stats(engine.weights)).to(engine.device)
-        feats.index_copy_(0, rows, engine.exit_features_all(e, stats, cache.acts, rows))
+        feats.index_copy_(0, rows, engine.exit_features_all(e, stats, cache.acts, rows, act_mul=cache.act_mul))
     return FeatureCache(feats, cache.slide_idx, cache.loc, cache.slides)
 
 
@@ -1056,7 +1185,7 @@ def read_labels(path):
     return labels, patients, values
 
 
-def main(argv=None):
+def arg_parser():
     ap = argparse.ArgumentParser(prog='python -m biscuit_amd.train', description=__doc__.split('\n\n')[0])
     ap.add_argument('tfrecords', nargs='+', help='Slideflow *.tfrecords, one per slide')
     ap.add_argument('--labels', required=True, help='CSV with slide,label[,patient]')
@@ -1087,7 +1216,20 @@ def main(argv=None):
                     'batch-norm statistics frozen; each fold then also writes exit.npz')
     ap.add_argument('--full', action='store_true', help='after the cross-validation, train the model on every slide for the number of '
                     'steps at which the outer folds stopped early (needs --early-stop) -> OUT/LABEL_FULL')
-    args = ap.parse_args(argv)
+    ap.add_argument('--act-cache', default='f32', choices=list(ACT_STORES), metavar='STORE', help="with --trainable exit, where and how "
+                    "block13_out is cached: 'f32' (default) float32 on the device; 'packed' the engine's own 16-bit tensor on the device, "
+                    "half the bytes and bit for bit the same results (--dtype f16 / bf16); 'host' that form in pinned host memory, each "
+                    "step's rows gathered onto the device; 'auto' the first of the three that fits")
+    return ap
+
+
+def main(argv=None):
+    args = arg_parser().parse_args(argv)
+    try:
+        if args.act_cache != 'auto':
+            act_row_bytes(args.act_cache, args.dtype)
+    except ValueError as e:
+        raise SystemExit(f'--act-cache: {e}') from None
     if args.epochs < 1 or args.outer_k < 2 or args.inner_k < 2:
         raise SystemExit('--epochs >= 1, --outer-k >= 2 and --inner-k >= 2')
     if args.validate_on_batch < 1 or args.validation_steps < 1:
@@ -1134,7 +1276,7 @@ def main(argv=None):
     eng = Engine(w, hp=hp, dtype=args.dtype, max_batch=256, max_mc=mc_n, act_exp=act_exp)
     try:
         cache = cached_features(eng, slides, args.cache, normalizer=hp.normalizer, norm_fit=norm_fit, augment=letters, views=n_views or None,
-                                seed=args.seed, activations=args.trainable == 'exit')
+                                seed=args.seed, activations=args.trainable == 'exit', store=args.act_cache)
         try:
             params = TrainParams(epochs=[args.epochs], dropout=hp.dropout, augment=letters, early_stop=bool(args.early_stop),
                                  trainable=args.trainable,

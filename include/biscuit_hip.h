@@ -735,7 +735,46 @@ int bq_head_train_steps(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, fl
  * bq_exit_train_steps: bq_head_train_steps' loop of bq_exit_grad + one Adam over P_ALL; the same bits as the single calls.
  *
  * d_ws: bq_exit_features_workspace_bytes(n) / bq_exit_train_workspace_bytes(n) bytes (0 for an n the calls refuse), under the rules
- * of the head's training workspace.  All are one linear chain of launches on `stream`: nothing is captured, allocated or waited for. */
+ * of the head's training workspace.  All are one linear chain of launches on `stream`: nothing is captured, allocated or waited for.
+ *
+ * The cache in other forms (DESIGN.md section 7 "Exit-flow fine-tuning", Sizes): the three calls with a trailing _c take a descriptor
+ * where the ones above take d_acts, n_act, and are otherwise the same calls -- the ones above are the _c calls with {BQ_ACT_F32, mul 1,
+ * BQ_ACT_DEVICE}.  A 16-bit cache (BQ_ACT_F16 / BQ_ACT_BF16) holds the engine's stored block13_out h, [n_rows][10][10][1024] of 2 bytes,
+ * and its row's x is float(h) * mul, mul a positive finite power of two: the float32 cache's numbers exactly, so every result has the
+ * float32 cache's bits.  A float32 cache has mul 1.  A 16-bit infinity or NaN reads as NaN, like a float32 one.
+ * where == BQ_ACT_HOST: the cache lies in mapped pinned host memory and p is its device pointer (bq_host_device_pointer).  Every
+ * step first copies its rows into a staging region at the end of the workspace with one kernel on `stream` (class exit_gather: whole
+ * rows, a row outside the cache filled with NaN) and reads only that copy; host memory is read once per step and row, by that kernel
+ * alone.  d_ws is then bq_exit_features_staged_workspace_bytes(n, type) / bq_exit_staged_workspace_bytes(n, type) bytes: the sizes
+ * above plus n rows of the cache's type (0 for an n or a type the calls refuse).  Still one linear chain on `stream`.
+ * bq_host_device_pointer: the device pointer of mapped pinned host memory `host` (hipHostMalloc / hipHostRegister, which need not
+ * be its first byte) -> *dev; BQ_ERR_ARG, *dev NULL, for any other memory, asked of the runtime without touching the memory.
+ * bq_trunk_u8_packed: bq_trunk_u8's walk -- the same launches by the same routes -- with block13_out written as the engine stores
+ * it, compact 16-bit [n][10][10][1024] in the engine's own type, neither widened nor scaled, and the power of two bq_trunk_u8
+ * multiplies by -> *mul: float(d_out16) * *mul is bq_trunk_u8's output bit for bit.  BQ_ERR_ARG on a float32 engine. */
+enum { BQ_ACT_F32 = 0, BQ_ACT_BF16 = 1, BQ_ACT_F16 = 2 };   /* the values of BQ_DTYPE_* */
+enum { BQ_ACT_DEVICE = 0, BQ_ACT_HOST = 1 };
+typedef struct bq_act_cache {
+    const void* p;     /* [n_rows][10][10][1024] of `type`, 16-byte aligned; BQ_ACT_HOST: the device pointer of the host memory */
+    int64_t n_rows;
+    int type;          /* BQ_ACT_F32 / BQ_ACT_F16 / BQ_ACT_BF16 */
+    float mul;         /* x = float(stored) * mul; 1 for BQ_ACT_F32 */
+    int where;         /* BQ_ACT_DEVICE / BQ_ACT_HOST */
+} bq_act_cache;
+int bq_trunk_u8_packed(bq_ctx* ctx, const uint8_t* d_tiles_u8, int n, void* d_out16, float* mul, void* d_ws, size_t ws_bytes,
+                       bq_stream_t stream);
+int bq_host_device_pointer(void* host, void** dev);
+size_t bq_exit_features_staged_workspace_bytes(int n, int type);
+size_t bq_exit_staged_workspace_bytes(int n, int type);
+int bq_exit_features_c(bq_ctx* ctx, const float* d_exit_params, const float* d_bn_stats, const bq_act_cache* cache, const int64_t* d_rows,
+                       int n, float* d_feat2048, void* d_ws, size_t ws_bytes, bq_stream_t stream);
+int bq_exit_grad_c(bq_ctx* ctx, const float* d_params, const float* d_bn_stats, const bq_act_cache* cache, const int64_t* d_rows,
+                   const uint8_t* d_labels, int n, int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, void* d_ws,
+                   size_t ws_bytes, bq_stream_t stream);
+int bq_exit_train_steps_c(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, float* d_grad, const float* d_bn_stats,
+                          const bq_act_cache* cache, const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n,
+                          int64_t step0, uint64_t seed, double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses,
+                          void* d_ws, size_t ws_bytes, bq_stream_t stream);
 int bq_trunk_u8(bq_ctx* ctx, const uint8_t* d_tiles_u8, int n, float* d_out_f32, void* d_ws, size_t ws_bytes, bq_stream_t stream);
 size_t bq_exit_features_workspace_bytes(int n);
 size_t bq_exit_train_workspace_bytes(int n);

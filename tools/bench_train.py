@@ -157,13 +157,18 @@ EXIT_GEMMS = ('pw1', 'pw2', 'dp1', 'du1', 'dp2', 'du2', 'dfeat')
 EXIT_DEPTHWISE = ('dw1', 'dw2', 'dd1', 'dd2', 'dh1')
 
 
-def bench_exit_steps(eng, steps, batch, tiles=512):
+def bench_exit_steps(eng, steps, batch, tiles=512, store='f32'):
     """One exit-flow training step (``Engine.exit_train_steps``: block 14 and the head under one Adam) at ``batch``: wall time per
     step, the library's time per launch class, and from each class's own flop and byte counts the GEMMs' share of the f32 matrix
-    peak and the depthwise kernels' share of the HBM bandwidth."""
+    peak and the depthwise kernels' share of the HBM bandwidth.  ``store`` (``--act-cache``): the cache as float32 on the device,
+    as the engine's 16-bit type there (``packed``), or that in pinned host memory (``host``: the gather's time and rate beside it)."""
     dev = eng.device
     rng = np.random.default_rng(1)
     acts = torch.rand((tiles,) + eng.EXIT_ACT_SHAPE, dtype=torch.float32, device=dev)
+    if store != 'f32':
+        acts = acts.to(eng._elt)
+    if store == 'host':
+        acts = torch.empty(acts.shape, dtype=acts.dtype, pin_memory=True).copy_(acts)
     rows = torch.from_numpy(rng.integers(0, tiles, steps * batch)).to(dev)
     labels = torch.from_numpy(rng.integers(0, 2, steps * batch).astype(np.uint8)).to(dev)
     w = torch.from_numpy(np.concatenate([T.flatten_exit(eng.weights), T.flatten_head(T.glorot_head(1))])).to(dev)
@@ -172,7 +177,7 @@ def bench_exit_steps(eng, steps, batch, tiles=512):
     lr = [1e-4] * steps
     eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, 0, 1, lr)
     torch.cuda.synchronize(dev)
-    walls = []
+    walls, extra = [], {}
     for r in range(3):
         t0 = time.perf_counter()
         eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, (r + 1) * steps, 1, lr)
@@ -181,16 +186,39 @@ def bench_exit_steps(eng, steps, batch, tiles=512):
     eng.profile_enable(True)
     eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, 4 * steps, 1, lr)
     torch.cuda.synchronize(dev)
-    prof = {p.name: p for p in eng.profile_read() if p.name.startswith(('exit_train_', 'head_train_'))}
+    prof = {p.name: p for p in eng.profile_read() if p.name.startswith(('exit_train_', 'head_train_', 'exit_gather'))}
     eng.profile_enable(False)
     us = {name: round(p.ms / max(p.launches, 1) * 1e3, 2) for name, p in prof.items()}
     per_s = lambda p: p.ms / max(p.launches, 1) * 1e-3
     peak = {k: round(prof['exit_train_' + k].flops / per_s(prof['exit_train_' + k]) / F32_MATRIX_PEAK, 3) for k in EXIT_GEMMS}
     hbm = {k: round(prof['exit_train_' + k].bytes / per_s(prof['exit_train_' + k]) / HBM_BYTES_PER_S, 3) for k in EXIT_DEPTHWISE}
-    return {'measure': 'exit_train_step', 'batch': batch, 'steps': steps, 'us_per_step_wall_median': round(float(np.median(walls)), 1),
+    if store == 'host':          # the gather's class counts the bytes it reads and writes: half of them cross the link
+        g = prof['exit_gather']
+        extra = {'gather_GB_per_s_over_the_link': round(g.bytes / 2 / per_s(g) / 1e9, 1),
+                 'gather_share_of_step': round(us['exit_gather'] / float(np.median(walls)), 3)}
+    return {'measure': 'exit_train_step', 'act_cache': store, **extra, 'batch': batch, 'steps': steps,
+            'us_per_step_wall_median': round(float(np.median(walls)), 1),
             'us_per_step_wall_runs': [round(x, 1) for x in walls], 'us_per_launch_by_class': us, 'us_launches_total': round(sum(us.values()), 1),
             'gemm_share_of_f32_matrix_peak': peak, 'depthwise_share_of_hbm_bandwidth': hbm,
-            'workspace_MB': round(eng._lib.bq_exit_train_workspace_bytes(batch) / 1e6, 1)}
+            'workspace_MB': round(eng._exit_need(True, batch, acts.dtype if store == 'host' else None) / 1e6, 1)}
+
+
+def bench_trunk(eng, batch=256, repeats=9):
+    """Cache construction's device call at ``batch``: ``Engine.trunk`` against ``Engine.trunk(packed=True)``, which leaves out the
+    widening copy and the scale pass -- the median of ``repeats`` event-timed calls of each, taken in turns."""
+    tiles = torch.randint(0, 256, (batch, 299, 299, 3), dtype=torch.uint8, device=eng.device)
+    ms = {False: [], True: []}
+    for r in range(repeats + 2):
+        for packed in (False, True):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            eng.trunk(tiles, packed=packed)
+            b.record()
+            b.synchronize()
+            if r >= 2:
+                ms[packed].append(a.elapsed_time(b))
+    return {'measure': 'trunk', 'batch': batch, 'trunk_ms_median': round(float(np.median(ms[False])), 3),
+            'trunk_packed_ms_median': round(float(np.median(ms[True])), 3)}
 
 
 def bench_exit_cv(eng, n_slides, n_tiles, mc_n, batch):
@@ -220,6 +248,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('--exit', action='store_true', help="measure exit-flow fine-tuning (trainable='exit') instead: one step at --batch, "
                     'and a toy nested CV (profiles/train_exit.txt)')
+    ap.add_argument('--act-cache', default='f32', choices=['f32', 'packed', 'host'], help='with --exit: the store of the activation cache '
+                    'the step reads (train.ACT_STORES); other than f32 also times trunk against trunk(packed=True) at batch 256 and skips the CV')
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--batch', type=int, default=128)
     ap.add_argument('--cache-slides', type=int, default=8)
@@ -231,8 +261,10 @@ def main(argv=None):
     eng = Engine(synthetic_weights(1), dtype='f16', max_batch=256, max_mc=args.mc)
     try:
         if args.exit:
-            print(json.dumps(bench_exit_steps(eng, min(args.steps, 20), args.batch)), flush=True)
-            if args.cv_slides > 0:
+            print(json.dumps(bench_exit_steps(eng, min(args.steps, 20), args.batch, store=args.act_cache)), flush=True)
+            if args.act_cache != 'f32':
+                print(json.dumps(bench_trunk(eng)), flush=True)
+            elif args.cv_slides > 0:
                 print(json.dumps(bench_exit_cv(eng, min(args.cv_slides, 12), min(args.cv_tiles, 64), args.mc, args.batch)), flush=True)
             return
         print(json.dumps(bench_steps(eng, args.steps, args.batch)), flush=True)
