@@ -134,6 +134,11 @@ ABI = {
     'bq_exit_grad_c': (_i, [_vp, _vp, _vp, C.POINTER(BqActCache), _vp, _vp, _i, _i64, _u64, C.c_double, _vp, _vp, _vp, _sz, _vp]),
     'bq_exit_train_steps_c': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BqActCache), _vp, _vp, _i, _i, _i, _i64, _u64, C.c_double,
                                    C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    'bq_exit_bn_workspace_bytes': (_sz, [_i, _i, _i]),
+    'bq_exit_grad_bn': (_i, [_vp, _vp, C.POINTER(BqActCache), _vp, _vp, _i, _i64, _u64, C.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'bq_exit_bn_move': (_i, [_vp, _vp, _vp, _i, _vp]),
+    'bq_exit_train_steps_bn': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BqActCache), _vp, _vp, _i, _i, _i, _i64, _u64, C.c_double,
+                                    C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -650,7 +650,9 @@ int enqueue_validate(bq_ctx* c, const Batch& b, const Drop& d, double* stats, do
 // x = block13_out [10][10][1024], in fp32 and NHWC:
 //     u1 = dw(x, D1)   z1 = u1 P1 [1024 x 1536]   h1 = relu(a1 z1 + b1)
 //     u2 = dw(h1, D2)  z2 = u2 P2 [1536 x 2048]   h2 = relu(a2 z2 + b2)      f = mean over the 100 positions of h2 -> the head above
-// with a = gamma / sqrt(var + eps), b = beta - a mean and the moving statistics frozen.  Only u and z are stored: every reader of h
+// with a = gamma / sqrt(var + eps), b = beta - a mean and the moving statistics frozen -- or, in training mode (bq_exit_grad_bn: the
+// kernels under "Training-mode batch norm" below, launched by a host-side branch on ExitBatch::bstats), mean and var the batch's own
+// over the 100 n rows of the layer's z, with the gradient through them.  Only u and z are stored: every reader of h
 // forms relu(fmaf(a, z, b)) again (bn_relu, one function).  The four pointwise products and their four transposes are
 // train_gemm_kernel (A_MAT_K / A_MAT_T: dP = u^T dz sums over K = 100 n rows), as is the head's input gradient (EPI_DX0); the
 // depthwise kernel, its two transposes, the pool and the BN backward are vector-ALU kernels over a tile's 100 positions x 256
@@ -871,6 +873,62 @@ __global__ void __launch_bounds__(256) exit_colsum_kernel(const float* __restric
     }
 }
 
+// Training-mode batch norm (bq_exit_grad_bn; DESIGN.md section 7 "Exit-flow fine-tuning", Two modes): the statistics of a layer are
+// the batch's own, over the M = 100 n rows of its stored z.  part[i][c] = (the sum over tile i's positions of z, or with SQ of
+// (z - mu)^2) / M, so that exit_colsum_kernel over the tiles gives mu, then var: two passes, never E[z^2] - mu^2.
+template <bool SQ, int C>
+__global__ void __launch_bounds__(256) exit_stat_kernel(const float* __restrict__ z, const float* __restrict__ mu, float m,
+                                                        float* __restrict__ part) {
+    __shared__ float4 lds[4][64];
+    const int i = blockIdx.y, cq = threadIdx.x & 63, c = (blockIdx.x * 64 + cq) * 4, q = threadIdx.x >> 6;
+    float4 mv = make_float4(0.f, 0.f, 0.f, 0.f), acc = mv;
+    if (SQ) mv = ld4(mu + c);
+    for (int pos = q; pos < X_POS; pos += 4) {
+        const float4 v = ld4(z + ((size_t)i * X_POS + pos) * C + c);
+        if (SQ) {
+            const float4 d = make_float4(v.x - mv.x, v.y - mv.y, v.z - mv.z, v.w - mv.w);
+            acc = fma4(d, d, acc);
+        } else {
+            acc = add4(acc, v);
+        }
+    }
+    lds[q][cq] = acc;
+    __syncthreads();
+    if (q == 0) {
+        const float4 v = sum_q(&lds[0][cq], 64);
+        st4(part + (size_t)i * C + c, make_float4(v.x / m, v.y / m, v.z / m, v.w / m));
+    }
+}
+
+// What the batch statistics add to exit_bn_back_kernel's dz = g a, in place over tile i: with xhat = (z - mu) inv and the layer's
+// finished sums dgb = dgamma [C] | dbeta [C],  dz -= a (dbeta / M + xhat dgamma / M).
+template <int C>
+__global__ void __launch_bounds__(256) exit_bn_fix_kernel(const float* __restrict__ z, const float* __restrict__ a, const float* __restrict__ mean,
+                                                          const float* __restrict__ inv, const float* __restrict__ dgb, float m,
+                                                          float* __restrict__ dz) {
+    const int i = blockIdx.y, c = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, q = threadIdx.x >> 6;
+    const float4 av = ld4(a + c), mv = ld4(mean + c), iv = ld4(inv + c), dg = ld4(dgb + c), db = ld4(dgb + C + c);
+    const float4 na = make_float4(-av.x, -av.y, -av.z, -av.w);
+    const float4 cg = make_float4(dg.x / m, dg.y / m, dg.z / m, dg.w / m), cb = make_float4(db.x / m, db.y / m, db.z / m, db.w / m);
+    for (int pos = q; pos < X_POS; pos += 4) {
+        const size_t o = ((size_t)i * X_POS + pos) * C + c;
+        const float4 zv = ld4(z + o);
+        const float4 xh = make_float4((zv.x - mv.x) * iv.x, (zv.y - mv.y) * iv.y, (zv.z - mv.z) * iv.z, (zv.w - mv.w) * iv.w);
+        st4(dz + o, fma4(na, fma4(xh, cg, cb), ld4(dz + o)));
+    }
+}
+
+// moving <- 0.99 moving + 0.01 batch over mean1 | var1 | mean2 | var2, the variances with the unbiased batch variance: their factor
+// fu = 0.01 M / (M - 1).  Two products and a sum per element, evaluated in float64 from the fp32 values and rounded once, as Adam's
+// update is: a moving mean whose two terms nearly cancel is still the correctly rounded value of the formula.
+constexpr int BN_STATS = 2 * X_C1 + 2 * X_C2;
+__global__ void __launch_bounds__(256) exit_bn_move_kernel(float* __restrict__ moving, const float* __restrict__ batch, double fu) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= BN_STATS) return;
+    const bool var = (j >= S_V1 && j < S_M2) || j >= S_V2;
+    moving[j] = (float)(0.99 * (double)moving[j] + (var ? fu : 0.01) * (double)batch[j]);
+}
+
 // The host tier's gather: stage[i] = cache[rows[i]], whole rows of row16 16-byte pieces, one load and one store each; `cache` is the
 // device pointer of mapped pinned host memory, which this kernel alone reads (once per piece: fine-grained memory is not cached).  A row
 // outside 0 .. n_rows - 1 is never read: its copy is `nan`, the NaN pattern of the cache's type in every element.
@@ -926,6 +984,7 @@ void launch_mat(const float* a, int lda, const float* bm, int ldb, float* out, i
 struct ExitBatch {
     const float* params; const float* stats; const void* acts; long long n_act; const long long* rows; int n;
     int type = BQ_ACT_F32; float mul = 1.f; void* stage = nullptr;
+    float* bstats = nullptr;    // training-mode BN: the batch statistics mu1 | var1 | mu2 | var2, written here; `stats` is then this
 };
 ExitBatch exit_batch(const float* params, const float* stats, const bq_act_cache& a, const long long* rows, int n) {
     ExitBatch b{params, stats, a.p, (long long)a.n_rows, rows, n};
@@ -952,8 +1011,25 @@ void enqueue_cache_reader(const ExitBatch& b, const float* x, float* out, hipStr
     else launch_cache_reader<IN_CACHE_BF16, WGRAD>(src, x, out, b.n, s);
 }
 
+// Training-mode BN of one layer, under the class `cls`: the batch's mu and var over the n tiles of the stored z (per-tile partial sums in
+// w.part -- the backward pass has no use for it yet --, then exit_colsum_kernel; the mean first, the variance around it), written where
+// the caller reads them, and exit_coef_kernel on those: the frozen call's coefficients, had it been given these statistics.
+template <int C>
+void enqueue_bn_stats(bq_ctx* c, const char* cls, const float* z, int n, const float* gamma, const float* beta, float* mu, float* var,
+                      const ExitWs& w, float* a, float* bb, float* inv, hipStream_t s) {
+    const double fm = (double)n * X_POS;
+    ProfScope ps(c, s, cls, 5.0 * fm * C, 8.0 * fm * C);
+    hipLaunchKernelGGL((exit_stat_kernel<false, C>), dim3(C / 256, n), dim3(256), 0, s, z, (const float*)nullptr, (float)(n * X_POS), w.part);
+    hipLaunchKernelGGL(exit_colsum_kernel, dim3(C / 32), dim3(256), 0, s, w.part, n, C, mu);
+    hipLaunchKernelGGL((exit_stat_kernel<true, C>), dim3(C / 256, n), dim3(256), 0, s, z, (const float*)mu, (float)(n * X_POS), w.part);
+    hipLaunchKernelGGL(exit_colsum_kernel, dim3(C / 32), dim3(256), 0, s, w.part, n, C, var);
+    hipLaunchKernelGGL(exit_coef_kernel, dim3(C / 256), dim3(256), 0, s, gamma, beta, (const float*)mu, (const float*)var, C, a, bb, inv);
+}
+
 // The forward half, seven launches under the classes `pre`coef, dw1, pw1, dw2, pw2, pool: acts[rows] -> w.f [n][2048] (u and z stay in w);
 // in front of them for a cache in host memory, under exit_gather, the batch's rows into b.stage, which both readers of the cache then read.
+// With b.bstats (training-mode BN; a training workspace) no coef launch opens the chain: each layer's statistics and coefficients
+// follow its pointwise product (enqueue_bn_stats).
 void enqueue_exit_forward(bq_ctx* c, const ExitBatch& b, const ExitWs& w, const std::string& pre, hipStream_t s) {
     const int n = b.n, M = n * X_POS;
     const double fm = (double)M;
@@ -964,7 +1040,7 @@ void enqueue_exit_forward(bq_ctx* c, const ExitBatch& b, const ExitWs& w, const 
         hipLaunchKernelGGL(exit_gather_kernel, dim3(GATHER_BLOCKS, n), dim3(256), 0, s, (const uint4*)b.acts, b.n_act, b.rows,
                            (int)(act_row_bytes(b.type) / 16), nan, (uint4*)b.stage);
     }
-    {
+    if (!b.bstats) {
         ProfScope ps(c, s, pre + "coef", 8.0 * (X_C1 + X_C2), 28.0 * (X_C1 + X_C2));
         hipLaunchKernelGGL(exit_coef_kernel, dim3(X_C1 / 256), dim3(256), 0, s, e + E_G1, e + E_B1, b.stats + S_M1, b.stats + S_V1, X_C1, w.a1,
                            w.b1, w.i1);
@@ -979,6 +1055,7 @@ void enqueue_exit_forward(bq_ctx* c, const ExitBatch& b, const ExitWs& w, const 
         ProfScope ps(c, s, pre + "pw1", 2.0 * fm * X_C0 * X_C1, 4.0 * (fm * X_C0 + fm * X_C1 + (double)X_C0 * X_C1));
         launch_mat<A_MAT_K, B_ROWS, EPI_STORE>(w.u1, X_C0, e + E_P1, X_C1, w.z1, X_C1, M, X_C1, X_C0, s);
     }
+    if (b.bstats) enqueue_bn_stats<X_C1>(c, "exit_train_stat1", w.z1, n, e + E_G1, e + E_B1, b.bstats + S_M1, b.bstats + S_V1, w, w.a1, w.b1, w.i1, s);
     {
         ProfScope ps(c, s, pre + "dw2", 20.0 * fm * X_C1, 8.0 * fm * X_C1);
         hipLaunchKernelGGL((exit_dw_kernel<IN_BN, X_C1, false>), dim3(X_C1 / 256, n), dim3(256), 0, s, DwSrc{w.z1, nullptr, 0, w.a1, w.b1},
@@ -988,6 +1065,7 @@ void enqueue_exit_forward(bq_ctx* c, const ExitBatch& b, const ExitWs& w, const 
         ProfScope ps(c, s, pre + "pw2", 2.0 * fm * X_C1 * X_C2, 4.0 * (fm * X_C1 + fm * X_C2 + (double)X_C1 * X_C2));
         launch_mat<A_MAT_K, B_ROWS, EPI_STORE>(w.u2, X_C1, e + E_P2, X_C2, w.z2, X_C2, M, X_C2, X_C1, s);
     }
+    if (b.bstats) enqueue_bn_stats<X_C2>(c, "exit_train_stat2", w.z2, n, e + E_G2, e + E_B2, b.bstats + S_M2, b.bstats + S_V2, w, w.a2, w.b2, w.i2, s);
     {
         ProfScope ps(c, s, pre + "pool", 3.0 * fm * X_C2, 4.0 * fm * X_C2);
         hipLaunchKernelGGL(exit_pool_kernel, dim3(X_C2 / 256, n), dim3(256), 0, s, w.z2, w.a2, w.b2, w.f);
@@ -1019,6 +1097,11 @@ int enqueue_exit_grad(bq_ctx* c, const ExitBatch& b, const unsigned char* labels
                            w.i2, w.dz2, w.part);
         hipLaunchKernelGGL(exit_colsum_kernel, dim3(2 * X_C2 / 32), dim3(256), 0, s, w.part, n, 2 * X_C2, grad + E_G2);
     }
+    if (b.bstats) {   // dz2 -= a2 (dbeta2 / M + xhat2 dgamma2 / M): the gradient through the batch's own statistics
+        ProfScope ps(c, s, "exit_train_bnfix2", 6.0 * fm * X_C2, 12.0 * fm * X_C2);
+        hipLaunchKernelGGL((exit_bn_fix_kernel<X_C2>), dim3(X_C2 / 256, n), dim3(256), 0, s, w.z2, w.a2, b.stats + S_M2, w.i2, grad + E_G2,
+                           (float)M, w.dz2);
+    }
     {   // dP2 = u2^T dz2
         ProfScope ps(c, s, "exit_train_dp2", 2.0 * fm * X_C1 * X_C2, 4.0 * (fm * X_C1 + fm * X_C2 + (double)X_C1 * X_C2));
         launch_mat<A_MAT_T, B_ROWS, EPI_STORE>(w.u2, X_C1, w.dz2, X_C2, grad + E_P2, X_C2, X_C1, X_C2, M, s);
@@ -1043,6 +1126,11 @@ int enqueue_exit_grad(bq_ctx* c, const ExitBatch& b, const unsigned char* labels
         hipLaunchKernelGGL((exit_bn_back_kernel<false, X_C1>), dim3(X_C1 / 256, n), dim3(256), 0, s, w.z1, w.dz1, w.a1, w.b1, b.stats + S_M1,
                            w.i1, w.dz1, w.part);
         hipLaunchKernelGGL(exit_colsum_kernel, dim3(2 * X_C1 / 32), dim3(256), 0, s, w.part, n, 2 * X_C1, grad + E_G1);
+    }
+    if (b.bstats) {
+        ProfScope ps(c, s, "exit_train_bnfix1", 6.0 * fm * X_C1, 12.0 * fm * X_C1);
+        hipLaunchKernelGGL((exit_bn_fix_kernel<X_C1>), dim3(X_C1 / 256, n), dim3(256), 0, s, w.z1, w.a1, b.stats + S_M1, w.i1, grad + E_G1,
+                           (float)M, w.dz1);
     }
     {   // dP1 = u1^T dz1
         ProfScope ps(c, s, "exit_train_dp1", 2.0 * fm * X_C0 * X_C1, 4.0 * (fm * X_C0 + fm * X_C1 + (double)X_C0 * X_C1));
@@ -1101,6 +1189,15 @@ size_t exit_ws_bytes(const bq_act_cache& a, int n, bool train) {
 // b.stage of a call whose largest batch is n
 void* exit_stage(const bq_act_cache& a, void* ws, int n, bool train) {
     return a.where == BQ_ACT_HOST ? (unsigned char*)ws + exit_ws(nullptr, n, train).total : nullptr;
+}
+
+// the moving statistics after a step over n tiles, M = 100 n (class exit_train_bnmove)
+int enqueue_bn_move(bq_ctx* c, float* moving, const float* batch, int n, hipStream_t s) {
+    const double m = (double)n * X_POS;
+    ProfScope ps(c, s, "exit_train_bnmove", 3.0 * BN_STATS, 12.0 * BN_STATS);
+    hipLaunchKernelGGL(exit_bn_move_kernel, dim3(BN_STATS / 256), dim3(256), 0, s, moving, batch, 0.01 * m / (m - 1.0));
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
 }
 
 }  // namespace
@@ -1224,6 +1321,68 @@ int bq_exit_train_steps(bq_ctx* c, float* d_params, float* d_m, float* d_v, floa
     const bq_act_cache cache{d_acts, n_act, BQ_ACT_F32, 1.f, BQ_ACT_DEVICE};
     return bq_exit_train_steps_c(c, d_params, d_m, d_v, d_grad, d_bn_stats, &cache, d_rows, d_labels, steps, batch, last_n, step0, seed, rate,
                                  h_lr, b1, b2, eps, d_losses, d_ws, ws_bytes, stream);
+}
+
+// ---- training-mode batch norm: the calls above with the batch's own statistics (enqueue_bn_stats, exit_bn_fix_kernel)
+size_t bq_exit_bn_workspace_bytes(int n, int type, int where) {
+    if (type < 0 || type > 2 || (where != BQ_ACT_DEVICE && where != BQ_ACT_HOST)) return 0;
+    const size_t base = exit_ws_bytes(bq_act_cache{nullptr, 0, type, 1.f, where}, n, true);
+    return base ? base + al(BN_STATS * 4) : 0;      // bq_exit_train_steps_bn keeps a step's batch statistics behind the rest
+}
+
+int bq_exit_grad_bn(bq_ctx* c, const float* d_params, const bq_act_cache* cache, const int64_t* d_rows, const uint8_t* d_labels, int n,
+                    int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, float* d_batch_stats, void* d_ws, size_t ws_bytes,
+                    bq_stream_t stream) {
+    std::string bad = bad_cache("bq_exit_grad_bn", cache);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    ExitBatch b = exit_batch(d_params, d_batch_stats, *cache, (const long long*)d_rows, n);
+    bad = bad_exit_grad(c, "bq_exit_grad_bn", b, d_labels, (long long)step, rate, d_ws, d_grad, d_loss);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < bq_exit_bn_workspace_bytes(n, cache->type, cache->where))
+        return fail(c, BQ_ERR_WORKSPACE, "bq_exit_grad_bn: workspace below bq_exit_bn_workspace_bytes(n, type, where)");
+    DeviceGuard guard(c->device);
+    b.stage = exit_stage(*cache, d_ws, n, true);
+    b.bstats = d_batch_stats;
+    return enqueue_exit_grad(c, b, d_labels, (long long)step, seed, rate, d_ws, d_grad, d_loss, (hipStream_t)stream);
+}
+
+int bq_exit_bn_move(bq_ctx* c, float* d_bn_stats, const float* d_batch_stats, int n, bq_stream_t stream) {
+    if (!c) return fail(c, BQ_ERR_ARG, "bq_exit_bn_move: null context");
+    if (n < 1 || n > EXIT_MAX_N) return fail(c, BQ_ERR_ARG, "bq_exit_bn_move: 1 <= n <= " + std::to_string(EXIT_MAX_N));
+    if (!aligned(d_bn_stats, 16) || !aligned(d_batch_stats, 16)) return fail(c, BQ_ERR_ARG, "bq_exit_bn_move: null or misaligned statistics");
+    DeviceGuard guard(c->device);
+    return enqueue_bn_move(c, d_bn_stats, d_batch_stats, n, (hipStream_t)stream);
+}
+
+int bq_exit_train_steps_bn(bq_ctx* c, float* d_params, float* d_m, float* d_v, float* d_grad, float* d_bn_stats, const bq_act_cache* cache,
+                           const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n, int64_t step0, uint64_t seed,
+                           double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws, size_t ws_bytes,
+                           bq_stream_t stream) {
+    if (!c) return fail(c, BQ_ERR_ARG, "bq_exit_train_steps_bn: null context");
+    if (steps < 1 || steps > (1 << 24) || last_n < 1 || last_n > batch || !h_lr)
+        return fail(c, BQ_ERR_ARG, "bq_exit_train_steps_bn: 1 <= steps <= 2^24, 1 <= last_n <= batch and a learning rate per step");
+    std::string bad = bad_cache("bq_exit_train_steps_bn", cache);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    ExitBatch b = exit_batch(d_params, d_bn_stats, *cache, (const long long*)d_rows, batch);
+    bad = bad_exit_grad(c, "bq_exit_train_steps_bn", b, d_labels, (long long)step0, rate, d_ws, d_grad, d_losses);
+    if (bad.empty() && step0 + steps > 0x100000000LL) bad = "bq_exit_train_steps_bn: the steps pass 2^32";
+    for (int i = 0; bad.empty() && i < steps; ++i) bad = bad_adam_args("bq_exit_train_steps_bn", d_params, d_m, d_v, d_grad, step0 + i, h_lr[i], b1, b2, eps);
+    if (!bad.empty()) return fail(c, BQ_ERR_ARG, bad);
+    if (ws_bytes < bq_exit_bn_workspace_bytes(batch, cache->type, cache->where))
+        return fail(c, BQ_ERR_WORKSPACE, "bq_exit_train_steps_bn: workspace below bq_exit_bn_workspace_bytes(batch, type, where)");
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    b.stage = exit_stage(*cache, d_ws, batch, true);
+    b.bstats = (float*)((unsigned char*)d_ws + exit_ws_bytes(*cache, batch, true));     // behind the largest step's regions and rows
+    b.stats = b.bstats;
+    for (int i = 0; i < steps; ++i) {
+        b.rows = (const long long*)d_rows + (size_t)i * batch;
+        b.n = i + 1 < steps ? batch : last_n;
+        RUN(enqueue_exit_grad(c, b, d_labels + (size_t)i * batch, (long long)step0 + i, seed, rate, d_ws, d_grad, d_losses + i, s));
+        RUN(enqueue_adam(c, d_params, d_m, d_v, d_grad, (long long)step0 + i, h_lr[i], b1, b2, eps, s, P_ALL, "exit_train_adam"));
+        RUN(enqueue_bn_move(c, d_bn_stats, b.bstats, b.n, s));
+    }
+    return BQ_OK;
 }
 
 size_t bq_head_train_workspace_bytes(int n) { return n < 1 || n > MAX_N ? 0 : train_ws(nullptr, n).total; }

@@ -1270,6 +1270,24 @@ class Engine:
         buffer (``staged``: as ``exit_train_scratch``'s; the family ``exit_features_staged``)."""
         return self._bytes(self._exit_need(False, int(n), staged))
 
+    def exit_bn_scratch(self, n, staged=None):
+        """``exit_train_scratch`` for the calls with ``bn='batch'`` [``bq_exit_bn_workspace_bytes``]; the families ``exit_bn`` and
+        ``exit_bn_staged``."""
+        return self._bytes(self._exit_bn_need(int(n), staged))
+
+    def _exit_bn_need(self, n, staged):
+        return int(self._lib.bq_exit_bn_workspace_bytes(n, self.ACT_TYPES[torch.float32 if staged is None else staged],
+                                                        _lib.BQ_ACT_DEVICE if staged is None else _lib.BQ_ACT_HOST))
+
+    def _bn_mode(self, call, bn, acts, cache):
+        """``bn`` is 'frozen' or 'batch' -> whether 'batch', and the descriptor its calls take for every cache (a float32 device
+        tensor's too).  The workspace of a 16-bit device cache is the float32 one's: the size does not depend on the type there."""
+        if bn not in ('frozen', 'batch'):
+            raise ValueError(f"{call}: bn is 'frozen' or 'batch', not {bn!r}")
+        if bn == 'batch' and cache is None:
+            cache = _lib.BqActCache(acts.data_ptr(), int(acts.shape[0]), _lib.BQ_DTYPE_F32, 1.0, _lib.BQ_ACT_DEVICE)
+        return bn == 'batch', cache
+
     ACT_TYPES = {torch.float32: _lib.BQ_DTYPE_F32, torch.bfloat16: _lib.BQ_DTYPE_BF16, torch.float16: _lib.BQ_DTYPE_F16}
 
     def _exit_need(self, train, n, staged):
@@ -1317,7 +1335,8 @@ class Engine:
     def _exit_batch(self, call, bn_stats, acts, rows, labels, count, act_mul=1.0):
         """``bn_stats`` float32 [7168], ``rows`` int64 and (unless None) ``labels`` uint8, ``count`` of each, all on this device, and
         ``acts`` [N, 10, 10, 1024] in a form ``_act_cache`` takes; ValueError otherwise -> ``_act_cache``'s pair."""
-        self._exit_vec(self.EXIT_BN_STATS, ('bn_stats', bn_stats))
+        if bn_stats is not None:                # (None: exit_grad in training mode, which does not read them)
+            self._exit_vec(self.EXIT_BN_STATS, ('bn_stats', bn_stats))
         cache = self._act_cache(call, acts, act_mul)
         if not (torch.is_tensor(rows) and rows.dtype == torch.int64 and rows.is_contiguous() and rows.numel() == count):
             raise ValueError(f'{call}: rows must be contiguous int64 [{count}]')
@@ -1361,19 +1380,35 @@ class Engine:
                                act_mul=act_mul)
         return out
 
-    def exit_grad(self, params, bn_stats, acts, rows, labels, step, seed, rate=None, grad=None, scratch=None, act_mul=1.0):
+    def exit_grad(self, params, bn_stats, acts, rows, labels, step, seed, rate=None, grad=None, scratch=None, act_mul=1.0, bn='frozen'):
         """Gradient of the mean cross-entropy over the rows ``acts[rows]`` through block 14 and the head (``bq_exit_grad``): ``params``
         float32 [P_ALL] -- the exit vector, then the head's --, ``labels`` uint8 [n] in {0, 1}, 1 <= n <= 256; dropout ``rate`` (the
         engine's when None) with pass = ``step`` and the rows as Philox tile counters.  -> ``(grad [P_ALL], loss [1])`` on the device.
-        ``acts``, ``act_mul``: as ``exit_features``'."""
+        ``acts``, ``act_mul``: as ``exit_features``'.
+
+        ``bn='batch'`` (``bq_exit_grad_bn``): training-mode batch norm -- each layer normalised by the batch's own mean and biased
+        variance over its 100 n rows, the gradient through them -- -> ``(grad, loss, batch_stats [7168])``: mu1 | var1 | mu2 | var2 as
+        used.  ``bn_stats`` is then neither read nor written and may be None (``exit_bn_move`` is the moving statistics' update)."""
         n = int(rows.numel()) if torch.is_tensor(rows) else -1
         if not 1 <= n <= self.EXIT_MAX_ROWS:
             raise ValueError(f'exit_grad: 1 <= n <= {self.EXIT_MAX_ROWS} rows, as an int64 tensor')
         self._exit_vec(self.ALL_PARAMS, ('params', params))
+        if bn_stats is None and bn != 'batch':
+            raise ValueError("exit_grad: bn_stats is None with bn='batch' only")
         cache, staged = self._exit_batch('exit_grad', bn_stats, acts, rows, labels, n, act_mul)
+        batch_mode, cache = self._bn_mode('exit_grad', bn, acts, cache)
         if grad is None:
             grad = torch.empty(self.ALL_PARAMS, dtype=torch.float32, device=self.device)
         self._exit_vec(self.ALL_PARAMS, ('grad', grad))
+        if batch_mode:
+            rate, scratch = self._head_open('exit_bn' if staged is None else 'exit_bn_staged', self._exit_bn_need(n, staged), rate, step, 1,
+                                            scratch, 'exit_grad: the rate lies in [0, 1) and the step in 0 .. 2^32 - 1')
+            loss = torch.empty(1, dtype=torch.float32, device=self.device)
+            batch_stats = torch.empty(self.EXIT_BN_STATS, dtype=torch.float32, device=self.device)
+            self._check(self._lib.bq_exit_grad_bn(self._ctx, _ptr(params), C.byref(cache), _ptr(rows), _ptr(labels), n, int(step), int(seed),
+                                                  rate, _ptr(grad), _ptr(loss), _ptr(batch_stats), _ptr(scratch), scratch.numel(),
+                                                  self._stream()))
+            return grad, loss, batch_stats
         rate, scratch = self._head_open('exit_train' if staged is None else 'exit_train_staged', self._exit_need(True, n, staged), rate, step, 1,
                                         scratch, 'exit_grad: the rate lies in [0, 1) and the step in 0 .. 2^32 - 1')
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
@@ -1397,11 +1432,22 @@ class Engine:
         self._check(self._lib.bq_adam_n(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), count, int(step), float(lr), float(b1),
                                         float(b2), float(eps), self._stream()))
 
+    def exit_bn_move(self, bn_stats, batch_stats, n):
+        """The moving statistics ``bn_stats`` [7168] in place after a training-mode step over ``n`` tiles whose batch statistics were
+        ``batch_stats`` (``bq_exit_bn_move``): 0.99 moving + 0.01 batch, the variances with the batch's unbiased one, M = 100 n."""
+        self._exit_vec(self.EXIT_BN_STATS, ('bn_stats', bn_stats), ('batch_stats', batch_stats))
+        if not 1 <= int(n) <= self.EXIT_MAX_ROWS:
+            raise ValueError(f'exit_bn_move: 1 <= n <= {self.EXIT_MAX_ROWS}')
+        self._check(self._lib.bq_exit_bn_move(self._ctx, _ptr(bn_stats), _ptr(batch_stats), int(n), self._stream()))
+
     def exit_train_steps(self, params, m, v, bn_stats, acts, rows, labels, batch, step0, seed, lr, rate=None, b1=0.9, b2=0.999, eps=1e-7,
-                         grad=None, scratch=None, act_mul=1.0):
+                         grad=None, scratch=None, act_mul=1.0, bn='frozen'):
         """``S`` = ceil(len(rows) / batch) steps of ``exit_grad`` + ``adam_n`` over [P_ALL] back to back (``bq_exit_train_steps``), as
         ``head_train_steps``: ``params``, ``m``, ``v`` change in place; -> losses float32 [S].  The same bits as the single calls.
-        ``acts``, ``act_mul``: as ``exit_features``'; a cache in host memory is gathered once per step."""
+        ``acts``, ``act_mul``: as ``exit_features``'; a cache in host memory is gathered once per step.
+
+        ``bn='batch'`` (``bq_exit_train_steps_bn``): steps of ``exit_grad(..., bn='batch')`` + ``adam_n`` + ``exit_bn_move``;
+        ``bn_stats`` changes in place as well."""
         count = int(rows.numel()) if torch.is_tensor(rows) else 0
         batch = int(batch)
         if not 1 <= batch <= self.EXIT_MAX_ROWS or count < 1:
@@ -1410,17 +1456,22 @@ class Engine:
         last_n = count - (steps - 1) * batch
         self._exit_vec(self.ALL_PARAMS, ('params', params), ('m', m), ('v', v))
         cache, staged = self._exit_batch('exit_train_steps', bn_stats, acts, rows, labels, count, act_mul)
+        batch_mode, cache = self._bn_mode('exit_train_steps', bn, acts, cache)
         if grad is None:
             grad = torch.empty(self.ALL_PARAMS, dtype=torch.float32, device=self.device)
         self._exit_vec(self.ALL_PARAMS, ('grad', grad))
         lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
-        rate, scratch = self._head_open('exit_train' if staged is None else 'exit_train_staged', self._exit_need(True, batch, staged), rate, step0,
+        family, need = ('exit_bn', self._exit_bn_need(batch, staged)) if batch_mode else ('exit_train', self._exit_need(True, batch, staged))
+        rate, scratch = self._head_open(family if staged is None else family + '_staged', need, rate, step0,
                                         steps, scratch, f'exit_train_steps: {steps} learning rates, a rate in [0, 1) and steps below 2^32',
                                         len(lr) == steps)
         losses = torch.empty(steps, dtype=torch.float32, device=self.device)
         tail = (steps, batch, last_n, int(step0), int(seed), rate, lr.ctypes.data_as(C.POINTER(C.c_double)), float(b1), float(b2), float(eps),
                 _ptr(losses), _ptr(scratch), scratch.numel(), self._stream())
-        if cache is None:
+        if batch_mode:
+            self._check(self._lib.bq_exit_train_steps_bn(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), _ptr(bn_stats), C.byref(cache),
+                                                         _ptr(rows), _ptr(labels), *tail))
+        elif cache is None:
             self._check(self._lib.bq_exit_train_steps(self._ctx, _ptr(params), _ptr(m), _ptr(v), _ptr(grad), _ptr(bn_stats), _ptr(acts),
                                                       int(acts.shape[0]), _ptr(rows), _ptr(labels), *tail))
         else:

@@ -27,11 +27,12 @@ rule and its defaults, and how balanced batches are drawn.
 Exit-flow fine-tuning (``--trainable exit``; DESIGN.md section 7 "Exit-flow fine-tuning"): ``cache_activations`` keeps every tile's
 ``block13_out`` [10, 10, 1024] (``Engine.trunk``; ``--act-cache``: float32 or the engine's own 16-bit form on the device, or pinned
 host memory) and each training moves Xception's block 14 together with the head
-(``Engine.exit_train_steps``), batch-norm statistics frozen -- a stated deviation from Slideflow, unpinned.  A fold then also writes
-``exit.npz``; ``exit_engine`` packs the result into an engine.
+(``Engine.exit_train_steps``).  Its batch norm runs in one of two modes (``--bn``): ``frozen`` (the default) keeps the imported
+moving statistics -- a stated deviation from Slideflow --, ``batch`` is Keras' training mode, as the reference trains: a batch is
+normalised by its own statistics, the gradient flows through them and the moving statistics follow the cohort (unpinned).  A fold
+then also writes ``exit.npz``; ``exit_engine`` packs the result into an engine.
 
-Out of scope: training blocks 1-13, training-mode BN, Slideflow's stain augmentation ``n``, TensorFlow checkpoints, multi-GPU
-training.
+Out of scope: training blocks 1-13, Slideflow's stain augmentation ``n``, TensorFlow checkpoints, multi-GPU training.
 """
 import argparse
 import json
@@ -63,6 +64,7 @@ EXIT_MAX_ROWS = 256
 ACT_SHAPE = (10, 10, 1024)                   # block13_out of one tile
 ACT_BYTES = 4 * int(np.prod(ACT_SHAPE))      # 409 600
 TRAINABLE = ('head', 'exit')
+BN_MODES = ('frozen', 'batch')
 EXIT_FILE = 'exit.npz'
 
 # Keras's Adam defaults and Slideflow's schedule form -- restated from memory, unpinned
@@ -108,11 +110,21 @@ class TrainParams:
     # 'head': the three dense layers on cached features; 'exit': block 14 with them, on cached block13_out (an ActivationCache), under
     # one Adam and one learning rate, batch-norm statistics frozen (DESIGN.md section 7 "Exit-flow fine-tuning"; unpinned)
     trainable: str = 'head'
+    # block 14's batch norm under trainable='exit' (DESIGN.md section 7 "Exit-flow fine-tuning", Two modes): 'frozen' keeps the imported
+    # moving statistics; 'batch' is Keras' training mode -- batch statistics, gradients through them, moving statistics updated
+    bn: str = 'frozen'
 
     @classmethod
     def nature2022(cls, **fields):
         """The reference's schedule: early stopping by accuracy, batches balanced by category (Slideflow's default)."""
         return cls(**{'early_stop': True, 'early_stop_method': 'accuracy', 'training_balance': 'category', **fields})
+
+    def _check_bn(self):
+        if self.bn not in BN_MODES or (self.bn == 'batch' and self.trainable != 'exit'):
+            raise ValueError(f"bn is one of {BN_MODES}, and 'batch' goes with trainable='exit' only (the head has no batch norm)")
+
+    def __post_init__(self):
+        self._check_bn()                     # at construction already; validate() asks again, the fields being mutable
 
     def validate(self):
         from . import augment as A
@@ -137,6 +149,7 @@ class TrainParams:
             raise ValueError(f'trainable is one of {TRAINABLE}, not {self.trainable!r}')
         if self.trainable == 'exit' and (int(self.batch_size) > EXIT_MAX_ROWS or self.validation_dropout):
             raise ValueError(f"trainable='exit': batch_size <= {EXIT_MAX_ROWS}, and validation in inference mode only")
+        self._check_bn()
         return self
 
     def learning_rate_at(self, step):
@@ -195,7 +208,7 @@ def unflatten_exit(vec):
 
 
 def exit_bn_stats(w):
-    """Block 14's frozen moving statistics of a weight dict -> float32 [7168]: mean1, variance1, mean2, variance2."""
+    """Block 14's moving statistics of a weight dict -> float32 [7168]: mean1, variance1, mean2, variance2."""
     parts = []
     for name, shape in EXIT_STATS:
         a = np.asarray(w[name], np.float32)
@@ -205,13 +218,39 @@ def exit_bn_stats(w):
     return np.concatenate(parts)
 
 
+def unflatten_exit_stats(vec):
+    """A vector [7168] -> ``{name: float32 array}`` of block 14's four moving-statistics tensors (copies)."""
+    vec = np.asarray(vec, np.float32).reshape(-1)
+    if vec.size != sum(s[0] for _, s in EXIT_STATS):
+        raise ValueError(f'block 14 has {sum(s[0] for _, s in EXIT_STATS)} moving statistics, not {vec.size}')
+    out, at = {}, 0
+    for name, shape in EXIT_STATS:
+        out[name] = vec[at:at + shape[0]].copy()
+        at += shape[0]
+    return out
+
+
+def has_exit_stats(tensors):
+    """Whether ``tensors`` is a trained block 14 that carries its own moving statistics (``bn='batch'``): all four of them -- or
+    none: ValueError for some -- and nothing but block 14's twelve tensors.  A whole model's weight dict is not such a result: its
+    block 14 is saved and read as before there were two modes, eight tensors under the engine's statistics."""
+    have = [name in tensors for name, _ in EXIT_STATS]
+    if any(have) and not all(have):
+        raise ValueError('a block 14 carries all four moving statistics or none')
+    return all(have) and set(tensors) <= {name for name, _ in EXIT_TENSORS + EXIT_STATS}
+
+
 def save_exit(path, tensors):
-    np.savez(path, **{name: np.asarray(tensors[name], np.float32) for name, _ in EXIT_TENSORS})
+    """``exit.npz``: block 14's eight trained tensors, and its four moving statistics where ``tensors`` has them (``bn='batch'``)."""
+    names = EXIT_TENSORS + (EXIT_STATS if has_exit_stats(tensors) else ())
+    np.savez(path, **{name: np.asarray(tensors[name], np.float32) for name, _ in names})
 
 
 def load_exit(path):
+    """``save_exit``'s file -> its tensors: eight, or twelve where the file holds the moving statistics."""
     with np.load(path) as z:
-        return {name: z[name] for name, _ in EXIT_TENSORS}
+        names = EXIT_TENSORS + (EXIT_STATS if has_exit_stats(z.files) else ())
+        return {name: z[name] for name, _ in names}
 
 
 def glorot_head(seed):
@@ -701,7 +740,7 @@ class FitResult:
     early_stop_batch: Optional[int]
     steps: int
     epochs: int = 1
-    exit: Optional[dict] = None              # trainable='exit': block 14's eight trained tensors
+    exit: Optional[dict] = None              # trainable='exit': block 14's eight trained tensors; bn='batch': and its four moving statistics
 
 
 # ------------------------------------------------------------------------------------------------------------ training
@@ -746,7 +785,12 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
     as [V N, 10, 10, 1024] when there are views) in whichever form and place the cache keeps them (``act_mul`` with them), and a check goes through ``Engine.exit_validate`` on the unaugmented activations
     at rate 0, in calls of at most 256 rows whose sums are added in order on the device, read once.  Block 14 starts from the
     engine's imported tensors, or from a dict ``init`` that also carries them (``EXIT_TENSORS``' names, beside the head's); its
-    moving statistics are the engine's and stay.  The result's ``exit`` holds the trained tensors (None for ``'head'``)."""
+    moving statistics are the engine's and stay.  The result's ``exit`` holds the trained tensors (None for ``'head'``).
+
+    With ``params.bn == 'batch'`` a training step normalises block 14 by its batch's own statistics (``exit_train_steps(...,
+    bn='batch')``) and the moving statistics are state beside the parameters: they start from ``init``'s where it names them, else
+    from the engine's, follow every step, and every check scores with the current ones.  A check, like every prediction, stays in
+    inference mode.  The result's ``exit`` then also holds the four statistics tensors (``EXIT_STATS``' names)."""
     import torch
     from .engine import BiscuitHipError
     p = (params or TrainParams()).validate()
@@ -782,7 +826,8 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
         if not isinstance(cache, ActivationCache) or cache.acts is None:
             raise ValueError("trainable='exit' trains on an ActivationCache (cache_activations), not on a FeatureCache")
         exit_start = init if isinstance(init, dict) and EXIT_TENSORS[0][0] in init else engine.weights
-        bn_stats = torch.from_numpy(exit_bn_stats(engine.weights)).to(dev)
+        stats_start = exit_start if p.bn == 'batch' and all(name in exit_start for name, _ in EXIT_STATS) else engine.weights
+        bn_stats = torch.from_numpy(exit_bn_stats(stats_start)).to(dev)      # bn='batch': state, updated in place by every step
         w = torch.from_numpy(np.concatenate([flatten_exit(exit_start), flatten_head(start)])).to(dev)
         feats = cache.act_views.reshape((-1,) + ACT_SHAPE) if cache.n_views() else cache.acts
     else:
@@ -801,7 +846,7 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
             if exit_mode:
                 losses.append(engine.exit_train_steps(w, m, v, bn_stats, feats, at[a * B:b * B], y[a * B:b * B], B, step, seed, lr,
                                                       rate=p.dropout, b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g,
-                                                      act_mul=cache.act_mul))
+                                                      act_mul=cache.act_mul, bn=p.bn))
             else:
                 losses.append(engine.head_train_steps(w, m, v, feats, at[a * B:b * B], y[a * B:b * B], B, step, seed, lr, rate=p.dropout,
                                                       b1=ADAM_BETA_1, b2=ADAM_BETA_2, eps=ADAM_EPSILON, grad=g))
@@ -834,7 +879,10 @@ def fit_head(engine, cache, rows, labels, *, val_rows=None, val_labels=None, sli
                               '(a feature that is not finite, or a diverged run)')
     if exit_mode:
         host = w.cpu().numpy()
-        return FitResult(unflatten_head(host[EXIT_PARAMS:]), losses, checks, stopped, step, int(max(p.epochs)), unflatten_exit(host[:EXIT_PARAMS]))
+        trained = unflatten_exit(host[:EXIT_PARAMS])
+        if p.bn == 'batch':
+            trained.update(unflatten_exit_stats(bn_stats.cpu().numpy()))
+        return FitResult(unflatten_head(host[EXIT_PARAMS:]), losses, checks, stopped, step, int(max(p.epochs)), trained)
     return FitResult(unflatten_head(w.cpu().numpy()), losses, checks, stopped, step, int(max(p.epochs)))
 
 
@@ -925,25 +973,28 @@ class HeadTrainer:
 
 def exit_feature_cache(engine, cache, exit_tensors, rows):
     """A ``FeatureCache`` over ``cache``'s tiles whose features at ``rows`` are ``Engine.exit_features`` of the cached activations
-    under ``exit_tensors`` (a trained block 14; its statistics the engine's): what ``predict`` reads after ``trainable='exit'``.
+    under ``exit_tensors`` (a trained block 14; its moving statistics its own where it carries them -- ``bn='batch'`` --, else the
+    engine's): what ``predict`` reads after ``trainable='exit'``.
     The other rows keep the imported block 14's features."""
     import torch
     rows = torch.from_numpy(np.asarray(rows, np.int64).reshape(-1)).to(engine.device)
     feats = cache.feats.clone()
     if len(rows):
         e = torch.from_numpy(flatten_exit(exit_tensors)).to(engine.device)
-        stats = torch.from_numpy(exit_bn_stats(engine.weights)).to(engine.device)
+        stats = torch.from_numpy(exit_bn_stats(exit_tensors if has_exit_stats(exit_tensors) else engine.weights)).to(engine.device)
         feats.index_copy_(0, rows, engine.exit_features_all(e, stats, cache.acts, rows, act_mul=cache.act_mul))
     return FeatureCache(feats, cache.slide_idx, cache.loc, cache.slides)
 
 
 def exit_engine(engine, exit_tensors, head, tiles=None, headroom_min=1.0):
     """A fresh engine of ``engine``'s configuration whose block 14 is ``exit_tensors`` and whose head is ``head`` (through
-    ``weights.pack_blob``, like ``head_engine``), with ``engine``'s activation exponents reused.  The exponents were calibrated on the
+    ``weights.pack_blob``, like ``head_engine``; the moving statistics ``exit_tensors`` carries, if any, fold in with them), with
+    ``engine``'s activation exponents reused.  The exponents were calibrated on the
     imported block 14: with ``tiles`` (uint8 [n, 299, 299, 3] on the device) one ``f16_headroom`` check runs on them, and
     ``F16RangeError`` says so when the trained block 14 saturates f16 or leaves less than ``headroom_min`` x of its range."""
     from .engine import Engine, F16RangeError
-    w = {**engine.weights, **{name: np.asarray(exit_tensors[name], np.float32) for name, _ in EXIT_TENSORS},
+    names = EXIT_TENSORS + (EXIT_STATS if has_exit_stats(exit_tensors) else ())
+    w = {**engine.weights, **{name: np.asarray(exit_tensors[name], np.float32) for name, _ in names},
          **{name: np.asarray(head[name], np.float32) for name, _ in HEAD_TENSORS}}
     eng = Engine(w, hp=engine.hp, dtype=engine.dtype, max_batch=engine.max_batch, max_mc=engine.max_mc, device=engine.device.index,
                  act_exp=engine.act_exp)
@@ -1214,6 +1265,9 @@ def arg_parser():
     ap.add_argument('--trainable', default='head', choices=list(TRAINABLE), help="'head' (default): the three dense layers on cached "
                     "features; 'exit': Xception's block 14 with them, on cached block13_out (409 600 bytes per tile and view on the device), "
                     'batch-norm statistics frozen; each fold then also writes exit.npz')
+    ap.add_argument('--bn', default='frozen', choices=list(BN_MODES), help="with --trainable exit, block 14's batch norm: 'frozen' (default) "
+                    "keeps the imported moving statistics; 'batch' is Keras' training mode, as the reference trains -- a batch normalised "
+                    'by its own statistics, gradients through them, moving statistics updated and written into exit.npz')
     ap.add_argument('--full', action='store_true', help='after the cross-validation, train the model on every slide for the number of '
                     'steps at which the outer folds stopped early (needs --early-stop) -> OUT/LABEL_FULL')
     ap.add_argument('--act-cache', default='f32', choices=list(ACT_STORES), metavar='STORE', help="with --trainable exit, where and how "
@@ -1234,6 +1288,8 @@ def main(argv=None):
         raise SystemExit('--epochs >= 1, --outer-k >= 2 and --inner-k >= 2')
     if args.validate_on_batch < 1 or args.validation_steps < 1:
         raise SystemExit('--validate-on-batch >= 1 and --validation-steps >= 1')
+    if args.bn == 'batch' and args.trainable != 'exit':
+        raise SystemExit('--bn batch trains block 14: it needs --trainable exit')
     if args.full and not args.early_stop:
         raise SystemExit('--full trains for the steps at which the folds stopped early: it needs --early-stop')
     from . import augment as A
@@ -1279,7 +1335,7 @@ def main(argv=None):
                                 seed=args.seed, activations=args.trainable == 'exit', store=args.act_cache)
         try:
             params = TrainParams(epochs=[args.epochs], dropout=hp.dropout, augment=letters, early_stop=bool(args.early_stop),
-                                 trainable=args.trainable,
+                                 trainable=args.trainable, bn=args.bn,
                                  early_stop_method=args.early_stop or 'accuracy', training_balance=args.balance,
                                  validate_on_batch=args.validate_on_batch, validation_steps=args.validation_steps).validate()
             trainer = HeadTrainer(eng, cache, labels, params=params, init=args.init, mc_n=mc_n, outcome=args.outcome, patients=patients)
@@ -1314,6 +1370,8 @@ def main(argv=None):
         schedule['balance'] = args.balance
     if args.full:
         schedule['full'] = full
+    if args.bn != 'frozen':
+        schedule['bn'] = args.bn
     with open(os.path.join(args.out, 'thresholds.json'), 'w') as f:
         json.dump({'thresholds': th, 'label_values': values, 'outer_k': args.outer_k, 'inner_k': args.inner_k, 'seed': args.seed,
                    'augment': letters, 'views': n_views, **schedule}, f, indent=1)

@@ -790,6 +790,42 @@ int bq_exit_train_steps(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, fl
                         uint64_t seed, double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses, void* d_ws,
                         size_t ws_bytes, bq_stream_t stream);
 
+/* Training-mode batch norm (DESIGN.md section 7 "Exit-flow fine-tuning", Two modes; unpinned: Keras' fused BatchNormalization,
+ * momentum 0.99, epsilon 1e-3, restated).  The calls above keep the moving statistics frozen; these normalise a batch by its own.
+ * For one layer, z [M][C] with M = 100 n -- every position of every tile of the batch --, in fp32:
+ *     mu = (1/M) sum z        var = (1/M) sum (z - mu)^2        (biased; two passes, never E[z^2] - mu^2)
+ *     a = gamma / sqrt(var + eps)    b = beta - a mu    h = relu(a z + b)
+ *     g = dh [h > 0]    xhat = (z - mu) / sqrt(var + eps)    dbeta = sum g    dgamma = sum g xhat
+ *     dz = a (g - dbeta / M - xhat dgamma / M)
+ *     moving_mean <- 0.99 moving_mean + 0.01 mu       moving_var <- 0.99 moving_var + 0.01 var M / (M - 1)
+ * Layer 1's statistics are taken over z1, layer 2's over z2, which already depends on layer 1's.  Only the training step depends on
+ * the batch: bq_exit_features, validation and the packed engine use the moving statistics.
+ *
+ * bq_exit_grad_bn: bq_exit_grad_c without d_bn_stats -- training mode does not read the moving statistics -- and with d_batch_stats
+ * float32 [7168], 16-byte aligned, written: mu1 [1536] | var1 [1536] | mu2 [2048] | var2 [2048], the biased statistics the step
+ * used.  The forward chain is bq_exit_grad_c's with each layer's statistics (per-tile partial sums, then the tiles in a fixed order;
+ * classes exit_train_stat1 / stat2) and coefficients behind its pointwise product: bq_exit_grad_c given d_batch_stats as d_bn_stats
+ * reproduces the loss, the head's gradient and dgamma2 | dbeta2 bit for bit.  Backwards, one in-place pass per layer (classes
+ * exit_train_bnfix2 / bnfix1) subtracts a (dbeta / M + xhat dgamma / M) from dz before the transposed products.  The same refusals; a
+ * NaN activation, a row outside the cache or a label above 1 gives a NaN loss, and a channel's NaN statistic spreads to every tile of
+ * the batch -- training-mode BN's nature.  Every sum has a fixed order and there are no floating-point atomics: the same bits every
+ * call.  One linear chain on `stream`: nothing is captured, allocated or waited for.
+ * bq_exit_bn_move: the moving statistics d_bn_stats [7168] in place after a step over n tiles whose statistics were d_batch_stats,
+ * M = 100 n: two products and a sum per element, evaluated in float64 and rounded once (class exit_train_bnmove).
+ * bq_exit_train_steps_bn: bq_exit_train_steps_c's loop of bq_exit_grad_bn + one Adam over P_ALL + bq_exit_bn_move on d_bn_stats, which
+ * changes in place; the last, shorter batch uses its own M.  The same bits as the single calls.
+ * d_ws: bq_exit_bn_workspace_bytes(n, type, where) bytes for either call, type and where the cache's: the training workspace of that
+ * cache plus a step's statistics; 0 for an n, a type or a place the calls refuse. */
+size_t bq_exit_bn_workspace_bytes(int n, int type, int where);
+int bq_exit_grad_bn(bq_ctx* ctx, const float* d_params, const bq_act_cache* cache, const int64_t* d_rows, const uint8_t* d_labels, int n,
+                    int64_t step, uint64_t seed, double rate, float* d_grad, float* d_loss, float* d_batch_stats, void* d_ws,
+                    size_t ws_bytes, bq_stream_t stream);
+int bq_exit_bn_move(bq_ctx* ctx, float* d_bn_stats, const float* d_batch_stats, int n, bq_stream_t stream);
+int bq_exit_train_steps_bn(bq_ctx* ctx, float* d_params, float* d_m, float* d_v, float* d_grad, float* d_bn_stats,
+                           const bq_act_cache* cache, const int64_t* d_rows, const uint8_t* d_labels, int steps, int batch, int last_n,
+                           int64_t step0, uint64_t seed, double rate, const double* h_lr, double b1, double b2, double eps, float* d_losses,
+                           void* d_ws, size_t ws_bytes, bq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

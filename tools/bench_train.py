@@ -155,13 +155,16 @@ def bench_cv(eng, n_slides, n_tiles, mc_n):
 F32_MATRIX_PEAK, HBM_BYTES_PER_S = 157.3e12, 8.0e12
 EXIT_GEMMS = ('pw1', 'pw2', 'dp1', 'du1', 'dp2', 'du2', 'dfeat')
 EXIT_DEPTHWISE = ('dw1', 'dw2', 'dd1', 'dd2', 'dh1')
+EXIT_BN = ('stat1', 'stat2', 'bnfix1', 'bnfix2', 'bnmove')            # what --bn batch adds to a step
 
 
-def bench_exit_steps(eng, steps, batch, tiles=512, store='f32'):
+def bench_exit_steps(eng, steps, batch, tiles=512, store='f32', bn='frozen'):
     """One exit-flow training step (``Engine.exit_train_steps``: block 14 and the head under one Adam) at ``batch``: wall time per
     step, the library's time per launch class, and from each class's own flop and byte counts the GEMMs' share of the f32 matrix
     peak and the depthwise kernels' share of the HBM bandwidth.  ``store`` (``--act-cache``): the cache as float32 on the device,
-    as the engine's 16-bit type there (``packed``), or that in pinned host memory (``host``: the gather's time and rate beside it)."""
+    as the engine's 16-bit type there (``packed``), or that in pinned host memory (``host``: the gather's time and rate beside it).
+    ``bn`` (``--bn``): 'batch' measures the training-mode step -- the statistics, the two in-place passes over dz and the moving
+    update beside the frozen step's launches -- and reports their classes' share of the HBM bandwidth as well."""
     dev = eng.device
     rng = np.random.default_rng(1)
     acts = torch.rand((tiles,) + eng.EXIT_ACT_SHAPE, dtype=torch.float32, device=dev)
@@ -175,16 +178,16 @@ def bench_exit_steps(eng, steps, batch, tiles=512, store='f32'):
     stats = torch.from_numpy(T.exit_bn_stats(eng.weights)).to(dev)
     m, v = torch.zeros_like(w), torch.zeros_like(w)
     lr = [1e-4] * steps
-    eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, 0, 1, lr)
+    eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, 0, 1, lr, bn=bn)
     torch.cuda.synchronize(dev)
     walls, extra = [], {}
     for r in range(3):
         t0 = time.perf_counter()
-        eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, (r + 1) * steps, 1, lr)
+        eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, (r + 1) * steps, 1, lr, bn=bn)
         torch.cuda.synchronize(dev)
         walls.append((time.perf_counter() - t0) / steps * 1e6)
     eng.profile_enable(True)
-    eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, 4 * steps, 1, lr)
+    eng.exit_train_steps(w, m, v, stats, acts, rows, labels, batch, 4 * steps, 1, lr, bn=bn)
     torch.cuda.synchronize(dev)
     prof = {p.name: p for p in eng.profile_read() if p.name.startswith(('exit_train_', 'head_train_', 'exit_gather'))}
     eng.profile_enable(False)
@@ -192,15 +195,20 @@ def bench_exit_steps(eng, steps, batch, tiles=512, store='f32'):
     per_s = lambda p: p.ms / max(p.launches, 1) * 1e-3
     peak = {k: round(prof['exit_train_' + k].flops / per_s(prof['exit_train_' + k]) / F32_MATRIX_PEAK, 3) for k in EXIT_GEMMS}
     hbm = {k: round(prof['exit_train_' + k].bytes / per_s(prof['exit_train_' + k]) / HBM_BYTES_PER_S, 3) for k in EXIT_DEPTHWISE}
+    if bn == 'batch':
+        extra = {'bn_us_per_step': round(sum(us['exit_train_' + k] for k in EXIT_BN), 1),
+                 'bn_share_of_hbm_bandwidth': {k: round(prof['exit_train_' + k].bytes / per_s(prof['exit_train_' + k]) / HBM_BYTES_PER_S, 3)
+                                               for k in EXIT_BN[:4]}}
     if store == 'host':          # the gather's class counts the bytes it reads and writes: half of them cross the link
         g = prof['exit_gather']
-        extra = {'gather_GB_per_s_over_the_link': round(g.bytes / 2 / per_s(g) / 1e9, 1),
-                 'gather_share_of_step': round(us['exit_gather'] / float(np.median(walls)), 3)}
-    return {'measure': 'exit_train_step', 'act_cache': store, **extra, 'batch': batch, 'steps': steps,
+        extra.update({'gather_GB_per_s_over_the_link': round(g.bytes / 2 / per_s(g) / 1e9, 1),
+                      'gather_share_of_step': round(us['exit_gather'] / float(np.median(walls)), 3)})
+    return {'measure': 'exit_train_step', 'act_cache': store, 'bn': bn, **extra, 'batch': batch, 'steps': steps,
             'us_per_step_wall_median': round(float(np.median(walls)), 1),
             'us_per_step_wall_runs': [round(x, 1) for x in walls], 'us_per_launch_by_class': us, 'us_launches_total': round(sum(us.values()), 1),
             'gemm_share_of_f32_matrix_peak': peak, 'depthwise_share_of_hbm_bandwidth': hbm,
-            'workspace_MB': round(eng._exit_need(True, batch, acts.dtype if store == 'host' else None) / 1e6, 1)}
+            'workspace_MB': round((eng._exit_bn_need(batch, acts.dtype if store == 'host' else None) if bn == 'batch' else
+                                   eng._exit_need(True, batch, acts.dtype if store == 'host' else None)) / 1e6, 1)}
 
 
 def bench_trunk(eng, batch=256, repeats=9):
@@ -250,6 +258,8 @@ def main(argv=None):
                     'and a toy nested CV (profiles/train_exit.txt)')
     ap.add_argument('--act-cache', default='f32', choices=['f32', 'packed', 'host'], help='with --exit: the store of the activation cache '
                     'the step reads (train.ACT_STORES); other than f32 also times trunk against trunk(packed=True) at batch 256 and skips the CV')
+    ap.add_argument('--bn', default='frozen', choices=list(T.BN_MODES), help="with --exit: block 14's batch norm in the measured step "
+                    "(train.BN_MODES); 'batch' skips the CV")
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--batch', type=int, default=128)
     ap.add_argument('--cache-slides', type=int, default=8)
@@ -261,7 +271,9 @@ def main(argv=None):
     eng = Engine(synthetic_weights(1), dtype='f16', max_batch=256, max_mc=args.mc)
     try:
         if args.exit:
-            print(json.dumps(bench_exit_steps(eng, min(args.steps, 20), args.batch, store=args.act_cache)), flush=True)
+            print(json.dumps(bench_exit_steps(eng, min(args.steps, 20), args.batch, store=args.act_cache, bn=args.bn)), flush=True)
+            if args.bn != 'frozen':
+                return
             if args.act_cache != 'f32':
                 print(json.dumps(bench_trunk(eng)), flush=True)
             elif args.cv_slides > 0:
